@@ -15,12 +15,18 @@ once after the timed region and timed on its own (`gather_ms`).
 Timed region: K steps through `abd_logp_dlogp_many` -- enqueued stream-ordered (the library rotates them over four HIP
 streams so that launches share the chip instead of draining it one after the other), one wait, results fetched
 (host-side prior terms included) -- opened by barrier + device sync, closed by a device sync; MAX over ranks.  Inputs
-are resident in HBM before it starts.  The K-step region is repeated R times (until >= 0.25 s of timed work,
-R <= 400): `value` and `ms_per_step` are the MEDIAN region, `region_ms` holds min / median / max.  Warm-up:
-W untimed steps as asked, repeated until at least 60 ms have passed -- after an idle period the part needs
-~3 ms of load to reach its sustained state, which 20 steps (0.5 ms) do not cover.
+are resident in HBM before it starts.  Warm-up: W untimed steps as asked, repeated until at least 60 ms have passed --
+after an idle period the part needs ~3 ms of load to reach its sustained state, which 20 steps (0.5 ms) do not cover.
 
-Also in the same JSON line:
+A plain run times exactly ONE K-step region: `value` and `ms_per_step` come from it, and the line's other measurements
+are null.  With --full the K-step region is repeated R more times (until >= 0.25 s of timed work, R <= 400): `value` and
+`ms_per_step` are the MEDIAN region, `region_ms` holds min / median / max, and everything below is measured as well.
+
+--dump-outputs DIR writes what the last timed step returned to its caller: DIR/logp.npy (chains,) and DIR/dlogp.npy
+(chains, 17), float64 (for N > 1 ranks: the gathered block's last step, (ranks, chains) and (ranks, chains, 17)).  The
+cohort, the chain states and the thetas are seeded, so the same arguments give the same inputs in every run.
+
+Also in the same JSON line (--full only):
   roofline     the TIMED launch shape: device time per launch from HIP events around every window of K
                stream-ordered launches (first launch .. all streams joined; abd_kernel_timing mode 2), against
                8 TB/s HBM with the algorithmic bytes of one launch.  `roofline.isolated` is ONE launch alone on
@@ -207,13 +213,20 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default: the config's)")
     ap.add_argument("--splits", default="", help="comma separated gap indexes, e.g. 100 or 66,133")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sampler", action="store_true", help="skip the sweep / compound-step / NUTS section (A/B runs of the kernels: tools/ab_bench.sh)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the bounded passes over BASELINE configs 5, 1 and 2 (`other_configs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the one timed K-step region: repeated regions (median), roofline, synchronous rate, CPU baselines "
+                         "with the parity spot check, sampler legs and the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logp / dlogp as DIR/logp.npy and DIR/dlogp.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-sampler", action="store_true", help="with --full: skip the sweep / compound-step / NUTS section (A/B runs of the kernels: tools/ab_bench.sh)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the bounded passes over BASELINE configs 5, 1 and 2 (`other_configs`)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--min-seconds", type=float, default=0.25, help="repeat the K-step region until this much timed work")
+    ap.add_argument("--min-seconds", type=float, default=0.25, help="with --full: repeat the K-step region until this much timed work")
     ap.add_argument("--max-repeats", type=int, default=400)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     cfg = dict(CONFIGS[args.config])
     if args.chains:
@@ -341,10 +354,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return t.cpu().numpy()
 
-    first = float(all_max([region()])[0])
-    n_rep = int(min(args.max_repeats, max(3, np.ceil(args.min_seconds / max(first, 1e-9)))))
-    w_per_launch, w_n = [], 0
-    own_times = np.array([region() for _ in range(n_rep)])
+    own_first = region()
+    first = float(all_max([own_first])[0])
+    if args.full:
+        n_rep = int(min(args.max_repeats, max(3, np.ceil(args.min_seconds / max(first, 1e-9)))))
+        w_per_launch, w_n = [], 0
+        own_times = np.array([region() for _ in range(n_rep)])
+    else:
+        n_rep, own_times = 1, np.array([own_first])  # a plain run: exactly K timed steps
     times = all_max(own_times)
     times_fastest_rank = all_min(own_times)  # a straggler shows as a gap between the two
     elapsed = float(np.median(times))
@@ -361,82 +378,91 @@ def main():
         gather_ms = float(all_max([time.perf_counter() - t_g])[0]) * 1e3
         assert gathered.shape == (world, K, C, 18)
 
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, written before anything else runs on the context
+        out_lp, out_g = (lp_all[-1], g_all[-1]) if dist is None else (gathered[:, -1, :, 0], gathered[:, -1, :, 1:])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logp.npy"), np.ascontiguousarray(out_lp, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "dlogp.npy"), np.ascontiguousarray(out_g, dtype=np.float64))
+
     total_evals = K * C * world
     value = total_evals / elapsed
 
-    # ---- synchronous caller rate (each step waits for its result): what lock-step NUTS over these chains sees ----
-    ks = min(K, 200)
-    sync_rates = []
-    for _ in range(3):
-        ctx.wait()
-        t1 = time.perf_counter()
-        for k in range(W, W + ks):
-            ctx.logp_dlogp_batch(chains, thetas[k])
-        sync_rates.append(ks * C / (time.perf_counter() - t1))
-    sync_rate = float(np.median(sync_rates))
+    sync_rate, roofline = None, None
+    if args.full:
+        # ---- synchronous caller rate (each step waits for its result): what lock-step NUTS over these chains sees ----
+        ks = min(K, 200)
+        sync_rates = []
+        for _ in range(3):
+            ctx.wait()
+            t1 = time.perf_counter()
+            for k in range(W, W + ks):
+                ctx.logp_dlogp_batch(chains, thetas[k])
+            sync_rates.append(ks * C / (time.perf_counter() - t1))
+        sync_rate = float(np.median(sync_rates))
 
-    # ---- the isolated kernel: HIP events around every launch, one stream, full grid ----
-    warm(0.02)
-    ctx.kernel_timing(1)
-    ctx.kernel_time(reset=True)
-    k_per_launch, k_n = [], 0
-    for _ in range(int(min(n_rep, 10))):
-        run_steps(W, W + K)
-        ms_r, n_r = ctx.kernel_time(reset=True)
-        k_per_launch.append(ms_r / max(n_r, 1))
-        k_n += n_r
-    ctx.kernel_timing(0)
-    # medians over the repetitions, like the timed regions (a stray slow window would otherwise carry the mean)
-    w_avg_s = float(np.median(w_per_launch)) * 1e-3
-    k_avg_s = float(np.median(k_per_launch)) * 1e-3
+        # ---- the isolated kernel: HIP events around every launch, one stream, full grid ----
+        warm(0.02)
+        ctx.kernel_timing(1)
+        ctx.kernel_time(reset=True)
+        k_per_launch, k_n = [], 0
+        for _ in range(int(min(n_rep, 10))):
+            run_steps(W, W + K)
+            ms_r, n_r = ctx.kernel_time(reset=True)
+            k_per_launch.append(ms_r / max(n_r, 1))
+            k_n += n_r
+        ctx.kernel_timing(0)
+        # medians over the repetitions, like the timed regions (a stray slow window would otherwise carry the mean)
+        w_avg_s = float(np.median(w_per_launch)) * 1e-3
+        k_avg_s = float(np.median(k_per_launch)) * 1e-3
 
-    alg_bytes = ctx.algorithmic_bytes(C)  # compulsory bytes of this library's layout (bit-packed indicators)
-    R = 4 if cfg["storage"] == "f32" else 8
-    survey_bytes = G * N * (4 * R + 2 + C) + C * N  # byte-per-cell indicator panels
-    achieved = alg_bytes / w_avg_s / 1e9
-    iso_achieved = alg_bytes / k_avg_s / 1e9
-    prof, prof_stale = {}, None
-    tp = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tp) and (not splits or default_cohort) and C == CONFIGS[args.config]["chains"]:
-        try:
-            whole = json.load(open(tp))
-            prof = whole.get(args.config, {})
-            # the counters were collected on a build of these sources: anything else and they describe another kernel
-            prof_stale = whole.get("kernel_sources_sha256") != kernel_sources_sha256()
-        except Exception:
-            prof = {}
-    pipe_prof = prof.get("pipe_grid", prof)
-    valu = None
-    if pipe_prof.get("valu_insts_per_launch"):
-        insts = float(pipe_prof["valu_insts_per_launch"])
-        tf = insts * 64 * 2 / w_avg_s / 1e12  # every vector instruction priced as one fp64 FMA on 64 lanes
-        valu = dict(bound="fp64-valu", stale=bool(prof_stale), insts_per_launch=int(insts), achieved_tflops_equiv=round(tf, 2), peak=FP64_VECTOR_TFLOPS,
-                    unit="TFLOP/s", frac=round(tf / FP64_VECTOR_TFLOPS, 4),
-                    insts_per_cell_chain=round(insts * 64 / (G * N * C), 2), source=pipe_prof.get("valu_source"),
-                    note="vector wave-instructions per launch (rocprofv3 SQ_INSTS_VALU, profiles/) x 64 lanes x 2 flop / device "
-                         "time per launch of the timed shape; 32-bit integer/select instructions issue at twice the fp64 rate, "
-                         "so 1.0 is not reachable and the lever is the instruction count")
-    roofline = dict(
-        bound="hbm", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
-        traffic=pipe_prof.get("hbm_bytes_per_launch"), traffic_stale=bool(prof_stale) if pipe_prof.get("hbm_bytes_per_launch") else None,
-        kernel="abd_dense_kernel" if ctx.is_dense else "abd_obs_kernel",
-        kernel_us=round(w_avg_s * 1e6, 3), launches=int(w_n),
-        launch_shape=f"stream-ordered, as timed: launches rotate over {ctx.n_pipes} HIP streams on different hardware queues, "
-                     "1 workgroup per CU each; device time from HIP events around the K launches of every timed region / K (median)",
-        algorithmic_bytes_per_launch=int(alg_bytes), survey_bytes_per_launch=int(survey_bytes), evals_per_launch=C,
-        isolated=dict(kernel_us=round(k_avg_s * 1e6, 3), achieved=round(iso_achieved, 2), frac=round(iso_achieved / HBM_PEAK_GBS, 4),
-                      launches=int(k_n), traffic=prof.get("hbm_bytes_per_launch"),
-                      launch_shape="one launch alone on the chip: one stream, full grid (4 workgroups per CU); what a "
-                                   "synchronous call runs"),
-        valu=valu,
-        note=("achieved = algorithmic_bytes_per_launch / kernel_us (the smaller, bit-packed byte count). The working set "
-              "(66 MB at config 3) sits in the 256 MiB Infinity Cache and the kernel is fp64-VALU bound: see roofline.valu")
-        if ctx.is_dense else "observation lists: ~0.9 MB per launch, bound by the two launches of an evaluation, not by bytes",
-    )
+        alg_bytes = ctx.algorithmic_bytes(C)  # compulsory bytes of this library's layout (bit-packed indicators)
+        R = 4 if cfg["storage"] == "f32" else 8
+        survey_bytes = G * N * (4 * R + 2 + C) + C * N  # byte-per-cell indicator panels
+        achieved = alg_bytes / w_avg_s / 1e9
+        iso_achieved = alg_bytes / k_avg_s / 1e9
+        prof, prof_stale = {}, None
+        tp = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tp) and (not splits or default_cohort) and C == CONFIGS[args.config]["chains"]:
+            try:
+                whole = json.load(open(tp))
+                prof = whole.get(args.config, {})
+                # the counters were collected on a build of these sources: anything else and they describe another kernel
+                prof_stale = whole.get("kernel_sources_sha256") != kernel_sources_sha256()
+            except Exception:
+                prof = {}
+        pipe_prof = prof.get("pipe_grid", prof)
+        valu = None
+        if pipe_prof.get("valu_insts_per_launch"):
+            insts = float(pipe_prof["valu_insts_per_launch"])
+            tf = insts * 64 * 2 / w_avg_s / 1e12  # every vector instruction priced as one fp64 FMA on 64 lanes
+            valu = dict(bound="fp64-valu", stale=bool(prof_stale), insts_per_launch=int(insts), achieved_tflops_equiv=round(tf, 2), peak=FP64_VECTOR_TFLOPS,
+                        unit="TFLOP/s", frac=round(tf / FP64_VECTOR_TFLOPS, 4),
+                        insts_per_cell_chain=round(insts * 64 / (G * N * C), 2), source=pipe_prof.get("valu_source"),
+                        note="vector wave-instructions per launch (rocprofv3 SQ_INSTS_VALU, profiles/) x 64 lanes x 2 flop / device "
+                             "time per launch of the timed shape; 32-bit integer/select instructions issue at twice the fp64 rate, "
+                             "so 1.0 is not reachable and the lever is the instruction count")
+        roofline = dict(
+            bound="hbm", achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 4),
+            traffic=pipe_prof.get("hbm_bytes_per_launch"), traffic_stale=bool(prof_stale) if pipe_prof.get("hbm_bytes_per_launch") else None,
+            kernel="abd_dense_kernel" if ctx.is_dense else "abd_obs_kernel",
+            kernel_us=round(w_avg_s * 1e6, 3), launches=int(w_n),
+            launch_shape=f"stream-ordered, as timed: launches rotate over {ctx.n_pipes} HIP streams on different hardware queues, "
+                         "1 workgroup per CU each; device time from HIP events around the K launches of every timed region / K (median)",
+            algorithmic_bytes_per_launch=int(alg_bytes), survey_bytes_per_launch=int(survey_bytes), evals_per_launch=C,
+            isolated=dict(kernel_us=round(k_avg_s * 1e6, 3), achieved=round(iso_achieved, 2), frac=round(iso_achieved / HBM_PEAK_GBS, 4),
+                          launches=int(k_n), traffic=prof.get("hbm_bytes_per_launch"),
+                          launch_shape="one launch alone on the chip: one stream, full grid (4 workgroups per CU); what a "
+                                       "synchronous call runs"),
+            valu=valu,
+            note=("achieved = algorithmic_bytes_per_launch / kernel_us (the smaller, bit-packed byte count). The working set "
+                  "(66 MB at config 3) sits in the 256 MiB Infinity Cache and the kernel is fp64-VALU bound: see roofline.valu")
+            if ctx.is_dense else "observation lists: ~0.9 MB per launch, bound by the two launches of an evaluation, not by bytes",
+        )
 
     # ---- CPU baselines on the host cores (rank 0, N=1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import abd_oracle as O
         from oracle import c_oracle
 
@@ -487,7 +513,7 @@ def main():
 
     # ---- the rate a sampling run gets, and the compound step around it (rank 0, N=1 only) ----
     compound, nuts, nuts_own, nuts_bal = None, None, None, None
-    if rank == 0 and world == 1 and not args.no_sampler:
+    if args.full and rank == 0 and world == 1 and not args.no_sampler:
         def sweep_ms(theta_rows, n=5):
             ts = []
             for k in range(n):
@@ -554,7 +580,7 @@ def main():
 
     wait_fallbacks, device_name = int(ctx.wait_fallbacks), ctx.device_name
     other = None
-    if rank == 0 and world == 1 and args.config == "c3" and not args.no_other_configs and not args.no_sampler:
+    if args.full and rank == 0 and world == 1 and args.config == "c3" and not args.no_other_configs and not args.no_sampler:
         ctx.close()
         ctx = None
         other = {key: other_config(key, device) for key in ("c5", "c1", "c2")}
@@ -584,7 +610,7 @@ def main():
                           "median_fastest_rank": round(float(np.median(times_fastest_rank)) * 1e3, 4)},
             "roofline": roofline,
             "cpu_baseline": cpu,
-            "sync_evals_per_s": round(sync_rate, 1),
+            "sync_evals_per_s": None if sync_rate is None else round(sync_rate, 1),
             "nuts_evals_per_s": None if nuts is None else nuts["value"],
             "nuts": nuts,
             "nuts_own_states": nuts_own,
@@ -598,6 +624,7 @@ def main():
             "dist": None if dist is None else {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                                 "device_of_rank0": device},
             "device": device_name,
+            "full": bool(args.full),
         }
         print(json.dumps(line), flush=True)
     if dist is not None:

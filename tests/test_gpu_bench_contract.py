@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _run(args, env=None, timeout=900):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = _run(["--steps", "20", "--warmup", "5", "--cpu-seconds", "4"])  # the steps / warm-up the driver runs it with
+    d = _run(["--full", "--steps", "20", "--warmup", "5", "--cpu-seconds", "4"])  # the steps / warm-up the driver runs it with
     assert d["metric"] == "logp+grad evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "weak"
     assert d["dtype"] == "f64" and d["data"] == "synthetic" and d["vs_baseline"] is None
@@ -111,8 +112,38 @@ def test_bench_rehearses_the_drivers_multi_gpu_shape():
 
 def test_bench_config_1_is_the_references_default_cohort():
     """BASELINE config 1: the reference's default cohort (observation lists), 4 chains per call."""
-    d = _run(["--config", "c1", "--steps", "50", "--warmup", "10", "--cpu-seconds", "3"])
+    d = _run(["--full", "--config", "c1", "--steps", "50", "--warmup", "10", "--cpu-seconds", "3"])
     assert d["config"]["n_inds"] == 1520 and d["config"]["n_gaps"] == 31 and d["config"]["splits"] == [14, 20]
     assert d["roofline"]["kernel"] == "abd_obs_kernel" and 0.5e6 < d["roofline"]["algorithmic_bytes_per_launch"] < 2e6
     assert d["value"] > 1e4 and d["sync_evals_per_s"] > 1e4 and d["nuts_evals_per_s"] > 1e4
     assert d["cpu_baseline"]["value"] > 0 and d["wait_fallbacks"] == 0
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run times ONE region of exactly --steps steps and measures nothing else; --dump-outputs writes what the
+    last timed step returned, which the C oracle reproduces from the same seeded inputs."""
+    from abdpymc_amd import synthetic
+    from oracle import abd_oracle as O
+    from oracle import c_oracle
+
+    K, W = 20, 5
+    d = _run(["--config", "c2", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path)])
+    assert d["metric"] == "logp+grad evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == K and d["warmup"] == W and d["repeats"] == 1 and d["full"] is False
+    assert d["value"] > 0 and abs(d["value"] - K * 4 / (d["ms_per_step"] * K / 1e3)) < 1e-3 * d["value"]
+    assert abs(d["region_ms"]["median"] - d["ms_per_step"] * K) < 1e-3 * d["region_ms"]["median"]
+    for key in ("roofline", "cpu_baseline", "sync_evals_per_s", "nuts", "compound_step", "other_configs"):
+        assert d[key] is None, key
+    lp, g = np.load(tmp_path / "logp.npy"), np.load(tmp_path / "dlogp.npy")
+    assert lp.dtype == np.float64 and g.dtype == np.float64 and lp.shape == (4,) and g.shape == (4, 17)
+    sc = synthetic.make_cohort(1000, 60)
+    coh = O.Cohort(sc.n_gaps, sc.n_inds, sc.vacs, sc.pcrpos, O.AntigenObs(sc.idx_gap, sc.idx_ind, sc.x_s, sc.y_s),
+                   O.AntigenObs(sc.idx_gap, sc.idx_ind, sc.x_n, sc.y_n))
+    co = c_oracle.COracle(coh, None)
+    for c in range(4):
+        i_raw, w = synthetic.make_chain_state(1000, 60, c)
+        theta = synthetic.make_thetas(60, K + W, c)[K + W - 1]
+        lp_ref, g_ref = co.logp_dlogp(theta, i_raw, w)
+        assert abs(lp[c] - lp_ref) <= 1e-6 * abs(lp_ref), (c, lp[c], lp_ref)
+        scale = np.maximum(np.abs(g_ref), 1e-6 * np.abs(g_ref).max())
+        assert (np.abs(g[c] - g_ref) / scale).max() <= 1e-6, c

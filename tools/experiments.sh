@@ -26,7 +26,7 @@ launch_shapes)
   for s in "1x4 4 1 1" "1x4xc 4 1 4" "2x2 2 2 1" "2x2xc 2 2 4" "4x1xc 1 4 1" "4x4(headline) 4 4 1" "4x4xc 4 4 4"; do
     set -- $s
     echo -n "$1: chains/launch $2, streams $3, split panels for <= $4 chains: "
-    ABD_PIPES=$3 ABD_XC_MAX_CB=$4 python3 bench.py --no-cpu-baseline --no-sampler --no-other-configs --steps 200 --chains $2 | line
+    ABD_PIPES=$3 ABD_XC_MAX_CB=$4 python3 bench.py --full --no-cpu-baseline --no-sampler --no-other-configs --steps 200 --chains $2 | line
   done ;;
 train_units)
   export ABD_HIP_LIB=$T
@@ -43,7 +43,7 @@ handoff)
   for lib in $P $PWD/build/libabd_hip_formal1.so $PWD/build/libabd_hip_formal2.so; do
     echo -n "$(basename $lib) c3: "; ABD_HIP_LIB=$lib nuts c3 4 200
     echo -n "$(basename $lib) default cohort: "; ABD_HIP_LIB=$lib nuts default 4 300
-    echo -n "$(basename $lib) bench: "; ABD_HIP_LIB=$lib python3 bench.py --no-cpu-baseline --no-sampler --no-other-configs --steps 200 | line
+    echo -n "$(basename $lib) bench: "; ABD_HIP_LIB=$lib python3 bench.py --full --no-cpu-baseline --no-sampler --no-other-configs --steps 200 | line
   done ;;
 sync_own_sum)
   export ABD_HIP_LIB=$T

@@ -16,19 +16,19 @@ for cfg in $CFGS; do
     c5) SW="--n-inds 100000 --n-gaps 200 --chains 1 --storage f32 --cpw 1 --blocks 0,256" ;;
     c1) SW="" ;;
   esac
-  echo "== $cfg: bench line" ; python3 bench.py --config $cfg --no-other-configs > "$OUT/${cfg}_bench.json" 2> "$OUT/${cfg}_bench.err" || { echo bench failed; tail -5 "$OUT/${cfg}_bench.err"; exit 1; }
+  echo "== $cfg: bench line" ; python3 bench.py --full --config $cfg --no-other-configs > "$OUT/${cfg}_bench.json" 2> "$OUT/${cfg}_bench.err" || { echo bench failed; tail -5 "$OUT/${cfg}_bench.err"; exit 1; }
   echo "== $cfg: kernel trace of the same command"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${cfg}_trace" -- python3 bench.py --config $cfg --no-cpu-baseline --no-other-configs > "$OUT/${cfg}_bench_under_rocprof.json" 2> "$OUT/${cfg}_trace.err" || { echo trace failed; tail -5 "$OUT/${cfg}_trace.err"; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${cfg}_trace" -- python3 bench.py --full --config $cfg --no-cpu-baseline --no-other-configs > "$OUT/${cfg}_bench_under_rocprof.json" 2> "$OUT/${cfg}_trace.err" || { echo trace failed; tail -5 "$OUT/${cfg}_trace.err"; exit 1; }
   find "$OUT/${cfg}_trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/${cfg}_kernel_stats.csv" \;
   if [ $cfg = c3 ]; then
-    echo "== the driver's command: python3 bench.py --gpus 1 --steps 20 --warmup 5 (every single-GPU BASELINE config in one line)"
-    ( time python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/driver_bench.json" ) 2> "$OUT/driver_bench.err" || { echo driver bench failed; tail -5 "$OUT/driver_bench.err"; exit 1; }
-    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/driver_trace" -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/driver_bench_under_rocprof.json" 2> "$OUT/driver_trace.err" || { echo driver trace failed; exit 1; }
+    echo "== python3 bench.py --gpus 1 --steps 20 --warmup 5 --full (every single-GPU BASELINE config in one line)"
+    ( time python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/driver_bench.json" ) 2> "$OUT/driver_bench.err" || { echo driver bench failed; tail -5 "$OUT/driver_bench.err"; exit 1; }
+    rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/driver_trace" -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/driver_bench_under_rocprof.json" 2> "$OUT/driver_trace.err" || { echo driver trace failed; exit 1; }
     find "$OUT/driver_trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/driver_kernel_stats.csv" \;
     rm -rf "$OUT/driver_trace"
   fi
   echo "== $cfg: isolated kernel (ABD_PIPES=1)"
-  ABD_PIPES=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${cfg}_trace1" -- python3 bench.py --config $cfg --no-cpu-baseline --no-sampler > "$OUT/${cfg}_bench_one_pipe_under_rocprof.json" 2> "$OUT/${cfg}_trace1.err" || { echo trace1 failed; exit 1; }
+  ABD_PIPES=1 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${cfg}_trace1" -- python3 bench.py --full --config $cfg --no-cpu-baseline --no-sampler > "$OUT/${cfg}_bench_one_pipe_under_rocprof.json" 2> "$OUT/${cfg}_trace1.err" || { echo trace1 failed; exit 1; }
   find "$OUT/${cfg}_trace1" -name "*kernel_stats.csv" -exec cp {} "$OUT/${cfg}_one_pipe_kernel_stats.csv" \;
   [ -z "$SW" ] && { rm -rf "$OUT/${cfg}_trace" "$OUT/${cfg}_trace1"; continue; }  # observation lists: launch-bound, no counter passes
   echo "== $cfg: PMC passes over tools/sweep.py $SW"
