@@ -76,6 +76,8 @@ class _Record(C.Structure):
         ("i", C.POINTER(C.c_int8)),
         ("ab_n_mu", C.POINTER(C.c_double)),
         ("ab_s_mu", C.POINTER(C.c_double)),
+        ("ll_s", C.POINTER(C.c_double)),
+        ("ll_n", C.POINTER(C.c_double)),
     ]
 
 
@@ -113,12 +115,15 @@ SYMBOLS = {
     "abd_fetch_many": (C.c_int, [_P, C.c_int32, _I32, _D, _D]),
     "abd_logp_dlogp_many": (C.c_int, [_P, C.c_int32, C.c_int32, _I32, _D, _D, _D]),
     "abd_deterministics": (C.c_int, [_P, C.c_int32, _D, _I8, _D, _D]),
+    "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_sampler_create": (C.c_int, [_P, C.c_int32, _I32, _D, C.POINTER(_SamplerOpts), C.POINTER(_P)]),
     "abd_sampler_destroy": (None, [_P]),
     "abd_sampler_run": (C.c_int, [_P, C.c_int64, _D, _D]),
     "abd_sampler_run_record": (C.c_int, [_P, C.c_int64, _D, _D, C.POINTER(_Record)]),
     "abd_sampler_set_adaptation": (C.c_int, [_P, C.c_int32, _D, C.c_double]),
     "abd_sampler_means": (C.c_int, [_P, C.c_int32, _D, _D, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_pointwise": (C.c_int, [_P, C.c_int32]),
+    "abd_sampler_pointwise_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
@@ -245,6 +250,7 @@ class Context:
             return a
 
         d.s, d.n = obs(s_obs), obs(n_obs)
+        self.n_obs_s, self.n_obs_n = int(d.s.n_obs), int(d.n.n_obs)  # readings of it_s_lik / it_n_lik
         vacs = np.asarray(vacs)
         if vacs.shape != (self.n_inds, self.n_gaps):
             raise ValueError(f"vacs shape {vacs.shape} != (n_inds, n_gaps) = {(self.n_inds, self.n_gaps)}")
@@ -460,6 +466,17 @@ class Context:
         )
         return i, mun, mus
 
+    def pointwise_loglik(self, chain: int, theta):
+        """Log-density of every OD reading at (theta, the chain slot's discrete state) -> (ll_s, ll_n), each in the order the
+        readings were given (what ``pm.compute_log_likelihood`` records per draw for ``it_s_lik`` / ``it_n_lik``)."""
+        t = _as(theta, np.float64)
+        if t.shape != (N_THETA,):
+            raise ValueError(f"theta must have shape ({N_THETA},)")
+        ll_s, ll_n = np.empty(self.n_obs_s), np.empty(self.n_obs_n)
+        _check(self._lib, self._lib.abd_pointwise_loglik(self._h, int(chain), _ptr(t, C.c_double), _ptr(ll_s, C.c_double),
+                                                         _ptr(ll_n, C.c_double)))
+        return ll_s, ll_n
+
     def theta_prior(self, theta):
         """The theta-only part of the joint logp (continuous priors + Jacobians) and its gradient."""
         t = _as(theta, np.float64)
@@ -475,11 +492,12 @@ class Context:
 
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
-                dense_metric: bool = False) -> "NativeSampler":
+                dense_metric: bool = False, pointwise: bool = False) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
-        independent units on their own HIP streams (abd_hip.h: abd_sampler_create)."""
+        independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
+        pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric)
+                             dense_metric, pointwise)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -558,7 +576,7 @@ class NativeSampler:
     per leapfrog of a unit of 1-4 chains, leapfrog trains (abd_hip.h)."""
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
-                 chain_offset=0, dense_metric=False):
+                 chain_offset=0, dense_metric=False, pointwise=False):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -577,6 +595,8 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_create(ctx._h, self.n, _ptr(ch, C.c_int32), _ptr(t0, C.c_double), C.byref(o),
                                                        C.byref(self._h)))
         ctx._samplers.add(self)
+        if pointwise:
+            _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -586,11 +606,13 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_run(self._h, int(n_iter), _ptr(theta, C.c_double), _ptr(stats, C.c_double)))
         return theta, {name: stats[:, :, k].copy() for k, name in enumerate(STAT_NAMES)}
 
-    def run_record(self, n_iter: int, first: int, i_raw=None, ab_s_waner=None, i=None, ab_n_mu=None, ab_s_mu=None, thin: int = 1):
+    def run_record(self, n_iter: int, first: int, i_raw=None, ab_s_waner=None, i=None, ab_n_mu=None, ab_s_mu=None, thin: int = 1,
+                   ll_s=None, ll_n=None):
         """
         run() that also writes every iteration's discrete state / Deterministics of every chain into the given
         C-contiguous arrays of shape (n, capacity, G, N) (int8 for i_raw and i, float64 for the two mu) and
-        (n, capacity, N) int8 for ab_s_waner, at draws first .. first + n_iter - 1.  thin = K > 1: only iterations
+        (n, capacity, N) int8 for ab_s_waner, at draws first .. first + n_iter - 1; ``ll_s`` / ``ll_n`` (n, capacity, K)
+        float64 receive the pointwise log-likelihood of the readings (``Context.pointwise_loglik``).  thin = K > 1: only iterations
         0, K, 2K, ... of the call are written, at draws first, first + 1, ... (ceil(n_iter / K) of them).
         """
         if thin < 1:
@@ -600,7 +622,9 @@ class NativeSampler:
         cap = None
         for name, arr, dt, tail in (("i_raw", i_raw, np.int8, (G, N)), ("ab_s_waner", ab_s_waner, np.int8, (N,)),
                                     ("i", i, np.int8, (G, N)), ("ab_n_mu", ab_n_mu, np.float64, (G, N)),
-                                    ("ab_s_mu", ab_s_mu, np.float64, (G, N))):
+                                    ("ab_s_mu", ab_s_mu, np.float64, (G, N)),
+                                    ("ll_s", ll_s, np.float64, (self._ctx.n_obs_s,)),
+                                    ("ll_n", ll_n, np.float64, (self._ctx.n_obs_n,))):
             if arr is None:
                 continue
             if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.shape[0] != self.n or arr.shape[2:] != tail:
@@ -624,6 +648,14 @@ class NativeSampler:
         n = C.c_int64()
         _check(self._lib, self._lib.abd_sampler_means(self._h, int(k), *[_ptr(o, C.c_double) for o in out], C.byref(n)))
         return out[0], out[1], out[2], n.value
+
+    def pointwise_stats(self, k: int):
+        """Pointwise log-likelihood statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S
+        readings then N in the caller's order; rows log sum exp(ll), mean(ll), sum of squared deviations (compare.merge)."""
+        out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_pointwise_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
+        return out, n.value
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

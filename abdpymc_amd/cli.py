@@ -40,7 +40,25 @@ def build_parser() -> argparse.ArgumentParser:
                         "exceed the host budget (ABD_RECORD_BUDGET_GB, default 8) is refused with the K that fits.")
     parser.add_argument("--dense_metric", help="Adapt a full mass matrix (PyMC's init='adapt_full') instead of a diagonal one.",
                         action="store_true")
+    parser.add_argument("--waic", help="Accumulate the pointwise log-likelihood of the OD readings on the device over all draws and "
+                        "report WAIC (elpd_waic, p_waic, se; per reading elpd_waic_i / p_waic_i in the output).", action="store_true")
+    parser.add_argument("--log_likelihood", help="Record the pointwise log-likelihood of every OD reading at the recorded (thinned) "
+                        "draws: ArviZ group log_likelihood (it_s_lik, it_n_lik), as pm.compute_log_likelihood.", action="store_true")
     return parser
+
+
+WAIC_KEYS = ("elpd_waic_i_it_s_lik", "elpd_waic_i_it_n_lik", "p_waic_i_it_s_lik", "p_waic_i_it_n_lik")
+
+
+def add_waic(res: dict) -> dict:
+    """compare.waic of a gathered ``waic=True`` result: the per-reading values go into ``res`` (keys WAIC_KEYS), the totals
+    are returned."""
+    from . import compare
+
+    w = compare.waic(res)
+    res["elpd_waic_i_it_s_lik"], res["elpd_waic_i_it_n_lik"] = w["elpd_waic_i_s"], w["elpd_waic_i_n"]
+    res["p_waic_i_it_s_lik"], res["p_waic_i_it_n_lik"] = w["p_waic_i_s"], w["p_waic_i_n"]
+    return w
 
 
 def write_posterior(res: dict, path: str, coords: dict) -> str:
@@ -53,10 +71,15 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
         dims = {"i_raw": ["gap", "ind"], "i": ["gap", "ind"], "ab_n_mu": ["gap", "ind"], "ab_s_mu": ["gap", "ind"],
                 "ab_s_waner": ["ind"], "mean_i": ["chain", "gap", "ind"], "mean_ab_n_mu": ["chain", "gap", "ind"],
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
-        skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu")
-        post = {k: v for k, v in res.items() if not k.startswith("stat_") and k not in skip}
+        skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
+        post = {k: v for k, v in res.items() if not k.startswith(("stat_", "waic_", "log_likelihood_")) and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
-        means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") if k in res}
+        means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS if k in res}
+        # pm.compute_log_likelihood: one variable per observed variable, its dim named as PyMC names an undimmed one
+        loglik = {k[len("log_likelihood_"):]: v for k, v in res.items() if k.startswith("log_likelihood_")}
+        dims.update({"it_s_lik": ["it_s_lik_dim_0"], "it_n_lik": ["it_n_lik_dim_0"],
+                     "elpd_waic_i_it_s_lik": ["it_s_lik_dim_0"], "p_waic_i_it_s_lik": ["it_s_lik_dim_0"],
+                     "elpd_waic_i_it_n_lik": ["it_n_lik_dim_0"], "p_waic_i_it_n_lik": ["it_n_lik_dim_0"]})
         if "draw_index" in res and res["draw_index"].shape[1] != next(iter(stats.values())).shape[1]:
             # --thin: an InferenceData has ONE draw axis, so the file holds the thinned draws of every variable (what
             # abdpymc-subsample-idata makes of a full one); the posterior means over ALL draws travel as constant data
@@ -64,7 +87,8 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
             n_all = next(iter(stats.values())).shape[1]
             post = {k: (v[:, idx] if v.shape[1] == n_all else v) for k, v in post.items()}
             stats = {k: v[:, idx] for k, v in stats.items()}
-        idata = az.from_dict(posterior=post, sample_stats=stats, constant_data=means or None, coords=coords, dims=dims)
+        idata = az.from_dict(posterior=post, sample_stats=stats, constant_data=means or None, log_likelihood=loglik or None,
+                             coords=coords, dims=dims)
         az.to_netcdf(idata, path)  # abd.py:924
         return path
     out = (path or "abd_posterior") + ("" if str(path or "").endswith(".npz") else ".npz")
@@ -116,7 +140,8 @@ def main(argv=None) -> int:
         raise SystemExit(f"--thin must be >= 1, got {args.thin}")
     res = sample(m, tune=args.tune, draws=args.draws, chains=mine, seed=args.seed,
                  record_deterministics=not args.no_deterministics, record_discrete=not args.no_discrete, progress=progress,
-                 chain_offset=first, dense_metric=args.dense_metric, thin=args.thin)  # abd.py:922
+                 chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
+                 waic=args.waic)  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
@@ -125,6 +150,10 @@ def main(argv=None) -> int:
         dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else None
         res = distributed.gather_results(res, counts, dist, dev)
     if rank == 0:
+        if args.waic:
+            w = add_waic(res)
+            print(f"WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_readings']} readings, "
+                  f"{w['n_draws']} draws; {w['n_warn']} readings with p_waic_i > 0.4)", file=sys.stderr)
         out = write_posterior(res, args.netcdf, data.coords)
         print(f"wrote {out}  ({chains} chains x {args.draws} draws on {world} x {name})", file=sys.stderr)
     if world > 1:

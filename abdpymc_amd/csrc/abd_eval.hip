@@ -3,6 +3,7 @@
 #include "abd_host.hpp"
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
+#include "abd_pointwise.hpp"
 
 namespace abdi {
 
@@ -500,9 +501,106 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
   return ABD_OK;
 }
 
+int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc, int64_t n_draw) {
+  const int64_t Ks = c->s.K, Kn = c->n.K;
+  if (Ks + Kn == 0 || (!ll_s && !ll_n && !acc)) return ABD_OK;
+  if (ll_s && ll_n && ll_n != ll_s + Ks) return fail(ABD_ERR_ARG, "internal: pointwise rows must be one S-then-N row");
+  const Transformed tr = transform(theta);
+  const ChainSlot& sl = c->slots[(size_t)chain];
+  PointwiseArgs w;
+  std::memset(&w, 0, sizeof w);
+  if (c->dense) {
+    w.y_n = c->n.yxi;
+    w.y_s = c->s.yxi;
+  } else {
+    w.y_n = c->n.y;
+    w.x_n = c->n.x;
+    w.y_s = c->s.y;
+    w.x_s = c->s.x;
+    w.g_n = c->n.g;
+    w.g_s = c->s.g;
+    w.j_n = c->n.j;
+    w.j_s = c->s.j;
+  }
+  w.vw = c->vw;
+  w.iw = sl.iw;
+  w.waner = sl.waner;
+  w.ll = ll_s ? ll_s : (ll_n ? ll_n - Ks : nullptr);  // (a row without its S part is never read there)
+  w.acc = acc;
+  w.rho_n = tr.rho_n;
+  w.rho_s = tr.rho_s;
+  constexpr double kLog2E = 1.4426950408889634074;
+  w.init_n = tr.init_n;
+  w.perm_n = tr.perm_n;
+  w.temp_n = tr.temp_n;
+  w.b2_n = tr.b_n * kLog2E;
+  w.d_n = tr.d_n;
+  w.inv_sig_n = 1.0 / tr.sig_n;
+  w.lnorm_n = -(theta[13] + 0.5 * kLog2Pi);  // log sigma is the value variable itself, as in the assembled loglik
+  w.init_s = tr.init_s;
+  w.perm_s = tr.perm_s;
+  w.b2_s = tr.b_s * kLog2E;
+  w.d_s = tr.d_s;
+  w.inv_sig_s = 1.0 / tr.sig_s;
+  w.lnorm_s = -(theta[16] + 0.5 * kLog2Pi);
+  w.K_s = Ks;
+  w.K_n = Kn;
+  w.n_draw = acc ? n_draw : 0;
+  w.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  w.G = c->G;
+  w.N = c->N;
+  w.nt = c->nt;
+  const bool f32 = c->storage == ABD_STORE_F32, wide = c->nt > ABD_MAXT;
+  using Kernel = void (*)(const PointwiseArgs);
+  Kernel k;
+  int blocks;
+  size_t lds;
+  if (c->dense) {
+    k = f32 ? (wide ? abd_pointwise_dense_kernel<float, ABD_MAXT_MAX> : abd_pointwise_dense_kernel<float, ABD_MAXT>)
+            : (wide ? abd_pointwise_dense_kernel<double, ABD_MAXT_MAX> : abd_pointwise_dense_kernel<double, ABD_MAXT>);
+    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
+    blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
+  } else {
+    k = f32 ? (wide ? abd_pointwise_obs_kernel<float, ABD_MAXT_MAX> : abd_pointwise_obs_kernel<float, ABD_MAXT>)
+            : (wide ? abd_pointwise_obs_kernel<double, ABD_MAXT_MAX> : abd_pointwise_obs_kernel<double, ABD_MAXT>);
+    const int64_t cap = (int64_t)c->n_cu * 8;
+    w.bn = (int32_t)std::min<int64_t>((Kn + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    w.bs = (int32_t)std::min<int64_t>((Ks + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    lds = (size_t)2 * (c->G + 1) * sizeof(double2_t);
+    blocks = w.bn + w.bs;
+  }
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
 }  // namespace abdi
 
 extern "C" {
+
+int abd_pointwise_loglik(abd_ctx* c, int32_t chain, const double* theta, double* ll_s, double* ll_n) {
+  if (!c || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  int rc = check_chains(c, 1, &chain);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int frc = flush_ring(c)) return frc;
+  if (int jrc = join_pipes(c)) return jrc;
+  const int64_t Ks = c->s.K, Kn = c->n.K;
+  if (Ks + Kn == 0 || (!ll_s && !ll_n)) return ABD_OK;
+  if (!c->d_pw) HIP_TRY(hipMalloc(&c->d_pw, (size_t)(Ks + Kn) * sizeof(double)));  // staging, kept for the next call
+  double* d_s = c->d_pw;
+  double* d_n = c->d_pw + Ks;
+  if (int lrc = launch_pointwise(c, chain, theta, c->stream, ll_s ? d_s : nullptr, ll_n ? d_n : nullptr, nullptr, 0)) return lrc;
+  std::vector<double> h((size_t)(Ks + Kn));
+  HIP_TRY(hipMemcpyAsync(h.data(), c->d_pw, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // back to the order the caller gave the readings in (abd_create)
+  if (ll_s)
+    for (int64_t k = 0; k < Ks; ++k) ll_s[c->order_s[(size_t)k]] = h[(size_t)k];
+  if (ll_n)
+    for (int64_t k = 0; k < Kn; ++k) ll_n[c->order_n[(size_t)k]] = h[(size_t)(Ks + k)];
+  return ABD_OK;
+}
 
 int abd_n_result_slots(abd_ctx*) { return kResultSlots; }
 

@@ -128,6 +128,7 @@ struct abd_ctx {
   int dense_blocks = 0;   // dense kernel grid.x
   uint64_t chunk_mask[3][ABD_MAXT_MAX] = {};
   AntigenDev s, n;
+  std::vector<int64_t> order_s, order_n;  // reading k of the device's sorted order is the caller's reading order_*[k]
   uint64_t* vw = nullptr;  // [nt][N]
   uint64_t* pw = nullptr;  // [nt][N]
   double* exp2_tab = nullptr;  // dense cohorts: 2^(j/1024) (abd_dense.hpp)
@@ -179,6 +180,7 @@ struct abd_ctx {
   unsigned long long* h_counts_chain = nullptr;  // ... and their pinned host copy
   bool gibbs_v1 = false;                   // ABD_GIBBS_V1=1: dense cohorts use the wave-per-proposal kernel too
   int g2_refill_min = ABD_G2_REFILL_MIN, g2_tail_lanes = ABD_G2_TAIL_LANES, g2_tail_age = ABD_G2_TAIL_AGE;  // scheduler knobs of abd_gibbs_dense_kernel (ABD_G2_*)
+  double* d_pw = nullptr;                  // staging of abd_pointwise_loglik: K_s + K_n doubles
   double* d_det = nullptr;                 // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
   std::vector<ResultSlot> results;
   hipStream_t stream = nullptr;
@@ -235,6 +237,11 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
 int enqueue_train_launch(abd_ctx* c, int chain, int pi, TrainArgs* t, const HostTerms& first_terms, double* seqp = nullptr);
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a);
 int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1);
+
+// Pointwise log-likelihood of chain `chain` at theta on stream st (abd_pointwise.hpp): rows ll_s / ll_n (sorted order; nullptr
+// skips) and / or the accumulators acc ([4][K_s + K_n]: S readings in columns [0, K_s), N readings after them) updated by draw
+// n_draw >= 1 (acc nullptr: not updated)
+int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc, int64_t n_draw);
 
 // ---- abd_gibbs.hip
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,

@@ -19,6 +19,11 @@ struct abd_sampler {
   int64_t rec_chunk = 0;
   double* d_rec_mu = nullptr;   // [2][n][rec_chunk][G*N]  (ab_n_mu, ab_s_mu)
   int8_t* d_rec_i8 = nullptr;   // [2][n][rec_chunk][G*N]  (i_raw, i) then [n][rec_chunk][N] (waner)
+  double* d_rec_ll = nullptr;   // [n][rec_chunk][K_s + K_n]  pointwise log-likelihood, the device's sorted order (S, then N)
+  // pointwise log-likelihood statistics of every draw (abd_pointwise.hpp): [n][4][K_s + K_n] running max, scaled sum of
+  // exp, mean, M2 per reading
+  double* d_pw_acc = nullptr;
+  bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise is refused after that)
   std::vector<double> lp, gr;  // starting points' logp / gradient
   int unit = 1;                // chains per independent unit (sampler_run_units)
   int threads = 1;  // host threads that drive the units (sampler_run_units)
@@ -203,6 +208,19 @@ bool train_ready(const abd_sampler* s, int u) {
   return true;
 }
 
+// the pointwise log-likelihood of chain k's draw at iteration `iter` (its point and discrete state are final): the draw's
+// record row at position `pos` of the chunk (rec nullptr: not recorded) and / or -- a draw, accumulation on -- its running
+// statistics.  Queued where the running sums go, on the same stream (behind the chain's sweep, in front of the next one)
+int pointwise_chain(abd_sampler* s, const abd_record* rec, int k, int64_t pos, int64_t iter, hipStream_t st) {
+  abd_ctx* c = s->c;
+  const size_t Kt = (size_t)(c->s.K + c->n.K);
+  double* row = (rec && (rec->ll_s || rec->ll_n)) ? s->d_rec_ll + ((size_t)k * s->rec_chunk + (size_t)pos) * Kt : nullptr;
+  double* acc = (s->d_pw_acc && iter >= s->o.tune) ? s->d_pw_acc + (size_t)k * 4 * Kt : nullptr;
+  if (!row && !acc) return ABD_OK;
+  return launch_pointwise(c, s->chains[(size_t)k], s->ch[(size_t)k].nuts.q, st, row, row ? row + c->s.K : nullptr, acc,
+                          iter - s->o.tune + 1);
+}
+
 // add chain k's Deterministics at its current point to its running sums (stream st)
 int accumulate_chain(abd_sampler* s, int k, hipStream_t st) {
   abd_ctx* c = s->c;
@@ -368,9 +386,11 @@ void abd_sampler_destroy(abd_sampler* s) {
     train_free(s);
     dtrain_free(s);
   }
-  if (s->d_sums || s->d_rec_mu || s->d_rec_i8) {
+  if (s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc) {
     (void)hipSetDevice(s->c->device);
     (void)hipStreamSynchronize(s->c->stream);
+    if (s->d_rec_ll) (void)hipFree(s->d_rec_ll);
+    if (s->d_pw_acc) (void)hipFree(s->d_pw_acc);
     if (s->d_sums) (void)hipFree(s->d_sums);
     if (s->d_rec_mu) (void)hipFree(s->d_rec_mu);
     if (s->d_rec_i8) (void)hipFree(s->d_rec_i8);
@@ -396,7 +416,25 @@ int record_flush_chain(abd_sampler* s, const abd_record* rec, int k, int64_t fir
   if (rec->i_raw) HIP_TRY(hipMemcpyAsync(rec->i_raw + host * cells, s->d_rec_i8 + dev * cells, filled * cells, hipMemcpyDeviceToHost, st));
   if (rec->i) HIP_TRY(hipMemcpyAsync(rec->i + host * cells, s->d_rec_i8 + per_var + dev * cells, filled * cells, hipMemcpyDeviceToHost, st));
   if (rec->ab_s_waner) HIP_TRY(hipMemcpyAsync(rec->ab_s_waner + host * N, s->d_rec_i8 + 2 * per_var + dev * N, filled * N, hipMemcpyDeviceToHost, st));
+  // pointwise log-likelihood: staged in the device's sorted order, scattered back to the caller's order of the readings
+  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
+  std::vector<double> ll;
+  if ((rec->ll_s || rec->ll_n) && Kt) {
+    ll.resize((size_t)filled * Kt);
+    HIP_TRY(hipMemcpyAsync(ll.data(), s->d_rec_ll + dev * Kt, ll.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
   HIP_TRY(hipStreamSynchronize(st));
+  for (size_t d = 0; d < ll.size() / std::max<size_t>(Kt, 1); ++d) {
+    const double* r = ll.data() + d * Kt;
+    if (rec->ll_s) {
+      double* o = rec->ll_s + (host + d) * Ks;
+      for (size_t k = 0; k < Ks; ++k) o[c->order_s[k]] = r[k];
+    }
+    if (rec->ll_n) {
+      double* o = rec->ll_n + (host + d) * Kn;
+      for (size_t k = 0; k < Kn; ++k) o[c->order_n[k]] = r[Ks + k];
+    }
+  }
   return ABD_OK;
 }
 
@@ -561,6 +599,7 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
       } else if (sums) {
         if (int rc = accumulate_chain(s, j, st)) return rc;
       }
+      if (int rc = pointwise_chain(s, (recording && un.k % thin == 0) ? rec : nullptr, j, un.staged, s->it + un.k, st)) return rc;
     }
     if (recording && un.k % thin == 0 && ++un.staged == s->rec_chunk) {
       for (int j = un.lo; j < un.hi; ++j)
@@ -832,6 +871,7 @@ int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* st
     // the discrete state; the point goes by value)
     const bool draw = s->it + r.k >= s->o.tune;
     double* sums = (draw && s->d_sums) ? s->d_sums + (size_t)j * 3 * (size_t)c->G * c->N : nullptr;
+    if (int rc = pointwise_chain(s, (recording && r.k % thin == 0) ? rec : nullptr, j, r.staged, s->it + r.k, d.side)) return rc;
     if (recording && r.k % thin == 0) {
       if (int rc = record_stage_chain(s, rec, j, r.staged, d.side, sums)) return rc;
       if (++r.staged == s->rec_chunk) {
@@ -1035,7 +1075,10 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (n_iter < 0) return fail(ABD_ERR_ARG, "n_iter=%lld is negative", (long long)n_iter);
   abd_ctx* c = s->c;
   const int n = s->n;
-  const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu);
+  const bool with_ll = rec && (rec->ll_s || rec->ll_n);
+  const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll);
+  const size_t Kt = (size_t)(c->s.K + c->n.K);
+  s->ran = true;
   if (recording) {
     if (rec->thin < 0) return fail(ABD_ERR_ARG, "record: thin=%lld is negative", (long long)rec->thin);
     const int64_t thin = std::max<int64_t>(1, rec->thin), n_rec = (n_iter + thin - 1) / thin;  // iterations 0, thin, 2 thin, ... of the call
@@ -1045,7 +1088,7 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
     if (!s->d_rec_mu) {
       HIP_TRY(hipSetDevice(c->device));
       const size_t cells = (size_t)c->G * c->N;
-      const size_t per_draw = (size_t)n * (cells * 18 + c->N);  // bytes staged per draw, all chains
+      const size_t per_draw = (size_t)n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
       s->rec_chunk = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(((size_t)256 << 20) / per_draw)));
       double* mu = nullptr;
       int8_t* i8 = nullptr;
@@ -1057,6 +1100,14 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
       }
       s->d_rec_mu = mu;
       s->d_rec_i8 = i8;
+    }
+    if (with_ll && !s->d_rec_ll) {
+      HIP_TRY(hipSetDevice(c->device));
+      const hipError_t e = hipMalloc(&s->d_rec_ll, std::max<size_t>(1, (size_t)n * s->rec_chunk * Kt) * sizeof(double));
+      if (e != hipSuccess) {
+        s->d_rec_ll = nullptr;
+        return fail(ABD_ERR_HIP, "record staging (pointwise log-likelihood): %s", hipGetErrorString(e));
+      }
     }
   }
   if (s->dtrains) return sampler_run_trains(s, n_iter, theta, stats, rec, recording);
@@ -1079,6 +1130,56 @@ int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* mu_n_me
     for (size_t e = 0; e < cells; ++e) outs[v][e] *= inv;
   }
   if (n_draws) *n_draws = s->n_accumulated;
+  return ABD_OK;
+}
+
+int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (s->ran) return fail(ABD_ERR_STATE, "pointwise accumulation must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  if (s->d_pw_acc) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(s->d_pw_acc);
+    s->d_pw_acc = nullptr;
+  }
+  if (!accumulate) return ABD_OK;
+  const size_t bytes = std::max<size_t>(1, (size_t)s->n * 4 * (size_t)(c->s.K + c->n.K)) * sizeof(double);
+  hipError_t e = hipMalloc(&s->d_pw_acc, bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    s->d_pw_acc = nullptr;
+    return fail(ABD_ERR_NOMEM, "pointwise accumulators: %zu bytes of device memory", bytes);
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_pw_acc, 0, bytes, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    if (s->d_pw_acc) (void)hipFree(s->d_pw_acc);
+    s->d_pw_acc = nullptr;
+    return fail(ABD_ERR_HIP, "pointwise accumulators: %s", hipGetErrorString(e));
+  }
+  return ABD_OK;
+}
+
+int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
+  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_pw_acc) return fail(ABD_ERR_STATE, "pointwise accumulation is not enabled (abd_sampler_enable_pointwise)");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
+    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
+  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
+  std::vector<double> acc(4 * Kt);
+  if (Kt) HIP_TRY(hipMemcpy(acc.data(), s->d_pw_acc + (size_t)k * 4 * Kt, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < Kt; ++r) {
+    const size_t o = r < Ks ? (size_t)c->order_s[r] : Ks + (size_t)c->order_n[r - Ks];  // the caller's order
+    out[o] = acc[r] + std::log(acc[Kt + r]);  // M + log S = log sum exp(ll)  (-inf before the first draw)
+    out[Kt + o] = acc[2 * Kt + r];
+    out[2 * Kt + o] = acc[3 * Kt + r];
+  }
+  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
   return ABD_OK;
 }
 

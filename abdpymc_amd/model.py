@@ -248,6 +248,13 @@ class AbdModel:
         i, mun, mus = self.ctx.deterministics(chain, self.ravel(point))
         return {"i": i, "ab_n_mu": mun, "ab_s_mu": mus}
 
+    def pointwise_loglik(self, point: Dict[str, np.ndarray], chain: int = 0) -> Dict[str, np.ndarray]:
+        """Log-density of every observed OD reading at ``point`` (``pm.compute_log_likelihood`` for one draw): one array per
+        observed variable, readings in the cohort's row order."""
+        self.ctx.set_discrete(chain, np.asarray(point["i_raw"]), np.asarray(point["ab_s_waner"]))
+        ll_s, ll_n = self.ctx.pointwise_loglik(chain, self.ravel(point))
+        return {"it_s_lik": ll_s, "it_n_lik": ll_n}
+
     def close(self):
         self.ctx.close()
 

@@ -277,10 +277,12 @@ def sample_chain(model, chain: int, tune: int, draws: int, seed: int, record_det
     return res
 
 
-def record_bytes(chains: int, n_rec: int, G: int, N: int, record_deterministics: bool, record_discrete: bool) -> int:
+def record_bytes(chains: int, n_rec: int, G: int, N: int, record_deterministics: bool, record_discrete: bool,
+                 n_readings: int = 0) -> int:
     """Host bytes of the per-draw arrays of a run that records ``n_rec`` draws per chain: i (int8) + ab_n_mu + ab_s_mu
-    (float64) per cell for the Deterministics, i_raw (int8) per cell + ab_s_waner (int8) per individual for the discrete state."""
-    per_draw = (G * N * 17 if record_deterministics else 0) + (G * N + N if record_discrete else 0)
+    (float64) per cell for the Deterministics, i_raw (int8) per cell + ab_s_waner (int8) per individual for the discrete state,
+    and a float64 per OD reading for the pointwise log-likelihood (``n_readings``: readings of both antigens; 0 = not recorded)."""
+    per_draw = (G * N * 17 if record_deterministics else 0) + (G * N + N if record_discrete else 0) + 8 * int(n_readings)
     return chains * n_rec * per_draw
 
 
@@ -295,7 +297,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   record_discrete: bool = True, progress: Optional[Callable[[int, int, int], None]] = None,
                   target_accept: float = 0.8, max_treedepth: int = 10, chunk: int = 50,
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
-                  budget_bytes: Optional[int] = None) -> Dict[str, np.ndarray]:
+                  budget_bytes: Optional[int] = None, log_likelihood: bool = False,
+                  waic: bool = False) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -308,6 +311,12 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     ``budget_bytes`` on the host (default ``record_budget_bytes()``) is refused with the ``thin`` that would fit.
     ``chain_offset`` is the global id of this process's first chain when chains are sharded over GPUs: local
     chain c uses the random streams of global chain ``chain_offset + c``.
+
+    ``log_likelihood``: also record the pointwise log-likelihood of every OD reading at the recorded draws (thinned like the
+    (gap, ind) arrays) as ``log_likelihood_it_s_lik`` / ``log_likelihood_it_n_lik`` (chains, n_rec, K), what
+    ``pm.compute_log_likelihood`` adds to an InferenceData.  ``waic``: accumulate its per-reading statistics over ALL
+    draws on the device (any cohort size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n;
+    S readings first), ``waic_n_draws`` (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``compare.waic`` reads them.
     """
     from .model import THETA_NAMES, constrain
 
@@ -316,9 +325,11 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     if thin < 1:
         raise ValueError(f"thin must be >= 1, got {thin}")
     n_rec = (draws + thin - 1) // thin
-    if record_deterministics or record_discrete:
+    K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if (log_likelihood or waic) else (0, 0)  # readings of it_s_lik / it_n_lik
+    if record_deterministics or record_discrete or log_likelihood:
         budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
-        need = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete)
+        need = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
+                            n_readings=(K_s + K_n) if log_likelihood else 0)
         if need > budget:
             per_draw = need // max(n_rec, 1)
             fit = max(1, budget // max(per_draw, 1))          # draws per chain set that fit
@@ -336,7 +347,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         q0[c] = model.ravel(pt) + rng.uniform(-1, 1, size=len(THETA_NAMES))  # start jitter U(-1, 1) on the value variables: pm.sample's default init 'jitter+adapt_diag'
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
-                      dense_metric=dense_metric)
+                      dense_metric=dense_metric, pointwise=waic)
     n_grad = chains  # the evaluation at the starting points
     done = 0
 
@@ -361,12 +372,13 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     if record_deterministics:
         det = dict(i=np.empty((chains, n_rec, G, N), dtype=np.int8), ab_n_mu=np.empty((chains, n_rec, G, N)),
                    ab_s_mu=np.empty((chains, n_rec, G, N)))
+    ll = dict(ll_s=np.empty((chains, n_rec, K_s)), ll_n=np.empty((chains, n_rec, K_n))) if log_likelihood else {}
     k = 0
     while k < draws:
         n = min(chunk, draws - k)
-        if record_deterministics or record_discrete:
+        if record_deterministics or record_discrete or log_likelihood:
             # staged on the device, copied out in large blocks straight into the arrays above
-            th, st = smp.run_record(n, k // thin, i_raw=out_i_raw, ab_s_waner=out_w, thin=thin, **(det or {}))
+            th, st = smp.run_record(n, k // thin, i_raw=out_i_raw, ab_s_waner=out_w, thin=thin, **(det or {}), **ll)
             n_grad += int(st["n_steps"].sum()) + n * chains
             done += n
             if progress is not None:
@@ -384,7 +396,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         res["i_raw"], res["ab_s_waner"] = out_i_raw, out_w
     if det is not None:
         res.update(det)
-    if record_discrete or det is not None:
+    if log_likelihood:
+        res["log_likelihood_it_s_lik"], res["log_likelihood_it_n_lik"] = ll["ll_s"], ll["ll_n"]
+    if waic:
+        stats_pw = [smp.pointwise_stats(c) for c in range(chains)]
+        for j, name in enumerate(("waic_lse", "waic_mean", "waic_m2")):
+            res[name] = np.stack([o[j] for o, _ in stats_pw])
+        res["waic_n_draws"] = np.array([n for _, n in stats_pw], dtype=np.int64)
+        res["waic_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
+    if record_discrete or det is not None or log_likelihood:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
         means = [smp.means(c) for c in range(chains)]
@@ -402,14 +422,19 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
 def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_deterministics: bool = True,
            progress: Optional[Callable[[int, int, int], None]] = None, device_gibbs: bool = True,
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
-           dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None) -> Dict[str, np.ndarray]:
+           dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
+           waic: bool = False) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
         raise ValueError(f"model was built with {model.n_chains} chain slots, {chains} requested")
     if native and device_gibbs and hasattr(model.ctx, "sampler"):
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
-                             chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes)
+                             chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
+                             log_likelihood=log_likelihood, waic=waic)
+    if log_likelihood or waic:
+        raise ValueError("log_likelihood / waic need the native sampler (sample(native=True)): the pointwise log-likelihood "
+                         "is recorded and accumulated inside it")
     if chain_offset or dense_metric or thin != 1:
         raise ValueError("chain_offset / dense_metric / thin need the native sampler")
     per_chain = []

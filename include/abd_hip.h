@@ -156,6 +156,12 @@ int abd_logp_dlogp_many(abd_ctx* ctx, int32_t n_steps, int32_t n, const int32_t*
 int abd_deterministics(abd_ctx* ctx, int32_t chain, const double* theta, int8_t* i, double* ab_n_mu,
                        double* ab_s_mu);
 
+/* Pointwise log-likelihood of the two observed Normals "it_s_lik", "it_n_lik" (abd.py:459-469) at theta and chain slot
+ * `chain`'s discrete state: ll_s receives s.n_obs doubles, ll_n n.n_obs, in the order the readings were given to abd_create
+ * (what pm.compute_log_likelihood records for one draw).  Either pointer may be NULL.  sum(ll_s) + sum(ll_n) is
+ * abd_loglik_dlogp's loglik to rounding. */
+int abd_pointwise_loglik(abd_ctx* ctx, int32_t chain, const double* theta, double* ll_s, double* ll_n);
+
 /* ---------------------------------------------------------------------------------------------------
  * The compound step pm.sample assigns to this model (reference call site abd.py:921-922), run natively
  * for several chains: NUTS on the 17 continuous variables, then one Gibbs sweep of [i_raw, ab_s_waner], then a
@@ -244,12 +250,23 @@ typedef struct abd_record {
   int8_t* i;
   double* ab_n_mu;
   double* ab_s_mu;
+  double* ll_s;        /* [n][capacity][s.n_obs], [n][capacity][n.n_obs]: the pointwise log-likelihood of every recorded draw */
+  double* ll_n;        /* (abd_pointwise_loglik), readings in the caller's order */
 } abd_record;
 int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double* stats, const abd_record* rec);
 /* Posterior means of the Deterministics of chain k (0 <= k < n) over the draws accumulated so far, each
  * (G, N); any pointer may be NULL.  *n_draws receives the number of accumulated draws. */
 int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* ab_n_mu_mean, double* ab_s_mu_mean,
                       int64_t* n_draws);
+/* Pointwise log-likelihood statistics of every draw (iteration >= tune), accumulated on the device per chain and reading.
+ * Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it); accumulate = 1 allocates 4 x (K_s + K_n)
+ * doubles per chain (K_*: the antigens' n_obs), 0 releases them. */
+int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate);
+/* The statistics of chain k (0 <= k < n) over its draws so far: out is [3][K_s + K_n] (S readings first, then N, each in the
+ * caller's order): row 0 log sum over draws of exp(ll) (not divided by the count), row 1 the mean of ll, row 2 the sum of
+ * squared deviations from it (M2).  They merge exactly over chains and processes: log-add-exp for row 0, Chan et al.'s
+ * pairwise formulas for rows 1 and 2 (abdpymc_amd/compare.py).  *n_draws (may be NULL) receives the number of draws. */
+int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws);
 /* Current diagonal of M^-1 (17) and step size of chain k; `metric` (17 x 17, may be NULL) receives the full
  * M^-1 (the diagonal matrix when the metric is diagonal). */
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);
