@@ -209,7 +209,6 @@ int enqueue_group(abd_ctx* c, int n, const int32_t* chains, const double* theta,
   const bool fused_sum = (sync_own || (force_pipe >= 0 && c->dense_own_sum && !(c->fuse_finalize && pp.on))) && ((c->dense && !lanes) || (lanes && train));
   if (train) {
     if (!fused_sum || n != 1) return fail(ABD_ERR_STATE, "internal: a leapfrog-train launch needs one chain and a kernel that sums its own rows");
-    train->dense = c->dense ? 1 : 0;
     train->tag = seq + 1.0;
     a.train = *train;
   }

@@ -27,7 +27,7 @@ struct abd_sampler {
   std::vector<double> lp, gr;  // starting points' logp / gradient
   int unit = 1;                // chains per independent unit (sampler_run_units)
   int threads = 1;  // host threads that drive the units (sampler_run_units)
-  // Leapfrog trains (abd_types.hpp: TrainArgs): dense cohort, one chain per unit, diagonal metric.  Every evaluation of such a
+  // Leapfrog trains of observation lists (abd_types.hpp: TrainArgs): one chain per unit, diagonal metric.  Every evaluation of such a
   // sampler is a train launch -- it assembles logp and gradient on the device and leaves the next point of the half for
   // the launch queued behind it -- and the host keeps up to `lookahead` launches of a half queued ahead of the record it
   // is waiting for, so a chain's leapfrogs follow each other at the device's pace, not at the host's round trip.
@@ -84,12 +84,28 @@ __global__ void abd_sweep_done_kernel(const unsigned long long* counts, unsigned
   }
 }
 
-void train_free(abd_sampler* s) {
+// Free a sampler and everything it may own, a half-built one included, once the device is through with it
+void sampler_release(abd_sampler* s) {
+  const bool trains = !s->tu.empty() || !s->dc.empty();
+  if (trains || s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc) {
+    (void)hipSetDevice(s->c->device);
+    // launches of a half that ended early may still be on their way; the buffers' last users are on the context's stream
+    (void)(trains ? hipDeviceSynchronize() : hipStreamSynchronize(s->c->stream));
+  }
   for (auto& t : s->tu) {
     if (t.slots) (void)hipFree(t.slots);
     if (t.rec_h) (void)hipHostFree(t.rec_h);
   }
-  s->tu.clear();
+  for (auto& d : s->dc) {
+    if (d.st) (void)hipFree(d.st);
+    if (d.ring_h) (void)hipHostFree(d.ring_h);
+    if (d.begin_h) (void)hipHostFree(d.begin_h);
+    if (d.done_h) (void)hipHostFree(d.done_h);
+    if (d.side) (void)hipStreamDestroy(d.side);
+  }
+  for (void* p : {(void*)s->d_sums, (void*)s->d_rec_mu, (void*)s->d_rec_i8, (void*)s->d_rec_ll, (void*)s->d_pw_acc})
+    if (p) (void)hipFree(p);
+  delete s;
 }
 
 int train_alloc(abd_sampler* s) {
@@ -102,17 +118,6 @@ int train_alloc(abd_sampler* s) {
     HIP_TRY(hipHostGetDevicePointer((void**)&t.rec_d, t.rec_h, 0));
   }
   return ABD_OK;
-}
-
-void dtrain_free(abd_sampler* s) {
-  for (auto& d : s->dc) {
-    if (d.st) (void)hipFree(d.st);
-    if (d.ring_h) (void)hipHostFree(d.ring_h);
-    if (d.begin_h) (void)hipHostFree(d.begin_h);
-    if (d.done_h) (void)hipHostFree(d.done_h);
-    if (d.side) (void)hipStreamDestroy(d.side);
-  }
-  s->dc.clear();
 }
 
 int dtrain_alloc(abd_sampler* s) {
@@ -206,27 +211,6 @@ bool train_ready(const abd_sampler* s, int u) {
   if (*(volatile const double*)&t.rec_h[k].tag != t.tags[k]) return false;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
   return true;
-}
-
-// the pointwise log-likelihood of chain k's draw at iteration `iter` (its point and discrete state are final): the draw's
-// record row at position `pos` of the chunk (rec nullptr: not recorded) and / or -- a draw, accumulation on -- its running
-// statistics.  Queued where the running sums go, on the same stream (behind the chain's sweep, in front of the next one)
-int pointwise_chain(abd_sampler* s, const abd_record* rec, int k, int64_t pos, int64_t iter, hipStream_t st) {
-  abd_ctx* c = s->c;
-  const size_t Kt = (size_t)(c->s.K + c->n.K);
-  double* row = (rec && (rec->ll_s || rec->ll_n)) ? s->d_rec_ll + ((size_t)k * s->rec_chunk + (size_t)pos) * Kt : nullptr;
-  double* acc = (s->d_pw_acc && iter >= s->o.tune) ? s->d_pw_acc + (size_t)k * 4 * Kt : nullptr;
-  if (!row && !acc) return ABD_OK;
-  return launch_pointwise(c, s->chains[(size_t)k], s->ch[(size_t)k].nuts.q, st, row, row ? row + c->s.K : nullptr, acc,
-                          iter - s->o.tune + 1);
-}
-
-// add chain k's Deterministics at its current point to its running sums (stream st)
-int accumulate_chain(abd_sampler* s, int k, hipStream_t st) {
-  abd_ctx* c = s->c;
-  const size_t cells = (size_t)c->G * c->N;
-  return launch_deterministics(c, s->chains[(size_t)k], s->ch[(size_t)k].nuts.q, st, nullptr, nullptr, nullptr,
-                               s->d_sums + (size_t)k * 3 * cells);
 }
 
 }  // namespace
@@ -345,57 +329,31 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
     if (!rc) rc = wait_rows(c, kSyncSlot + u, m, c->seq, c->pipe[unit_pipe(c, u)].st);
     if (!rc) rc = fetch_slot(c, kSyncSlot + u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA);
   }
-  if (rc) {
-    train_free(s);
-    dtrain_free(s);
-    delete s;
-    return rc;
-  }
-  for (int k = 0; k < n; ++k) {
+  for (int k = 0; k < n && !rc; ++k) {
     if (!std::isfinite(s->lp[(size_t)k])) {
-      train_free(s);
-      dtrain_free(s);
-      delete s;
-      return fail(ABD_ERR_ARG, "logp at the starting point of chain %d is not finite", chains[k]);
+      rc = fail(ABD_ERR_ARG, "logp at the starting point of chain %d is not finite", chains[k]);
+      break;
     }
     s->ch[(size_t)k].init(theta0 + (size_t)k * ABD_N_THETA, s->lp[(size_t)k], s->gr.data() + (size_t)k * ABD_N_THETA,
                           opts->seed, (uint64_t)((int64_t)chains[k] + opts->chain_offset), opts->tune, opts->max_treedepth, opts->target_accept,
                           opts->dense_metric != 0);
   }
-  if (opts->accumulate) {
+  if (!rc && opts->accumulate) {
     const size_t bytes = (size_t)n * 3 * c->G * c->N * sizeof(double);
     hipError_t e = hipMalloc(&s->d_sums, bytes);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_sums, 0, bytes, c->stream);
-    if (e != hipSuccess) {
-      if (s->d_sums) (void)hipFree(s->d_sums);
-      train_free(s);
-      dtrain_free(s);
-      delete s;
-      return fail(ABD_ERR_HIP, "sampler sums: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) rc = fail(ABD_ERR_HIP, "sampler sums: %s", hipGetErrorString(e));
+  }
+  if (rc) {
+    sampler_release(s);
+    return rc;
   }
   *out = s;
   return ABD_OK;
 }
 
 void abd_sampler_destroy(abd_sampler* s) {
-  if (!s) return;
-  if (!s->tu.empty() || !s->dc.empty()) {
-    (void)hipSetDevice(s->c->device);
-    (void)hipDeviceSynchronize();  // launches of a half that ended early may still be on their way
-    train_free(s);
-    dtrain_free(s);
-  }
-  if (s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc) {
-    (void)hipSetDevice(s->c->device);
-    (void)hipStreamSynchronize(s->c->stream);
-    if (s->d_rec_ll) (void)hipFree(s->d_rec_ll);
-    if (s->d_pw_acc) (void)hipFree(s->d_pw_acc);
-    if (s->d_sums) (void)hipFree(s->d_sums);
-    if (s->d_rec_mu) (void)hipFree(s->d_rec_mu);
-    if (s->d_rec_i8) (void)hipFree(s->d_rec_i8);
-  }
-  delete s;
+  if (s) sampler_release(s);
 }
 
 int abd_sampler_run(abd_sampler* s, int64_t n_iter, double* theta, double* stats) {
@@ -438,29 +396,83 @@ int record_flush_chain(abd_sampler* s, const abd_record* rec, int k, int64_t fir
   return ABD_OK;
 }
 
-// stage the current draw of chain k at position `pos` of its chunk (all asynchronous on stream st)
-int record_stage_chain(abd_sampler* s, const abd_record* rec, int k, int64_t pos, hipStream_t st, double* sums = nullptr) {
-  abd_ctx* c = s->c;
-  const size_t cells = (size_t)c->G * c->N, N = (size_t)c->N;
-  const size_t per_var = (size_t)s->n * s->rec_chunk * cells;
-  const size_t at = ((size_t)k * s->rec_chunk + pos);
-  const int chain = s->chains[(size_t)k];
-  const ChainSlot& slot = c->slots[(size_t)chain];
-  if (rec->i || rec->ab_n_mu || rec->ab_s_mu || sums)  // (sums: the draw also goes into the device-resident running sums)
-    if (int rc = launch_deterministics(c, chain, s->ch[(size_t)k].nuts.q, st, rec->i ? s->d_rec_i8 + per_var + at * cells : (int8_t*)nullptr,
-                                       rec->ab_n_mu ? s->d_rec_mu + at * cells : (double*)nullptr,
-                                       rec->ab_s_mu ? s->d_rec_mu + per_var + at * cells : (double*)nullptr, sums))
-      return rc;
-  if (rec->i_raw)
-    if (int rc = launch_unpack(c, chain, s->d_rec_i8 + at * cells, st)) return rc;
-  if (rec->ab_s_waner)
-    HIP_TRY(hipMemcpyAsync(s->d_rec_i8 + 2 * per_var + at * N, slot.waner, N, hipMemcpyDeviceToDevice, st));
-  return ABD_OK;
+// One abd_sampler_run_record call as both run loops see it: the caller's arrays, and per chain the draws of its record that
+// are staged on the device ([flushed_to, flushed_to + staged) of the caller's record).  The chains of a unit move through
+// their iterations together; a chain belongs to one host thread.
+struct RunFrame {
+  abd_sampler* s;
+  int64_t n_iter;
+  double* theta;
+  double* stats;
+  const abd_record* rec;  // nullptr: nothing is recorded
+  int64_t thin;           // iterations 0, thin, 2 thin, ... of the call are recorded
+  std::chrono::steady_clock::time_point t_begin;
+  struct Staging {
+    int64_t staged = 0, flushed_to = 0;
+  };
+  std::vector<Staging> staging;
+};
+
+// the caller's theta and stats rows of chain j at iteration k of the call (its point is final); counts: accepted / proposed
+// of the chain's sweep (nullptr: no sweep)
+void write_draw(const RunFrame& f, int j, int64_t k, const unsigned long long* counts) {
+  const abdnuts::Nuts& nu = f.s->ch[(size_t)j].nuts;
+  const size_t row = (size_t)j * f.n_iter + k;
+  if (f.theta) std::memcpy(f.theta + row * ABD_N_THETA, nu.q, sizeof(double) * ABD_N_THETA);
+  if (!f.stats) return;
+  double* o = f.stats + row * ABD_N_STATS;
+  o[ABD_STAT_LP] = nu.lp;
+  o[ABD_STAT_TREE_DEPTH] = nu.stats.tree_depth;
+  o[ABD_STAT_N_STEPS] = nu.stats.n_steps;
+  o[ABD_STAT_MEAN_TREE_ACCEPT] = nu.stats.mean_tree_accept;
+  o[ABD_STAT_STEP_SIZE] = nu.stats.step_size;
+  o[ABD_STAT_DIVERGING] = nu.stats.diverging ? 1.0 : 0.0;
+  o[ABD_STAT_ENERGY] = nu.stats.energy;
+  o[ABD_STAT_MAX_ENERGY_ERROR] = nu.stats.max_energy_error;
+  o[ABD_STAT_GIBBS_ACCEPTED] = counts ? (double)counts[0] : 0.0;
+  o[ABD_STAT_GIBBS_PROPOSED] = counts ? (double)counts[1] : 0.0;
+  o[ABD_STAT_T_DONE] = std::chrono::duration<double>(std::chrono::steady_clock::now() - f.t_begin).count();
 }
 
-}  // namespace
-
-namespace {
+// the device work of chain j's draw at iteration k of the call (point and discrete state are final), all on stream st, behind
+// the chain's sweep and in front of its next one: the Deterministics into the draw's record and / or the running sums (one
+// launch), the rest of the record, the pointwise log-likelihood.  These kernels read the discrete state and the point (by
+// value), nothing else.  Then the chain's staging: a full chunk, and what is left at the call's last iteration, is copied
+// out and waited for.  Nothing else is launched here.
+int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
+  abd_sampler* s = f.s;
+  abd_ctx* c = s->c;
+  const abd_record* rec = (f.rec && k % f.thin == 0) ? f.rec : nullptr;  // (nullptr: this draw is not recorded)
+  const int64_t iter = s->it + k;
+  const bool draw = iter >= s->o.tune;
+  RunFrame::Staging& sg = f.staging[(size_t)j];
+  const int chain = s->chains[(size_t)j];
+  const double* q = s->ch[(size_t)j].nuts.q;
+  const size_t cells = (size_t)c->G * c->N, N = (size_t)c->N, Kt = (size_t)(c->s.K + c->n.K);
+  const size_t per_var = (size_t)s->n * s->rec_chunk * cells, at = (size_t)j * s->rec_chunk + (size_t)sg.staged;
+  double* sums = (draw && s->d_sums) ? s->d_sums + (size_t)j * 3 * cells : nullptr;
+  int8_t* i = (rec && rec->i) ? s->d_rec_i8 + per_var + at * cells : nullptr;
+  double* n_mu = (rec && rec->ab_n_mu) ? s->d_rec_mu + at * cells : nullptr;
+  double* s_mu = (rec && rec->ab_s_mu) ? s->d_rec_mu + per_var + at * cells : nullptr;
+  if (i || n_mu || s_mu || sums)
+    if (int rc = launch_deterministics(c, chain, q, st, i, n_mu, s_mu, sums)) return rc;
+  if (rec && rec->i_raw)
+    if (int rc = launch_unpack(c, chain, s->d_rec_i8 + at * cells, st)) return rc;
+  if (rec && rec->ab_s_waner)
+    HIP_TRY(hipMemcpyAsync(s->d_rec_i8 + 2 * per_var + at * N, c->slots[(size_t)chain].waner, N, hipMemcpyDeviceToDevice, st));
+  // pointwise log-likelihood: the record's row and / or -- a draw, accumulation on -- the running statistics
+  double* ll = (rec && (rec->ll_s || rec->ll_n)) ? s->d_rec_ll + at * Kt : nullptr;
+  double* acc = (draw && s->d_pw_acc) ? s->d_pw_acc + (size_t)j * 4 * Kt : nullptr;
+  if (ll || acc)
+    if (int rc = launch_pointwise(c, chain, q, st, ll, ll ? ll + c->s.K : nullptr, acc, iter - s->o.tune + 1)) return rc;
+  if (rec) sg.staged += 1;
+  if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
+    if (int rc = record_flush_chain(s, f.rec, j, sg.flushed_to, sg.staged, st)) return rc;
+    sg.flushed_to += sg.staged;
+    sg.staged = 0;
+  }
+  return ABD_OK;
+}
 
 // The sampler's chains run as independent UNITS of `unit` consecutive chains (1 for large dense cohorts, 4 otherwise;
 // abd_sampler_create), unit u on HIP stream u mod 8 with its own private result rows (slot kSyncSlot + u):
@@ -473,24 +485,22 @@ namespace {
 // units' launches overlap on the device.  Within a unit the chains share launches (small cohorts are launch-bound:
 // ~6 us of host time per evaluation launch).  Same compound step per chain, same random streams, and the numbers a
 // unit's launch produces depend only on the unit (fixed grid), never on the other units or on timing.
-int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* stats, const abd_record* rec, bool recording) {
+int sampler_run_units(RunFrame& f) {
+  abd_sampler* s = f.s;
   abd_ctx* c = s->c;
+  const int64_t n_iter = f.n_iter;
   const int n = s->n, B = s->unit;
   const int n_units = (n + B - 1) / B;
-  const int64_t thin = recording ? std::max<int64_t>(1, rec->thin) : 1;  // iterations 0, thin, 2 thin, ... of the call are recorded
   enum { EVAL, POST, DONE };
   struct Unit {
     int lo = 0, hi = 0, m = 0, state = EVAL;
     int64_t k = 0;       // iterations completed in this call
-    int64_t staged = 0;  // draws staged on the device, not yet copied out
-    int64_t flushed_to = 0;
     double tag = 0.0;
     std::chrono::steady_clock::time_point t_queued;  // profile: when its last evaluation had been queued
     std::vector<int32_t> ids, who;
     std::vector<double> th, lp, gr;
   };
   std::vector<Unit> units((size_t)n_units);
-  const std::chrono::steady_clock::time_point t_run_begin = std::chrono::steady_clock::now();
   // host threads (see below): a power of two <= 8, so that units that share a HIP stream (u and u + 8) share their thread
   // (one thread while abd_kernel_timing is on: the event bookkeeping of enqueue_group belongs to the context, not to a unit)
   int T_all = 1;
@@ -500,9 +510,6 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
   // those rows, whichever sampler drives them
   while (c->unit_seq.size() < (size_t)n_units) c->unit_seq.push_back((double)(c->unit_seq.size() + 1) * 1099511627776.0);
   s->unit_tags = T_all > 1;
-  HIP_TRY(hipSetDevice(c->device));
-  if (int frc = flush_ring(c)) return frc;
-  HIP_TRY(hipStreamSynchronize(c->stream));  // whatever the caller queued on the context's stream comes first
   auto stream_of = [&](int u) { return c->pipe[unit_pipe(c, u)].st; };
   // evaluate the points th[0 .. m) of the unit's chains who[0 .. m)
   auto launch_eval = [&](int u) -> int {
@@ -562,26 +569,7 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
   // then the next iteration's first leapfrogs, or DONE
   auto finish_iteration = [&](int u, bool with_counts) -> int {
     Unit& un = units[(size_t)u];
-    hipStream_t st = stream_of(u);
-    const bool draw = s->it + un.k >= s->o.tune;
-    for (int j = un.lo; j < un.hi; ++j) {
-      const abdnuts::Nuts& nu = s->ch[(size_t)j].nuts;
-      if (theta) std::memcpy(theta + ((size_t)j * n_iter + un.k) * ABD_N_THETA, nu.q, sizeof(double) * ABD_N_THETA);
-      if (stats) {
-        double* o = stats + ((size_t)j * n_iter + un.k) * ABD_N_STATS;
-        o[ABD_STAT_LP] = nu.lp;
-        o[ABD_STAT_TREE_DEPTH] = nu.stats.tree_depth;
-        o[ABD_STAT_N_STEPS] = nu.stats.n_steps;
-        o[ABD_STAT_MEAN_TREE_ACCEPT] = nu.stats.mean_tree_accept;
-        o[ABD_STAT_STEP_SIZE] = nu.stats.step_size;
-        o[ABD_STAT_DIVERGING] = nu.stats.diverging ? 1.0 : 0.0;
-        o[ABD_STAT_ENERGY] = nu.stats.energy;
-        o[ABD_STAT_MAX_ENERGY_ERROR] = nu.stats.max_energy_error;
-        o[ABD_STAT_GIBBS_ACCEPTED] = with_counts ? (double)c->h_counts_chain[2 * (size_t)j] : 0.0;
-        o[ABD_STAT_GIBBS_PROPOSED] = with_counts ? (double)c->h_counts_chain[2 * (size_t)j + 1] : 0.0;
-        o[ABD_STAT_T_DONE] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_run_begin).count();
-      }
-    }
+    for (int j = un.lo; j < un.hi; ++j) write_draw(f, j, un.k, with_counts ? c->h_counts_chain + 2 * (size_t)j : nullptr);
     // the next iteration's first leapfrogs go out BEFORE this iteration's recording is queued: the recording kernels read the
     // point (by value) and the discrete state, which only the next sweep -- queued after them -- changes, and the host's time
     // for queueing them (several launches per draw) passes while the device is already at work for the chain
@@ -591,29 +579,10 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
       un.state = EVAL;
       if (int rc = launch_tree(u)) return rc;
     }
-    for (int j = un.lo; j < un.hi; ++j) {
-      // running sums and the draw's record share one launch of the Deterministics kernel where both are wanted
-      double* sums = (draw && s->d_sums) ? s->d_sums + (size_t)j * 3 * (size_t)c->G * c->N : nullptr;
-      if (recording && un.k % thin == 0) {
-        if (int rc = record_stage_chain(s, rec, j, un.staged, st, sums)) return rc;
-      } else if (sums) {
-        if (int rc = accumulate_chain(s, j, st)) return rc;
-      }
-      if (int rc = pointwise_chain(s, (recording && un.k % thin == 0) ? rec : nullptr, j, un.staged, s->it + un.k, st)) return rc;
-    }
-    if (recording && un.k % thin == 0 && ++un.staged == s->rec_chunk) {
-      for (int j = un.lo; j < un.hi; ++j)
-        if (int rc = record_flush_chain(s, rec, j, un.flushed_to, un.staged, st)) return rc;
-      un.flushed_to += un.staged;
-      un.staged = 0;
-    }
+    for (int j = un.lo; j < un.hi; ++j)
+      if (int rc = queue_draw(f, j, un.k, stream_of(u))) return rc;
     un.k += 1;
-    if (last) {
-      un.state = DONE;
-      if (recording)
-        for (int j = un.lo; j < un.hi; ++j)
-          if (int rc = record_flush_chain(s, rec, j, un.flushed_to, un.staged, st)) return rc;
-    }
+    if (last) un.state = DONE;
     return ABD_OK;
   };
   for (int u = 0; u < n_units; ++u) {
@@ -626,7 +595,6 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
     un.th.resize(cap * ABD_N_THETA);
     un.lp.resize(cap);
     un.gr.resize(cap * ABD_N_THETA);
-    un.flushed_to = recording ? rec->first : 0;
     if (n_iter == 0) {
       un.state = DONE;
       continue;
@@ -774,12 +742,6 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
       if (!errors[(size_t)t].empty()) return fail(first_error.load(), "%s", errors[(size_t)t].c_str());
     return fail(first_error.load(), "sampler thread failed");
   }
-  // the context's stream continues behind everything the units queued
-  for (int pi = 1; pi < c->n_streams; ++pi) c->pipe[pi].busy = true;
-  if (int jrc = join_pipes(c)) return jrc;
-  const int64_t first_draw = std::max<int64_t>(s->it, s->o.tune);
-  if (s->d_sums && s->it + n_iter > first_draw) s->n_accumulated += s->it + n_iter - first_draw;
-  s->it += n_iter;
   return ABD_OK;
 }
 
@@ -792,11 +754,12 @@ int sampler_run_units(abd_sampler* s, int64_t n_iter, double* theta, double* sta
 // chain's iteration goes on beside the unit's launches: sweep + counts on the chain's own stream, then -- the discrete
 // state has changed -- a BEGIN whose first step evaluates the start point (EVAL0) before the tree starts from it.
 // Nothing a chain computes depends on the other chains or on timing: launch shape and step order are fixed per chain.
-int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* stats, const abd_record* rec, bool recording) {
+int sampler_run_trains(RunFrame& f) {
+  abd_sampler* s = f.s;
   abd_ctx* c = s->c;
+  const int64_t n_iter = f.n_iter;
   const int n = s->n, B = s->unit;
   const int n_units = (n + B - 1) / B;
-  const int64_t thin = recording ? std::max<int64_t>(1, rec->thin) : 1;
   enum { NEED_BEGIN, TREE, SWEEP, DONE };
   struct Step {
     int64_t idx;     // record index
@@ -814,18 +777,12 @@ int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* st
     int pend_slot = -1;      // the last step left its record beside pt[pend_slot] ...
     int64_t pend_idx = 0;    // ... for the next launch's service workgroup to pass on
     std::deque<Step> fifo;
-    int64_t staged = 0, flushed_to = 0;  // recording: draws staged on the device / copied out
   };
   std::vector<Run> runs((size_t)n);
-  HIP_TRY(hipSetDevice(c->device));
-  if (int frc = flush_ring(c)) return frc;
-  HIP_TRY(hipStreamSynchronize(c->stream));  // whatever the caller queued on the context's stream comes first
   static const bool profile = env_int("ABD_SAMPLER_PROFILE", 0) != 0;
-  using clk = std::chrono::steady_clock;
   g_launch_profile = LaunchProfile();
   g_launch_profile.on = profile;
   long n_launches = 0, n_records = 0, n_stale = 0;
-  const clk::time_point t_begin = clk::now();
 
   auto stage_begin = [&](int j, bool eval_first, bool eval_only) {
     // hand chain j's next transition to the device: begin_draw() has been called (momentum and directions drawn)
@@ -847,55 +804,23 @@ int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* st
     r.eval_only = eval_only;
     r.state = NEED_BEGIN;
   };
-  // outputs of iteration r.k of chain j (point and discrete state are final), its recording, then the next transition
+  // outputs of iteration r.k of chain j (point and discrete state are final) and its draw's device work, on the chain's own
+  // stream; then the next transition
   auto iteration_done = [&](int j, bool with_counts) -> int {
     Run& r = runs[(size_t)j];
     abd_sampler::DChain& d = s->dc[(size_t)j];
-    const abdnuts::Nuts& nu = s->ch[(size_t)j].nuts;
-    if (theta) std::memcpy(theta + ((size_t)j * n_iter + r.k) * ABD_N_THETA, nu.q, sizeof(double) * ABD_N_THETA);
-    if (stats) {
-      double* o = stats + ((size_t)j * n_iter + r.k) * ABD_N_STATS;
-      o[ABD_STAT_LP] = nu.lp;
-      o[ABD_STAT_TREE_DEPTH] = nu.stats.tree_depth;
-      o[ABD_STAT_N_STEPS] = nu.stats.n_steps;
-      o[ABD_STAT_MEAN_TREE_ACCEPT] = nu.stats.mean_tree_accept;
-      o[ABD_STAT_STEP_SIZE] = nu.stats.step_size;
-      o[ABD_STAT_DIVERGING] = nu.stats.diverging ? 1.0 : 0.0;
-      o[ABD_STAT_ENERGY] = nu.stats.energy;
-      o[ABD_STAT_MAX_ENERGY_ERROR] = nu.stats.max_energy_error;
-      o[ABD_STAT_GIBBS_ACCEPTED] = with_counts ? (double)d.done_h[0] : 0.0;
-      o[ABD_STAT_GIBBS_PROPOSED] = with_counts ? (double)d.done_h[1] : 0.0;
-      o[ABD_STAT_T_DONE] = std::chrono::duration<double>(clk::now() - t_begin).count();
-    }
-    // running sums and the draw's record: on the chain's own stream, behind its sweep and in front of the next one (they read
-    // the discrete state; the point goes by value)
-    const bool draw = s->it + r.k >= s->o.tune;
-    double* sums = (draw && s->d_sums) ? s->d_sums + (size_t)j * 3 * (size_t)c->G * c->N : nullptr;
-    if (int rc = pointwise_chain(s, (recording && r.k % thin == 0) ? rec : nullptr, j, r.staged, s->it + r.k, d.side)) return rc;
-    if (recording && r.k % thin == 0) {
-      if (int rc = record_stage_chain(s, rec, j, r.staged, d.side, sums)) return rc;
-      if (++r.staged == s->rec_chunk) {
-        if (int rc = record_flush_chain(s, rec, j, r.flushed_to, r.staged, d.side)) return rc;
-        r.flushed_to += r.staged;
-        r.staged = 0;
-      }
-    } else if (sums) {
-      if (int rc = accumulate_chain(s, j, d.side)) return rc;
-    }
-    r.k += 1;
-    if (r.k == n_iter) {
-      r.state = DONE;
-      if (recording)
-        if (int rc = record_flush_chain(s, rec, j, r.flushed_to, r.staged, d.side)) return rc;
-      r.staged = 0;
-    }
+    write_draw(f, j, r.k, with_counts ? d.done_h : nullptr);
+    if (int rc = queue_draw(f, j, r.k, d.side)) return rc;
+    if (++r.k == n_iter) r.state = DONE;
     return ABD_OK;
   };
   // chain j's tree has ended (the NUTS state machine holds the new point): adaptation, then the sweep or the next transition
   auto transition_end = [&](int j) -> int {
     Run& r = runs[(size_t)j];
     abd_sampler::DChain& d = s->dc[(size_t)j];
-    r.epoch += 1;  // what is still queued for the chain belongs to a tree that is over
+    // steps still queued for the chain belong to a tree that is over: they run and may overlap its sweep, which is harmless
+    // only because their records are never read
+    r.epoch += 1;
     s->ch[(size_t)j].end_transition();
     if (s->o.gibbs) {
       const int32_t id = s->chains[(size_t)j];
@@ -917,10 +842,7 @@ int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* st
     return ABD_OK;
   };
 
-  for (int j = 0; j < n; ++j) {
-    Run& r = runs[(size_t)j];
-    r.flushed_to = recording ? rec->first : 0;
-    if (n_iter == 0) continue;
+  for (int j = 0; j < n && n_iter > 0; ++j) {
     s->ch[(size_t)j].begin();
     stage_begin(j, false, false);  // logp and gradient at the chain's point are known (abd_sampler_create, or the run before)
   }
@@ -1055,16 +977,11 @@ int sampler_run_trains(abd_sampler* s, int64_t n_iter, double* theta, double* st
   g_launch_profile.on = false;
   if (rc_loop != ABD_OK) return rc_loop;
   if (profile) {
-    const double wall = std::chrono::duration<double>(clk::now() - t_begin).count();
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - f.t_begin).count();
     std::fprintf(stderr, "abd sampler (trains): %d units of %d chains, %ld launches, %ld records (%ld stale steps) in %.3f s; %.2f us inside the "
                  "launch call per launch\n", n_units, B, n_launches, n_records, n_stale, wall,
                  g_launch_profile.evals ? 1e6 * g_launch_profile.eval_s / g_launch_profile.evals : 0.0);
   }
-  for (int pi = 1; pi < c->n_streams; ++pi) c->pipe[pi].busy = true;
-  if (int jrc = join_pipes(c)) return jrc;
-  const int64_t first_draw = std::max<int64_t>(s->it, s->o.tune);
-  if (s->d_sums && s->it + n_iter > first_draw) s->n_accumulated += s->it + n_iter - first_draw;
-  s->it += n_iter;
   return ABD_OK;
 }
 
@@ -1110,8 +1027,21 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
       }
     }
   }
-  if (s->dtrains) return sampler_run_trains(s, n_iter, theta, stats, rec, recording);
-  return sampler_run_units(s, n_iter, theta, stats, rec, recording);
+  RunFrame f{s, n_iter, theta, stats, recording ? rec : nullptr, recording ? std::max<int64_t>(1, rec->thin) : 1, {}, {}};
+  f.staging.resize((size_t)n);
+  for (auto& sg : f.staging) sg.flushed_to = recording ? rec->first : 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = flush_ring(c)) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // whatever the caller queued on the context's stream comes first
+  f.t_begin = std::chrono::steady_clock::now();
+  if (int rc = s->dtrains ? sampler_run_trains(f) : sampler_run_units(f)) return rc;
+  // the context's stream continues behind everything the run queued
+  for (int pi = 1; pi < c->n_streams; ++pi) c->pipe[pi].busy = true;
+  if (int rc = join_pipes(c)) return rc;
+  const int64_t first_draw = std::max<int64_t>(s->it, s->o.tune);
+  if (s->d_sums && s->it + n_iter > first_draw) s->n_accumulated += s->it + n_iter - first_draw;
+  s->it += n_iter;
+  return ABD_OK;
 }
 
 int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* mu_n_mean, double* mu_s_mean, int64_t* n_draws) {

@@ -84,8 +84,7 @@ struct TrainArgs {
   int32_t use_slot;         // >= 0: this launch's point is slots[use_slot]; < 0: `first` below (the host staged it)
   int32_t next_slot;        // where this launch leaves the next point
   int32_t own_record;       // 1: this launch writes its own record to `rec` (no successor is going to pass it on)
-  int32_t dense;            // 1: the sums come from the dense kernel (its sum for d/db is scaled: abd_terms.hpp), 0: observation lists
-  int32_t pad_;
+  int32_t pad_[2];          // (the fields behind keep their offsets)
   TrainRecord* fwd_rec;     // use_slot >= 0: the predecessor's record, written by this launch from slots[use_slot] ...
   double fwd_tag;           // ... under the predecessor's tag; nullptr: the predecessor wrote its own
   double inv_mass[ABD_NT];  // diagonal of M^-1
@@ -233,7 +232,7 @@ struct EvalArgs {
   int32_t n_chains, n_lg;     // n_lg: 64-individual lane groups (dense kernel)
   uint64_t chunk_mask[3][ABD_MAXT_MAX];
   ChainPar ch[ABD_MAX_BATCH_K];
-  TrainArgs train;  // dense kernel, one chain per launch (abd_sampler.hip)
+  TrainArgs train;  // observation-list kernel, one chain per launch (abd_sampler.hip: list trains)
 };
 
 // row / G of the dense kernel's range arithmetic (abd_dense.hpp: range_of) by a 32-bit reciprocal: magic = ceil(2^32 / G),

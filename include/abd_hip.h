@@ -178,9 +178,10 @@ int abd_pointwise_loglik(abd_ctx* ctx, int32_t chain, const double* theta, doubl
  *     doubling directions of the transition (drawn by the host before the tree starts), the leaves still to go.  A launch takes
  *     the 1, 2 or 4 chains of its unit one leapfrog further each, whatever stage each of them is in, and goes on ACROSS the
  *     halves of a doubling and across doublings; the host reads the launches' records from a ring in mapped memory, runs the
- *     tree logic (U-turn tests, multinomial choice) behind the device and tells the state machine when a transition is over
- *     (launches queued beyond that point find the chain idle and skip it).  The chain's sweep runs on a side stream of its
- *     own while the other chains of the unit go on.  Units: one chain up to 4 chains, two up to 7, four beyond.
+ *     tree logic (U-turn tests, multinomial choice) behind the device and hands the chain its next transition when one is over.
+ *     Steps queued beyond the end of a tree still run for that chain and may overlap its sweep; their records are never read,
+ *     which is the only reason the overlap is harmless.  The chain's sweep runs on a side stream of its own while the other
+ *     chains of the unit go on.  Units: one chain up to 4 chains, two up to 7, four beyond.
  *   - Observation lists: units of one chain; a train ends with the half of the doubling it serves.
  * A train run is exactly repeatable, does not depend on the other chains or on timing, and equals the host-driven run
  * (ABD_SAMPLER_TRAINS=0) to rounding, not bit for bit: the closed forms of the transforms are the device's exp / log1p
