@@ -620,12 +620,14 @@ int abd_create(const abd_desc* d, abd_ctx** out) {
   c->pipe_blocks = std::min(c->dense_blocks, c->n_cu * std::max(1, dbpc / c->n_pipes));  // measured best: 3 pipes x 1 workgroup per CU
   if (const int pb = tune_int("ABD_PIPE_BLOCKS", 0)) c->pipe_blocks = std::max(1, std::min(pb, c->blocks_max));
   c->dbpc = dbpc;
-  c->group_blocks = std::min(c->dense_blocks, c->n_cu * std::max(1, dbpc / 2));
+  // a sampler unit's launch: one workgroup per CU, whatever the number of units in flight -- a unit's numbers must not depend
+  // on it.  256 on gfx950 = ABD_TRAIN_ONE_LEVEL: few enough for the launch to sum its own rows (abd_eval.hip: plan_launch)
+  c->group_blocks = c->n_cu;
+  if (const int gb = tune_int("ABD_GROUP_BLOCKS_PER_CU", 0)) c->group_blocks = std::max(1, std::min(c->n_cu * gb, c->blocks_max));
   for (int pi = 0; pi < kMaxPipes; ++pi)
     if (c->pipe[pi].st)
       for (int b = 0; b < 2; ++b)
         CREATE_TRY(hipMalloc(&c->pipe[pi].partials[b], (size_t)c->n_slots * c->blocks_max * ABD_NOUT * sizeof(double)));
-  c->fuse_finalize = tune_int("ABD_FUSE_FINALIZE", 1) != 0;
   c->xcd_remap = tune_int("ABD_XCD_REMAP", 1) != 0;
   c->fin_rows = std::max(0, tune_int("ABD_FIN_ROWS", 2));
   const size_t out_bytes = (size_t)(kResultSlots + c->n_sync_slots) * c->n_slots * ABD_NOUT * sizeof(double);
@@ -641,15 +643,11 @@ int abd_create(const abd_desc* d, abd_ctx** out) {
   CREATE_TRY(hipMalloc(&c->d_fin_count, (size_t)kMaxPipes * ABD_MAX_BATCH * sizeof(unsigned int)));
   CREATE_TRY(hipMemset(c->d_fin_count, 0, (size_t)kMaxPipes * ABD_MAX_BATCH * sizeof(unsigned int)));
   {
-    const size_t tc_bytes = (size_t)kMaxPipes * ABD_MAX_BATCH * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE * sizeof(unsigned int);
+    const size_t tc_bytes = (size_t)kMaxPipes * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE * sizeof(unsigned int);
     CREATE_TRY(hipMalloc(&c->d_train_count, tc_bytes));
     CREATE_TRY(hipMemset(c->d_train_count, 0, tc_bytes));
   }
   c->dense_own_sum = env_int("ABD_DENSE_OWN_SUM", 1) != 0;
-  // measured (round 4, profiles/r04: sync_own_sum_ab.txt): 28.8 / 33.8 / 43.1 us per call of 1 / 2 / 4 chains at config 3 with the
-  // launch summing its own rows (two-level count-in at 1 024 workgroups), 28.1 / 32.0 / 41.9 us with the sum as a second
-  // launch: the second launch stays
-  c->sync_own_sum = c->dense_own_sum && tune_int("ABD_SYNC_OWN_SUM", 0) != 0;
   CREATE_TRY(hipHostMalloc(&c->h_counts_chain, (size_t)c->n_slots * 2 * sizeof(unsigned long long), hipHostMallocDefault));
   c->gibbs_v1 = env_int("ABD_GIBBS_V1", 0) != 0;
   c->g2_refill_min = std::max(1, std::min(64, tune_int("ABD_G2_REFILL_MIN", ABD_G2_REFILL_MIN)));

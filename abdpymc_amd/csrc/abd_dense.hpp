@@ -864,7 +864,7 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
   if ((lane & 3) == 0) red[wave * ABD_NOUT + reduce16_index(lane)] = tot;
   __syncthreads();
   bool own_sum = TRAINK;  // does the launch sum its own partial rows?
-  if constexpr (!TRAINK) own_sum = a.fin_count != nullptr || a.fin_count2 != nullptr;
+  if constexpr (!TRAINK) own_sum = a.fin_count != nullptr;
   if (tid < CB * ABD_NOUT) {
     const int cc = tid / ABD_NOUT, k = tid % ABD_NOUT;
     double v = 0.0;
@@ -930,24 +930,7 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
     double* sm_chain = reinterpret_cast<double*>(smem);  // [CB][ABD_TRAIN_SM]
     if (!two_level_sums<CB>(a.partials, a.partials + (int64_t)CB * nblk * ABD_NOUT, a.fin_count, nblk, blk, step_mask, flag, sm_chain, tid)) return;
     if (wave < CB && a.tc[wave].action != ABD_TR_SKIP) train_step(a, a.tc[wave], sm_chain + wave * ABD_TRAIN_SM, lane);
-  } else if (a.fin_count2 != nullptr) {
-    // a synchronous call's launch (a grid that fills the chip: 1 024 workgroups): counted in in two levels like a train launch;
-    // the workgroup that comes last writes each chain's row -- 15 sums, the tag behind a system-scope fence -- for the host
-    double* sm_chain = reinterpret_cast<double*>(smem);
-    const int n_rows_chains = (int)gridDim.y * CB;  // chains of the launch: the shard rows lie behind all partial rows
-    if (!two_level_sums<CB>(a.partials + (int64_t)cbase * nblk * ABD_NOUT,
-                            a.partials + ((int64_t)n_rows_chains * nblk + (int64_t)cbase * ABD_TRAIN_SHARDS) * ABD_NOUT,
-                            a.fin_count2 + (int64_t)blockIdx.y * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE, nblk, blk, (1u << CB) - 1u, flag,
-                            sm_chain, tid))
-      return;
-    if (wave == 0) {
-      if (lane < CB * ABD_NOUT && lane % ABD_NOUT < ABD_NOUT - 1)
-        a.fin_out[(int64_t)(cbase + lane / ABD_NOUT) * ABD_NOUT + lane % ABD_NOUT] = sm_chain[(lane / ABD_NOUT) * ABD_TRAIN_SM + lane % ABD_NOUT];
-      __threadfence_system();
-      __builtin_amdgcn_wave_barrier();
-      if (lane < CB) __hip_atomic_store(a.fin_out + (int64_t)(cbase + lane) * ABD_NOUT + (ABD_NOUT - 1), a.fin_tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  } else {
+  } else if (a.fin_count != nullptr) {  // (always, here: with a plain `else` the 2- and 4-chain forms take 2 more VGPRs)
     if (wave == 0) {
       handoff_drain_stores();
       if (lane < CB) {

@@ -17,51 +17,22 @@ size_t table_lds_bytes(int G, int cpw, int red_rows, bool exp2_tab) {
                               (exp2_tab ? (size_t)ABD_EXP2_TAB * sizeof(double) : 0));
 }
 
-template <typename K>
-hipError_t launch_k(K kernel, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a) {
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
+// The evaluation kernels (abd_dense.hpp, abd_obs.hpp, abd_sparse.hpp) and their instantiations
+enum class Family { Dense, Lanes, Sparse };  // dense panels; observation lists: lane per observation / wave per individual
+using EvalKernel = void (*)(const EvalArgs);
+template <typename R, bool GRAD>
+EvalKernel eval_kernel(Family f, int cpw, bool xc, bool wide) {  // wide: more than 256 gaps, 8 words per individual
+  switch (f) {
+    case Family::Dense:  // xc: split panels, R + 1 instead of 2 R bytes per cell and antigen
+      if (cpw == 4) return xc ? abd_dense_kernel<R, 4, GRAD, true> : abd_dense_kernel<R, 4, GRAD, false>;
+      if (cpw == 2) return xc ? abd_dense_kernel<R, 2, GRAD, true> : abd_dense_kernel<R, 2, GRAD, false>;
+      return xc ? abd_dense_kernel<R, 1, GRAD, true> : abd_dense_kernel<R, 1, GRAD, false>;
+    case Family::Sparse:  // no 4-chain form: it needs 169 VGPRs (2 waves per SIMD) and spills 245 SGPRs (plan_launch caps it at 2)
+      if (cpw == 2) return wide ? abd_sparse_kernel<R, 2, GRAD, ABD_MAXT_MAX> : abd_sparse_kernel<R, 2, GRAD, ABD_MAXT>;
+      return wide ? abd_sparse_kernel<R, 1, GRAD, ABD_MAXT_MAX> : abd_sparse_kernel<R, 1, GRAD, ABD_MAXT>;
+    default:
+      return wide ? abd_obs_kernel<R, GRAD, ABD_MAXT_MAX> : abd_obs_kernel<R, GRAD, ABD_MAXT>;
   }
-  hipLaunchKernelGGL(kernel, grid, dim3(ABD_BLOCK), lds, st, a);
-  return hipGetLastError();
-}
-
-template <typename R, int C>
-hipError_t launch_dense_g(bool grad, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a, bool xc) {
-  if (xc)  // split panels: R + 1 instead of 2 R bytes per cell and antigen
-    return grad ? launch_k(abd_dense_kernel<R, C, true, true>, grid, lds, st, a) : launch_k(abd_dense_kernel<R, C, false, true>, grid, lds, st, a);
-  return grad ? launch_k(abd_dense_kernel<R, C, true, false>, grid, lds, st, a) : launch_k(abd_dense_kernel<R, C, false, false>, grid, lds, st, a);
-}
-template <typename R>
-hipError_t launch_dense(int C, bool grad, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a, bool xc) {
-  switch (C) {
-    case 4: return launch_dense_g<R, 4>(grad, grid, lds, st, a, xc);
-    case 2: return launch_dense_g<R, 2>(grad, grid, lds, st, a, xc);
-    default: return launch_dense_g<R, 1>(grad, grid, lds, st, a, xc);
-  }
-}
-template <typename R, int C>
-hipError_t launch_sparse_g(bool grad, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a) {
-  if (a.nt > ABD_MAXT)  // more than 256 gaps: the kernels that keep an individual's words in registers are built for 8 words too
-    return grad ? launch_k(abd_sparse_kernel<R, C, true, ABD_MAXT_MAX>, grid, lds, st, a)
-                : launch_k(abd_sparse_kernel<R, C, false, ABD_MAXT_MAX>, grid, lds, st, a);
-  return grad ? launch_k(abd_sparse_kernel<R, C, true, ABD_MAXT>, grid, lds, st, a)
-              : launch_k(abd_sparse_kernel<R, C, false, ABD_MAXT>, grid, lds, st, a);
-}
-template <typename R>
-hipError_t launch_sparse(int C, bool grad, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a) {
-  switch (C) {  // no 4-chain form: it needs 169 VGPRs (2 waves per SIMD) and spills 245 SGPRs (pick_cpw caps this path at 2)
-    case 2: return launch_sparse_g<R, 2>(grad, grid, lds, st, a);
-    default: return launch_sparse_g<R, 1>(grad, grid, lds, st, a);
-  }
-}
-
-template <typename R>
-hipError_t launch_obs(bool grad, dim3 grid, size_t lds, hipStream_t st, const EvalArgs& a) {
-  if (a.nt > ABD_MAXT)
-    return grad ? launch_k(abd_obs_kernel<R, true, ABD_MAXT_MAX>, grid, lds, st, a) : launch_k(abd_obs_kernel<R, false, ABD_MAXT_MAX>, grid, lds, st, a);
-  return grad ? launch_k(abd_obs_kernel<R, true, ABD_MAXT>, grid, lds, st, a) : launch_k(abd_obs_kernel<R, false, ABD_MAXT>, grid, lds, st, a);
 }
 
 // does a dense launch with cpw chains per workgroup read the split panels (od + one-byte dilution code) or the pair panels?
@@ -80,7 +51,7 @@ int pick_cpw(const abd_ctx* c, int n) {
 // grid of the dense kernel: an exact multiple of the CU count (every wave slot gets the same number of
 // gap rows), capped so a slot has at least kMinRows rows
 // share: 0 = the launch has the chip to itself, 1 = it is one of n_pipes stream-ordered launches in flight,
-// 2 = it is one of the native sampler's chain groups in flight (c->group_blocks: the chip divided by their number)
+// 2 = it is a native-sampler unit's, one of several in flight (c->group_blocks: one workgroup per CU)
 int dense_blocks(const abd_ctx* c, int cpw, int share, int grid_rows) {
   const int nsub = ABD_WAVES_PER_BLOCK / cpw;
   const int64_t rows = (int64_t)c->n_lg * c->G;
@@ -109,20 +80,14 @@ void range_split(const abd_ctx* c, int blocks, int nsub, ARGS& a, bool fused_sum
   a.rg_g_magic = abd_div_magic((uint32_t)c->G);
 }
 
-// Which of the context's streams can have kernels on the device at the same time?  HIP multiplexes its streams over a few
-// hardware queues (4 by default) and a queue runs one kernel after the other, whichever stream it came from.  One wave
-// per stream that stays for 150 us, launched back to back: a stream whose wave starts only when an earlier stream's
+// queue the Pending sum of pipe pi, if any, as its own launch
 int flush_pipe(abd_ctx* c, int pi) {
   abd_ctx::Pipe& p = c->pipe[pi];
   if (p.on) {
-    std::chrono::steady_clock::time_point lp0;
-    if (g_launch_profile.on) lp0 = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(abd_finalize_kernel, dim3(p.n), dim3(ABD_FIN_THREADS), 0, p.st, p.partials[p.buf], p.blocks, p.out, p.tag);
-    if (g_launch_profile.on) {
-      g_launch_profile.sum_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - lp0).count();
-      g_launch_profile.sums++;
-    }
-    HIP_TRY(hipGetLastError());
+    const hipError_t le = profiled_launch(true, [&] {
+      return launch_kernel(abd_finalize_kernel, dim3(p.n), dim3(ABD_FIN_THREADS), 0, p.st, p.partials[p.buf], p.blocks, p.out, p.tag);
+    });
+    HIP_TRY(le);
     p.on = false;
   }
   return ABD_OK;
@@ -149,136 +114,155 @@ int flush_pending(abd_ctx* c) {
   return join_pipes(c);
 }
 
-// Enqueue the evaluation of `n` chains (n <= ABD_MAX_BATCH); their sums go to rows d_out_rows[0..n).
-int enqueue_group(abd_ctx* c, int n, const int32_t* chains, const double* theta, bool grad, double* d_out_rows,
-                  bool deferred = false, int force_pipe = -1, const HostTerms* host = nullptr, double* seqp = nullptr,
-                  TrainArgs* train = nullptr, bool sync_call = false) {
+// A launch goes on pipe pi: the pipe's Pending sum first (unless the launch has taken it over); join_pipes waits for a pipe
+// other than 0 from now on
+int use_pipe(abd_ctx* c, int pi) {
+  if (int rc = flush_pipe(c, pi)) return rc;
+  if (pi > 0) c->pipe[pi].busy = true;
+  return ABD_OK;
+}
+
+// Who does the fixed-order sum of a launch's partial rows
+enum class Sum {
+  Pending,      // the next dense launch on the same pipe, in its first workgroups (EvalArgs::prev_*), or flush_pipe
+  FinalizeNow,  // abd_finalize_kernel, queued right behind the launch
+  Own,          // the launch's last workgroup (abd_dense.hpp, abd_obs.hpp: one counter per chain in d_fin_count)
+};
+
+// How an evaluation launch runs: everything enqueue_group needs beyond the chains themselves
+struct LaunchPlan {
+  Family family;
+  int cpw;      // chains per workgroup
+  dim3 grid;    // (workgroups, n / cpw)
+  size_t lds;
+  int pipe;
+  bool rotate;  // the pipe is the next one of the stream-ordered rotation
+  bool join;    // pipe 0 behind everything queued on the other pipes
+  Sum sum;
+};
+
+LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n) {
+  LaunchPlan p;
+  p.family = c->dense ? Family::Dense : (c->obs_lanes ? Family::Lanes : Family::Sparse);
+  p.cpw = p.family == Family::Lanes ? 1 : pick_cpw(c, n);
+  if (p.family == Family::Sparse) p.cpw = std::min(p.cpw, 2);  // (no 4-chain form: eval_kernel)
+  // stream-ordered dense launches rotate over the pipes (not under timing 1: one launch at a time); a unit's launches stay on
+  // its own pipe; everything else runs on pipe 0 after a join
+  const bool own_pipe = who.kind == Caller::Unit || who.kind == Caller::Train;
+  p.rotate = who.kind == Caller::Stream && c->n_pipes > 1 && c->dense && c->timing != 1;
+  p.join = !own_pipe && !p.rotate;
+  p.pipe = own_pipe ? who.pipe : (p.rotate ? c->pipe_order[c->next_pipe] : 0);
+  int blocks;
+  if (p.family == Family::Dense) {
+    // the last launch of a batch of stream-ordered steps ends alone on the chip: it gets the grid of a launch that has the
+    // chip to itself (one wave per SIMD issues at half the rate; a K = 20 region 376 -> 373 us; a longer tail did not pay)
+    const int share = who.kind == Caller::Unit ? 2 : (p.rotate && c->steps_behind != 0 ? 1 : 0);
+    blocks = dense_blocks(c, p.cpw, share, n / p.cpw);
+    p.lds = abd_dense_lds(c->G, p.cpw, dense_xc(c, p.cpw));
+  } else if (p.family == Family::Lanes) {
+    blocks = c->ob_n + c->ob_s + c->ob_c;
+    p.lds = who.kind == Caller::Train ? abd_obs_lds_own_sum(c->G) : abd_obs_lds_head(c->G);
+  } else {
+    blocks = c->blocks_x;
+    p.lds = table_lds_bytes(c->G, p.cpw, ABD_WAVES_PER_BLOCK * p.cpw);
+  }
+  p.grid = dim3(blocks, n / p.cpw);
+  // Who sums the partial rows:
+  //   caller   dense cohort                                        observation lists
+  //   Stream   Pending                                             FinalizeNow
+  //   Sync     Pending                                             FinalizeNow
+  //   Unit     Own (ABD_DENSE_OWN_SUM=1, <= ABD_TRAIN_ONE_LEVEL    FinalizeNow
+  //            workgroups), else FinalizeNow
+  //   Train    -- (an error: enqueue_group)                        Own (lane per observation)
+  // Only the dense kernel can carry an earlier launch's sum; a unit's rows are awaited before anything else goes on its pipe.
+  // A plain launch sums its own rows only with at most ABD_TRAIN_ONE_LEVEL workgroups -- a unit's grid is c->group_blocks,
+  // one workgroup per CU -- on one counter per chain; beyond that abd_finalize_kernel adds the rows in the same order.  (An
+  // observation-lane launch the host waits for is as fast with the second launch: profiles/README.md, history.)
+  if (!c->dense)
+    p.sum = who.kind == Caller::Train ? Sum::Own : Sum::FinalizeNow;
+  else if (who.kind == Caller::Unit)
+    p.sum = c->dense_own_sum && blocks <= ABD_TRAIN_ONE_LEVEL ? Sum::Own : Sum::FinalizeNow;
+  else
+    p.sum = Sum::Pending;
+  return p;
+}
+
+int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows) {
+  const LaunchPlan p = plan_launch(c, who, n);
+  if (who.kind == Caller::Train && (n != 1 || p.family != Family::Lanes))
+    return fail(ABD_ERR_STATE, "internal: a leapfrog-train launch needs one chain and the observation-lane kernel");
+  if ((int)p.grid.x > c->blocks_max) return fail(ABD_ERR_STATE, "internal: grid %d exceeds partial rows %d", (int)p.grid.x, c->blocks_max);
   // completion tags: the context's sequence, or the caller's own (a sampler unit handled by its own host thread: its
   // result rows are private, so its tags only have to be unique among themselves)
-  double& seq = seqp ? *seqp : c->seq;
+  double& seq = who.seq ? *who.seq : c->seq;
   EvalArgs a;
   base_args(c, a);
   a.n_chains = n;
-  for (int k = 0; k < n; ++k)
-    a.ch[k] = host ? chain_par(c, chains[k], host[k].tr) : chain_par(c, chains[k], theta + (size_t)k * ABD_N_THETA);
-  const bool lanes = !c->dense && c->obs_lanes;
-  int cpw = lanes ? 1 : pick_cpw(c, n);
-  if (!lanes && !c->dense) cpw = std::min(cpw, 2);  // wave-per-individual list kernel: see launch_sparse
-  // stream-ordered dense launches rotate over the pipes; everything else runs on pipe 0 after a join
-  const bool rotate = deferred && c->n_pipes > 1 && c->dense && c->fuse_finalize && c->timing != 1;  // timing 1: one launch at a time
-  int blocks;
-  size_t lds;
-  if (lanes) {
-    blocks = c->ob_n + c->ob_s + c->ob_c;
-    lds = train ? abd_obs_lds_own_sum(c->G) : abd_obs_lds_head(c->G);
-  } else if (c->dense) {
-    // the last launch of a batch of stream-ordered steps ends alone on the chip: it gets the grid of a launch that has the
-    // chip to itself (one wave per SIMD issues at half the rate; a K = 20 region 376 -> 373 us; a longer tail did not pay)
-    blocks = dense_blocks(c, cpw, force_pipe >= 0 ? 2 : (rotate && c->steps_behind != 0 ? 1 : 0), n / cpw);
-    lds = abd_dense_lds(c->G, cpw, dense_xc(c, cpw));
-  } else {
-    blocks = c->blocks_x;
-    lds = table_lds_bytes(c->G, cpw, ABD_WAVES_PER_BLOCK * cpw);
-  }
-  if (blocks > c->blocks_max) return fail(ABD_ERR_STATE, "internal: grid %d exceeds partial rows %d", blocks, c->blocks_max);
-  if (c->dense && !lanes)
-    range_split(c, blocks, ABD_WAVES_PER_BLOCK / cpw, a);
-  dim3 grid(blocks, n / cpw);
-  int pi = 0;
-  if (force_pipe >= 0) {
-    pi = force_pipe;  // the caller keeps several synchronous groups in flight, one per pipe (abd_sampler_run_record)
-  } else if (rotate) {
-    pi = c->pipe_order[c->next_pipe];  // streams of different hardware queues (identity until probe_stream_queues has run)
-    c->next_pipe = (c->next_pipe + 1) % c->n_pipes;
-  } else if (int jrc = join_pipes(c)) {
-    return jrc;
-  }
-  abd_ctx::Pipe& pp = c->pipe[pi];
-  if (pi > 0) pp.busy = true;
-  const int buf = pp.pbuf;
-  pp.pbuf ^= 1;
-  a.partials = pp.partials[buf];
-  // a sampler unit's dense launch sums its own partial rows: no second launch
-  if (train && pp.on)
-    if (int frc = flush_pipe(c, pi)) return frc;  // a train launch sums its own rows: nothing may be pending on its pipe
-  // (the observation-lane kernel sums its own rows only in a train launch: for an evaluation the host waits for, the second
-  // launch is as fast -- profiles/README.md, history)
-  // (a synchronous call's dense launch too: the host waits for nothing but its rows, and a second launch is 3.6 us of it)
-  const bool sync_own = sync_call && c->sync_own_sum && c->dense && !lanes && !pp.on && c->timing == 0 &&
-                        (int64_t)n * (blocks + ABD_TRAIN_SHARDS) <= (int64_t)c->n_slots * c->blocks_max;
-  const bool fused_sum = (sync_own || (force_pipe >= 0 && c->dense_own_sum && !(c->fuse_finalize && pp.on))) && ((c->dense && !lanes) || (lanes && train));
-  if (train) {
-    if (!fused_sum || n != 1) return fail(ABD_ERR_STATE, "internal: a leapfrog-train launch needs one chain and a kernel that sums its own rows");
-    train->tag = seq + 1.0;
-    a.train = *train;
-  }
-  if (fused_sum) {
-    if (c->dense && !lanes && blocks > ABD_TRAIN_ONE_LEVEL)  // a grid that fills the chip: two-level count-in (abd_dense.hpp)
-      a.fin_count2 = c->d_train_count + (size_t)pi * ABD_MAX_BATCH * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE;
-    else
-      a.fin_count = c->d_fin_count + (size_t)pi * ABD_MAX_BATCH;
-    a.fin_out = d_out_rows;
-    a.fin_tag = seq + 1.0;
-  }
+  for (int k = 0; k < n; ++k) a.ch[k] = chain_par(c, chains[k], host[k].tr);
+  if (p.family == Family::Dense) range_split(c, (int)p.grid.x, ABD_WAVES_PER_BLOCK / p.cpw, a);
   a.fin_rows = c->fin_rows;
   a.xcd_remap = c->xcd_remap ? 1 : 0;
-  if (c->dense && c->fuse_finalize && pp.on && pp.n <= blocks) {
-    // this launch's first workgroups sum the partials of the previous launch on the same pipe
+  if (p.rotate) {
+    c->next_pipe = (c->next_pipe + 1) % c->n_pipes;  // (streams of different hardware queues first: probe_stream_queues)
+  } else if (p.join) {
+    if (int rc = join_pipes(c)) return rc;
+  }
+  abd_ctx::Pipe& pp = c->pipe[p.pipe];
+  // the Pending sum on this pipe is done by this launch's first workgroups if it is a dense launch that does not sum its own
+  // rows and has a workgroup for every chain of it
+  if (p.family == Family::Dense && p.sum != Sum::Own && pp.on && pp.n <= (int)p.grid.x) {
     a.prev_partials = pp.partials[pp.buf];
     a.prev_out = pp.out;
     a.prev_n_chains = pp.n;
     a.prev_blocks = pp.blocks;
     a.prev_tag = pp.tag;
     pp.on = false;
-  } else {
-    int frc = flush_pipe(c, pi);
-    if (frc) return frc;
   }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->timing == 1 || (c->timing == 2 && deferred && !c->win_open)) {
+  if (int rc = use_pipe(c, p.pipe)) return rc;
+  const int buf = pp.pbuf;
+  pp.pbuf ^= 1;
+  a.partials = pp.partials[buf];
+  if (p.sum == Sum::Own) {
+    a.fin_count = c->d_fin_count + (size_t)p.pipe * ABD_MAX_BATCH;
+    a.fin_out = rows;
+    a.fin_tag = seq + 1.0;
+    if (who.train) {
+      who.train->tag = seq + 1.0;
+      a.train = *who.train;
+    }
+  }
+  // timing 1: events around every launch; timing 2: the first stream-ordered launch after an abd_wait opens the window
+  const bool stream_ordered = who.kind == Caller::Stream;
+  hipEvent_t e1 = nullptr;
+  if (c->timing == 1 || (c->timing == 2 && stream_ordered && !c->win_open)) {
     if (c->ev_used == c->ev_pool.size()) {
       hipEvent_t a0, a1;
       HIP_TRY(hipEventCreate(&a0));
       HIP_TRY(hipEventCreate(&a1));
       c->ev_pool.emplace_back(a0, a1);
     }
-    e0 = c->ev_pool[c->ev_used].first;
-    e1 = c->ev_pool[c->ev_used].second;
-    if (c->timing == 1) c->ev_used++;
     // window mode: every pipe is idle here (the previous abd_wait joined and synchronised them), so the stream of
     // the window's first launch carries its start; the end is recorded by flush_ring once all pipes have joined
-    HIP_TRY(hipEventRecord(e0, pp.st));
+    HIP_TRY(hipEventRecord(c->ev_pool[c->ev_used].first, pp.st));
+    if (c->timing == 1) e1 = c->ev_pool[c->ev_used++].second;
     if (c->timing == 2) c->win_open = true;
   }
-  if (c->timing == 2 && deferred) c->win_launches++;
-  hipError_t le;
-  std::chrono::steady_clock::time_point lp0;
-  if (g_launch_profile.on) lp0 = std::chrono::steady_clock::now();
-  if (lanes)
-    le = c->storage == ABD_STORE_F32 ? launch_obs<float>(grad, grid, lds, pp.st, a)
-                                     : launch_obs<double>(grad, grid, lds, pp.st, a);
-  else if (c->dense)
-    le = c->storage == ABD_STORE_F32 ? launch_dense<float>(cpw, grad, grid, lds, pp.st, a, dense_xc(c, cpw))
-                                     : launch_dense<double>(cpw, grad, grid, lds, pp.st, a, dense_xc(c, cpw));
-  else
-    le = c->storage == ABD_STORE_F32 ? launch_sparse<float>(cpw, grad, grid, lds, pp.st, a)
-                                     : launch_sparse<double>(cpw, grad, grid, lds, pp.st, a);
-  if (g_launch_profile.on) {
-    g_launch_profile.eval_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - lp0).count();
-    g_launch_profile.evals++;
-  }
-  if (c->timing == 1) HIP_TRY(hipEventRecord(e1, pp.st));
+  if (c->timing == 2 && stream_ordered) c->win_launches++;
+  const bool f32 = c->storage == ABD_STORE_F32, xc = p.family == Family::Dense && dense_xc(c, p.cpw), wide = c->nt > ABD_MAXT;
+  const EvalKernel k = f32 ? (grad ? eval_kernel<float, true>(p.family, p.cpw, xc, wide) : eval_kernel<float, false>(p.family, p.cpw, xc, wide))
+                           : (grad ? eval_kernel<double, true>(p.family, p.cpw, xc, wide) : eval_kernel<double, false>(p.family, p.cpw, xc, wide));
+  const hipError_t le = profiled_launch(false, [&] { return launch_kernel(k, p.grid, dim3(ABD_BLOCK), p.lds, pp.st, a); });
+  if (e1) HIP_TRY(hipEventRecord(e1, pp.st));
   HIP_TRY(le);
   seq += 1.0;
-  if (fused_sum) return ABD_OK;
+  if (p.sum == Sum::Own) return ABD_OK;
   pp.on = true;
   pp.buf = buf;
   pp.n = n;
-  pp.blocks = blocks;
-  pp.out = d_out_rows;
+  pp.blocks = (int)p.grid.x;
+  pp.out = rows;
   pp.tag = seq;
-  if (!(c->dense && c->fuse_finalize)) return flush_pipe(c, pi);
-  return ABD_OK;
+  return p.sum == Sum::FinalizeNow ? flush_pipe(c, p.pipe) : ABD_OK;
 }
 
 int flush_ring(abd_ctx* c) {
@@ -359,8 +343,7 @@ int wait_slot(abd_ctx* c, int slot) {
   return ABD_OK;
 }
 
-int enqueue_slot(abd_ctx* c, int slot, int n, const int32_t* chains, const double* theta, bool grad, bool deferred,
-                 int force_pipe, double* seqp, bool sync_call) {
+int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* chains, const double* theta, bool grad) {
   if (slot < 0 || slot >= kSyncSlot + c->n_sync_slots) return fail(ABD_ERR_ARG, "result slot %d outside [0, %d)", slot, kResultSlots);
   int rc = check_chains(c, n, chains);
   if (rc) return rc;
@@ -374,45 +357,21 @@ int enqueue_slot(abd_ctx* c, int slot, int n, const int32_t* chains, const doubl
   for (int k = 0; k < n; ++k) r.host[(size_t)k] = prepare(theta + (size_t)k * ABD_N_THETA);
   // every result row lives in mapped host memory (one PCIe write of 16 doubles + tag per chain, ~3 us inside the kernel)
   double* rows = c->d_out + (size_t)slot * c->n_slots * ABD_NOUT;
-  r.tag_first = (seqp ? *seqp : c->seq) + 1.0;
-  if (deferred) c->pending_slots.push_back(slot);
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int m = std::min(ABD_MAX_BATCH, n - k0);
-    rc = enqueue_group(c, m, chains + k0, theta + (size_t)k0 * ABD_N_THETA, grad, rows + (size_t)k0 * ABD_NOUT, deferred, force_pipe,
-                       r.host.data() + k0, seqp, nullptr, sync_call);
-    if (!rc && force_pipe >= 0) rc = flush_pipe(c, force_pipe);  // a group's fixed-order sum follows on its own stream
-    if (rc) return rc;
-  }
+  r.tag_first = (who.seq ? *who.seq : c->seq) + 1.0;
+  if (who.kind == Caller::Stream) c->pending_slots.push_back(slot);
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
+    if ((rc = enqueue_group(c, who, std::min(ABD_MAX_BATCH, n - k0), chains + k0, r.host.data() + k0, grad, rows + (size_t)k0 * ABD_NOUT)))
+      return rc;
   return ABD_OK;
 }
 
-// One launch of a leapfrog train (abd_types.hpp: TrainArgs; abd_sampler.hip) for `chain` on pipe `pi`: the launch assembles
-// its own result and leaves it in t->rec under t->tag (set here); nothing is kept in the result slots.
-int enqueue_train_launch(abd_ctx* c, int chain, int pi, TrainArgs* t, const HostTerms& first_terms, double* seqp) {
-  const int32_t ch = chain;
-  return enqueue_group(c, 1, &ch, nullptr, true, c->d_out + (size_t)kSyncSlot * c->n_slots * ABD_NOUT, false, pi, &first_terms, seqp, t);
-}
-
 // ---- leapfrog-train launches of dense cohorts (abd_train.hpp; abd_sampler.hip) ----
-template <typename R, int CB>
-hipError_t launch_train_cb(bool xc, dim3 grid, size_t lds, hipStream_t st, const DenseTrainArgs& a) {
-  auto go = [&](auto kernel) -> hipError_t {
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(ABD_BLOCK), lds, st, a);
-    return hipGetLastError();
-  };
-  return xc ? go(abd_train_kernel<R, CB, true>) : go(abd_train_kernel<R, CB, false>);
-}
+using TrainKernel = void (*)(const DenseTrainArgs);
 template <typename R>
-hipError_t launch_train(int cb, bool xc, dim3 grid, size_t lds, hipStream_t st, const DenseTrainArgs& a) {
-  switch (cb) {
-    case 4: return launch_train_cb<R, 4>(xc, grid, lds, st, a);
-    case 2: return launch_train_cb<R, 2>(xc, grid, lds, st, a);
-    default: return launch_train_cb<R, 1>(xc, grid, lds, st, a);
-  }
+TrainKernel train_kernel(int cb, bool xc) {
+  if (cb == 4) return xc ? abd_train_kernel<R, 4, true> : abd_train_kernel<R, 4, false>;
+  if (cb == 2) return xc ? abd_train_kernel<R, 2, true> : abd_train_kernel<R, 2, false>;
+  return xc ? abd_train_kernel<R, 1, true> : abd_train_kernel<R, 1, false>;
 }
 
 // Queue one launch of a train unit of cb (1, 2 or 4) chains on pipe pi: a->tc[0 .. cb) filled by the caller, everything
@@ -451,12 +410,9 @@ int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* 
   a->n_dict_s = c->s.n_dict;
   a->vw = c->vw;
   a->exp2_tab = c->exp2_tab;
-  abd_ctx::Pipe& pp = c->pipe[pi];
-  if (pp.on)
-    if (int frc = flush_pipe(c, pi)) return frc;  // (a pending fixed-order sum of an earlier plain launch on this stream)
-  if (pi > 0) pp.busy = true;
-  a->partials = pp.partials[0];
-  a->fin_count = c->d_train_count + (size_t)pi * ABD_MAX_BATCH * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE;
+  if (int rc = use_pipe(c, pi)) return rc;
+  a->partials = c->pipe[pi].partials[0];
+  a->fin_count = c->d_train_count + (size_t)pi * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE;
   if ((int64_t)cb * (blocks + ABD_TRAIN_SHARDS) > (int64_t)c->n_slots * c->blocks_max)
     return fail(ABD_ERR_STATE, "internal: train launch of %d x %d workgroups exceeds the partial rows", cb, blocks);
   a->prior_const = c->prior_const;
@@ -478,13 +434,8 @@ int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* 
   range_split(c, blocks, ABD_WAVES_PER_BLOCK / cb, *a, false);
   const size_t lds = abd_dense_lds(c->G, cb, xc, true);
   dim3 grid(blocks + a->service, 1);
-  std::chrono::steady_clock::time_point lp0;
-  if (g_launch_profile.on) lp0 = std::chrono::steady_clock::now();
-  const hipError_t le = c->storage == ABD_STORE_F32 ? launch_train<float>(cb, xc, grid, lds, pp.st, *a) : launch_train<double>(cb, xc, grid, lds, pp.st, *a);
-  if (g_launch_profile.on) {
-    g_launch_profile.eval_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - lp0).count();
-    g_launch_profile.evals++;
-  }
+  const TrainKernel k = c->storage == ABD_STORE_F32 ? train_kernel<float>(cb, xc) : train_kernel<double>(cb, xc);
+  const hipError_t le = profiled_launch(false, [&] { return launch_kernel(k, grid, dim3(ABD_BLOCK), lds, c->pipe[pi].st, *a); });
   HIP_TRY(le);
   return ABD_OK;
 }
@@ -568,9 +519,18 @@ int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st,
     lds = (size_t)2 * (c->G + 1) * sizeof(double2_t);
     blocks = w.bn + w.bs;
   }
-  hipLaunchKernelGGL(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w));
   return ABD_OK;
+}
+
+// A synchronous call: whatever was queued stream-ordered before it is summed and joined first (flush_ring), then the
+// evaluation of n chains (logp and, with grad non-null, the gradient) on pipe 0, its rows awaited and assembled
+int eval_sync(abd_ctx* c, int n, const int32_t* chains, const double* theta, double* logp, double* grad, bool with_priors = true) {
+  if (int rc = flush_ring(c)) return rc;
+  if (int rc = enqueue_slot(c, Caller{Caller::Sync}, kSyncSlot, n, chains, theta, grad != nullptr)) return rc;
+  if (int rc = flush_pending(c)) return rc;  // (the sum of the last group follows right away)
+  if (int rc = wait_rows(c, kSyncSlot, n, c->seq)) return rc;
+  return fetch_slot(c, kSyncSlot, logp, grad, with_priors);
 }
 
 }  // namespace abdi
@@ -606,7 +566,7 @@ int abd_n_result_slots(abd_ctx*) { return kResultSlots; }
 int abd_logp_dlogp_batch_enqueue(abd_ctx* c, int32_t slot, int32_t n, const int32_t* chains, const double* theta) {
   if (!c || !chains || !theta) return fail(ABD_ERR_ARG, "NULL argument");
   if (slot < 0 || slot >= kResultSlots) return fail(ABD_ERR_ARG, "result slot %d outside [0, %d)", slot, kResultSlots);
-  return enqueue_slot(c, slot, n, chains, theta, true, true);
+  return enqueue_slot(c, Caller{Caller::Stream}, slot, n, chains, theta, true);
 }
 
 int abd_wait(abd_ctx* c) {
@@ -649,7 +609,7 @@ int abd_logp_dlogp_many(abd_ctx* c, int32_t n_steps, int32_t n, const int32_t* c
     const int s1 = std::min(n_steps, s0 + kResultSlots);
     for (int k = s0; k < s1; ++k) {
       c->steps_behind = n_steps - 1 - k;
-      const int rc = enqueue_slot(c, k - s0, n, chains, theta + (size_t)k * per_step, grad != nullptr, true);
+      const int rc = enqueue_slot(c, Caller{Caller::Stream}, k - s0, n, chains, theta + (size_t)k * per_step, grad != nullptr);
       c->steps_behind = -1;
       if (rc) return rc;
     }
@@ -668,12 +628,7 @@ int abd_logp_dlogp_many(abd_ctx* c, int32_t n_steps, int32_t n, const int32_t* c
 
 int abd_logp_dlogp_batch(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, double* logp, double* grad) {
   if (!c || !chains || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
-  if (int frc = flush_ring(c)) return frc;
-  int rc = enqueue_slot(c, kSyncSlot, n, chains, theta, true, false, -1, nullptr, true);
-  if (rc) return rc;
-  if (int prc = flush_pending(c)) return prc;  // (a launch that did not sum its own rows: the sum follows right away)
-  if (int wrc = wait_rows(c, kSyncSlot, c->results[kSyncSlot].n, c->seq)) return wrc;
-  return fetch_slot(c, kSyncSlot, logp, grad);
+  return eval_sync(c, n, chains, theta, logp, grad);
 }
 
 int abd_logp_dlogp(abd_ctx* c, int32_t chain, const double* theta, double* logp, double* grad) {
@@ -682,21 +637,14 @@ int abd_logp_dlogp(abd_ctx* c, int32_t chain, const double* theta, double* logp,
 
 int abd_loglik_dlogp(abd_ctx* c, int32_t chain, const double* theta, double* loglik, double* grad) {
   if (!c || !theta || !loglik || !grad) return fail(ABD_ERR_ARG, "NULL argument");
-  int rc = enqueue_slot(c, kSyncSlot, 1, &chain, theta, true, false, -1, nullptr, true);
-  if (rc) return rc;
-  if (int prc = flush_pending(c)) return prc;
-  if (int wrc = wait_rows(c, kSyncSlot, c->results[kSyncSlot].n, c->seq)) return wrc;
-  return fetch_slot(c, kSyncSlot, loglik, grad, false);
+  return eval_sync(c, 1, &chain, theta, loglik, grad, false);
 }
 
 int abd_logp(abd_ctx* c, int32_t chain, const double* theta, double* logp) {
   if (!c || !theta || !logp) return fail(ABD_ERR_ARG, "NULL argument");
-  int rc = enqueue_slot(c, kSyncSlot, 1, &chain, theta, false, false, -1, nullptr, true);
-  if (rc) return rc;
-  if (int prc = flush_pending(c)) return prc;
-  if (int wrc = wait_rows(c, kSyncSlot, c->results[kSyncSlot].n, c->seq)) return wrc;
-  return fetch_slot(c, kSyncSlot, logp, nullptr);
+  return eval_sync(c, 1, &chain, theta, logp, nullptr);
 }
+
 int abd_kernel_timing(abd_ctx* c, int32_t mode) {
   if (!c) return fail(ABD_ERR_ARG, "ctx is NULL");
   if (mode < 0 || mode > 2) return fail(ABD_ERR_ARG, "timing mode %d outside {0, 1, 2}", mode);

@@ -6,21 +6,19 @@
 
 namespace abdi {
 
-// the wave-per-proposal sweep kernel for 4 or 8 words per individual (<= 256 / <= 512 gaps); observation lists of at most 64
-// gaps -- the reference's own cohorts have 26 and 31 -- get a one-word instantiation: this kernel holds the individual's packed
-// rows in scalar registers, and with one word instead of four they fit (no spills; profiles/r04)
-template <typename R, bool DENSE>
-void launch_gibbs_v1(int nt, dim3 grid, size_t lds, hipStream_t st, const GibbsArgs& ga) {
-  if constexpr (!DENSE) {
-    if (nt == 1) {
-      hipLaunchKernelGGL((abd_gibbs_kernel<R, DENSE, 1>), grid, dim3(ABD_BLOCK), lds, st, ga);
-      return;
-    }
-  }
-  if (nt > ABD_MAXT)
-    hipLaunchKernelGGL((abd_gibbs_kernel<R, DENSE, ABD_MAXT_MAX>), grid, dim3(ABD_BLOCK), lds, st, ga);
-  else
-    hipLaunchKernelGGL((abd_gibbs_kernel<R, DENSE, ABD_MAXT>), grid, dim3(ABD_BLOCK), lds, st, ga);
+using GibbsKernel = void (*)(const GibbsArgs);
+// lanes = proposals (abd_gibbs2.hpp; `stats`: the variant with the scheduler's development counters), or the wave-per-proposal
+// kernel for 4 or 8 words per individual (<= 256 / <= 512 gaps); observation lists of at most 64 gaps -- the reference's own
+// cohorts have 26 and 31 -- get a one-word instantiation of it: it holds the individual's packed rows in scalar registers, and
+// with one word instead of four they fit (no spills; profiles/r04)
+template <typename R>
+GibbsKernel gibbs_kernel(const abd_ctx* c, bool lanes, bool stats) {
+  const bool wide = c->nt > ABD_MAXT;
+  if (lanes && stats) return wide ? abd_gibbs_dense_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, true, ABD_MAXT>;
+  if (lanes) return wide ? abd_gibbs_dense_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, false, ABD_MAXT>;
+  if (c->dense) return wide ? abd_gibbs_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_kernel<R, true, ABD_MAXT>;
+  if (c->nt == 1) return abd_gibbs_kernel<R, false, 1>;
+  return wide ? abd_gibbs_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_kernel<R, false, ABD_MAXT>;
 }
 
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
@@ -57,49 +55,22 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
   // beside it (12 waves x 168 registers fill the CU's register file); the sweep itself 0.39 -> 0.41 ms, the compound
   // iteration of 4 chains at config 3 6.17 -> 5.90 ms.  Trajectories do not depend on the launch shape.
   if (m == 1) nw2 = std::max(4, std::min(nw2, tune_int("ABD_G2_WAVES_ONE", 8)));
-  if (c->dense && !c->gibbs_v1 && nw2 >= 4) {  // (4 or 8 words per individual: <= 256 / <= 512 gaps)
-    // lanes = proposals (abd_gibbs2.hpp): one workgroup per CU, the individuals of a chain handed out from one queue
-    // per chain
-    const size_t lds2 = abd_g2_lds(c->G, rbytes, nw2);
+  const bool lanes = c->dense && !c->gibbs_v1 && nw2 >= 4;  // (4 or 8 words per individual: <= 256 / <= 512 gaps)
+  dim3 grid, block(ABD_BLOCK);
+  size_t lds;
+  if (lanes) {
+    // one workgroup per CU, the individuals of a chain handed out from one queue per chain
+    lds = abd_g2_lds(c->G, rbytes, nw2);
     HIP_TRY(hipMemsetAsync(work_dev, 0, (size_t)m * sizeof(unsigned int), st));
-    const int bx = std::max(1, std::min(c->n_cu / m, (c->N + nw2 - 1) / nw2));
-    dim3 grid2(bx, m);
-    auto launch2 = [&](auto kernel) -> hipError_t {
-      if (lds2 > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e != hipSuccess) return e;
-      }
-      hipLaunchKernelGGL(kernel, grid2, dim3(64 * nw2), lds2, st, ga);
-      return hipSuccess;
-    };
-    const bool f32 = c->storage == ABD_STORE_F32;
-    if (c->nt > ABD_MAXT) {
-      if (stats_dev)  // ABD_GIBBS_STATS=1: the variant with the scheduler's development counters
-        HIP_TRY(f32 ? launch2(abd_gibbs_dense_kernel<float, true, ABD_MAXT_MAX>) : launch2(abd_gibbs_dense_kernel<double, true, ABD_MAXT_MAX>));
-      else
-        HIP_TRY(f32 ? launch2(abd_gibbs_dense_kernel<float, false, ABD_MAXT_MAX>) : launch2(abd_gibbs_dense_kernel<double, false, ABD_MAXT_MAX>));
-    } else if (stats_dev) {
-      HIP_TRY(f32 ? launch2(abd_gibbs_dense_kernel<float, true, ABD_MAXT>) : launch2(abd_gibbs_dense_kernel<double, true, ABD_MAXT>));
-    } else {
-      HIP_TRY(f32 ? launch2(abd_gibbs_dense_kernel<float, false, ABD_MAXT>) : launch2(abd_gibbs_dense_kernel<double, false, ABD_MAXT>));
-    }
+    grid = dim3(std::max(1, std::min(c->n_cu / m, (c->N + nw2 - 1) / nw2)), m);
+    block = dim3(64 * nw2);
   } else {
-    const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
-    const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)ABD_WAVES_PER_BLOCK * abd_gibbs_wave_lds(c->G);
-    dim3 grid(blocks, m);
-    if (c->dense) {
-      if (c->storage == ABD_STORE_F32)
-        launch_gibbs_v1<float, true>(c->nt, grid, lds, st, ga);
-      else
-        launch_gibbs_v1<double, true>(c->nt, grid, lds, st, ga);
-    } else {
-      if (c->storage == ABD_STORE_F32)
-        launch_gibbs_v1<float, false>(c->nt, grid, lds, st, ga);
-      else
-        launch_gibbs_v1<double, false>(c->nt, grid, lds, st, ga);
-    }
+    grid = dim3(std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8)), m);
+    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)ABD_WAVES_PER_BLOCK * abd_gibbs_wave_lds(c->G);
   }
-  HIP_TRY(hipGetLastError());
+  const bool stats = stats_dev != nullptr;  // ABD_GIBBS_STATS=1
+  const GibbsKernel k = c->storage == ABD_STORE_F32 ? gibbs_kernel<float>(c, lanes, stats) : gibbs_kernel<double>(c, lanes, stats);
+  HIP_TRY(launch_kernel(k, grid, block, lds, st, ga));
   return ABD_OK;
 }
 

@@ -70,6 +70,46 @@ struct LaunchProfile {
 };
 extern LaunchProfile g_launch_profile;
 
+// Launch `kernel` with `lds` bytes of dynamic LDS (beyond 64 KiB the kernel has to be allowed them first); the launch's error.
+template <typename K, typename... A>
+hipError_t launch_kernel(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  if (lds > 64 * 1024)
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
+      return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  return hipGetLastError();
+}
+
+// run `launch` (a launch_kernel call); with ABD_SAMPLER_PROFILE on, its host time goes to the sums' or the evaluations' account
+template <typename F>
+hipError_t profiled_launch(bool sum, F&& launch) {
+  if (!g_launch_profile.on) return launch();
+  const auto t0 = std::chrono::steady_clock::now();
+  const hipError_t e = launch();
+  const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (sum) {
+    g_launch_profile.sum_s += s;
+    g_launch_profile.sums++;
+  } else {
+    g_launch_profile.eval_s += s;
+    g_launch_profile.evals++;
+  }
+  return e;
+}
+
+// Who queues an evaluation launch (abd_eval.hip: plan_launch decides everything else from it and the number of chains)
+struct Caller {
+  enum Kind {
+    Stream,  // stream-ordered (abd_logp_dlogp_batch_enqueue, abd_logp_dlogp_many): dense launches rotate over the pipes
+    Sync,    // a synchronous call: pipe 0, behind everything queued before it
+    Unit,    // a native-sampler unit: its own pipe, never joined with the others (units may be driven by several host threads)
+    Train,   // one launch of an observation-list leapfrog train (TrainArgs), on its unit's pipe
+  } kind;
+  int pipe = 0;                // Unit, Train
+  double* seq = nullptr;       // Unit, Train: the unit's own completion-tag sequence (nullptr: the context's)
+  TrainArgs* train = nullptr;  // Train
+};
+
 struct AntigenDev {
   int64_t K = 0;
   void* y = nullptr;       // sparse: R[K], sorted by (ind, gap)
@@ -134,10 +174,11 @@ struct abd_ctx {
   double* exp2_tab = nullptr;  // dense cohorts: 2^(j/1024) (abd_dense.hpp)
   int8_t* stage_gn = nullptr;  // (G, N) upload staging for i_raw
   std::vector<ChainSlot> slots;
-  // A pipe = a HIP stream with its own pair of partial buffers and its own pending fixed-order sum.  Pipe 0 is
-  // the context's stream (everything synchronous runs there).  Stream-ordered dense launches alternate between
-  // pipe 0 and pipe 1: launch k+2 sums launch k's partials (same pipe), so the two streams never wait for each
-  // other and the head of one launch overlaps the tail of the previous one.
+  // A pipe = a HIP stream with its own pair of partial buffers and at most one Pending fixed-order sum (abd_eval.hip:
+  // plan_launch names who sums a launch's partial rows: Pending, FinalizeNow or Own).  Pipe 0 is the context's stream
+  // (everything synchronous runs there).  Stream-ordered dense launches rotate over n_pipes pipes: the next launch on
+  // the same pipe sums a launch's partials in its first workgroups, so the streams never wait for each other and the
+  // head of one launch overlaps the tail of the previous one.
   struct Pipe {
     hipStream_t st = nullptr;
     double* partials[2] = {nullptr, nullptr};  // [n_slots][blocks_max][ABD_NOUT], alternating per launch
@@ -152,20 +193,18 @@ struct abd_ctx {
   int n_streams = kMaxPipes;  // pipes that exist (the native sampler gives every chain a stream: chain k -> pipe k mod 8)
   int n_sync_slots = 4;   // private result rows of synchronous calls (slot kSyncSlot) and of the sampler's chains in flight
   int pipe_blocks = 0;    // dense grid of a launch that shares the chip with n_pipes - 1 others
-  int group_blocks = 0;   // dense grid of one of the sampler's chain groups in flight (set by abd_sampler_create)
+  int group_blocks = 0;   // dense grid of a sampler unit's launch: one workgroup per CU, whatever the number of units
   int dbpc = 4;           // dense kernel: workgroups per CU of a launch that has the chip to itself
   int next_pipe = 0;
   hipEvent_t join_ev[kMaxPipes] = {};
   double seq = 0.0;  // completion tags: 1, 2, 3, ... (exact in a double)
-  bool fuse_finalize = true;
   // A sampler unit's dense launch sums its own partial rows (abd_dense.hpp; ABD_DENSE_OWN_SUM=0: second launch).  Same
   // bits; the result arrives 2-2.7 us later than from the pre-queued second launch, but the host spends 3.6 instead of
   // 7.2 us per result: config 3, evaluations/s seen by NUTS 33.6 k -> 36.9 k (1 chain), 53 k -> 59 k (8), 77 k -> 88 k (16),
   // unchanged with 4
   bool dense_own_sum = true;
   unsigned int* d_fin_count = nullptr;  // [kMaxPipes][ABD_MAX_BATCH] zeroed counters of that sum
-  unsigned int* d_train_count = nullptr;  // [kMaxPipes][ABD_MAX_BATCH][1 + ABD_TRAIN_SHARDS][ABD_TRAIN_CNT_STRIDE] zeroed counters of the two-level count-in (abd_dense.hpp: train launches use row 0 of their pipe, synchronous calls one row per grid row)
-  bool sync_own_sum = false;  // tuning build only: a synchronous call's dense launch sums its own partial rows (measured slower than the second launch)
+  unsigned int* d_train_count = nullptr;  // [kMaxPipes][1 + ABD_TRAIN_SHARDS][ABD_TRAIN_CNT_STRIDE] zeroed counters of a dense train launch's count-in (abd_dense.hpp)
   uint32_t ind_offset = 0;  // global index of this context's first individual (Gibbs random streams)
   bool xcd_remap = true;
   int fin_rows = 2;
@@ -231,10 +270,11 @@ int join_pipes(abd_ctx* c);
 int flush_pending(abd_ctx* c);
 int flush_ring(abd_ctx* c);
 int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st = nullptr);
-int enqueue_slot(abd_ctx* c, int slot, int n, const int32_t* chains, const double* theta, bool grad, bool deferred = false,
-                 int force_pipe = -1, double* seqp = nullptr, bool sync_call = false);
+// queue the evaluation of n chains at theta into result slot `slot` (groups of <= ABD_MAX_BATCH chains, one launch each)
+int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* chains, const double* theta, bool grad);
+// one launch of n <= ABD_MAX_BATCH chains whose host terms are ready; its sums go to rows[0 .. n)
+int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows);
 int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_priors = true);
-int enqueue_train_launch(abd_ctx* c, int chain, int pi, TrainArgs* t, const HostTerms& first_terms, double* seqp = nullptr);
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a);
 int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1);
 

@@ -178,7 +178,9 @@ int train_launch(abd_sampler* s, int u, const double* theta, const double* p_hal
     }
   }
   // (units driven by their own host threads tag their launches from their own sequence: abd_host.hpp, unit_seq)
-  if (int rc = enqueue_train_launch(c, s->chains[(size_t)u], unit_pipe(c, u), &ta, ht, s->unit_tags ? &c->unit_seq[(size_t)u] : nullptr)) return rc;
+  // (the launch assembles its own result and leaves it in ta.rec under ta.tag, set by enqueue_group: no result rows)
+  const Caller who{Caller::Train, unit_pipe(c, u), s->unit_tags ? &c->unit_seq[(size_t)u] : nullptr, &ta};
+  if (int rc = enqueue_group(c, who, 1, &s->chains[(size_t)u], &ht, true, nullptr)) return rc;
   t.tags[t.prod % abd_sampler::kTrainRing] = ta.tag;
   t.prod += 1;
   t.next_slot = ta.next_slot;
@@ -273,10 +275,6 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
   s->unit = std::max(1, std::min({s->unit, n, (int)ABD_MAX_BATCH}));
   if (s->dtrains && s->unit != 1 && s->unit != 2 && s->unit != 4) s->dtrains = false;  // (a train unit is a workgroup's waves)
 
-  // several units' launches are in flight: one workgroup per CU each, whatever the number of units -- a unit's numbers
-  // must not depend on it
-  c->group_blocks = std::min(c->dense_blocks, c->n_cu);
-  if (const int gb = tune_int("ABD_GROUP_BLOCKS_PER_CU", 0)) c->group_blocks = std::max(1, std::min(c->n_cu * gb, c->blocks_max));
   // the starting points through the launch shape the units will use
   rc = hipSetDevice(c->device) == hipSuccess ? flush_ring(c) : fail(ABD_ERR_HIP, "hipSetDevice failed");
   if (!rc && (n + s->unit - 1) / s->unit > 1 && tune_int("ABD_PROBE_QUEUES", 1) != 0) rc = probe_stream_queues(c);
@@ -325,7 +323,7 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
       }
       continue;
     }
-    rc = enqueue_slot(c, kSyncSlot + u, m, chains + lo, theta0 + (size_t)lo * ABD_N_THETA, true, false, unit_pipe(c, u));
+    rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u)}, kSyncSlot + u, m, chains + lo, theta0 + (size_t)lo * ABD_N_THETA, true);
     if (!rc) rc = wait_rows(c, kSyncSlot + u, m, c->seq, c->pipe[unit_pipe(c, u)].st);
     if (!rc) rc = fetch_slot(c, kSyncSlot + u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA);
   }
@@ -519,7 +517,7 @@ int sampler_run_units(RunFrame& f) {
       return train_launch(s, u, un.th.data(), nullptr, 0.0, s->ch[(size_t)u].nuts.inv_mass, true);
     }
     double* seqp = T_all > 1 ? &c->unit_seq[(size_t)u] : nullptr;
-    int rc = enqueue_slot(c, kSyncSlot + u, un.m, un.ids.data(), un.th.data(), true, false, unit_pipe(c, u), seqp);
+    int rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u), seqp}, kSyncSlot + u, un.m, un.ids.data(), un.th.data(), true);
     if (rc) return rc;
     un.tag = seqp ? *seqp : c->seq;
     un.t_queued = std::chrono::steady_clock::now();

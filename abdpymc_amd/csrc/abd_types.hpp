@@ -222,10 +222,10 @@ struct EvalArgs {
   int32_t fin_rows;    // gap rows the finalizing workgroups are excused from
   int32_t xcd_remap;   // dense kernel: workgroup -> range mapping that keeps neighbouring ranges on one XCD
   double prev_tag;          // completion tag of the previous launch (see finalize_chain)
-  // observation-lane kernel: the workgroup of a chain that finishes last sums that chain's partial rows itself
-  // (abd_obs.hpp) -- one launch per evaluation instead of two.  fin_count: one zeroed counter per grid row.
+  // a launch that sums its own rows (abd_eval.hip: Sum::Own -- a sampler unit's dense launch, an observation-list train
+  // launch): the workgroup of a chain that counts in last sums that chain's partial rows itself, one launch per evaluation
+  // instead of two.  fin_count: one zeroed counter per chain (nullptr: the sum is another launch's).
   unsigned int* fin_count;
-  unsigned int* fin_count2;  // dense kernel, a grid of more than ABD_TRAIN_ONE_LEVEL workgroups: counters of the two-level count-in, one set per grid row (abd_dense.hpp: two_level_sums)
   double* fin_out;
   double fin_tag;
   int32_t G, N, nt, n_chunks;

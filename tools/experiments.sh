@@ -8,7 +8,6 @@
 #   train_grid     workgroups per CU of a one-chain train launch, 1 / 2 / 4 chains
 #   handoff        the own-sum hand-off as shipped against the release/acquire forms (-DABD_HANDOFF_FORMAL=1 / 2):
 #                  python tools/build_variant.py formal1 -DABD_HANDOFF_FORMAL=1; ... formal2 -DABD_HANDOFF_FORMAL=2
-#   sync_own_sum   a synchronous call's launch summing its own rows against the second launch (ABD_SYNC_OWN_SUM)
 #   sweep_knobs    scheduler constants of the lane-per-proposal sweep kernel
 #   sweep_ab       the sweep of the library in the tree against another build (LIB_B=path; product libraries, no tuning build)
 set -e
@@ -45,9 +44,6 @@ handoff)
     echo -n "$(basename $lib) default cohort: "; ABD_HIP_LIB=$lib nuts default 4 300
     echo -n "$(basename $lib) bench: "; ABD_HIP_LIB=$lib python3 bench.py --full --no-cpu-baseline --no-sampler --no-other-configs --steps 200 | line
   done ;;
-sync_own_sum)
-  export ABD_HIP_LIB=$T
-  for v in 0 1; do echo "ABD_SYNC_OWN_SUM=$v"; ABD_SYNC_OWN_SUM=$v python3 tools/probe_sync_latency.py; done ;;
 sweep_knobs)
   export ABD_HIP_LIB=$T
   for st in truth random; do
