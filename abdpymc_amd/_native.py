@@ -78,6 +78,8 @@ class _Record(C.Structure):
         ("ab_s_mu", C.POINTER(C.c_double)),
         ("ll_s", C.POINTER(C.c_double)),
         ("ll_n", C.POINTER(C.c_double)),
+        ("yrep_s", C.POINTER(C.c_double)),
+        ("yrep_n", C.POINTER(C.c_double)),
     ]
 
 
@@ -116,6 +118,7 @@ SYMBOLS = {
     "abd_logp_dlogp_many": (C.c_int, [_P, C.c_int32, C.c_int32, _I32, _D, _D, _D]),
     "abd_deterministics": (C.c_int, [_P, C.c_int32, _D, _I8, _D, _D]),
     "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
+    "abd_posterior_predictive": (C.c_int, [_P, C.c_int32, _D, C.c_uint64, C.c_uint32, C.c_uint64, _D, _D, _D, _D]),
     "abd_sampler_create": (C.c_int, [_P, C.c_int32, _I32, _D, C.POINTER(_SamplerOpts), C.POINTER(_P)]),
     "abd_sampler_destroy": (None, [_P]),
     "abd_sampler_run": (C.c_int, [_P, C.c_int64, _D, _D]),
@@ -124,6 +127,8 @@ SYMBOLS = {
     "abd_sampler_means": (C.c_int, [_P, C.c_int32, _D, _D, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_pointwise": (C.c_int, [_P, C.c_int32]),
     "abd_sampler_pointwise_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_predictive": (C.c_int, [_P, C.c_int32]),
+    "abd_sampler_predictive_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
@@ -477,6 +482,22 @@ class Context:
                                                          _ptr(ll_n, C.c_double)))
         return ll_s, ll_n
 
+    def posterior_predictive(self, chain: int, theta, seed: int = 0, stream: int = 0, draw: int = 0, mean: bool = False):
+        """Posterior predictive replicate of every OD reading at (theta, the chain slot's discrete state) -> (yrep_s, yrep_n),
+        each in the order the readings were given; ``mean=True`` adds the noise-free means (m_s, m_n).  The normals are keyed
+        by (seed, stream, draw) and the reading (abd_hip.h: abd_posterior_predictive): the native sampler's recorded replicate
+        of chain c at iteration t is ``posterior_predictive(.., seed, chain_offset + c, t)``."""
+        t = _as(theta, np.float64)
+        if t.shape != (N_THETA,):
+            raise ValueError(f"theta must have shape ({N_THETA},)")
+        y_s, y_n = np.empty(self.n_obs_s), np.empty(self.n_obs_n)
+        m_s, m_n = (np.empty(self.n_obs_s), np.empty(self.n_obs_n)) if mean else (None, None)
+        _check(self._lib, self._lib.abd_posterior_predictive(
+            self._h, int(chain), _ptr(t, C.c_double), C.c_uint64(int(seed) & (2**64 - 1)), C.c_uint32(int(stream) & 0xFFFFFFFF),
+            C.c_uint64(int(draw) & (2**64 - 1)), _ptr(y_s, C.c_double), _ptr(y_n, C.c_double),
+            None if m_s is None else _ptr(m_s, C.c_double), None if m_n is None else _ptr(m_n, C.c_double)))
+        return (y_s, y_n, m_s, m_n) if mean else (y_s, y_n)
+
     def theta_prior(self, theta):
         """The theta-only part of the joint logp (continuous priors + Jacobians) and its gradient."""
         t = _as(theta, np.float64)
@@ -492,12 +513,13 @@ class Context:
 
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
-                dense_metric: bool = False, pointwise: bool = False) -> "NativeSampler":
+                dense_metric: bool = False, pointwise: bool = False, predictive: bool = False) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
         independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
-        pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``)."""
+        pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
+        the posterior predictive check statistics (``NativeSampler.predictive_stats``)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise)
+                             dense_metric, pointwise, predictive)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -576,7 +598,7 @@ class NativeSampler:
     per leapfrog of a unit of 1-4 chains, leapfrog trains (abd_hip.h)."""
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
-                 chain_offset=0, dense_metric=False, pointwise=False):
+                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -597,6 +619,8 @@ class NativeSampler:
         ctx._samplers.add(self)
         if pointwise:
             _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
+        if predictive:
+            _check(self._lib, self._lib.abd_sampler_enable_predictive(self._h, 1))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -607,12 +631,14 @@ class NativeSampler:
         return theta, {name: stats[:, :, k].copy() for k, name in enumerate(STAT_NAMES)}
 
     def run_record(self, n_iter: int, first: int, i_raw=None, ab_s_waner=None, i=None, ab_n_mu=None, ab_s_mu=None, thin: int = 1,
-                   ll_s=None, ll_n=None):
+                   ll_s=None, ll_n=None, yrep_s=None, yrep_n=None):
         """
         run() that also writes every iteration's discrete state / Deterministics of every chain into the given
         C-contiguous arrays of shape (n, capacity, G, N) (int8 for i_raw and i, float64 for the two mu) and
         (n, capacity, N) int8 for ab_s_waner, at draws first .. first + n_iter - 1; ``ll_s`` / ``ll_n`` (n, capacity, K)
-        float64 receive the pointwise log-likelihood of the readings (``Context.pointwise_loglik``).  thin = K > 1: only iterations
+        float64 receive the pointwise log-likelihood of the readings (``Context.pointwise_loglik``), ``yrep_s`` / ``yrep_n`` their
+        posterior predictive replicates (``Context.posterior_predictive`` keyed by the sampler's seed, the chain's global id and
+        the iteration).  thin = K > 1: only iterations
         0, K, 2K, ... of the call are written, at draws first, first + 1, ... (ceil(n_iter / K) of them).
         """
         if thin < 1:
@@ -624,7 +650,9 @@ class NativeSampler:
                                     ("i", i, np.int8, (G, N)), ("ab_n_mu", ab_n_mu, np.float64, (G, N)),
                                     ("ab_s_mu", ab_s_mu, np.float64, (G, N)),
                                     ("ll_s", ll_s, np.float64, (self._ctx.n_obs_s,)),
-                                    ("ll_n", ll_n, np.float64, (self._ctx.n_obs_n,))):
+                                    ("ll_n", ll_n, np.float64, (self._ctx.n_obs_n,)),
+                                    ("yrep_s", yrep_s, np.float64, (self._ctx.n_obs_s,)),
+                                    ("yrep_n", yrep_n, np.float64, (self._ctx.n_obs_n,))):
             if arr is None:
                 continue
             if arr.dtype != dt or not arr.flags.c_contiguous or not arr.flags.writeable or arr.shape[0] != self.n or arr.shape[2:] != tail:
@@ -655,6 +683,15 @@ class NativeSampler:
         out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
         n = C.c_int64()
         _check(self._lib, self._lib.abd_sampler_pointwise_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
+        return out, n.value
+
+    def predictive_stats(self, k: int):
+        """Posterior predictive check statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S
+        readings then N in the caller's order; rows mean and sum of squared deviations of the predictive mean, mean tail
+        probability P(y_rep <= y) (predictive.merge)."""
+        out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_predictive_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
         return out, n.value
 
     def adaptation(self, k: int):

@@ -44,10 +44,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "report WAIC (elpd_waic, p_waic, se; per reading elpd_waic_i / p_waic_i in the output).", action="store_true")
     parser.add_argument("--log_likelihood", help="Record the pointwise log-likelihood of every OD reading at the recorded (thinned) "
                         "draws: ArviZ group log_likelihood (it_s_lik, it_n_lik), as pm.compute_log_likelihood.", action="store_true")
+    parser.add_argument("--posterior_predictive", help="Record a posterior predictive replicate of every OD reading at the recorded "
+                        "(thinned) draws: ArviZ groups posterior_predictive (it_s_lik, it_n_lik), as pm.sample_posterior_predictive, "
+                        "and observed_data.", action="store_true")
+    parser.add_argument("--ppc", help="Accumulate a posterior predictive check of the OD readings on the device over all draws and "
+                        "report per antigen the readings with an extreme tail probability p = P(y_rep <= y | y) (per reading "
+                        "ppc_p_it_s_lik / ppc_p_it_n_lik in the output).", action="store_true")
     return parser
 
 
 WAIC_KEYS = ("elpd_waic_i_it_s_lik", "elpd_waic_i_it_n_lik", "p_waic_i_it_s_lik", "p_waic_i_it_n_lik")
+PPC_KEYS = ("ppc_p_it_s_lik", "ppc_p_it_n_lik")
 
 
 def add_waic(res: dict) -> dict:
@@ -61,6 +68,22 @@ def add_waic(res: dict) -> dict:
     return w
 
 
+def add_ppc(res: dict) -> dict:
+    """predictive.summary of a gathered ``ppc=True`` result: the tail probability of every reading goes into ``res`` (keys
+    PPC_KEYS), the summary is returned."""
+    from . import predictive
+
+    sm = predictive.summary(res)
+    res["ppc_p_it_s_lik"], res["ppc_p_it_n_lik"] = sm["it_s_lik"]["p"], sm["it_n_lik"]["p"]
+    return sm
+
+
+def add_observed(res: dict, data) -> None:
+    """The observed ODs of both antigens (no chain axis: added on the rank that writes, after any gather)."""
+    res["observed_data_it_s_lik"] = np.asarray(data.s.obs[3], dtype=np.float64)
+    res["observed_data_it_n_lik"] = np.asarray(data.n.obs[3], dtype=np.float64)
+
+
 def write_posterior(res: dict, path: str, coords: dict) -> str:
     try:
         import arviz as az  # noqa: F401
@@ -72,14 +95,20 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "ab_s_waner": ["ind"], "mean_i": ["chain", "gap", "ind"], "mean_ab_n_mu": ["chain", "gap", "ind"],
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
-        post = {k: v for k, v in res.items() if not k.startswith(("stat_", "waic_", "log_likelihood_")) and k not in skip}
+        post = {k: v for k, v in res.items()
+                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_"))
+                and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
-        means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS if k in res}
+        means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS + PPC_KEYS if k in res}
         # pm.compute_log_likelihood: one variable per observed variable, its dim named as PyMC names an undimmed one
         loglik = {k[len("log_likelihood_"):]: v for k, v in res.items() if k.startswith("log_likelihood_")}
+        # pm.sample_posterior_predictive: the replicates under the observed variables' names, beside the observed values
+        pp = {k[len("posterior_predictive_"):]: v for k, v in res.items() if k.startswith("posterior_predictive_")}
+        obs = {k[len("observed_data_"):]: v for k, v in res.items() if k.startswith("observed_data_")}
         dims.update({"it_s_lik": ["it_s_lik_dim_0"], "it_n_lik": ["it_n_lik_dim_0"],
                      "elpd_waic_i_it_s_lik": ["it_s_lik_dim_0"], "p_waic_i_it_s_lik": ["it_s_lik_dim_0"],
-                     "elpd_waic_i_it_n_lik": ["it_n_lik_dim_0"], "p_waic_i_it_n_lik": ["it_n_lik_dim_0"]})
+                     "elpd_waic_i_it_n_lik": ["it_n_lik_dim_0"], "p_waic_i_it_n_lik": ["it_n_lik_dim_0"],
+                     "ppc_p_it_s_lik": ["it_s_lik_dim_0"], "ppc_p_it_n_lik": ["it_n_lik_dim_0"]})
         if "draw_index" in res and res["draw_index"].shape[1] != next(iter(stats.values())).shape[1]:
             # --thin: an InferenceData has ONE draw axis, so the file holds the thinned draws of every variable (what
             # abdpymc-subsample-idata makes of a full one); the posterior means over ALL draws travel as constant data
@@ -88,7 +117,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
             post = {k: (v[:, idx] if v.shape[1] == n_all else v) for k, v in post.items()}
             stats = {k: v[:, idx] for k, v in stats.items()}
         idata = az.from_dict(posterior=post, sample_stats=stats, constant_data=means or None, log_likelihood=loglik or None,
-                             coords=coords, dims=dims)
+                             posterior_predictive=pp or None, observed_data=obs or None, coords=coords, dims=dims)
         az.to_netcdf(idata, path)  # abd.py:924
         return path
     out = (path or "abd_posterior") + ("" if str(path or "").endswith(".npz") else ".npz")
@@ -141,7 +170,7 @@ def main(argv=None) -> int:
     res = sample(m, tune=args.tune, draws=args.draws, chains=mine, seed=args.seed,
                  record_deterministics=not args.no_deterministics, record_discrete=not args.no_discrete, progress=progress,
                  chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
-                 waic=args.waic)  # abd.py:922
+                 waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc)  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
@@ -154,6 +183,14 @@ def main(argv=None) -> int:
             w = add_waic(res)
             print(f"WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_readings']} readings, "
                   f"{w['n_draws']} draws; {w['n_warn']} readings with p_waic_i > 0.4)", file=sys.stderr)
+        if args.ppc:
+            sm = add_ppc(res)
+            for name in ("it_s_lik", "it_n_lik"):
+                a = sm[name]
+                print(f"PPC {name}: {a['n_extreme']} of {a['n_readings']} readings ({100 * a['share_extreme']:.2f} %) with p < 0.025 "
+                      f"({a['n_low']}) or p > 0.975 ({a['n_high']}); {sm['n_draws']} draws", file=sys.stderr)
+        if args.posterior_predictive:
+            add_observed(res, data)
         out = write_posterior(res, args.netcdf, data.coords)
         print(f"wrote {out}  ({chains} chains x {args.draws} draws on {world} x {name})", file=sys.stderr)
     if world > 1:

@@ -426,6 +426,8 @@ void free_ctx(abd_ctx* c) {
   if (c->h_counts_chain) (void)hipHostFree(c->h_counts_chain);
   if (c->d_det) (void)hipFree(c->d_det);
   if (c->d_pw) (void)hipFree(c->d_pw);
+  if (c->d_order) (void)hipFree(c->d_order);
+  if (c->d_pp) (void)hipFree(c->d_pp);
   for (auto& e : c->win_end)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->ev_pool) {

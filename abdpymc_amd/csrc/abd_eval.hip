@@ -4,6 +4,7 @@
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
 #include "abd_pointwise.hpp"
+#include "abd_predictive.hpp"
 
 namespace abdi {
 
@@ -523,6 +524,107 @@ int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st,
   return ABD_OK;
 }
 
+int upload_order(abd_ctx* c) {
+  if (c->d_order) return ABD_OK;
+  const int64_t Ks = c->s.K, Kn = c->n.K;
+  if (Ks >= ((int64_t)1 << 32) || Kn >= ((int64_t)1 << 32))
+    return fail(ABD_ERR_ARG, "posterior predictive: %lld / %lld readings, at most 2^32 - 1 per antigen", (long long)Ks, (long long)Kn);
+  std::vector<uint32_t> h((size_t)std::max<int64_t>(1, Ks + Kn));
+  for (int64_t k = 0; k < Ks; ++k) h[(size_t)k] = (uint32_t)c->order_s[(size_t)k];
+  for (int64_t k = 0; k < Kn; ++k) h[(size_t)(Ks + k)] = (uint32_t)c->order_n[(size_t)k];
+  uint32_t* d = nullptr;
+  HIP_TRY(hipMalloc(&d, h.size() * sizeof(uint32_t)));
+  if (hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return fail(ABD_ERR_HIP, "posterior predictive: upload of the reading order failed");
+  }
+  c->d_order = d;
+  return ABD_OK;
+}
+
+int launch_predictive(abd_ctx* c, int chain, const double* theta, hipStream_t st, uint64_t seed, uint32_t stream, uint64_t draw,
+                      double* yrep, double* mean, double* acc, int64_t n_draw) {
+  const int64_t Ks = c->s.K, Kn = c->n.K;
+  if (Ks + Kn == 0 || (!yrep && !mean && !acc)) return ABD_OK;
+  if (!c->d_order) return fail(ABD_ERR_STATE, "internal: the reading order is not on the device (upload_order)");
+  const Transformed tr = transform(theta);
+  const ChainSlot& sl = c->slots[(size_t)chain];
+  PredictiveArgs w;
+  std::memset(&w, 0, sizeof w);
+  if (c->dense) {
+    w.y_n = c->n.yxi;
+    w.y_s = c->s.yxi;
+  } else {
+    w.y_n = c->n.y;
+    w.x_n = c->n.x;
+    w.y_s = c->s.y;
+    w.x_s = c->s.x;
+    w.g_n = c->n.g;
+    w.g_s = c->s.g;
+    w.j_n = c->n.j;
+    w.j_s = c->s.j;
+  }
+  w.vw = c->vw;
+  w.iw = sl.iw;
+  w.waner = sl.waner;
+  w.ord = c->d_order;
+  w.yrep = yrep;
+  w.mean = mean;
+  w.acc = acc;
+  w.rho_n = tr.rho_n;
+  w.rho_s = tr.rho_s;
+  constexpr double kLog2E = 1.4426950408889634074;
+  w.init_n = tr.init_n;
+  w.perm_n = tr.perm_n;
+  w.temp_n = tr.temp_n;
+  w.b2_n = tr.b_n * kLog2E;
+  w.d_n = tr.d_n;
+  w.sig_n = tr.sig_n;
+  w.inv_sig_n = 1.0 / tr.sig_n;
+  w.init_s = tr.init_s;
+  w.perm_s = tr.perm_s;
+  w.b2_s = tr.b_s * kLog2E;
+  w.d_s = tr.d_s;
+  w.sig_s = tr.sig_s;
+  w.inv_sig_s = 1.0 / tr.sig_s;
+  w.K_s = Ks;
+  w.K_n = Kn;
+  w.n_draw = acc ? n_draw : 0;
+  w.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  // the stream (abd_predictive.hpp): key (seed_lo, seed_hi), counter (r, stream, draw_lo, c3 of the antigen)
+  w.seed_lo = (uint32_t)seed;
+  w.seed_hi = (uint32_t)(seed >> 32);
+  w.stream = stream;
+  w.draw_lo = (uint32_t)draw;
+  const uint32_t draw_hi = (uint32_t)(draw >> 32) & 0x3FFFFFFFu;
+  w.c3_s = 0x80000000u | (0u << 30) | draw_hi;
+  w.c3_n = 0x80000000u | (1u << 30) | draw_hi;
+  w.G = c->G;
+  w.N = c->N;
+  w.nt = c->nt;
+  const bool f32 = c->storage == ABD_STORE_F32, wide = c->nt > ABD_MAXT;
+  using Kernel = void (*)(const PredictiveArgs);
+  Kernel k;
+  int blocks;
+  size_t lds;
+  if (c->dense) {
+    k = f32 ? (wide ? abd_predictive_dense_kernel<float, ABD_MAXT_MAX> : abd_predictive_dense_kernel<float, ABD_MAXT>)
+            : (wide ? abd_predictive_dense_kernel<double, ABD_MAXT_MAX> : abd_predictive_dense_kernel<double, ABD_MAXT>);
+    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
+    blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
+  } else {
+    k = f32 ? (wide ? abd_predictive_obs_kernel<float, ABD_MAXT_MAX> : abd_predictive_obs_kernel<float, ABD_MAXT>)
+            : (wide ? abd_predictive_obs_kernel<double, ABD_MAXT_MAX> : abd_predictive_obs_kernel<double, ABD_MAXT>);
+    const int64_t cap = (int64_t)c->n_cu * 8;
+    w.bn = (int32_t)std::min<int64_t>((Kn + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    w.bs = (int32_t)std::min<int64_t>((Ks + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    lds = (size_t)2 * (c->G + 1) * sizeof(double2_t);
+    blocks = w.bn + w.bs;
+  }
+  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w));
+  return ABD_OK;
+}
+
 // A synchronous call: whatever was queued stream-ordered before it is summed and joined first (flush_ring), then the
 // evaluation of n chains (logp and, with grad non-null, the gradient) on pipe 0, its rows awaited and assembled
 int eval_sync(abd_ctx* c, int n, const int32_t* chains, const double* theta, double* logp, double* grad, bool with_priors = true) {
@@ -558,6 +660,37 @@ int abd_pointwise_loglik(abd_ctx* c, int32_t chain, const double* theta, double*
     for (int64_t k = 0; k < Ks; ++k) ll_s[c->order_s[(size_t)k]] = h[(size_t)k];
   if (ll_n)
     for (int64_t k = 0; k < Kn; ++k) ll_n[c->order_n[(size_t)k]] = h[(size_t)(Ks + k)];
+  return ABD_OK;
+}
+
+int abd_posterior_predictive(abd_ctx* c, int32_t chain, const double* theta, uint64_t seed, uint32_t stream, uint64_t draw,
+                             double* yrep_s, double* yrep_n, double* mean_s, double* mean_n) {
+  if (!c || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  int rc = check_chains(c, 1, &chain);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int frc = flush_ring(c)) return frc;
+  if (int jrc = join_pipes(c)) return jrc;
+  if (int urc = upload_order(c)) return urc;
+  const int64_t Ks = c->s.K, Kn = c->n.K, Kt = Ks + Kn;
+  const bool rep = yrep_s || yrep_n, mean = mean_s || mean_n;
+  if (Kt == 0 || (!rep && !mean)) return ABD_OK;
+  if (!c->d_pp) HIP_TRY(hipMalloc(&c->d_pp, (size_t)(2 * Kt) * sizeof(double)));  // staging, kept for the next call
+  if (int lrc = launch_predictive(c, chain, theta, c->stream, seed, stream, draw, rep ? c->d_pp : nullptr, mean ? c->d_pp + Kt : nullptr,
+                                  nullptr, 0))
+    return lrc;
+  std::vector<double> h((size_t)(2 * Kt));
+  HIP_TRY(hipMemcpyAsync(h.data(), c->d_pp, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  // back to the order the caller gave the readings in (abd_create)
+  double* outs[2][2] = {{yrep_s, yrep_n}, {mean_s, mean_n}};
+  for (int v = 0; v < 2; ++v) {
+    const double* r = h.data() + (size_t)v * Kt;
+    if (double* o = outs[v][0])
+      for (int64_t k = 0; k < Ks; ++k) o[c->order_s[(size_t)k]] = r[k];
+    if (double* o = outs[v][1])
+      for (int64_t k = 0; k < Kn; ++k) o[c->order_n[(size_t)k]] = r[Ks + k];
+  }
   return ABD_OK;
 }
 

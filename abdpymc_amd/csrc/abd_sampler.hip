@@ -23,7 +23,11 @@ struct abd_sampler {
   // pointwise log-likelihood statistics of every draw (abd_pointwise.hpp): [n][4][K_s + K_n] running max, scaled sum of
   // exp, mean, M2 per reading
   double* d_pw_acc = nullptr;
-  bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise is refused after that)
+  double* d_rec_yrep = nullptr;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
+  // posterior predictive check statistics of every draw (abd_predictive.hpp): [n][3][K_s + K_n] mean, M2 of the predictive
+  // mean, mean tail probability per reading
+  double* d_pp_acc = nullptr;
+  bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise / _predictive are refused after that)
   std::vector<double> lp, gr;  // starting points' logp / gradient
   int unit = 1;                // chains per independent unit (sampler_run_units)
   int threads = 1;  // host threads that drive the units (sampler_run_units)
@@ -87,7 +91,7 @@ __global__ void abd_sweep_done_kernel(const unsigned long long* counts, unsigned
 // Free a sampler and everything it may own, a half-built one included, once the device is through with it
 void sampler_release(abd_sampler* s) {
   const bool trains = !s->tu.empty() || !s->dc.empty();
-  if (trains || s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc) {
+  if (trains || s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc || s->d_rec_yrep || s->d_pp_acc) {
     (void)hipSetDevice(s->c->device);
     // launches of a half that ended early may still be on their way; the buffers' last users are on the context's stream
     (void)(trains ? hipDeviceSynchronize() : hipStreamSynchronize(s->c->stream));
@@ -103,7 +107,8 @@ void sampler_release(abd_sampler* s) {
     if (d.done_h) (void)hipHostFree(d.done_h);
     if (d.side) (void)hipStreamDestroy(d.side);
   }
-  for (void* p : {(void*)s->d_sums, (void*)s->d_rec_mu, (void*)s->d_rec_i8, (void*)s->d_rec_ll, (void*)s->d_pw_acc})
+  for (void* p : {(void*)s->d_sums, (void*)s->d_rec_mu, (void*)s->d_rec_i8, (void*)s->d_rec_ll, (void*)s->d_pw_acc,
+                  (void*)s->d_rec_yrep, (void*)s->d_pp_acc})
     if (p) (void)hipFree(p);
   delete s;
 }
@@ -372,25 +377,33 @@ int record_flush_chain(abd_sampler* s, const abd_record* rec, int k, int64_t fir
   if (rec->i_raw) HIP_TRY(hipMemcpyAsync(rec->i_raw + host * cells, s->d_rec_i8 + dev * cells, filled * cells, hipMemcpyDeviceToHost, st));
   if (rec->i) HIP_TRY(hipMemcpyAsync(rec->i + host * cells, s->d_rec_i8 + per_var + dev * cells, filled * cells, hipMemcpyDeviceToHost, st));
   if (rec->ab_s_waner) HIP_TRY(hipMemcpyAsync(rec->ab_s_waner + host * N, s->d_rec_i8 + 2 * per_var + dev * N, filled * N, hipMemcpyDeviceToHost, st));
-  // pointwise log-likelihood: staged in the device's sorted order, scattered back to the caller's order of the readings
+  // per-reading rows (pointwise log-likelihood, posterior predictive replicates): staged in the device's sorted order,
+  // scattered back to the caller's order of the readings
   const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
-  std::vector<double> ll;
-  if ((rec->ll_s || rec->ll_n) && Kt) {
-    ll.resize((size_t)filled * Kt);
-    HIP_TRY(hipMemcpyAsync(ll.data(), s->d_rec_ll + dev * Kt, ll.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
+  struct Rows {
+    const double* dev;
+    double* out_s;
+    double* out_n;
+    std::vector<double> h;
+  } rows[2] = {{s->d_rec_ll, rec->ll_s, rec->ll_n, {}}, {s->d_rec_yrep, rec->yrep_s, rec->yrep_n, {}}};
+  for (Rows& r : rows)
+    if ((r.out_s || r.out_n) && Kt) {
+      r.h.resize((size_t)filled * Kt);
+      HIP_TRY(hipMemcpyAsync(r.h.data(), r.dev + dev * Kt, r.h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
   HIP_TRY(hipStreamSynchronize(st));
-  for (size_t d = 0; d < ll.size() / std::max<size_t>(Kt, 1); ++d) {
-    const double* r = ll.data() + d * Kt;
-    if (rec->ll_s) {
-      double* o = rec->ll_s + (host + d) * Ks;
-      for (size_t k = 0; k < Ks; ++k) o[c->order_s[k]] = r[k];
+  for (const Rows& rw : rows)
+    for (size_t d = 0; d < rw.h.size() / std::max<size_t>(Kt, 1); ++d) {
+      const double* r = rw.h.data() + d * Kt;
+      if (rw.out_s) {
+        double* o = rw.out_s + (host + d) * Ks;
+        for (size_t k = 0; k < Ks; ++k) o[c->order_s[k]] = r[k];
+      }
+      if (rw.out_n) {
+        double* o = rw.out_n + (host + d) * Kn;
+        for (size_t k = 0; k < Kn; ++k) o[c->order_n[k]] = r[Ks + k];
+      }
     }
-    if (rec->ll_n) {
-      double* o = rec->ll_n + (host + d) * Kn;
-      for (size_t k = 0; k < Kn; ++k) o[c->order_n[k]] = r[Ks + k];
-    }
-  }
   return ABD_OK;
 }
 
@@ -434,7 +447,7 @@ void write_draw(const RunFrame& f, int j, int64_t k, const unsigned long long* c
 
 // the device work of chain j's draw at iteration k of the call (point and discrete state are final), all on stream st, behind
 // the chain's sweep and in front of its next one: the Deterministics into the draw's record and / or the running sums (one
-// launch), the rest of the record, the pointwise log-likelihood.  These kernels read the discrete state and the point (by
+// launch), the rest of the record, the pointwise log-likelihood, the posterior predictive.  These kernels read the discrete state and the point (by
 // value), nothing else.  Then the chain's staging: a full chunk, and what is left at the call's last iteration, is copied
 // out and waited for.  Nothing else is launched here.
 int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
@@ -463,6 +476,14 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   double* acc = (draw && s->d_pw_acc) ? s->d_pw_acc + (size_t)j * 4 * Kt : nullptr;
   if (ll || acc)
     if (int rc = launch_pointwise(c, chain, q, st, ll, ll ? ll + c->s.K : nullptr, acc, iter - s->o.tune + 1)) return rc;
+  // posterior predictive: the record's replicate row (keyed by seed, the chain's global id and the iteration, so that
+  // abd_posterior_predictive reproduces it) and / or -- a draw, accumulation on -- the check statistics
+  double* yrep = (rec && (rec->yrep_s || rec->yrep_n)) ? s->d_rec_yrep + at * Kt : nullptr;
+  double* pacc = (draw && s->d_pp_acc) ? s->d_pp_acc + (size_t)j * 3 * Kt : nullptr;
+  if (yrep || pacc)
+    if (int rc = launch_predictive(c, chain, q, st, s->o.seed, (uint32_t)((int64_t)chain + s->o.chain_offset), (uint64_t)iter, yrep,
+                                   nullptr, pacc, iter - s->o.tune + 1))
+      return rc;
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
     if (int rc = record_flush_chain(s, f.rec, j, sg.flushed_to, sg.staged, st)) return rc;
@@ -991,7 +1012,8 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   abd_ctx* c = s->c;
   const int n = s->n;
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
-  const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll);
+  const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
+  const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
   const size_t Kt = (size_t)(c->s.K + c->n.K);
   s->ran = true;
   if (recording) {
@@ -1003,7 +1025,8 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
     if (!s->d_rec_mu) {
       HIP_TRY(hipSetDevice(c->device));
       const size_t cells = (size_t)c->G * c->N;
-      const size_t per_draw = (size_t)n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
+      const size_t per_draw = (size_t)n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0) +
+                                           (with_yrep ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
       s->rec_chunk = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(((size_t)256 << 20) / per_draw)));
       double* mu = nullptr;
       int8_t* i8 = nullptr;
@@ -1022,6 +1045,17 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
       if (e != hipSuccess) {
         s->d_rec_ll = nullptr;
         return fail(ABD_ERR_HIP, "record staging (pointwise log-likelihood): %s", hipGetErrorString(e));
+      }
+    }
+    if (with_yrep) {
+      HIP_TRY(hipSetDevice(c->device));
+      if (int urc = upload_order(c)) return urc;
+      if (!s->d_rec_yrep) {
+        const hipError_t e = hipMalloc(&s->d_rec_yrep, std::max<size_t>(1, (size_t)n * s->rec_chunk * Kt) * sizeof(double));
+        if (e != hipSuccess) {
+          s->d_rec_yrep = nullptr;
+          return fail(ABD_ERR_HIP, "record staging (posterior predictive): %s", hipGetErrorString(e));
+        }
       }
     }
   }
@@ -1106,6 +1140,55 @@ int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t*
     out[o] = acc[r] + std::log(acc[Kt + r]);  // M + log S = log sum exp(ll)  (-inf before the first draw)
     out[Kt + o] = acc[2 * Kt + r];
     out[2 * Kt + o] = acc[3 * Kt + r];
+  }
+  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
+  return ABD_OK;
+}
+
+int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (s->ran) return fail(ABD_ERR_STATE, "predictive accumulation must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  if (s->d_pp_acc) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(s->d_pp_acc);
+    s->d_pp_acc = nullptr;
+  }
+  if (!accumulate) return ABD_OK;
+  if (int rc = upload_order(c)) return rc;
+  const size_t bytes = std::max<size_t>(1, (size_t)s->n * 3 * (size_t)(c->s.K + c->n.K)) * sizeof(double);
+  hipError_t e = hipMalloc(&s->d_pp_acc, bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    s->d_pp_acc = nullptr;
+    return fail(ABD_ERR_NOMEM, "predictive accumulators: %zu bytes of device memory", bytes);
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(s->d_pp_acc, 0, bytes, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    if (s->d_pp_acc) (void)hipFree(s->d_pp_acc);
+    s->d_pp_acc = nullptr;
+    return fail(ABD_ERR_HIP, "predictive accumulators: %s", hipGetErrorString(e));
+  }
+  return ABD_OK;
+}
+
+int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
+  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_pp_acc) return fail(ABD_ERR_STATE, "predictive accumulation is not enabled (abd_sampler_enable_predictive)");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
+    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
+  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
+  std::vector<double> acc(3 * Kt);
+  if (Kt) HIP_TRY(hipMemcpy(acc.data(), s->d_pp_acc + (size_t)k * 3 * Kt, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < Kt; ++r) {
+    const size_t o = r < Ks ? (size_t)c->order_s[r] : Ks + (size_t)c->order_n[r - Ks];  // the caller's order
+    for (size_t row = 0; row < 3; ++row) out[row * Kt + o] = acc[row * Kt + r];
   }
   if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
   return ABD_OK;

@@ -255,6 +255,15 @@ class AbdModel:
         ll_s, ll_n = self.ctx.pointwise_loglik(chain, self.ravel(point))
         return {"it_s_lik": ll_s, "it_n_lik": ll_n}
 
+    def posterior_predictive(self, point: Dict[str, np.ndarray], chain: int = 0, seed: int = 0, stream: int = 0,
+                             draw: int = 0) -> Dict[str, np.ndarray]:
+        """A posterior predictive replicate of every observed OD reading at ``point`` (``pm.sample_posterior_predictive`` for
+        one draw), the normals keyed by (seed, stream, draw) (``Context.posterior_predictive``): one array per observed
+        variable, readings in the cohort's row order."""
+        self.ctx.set_discrete(chain, np.asarray(point["i_raw"]), np.asarray(point["ab_s_waner"]))
+        y_s, y_n = self.ctx.posterior_predictive(chain, self.ravel(point), seed=seed, stream=stream, draw=draw)
+        return {"it_s_lik": y_s, "it_n_lik": y_n}
+
     def close(self):
         self.ctx.close()
 

@@ -278,11 +278,13 @@ def sample_chain(model, chain: int, tune: int, draws: int, seed: int, record_det
 
 
 def record_bytes(chains: int, n_rec: int, G: int, N: int, record_deterministics: bool, record_discrete: bool,
-                 n_readings: int = 0) -> int:
+                 n_readings: int = 0, n_replicates: int = 0) -> int:
     """Host bytes of the per-draw arrays of a run that records ``n_rec`` draws per chain: i (int8) + ab_n_mu + ab_s_mu
     (float64) per cell for the Deterministics, i_raw (int8) per cell + ab_s_waner (int8) per individual for the discrete state,
-    and a float64 per OD reading for the pointwise log-likelihood (``n_readings``: readings of both antigens; 0 = not recorded)."""
-    per_draw = (G * N * 17 if record_deterministics else 0) + (G * N + N if record_discrete else 0) + 8 * int(n_readings)
+    a float64 per OD reading for the pointwise log-likelihood (``n_readings``: readings of both antigens; 0 = not recorded)
+    and a float64 per OD reading for the posterior predictive replicates (``n_replicates``; 0 = not recorded)."""
+    per_draw = ((G * N * 17 if record_deterministics else 0) + (G * N + N if record_discrete else 0) + 8 * int(n_readings)
+                + 8 * int(n_replicates))
     return chains * n_rec * per_draw
 
 
@@ -298,7 +300,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   target_accept: float = 0.8, max_treedepth: int = 10, chunk: int = 50,
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
                   budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-                  waic: bool = False) -> Dict[str, np.ndarray]:
+                  waic: bool = False, posterior_predictive: bool = False, ppc: bool = False) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -317,6 +319,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     ``pm.compute_log_likelihood`` adds to an InferenceData.  ``waic``: accumulate its per-reading statistics over ALL
     draws on the device (any cohort size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n;
     S readings first), ``waic_n_draws`` (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``compare.waic`` reads them.
+
+    ``posterior_predictive``: also record a posterior predictive replicate of every OD reading at the recorded draws (thinned
+    likewise) as ``posterior_predictive_it_s_lik`` / ``posterior_predictive_it_n_lik`` (chains, n_rec, K), what
+    ``pm.sample_posterior_predictive`` returns; chain c's replicate of iteration t (tune included) is
+    ``Context.posterior_predictive(.., seed, chain_offset + c, t)`` (``predictive.sample_posterior_predictive``).  ``ppc``:
+    accumulate per-reading check statistics over ALL draws on the device -- ``ppc_mean`` / ``ppc_m2`` (mean and sum of squared
+    deviations of the predictive mean) and ``ppc_pit`` (mean of P(y_rep <= y | draw)), each (chains, K_s + K_n), S readings
+    first, ``ppc_n_draws`` (chains,) and ``ppc_n_obs`` (chains, 2): ``predictive.summary`` reads them.  Neither option draws
+    from any random stream the chains use: their trajectories do not change.
     """
     from .model import THETA_NAMES, constrain
 
@@ -325,11 +336,13 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     if thin < 1:
         raise ValueError(f"thin must be >= 1, got {thin}")
     n_rec = (draws + thin - 1) // thin
-    K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if (log_likelihood or waic) else (0, 0)  # readings of it_s_lik / it_n_lik
-    if record_deterministics or record_discrete or log_likelihood:
+    K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if (log_likelihood or waic or posterior_predictive or ppc) else (0, 0)  # readings of it_s_lik / it_n_lik
+    per_reading = log_likelihood or posterior_predictive  # per-draw rows of the readings
+    if record_deterministics or record_discrete or per_reading:
         budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
         need = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
-                            n_readings=(K_s + K_n) if log_likelihood else 0)
+                            n_readings=(K_s + K_n) if log_likelihood else 0,
+                            n_replicates=(K_s + K_n) if posterior_predictive else 0)
         if need > budget:
             per_draw = need // max(n_rec, 1)
             fit = max(1, budget // max(per_draw, 1))          # draws per chain set that fit
@@ -347,7 +360,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         q0[c] = model.ravel(pt) + rng.uniform(-1, 1, size=len(THETA_NAMES))  # start jitter U(-1, 1) on the value variables: pm.sample's default init 'jitter+adapt_diag'
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
-                      dense_metric=dense_metric, pointwise=waic)
+                      dense_metric=dense_metric, pointwise=waic, predictive=ppc)
     n_grad = chains  # the evaluation at the starting points
     done = 0
 
@@ -373,10 +386,12 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         det = dict(i=np.empty((chains, n_rec, G, N), dtype=np.int8), ab_n_mu=np.empty((chains, n_rec, G, N)),
                    ab_s_mu=np.empty((chains, n_rec, G, N)))
     ll = dict(ll_s=np.empty((chains, n_rec, K_s)), ll_n=np.empty((chains, n_rec, K_n))) if log_likelihood else {}
+    if posterior_predictive:
+        ll.update(yrep_s=np.empty((chains, n_rec, K_s)), yrep_n=np.empty((chains, n_rec, K_n)))
     k = 0
     while k < draws:
         n = min(chunk, draws - k)
-        if record_deterministics or record_discrete or log_likelihood:
+        if record_deterministics or record_discrete or per_reading:
             # staged on the device, copied out in large blocks straight into the arrays above
             th, st = smp.run_record(n, k // thin, i_raw=out_i_raw, ab_s_waner=out_w, thin=thin, **(det or {}), **ll)
             n_grad += int(st["n_steps"].sum()) + n * chains
@@ -404,7 +419,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
             res[name] = np.stack([o[j] for o, _ in stats_pw])
         res["waic_n_draws"] = np.array([n for _, n in stats_pw], dtype=np.int64)
         res["waic_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
-    if record_discrete or det is not None or log_likelihood:
+    if posterior_predictive:
+        res["posterior_predictive_it_s_lik"], res["posterior_predictive_it_n_lik"] = ll["yrep_s"], ll["yrep_n"]
+    if ppc:
+        stats_pp = [smp.predictive_stats(c) for c in range(chains)]
+        for j, name in enumerate(("ppc_mean", "ppc_m2", "ppc_pit")):
+            res[name] = np.stack([o[j] for o, _ in stats_pp])
+        res["ppc_n_draws"] = np.array([n for _, n in stats_pp], dtype=np.int64)
+        res["ppc_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
+    if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
         means = [smp.means(c) for c in range(chains)]
@@ -423,7 +446,7 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            progress: Optional[Callable[[int, int, int], None]] = None, device_gibbs: bool = True,
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-           waic: bool = False) -> Dict[str, np.ndarray]:
+           waic: bool = False, posterior_predictive: bool = False, ppc: bool = False) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
@@ -431,7 +454,10 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
     if native and device_gibbs and hasattr(model.ctx, "sampler"):
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
-                             log_likelihood=log_likelihood, waic=waic)
+                             log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc)
+    if posterior_predictive or ppc:
+        raise ValueError("posterior_predictive / ppc need the native sampler (sample(native=True)): the replicates and the check "
+                         "statistics are drawn and accumulated inside it")
     if log_likelihood or waic:
         raise ValueError("log_likelihood / waic need the native sampler (sample(native=True)): the pointwise log-likelihood "
                          "is recorded and accumulated inside it")

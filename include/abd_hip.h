@@ -162,6 +162,17 @@ int abd_deterministics(abd_ctx* ctx, int32_t chain, const double* theta, int8_t*
  * abd_loglik_dlogp's loglik to rounding. */
 int abd_pointwise_loglik(abd_ctx* ctx, int32_t chain, const double* theta, double* ll_s, double* ll_n);
 
+/* Posterior predictive of the two observed Normals at theta and chain slot `chain`'s discrete state (what
+ * pm.sample_posterior_predictive draws for one draw): per OD reading the noise-free mean m = d / (1 + exp(-b (x - a))) into
+ * mean_*, and the replicate y_rep = m + sigma z into yrep_*, s.n_obs / n.n_obs doubles each in the caller's reading order; any
+ * pointer may be NULL.  z ~ N(0, 1) comes from Philox4x32-10 with key (seed lo, seed hi) and counter (r, stream, draw lo,
+ * 0x80000000 | antigen << 30 | (draw >> 32) & 0x3FFFFFFF) -- r the reading's index in the caller's order within its antigen
+ * (S 0, N 1) -- as u1 = ((w0 >> 5) 2^26 + (w1 >> 6) + 0.5) 2^-53, u2 likewise of w2, w3, z = sqrt(-2 ln u1) cospi(2 u2).  So
+ * the noise depends on (seed, stream, draw, antigen, r) only.  The native sampler records with seed = opts.seed, stream =
+ * chain_offset + chain slot, draw = the iteration number.  ABD_ERR_ARG for 2^32 or more readings of an antigen. */
+int abd_posterior_predictive(abd_ctx* ctx, int32_t chain, const double* theta, uint64_t seed, uint32_t stream, uint64_t draw,
+                             double* yrep_s, double* yrep_n, double* mean_s, double* mean_n);
+
 /* ---------------------------------------------------------------------------------------------------
  * The compound step pm.sample assigns to this model (reference call site abd.py:921-922), run natively
  * for several chains: NUTS on the 17 continuous variables, then one Gibbs sweep of [i_raw, ab_s_waner], then a
@@ -253,6 +264,8 @@ typedef struct abd_record {
   double* ab_s_mu;
   double* ll_s;        /* [n][capacity][s.n_obs], [n][capacity][n.n_obs]: the pointwise log-likelihood of every recorded draw */
   double* ll_n;        /* (abd_pointwise_loglik), readings in the caller's order */
+  double* yrep_s;      /* [n][capacity][s.n_obs], [n][capacity][n.n_obs]: the posterior predictive replicate of every recorded */
+  double* yrep_n;      /* draw, bit-identical to abd_posterior_predictive at that draw's point (keys: abd_posterior_predictive) */
 } abd_record;
 int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double* stats, const abd_record* rec);
 /* Posterior means of the Deterministics of chain k (0 <= k < n) over the draws accumulated so far, each
@@ -268,6 +281,15 @@ int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate);
  * squared deviations from it (M2).  They merge exactly over chains and processes: log-add-exp for row 0, Chan et al.'s
  * pairwise formulas for rows 1 and 2 (abdpymc_amd/compare.py).  *n_draws (may be NULL) receives the number of draws. */
 int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws);
+/* Posterior predictive check statistics of every draw (iteration >= tune), accumulated on the device per chain and reading.
+ * Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it); accumulate = 1 allocates 3 x (K_s + K_n) doubles
+ * per chain, 0 releases them.  No random numbers are drawn: the chains' trajectories do not change. */
+int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate);
+/* The statistics of chain k (0 <= k < n) over its draws so far: out is [3][K_s + K_n] (S readings first, then N, each in the
+ * caller's order): row 0 the mean of the predictive mean m, row 1 the sum of its squared deviations (M2), row 2 the mean of
+ * Phi((y - m) / sigma), the tail probability P(y_rep <= y).  They merge exactly over chains and processes: Chan et al. for
+ * rows 0 and 1, a count-weighted mean for row 2 (abdpymc_amd/predictive.py).  *n_draws (may be NULL): the number of draws. */
+int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws);
 /* Current diagonal of M^-1 (17) and step size of chain k; `metric` (17 x 17, may be NULL) receives the full
  * M^-1 (the diagonal matrix when the metric is diagonal). */
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);

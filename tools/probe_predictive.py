@@ -1,0 +1,67 @@
+"""
+Cost of the posterior predictive check at BASELINE config 3 (dense, 10 000 individuals x 200 gaps, 4 M readings): wall time of
+a 4-chain compound sampler run with and without on-device check statistics (sample(..., ppc=True)), at two run lengths so that
+the fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both WAIC and the check on, for
+``rocprofv3 --kernel-trace --stats -- python tools/probe_predictive.py --profile``: the kernel's own time per draw and chain
+(abd_predictive_dense_kernel) next to the pointwise kernel's in the same run.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from abdpymc_amd import synthetic  # noqa: E402
+from abdpymc_amd.model import AbdModel  # noqa: E402
+from abdpymc_amd.sampler import sample  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--inds", type=int, default=10000)
+    ap.add_argument("--gaps", type=int, default=200)
+    ap.add_argument("--chains", type=int, default=4)
+    ap.add_argument("--tune", type=int, default=100)
+    ap.add_argument("--draws", type=int, nargs=2, default=[100, 400])
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--profile", action="store_true")
+    a = ap.parse_args()
+    sc = synthetic.make_cohort(a.inds, a.gaps, seed=3)
+    d = SimpleNamespace(n_gaps=sc.n_gaps, n_inds=sc.n_inds, vacs=sc.vacs, pcrpos=sc.pcrpos,
+                        coords={"gap": np.arange(sc.n_gaps), "ind": np.arange(sc.n_inds)},
+                        s=SimpleNamespace(obs=sc.s_obs), n=SimpleNamespace(obs=sc.n_obs))
+    m = AbdModel(d, n_chains=a.chains)
+    kw = dict(tune=a.tune, chains=a.chains, seed=1, record_deterministics=False, record_discrete=False)
+    if a.profile:
+        t0 = time.perf_counter()
+        sample(m, draws=a.draws[0], waic=True, ppc=True, **kw)
+        print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], waic=True, ppc=True,
+                              wall_s=time.perf_counter() - t0)))
+        m.close()
+        return
+    sample(m, **dict(kw, tune=5), draws=5, ppc=True)  # warm-up: code objects, allocations
+    t = {f"{leg}_{n}": [] for n in a.draws for leg in ("plain", "ppc")}
+    for _ in range(a.reps):  # alternated, so that drift hits both legs alike
+        for n in a.draws:
+            for leg in ("plain", "ppc"):
+                t0 = time.perf_counter()
+                sample(m, draws=n, ppc=leg == "ppc", **kw)
+                t[f"{leg}_{n}"].append(time.perf_counter() - t0)
+    best = {k: min(v) for k, v in t.items()}
+    d0, d1 = a.draws
+    extra0, extra1 = best[f"ppc_{d0}"] - best[f"plain_{d0}"], best[f"ppc_{d1}"] - best[f"plain_{d1}"]
+    per_draw = (extra1 - extra0) / (d1 - d0)  # seconds per draw (all chains)
+    print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws, wall_s=t,
+                          overhead={str(n): best[f"ppc_{n}"] / best[f"plain_{n}"] - 1.0 for n in a.draws},
+                          per_draw_ms=1e3 * per_draw, per_draw_chain_us=1e6 * per_draw / a.chains,
+                          fixed_ms=1e3 * (extra0 - per_draw * d0))))
+    m.close()
+
+
+if __name__ == "__main__":
+    main()
