@@ -677,22 +677,22 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_means(self._h, int(k), *[_ptr(o, C.c_double) for o in out], C.byref(n)))
         return out[0], out[1], out[2], n.value
 
+    def _reading_stats(self, fn, k: int):
+        out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
+        n = C.c_int64()
+        _check(self._lib, fn(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
+        return out, n.value
+
     def pointwise_stats(self, k: int):
         """Pointwise log-likelihood statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S
         readings then N in the caller's order; rows log sum exp(ll), mean(ll), sum of squared deviations (compare.merge)."""
-        out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
-        n = C.c_int64()
-        _check(self._lib, self._lib.abd_sampler_pointwise_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
-        return out, n.value
+        return self._reading_stats(self._lib.abd_sampler_pointwise_stats, k)
 
     def predictive_stats(self, k: int):
         """Posterior predictive check statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S
         readings then N in the caller's order; rows mean and sum of squared deviations of the predictive mean, mean tail
         probability P(y_rep <= y) (predictive.merge)."""
-        out = np.empty((3, self._ctx.n_obs_s + self._ctx.n_obs_n))
-        n = C.c_int64()
-        _check(self._lib, self._lib.abd_sampler_predictive_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n)))
-        return out, n.value
+        return self._reading_stats(self._lib.abd_sampler_predictive_stats, k)
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

@@ -425,9 +425,8 @@ void free_ctx(abd_ctx* c) {
   if (c->d_train_count) (void)hipFree(c->d_train_count);
   if (c->h_counts_chain) (void)hipHostFree(c->h_counts_chain);
   if (c->d_det) (void)hipFree(c->d_det);
-  if (c->d_pw) (void)hipFree(c->d_pw);
+  if (c->d_stage) (void)hipFree(c->d_stage);
   if (c->d_order) (void)hipFree(c->d_order);
-  if (c->d_pp) (void)hipFree(c->d_pp);
   for (auto& e : c->win_end)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->ev_pool) {
@@ -579,7 +578,7 @@ int abd_create(const abd_desc* d, abd_ctx** out) {
     free_ctx(c);
     return rc;
   }
-  c->order_s = std::move(so_s.order);  // sorted position -> caller's index (abd_pointwise_loglik scatters through it)
+  c->order_s = std::move(so_s.order);  // sorted position -> caller's index (abd_eval.hip: scatter_readings)
   c->order_n = std::move(so_n.order);
   c->xc_ok = c->dense && c->s.od && c->n.od;
   c->xc_max_cb = tune_int("ABD_XC_MAX_CB", c->xc_max_cb);

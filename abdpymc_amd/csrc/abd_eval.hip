@@ -3,8 +3,7 @@
 #include "abd_host.hpp"
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
-#include "abd_pointwise.hpp"
-#include "abd_predictive.hpp"
+#include "abd_readings.hpp"
 
 namespace abdi {
 
@@ -452,13 +451,11 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
   return ABD_OK;
 }
 
-int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc, int64_t n_draw) {
-  const int64_t Ks = c->s.K, Kn = c->n.K;
-  if (Ks + Kn == 0 || (!ll_s && !ll_n && !acc)) return ABD_OK;
-  if (ll_s && ll_n && ll_n != ll_s + Ks) return fail(ABD_ERR_ARG, "internal: pointwise rows must be one S-then-N row");
-  const Transformed tr = transform(theta);
-  const ChainSlot& sl = c->slots[(size_t)chain];
-  PointwiseArgs w;
+// ---- per-reading launches (abd_readings.hpp) ----
+
+// The readings, chain slot `chain`'s words and the curve at tr, as both walkers read them
+Readings readings_of(const abd_ctx* c, int chain, const Transformed& tr) {
+  Readings w;
   std::memset(&w, 0, sizeof w);
   if (c->dense) {
     w.y_n = c->n.yxi;
@@ -472,56 +469,73 @@ int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st,
     w.g_s = c->s.g;
     w.j_n = c->n.j;
     w.j_s = c->s.j;
+    const int64_t cap = (int64_t)c->n_cu * 8;
+    w.bn = (int32_t)std::min<int64_t>((c->n.K + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    w.bs = (int32_t)std::min<int64_t>((c->s.K + ABD_BLOCK - 1) / ABD_BLOCK, cap);
   }
+  const ChainSlot& sl = c->slots[(size_t)chain];
   w.vw = c->vw;
   w.iw = sl.iw;
   w.waner = sl.waner;
-  w.ll = ll_s ? ll_s : (ll_n ? ll_n - Ks : nullptr);  // (a row without its S part is never read there)
-  w.acc = acc;
-  w.rho_n = tr.rho_n;
-  w.rho_s = tr.rho_s;
   constexpr double kLog2E = 1.4426950408889634074;
-  w.init_n = tr.init_n;
-  w.perm_n = tr.perm_n;
+  w.rho[kAgN] = tr.rho_n;
+  w.rho[kAgS] = tr.rho_s;
+  w.init[kAgN] = tr.init_n;
+  w.init[kAgS] = tr.init_s;
+  w.perm[kAgN] = tr.perm_n;
+  w.perm[kAgS] = tr.perm_s;
+  w.b2[kAgN] = tr.b_n * kLog2E;
+  w.b2[kAgS] = tr.b_s * kLog2E;
+  w.d[kAgN] = tr.d_n;
+  w.d[kAgS] = tr.d_s;
   w.temp_n = tr.temp_n;
-  w.b2_n = tr.b_n * kLog2E;
-  w.d_n = tr.d_n;
-  w.inv_sig_n = 1.0 / tr.sig_n;
-  w.lnorm_n = -(theta[13] + 0.5 * kLog2Pi);  // log sigma is the value variable itself, as in the assembled loglik
-  w.init_s = tr.init_s;
-  w.perm_s = tr.perm_s;
-  w.b2_s = tr.b_s * kLog2E;
-  w.d_s = tr.d_s;
-  w.inv_sig_s = 1.0 / tr.sig_s;
-  w.lnorm_s = -(theta[16] + 0.5 * kLog2Pi);
-  w.K_s = Ks;
-  w.K_n = Kn;
-  w.n_draw = acc ? n_draw : 0;
-  w.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  w.K_s = c->s.K;
+  w.K_n = c->n.K;
   w.G = c->G;
   w.N = c->N;
   w.nt = c->nt;
+  return w;
+}
+
+// One launch of op over every reading of chain slot `chain` at tr on stream st.  Dense: a wave per individual, three power
+// tables, at most 8 workgroups per CU; lists: a lane per reading, two tables, bn + bs workgroups.
+template <typename Op>
+int launch_readings(abd_ctx* c, int chain, const Transformed& tr, const Op& op, hipStream_t st) {
+  const ReadingArgs<Op> a{readings_of(c, chain, tr), op};
   const bool f32 = c->storage == ABD_STORE_F32, wide = c->nt > ABD_MAXT;
-  using Kernel = void (*)(const PointwiseArgs);
+  using Kernel = void (*)(const ReadingArgs<Op>);
   Kernel k;
   int blocks;
   size_t lds;
   if (c->dense) {
-    k = f32 ? (wide ? abd_pointwise_dense_kernel<float, ABD_MAXT_MAX> : abd_pointwise_dense_kernel<float, ABD_MAXT>)
-            : (wide ? abd_pointwise_dense_kernel<double, ABD_MAXT_MAX> : abd_pointwise_dense_kernel<double, ABD_MAXT>);
+    k = f32 ? (wide ? abd_readings_dense_kernel<Op, float, ABD_MAXT_MAX> : abd_readings_dense_kernel<Op, float, ABD_MAXT>)
+            : (wide ? abd_readings_dense_kernel<Op, double, ABD_MAXT_MAX> : abd_readings_dense_kernel<Op, double, ABD_MAXT>);
     lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
     blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
   } else {
-    k = f32 ? (wide ? abd_pointwise_obs_kernel<float, ABD_MAXT_MAX> : abd_pointwise_obs_kernel<float, ABD_MAXT>)
-            : (wide ? abd_pointwise_obs_kernel<double, ABD_MAXT_MAX> : abd_pointwise_obs_kernel<double, ABD_MAXT>);
-    const int64_t cap = (int64_t)c->n_cu * 8;
-    w.bn = (int32_t)std::min<int64_t>((Kn + ABD_BLOCK - 1) / ABD_BLOCK, cap);
-    w.bs = (int32_t)std::min<int64_t>((Ks + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    k = f32 ? (wide ? abd_readings_lists_kernel<Op, float, ABD_MAXT_MAX> : abd_readings_lists_kernel<Op, float, ABD_MAXT>)
+            : (wide ? abd_readings_lists_kernel<Op, double, ABD_MAXT_MAX> : abd_readings_lists_kernel<Op, double, ABD_MAXT>);
     lds = (size_t)2 * (c->G + 1) * sizeof(double2_t);
-    blocks = w.bn + w.bs;
+    blocks = a.rd.bn + a.rd.bs;
   }
-  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w));
+  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, a));
   return ABD_OK;
+}
+
+int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll, double* acc, int64_t n_draw) {
+  if (c->s.K + c->n.K == 0 || (!ll && !acc)) return ABD_OK;
+  const Transformed tr = transform(theta);
+  LogLik op;
+  std::memset(&op, 0, sizeof op);
+  op.ll = ll;
+  op.acc = acc;
+  op.n_draw = acc ? n_draw : 0;
+  op.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  op.inv_sig[kAgN] = 1.0 / tr.sig_n;
+  op.inv_sig[kAgS] = 1.0 / tr.sig_s;
+  op.lnorm[kAgN] = -(theta[13] + 0.5 * kLog2Pi);  // log sigma is the value variable itself, as in the assembled loglik
+  op.lnorm[kAgS] = -(theta[16] + 0.5 * kLog2Pi);
+  return launch_readings(c, chain, tr, op, st);
 }
 
 int upload_order(abd_ctx* c) {
@@ -544,84 +558,52 @@ int upload_order(abd_ctx* c) {
 
 int launch_predictive(abd_ctx* c, int chain, const double* theta, hipStream_t st, uint64_t seed, uint32_t stream, uint64_t draw,
                       double* yrep, double* mean, double* acc, int64_t n_draw) {
-  const int64_t Ks = c->s.K, Kn = c->n.K;
-  if (Ks + Kn == 0 || (!yrep && !mean && !acc)) return ABD_OK;
+  if (c->s.K + c->n.K == 0 || (!yrep && !mean && !acc)) return ABD_OK;
   if (!c->d_order) return fail(ABD_ERR_STATE, "internal: the reading order is not on the device (upload_order)");
   const Transformed tr = transform(theta);
-  const ChainSlot& sl = c->slots[(size_t)chain];
-  PredictiveArgs w;
-  std::memset(&w, 0, sizeof w);
-  if (c->dense) {
-    w.y_n = c->n.yxi;
-    w.y_s = c->s.yxi;
-  } else {
-    w.y_n = c->n.y;
-    w.x_n = c->n.x;
-    w.y_s = c->s.y;
-    w.x_s = c->s.x;
-    w.g_n = c->n.g;
-    w.g_s = c->s.g;
-    w.j_n = c->n.j;
-    w.j_s = c->s.j;
-  }
-  w.vw = c->vw;
-  w.iw = sl.iw;
-  w.waner = sl.waner;
-  w.ord = c->d_order;
-  w.yrep = yrep;
-  w.mean = mean;
-  w.acc = acc;
-  w.rho_n = tr.rho_n;
-  w.rho_s = tr.rho_s;
-  constexpr double kLog2E = 1.4426950408889634074;
-  w.init_n = tr.init_n;
-  w.perm_n = tr.perm_n;
-  w.temp_n = tr.temp_n;
-  w.b2_n = tr.b_n * kLog2E;
-  w.d_n = tr.d_n;
-  w.sig_n = tr.sig_n;
-  w.inv_sig_n = 1.0 / tr.sig_n;
-  w.init_s = tr.init_s;
-  w.perm_s = tr.perm_s;
-  w.b2_s = tr.b_s * kLog2E;
-  w.d_s = tr.d_s;
-  w.sig_s = tr.sig_s;
-  w.inv_sig_s = 1.0 / tr.sig_s;
-  w.K_s = Ks;
-  w.K_n = Kn;
-  w.n_draw = acc ? n_draw : 0;
-  w.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
-  // the stream (abd_predictive.hpp): key (seed_lo, seed_hi), counter (r, stream, draw_lo, c3 of the antigen)
-  w.seed_lo = (uint32_t)seed;
-  w.seed_hi = (uint32_t)(seed >> 32);
-  w.stream = stream;
-  w.draw_lo = (uint32_t)draw;
+  Predictive op;
+  std::memset(&op, 0, sizeof op);
+  op.ord = c->d_order;
+  op.yrep = yrep;
+  op.mean = mean;
+  op.acc = acc;
+  op.n_draw = acc ? n_draw : 0;
+  op.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  op.sig[kAgN] = tr.sig_n;
+  op.sig[kAgS] = tr.sig_s;
+  op.inv_sig[kAgN] = 1.0 / tr.sig_n;
+  op.inv_sig[kAgS] = 1.0 / tr.sig_s;
+  // the stream (abd_readings.hpp): key (seed_lo, seed_hi), counter (r, stream, draw_lo, c3 of the antigen)
+  op.seed_lo = (uint32_t)seed;
+  op.seed_hi = (uint32_t)(seed >> 32);
+  op.stream = stream;
+  op.draw_lo = (uint32_t)draw;
   const uint32_t draw_hi = (uint32_t)(draw >> 32) & 0x3FFFFFFFu;
-  w.c3_s = 0x80000000u | (0u << 30) | draw_hi;
-  w.c3_n = 0x80000000u | (1u << 30) | draw_hi;
-  w.G = c->G;
-  w.N = c->N;
-  w.nt = c->nt;
-  const bool f32 = c->storage == ABD_STORE_F32, wide = c->nt > ABD_MAXT;
-  using Kernel = void (*)(const PredictiveArgs);
-  Kernel k;
-  int blocks;
-  size_t lds;
-  if (c->dense) {
-    k = f32 ? (wide ? abd_predictive_dense_kernel<float, ABD_MAXT_MAX> : abd_predictive_dense_kernel<float, ABD_MAXT>)
-            : (wide ? abd_predictive_dense_kernel<double, ABD_MAXT_MAX> : abd_predictive_dense_kernel<double, ABD_MAXT>);
-    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
-    blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
-  } else {
-    k = f32 ? (wide ? abd_predictive_obs_kernel<float, ABD_MAXT_MAX> : abd_predictive_obs_kernel<float, ABD_MAXT>)
-            : (wide ? abd_predictive_obs_kernel<double, ABD_MAXT_MAX> : abd_predictive_obs_kernel<double, ABD_MAXT>);
-    const int64_t cap = (int64_t)c->n_cu * 8;
-    w.bn = (int32_t)std::min<int64_t>((Kn + ABD_BLOCK - 1) / ABD_BLOCK, cap);
-    w.bs = (int32_t)std::min<int64_t>((Ks + ABD_BLOCK - 1) / ABD_BLOCK, cap);
-    lds = (size_t)2 * (c->G + 1) * sizeof(double2_t);
-    blocks = w.bn + w.bs;
+  op.c3[kAgS] = 0x80000000u | (0u << 30) | draw_hi;
+  op.c3[kAgN] = 0x80000000u | (1u << 30) | draw_hi;
+  return launch_readings(c, chain, tr, op, st);
+}
+
+// A synchronous per-reading call of chain slot `chain`: whatever was queued before it is summed and joined, then `launch` writes
+// `rows` S-then-N rows into the context's staging on its stream, and they come back into h (left empty without readings or rows)
+template <typename F>
+int readings_sync(abd_ctx* c, int32_t chain, int rows, std::vector<double>& h, F&& launch) {
+  if (int rc = check_chains(c, 1, &chain)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = flush_ring(c)) return rc;
+  const size_t Kt = (size_t)(c->s.K + c->n.K);
+  if (Kt == 0 || rows == 0) return ABD_OK;
+  if (c->stage_rows < rows) {  // the staging grows to the most rows a call has needed and is kept for the next call
+    if (c->d_stage) (void)hipFree(c->d_stage);
+    c->d_stage = nullptr;
+    c->stage_rows = 0;
+    HIP_TRY(hipMalloc(&c->d_stage, (size_t)rows * Kt * sizeof(double)));
+    c->stage_rows = rows;
   }
-  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), lds, st, w));
+  if (int rc = launch(c->d_stage)) return rc;
+  h.resize((size_t)rows * Kt);
+  HIP_TRY(hipMemcpyAsync(h.data(), c->d_stage, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ABD_OK;
 }
 
@@ -641,56 +623,29 @@ extern "C" {
 
 int abd_pointwise_loglik(abd_ctx* c, int32_t chain, const double* theta, double* ll_s, double* ll_n) {
   if (!c || !theta) return fail(ABD_ERR_ARG, "NULL argument");
-  int rc = check_chains(c, 1, &chain);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if (int frc = flush_ring(c)) return frc;
-  if (int jrc = join_pipes(c)) return jrc;
-  const int64_t Ks = c->s.K, Kn = c->n.K;
-  if (Ks + Kn == 0 || (!ll_s && !ll_n)) return ABD_OK;
-  if (!c->d_pw) HIP_TRY(hipMalloc(&c->d_pw, (size_t)(Ks + Kn) * sizeof(double)));  // staging, kept for the next call
-  double* d_s = c->d_pw;
-  double* d_n = c->d_pw + Ks;
-  if (int lrc = launch_pointwise(c, chain, theta, c->stream, ll_s ? d_s : nullptr, ll_n ? d_n : nullptr, nullptr, 0)) return lrc;
-  std::vector<double> h((size_t)(Ks + Kn));
-  HIP_TRY(hipMemcpyAsync(h.data(), c->d_pw, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  // back to the order the caller gave the readings in (abd_create)
-  if (ll_s)
-    for (int64_t k = 0; k < Ks; ++k) ll_s[c->order_s[(size_t)k]] = h[(size_t)k];
-  if (ll_n)
-    for (int64_t k = 0; k < Kn; ++k) ll_n[c->order_n[(size_t)k]] = h[(size_t)(Ks + k)];
+  std::vector<double> h;
+  if (int rc = readings_sync(c, chain, (ll_s || ll_n) ? 1 : 0, h,
+                             [&](double* d) { return launch_pointwise(c, chain, theta, c->stream, d, nullptr, 0); }))
+    return rc;
+  const ReadingOut out[1] = {{ll_s, ll_n}};
+  if (!h.empty()) scatter_readings(c, out, [&](int, size_t k) { return h[k]; });
   return ABD_OK;
 }
 
 int abd_posterior_predictive(abd_ctx* c, int32_t chain, const double* theta, uint64_t seed, uint32_t stream, uint64_t draw,
                              double* yrep_s, double* yrep_n, double* mean_s, double* mean_n) {
   if (!c || !theta) return fail(ABD_ERR_ARG, "NULL argument");
-  int rc = check_chains(c, 1, &chain);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if (int frc = flush_ring(c)) return frc;
-  if (int jrc = join_pipes(c)) return jrc;
-  if (int urc = upload_order(c)) return urc;
-  const int64_t Ks = c->s.K, Kn = c->n.K, Kt = Ks + Kn;
   const bool rep = yrep_s || yrep_n, mean = mean_s || mean_n;
-  if (Kt == 0 || (!rep && !mean)) return ABD_OK;
-  if (!c->d_pp) HIP_TRY(hipMalloc(&c->d_pp, (size_t)(2 * Kt) * sizeof(double)));  // staging, kept for the next call
-  if (int lrc = launch_predictive(c, chain, theta, c->stream, seed, stream, draw, rep ? c->d_pp : nullptr, mean ? c->d_pp + Kt : nullptr,
-                                  nullptr, 0))
-    return lrc;
-  std::vector<double> h((size_t)(2 * Kt));
-  HIP_TRY(hipMemcpyAsync(h.data(), c->d_pp, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  // back to the order the caller gave the readings in (abd_create)
-  double* outs[2][2] = {{yrep_s, yrep_n}, {mean_s, mean_n}};
-  for (int v = 0; v < 2; ++v) {
-    const double* r = h.data() + (size_t)v * Kt;
-    if (double* o = outs[v][0])
-      for (int64_t k = 0; k < Ks; ++k) o[c->order_s[(size_t)k]] = r[k];
-    if (double* o = outs[v][1])
-      for (int64_t k = 0; k < Kn; ++k) o[c->order_n[(size_t)k]] = r[Ks + k];
-  }
+  const size_t Kt = (size_t)(c->s.K + c->n.K);
+  std::vector<double> h;
+  if (int rc = readings_sync(c, chain, (rep || mean) ? 2 : 0, h, [&](double* d) {
+        if (int urc = upload_order(c)) return urc;
+        return launch_predictive(c, chain, theta, c->stream, seed, stream, draw, rep ? d : nullptr, mean ? d + Kt : nullptr, nullptr, 0);
+      }))
+    return rc;
+  if (h.empty()) return ABD_OK;
+  const ReadingOut out[2] = {{yrep_s, yrep_n}, {mean_s, mean_n}};
+  scatter_readings(c, out, [&](int v, size_t k) { return h[v * Kt + k]; });
   return ABD_OK;
 }
 

@@ -219,9 +219,9 @@ struct abd_ctx {
   unsigned long long* h_counts_chain = nullptr;  // ... and their pinned host copy
   bool gibbs_v1 = false;                   // ABD_GIBBS_V1=1: dense cohorts use the wave-per-proposal kernel too
   int g2_refill_min = ABD_G2_REFILL_MIN, g2_tail_lanes = ABD_G2_TAIL_LANES, g2_tail_age = ABD_G2_TAIL_AGE;  // scheduler knobs of abd_gibbs_dense_kernel (ABD_G2_*)
-  double* d_pw = nullptr;                  // staging of abd_pointwise_loglik: K_s + K_n doubles
+  double* d_stage = nullptr;               // staging of abd_pointwise_loglik / abd_posterior_predictive: stage_rows rows of K_s + K_n doubles
+  int stage_rows = 0;
   uint32_t* d_order = nullptr;             // order_s then order_n as uint32 (the predictive stream's counter), uploaded on first use
-  double* d_pp = nullptr;                  // staging of abd_posterior_predictive: replicates, then means (K_s + K_n doubles each)
   double* d_det = nullptr;                 // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
   std::vector<ResultSlot> results;
   hipStream_t stream = nullptr;
@@ -280,18 +280,39 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a);
 int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1);
 
-// Pointwise log-likelihood of chain `chain` at theta on stream st (abd_pointwise.hpp): rows ll_s / ll_n (sorted order; nullptr
-// skips) and / or the accumulators acc ([4][K_s + K_n]: S readings in columns [0, K_s), N readings after them) updated by draw
-// n_draw >= 1 (acc nullptr: not updated)
-int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc, int64_t n_draw);
+// Pointwise log-likelihood of chain `chain` at theta on stream st (abd_readings.hpp: LogLik): the row ll (sorted order, S
+// readings then N; nullptr skips) and / or the accumulators acc ([4][K_s + K_n]) updated by draw n_draw >= 1 (acc nullptr:
+// not updated)
+int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll, double* acc, int64_t n_draw);
 // The caller's reading order on the device (c->d_order), uploaded once; ABD_ERR_ARG for 2^32 readings or more of an antigen.
 // Not thread-safe: callers upload before any run loop starts.
 int upload_order(abd_ctx* c);
-// Posterior predictive of chain `chain` at theta on stream st (abd_predictive.hpp), the normals keyed by (seed, stream, draw):
-// rows yrep / mean (sorted order, S readings then N; nullptr skips) and / or the accumulators acc ([3][K_s + K_n]) updated by
-// draw n_draw >= 1 (acc nullptr: not updated).  upload_order must have succeeded.
+// Posterior predictive of chain `chain` at theta on stream st (abd_readings.hpp: Predictive), the normals keyed by (seed,
+// stream, draw): rows yrep / mean (sorted order, S readings then N; nullptr skips) and / or the accumulators acc
+// ([3][K_s + K_n]) updated by draw n_draw >= 1 (acc nullptr: not updated).  upload_order must have succeeded.
 int launch_predictive(abd_ctx* c, int chain, const double* theta, hipStream_t st, uint64_t seed, uint32_t stream, uint64_t draw,
                       double* yrep, double* mean, double* acc, int64_t n_draw);
+// R rows of per-reading values in the device's sorted order (S readings, then N) back to the caller's order of each antigen
+// (abd_create), in one pass over the readings: row v of sorted reading k is at(v, k) and goes to out[v].s (an S reading) or
+// out[v].n (an N reading); nullptr skips
+struct ReadingOut {
+  double* s;
+  double* n;
+};
+template <int R, typename At>
+void scatter_readings(const abd_ctx* c, const ReadingOut (&out)[R], At at) {
+  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K;
+  for (size_t k = 0; k < Ks; ++k) {
+    const size_t o = (size_t)c->order_s[k];
+    for (int v = 0; v < R; ++v)
+      if (out[v].s) out[v].s[o] = at(v, k);
+  }
+  for (size_t k = 0; k < Kn; ++k) {
+    const size_t o = (size_t)c->order_n[k];
+    for (int v = 0; v < R; ++v)
+      if (out[v].n) out[v].n[o] = at(v, Ks + k);
+  }
+}
 
 // ---- abd_gibbs.hip
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,

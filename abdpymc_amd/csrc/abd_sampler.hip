@@ -20,12 +20,12 @@ struct abd_sampler {
   double* d_rec_mu = nullptr;   // [2][n][rec_chunk][G*N]  (ab_n_mu, ab_s_mu)
   int8_t* d_rec_i8 = nullptr;   // [2][n][rec_chunk][G*N]  (i_raw, i) then [n][rec_chunk][N] (waner)
   double* d_rec_ll = nullptr;   // [n][rec_chunk][K_s + K_n]  pointwise log-likelihood, the device's sorted order (S, then N)
-  // pointwise log-likelihood statistics of every draw (abd_pointwise.hpp): [n][4][K_s + K_n] running max, scaled sum of
-  // exp, mean, M2 per reading
+  // pointwise log-likelihood statistics of every draw (abd_readings.hpp: LogLik): [n][4][K_s + K_n] running max, scaled sum
+  // of exp, mean, M2 per reading
   double* d_pw_acc = nullptr;
   double* d_rec_yrep = nullptr;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
-  // posterior predictive check statistics of every draw (abd_predictive.hpp): [n][3][K_s + K_n] mean, M2 of the predictive
-  // mean, mean tail probability per reading
+  // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
+  // predictive mean, mean tail probability per reading
   double* d_pp_acc = nullptr;
   bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise / _predictive are refused after that)
   std::vector<double> lp, gr;  // starting points' logp / gradient
@@ -220,6 +220,69 @@ bool train_ready(const abd_sampler* s, int u) {
   return true;
 }
 
+// Record staging of one per-reading row per draw ([n][rec_chunk][K_s + K_n]: d_rec_ll, d_rec_yrep), allocated on first use
+int alloc_rec_rows(abd_sampler* s, double*& d, const char* what) {
+  if (d) return ABD_OK;
+  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
+  const hipError_t e = hipMalloc(&d, std::max<size_t>(1, (size_t)s->n * s->rec_chunk * Kt) * sizeof(double));
+  if (e != hipSuccess) {
+    d = nullptr;
+    return fail(ABD_ERR_HIP, "record staging (%s): %s", what, hipGetErrorString(e));
+  }
+  return ABD_OK;
+}
+
+// A per-chain block of `rows` x (K_s + K_n) accumulators (abd_sampler_enable_pointwise / _predictive): the old one freed, a
+// new one allocated and zeroed if `accumulate` (after the upload of the reading order if the launches read it: `order`)
+int enable_acc(abd_sampler* s, double*& acc, int rows, int32_t accumulate, bool order, const char* what) {
+  if (s->ran) return fail(ABD_ERR_STATE, "%s accumulation must be enabled before the first abd_sampler_run call", what);
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  if (acc) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)hipFree(acc);
+    acc = nullptr;
+  }
+  if (!accumulate) return ABD_OK;
+  if (order)
+    if (int rc = upload_order(c)) return rc;
+  const size_t bytes = std::max<size_t>(1, (size_t)s->n * rows * (size_t)(c->s.K + c->n.K)) * sizeof(double);
+  hipError_t e = hipMalloc(&acc, bytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    acc = nullptr;
+    return fail(ABD_ERR_NOMEM, "%s accumulators: %zu bytes of device memory", what, bytes);
+  }
+  if (e == hipSuccess) e = hipMemsetAsync(acc, 0, bytes, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    if (acc) (void)hipFree(acc);
+    acc = nullptr;
+    return fail(ABD_ERR_HIP, "%s accumulators: %s", what, hipGetErrorString(e));
+  }
+  return ABD_OK;
+}
+
+// Chain k's block of `rows` x (K_s + K_n) accumulators, once every update has landed, as three rows in the caller's reading
+// order (S readings, then N) into out: row v of sorted reading r is at(h, v, r) of the host copy h; n_draws: the draws it holds
+template <typename At>
+int read_acc(abd_sampler* s, const double* acc, int32_t k, int rows, const char* what, double* out, int64_t* n_draws, At at) {
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!acc) return fail(ABD_ERR_STATE, "%s accumulation is not enabled (abd_sampler_enable_%s)", what, what);
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
+    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
+  const size_t Ks = (size_t)c->s.K, Kt = Ks + (size_t)c->n.K;
+  std::vector<double> h((size_t)rows * Kt);
+  if (Kt) HIP_TRY(hipMemcpy(h.data(), acc + (size_t)k * rows * Kt, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  const ReadingOut o[3] = {{out, out + Ks}, {out + Kt, out + Kt + Ks}, {out + 2 * Kt, out + 2 * Kt + Ks}};
+  scatter_readings(c, o, [hp = h.data(), at](int v, size_t r) { return at(hp, v, r); });
+  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
+  return ABD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -394,15 +457,9 @@ int record_flush_chain(abd_sampler* s, const abd_record* rec, int k, int64_t fir
   HIP_TRY(hipStreamSynchronize(st));
   for (const Rows& rw : rows)
     for (size_t d = 0; d < rw.h.size() / std::max<size_t>(Kt, 1); ++d) {
+      const ReadingOut o[1] = {{rw.out_s ? rw.out_s + (host + d) * Ks : nullptr, rw.out_n ? rw.out_n + (host + d) * Kn : nullptr}};
       const double* r = rw.h.data() + d * Kt;
-      if (rw.out_s) {
-        double* o = rw.out_s + (host + d) * Ks;
-        for (size_t k = 0; k < Ks; ++k) o[c->order_s[k]] = r[k];
-      }
-      if (rw.out_n) {
-        double* o = rw.out_n + (host + d) * Kn;
-        for (size_t k = 0; k < Kn; ++k) o[c->order_n[k]] = r[Ks + k];
-      }
+      scatter_readings(c, o, [r](int, size_t k) { return r[k]; });
     }
   return ABD_OK;
 }
@@ -475,7 +532,7 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   double* ll = (rec && (rec->ll_s || rec->ll_n)) ? s->d_rec_ll + at * Kt : nullptr;
   double* acc = (draw && s->d_pw_acc) ? s->d_pw_acc + (size_t)j * 4 * Kt : nullptr;
   if (ll || acc)
-    if (int rc = launch_pointwise(c, chain, q, st, ll, ll ? ll + c->s.K : nullptr, acc, iter - s->o.tune + 1)) return rc;
+    if (int rc = launch_pointwise(c, chain, q, st, ll, acc, iter - s->o.tune + 1)) return rc;
   // posterior predictive: the record's replicate row (keyed by seed, the chain's global id and the iteration, so that
   // abd_posterior_predictive reproduces it) and / or -- a draw, accumulation on -- the check statistics
   double* yrep = (rec && (rec->yrep_s || rec->yrep_n)) ? s->d_rec_yrep + at * Kt : nullptr;
@@ -1039,24 +1096,12 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
       s->d_rec_mu = mu;
       s->d_rec_i8 = i8;
     }
-    if (with_ll && !s->d_rec_ll) {
-      HIP_TRY(hipSetDevice(c->device));
-      const hipError_t e = hipMalloc(&s->d_rec_ll, std::max<size_t>(1, (size_t)n * s->rec_chunk * Kt) * sizeof(double));
-      if (e != hipSuccess) {
-        s->d_rec_ll = nullptr;
-        return fail(ABD_ERR_HIP, "record staging (pointwise log-likelihood): %s", hipGetErrorString(e));
-      }
-    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (with_ll)
+      if (int rc = alloc_rec_rows(s, s->d_rec_ll, "pointwise log-likelihood")) return rc;
     if (with_yrep) {
-      HIP_TRY(hipSetDevice(c->device));
-      if (int urc = upload_order(c)) return urc;
-      if (!s->d_rec_yrep) {
-        const hipError_t e = hipMalloc(&s->d_rec_yrep, std::max<size_t>(1, (size_t)n * s->rec_chunk * Kt) * sizeof(double));
-        if (e != hipSuccess) {
-          s->d_rec_yrep = nullptr;
-          return fail(ABD_ERR_HIP, "record staging (posterior predictive): %s", hipGetErrorString(e));
-        }
-      }
+      if (int rc = upload_order(c)) return rc;
+      if (int rc = alloc_rec_rows(s, s->d_rec_yrep, "posterior predictive")) return rc;
     }
   }
   RunFrame f{s, n_iter, theta, stats, recording ? rec : nullptr, recording ? std::max<int64_t>(1, rec->thin) : 1, {}, {}};
@@ -1097,101 +1142,27 @@ int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* mu_n_me
 
 int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (s->ran) return fail(ABD_ERR_STATE, "pointwise accumulation must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  if (s->d_pw_acc) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(s->d_pw_acc);
-    s->d_pw_acc = nullptr;
-  }
-  if (!accumulate) return ABD_OK;
-  const size_t bytes = std::max<size_t>(1, (size_t)s->n * 4 * (size_t)(c->s.K + c->n.K)) * sizeof(double);
-  hipError_t e = hipMalloc(&s->d_pw_acc, bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    s->d_pw_acc = nullptr;
-    return fail(ABD_ERR_NOMEM, "pointwise accumulators: %zu bytes of device memory", bytes);
-  }
-  if (e == hipSuccess) e = hipMemsetAsync(s->d_pw_acc, 0, bytes, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    if (s->d_pw_acc) (void)hipFree(s->d_pw_acc);
-    s->d_pw_acc = nullptr;
-    return fail(ABD_ERR_HIP, "pointwise accumulators: %s", hipGetErrorString(e));
-  }
-  return ABD_OK;
+  return enable_acc(s, s->d_pw_acc, 4, accumulate, false, "pointwise");
 }
 
 int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
   if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_pw_acc) return fail(ABD_ERR_STATE, "pointwise accumulation is not enabled (abd_sampler_enable_pointwise)");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
-    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
-  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
-  std::vector<double> acc(4 * Kt);
-  if (Kt) HIP_TRY(hipMemcpy(acc.data(), s->d_pw_acc + (size_t)k * 4 * Kt, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < Kt; ++r) {
-    const size_t o = r < Ks ? (size_t)c->order_s[r] : Ks + (size_t)c->order_n[r - Ks];  // the caller's order
-    out[o] = acc[r] + std::log(acc[Kt + r]);  // M + log S = log sum exp(ll)  (-inf before the first draw)
-    out[Kt + o] = acc[2 * Kt + r];
-    out[2 * Kt + o] = acc[3 * Kt + r];
-  }
-  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
-  return ABD_OK;
+  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
+  // rows M, S, mean, M2 -> M + log S = log sum exp(ll) (-inf before the first draw), mean, M2
+  return read_acc(s, s->d_pw_acc, k, 4, "pointwise", out, n_draws, [Kt](const double* h, int v, size_t r) {
+    return v == 0 ? h[r] + std::log(h[Kt + r]) : h[(v + 1) * Kt + r];
+  });
 }
 
 int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (s->ran) return fail(ABD_ERR_STATE, "predictive accumulation must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  if (s->d_pp_acc) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(s->d_pp_acc);
-    s->d_pp_acc = nullptr;
-  }
-  if (!accumulate) return ABD_OK;
-  if (int rc = upload_order(c)) return rc;
-  const size_t bytes = std::max<size_t>(1, (size_t)s->n * 3 * (size_t)(c->s.K + c->n.K)) * sizeof(double);
-  hipError_t e = hipMalloc(&s->d_pp_acc, bytes);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    s->d_pp_acc = nullptr;
-    return fail(ABD_ERR_NOMEM, "predictive accumulators: %zu bytes of device memory", bytes);
-  }
-  if (e == hipSuccess) e = hipMemsetAsync(s->d_pp_acc, 0, bytes, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    if (s->d_pp_acc) (void)hipFree(s->d_pp_acc);
-    s->d_pp_acc = nullptr;
-    return fail(ABD_ERR_HIP, "predictive accumulators: %s", hipGetErrorString(e));
-  }
-  return ABD_OK;
+  return enable_acc(s, s->d_pp_acc, 3, accumulate, true, "predictive");
 }
 
 int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
   if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_pp_acc) return fail(ABD_ERR_STATE, "predictive accumulation is not enabled (abd_sampler_enable_predictive)");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
-    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
-  const size_t Ks = (size_t)c->s.K, Kn = (size_t)c->n.K, Kt = Ks + Kn;
-  std::vector<double> acc(3 * Kt);
-  if (Kt) HIP_TRY(hipMemcpy(acc.data(), s->d_pp_acc + (size_t)k * 3 * Kt, acc.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < Kt; ++r) {
-    const size_t o = r < Ks ? (size_t)c->order_s[r] : Ks + (size_t)c->order_n[r - Ks];  // the caller's order
-    for (size_t row = 0; row < 3; ++row) out[row * Kt + o] = acc[row * Kt + r];
-  }
-  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
-  return ABD_OK;
+  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
+  return read_acc(s, s->d_pp_acc, k, 3, "predictive", out, n_draws, [Kt](const double* h, int v, size_t r) { return h[v * Kt + r]; });
 }
 
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric) {

@@ -413,20 +413,17 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         res.update(det)
     if log_likelihood:
         res["log_likelihood_it_s_lik"], res["log_likelihood_it_n_lik"] = ll["ll_s"], ll["ll_n"]
-    if waic:
-        stats_pw = [smp.pointwise_stats(c) for c in range(chains)]
-        for j, name in enumerate(("waic_lse", "waic_mean", "waic_m2")):
-            res[name] = np.stack([o[j] for o, _ in stats_pw])
-        res["waic_n_draws"] = np.array([n for _, n in stats_pw], dtype=np.int64)
-        res["waic_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
     if posterior_predictive:
         res["posterior_predictive_it_s_lik"], res["posterior_predictive_it_n_lik"] = ll["yrep_s"], ll["yrep_n"]
-    if ppc:
-        stats_pp = [smp.predictive_stats(c) for c in range(chains)]
-        for j, name in enumerate(("ppc_mean", "ppc_m2", "ppc_pit")):
-            res[name] = np.stack([o[j] for o, _ in stats_pp])
-        res["ppc_n_draws"] = np.array([n for _, n in stats_pp], dtype=np.int64)
-        res["ppc_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
+    for on, stats_of, prefix, names in ((waic, smp.pointwise_stats, "waic", ("lse", "mean", "m2")),
+                                        (ppc, smp.predictive_stats, "ppc", ("mean", "m2", "pit"))):
+        if not on:
+            continue
+        per_chain = [stats_of(c) for c in range(chains)]
+        for j, name in enumerate(names):
+            res[f"{prefix}_{name}"] = np.stack([o[j] for o, _ in per_chain])
+        res[f"{prefix}_n_draws"] = np.array([n for _, n in per_chain], dtype=np.int64)
+        res[f"{prefix}_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
     if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:

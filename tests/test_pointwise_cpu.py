@@ -1,6 +1,6 @@
 """
 WAIC from pointwise log-likelihood statistics (abdpymc_amd.compare) and the CLI / record-budget plumbing of the pointwise
-log-likelihood, without a GPU: the device's accumulator update (abd_pointwise.hpp) is restated here in numpy.
+log-likelihood, without a GPU: the device's accumulator update (abd_readings.hpp: LogLik) is restated here in numpy.
 """
 import numpy as np
 import pytest

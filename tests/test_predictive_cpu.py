@@ -31,7 +31,7 @@ def philox_np(c0, c1, c2, c3, k0, k1):
 
 
 def stream_uniforms(seed, stream, draw, antigen, r):
-    """u1, u2 of caller readings r (array) of one antigen: the counter and the 53-bit uniforms of abd_predictive.hpp."""
+    """u1, u2 of caller readings r (array) of one antigen: the counter and the 53-bit uniforms of abd_readings.hpp: Predictive."""
     r = np.asarray(r, dtype=np.uint64)
     c3 = 0x80000000 | (antigen << 30) | ((draw >> 32) & 0x3FFFFFFF)
     w = philox_np(r, stream, draw & 0xFFFFFFFF, c3, seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)

@@ -1,9 +1,10 @@
 """
-Cost of the posterior predictive check at BASELINE config 3 (dense, 10 000 individuals x 200 gaps, 4 M readings): wall time of
-a 4-chain compound sampler run with and without on-device check statistics (sample(..., ppc=True)), at two run lengths so that
-the fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both WAIC and the check on, for
-``rocprofv3 --kernel-trace --stats -- python tools/probe_predictive.py --profile``: the kernel's own time per draw and chain
-(abd_predictive_dense_kernel) next to the pointwise kernel's in the same run.  Prints one JSON line.
+Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals x 200 gaps, 4 M readings): wall time of a
+4-chain compound sampler run with and without on-device WAIC accumulation (``--leg waic``: sample(..., waic=True)) or posterior
+predictive check statistics (``--leg ppc``: sample(..., ppc=True)), alternated.  With two run lengths (``--draws 100 400``) the
+fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both on, for
+``rocprofv3 --kernel-trace --stats -- python tools/probe_readings.py --profile``: the kernel's own time per draw and chain of
+each op (abd_readings_dense_kernel<LogLik, ...>, <Predictive, ...>) in the same run.  Prints one JSON line.
 """
 import argparse
 import json
@@ -23,11 +24,12 @@ from abdpymc_amd.sampler import sample  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("waic", "ppc"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
     ap.add_argument("--tune", type=int, default=100)
-    ap.add_argument("--draws", type=int, nargs=2, default=[100, 400])
+    ap.add_argument("--draws", type=int, nargs="+", default=[100])
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
@@ -44,22 +46,25 @@ def main():
                               wall_s=time.perf_counter() - t0)))
         m.close()
         return
-    sample(m, **dict(kw, tune=5), draws=5, ppc=True)  # warm-up: code objects, allocations
-    t = {f"{leg}_{n}": [] for n in a.draws for leg in ("plain", "ppc")}
+    sample(m, **dict(kw, tune=5), draws=5, **{a.leg: True})  # warm-up: code objects, allocations
+    legs = ("plain", a.leg)
+    t = {f"{leg}_{n}": [] for n in a.draws for leg in legs}
     for _ in range(a.reps):  # alternated, so that drift hits both legs alike
         for n in a.draws:
-            for leg in ("plain", "ppc"):
+            for leg in legs:
                 t0 = time.perf_counter()
-                sample(m, draws=n, ppc=leg == "ppc", **kw)
+                sample(m, draws=n, **{a.leg: leg != "plain"}, **kw)
                 t[f"{leg}_{n}"].append(time.perf_counter() - t0)
     best = {k: min(v) for k, v in t.items()}
-    d0, d1 = a.draws
-    extra0, extra1 = best[f"ppc_{d0}"] - best[f"plain_{d0}"], best[f"ppc_{d1}"] - best[f"plain_{d1}"]
-    per_draw = (extra1 - extra0) / (d1 - d0)  # seconds per draw (all chains)
-    print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws, wall_s=t,
-                          overhead={str(n): best[f"ppc_{n}"] / best[f"plain_{n}"] - 1.0 for n in a.draws},
-                          per_draw_ms=1e3 * per_draw, per_draw_chain_us=1e6 * per_draw / a.chains,
-                          fixed_ms=1e3 * (extra0 - per_draw * d0))))
+    out = dict(leg=a.leg, inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws, wall_s=t,
+               overhead={str(n): best[f"{a.leg}_{n}"] / best[f"plain_{n}"] - 1.0 for n in a.draws})
+    if len(a.draws) == 2 and a.draws[0] != a.draws[1]:
+        d0, d1 = a.draws
+        extra0, extra1 = best[f"{a.leg}_{d0}"] - best[f"plain_{d0}"], best[f"{a.leg}_{d1}"] - best[f"plain_{d1}"]
+        per_draw = (extra1 - extra0) / (d1 - d0)  # seconds per draw (all chains)
+        out.update(per_draw_ms=1e3 * per_draw, per_draw_chain_us=1e6 * per_draw / a.chains,
+                   fixed_ms=1e3 * (extra0 - per_draw * d0))
+    print(json.dumps(out))
     m.close()
 
 
