@@ -650,7 +650,6 @@ int abd_create(const abd_desc* d, abd_ctx** out) {
   }
   c->dense_own_sum = env_int("ABD_DENSE_OWN_SUM", 1) != 0;
   CREATE_TRY(hipHostMalloc(&c->h_counts_chain, (size_t)c->n_slots * 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  c->gibbs_v1 = env_int("ABD_GIBBS_V1", 0) != 0;
   c->g2_refill_min = std::max(1, std::min(64, tune_int("ABD_G2_REFILL_MIN", ABD_G2_REFILL_MIN)));
   c->g2_tail_lanes = std::max(0, std::min(64, tune_int("ABD_G2_TAIL_LANES", ABD_G2_TAIL_LANES)));
   c->g2_tail_age = std::max(0, tune_int("ABD_G2_TAIL_AGE", ABD_G2_TAIL_AGE));

@@ -186,46 +186,58 @@ __device__ __forceinline__ void fill_ones_table(double2_t* tab, int n_entries, i
   }
 }
 
-// Integer pre-pass for one individual and one chain (abd.py:640-667) on packed words.  Works equally on
-// wave-uniform values (sparse kernel: scalar unit) and on per-lane values (dense kernel).
+// Integer pre-pass for one individual and one chain (abd.py:640-667) on packed words, in its two steps.  They work equally on
+// wave-uniform values (the list kernels and the sweep: scalar unit) and on per-lane values (dense kernel).
 //   raw/pcr : words of i_raw / pcrpos, bit b of word t <-> gap 64 t + b
-//   out     : the Deterministic "i"
-template <int MT, typename ARGS>  // MT: 64-gap words per individual; ARGS: anything with n_chunks and chunk_mask
-__device__ __forceinline__ void constrain_masks(const uint64_t (&raw)[MT], const uint64_t (&pcr)[MT],
-                                                const ARGS& a, uint64_t (&out)[MT]) {
-  uint64_t i0[MT];
-  if (a.n_chunks <= 1) {
+//
+// Step 1, i0: the infections before the three-gap pass.
+//   cmk: the chunk masks, [3][ABD_MAXT_MAX] (EvalArgs::chunk_mask; the dense sweep kernel keeps a copy in LDS)
+template <int MT>
+__device__ __forceinline__ void constrain_i0(const uint64_t (&raw)[MT], const uint64_t (&pcr)[MT], int n_chunks, const uint64_t* cmk,
+                                             uint64_t (&i0)[MT]) {
+  if (n_chunks <= 1) {
     // OneTimeChunk: where(i_raw + pcrpos > 0, 1, 0)   abd.py:643-647
 #pragma unroll
     for (int t = 0; t < MT; ++t) i0[t] = raw[t] | pcr[t];
   } else {
 #pragma unroll
     for (int t = 0; t < MT; ++t) i0[t] = 0;
-    for (int c = 0; c < a.n_chunks; ++c) {
+    for (int c = 0; c < n_chunks; ++c) {
       // mask_multiple_infections on the chunk: keep the first 1   abd.py:818
       // incorporate_pcrpos: any PCR+ in the chunk replaces the whole chunk column   abd.py:771
       bool has_pcr = false;
 #pragma unroll
-      for (int t = 0; t < MT; ++t) has_pcr |= (pcr[t] & a.chunk_mask[c][t]) != 0;
+      for (int t = 0; t < MT; ++t) has_pcr |= (pcr[t] & cmk[c * ABD_MAXT_MAX + t]) != 0;
       bool found = false;
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
-        const uint64_t cm = a.chunk_mask[c][t];
-        uint64_t r = raw[t] & cm;
-        uint64_t first = found ? 0ull : (r & (0ull - r));
+        const uint64_t cm = cmk[c * ABD_MAXT_MAX + t];
+        const uint64_t r = raw[t] & cm;
+        const uint64_t first = found ? 0ull : (r & (0ull - r));
         found |= r != 0;
         i0[t] |= has_pcr ? (pcr[t] & cm) : first;
       }
     }
   }
-  // mask_three_gaps: out[t] = in[t] unless out[t-1] | out[t-2] | out[t-3]   abd.py:560-601.
-  // Greedy over set bits in ascending order is the same recurrence: a set bit is kept iff no kept bit
-  // lies in the three gaps before it.
+}
+
+// Step 2, mask_three_gaps: out[t] = in[t] unless out[t-1] | out[t-2] | out[t-3]   abd.py:560-601.  Greedy over set bits in
+// ascending order is the same recurrence: a set bit is kept iff no kept bit lies in the three gaps before it.  The pass is
+// causal, so it can be restarted at gap p0: the kept infections before p0 (`before` = I & bits below p0) are what they were,
+// and the greedy pass goes on from the last of them over the bits of i0 at >= p0.  (p0 = 0, before = 0: the whole pass.)
+template <int MT>
+__device__ __forceinline__ void three_gaps_from(const uint64_t (&i0)[MT], const uint64_t (&before)[MT], int p0,
+                                                uint64_t (&out)[MT]) {
   int block_until = 0;
 #pragma unroll
+  for (int t = MT - 1; t >= 0; --t)
+    if (before[t] != 0 && block_until == 0) block_until = t * 64 + 63 - __builtin_clzll(before[t]) + 4;
+#pragma unroll
   for (int t = 0; t < MT; ++t) {
-    uint64_t m = i0[t];
-    uint64_t keep = 0;
+    const int rel = p0 - t * 64;  // bits >= rel of word t are at or after p0
+    const uint64_t from = rel <= 0 ? ~0ull : (rel >= 64 ? 0ull : ~((1ull << rel) - 1ull));
+    uint64_t m = i0[t] & from;
+    uint64_t keep = before[t];
     while (m) {
       const int b = __builtin_ctzll(m);
       m &= m - 1;
@@ -237,6 +249,17 @@ __device__ __forceinline__ void constrain_masks(const uint64_t (&raw)[MT], const
     }
     out[t] = keep;
   }
+}
+
+// The whole pre-pass: out = the Deterministic "i".  ARGS: anything with n_chunks and chunk_mask[3][ABD_MAXT_MAX].
+template <int MT, typename ARGS>  // MT: 64-gap words per individual
+__device__ __forceinline__ void constrain_masks(const uint64_t (&raw)[MT], const uint64_t (&pcr)[MT],
+                                                const ARGS& a, uint64_t (&out)[MT]) {
+  uint64_t i0[MT], none[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) none[t] = 0;
+  constrain_i0<MT>(raw, pcr, a.n_chunks, &a.chunk_mask[0][0], i0);
+  three_gaps_from<MT>(i0, none, 0, out);
 }
 
 template <typename R>

@@ -1,24 +1,23 @@
 // abd_gibbs.hip -- the device Gibbs sweep of the C ABI (abd_gibbs_sweep; include/abd_hip.h): what PyMC's
 // BinaryGibbsMetropolis does to [i_raw, ab_s_waner] inside pm.sample (abd.py:922).
 #include "abd_host.hpp"
-#include "abd_gibbs.hpp"
-#include "abd_gibbs2.hpp"
+#include "abd_gibbs_lists.hpp"
+#include "abd_gibbs_dense.hpp"
 
 namespace abdi {
 
 using GibbsKernel = void (*)(const GibbsArgs);
-// lanes = proposals (abd_gibbs2.hpp; `stats`: the variant with the scheduler's development counters), or the wave-per-proposal
-// kernel for 4 or 8 words per individual (<= 256 / <= 512 gaps); observation lists of at most 64 gaps -- the reference's own
-// cohorts have 26 and 31 -- get a one-word instantiation of it: it holds the individual's packed rows in scalar registers, and
-// with one word instead of four they fit (no spills; profiles/r04)
+// dense panels: lanes = proposals (abd_gibbs_dense.hpp; `stats`: the variant with the scheduler's development counters);
+// observation lists: lanes = observations (abd_gibbs_lists.hpp).  Both for 4 or 8 words per individual (<= 256 / <= 512 gaps);
+// lists of at most 64 gaps -- the reference's own cohorts have 26 and 31 -- get a one-word instantiation: it holds the
+// individual's packed rows in scalar registers, and with one word instead of four they fit (profiles/r04)
 template <typename R>
-GibbsKernel gibbs_kernel(const abd_ctx* c, bool lanes, bool stats) {
+GibbsKernel gibbs_kernel(const abd_ctx* c, bool stats) {
   const bool wide = c->nt > ABD_MAXT;
-  if (lanes && stats) return wide ? abd_gibbs_dense_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, true, ABD_MAXT>;
-  if (lanes) return wide ? abd_gibbs_dense_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, false, ABD_MAXT>;
-  if (c->dense) return wide ? abd_gibbs_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_kernel<R, true, ABD_MAXT>;
-  if (c->nt == 1) return abd_gibbs_kernel<R, false, 1>;
-  return wide ? abd_gibbs_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_kernel<R, false, ABD_MAXT>;
+  if (c->dense && stats) return wide ? abd_gibbs_dense_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, true, ABD_MAXT>;
+  if (c->dense) return wide ? abd_gibbs_dense_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, false, ABD_MAXT>;
+  if (c->nt == 1) return abd_gibbs_kernel<R, 1>;
+  return wide ? abd_gibbs_kernel<R, ABD_MAXT_MAX> : abd_gibbs_kernel<R, ABD_MAXT>;
 }
 
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
@@ -49,16 +48,15 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
   ga.tail_age = c->g2_tail_age;
   ga.stats = stats_dev;
   if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8 * sizeof(unsigned long long), st));
-  const int rbytes = c->storage == ABD_STORE_F32 ? 4 : 8;
-  int nw2 = abd_g2_waves(c->G, rbytes);  // waves of a workgroup = of a CU: as many as its LDS holds, 12 at most
-  // a one-chain sweep is a sampler unit's: with 8 waves per CU (2 per SIMD) the other units' evaluation kernels find room
-  // beside it (12 waves x 168 registers fill the CU's register file); the sweep itself 0.39 -> 0.41 ms, the compound
-  // iteration of 4 chains at config 3 6.17 -> 5.90 ms.  Trajectories do not depend on the launch shape.
-  if (m == 1) nw2 = std::max(4, std::min(nw2, tune_int("ABD_G2_WAVES_ONE", 8)));
-  const bool lanes = c->dense && !c->gibbs_v1 && nw2 >= 4;  // (4 or 8 words per individual: <= 256 / <= 512 gaps)
   dim3 grid, block(ABD_BLOCK);
   size_t lds;
-  if (lanes) {
+  if (c->dense) {
+    const int rbytes = c->storage == ABD_STORE_F32 ? 4 : 8;
+    int nw2 = abd_g2_waves(c->G, rbytes);  // waves of a workgroup = of a CU: as many as its LDS holds, 4 .. 12
+    // a one-chain sweep is a sampler unit's: with 8 waves per CU (2 per SIMD) the other units' evaluation kernels find room
+    // beside it (12 waves x 168 registers fill the CU's register file); the sweep itself 0.39 -> 0.41 ms, the compound
+    // iteration of 4 chains at config 3 6.17 -> 5.90 ms.  Trajectories do not depend on the launch shape.
+    if (m == 1) nw2 = std::max(ABD_G2_MIN_WAVES, std::min(nw2, tune_int("ABD_G2_WAVES_ONE", 8)));
     // one workgroup per CU, the individuals of a chain handed out from one queue per chain
     lds = abd_g2_lds(c->G, rbytes, nw2);
     HIP_TRY(hipMemsetAsync(work_dev, 0, (size_t)m * sizeof(unsigned int), st));
@@ -66,18 +64,20 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
     block = dim3(64 * nw2);
   } else {
     grid = dim3(std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8)), m);
-    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)ABD_WAVES_PER_BLOCK * abd_gibbs_wave_lds(c->G);
+    lds = abd_gibbs_lds(c->G);
   }
   const bool stats = stats_dev != nullptr;  // ABD_GIBBS_STATS=1
-  const GibbsKernel k = c->storage == ABD_STORE_F32 ? gibbs_kernel<float>(c, lanes, stats) : gibbs_kernel<double>(c, lanes, stats);
+  const GibbsKernel k = c->storage == ABD_STORE_F32 ? gibbs_kernel<float>(c, stats) : gibbs_kernel<double>(c, stats);
   HIP_TRY(launch_kernel(k, grid, block, lds, st, ga));
   return ABD_OK;
 }
 
 }  // namespace abdi
 
-static int gibbs_sweep_impl(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
-                            uint32_t stream_offset, int64_t* accepted, int64_t* proposed) {
+extern "C" {
+
+int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
+                    int64_t* accepted, int64_t* proposed) {
   if (!c || !chains || !theta) return fail(ABD_ERR_ARG, "NULL argument");
   int rc = check_chains(c, n, chains);
   if (rc) return rc;
@@ -91,7 +91,7 @@ static int gibbs_sweep_impl(abd_ctx* c, int32_t n, const int32_t* chains, const 
   for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
     const int m = std::min(ABD_MAX_BATCH, n - k0);
     unsigned long long* stats_dev = want_stats ? c->d_counts + (size_t)c->n_slots * 2 : nullptr;
-    rc = enqueue_gibbs(c, m, chains + k0, theta + (size_t)k0 * ABD_N_THETA, seed, sweep, stream_offset, c->stream, c->d_counts,
+    rc = enqueue_gibbs(c, m, chains + k0, theta + (size_t)k0 * ABD_N_THETA, seed, sweep, 0u, c->stream, c->d_counts,
                        c->d_work, stats_dev);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(counts.data() + (size_t)k0 * 2, c->d_counts, (size_t)m * 2 * sizeof(unsigned long long),
@@ -111,13 +111,6 @@ static int gibbs_sweep_impl(abd_ctx* c, int32_t n, const int32_t* chains, const 
     if (proposed) proposed[k] = (int64_t)counts[(size_t)k * 2 + 1];
   }
   return ABD_OK;
-}
-
-extern "C" {
-
-int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
-                    int64_t* accepted, int64_t* proposed) {
-  return gibbs_sweep_impl(c, n, chains, theta, seed, sweep, 0u, accepted, proposed);
 }
 
 }  // extern "C"

@@ -1,12 +1,11 @@
-// abd_gibbs2.hpp -- the binary Gibbs-Metropolis sweep for DENSE panels, speculative lane-per-proposal form
-// (included by abd_gibbs.hip after abd_gibbs.hpp, whose Philox stream, GibbsArgs and helpers it shares).
+// abd_gibbs_dense.hpp -- the binary Gibbs-Metropolis sweep for DENSE panels, speculative lane-per-proposal form
+// (abd_gibbs.hpp: what the sweep is, why one individual's proposals can run on their own and in which random order, and
+// everything the two sweep kernels share).
 //
-// Same sweep as abd_gibbs_kernel (PyMC's BinaryGibbsMetropolis on [i_raw, ab_s_waner], abd.py:427, 373, 922; see
-// abd_gibbs.hpp for why one individual's proposals can run on their own and in which random order), same random
-// stream, same decisions -- a different mapping onto the wave:
+// Same sweep as abd_gibbs_kernel (abd_gibbs_lists.hpp), same random stream, same decisions -- a different mapping onto the wave:
 //
-//   abd_gibbs_kernel        one proposal at a time, LANES = the 64 gaps of a round; every proposal pays whole rounds,
-//                           a wave-wide sum, and a pass over the packed words on the scalar unit
+//   abd_gibbs_kernel        one proposal at a time, LANES = the individual's observations; every proposal pays a term per
+//                           lane, a wave-wide sum, and a pass over the packed words on the scalar unit
 //   abd_gibbs_dense_kernel  LANES = PROPOSALS.  Almost every proposal is rejected (0.05 - 2 acceptances per individual
 //                           and sweep), so the next proposals in the individual's random order are evaluated
 //                           SPECULATIVELY against the current state, each by its own lane: the lane works out how the
@@ -59,7 +58,6 @@
 
 #define ABD_G2_MAX_WAVES 12  // waves of a workgroup (= of a CU: one workgroup per CU, three waves per SIMD, <= 168 registers)
 #define ABD_G2_MAX_WAVES_WIDE 8  // ... of the 512-gap kernel: its LDS holds fewer anyway, and two waves per SIMD may use 256 registers
-__host__ __device__ constexpr size_t abd_g2_pad16(size_t b) { return (b + 15) / 16 * 16; }
 __host__ __device__ constexpr int abd_g2_words(int G) { return (G + 63) / 64 > ABD_MAXT ? ABD_MAXT_MAX : ABD_MAXT; }
 // per-wave LDS bytes (12.4 KB at G = 200, fp64: LDS, not registers, decides how many waves a CU holds)
 struct G2Layout {
@@ -67,107 +65,60 @@ struct G2Layout {
 };
 __host__ __device__ constexpr G2Layout abd_g2_layout(int G, int rbytes) {
   G2Layout L{};
-  size_t b = abd_g2_pad16((size_t)G * 2 * rbytes);  // {od, log_dilution} per gap, N ...
+  size_t b = abd_gibbs_pad16((size_t)G * 2 * rbytes);  // {od, log_dilution} per gap, N ...
   L.dataS = b;
-  b += abd_g2_pad16((size_t)G * 2 * rbytes);         // ... then S
+  b += abd_gibbs_pad16((size_t)G * 2 * rbytes);         // ... then S
   L.suf = b;
-  b += abd_g2_pad16((size_t)(G + 1) * 8);            // suf[g] = -(sum of the current terms of gaps >= g); suf[G] = 0
+  b += abd_gibbs_pad16((size_t)(G + 1) * 8);            // suf[g] = -(sum of the current terms of gaps >= g); suf[G] = 0
   L.accw = b;
-  b += abd_g2_pad16((size_t)(G + 1) * 4);            // the acceptance draw's Philox word by dim
+  b += abd_gibbs_pad16((size_t)(G + 1) * 4);            // the acceptance draw's Philox word by dim
   L.plist = b;
-  b += abd_g2_pad16((size_t)(G + 1) * 2);            // proposal list: dim by position in the sweep
+  b += abd_gibbs_pad16((size_t)(G + 1) * 2);            // proposal list: dim by position in the sweep
   L.result = b;
-  b += abd_g2_pad16((size_t)(G + 1));                // result by position
+  b += abd_gibbs_pad16((size_t)(G + 1));                // result by position
   L.rows = b;
-  b += abd_g2_pad16((size_t)4 * abd_g2_words(G) * 8);  // packed rows: vaccinations, PCR+, i_raw, kept infections I
+  b += abd_gibbs_pad16((size_t)4 * abd_g2_words(G) * 8);  // packed rows: vaccinations, PCR+, i_raw, kept infections I
   L.epos = b;
-  b += abd_g2_pad16((size_t)2 * (G + 1) * 2);        // exposures in the order their responses are summed: per 64-gap word the kept infections, then the vaccinations (bit 15: a vaccination)
+  b += abd_gibbs_pad16((size_t)2 * (G + 1) * 2);        // exposures in the order their responses are summed: per 64-gap word the kept infections, then the vaccinations (bit 15: a vaccination)
   L.i0pos = b;
-  b += abd_g2_pad16((size_t)(G + 1) * 2);            // positions of i0, ascending
+  b += abd_gibbs_pad16((size_t)(G + 1) * 2);            // positions of i0, ascending
   L.ipos = b;
-  b += abd_g2_pad16((size_t)(G / 4 + 2) * 2);        // positions of the kept infections I, ascending (at most one in four gaps)
+  b += abd_gibbs_pad16((size_t)(G / 4 + 2) * 2);        // positions of the kept infections I, ascending (at most one in four gaps)
   L.tpos = b;
-  b += abd_g2_pad16((size_t)(G / 4 + 2) * 2);        // the kept infections of a proposed state the whole wave evaluates (ABD_G2_COMPLEX)
+  b += abd_gibbs_pad16((size_t)(G / 4 + 2) * 2);        // the kept infections of a proposed state the whole wave evaluates (ABD_G2_COMPLEX)
   L.vpos = b;
-  b += abd_g2_pad16((size_t)(G + 1) * 2);            // positions of the vaccinations, ascending
+  b += abd_gibbs_pad16((size_t)(G + 1) * 2);            // positions of the vaccinations, ascending
   L.inl = b;
   b += (size_t)ABD_G2_KCAP * 64 * 2;                 // [ABD_G2_KCAP][64] a lane's new kept infections from its first changed gap on
   L.total = b;
   return L;
 }
 // (the kernel lays a wave's regions out for the gap CAPACITY of its template, 256 or 512, so that their offsets are immediates)
-__host__ __device__ inline size_t abd_g2_wave_lds(int G, int rbytes) { return abd_g2_layout(G, rbytes).total; }
+__host__ __device__ constexpr size_t abd_g2_wave_lds(int G, int rbytes) { return abd_g2_layout(G, rbytes).total; }
 // LDS of the tables every wave of the workgroup shares: [2][G+1] power tables + [G+1] ones + 2^(j/1024) + the chunk masks
-__host__ __device__ inline size_t abd_g2_shared_lds(int G) {
+__host__ __device__ constexpr size_t abd_g2_shared_lds(int G) {
   return (size_t)3 * (G + 1) * sizeof(double2_t) + (size_t)ABD_EXP2_TAB * sizeof(double) + (size_t)3 * ABD_MAXT_MAX * 8;
 }
 // waves per workgroup that fit the CU's 160 KB (0: not even one)
-__host__ __device__ inline int abd_g2_waves(int G, int rbytes) {
+__host__ __device__ constexpr int abd_g2_waves(int G, int rbytes) {
   const size_t avail = (size_t)160 * 1024 - abd_g2_shared_lds(G);
   const size_t w = avail / abd_g2_wave_lds(G, rbytes);
   const size_t cap = abd_g2_words(G) > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G2_MAX_WAVES;
   return (int)(w > cap ? cap : w);
 }
-__host__ __device__ inline size_t abd_g2_lds(int G, int rbytes, int n_waves) {
+__host__ __device__ constexpr size_t abd_g2_lds(int G, int rbytes, int n_waves) {
   return abd_g2_shared_lds(G) + (size_t)n_waves * abd_g2_wave_lds(G, rbytes);
 }
-
-// i0 of constrain_infections before the three-gap pass (abd.py:643-647 one chunk; abd.py:818 + 771 per chunk otherwise).
-// Works on wave-uniform and on per-lane words alike.
-// cmk: the chunk masks, [3][ABD_MAXT_MAX] (EvalArgs::chunk_mask; the sweep kernel keeps a copy in LDS)
-template <int MT>
-__device__ __forceinline__ void constrain_i0(const uint64_t (&raw)[MT], const uint64_t (&pcr)[MT], int n_chunks, const uint64_t* cmk,
-                                             uint64_t (&i0)[MT]) {
-  if (n_chunks <= 1) {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) i0[t] = raw[t] | pcr[t];
-  } else {
-#pragma unroll
-    for (int t = 0; t < MT; ++t) i0[t] = 0;
-    for (int c = 0; c < n_chunks; ++c) {
-      bool has_pcr = false;
-#pragma unroll
-      for (int t = 0; t < MT; ++t) has_pcr |= (pcr[t] & cmk[c * ABD_MAXT_MAX + t]) != 0;
-      bool found = false;
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        const uint64_t cm = cmk[c * ABD_MAXT_MAX + t];
-        const uint64_t r = raw[t] & cm;
-        const uint64_t first = found ? 0ull : (r & (0ull - r));
-        found |= r != 0;
-        i0[t] |= has_pcr ? (pcr[t] & cm) : first;
-      }
-    }
-  }
+// Every cohort abd_create admits gets at least one wave per SIMD (the fewest: 4, fp64 from 453 gaps on), so this kernel is
+// the only sweep of dense cohorts and needs no fallback.
+#define ABD_G2_MIN_WAVES 4
+__host__ __device__ constexpr int abd_g2_fewest_waves(int rbytes) {
+  int w = ABD_G2_MAX_WAVES;
+  for (int G = 1; G <= 64 * ABD_MAXT_MAX; ++G) w = abd_g2_waves(G, rbytes) < w ? abd_g2_waves(G, rbytes) : w;
+  return w;
 }
-
-// mask_three_gaps (abd.py:560-601) restarted at gap p0: the kept infections before p0 (`before` = I & bits below p0) are
-// what they were -- the pass is causal -- and the greedy pass goes on from the last of them over the bits of i0 at >= p0.
-template <int MT>
-__device__ __forceinline__ void three_gaps_from(const uint64_t (&i0)[MT], const uint64_t (&before)[MT], int p0,
-                                                uint64_t (&out)[MT]) {
-  int block_until = 0;
-#pragma unroll
-  for (int t = MT - 1; t >= 0; --t)
-    if (before[t] != 0 && block_until == 0) block_until = t * 64 + 63 - __builtin_clzll(before[t]) + 4;
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    const int rel = p0 - t * 64;  // bits >= rel of word t are at or after p0
-    const uint64_t from = rel <= 0 ? ~0ull : (rel >= 64 ? 0ull : ~((1ull << rel) - 1ull));
-    uint64_t m = i0[t] & from;
-    uint64_t keep = before[t];
-    while (m) {
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      const int g = t * 64 + b;
-      if (g >= block_until) {
-        keep |= 1ull << b;
-        block_until = g + 4;
-      }
-    }
-    out[t] = keep;
-  }
-}
+static_assert(abd_g2_fewest_waves(4) >= ABD_G2_MIN_WAVES && abd_g2_fewest_waves(8) >= ABD_G2_MIN_WAVES,
+              "the per-wave LDS layout leaves a cohort of at most 64 * ABD_MAXT_MAX gaps fewer than one wave per SIMD");
 
 template <int MT>
 __device__ __forceinline__ int first_bit(const uint64_t (&w)[MT]) {  // position of the lowest set bit, or 1 << 20
@@ -407,11 +358,9 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
   const double theta0 = ga.theta0[c], theta7 = ga.theta7[c];
   // rho^(lane + 1) = table entry lane + 2 (only used when a previous round exists, i.e. G > 64 >= lane + 1)
   const double pwn = tabs[min(lane0 + 2, G)].x, pws_w = tabs[tstride + min(lane0 + 2, G)].x;
-  const uint32_t k0_0 = ga.seed_lo ^ (ga.sweep * 0x9E3779B9u), k1_0 = ga.seed_hi;
+  const uint32_t k0_0 = gibbs_key_lo(ga), k1_0 = ga.seed_hi;
   const uint32_t cs = ga.stream[c];
-  uint64_t* rw = const_cast<uint64_t*>(cp.rw);
-  int8_t* waner = const_cast<int8_t*>(cp.waner);
-  uint64_t* iw = const_cast<uint64_t*>(cp.iw);
+  const GibbsSlot slot = gibbs_slot(cp);
   // where the time chunks begin (abd.py:865-882; an empty chunk begins nowhere)
   int chunk_lo1 = ABD_G2_NONE, chunk_lo2 = ABD_G2_NONE;
   if (a.n_chunks > 1) {
@@ -449,17 +398,10 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
 
     // ---- this individual's discrete state and data: into LDS ----
     int firstV = ABD_G2_NONE, n_v = 0, pc0 = 0;
+    bool wj = __builtin_amdgcn_readfirstlane((int)slot.waner[j]) != 0;
     {
       uint64_t V[MT], P[MT], Rw[MT];
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        V[t] = P[t] = Rw[t] = 0;
-        if (t < nt) {
-          V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-          if (a.pw) P[t] = uniform_word(a.pw, (int64_t)t * N + j);
-          Rw[t] = uniform_word(rw, (int64_t)t * N + j);
-        }
-      }
+      gibbs_load_rows<MT>(a, slot, j, nt, V, P, Rw);
       for (int g = lane; g < G; g += 64) {  // the individual's gap axis from the individual-major copy: contiguous, 1 KB per wave load
         dataN[g] = reinterpret_cast<const YX<R>*>(a.yxi_n)[(int64_t)j * G + g];
         dataS[g] = reinterpret_cast<const YX<R>*>(a.yxi_s)[(int64_t)j * G + g];
@@ -474,17 +416,12 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
       }
       firstV = first_bit<MT>(V);
 #pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        n_v = g2_append_positions(V[t], t, lane, vpos, n_v, 0);
-        pc0 += __builtin_popcountll(Rw[t]);
-      }
+      for (int t = 0; t < MT; ++t) n_v = g2_append_positions(V[t], t, lane, vpos, n_v, 0);
+      pc0 = gibbs_state_counts<MT>(Rw, wj);  // sum(i_raw) and ab_s_waner of this individual before the sweep
     }
-    bool wj = __builtin_amdgcn_readfirstlane((int)waner[j]) != 0;
-    pc0 += wj ? (1 << 16) : 0;  // sum(i_raw) and ab_s_waner of this individual before the sweep
 
     // ---- random order of this individual's proposals ----
-    // Philox words as abd_gibbs_kernel: word 0 orders the dims (low 9 bits = the dim), word 1 < 0.8 2^32 proposes the
-    // dim, word 2 is the acceptance uniform.  Dims that are not proposed never enter the list.
+    // Dims that are not proposed never enter the list.
     int n_prop = 0, w_rank = 0;
     bool w_proposed;
     {
@@ -494,19 +431,19 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
         const int d = r * 64 + lane;
         key[r] = 0xFFFFFFFFu;
         if (d < G) {
-          const Philox4 rr = philox4x32_10((uint32_t)d, (uint32_t)j + ga.ind_offset, cs, 0u, k0, k1);
-          if (rr.w[1] < ABD_TRANSIT_P_U32) {
-            key[r] = (rr.w[0] & ~0x1FFu) | (uint32_t)d;
-            accw[d] = rr.w[2];
+          const GibbsDraw rr = gibbs_draw(ga, d, j, cs, k0, k1);
+          if (rr.proposed) {
+            key[r] = rr.key;
+            accw[d] = rr.accept;
           }
         }
         n_prop += __builtin_popcountll(__builtin_amdgcn_ballot_w64(key[r] != 0xFFFFFFFFu));
       }
       bitonic_sort<MT>(key, lane);
       // the ab_s_waner dim (dim G) takes its place among them
-      const Philox4 rwz = philox4x32_10((uint32_t)G, (uint32_t)j + ga.ind_offset, cs, 0u, k0, k1);
-      w_proposed = rwz.w[1] < ABD_TRANSIT_P_U32;
-      const uint32_t w_key = (rwz.w[0] & ~0x1FFu) | (uint32_t)G;
+      const GibbsDraw rwz = gibbs_draw(ga, G, j, cs, k0, k1);
+      w_proposed = rwz.proposed;
+      const uint32_t w_key = rwz.key;
 #pragma unroll
       for (int r = 0; r < MT; ++r) w_rank += __builtin_popcountll(__builtin_amdgcn_ballot_w64(key[r] < w_key));  // proposed i_raw dims ordered before it
       if (!w_proposed) w_rank = 1 << 20;
@@ -518,7 +455,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
       if (w_proposed) {
         if (lane == 0) {
           plist[w_rank] = (uint16_t)G;
-          accw[G] = rwz.w[2];
+          accw[G] = rwz.accept;
         }
         n_prop += 1;
       }
@@ -648,7 +585,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
           } else {
             // how the flip of raw bit d changes i0 (abd.py:643-647 / 818 + 771): one position leaves (a_rm), one enters (b_add)
             const bool was_one = ((row_r[d >> 6] >> (d & 63)) & 1ull) != 0;
-            const double delta0 = was_one ? -theta0 : theta0;  // Bernoulli(i_raw | p) on the RAW matrix (abd.py:427)
+            const double delta0 = gibbs_prior_delta(!was_one, theta0);
             int a_rm = ABD_G2_NONE, b_add = ABD_G2_NONE;
             if (nch <= 1) {
               const bool pcr_bit = a.pw != nullptr && ((row_p[d >> 6] >> (d & 63)) & 1ull) != 0;
@@ -724,7 +661,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
             }
             if (gf >= ABD_G2_NONE) {
               // the constrained infections do not change: the prior term decides
-              result[pidx] = (delta0 > 0.0 || delta0 > lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+              result[pidx] = gibbs_accept(delta0, lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
             } else if (overflow) {
               result[pidx] = ABD_G2_COMPLEX;  // more new infections than a lane holds: the whole wave evaluates it at the frontier
             } else {
@@ -791,7 +728,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
         const bool dead = fma(S, 1.0 - 1e-9, B0) < thr;
         if (dead || g >= G) {
           const double delta = B0 + S;
-          result[pidx] = (!dead && (delta > 0.0 || delta > lu)) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          result[pidx] = (!dead && gibbs_accept(delta, lu)) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
           active = false;
           finished = true;
         }
@@ -824,7 +761,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
         const double rest = wave_sum_uniform(tsum);
         if (lane == Lw) {
           const double delta = B0 + (S + rest);
-          result[pidx] = (delta > 0.0 || delta > lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          result[pidx] = gibbs_accept(delta, lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
           active = false;
         }
         dirty = true;
@@ -855,7 +792,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
           const uint16_t* il = ipos;  // the proposed state's infections: the current ones (waning flip) ...
           int nil = n_i;
           if (d == G) {
-            delta_prior = wn ? theta7 : -theta7;  // Bernoulli(waner | p_waner) abd.py:373
+            delta_prior = gibbs_prior_delta(wn, theta7);
           } else {
             // ... or those of the flipped raw row, constrained from scratch (abd.py:640-667), as a list
             uint64_t Rn[MT], P[MT], I0n[MT], In[MT], none[MT];
@@ -872,7 +809,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
             }
             constrain_i0<MT>(Rn, P, nch, cmk, I0n);
             three_gaps_from<MT>(I0n, none, 0, In);
-            delta_prior = was_one ? -theta0 : theta0;
+            delta_prior = gibbs_prior_delta(!was_one, theta0);
             nil = 0;
 #pragma unroll
             for (int t = 0; t < MT; ++t) nil = g2_append_positions(In[t], t, lane, tpos, nil, 0);
@@ -887,7 +824,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
           for (int t = 0; t < MT; ++t) tsum += term[t];
           const double delta = delta_prior + (wave_sum_uniform(tsum) - total_cur);
           const double log_u = readfirstlane_f64(log_uniform_u32(accw[d], tab_e2));
-          accepted = delta > 0.0 || delta > log_u;
+          accepted = gibbs_accept(delta, log_u);
           if (accepted && d == G) wj = wn;
         }
         if (accepted && d < G && lane == 0) row_r[d >> 6] ^= 1ull << (d & 63);
@@ -905,33 +842,18 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
     }
     n_prop_total += (unsigned int)frontier;
 
-    // ---- write the individual's state back: raw bits, waning flag, and what the slot keeps beside them (the
-    // constrained words the evaluation kernels read, the changes of sum(i_raw) and sum(ab_s_waner)) ----
-    int pc1 = wj ? (1 << 16) : 0;
+    // ---- write the individual's state back ----
+    int pc1;
     {
       uint64_t Rw[MT];
       g2_load_row<MT>(row_r, Rw);
-#pragma unroll
-      for (int t = 0; t < MT; ++t) pc1 += __builtin_popcountll(Rw[t]);
+      pc1 = gibbs_state_counts<MT>(Rw, wj);
     }
-    if (lane < nt) {
-      rw[(int64_t)lane * N + j] = row_r[lane];
-      iw[(int64_t)lane * N + j] = row_i[lane];
-    }
-    if (lane == 0) waner[j] = wj ? 1 : 0;
-    d_n1 += (pc1 & 0xFFFF) - (pc0 & 0xFFFF);
-    d_m1 += (pc1 >> 16) - (pc0 >> 16);
+    const int lw = min(lane, MT - 1);  // (lanes >= nt store nothing)
+    gibbs_store_state(slot, N, j, nt, lane, row_r[lw], row_i[lw], wj, pc0, pc1, d_n1, d_m1);
     __builtin_amdgcn_wave_barrier();
   }
-  if (lane0 == 0 && (d_n1 | d_m1)) {
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(const_cast<long long*>(cp.cnt));
-    atomicAdd(cnt + 0, (unsigned long long)(long long)d_n1);  // two's complement: a negative change wraps to the right sum
-    atomicAdd(cnt + 1, (unsigned long long)(long long)d_m1);
-  }
-  if (lane0 == 0 && (n_acc | n_prop_total)) {
-    atomicAdd(ga.counts + 2 * c + 0, (unsigned long long)n_acc);
-    atomicAdd(ga.counts + 2 * c + 1, (unsigned long long)n_prop_total);
-  }
+  gibbs_finish(ga, cp, c, lane0, d_n1, d_m1, n_acc, n_prop_total);
   if (STATS && lane0 == 0 && ga.stats) {
     atomicAdd(ga.stats + 0, st_inds);
     atomicAdd(ga.stats + 1, st_iter);

@@ -217,7 +217,6 @@ struct abd_ctx {
   unsigned int* d_work = nullptr;          // [2][n_slots] work queue heads of abd_gibbs_dense_kernel (second half: per-chain sweeps of the sampler)
   unsigned long long* d_counts_chain = nullptr;  // [n_slots][2] counts of the sampler's per-chain sweeps ...
   unsigned long long* h_counts_chain = nullptr;  // ... and their pinned host copy
-  bool gibbs_v1 = false;                   // ABD_GIBBS_V1=1: dense cohorts use the wave-per-proposal kernel too
   int g2_refill_min = ABD_G2_REFILL_MIN, g2_tail_lanes = ABD_G2_TAIL_LANES, g2_tail_age = ABD_G2_TAIL_AGE;  // scheduler knobs of abd_gibbs_dense_kernel (ABD_G2_*)
   double* d_stage = nullptr;               // staging of abd_pointwise_loglik / abd_posterior_predictive: stage_rows rows of K_s + K_n doubles
   int stage_rows = 0;

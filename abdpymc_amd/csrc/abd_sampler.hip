@@ -502,6 +502,16 @@ void write_draw(const RunFrame& f, int j, int64_t k, const unsigned long long* c
   o[ABD_STAT_T_DONE] = std::chrono::duration<double>(std::chrono::steady_clock::now() - f.t_begin).count();
 }
 
+// The sweep of iteration k of the call on the sampler's chains lo .. lo + m - 1 (slot ids `ids`, points `theta`), queued on
+// stream st: the sweep's random stream (its seed is derived from the sampler's, the chains' counter words are offset by
+// chain_offset, the sweep number is the iteration) and the chains' own counts and work-queue heads.  The counts of chain j
+// land in c->d_counts_chain + 2 j.
+int queue_sweep(abd_sampler* s, int lo, int m, const int32_t* ids, const double* theta, int64_t k, hipStream_t st) {
+  abd_ctx* c = s->c;
+  return enqueue_gibbs(c, m, ids, theta, (s->o.seed << 20) ^ 0x5EEDull, (uint32_t)(s->it + k), (uint32_t)s->o.chain_offset, st,
+                       c->d_counts_chain + 2 * (size_t)lo, c->d_work + c->n_slots + lo, nullptr);
+}
+
 // the device work of chain j's draw at iteration k of the call (point and discrete state are final), all on stream st, behind
 // the chain's sweep and in front of its next one: the Deterministics into the draw's record and / or the running sums (one
 // launch), the rest of the record, the pointwise log-likelihood, the posterior predictive.  These kernels read the discrete state and the point (by
@@ -757,10 +767,7 @@ int sampler_run_units(RunFrame& f) {
             un.who[(size_t)(j - un.lo)] = j;
             std::memcpy(un.th.data() + (size_t)(j - un.lo) * ABD_N_THETA, s->ch[(size_t)j].nuts.q, sizeof(double) * ABD_N_THETA);
           }
-          if (int rc = enqueue_gibbs(c, un.m, un.ids.data(), un.th.data(), (s->o.seed << 20) ^ 0x5EEDull, (uint32_t)(s->it + un.k),
-                                     (uint32_t)s->o.chain_offset, st, c->d_counts_chain + 2 * (size_t)un.lo,
-                                     c->d_work + c->n_slots + un.lo, nullptr))
-            return rc;
+          if (int rc = queue_sweep(s, un.lo, un.m, un.ids.data(), un.th.data(), un.k, st)) return rc;
           HIP_TRY(hipMemcpyAsync(c->h_counts_chain + 2 * (size_t)un.lo, c->d_counts_chain + 2 * (size_t)un.lo,
                                  (size_t)un.m * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
           un.state = POST;
@@ -900,9 +907,7 @@ int sampler_run_trains(RunFrame& f) {
     s->ch[(size_t)j].end_transition();
     if (s->o.gibbs) {
       const int32_t id = s->chains[(size_t)j];
-      if (int rc = enqueue_gibbs(c, 1, &id, s->ch[(size_t)j].nuts.q, (s->o.seed << 20) ^ 0x5EEDull, (uint32_t)(s->it + r.k), (uint32_t)s->o.chain_offset,
-                                 d.side, c->d_counts_chain + 2 * (size_t)j, c->d_work + c->n_slots + j, nullptr))
-        return rc;
+      if (int rc = queue_sweep(s, j, 1, &id, s->ch[(size_t)j].nuts.q, r.k, d.side)) return rc;
       d.sweep_tag += 1.0;
       hipLaunchKernelGGL(abd_sweep_done_kernel, dim3(1), dim3(64), 0, d.side, c->d_counts_chain + 2 * (size_t)j, d.done_d,
                          reinterpret_cast<double*>(d.done_d + 2), d.sweep_tag);

@@ -292,12 +292,6 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
 #ifndef ABD_TRANSIT_P_U32  // (a diagnostic build may set it to 0: a sweep that proposes nothing measures the per-individual set-up)
 #define ABD_TRANSIT_P_U32 3435973836u  // floor(0.8 * 2^32): propose iff word 1 < this   (transit_p = 0.8)
 #endif
-// per-wave LDS of abd_gibbs_kernel: sort keys u32[G+1] + order u16[G+1] + transit u8[G+1] + log u f64[G+1], each padded to 16 bytes
-__host__ __device__ inline size_t abd_gibbs_pad16(size_t b) { return (b + 15) / 16 * 16; }
-__host__ __device__ inline size_t abd_gibbs_wave_lds(int G) {
-  const size_t n = (size_t)G + 1;
-  return abd_gibbs_pad16(4 * n) + abd_gibbs_pad16(2 * n) + abd_gibbs_pad16(n) + abd_gibbs_pad16(8 * n);
-}
 
 struct GibbsArgs {
   EvalArgs e;  // panels, packed words, chain parameters (ch[k].rw / waner are updated IN PLACE)
@@ -311,11 +305,11 @@ struct GibbsArgs {
   unsigned long long* counts;      // [n_chains][2]: accepted, proposed (integer atomics: order-free)
   unsigned int* work;              // [n_chains]: next individual of each chain (abd_gibbs_dense_kernel's work queue), zeroed per launch
   unsigned long long* stats;       // nullptr, or 8 development counters of abd_gibbs_dense_kernel (ABD_GIBBS_STATS=1)
-  int32_t refill_min, tail_lanes, tail_age;  // scheduler knobs of abd_gibbs_dense_kernel (abd_gibbs2.hpp)
+  int32_t refill_min, tail_lanes, tail_age;  // scheduler knobs of abd_gibbs_dense_kernel (abd_gibbs_dense.hpp)
 };
 
 
-// scheduler constants of abd_gibbs_dense_kernel (abd_gibbs2.hpp)
+// scheduler constants of abd_gibbs_dense_kernel (abd_gibbs_dense.hpp)
 #define ABD_G2_REFILL_MIN 16         // idle lanes that trigger a refill (a refill costs ~2-3 walk steps)
 #define ABD_G2_TAIL_LANES 8          // walkers left when the whole wave starts finishing them one at a time ...
 #define ABD_G2_TAIL_AGE 6            // ... those that have survived this many gaps

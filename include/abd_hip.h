@@ -35,7 +35,7 @@ extern "C" {
  * kernels that hold an individual's gap axis in registers (observation lists, the sweep, the Deterministics) are built
  * for 4 and for 8 packed 64-bit words, so n_gaps <= 512 (abd_create refuses more with ABD_ERR_ARG; the dense evaluation
  * kernel reads words on demand and has no such limit of its own).  The reference's cohorts have 26 / 31 monthly gaps,
- * BASELINE's synthetic ones 60 / 200.  Beyond 256 gaps dense cohorts sweep with the wave-per-proposal kernel. */
+ * BASELINE's synthetic ones 60 / 200. */
 #define ABD_MAX_GAPS 512
 #define ABD_MAX_BATCH 16  /* chains per kernel launch (larger batches are split) */
 
@@ -356,7 +356,6 @@ int abd_n_pipes(abd_ctx* ctx);
  *                                            rotate over; 1 = every launch alone on the context's stream (profiling)
  *   ABD_OBS_LANES        by list density     observation lists: 1 = lane-per-observation kernel, 0 = wave-per-individual
  *   ABD_FORCE_SPARSE     0                   1 = keep a dense panel as observation lists (exercises the list kernels)
- *   ABD_GIBBS_V1         0                   1 = dense cohorts sweep with the wave-per-proposal kernel (cross-check)
  *   ABD_DENSE_OWN_SUM    1                   0 = a sampler unit's launch is summed by a second launch (same bits; no leapfrog trains then)
  *   ABD_SAMPLER_THREADS  1 dense / 4 lists   host threads that drive the native sampler's units (<= 8 are used)
  *   ABD_SAMPLER_UNIT     by cohort           chains per independent unit of the native sampler (dense: 1 up to 4 chains, 2 up to 7,

@@ -246,8 +246,8 @@ int abd_oracle_logp_dlogp(int G, int N, int n_splits, const int* splits, const i
 }
 
 /* ---------------------------------------------------------------------------------------------------
- * Binary Gibbs-Metropolis sweep over [i_raw, ab_s_waner]: CPU restatement of abd_gibbs_kernel
- * (abdpymc_amd/csrc/abd_gibbs.hpp), same Philox4x32-10 stream, same order, same acceptance rule.
+ * Binary Gibbs-Metropolis sweep over [i_raw, ab_s_waner]: CPU restatement of the sweep kernels
+ * (abdpymc_amd/csrc/abd_gibbs.hpp and the two kernels that include it), same Philox4x32-10 stream, same order, same acceptance rule.
  * Semantics: PyMC BinaryGibbsMetropolis.astep (transit_p = 0.8, shuffled dims, metrop_select) on the two
  * discrete variables (abd.py:427, 373); the per-individual delta equals the joint-logp difference
  * (tests/test_gibbs.py checks that against full joint evaluations).

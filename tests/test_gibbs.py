@@ -164,7 +164,7 @@ def test_gpu_sweep_matches_cpu_restatement_dense(G, N, splits):
 def test_gpu_sweep_dense_states_full_of_infections(G, N, splits, rate):
     """Raw states with (nearly) every gap set: the kept infections are one in four gaps, far more than a lane of the
     lane-per-proposal kernel holds for its walk (ABD_G2_KCAP) -- those proposals are evaluated by the whole wave at the
-    frontier.  Same trajectories as the CPU restatement, and as the wave-per-proposal kernel."""
+    frontier.  Same trajectories as the CPU restatement."""
     coh = oracle_cohort_from_synth(synthetic.make_cohort(N, G, seed=3 * G + N))
     co = c_oracle.COracle(coh, splits)
     ctx = _ctx(coh, splits, n_chains=1)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Gibbs sweeps on the reference's default cohort (observation lists: the wave-per-proposal kernel), for timing and
+"""Gibbs sweeps on the reference's default cohort (observation lists: abd_gibbs_kernel), for timing and
 `rocprofv3 --pmc` passes.  usage: probe_gibbs_default_cohort.py [reps] [chains]"""
 import os, sys, time
 import numpy as np

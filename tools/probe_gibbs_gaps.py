@@ -23,6 +23,5 @@ for G in [int(x) for x in sys.argv[1:]] or [200, 256, 300, 512]:
         ts.append(time.perf_counter() - t0)
         props = int(np.sum(prop))
     t = float(np.median(ts))
-    print(f"G={G}: sweep of {C} chains {1e3 * t:.2f} ms, {props} proposals, {1e9 * t / props:.2f} ns per proposal"
-          + (" (wave-per-proposal kernel)" if os.environ.get("ABD_GIBBS_V1") == "1" else ""))
+    print(f"G={G}: sweep of {C} chains {1e3 * t:.2f} ms, {props} proposals, {1e9 * t / props:.2f} ns per proposal")
     ctx.close()

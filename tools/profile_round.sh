@@ -50,10 +50,8 @@ if [ "${GIBBS:-1}" = "1" ]; then
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY -d "$OUT/gibbs_pmc" --output-format csv -- python3 tools/probe_gibbs.py 3 $arg > "$OUT/gibbs_pmc.log" 2>&1
     python3 tools/pmc_summary.py "$OUT/gibbs_pmc" gibbs > "$OUT/gibbs_${mode}_pmc_sq.txt" 2>&1
     rm -rf "$OUT/gibbs_pmc"
-    ABD_GIBBS_V1=1 python3 tools/probe_gibbs.py 10 $arg > "$OUT/gibbs_${mode}_time_wave_per_proposal_kernel.txt" 2>&1
   done
   python3 tools/probe_gibbs_gaps.py 200 256 300 512 > "$OUT/gibbs_gaps.txt" 2>&1
-  ABD_GIBBS_V1=1 python3 tools/probe_gibbs_gaps.py 200 300 >> "$OUT/gibbs_gaps.txt" 2>&1
   python3 tools/probe_gibbs_scaling.py > "$OUT/gibbs_one_chain_by_cohort_size.txt" 2>&1
   for c in 1 2 4 8 16; do ABD_PROBE_SAME_STATE=1 ABD_PROBE_THETA_ROW=5 python3 tools/probe_nuts_rate.py c3 $c 200; done > "$OUT/nuts_rate_c3.txt" 2>&1
   for u in 1 2 4; do ABD_SAMPLER_UNIT=$u ABD_PROBE_SAME_STATE=1 ABD_PROBE_THETA_ROW=5 python3 tools/probe_nuts_rate.py c3 8 200; done > "$OUT/nuts_rate_c3_8_chains_by_unit.txt" 2>&1
