@@ -5,6 +5,7 @@
 // here on the host (17 scalars), the O(G*N) data term on the device (abd_dense.hpp, abd_obs.hpp, abd_sparse.hpp).
 #include "abd_host.hpp"
 
+#include <memory>
 #include <unordered_map>
 #include "abd_small.hpp"
 
@@ -83,18 +84,18 @@ ConstrainArgs constrain_args(const abd_ctx* c) {
 
 #ifdef ABD_STAMPS
 unsigned long long* stamps_buffer() {
-  static unsigned long long* stamps = nullptr;
+  static MappedBuf<unsigned long long>& stamps = *new MappedBuf<unsigned long long>();  // lives as long as the process
   if (!stamps) {
-    (void)hipHostMalloc((void**)&stamps, 4096 * 16 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
+    (void)stamps.alloc(4096 * 16);
     if (const char* e = std::getenv("ABD_STAMPS_PTR_OUT")) {  // the probe reads the buffer through its address
       FILE* f = std::fopen(e, "w");
       if (f) {
-        std::fprintf(f, "%llu\n", (unsigned long long)(uintptr_t)stamps);
+        std::fprintf(f, "%llu\n", (unsigned long long)(uintptr_t)stamps.host());
         std::fclose(f);
       }
     }
   }
-  return stamps;
+  return stamps.dev();
 }
 #endif
 
@@ -149,16 +150,19 @@ int probe_stream_queues(abd_ctx* c) {
   // are two per queue, not three on one (the queue with the most units sets the pace of a run).
   constexpr int kCand = 2 * kMaxPipes;
   const int ns = c->n_streams;
+  Stream spare[kMaxPipes];  // candidate ns + k; whatever the exchange leaves here goes when the function returns
   hipStream_t cand[kCand] = {};
   int n_cand = ns;
   for (int pi = 0; pi < ns; ++pi) cand[pi] = c->pipe[pi].st;
-  for (; n_cand < ns + kMaxPipes; ++n_cand)
-    if (hipStreamCreateWithFlags(&cand[n_cand], hipStreamNonBlocking) != hipSuccess) {
+  for (; n_cand < ns + kMaxPipes; ++n_cand) {
+    if (spare[n_cand - ns].create() != hipSuccess) {
       (void)hipGetLastError();
       break;
     }
-  unsigned long long* d = nullptr;
-  hipError_t le = hipMalloc(&d, (size_t)kCand * 2 * sizeof(unsigned long long));
+    cand[n_cand] = spare[n_cand - ns];
+  }
+  DevBuf<unsigned long long> d;
+  hipError_t le = d.alloc((size_t)kCand * 2);
   // Stream k's wave stays for 150 + 20 k us, so the waves end at least 20 us apart and a wave that had to wait for a
   // queue starts within a few us of exactly one earlier wave's end: it is behind that one.  A wave that starts while all
   // earlier ones are still there has a queue to itself.  A host hiccup between two launches can make a stream look
@@ -189,7 +193,6 @@ int probe_stream_queues(abd_ctx* c) {
       std::copy(q_of, q_of + kCand, best);
     }
   }
-  if (d) (void)hipFree(d);
   const int nq = std::max(1, best_nq);
   // exchange: pipe 0 is the context's main stream and stays; a pipe whose queue holds more than its share gives its stream
   // up for a spare one on the queue that holds the fewest
@@ -203,20 +206,18 @@ int probe_stream_queues(abd_ctx* c) {
       for (int k = 1; k < nq; ++k)
         if (load[k] < load[q_min]) q_min = k;
       if (load[q] - load[q_min] < 2) continue;
-      int spare = -1;
-      for (int k = ns; k < n_cand && spare < 0; ++k)
-        if (!used[k] && best[k] == q_min) spare = k;
-      if (spare < 0) continue;
-      used[spare] = true;
-      std::swap(cand[pi], cand[spare]);
-      c->pipe[pi].st = cand[pi];
+      int k_spare = -1;
+      for (int k = ns; k < n_cand && k_spare < 0; ++k)
+        if (!used[k] && best[k] == q_min) k_spare = k;
+      if (k_spare < 0) continue;
+      used[k_spare] = true;
+      std::swap(c->pipe[pi].st, spare[k_spare - ns]);
+      cand[pi] = c->pipe[pi].st;
       best[pi] = q_min;
       load[q]--;
       load[q_min]++;
     }
   }
-  for (int k = ns; k < n_cand; ++k)
-    if (cand[k]) (void)hipStreamDestroy(cand[k]);
   HIP_TRY(le);
   // queue numbers in order of first appearance among the context's streams
   int renum[kCand], n_seen = 0;
@@ -242,7 +243,6 @@ int probe_stream_queues(abd_ctx* c) {
   return ABD_OK;
 }
 
-// the HIP stream (pipe) of the native sampler's unit u
 int check_chains(abd_ctx* c, int n, const int32_t* chains) {
   if (!c) return fail(ABD_ERR_ARG, "ctx is NULL");
   if (n < 1 || n > c->n_slots) return fail(ABD_ERR_ARG, "n=%d outside [1, n_chain_slots=%d]", n, c->n_slots);
@@ -299,14 +299,12 @@ int upload_antigen(abd_ctx* c, const abd_antigen_obs& o, const SortedObs& so, An
         const int64_t src = so.order[(size_t)j * G + g];
         yx[(size_t)g * N + j] = YX<R>{(R)o.od[src], (R)o.log_dilution[src]};
       }
-    HIP_TRY(hipMalloc(&d.yx, yx.size() * sizeof(YX<R>)));
-    HIP_TRY(hipMemcpy(d.yx, yx.data(), yx.size() * sizeof(YX<R>), hipMemcpyHostToDevice));
+    HIP_TRY(d.yx.upload(yx.data(), yx.size() * sizeof(YX<R>)));
     {  // the individual-major copy the sweep kernels read: element (g, j) at [j * G + g]
       std::vector<YX<R>> yxi((size_t)G * N);
       for (int j = 0; j < N; ++j)
         for (int g = 0; g < G; ++g) yxi[(size_t)j * G + g] = yx[(size_t)g * N + j];
-      HIP_TRY(hipMalloc(&d.yxi, yxi.size() * sizeof(YX<R>)));
-      HIP_TRY(hipMemcpy(d.yxi, yxi.data(), yxi.size() * sizeof(YX<R>), hipMemcpyHostToDevice));
+      HIP_TRY(d.yxi.upload(yxi.data(), yxi.size() * sizeof(YX<R>)));
     }
     // the split panels of one-chain launches: od alone + one byte per cell coding its log dilution (assays use a handful of
     // dilutions; lossless: the dictionary holds the values of the pair panel, i.e. rounded to the storage type).  Lane-group-major: element (g, j) at
@@ -339,13 +337,10 @@ int upload_antigen(abd_ctx* c, const abd_antigen_obs& o, const SortedObs& so, An
       for (size_t j = 0; j < (size_t)N; ++j)
         for (size_t g = 0; g < (size_t)G; ++g) od[cell_of(g, j)] = yx[g * N + j].y;
       d.n_dict = (int)dict.size();
-      HIP_TRY(hipMalloc(&d.od, od.size() * sizeof(R)));
-      HIP_TRY(hipMemcpy(d.od, od.data(), od.size() * sizeof(R), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc(&d.xc, code.size()));
-      HIP_TRY(hipMemcpy(d.xc, code.data(), code.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc(&d.dict, ABD_XDICT * sizeof(double)));
+      HIP_TRY(d.od.upload(od.data(), od.size() * sizeof(R)));
+      HIP_TRY(d.xc.upload(code.data(), code.size()));
       dict.resize(ABD_XDICT, 0.0);
-      HIP_TRY(hipMemcpy(d.dict, dict.data(), ABD_XDICT * sizeof(double), hipMemcpyHostToDevice));
+      HIP_TRY(d.dict.upload(dict.data(), ABD_XDICT));
     }
     return ABD_OK;
   }
@@ -359,16 +354,11 @@ int upload_antigen(abd_ctx* c, const abd_antigen_obs& o, const SortedObs& so, An
     g[k] = (uint16_t)o.idx_gap[src];
     jj[k] = (int32_t)o.idx_ind[src];
   }
-  HIP_TRY(hipMalloc(&d.j, jj.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(d.j, jj.data(), jj.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&d.y, y.size() * sizeof(R)));
-  HIP_TRY(hipMalloc(&d.x, x.size() * sizeof(R)));
-  HIP_TRY(hipMemcpy(d.y, y.data(), y.size() * sizeof(R), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d.x, x.data(), x.size() * sizeof(R), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&d.g, g.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(d.g, g.data(), g.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&d.ptr, so.ptr.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(d.ptr, so.ptr.data(), so.ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(d.j.upload(jj.data(), jj.size()));
+  HIP_TRY(d.y.upload(y.data(), y.size() * sizeof(R)));
+  HIP_TRY(d.x.upload(x.data(), x.size() * sizeof(R)));
+  HIP_TRY(d.g.upload(g.data(), g.size()));
+  HIP_TRY(d.ptr.upload(so.ptr.data(), so.ptr.size()));
   return ABD_OK;
 }
 
@@ -382,60 +372,179 @@ std::vector<uint64_t> pack_ng(const int8_t* src, int G, int N, int nt) {
   return w;
 }
 
-void free_ctx(abd_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (auto* a : {&c->s, &c->n}) {
-    if (a->y) (void)hipFree(a->y);
-    if (a->x) (void)hipFree(a->x);
-    if (a->g) (void)hipFree(a->g);
-    if (a->ptr) (void)hipFree(a->ptr);
-    if (a->j) (void)hipFree(a->j);
-    if (a->yx) (void)hipFree(a->yx);
-    if (a->od) (void)hipFree(a->od);
-    if (a->xc) (void)hipFree(a->xc);
-    if (a->yxi) (void)hipFree(a->yxi);
-    if (a->dict) (void)hipFree(a->dict);
+// ---- abd_create, step by step (each returns ABD_OK or the code of the error it has set)
+namespace {
+
+int validate_desc(const abd_desc* d) {
+  const int G = d->n_gaps, N = d->n_inds;
+  if (G < 2) return fail(ABD_ERR_ARG, "n_gaps must be >= 2 (Beta(1, n_gaps - 1) prior on p), got %d", G);
+  if (G > ABD_MAX_GAPS) return fail(ABD_ERR_ARG, "n_gaps=%d exceeds ABD_MAX_GAPS=%d", G, ABD_MAX_GAPS);
+  if (N < 1) return fail(ABD_ERR_ARG, "n_inds must be >= 1, got %d", N);
+  if ((int64_t)G * N >= (int64_t)1 << 31) return fail(ABD_ERR_ARG, "n_gaps*n_inds too large");
+  if (d->n_chain_slots < 1) return fail(ABD_ERR_ARG, "n_chain_slots must be >= 1");
+  if (d->storage != ABD_STORE_F64 && d->storage != ABD_STORE_F32) return fail(ABD_ERR_ARG, "unknown storage %d", d->storage);
+  if (!d->vacs) return fail(ABD_ERR_ARG, "vacs is NULL");
+  // check_splits (abd.py:604-622) -- same conditions, same messages
+  if (d->n_splits < 0 || d->n_splits > 2) return fail(ABD_ERR_ARG, "only implemented 1-3 time chunks (0-2 splits)");
+  for (int k = 0; k < d->n_splits; ++k)
+    if (d->splits[k] < 0) return fail(ABD_ERR_ARG, "split indexes must be positive");
+  if (d->n_splits == 2 && d->splits[0] > d->splits[1]) return fail(ABD_ERR_ARG, "splits must be in ascending order");
+  if (d->n_splits > 0 && d->splits[d->n_splits - 1] > G) return fail(ABD_ERR_ARG, "largest split must be less than n_gaps - 1, (%d)", d->splits[d->n_splits - 1]);
+  if (d->n_splits == 2 && d->splits[0] == d->splits[1]) return fail(ABD_ERR_ARG, "splits not unique");
+  for (int64_t k = 0; k < (int64_t)G * N; ++k) {
+    if ((d->vacs[k] != 0 && d->vacs[k] != 1)) return fail(ABD_ERR_ARG, "vacs must be 0/1");
+    if (d->pcrpos && d->pcrpos[k] != 0 && d->pcrpos[k] != 1) return fail(ABD_ERR_ARG, "pcrpos must be 0/1");
   }
-  if (c->vw) (void)hipFree(c->vw);
-  if (c->pw) (void)hipFree(c->pw);
-  if (c->exp2_tab) (void)hipFree(c->exp2_tab);
-  if (c->stage_gn) (void)hipFree(c->stage_gn);
-  for (auto& s : c->slots) {
-    if (s.rw) (void)hipFree(s.rw);
-    if (s.waner) (void)hipFree(s.waner);
-    if (s.iw) (void)hipFree(s.iw);
-    if (s.cnt) (void)hipFree(s.cnt);
-  }
-  for (int pi = 1; pi < kMaxPipes; ++pi)
-    if (c->pipe[pi].st) (void)hipStreamSynchronize(c->pipe[pi].st);
-  for (int pi = 0; pi < kMaxPipes; ++pi)
-    for (int b = 0; b < 2; ++b)
-      if (c->pipe[pi].partials[b]) (void)hipFree(c->pipe[pi].partials[b]);
-  for (int pi = 1; pi < kMaxPipes; ++pi) {
-    if (c->join_ev[pi]) (void)hipEventDestroy(c->join_ev[pi]);
-    if (c->pipe[pi].st) (void)hipStreamDestroy(c->pipe[pi].st);
-  }
-  if (c->h_out) (void)hipHostFree(c->h_out);
-  if (c->d_counts) (void)hipFree(c->d_counts);
-  if (c->d_work) (void)hipFree(c->d_work);
-  if (c->d_counts_chain) (void)hipFree(c->d_counts_chain);
-  if (c->d_fin_count) (void)hipFree(c->d_fin_count);
-  if (c->d_train_count) (void)hipFree(c->d_train_count);
-  if (c->h_counts_chain) (void)hipHostFree(c->h_counts_chain);
-  if (c->d_det) (void)hipFree(c->d_det);
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  if (c->d_order) (void)hipFree(c->d_order);
-  for (auto& e : c->win_end)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ev_pool) {
-    (void)hipEventDestroy(e.first);
-    (void)hipEventDestroy(e.second);
-  }
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  return ABD_OK;
 }
+
+// the cohort's sizes, the device and the context's stream, the kernels' grids (one_per_cell: both antigens fill the panel)
+int derive_sizes(abd_ctx* c, const abd_desc* d, bool one_per_cell) {
+  const int G = d->n_gaps, N = d->n_inds;
+  c->G = G;
+  c->N = N;
+  c->nt = (G + 63) / 64;
+  c->prior_const = prior_constant(G);
+  c->n_lg = (N + 63) / 64;
+  c->n_chunks = d->n_splits + 1;
+  c->storage = d->storage;
+  c->dense = one_per_cell;
+  // the dense kernel addresses the gap rows of a piece (up to G of them) with a 32-bit scalar offset (abd_dense.hpp);
+  // beyond 2^28 cells (fp64; 2^29 in fp32 storage) per GPU the cohort takes the observation-list kernels instead
+  if ((int64_t)N * (d->storage == ABD_STORE_F32 ? 8 : 16) * (G + 2) >= ((int64_t)1 << 32)) c->dense = false;
+  // ... and splits the (lane group, gap) plane by 32-bit arithmetic: row / G by a 32-bit reciprocal must be exact for every
+  // row of the plane (abd_types.hpp: abd_div_magic_exact; 6.8 M individuals at 200 gaps -- beyond the limit above anyway)
+  if (!abd_div_magic_exact((uint64_t)c->n_lg * (uint64_t)G, (uint32_t)G)) c->dense = false;
+  if (env_int("ABD_FORCE_SPARSE", 0)) c->dense = false;
+  c->ignore_pcr = d->pcrpos == nullptr;
+  c->n_slots = d->n_chain_slots;
+  {
+    const int edges[4] = {0, d->n_splits > 0 ? d->splits[0] : G, d->n_splits > 1 ? d->splits[1] : G, G};
+    for (int ch = 0; ch < c->n_chunks; ++ch) {
+      const int lo = edges[ch], hi = (ch == c->n_chunks - 1) ? G : edges[ch + 1];
+      for (int g = lo; g < hi; ++g) c->chunk_mask[ch][g >> 6] |= 1ull << (g & 63);
+    }
+  }
+
+  int dev = d->device;
+  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+  c->device = dev;
+  HIP_TRY(hipSetDevice(dev));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, dev));
+  c->n_cu = prop.multiProcessorCount;
+  snprintf(c->name, sizeof c->name, "%s %s %d CUs", prop.name, prop.gcnArchName, prop.multiProcessorCount);
+  HIP_TRY(c->pipe[0].st.create());
+  c->stream = c->pipe[0].st;
+
+  // sparse kernel: persistent waves, one individual at a time
+  const int bpc = std::max(1, tune_int("ABD_BLOCKS_PER_CU", 2));
+  const int sparse_max = std::max(1, std::min((N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 16));
+  c->blocks_x = std::max(1, std::min(sparse_max, c->n_cu * bpc));
+  // dense kernel: 4 workgroups per CU = 4 waves per SIMD (<= 128 VGPRs, ~29 KB LDS each): one round, equal ranges
+  c->dbpc = std::max(1, tune_int("ABD_DENSE_BLOCKS_PER_CU", 4));
+  {
+    const int cap = c->n_cu * 8;
+    c->ob_n = (int)std::min<int64_t>((d->n.n_obs + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    c->ob_s = (int)std::min<int64_t>((d->s.n_obs + ABD_BLOCK - 1) / ABD_BLOCK, cap);
+    c->ob_c = 1;  // one workgroup carries the slot's counters (sum(i_raw), sum(ab_s_waner)) into the sums
+    // lane per observation unless the lists are so full that a wave per individual keeps its 64 lanes busy
+    // for two rounds or more and amortises the constraint pass (measured crossover, tools/bench_sparse.py)
+    c->obs_lanes = d->s.n_obs + d->n.n_obs < (int64_t)256 * N;
+    c->obs_lanes = env_int("ABD_OBS_LANES", c->obs_lanes ? 1 : 0) != 0;
+  }
+  c->blocks_max = std::max({sparse_max, c->n_cu * 16, c->ob_n + c->ob_s + c->ob_c});
+  c->dense_blocks = std::min(c->n_cu * c->dbpc, c->blocks_max);
+  if (dense_lds_bytes(G, 4) > 160 * 1024) return fail(ABD_ERR_ARG, "LDS tables for n_gaps=%d do not fit", G);
+  return ABD_OK;
+}
+
+// the read-only panels: both antigens' readings, vaccinations, PCR positives, the 2^(j/1024) table, the upload staging
+int upload_panels(abd_ctx* c, const abd_desc* d, SortedObs& so_s, SortedObs& so_n) {
+  const int G = c->G, N = c->N;
+  const auto upload = c->storage == ABD_STORE_F32 ? upload_antigen<float> : upload_antigen<double>;
+  if (int rc = upload(c, d->s, so_s, c->s)) return rc;
+  if (int rc = upload(c, d->n, so_n, c->n)) return rc;
+  c->order_s = std::move(so_s.order);  // sorted position -> caller's index (abd_eval.hip: scatter_readings)
+  c->order_n = std::move(so_n.order);
+  c->xc_ok = c->dense && c->s.od && c->n.od;
+  c->xc_max_cb = tune_int("ABD_XC_MAX_CB", c->xc_max_cb);
+  const size_t words = (size_t)c->nt * N;
+  const std::vector<uint64_t> vw = pack_ng(d->vacs, G, N, c->nt);
+  const std::vector<uint64_t> pw = pack_ng(d->pcrpos, G, N, c->nt);
+  HIP_TRY(c->vw.upload(vw.data(), words));
+  HIP_TRY(c->pw.upload(pw.data(), words));
+  if (c->dense) {
+    // 2^(j/1024) rounded once from the 64-bit-mantissa value
+    std::vector<double> tab(ABD_EXP2_TAB);
+    for (int j = 0; j < ABD_EXP2_TAB; ++j) tab[(size_t)j] = (double)exp2l((long double)j / (long double)ABD_EXP2_TAB);
+    HIP_TRY(c->exp2_tab.upload(tab.data(), tab.size()));
+  }
+  HIP_TRY(c->stage_gn.alloc((size_t)G * N));
+  return ABD_OK;
+}
+
+int create_slots(abd_ctx* c) {
+  const size_t words = (size_t)c->nt * c->N;
+  c->slots.resize((size_t)c->n_slots);
+  for (auto& s : c->slots) {
+    HIP_TRY(s.rw.alloc(words));
+    HIP_TRY(s.waner.alloc((size_t)c->N));
+    HIP_TRY(s.iw.alloc(words));
+    HIP_TRY(s.cnt.alloc(2));
+  }
+  return ABD_OK;
+}
+
+// the pipes with their partial rows, the result rows in mapped host memory, the counters, the streams' hardware queues
+int create_pipes(abd_ctx* c) {
+  c->n_pipes = std::max(1, std::min(6, env_int("ABD_PIPES", c->n_pipes)));
+  if (!c->dense) c->n_pipes = 1;  // only the dense kernel has a grid for sharing the chip; the others just overlap
+  c->n_streams = kMaxPipes;
+  c->n_sync_slots = std::max(4, c->n_slots);
+  for (int pi = 1; pi < c->n_streams; ++pi) {
+    HIP_TRY(c->pipe[pi].st.create());
+    HIP_TRY(c->join_ev[pi].create(hipEventDisableTiming));
+  }
+  // a launch that shares the chip with the other pipes' launches gets 1/n_pipes of the workgroup slots: fewer,
+  // longer ranges, i.e. less per-range set-up for the same work
+  c->pipe_blocks = std::min(c->dense_blocks, c->n_cu * std::max(1, c->dbpc / c->n_pipes));  // measured best: 3 pipes x 1 workgroup per CU
+  if (const int pb = tune_int("ABD_PIPE_BLOCKS", 0)) c->pipe_blocks = std::max(1, std::min(pb, c->blocks_max));
+  // a sampler unit's launch: one workgroup per CU, whatever the number of units in flight -- a unit's numbers must not depend
+  // on it.  256 on gfx950 = ABD_TRAIN_ONE_LEVEL: few enough for the launch to sum its own rows (abd_eval.hip: plan_launch)
+  c->group_blocks = c->n_cu;
+  if (const int gb = tune_int("ABD_GROUP_BLOCKS_PER_CU", 0)) c->group_blocks = std::max(1, std::min(c->n_cu * gb, c->blocks_max));
+  for (int pi = 0; pi < kMaxPipes; ++pi)
+    if (c->pipe[pi].st)
+      for (int b = 0; b < 2; ++b) HIP_TRY(c->pipe[pi].partials[b].alloc((size_t)c->n_slots * c->blocks_max * ABD_NOUT));
+  c->xcd_remap = tune_int("ABD_XCD_REMAP", 1) != 0;
+  c->fin_rows = std::max(0, tune_int("ABD_FIN_ROWS", 2));
+  // COHERENT (fine-grained) on purpose: synchronous calls poll a completion tag in this memory while the stream
+  // is still running.  With hipHostMallocMapped alone the allocation is non-coherent: the GPU caches it and the
+  // two 64-byte halves of a result row could reach the host in either order (tag visible, data stale).
+  HIP_TRY(c->out.alloc((size_t)(kResultSlots + c->n_sync_slots) * c->n_slots * ABD_NOUT));
+  HIP_TRY(c->d_counts.alloc((size_t)c->n_slots * 2 + 8));  // + 8 development counters
+  HIP_TRY(c->d_work.alloc((size_t)2 * c->n_slots));
+  HIP_TRY(c->d_counts_chain.alloc((size_t)c->n_slots * 2));
+  HIP_TRY(c->d_fin_count.alloc_zero((size_t)kMaxPipes * ABD_MAX_BATCH, c->stream));
+  HIP_TRY(c->d_train_count.alloc_zero((size_t)kMaxPipes * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE, c->stream));
+  c->dense_own_sum = env_int("ABD_DENSE_OWN_SUM", 1) != 0;
+  HIP_TRY(c->h_counts_chain.alloc_pinned((size_t)c->n_slots * 2));
+  c->g2_refill_min = std::max(1, std::min(64, tune_int("ABD_G2_REFILL_MIN", ABD_G2_REFILL_MIN)));
+  c->g2_tail_lanes = std::max(0, std::min(64, tune_int("ABD_G2_TAIL_LANES", ABD_G2_TAIL_LANES)));
+  c->g2_tail_age = std::max(0, tune_int("ABD_G2_TAIL_AGE", ABD_G2_TAIL_AGE));
+  c->results.resize((size_t)kResultSlots + c->n_sync_slots);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->dense && c->n_pipes > 1) {
+    // the pipes must sit on different hardware queues (two launches in one queue run one after the other: 4 pipes on
+    // streams 0..3, two of which share a queue here, gave 143 k evals/s at config 3 against 192 k on streams 0, 1, 2, 5)
+    if (int rc = probe_stream_queues(c)) return rc;
+    c->n_pipes = std::min(c->n_pipes, c->n_queues);
+  }
+  return ABD_OK;
+}
+
+}  // namespace
 
 int launch_deterministics(abd_ctx* c, int chain, const double* theta, hipStream_t st, int8_t* out_i, double* out_mun, double* out_mus,
                           double* sums) {
@@ -462,6 +571,13 @@ int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st) {
 
 }  // namespace abdi
 
+// Quiesce: nothing on the context's streams may still use a member when the members go (abd_host.hpp)
+abd_ctx::~abd_ctx() {
+  (void)hipSetDevice(device);
+  for (Pipe& p : pipe)
+    if (p.st) (void)hipStreamSynchronize(p.st);
+}
+
 extern "C" {
 
 const char* abd_version(void) { return "abdpymc_amd hip gfx950 0.2"; }
@@ -471,206 +587,22 @@ const char* abd_last_error(void) { return last_error(); }
 int abd_create(const abd_desc* d, abd_ctx** out) {
   if (!d || !out) return fail(ABD_ERR_ARG, "desc / out is NULL");
   *out = nullptr;
-  const int G = d->n_gaps, N = d->n_inds;
-  if (G < 2) return fail(ABD_ERR_ARG, "n_gaps must be >= 2 (Beta(1, n_gaps - 1) prior on p), got %d", G);
-  if (G > ABD_MAX_GAPS) return fail(ABD_ERR_ARG, "n_gaps=%d exceeds ABD_MAX_GAPS=%d", G, ABD_MAX_GAPS);
-  if (N < 1) return fail(ABD_ERR_ARG, "n_inds must be >= 1, got %d", N);
-  if ((int64_t)G * N >= (int64_t)1 << 31) return fail(ABD_ERR_ARG, "n_gaps*n_inds too large");
-  if (d->n_chain_slots < 1) return fail(ABD_ERR_ARG, "n_chain_slots must be >= 1");
-  if (d->storage != ABD_STORE_F64 && d->storage != ABD_STORE_F32) return fail(ABD_ERR_ARG, "unknown storage %d", d->storage);
-  if (!d->vacs) return fail(ABD_ERR_ARG, "vacs is NULL");
-  // check_splits (abd.py:604-622) -- same conditions, same messages
-  if (d->n_splits < 0 || d->n_splits > 2) return fail(ABD_ERR_ARG, "only implemented 1-3 time chunks (0-2 splits)");
-  for (int k = 0; k < d->n_splits; ++k)
-    if (d->splits[k] < 0) return fail(ABD_ERR_ARG, "split indexes must be positive");
-  if (d->n_splits == 2 && d->splits[0] > d->splits[1]) return fail(ABD_ERR_ARG, "splits must be in ascending order");
-  if (d->n_splits > 0 && d->splits[d->n_splits - 1] > G) return fail(ABD_ERR_ARG, "largest split must be less than n_gaps - 1, (%d)", d->splits[d->n_splits - 1]);
-  if (d->n_splits == 2 && d->splits[0] == d->splits[1]) return fail(ABD_ERR_ARG, "splits not unique");
-  for (int64_t k = 0; k < (int64_t)G * N; ++k) {
-    if ((d->vacs[k] != 0 && d->vacs[k] != 1)) return fail(ABD_ERR_ARG, "vacs must be 0/1");
-    if (d->pcrpos && d->pcrpos[k] != 0 && d->pcrpos[k] != 1) return fail(ABD_ERR_ARG, "pcrpos must be 0/1");
-  }
-
+  if (int rc = validate_desc(d)) return rc;
   SortedObs so_s, so_n;
-  int rc = sort_obs(d->s, G, N, "s", so_s);
-  if (rc) return rc;
-  rc = sort_obs(d->n, G, N, "n", so_n);
-  if (rc) return rc;
-
-  abd_ctx* c = new (std::nothrow) abd_ctx();
+  if (int rc = sort_obs(d->s, d->n_gaps, d->n_inds, "s", so_s)) return rc;
+  if (int rc = sort_obs(d->n, d->n_gaps, d->n_inds, "n", so_n)) return rc;
+  std::unique_ptr<abd_ctx> c(new (std::nothrow) abd_ctx());  // every early return below releases the half-built context
   if (!c) return fail(ABD_ERR_NOMEM, "out of host memory");
-  c->G = G;
-  c->N = N;
-  c->nt = (G + 63) / 64;
-  c->prior_const = prior_constant(G);
-  c->n_lg = (N + 63) / 64;
-  c->n_chunks = d->n_splits + 1;
-  c->storage = d->storage;
-  c->dense = so_s.one_per_cell && so_n.one_per_cell;
-  // the dense kernel addresses the gap rows of a piece (up to G of them) with a 32-bit scalar offset (abd_dense.hpp);
-  // beyond 2^28 cells (fp64; 2^29 in fp32 storage) per GPU the cohort takes the observation-list kernels instead
-  if ((int64_t)N * (d->storage == ABD_STORE_F32 ? 8 : 16) * (G + 2) >= ((int64_t)1 << 32)) c->dense = false;
-  // ... and splits the (lane group, gap) plane by 32-bit arithmetic: row / G by a 32-bit reciprocal must be exact for every
-  // row of the plane (abd_types.hpp: abd_div_magic_exact; 6.8 M individuals at 200 gaps -- beyond the limit above anyway)
-  if (!abd_div_magic_exact((uint64_t)c->n_lg * (uint64_t)G, (uint32_t)G)) c->dense = false;
-  if (env_int("ABD_FORCE_SPARSE", 0)) c->dense = false;
-  c->ignore_pcr = d->pcrpos == nullptr;
-  c->n_slots = d->n_chain_slots;
-  {
-    const int edges[4] = {0, d->n_splits > 0 ? d->splits[0] : G, d->n_splits > 1 ? d->splits[1] : G, G};
-    for (int ch = 0; ch < c->n_chunks; ++ch) {
-      const int lo = edges[ch], hi = (ch == c->n_chunks - 1) ? G : edges[ch + 1];
-      for (int g = lo; g < hi; ++g) c->chunk_mask[ch][g >> 6] |= 1ull << (g & 63);
-    }
-  }
-
-#define CREATE_TRY(expr)                                                                            \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      fail(ABD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                    \
-      free_ctx(c);                                                                                  \
-      return ABD_ERR_HIP;                                                                           \
-    }                                                                                               \
-  } while (0)
-
-  int dev = d->device;
-  if (dev < 0) CREATE_TRY(hipGetDevice(&dev));
-  c->device = dev;
-  CREATE_TRY(hipSetDevice(dev));
-  hipDeviceProp_t prop;
-  CREATE_TRY(hipGetDeviceProperties(&prop, dev));
-  c->n_cu = prop.multiProcessorCount;
-  snprintf(c->name, sizeof c->name, "%s %s %d CUs", prop.name, prop.gcnArchName, prop.multiProcessorCount);
-  CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-
-  // sparse kernel: persistent waves, one individual at a time
-  const int bpc = std::max(1, tune_int("ABD_BLOCKS_PER_CU", 2));
-  const int sparse_max = std::max(1, std::min((N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 16));
-  c->blocks_x = std::max(1, std::min(sparse_max, c->n_cu * bpc));
-  // dense kernel: 4 workgroups per CU = 4 waves per SIMD (<= 128 VGPRs, ~29 KB LDS each): one round, equal ranges
-  const int dbpc = std::max(1, tune_int("ABD_DENSE_BLOCKS_PER_CU", 4));
-  {
-    const int cap = c->n_cu * 8;
-    c->ob_n = (int)std::min<int64_t>((d->n.n_obs + ABD_BLOCK - 1) / ABD_BLOCK, cap);
-    c->ob_s = (int)std::min<int64_t>((d->s.n_obs + ABD_BLOCK - 1) / ABD_BLOCK, cap);
-    c->ob_c = 1;  // one workgroup carries the slot's counters (sum(i_raw), sum(ab_s_waner)) into the sums
-    // lane per observation unless the lists are so full that a wave per individual keeps its 64 lanes busy
-    // for two rounds or more and amortises the constraint pass (measured crossover, tools/bench_sparse.py)
-    c->obs_lanes = d->s.n_obs + d->n.n_obs < (int64_t)256 * N;
-    c->obs_lanes = env_int("ABD_OBS_LANES", c->obs_lanes ? 1 : 0) != 0;
-  }
-  c->blocks_max = std::max({sparse_max, c->n_cu * 16, c->ob_n + c->ob_s + c->ob_c});
-  c->dense_blocks = std::min(c->n_cu * dbpc, c->blocks_max);
-  if (dense_lds_bytes(G, 4) > 160 * 1024) {
-    free_ctx(c);
-    return fail(ABD_ERR_ARG, "LDS tables for n_gaps=%d do not fit", G);
-  }
-
-  if (c->storage == ABD_STORE_F32) {
-    rc = upload_antigen<float>(c, d->s, so_s, c->s);
-    if (!rc) rc = upload_antigen<float>(c, d->n, so_n, c->n);
-  } else {
-    rc = upload_antigen<double>(c, d->s, so_s, c->s);
-    if (!rc) rc = upload_antigen<double>(c, d->n, so_n, c->n);
-  }
-  if (rc) {
-    free_ctx(c);
-    return rc;
-  }
-  c->order_s = std::move(so_s.order);  // sorted position -> caller's index (abd_eval.hip: scatter_readings)
-  c->order_n = std::move(so_n.order);
-  c->xc_ok = c->dense && c->s.od && c->n.od;
-  c->xc_max_cb = tune_int("ABD_XC_MAX_CB", c->xc_max_cb);
-  const size_t cells = (size_t)G * N;
-  const size_t words = (size_t)c->nt * N;
-  {
-    const std::vector<uint64_t> vw = pack_ng(d->vacs, G, N, c->nt);
-    const std::vector<uint64_t> pw = pack_ng(d->pcrpos, G, N, c->nt);
-    CREATE_TRY(hipMalloc(&c->vw, words * sizeof(uint64_t)));
-    CREATE_TRY(hipMalloc(&c->pw, words * sizeof(uint64_t)));
-    CREATE_TRY(hipMemcpy(c->vw, vw.data(), words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(c->pw, pw.data(), words * sizeof(uint64_t), hipMemcpyHostToDevice));
-  }
-  if (c->dense) {
-    // 2^(j/1024) rounded once from the 64-bit-mantissa value
-    std::vector<double> tab(ABD_EXP2_TAB);
-    for (int j = 0; j < ABD_EXP2_TAB; ++j) tab[(size_t)j] = (double)exp2l((long double)j / (long double)ABD_EXP2_TAB);
-    CREATE_TRY(hipMalloc(&c->exp2_tab, tab.size() * sizeof(double)));
-    CREATE_TRY(hipMemcpy(c->exp2_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-  }
-  CREATE_TRY(hipMalloc(&c->stage_gn, cells));
-  c->slots.resize((size_t)c->n_slots);
-  for (auto& s : c->slots) {
-    CREATE_TRY(hipMalloc(&s.rw, words * sizeof(uint64_t)));
-    CREATE_TRY(hipMalloc(&s.waner, (size_t)N));
-    CREATE_TRY(hipMalloc(&s.iw, words * sizeof(uint64_t)));
-    CREATE_TRY(hipMalloc(&s.cnt, 2 * sizeof(long long)));
-  }
-  c->pipe[0].st = c->stream;
-  c->n_pipes = std::max(1, std::min(6, env_int("ABD_PIPES", c->n_pipes)));
-  if (!c->dense) c->n_pipes = 1;  // only the dense kernel has a grid for sharing the chip; the others just overlap
-  c->n_streams = kMaxPipes;
-  c->n_sync_slots = std::max(4, c->n_slots);
-  for (int pi = 1; pi < c->n_streams; ++pi) {
-    CREATE_TRY(hipStreamCreateWithFlags(&c->pipe[pi].st, hipStreamNonBlocking));
-    CREATE_TRY(hipEventCreateWithFlags(&c->join_ev[pi], hipEventDisableTiming));
-  }
-  // a launch that shares the chip with the other pipes' launches gets 1/n_pipes of the workgroup slots: fewer,
-  // longer ranges, i.e. less per-range set-up for the same work
-  c->pipe_blocks = std::min(c->dense_blocks, c->n_cu * std::max(1, dbpc / c->n_pipes));  // measured best: 3 pipes x 1 workgroup per CU
-  if (const int pb = tune_int("ABD_PIPE_BLOCKS", 0)) c->pipe_blocks = std::max(1, std::min(pb, c->blocks_max));
-  c->dbpc = dbpc;
-  // a sampler unit's launch: one workgroup per CU, whatever the number of units in flight -- a unit's numbers must not depend
-  // on it.  256 on gfx950 = ABD_TRAIN_ONE_LEVEL: few enough for the launch to sum its own rows (abd_eval.hip: plan_launch)
-  c->group_blocks = c->n_cu;
-  if (const int gb = tune_int("ABD_GROUP_BLOCKS_PER_CU", 0)) c->group_blocks = std::max(1, std::min(c->n_cu * gb, c->blocks_max));
-  for (int pi = 0; pi < kMaxPipes; ++pi)
-    if (c->pipe[pi].st)
-      for (int b = 0; b < 2; ++b)
-        CREATE_TRY(hipMalloc(&c->pipe[pi].partials[b], (size_t)c->n_slots * c->blocks_max * ABD_NOUT * sizeof(double)));
-  c->xcd_remap = tune_int("ABD_XCD_REMAP", 1) != 0;
-  c->fin_rows = std::max(0, tune_int("ABD_FIN_ROWS", 2));
-  const size_t out_bytes = (size_t)(kResultSlots + c->n_sync_slots) * c->n_slots * ABD_NOUT * sizeof(double);
-  // COHERENT (fine-grained) on purpose: synchronous calls poll a completion tag in this memory while the stream
-  // is still running.  With hipHostMallocMapped alone the allocation is non-coherent: the GPU caches it and the
-  // two 64-byte halves of a result row could reach the host in either order (tag visible, data stale).
-  CREATE_TRY(hipHostMalloc(&c->h_out, out_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-  std::memset(c->h_out, 0, out_bytes);
-  CREATE_TRY(hipHostGetDevicePointer((void**)&c->d_out, c->h_out, 0));
-  CREATE_TRY(hipMalloc(&c->d_counts, ((size_t)c->n_slots * 2 + 8) * sizeof(unsigned long long)));  // + 8 development counters
-  CREATE_TRY(hipMalloc(&c->d_work, (size_t)2 * c->n_slots * sizeof(unsigned int)));
-  CREATE_TRY(hipMalloc(&c->d_counts_chain, (size_t)c->n_slots * 2 * sizeof(unsigned long long)));
-  CREATE_TRY(hipMalloc(&c->d_fin_count, (size_t)kMaxPipes * ABD_MAX_BATCH * sizeof(unsigned int)));
-  CREATE_TRY(hipMemset(c->d_fin_count, 0, (size_t)kMaxPipes * ABD_MAX_BATCH * sizeof(unsigned int)));
-  {
-    const size_t tc_bytes = (size_t)kMaxPipes * (1 + ABD_TRAIN_SHARDS) * ABD_TRAIN_CNT_STRIDE * sizeof(unsigned int);
-    CREATE_TRY(hipMalloc(&c->d_train_count, tc_bytes));
-    CREATE_TRY(hipMemset(c->d_train_count, 0, tc_bytes));
-  }
-  c->dense_own_sum = env_int("ABD_DENSE_OWN_SUM", 1) != 0;
-  CREATE_TRY(hipHostMalloc(&c->h_counts_chain, (size_t)c->n_slots * 2 * sizeof(unsigned long long), hipHostMallocDefault));
-  c->g2_refill_min = std::max(1, std::min(64, tune_int("ABD_G2_REFILL_MIN", ABD_G2_REFILL_MIN)));
-  c->g2_tail_lanes = std::max(0, std::min(64, tune_int("ABD_G2_TAIL_LANES", ABD_G2_TAIL_LANES)));
-  c->g2_tail_age = std::max(0, tune_int("ABD_G2_TAIL_AGE", ABD_G2_TAIL_AGE));
-  c->results.resize((size_t)kResultSlots + c->n_sync_slots);
-  CREATE_TRY(hipStreamSynchronize(c->stream));
-  if (c->dense && c->n_pipes > 1) {
-    // the pipes must sit on different hardware queues (two launches in one queue run one after the other: 4 pipes on
-    // streams 0..3, two of which share a queue here, gave 143 k evals/s at config 3 against 192 k on streams 0, 1, 2, 5)
-    if (int prc = probe_stream_queues(c)) {
-      free_ctx(c);
-      return prc;
-    }
-    c->n_pipes = std::min(c->n_pipes, c->n_queues);
-  }
-#undef CREATE_TRY
-  *out = c;
+  if (int rc = derive_sizes(c.get(), d, so_s.one_per_cell && so_n.one_per_cell)) return rc;
+  if (int rc = upload_panels(c.get(), d, so_s, so_n)) return rc;
+  if (int rc = create_slots(c.get())) return rc;
+  if (int rc = create_pipes(c.get())) return rc;
+  *out = c.release();
   return ABD_OK;
 }
 
 int abd_destroy(abd_ctx* c) {
-  free_ctx(c);
+  delete c;
   return ABD_OK;
 }
 
@@ -693,6 +625,7 @@ int abd_set_discrete(abd_ctx* c, int32_t chain, const int8_t* i_raw, const int8_
     if (waner[j] != 0 && waner[j] != 1) return fail(ABD_ERR_ARG, "ab_s_waner must be 0/1");
   HIP_TRY(hipSetDevice(c->device));
   ChainSlot& s = c->slots[(size_t)chain];
+  long long* const cnt = s.cnt;
   // synchronous copies: the caller's buffers may be reused immediately
   if (int jrc = join_pipes(c)) return jrc;
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -705,10 +638,10 @@ int abd_set_discrete(abd_ctx* c, int32_t chain, const int8_t* i_raw, const int8_
   HIP_TRY(hipMemsetAsync(s.cnt, 0, 2 * sizeof(long long), c->stream));
   if (c->nt > ABD_MAXT)
     hipLaunchKernelGGL(abd_constrain_kernel<ABD_MAXT_MAX>, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, constrain_args(c), s.rw,
-                       s.waner, s.iw, reinterpret_cast<unsigned long long*>(s.cnt));
+                       s.waner, s.iw, reinterpret_cast<unsigned long long*>(cnt));
   else
     hipLaunchKernelGGL(abd_constrain_kernel<ABD_MAXT>, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, constrain_args(c), s.rw,
-                       s.waner, s.iw, reinterpret_cast<unsigned long long*>(s.cnt));
+                       s.waner, s.iw, reinterpret_cast<unsigned long long*>(cnt));
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   s.set = true;
@@ -724,12 +657,13 @@ int abd_flip_discrete(abd_ctx* c, int32_t chain, int64_t flat) {
   HIP_TRY(hipSetDevice(c->device));
   if (int jrc = join_pipes(c)) return jrc;
   ChainSlot& s = c->slots[(size_t)chain];
+  long long* const cnt = s.cnt;
   if (c->nt > ABD_MAXT)
     hipLaunchKernelGGL(abd_flip_kernel<ABD_MAXT_MAX>, dim3(1), dim3(1), 0, c->stream, constrain_args(c), s.rw, s.waner, s.iw,
-                       reinterpret_cast<unsigned long long*>(s.cnt), c->G, flat);
+                       reinterpret_cast<unsigned long long*>(cnt), c->G, flat);
   else
     hipLaunchKernelGGL(abd_flip_kernel<ABD_MAXT>, dim3(1), dim3(1), 0, c->stream, constrain_args(c), s.rw, s.waner, s.iw,
-                       reinterpret_cast<unsigned long long*>(s.cnt), c->G, flat);
+                       reinterpret_cast<unsigned long long*>(cnt), c->G, flat);
   HIP_TRY(hipGetLastError());
   return ABD_OK;
 }
@@ -740,7 +674,7 @@ int abd_deterministics(abd_ctx* c, int32_t chain, const double* theta, int8_t* i
   HIP_TRY(hipSetDevice(c->device));
   if (int jrc = join_pipes(c)) return jrc;
   const size_t cells = (size_t)c->G * c->N;
-  if (!c->d_det) HIP_TRY(hipMalloc(&c->d_det, cells * (2 * sizeof(double) + 1)));  // staging, kept for the next draw
+  if (!c->d_det) HIP_TRY(c->d_det.alloc(2 * cells + (cells + 7) / 8));  // staging, kept for the next draw
   double* d_n = c->d_det;
   double* d_s = c->d_det + cells;
   int8_t* d_i = reinterpret_cast<int8_t*>(c->d_det + 2 * cells);
@@ -754,7 +688,6 @@ int abd_deterministics(abd_ctx* c, int32_t chain, const double* theta, int8_t* i
   return ABD_OK;
 }
 
-// Queue one sweep launch for m <= ABD_MAX_BATCH chains on stream st (nothing is waited for): counts of chain k of the
 int abd_get_discrete(abd_ctx* c, int32_t chain, int8_t* i_raw, int8_t* waner) {
   if (!c) return fail(ABD_ERR_ARG, "ctx is NULL");
   int rc = check_chains(c, 1, &chain);

@@ -236,10 +236,10 @@ int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, c
   hipEvent_t e1 = nullptr;
   if (c->timing == 1 || (c->timing == 2 && stream_ordered && !c->win_open)) {
     if (c->ev_used == c->ev_pool.size()) {
-      hipEvent_t a0, a1;
-      HIP_TRY(hipEventCreate(&a0));
-      HIP_TRY(hipEventCreate(&a1));
-      c->ev_pool.emplace_back(a0, a1);
+      Event a0, a1;
+      HIP_TRY(a0.create());
+      HIP_TRY(a1.create());
+      c->ev_pool.emplace_back(std::move(a0), std::move(a1));
     }
     // window mode: every pipe is idle here (the previous abd_wait joined and synchronised them), so the stream of
     // the window's first launch carries its start; the end is recorded by flush_ring once all pipes have joined
@@ -273,8 +273,8 @@ int flush_ring(abd_ctx* c) {
     const size_t w = c->ev_used;
     if (c->win_end.size() < (w + 1) * kMaxPipes) {
       const size_t old_n = c->win_end.size();
-      c->win_end.resize((w + 1) * kMaxPipes, nullptr);
-      for (size_t k = old_n; k < c->win_end.size(); ++k) HIP_TRY(hipEventCreate(&c->win_end[k]));
+      c->win_end.resize((w + 1) * kMaxPipes);
+      for (size_t k = old_n; k < c->win_end.size(); ++k) HIP_TRY(c->win_end[k].create());
     }
     if (c->win_mask.size() < w + 1) c->win_mask.resize(w + 1, 0u);
     c->win_mask[w] = 0u;
@@ -293,7 +293,7 @@ int flush_ring(abd_ctx* c) {
 // Wait for the rows of a synchronous call (written into mapped host memory) by polling their completion tag;
 // falls back to a stream synchronise if it does not show up quickly.
 int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st) {
-  volatile const double* rows = c->h_out + (size_t)slot * c->n_slots * ABD_NOUT;
+  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
   // every row is written by its own workgroup (row, system-scope fence, tag), in no particular order: wait for
   // each tag.  Rows of an earlier group of the same call carry a smaller tag and count as landed once a later
   // group's rows are there (groups complete in stream order), so only the last group's tag value is awaited.
@@ -322,7 +322,7 @@ int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st) {
 // Polls; after a second hands over to a synchronise of the context's stream (which every pipe has joined by then).
 int wait_slot(abd_ctx* c, int slot) {
   const ResultSlot& r = c->results[slot];
-  volatile const double* rows = c->h_out + (size_t)slot * c->n_slots * ABD_NOUT;
+  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
   const auto t_poll = std::chrono::steady_clock::now();
   int k = r.n - 1;
   for (long spin = 0;; ++spin) {
@@ -356,7 +356,7 @@ int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* 
   r.host.resize((size_t)n);
   for (int k = 0; k < n; ++k) r.host[(size_t)k] = prepare(theta + (size_t)k * ABD_N_THETA);
   // every result row lives in mapped host memory (one PCIe write of 16 doubles + tag per chain, ~3 us inside the kernel)
-  double* rows = c->d_out + (size_t)slot * c->n_slots * ABD_NOUT;
+  double* rows = c->out.dev() + (size_t)slot * c->n_slots * ABD_NOUT;
   r.tag_first = (who.seq ? *who.seq : c->seq) + 1.0;
   if (who.kind == Caller::Stream) c->pending_slots.push_back(slot);
   for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
@@ -444,7 +444,7 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
   if (slot < 0 || slot >= kSyncSlot + c->n_sync_slots) return fail(ABD_ERR_ARG, "result slot %d outside [0, %d)", slot, kResultSlots);
   const ResultSlot& r = c->results[slot];
   if (r.n == 0) return fail(ABD_ERR_STATE, "result slot %d is empty", slot);
-  const double* rows = c->h_out + (size_t)slot * c->n_slots * ABD_NOUT;
+  const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
   for (int k = 0; k < r.n; ++k)
     assemble(c, r.host[(size_t)k], r.theta.data() + (size_t)k * ABD_N_THETA, rows + (size_t)k * ABD_NOUT, logp + k,
              (grad && r.grad) ? grad + (size_t)k * ABD_N_THETA : nullptr, with_priors);
@@ -546,13 +546,9 @@ int upload_order(abd_ctx* c) {
   std::vector<uint32_t> h((size_t)std::max<int64_t>(1, Ks + Kn));
   for (int64_t k = 0; k < Ks; ++k) h[(size_t)k] = (uint32_t)c->order_s[(size_t)k];
   for (int64_t k = 0; k < Kn; ++k) h[(size_t)(Ks + k)] = (uint32_t)c->order_n[(size_t)k];
-  uint32_t* d = nullptr;
-  HIP_TRY(hipMalloc(&d, h.size() * sizeof(uint32_t)));
-  if (hipMemcpy(d, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return fail(ABD_ERR_HIP, "posterior predictive: upload of the reading order failed");
-  }
-  c->d_order = d;
+  DevBuf<uint32_t> d;  // (c->d_order is set only once the order is there: it is the "uploaded" flag)
+  HIP_TRY(d.upload(h.data(), h.size()));
+  c->d_order = std::move(d);
   return ABD_OK;
 }
 
@@ -593,11 +589,8 @@ int readings_sync(abd_ctx* c, int32_t chain, int rows, std::vector<double>& h, F
   if (int rc = flush_ring(c)) return rc;
   const size_t Kt = (size_t)(c->s.K + c->n.K);
   if (Kt == 0 || rows == 0) return ABD_OK;
-  if (c->stage_rows < rows) {  // the staging grows to the most rows a call has needed and is kept for the next call
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->stage_rows = 0;
-    HIP_TRY(hipMalloc(&c->d_stage, (size_t)rows * Kt * sizeof(double)));
+  if (!c->d_stage || c->stage_rows < rows) {  // the staging grows to the most rows a call has needed and is kept for the next call
+    HIP_TRY(c->d_stage.alloc((size_t)rows * Kt));
     c->stage_rows = rows;
   }
   if (int rc = launch(c->d_stage)) return rc;

@@ -4,6 +4,11 @@
 //   abd_gibbs.hip    the device Gibbs sweep
 //   abd_sampler.hip  the native compound sampler (NUTS state machine in abd_nuts.hpp + the sweep)
 // Nothing here is part of the C ABI (include/abd_hip.h).
+//
+// Device resources are members of owning handles (abd_owned.hpp); nothing is freed by hand.  Teardown: the destructors of
+// abd_ctx and abd_sampler first quiesce -- set the device and synchronise every stream that may still use a member -- and
+// then the members go in reverse declaration order: the pipes (a stream, then its partial buffers) and the events are
+// declared before every other buffer, so they are the last to go.
 #pragma once
 
 #include <algorithm>
@@ -23,6 +28,7 @@
 
 #include "../../include/abd_hip.h"
 #include "abd_types.hpp"
+#include "abd_owned.hpp"
 #include "abd_terms.hpp"
 
 static_assert(ABD_MAX_BATCH == ABD_MAX_BATCH_K, "header / kernel batch size mismatch");
@@ -112,27 +118,27 @@ struct Caller {
 
 struct AntigenDev {
   int64_t K = 0;
-  void* y = nullptr;       // sparse: R[K], sorted by (ind, gap)
-  void* x = nullptr;       // sparse: R[K]
-  uint16_t* g = nullptr;   // sparse: gap per obs
-  int32_t* ptr = nullptr;  // sparse: (N+1)
-  int32_t* j = nullptr;    // sparse: individual per obs
-  void* yx = nullptr;      // dense: [G][N] of {od, log_dilution}
-  void* yxi = nullptr;     // dense: the same pairs individual-major, [N][G] (the sweep kernels' reads)
+  DevBuf<unsigned char> y;  // sparse: R[K], sorted by (ind, gap)
+  DevBuf<unsigned char> x;  // sparse: R[K]
+  DevBuf<uint16_t> g;    // sparse: gap per obs
+  DevBuf<int32_t> ptr;   // sparse: (N+1)
+  DevBuf<int32_t> j;     // sparse: individual per obs
+  DevBuf<unsigned char> yx;  // dense: [G][N] of {od, log_dilution}
+  DevBuf<unsigned char> yxi;  // dense: the same pairs individual-major, [N][G] (the sweep kernels' reads)
   // dense, when the antigen has <= 256 distinct log dilutions: the split panels of one-chain launches (abd_dense.hpp: XC)
-  void* od = nullptr;        // [lane group][G][64] od in the storage type (lane-group-major)
-  uint8_t* xc = nullptr;     // [lane group][G][64] code of the cell's log dilution
-  double* dict = nullptr;    // [n_dict] the distinct log dilutions
+  DevBuf<unsigned char> od;  // [lane group][G][64] od in the storage type (lane-group-major)
+  DevBuf<uint8_t> xc;    // [lane group][G][64] code of the cell's log dilution
+  DevBuf<double> dict;   // [n_dict] the distinct log dilutions
   int n_dict = 0;
 };
 
 struct ChainSlot {
-  uint64_t* rw = nullptr;   // [nt][N] packed i_raw
-  int8_t* waner = nullptr;  // [N]
+  DevBuf<uint64_t> rw;    // [nt][N] packed i_raw
+  DevBuf<int8_t> waner;   // [N]
   // derived from (rw, waner) and kept current by every writer of the slot (abd_set_discrete, abd_flip_discrete, the sweep
   // kernels): the constrained infections the evaluation kernels read, and {sum(i_raw), sum(ab_s_waner)}
-  uint64_t* iw = nullptr;      // [nt][N] packed i = constrain(i_raw, pcrpos)   abd.py:640-667
-  long long* cnt = nullptr;    // [2]
+  DevBuf<uint64_t> iw;     // [nt][N] packed i = constrain(i_raw, pcrpos)   abd.py:640-667
+  DevBuf<long long> cnt;   // [2]
   bool set = false;
 };
 
@@ -167,21 +173,15 @@ struct abd_ctx {
   int cpw_forced = 0;
   int dense_blocks = 0;   // dense kernel grid.x
   uint64_t chunk_mask[3][ABD_MAXT_MAX] = {};
-  AntigenDev s, n;
-  std::vector<int64_t> order_s, order_n;  // reading k of the device's sorted order is the caller's reading order_*[k]
-  uint64_t* vw = nullptr;  // [nt][N]
-  uint64_t* pw = nullptr;  // [nt][N]
-  double* exp2_tab = nullptr;  // dense cohorts: 2^(j/1024) (abd_dense.hpp)
-  int8_t* stage_gn = nullptr;  // (G, N) upload staging for i_raw
-  std::vector<ChainSlot> slots;
+  ~abd_ctx();  // quiesces; then the members below go in reverse order, pipes and events last
   // A pipe = a HIP stream with its own pair of partial buffers and at most one Pending fixed-order sum (abd_eval.hip:
   // plan_launch names who sums a launch's partial rows: Pending, FinalizeNow or Own).  Pipe 0 is the context's stream
   // (everything synchronous runs there).  Stream-ordered dense launches rotate over n_pipes pipes: the next launch on
   // the same pipe sums a launch's partials in its first workgroups, so the streams never wait for each other and the
   // head of one launch overlaps the tail of the previous one.
   struct Pipe {
-    hipStream_t st = nullptr;
-    double* partials[2] = {nullptr, nullptr};  // [n_slots][blocks_max][ABD_NOUT], alternating per launch
+    Stream st;
+    DevBuf<double> partials[2];  // [n_slots][blocks_max][ABD_NOUT], alternating per launch
     int pbuf = 0;
     bool on = false;  // pending: the fixed-order sum of the last launch's partials has not been queued yet
     int buf = 0, n = 0, blocks = 0;
@@ -189,6 +189,18 @@ struct abd_ctx {
     double tag = 0.0;
     bool busy = false;  // pipe 1: work queued since the last join with pipe 0
   } pipe[kMaxPipes];
+  hipStream_t stream = nullptr;  // = pipe[0].st, which owns it
+  Event join_ev[kMaxPipes];
+  std::vector<std::pair<Event, Event>> ev_pool;  // timing: start / end events (see `timing` below)
+  std::vector<Event> win_end;  // timing 2: [window][kMaxPipes] end of each pipe's work in the window (the window ends with the latest)
+  std::vector<uint32_t> win_mask;   // ... and which pipes had work in it
+  AntigenDev s, n;
+  std::vector<int64_t> order_s, order_n;  // reading k of the device's sorted order is the caller's reading order_*[k]
+  DevBuf<uint64_t> vw;  // [nt][N]
+  DevBuf<uint64_t> pw;  // [nt][N]
+  DevBuf<double> exp2_tab;  // dense cohorts: 2^(j/1024) (abd_dense.hpp)
+  DevBuf<int8_t> stage_gn;  // (G, N) upload staging for i_raw
+  std::vector<ChainSlot> slots;
   int n_pipes = 4;        // streams that stream-ordered dense launches rotate over (1 = everything on the context's stream); at most one per hardware queue
   int n_streams = kMaxPipes;  // pipes that exist (the native sampler gives every chain a stream: chain k -> pipe k mod 8)
   int n_sync_slots = 4;   // private result rows of synchronous calls (slot kSyncSlot) and of the sampler's chains in flight
@@ -196,43 +208,37 @@ struct abd_ctx {
   int group_blocks = 0;   // dense grid of a sampler unit's launch: one workgroup per CU, whatever the number of units
   int dbpc = 4;           // dense kernel: workgroups per CU of a launch that has the chip to itself
   int next_pipe = 0;
-  hipEvent_t join_ev[kMaxPipes] = {};
   double seq = 0.0;  // completion tags: 1, 2, 3, ... (exact in a double)
   // A sampler unit's dense launch sums its own partial rows (abd_dense.hpp; ABD_DENSE_OWN_SUM=0: second launch).  Same
   // bits; the result arrives 2-2.7 us later than from the pre-queued second launch, but the host spends 3.6 instead of
   // 7.2 us per result: config 3, evaluations/s seen by NUTS 33.6 k -> 36.9 k (1 chain), 53 k -> 59 k (8), 77 k -> 88 k (16),
   // unchanged with 4
   bool dense_own_sum = true;
-  unsigned int* d_fin_count = nullptr;  // [kMaxPipes][ABD_MAX_BATCH] zeroed counters of that sum
-  unsigned int* d_train_count = nullptr;  // [kMaxPipes][1 + ABD_TRAIN_SHARDS][ABD_TRAIN_CNT_STRIDE] zeroed counters of a dense train launch's count-in (abd_dense.hpp)
+  DevBuf<unsigned int> d_fin_count;  // [kMaxPipes][ABD_MAX_BATCH] zeroed counters of that sum
+  DevBuf<unsigned int> d_train_count;  // [kMaxPipes][1 + ABD_TRAIN_SHARDS][ABD_TRAIN_CNT_STRIDE] zeroed counters of a dense train launch's count-in (abd_dense.hpp)
   uint32_t ind_offset = 0;  // global index of this context's first individual (Gibbs random streams)
   bool xcd_remap = true;
   int fin_rows = 2;
   int steps_behind = -1;  // abd_logp_dlogp_many: steps still to be queued behind the one being queued (-1: unknown)
   double prior_const = 0.0;
-  double* h_out = nullptr;     // pinned + mapped: [kResultSlots + n_sync_slots][n_slots][ABD_NOUT]
-  double* d_out = nullptr;     // device view of h_out
+  MappedBuf<double> out;  // result rows, [kResultSlots + n_sync_slots][n_slots][ABD_NOUT]
   std::vector<int> pending_slots;  // slots queued stream-ordered since the last abd_wait
-  unsigned long long* d_counts = nullptr;  // [n_slots][2] Gibbs accepted / proposed
-  unsigned int* d_work = nullptr;          // [2][n_slots] work queue heads of abd_gibbs_dense_kernel (second half: per-chain sweeps of the sampler)
-  unsigned long long* d_counts_chain = nullptr;  // [n_slots][2] counts of the sampler's per-chain sweeps ...
-  unsigned long long* h_counts_chain = nullptr;  // ... and their pinned host copy
+  DevBuf<unsigned long long> d_counts;  // [n_slots][2] Gibbs accepted / proposed
+  DevBuf<unsigned int> d_work;             // [2][n_slots] work queue heads of abd_gibbs_dense_kernel (second half: per-chain sweeps of the sampler)
+  DevBuf<unsigned long long> d_counts_chain;  // [n_slots][2] counts of the sampler's per-chain sweeps ...
+  MappedBuf<unsigned long long> h_counts_chain;  // ... and their pinned host copy (plain pinned: host() only)
   int g2_refill_min = ABD_G2_REFILL_MIN, g2_tail_lanes = ABD_G2_TAIL_LANES, g2_tail_age = ABD_G2_TAIL_AGE;  // scheduler knobs of abd_gibbs_dense_kernel (ABD_G2_*)
-  double* d_stage = nullptr;               // staging of abd_pointwise_loglik / abd_posterior_predictive: stage_rows rows of K_s + K_n doubles
+  DevBuf<double> d_stage;                  // staging of abd_pointwise_loglik / abd_posterior_predictive: stage_rows rows of K_s + K_n doubles
   int stage_rows = 0;
-  uint32_t* d_order = nullptr;             // order_s then order_n as uint32 (the predictive stream's counter), uploaded on first use
-  double* d_det = nullptr;                 // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
+  DevBuf<uint32_t> d_order;                // order_s then order_n as uint32 (the predictive stream's counter), uploaded on first use
+  DevBuf<double> d_det;                    // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
   std::vector<ResultSlot> results;
-  hipStream_t stream = nullptr;
   // timing: 1 = HIP events around every evaluation-kernel launch, launches serialised on one stream with the full
   // grid (the isolated kernel); 2 = HIP events around every WINDOW of stream-ordered launches (first launch after an
   // abd_wait .. all pipes joined at the next abd_wait): the launch shape a stream-ordered caller really runs
   int timing = 0;
   bool win_open = false;
   int64_t win_launches = 0;  // launches inside the windows collected so far
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-  std::vector<hipEvent_t> win_end;  // timing 2: [window][kMaxPipes] end of each pipe's work in the window (the window ends with the latest)
-  std::vector<uint32_t> win_mask;   // ... and which pipes had work in it
   size_t ev_used = 0;
   double ev_total_ms = 0.0;
   int64_t ev_count = 0;

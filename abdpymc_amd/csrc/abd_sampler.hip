@@ -5,28 +5,18 @@
 #include "abd_nuts.hpp"
 
 #include <deque>
+#include <memory>
 
 struct abd_sampler {
+  ~abd_sampler();  // quiesces; then the members go in reverse order (abd_host.hpp)
   abd_ctx* c = nullptr;
   int n = 0;
   abd_sampler_opts o{};
   std::vector<int32_t> chains;
   std::vector<abdnuts::AdaptiveNuts> ch;
   int64_t it = 0;
-  double* d_sums = nullptr;  // [n][3][G*N]
-  int64_t n_accumulated = 0;
-  // recording: device staging of up to rec_chunk draws per chain, [n][rec_chunk][...] per variable
-  int64_t rec_chunk = 0;
-  double* d_rec_mu = nullptr;   // [2][n][rec_chunk][G*N]  (ab_n_mu, ab_s_mu)
-  int8_t* d_rec_i8 = nullptr;   // [2][n][rec_chunk][G*N]  (i_raw, i) then [n][rec_chunk][N] (waner)
-  double* d_rec_ll = nullptr;   // [n][rec_chunk][K_s + K_n]  pointwise log-likelihood, the device's sorted order (S, then N)
-  // pointwise log-likelihood statistics of every draw (abd_readings.hpp: LogLik): [n][4][K_s + K_n] running max, scaled sum
-  // of exp, mean, M2 per reading
-  double* d_pw_acc = nullptr;
-  double* d_rec_yrep = nullptr;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
-  // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
-  // predictive mean, mean tail probability per reading
-  double* d_pp_acc = nullptr;
+  int64_t n_accumulated = 0;  // draws in d_sums
+  int64_t rec_chunk = 0;      // recording: device staging of up to rec_chunk draws per chain, [n][rec_chunk][...] per variable
   bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise / _predictive are refused after that)
   std::vector<double> lp, gr;  // starting points' logp / gradient
   int unit = 1;                // chains per independent unit (sampler_run_units)
@@ -40,9 +30,8 @@ struct abd_sampler {
   int lookahead = 8;
   static constexpr int kTrainRing = 32;  // records per unit: > lookahead + 1
   struct TrainUnit {
-    TrainPoint* slots = nullptr;     // device, [2]
-    TrainRecord* rec_h = nullptr;    // mapped host memory, [kTrainRing] ...
-    TrainRecord* rec_d = nullptr;    // ... as the device sees it
+    DevBuf<TrainPoint> slots;        // [2]
+    MappedBuf<TrainRecord> rec;      // [kTrainRing]
     uint64_t prod = 0, cons = 0;     // launches queued / records taken (or given up: the rest of a half that ended early)
     double tags[kTrainRing] = {};
     int next_slot = 0;               // the slot the last queued launch leaves its successor's point in
@@ -57,21 +46,30 @@ struct abd_sampler {
   int dtrain_blocks = 0;     // workgroups (with a range) of a unit's launch: the unit's fixed shape
   int dtrain_lookahead = 3;  // steps of a unit the host keeps queued ahead of the oldest record it has not seen
   struct DChain {
-    TrainChain* st = nullptr;        // device
-    TrainRecord* ring_h = nullptr;   // mapped host memory [ABD_TRAIN_RING] ...
-    TrainRecord* ring_d = nullptr;   // ... as the device sees it
-    TrainBegin* begin_h = nullptr;   // mapped host memory [kBeginBlocks]
-    TrainBegin* begin_d = nullptr;
-    hipStream_t side = nullptr;      // the chain's sweep and its recording kernels
-    // mapped host memory: [0], [1] the sweep's accepted / proposed counts, [2] (as a double) the tag of the sweep they belong to
-    unsigned long long* done_h = nullptr;
-    unsigned long long* done_d = nullptr;
+    Stream side;                     // the chain's sweep and its recording kernels
+    DevBuf<TrainChain> st;
+    MappedBuf<TrainRecord> ring;     // [ABD_TRAIN_RING]
+    MappedBuf<TrainBegin> begin;     // [kBeginBlocks]
+    // [0], [1] the sweep's accepted / proposed counts, [2] (as a double) the tag of the sweep they belong to
+    MappedBuf<unsigned long long> done;
     double sweep_tag = 0.0;          // tag of the chain's last sweep (1, 2, 3, ...)
     int64_t n_rec = 0;               // records the steps queued so far produce (index of the next one)
     int64_t n_begin = 0;             // transitions handed over so far
   };
   static constexpr int kBeginBlocks = 4;
   std::vector<DChain> dc;
+  // device buffers, declared behind the trains' streams: they go first
+  DevBuf<double> d_sums;  // [n][3][G*N]
+  DevBuf<double> d_rec_mu;   // [2][n][rec_chunk][G*N]  (ab_n_mu, ab_s_mu)
+  DevBuf<int8_t> d_rec_i8;   // [2][n][rec_chunk][G*N]  (i_raw, i) then [n][rec_chunk][N] (waner)
+  DevBuf<double> d_rec_ll;   // [n][rec_chunk][K_s + K_n]  pointwise log-likelihood, the device's sorted order (S, then N)
+  // pointwise log-likelihood statistics of every draw (abd_readings.hpp: LogLik): [n][4][K_s + K_n] running max, scaled sum
+  // of exp, mean, M2 per reading
+  DevBuf<double> d_pw_acc;
+  DevBuf<double> d_rec_yrep;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
+  // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
+  // predictive mean, mean tail probability per reading
+  DevBuf<double> d_pp_acc;
 };
 
 namespace {
@@ -88,39 +86,12 @@ __global__ void abd_sweep_done_kernel(const unsigned long long* counts, unsigned
   }
 }
 
-// Free a sampler and everything it may own, a half-built one included, once the device is through with it
-void sampler_release(abd_sampler* s) {
-  const bool trains = !s->tu.empty() || !s->dc.empty();
-  if (trains || s->d_sums || s->d_rec_mu || s->d_rec_i8 || s->d_rec_ll || s->d_pw_acc || s->d_rec_yrep || s->d_pp_acc) {
-    (void)hipSetDevice(s->c->device);
-    // launches of a half that ended early may still be on their way; the buffers' last users are on the context's stream
-    (void)(trains ? hipDeviceSynchronize() : hipStreamSynchronize(s->c->stream));
-  }
-  for (auto& t : s->tu) {
-    if (t.slots) (void)hipFree(t.slots);
-    if (t.rec_h) (void)hipHostFree(t.rec_h);
-  }
-  for (auto& d : s->dc) {
-    if (d.st) (void)hipFree(d.st);
-    if (d.ring_h) (void)hipHostFree(d.ring_h);
-    if (d.begin_h) (void)hipHostFree(d.begin_h);
-    if (d.done_h) (void)hipHostFree(d.done_h);
-    if (d.side) (void)hipStreamDestroy(d.side);
-  }
-  for (void* p : {(void*)s->d_sums, (void*)s->d_rec_mu, (void*)s->d_rec_i8, (void*)s->d_rec_ll, (void*)s->d_pw_acc,
-                  (void*)s->d_rec_yrep, (void*)s->d_pp_acc})
-    if (p) (void)hipFree(p);
-  delete s;
-}
-
 int train_alloc(abd_sampler* s) {
   s->tu.resize((size_t)s->n);
   for (auto& t : s->tu) {
-    HIP_TRY(hipMalloc(&t.slots, 2 * sizeof(TrainPoint)));
+    HIP_TRY(t.slots.alloc(2));
     HIP_TRY(hipMemset(t.slots, 0, 2 * sizeof(TrainPoint)));
-    HIP_TRY(hipHostMalloc((void**)&t.rec_h, abd_sampler::kTrainRing * sizeof(TrainRecord), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(t.rec_h, 0, abd_sampler::kTrainRing * sizeof(TrainRecord));
-    HIP_TRY(hipHostGetDevicePointer((void**)&t.rec_d, t.rec_h, 0));
+    HIP_TRY(t.rec.alloc(abd_sampler::kTrainRing));
   }
   return ABD_OK;
 }
@@ -128,18 +99,11 @@ int train_alloc(abd_sampler* s) {
 int dtrain_alloc(abd_sampler* s) {
   s->dc.resize((size_t)s->n);
   for (auto& d : s->dc) {
-    HIP_TRY(hipMalloc(&d.st, sizeof(TrainChain)));
-    HIP_TRY(hipMemset(d.st, 0, sizeof(TrainChain)));
-    HIP_TRY(hipHostMalloc((void**)&d.ring_h, ABD_TRAIN_RING * sizeof(TrainRecord), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(d.ring_h, 0, ABD_TRAIN_RING * sizeof(TrainRecord));
-    HIP_TRY(hipHostGetDevicePointer((void**)&d.ring_d, d.ring_h, 0));
-    HIP_TRY(hipHostMalloc((void**)&d.begin_h, abd_sampler::kBeginBlocks * sizeof(TrainBegin), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(d.begin_h, 0, abd_sampler::kBeginBlocks * sizeof(TrainBegin));
-    HIP_TRY(hipHostGetDevicePointer((void**)&d.begin_d, d.begin_h, 0));
-    HIP_TRY(hipStreamCreateWithFlags(&d.side, hipStreamNonBlocking));
-    HIP_TRY(hipHostMalloc((void**)&d.done_h, 4 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(d.done_h, 0, 4 * sizeof(unsigned long long));
-    HIP_TRY(hipHostGetDevicePointer((void**)&d.done_d, d.done_h, 0));
+    HIP_TRY(d.st.alloc_zero(1, s->c->stream));  // (waited for below)
+    HIP_TRY(d.ring.alloc(ABD_TRAIN_RING));
+    HIP_TRY(d.begin.alloc(abd_sampler::kBeginBlocks));
+    HIP_TRY(d.side.create());
+    HIP_TRY(d.done.alloc(4));
   }
   HIP_TRY(hipDeviceSynchronize());
   return ABD_OK;
@@ -157,7 +121,7 @@ int train_launch(abd_sampler* s, int u, const double* theta, const double* p_hal
   std::memset(&ta, 0, sizeof ta);
   ta.enabled = 1;
   ta.slots = t.slots;
-  ta.rec = t.rec_d + (t.prod % abd_sampler::kTrainRing);
+  ta.rec = t.rec.dev() + (t.prod % abd_sampler::kTrainRing);
   ta.ve = ve;
   ta.prior_const = c->prior_const;
   ta.own_record = own_record ? 1 : 0;
@@ -178,7 +142,7 @@ int train_launch(abd_sampler* s, int u, const double* theta, const double* p_hal
     ta.next_slot = t.next_slot ^ 1;
     if (!t.last_own_record) {  // the predecessor left its record beside the point: this launch passes it on
       const size_t kp = (size_t)((t.prod - 1) % abd_sampler::kTrainRing);
-      ta.fwd_rec = t.rec_d + kp;
+      ta.fwd_rec = t.rec.dev() + kp;
       ta.fwd_tag = t.tags[kp];
     }
   }
@@ -215,51 +179,43 @@ bool train_ready(const abd_sampler* s, int u) {
   const abd_sampler::TrainUnit& t = s->tu[(size_t)u];
   if (t.cons >= t.prod) return false;
   const size_t k = (size_t)(t.cons % abd_sampler::kTrainRing);
-  if (*(volatile const double*)&t.rec_h[k].tag != t.tags[k]) return false;
+  if (*(volatile const double*)&t.rec.host()[k].tag != t.tags[k]) return false;
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
   return true;
 }
 
 // Record staging of one per-reading row per draw ([n][rec_chunk][K_s + K_n]: d_rec_ll, d_rec_yrep), allocated on first use
-int alloc_rec_rows(abd_sampler* s, double*& d, const char* what) {
+int alloc_rec_rows(abd_sampler* s, DevBuf<double>& d, const char* what) {
   if (d) return ABD_OK;
   const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
-  const hipError_t e = hipMalloc(&d, std::max<size_t>(1, (size_t)s->n * s->rec_chunk * Kt) * sizeof(double));
-  if (e != hipSuccess) {
-    d = nullptr;
+  if (const hipError_t e = d.alloc(std::max<size_t>(1, (size_t)s->n * s->rec_chunk * Kt)))
     return fail(ABD_ERR_HIP, "record staging (%s): %s", what, hipGetErrorString(e));
-  }
   return ABD_OK;
 }
 
 // A per-chain block of `rows` x (K_s + K_n) accumulators (abd_sampler_enable_pointwise / _predictive): the old one freed, a
 // new one allocated and zeroed if `accumulate` (after the upload of the reading order if the launches read it: `order`)
-int enable_acc(abd_sampler* s, double*& acc, int rows, int32_t accumulate, bool order, const char* what) {
+int enable_acc(abd_sampler* s, DevBuf<double>& acc, int rows, int32_t accumulate, bool order, const char* what) {
   if (s->ran) return fail(ABD_ERR_STATE, "%s accumulation must be enabled before the first abd_sampler_run call", what);
   abd_ctx* c = s->c;
   HIP_TRY(hipSetDevice(c->device));
   if (acc) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hipFree(acc);
-    acc = nullptr;
+    acc.reset();
   }
   if (!accumulate) return ABD_OK;
   if (order)
     if (int rc = upload_order(c)) return rc;
-  const size_t bytes = std::max<size_t>(1, (size_t)s->n * rows * (size_t)(c->s.K + c->n.K)) * sizeof(double);
-  hipError_t e = hipMalloc(&acc, bytes);
+  const size_t n_acc = std::max<size_t>(1, (size_t)s->n * rows * (size_t)(c->s.K + c->n.K));
+  DevBuf<double> fresh;  // (acc stays empty unless the block is there and zeroed)
+  const hipError_t e = fresh.alloc_zero(n_acc, c->stream);
   if (e == hipErrorOutOfMemory) {
     (void)hipGetLastError();
-    acc = nullptr;
-    return fail(ABD_ERR_NOMEM, "%s accumulators: %zu bytes of device memory", what, bytes);
+    return fail(ABD_ERR_NOMEM, "%s accumulators: %zu bytes of device memory", what, n_acc * sizeof(double));
   }
-  if (e == hipSuccess) e = hipMemsetAsync(acc, 0, bytes, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    if (acc) (void)hipFree(acc);
-    acc = nullptr;
-    return fail(ABD_ERR_HIP, "%s accumulators: %s", what, hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "%s accumulators: %s", what, hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  acc = std::move(fresh);
   return ABD_OK;
 }
 
@@ -285,14 +241,20 @@ int read_acc(abd_sampler* s, const double* acc, int32_t k, int rows, const char*
 
 }  // namespace
 
+// Quiesce: launches of a half that ended early may still be on their way (trains); without trains the members' last users
+// are on the context's stream
+abd_sampler::~abd_sampler() {
+  (void)hipSetDevice(c->device);
+  (void)((!tu.empty() || !dc.empty()) ? hipDeviceSynchronize() : hipStreamSynchronize(c->stream));
+}
+
 extern "C" {
 
 int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta0, const abd_sampler_opts* opts,
                        abd_sampler** out) {
   if (!c || !chains || !theta0 || !opts || !out) return fail(ABD_ERR_ARG, "NULL argument");
   *out = nullptr;
-  int rc = check_chains(c, n, chains);
-  if (rc) return rc;
+  if (int rc = check_chains(c, n, chains)) return rc;
   for (int a = 0; a < n; ++a)
     for (int b = a + 1; b < n; ++b)
       if (chains[a] == chains[b]) return fail(ABD_ERR_ARG, "chain %d listed twice", chains[a]);
@@ -302,7 +264,8 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
     return fail(ABD_ERR_ARG, "max_treedepth=%d outside [1, %d]", opts->max_treedepth, abdnuts::MAX_DEPTH);
   if (!(opts->target_accept > 0.0 && opts->target_accept < 1.0))
     return fail(ABD_ERR_ARG, "target_accept=%g outside (0, 1)", opts->target_accept);
-  abd_sampler* s = new (std::nothrow) abd_sampler();
+  std::unique_ptr<abd_sampler> sp(new (std::nothrow) abd_sampler());  // every early return releases the half-built sampler
+  abd_sampler* const s = sp.get();
   if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
   s->c = c;
   s->n = n;
@@ -344,8 +307,10 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
   if (s->dtrains && s->unit != 1 && s->unit != 2 && s->unit != 4) s->dtrains = false;  // (a train unit is a workgroup's waves)
 
   // the starting points through the launch shape the units will use
-  rc = hipSetDevice(c->device) == hipSuccess ? flush_ring(c) : fail(ABD_ERR_HIP, "hipSetDevice failed");
-  if (!rc && (n + s->unit - 1) / s->unit > 1 && tune_int("ABD_PROBE_QUEUES", 1) != 0) rc = probe_stream_queues(c);
+  if (hipSetDevice(c->device) != hipSuccess) return fail(ABD_ERR_HIP, "hipSetDevice failed");
+  if (int rc = flush_ring(c)) return rc;
+  if ((n + s->unit - 1) / s->unit > 1 && tune_int("ABD_PROBE_QUEUES", 1) != 0)
+    if (int rc = probe_stream_queues(c)) return rc;
   s->trains = trains_ok && !c->dense && s->unit == 1;
   if (s->dtrains) {
     // the unit's launch shape: two workgroups per CU, however many units there are (config 3, evaluations/s seen by NUTS over
@@ -364,63 +329,48 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
     s->dtrain_blocks = std::min(s->dtrain_blocks, c->n_cu * per_cu);
     if (const int tb = tune_int("ABD_TRAIN_BLOCKS_PER_CU", 0)) s->dtrain_blocks = std::max(1, std::min({c->n_cu * tb, c->blocks_max, dense_blocks(c, s->unit, 0, 1)}));
     s->dtrain_lookahead = std::max(2, std::min(ABD_TRAIN_RING / 2, tune_int("ABD_TRAIN_LOOKAHEAD", 3)));
-    if (!rc) rc = dtrain_alloc(s);
+    if (int rc = dtrain_alloc(s)) return rc;
   }
   s->lookahead = std::max(0, std::min(abd_sampler::kTrainRing - 2, tune_int("ABD_TRAIN_LOOKAHEAD", 8)));
-  if (!rc && s->trains) rc = train_alloc(s);
-  for (int u = 0, lo = 0; lo < n && !rc; ++u, lo += s->unit) {
+  if (s->trains)
+    if (int rc = train_alloc(s)) return rc;
+  for (int u = 0, lo = 0; lo < n; ++u, lo += s->unit) {
     const int m = std::min(s->unit, n - lo);
     if (s->trains) {  // every evaluation of this sampler is assembled on the device (see abd_sampler::trains)
       const double ones[ABD_N_THETA] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-      rc = train_launch(s, u, theta0 + (size_t)lo * ABD_N_THETA, nullptr, 0.0, ones, true);
-      for (long spin = 0; !rc && !train_ready(s, u); ++spin) {
+      if (int rc = train_launch(s, u, theta0 + (size_t)lo * ABD_N_THETA, nullptr, 0.0, ones, true)) return rc;
+      for (long spin = 0; !train_ready(s, u); ++spin) {
         if (spin > 4000000) {
           __atomic_fetch_add(&c->wait_fallbacks, (int64_t)1, __ATOMIC_RELAXED);
-          if (hipStreamSynchronize(c->pipe[unit_pipe(c, u)].st) != hipSuccess) rc = fail(ABD_ERR_HIP, "hipStreamSynchronize failed");
-          if (!rc && !train_ready(s, u)) rc = fail(ABD_ERR_STATE, "the record of chain %d's starting point never received its tag", chains[lo]);
+          if (hipStreamSynchronize(c->pipe[unit_pipe(c, u)].st) != hipSuccess) return fail(ABD_ERR_HIP, "hipStreamSynchronize failed");
+          if (!train_ready(s, u)) return fail(ABD_ERR_STATE, "the record of chain %d's starting point never received its tag", chains[lo]);
           break;
         }
         __builtin_ia32_pause();
       }
-      if (!rc) {
-        abd_sampler::TrainUnit& t = s->tu[(size_t)u];
-        const TrainRecord& r = t.rec_h[t.cons % abd_sampler::kTrainRing];
-        s->lp[(size_t)lo] = r.lp;
-        std::memcpy(s->gr.data() + (size_t)lo * ABD_N_THETA, r.g, sizeof(double) * ABD_N_THETA);
-        t.cons += 1;
-      }
+      abd_sampler::TrainUnit& t = s->tu[(size_t)u];
+      const TrainRecord& r = t.rec.host()[t.cons % abd_sampler::kTrainRing];
+      s->lp[(size_t)lo] = r.lp;
+      std::memcpy(s->gr.data() + (size_t)lo * ABD_N_THETA, r.g, sizeof(double) * ABD_N_THETA);
+      t.cons += 1;
       continue;
     }
-    rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u)}, kSyncSlot + u, m, chains + lo, theta0 + (size_t)lo * ABD_N_THETA, true);
-    if (!rc) rc = wait_rows(c, kSyncSlot + u, m, c->seq, c->pipe[unit_pipe(c, u)].st);
-    if (!rc) rc = fetch_slot(c, kSyncSlot + u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA);
+    if (int rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u)}, kSyncSlot + u, m, chains + lo, theta0 + (size_t)lo * ABD_N_THETA, true)) return rc;
+    if (int rc = wait_rows(c, kSyncSlot + u, m, c->seq, c->pipe[unit_pipe(c, u)].st)) return rc;
+    if (int rc = fetch_slot(c, kSyncSlot + u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA)) return rc;
   }
-  for (int k = 0; k < n && !rc; ++k) {
-    if (!std::isfinite(s->lp[(size_t)k])) {
-      rc = fail(ABD_ERR_ARG, "logp at the starting point of chain %d is not finite", chains[k]);
-      break;
-    }
+  for (int k = 0; k < n; ++k) {
+    if (!std::isfinite(s->lp[(size_t)k])) return fail(ABD_ERR_ARG, "logp at the starting point of chain %d is not finite", chains[k]);
     s->ch[(size_t)k].init(theta0 + (size_t)k * ABD_N_THETA, s->lp[(size_t)k], s->gr.data() + (size_t)k * ABD_N_THETA,
                           opts->seed, (uint64_t)((int64_t)chains[k] + opts->chain_offset), opts->tune, opts->max_treedepth, opts->target_accept,
                           opts->dense_metric != 0);
   }
-  if (!rc && opts->accumulate) {
-    const size_t bytes = (size_t)n * 3 * c->G * c->N * sizeof(double);
-    hipError_t e = hipMalloc(&s->d_sums, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_sums, 0, bytes, c->stream);
-    if (e != hipSuccess) rc = fail(ABD_ERR_HIP, "sampler sums: %s", hipGetErrorString(e));
-  }
-  if (rc) {
-    sampler_release(s);
-    return rc;
-  }
-  *out = s;
+  if (opts->accumulate) HIP_TRY(s->d_sums.alloc_zero((size_t)n * 3 * c->G * c->N, c->stream));
+  *out = sp.release();
   return ABD_OK;
 }
 
-void abd_sampler_destroy(abd_sampler* s) {
-  if (s) sampler_release(s);
-}
+void abd_sampler_destroy(abd_sampler* s) { delete s; }
 
 int abd_sampler_run(abd_sampler* s, int64_t n_iter, double* theta, double* stats) {
   return abd_sampler_run_record(s, n_iter, theta, stats, nullptr);
@@ -596,7 +546,7 @@ int sampler_run_units(RunFrame& f) {
   // those rows, whichever sampler drives them
   while (c->unit_seq.size() < (size_t)n_units) c->unit_seq.push_back((double)(c->unit_seq.size() + 1) * 1099511627776.0);
   s->unit_tags = T_all > 1;
-  auto stream_of = [&](int u) { return c->pipe[unit_pipe(c, u)].st; };
+  auto stream_of = [&](int u) -> hipStream_t { return c->pipe[unit_pipe(c, u)].st; };
   // evaluate the points th[0 .. m) of the unit's chains who[0 .. m)
   auto launch_eval = [&](int u) -> int {
     Unit& un = units[(size_t)u];
@@ -645,7 +595,7 @@ int sampler_run_units(RunFrame& f) {
   auto ready = [&](int u) -> bool {  // have all result rows of the unit's launch landed? (never blocks)
     const Unit& un = units[(size_t)u];
     if (s->trains) return train_ready(s, u);
-    volatile const double* rows = c->h_out + (size_t)(kSyncSlot + u) * c->n_slots * ABD_NOUT;
+    volatile const double* rows = c->out.host() + (size_t)(kSyncSlot + u) * c->n_slots * ABD_NOUT;
     for (int k = un.m - 1; k >= 0; --k)
       if (rows[(size_t)k * ABD_NOUT + ABD_NOUT - 1] != un.tag) return false;
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
@@ -655,7 +605,7 @@ int sampler_run_units(RunFrame& f) {
   // then the next iteration's first leapfrogs, or DONE
   auto finish_iteration = [&](int u, bool with_counts) -> int {
     Unit& un = units[(size_t)u];
-    for (int j = un.lo; j < un.hi; ++j) write_draw(f, j, un.k, with_counts ? c->h_counts_chain + 2 * (size_t)j : nullptr);
+    for (int j = un.lo; j < un.hi; ++j) write_draw(f, j, un.k, with_counts ? c->h_counts_chain.host() + 2 * (size_t)j : nullptr);
     // the next iteration's first leapfrogs go out BEFORE this iteration's recording is queued: the recording kernels read the
     // point (by value) and the discrete state, which only the next sweep -- queued after them -- changes, and the host's time
     // for queueing them (several launches per draw) passes while the device is already at work for the chain
@@ -727,7 +677,7 @@ int sampler_run_units(RunFrame& f) {
         const double *next_q = nullptr, *next_p_half = nullptr;
         if (s->trains) {  // the launch assembled its own result: take the record
           abd_sampler::TrainUnit& t = s->tu[(size_t)u];
-          const TrainRecord& r = t.rec_h[t.cons % abd_sampler::kTrainRing];
+          const TrainRecord& r = t.rec.host()[t.cons % abd_sampler::kTrainRing];
           un.lp[0] = r.lp;
           std::memcpy(un.gr.data(), r.g, sizeof(double) * ABD_N_THETA);
           next_q = r.next_theta;  // (the slot is not written again before kTrainRing more launches have been queued)
@@ -768,7 +718,7 @@ int sampler_run_units(RunFrame& f) {
             std::memcpy(un.th.data() + (size_t)(j - un.lo) * ABD_N_THETA, s->ch[(size_t)j].nuts.q, sizeof(double) * ABD_N_THETA);
           }
           if (int rc = queue_sweep(s, un.lo, un.m, un.ids.data(), un.th.data(), un.k, st)) return rc;
-          HIP_TRY(hipMemcpyAsync(c->h_counts_chain + 2 * (size_t)un.lo, c->d_counts_chain + 2 * (size_t)un.lo,
+          HIP_TRY(hipMemcpyAsync(c->h_counts_chain.host() + 2 * (size_t)un.lo, c->d_counts_chain + 2 * (size_t)un.lo,
                                  (size_t)un.m * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
           un.state = POST;
           if (int rc = launch_eval(u)) return rc;
@@ -873,7 +823,7 @@ int sampler_run_trains(RunFrame& f) {
     abd_sampler::DChain& d = s->dc[(size_t)j];
     const abdnuts::Nuts& nu = s->ch[(size_t)j].nuts;
     r.begin_block = (int)(d.n_begin++ % abd_sampler::kBeginBlocks);
-    TrainBegin& b = d.begin_h[r.begin_block];
+    TrainBegin& b = d.begin.host()[r.begin_block];
     std::memcpy(b.q0, nu.q, sizeof b.q0);
     std::memcpy(b.p0, nu.p0_pending, sizeof b.p0);
     std::memcpy(b.g0, nu.g, sizeof b.g0);
@@ -892,7 +842,7 @@ int sampler_run_trains(RunFrame& f) {
   auto iteration_done = [&](int j, bool with_counts) -> int {
     Run& r = runs[(size_t)j];
     abd_sampler::DChain& d = s->dc[(size_t)j];
-    write_draw(f, j, r.k, with_counts ? d.done_h : nullptr);
+    write_draw(f, j, r.k, with_counts ? d.done.host() : nullptr);
     if (int rc = queue_draw(f, j, r.k, d.side)) return rc;
     if (++r.k == n_iter) r.state = DONE;
     return ABD_OK;
@@ -909,8 +859,8 @@ int sampler_run_trains(RunFrame& f) {
       const int32_t id = s->chains[(size_t)j];
       if (int rc = queue_sweep(s, j, 1, &id, s->ch[(size_t)j].nuts.q, r.k, d.side)) return rc;
       d.sweep_tag += 1.0;
-      hipLaunchKernelGGL(abd_sweep_done_kernel, dim3(1), dim3(64), 0, d.side, c->d_counts_chain + 2 * (size_t)j, d.done_d,
-                         reinterpret_cast<double*>(d.done_d + 2), d.sweep_tag);
+      hipLaunchKernelGGL(abd_sweep_done_kernel, dim3(1), dim3(64), 0, d.side, c->d_counts_chain + 2 * (size_t)j, d.done.dev(),
+                         reinterpret_cast<double*>(d.done.dev() + 2), d.sweep_tag);
       HIP_TRY(hipGetLastError());
       r.state = SWEEP;
       return ABD_OK;
@@ -945,7 +895,7 @@ int sampler_run_trains(RunFrame& f) {
             ++n_stale;
             continue;
           }
-          const TrainRecord& tr = d.ring_h[e.idx % ABD_TRAIN_RING];
+          const TrainRecord& tr = d.ring.host()[e.idx % ABD_TRAIN_RING];
           if (*(volatile const double*)&tr.tag != (double)(e.idx + 1)) break;
           __atomic_thread_fence(__ATOMIC_ACQUIRE);
           r.fifo.pop_front();
@@ -970,7 +920,7 @@ int sampler_run_trains(RunFrame& f) {
         Run& r = runs[(size_t)j];
         if (r.state != SWEEP) continue;
         const abd_sampler::DChain& dj = s->dc[(size_t)j];
-        if (*reinterpret_cast<volatile const double*>(dj.done_h + 2) != dj.sweep_tag) continue;
+        if (*reinterpret_cast<volatile const double*>(dj.done.host() + 2) != dj.sweep_tag) continue;
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
         progressed = true;
         const bool last = r.k + 1 == n_iter;
@@ -999,8 +949,8 @@ int sampler_run_trains(RunFrame& f) {
           const ChainSlot& slot = c->slots[(size_t)s->chains[(size_t)j]];
           TrainChainArgs& tc = a.tc[j - lo];
           tc.st = d.st;
-          tc.ring = d.ring_d;
-          tc.begin = d.begin_d;
+          tc.ring = d.ring.dev();
+          tc.begin = d.begin.dev();
           tc.iw = slot.iw;
           tc.cnt = slot.cnt;
           tc.waner = slot.waner;
@@ -1008,7 +958,7 @@ int sampler_run_trains(RunFrame& f) {
           tc.fwd_slot = -1;
           if (r.state == NEED_BEGIN) {
             tc.action = ABD_TR_BEGIN;
-            tc.begin = d.begin_d + r.begin_block;
+            tc.begin = d.begin.dev() + r.begin_block;
             r.state = TREE;
             r.parity = 0;
             r.steps_queued = 0;
@@ -1090,16 +1040,12 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
       const size_t per_draw = (size_t)n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0) +
                                            (with_yrep ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
       s->rec_chunk = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(((size_t)256 << 20) / per_draw)));
-      double* mu = nullptr;
-      int8_t* i8 = nullptr;
-      hipError_t e = hipMalloc(&mu, (size_t)2 * n * s->rec_chunk * cells * sizeof(double));
-      if (e == hipSuccess) e = hipMalloc(&i8, (size_t)2 * n * s->rec_chunk * cells + (size_t)n * s->rec_chunk * c->N);
-      if (e != hipSuccess) {
-        if (mu) (void)hipFree(mu);
-        return fail(ABD_ERR_HIP, "record staging: %s", hipGetErrorString(e));
-      }
-      s->d_rec_mu = mu;
-      s->d_rec_i8 = i8;
+      DevBuf<double> mu;  // (the sampler takes both or neither: d_rec_mu is the "allocated" flag)
+      DevBuf<int8_t> i8;
+      HIP_TRY(mu.alloc((size_t)2 * n * s->rec_chunk * cells));
+      HIP_TRY(i8.alloc((size_t)2 * n * s->rec_chunk * cells + (size_t)n * s->rec_chunk * c->N));
+      s->d_rec_mu = std::move(mu);
+      s->d_rec_i8 = std::move(i8);
     }
     HIP_TRY(hipSetDevice(c->device));
     if (with_ll)
