@@ -83,6 +83,17 @@ class _Record(C.Structure):
     ]
 
 
+class _SimAntibody(C.Structure):
+    _fields_ = [(name, C.c_double) for name in ("protect_a", "protect_b", "elisa_b", "elisa_d", "elisa_sd", "init", "perm_rise",
+                                                "temp_rise_i", "temp_rise_v", "temp_wane")]
+
+
+class _SimParams(C.Structure):
+    _fields_ = [("s", _SimAntibody), ("n", _SimAntibody)]
+
+
+SIM_OUTPUTS = ("infections", "s_titer", "n_titer", "od_s", "od_n", "n_infected")  # abd_simulate's outputs, in its order
+
 N_STATS = 11
 STAT_NAMES = ("lp", "tree_depth", "n_steps", "mean_tree_accept", "step_size", "diverging", "energy", "max_energy_error",
               "gibbs_accepted", "gibbs_proposed", "t_done")
@@ -119,6 +130,8 @@ SYMBOLS = {
     "abd_deterministics": (C.c_int, [_P, C.c_int32, _D, _I8, _D, _D]),
     "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_posterior_predictive": (C.c_int, [_P, C.c_int32, _D, C.c_uint64, C.c_uint32, C.c_uint64, _D, _D, _D, _D]),
+    "abd_simulate": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, _I8, _D, _D, _D, _D, _D]),
+    "abd_simulate_staged": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64, _I8, _D, _D, _D, _D, _D]),
     "abd_sampler_create": (C.c_int, [_P, C.c_int32, _I32, _D, C.POINTER(_SamplerOpts), C.POINTER(_P)]),
     "abd_sampler_destroy": (None, [_P]),
     "abd_sampler_run": (C.c_int, [_P, C.c_int64, _D, _D]),
@@ -497,6 +510,42 @@ class Context:
             C.c_uint64(int(draw) & (2**64 - 1)), _ptr(y_s, C.c_double), _ptr(y_n, C.c_double),
             None if m_s is None else _ptr(m_s, C.c_double), None if m_n is None else _ptr(m_n, C.c_double)))
         return (y_s, y_n, m_s, m_n) if mean else (y_s, y_n)
+
+    def simulate(self, params, lam0, seed: int = 0, first_replicate: int = 0, n_replicates: int = 1, outputs=SIM_OUTPUTS,
+                 staging_bytes: Optional[int] = None):
+        """Replicates ``first_replicate .. first_replicate + n_replicates - 1`` of the forward simulation of this cohort
+        (abd_hip.h: abd_simulate) at ``lam0`` (n_gaps infection probabilities).  ``params``: {"s": {...}, "n": {...}} with the
+        ten fields of ``abd_sim_antibody`` each.  -> dict of the ``outputs`` asked for (any of ``SIM_OUTPUTS``):
+        infections (R, n_inds, n_gaps) int8, s_titer / n_titer (R, n_inds, n_gaps), od_s / od_n (R, n_obs) in the order the
+        readings were given, n_infected (R, n_gaps) int64.  A replicate depends on (seed, its number) only.
+        ``staging_bytes``: device memory one chunk of replicates may occupy in this call (None: the library's default)."""
+        lam = _as(lam0, np.float64)
+        if lam.ndim != 1:
+            raise ValueError("lam0 should be 1D")
+        if lam.shape[0] != self.n_gaps:
+            raise ValueError("must have single infection rate for each time gap")
+        outputs = tuple(outputs)
+        unknown = [o for o in outputs if o not in SIM_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown outputs {unknown}: choose from {SIM_OUTPUTS}")
+        p = _SimParams()
+        for ag in ("s", "n"):
+            for name, _ in _SimAntibody._fields_:
+                setattr(getattr(p, ag), name, float(params[ag][name]))
+        R = int(n_replicates)
+        if R < 1:
+            raise ValueError(f"n_replicates must be >= 1, got {R}")
+        if not (0 <= int(first_replicate) and int(first_replicate) + R <= 2 ** 32):
+            raise ValueError(f"first_replicate + n_replicates = {int(first_replicate) + R} exceeds 2^32")
+        G, N = self.n_gaps, self.n_inds
+        shapes = {"infections": ((R, N, G), np.int8), "s_titer": ((R, N, G), np.float64), "n_titer": ((R, N, G), np.float64),
+                  "od_s": ((R, self.n_obs_s), np.float64), "od_n": ((R, self.n_obs_n), np.float64),
+                  "n_infected": ((R, G), np.int64)}
+        out = {name: np.zeros(*shapes[name]) for name in SIM_OUTPUTS if name in outputs}
+        ptrs = [_ptr(out[name]) if name in out and out[name].size else None for name in SIM_OUTPUTS]
+        _check(self._lib, self._lib.abd_simulate_staged(self._h, C.byref(p), _ptr(lam), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                        C.c_uint32(int(first_replicate)), R, int(staging_bytes or 0), *ptrs))
+        return out
 
     def theta_prior(self, theta):
         """The theta-only part of the joint logp (continuous priors + Jacobians) and its gradient."""

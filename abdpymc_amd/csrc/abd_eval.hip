@@ -4,6 +4,7 @@
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
 #include "abd_readings.hpp"
+#include "abd_simulate.hpp"
 
 namespace abdi {
 
@@ -542,7 +543,7 @@ int upload_order(abd_ctx* c) {
   if (c->d_order) return ABD_OK;
   const int64_t Ks = c->s.K, Kn = c->n.K;
   if (Ks >= ((int64_t)1 << 32) || Kn >= ((int64_t)1 << 32))
-    return fail(ABD_ERR_ARG, "posterior predictive: %lld / %lld readings, at most 2^32 - 1 per antigen", (long long)Ks, (long long)Kn);
+    return fail(ABD_ERR_ARG, "%lld / %lld readings: at most 2^32 - 1 per antigen can be keyed by their index", (long long)Ks, (long long)Kn);
   std::vector<uint32_t> h((size_t)std::max<int64_t>(1, Ks + Kn));
   for (int64_t k = 0; k < Ks; ++k) h[(size_t)k] = (uint32_t)c->order_s[(size_t)k];
   for (int64_t k = 0; k < Kn; ++k) h[(size_t)(Ks + k)] = (uint32_t)c->order_n[(size_t)k];
@@ -609,6 +610,68 @@ int eval_sync(abd_ctx* c, int n, const int32_t* chains, const double* theta, dou
   if (int rc = wait_rows(c, kSyncSlot, n, c->seq)) return rc;
   return fetch_slot(c, kSyncSlot, logp, grad, with_priors);
 }
+
+
+// ---- the cohort simulator (abd_simulate.hpp) ----
+
+namespace {
+
+int check_sim_antibody(const char* ag, const abd_sim_antibody& p) {
+  const struct {
+    const char* name;
+    double v;
+  } f[] = {{"protect_a", p.protect_a}, {"protect_b", p.protect_b}, {"elisa_b", p.elisa_b}, {"elisa_d", p.elisa_d},
+           {"elisa_sd", p.elisa_sd}, {"init", p.init}, {"perm_rise", p.perm_rise}, {"temp_rise_i", p.temp_rise_i},
+           {"temp_rise_v", p.temp_rise_v}, {"temp_wane", p.temp_wane}};
+  for (const auto& e : f)
+    if (!std::isfinite(e.v)) return fail(ABD_ERR_ARG, "%s.%s must be finite, got %g", ag, e.name, e.v);
+  if (!(p.protect_b > 0.0)) return fail(ABD_ERR_ARG, "%s.protect_b must be > 0, got %g", ag, p.protect_b);
+  if (!(p.elisa_b < 0.0)) return fail(ABD_ERR_ARG, "%s.elisa_b must be < 0, got %g", ag, p.elisa_b);
+  if (!(p.elisa_d > 0.0)) return fail(ABD_ERR_ARG, "%s.elisa_d must be > 0, got %g", ag, p.elisa_d);
+  if (!(p.elisa_sd > 0.0)) return fail(ABD_ERR_ARG, "%s.elisa_sd must be > 0, got %g", ag, p.elisa_sd);
+  if (!(p.perm_rise >= 0.0)) return fail(ABD_ERR_ARG, "%s.perm_rise must be >= 0, got %g", ag, p.perm_rise);
+  if (!(p.temp_rise_i >= 0.0)) return fail(ABD_ERR_ARG, "%s.temp_rise_i must be >= 0, got %g", ag, p.temp_rise_i);
+  if (!(p.temp_rise_v >= 0.0)) return fail(ABD_ERR_ARG, "%s.temp_rise_v must be >= 0, got %g", ag, p.temp_rise_v);
+  if (!(p.temp_wane > 0.0 && p.temp_wane <= 1.0)) return fail(ABD_ERR_ARG, "%s.temp_wane must be in (0, 1], got %g", ag, p.temp_wane);
+  return ABD_OK;
+}
+
+SimWalkAb sim_walk_ab(const abd_sim_antibody& p) {
+  return {p.protect_a, p.protect_b, p.init, p.perm_rise, p.temp_rise_i, p.temp_rise_v, p.temp_wane};
+}
+
+// the OD readings of one antigen (kAgS / kAgN) for the chunk's replicates, from the walk's staged titers
+int launch_sim_readings(abd_ctx* c, int ag, const abd_sim_antibody& p, uint64_t seed, uint32_t rho0, int rc_n, const double* titer,
+                        double* od) {
+  const AntigenDev& d = ag == kAgS ? c->s : c->n;
+  if (d.K == 0) return ABD_OK;
+  SimReadArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.yx = d.yxi;
+  a.x = d.x;
+  a.g = d.g;
+  a.j = d.j;
+  a.ord = c->d_order + (ag == kAgS ? 0 : c->s.K);
+  a.titer = titer;
+  a.od = od;
+  a.b = p.elisa_b;
+  a.d = p.elisa_d;
+  a.sd = p.elisa_sd;
+  a.K = d.K;
+  a.G = c->G;
+  a.N = c->N;
+  a.seed_lo = (uint32_t)seed;
+  a.seed_hi = (uint32_t)(seed >> 32);
+  a.rho0 = rho0;
+  a.c3 = kSimNoise | (uint32_t)ag;
+  const bool f32 = c->storage == ABD_STORE_F32;
+  const auto k = c->dense ? (f32 ? abd_sim_read_kernel<float, true> : abd_sim_read_kernel<double, true>)
+                          : (f32 ? abd_sim_read_kernel<float, false> : abd_sim_read_kernel<double, false>);
+  HIP_TRY(launch_kernel(k, dim3((unsigned)((d.K + 255) / 256), (unsigned)rc_n), dim3(256), 0, c->stream, a));
+  return ABD_OK;
+}
+
+}  // namespace
 
 }  // namespace abdi
 
@@ -772,5 +835,105 @@ int abd_kernel_time(abd_ctx* c, double* total_ms, int64_t* launches, int32_t res
 }
 
 int64_t abd_wait_fallbacks(abd_ctx* c) { return c ? c->wait_fallbacks : -1; }
+
+int abd_simulate(abd_ctx* c, const abd_sim_params* par, const double* lam0, uint64_t seed, uint32_t first_replicate,
+                 int32_t n_replicates, int8_t* infections, double* s_titer, double* n_titer, double* od_s, double* od_n,
+                 int64_t* n_infected) {
+  return abd_simulate_staged(c, par, lam0, seed, first_replicate, n_replicates, 0, infections, s_titer, n_titer, od_s, od_n, n_infected);
+}
+
+int abd_simulate_staged(abd_ctx* c, const abd_sim_params* par, const double* lam0, uint64_t seed, uint32_t first_replicate,
+                        int32_t n_replicates, int64_t staging_bytes, int8_t* infections, double* s_titer, double* n_titer,
+                        double* od_s, double* od_n, int64_t* n_infected) {
+  if (!c) return fail(ABD_ERR_ARG, "ctx is NULL");
+  if (staging_bytes < 0) return fail(ABD_ERR_ARG, "staging_bytes=%lld is negative", (long long)staging_bytes);
+  if (staging_bytes == 0) staging_bytes = kSimStageBytes;
+  if (!par) return fail(ABD_ERR_ARG, "params is NULL");
+  if (!lam0) return fail(ABD_ERR_ARG, "lam0 is NULL");
+  if (int rc = check_sim_antibody("s", par->s)) return rc;
+  if (int rc = check_sim_antibody("n", par->n)) return rc;
+  const int G = c->G, N = c->N;
+  for (int g = 0; g < G; ++g)
+    if (!std::isfinite(lam0[g])) return fail(ABD_ERR_ARG, "lam0[%d] must be finite, got %g", g, lam0[g]);
+  if (n_replicates < 1) return fail(ABD_ERR_ARG, "n_replicates must be >= 1, got %d", n_replicates);
+  if ((uint64_t)first_replicate + (uint64_t)n_replicates > ((uint64_t)1 << 32))
+    return fail(ABD_ERR_ARG, "first_replicate + n_replicates = %llu exceeds 2^32", (unsigned long long)first_replicate + (unsigned long long)n_replicates);
+  if (c->s.K == 0) od_s = nullptr;
+  if (c->n.K == 0) od_n = nullptr;
+  if (!infections && !s_titer && !n_titer && !od_s && !od_n && !n_infected) return ABD_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = flush_ring(c)) return rc;
+  if (od_s || od_n)
+    if (int rc = upload_order(c)) return rc;
+
+  // Staging of one chunk of replicates within the budget (at least one replicate): the outputs asked for, and the titers
+  // the readings gather.  Every part starts on a 256-byte boundary.
+  const size_t cells = (size_t)G * N, Ks = (size_t)c->s.K, Kn = (size_t)c->n.K;
+  const bool want_s = s_titer || od_s, want_n = n_titer || od_n;
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t per_rep = (infections ? cells : 0) + ((want_s ? 1 : 0) + (want_n ? 1 : 0)) * cells * sizeof(double) +
+                         (od_s ? Ks * sizeof(double) : 0) + (od_n ? Kn * sizeof(double) : 0) + (n_infected ? (size_t)G * 8 : 0);
+  const int rc_max = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)n_replicates, (int64_t)((size_t)staging_bytes / per_rep), 65535}));
+  DevBuf<unsigned char> stage;  // released on every return below; nothing is queued on it when an error returns (see sync)
+  DevBuf<double> d_lam;
+  HIP_TRY(d_lam.upload(lam0, (size_t)G));
+  const size_t o_inf = 0;
+  const size_t o_s = o_inf + pad(infections ? cells * rc_max : 0);
+  const size_t o_n = o_s + pad(want_s ? cells * rc_max * sizeof(double) : 0);
+  const size_t o_ods = o_n + pad(want_n ? cells * rc_max * sizeof(double) : 0);
+  const size_t o_odn = o_ods + pad(od_s ? Ks * rc_max * sizeof(double) : 0);
+  const size_t o_cnt = o_odn + pad(od_n ? Kn * rc_max * sizeof(double) : 0);
+  const size_t total = o_cnt + pad(n_infected ? (size_t)G * rc_max * 8 : 0);
+  HIP_TRY(stage.alloc(total));
+  unsigned char* const sb = stage;
+  int8_t* const d_inf = infections ? reinterpret_cast<int8_t*>(sb + o_inf) : nullptr;
+  double* const d_s = want_s ? reinterpret_cast<double*>(sb + o_s) : nullptr;
+  double* const d_n = want_n ? reinterpret_cast<double*>(sb + o_n) : nullptr;
+  double* const d_ods = od_s ? reinterpret_cast<double*>(sb + o_ods) : nullptr;
+  double* const d_odn = od_n ? reinterpret_cast<double*>(sb + o_odn) : nullptr;
+  unsigned long long* const d_cnt = n_infected ? reinterpret_cast<unsigned long long*>(sb + o_cnt) : nullptr;
+
+  // one chunk: the walk, the readings, the copies back; the stream is drained before the staging is reused or released
+  auto chunk = [&](int r0, int rn) -> int {
+    SimWalkArgs w;
+    std::memset(&w, 0, sizeof w);
+    w.par.s = sim_walk_ab(par->s);
+    w.par.n = sim_walk_ab(par->n);
+    w.lam0 = d_lam;
+    w.vw = c->vw;
+    w.pw = c->ignore_pcr ? nullptr : (const uint64_t*)c->pw;
+    w.inf = d_inf;
+    w.st = d_s;
+    w.nt = d_n;
+    w.cnt = d_cnt;
+    w.seed_lo = (uint32_t)seed;
+    w.seed_hi = (uint32_t)(seed >> 32);
+    w.ind_offset = c->ind_offset;
+    w.rho0 = first_replicate + (uint32_t)r0;
+    w.G = G;
+    w.N = N;
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)G * rn * 8, c->stream));
+    HIP_TRY(launch_kernel(abd_sim_walk_kernel, dim3((unsigned)c->n_lg, (unsigned)rn), dim3(64), 0, c->stream, w));
+    if (d_ods)
+      if (int rc = launch_sim_readings(c, kAgS, par->s, seed, w.rho0, rn, d_s, d_ods)) return rc;
+    if (d_odn)
+      if (int rc = launch_sim_readings(c, kAgN, par->n, seed, w.rho0, rn, d_n, d_odn)) return rc;
+    const size_t r = (size_t)r0, n = (size_t)rn;
+    if (infections) HIP_TRY(hipMemcpyAsync(infections + r * cells, d_inf, n * cells, hipMemcpyDeviceToHost, c->stream));
+    if (s_titer) HIP_TRY(hipMemcpyAsync(s_titer + r * cells, d_s, n * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_titer) HIP_TRY(hipMemcpyAsync(n_titer + r * cells, d_n, n * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (od_s) HIP_TRY(hipMemcpyAsync(od_s + r * Ks, d_ods, n * Ks * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (od_n) HIP_TRY(hipMemcpyAsync(od_n + r * Kn, d_odn, n * Kn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_infected) HIP_TRY(hipMemcpyAsync(n_infected + r * (size_t)G, d_cnt, n * (size_t)G * 8, hipMemcpyDeviceToHost, c->stream));
+    return ABD_OK;
+  };
+  for (int r0 = 0; r0 < n_replicates; r0 += rc_max) {
+    const int rc = chunk(r0, std::min(rc_max, n_replicates - r0));
+    const hipError_t se = hipStreamSynchronize(c->stream);  // also after a failed chunk: nothing may still use the staging
+    if (rc) return rc;
+    HIP_TRY(se);
+  }
+  return ABD_OK;
+}
 
 }  // extern "C"

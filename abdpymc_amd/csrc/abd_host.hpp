@@ -67,6 +67,7 @@ constexpr int kResultSlots = 1024;
 constexpr int kSyncSlot = kResultSlots;  // private rows of the synchronous calls: they never touch a caller's slot
 constexpr int kMaxPipes = 8;             // HIP streams of a context
 constexpr int kMinRows = 4;
+constexpr int64_t kSimStageBytes = (int64_t)1 << 30;  // abd_simulate: default device staging budget of one chunk of replicates
 
 // ABD_SAMPLER_PROFILE: time the host spends inside hipLaunchKernelGGL for evaluation launches and their sums
 struct LaunchProfile {

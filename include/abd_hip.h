@@ -174,6 +174,55 @@ int abd_posterior_predictive(abd_ctx* ctx, int32_t chain, const double* theta, u
                              double* yrep_s, double* yrep_n, double* mean_s, double* mean_n);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The forward simulator of a cohort (reference abdpymc/simulation.py:222-279 Individual.infection_responses, 328-353
+ * Cohort.simulate_row): what would this cohort's data look like under these dynamics, ELISA curves, protection curves and
+ * this force of infection.  The context supplies the vaccinations, the PCR positives (none are forced on a context created
+ * without pcrpos) and the readings' (gap, ind, log_dilution) -- on an fp32-storage context log_dilution as stored.
+ * For replicate rho, individual j and gaps t = 0 .. G-1 in sequence, with s_temp = n_temp = 0 before gap 0 and s_prev,
+ * n_prev the titers of gap t - 1 (the bare init values at t = 0):
+ *   exposed = u_e < lam0[t];  p_x = 1 / (1 + exp(-protect_b_x (x_prev - protect_a_x)));  protected = u_s < p_s or u_n < p_n
+ *   infected = pcrpos[j, t] == 1 or (exposed and not protected)
+ *   s_temp = s_temp temp_wane_s + infected temp_rise_i_s + vacs[j, t] temp_rise_v_s
+ *   n_temp = n_temp temp_wane_n + infected temp_rise_i_n                         (N's temp_rise_v is unused)
+ *   s[t] = init_s + s_temp + (perm_rise_s once an infection or a vaccination has occurred in gaps 0 .. t)
+ *   n[t] = init_n + n_temp + (perm_rise_n once an infection has)
+ * There is no three-gap mask (the reference's simulator has none).  A reading k of antigen x at (gap, ind, log_dilution):
+ *   od = elisa_d_x / (1 + exp(-elisa_b_x (log_dilution - x[ind, gap]))) + elisa_sd_x z_k
+ * Random numbers: Philox4x32-10 with key (seed lo, seed hi) and the counters
+ *   exposure       (ind_offset + j, rho, t, 0x40000000)       u_e from words 0, 1
+ *   protection     (ind_offset + j, rho, t, 0x40000001)       u_s from words 0, 1; u_n from words 2, 3
+ *   reading noise  (r, rho, 0, 0x40000010 | antigen)          z the first Box-Muller value, as abd_posterior_predictive forms it
+ * with r the reading's index in the caller's order within its antigen (S 0, N 1), ind_offset from abd_set_individual_offset
+ * and uniforms ((a >> 5) 2^26 + (b >> 6) + 0.5) 2^-53.  The sweep's counters have a fourth word of 0 and the predictive
+ * stream sets its top bit, so none of the three streams meet.  Consequences:
+ *   - a replicate depends on (seed, rho) only: not on how many replicates a call asks for, on how the call is cut into
+ *     staging chunks, on which outputs are asked for, or on dense panels versus observation lists;
+ *   - an individual's infections and titers depend on its GLOBAL index, so they are identical on a cohort sharded by
+ *     individual; the reading noise is keyed by the local reading index and is not. */
+typedef struct {
+  double protect_a, protect_b;                                  /* protection curve: 50 % titer, slope (> 0) */
+  double elisa_b, elisa_d, elisa_sd;                            /* OD curve: slope (< 0), maximum (> 0), noise sd (> 0) */
+  double init, perm_rise, temp_rise_i, temp_rise_v, temp_wane;  /* dynamics: rises >= 0, 0 < temp_wane <= 1 */
+} abd_sim_antibody;
+typedef struct {
+  abd_sim_antibody s, n;
+} abd_sim_params;
+/* Replicates first_replicate .. first_replicate + n_replicates - 1 (R of them) of the simulation at lam0 (G per-gap
+ * infection probabilities).  infections, s_titer, n_titer: [R][N][G], each replicate (n_inds, n_gaps) row-major as the
+ * reference's Cohort holds them; od_s, od_n: [R][s.n_obs], [R][n.n_obs] in the caller's reading order; n_infected: [R][G]
+ * infections per gap.  Any output may be NULL.  Everything runs on the context's stream; the replicates pass through device
+ * staging in chunks (abd_simulate_staged).  ABD_ERR_ARG, the message naming the field, for a parameter that is not
+ * finite or breaks the rules above, a non-finite lam0 entry, n_replicates < 1, first_replicate + n_replicates beyond 2^32. */
+int abd_simulate(abd_ctx* ctx, const abd_sim_params* params, const double* lam0, uint64_t seed, uint32_t first_replicate,
+                 int32_t n_replicates, int8_t* infections, double* s_titer, double* n_titer, double* od_s, double* od_n,
+                 int64_t* n_infected);
+/* abd_simulate with the device memory one chunk of its replicates may occupy given for this call (0: the default, 1 GiB).  A
+ * chunk holds at least one replicate whatever the budget.  The result does not depend on it. */
+int abd_simulate_staged(abd_ctx* ctx, const abd_sim_params* params, const double* lam0, uint64_t seed, uint32_t first_replicate,
+                        int32_t n_replicates, int64_t staging_bytes, int8_t* infections, double* s_titer, double* n_titer,
+                        double* od_s, double* od_n, int64_t* n_infected);
+
+/* ---------------------------------------------------------------------------------------------------
  * The compound step pm.sample assigns to this model (reference call site abd.py:921-922), run natively
  * for several chains: NUTS on the 17 continuous variables, then one Gibbs sweep of [i_raw, ab_s_waner], then a
  * re-evaluation at the new discrete state.  This removes the host-language cost per leapfrog (PyMC: Python;
