@@ -128,6 +128,8 @@ SYMBOLS = {
     "abd_fetch_many": (C.c_int, [_P, C.c_int32, _I32, _D, _D]),
     "abd_logp_dlogp_many": (C.c_int, [_P, C.c_int32, C.c_int32, _I32, _D, _D, _D]),
     "abd_deterministics": (C.c_int, [_P, C.c_int32, _D, _I8, _D, _D]),
+    "abd_curves": (C.c_int, [_P, C.c_int32, _D, C.c_double, C.c_double, _D, _D, _D]),
+    "abd_set_follow_up": (C.c_int, [_P, _I32]),
     "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_posterior_predictive": (C.c_int, [_P, C.c_int32, _D, C.c_uint64, C.c_uint32, C.c_uint64, _D, _D, _D, _D]),
     "abd_simulate": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, _I8, _D, _D, _D, _D, _D]),
@@ -142,6 +144,8 @@ SYMBOLS = {
     "abd_sampler_pointwise_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_predictive": (C.c_int, [_P, C.c_int32]),
     "abd_sampler_predictive_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_curves": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double]),
+    "abd_sampler_curves": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, _D, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
@@ -484,6 +488,34 @@ class Context:
         )
         return i, mun, mus
 
+    def set_follow_up(self, last_gap=None):
+        """End of follow-up per individual for the curves: ``last_gap`` is (N,) with -1 <= v < G (-1: never followed);
+        ``None``: everyone to the last gap.  ``ValueError`` for a value outside."""
+        if last_gap is None:
+            _check(self._lib, self._lib.abd_set_follow_up(self._h, None))
+            return
+        lg = np.asarray(last_gap)
+        if lg.shape != (self.n_inds,) or not np.issubdtype(lg.dtype, np.integer):
+            raise ValueError(f"last_gap must be an integer array of shape ({self.n_inds},)")
+        if lg.size and (lg.min() < -1 or lg.max() >= self.n_gaps):  # (before the cast to int32 could wrap a value round)
+            raise ValueError(f"last_gap outside [-1, {self.n_gaps})")
+        lg = _as(lg, np.int32)
+        _check(self._lib, self._lib.abd_set_follow_up(self._h, _ptr(lg, C.c_int32)))
+
+    def curves(self, chain: int, theta, thr_s: float = np.inf, thr_n: float = np.inf):
+        """The epidemic curves of (theta, the chain slot's discrete state), reduced over the individuals on the device ->
+        {"counts": (4, G) int64 -- infected, ever_infected, seropos_s, seropos_n --, "n_infections": (8,) int64,
+        "titer_sums": (2, G) -- ab_s_mu, ab_n_mu}: ``curves.from_deterministics`` of ``deterministics(chain, theta)`` under
+        the context's follow-up (``set_follow_up``)."""
+        t = _as(theta, np.float64)
+        if t.shape != (N_THETA,):
+            raise ValueError(f"theta must have shape ({N_THETA},)")
+        G = self.n_gaps
+        counts, n_inf, sums = np.empty((4, G), np.int64), np.empty(8, np.int64), np.empty((2, G))
+        _check(self._lib, self._lib.abd_curves(self._h, int(chain), _ptr(t, C.c_double), float(thr_s), float(thr_n),
+                                               _out(counts, np.int64), _out(n_inf, np.int64), _out(sums, np.float64)))
+        return {"counts": counts, "n_infections": n_inf, "titer_sums": sums}
+
     def pointwise_loglik(self, chain: int, theta):
         """Log-density of every OD reading at (theta, the chain slot's discrete state) -> (ll_s, ll_n), each in the order the
         readings were given (what ``pm.compute_log_likelihood`` records per draw for ``it_s_lik`` / ``it_n_lik``)."""
@@ -562,13 +594,16 @@ class Context:
 
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
-                dense_metric: bool = False, pointwise: bool = False, predictive: bool = False) -> "NativeSampler":
+                dense_metric: bool = False, pointwise: bool = False, predictive: bool = False, curves: int = 0,
+                sero_thresholds=None) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
         independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
         pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
-        the posterior predictive check statistics (``NativeSampler.predictive_stats``)."""
+        the posterior predictive check statistics (``NativeSampler.predictive_stats``); ``curves``: keep the epidemic curves
+        of that many draws per chain on the device (``NativeSampler.curves``), seropositive at ``sero_thresholds`` = (thr_s,
+        thr_n) on the titer scale (``None``: off)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise, predictive)
+                             dense_metric, pointwise, predictive, curves, sero_thresholds)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -647,7 +682,7 @@ class NativeSampler:
     per leapfrog of a unit of 1-4 chains, leapfrog trains (abd_hip.h)."""
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
-                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False):
+                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -670,6 +705,11 @@ class NativeSampler:
             _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
         if predictive:
             _check(self._lib, self._lib.abd_sampler_enable_predictive(self._h, 1))
+        if int(curves) < 0:
+            raise ValueError(f"curves must be a number of draws >= 0, got {curves}")
+        if int(curves):
+            thr_s, thr_n = (np.inf, np.inf) if sero_thresholds is None else sero_thresholds
+            _check(self._lib, self._lib.abd_sampler_enable_curves(self._h, int(curves), float(thr_s), float(thr_n)))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -742,6 +782,19 @@ class NativeSampler:
         readings then N in the caller's order; rows mean and sum of squared deviations of the predictive mean, mean tail
         probability P(y_rep <= y) (predictive.merge)."""
         return self._reading_stats(self._lib.abd_sampler_predictive_stats, k)
+
+    def curves(self, k: int):
+        """The epidemic curves of every draw of the k-th chain so far (``Context.curves`` per draw) -> {"counts": (draws, 4, G)
+        int64, "n_infections": (draws, 8) int64, "titer_sums": (draws, 2, G)}."""
+        G = self._ctx.n_gaps
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_curves(self._h, int(k), 0, 0, None, None, None, C.byref(n)))
+        d = n.value
+        counts, n_inf, sums = np.empty((d, 4, G), np.int64), np.empty((d, 8), np.int64), np.empty((d, 2, G))
+        if d:
+            _check(self._lib, self._lib.abd_sampler_curves(self._h, int(k), 0, d, _out(counts, np.int64), _out(n_inf, np.int64),
+                                                           _out(sums, np.float64), None))
+        return {"counts": counts, "n_infections": n_inf, "titer_sums": sums}
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

@@ -50,6 +50,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--ppc", help="Accumulate a posterior predictive check of the OD readings on the device over all draws and "
                         "report per antigen the readings with an extreme tail probability p = P(y_rep <= y | y) (per reading "
                         "ppc_p_it_s_lik / ppc_p_it_n_lik in the output).", action="store_true")
+    parser.add_argument("--curves", help="Keep the epidemic curves of every draw (infections per gap, cumulative attack rate, "
+                        "seroprevalence, mean titers; reduced over the individuals on the device, --thin does not apply) and report "
+                        "the final cumulative attack rate and the peak monthly incidence with 95 %% intervals (curves_* in the "
+                        "output).  An individual counts up to its last serum sample.", action="store_true")
+    parser.add_argument("--sero_threshold_s", help="With --curves: S titer from which an individual counts as seropositive.",
+                        type=float, default=float("inf"))
+    parser.add_argument("--sero_threshold_n", help="With --curves: N titer from which an individual counts as seropositive.",
+                        type=float, default=float("inf"))
     return parser
 
 
@@ -78,6 +86,16 @@ def add_ppc(res: dict) -> dict:
     return sm
 
 
+def add_curves(res: dict) -> dict:
+    """curves.summary of a gathered ``curves=True`` result: its arrays go into ``res`` (``curves_summary_*``: rows lower, median,
+    upper per gap), the summary is returned."""
+    from . import curves
+
+    sm = curves.summary(res)
+    res.update(curves.summary_arrays(sm))
+    return sm
+
+
 def add_observed(res: dict, data) -> None:
     """The observed ODs of both antigens (no chain axis: added on the rank that writes, after any gather)."""
     res["observed_data_it_s_lik"] = np.asarray(data.s.obs[3], dtype=np.float64)
@@ -96,10 +114,15 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
         post = {k: v for k, v in res.items()
-                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_"))
+                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_"))
                 and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
         means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS + PPC_KEYS if k in res}
+        # the epidemic curves: one row per draw, so they sit (and are thinned) with the statistics; what has no draw axis --
+        # the number followed, the summary -- travels with the means
+        for k, v in res.items():
+            if k.startswith("curves_"):
+                (means if k.startswith(("curves_summary_", "curves_n_followed")) else stats)[k] = v
         # pm.compute_log_likelihood: one variable per observed variable, its dim named as PyMC names an undimmed one
         loglik = {k[len("log_likelihood_"):]: v for k, v in res.items() if k.startswith("log_likelihood_")}
         # pm.sample_posterior_predictive: the replicates under the observed variables' names, beside the observed values
@@ -109,6 +132,8 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                      "elpd_waic_i_it_s_lik": ["it_s_lik_dim_0"], "p_waic_i_it_s_lik": ["it_s_lik_dim_0"],
                      "elpd_waic_i_it_n_lik": ["it_n_lik_dim_0"], "p_waic_i_it_n_lik": ["it_n_lik_dim_0"],
                      "ppc_p_it_s_lik": ["it_s_lik_dim_0"], "ppc_p_it_n_lik": ["it_n_lik_dim_0"]})
+        dims.update({k: ["gap"] for k in stats if k.startswith("curves_") and k != "curves_n_infections"})
+        dims["curves_n_followed"] = ["chain", "gap"]
         if "draw_index" in res and res["draw_index"].shape[1] != next(iter(stats.values())).shape[1]:
             # --thin: an InferenceData has ONE draw axis, so the file holds the thinned draws of every variable (what
             # abdpymc-subsample-idata makes of a full one); the posterior means over ALL draws travel as constant data
@@ -170,7 +195,8 @@ def main(argv=None) -> int:
     res = sample(m, tune=args.tune, draws=args.draws, chains=mine, seed=args.seed,
                  record_deterministics=not args.no_deterministics, record_discrete=not args.no_discrete, progress=progress,
                  chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
-                 waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc)  # abd.py:922
+                 waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc, curves=args.curves,
+                 sero_thresholds=(args.sero_threshold_s, args.sero_threshold_n))  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
@@ -189,6 +215,18 @@ def main(argv=None) -> int:
                 a = sm[name]
                 print(f"PPC {name}: {a['n_extreme']} of {a['n_readings']} readings ({100 * a['share_extreme']:.2f} %) with p < 0.025 "
                       f"({a['n_low']}) or p > 0.975 ({a['n_high']}); {sm['n_draws']} draws", file=sys.stderr)
+        if args.curves:
+            sm = add_curves(res)
+            followed = np.flatnonzero(sm["n_followed"] > 0)
+            if followed.size and sm["n_draws"]:
+                g, inc = followed[-1], sm["incidence"]
+                peak = followed[np.argmax(inc["median"][followed])]
+                ar = sm["attack_rate"]
+                pct = int(round(100 * sm["prob"]))
+                print(f"curves: cumulative attack rate at gap {g} {100 * ar['median'][g]:.1f} % ({pct} % interval "
+                      f"{100 * ar['lower'][g]:.1f}-{100 * ar['upper'][g]:.1f}; {sm['n_followed'][g]} followed); peak monthly incidence "
+                      f"{100 * inc['median'][peak]:.1f} % ({100 * inc['lower'][peak]:.1f}-{100 * inc['upper'][peak]:.1f}) at gap {peak}; "
+                      f"{sm['n_draws']} draws", file=sys.stderr)
         if args.posterior_predictive:
             add_observed(res, data)
         out = write_posterior(res, args.netcdf, data.coords)

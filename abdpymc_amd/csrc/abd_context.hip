@@ -8,6 +8,7 @@
 #include <memory>
 #include <unordered_map>
 #include "abd_small.hpp"
+#include "abd_curves.hpp"
 
 namespace abdi {
 
@@ -562,6 +563,44 @@ int launch_deterministics(abd_ctx* c, int chain, const double* theta, hipStream_
   return ABD_OK;
 }
 
+size_t curves_row_cols(const abd_ctx* c) { return (size_t)abd_curves_row_cols(c->G); }
+size_t curves_scratch_cols(const abd_ctx* c) { return (size_t)abd_curves_slabs(c->N) * curves_row_cols(c); }
+
+int launch_curves(abd_ctx* c, int chain, const double* theta, double thr_s, double thr_n, hipStream_t st, unsigned long long* scratch,
+                  unsigned long long* row) {
+  const ChainPar p = chain_par(c, chain, theta);
+  CurvesArgs a;
+  a.vw = c->vw;
+  a.iw = p.iw;
+  a.waner = p.waner;
+  a.last = c->d_last;
+  a.slab_rows = scratch;
+  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
+  a.init_s = p.init_s, a.perm_s = p.perm_s;
+  a.thr_s = thr_s, a.thr_n = thr_n;
+  a.G = c->G, a.N = c->N, a.nt = c->nt, a.n_slabs = abd_curves_slabs(c->N);
+  // power tables, then the slab's row: [2][G] doubles, [4][G] + 8 ints (41 KB at 512 gaps)
+  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)2 * c->G * sizeof(double) + ((size_t)4 * c->G + ABD_CURVES_NBIN) * sizeof(int);
+  const int blocks = std::max(1, std::min(a.n_slabs, c->n_cu * 8));  // (a slab's row does not depend on who computes it)
+  if (c->nt > ABD_MAXT)
+    hipLaunchKernelGGL(abd_curves_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  else
+    hipLaunchKernelGGL(abd_curves_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  const int sum_blocks = (int)((curves_row_cols(c) + ABD_CURVES_SUM_COLS - 1) / ABD_CURVES_SUM_COLS);
+  hipLaunchKernelGGL(abd_curves_sum_kernel, dim3(sum_blocks), dim3(ABD_CURVES_SUM_PARTS * ABD_CURVES_SUM_COLS), 0, st, scratch, a.n_slabs,
+                     c->G, row);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
+void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* counts, int64_t* n_infections, double* titer_sums) {
+  const size_t G = (size_t)c->G;
+  if (counts) std::memcpy(counts, row, 4 * G * sizeof(int64_t));
+  if (n_infections) std::memcpy(n_infections, row + 4 * G, ABD_CURVES_NBIN * sizeof(int64_t));
+  if (titer_sums) std::memcpy(titer_sums, row + 4 * G + ABD_CURVES_NBIN, 2 * G * sizeof(double));
+}
+
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st) {
   dim3 grid((c->N + 255) / 256, c->G);
   hipLaunchKernelGGL(abd_unpack_bits_kernel, grid, dim3(256), 0, st, c->slots[(size_t)chain].rw, dst, c->G, c->N);
@@ -685,6 +724,42 @@ int abd_deterministics(abd_ctx* c, int32_t chain, const double* theta, int8_t* i
   if (mu_s) HIP_TRY(hipMemcpyAsync(mu_s, d_s, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (i) HIP_TRY(hipMemcpyAsync(i, d_i, cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return ABD_OK;
+}
+
+int abd_set_follow_up(abd_ctx* c, const int32_t* last_gap) {
+  if (!c) return fail(ABD_ERR_ARG, "ctx is NULL");
+  if (last_gap)
+    for (int j = 0; j < c->N; ++j)
+      if (last_gap[j] < -1 || last_gap[j] >= c->G)
+        return fail(ABD_ERR_ARG, "last_gap[%d]=%d outside [-1, %d)", j, last_gap[j], c->G);
+  HIP_TRY(hipSetDevice(c->device));
+  if (int jrc = join_pipes(c)) return jrc;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a queued abd_curves launch may still read the old array)
+  if (!last_gap) {
+    c->d_last.reset();
+    return ABD_OK;
+  }
+  DevBuf<int32_t> fresh;  // (the old follow-up stays if this one cannot be stored)
+  HIP_TRY(fresh.upload(last_gap, (size_t)c->N));
+  c->d_last = std::move(fresh);
+  return ABD_OK;
+}
+
+int abd_curves(abd_ctx* c, int32_t chain, const double* theta, double thr_s, double thr_n, int64_t* counts, int64_t* n_infections,
+               double* titer_sums) {
+  if (!c || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  int rc = check_chains(c, 1, &chain);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int jrc = join_pipes(c)) return jrc;
+  const size_t n_scratch = curves_scratch_cols(c), n_row = curves_row_cols(c);
+  if (!c->d_curves) HIP_TRY(c->d_curves.alloc(n_scratch + n_row));  // kept for the next call
+  if (int lrc = launch_curves(c, chain, theta, thr_s, thr_n, c->stream, c->d_curves, c->d_curves + n_scratch)) return lrc;
+  std::vector<unsigned long long> h(n_row);
+  HIP_TRY(hipMemcpyAsync(h.data(), c->d_curves + n_scratch, n_row * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  split_curves_row(c, h.data(), counts, n_infections, titer_sums);
   return ABD_OK;
 }
 

@@ -233,6 +233,8 @@ struct abd_ctx {
   int stage_rows = 0;
   DevBuf<uint32_t> d_order;                // order_s then order_n as uint32 (the predictive stream's counter), uploaded on first use
   DevBuf<double> d_det;                    // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
+  DevBuf<int32_t> d_last;                  // [N] end of follow-up (abd_set_follow_up); empty: G - 1 for everyone
+  DevBuf<unsigned long long> d_curves;     // abd_curves: the slab rows (curves_scratch_cols), then the call's row
   std::vector<ResultSlot> results;
   // timing: 1 = HIP events around every evaluation-kernel launch, launches serialised on one stream with the full
   // grid (the isolated kernel); 2 = HIP events around every WINDOW of stream-ordered launches (first launch after an
@@ -267,6 +269,15 @@ inline int unit_pipe(const abd_ctx* c, int u) { return c->pipe_order[u % c->n_st
 int check_chains(abd_ctx* c, int n, const int32_t* chains);
 // Deterministics of chain `chain` at theta on stream st: written (G, N) gap-major and / or added to running sums
 int launch_deterministics(abd_ctx* c, int chain, const double* theta, hipStream_t st, int8_t* out_i, double* out_mun, double* out_mus, double* sums);
+// Epidemic curves of chain `chain` at theta on stream st (abd_curves.hpp): slab rows into `scratch` (curves_scratch_cols(c)
+// columns, the launch's own until it has run), the row of curves_row_cols(c) columns into `row`.  Touches no member of the
+// context but d_last: the sampler's host threads call it side by side.
+int launch_curves(abd_ctx* c, int chain, const double* theta, double thr_s, double thr_n, hipStream_t st, unsigned long long* scratch,
+                  unsigned long long* row);
+size_t curves_row_cols(const abd_ctx* c);
+size_t curves_scratch_cols(const abd_ctx* c);
+// a row as the C ABI hands it out: counts [4][G], n_infections [8], titer_sums [2][G]; nullptr skips
+void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* counts, int64_t* n_infections, double* titer_sums);
 // the chain's packed i_raw as (G, N) int8 on stream st
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st);
 

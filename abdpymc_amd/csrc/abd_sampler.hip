@@ -70,6 +70,11 @@ struct abd_sampler {
   // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
   // predictive mean, mean tail probability per reading
   DevBuf<double> d_pp_acc;
+  // epidemic curves of every draw (abd_curves.hpp): [n][curves_capacity] rows of 6 G + 8 columns, and every chain's own slab
+  // rows [n][curves_scratch_cols] (the chains' launches run side by side)
+  DevBuf<unsigned long long> d_curves, d_curves_scratch;
+  int64_t curves_capacity = 0;
+  double curves_thr_s = 0.0, curves_thr_n = 0.0;
 };
 
 namespace {
@@ -500,6 +505,11 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   if (yrep || pacc)
     if (int rc = launch_predictive(c, chain, q, st, s->o.seed, (uint32_t)((int64_t)chain + s->o.chain_offset), (uint64_t)iter, yrep,
                                    nullptr, pacc, iter - s->o.tune + 1))
+      return rc;
+  // epidemic curves: every draw's row, whatever is recorded (abd_sampler_run_record has checked the capacity)
+  if (draw && s->d_curves)
+    if (int rc = launch_curves(c, chain, q, s->curves_thr_s, s->curves_thr_n, st, s->d_curves_scratch + (size_t)j * curves_scratch_cols(c),
+                               s->d_curves + ((size_t)j * s->curves_capacity + (size_t)(iter - s->o.tune)) * curves_row_cols(c)))
       return rc;
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
@@ -1023,6 +1033,9 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (n_iter < 0) return fail(ABD_ERR_ARG, "n_iter=%lld is negative", (long long)n_iter);
   abd_ctx* c = s->c;
   const int n = s->n;
+  if (s->d_curves && s->it + n_iter - s->o.tune > s->curves_capacity)  // (before anything is launched or marked as run)
+    return fail(ABD_ERR_STATE, "curves: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
+                (long long)s->curves_capacity);
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
@@ -1114,6 +1127,57 @@ int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t
   if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
   const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
   return read_acc(s, s->d_pp_acc, k, 3, "predictive", out, n_draws, [Kt](const double* h, int v, size_t r) { return h[v * Kt + r]; });
+}
+
+int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, double thr_n) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
+  if (s->ran) return fail(ABD_ERR_STATE, "curves must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  s->d_curves.reset();  // (nothing has been launched on them: the sampler has not run)
+  s->d_curves_scratch.reset();
+  s->curves_capacity = 0;
+  if (capacity == 0) return ABD_OK;
+  const size_t n_rows = (size_t)s->n * (size_t)capacity * curves_row_cols(c);
+  DevBuf<unsigned long long> rows, scratch;  // (the sampler takes both or neither)
+  hipError_t e = rows.alloc(n_rows);
+  if (e == hipSuccess) e = scratch.alloc((size_t)s->n * curves_scratch_cols(c));
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "curves: %zu bytes of device memory", n_rows * sizeof(unsigned long long));
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "curves: %s", hipGetErrorString(e));
+  s->d_curves = std::move(rows);
+  s->d_curves_scratch = std::move(scratch);
+  s->curves_capacity = capacity;
+  s->curves_thr_s = thr_s;
+  s->curves_thr_n = thr_n;
+  return ABD_OK;
+}
+
+int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections, double* titer_sums,
+                       int64_t* n_draws) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_curves) return fail(ABD_ERR_STATE, "curves are not enabled (abd_sampler_enable_curves)");
+  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
+  if (n_draws) *n_draws = have;
+  if (first < 0 || count < 0 || first > have || count > have - first)
+    return fail(ABD_ERR_ARG, "curves: draws [%lld, %lld) are beyond the %lld the chain has", (long long)first, (long long)(first + count),
+                (long long)have);
+  if (count == 0) return ABD_OK;
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
+  const size_t n_row = curves_row_cols(c), G = (size_t)c->G;
+  std::vector<unsigned long long> h((size_t)count * n_row);
+  HIP_TRY(hipMemcpy(h.data(), s->d_curves + ((size_t)k * s->curves_capacity + (size_t)first) * n_row, h.size() * sizeof(unsigned long long),
+                    hipMemcpyDeviceToHost));
+  for (size_t d = 0; d < (size_t)count; ++d)
+    split_curves_row(c, h.data() + d * n_row, counts ? counts + d * 4 * G : nullptr, n_infections ? n_infections + d * 8 : nullptr,
+                     titer_sums ? titer_sums + d * 2 * G : nullptr);
+  return ABD_OK;
 }
 
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric) {

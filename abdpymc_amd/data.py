@@ -68,6 +68,11 @@ class TiterData:
         self.pcrpos = pcrpos
         self.n_gaps = int(n_gaps)  # max(df.elapsed_months) + 1   abd.py:101
         self.n_inds = int(n_inds)  # max(df.individual_i) + 1     abd.py:102
+        # the last gap in which each individual has a serum sample of either antigen, -1 for none (abd.py:119-125): where its
+        # follow-up ends (curves.py)
+        self.last_gap = np.full(self.n_inds, -1, dtype=np.int64)
+        for ag in (s, n):
+            np.maximum.at(self.last_gap, ag.idx_ind, ag.idx_gap)
         self.coords = dict(ind=np.arange(self.n_inds), gap=np.arange(self.n_gaps))  # abd.py:126
         # record id of every individual in order of first appearance in the table (abd.py:104-110); not used by the model
         self.record_ids = None if record_ids is None else np.asarray(record_ids)

@@ -300,7 +300,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   target_accept: float = 0.8, max_treedepth: int = 10, chunk: int = 50,
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
                   budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-                  waic: bool = False, posterior_predictive: bool = False, ppc: bool = False) -> Dict[str, np.ndarray]:
+                  waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
+                  sero_thresholds=None) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -328,7 +329,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     deviations of the predictive mean) and ``ppc_pit`` (mean of P(y_rep <= y | draw)), each (chains, K_s + K_n), S readings
     first, ``ppc_n_draws`` (chains,) and ``ppc_n_obs`` (chains, 2): ``predictive.summary`` reads them.  Neither option draws
     from any random stream the chains use: their trajectories do not change.
+
+    ``curves``: keep the epidemic curves of EVERY draw, reduced over the individuals on the device (``curves.py``; ``thin`` does
+    not apply): ``curves_infected`` / ``curves_ever_infected`` / ``curves_seropos_s`` / ``curves_seropos_n`` (counts) and
+    ``curves_titer_s`` / ``curves_titer_n`` (titer sums), each (chains, draws, G), ``curves_n_infections`` (chains, draws, 8) and
+    ``curves_n_followed`` (chains, G); ``curves.summary`` reads them.  An individual counts up to its last serum sample
+    (``model.data.last_gap`` where the model's data has one, else every gap); ``sero_thresholds`` = (thr_s, thr_n) on the titer
+    scale switch the seropositive counts on.  The trajectories do not change either.
     """
+    from . import curves as curves_mod
     from .model import THETA_NAMES, constrain
 
     ctx = model.ctx
@@ -360,7 +369,11 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         q0[c] = model.ravel(pt) + rng.uniform(-1, 1, size=len(THETA_NAMES))  # start jitter U(-1, 1) on the value variables: pm.sample's default init 'jitter+adapt_diag'
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
-                      dense_metric=dense_metric, pointwise=waic, predictive=ppc)
+                      dense_metric=dense_metric, pointwise=waic, predictive=ppc, curves=draws if curves else 0,
+                      sero_thresholds=sero_thresholds)
+    if curves:
+        last_gap = getattr(getattr(model, "data", None), "last_gap", None)
+        ctx.set_follow_up(last_gap)
     n_grad = chains  # the evaluation at the starting points
     done = 0
 
@@ -424,6 +437,10 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
             res[f"{prefix}_{name}"] = np.stack([o[j] for o, _ in per_chain])
         res[f"{prefix}_n_draws"] = np.array([n for _, n in per_chain], dtype=np.int64)
         res[f"{prefix}_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
+    if curves:
+        per_chain = [smp.curves(c) for c in range(chains)]
+        res.update(curves_mod.as_result(*(np.stack([pc[k] for pc in per_chain]) for k in ("counts", "n_infections", "titer_sums")),
+                                        curves_mod.n_followed(np.full(N, G - 1) if last_gap is None else last_gap, G)))
     if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
@@ -443,7 +460,8 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            progress: Optional[Callable[[int, int, int], None]] = None, device_gibbs: bool = True,
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-           waic: bool = False, posterior_predictive: bool = False, ppc: bool = False) -> Dict[str, np.ndarray]:
+           waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
+           sero_thresholds=None) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
@@ -451,7 +469,10 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
     if native and device_gibbs and hasattr(model.ctx, "sampler"):
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
-                             log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc)
+                             log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc,
+                             curves=curves, sero_thresholds=sero_thresholds)
+    if curves:
+        raise ValueError("curves need the native sampler (sample(native=True)): every draw is reduced on the device inside it")
     if posterior_predictive or ppc:
         raise ValueError("posterior_predictive / ppc need the native sampler (sample(native=True)): the replicates and the check "
                          "statistics are drawn and accumulated inside it")

@@ -156,6 +156,27 @@ int abd_logp_dlogp_many(abd_ctx* ctx, int32_t n_steps, int32_t n, const int32_t*
 int abd_deterministics(abd_ctx* ctx, int32_t chain, const double* theta, int8_t* i, double* ab_n_mu,
                        double* ab_s_mu);
 
+/* The epidemic curves of one draw: the Deterministics of chain slot `chain` at theta reduced over the individuals on the
+ * device.  last_gap[j] in [-1, G-1] is the end of individual j's follow-up (its last serum sample; -1: never followed) and
+ * cell (g, j) is FOLLOWED iff g <= last_gap[j].
+ *   counts [4][G]       row 0 infected       #{j followed at g: i[g, j] = 1}
+ *                       row 1 ever_infected  #{j followed at g: i[g', j] = 1 for some g' <= g}
+ *                       row 2 seropos_s      #{j followed at g: ab_s_mu[g, j] >= thr_s}
+ *                       row 3 seropos_n      #{j followed at g: ab_n_mu[g, j] >= thr_n}
+ *   n_infections [8]    entry k: individuals with last_gap[j] >= 0 that have exactly k infections in gaps 0 .. last_gap[j];
+ *                       entry 7: 7 or more
+ *   titer_sums [2][G]   row 0 the sum over the followed j of ab_s_mu[g, j], row 1 of ab_n_mu[g, j] (the caller divides by the
+ *                       number followed, which depends on last_gap alone)
+ * i, ab_s_mu, ab_n_mu are exactly what abd_deterministics returns.  thr_s, thr_n are on the titer scale; +inf switches a
+ * count off.  Any output may be NULL.  A result depends on (N, G, last_gap, the slot's state, theta, the thresholds) only and
+ * is bit-reproducible: fixed-order sums, no floating-point atomics (abdpymc_amd/csrc/abd_curves.hpp).  Non-finite theta:
+ * non-finite sums, comparisons false, status 0. */
+int abd_curves(abd_ctx* ctx, int32_t chain, const double* theta, double thr_s, double thr_n, int64_t* counts, int64_t* n_infections,
+               double* titer_sums);
+/* The follow-up the curves use: last_gap is (N,) with -1 <= last_gap[j] < G (ABD_ERR_ARG outside); NULL: everyone to G-1,
+ * the state after abd_create.  Affects the curves only. */
+int abd_set_follow_up(abd_ctx* ctx, const int32_t* last_gap);
+
 /* Pointwise log-likelihood of the two observed Normals "it_s_lik", "it_n_lik" (abd.py:459-469) at theta and chain slot
  * `chain`'s discrete state: ll_s receives s.n_obs doubles, ll_n n.n_obs, in the order the readings were given to abd_create
  * (what pm.compute_log_likelihood records for one draw).  Either pointer may be NULL.  sum(ll_s) + sum(ll_n) is
@@ -339,6 +360,18 @@ int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate);
  * Phi((y - m) / sigma), the tail probability P(y_rep <= y).  They merge exactly over chains and processes: Chan et al. for
  * rows 0 and 1, a count-weighted mean for row 2 (abdpymc_amd/predictive.py).  *n_draws (may be NULL): the number of draws. */
 int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws);
+/* The epidemic curves (abd_curves) of every draw (iteration >= tune) of every chain, kept on the device: a row of 6 G + 8
+ * numbers per draw, whatever abd_record and its thin ask for.  Allowed before the first abd_sampler_run* call (ABD_ERR_STATE
+ * after it); capacity > 0 allocates rows for that many draws per chain, 0 releases them.  While they are enabled an
+ * abd_sampler_run* call whose draws would pass capacity fails with ABD_ERR_STATE before anything is launched.  The follow-up
+ * is the context's (abd_set_follow_up) at the time of each draw.  No random numbers are drawn: the chains' trajectories do
+ * not change. */
+int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, double thr_n);
+/* Draws first .. first + count - 1 of chain k (0 <= k < n; draw 0 is iteration `tune`): counts [count][4][G], n_infections
+ * [count][8], titer_sums [count][2][G] as abd_curves lays them out; any may be NULL.  *n_draws (may be NULL) receives the
+ * number of draws the chain has.  ABD_ERR_ARG for a range beyond it.  May be called between run calls. */
+int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections,
+                       double* titer_sums, int64_t* n_draws);
 /* Current diagonal of M^-1 (17) and step size of chain k; `metric` (17 x 17, may be NULL) receives the full
  * M^-1 (the diagonal matrix when the metric is diagonal). */
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);
