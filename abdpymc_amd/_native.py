@@ -146,6 +146,8 @@ SYMBOLS = {
     "abd_sampler_predictive_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_curves": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double]),
     "abd_sampler_curves": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, _D, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_diagnostics": (C.c_int, [_P, C.c_int64, C.c_int64]),
+    "abd_sampler_diagnostics": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
@@ -595,15 +597,16 @@ class Context:
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
                 dense_metric: bool = False, pointwise: bool = False, predictive: bool = False, curves: int = 0,
-                sero_thresholds=None) -> "NativeSampler":
+                sero_thresholds=None, diagnostics=None) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
         independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
         pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
         the posterior predictive check statistics (``NativeSampler.predictive_stats``); ``curves``: keep the epidemic curves
         of that many draws per chain on the device (``NativeSampler.curves``), seropositive at ``sero_thresholds`` = (thr_s,
-        thr_n) on the titer scale (``None``: off)."""
+        thr_n) on the titer scale (``None``: off); ``diagnostics`` = (D, L): accumulate per cell what split R-hat and a
+        batch-means ESS need over the D planned draws, in batches of L (``NativeSampler.diagnostics``; ``None``: off)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise, predictive, curves, sero_thresholds)
+                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -682,7 +685,8 @@ class NativeSampler:
     per leapfrog of a unit of 1-4 chains, leapfrog trains (abd_hip.h)."""
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
-                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None):
+                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None,
+                 diagnostics=None):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -710,6 +714,9 @@ class NativeSampler:
         if int(curves):
             thr_s, thr_n = (np.inf, np.inf) if sero_thresholds is None else sero_thresholds
             _check(self._lib, self._lib.abd_sampler_enable_curves(self._h, int(curves), float(thr_s), float(thr_n)))
+        if diagnostics is not None:
+            planned, batch = diagnostics
+            _check(self._lib, self._lib.abd_sampler_enable_diagnostics(self._h, int(planned), int(batch)))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -795,6 +802,17 @@ class NativeSampler:
             _check(self._lib, self._lib.abd_sampler_curves(self._h, int(k), 0, d, _out(counts, np.int64), _out(n_inf, np.int64),
                                                            _out(sums, np.float64), None))
         return {"counts": counts, "n_infections": n_inf, "titer_sums": sums}
+
+    def diagnostics(self, k: int):
+        """The convergence accumulators of the k-th chain over its draws so far (abd_hip.h: abd_sampler_diagnostics) ->
+        {"i_counts": (4, G, N) int64 -- c_h0, c_h1, sum_cb, sum_cb2 --, "ab_n_mu", "ab_s_mu": (6, G, N) -- mean_h0, M2_h0,
+        mean_h1, M2_h1, bm_mean, bm_M2 --, "info": (4,) int64 -- draws in half 0, in half 1, batches closed, L}:
+        ``diagnostics.from_draws`` of the chain's draws."""
+        G, N = self._ctx.n_gaps, self._ctx.n_inds
+        cnt, mun, mus, info = np.empty((4, G, N), np.int64), np.empty((6, G, N)), np.empty((6, G, N)), np.empty(4, np.int64)
+        _check(self._lib, self._lib.abd_sampler_diagnostics(self._h, int(k), _out(cnt, np.int64), _out(mun, np.float64),
+                                                            _out(mus, np.float64), _out(info, np.int64)))
+        return {"i_counts": cnt, "ab_n_mu": mun, "ab_s_mu": mus, "info": info}
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

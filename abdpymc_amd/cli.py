@@ -58,6 +58,12 @@ def build_parser() -> argparse.ArgumentParser:
                         type=float, default=float("inf"))
     parser.add_argument("--sero_threshold_n", help="With --curves: N titer from which an individual counts as seropositive.",
                         type=float, default=float("inf"))
+    parser.add_argument("--diagnostics", help="Accumulate per cell of i / ab_n_mu / ab_s_mu, over all draws on the device, what split "
+                        "R-hat and a batch-means effective sample size need (--thin does not apply) and report the largest R-hat, the "
+                        "share of cells above 1.01 and the smallest ESS per variable, and the worst of the 17 scalars (diag_* and "
+                        "diag_summary_* in the output).", action="store_true")
+    parser.add_argument("--diag_batch", help="With --diagnostics: draws per batch of the batch-means ESS (default: the square root of "
+                        "half the draws).", type=int)
     return parser
 
 
@@ -96,6 +102,29 @@ def add_curves(res: dict) -> dict:
     return sm
 
 
+def add_diagnostics(res: dict, last_gap=None) -> dict:
+    """diagnostics.summary of a gathered ``diagnostics=True`` result: its arrays go into ``res`` (``diag_summary_*``), the summary
+    is returned."""
+    from . import diagnostics
+
+    sm = diagnostics.summary(res, last_gap)
+    res.update(diagnostics.summary_arrays(sm))
+    return sm
+
+
+def diagnostics_line(sm: dict) -> str:
+    """The CLI's one line about convergence: per variable over the followed cells, then the worst scalar."""
+    parts = []
+    for var in ("i", "ab_n_mu", "ab_s_mu"):
+        f = sm[var].get("followed", sm[var])
+        parts.append(f"{var} max R-hat {f['max_rhat']:.3f}, {100 * f['share_rhat_above_1.01']:.1f} % of {f['n_cells'] - f['n_constant']} "
+                     f"non-constant followed cells above 1.01, min ESS {f['min_ess']:.0f}")
+    sc = {k: v["rhat"] for k, v in sm["scalars"].items() if np.isfinite(v["rhat"])}
+    worst = max(sc, key=sc.get) if sc else None
+    parts.append(f"worst scalar {worst} R-hat {sc[worst]:.3f}" if worst else "no scalar with a finite R-hat")
+    return "diagnostics: " + "; ".join(parts)
+
+
 def add_observed(res: dict, data) -> None:
     """The observed ODs of both antigens (no chain axis: added on the rank that writes, after any gather)."""
     res["observed_data_it_s_lik"] = np.asarray(data.s.obs[3], dtype=np.float64)
@@ -114,7 +143,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
         post = {k: v for k, v in res.items()
-                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_"))
+                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_", "diag_"))
                 and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
         means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS + PPC_KEYS if k in res}
@@ -123,6 +152,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
         for k, v in res.items():
             if k.startswith("curves_"):
                 (means if k.startswith(("curves_summary_", "curves_n_followed")) else stats)[k] = v
+        means.update({k: v for k, v in res.items() if k.startswith("diag_") and k != "diag_summary_scalar_names"})  # no draw axis
         # pm.compute_log_likelihood: one variable per observed variable, its dim named as PyMC names an undimmed one
         loglik = {k[len("log_likelihood_"):]: v for k, v in res.items() if k.startswith("log_likelihood_")}
         # pm.sample_posterior_predictive: the replicates under the observed variables' names, beside the observed values
@@ -196,7 +226,8 @@ def main(argv=None) -> int:
                  record_deterministics=not args.no_deterministics, record_discrete=not args.no_discrete, progress=progress,
                  chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
                  waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc, curves=args.curves,
-                 sero_thresholds=(args.sero_threshold_s, args.sero_threshold_n))  # abd.py:922
+                 sero_thresholds=(args.sero_threshold_s, args.sero_threshold_n), diagnostics=args.diagnostics,
+                 diag_batch=args.diag_batch)  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
@@ -227,6 +258,8 @@ def main(argv=None) -> int:
                       f"{100 * ar['lower'][g]:.1f}-{100 * ar['upper'][g]:.1f}; {sm['n_followed'][g]} followed); peak monthly incidence "
                       f"{100 * inc['median'][peak]:.1f} % ({100 * inc['lower'][peak]:.1f}-{100 * inc['upper'][peak]:.1f}) at gap {peak}; "
                       f"{sm['n_draws']} draws", file=sys.stderr)
+        if args.diagnostics:
+            print(diagnostics_line(add_diagnostics(res, getattr(data, "last_gap", None))), file=sys.stderr)
         if args.posterior_predictive:
             add_observed(res, data)
         out = write_posterior(res, args.netcdf, data.coords)

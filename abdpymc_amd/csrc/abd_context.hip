@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include "abd_small.hpp"
 #include "abd_curves.hpp"
+#include "abd_diag.hpp"
 
 namespace abdi {
 
@@ -599,6 +600,36 @@ void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* 
   if (counts) std::memcpy(counts, row, 4 * G * sizeof(int64_t));
   if (n_infections) std::memcpy(n_infections, row + 4 * G, ABD_CURVES_NBIN * sizeof(int64_t));
   if (titer_sums) std::memcpy(titer_sums, row + 4 * G + ABD_CURVES_NBIN, 2 * G * sizeof(double));
+}
+
+int launch_diag(abd_ctx* c, int chain, const double* theta, hipStream_t st, int64_t d, int64_t H, int64_t L, double* tit, uint32_t* inf,
+                unsigned long long* cb2) {
+  const ChainPar p = chain_par(c, chain, theta);
+  DiagArgs a;
+  a.vw = c->vw;
+  a.iw = p.iw;
+  a.waner = p.waner;
+  a.tit = tit, a.inf = reinterpret_cast<DiagInf*>(inf), a.cb2 = cb2;
+  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
+  a.init_s = p.init_s, a.perm_s = p.perm_s;
+  a.w = diag_draw(d, H, L);
+  a.G = c->G, a.N = c->N, a.nt = c->nt;
+  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
+  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
+  if (c->nt > ABD_MAXT)
+    hipLaunchKernelGGL(abd_diag_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  else
+    hipLaunchKernelGGL(abd_diag_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
+int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsigned long long* dst, hipStream_t st) {
+  const int64_t tiles = (int64_t)((c->G + ABD_DIAG_TILE - 1) / ABD_DIAG_TILE) * ((c->N + ABD_DIAG_TILE - 1) / ABD_DIAG_TILE);
+  hipLaunchKernelGGL(abd_diag_export_kernel, dim3((unsigned)tiles), dim3(256), 0, st, static_cast<const unsigned char*>(src), stride, width,
+                     c->G, c->N, dst);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
 }
 
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st) {

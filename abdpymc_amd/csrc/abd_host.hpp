@@ -278,6 +278,14 @@ size_t curves_row_cols(const abd_ctx* c);
 size_t curves_scratch_cols(const abd_ctx* c);
 // a row as the C ABI hands it out: counts [4][G], n_infections [8], titer_sums [2][G]; nullptr skips
 void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* counts, int64_t* n_infections, double* titer_sums);
+// Draw d (= iteration - tune, in [0, 2 H)) of chain `chain` at theta into its convergence accumulators on stream st
+// (abd_diag.hpp; H the half length, L the batch length): tit [2][7][G*N], inf [G*N][4] and cb2 [G*N] are the chain's own
+// planes.  Touches no member of the context.
+int launch_diag(abd_ctx* c, int chain, const double* theta, hipStream_t st, int64_t d, int64_t H, int64_t L, double* tit, uint32_t* inf,
+                unsigned long long* cb2);
+// One individual-major plane of the accumulators (first element src, elements `stride` bytes apart, `width` 4 or 8 bytes
+// wide) into dst [G*N] in the caller's gap-major order, 8 bytes per cell, on stream st
+int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsigned long long* dst, hipStream_t st);
 // the chain's packed i_raw as (G, N) int8 on stream st
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st);
 

@@ -75,6 +75,12 @@ struct abd_sampler {
   DevBuf<unsigned long long> d_curves, d_curves_scratch;
   int64_t curves_capacity = 0;
   double curves_thr_s = 0.0, curves_thr_n = 0.0;
+  // convergence accumulators over all draws (abd_diag.hpp), individual-major planes per chain: [n][2][7][G*N] of the two
+  // titers, [n][G*N][4] and [n][G*N] of i, and one plane [G*N] of staging for the read-out
+  DevBuf<double> d_diag_tit;
+  DevBuf<uint32_t> d_diag_inf;
+  DevBuf<unsigned long long> d_diag_cb2, d_diag_stage;
+  int64_t diag_draws = 0, diag_H = 0, diag_L = 0;  // planned draws D, H = D / 2, batch length
 };
 
 namespace {
@@ -510,6 +516,11 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   if (draw && s->d_curves)
     if (int rc = launch_curves(c, chain, q, s->curves_thr_s, s->curves_thr_n, st, s->d_curves_scratch + (size_t)j * curves_scratch_cols(c),
                                s->d_curves + ((size_t)j * s->curves_capacity + (size_t)(iter - s->o.tune)) * curves_row_cols(c)))
+      return rc;
+  // convergence accumulators: every draw of the two halves, whatever is recorded (abd_sampler_run_record has checked D)
+  if (draw && s->d_diag_tit && iter - s->o.tune < 2 * s->diag_H)
+    if (int rc = launch_diag(c, chain, q, st, iter - s->o.tune, s->diag_H, s->diag_L, s->d_diag_tit + (size_t)j * 2 * 7 * cells,
+                             s->d_diag_inf + (size_t)j * 4 * cells, s->d_diag_cb2 + (size_t)j * cells))
       return rc;
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
@@ -1036,6 +1047,9 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (s->d_curves && s->it + n_iter - s->o.tune > s->curves_capacity)  // (before anything is launched or marked as run)
     return fail(ABD_ERR_STATE, "curves: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
                 (long long)s->curves_capacity);
+  if (s->d_diag_tit && s->it + n_iter - s->o.tune > s->diag_draws)
+    return fail(ABD_ERR_STATE, "diagnostics: draws up to %lld pass the planned %lld", (long long)(s->it + n_iter - s->o.tune),
+                (long long)s->diag_draws);
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
@@ -1177,6 +1191,88 @@ int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, 
   for (size_t d = 0; d < (size_t)count; ++d)
     split_curves_row(c, h.data() + d * n_row, counts ? counts + d * 4 * G : nullptr, n_infections ? n_infections + d * 8 : nullptr,
                      titer_sums ? titer_sums + d * 2 * G : nullptr);
+  return ABD_OK;
+}
+
+int abd_sampler_enable_diagnostics(abd_sampler* s, int64_t planned_draws, int64_t batch_len) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (planned_draws < 0 || planned_draws == 1) return fail(ABD_ERR_ARG, "diagnostics: planned_draws=%lld is neither 0 nor >= 2", (long long)planned_draws);
+  if (planned_draws && batch_len < 1) return fail(ABD_ERR_ARG, "diagnostics: batch_len=%lld is below 1", (long long)batch_len);
+  if (s->ran) return fail(ABD_ERR_STATE, "diagnostics must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  s->d_diag_tit.reset();  // (nothing has been launched on them: the sampler has not run)
+  s->d_diag_inf.reset();
+  s->d_diag_cb2.reset();
+  s->d_diag_stage.reset();
+  s->diag_draws = s->diag_H = s->diag_L = 0;
+  if (planned_draws == 0) return ABD_OK;
+  const size_t cells = (size_t)c->G * c->N, n = (size_t)s->n;
+  const size_t bytes = n * cells * (2 * 7 * sizeof(double) + 4 * sizeof(uint32_t) + sizeof(unsigned long long)) + cells * sizeof(unsigned long long);
+  DevBuf<double> tit;  // (the sampler takes all four or none)
+  DevBuf<uint32_t> inf;
+  DevBuf<unsigned long long> cb2, stage;
+  hipError_t e = tit.alloc_zero(std::max<size_t>(1, n * 2 * 7 * cells), c->stream);
+  if (e == hipSuccess) e = inf.alloc_zero(std::max<size_t>(1, n * 4 * cells), c->stream);
+  if (e == hipSuccess) e = cb2.alloc_zero(std::max<size_t>(1, n * cells), c->stream);
+  if (e == hipSuccess) e = stage.alloc(std::max<size_t>(1, cells));
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "diagnostics: %zu bytes of device memory", bytes);
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "diagnostics: %s", hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->d_diag_tit = std::move(tit);
+  s->d_diag_inf = std::move(inf);
+  s->d_diag_cb2 = std::move(cb2);
+  s->d_diag_stage = std::move(stage);
+  s->diag_draws = planned_draws;
+  s->diag_H = planned_draws / 2;
+  s->diag_L = batch_len;
+  return ABD_OK;
+}
+
+int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double* ab_n_mu, double* ab_s_mu, int64_t* info) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_diag_tit) return fail(ABD_ERR_STATE, "diagnostics are not enabled (abd_sampler_enable_diagnostics)");
+  const int64_t H = s->diag_H, L = s->diag_L, B = H / L;
+  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune), n0 = std::min(have, H), n1 = std::min(std::max<int64_t>(0, have - H), H);
+  if (info) {
+    info[0] = n0;
+    info[1] = n1;
+    info[2] = std::min(n0 / L, B) + std::min(n1 / L, B);
+    info[3] = L;
+  }
+  if (!i_counts && !ab_n_mu && !ab_s_mu) return ABD_OK;
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
+  const size_t cells = (size_t)c->G * c->N;
+  // one plane at a time through the staging plane: transposed on the device, copied out (the copy waits for the kernel and
+  // the next kernel for the copy: the context's stream)
+  auto plane = [&](const void* src, int stride, int width, void* out) -> int {
+    if (int rc = launch_diag_export(c, src, stride, width, s->d_diag_stage, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s->d_diag_stage, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ABD_OK;
+  };
+  if (!cells) return ABD_OK;
+  if (i_counts) {
+    const uint32_t* inf = s->d_diag_inf + (size_t)k * 4 * cells;
+    const int comp[3] = {0, 1, 3};  // c_h0, c_h1, sum_cb of the 16-byte element (cur is not handed out)
+    for (int v = 0; v < 3; ++v)
+      if (int rc = plane(inf + comp[v], 16, 4, i_counts + (size_t)v * cells)) return rc;
+    if (int rc = plane(s->d_diag_cb2 + (size_t)k * cells, 8, 8, i_counts + 3 * cells)) return rc;
+  }
+  double* outs[2] = {ab_n_mu, ab_s_mu};
+  const int planes[6] = {0, 1, 2, 3, 5, 6};  // mean_h0, M2_h0, mean_h1, M2_h1, bm_mean, bm_M2 (cur is not handed out)
+  for (int x = 0; x < 2; ++x) {
+    if (!outs[x]) continue;
+    const double* tit = s->d_diag_tit + ((size_t)k * 2 + x) * 7 * cells;
+    for (int v = 0; v < 6; ++v)
+      if (int rc = plane(tit + (size_t)planes[v] * cells, 8, 8, outs[x] + (size_t)v * cells)) return rc;
+  }
   return ABD_OK;
 }
 

@@ -301,7 +301,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
                   budget_bytes: Optional[int] = None, log_likelihood: bool = False,
                   waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-                  sero_thresholds=None) -> Dict[str, np.ndarray]:
+                  sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -336,8 +336,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     ``curves_n_followed`` (chains, G); ``curves.summary`` reads them.  An individual counts up to its last serum sample
     (``model.data.last_gap`` where the model's data has one, else every gap); ``sero_thresholds`` = (thr_s, thr_n) on the titer
     scale switch the seropositive counts on.  The trajectories do not change either.
+
+    ``diagnostics``: accumulate per cell, over ALL draws on the device, what split R-hat and a batch-means effective sample size
+    of ``i``, ``ab_n_mu``, ``ab_s_mu`` need (``diagnostics.py``; ``thin`` does not apply): ``diag_i_counts`` (chains, 4, G, N) int64,
+    ``diag_ab_n_mu`` / ``diag_ab_s_mu`` (chains, 6, G, N) and ``diag_info`` (chains, 4); ``diagnostics.rhat`` / ``ess`` / ``summary``
+    read them.  ``diag_batch`` is the batch length (default ``max(1, floor(sqrt(draws // 2)))``).  Needs ``draws >= 2``; the
+    arrays' host bytes count against ``budget_bytes``.  The trajectories do not change either.
     """
     from . import curves as curves_mod
+    from . import diagnostics as diag_mod
     from .model import THETA_NAMES, constrain
 
     ctx = model.ctx
@@ -347,6 +354,12 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     n_rec = (draws + thin - 1) // thin
     K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if (log_likelihood or waic or posterior_predictive or ppc) else (0, 0)  # readings of it_s_lik / it_n_lik
     per_reading = log_likelihood or posterior_predictive  # per-draw rows of the readings
+    if diagnostics:
+        if draws < 2:
+            raise ValueError(f"diagnostics need draws >= 2 (two half-chains), got {draws}")
+        diag_batch = diag_mod.default_batch(draws) if diag_batch is None else int(diag_batch)
+        if diag_batch < 1:
+            raise ValueError(f"diag_batch must be >= 1, got {diag_batch}")
     if record_deterministics or record_discrete or per_reading:
         budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
         need = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
@@ -360,6 +373,18 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                 f"recording {n_rec} draws of {chains} chains x ({G}, {N}) needs {need / 2 ** 30:.1f} GiB of host arrays, over the "
                 f"budget of {budget / 2 ** 30:.1f} GiB: thin >= {thin_fit} fits (or record less: no_deterministics / "
                 f"record_discrete=False; the posterior means are returned either way; ABD_RECORD_BUDGET_GB raises the budget)")
+    if diagnostics:
+        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
+        own = diag_mod.result_bytes(chains, G, N)
+        need = own + record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
+                                  n_readings=(K_s + K_n) if log_likelihood else 0,
+                                  n_replicates=(K_s + K_n) if posterior_predictive else 0)
+        if need > budget:
+            raise ValueError(
+                f"the diagnostics of {chains} chains x ({G}, {N}) take {own / 2 ** 30:.2f} GiB of host arrays (16 planes of 8 bytes "
+                f"per cell and chain) and the recorded draws {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
+                f"{budget / 2 ** 30:.2f} GiB: record fewer draws (thin, no_deterministics / record_discrete=False) or raise "
+                f"ABD_RECORD_BUDGET_GB")
     chunk = max(thin, chunk - chunk % thin) if thin > 1 else chunk  # calls record iterations 0, thin, ... of THEIR range
     pt = model.initial_point()
     q0 = np.empty((chains, len(THETA_NAMES)))
@@ -370,7 +395,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
                       dense_metric=dense_metric, pointwise=waic, predictive=ppc, curves=draws if curves else 0,
-                      sero_thresholds=sero_thresholds)
+                      sero_thresholds=sero_thresholds, diagnostics=(draws, diag_batch) if diagnostics else None)
     if curves:
         last_gap = getattr(getattr(model, "data", None), "last_gap", None)
         ctx.set_follow_up(last_gap)
@@ -441,6 +466,10 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         per_chain = [smp.curves(c) for c in range(chains)]
         res.update(curves_mod.as_result(*(np.stack([pc[k] for pc in per_chain]) for k in ("counts", "n_infections", "titer_sums")),
                                         curves_mod.n_followed(np.full(N, G - 1) if last_gap is None else last_gap, G)))
+    if diagnostics:
+        per_chain = [smp.diagnostics(c) for c in range(chains)]
+        for key, name in (("i_counts", "diag_i_counts"), ("ab_n_mu", "diag_ab_n_mu"), ("ab_s_mu", "diag_ab_s_mu"), ("info", "diag_info")):
+            res[name] = np.stack([pc[key] for pc in per_chain])
     if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
@@ -461,7 +490,7 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
            waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-           sero_thresholds=None) -> Dict[str, np.ndarray]:
+           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
@@ -470,7 +499,9 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
                              log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc,
-                             curves=curves, sero_thresholds=sero_thresholds)
+                             curves=curves, sero_thresholds=sero_thresholds, diagnostics=diagnostics, diag_batch=diag_batch)
+    if diagnostics:
+        raise ValueError("diagnostics need the native sampler (sample(native=True)): the moments of every draw are accumulated inside it")
     if curves:
         raise ValueError("curves need the native sampler (sample(native=True)): every draw is reduced on the device inside it")
     if posterior_predictive or ppc:

@@ -372,6 +372,41 @@ int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, do
  * number of draws the chain has.  ABD_ERR_ARG for a range beyond it.  May be called between run calls. */
 int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections,
                        double* titer_sums, int64_t* n_draws);
+
+/* Per-cell convergence accumulators over ALL draws: what split R-hat and a batch-means effective sample size of the
+ * Deterministics "i", "ab_n_mu", "ab_s_mu" need, kept on the device because a run at full size never keeps its draws
+ * (abdpymc_amd/csrc/abd_diag.hpp; abdpymc_amd/diagnostics.py: from_draws is the same definition as NumPy, rhat / ess read it).
+ *
+ * planned_draws = D >= 2 and batch_len = L >= 1.  Draw d = 0, 1, ... is iteration tune + d.
+ *   H = D / 2 (integer division) is the half length: half 0 is draws 0 .. H-1, half 1 draws H .. 2H-1.  A draw >= 2H (the last
+ *   one when D is odd) is not accumulated.  A run call whose draws would pass D fails with ABD_ERR_STATE before anything is
+ *   launched.
+ *   Each half is cut into B = H / L whole batches of L draws from its start; the trailing H % L draws of a half enter the
+ *   half's moments but no batch.  No batch straddles the halves.
+ * Per chain and cell (g, j), for x = ab_n_mu and for x = ab_s_mu (the Deterministics' titers), seven doubles, all 0 at first:
+ *   mean_h, M2_h for h = 0, 1 -- Welford, n the draw's 1-based place in its half, inv_n = 1.0 / n computed by the host:
+ *       d = x - mean;  mean += d * inv_n;  M2 += d * (x - mean)
+ *   cur -- the running sum of the open batch: cur = x on the first draw of a batch, else cur += x
+ *   bm_mean, bm_M2 -- Welford over the closed batches' means, updated by the draw that closes a batch, inv_L = 1.0 / L and
+ *   inv_b = 1.0 / (batches closed so far in this chain, this one included, both halves pooled):
+ *       bm = cur * inv_L;  e = bm - bm_mean;  bm_mean += e * inv_b;  bm_M2 += e * (bm - bm_mean)
+ * and for i, whose value is 0 or 1 so that every moment is a function of counts, integers only:
+ *   uint32 c_h0, c_h1 (ones in either half), uint32 cur (ones in the open batch), uint32 sum_cb (the sum of the closed
+ *   batches' counts), uint64 sum_cb2 (the sum of their squares).
+ * That is 136 bytes per cell and chain.  A cell belongs to one lane, a chain has its own planes, the update is a fixed-order
+ * read-modify-write: there are no atomics of any kind and the result is bit-reproducible -- it depends on the draws alone,
+ * not on the launch shape, on how the run is cut into calls, on abd_record or on thin.  No random numbers are drawn: the
+ * trajectories do not change.
+ *
+ * Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it).  planned_draws = 0 releases the buffers;
+ * planned_draws of 1 or negative, or planned_draws > 0 with batch_len < 1: ABD_ERR_ARG.  ABD_ERR_NOMEM, the message naming
+ * the bytes, when the device cannot hold them. */
+int abd_sampler_enable_diagnostics(abd_sampler* s, int64_t planned_draws, int64_t batch_len);
+/* The accumulators of chain k, (G, N) gap-major per plane like the Deterministics: i_counts [4][G*N] = c_h0, c_h1, sum_cb,
+ * sum_cb2 (widened to int64); ab_n_mu and ab_s_mu [6][G*N] = mean_h0, M2_h0, mean_h1, M2_h1, bm_mean, bm_M2; info[4] = draws
+ * in half 0, draws in half 1, batches closed, L.  Any pointer may be NULL.  May be called between run calls.  ABD_ERR_STATE
+ * ("not enabled") without abd_sampler_enable_diagnostics. */
+int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double* ab_n_mu, double* ab_s_mu, int64_t info[4]);
 /* Current diagonal of M^-1 (17) and step size of chain k; `metric` (17 x 17, may be NULL) receives the full
  * M^-1 (the diagonal matrix when the metric is diagonal). */
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);

@@ -2,12 +2,13 @@
 Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals x 200 gaps, 4 M readings): wall time of a
 4-chain compound sampler run with and without on-device WAIC accumulation (``--leg waic``: sample(..., waic=True)) or posterior
 predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the epidemic curves of every draw (``--leg curves``:
-sample(..., curves=True); not a per-reading output, but the same question), alternated.  With two run lengths (``--draws 100 400``) the
+sample(..., curves=True); not a per-reading output, but the same question) or the per-cell convergence accumulators
+(``--leg diagnostics``: sample(..., diagnostics=True); likewise), alternated.  With two run lengths (``--draws 100 400``) the
 fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both on, for
 ``rocprofv3 --kernel-trace --stats -- python tools/probe_readings.py --profile``: the kernel's own time per draw and chain of
 each op (abd_readings_dense_kernel<LogLik, ...>, <Predictive, ...>) in the same run; with ``--leg curves`` the short sample has
-the curves on instead (abd_curves_kernel, abd_curves_sum_kernel beside abd_deterministics_kernel with its running sums).  Prints
-one JSON line.
+the curves on instead (abd_curves_kernel, abd_curves_sum_kernel beside abd_deterministics_kernel with its running sums), with
+``--leg diagnostics`` the accumulators (abd_diag_kernel beside the same).  Prints one JSON line.
 """
 import argparse
 import json
@@ -27,7 +28,7 @@ from abdpymc_amd.sampler import sample  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("waic", "ppc", "curves"), default="waic")
+    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
@@ -44,7 +45,7 @@ def main():
     kw = dict(tune=a.tune, chains=a.chains, seed=1, record_deterministics=False, record_discrete=False)
     if a.profile:
         t0 = time.perf_counter()
-        on = dict(curves=True) if a.leg == "curves" else dict(waic=True, ppc=True)
+        on = {a.leg: True} if a.leg in ("curves", "diagnostics") else dict(waic=True, ppc=True)
         sample(m, draws=a.draws[0], **on, **kw)
         print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on,
                               wall_s=time.perf_counter() - t0)))
