@@ -101,6 +101,24 @@ STAT_NAMES = ("lp", "tree_depth", "n_steps", "mean_tree_accept", "step_size", "d
 _lib = None
 
 # every symbol include/abd_hip.h declares: name -> (restype, argtypes)
+class _RiskSpec(C.Structure):  # abd_risk_spec
+    _fields_ = [("start", C.c_int32), ("end", C.c_int32), ("first_only", C.c_int32), ("n_edges_s", C.c_int32),
+                ("n_edges_n", C.c_int32), ("edges_s", C.c_double * 7), ("edges_n", C.c_double * 7)]
+
+
+def _risk_spec(spec) -> "_RiskSpec":
+    """``risk.spec``'s dict (or anything with its keys) as the ABI's struct; the library checks the values."""
+    r = _RiskSpec()
+    r.start, r.end, r.first_only = int(spec["start"]), int(spec["end"]), int(spec["first_only"])
+    for name in ("edges_s", "edges_n"):
+        e = np.atleast_1d(np.asarray(spec[name], dtype=np.float64))
+        if e.ndim != 1 or e.size > 7:
+            raise ValueError(f"{name}: at most 7 edges in one dimension, got shape {e.shape}")
+        setattr(r, "n_" + name, int(e.size))
+        getattr(r, name)[: e.size] = e.tolist()
+    return r
+
+
 _P = C.c_void_p
 # array arguments (double*, int32_t*, int8_t*) are passed as plain addresses: building a typed ctypes pointer per argument
 # (ndarray.ctypes.data_as) costs 1.5-3 us each, which is a third of a synchronous call on a small cohort
@@ -130,6 +148,7 @@ SYMBOLS = {
     "abd_deterministics": (C.c_int, [_P, C.c_int32, _D, _I8, _D, _D]),
     "abd_curves": (C.c_int, [_P, C.c_int32, _D, C.c_double, C.c_double, _D, _D, _D]),
     "abd_set_follow_up": (C.c_int, [_P, _I32]),
+    "abd_risk": (C.c_int, [_P, C.c_int32, _D, C.POINTER(_RiskSpec), _D]),
     "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_posterior_predictive": (C.c_int, [_P, C.c_int32, _D, C.c_uint64, C.c_uint32, C.c_uint64, _D, _D, _D, _D]),
     "abd_simulate": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, _I8, _D, _D, _D, _D, _D]),
@@ -146,6 +165,8 @@ SYMBOLS = {
     "abd_sampler_predictive_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_curves": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double]),
     "abd_sampler_curves": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, _D, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_risk": (C.c_int, [_P, C.c_int64, C.POINTER(_RiskSpec)]),
+    "abd_sampler_risk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_diagnostics": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "abd_sampler_diagnostics": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
@@ -518,6 +539,18 @@ class Context:
                                                _out(counts, np.int64), _out(n_inf, np.int64), _out(sums, np.float64)))
         return {"counts": counts, "n_infections": n_inf, "titer_sums": sums}
 
+    def risk(self, chain: int, theta, spec):
+        """The infection-risk-by-titer table of (theta, the chain slot's discrete state), reduced over the individuals on the
+        device -> (2, 2, G, 8) int64, antigen (S, N) x (at risk, events) x gap x bin: ``risk.from_deterministics`` of
+        ``deterministics(chain, theta)`` under the context's follow-up (``set_follow_up``) and ``spec`` (``risk.spec``)."""
+        t = _as(theta, np.float64)
+        if t.shape != (N_THETA,):
+            raise ValueError(f"theta must have shape ({N_THETA},)")
+        sp = _risk_spec(spec)
+        table = np.empty((2, 2, self.n_gaps, 8), np.int64)
+        _check(self._lib, self._lib.abd_risk(self._h, int(chain), _ptr(t, C.c_double), C.byref(sp), _out(table, np.int64)))
+        return table
+
     def pointwise_loglik(self, chain: int, theta):
         """Log-density of every OD reading at (theta, the chain slot's discrete state) -> (ll_s, ll_n), each in the order the
         readings were given (what ``pm.compute_log_likelihood`` records per draw for ``it_s_lik`` / ``it_n_lik``)."""
@@ -597,16 +630,18 @@ class Context:
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
                 dense_metric: bool = False, pointwise: bool = False, predictive: bool = False, curves: int = 0,
-                sero_thresholds=None, diagnostics=None) -> "NativeSampler":
+                sero_thresholds=None, diagnostics=None, risk: int = 0, risk_spec=None) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
         independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
         pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
         the posterior predictive check statistics (``NativeSampler.predictive_stats``); ``curves``: keep the epidemic curves
         of that many draws per chain on the device (``NativeSampler.curves``), seropositive at ``sero_thresholds`` = (thr_s,
         thr_n) on the titer scale (``None``: off); ``diagnostics`` = (D, L): accumulate per cell what split R-hat and a
-        batch-means ESS need over the D planned draws, in batches of L (``NativeSampler.diagnostics``; ``None``: off)."""
+        batch-means ESS need over the D planned draws, in batches of L (``NativeSampler.diagnostics``; ``None``: off); ``risk``:
+        keep the infection-risk-by-titer table of that many draws per chain on the device, counted under ``risk_spec``
+        (``risk.spec``; ``NativeSampler.risk``)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics)
+                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics, risk, risk_spec)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -686,7 +721,7 @@ class NativeSampler:
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
                  chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None,
-                 diagnostics=None):
+                 diagnostics=None, risk=0, risk_spec=None):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -717,6 +752,13 @@ class NativeSampler:
         if diagnostics is not None:
             planned, batch = diagnostics
             _check(self._lib, self._lib.abd_sampler_enable_diagnostics(self._h, int(planned), int(batch)))
+        if int(risk) < 0:
+            raise ValueError(f"risk must be a number of draws >= 0, got {risk}")
+        if int(risk):
+            if risk_spec is None:
+                raise ValueError("risk needs a risk_spec (risk.spec)")
+            sp = _risk_spec(risk_spec)
+            _check(self._lib, self._lib.abd_sampler_enable_risk(self._h, int(risk), C.byref(sp)))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -813,6 +855,18 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_diagnostics(self._h, int(k), _out(cnt, np.int64), _out(mun, np.float64),
                                                             _out(mus, np.float64), _out(info, np.int64)))
         return {"i_counts": cnt, "ab_n_mu": mun, "ab_s_mu": mus, "info": info}
+
+    def risk(self, k: int):
+        """The infection-risk-by-titer table of every draw of the k-th chain so far (``Context.risk`` per draw) -> (draws, 2, 2, G,
+        8) int64."""
+        G = self._ctx.n_gaps
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_risk(self._h, int(k), 0, 0, None, C.byref(n)))
+        d = n.value
+        table = np.empty((d, 2, 2, G, 8), np.int64)
+        if d:
+            _check(self._lib, self._lib.abd_sampler_risk(self._h, int(k), 0, d, _out(table, np.int64), None))
+        return table
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

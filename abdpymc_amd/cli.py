@@ -64,6 +64,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "diag_summary_* in the output).", action="store_true")
     parser.add_argument("--diag_batch", help="With --diagnostics: draws per batch of the batch-means ESS (default: the square root of "
                         "half the draws).", type=int)
+    parser.add_argument("--risk", help="Keep the infection-risk-by-titer table of every draw (person-gaps at risk and infections by gap "
+                        "and by bin of the previous gap's titer; reduced over the individuals on the device, --thin does not apply) "
+                        "and report per antigen the protection (1 - the rate ratio stratified by gap) of the highest populated bin "
+                        "against bin 0 with its 95 %% interval (risk_* in the output).  An individual counts up to its last serum "
+                        "sample and, without --risk_all_infections, up to its first infection inside the window.", action="store_true")
+    parser.add_argument("--risk_edges_s", help="With --risk: up to 7 ascending S titer bin edges, separated by commas.", default="")
+    parser.add_argument("--risk_edges_n", help="With --risk: up to 7 ascending N titer bin edges, separated by commas.", default="")
+    parser.add_argument("--risk_start", help="With --risk: the window's first gap; risk is counted from the gap after it.", type=int,
+                        default=0)
+    parser.add_argument("--risk_end", help="With --risk: the end of the window, one past its last gap (default: the number of gaps).",
+                        type=int)
+    parser.add_argument("--risk_all_infections", help="With --risk: count every infection of an individual inside the window, not "
+                        "only the first.", action="store_true")
     return parser
 
 
@@ -100,6 +113,53 @@ def add_curves(res: dict) -> dict:
     sm = curves.summary(res)
     res.update(curves.summary_arrays(sm))
     return sm
+
+
+def risk_spec_of(args, n_gaps: int):
+    """The ``risk.spec`` the --risk flags ask for (``None`` without --risk); ``SystemExit`` for what ``risk.spec`` refuses."""
+    if not args.risk:
+        return None
+    from . import risk
+
+    try:
+        edges = [[float(x) for x in text.split(",") if x.strip()] for text in (args.risk_edges_s, args.risk_edges_n)]
+        return risk.spec(args.risk_start, args.risk_end, edges[0], edges[1], not args.risk_all_infections, n_gaps=n_gaps)
+    except ValueError as e:
+        raise SystemExit(f"--risk: {e}")
+
+
+def add_risk(res: dict) -> dict:
+    """risk.summary of a gathered ``risk=spec`` result.  The per-draw table is replaced in ``res`` by what a posterior file
+    keeps of it: ``risk_by_bin`` (chains, draws, 2, 2, 8) the table summed over the gaps, ``risk_rate_ratio`` (chains, draws, 2,
+    8) the per-draw rate ratios against bin 0, ``risk_table_sum`` (chains, 2, 2, G, 8) the table summed over the draws, and
+    ``risk_summary_*``.  The summary is returned."""
+    from . import risk
+
+    sm = risk.summary(res)
+    table = res.pop("risk_table")
+    pd = risk.per_draw(table)
+    res["risk_by_bin"], res["risk_rate_ratio"] = pd["by_bin"], pd["rate_ratio"]
+    res["risk_table_sum"] = table.sum(axis=1)
+    res.update(risk.summary_arrays(sm))
+    return sm
+
+
+def risk_line(sm: dict) -> str:
+    """The CLI's one line about infection risk by titer: per antigen the highest populated bin against bin 0."""
+    pct = int(round(100 * sm["prob"]))
+    parts = []
+    for name in ("s", "n"):
+        a = sm[name]
+        used = np.flatnonzero(np.nan_to_num(a["person_gaps"]["median"]) > 0)
+        top = int(used[-1]) if used.size else 0
+        if top == 0:
+            parts.append(f"{name.upper()} no populated bin above bin 0")
+            continue
+        p = a["protection"]
+        parts.append(f"{name.upper()} protection of bin {top} against bin 0 {100 * p['median'][top]:.1f} % ({pct} % interval "
+                     f"{100 * p['lower'][top]:.1f} to {100 * p['upper'][top]:.1f}; defined in {int(p['n_defined'][top])} of "
+                     f"{sm['n_draws']} draws)")
+    return "risk: " + "; ".join(parts)
 
 
 def add_diagnostics(res: dict, last_gap=None) -> dict:
@@ -143,7 +203,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
         post = {k: v for k, v in res.items()
-                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_", "diag_"))
+                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_", "diag_", "risk_"))
                 and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
         means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS + PPC_KEYS if k in res}
@@ -153,6 +213,10 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
             if k.startswith("curves_"):
                 (means if k.startswith(("curves_summary_", "curves_n_followed")) else stats)[k] = v
         means.update({k: v for k, v in res.items() if k.startswith("diag_") and k != "diag_summary_scalar_names"})  # no draw axis
+        # the risk tables: what has a draw axis sits (and is thinned) with the statistics, the rest travels with the means
+        for k, v in res.items():
+            if k.startswith("risk_"):
+                (stats if k in ("risk_table", "risk_by_bin", "risk_rate_ratio") else means)[k] = v
         # pm.compute_log_likelihood: one variable per observed variable, its dim named as PyMC names an undimmed one
         loglik = {k[len("log_likelihood_"):]: v for k, v in res.items() if k.startswith("log_likelihood_")}
         # pm.sample_posterior_predictive: the replicates under the observed variables' names, beside the observed values
@@ -196,6 +260,7 @@ def main(argv=None) -> int:
         if (not args.split_delta) and (not args.split_omicron)
         else data.calculate_splits(delta=args.split_delta, omicron=args.split_omicron)
     )  # abd.py:915-919
+    risk_spec = risk_spec_of(args, data.n_gaps)  # (refused before anything is built)
     # pm.sample(cores=...) (abd.py:922) runs chains = max(2, cores) with cores = min(4, CPU count) when not given
     import os
 
@@ -227,7 +292,7 @@ def main(argv=None) -> int:
                  chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
                  waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc, curves=args.curves,
                  sero_thresholds=(args.sero_threshold_s, args.sero_threshold_n), diagnostics=args.diagnostics,
-                 diag_batch=args.diag_batch)  # abd.py:922
+                 diag_batch=args.diag_batch, risk=risk_spec)  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
@@ -258,6 +323,8 @@ def main(argv=None) -> int:
                       f"{100 * ar['lower'][g]:.1f}-{100 * ar['upper'][g]:.1f}; {sm['n_followed'][g]} followed); peak monthly incidence "
                       f"{100 * inc['median'][peak]:.1f} % ({100 * inc['lower'][peak]:.1f}-{100 * inc['upper'][peak]:.1f}) at gap {peak}; "
                       f"{sm['n_draws']} draws", file=sys.stderr)
+        if args.risk:
+            print(risk_line(add_risk(res)), file=sys.stderr)
         if args.diagnostics:
             print(diagnostics_line(add_diagnostics(res, getattr(data, "last_gap", None))), file=sys.stderr)
         if args.posterior_predictive:

@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include "abd_small.hpp"
 #include "abd_curves.hpp"
+#include "abd_risk.hpp"
 #include "abd_diag.hpp"
 
 namespace abdi {
@@ -632,6 +633,59 @@ int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsig
   return ABD_OK;
 }
 
+size_t risk_table_cols(const abd_ctx* c) { return (size_t)abd_risk_table_cols(c->G); }
+size_t risk_scratch_cols(const abd_ctx* c) { return (size_t)abd_curves_slabs(c->N) * (size_t)abd_risk_packed_cols(c->G); }
+
+int check_risk_spec(const abd_ctx* c, const abd_risk_spec* spec) {
+  if (!spec) return fail(ABD_ERR_ARG, "risk: spec is NULL");
+  if (spec->start < 0 || spec->end > c->G || (int64_t)spec->end - spec->start < 2)
+    return fail(ABD_ERR_ARG, "risk: window (%d, %d) needs 0 <= start, end <= %d and end - start >= 2", spec->start, spec->end, c->G);
+  if (spec->first_only != 0 && spec->first_only != 1) return fail(ABD_ERR_ARG, "risk: first_only=%d is not 0 or 1", spec->first_only);
+  const struct { const char* name; int n; const double* e; } ag[2] = {{"edges_s", spec->n_edges_s, spec->edges_s},
+                                                                     {"edges_n", spec->n_edges_n, spec->edges_n}};
+  for (const auto& x : ag) {
+    if (x.n < 0 || x.n > ABD_RISK_MAX_EDGES) return fail(ABD_ERR_ARG, "risk: n_%s=%d outside [0, %d]", x.name, x.n, ABD_RISK_MAX_EDGES);
+    for (int k = 0; k < x.n; ++k) {
+      if (!std::isfinite(x.e[k])) return fail(ABD_ERR_ARG, "risk: %s[%d] is not finite", x.name, k);
+      if (k && !(x.e[k] > x.e[k - 1])) return fail(ABD_ERR_ARG, "risk: %s is not strictly ascending at [%d]", x.name, k);
+    }
+  }
+  return ABD_OK;
+}
+
+int launch_risk(abd_ctx* c, int chain, const double* theta, const abd_risk_spec& spec, hipStream_t st, unsigned long long* scratch,
+                uint32_t* table) {
+  const ChainPar p = chain_par(c, chain, theta);
+  RiskArgs a;
+  a.vw = c->vw;
+  a.iw = p.iw;
+  a.waner = p.waner;
+  a.last = c->d_last;
+  a.slab_rows = scratch;
+  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
+  a.init_s = p.init_s, a.perm_s = p.perm_s;
+  for (int k = 0; k < ABD_RISK_MAX_EDGES; ++k) {
+    a.edges_s[k] = k < spec.n_edges_s ? spec.edges_s[k] : HUGE_VAL;
+    a.edges_n[k] = k < spec.n_edges_n ? spec.edges_n[k] : HUGE_VAL;
+  }
+  a.G = c->G, a.N = c->N, a.nt = c->nt, a.n_slabs = abd_curves_slabs(c->N);
+  a.start = spec.start, a.end = spec.end, a.first_only = spec.first_only;
+  // power tables, then the slab's packed row: [4][G] 64-bit words, then the edges (41 KB at 512 gaps)
+  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)abd_risk_packed_cols(c->G) * sizeof(unsigned long long) +
+                     (size_t)2 * ABD_RISK_MAX_EDGES * sizeof(double);
+  const int blocks = std::max(1, std::min(a.n_slabs, c->n_cu * 8));  // (a slab's row does not depend on who computes it)
+  if (c->nt > ABD_MAXT)
+    hipLaunchKernelGGL(abd_risk_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  else
+    hipLaunchKernelGGL(abd_risk_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  const int sum_blocks = (int)((abd_risk_packed_cols(c->G) + ABD_RISK_SUM_COLS - 1) / ABD_RISK_SUM_COLS);
+  hipLaunchKernelGGL(abd_risk_sum_kernel, dim3(sum_blocks), dim3(ABD_RISK_SUM_PARTS * ABD_RISK_SUM_COLS), 0, st, scratch, a.n_slabs, c->G,
+                     table);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st) {
   dim3 grid((c->N + 255) / 256, c->G);
   hipLaunchKernelGGL(abd_unpack_bits_kernel, grid, dim3(256), 0, st, c->slots[(size_t)chain].rw, dst, c->G, c->N);
@@ -791,6 +845,24 @@ int abd_curves(abd_ctx* c, int32_t chain, const double* theta, double thr_s, dou
   HIP_TRY(hipMemcpyAsync(h.data(), c->d_curves + n_scratch, n_row * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   split_curves_row(c, h.data(), counts, n_infections, titer_sums);
+  return ABD_OK;
+}
+
+int abd_risk(abd_ctx* c, int32_t chain, const double* theta, const abd_risk_spec* spec, int64_t* table) {
+  if (!c || !theta || !table) return fail(ABD_ERR_ARG, "NULL argument");
+  int rc = check_chains(c, 1, &chain);
+  if (rc) return rc;
+  if (int src = check_risk_spec(c, spec)) return src;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int jrc = join_pipes(c)) return jrc;
+  const size_t n_scratch = risk_scratch_cols(c), n_tab = risk_table_cols(c);
+  if (!c->d_risk) HIP_TRY(c->d_risk.alloc(n_scratch + (n_tab + 1) / 2));  // kept for the next call
+  uint32_t* d_tab = reinterpret_cast<uint32_t*>(c->d_risk + n_scratch);
+  if (int lrc = launch_risk(c, chain, theta, *spec, c->stream, c->d_risk, d_tab)) return lrc;
+  std::vector<uint32_t> h(n_tab);
+  HIP_TRY(hipMemcpyAsync(h.data(), d_tab, n_tab * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t e = 0; e < n_tab; ++e) table[e] = (int64_t)h[e];
   return ABD_OK;
 }
 

@@ -235,6 +235,7 @@ struct abd_ctx {
   DevBuf<double> d_det;                    // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
   DevBuf<int32_t> d_last;                  // [N] end of follow-up (abd_set_follow_up); empty: G - 1 for everyone
   DevBuf<unsigned long long> d_curves;     // abd_curves: the slab rows (curves_scratch_cols), then the call's row
+  DevBuf<unsigned long long> d_risk;       // abd_risk: the packed slab rows (risk_scratch_cols), then the call's table (32-bit counts)
   std::vector<ResultSlot> results;
   // timing: 1 = HIP events around every evaluation-kernel launch, launches serialised on one stream with the full
   // grid (the isolated kernel); 2 = HIP events around every WINDOW of stream-ordered launches (first launch after an
@@ -278,6 +279,15 @@ size_t curves_row_cols(const abd_ctx* c);
 size_t curves_scratch_cols(const abd_ctx* c);
 // a row as the C ABI hands it out: counts [4][G], n_infections [8], titer_sums [2][G]; nullptr skips
 void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* counts, int64_t* n_infections, double* titer_sums);
+// abd_risk_spec as the ABI defines a good one (window, edges, first_only): ABD_OK or fail(ABD_ERR_ARG, ...)
+int check_risk_spec(const abd_ctx* c, const abd_risk_spec* spec);
+// Risk table of chain `chain` at theta on stream st (abd_risk.hpp): packed slab rows into `scratch` (risk_scratch_cols(c)
+// 64-bit words, the launch's own until it has run), the table of risk_table_cols(c) 32-bit counts into `table`.  The spec has
+// passed check_risk_spec.  Touches no member of the context but d_last: the sampler's host threads call it side by side.
+int launch_risk(abd_ctx* c, int chain, const double* theta, const abd_risk_spec& spec, hipStream_t st, unsigned long long* scratch,
+                uint32_t* table);
+size_t risk_table_cols(const abd_ctx* c);
+size_t risk_scratch_cols(const abd_ctx* c);
 // Draw d (= iteration - tune, in [0, 2 H)) of chain `chain` at theta into its convergence accumulators on stream st
 // (abd_diag.hpp; H the half length, L the batch length): tit [2][7][G*N], inf [G*N][4] and cb2 [G*N] are the chain's own
 // planes.  Touches no member of the context.

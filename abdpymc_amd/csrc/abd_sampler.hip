@@ -75,6 +75,12 @@ struct abd_sampler {
   DevBuf<unsigned long long> d_curves, d_curves_scratch;
   int64_t curves_capacity = 0;
   double curves_thr_s = 0.0, curves_thr_n = 0.0;
+  // risk table of every draw (abd_risk.hpp): [n][risk_capacity] tables of 32 G 32-bit counts, and every chain's own packed slab
+  // rows [n][risk_scratch_cols]
+  DevBuf<uint32_t> d_risk;
+  DevBuf<unsigned long long> d_risk_scratch;
+  int64_t risk_capacity = 0;
+  abd_risk_spec risk_spec = {};
   // convergence accumulators over all draws (abd_diag.hpp), individual-major planes per chain: [n][2][7][G*N] of the two
   // titers, [n][G*N][4] and [n][G*N] of i, and one plane [G*N] of staging for the read-out
   DevBuf<double> d_diag_tit;
@@ -521,6 +527,11 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   if (draw && s->d_diag_tit && iter - s->o.tune < 2 * s->diag_H)
     if (int rc = launch_diag(c, chain, q, st, iter - s->o.tune, s->diag_H, s->diag_L, s->d_diag_tit + (size_t)j * 2 * 7 * cells,
                              s->d_diag_inf + (size_t)j * 4 * cells, s->d_diag_cb2 + (size_t)j * cells))
+      return rc;
+  // risk table: every draw's, as the curves
+  if (draw && s->d_risk)
+    if (int rc = launch_risk(c, chain, q, s->risk_spec, st, s->d_risk_scratch + (size_t)j * risk_scratch_cols(c),
+                             s->d_risk + ((size_t)j * s->risk_capacity + (size_t)(iter - s->o.tune)) * risk_table_cols(c)))
       return rc;
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
@@ -1050,6 +1061,9 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (s->d_diag_tit && s->it + n_iter - s->o.tune > s->diag_draws)
     return fail(ABD_ERR_STATE, "diagnostics: draws up to %lld pass the planned %lld", (long long)(s->it + n_iter - s->o.tune),
                 (long long)s->diag_draws);
+  if (s->d_risk && s->it + n_iter - s->o.tune > s->risk_capacity)
+    return fail(ABD_ERR_STATE, "risk: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
+                (long long)s->risk_capacity);
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
@@ -1273,6 +1287,56 @@ int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double
     for (int v = 0; v < 6; ++v)
       if (int rc = plane(tit + (size_t)planes[v] * cells, 8, 8, outs[x] + (size_t)v * cells)) return rc;
   }
+  return ABD_OK;
+}
+
+int abd_sampler_enable_risk(abd_sampler* s, int64_t capacity, const abd_risk_spec* spec) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
+  if (s->ran) return fail(ABD_ERR_STATE, "risk must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  if (capacity > 0)
+    if (int rc = check_risk_spec(c, spec)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  s->d_risk.reset();  // (nothing has been launched on them: the sampler has not run)
+  s->d_risk_scratch.reset();
+  s->risk_capacity = 0;
+  if (capacity == 0) return ABD_OK;
+  const size_t n_counts = (size_t)s->n * (size_t)capacity * risk_table_cols(c);
+  DevBuf<uint32_t> rows;
+  DevBuf<unsigned long long> scratch;  // (the sampler takes both or neither)
+  hipError_t e = rows.alloc(n_counts);
+  if (e == hipSuccess) e = scratch.alloc((size_t)s->n * risk_scratch_cols(c));
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "risk: %zu bytes of device memory", n_counts * sizeof(uint32_t));
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "risk: %s", hipGetErrorString(e));
+  s->d_risk = std::move(rows);
+  s->d_risk_scratch = std::move(scratch);
+  s->risk_capacity = capacity;
+  s->risk_spec = *spec;
+  return ABD_OK;
+}
+
+int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* table, int64_t* n_draws) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_risk) return fail(ABD_ERR_STATE, "risk is not enabled (abd_sampler_enable_risk)");
+  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
+  if (n_draws) *n_draws = have;
+  if (first < 0 || count < 0 || first > have || count > have - first)
+    return fail(ABD_ERR_ARG, "risk: draws [%lld, %lld) are beyond the %lld the chain has", (long long)first, (long long)(first + count),
+                (long long)have);
+  if (count == 0 || !table) return ABD_OK;
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
+  const size_t n_tab = risk_table_cols(c);
+  std::vector<uint32_t> h((size_t)count * n_tab);
+  HIP_TRY(hipMemcpy(h.data(), s->d_risk + ((size_t)k * s->risk_capacity + (size_t)first) * n_tab, h.size() * sizeof(uint32_t),
+                    hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < h.size(); ++e) table[e] = (int64_t)h[e];
   return ABD_OK;
 }
 

@@ -301,7 +301,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
                   budget_bytes: Optional[int] = None, log_likelihood: bool = False,
                   waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-                  sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None) -> Dict[str, np.ndarray]:
+                  sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None,
+                  risk=None) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -342,9 +343,16 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     ``diag_ab_n_mu`` / ``diag_ab_s_mu`` (chains, 6, G, N) and ``diag_info`` (chains, 4); ``diagnostics.rhat`` / ``ess`` / ``summary``
     read them.  ``diag_batch`` is the batch length (default ``max(1, floor(sqrt(draws // 2)))``).  Needs ``draws >= 2``; the
     arrays' host bytes count against ``budget_bytes``.  The trajectories do not change either.
+
+    ``risk`` = a ``risk.spec``: keep the infection-risk-by-titer table of EVERY draw, reduced over the individuals on the device
+    (``risk.py``; ``thin`` does not apply): ``risk_table`` (chains, draws, 2, 2, G, 8) int64 -- antigen (S, N) x (at risk, events)
+    x gap x bin of the previous gap's titer -- and the spec, one row per chain: ``risk_edges_s`` / ``risk_edges_n`` (chains, 7),
+    NaN beyond the edges given, and ``risk_window`` (chains, 3) = (start, end, first_only); ``risk.summary`` reads them.  The
+    follow-up is the curves'.  The table's host bytes count against ``budget_bytes``.  The trajectories do not change either.
     """
     from . import curves as curves_mod
     from . import diagnostics as diag_mod
+    from . import risk as risk_mod
     from .model import THETA_NAMES, constrain
 
     ctx = model.ctx
@@ -385,6 +393,19 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                 f"per cell and chain) and the recorded draws {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
                 f"{budget / 2 ** 30:.2f} GiB: record fewer draws (thin, no_deterministics / record_discrete=False) or raise "
                 f"ABD_RECORD_BUDGET_GB")
+    if risk is not None:
+        risk = risk_mod.spec(risk["start"], risk["end"], risk["edges_s"], risk["edges_n"], risk["first_only"], n_gaps=G)
+        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
+        own = chains * draws * 4 * G * risk_mod.N_BINS * 8
+        need = own + (diag_mod.result_bytes(chains, G, N) if diagnostics else 0) + record_bytes(
+            chains, n_rec, G, N, record_deterministics, record_discrete, n_readings=(K_s + K_n) if log_likelihood else 0,
+            n_replicates=(K_s + K_n) if posterior_predictive else 0)
+        if need > budget:
+            raise ValueError(
+                f"the risk tables of {chains} chains x {draws} draws x {G} gaps take {own / 2 ** 30:.2f} GiB of host arrays (32 counts "
+                f"of 8 bytes per gap and draw) and the other recorded arrays {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
+                f"{budget / 2 ** 30:.2f} GiB: fewer draws, record less (thin, no_deterministics / record_discrete=False) or raise "
+                f"ABD_RECORD_BUDGET_GB")
     chunk = max(thin, chunk - chunk % thin) if thin > 1 else chunk  # calls record iterations 0, thin, ... of THEIR range
     pt = model.initial_point()
     q0 = np.empty((chains, len(THETA_NAMES)))
@@ -395,8 +416,9 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
                       dense_metric=dense_metric, pointwise=waic, predictive=ppc, curves=draws if curves else 0,
-                      sero_thresholds=sero_thresholds, diagnostics=(draws, diag_batch) if diagnostics else None)
-    if curves:
+                      sero_thresholds=sero_thresholds, diagnostics=(draws, diag_batch) if diagnostics else None,
+                      risk=draws if risk is not None else 0, risk_spec=risk)
+    if curves or risk is not None:
         last_gap = getattr(getattr(model, "data", None), "last_gap", None)
         ctx.set_follow_up(last_gap)
     n_grad = chains  # the evaluation at the starting points
@@ -466,6 +488,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         per_chain = [smp.curves(c) for c in range(chains)]
         res.update(curves_mod.as_result(*(np.stack([pc[k] for pc in per_chain]) for k in ("counts", "n_infections", "titer_sums")),
                                         curves_mod.n_followed(np.full(N, G - 1) if last_gap is None else last_gap, G)))
+    if risk is not None:
+        res.update(risk_mod.as_result(np.stack([smp.risk(c) for c in range(chains)]), risk))
     if diagnostics:
         per_chain = [smp.diagnostics(c) for c in range(chains)]
         for key, name in (("i_counts", "diag_i_counts"), ("ab_n_mu", "diag_ab_n_mu"), ("ab_s_mu", "diag_ab_s_mu"), ("info", "diag_info")):
@@ -490,7 +514,7 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
            waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None) -> Dict[str, np.ndarray]:
+           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None, risk=None) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
@@ -499,7 +523,10 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
                              log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc,
-                             curves=curves, sero_thresholds=sero_thresholds, diagnostics=diagnostics, diag_batch=diag_batch)
+                             curves=curves, sero_thresholds=sero_thresholds, diagnostics=diagnostics, diag_batch=diag_batch,
+                             risk=risk)
+    if risk is not None:
+        raise ValueError("risk needs the native sampler (sample(native=True)): every draw is reduced on the device inside it")
     if diagnostics:
         raise ValueError("diagnostics need the native sampler (sample(native=True)): the moments of every draw are accumulated inside it")
     if curves:

@@ -177,6 +177,25 @@ int abd_curves(abd_ctx* ctx, int32_t chain, const double* theta, double thr_s, d
  * the state after abd_create.  Affects the curves only. */
 int abd_set_follow_up(abd_ctx* ctx, const int32_t* last_gap);
 
+/* Infection risk by titer of one draw: the person-time table of "infection in gap g given the titer of gap g - 1" of the
+ * Deterministics of chain slot `chain` at theta, reduced over the individuals on the device.  The window is (start, end) with
+ * 0 <= start, end <= G, end - start >= 2; edges_s[0 .. n_edges_s) and edges_n[0 .. n_edges_n) are finite, strictly ascending
+ * bin edges on the titer scale (0 <= n_edges <= 7; the entries beyond n_edges are not read); first_only is 0 or 1.
+ * Anything else is ABD_ERR_ARG.  Cell (g, j) is AT RISK iff start < g < end, g <= last_gap[j] (abd_set_follow_up) and,
+ * when first_only, i[g', j] = 0 for every start < g' < g: at most one infection per individual inside the window.  It is an
+ * EVENT iff it is at risk and i[g, j] = 1.
+ *   table [2][2][G][8]   antigen (0 S, 1 N) x (0 at risk, 1 events) x gap x bin
+ * A cell is counted in the bin #{e in edges: x >= e} of the titer of the PREVIOUS gap, x = ab_s_mu[g-1, j] for S and
+ * ab_n_mu[g-1, j] for N, exactly what abd_deterministics returns; bins above n_edges stay empty, gaps outside the window are
+ * zero.  The table depends on (N, G, last_gap, the slot's state, theta, the spec) only: integer sums, no atomics
+ * (abdpymc_amd/csrc/abd_risk.hpp).  Non-finite theta: every comparison fails, so every cell at risk lands in bin 0; the
+ * totals over the bins do not change and the status is 0. */
+typedef struct abd_risk_spec {
+  int32_t start, end, first_only, n_edges_s, n_edges_n;
+  double edges_s[7], edges_n[7];
+} abd_risk_spec;
+int abd_risk(abd_ctx* ctx, int32_t chain, const double* theta, const abd_risk_spec* spec, int64_t* table);
+
 /* Pointwise log-likelihood of the two observed Normals "it_s_lik", "it_n_lik" (abd.py:459-469) at theta and chain slot
  * `chain`'s discrete state: ll_s receives s.n_obs doubles, ll_n n.n_obs, in the order the readings were given to abd_create
  * (what pm.compute_log_likelihood records for one draw).  Either pointer may be NULL.  sum(ll_s) + sum(ll_n) is
@@ -372,6 +391,18 @@ int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, do
  * number of draws the chain has.  ABD_ERR_ARG for a range beyond it.  May be called between run calls. */
 int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections,
                        double* titer_sums, int64_t* n_draws);
+/* The risk table (abd_risk) of every draw (iteration >= tune) of every chain, kept on the device: 64 G counts of 32 bits
+ * per draw (a count is at most N < 2^31), whatever abd_record and its thin ask for.  Allowed before the first abd_sampler_run*
+ * call (ABD_ERR_STATE after it); capacity > 0 allocates rows for that many draws per chain (ABD_ERR_NOMEM, the message naming
+ * the bytes, if they do not fit), 0 releases them; ABD_ERR_ARG for a spec abd_risk refuses.  While it is enabled an
+ * abd_sampler_run* call whose draws would pass capacity fails with ABD_ERR_STATE before anything is launched.  The follow-up
+ * is the context's (abd_set_follow_up) at the time of each draw.  No random numbers are drawn: the chains' trajectories do
+ * not change. */
+int abd_sampler_enable_risk(abd_sampler* s, int64_t capacity, const abd_risk_spec* spec);
+/* Draws first .. first + count - 1 of chain k (0 <= k < n; draw 0 is iteration `tune`): table [count][2][2][G][8] as abd_risk
+ * lays it out; may be NULL.  *n_draws (may be NULL) receives the number of draws the chain has.  ABD_ERR_ARG for a range
+ * beyond it, ABD_ERR_STATE when the table is not enabled.  May be called between run calls. */
+int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* table, int64_t* n_draws);
 
 /* Per-cell convergence accumulators over ALL draws: what split R-hat and a batch-means effective sample size of the
  * Deterministics "i", "ab_n_mu", "ab_s_mu" need, kept on the device because a run at full size never keeps its draws

@@ -3,12 +3,15 @@ Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals 
 4-chain compound sampler run with and without on-device WAIC accumulation (``--leg waic``: sample(..., waic=True)) or posterior
 predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the epidemic curves of every draw (``--leg curves``:
 sample(..., curves=True); not a per-reading output, but the same question) or the per-cell convergence accumulators
-(``--leg diagnostics``: sample(..., diagnostics=True); likewise), alternated.  With two run lengths (``--draws 100 400``) the
+(``--leg diagnostics``: sample(..., diagnostics=True); likewise) or the infection-risk-by-titer table of every draw (``--leg
+risk``: sample(..., risk=spec) with 7 edges per antigen, the whole window, first infections only; likewise), alternated.  With two run lengths (``--draws 100 400``) the
 fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both on, for
 ``rocprofv3 --kernel-trace --stats -- python tools/probe_readings.py --profile``: the kernel's own time per draw and chain of
 each op (abd_readings_dense_kernel<LogLik, ...>, <Predictive, ...>) in the same run; with ``--leg curves`` the short sample has
 the curves on instead (abd_curves_kernel, abd_curves_sum_kernel beside abd_deterministics_kernel with its running sums), with
-``--leg diagnostics`` the accumulators (abd_diag_kernel beside the same).  Prints one JSON line.
+``--leg diagnostics`` the accumulators (abd_diag_kernel beside the same), with ``--leg risk`` the risk table AND the curves
+(abd_risk_kernel, abd_risk_sum_kernel beside abd_curves_kernel, abd_curves_sum_kernel: the two walk the same words).  Prints
+one JSON line.
 """
 import argparse
 import json
@@ -21,14 +24,14 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from abdpymc_amd import synthetic  # noqa: E402
+from abdpymc_amd import risk, synthetic  # noqa: E402
 from abdpymc_amd.model import AbdModel  # noqa: E402
 from abdpymc_amd.sampler import sample  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics"), default="waic")
+    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics", "risk"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
@@ -43,22 +46,29 @@ def main():
                         s=SimpleNamespace(obs=sc.s_obs), n=SimpleNamespace(obs=sc.n_obs))
     m = AbdModel(d, n_chains=a.chains)
     kw = dict(tune=a.tune, chains=a.chains, seed=1, record_deterministics=False, record_discrete=False)
+    spec = risk.spec(0, a.gaps, 0.5 * np.arange(1, 8), 0.5 * np.arange(1, 8), 1)
+
+    def leg_kw(on):  # the option of this leg, switched on or off
+        return dict(risk=spec if on else None) if a.leg == "risk" else {a.leg: on}
+
     if a.profile:
         t0 = time.perf_counter()
         on = {a.leg: True} if a.leg in ("curves", "diagnostics") else dict(waic=True, ppc=True)
-        sample(m, draws=a.draws[0], **on, **kw)
-        print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on,
+        if a.leg == "risk":
+            on = dict(curves=True)
+        sample(m, draws=a.draws[0], **on, **(leg_kw(True) if a.leg == "risk" else {}), **kw)
+        print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on, risk=a.leg == "risk",
                               wall_s=time.perf_counter() - t0)))
         m.close()
         return
-    sample(m, **dict(kw, tune=5), draws=5, **{a.leg: True})  # warm-up: code objects, allocations
+    sample(m, **dict(kw, tune=5), draws=5, **leg_kw(True))  # warm-up: code objects, allocations
     legs = ("plain", a.leg)
     t = {f"{leg}_{n}": [] for n in a.draws for leg in legs}
     for _ in range(a.reps):  # alternated, so that drift hits both legs alike
         for n in a.draws:
             for leg in legs:
                 t0 = time.perf_counter()
-                sample(m, draws=n, **{a.leg: leg != "plain"}, **kw)
+                sample(m, draws=n, **leg_kw(leg != "plain"), **kw)
                 t[f"{leg}_{n}"].append(time.perf_counter() - t0)
     best = {k: min(v) for k, v in t.items()}
     out = dict(leg=a.leg, inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws, wall_s=t,
