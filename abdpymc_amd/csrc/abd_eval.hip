@@ -1,6 +1,7 @@
 // abd_eval.hip -- evaluation launches of the C ABI (include/abd_hip.h): the dense-panel and observation-list kernels,
 // the pipes (HIP streams) stream-ordered launches rotate over, completion tags in mapped host memory, device timing.
 #include "abd_host.hpp"
+#include "abd_fuse_plan.hpp"
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
 #include "abd_readings.hpp"
@@ -53,16 +54,21 @@ int pick_cpw(const abd_ctx* c, int n) {
 // gap rows), capped so a slot has at least kMinRows rows
 // share: 0 = the launch has the chip to itself, 1 = it is one of n_pipes stream-ordered launches in flight,
 // 2 = it is a native-sampler unit's, one of several in flight (c->group_blocks: one workgroup per CU)
-int dense_blocks(const abd_ctx* c, int cpw, int share, int grid_rows) {
+// steps: consecutive steps the launch carries (abd_fuse_plan.hpp), grid_rows / steps rows each: a launch that shares the chip
+// has 1 / steps of the ranges per row, so that a pipe's launch is as many workgroups as that of a single step
+int dense_blocks(const abd_ctx* c, int cpw, int share, int grid_rows, int steps) {
   const int nsub = ABD_WAVES_PER_BLOCK / cpw;
   const int64_t rows = (int64_t)c->n_lg * c->G;
   const int64_t cap = std::max<int64_t>(1, rows / ((int64_t)kMinRows * nsub));
   // a launch with several grid rows (more than 4 chains) fills the chip with fewer, longer ranges per row
   const int64_t alone = std::max<int64_t>(c->n_cu, c->dense_blocks / std::max(1, grid_rows));
   const int64_t half = std::max<int64_t>(c->n_cu, c->group_blocks / std::max(1, grid_rows));
-  const int64_t want = share == 1 ? (int64_t)c->pipe_blocks : (share == 2 ? half : alone);
+  const int64_t want = share == 1 ? std::max<int64_t>(1, c->pipe_blocks / std::max(1, steps)) : (share == 2 ? half : alone);
   return (int)std::max<int64_t>(1, std::min<int64_t>({want, cap, (int64_t)c->blocks_max}));
 }
+
+// do the partial rows of a launch of n_rows chains (rows of several steps: abd_fuse_plan.hpp) x `blocks` workgroups fit a pipe's buffer?
+bool partial_rows_fit(const abd_ctx* c, int n_rows, int64_t blocks) { return (int64_t)n_rows * blocks <= (int64_t)c->n_slots * c->blocks_max; }
 
 // The ranges of a dense launch of `blocks` workgroups x `nsub` ranges each: equal shares (+-1) of the n_lg x G rows; with
 // one range per workgroup (nsub == 1) the first ABD_MAX_BATCH ranges -- the workgroups that may carry the fused
@@ -134,7 +140,7 @@ enum class Sum {
 struct LaunchPlan {
   Family family;
   int cpw;      // chains per workgroup
-  dim3 grid;    // (workgroups, n / cpw)
+  dim3 grid;    // (workgroups, steps * n / cpw)
   size_t lds;
   int pipe;
   bool rotate;  // the pipe is the next one of the stream-ordered rotation
@@ -142,7 +148,9 @@ struct LaunchPlan {
   Sum sum;
 };
 
-LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n) {
+// n: chains of one step; steps: consecutive steps of those chains in the launch (1 unless abd_logp_dlogp_many fuses).  cpw,
+// and with it the kernel's form, is that of a single step.
+LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n, int steps) {
   LaunchPlan p;
   p.family = c->dense ? Family::Dense : (c->obs_lanes ? Family::Lanes : Family::Sparse);
   p.cpw = p.family == Family::Lanes ? 1 : pick_cpw(c, n);
@@ -158,7 +166,7 @@ LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n) {
     // the last launch of a batch of stream-ordered steps ends alone on the chip: it gets the grid of a launch that has the
     // chip to itself (one wave per SIMD issues at half the rate; a K = 20 region 376 -> 373 us; a longer tail did not pay)
     const int share = who.kind == Caller::Unit ? 2 : (p.rotate && c->steps_behind != 0 ? 1 : 0);
-    blocks = dense_blocks(c, p.cpw, share, n / p.cpw);
+    blocks = dense_blocks(c, p.cpw, share, steps * n / p.cpw, steps);
     p.lds = abd_dense_lds(c->G, p.cpw, dense_xc(c, p.cpw));
   } else if (p.family == Family::Lanes) {
     blocks = c->ob_n + c->ob_s + c->ob_c;
@@ -167,7 +175,7 @@ LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n) {
     blocks = c->blocks_x;
     p.lds = table_lds_bytes(c->G, p.cpw, ABD_WAVES_PER_BLOCK * p.cpw);
   }
-  p.grid = dim3(blocks, n / p.cpw);
+  p.grid = dim3(blocks, steps * n / p.cpw);
   // Who sums the partial rows:
   //   caller   dense cohort                                        observation lists
   //   Stream   Pending                                             FinalizeNow
@@ -188,8 +196,13 @@ LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n) {
   return p;
 }
 
-int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows) {
-  const LaunchPlan p = plan_launch(c, who, n);
+int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows, int steps) {
+  const LaunchPlan p = plan_launch(c, who, n, steps);
+  const int n_rows = n * steps;  // chains of the launch as the kernel sees them: step s, chain j is row s * n + j
+  if (steps < 1 || n_rows > ABD_MAX_BATCH || (steps > 1 && (p.family != Family::Dense || p.sum != Sum::Pending)))
+    return fail(ABD_ERR_STATE, "internal: a launch of %d steps x %d chains", steps, n);
+  if (steps > 1 && !partial_rows_fit(c, n_rows, p.grid.x))
+    return fail(ABD_ERR_STATE, "internal: a launch of %d rows x %d workgroups exceeds the partial rows", n_rows, (int)p.grid.x);
   if (who.kind == Caller::Train && (n != 1 || p.family != Family::Lanes))
     return fail(ABD_ERR_STATE, "internal: a leapfrog-train launch needs one chain and the observation-lane kernel");
   if ((int)p.grid.x > c->blocks_max) return fail(ABD_ERR_STATE, "internal: grid %d exceeds partial rows %d", (int)p.grid.x, c->blocks_max);
@@ -198,8 +211,8 @@ int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, c
   double& seq = who.seq ? *who.seq : c->seq;
   EvalArgs a;
   base_args(c, a);
-  a.n_chains = n;
-  for (int k = 0; k < n; ++k) a.ch[k] = chain_par(c, chains[k], host[k].tr);
+  a.n_chains = n_rows;
+  for (int k = 0; k < n_rows; ++k) a.ch[k] = chain_par(c, chains[k % n], host[k].tr);
   if (p.family == Family::Dense) range_split(c, (int)p.grid.x, ABD_WAVES_PER_BLOCK / p.cpw, a);
   a.fin_rows = c->fin_rows;
   a.xcd_remap = c->xcd_remap ? 1 : 0;
@@ -248,7 +261,7 @@ int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, c
     if (c->timing == 1) e1 = c->ev_pool[c->ev_used++].second;
     if (c->timing == 2) c->win_open = true;
   }
-  if (c->timing == 2 && stream_ordered) c->win_launches++;
+  if (c->timing == 2 && stream_ordered) c->win_launches += steps;  // (abd_kernel_time counts steps)
   const bool f32 = c->storage == ABD_STORE_F32, xc = p.family == Family::Dense && dense_xc(c, p.cpw), wide = c->nt > ABD_MAXT;
   const EvalKernel k = f32 ? (grad ? eval_kernel<float, true>(p.family, p.cpw, xc, wide) : eval_kernel<float, false>(p.family, p.cpw, xc, wide))
                            : (grad ? eval_kernel<double, true>(p.family, p.cpw, xc, wide) : eval_kernel<double, false>(p.family, p.cpw, xc, wide));
@@ -259,7 +272,7 @@ int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, c
   if (p.sum == Sum::Own) return ABD_OK;
   pp.on = true;
   pp.buf = buf;
-  pp.n = n;
+  pp.n = n_rows;
   pp.blocks = (int)p.grid.x;
   pp.out = rows;
   pp.tag = seq;
@@ -323,7 +336,7 @@ int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st) {
 // Polls; after a second hands over to a synchronise of the context's stream (which every pipe has joined by then).
 int wait_slot(abd_ctx* c, int slot) {
   const ResultSlot& r = c->results[slot];
-  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
+  volatile const double* rows = c->out.host() + r.row0 * ABD_NOUT;
   const auto t_poll = std::chrono::steady_clock::now();
   int k = r.n - 1;
   for (long spin = 0;; ++spin) {
@@ -352,18 +365,46 @@ int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* 
   ResultSlot& r = c->results[slot];
   r.n = n;
   r.grad = grad;
+  r.row0 = (size_t)slot * c->n_slots;
   r.chains.assign(chains, chains + n);
   r.theta.assign(theta, theta + (size_t)n * ABD_N_THETA);
   r.host.resize((size_t)n);
   for (int k = 0; k < n; ++k) r.host[(size_t)k] = prepare(theta + (size_t)k * ABD_N_THETA);
   // every result row lives in mapped host memory (one PCIe write of 16 doubles + tag per chain, ~3 us inside the kernel)
-  double* rows = c->out.dev() + (size_t)slot * c->n_slots * ABD_NOUT;
+  double* rows = c->out.dev() + r.row0 * ABD_NOUT;
   r.tag_first = (who.seq ? *who.seq : c->seq) + 1.0;
   if (who.kind == Caller::Stream) c->pending_slots.push_back(slot);
   for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
     if ((rc = enqueue_group(c, who, std::min(ABD_MAX_BATCH, n - k0), chains + k0, r.host.data() + k0, grad, rows + (size_t)k0 * ABD_NOUT)))
       return rc;
   return ABD_OK;
+}
+
+// Queue `steps` consecutive steps of the same n chains (theta: steps x n x 17) as ONE dense stream-ordered launch into result
+// slots slot0 .. slot0 + steps - 1.  The launch's rows are one block, step s at rows [s n, (s + 1) n) of it, and the block
+// starts where slot0's rows do: n <= n_chain_slots, so it ends inside the rows of the slots it fills.  All rows carry the
+// launch's completion tag.
+int enqueue_fused(abd_ctx* c, int slot0, int steps, int n, const int32_t* chains, const double* theta, bool grad) {
+  if (slot0 < 0 || steps < 1 || slot0 + steps > kResultSlots || n > c->n_slots || n * steps > ABD_MAX_BATCH)
+    return fail(ABD_ERR_STATE, "internal: %d fused steps of %d chains at result slot %d", steps, n, slot0);
+  if (int rc = check_chains(c, n, chains)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t row0 = (size_t)slot0 * c->n_slots;
+  HostTerms host[ABD_MAX_BATCH];
+  for (int s = 0; s < steps; ++s) {
+    ResultSlot& r = c->results[slot0 + s];
+    const double* th = theta + (size_t)s * n * ABD_N_THETA;
+    r.n = n;
+    r.grad = grad;
+    r.row0 = row0 + (size_t)s * n;
+    r.chains.assign(chains, chains + n);
+    r.theta.assign(th, th + (size_t)n * ABD_N_THETA);
+    r.host.resize((size_t)n);
+    for (int k = 0; k < n; ++k) host[s * n + k] = r.host[(size_t)k] = prepare(th + (size_t)k * ABD_N_THETA);
+    r.tag_first = c->seq + 1.0;
+    c->pending_slots.push_back(slot0 + s);
+  }
+  return enqueue_group(c, Caller{Caller::Stream}, n, chains, host, grad, c->out.dev() + row0 * ABD_NOUT, steps);
 }
 
 // ---- leapfrog-train launches of dense cohorts (abd_train.hpp; abd_sampler.hip) ----
@@ -445,7 +486,7 @@ int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_prior
   if (slot < 0 || slot >= kSyncSlot + c->n_sync_slots) return fail(ABD_ERR_ARG, "result slot %d outside [0, %d)", slot, kResultSlots);
   const ResultSlot& r = c->results[slot];
   if (r.n == 0) return fail(ABD_ERR_STATE, "result slot %d is empty", slot);
-  const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
+  const double* rows = c->out.host() + r.row0 * ABD_NOUT;
   for (int k = 0; k < r.n; ++k)
     assemble(c, r.host[(size_t)k], r.theta.data() + (size_t)k * ABD_N_THETA, rows + (size_t)k * ABD_NOUT, logp + k,
              (grad && r.grad) ? grad + (size_t)k * ABD_N_THETA : nullptr, with_priors);
@@ -749,11 +790,28 @@ int abd_logp_dlogp_many(abd_ctx* c, int32_t n_steps, int32_t n, const int32_t* c
   if (!c || !chains || !theta || !logp) return fail(ABD_ERR_ARG, "NULL argument");
   if (n_steps < 0) return fail(ABD_ERR_ARG, "n_steps=%d is negative", n_steps);
   const size_t per_step = (size_t)n * ABD_N_THETA;
+  // Dense cohorts: consecutive steps share launches (abd_fuse_plan.hpp) where the launch's rows fit the partial and the result
+  // rows; not under timing 1 (the isolated kernel, one single-step launch at a time)
+  int max_steps = 1;
+  if (c->dense && c->timing != 1 && n >= 1 && n <= c->n_slots && n <= ABD_MAX_BATCH) {
+    const int cpw = pick_cpw(c, n);
+    for (max_steps = std::min(kFuseMaxSteps, ABD_MAX_BATCH / n); max_steps > 1; --max_steps) {
+      const int rows = max_steps * n / cpw;
+      const int64_t widest = std::max(dense_blocks(c, cpw, 0, rows, max_steps), dense_blocks(c, cpw, 1, rows, max_steps));
+      if (partial_rows_fit(c, max_steps * n, widest)) break;
+    }
+  }
+  const int pipes = c->n_pipes > 1 && c->timing != 1 ? c->n_pipes : 1;
+  const std::vector<FusedLaunch> plan = fuse_plan(n_steps, n, pipes, kResultSlots, tune_int("ABD_FUSE_STEPS", 0), max_steps, ABD_MAX_BATCH);
+  size_t next = 0;  // the plan's launches never cross a window
   for (int s0 = 0; s0 < n_steps; s0 += kResultSlots) {  // windows of the result ring
     const int s1 = std::min(n_steps, s0 + kResultSlots);
-    for (int k = s0; k < s1; ++k) {
-      c->steps_behind = n_steps - 1 - k;
-      const int rc = enqueue_slot(c, Caller{Caller::Stream}, k - s0, n, chains, theta + (size_t)k * per_step, grad != nullptr);
+    for (; next < plan.size() && plan[next].first < s1; ++next) {
+      const FusedLaunch& l = plan[next];
+      const int k = l.first;
+      c->steps_behind = l.alone ? 0 : n_steps - k - l.steps;  // 0: the call's last launch, shaped for an empty chip
+      const int rc = l.steps == 1 ? enqueue_slot(c, Caller{Caller::Stream}, k - s0, n, chains, theta + (size_t)k * per_step, grad != nullptr)
+                                  : enqueue_fused(c, k - s0, l.steps, n, chains, theta + (size_t)k * per_step, grad != nullptr);
       c->steps_behind = -1;
       if (rc) return rc;
     }
@@ -764,6 +822,10 @@ int abd_logp_dlogp_many(abd_ctx* c, int32_t n_steps, int32_t n, const int32_t* c
     for (int k = s0; k < s1; ++k) {
       if (int rc = wait_slot(c, k - s0)) return rc;
       if (int rc = fetch_slot(c, k - s0, logp + (size_t)k * n, grad ? grad + (size_t)k * per_step : nullptr)) return rc;
+      // a step that shared a launch has its rows inside the first step's block, where a later enqueue into that slot writes:
+      // it is taken here and leaves nothing behind for abd_fetch
+      ResultSlot& r = c->results[k - s0];
+      if (r.row0 != (size_t)(k - s0) * c->n_slots) r.n = 0;
     }
     c->pending_slots.clear();
   }

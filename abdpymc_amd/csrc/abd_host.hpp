@@ -146,6 +146,7 @@ struct ChainSlot {
 struct ResultSlot {
   int n = 0;
   bool grad = true;
+  size_t row0 = 0;  // the slot's first row in abd_ctx::out (slot * n_slots, or inside the block of a launch of several steps: enqueue_fused)
   std::vector<int32_t> chains;
   std::vector<double> theta;  // n x 17
   std::vector<HostTerms> host;  // n: the host-side terms of every theta, computed when the evaluation is queued
@@ -220,7 +221,7 @@ struct abd_ctx {
   uint32_t ind_offset = 0;  // global index of this context's first individual (Gibbs random streams)
   bool xcd_remap = true;
   int fin_rows = 2;
-  int steps_behind = -1;  // abd_logp_dlogp_many: steps still to be queued behind the one being queued (-1: unknown)
+  int steps_behind = -1;  // abd_logp_dlogp_many: steps still to be queued behind the launch being queued (-1: unknown)
   double prior_const = 0.0;
   MappedBuf<double> out;  // result rows, [kResultSlots + n_sync_slots][n_slots][ABD_NOUT]
   std::vector<int> pending_slots;  // slots queued stream-ordered since the last abd_wait
@@ -242,7 +243,7 @@ struct abd_ctx {
   // abd_wait .. all pipes joined at the next abd_wait): the launch shape a stream-ordered caller really runs
   int timing = 0;
   bool win_open = false;
-  int64_t win_launches = 0;  // launches inside the windows collected so far
+  int64_t win_launches = 0;  // steps (a launch may carry several: abd_fuse_plan.hpp) inside the windows collected so far
   size_t ev_used = 0;
   double ev_total_ms = 0.0;
   int64_t ev_count = 0;
@@ -309,11 +310,12 @@ int flush_ring(abd_ctx* c);
 int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st = nullptr);
 // queue the evaluation of n chains at theta into result slot `slot` (groups of <= ABD_MAX_BATCH chains, one launch each)
 int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* chains, const double* theta, bool grad);
-// one launch of n <= ABD_MAX_BATCH chains whose host terms are ready; its sums go to rows[0 .. n)
-int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows);
+// one launch of n chains at `steps` consecutive steps (n * steps <= ABD_MAX_BATCH; steps > 1: dense, stream-ordered) whose host
+// terms are ready, host[s * n + j] those of step s, chain j; its sums go to rows[0 .. n * steps) in the same order
+int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows, int steps = 1);
 int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_priors = true);
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a);
-int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1);
+int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1, int steps = 1);
 
 // Pointwise log-likelihood of chain `chain` at theta on stream st (abd_readings.hpp: LogLik): the row ll (sorted order, S
 // readings then N; nullptr skips) and / or the accumulators acc ([4][K_s + K_n]) updated by draw n_draw >= 1 (acc nullptr:

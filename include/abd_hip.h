@@ -147,7 +147,12 @@ int abd_fetch(abd_ctx* ctx, int32_t slot, double* logp, double* grad);
 int abd_fetch_many(abd_ctx* ctx, int32_t n_slots, const int32_t* slots, double* logp, double* grad);
 /* n_steps independent evaluations of the same chains in one call: theta is n_steps x n x 17, logp n_steps x n, grad
  * n_steps x n x 17 (NULL: logp only).  The stream-ordered form end to end -- enqueue every step, wait once, fetch --
- * for callers that hold many points at once (tempering, particle methods, a benchmark); result slots 0 .. are used. */
+ * for callers that hold many points at once (tempering, particle methods, a benchmark); result slots 0 .. are used.
+ * Dense cohorts: the call has every theta in hand, so a launch carries up to four consecutive steps (at most 16 rows of
+ * chains; how many depends on n_steps, n and the number of streams only), each step on a quarter of the ranges: the
+ * per-range work of the kernel is paid once for the four.  Repeatable bit for bit; against single enqueued steps the
+ * ranges differ, so the sums agree to rounding (~1e-15).  The call hands every result over itself and leaves none behind
+ * in the result slots: abd_fetch of a slot is for what abd_logp_dlogp_batch_enqueue put there. */
 int abd_logp_dlogp_many(abd_ctx* ctx, int32_t n_steps, int32_t n, const int32_t* chains, const double* theta,
                         double* logp, double* grad);
 
@@ -465,7 +470,8 @@ int abd_set_individual_offset(abd_ctx* ctx, int64_t first_individual);
  * bracket every WINDOW of stream-ordered launches (first abd_logp_dlogp_batch_enqueue after an abd_wait ..
  * every stream joined at the next abd_wait) -- device time per launch as a stream-ordered caller runs them.
  * mode 0: off.  abd_kernel_time returns the accumulated device time and launch count since the last reset
- * (synchronises). */
+ * (synchronises).  In mode 2 the count is in STEPS: a launch of abd_logp_dlogp_many that carries several steps counts
+ * as that many, so device time / count stays the device time per step of n chains whatever the launches are. */
 int abd_kernel_timing(abd_ctx* ctx, int32_t mode);
 /* Every waiting call (synchronous evaluations, abd_wait, abd_logp_dlogp_many, the native sampler) waits for its result
  * rows by polling a completion tag in mapped host memory; if a tag does not show in time (~2 M polls / 1 s) the call
