@@ -478,9 +478,15 @@ int upload_panels(abd_ctx* c, const abd_desc* d, SortedObs& so_s, SortedObs& so_
   HIP_TRY(c->vw.upload(vw.data(), words));
   HIP_TRY(c->pw.upload(pw.data(), words));
   if (c->dense) {
-    // 2^(j/1024) rounded once from the 64-bit-mantissa value
+    // 2^(j/1024) rounded once from the 64-bit-mantissa value, stored pre-biased (abd_types.hpp: abd_exp2_prebias)
     std::vector<double> tab(ABD_EXP2_TAB);
-    for (int j = 0; j < ABD_EXP2_TAB; ++j) tab[(size_t)j] = (double)exp2l((long double)j / (long double)ABD_EXP2_TAB);
+    for (int j = 0; j < ABD_EXP2_TAB; ++j) {
+      const double t = (double)exp2l((long double)j / (long double)ABD_EXP2_TAB);
+      uint64_t bits;
+      std::memcpy(&bits, &t, sizeof bits);
+      bits = abd_exp2_prebias(bits, j);
+      std::memcpy(&tab[(size_t)j], &bits, sizeof bits);
+    }
     HIP_TRY(c->exp2_tab.upload(tab.data(), tab.size()));
   }
   HIP_TRY(c->stage_gn.alloc((size_t)G * N));

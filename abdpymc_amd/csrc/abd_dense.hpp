@@ -27,7 +27,8 @@
 //   * indicator bits -> 0.0 / 1.0 doubles by v_bfe_i32 (scalar bit index) + v_and with the high word of 1.0;
 //     the "exposed so far" flags of perm_response (abd.py:306) are integer ORs of those high words
 //   * e^u = 2^(t/1024), t = 1024 e + j + f: T[j] = 2^(j/1024) from a 1024-entry LDS table, a cubic in f,
-//     the exponent e added into T's high word; 1 + 2^t is ONE fma (tools/exp2_table.py: 3.5e-16)
+//     the exponent e added into T's high word -- the table is pre-biased (abd_types.hpp), so that is hi + (k << 10) of the
+//     clamped k, with no shift to separate e; 1 + 2^t is ONE fma (tools/exp2_table.py: 3.5e-16)
 //   * one v_rcp_f64 per cell for both antigens (1/A = B/(AB))
 //   * gap rows are addressed as scalar row offset + a constant per-lane offset (no vector address arithmetic)
 #pragma once
@@ -155,17 +156,17 @@ __device__ __forceinline__ void one_plus_exp2_pair(double t_n, double t_s, const
   int k_n, k_s;
   asm("v_cvt_i32_f64 %0, %1" : "=v"(k_n) : "v"(kf_n));  // saturating; a C++ cast of an out-of-range double is undefined
   asm("v_cvt_i32_f64 %0, %1" : "=v"(k_s) : "v"(kf_s));
-  const double T_n = tab[k_n & (ABD_EXP2_TAB - 1)], T_s = tab[k_s & (ABD_EXP2_TAB - 1)];
+  const int kc_n = min(max(k_n, ABD_EXP2_K_MIN), ABD_EXP2_K_MAX), kc_s = min(max(k_s, ABD_EXP2_K_MIN), ABD_EXP2_K_MAX);  // v_med3_i32
+  const double T_n = tab[kc_n & (ABD_EXP2_TAB - 1)], T_s = tab[kc_s & (ABD_EXP2_TAB - 1)];  // pre-biased entries (abd_types.hpp)
   double p_n, p_s;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p_n) : "s"(0x1.c6b08d910ecbdp-35), "v"(f_n), "v"(c2v));  // tools/exp2_table.py 1024 3
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(p_s) : "s"(0x1.c6b08d910ecbdp-35), "v"(f_s), "v"(c2v));
-  const int e_n = min(max(k_n >> 10, -1022), 510), e_s = min(max(k_s >> 10, -1022), 510);  // v_med3_i32
   p_n = fma(p_n, f_n, 0x1.62e42fefa39efp-11);
   p_s = fma(p_s, f_s, 0x1.62e42fefa39efp-11);
   p_n = fma(p_n, f_n, 1.0);
   p_s = fma(p_s, f_s, 1.0);
-  const double Ts_n = __hiloint2double(__double2hiint(T_n) + (e_n << 20), __double2loint(T_n));  // T 2^e: v_lshl_add_u32
-  const double Ts_s = __hiloint2double(__double2hiint(T_s) + (e_s << 20), __double2loint(T_s));
+  const double Ts_n = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T_n), kc_n), __double2loint(T_n));  // T 2^e: v_lshl_add_u32
+  const double Ts_s = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T_s), kc_s), __double2loint(T_s));
   A = fma(Ts_n, p_n, 1.0);
   B = fma(Ts_s, p_s, 1.0);
 }

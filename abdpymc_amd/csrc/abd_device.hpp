@@ -459,22 +459,22 @@ __device__ __forceinline__ double fma_v(double rho_vgpr, double x, double y) {
 }
 
 // 1 + 2^(t1024 / 1024).  kf = rint(t1024), f = t1024 - kf exact; v_cvt_i32_f64 saturates, so any finite t1024 gives
-// a finite result (the exponent is clamped to [-1022, 510]: 2^510 keeps the product of the two antigens' terms
-// finite, below 2^-1022 the term is 1 anyway); NaN stays NaN.
+// a finite result (k is clamped so that the exponent stays in [-1022, 510]: 2^510 keeps the product of the two antigens'
+// terms finite, below 2^-1022 the term is 1 anyway); NaN stays NaN.  tab: the pre-biased table (abd_types.hpp).
 __device__ __forceinline__ double one_plus_exp2_tab(double t1024, const double* tab /* LDS */) {
   const double kf = __builtin_rint(t1024);
   const double f = t1024 - kf;
   int k;
   asm("v_cvt_i32_f64 %0, %1" : "=v"(k) : "v"(kf));  // saturating; a C++ cast of an out-of-range double is undefined
-  const double T = tab[k & (ABD_EXP2_TAB - 1)];
-  const int e = min(max(k >> 10, -1022), 510);  // v_med3_i32
-  const double Ts = __hiloint2double(__double2hiint(T) + (e << 20), __double2loint(T));  // T 2^e: v_lshl_add_u32
+  const int kc = min(max(k, ABD_EXP2_K_MIN), ABD_EXP2_K_MAX);  // v_med3_i32
+  const double T = tab[kc & (ABD_EXP2_TAB - 1)];               // pre-biased entry (abd_types.hpp: abd_exp2_prebias)
+  const double Ts = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T), kc), __double2loint(T));  // T 2^e: v_lshl_add_u32
   double p = fma(0x1.c6b08d910ecbdp-35, f, 0x1.ebfbe033445b4p-23);  // tools/exp2_table.py 1024 3
   p = fma(p, f, 0x1.62e42fefa39efp-11);
   p = fma(p, f, 1.0);
   return fma(Ts, p, 1.0);
 }
-static_assert(ABD_EXP2_TAB == 1024, "one_plus_exp2_tab: k >> 10 and the polynomial assume 1024 entries");
+static_assert(ABD_EXP2_TAB == 1024, "one_plus_exp2_tab: the pre-bias (j << 10) and the polynomial assume 1024 entries");
 
 struct Resp {
   double un, dn, us, ds;

@@ -143,14 +143,15 @@ __device__ __forceinline__ double g2_term(double an, double xn, double yn, doubl
 // log((w + 1/2) / 2^32), the log of the acceptance uniform, to ~4e-15 absolute (the library log costs ~100 fp64
 // instructions, five of them per lane and individual): v_log_f32 places the mantissa m in [1, 2) in bin j of the
 // 2^(j/1024) table, m 2^(-j/1024) - 1 = r is tiny (the table read backwards is the reciprocal: 2^(-j/1024) =
-// T[1024 - j] / 2) and log(1 + r) takes four terms.
+// T[1024 - j] / 2, which is the pre-biased table's entry for k = -j: abd_types.hpp) and log(1 + r) takes four terms.
 __device__ __forceinline__ double log_uniform_u32(uint32_t w, const double* tab_e2 /* LDS */) {
   const double u = (double)w + 0.5;                                   // exact, in [0.5, 2^32)
   const double m = 2.0 * __builtin_amdgcn_frexp_mant(u);              // [1, 2)
   const int e2 = __builtin_amdgcn_frexp_exp(u) - 1;                   // u = m 2^e2
   int j = (int)__builtin_rintf(__builtin_amdgcn_logf((float)m) * 1024.0f);  // v_log_f32 = log2
   j = min(max(j, 0), 1024);
-  const double inv_t = j == 0 ? 1.0 : 0.5 * tab_e2[1024 - j];         // 2^(-j/1024)
+  const double T = tab_e2[-j & (ABD_EXP2_TAB - 1)];                   // pre-biased entry of k = -j in [-1024, 0]
+  const double inv_t = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T), -j), __double2loint(T));  // 2^(-j/1024)
   const double r = fma(m, inv_t, -1.0);                               // |r| < 4e-4
   double pl = fma(r, -0.25, 1.0 / 3.0);
   pl = fma(pl, r, -0.5);

@@ -211,7 +211,7 @@ struct EvalArgs {
   // round trip in front of everything else a workgroup loads
   int32_t rg_base, rg_extra, rg_e_fin, rg_n_short;
   uint32_t rg_g_magic;
-  const double* exp2_tab;  // dense kernel: 2^(j/1024), j = 0..1023, correctly rounded (copied to LDS per workgroup)
+  const double* exp2_tab;  // dense kernel: 2^(j/1024), j = 0..1023, correctly rounded and pre-biased (copied to LDS per workgroup)
   double* partials;    // [n_chains][grid.x][ABD_NOUT]
   // dense kernel only: the fixed-order sum of the PREVIOUS launch's partials, done by the first
   // prev_n_chains workgroups of this launch (saves a kernel and a boundary per step when launches are
@@ -258,7 +258,21 @@ struct YX {
 
 
 #define ABD_EXP2_TAB 1024  // entries of the 2^(j/1024) table (8 KB of LDS per workgroup)
-#define ABD_XDICT 256      // distinct log dilutions per antigen the split panels can code (one byte per cell; abd_dense.hpp: XC)
+// The table is stored PRE-BIASED: entry j is 2^(j/1024) with its high word reduced by j << 10 (mod 2^32).  With
+// k = 1024 e + j clamped ONCE to kc in [ABD_EXP2_K_MIN, ABD_EXP2_K_MAX], the high word of 2^(j/1024) 2^e is
+// entry[kc & 1023].hi + (kc << 10): the j << 10 of the shift cancels the bias and leaves e << 20 in the exponent field, so
+// the exponent never has to be separated from k (one shift less per 2^t than hi + ((k >> 10) << 20)).  Same bits for every k
+// inside the clamp; outside it the entry read is that of the bound (j = 0 below, j = 1023 above) instead of k & 1023 --
+// terms below 2^-1022 or above 2^510, which reach no sum.  tests/native/exp2_harness.cpp checks every k on the CPU.
+#define ABD_EXP2_K_MIN (-1022 * 1024)
+#define ABD_EXP2_K_MAX (510 * 1024 + 1023)
+__host__ __device__ inline uint64_t abd_exp2_prebias(uint64_t bits_of_2_to_j_1024, int j) {
+  const uint32_t hi = (uint32_t)(bits_of_2_to_j_1024 >> 32) - ((uint32_t)j << 10);
+  return ((uint64_t)hi << 32) | (bits_of_2_to_j_1024 & 0xFFFFFFFFull);
+}
+__host__ __device__ inline int abd_exp2_clamp(int k) { return k < ABD_EXP2_K_MIN ? ABD_EXP2_K_MIN : k > ABD_EXP2_K_MAX ? ABD_EXP2_K_MAX : k; }
+__host__ __device__ inline uint32_t abd_exp2_scaled_hi(uint32_t entry_hi, int kc) { return entry_hi + ((uint32_t)kc << 10); }
+#define ABD_XDICT 256     // distinct log dilutions per antigen the split panels can code (one byte per cell; abd_dense.hpp: XC)
 
 struct Philox4 {
   uint32_t w[4];

@@ -6,6 +6,11 @@ Table-assisted 2^t for the dense kernel (abd_dense.hpp):  2^t = 2^e * T[j] * P(f
 Prints the near-minimax coefficients (Chebyshev interpolation of (2^(f/1024) - 1) / f in 60-digit arithmetic) and
 the measured worst relative error of the whole scheme evaluated in IEEE double (fma emulated exactly with
 fractions) against 60-digit references.
+
+The kernels read the table PRE-BIASED (abd_types.hpp: abd_exp2_prebias): entry j's high word is stored less j << 10
+(mod 2^32), so that with k = 1024 e + j clamped to [-1022 * 1024, 510 * 1024 + 1023] the high word of T[j] 2^e is
+entry[k & 1023].hi + (k << 10) -- no shift to separate e.  The last lines check that identity over the whole clamp range
+(the value evaluated above is therefore unchanged) and, with a fourth argument, print the first stored entries.
 """
 import sys
 from decimal import Decimal as D, getcontext
@@ -89,5 +94,22 @@ for trial in range(20000):
     err = abs(D(val) / ref - 1)
     worst = max(worst, err)
 print(f"table {NTAB}, degree {DEG}: worst relative error of 2^t over 20000 points: {float(worst):.3e}")
+
+# ---- the stored, pre-biased table ----
+import struct
+
+LOG = int(math.log2(NTAB))
+SH = 20 - LOG  # k << SH puts e at bit 20 of the high word; the j part of it is what the bias removes
+bits = [struct.unpack("<Q", struct.pack("<d", x))[0] for x in tab]
+stored = [(((b >> 32) - (j << SH)) & 0xFFFFFFFF) << 32 | (b & 0xFFFFFFFF) for j, b in enumerate(bits)]
+K_MIN, K_MAX = -1022 * NTAB, 510 * NTAB + NTAB - 1
+bad = 0
+for k in range(K_MIN, K_MAX + 1):
+    e, j = k >> LOG, k & (NTAB - 1)
+    plain = ((bits[j] >> 32) + (e << 20)) & 0xFFFFFFFF
+    biased = ((stored[j] >> 32) + (k << SH)) & 0xFFFFFFFF
+    bad += plain != biased
+print(f"pre-biased table: high words differ from hi(T[j]) + (e << 20) at {bad} of {K_MAX - K_MIN + 1} k in [{K_MIN}, {K_MAX}]")
 if len(sys.argv) > 3:
     print("first entries:", [x.hex() for x in tab[:3]])
+    print("first stored entries (bits):", [f"{x:#018x}" for x in stored[:3]])
