@@ -169,6 +169,9 @@ SYMBOLS = {
     "abd_sampler_risk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_diagnostics": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "abd_sampler_diagnostics": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D]),
+    "abd_sampler_enable_timelines": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "abd_sampler_timelines": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_timeline_quantiles": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
@@ -630,7 +633,7 @@ class Context:
     def sampler(self, chains, theta0, tune: int, seed: int = 0, target_accept: float = 0.8, max_treedepth: int = 10,
                 gibbs: bool = True, accumulate: bool = False, chain_offset: int = 0,
                 dense_metric: bool = False, pointwise: bool = False, predictive: bool = False, curves: int = 0,
-                sero_thresholds=None, diagnostics=None, risk: int = 0, risk_spec=None) -> "NativeSampler":
+                sero_thresholds=None, diagnostics=None, risk: int = 0, risk_spec=None, timelines=None) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
         independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
         pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
@@ -639,9 +642,11 @@ class Context:
         thr_n) on the titer scale (``None``: off); ``diagnostics`` = (D, L): accumulate per cell what split R-hat and a
         batch-means ESS need over the D planned draws, in batches of L (``NativeSampler.diagnostics``; ``None``: off); ``risk``:
         keep the infection-risk-by-titer table of that many draws per chain on the device, counted under ``risk_spec``
-        (``risk.spec``; ``NativeSampler.risk``)."""
+        (``risk.spec``; ``NativeSampler.risk``); ``timelines`` = (D, (lo_n, hi_n), (lo_s, hi_s)): accumulate per cell the titer
+        histograms over those ranges and the infection timing counters over the D planned draws (``NativeSampler.timelines`` /
+        ``timeline_quantiles``; ``None``: off)."""
         return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics, risk, risk_spec)
+                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics, risk, risk_spec, timelines)
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -721,7 +726,7 @@ class NativeSampler:
 
     def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
                  chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None,
-                 diagnostics=None, risk=0, risk_spec=None):
+                 diagnostics=None, risk=0, risk_spec=None, timelines=None):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -759,6 +764,10 @@ class NativeSampler:
                 raise ValueError("risk needs a risk_spec (risk.spec)")
             sp = _risk_spec(risk_spec)
             _check(self._lib, self._lib.abd_sampler_enable_risk(self._h, int(risk), C.byref(sp)))
+        if timelines is not None:
+            planned, (lo_n, hi_n), (lo_s, hi_s) = timelines
+            _check(self._lib, self._lib.abd_sampler_enable_timelines(self._h, int(planned), float(lo_n), float(hi_n), float(lo_s),
+                                                                     float(hi_s)))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
@@ -855,6 +864,35 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_diagnostics(self._h, int(k), _out(cnt, np.int64), _out(mun, np.float64),
                                                             _out(mus, np.float64), _out(info, np.int64)))
         return {"i_counts": cnt, "ab_n_mu": mun, "ab_s_mu": mus, "info": info}
+
+    def timelines(self, k: int, hist: bool = False):
+        """The timeline counters of the k-th chain over its draws so far (abd_hip.h: abd_sampler_timelines) -> {"inf", "cum":
+        (G, N) int64, "ninf": (N, 8) int64, "n_draws": int} and, with ``hist``, {"hist_n", "hist_s": (G, N, 64) uint16}:
+        ``timelines.from_draws`` of the chain's draws."""
+        G, N = self._ctx.n_gaps, self._ctx.n_inds
+        inf, cum, ninf = np.empty((G, N), np.int64), np.empty((G, N), np.int64), np.empty((N, 8), np.int64)
+        hn, hs = (np.empty((G, N, 64), np.uint16), np.empty((G, N, 64), np.uint16)) if hist else (None, None)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_timelines(self._h, int(k), None if hn is None else _out(hn, np.uint16),
+                                                          None if hs is None else _out(hs, np.uint16), _out(inf, np.int64),
+                                                          _out(cum, np.int64), _out(ninf, np.int64), C.byref(n)))
+        out = {"inf": inf, "cum": cum, "ninf": ninf, "n_draws": n.value}
+        if hist:
+            out["hist_n"], out["hist_s"] = hn, hs
+        return out
+
+    def timeline_quantiles(self, q):
+        """Quantiles ``q`` (1 to 8 numbers in [0, 1]) of the two titers per cell from the histograms pooled over the sampler's chains,
+        computed on the device (abd_hip.h: abd_sampler_timeline_quantiles) -> (q_n, q_s), each (len(q), G, N)."""
+        G, N = self._ctx.n_gaps, self._ctx.n_inds
+        qa = _as(np.atleast_1d(q), np.float64)
+        if qa.ndim != 1:
+            raise ValueError(f"q must be one-dimensional, got shape {qa.shape}")
+        nq = int(qa.size)
+        out_n, out_s = np.empty((max(nq, 1), G, N)), np.empty((max(nq, 1), G, N))
+        _check(self._lib, self._lib.abd_sampler_timeline_quantiles(self._h, nq, _ptr(qa, C.c_double), _out(out_n, np.float64),
+                                                                   _out(out_s, np.float64)))
+        return out_n[:nq], out_s[:nq]
 
     def risk(self, k: int):
         """The infection-risk-by-titer table of every draw of the k-th chain so far (``Context.risk`` per draw) -> (draws, 2, 2, G,

@@ -77,6 +77,14 @@ def build_parser() -> argparse.ArgumentParser:
                         type=int)
     parser.add_argument("--risk_all_infections", help="With --risk: count every infection of an individual inside the window, not "
                         "only the first.", action="store_true")
+    parser.add_argument("--timelines", help="Accumulate per cell, over all draws on the device, what a per-individual timeline needs "
+                        "(--thin does not apply): histograms of the S and N titers, from which the median and a 95 %% band are read, "
+                        "the infection probability and the exact probability of at least one infection so far in the cell's time "
+                        "chunk, and per individual the distribution of the number of infections (tl_* and tl_summary_* in the "
+                        "output).  Reports the individuals more likely infected than not, the median width of the bands and the share "
+                        "of bands that touch the ends of the range.", action="store_true")
+    parser.add_argument("--timeline_range_s", help="With --timelines: the S titer range of the histograms, --timeline_range_s=lo,hi.", default="-4,8")
+    parser.add_argument("--timeline_range_n", help="With --timelines: the N titer range of the histograms, --timeline_range_n=lo,hi.", default="-4,8")
     return parser
 
 
@@ -185,6 +193,39 @@ def diagnostics_line(sm: dict) -> str:
     return "diagnostics: " + "; ".join(parts)
 
 
+def timeline_ranges_of(args):
+    """((lo_n, hi_n), (lo_s, hi_s)) of the --timeline_range_* flags; ``SystemExit`` for what ``timelines.check_range`` refuses."""
+    from . import timelines
+
+    out = []
+    for flag, text in (("--timeline_range_n", args.timeline_range_n), ("--timeline_range_s", args.timeline_range_s)):
+        try:
+            lo, hi = (float(x) for x in text.split(","))
+            out.append(timelines.check_range(lo, hi))
+        except ValueError as e:
+            raise SystemExit(f"{flag}: need lo,hi with lo < hi, got {text!r} ({e})")
+    return tuple(out)
+
+
+def add_timelines(res: dict, last_gap=None) -> dict:
+    """timelines.summary of a gathered ``timelines=True`` result: its arrays go into ``res`` (``tl_summary_*``), the summary is
+    returned.  A result gathered from several ranks carries the histograms and no pooled quantiles (``timeline_q=None``): they are
+    pooled here (``timelines.merge`` / ``quantiles`` at ``DEFAULT_Q``) and the histograms are dropped from ``res``."""
+    from . import timelines
+
+    sm = timelines.summary(res, last_gap)
+    if "tl_q_n" not in res:
+        m = timelines.merge(res)
+        q = np.array(timelines.DEFAULT_Q)
+        res["tl_q"] = np.tile(q, (np.asarray(res["tl_inf"]).shape[0], 1))
+        res["tl_q_n"] = timelines.quantiles(m["hist_n"], q, *m["range"][0])
+        res["tl_q_s"] = timelines.quantiles(m["hist_s"], q, *m["range"][1])
+        for k in timelines.HIST_KEYS:
+            res.pop(k)
+    res.update(timelines.summary_arrays(sm))
+    return sm
+
+
 def add_observed(res: dict, data) -> None:
     """The observed ODs of both antigens (no chain axis: added on the rank that writes, after any gather)."""
     res["observed_data_it_s_lik"] = np.asarray(data.s.obs[3], dtype=np.float64)
@@ -203,7 +244,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS
         post = {k: v for k, v in res.items()
-                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_", "diag_", "risk_"))
+                if not k.startswith(("stat_", "waic_", "log_likelihood_", "posterior_predictive_", "ppc_", "observed_data_", "curves_", "diag_", "risk_", "tl_"))
                 and k not in skip}
         stats = {k[5:]: v for k, v in res.items() if k.startswith("stat_")}
         means = {k: res[k] for k in ("mean_i", "mean_ab_n_mu", "mean_ab_s_mu") + WAIC_KEYS + PPC_KEYS if k in res}
@@ -213,6 +254,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
             if k.startswith("curves_"):
                 (means if k.startswith(("curves_summary_", "curves_n_followed")) else stats)[k] = v
         means.update({k: v for k, v in res.items() if k.startswith("diag_") and k != "diag_summary_scalar_names"})  # no draw axis
+        means.update({k: v for k, v in res.items() if k.startswith("tl_")})  # no draw axis either
         # the risk tables: what has a draw axis sits (and is thinned) with the statistics, the rest travels with the means
         for k, v in res.items():
             if k.startswith("risk_"):
@@ -261,6 +303,7 @@ def main(argv=None) -> int:
         else data.calculate_splits(delta=args.split_delta, omicron=args.split_omicron)
     )  # abd.py:915-919
     risk_spec = risk_spec_of(args, data.n_gaps)  # (refused before anything is built)
+    tl_ranges = timeline_ranges_of(args) if args.timelines else ((-4, 8), (-4, 8))
     # pm.sample(cores=...) (abd.py:922) runs chains = max(2, cores) with cores = min(4, CPU count) when not given
     import os
 
@@ -287,16 +330,37 @@ def main(argv=None) -> int:
 
     if args.thin < 1:
         raise SystemExit(f"--thin must be >= 1, got {args.thin}")
+    if args.timelines and world > 1:
+        # every rank hands its chains' histograms to rank 0, which pools them: refused (by every rank alike, before anything runs)
+        # when what rank 0 holds after the gather -- the histograms and counters of all chains beside their recorded draws --
+        # would not fit its host budget
+        from . import timelines as tl_mod
+        from .sampler import record_budget_bytes, record_bytes
+
+        K = (len(data.s) + len(data.n)) if (args.log_likelihood or args.posterior_predictive) else 0
+        own = tl_mod.result_bytes(chains, data.n_gaps, data.n_inds, n_q=0, hist=True)
+        rest = record_bytes(chains, -(-args.draws // args.thin), data.n_gaps, data.n_inds, not args.no_deterministics, not args.no_discrete,
+                            n_readings=K if args.log_likelihood else 0, n_replicates=K if args.posterior_predictive else 0)
+        if own + rest > record_budget_bytes():
+            if dist is not None:
+                dist.destroy_process_group()
+            raise SystemExit(f"--timelines over {world} processes gathers the histograms of {chains} chains on one rank: {own} bytes "
+                             f"beside {rest} bytes of recorded draws, over the host budget of {record_budget_bytes()} bytes "
+                             f"(ABD_RECORD_BUDGET_GB raises it; --thin, --no_deterministics, --no_discrete record less; one process "
+                             f"needs no histograms on the host)")
     res = sample(m, tune=args.tune, draws=args.draws, chains=mine, seed=args.seed,
                  record_deterministics=not args.no_deterministics, record_discrete=not args.no_discrete, progress=progress,
                  chain_offset=first, dense_metric=args.dense_metric, thin=args.thin, log_likelihood=args.log_likelihood,
                  waic=args.waic, posterior_predictive=args.posterior_predictive, ppc=args.ppc, curves=args.curves,
                  sero_thresholds=(args.sero_threshold_s, args.sero_threshold_n), diagnostics=args.diagnostics,
-                 diag_batch=args.diag_batch, risk=risk_spec)  # abd.py:922
+                 diag_batch=args.diag_batch, risk=risk_spec, timelines=args.timelines, timeline_ranges=tl_ranges,
+                 timeline_q=None if world > 1 else (0.025, 0.5, 0.975),  # (several ranks: rank 0 pools the histograms)
+                 timelines_hist=args.timelines and world > 1)  # abd.py:922
     name = m.ctx.device_name
     m.close()
     if world > 1:
         import torch
+
 
         dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else None
         res = distributed.gather_results(res, counts, dist, dev)
@@ -327,6 +391,10 @@ def main(argv=None) -> int:
             print(risk_line(add_risk(res)), file=sys.stderr)
         if args.diagnostics:
             print(diagnostics_line(add_diagnostics(res, getattr(data, "last_gap", None))), file=sys.stderr)
+        if args.timelines:
+            from . import timelines
+
+            print(timelines.line(add_timelines(res, getattr(data, "last_gap", None))), file=sys.stderr)
         if args.posterior_predictive:
             add_observed(res, data)
         out = write_posterior(res, args.netcdf, data.coords)

@@ -11,6 +11,11 @@
 #include "abd_curves.hpp"
 #include "abd_risk.hpp"
 #include "abd_diag.hpp"
+#include "abd_timeline.hpp"
+
+static_assert(ABD_TL_BINS == ABD_TIMELINE_BINS && ABD_TL_MAX_DRAWS == ABD_TIMELINE_MAX_DRAWS && ABD_TL_MAX_Q == ABD_TIMELINE_MAX_Q &&
+                  ABD_TL_NINF == ABD_TIMELINE_NINF,
+              "abd_timeline.hpp and include/abd_hip.h describe the same counters");
 
 namespace abdi {
 
@@ -410,6 +415,7 @@ int derive_sizes(abd_ctx* c, const abd_desc* d, bool one_per_cell) {
   c->prior_const = prior_constant(G);
   c->n_lg = (N + 63) / 64;
   c->n_chunks = d->n_splits + 1;
+  for (int k = 0; k < d->n_splits; ++k) c->splits[k] = d->splits[k];
   c->storage = d->storage;
   c->dense = one_per_cell;
   // the dense kernel addresses the gap rows of a piece (up to G of them) with a 32-bit scalar offset (abd_dense.hpp);
@@ -635,6 +641,48 @@ int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsig
   const int64_t tiles = (int64_t)((c->G + ABD_DIAG_TILE - 1) / ABD_DIAG_TILE) * ((c->N + ABD_DIAG_TILE - 1) / ABD_DIAG_TILE);
   hipLaunchKernelGGL(abd_diag_export_kernel, dim3((unsigned)tiles), dim3(256), 0, st, static_cast<const unsigned char*>(src), stride, width,
                      c->G, c->N, dst);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
+int launch_timeline(abd_ctx* c, int chain, const double* theta, const double range_n[2], const double range_s[2], hipStream_t st,
+                    uint32_t* hist_n, uint32_t* hist_s, uint32_t* cell, uint32_t* ninf) {
+  const ChainPar p = chain_par(c, chain, theta);
+  TimelineArgs a;
+  a.vw = c->vw;
+  a.iw = p.iw;
+  a.waner = p.waner;
+  a.last = c->d_last;
+  a.hist_n = hist_n, a.hist_s = hist_s, a.cell = reinterpret_cast<TimelineCell*>(cell), a.ninf = ninf;
+  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
+  a.init_s = p.init_s, a.perm_s = p.perm_s;
+  a.rn = timeline_range(range_n[0], range_n[1]), a.rs = timeline_range(range_s[0], range_s[1]);
+  a.G = c->G, a.N = c->N, a.nt = c->nt;
+  a.n_splits = c->n_chunks - 1, a.s0 = c->splits[0], a.s1 = c->splits[1];
+  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
+  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
+  if (c->nt > ABD_MAXT)
+    hipLaunchKernelGGL(abd_timeline_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  else
+    hipLaunchKernelGGL(abd_timeline_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
+int launch_timeline_hist_export(abd_ctx* c, const uint32_t* src, int g0, int n_g, void* dst, hipStream_t st) {
+  const int64_t cells = (int64_t)n_g * c->N;  // 32 per pass of a workgroup
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((cells + 31) / 32, (int64_t)c->n_cu * 16));
+  hipLaunchKernelGGL(abd_timeline_hist_export_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<const uint4*>(src), c->G, c->N, g0,
+                     n_g, static_cast<uint4*>(dst));
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
+
+int launch_timeline_quantiles(abd_ctx* c, const uint32_t* hist, int64_t chain_stride, int n_chains, const double range[2], int n_q,
+                              const double* q, double* out, hipStream_t st) {
+  const int64_t tiles = (int64_t)((c->G + ABD_TL_QTILE - 1) / ABD_TL_QTILE) * ((c->N + ABD_TL_QTILE - 1) / ABD_TL_QTILE);
+  hipLaunchKernelGGL(abd_timeline_quantile_kernel, dim3((unsigned)tiles), dim3(256), 0, st, hist, chain_stride, n_chains, c->G, c->N,
+                     timeline_range(range[0], range[1]), n_q, q, out);
   HIP_TRY(hipGetLastError());
   return ABD_OK;
 }

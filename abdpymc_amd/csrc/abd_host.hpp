@@ -175,6 +175,7 @@ struct abd_ctx {
   int cpw_forced = 0;
   int dense_blocks = 0;   // dense kernel grid.x
   uint64_t chunk_mask[3][ABD_MAXT_MAX] = {};
+  int splits[2] = {0, 0};  // the chunks' inner borders, n_chunks - 1 of them (abd_timeline.hpp: timeline_cum)
   ~abd_ctx();  // quiesces; then the members below go in reverse order, pipes and events last
   // A pipe = a HIP stream with its own pair of partial buffers and at most one Pending fixed-order sum (abd_eval.hip:
   // plan_launch names who sums a launch's partial rows: Pending, FinalizeNow or Own).  Pipe 0 is the context's stream
@@ -297,6 +298,17 @@ int launch_diag(abd_ctx* c, int chain, const double* theta, hipStream_t st, int6
 // One individual-major plane of the accumulators (first element src, elements `stride` bytes apart, `width` 4 or 8 bytes
 // wide) into dst [G*N] in the caller's gap-major order, 8 bytes per cell, on stream st
 int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsigned long long* dst, hipStream_t st);
+// One draw of chain `chain` at theta into its timeline counters on stream st (abd_timeline.hpp): hist_n and hist_s [G*N][32]
+// words, cell [G*N][2] and ninf [N][8] are the chain's own planes; range_n / range_s the titer ranges (lo, hi).  Touches no member of
+// the context but d_last: the sampler's host threads call it side by side.
+int launch_timeline(abd_ctx* c, int chain, const double* theta, const double range_n[2], const double range_s[2], hipStream_t st,
+                    uint32_t* hist_n, uint32_t* hist_s, uint32_t* cell, uint32_t* ninf);
+// Gap rows [g0, g0 + n_g) of one individual-major histogram plane into dst [n_g][N][64] 16-bit counters on stream st
+int launch_timeline_hist_export(abd_ctx* c, const uint32_t* src, int g0, int n_g, void* dst, hipStream_t st);
+// Quantiles q[0 .. n_q) (device memory) of the histograms over range (lo, hi) pooled over n_chains planes `chain_stride` words
+// apart into out [n_q][G][N] on stream st
+int launch_timeline_quantiles(abd_ctx* c, const uint32_t* hist, int64_t chain_stride, int n_chains, const double range[2], int n_q,
+                              const double* q, double* out, hipStream_t st);
 // the chain's packed i_raw as (G, N) int8 on stream st
 int launch_unpack(abd_ctx* c, int chain, int8_t* dst, hipStream_t st);
 

@@ -87,6 +87,13 @@ struct abd_sampler {
   DevBuf<uint32_t> d_diag_inf;
   DevBuf<unsigned long long> d_diag_cb2, d_diag_stage;
   int64_t diag_draws = 0, diag_H = 0, diag_L = 0;  // planned draws D, H = D / 2, batch length
+  // per-individual timelines over all draws (abd_timeline.hpp), individual-major planes per chain: [n][2][G*N][32] words of
+  // the two titers' histograms (ab_n_mu, then ab_s_mu), [n][G*N][2] inf and cum, [n][N][8] ninf, and the read-out's staging
+  DevBuf<uint32_t> d_tl_hist, d_tl_cell, d_tl_ninf;
+  DevBuf<unsigned long long> d_tl_stage;
+  size_t tl_stage_bytes = 0;
+  int64_t tl_draws = 0;  // planned draws
+  double tl_range_n[2] = {0.0, 0.0}, tl_range_s[2] = {0.0, 0.0};
 };
 
 namespace {
@@ -527,6 +534,12 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   if (draw && s->d_diag_tit && iter - s->o.tune < 2 * s->diag_H)
     if (int rc = launch_diag(c, chain, q, st, iter - s->o.tune, s->diag_H, s->diag_L, s->d_diag_tit + (size_t)j * 2 * 7 * cells,
                              s->d_diag_inf + (size_t)j * 4 * cells, s->d_diag_cb2 + (size_t)j * cells))
+      return rc;
+  // timelines: every draw, whatever is recorded (abd_sampler_run_record has checked the planned draws)
+  if (draw && s->d_tl_hist)
+    if (int rc = launch_timeline(c, chain, q, s->tl_range_n, s->tl_range_s, st, s->d_tl_hist + (size_t)j * 2 * cells * (ABD_TIMELINE_BINS / 2),
+                                 s->d_tl_hist + ((size_t)j * 2 + 1) * cells * (ABD_TIMELINE_BINS / 2), s->d_tl_cell + (size_t)j * 2 * cells,
+                                 s->d_tl_ninf + (size_t)j * ABD_TIMELINE_NINF * N))
       return rc;
   // risk table: every draw's, as the curves
   if (draw && s->d_risk)
@@ -1064,6 +1077,9 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (s->d_risk && s->it + n_iter - s->o.tune > s->risk_capacity)
     return fail(ABD_ERR_STATE, "risk: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
                 (long long)s->risk_capacity);
+  if (s->d_tl_hist && s->it + n_iter - s->o.tune > s->tl_draws)
+    return fail(ABD_ERR_STATE, "timelines: draws up to %lld pass the planned %lld", (long long)(s->it + n_iter - s->o.tune),
+                (long long)s->tl_draws);
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
@@ -1286,6 +1302,125 @@ int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double
     const double* tit = s->d_diag_tit + ((size_t)k * 2 + x) * 7 * cells;
     for (int v = 0; v < 6; ++v)
       if (int rc = plane(tit + (size_t)planes[v] * cells, 8, 8, outs[x] + (size_t)v * cells)) return rc;
+  }
+  return ABD_OK;
+}
+
+int abd_sampler_enable_timelines(abd_sampler* s, int64_t planned_draws, double lo_n, double hi_n, double lo_s, double hi_s) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (planned_draws < 0 || planned_draws > ABD_TIMELINE_MAX_DRAWS)
+    return fail(ABD_ERR_ARG, "timelines: planned_draws=%lld outside [0, %d] (16-bit counters)", (long long)planned_draws, ABD_TIMELINE_MAX_DRAWS);
+  if (planned_draws) {
+    const struct { const char* name; double lo, hi; } ag[2] = {{"ab_n_mu", lo_n, hi_n}, {"ab_s_mu", lo_s, hi_s}};
+    for (const auto& x : ag)
+      if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi) || !std::isfinite(x.hi - x.lo))
+        return fail(ABD_ERR_ARG, "timelines: the range [%g, %g) of %s is not finite and ascending", x.lo, x.hi, x.name);
+  }
+  if (s->ran) return fail(ABD_ERR_STATE, "timelines must be enabled before the first abd_sampler_run call");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  s->d_tl_hist.reset();  // (nothing has been launched on them: the sampler has not run)
+  s->d_tl_cell.reset();
+  s->d_tl_ninf.reset();
+  s->d_tl_stage.reset();
+  s->tl_draws = 0;
+  s->tl_stage_bytes = 0;
+  if (planned_draws == 0) return ABD_OK;
+  const size_t cells = (size_t)c->G * c->N, n = (size_t)s->n, line = ABD_TIMELINE_BINS * sizeof(uint16_t);
+  // staging of the read-out: a plane of 8 bytes per cell, and at least one gap's row of histograms
+  const size_t stage_bytes = std::max(cells * sizeof(unsigned long long), (size_t)c->N * line);
+  const size_t bytes = n * (cells * (2 * line + 2 * sizeof(uint32_t)) + (size_t)c->N * ABD_TIMELINE_NINF * sizeof(uint32_t)) + stage_bytes;
+  DevBuf<uint32_t> hist, cell, ninf;  // (the sampler takes all four or none)
+  DevBuf<unsigned long long> stage;
+  hipError_t e = hist.alloc_zero(n * 2 * cells * (line / sizeof(uint32_t)), c->stream);
+  if (e == hipSuccess) e = cell.alloc_zero(n * 2 * cells, c->stream);
+  if (e == hipSuccess) e = ninf.alloc_zero(n * ABD_TIMELINE_NINF * (size_t)c->N, c->stream);
+  if (e == hipSuccess) e = stage.alloc(stage_bytes / sizeof(unsigned long long));
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "timelines: %zu bytes of device memory", bytes);
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "timelines: %s", hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  s->d_tl_hist = std::move(hist);
+  s->d_tl_cell = std::move(cell);
+  s->d_tl_ninf = std::move(ninf);
+  s->d_tl_stage = std::move(stage);
+  s->tl_stage_bytes = stage_bytes;
+  s->tl_draws = planned_draws;
+  s->tl_range_n[0] = lo_n, s->tl_range_n[1] = hi_n, s->tl_range_s[0] = lo_s, s->tl_range_s[1] = hi_s;
+  return ABD_OK;
+}
+
+int abd_sampler_timelines(abd_sampler* s, int32_t k, uint16_t* hist_n, uint16_t* hist_s, int64_t* inf, int64_t* cum, int64_t* ninf,
+                          int64_t* n_draws) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_tl_hist) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
+  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
+  if (!hist_n && !hist_s && !inf && !cum && !ninf) return ABD_OK;
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
+  const size_t cells = (size_t)c->G * c->N, N = (size_t)c->N, line = ABD_TIMELINE_BINS * sizeof(uint16_t);
+  // through the staging buffer on the context's stream: the copy waits for the kernel and the next kernel for the copy
+  int64_t* planes[2] = {inf, cum};
+  for (int v = 0; v < 2; ++v) {
+    if (!planes[v]) continue;
+    if (int rc = launch_diag_export(c, s->d_tl_cell + (size_t)k * 2 * cells + v, 8, 4, s->d_tl_stage, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(planes[v], s->d_tl_stage, cells * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  uint16_t* hists[2] = {hist_n, hist_s};
+  const int rows = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->G, s->tl_stage_bytes / (N * line)));  // gap rows per pass
+  for (int v = 0; v < 2; ++v) {
+    if (!hists[v]) continue;
+    const uint32_t* src = s->d_tl_hist + ((size_t)k * 2 + v) * cells * (line / sizeof(uint32_t));
+    for (int g0 = 0; g0 < c->G; g0 += rows) {
+      const int n_g = std::min(rows, c->G - g0);
+      if (int rc = launch_timeline_hist_export(c, src, g0, n_g, s->d_tl_stage, c->stream)) return rc;
+      HIP_TRY(hipMemcpyAsync(hists[v] + (size_t)g0 * N * ABD_TIMELINE_BINS, s->d_tl_stage, (size_t)n_g * N * line, hipMemcpyDeviceToHost,
+                             c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+  }
+  if (ninf) {
+    std::vector<uint32_t> h(N * ABD_TIMELINE_NINF);
+    HIP_TRY(hipMemcpy(h.data(), s->d_tl_ninf + (size_t)k * ABD_TIMELINE_NINF * N, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < h.size(); ++e) ninf[e] = (int64_t)h[e];
+  }
+  return ABD_OK;
+}
+
+int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q, double* out_n, double* out_s) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (n_q < 1 || n_q > ABD_TIMELINE_MAX_Q) return fail(ABD_ERR_ARG, "timelines: n_q=%d outside [1, %d]", n_q, ABD_TIMELINE_MAX_Q);
+  if (!q) return fail(ABD_ERR_ARG, "timelines: q is NULL");
+  for (int e = 0; e < n_q; ++e)
+    if (!(q[e] >= 0.0 && q[e] <= 1.0)) return fail(ABD_ERR_ARG, "timelines: q[%d]=%g outside [0, 1]", e, q[e]);
+  if (!s->d_tl_hist) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
+  if (!out_n && !out_s) return ABD_OK;
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
+  const size_t cells = (size_t)c->G * c->N, words = ABD_TIMELINE_BINS / 2;
+  DevBuf<double> d_q, d_out;  // the read-out's own: n_q planes of 8 bytes per cell
+  hipError_t e = d_q.upload(q, (size_t)n_q);
+  if (e == hipSuccess) e = d_out.alloc((size_t)n_q * cells);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "timelines: %zu bytes of device memory for the quantiles", (size_t)n_q * cells * sizeof(double));
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "timelines: %s", hipGetErrorString(e));
+  double* outs[2] = {out_n, out_s};
+  const double* ranges[2] = {s->tl_range_n, s->tl_range_s};
+  for (int v = 0; v < 2; ++v) {
+    if (!outs[v]) continue;
+    if (int rc = launch_timeline_quantiles(c, s->d_tl_hist + (size_t)v * cells * words, (int64_t)(2 * cells * words), s->n, ranges[v], n_q, d_q,
+                                           d_out, c->stream))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(outs[v], d_out, (size_t)n_q * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
   }
   return ABD_OK;
 }

@@ -51,6 +51,10 @@ def split_counts(n_chains: int, world: int) -> List[int]:
     return [base + (1 if r < extra else 0) for r in range(world)]
 
 
+# the array types both backends' gather carries as they are
+_CARRIED = ("float64", "float32", "float16", "int64", "int32", "int8", "uint8")
+
+
 def gather_results(res: dict, counts: List[int], dist=None, device=None, dst: int = 0):
     """
     Concatenate per-rank result dicts (arrays with a leading local-chain axis) along the chain axis, in rank
@@ -58,6 +62,8 @@ def gather_results(res: dict, counts: List[int], dist=None, device=None, dst: in
     travels in its own dtype (the int8 ``i_raw`` / ``i`` panels of a recorded run are the bulk of the bytes: as
     float64 all-gathered to every rank, as before, 1 000 draws of config 3 were 16 GB per chain per rank).
     Shards may differ in size by one chain: blocks are padded to the largest shard and trimmed afterwards.
+    Arrays of a type the collectives of gloo or NCCL do not carry (the timelines' uint16 histograms; any 16-bit or unsigned
+    integer beyond uint8) travel as their bytes, uint8 with a trailing axis of the item size, and come back in their own type.
     """
     if dist is None or not dist.is_initialized() or dist.get_world_size() == 1:
         return res
@@ -70,6 +76,10 @@ def gather_results(res: dict, counts: List[int], dist=None, device=None, dst: in
         a = np.ascontiguousarray(res[key])
         if a.ndim == 0 or a.shape[0] != counts[rank]:
             raise ValueError(f"{key}: leading axis {a.shape} is not this rank's chain count {counts[rank]}")
+        own = a.dtype
+        as_bytes = own.name not in _CARRIED
+        if as_bytes:
+            a = a.reshape(a.shape + (1,)).view(np.uint8)
         pad = np.zeros((cmax,) + a.shape[1:], dtype=a.dtype)
         pad[: a.shape[0]] = a
         t = torch.from_numpy(pad)
@@ -78,7 +88,8 @@ def gather_results(res: dict, counts: List[int], dist=None, device=None, dst: in
         parts = [torch.empty_like(t) for _ in range(world)] if rank == dst else None
         dist.gather(t, parts, dst=dst)
         if rank == dst:
-            out[key] = np.concatenate([parts[r][: counts[r]].cpu().numpy() for r in range(world)])
+            got = np.concatenate([parts[r][: counts[r]].cpu().numpy() for r in range(world)])
+            out[key] = got.view(own)[..., 0] if as_bytes else got
     return out
 
 

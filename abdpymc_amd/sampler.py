@@ -302,7 +302,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   budget_bytes: Optional[int] = None, log_likelihood: bool = False,
                   waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
                   sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None,
-                  risk=None) -> Dict[str, np.ndarray]:
+                  risk=None, timelines: bool = False, timeline_ranges=((-4, 8), (-4, 8)), timeline_q=(0.025, 0.5, 0.975),
+                  timelines_hist: bool = False) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -349,8 +350,21 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     x gap x bin of the previous gap's titer -- and the spec, one row per chain: ``risk_edges_s`` / ``risk_edges_n`` (chains, 7),
     NaN beyond the edges given, and ``risk_window`` (chains, 3) = (start, end, first_only); ``risk.summary`` reads them.  The
     follow-up is the curves'.  The table's host bytes count against ``budget_bytes``.  The trajectories do not change either.
+
+    ``timelines``: accumulate per cell, over ALL draws on the device, what a per-individual timeline needs (``timelines.py``;
+    ``thin`` does not apply): histograms of the two titers over ``timeline_ranges`` = ((lo_n, hi_n), (lo_s, hi_s)) (default: the
+    reference's plot range) and the infection timing counters.  Per chain ``tl_inf`` / ``tl_cum`` (chains, G, N) int64 -- draws
+    with an infection in the cell; with one so far in the cell's time chunk --, ``tl_ninf`` (chains, N, 8) int64 -- draws by the
+    number of infections within follow-up (the curves') --, ``tl_info`` (chains, 1) the draws, ``tl_range`` (chains, 2, 2) and
+    ``tl_q`` (chains, Q); pooled over the chains by a device kernel ``tl_q_n`` / ``tl_q_s`` (Q, G, N), the quantiles ``timeline_q``
+    (1 to 8 levels; ``timelines.summary`` reads the smallest, the one nearest 0.5 and the largest as lower, median and upper;
+    ``None``: no pooled quantiles, none of the three keys -- for a caller that pools the histograms of several processes itself)
+    of ``ab_n_mu`` / ``ab_s_mu``; with ``timelines_hist`` also the histograms ``tl_hist_n`` / ``tl_hist_s`` (chains,
+    G, N, 64) uint16.  ``timelines.summary`` / ``individual`` read them.  At most 65535 draws per chain; the arrays' host bytes
+    count against ``budget_bytes``.  The trajectories do not change either.
     """
     from . import curves as curves_mod
+    from . import timelines as tl_mod
     from . import diagnostics as diag_mod
     from . import risk as risk_mod
     from .model import THETA_NAMES, constrain
@@ -406,6 +420,28 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                 f"of 8 bytes per gap and draw) and the other recorded arrays {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
                 f"{budget / 2 ** 30:.2f} GiB: fewer draws, record less (thin, no_deterministics / record_discrete=False) or raise "
                 f"ABD_RECORD_BUDGET_GB")
+    if timelines:
+        timeline_ranges = tuple(tl_mod.check_range(*r) for r in timeline_ranges)
+        if len(timeline_ranges) != 2:
+            raise ValueError("timeline_ranges must be ((lo_n, hi_n), (lo_s, hi_s))")
+        pooled = timeline_q is not None  # (None: the device's pooled quantiles are not read out)
+        timeline_q = np.atleast_1d(np.asarray(timeline_q if pooled else [0.5], dtype=np.float64))
+        if timeline_q.ndim != 1 or not 1 <= timeline_q.size <= tl_mod.MAX_Q or not ((timeline_q >= 0) & (timeline_q <= 1)).all():
+            raise ValueError(f"timeline_q must be 1 to {tl_mod.MAX_Q} numbers in [0, 1]")
+        if not 1 <= draws <= tl_mod.MAX_DRAWS:
+            raise ValueError(f"timelines count in 16 bits: 1 to {tl_mod.MAX_DRAWS} draws per chain, got {draws}")
+        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
+        own = tl_mod.result_bytes(chains, G, N, timeline_q.size if pooled else 0, timelines_hist)
+        need = own + (diag_mod.result_bytes(chains, G, N) if diagnostics else 0) + (
+            chains * draws * 4 * G * risk_mod.N_BINS * 8 if risk is not None else 0) + record_bytes(
+            chains, n_rec, G, N, record_deterministics, record_discrete, n_readings=(K_s + K_n) if log_likelihood else 0,
+            n_replicates=(K_s + K_n) if posterior_predictive else 0)
+        if need > budget:
+            raise ValueError(
+                f"the timelines of {chains} chains x ({G}, {N}) take {own / 2 ** 30:.2f} GiB ({own} bytes) of host arrays"
+                f"{' (the histograms: 256 bytes per cell and chain)' if timelines_hist else ''} and the other recorded arrays "
+                f"{(need - own) / 2 ** 30:.2f} GiB, over the budget of {budget / 2 ** 30:.2f} GiB: record less (thin, "
+                f"no_deterministics / record_discrete=False) or raise ABD_RECORD_BUDGET_GB")
     chunk = max(thin, chunk - chunk % thin) if thin > 1 else chunk  # calls record iterations 0, thin, ... of THEIR range
     pt = model.initial_point()
     q0 = np.empty((chains, len(THETA_NAMES)))
@@ -417,8 +453,9 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
                       dense_metric=dense_metric, pointwise=waic, predictive=ppc, curves=draws if curves else 0,
                       sero_thresholds=sero_thresholds, diagnostics=(draws, diag_batch) if diagnostics else None,
-                      risk=draws if risk is not None else 0, risk_spec=risk)
-    if curves or risk is not None:
+                      risk=draws if risk is not None else 0, risk_spec=risk,
+                      timelines=(draws, *timeline_ranges) if timelines else None)
+    if curves or risk is not None or timelines:
         last_gap = getattr(getattr(model, "data", None), "last_gap", None)
         ctx.set_follow_up(last_gap)
     n_grad = chains  # the evaluation at the starting points
@@ -494,6 +531,15 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         per_chain = [smp.diagnostics(c) for c in range(chains)]
         for key, name in (("i_counts", "diag_i_counts"), ("ab_n_mu", "diag_ab_n_mu"), ("ab_s_mu", "diag_ab_s_mu"), ("info", "diag_info")):
             res[name] = np.stack([pc[key] for pc in per_chain])
+    if timelines:
+        per_chain = [smp.timelines(c, hist=timelines_hist) for c in range(chains)]
+        for key in ("inf", "cum", "ninf") + (("hist_n", "hist_s") if timelines_hist else ()):
+            res["tl_" + key] = np.stack([pc[key] for pc in per_chain])
+        res["tl_info"] = np.array([[pc["n_draws"]] for pc in per_chain], dtype=np.int64)
+        res["tl_range"] = np.tile(np.array(timeline_ranges, dtype=np.float64), (chains, 1, 1))
+        if pooled:
+            res["tl_q"] = np.tile(timeline_q, (chains, 1))
+            res["tl_q_n"], res["tl_q_s"] = smp.timeline_quantiles(timeline_q)
     if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
@@ -514,7 +560,9 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
            waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None, risk=None) -> Dict[str, np.ndarray]:
+           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None, risk=None,
+           timelines: bool = False, timeline_ranges=((-4, 8), (-4, 8)), timeline_q=(0.025, 0.5, 0.975),
+           timelines_hist: bool = False) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
     (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
     if chains > model.n_chains:
@@ -524,7 +572,10 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
                              log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc,
                              curves=curves, sero_thresholds=sero_thresholds, diagnostics=diagnostics, diag_batch=diag_batch,
-                             risk=risk)
+                             risk=risk, timelines=timelines, timeline_ranges=timeline_ranges, timeline_q=timeline_q,
+                             timelines_hist=timelines_hist)
+    if timelines:
+        raise ValueError("timelines need the native sampler (sample(native=True)): the counters of every draw are accumulated inside it")
     if risk is not None:
         raise ValueError("risk needs the native sampler (sample(native=True)): every draw is reduced on the device inside it")
     if diagnostics:

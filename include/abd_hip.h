@@ -443,6 +443,50 @@ int abd_sampler_enable_diagnostics(abd_sampler* s, int64_t planned_draws, int64_
  * in half 0, draws in half 1, batches closed, L.  Any pointer may be NULL.  May be called between run calls.  ABD_ERR_STATE
  * ("not enabled") without abd_sampler_enable_diagnostics. */
 int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double* ab_n_mu, double* ab_s_mu, int64_t info[4]);
+
+/* Per-individual timelines over ALL draws: what the reference's per-individual figure (timelines.py: plot_individual) reads
+ * from the (draw, gap, ind) arrays of the whole posterior -- the spread of the two titers of a cell, its infection probability
+ * and the probability of at least one infection so far inside the cell's time chunk -- kept on the device because a run at full
+ * size never keeps its draws (abdpymc_amd/csrc/abd_timeline.hpp; abdpymc_amd/timelines.py: from_draws is the same definition
+ * as NumPy).  Accumulated per chain for every draw (iteration >= tune), whatever abd_record and its thin ask for.
+ *
+ * Titer histograms.  Per cell (g, j), for x = ab_n_mu over [lo_n, hi_n) and for x = ab_s_mu over [lo_s, hi_s) (the
+ * Deterministics' titers), ABD_TIMELINE_BINS = 64 counters of 16 bits, all 0 at first.  With inv_w = 62 / (hi - lo) computed
+ * once by the host, a draw adds 1 to bin
+ *       0 if x < lo;   63 if x >= hi or x is NaN;   else 1 + min(61, (int)floor((x - lo) * inv_w))
+ * so that bins 1 .. 62 are 62 interior bins of width w = (hi - lo) / 62.  16-bit counters: planned_draws <= 65535.
+ * Infection timing, integers only.  Per cell two uint32: inf, the draws with i[g, j] = 1, and cum, the draws with i[g', j] = 1
+ * for some g' <= g in the same chunk as g (chunk borders 0, splits..., n_gaps of abd_desc; no splits: one chunk).  Per
+ * individual ninf[8], uint32: the draws by the number of infections at gaps <= last[j], [7] pooling 7 and more; last is the
+ * context's follow-up (abd_set_follow_up) at the time of each draw, n_gaps - 1 without one, and the row of a never-followed
+ * individual (last = -1) stays 0.  The cell planes ignore the follow-up.
+ * That is 264 bytes per cell and chain.  A cell belongs to one lane, a chain has its own planes, the update is a plain
+ * read-modify-write: there are no atomics of any kind and the result is bit-reproducible -- it depends on the draws alone, not
+ * on the launch shape, on how the run is cut into calls, on abd_record or on thin.  No random numbers are drawn: the
+ * trajectories do not change.
+ *
+ * Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it).  planned_draws = 0 releases the buffers;
+ * planned_draws negative or above ABD_TIMELINE_MAX_DRAWS, or planned_draws > 0 with a range that is not finite and ascending
+ * (lo < hi, hi - lo finite): ABD_ERR_ARG.  ABD_ERR_NOMEM, the message naming the bytes, when the device cannot hold them (about
+ * 0.5 GB per chain at 10 000 x 200).  A run call whose draws would pass planned_draws fails with ABD_ERR_STATE before anything is
+ * launched. */
+#define ABD_TIMELINE_BINS 64
+#define ABD_TIMELINE_MAX_DRAWS 65535
+#define ABD_TIMELINE_MAX_Q 8
+#define ABD_TIMELINE_NINF 8
+int abd_sampler_enable_timelines(abd_sampler* s, int64_t planned_draws, double lo_n, double hi_n, double lo_s, double hi_s);
+/* The counters of chain k (0 <= k < n) over its draws so far, gap-major like the Deterministics: hist_n and hist_s
+ * [G][N][64] uint16, inf and cum [G][N] (widened to int64), ninf [N][8] (widened to int64); *n_draws the number of draws.  Any
+ * pointer may be NULL.  May be called between run calls.  ABD_ERR_STATE ("not enabled") without abd_sampler_enable_timelines. */
+int abd_sampler_timelines(abd_sampler* s, int32_t k, uint16_t* hist_n, uint16_t* hist_s, int64_t* inf, int64_t* cum, int64_t* ninf,
+                          int64_t* n_draws);
+/* Quantiles of the titers per cell from the histograms POOLED over the sampler's chains (32-bit sums), computed on the device:
+ * 8 bytes per quantile and cell reach the host instead of 128 per chain and cell.  1 <= n_q <= ABD_TIMELINE_MAX_Q, each q in
+ * [0, 1] (else ABD_ERR_ARG); out_n and out_s are [n_q][G][N], either may be NULL.  With c[0..63] a cell's pooled counts, C
+ * their inclusive cumulative sums and n their total:  n = 0 gives NaN;  else t = q n and b the smallest bin with c[b] > 0
+ * and C[b] >= t:  b = 0 gives lo,  b = 63 gives hi,  else  lo + w ((b - 1) + (t - C[b-1]) / c[b])
+ * (abdpymc_amd/timelines.py: quantiles is the same definition as NumPy). */
+int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q, double* out_n, double* out_s);
 /* Current diagonal of M^-1 (17) and step size of chain k; `metric` (17 x 17, may be NULL) receives the full
  * M^-1 (the diagonal matrix when the metric is diagonal). */
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);

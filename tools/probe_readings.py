@@ -4,13 +4,17 @@ Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals 
 predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the epidemic curves of every draw (``--leg curves``:
 sample(..., curves=True); not a per-reading output, but the same question) or the per-cell convergence accumulators
 (``--leg diagnostics``: sample(..., diagnostics=True); likewise) or the infection-risk-by-titer table of every draw (``--leg
-risk``: sample(..., risk=spec) with 7 edges per antigen, the whole window, first infections only; likewise), alternated.  With two run lengths (``--draws 100 400``) the
+risk``: sample(..., risk=spec) with 7 edges per antigen, the whole window, first infections only; likewise) or the per-individual
+timelines (``--leg timelines``: sample(..., timelines=True) over the default ranges, with the device's quantile read-out at the end
+of the run; likewise), alternated.  With two run lengths (``--draws 100 400``) the
 fixed (per run) and per-draw costs separate.  ``--profile`` runs one short sample with both on, for
 ``rocprofv3 --kernel-trace --stats -- python tools/probe_readings.py --profile``: the kernel's own time per draw and chain of
 each op (abd_readings_dense_kernel<LogLik, ...>, <Predictive, ...>) in the same run; with ``--leg curves`` the short sample has
 the curves on instead (abd_curves_kernel, abd_curves_sum_kernel beside abd_deterministics_kernel with its running sums), with
 ``--leg diagnostics`` the accumulators (abd_diag_kernel beside the same), with ``--leg risk`` the risk table AND the curves
-(abd_risk_kernel, abd_risk_sum_kernel beside abd_curves_kernel, abd_curves_sum_kernel: the two walk the same words).  Prints
+(abd_risk_kernel, abd_risk_sum_kernel beside abd_curves_kernel, abd_curves_sum_kernel: the two walk the same words), with
+``--leg timelines`` the timelines AND the convergence accumulators (abd_timeline_kernel beside abd_diag_kernel, the same walker;
+abd_timeline_quantile_kernel is the read-out).  Prints
 one JSON line.
 """
 import argparse
@@ -31,7 +35,7 @@ from abdpymc_amd.sampler import sample  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics", "risk"), default="waic")
+    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics", "risk", "timelines"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
@@ -56,6 +60,8 @@ def main():
         on = {a.leg: True} if a.leg in ("curves", "diagnostics") else dict(waic=True, ppc=True)
         if a.leg == "risk":
             on = dict(curves=True)
+        if a.leg == "timelines":
+            on = dict(timelines=True, diagnostics=True)
         sample(m, draws=a.draws[0], **on, **(leg_kw(True) if a.leg == "risk" else {}), **kw)
         print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on, risk=a.leg == "risk",
                               wall_s=time.perf_counter() - t0)))
