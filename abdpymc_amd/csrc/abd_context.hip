@@ -75,9 +75,30 @@ ChainPar chain_par(const abd_ctx* c, int chain, const Transformed& tr) {
   p.waner = c->slots[chain].waner;
   p.iw = c->slots[chain].iw;
   p.cnt = c->slots[chain].cnt;
+  p.pl = c->slots[chain].pl;
   return p;
 }
 ChainPar chain_par(const abd_ctx* c, int chain, const double* t) { return chain_par(c, chain, transform(t)); }
+
+int enqueue_planes(abd_ctx* c, int m, const int32_t* chains, hipStream_t st, int lg0, int n_lg) {
+  if (!c->dense) return ABD_OK;
+  if (m < 1 || m > ABD_MAX_BATCH_K) return fail(ABD_ERR_STATE, "internal: planes of %d slots in one launch", m);
+  if (n_lg < 0) n_lg = c->n_lg - lg0;
+  if (lg0 < 0 || n_lg < 1 || lg0 + n_lg > c->n_lg) return fail(ABD_ERR_STATE, "internal: planes of lane groups [%d, %d) of %d", lg0, lg0 + n_lg, c->n_lg);
+  PlaneArgs a;
+  std::memset(&a, 0, sizeof a);
+  for (int k = 0; k < m; ++k) {
+    a.src[k] = c->slots[(size_t)chains[k]].iw;
+    a.dst[k] = c->slots[(size_t)chains[k]].pl;
+  }
+  a.N = c->N;
+  a.G = c->G;
+  a.which = 0;
+  a.lg0 = lg0;
+  hipLaunchKernelGGL(abd_planes_kernel, dim3(n_lg, c->nt, m), dim3(64), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return ABD_OK;
+}
 
 ConstrainArgs constrain_args(const abd_ctx* c) {
   ConstrainArgs a;
@@ -507,7 +528,21 @@ int create_slots(abd_ctx* c) {
     HIP_TRY(s.waner.alloc((size_t)c->N));
     HIP_TRY(s.iw.alloc(words));
     HIP_TRY(s.cnt.alloc(2));
+    if (c->dense) {
+      // the planes: zero (padding gaps, and no infections yet), then the static vaccination masks
+      HIP_TRY(s.pl.alloc_zero(abd_plane_words(c->n_lg, c->G), c->stream));
+      PlaneArgs a;
+      std::memset(&a, 0, sizeof a);
+      a.src[0] = c->vw;
+      a.dst[0] = s.pl;
+      a.N = c->N;
+      a.G = c->G;
+      a.which = 1;
+      hipLaunchKernelGGL(abd_planes_kernel, dim3(c->n_lg, c->nt, 1), dim3(64), 0, c->stream, a);
+      HIP_TRY(hipGetLastError());
+    }
   }
+  c->dense_planes = env_int("ABD_DENSE_PLANES", 1) != 0;
   return ABD_OK;
 }
 
@@ -821,6 +856,7 @@ int abd_set_discrete(abd_ctx* c, int32_t chain, const int8_t* i_raw, const int8_
     hipLaunchKernelGGL(abd_constrain_kernel<ABD_MAXT>, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, constrain_args(c), s.rw,
                        s.waner, s.iw, reinterpret_cast<unsigned long long*>(cnt));
   HIP_TRY(hipGetLastError());
+  if (int prc = enqueue_planes(c, 1, &chain, c->stream)) return prc;
   HIP_TRY(hipStreamSynchronize(c->stream));
   s.set = true;
   return ABD_OK;
@@ -843,6 +879,9 @@ int abd_flip_discrete(abd_ctx* c, int32_t chain, int64_t flat) {
     hipLaunchKernelGGL(abd_flip_kernel<ABD_MAXT>, dim3(1), dim3(1), 0, c->stream, constrain_args(c), s.rw, s.waner, s.iw,
                        reinterpret_cast<unsigned long long*>(cnt), c->G, flat);
   HIP_TRY(hipGetLastError());
+  // (a flip of i_raw may move any constrained bit of its individual: that individual's lane group, every word)
+  if (flat < (int64_t)c->G * c->N)
+    if (int prc = enqueue_planes(c, 1, &chain, c->stream, (int)((flat % c->N) / 64), 1)) return prc;
   return ABD_OK;
 }
 int abd_deterministics(abd_ctx* c, int32_t chain, const double* theta, int8_t* i, double* mu_n, double* mu_s) {

@@ -25,7 +25,10 @@
 //   * the chain constants are pre-scaled by c = 1024 b log2(e): t = c (a - x) is fma(-c, x, c a) with
 //     c a = fma(c temp, U, fma(cf, c perm, c init)); the sum for d/db is sum h t (the host divides by c)
 //   * indicator bits -> 0.0 / 1.0 doubles by v_bfe_i32 (scalar bit index) + v_and with the high word of 1.0;
-//     the "exposed so far" flags of perm_response (abd.py:306) are integer ORs of those high words
+//     the "exposed so far" flags of perm_response (abd.py:306) are integer ORs of those high words (legacy form) -- or, in
+//     the plane form (dense_walk_planes; the evaluation kernels), one v_cndmask each on lane masks that arrive by scalar
+//     loads from the slot's exposure planes (abd_planes.hpp), with cf and c init + cf c perm kept in registers and rewritten
+//     only in a gap that exposes a lane for the first time: 58 instead of 64 vector instructions per gap row, same bits
 //   * e^u = 2^(t/1024), t = 1024 e + j + f: T[j] = 2^(j/1024) from a 1024-entry LDS table, a cubic in f,
 //     the exponent e added into T's high word -- the table is pre-biased (abd_types.hpp), so that is hi + (k << 10) of the
 //     clamped k, with no shift to separate e; 1 + 2^t is ONE fma (tools/exp2_table.py: 3.5e-16)
@@ -36,6 +39,7 @@
 #include <cstddef>
 
 #include "abd_device.hpp"
+#include "abd_planes.hpp"
 #include "abd_terms.hpp"
 
 // One {od, log_dilution} pair of a gap row: buffer load with a scalar row offset and a constant per-lane offset.
@@ -151,6 +155,7 @@ __device__ __forceinline__ uint32_t word32(const uint32_t* base, uint32_t j2, in
 #define ABD_EXP2_C2 0x1.ebfbe033445b4p-23
 __device__ __forceinline__ void one_plus_exp2_pair(double t_n, double t_s, const double* tab /* LDS */, double c2v, double& A,
                                                    double& B) {
+#pragma clang fp contract(off)  // (the operations below are the ones issued: see obs_pair_scaled)
   const double kf_n = __builtin_rint(t_n), kf_s = __builtin_rint(t_s);
   const double f_n = t_n - kf_n, f_s = t_s - kf_s;
   int k_n, k_s;
@@ -173,9 +178,13 @@ __device__ __forceinline__ void one_plus_exp2_pair(double t_n, double t_s, const
 
 // Both antigens of one cell at once: the two reciprocals 1/(1+e_n), 1/(1+e_s) come from ONE v_rcp_f64 (quarter
 // rate) of the product -- 1/A = B/(AB), 1/B = A/(AB).  t_n = 1024 log2(e) b_n (a_n - x_n), t_s likewise.
+// The arithmetic is pinned: contraction is off here, in one_plus_exp2_pair and in dense_walk, and every operation is written
+// as the instruction it is (an fma where the sum takes the unrounded product, a multiply or an add where it does not), so
+// that the bits of the 13 sums do not depend on how the compiler cuts the gap loop into blocks.
 template <bool GRAD>
 __device__ __forceinline__ void obs_pair_scaled(double t_n, double yn, double d_n, double t_s, double ys, double d_s,
                                                 const double* tab, double c2v, double (&acc)[16], double& h_n, double& h_s) {
+#pragma clang fp contract(off)
   double A, B;
   one_plus_exp2_pair(t_n, t_s, tab, c2v, A, B);
   const double r = rcp_newton(A * B);
@@ -184,12 +193,12 @@ __device__ __forceinline__ void obs_pair_scaled(double t_n, double yn, double d_
   acc[A_N_Q2] = fma(q_n, q_n, acc[A_N_Q2]);
   acc[A_S_Q2] = fma(q_s, q_s, acc[A_S_Q2]);
   if (GRAD) {
-    const double u_n = q_n * s_n, u_s = q_s * s_s;
-    acc[A_N_QS] += u_n;
-    acc[A_S_QS] += u_s;
+    const double u_n = q_n * s_n, u_s = q_s * s_s;  // (rounded: h is built on it)
+    acc[A_N_QS] = fma(s_n, q_n, acc[A_N_QS]);       // sum q s takes the unrounded product
+    acc[A_S_QS] = fma(s_s, q_s, acc[A_S_QS]);
     h_n = fma(-u_n, s_n, u_n);  // q s (1 - s)
     h_s = fma(-u_s, s_s, u_s);
-    acc[A_N_H] += h_n;
+    acc[A_N_H] += h_n;  // plain adds
     acc[A_S_H] += h_s;
     acc[A_N_HX] = fma(h_n, t_n, acc[A_N_HX]);  // c_n sum h (a - x): the host divides by c_n (abd_context.hip: assemble)
     acc[A_S_HX] = fma(h_s, t_s, acc[A_S_HX]);
@@ -246,7 +255,8 @@ struct PieceLoads {
   int wj;                           // ab_s_waner of the lane's individual
 };
 
-template <typename R, bool XC, typename ARGS>
+// WORDS = false: the plane form of the walk, which takes the piece's indicator bits from the exposure planes instead
+template <typename R, bool XC, bool WORDS, typename ARGS>
 __device__ __forceinline__ void piece_issue_loads(const ARGS& a, const RowDesc<XC>& rs_n, const RowDesc<XC>& rs_s,
                                                   const uint32_t* ibase, const uint32_t* vbase, const int8_t* waner, int lane, int j,
                                                   int g0, int g1, PieceLoads<R, XC>& pl) {
@@ -266,13 +276,15 @@ __device__ __forceinline__ void piece_issue_loads(const ARGS& a, const RowDesc<X
     pl.on = row_load<R, XC>(rs_n, lane, ro, N);
     pl.os = row_load<R, XC>(rs_s, lane, ro, N);
   }
-  const uint32_t j2 = 2u * (uint32_t)j;
-  pl.seg_i = word32(ibase, j2, q, N);
-  pl.seg_v = word32(vbase, j2, q, N);
-  pl.nxt_i = pl.nxt_v = 0;
-  if (q < q_end) {
-    pl.nxt_i = word32(ibase, j2, q + 1, N);
-    pl.nxt_v = word32(vbase, j2, q + 1, N);
+  pl.seg_i = pl.seg_v = pl.nxt_i = pl.nxt_v = 0;
+  if constexpr (WORDS) {
+    const uint32_t j2 = 2u * (uint32_t)j;
+    pl.seg_i = word32(ibase, j2, q, N);
+    pl.seg_v = word32(vbase, j2, q, N);
+    if (q < q_end) {
+      pl.nxt_i = word32(ibase, j2, q + 1, N);
+      pl.nxt_v = word32(vbase, j2, q + 1, N);
+    }
   }
   pl.wj = waner[j];
 }
@@ -365,6 +377,7 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
                                            uint32_t j2, PieceLoads<R, XC>& pl, int lane, int g0, int g1, bool wj, double tn, double dn, double ts,
                                            double ds, uint32_t cfn_hi, uint32_t cfs_hi, const double* tab_e2, double c2v,
                                            double (&acc)[16]) {
+#pragma clang fp contract(off)  // (covers the step lambda below; e_i + e_v is an add, everything else an explicit fma)
   const int N = a.N;
   const double rho_n = k.rho_n, ct_n = k.ct_n, cp_n = k.cp_n, ci_n = k.ci_n, mc_n = k.mc_n;
   const double c_s = k.c_s, cp_s = k.cp_s, ci_s = k.ci_s, mc_s = k.mc_s, d_n = k.d_n, d_s = k.d_s;
@@ -442,6 +455,109 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
     if (g < g1 && (g & 31) == 0) next_word();
   }
   if (g < g1) step(g, en, es);  // (its word is in place: the loop above changed it, or the piece is this one gap)
+  acc[A_S_HD] += wj ? hd_s : 0.0;  // d rho_j / d rho_s = waner_j
+}
+
+
+// ---- the plane form of the walk (abd_planes.hpp) ----
+// The same arithmetic, operation for operation, with the exposure bookkeeping taken out of the vector unit: the lane masks
+// of the coming pair of gaps arrive by one scalar load (constant address space: loads only), the indicators e_i, e_v are one
+// v_cndmask each on the mask, and cf_n, cf_s with the bases c init + cf c perm are loop-carried registers that are rewritten
+// only in a gap that exposes a lane for the first time -- scalar mask arithmetic and one branch per gap.  The refreshed base
+// is fma(1.0, c perm, c init): the bits the legacy form's fma(cf, c perm, c init) has for cf = 1.
+typedef uint64_t abd_u64x2 __attribute__((ext_vector_type(2)));  // PlaneGap {i, v}
+typedef uint64_t abd_u64x4 __attribute__((ext_vector_type(4)));  // PlanePair {i, v} of gap g (even), {i, v} of gap g + 1
+static_assert(sizeof(abd_u64x2) == sizeof(PlaneGap) && sizeof(abd_u64x4) == sizeof(PlanePair), "plane layout (abd_types.hpp)");
+typedef const abd_u64x2 __attribute__((address_space(4)))* plane_gap_ptr;
+typedef const abd_u64x4 __attribute__((address_space(4)))* plane_pair_ptr;
+// the plane row of lane group lg (wave-uniform): gap g of it is row[g]
+__device__ __forceinline__ plane_gap_ptr plane_row(const uint64_t* planes, int lg, int G) {
+  return (plane_gap_ptr)(uintptr_t)(planes + abd_plane_index(lg, 0, G, 0));
+}
+__device__ __forceinline__ uint32_t mask_select(uint64_t mask, uint32_t on, uint32_t off) {
+  return __builtin_amdgcn_inverse_ballot_w64(mask) ? on : off;  // v_cndmask_b32 on a scalar mask
+}
+
+template <typename R, bool GRAD, bool XC, typename ARGS>
+__device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChain& k, const RowDesc<XC>& rs_n,
+                                                  const RowDesc<XC>& rs_s, const double* dict_n, const double* dict_s,
+                                                  plane_gap_ptr prow, PieceLoads<R, XC>& pl, int lane, int g0, int g1, bool wj, double tn,
+                                                  double dn, double ts, double ds, uint32_t cfn_hi, uint32_t cfs_hi, ExposureSeen seen,
+                                                  const double* tab_e2, double c2v, double (&acc)[16]) {
+#pragma clang fp contract(off)
+  const int N = a.N;
+  const double rho_n = k.rho_n, ct_n = k.ct_n, mc_n = k.mc_n;
+  const double c_s = k.c_s, mc_s = k.mc_s, d_n = k.d_n, d_s = k.d_s;
+  const double rho_j = wj ? k.rho_s : 1.0;  // abd.py:374
+  double hd_s = 0.0;
+  const uint32_t z_ei = zero_vgpr(), z_ev = zero_vgpr(), z_cn = zero_vgpr(), z_cs = zero_vgpr();
+  // c init + cf c perm for cf = 1 (wave-uniform) and this lane's start value
+  const double b1_n = fma(1.0, k.cp_n, k.ci_n), b1_s = fma(1.0, k.cp_s, k.ci_s);
+  double base_n = cfn_hi ? b1_n : fma(0.0, k.cp_n, k.ci_n), base_s = cfs_hi ? b1_s : fma(0.0, k.cp_s, k.ci_s);
+  const int last = g1 - 1 - g0;
+  auto ldrow = [&](const RowDesc<XC>& rs, int g) { return row_load<R, XC>(rs, lane, min(g - g0, last), N); };
+
+  auto step = [&](uint64_t m_i, uint64_t m_v, const RowData<R, XC>& on, const RowData<R, XC>& os) {
+    // first exposures of this gap (it already counts, abd.py:306): rare, wave-uniform
+    const ExposureSeen nw = abd_exposure_new(seen, m_i, m_v);
+    if ((nw.n | nw.s) != 0) {
+      cfn_hi = mask_select(nw.n, 0x3FF00000u, cfn_hi);
+      cfs_hi = mask_select(nw.s, 0x3FF00000u, cfs_hi);
+      base_n = __hiloint2double((int)mask_select(nw.n, (uint32_t)__double2hiint(b1_n), (uint32_t)__double2hiint(base_n)),
+                                (int)mask_select(nw.n, (uint32_t)__double2loint(b1_n), (uint32_t)__double2loint(base_n)));
+      base_s = __hiloint2double((int)mask_select(nw.s, (uint32_t)__double2hiint(b1_s), (uint32_t)__double2hiint(base_s)),
+                                (int)mask_select(nw.s, (uint32_t)__double2loint(b1_s), (uint32_t)__double2loint(base_s)));
+      abd_exposure_mark(seen, m_i, m_v);
+    }
+    const double e_i = hi_to_double(mask_select(m_i, 0x3FF00000u, 0u), z_ei), e_v = hi_to_double(mask_select(m_v, 0x3FF00000u, 0u), z_ev);
+    dn = fma_s(rho_n, dn, tn);
+    tn = fma_s(rho_n, tn, e_i);
+    ds = fma_v(rho_j, ds, ts);
+    ts = fma_v(rho_j, ts, e_i + e_v);  // unit boosts: temp unused (abd.py:272)
+    const double cf_n = hi_to_double(cfn_hi, z_cn), cf_s = hi_to_double(cfs_hi, z_cs);
+    const double t_n = fma(mc_n, row_x<R, XC>(on, dict_n), fma(ct_n, tn, base_n));
+    const double t_s = fma(mc_s, row_x<R, XC>(os, dict_s), fma(c_s, ts, base_s));
+    double h_n = 0.0, h_s = 0.0;
+    obs_pair_scaled<GRAD>(t_n, row_y<R, XC>(on), d_n, t_s, row_y<R, XC>(os), d_s, tab_e2, c2v, acc, h_n, h_s);
+    if (GRAD) {
+      acc[A_N_HC] = fma(h_n, cf_n, acc[A_N_HC]);
+      acc[A_N_HU] = fma(h_n, tn, acc[A_N_HU]);
+      acc[A_N_HD] = fma(h_n, dn, acc[A_N_HD]);
+      acc[A_S_HC] = fma(h_s, cf_s, acc[A_S_HC]);
+      hd_s = fma(h_s, ds, hd_s);
+      // the next gap's refresh goes behind this gap's last use of cf and the bases, so that it overwrites them in place
+      // (left free, the compiler keeps the values from before and after a refresh live together and pays in v_mov_b64)
+      asm volatile("" : "+v"(cfn_hi), "+v"(cfs_hi), "+v"(base_n), "+v"(base_s), "+v"(acc[A_N_HC]), "+v"(acc[A_S_HC]));
+    } else {
+      asm volatile("" : "+v"(base_n), "+v"(base_s), "+v"(acc[A_N_Q2]), "+v"(acc[A_S_Q2]));
+    }
+  };
+
+  // rows as in the legacy form: one buffer for the even and one for the odd gaps per antigen, refilled two gaps ahead; the
+  // masks of a pair of gaps are fetched while the pair before it is walked
+  RowData<R, XC> en = pl.en, es = pl.es, on = pl.on, os = pl.os;
+  int g = g0;
+  abd_u64x4 cur = *(plane_pair_ptr)(prow + ((g0 + 1) & ~1));  // (the row is padded: abd_plane_gaps)
+  if (g & 1) {
+    const abd_u64x2 m = prow[g];
+    step(m.x, m.y, on, os);
+    on = ldrow(rs_n, g + 2);
+    os = ldrow(rs_s, g + 2);
+    ++g;
+  }
+  while (g + 1 < g1) {
+    const abd_u64x4 nxt = *(plane_pair_ptr)(prow + g + 2);
+    __builtin_amdgcn_sched_barrier(0);  // (the fetch stays up here: left free it sinks to the end of the pair and is waited for at once)
+    step(cur.x, cur.y, en, es);
+    en = ldrow(rs_n, g + 2);
+    es = ldrow(rs_s, g + 2);
+    step(cur.z, cur.w, on, os);
+    on = ldrow(rs_n, g + 3);
+    os = ldrow(rs_s, g + 3);
+    cur = nxt;
+    g += 2;
+  }
+  if (g < g1) step(cur.x, cur.y, en, es);
   acc[A_S_HD] += wj ? hd_s : 0.0;  // d rho_j / d rho_s = waner_j
 }
 
@@ -657,7 +773,7 @@ __device__ __forceinline__ bool two_level_sums(const double* rows, double* shard
 // The kernel's body for both of its entry points: abd_dense_kernel (EvalArgs: the chains' constants arrive in the kernel
 // arguments, the sums go back to the host) and abd_train_kernel (DenseTrainArgs: a leapfrog-train launch -- the constants
 // of a chain are those of the point its TrainChain holds, and the launch's last workgroup runs the chains' state machines).
-template <typename R, int CB, bool GRAD, bool XC, typename ARGS>
+template <typename R, int CB, bool GRAD, bool XC, bool PL, typename ARGS>
 __device__ __forceinline__ void dense_body(const ARGS& a) {
   constexpr bool TRAINK = is_train_args<ARGS>::value;
   static_assert(CB * ABD_NOUT <= 64, "the own-sum hand-off needs every partial row of the workgroup stored by wave 0");
@@ -697,6 +813,7 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
     p.rw = nullptr;
     p.waner = tc.waner;
     p.iw = tc.iw;
+    p.pl = tc.pl;
     p.cnt = tc.cnt;
     p.perm_n = p.temp_n = p.rho_n = p.init_n = p.perm_s = p.rho_s = p.init_s = p.b_n = p.d_n = p.b_s = p.d_s = 0.0;
     if (chain_on) {
@@ -779,7 +896,7 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
   uint32_t wi[ABD_SW], wv[ABD_SW];  // only a range's first piece can start inside an individual's gaps
   const bool first_inside = rows_left > 0 && j < N && g0 > 0;
   RowDesc<XC> rs_n = row_desc<R, XC>(a, 0, lg, g0), rs_s = row_desc<R, XC>(a, 1, lg, g0);
-  if (rows_left > 0 && j < N) piece_issue_loads<R, XC>(a, rs_n, rs_s, ibase, vbase, p.waner, lane, j, g0, g1, pl);
+  if (rows_left > 0 && j < N) piece_issue_loads<R, XC, !PL>(a, rs_n, rs_s, ibase, vbase, p.waner, lane, j, g0, g1, pl);
   if (first_inside) state_issue_loads(ibase, vbase, 2u * (uint32_t)j, N, g0, wi, wv);
   // sum(i_raw), sum(ab_s_waner) of the chain: kept with the slot's discrete state (Bernoulli(i_raw | p) is on the RAW
   // matrix, abd.py:427; Q2); the first range of a chain carries them into the sums
@@ -834,15 +951,26 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
   ABD_STAMP(5);
   if (first_inside)
     dense_start_state(wi, wv, ibase, vbase, 2u * (uint32_t)j, N, g0, tab_n, tab_s, pl.wj != 0, tn, dn, ts, ds, cfn_hi, cfs_hi);
+  // plane form: the lanes exposed before the first piece, as lane masks (every lane is here; a lane without a start state has 0)
+  ExposureSeen seen = {0, 0};
+  if constexpr (PL) {
+    seen.n = __builtin_amdgcn_ballot_w64(cfn_hi != 0);
+    seen.s = __builtin_amdgcn_ballot_w64(cfs_hi != 0);
+  }
   if (NSUB == 1) __syncthreads();
   ABD_STAMP(6);
 
   while (rows_left > 0) {
     // ---- one piece: lane group lg, gaps [g0, g1) ----
     rows_left -= g1 - g0;
-    if (j < N)
-      dense_walk<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, ibase, vbase, 2u * (uint32_t)j, pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi, cfs_hi, tab_e2, c2v,
-                          acc);
+    if (j < N) {
+      if constexpr (PL)
+        dense_walk_planes<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, plane_row(p.pl, lg, G), pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi,
+                                       cfs_hi, seen, tab_e2, c2v, acc);
+      else
+        dense_walk<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, ibase, vbase, 2u * (uint32_t)j, pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi, cfs_hi,
+                                tab_e2, c2v, acc);
+    }
     if (rows_left <= 0) break;
     // the range goes on at gap 0 of the next lane group, from the zero state
     ++lg;
@@ -851,9 +979,10 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
     j = lg * 64 + lane;
     tn = dn = ts = ds = 0.0;
     cfn_hi = cfs_hi = 0;
+    seen.n = seen.s = 0;
     rs_n = row_desc<R, XC>(a, 0, lg, g0);
     rs_s = row_desc<R, XC>(a, 1, lg, g0);
-    if (j < N) piece_issue_loads<R, XC>(a, rs_n, rs_s, ibase, vbase, p.waner, lane, j, g0, g1, pl);
+    if (j < N) piece_issue_loads<R, XC, !PL>(a, rs_n, rs_s, ibase, vbase, p.waner, lane, j, g0, g1, pl);
   }
 
   ABD_STAMP(7);
@@ -957,16 +1086,28 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
   }
 }
 
-template <typename R, int CB, bool GRAD, bool XC>
+// Which instantiations have a plane form of the walk (PL).  Two conditions.  Resources: the compiler's resource report must
+// show the plane form scratch-free with at most 128 VGPRs and occupancy 4 (tools/resource_usage.py on the build log) -- every
+// instantiation meets that.  Time: the form must not be slower where the instantiation runs -- the train kernels do not meet
+// that: a sampler unit's launch has one wave per SIMD, nothing hides the latency of the scalar mask fetch there (it shares
+// its counter with the LDS reads of the 2^t tables), and NUTS at config 3 went from 130.9 k to 122.7 k leapfrogs/s
+// (profiles/r09/h_ab_driver_train_planes.txt).  They keep the legacy form whatever ABD_DENSE_PLANES says; both forms give
+// the same bits, so which one an instantiation gets never shows in a result.
+template <typename R, int CB, bool GRAD, bool XC, bool TRAIN>
+struct dense_plane_form {
+  static constexpr bool value = !TRAIN;
+};
+
+template <typename R, int CB, bool GRAD, bool XC, bool PL>
 #ifndef ABD_DENSE_MINW
 #define ABD_DENSE_MINW 4
 #endif
 __global__ __launch_bounds__(ABD_BLOCK, ABD_DENSE_MINW) void abd_dense_kernel(const EvalArgs a) {  // 4 waves per SIMD: <= 128 VGPRs
-  dense_body<R, CB, GRAD, XC, EvalArgs>(a);
+  dense_body<R, CB, GRAD, XC, PL, EvalArgs>(a);
 }
 
 // a leapfrog-train launch of a unit of CB chains (abd_train.hpp; abd_sampler.hip)
-template <typename R, int CB, bool XC>
+template <typename R, int CB, bool XC, bool PL>
 __global__ __launch_bounds__(ABD_BLOCK, ABD_DENSE_MINW) void abd_train_kernel(const DenseTrainArgs a) {
-  dense_body<R, CB, true, XC, DenseTrainArgs>(a);
+  dense_body<R, CB, true, XC, PL, DenseTrainArgs>(a);
 }

@@ -22,13 +22,20 @@ size_t table_lds_bytes(int G, int cpw, int red_rows, bool exp2_tab) {
 // The evaluation kernels (abd_dense.hpp, abd_obs.hpp, abd_sparse.hpp) and their instantiations
 enum class Family { Dense, Lanes, Sparse };  // dense panels; observation lists: lane per observation / wave per individual
 using EvalKernel = void (*)(const EvalArgs);
+// planes: the context wants the plane form of the gap loop (ABD_DENSE_PLANES) -- given where the instantiation has one
+template <typename R, int CB, bool GRAD, bool XC>
+EvalKernel dense_kernel(bool planes) {
+  if constexpr (dense_plane_form<R, CB, GRAD, XC, false>::value)
+    if (planes) return abd_dense_kernel<R, CB, GRAD, XC, true>;
+  return abd_dense_kernel<R, CB, GRAD, XC, false>;
+}
 template <typename R, bool GRAD>
-EvalKernel eval_kernel(Family f, int cpw, bool xc, bool wide) {  // wide: more than 256 gaps, 8 words per individual
+EvalKernel eval_kernel(Family f, int cpw, bool xc, bool wide, bool planes) {  // wide: more than 256 gaps, 8 words per individual
   switch (f) {
     case Family::Dense:  // xc: split panels, R + 1 instead of 2 R bytes per cell and antigen
-      if (cpw == 4) return xc ? abd_dense_kernel<R, 4, GRAD, true> : abd_dense_kernel<R, 4, GRAD, false>;
-      if (cpw == 2) return xc ? abd_dense_kernel<R, 2, GRAD, true> : abd_dense_kernel<R, 2, GRAD, false>;
-      return xc ? abd_dense_kernel<R, 1, GRAD, true> : abd_dense_kernel<R, 1, GRAD, false>;
+      if (cpw == 4) return xc ? dense_kernel<R, 4, GRAD, true>(planes) : dense_kernel<R, 4, GRAD, false>(planes);
+      if (cpw == 2) return xc ? dense_kernel<R, 2, GRAD, true>(planes) : dense_kernel<R, 2, GRAD, false>(planes);
+      return xc ? dense_kernel<R, 1, GRAD, true>(planes) : dense_kernel<R, 1, GRAD, false>(planes);
     case Family::Sparse:  // no 4-chain form: it needs 169 VGPRs (2 waves per SIMD) and spills 245 SGPRs (plan_launch caps it at 2)
       if (cpw == 2) return wide ? abd_sparse_kernel<R, 2, GRAD, ABD_MAXT_MAX> : abd_sparse_kernel<R, 2, GRAD, ABD_MAXT>;
       return wide ? abd_sparse_kernel<R, 1, GRAD, ABD_MAXT_MAX> : abd_sparse_kernel<R, 1, GRAD, ABD_MAXT>;
@@ -263,8 +270,9 @@ int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, c
   }
   if (c->timing == 2 && stream_ordered) c->win_launches += steps;  // (abd_kernel_time counts steps)
   const bool f32 = c->storage == ABD_STORE_F32, xc = p.family == Family::Dense && dense_xc(c, p.cpw), wide = c->nt > ABD_MAXT;
-  const EvalKernel k = f32 ? (grad ? eval_kernel<float, true>(p.family, p.cpw, xc, wide) : eval_kernel<float, false>(p.family, p.cpw, xc, wide))
-                           : (grad ? eval_kernel<double, true>(p.family, p.cpw, xc, wide) : eval_kernel<double, false>(p.family, p.cpw, xc, wide));
+  const bool pf = c->dense_planes;
+  const EvalKernel k = f32 ? (grad ? eval_kernel<float, true>(p.family, p.cpw, xc, wide, pf) : eval_kernel<float, false>(p.family, p.cpw, xc, wide, pf))
+                           : (grad ? eval_kernel<double, true>(p.family, p.cpw, xc, wide, pf) : eval_kernel<double, false>(p.family, p.cpw, xc, wide, pf));
   const hipError_t le = profiled_launch(false, [&] { return launch_kernel(k, p.grid, dim3(ABD_BLOCK), p.lds, pp.st, a); });
   if (e1) HIP_TRY(hipEventRecord(e1, pp.st));
   HIP_TRY(le);
@@ -409,11 +417,17 @@ int enqueue_fused(abd_ctx* c, int slot0, int steps, int n, const int32_t* chains
 
 // ---- leapfrog-train launches of dense cohorts (abd_train.hpp; abd_sampler.hip) ----
 using TrainKernel = void (*)(const DenseTrainArgs);
+template <typename R, int CB, bool XC>
+TrainKernel train_kernel_form(bool planes) {
+  if constexpr (dense_plane_form<R, CB, true, XC, true>::value)
+    if (planes) return abd_train_kernel<R, CB, XC, true>;
+  return abd_train_kernel<R, CB, XC, false>;
+}
 template <typename R>
-TrainKernel train_kernel(int cb, bool xc) {
-  if (cb == 4) return xc ? abd_train_kernel<R, 4, true> : abd_train_kernel<R, 4, false>;
-  if (cb == 2) return xc ? abd_train_kernel<R, 2, true> : abd_train_kernel<R, 2, false>;
-  return xc ? abd_train_kernel<R, 1, true> : abd_train_kernel<R, 1, false>;
+TrainKernel train_kernel(int cb, bool xc, bool planes) {
+  if (cb == 4) return xc ? train_kernel_form<R, 4, true>(planes) : train_kernel_form<R, 4, false>(planes);
+  if (cb == 2) return xc ? train_kernel_form<R, 2, true>(planes) : train_kernel_form<R, 2, false>(planes);
+  return xc ? train_kernel_form<R, 1, true>(planes) : train_kernel_form<R, 1, false>(planes);
 }
 
 // Queue one launch of a train unit of cb (1, 2 or 4) chains on pipe pi: a->tc[0 .. cb) filled by the caller, everything
@@ -425,7 +439,7 @@ int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* 
   for (int k = 0; k < cb; ++k) {
     TrainChainArgs& tc = a->tc[k];
     if (tc.action != ABD_TR_SKIP || tc.fwd_slot >= 0) {
-      if (!tc.st || !tc.ring || !tc.iw || !tc.cnt || !tc.waner || (tc.action == ABD_TR_BEGIN && !tc.begin))
+      if (!tc.st || !tc.ring || !tc.iw || !tc.pl || !tc.cnt || !tc.waner || (tc.action == ABD_TR_BEGIN && !tc.begin))
         return fail(ABD_ERR_STATE, "internal: train launch with a NULL pointer for chain %d of the unit", k);
       if ((tc.action == ABD_TR_STEP && (tc.use_slot | 1) != 1) || tc.fwd_slot > 1)
         return fail(ABD_ERR_STATE, "internal: train launch with slot %d / %d for chain %d of the unit", tc.use_slot, tc.fwd_slot, k);
@@ -476,7 +490,7 @@ int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* 
   range_split(c, blocks, ABD_WAVES_PER_BLOCK / cb, *a, false);
   const size_t lds = abd_dense_lds(c->G, cb, xc, true);
   dim3 grid(blocks + a->service, 1);
-  const TrainKernel k = c->storage == ABD_STORE_F32 ? train_kernel<float>(cb, xc) : train_kernel<double>(cb, xc);
+  const TrainKernel k = c->storage == ABD_STORE_F32 ? train_kernel<float>(cb, xc, c->dense_planes) : train_kernel<double>(cb, xc, c->dense_planes);
   const hipError_t le = profiled_launch(false, [&] { return launch_kernel(k, grid, dim3(ABD_BLOCK), lds, c->pipe[pi].st, *a); });
   HIP_TRY(le);
   return ABD_OK;

@@ -69,7 +69,8 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
   const bool stats = stats_dev != nullptr;  // ABD_GIBBS_STATS=1
   const GibbsKernel k = c->storage == ABD_STORE_F32 ? gibbs_kernel<float>(c, stats) : gibbs_kernel<double>(c, stats);
   HIP_TRY(launch_kernel(k, grid, block, lds, st, ga));
-  return ABD_OK;
+  // the sweep rewrote iw (abd_gibbs.hpp: gibbs_store_state): the exposure planes of its chains follow on the same stream
+  return enqueue_planes(c, m, chains, st);
 }
 
 }  // namespace abdi

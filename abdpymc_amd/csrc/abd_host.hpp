@@ -140,6 +140,8 @@ struct ChainSlot {
   // kernels): the constrained infections the evaluation kernels read, and {sum(i_raw), sum(ab_s_waner)}
   DevBuf<uint64_t> iw;     // [nt][N] packed i = constrain(i_raw, pcrpos)   abd.py:640-667
   DevBuf<long long> cnt;   // [2]
+  // dense cohorts: the exposure planes (abd_planes.hpp), transposed from iw by enqueue_planes behind every writer of iw
+  DevBuf<uint64_t> pl;     // [n_lg][abd_plane_gaps(G)][2]
   bool set = false;
 };
 
@@ -217,6 +219,9 @@ struct abd_ctx {
   // 7.2 us per result: config 3, evaluations/s seen by NUTS 33.6 k -> 36.9 k (1 chain), 53 k -> 59 k (8), 77 k -> 88 k (16),
   // unchanged with 4
   bool dense_own_sum = true;
+  // ABD_DENSE_PLANES: the dense and train kernels take the exposure bookkeeping of the gap loop from the slots' planes
+  // (abd_dense.hpp: dense_walk_planes) where the instantiation has a plane form; 0 = the legacy form everywhere.  Same bits.
+  bool dense_planes = true;
   DevBuf<unsigned int> d_fin_count;  // [kMaxPipes][ABD_MAX_BATCH] zeroed counters of that sum
   DevBuf<unsigned int> d_train_count;  // [kMaxPipes][1 + ABD_TRAIN_SHARDS][ABD_TRAIN_CNT_STRIDE] zeroed counters of a dense train launch's count-in (abd_dense.hpp)
   uint32_t ind_offset = 0;  // global index of this context's first individual (Gibbs random streams)
@@ -264,6 +269,9 @@ void assemble(const abd_ctx* c, const HostTerms& h, const double* t, const doubl
 ChainPar chain_par(const abd_ctx* c, int chain, const Transformed& tr);
 ChainPar chain_par(const abd_ctx* c, int chain, const double* t);
 void base_args(const abd_ctx* c, EvalArgs& a);
+// Queue the transpose of iw into the exposure planes of m slots (<= ABD_MAX_BATCH_K) on stream st, behind whatever wrote iw
+// there; n_lg lane groups from lg0 on (n_lg < 0: all).  Nothing to do for a cohort kept as observation lists.
+int enqueue_planes(abd_ctx* c, int m, const int32_t* chains, hipStream_t st, int lg0 = 0, int n_lg = -1);
 #ifdef ABD_STAMPS
 unsigned long long* stamps_buffer();  // diagnostic build: in-kernel s_memrealtime stamps (tools/probe_stamps.py)
 #endif

@@ -997,6 +997,7 @@ int sampler_run_trains(RunFrame& f) {
           tc.ring = d.ring.dev();
           tc.begin = d.begin.dev();
           tc.iw = slot.iw;
+          tc.pl = slot.pl;
           tc.cnt = slot.cnt;
           tc.waner = slot.waner;
           tc.action = ABD_TR_SKIP;

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "abd_device.hpp"
+#include "abd_planes.hpp"
 
 // One wave that stays on the device for `ticks` of the 100 MHz s_memrealtime counter and says when (abd_context.hip:
 // probe_stream_queues -- which of the context's HIP streams can have kernels on the device at the same time)
@@ -104,6 +105,28 @@ __global__ void abd_flip_kernel(const ConstrainArgs a, uint64_t* rw, int8_t* wan
     waner[flat - gn] = w;
     cnt[1] += w ? 1ull : ~0ull;
   }
+}
+
+// Exposure planes (abd_planes.hpp) of up to ABD_MAX_BATCH_K slots from their packed words: 64 x 64-bit tiles transposed with
+// ballots, one wave per (lane group, 64-gap word, slot) -- grid (lane groups from lg0 on, nt, slots).  Launched stream-ordered
+// behind every writer of iw: a writer cannot update the planes itself, since neighbouring individuals share a 64-bit mask
+// and per-individual writers would race.  which = 0: src = iw, the infection masks; 1: src = vw, the vaccination masks.
+struct PlaneArgs {
+  const uint64_t* src[ABD_MAX_BATCH_K];  // [nt][N]
+  uint64_t* dst[ABD_MAX_BATCH_K];        // [n_lg][abd_plane_gaps(G)][2]
+  int32_t N, G, which, lg0;
+};
+__global__ __launch_bounds__(64) void abd_planes_kernel(const PlaneArgs a) {
+  const int lane = threadIdx.x, lg = a.lg0 + (int)blockIdx.x, t = blockIdx.y, k = blockIdx.z;
+  const int j = lg * 64 + lane;
+  const uint64_t w = j < a.N ? a.src[k][(int64_t)t * a.N + j] : 0ull;  // lane = individual
+  uint64_t mine = 0;
+  for (int b = 0; b < 64; ++b) {
+    const uint64_t m = __builtin_amdgcn_ballot_w64(((w >> b) & 1ull) != 0);
+    if (lane == b) mine = m;  // lane = gap
+  }
+  const int g = t * 64 + lane;
+  if (g < a.G) a.dst[k][abd_plane_index(lg, g, a.G, a.which)] = mine;
 }
 
 // Deterministics "i", "ab_n_mu", "ab_s_mu" for one chain, written (G, N) gap-major as PyMC records them;

@@ -178,7 +178,7 @@ ABD_HD void chain_par_from_tr(ChainPar& p, const double* tr) {
   p.b_s = tr[14];
   p.d_s = tr[15];
 }
-static_assert(sizeof(ChainPar) == 11 * sizeof(double) + 4 * sizeof(void*), "ChainPar changed: review chain_par_from_tr (11 constants) and chain_par (4 pointers)");
+static_assert(sizeof(ChainPar) == 11 * sizeof(double) + 5 * sizeof(void*), "ChainPar changed: review chain_par_from_tr (11 constants) and chain_par (5 pointers)");
 
 // ---- the same closed forms, one value variable per caller: lane k of a wave computes what belongs to theta[k] ----
 // (abd_dense.hpp: a leapfrog train's launch assembles its own result; a serial pass over the 17 variables costs one lane

@@ -51,6 +51,23 @@ struct ChainPar {
   // like rw, and {sum(i_raw), sum(ab_s_waner)}
   const uint64_t* iw;
   const long long* cnt;
+  // dense cohorts: the slot's exposure planes (PlaneGap below), refreshed stream-ordered behind every writer of iw; read by
+  // the dense and train kernels only (everything else reads iw); nullptr for a cohort kept as observation lists
+  const uint64_t* pl;
+};
+
+// ---- exposure planes (abd_planes.hpp) ----
+// Per chain slot, beside iw: [lane group][abd_plane_gaps(G)] of PlaneGap -- for every (64-individual lane group, gap) the
+// 64-bit lane mask of the constrained infections (bit l: individual 64 lg + l) with the vaccination mask of the same cell
+// beside it, so that the gap loop fetches the four masks of a pair of gaps (PlanePair: g even) with one 32-byte scalar
+// load.  Rows are padded to an even number of gaps plus one pair of zeros (the loop fetches one pair ahead).  The infection
+// masks are rewritten by abd_planes_kernel (abd_small.hpp) behind abd_constrain_kernel, abd_flip_kernel and the sweeps;
+// the vaccination masks are static and written when the slot is created.  0.5 MB per slot at 10 000 x 200.
+struct alignas(16) PlaneGap {
+  uint64_t i, v;
+};
+struct alignas(32) PlanePair {
+  PlaneGap a, b;  // gaps g (even) and g + 1
 };
 
 // ---- leapfrog trains (abd_dense.hpp: train_epilogue; abd_sampler.hip) ----
@@ -135,6 +152,7 @@ struct TrainChainArgs {      // one chain of a train launch
   const uint64_t* iw;        // the chain slot's discrete state (ChainPar)
   const long long* cnt;
   const int8_t* waner;
+  const uint64_t* pl;        // ... and its exposure planes
   int32_t action;            // ABD_TR_*
   int32_t use_slot;          // STEP: the point is st->pt[use_slot]; the next one goes to pt[use_slot ^ 1]
   int32_t own;               // STEP: the launch writes the step's record itself (nothing queued behind it would pass it on)
@@ -234,6 +252,8 @@ struct EvalArgs {
   ChainPar ch[ABD_MAX_BATCH_K];
   TrainArgs train;  // observation-list kernel, one chain per launch (abd_sampler.hip: list trains)
 };
+// kernel arguments travel in one 4 KiB segment (ABD_MAX_BATCH_K ChainPar are the bulk of EvalArgs)
+static_assert(sizeof(EvalArgs) <= 4096 && sizeof(DenseTrainArgs) <= 4096, "kernel arguments exceed the 4 KiB argument segment");
 
 // row / G of the dense kernel's range arithmetic (abd_dense.hpp: range_of) by a 32-bit reciprocal: magic = ceil(2^32 / G),
 // row / G = (row * magic) >> 32.  With e = magic G - 2^32 (0 <= e < G) the quotient is exact as long as row e < 2^32;

@@ -555,6 +555,8 @@ int abd_n_pipes(abd_ctx* ctx);
  *   ABD_OBS_LANES        by list density     observation lists: 1 = lane-per-observation kernel, 0 = wave-per-individual
  *   ABD_FORCE_SPARSE     0                   1 = keep a dense panel as observation lists (exercises the list kernels)
  *   ABD_DENSE_OWN_SUM    1                   0 = a sampler unit's launch is summed by a second launch (same bits; no leapfrog trains then)
+ *   ABD_DENSE_PLANES     1                   0 = the dense and train kernels keep the exposure bookkeeping of the gap loop in the
+ *                                            vector unit (legacy form) instead of reading the slots' exposure planes (same bits)
  *   ABD_SAMPLER_THREADS  1 dense / 4 lists   host threads that drive the native sampler's units (<= 8 are used)
  *   ABD_SAMPLER_UNIT     by cohort           chains per independent unit of the native sampler (dense: 1 up to 4 chains, 2 up to 7,
  *                                            4 beyond; 1, 2 or 4)
