@@ -27,8 +27,13 @@
 //   * indicator bits -> 0.0 / 1.0 doubles by v_bfe_i32 (scalar bit index) + v_and with the high word of 1.0;
 //     the "exposed so far" flags of perm_response (abd.py:306) are integer ORs of those high words (legacy form) -- or, in
 //     the plane form (dense_walk_planes; the evaluation kernels), one v_cndmask each on lane masks that arrive by scalar
-//     loads from the slot's exposure planes (abd_planes.hpp), with cf and c init + cf c perm kept in registers and rewritten
+//     loads from the slot's exposure planes (abd_planes.hpp), with c init + cf c perm kept in registers and rewritten
 //     only in a gap that exposes a lane for the first time: 58 instead of 64 vector instructions per gap row, same bits
+//   * the perm sums (sum h cf) are not taken gap by gap: per lane and piece they are a difference of the running H sum,
+//     taken in the accumulator itself at the piece's ends and in the gap of a first exposure (abd_planes.hpp: abd_hc_open /
+//     abd_hc_close); the S boost e_i + e_v in {0, 1, 2} is two v_cndmask on the high word (abd_s_boost_hi) instead of an
+//     fp64 add: 56 vector instructions per gap row, 45 of them at the fp64 rate.  The evaluation kernels only; the train
+//     kernels keep the gap-by-gap fma (dense_body)
 //   * e^u = 2^(t/1024), t = 1024 e + j + f: T[j] = 2^(j/1024) from a 1024-entry LDS table, a cubic in f,
 //     the exponent e added into T's high word -- the table is pre-biased (abd_types.hpp), so that is hi + (k << 10) of the
 //     clamped k, with no shift to separate e; 1 + 2^t is ONE fma (tools/exp2_table.py: 3.5e-16)
@@ -370,7 +375,10 @@ __device__ __forceinline__ void dense_start_state(uint32_t (&wi)[ABD_SW], uint32
 }
 
 // Walk gaps [g0, g1) of lane group lg: recurrence form (abd.py:288) + likelihood terms into acc.
-template <typename R, bool GRAD, bool XC, typename ARGS>
+// HCD: the perm sums A_N_HC / A_S_HC as differences of the H sums (abd_planes.hpp: abd_hc_open / abd_hc_close) -- the form of
+// the evaluation kernels, the same bits as the plane form's; without it the sums are taken gap by gap as fma(h, cf, .), the
+// form the train kernels keep (dense_body).  The two agree to rounding, not bit for bit.
+template <typename R, bool GRAD, bool XC, bool HCD, typename ARGS>
 __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, const RowDesc<XC>& rs_n,
                                            const RowDesc<XC>& rs_s, const double* dict_n, const double* dict_s,
                                            const uint32_t* ibase, const uint32_t* vbase,
@@ -384,6 +392,10 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
   const double rho_j = wj ? k.rho_s : 1.0;  // abd.py:374
   double hd_s = 0.0;
   const uint32_t z_ei = zero_vgpr(), z_ev = zero_vgpr(), z_cn = zero_vgpr(), z_cs = zero_vgpr();
+  if constexpr (GRAD && HCD) {  // step 1: a lane exposed before the piece
+    acc[A_N_HC] = abd_hc_open(acc[A_N_HC], acc[A_N_H], cfn_hi != 0);
+    acc[A_S_HC] = abd_hc_open(acc[A_S_HC], acc[A_S_H], cfs_hi != 0);
+  }
   const int last = g1 - 1 - g0;
   // gap rows through buffer loads: descriptor base = the piece's first row of this lane group, scalar offset = row
   // within the piece, vector offset = the lane's constant -- no vector address arithmetic at all
@@ -408,6 +420,13 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
     const uint32_t ei_hi = (uint32_t)__builtin_amdgcn_sbfe((int)seg_i, bit, 1u) & 0x3FF00000u;
     const uint32_t ev_hi = (uint32_t)__builtin_amdgcn_sbfe((int)seg_v, bit, 1u) & 0x3FF00000u;
     const double e_i = hi_to_double(ei_hi, z_ei), e_v = hi_to_double(ev_hi, z_ev);
+    if constexpr (GRAD && HCD) {  // step 2: the lanes this gap exposes for the first time (rare: one wave-uniform test)
+      const bool first_n = (ei_hi & ~cfn_hi) != 0, first_s = ((ei_hi | ev_hi) & ~cfs_hi) != 0;
+      if (__builtin_amdgcn_ballot_w64(first_n | first_s) != 0) {  // (a dose may come before the first infection)
+        acc[A_N_HC] = abd_hc_open(acc[A_N_HC], acc[A_N_H], first_n);
+        acc[A_S_HC] = abd_hc_open(acc[A_S_HC], acc[A_S_H], first_s);
+      }
+    }
     cfn_hi |= ei_hi;
     cfs_hi |= ei_hi | ev_hi;
     dn = fma_s(rho_n, dn, tn);
@@ -421,10 +440,10 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
     double h_n = 0.0, h_s = 0.0;
     obs_pair_scaled<GRAD>(t_n, row_y<R, XC>(on), d_n, t_s, row_y<R, XC>(os), d_s, tab_e2, c2v, acc, h_n, h_s);
     if (GRAD) {
-      acc[A_N_HC] = fma(h_n, cf_n, acc[A_N_HC]);
+      if constexpr (!HCD) acc[A_N_HC] = fma(h_n, cf_n, acc[A_N_HC]);
       acc[A_N_HU] = fma(h_n, tn, acc[A_N_HU]);
       acc[A_N_HD] = fma(h_n, dn, acc[A_N_HD]);
-      acc[A_S_HC] = fma(h_s, cf_s, acc[A_S_HC]);
+      if constexpr (!HCD) acc[A_S_HC] = fma(h_s, cf_s, acc[A_S_HC]);
       hd_s = fma(h_s, ds, hd_s);
     }
   };
@@ -455,16 +474,22 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
     if (g < g1 && (g & 31) == 0) next_word();
   }
   if (g < g1) step(g, en, es);  // (its word is in place: the loop above changed it, or the piece is this one gap)
+  if constexpr (GRAD && HCD) {  // step 3: a lane exposed by the piece's end
+    acc[A_N_HC] = abd_hc_close(acc[A_N_HC], acc[A_N_H], cfn_hi != 0);
+    acc[A_S_HC] = abd_hc_close(acc[A_S_HC], acc[A_S_H], cfs_hi != 0);
+  }
   acc[A_S_HD] += wj ? hd_s : 0.0;  // d rho_j / d rho_s = waner_j
 }
 
 
 // ---- the plane form of the walk (abd_planes.hpp) ----
 // The same arithmetic, operation for operation, with the exposure bookkeeping taken out of the vector unit: the lane masks
-// of the coming pair of gaps arrive by one scalar load (constant address space: loads only), the indicators e_i, e_v are one
-// v_cndmask each on the mask, and cf_n, cf_s with the bases c init + cf c perm are loop-carried registers that are rewritten
-// only in a gap that exposes a lane for the first time -- scalar mask arithmetic and one branch per gap.  The refreshed base
-// is fma(1.0, c perm, c init): the bits the legacy form's fma(cf, c perm, c init) has for cf = 1.
+// of the coming pair of gaps arrive by one scalar load (constant address space: loads only), the indicator e_i is one
+// v_cndmask on the mask and the S boost e_i + e_v two (on m_i | m_v and m_i & m_v), and the bases c init + cf c perm are
+// loop-carried registers that are rewritten only in a gap that exposes a lane for the first time -- scalar mask arithmetic
+// and one branch per gap.  The refreshed base is fma(1.0, c perm, c init): the bits the legacy form's fma(cf, c perm, c init)
+// has for cf = 1.  cf itself is not kept: the perm sums it weighted are differences of the H sums (abd_planes.hpp), opened in
+// the same rare branch.  (Always the difference form: the legacy form with HCD gives the same bits.)
 typedef uint64_t abd_u64x2 __attribute__((ext_vector_type(2)));  // PlaneGap {i, v}
 typedef uint64_t abd_u64x4 __attribute__((ext_vector_type(4)));  // PlanePair {i, v} of gap g (even), {i, v} of gap g + 1
 static_assert(sizeof(abd_u64x2) == sizeof(PlaneGap) && sizeof(abd_u64x4) == sizeof(PlanePair), "plane layout (abd_types.hpp)");
@@ -482,18 +507,23 @@ template <typename R, bool GRAD, bool XC, typename ARGS>
 __device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChain& k, const RowDesc<XC>& rs_n,
                                                   const RowDesc<XC>& rs_s, const double* dict_n, const double* dict_s,
                                                   plane_gap_ptr prow, PieceLoads<R, XC>& pl, int lane, int g0, int g1, bool wj, double tn,
-                                                  double dn, double ts, double ds, uint32_t cfn_hi, uint32_t cfs_hi, ExposureSeen seen,
-                                                  const double* tab_e2, double c2v, double (&acc)[16]) {
+                                                  double dn, double ts, double ds, ExposureSeen seen, const double* tab_e2, double c2v,
+                                                  double (&acc)[16]) {
 #pragma clang fp contract(off)
   const int N = a.N;
   const double rho_n = k.rho_n, ct_n = k.ct_n, mc_n = k.mc_n;
   const double c_s = k.c_s, mc_s = k.mc_s, d_n = k.d_n, d_s = k.d_s;
   const double rho_j = wj ? k.rho_s : 1.0;  // abd.py:374
   double hd_s = 0.0;
-  const uint32_t z_ei = zero_vgpr(), z_ev = zero_vgpr(), z_cn = zero_vgpr(), z_cs = zero_vgpr();
+  const uint32_t z_ei = zero_vgpr(), z_eb = zero_vgpr();
   // c init + cf c perm for cf = 1 (wave-uniform) and this lane's start value
   const double b1_n = fma(1.0, k.cp_n, k.ci_n), b1_s = fma(1.0, k.cp_s, k.ci_s);
-  double base_n = cfn_hi ? b1_n : fma(0.0, k.cp_n, k.ci_n), base_s = cfs_hi ? b1_s : fma(0.0, k.cp_s, k.ci_s);
+  const bool before_n = __builtin_amdgcn_inverse_ballot_w64(seen.n), before_s = __builtin_amdgcn_inverse_ballot_w64(seen.s);
+  double base_n = before_n ? b1_n : fma(0.0, k.cp_n, k.ci_n), base_s = before_s ? b1_s : fma(0.0, k.cp_s, k.ci_s);
+  if constexpr (GRAD) {  // step 1 of the perm sums (abd_planes.hpp): a lane exposed before the piece
+    acc[A_N_HC] = abd_hc_open(acc[A_N_HC], acc[A_N_H], before_n);
+    acc[A_S_HC] = abd_hc_open(acc[A_S_HC], acc[A_S_H], before_s);
+  }
   const int last = g1 - 1 - g0;
   auto ldrow = [&](const RowDesc<XC>& rs, int g) { return row_load<R, XC>(rs, lane, min(g - g0, last), N); };
 
@@ -501,34 +531,35 @@ __device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChai
     // first exposures of this gap (it already counts, abd.py:306): rare, wave-uniform
     const ExposureSeen nw = abd_exposure_new(seen, m_i, m_v);
     if ((nw.n | nw.s) != 0) {
-      cfn_hi = mask_select(nw.n, 0x3FF00000u, cfn_hi);
-      cfs_hi = mask_select(nw.s, 0x3FF00000u, cfs_hi);
+      if constexpr (GRAD) {  // step 2: before this gap's h is added
+        acc[A_N_HC] = abd_hc_open(acc[A_N_HC], acc[A_N_H], __builtin_amdgcn_inverse_ballot_w64(nw.n));
+        acc[A_S_HC] = abd_hc_open(acc[A_S_HC], acc[A_S_H], __builtin_amdgcn_inverse_ballot_w64(nw.s));
+      }
       base_n = __hiloint2double((int)mask_select(nw.n, (uint32_t)__double2hiint(b1_n), (uint32_t)__double2hiint(base_n)),
                                 (int)mask_select(nw.n, (uint32_t)__double2loint(b1_n), (uint32_t)__double2loint(base_n)));
       base_s = __hiloint2double((int)mask_select(nw.s, (uint32_t)__double2hiint(b1_s), (uint32_t)__double2hiint(base_s)),
                                 (int)mask_select(nw.s, (uint32_t)__double2loint(b1_s), (uint32_t)__double2loint(base_s)));
       abd_exposure_mark(seen, m_i, m_v);
     }
-    const double e_i = hi_to_double(mask_select(m_i, 0x3FF00000u, 0u), z_ei), e_v = hi_to_double(mask_select(m_v, 0x3FF00000u, 0u), z_ev);
+    const double e_i = hi_to_double(mask_select(m_i, 0x3FF00000u, 0u), z_ei);
+    // e_i + e_v in {0, 1, 2} by two selects on scalar masks (abd_planes.hpp: abd_s_boost_hi), no fp64 add
+    const double e_b = hi_to_double(abd_s_boost_hi(__builtin_amdgcn_inverse_ballot_w64(m_i | m_v), __builtin_amdgcn_inverse_ballot_w64(m_i & m_v)), z_eb);
     dn = fma_s(rho_n, dn, tn);
     tn = fma_s(rho_n, tn, e_i);
     ds = fma_v(rho_j, ds, ts);
-    ts = fma_v(rho_j, ts, e_i + e_v);  // unit boosts: temp unused (abd.py:272)
-    const double cf_n = hi_to_double(cfn_hi, z_cn), cf_s = hi_to_double(cfs_hi, z_cs);
+    ts = fma_v(rho_j, ts, e_b);  // unit boosts: temp unused (abd.py:272)
     const double t_n = fma(mc_n, row_x<R, XC>(on, dict_n), fma(ct_n, tn, base_n));
     const double t_s = fma(mc_s, row_x<R, XC>(os, dict_s), fma(c_s, ts, base_s));
     double h_n = 0.0, h_s = 0.0;
     obs_pair_scaled<GRAD>(t_n, row_y<R, XC>(on), d_n, t_s, row_y<R, XC>(os), d_s, tab_e2, c2v, acc, h_n, h_s);
     if (GRAD) {
-      acc[A_N_HC] = fma(h_n, cf_n, acc[A_N_HC]);
+      // (nothing is pinned at the end of a gradient gap: with cf out of the loop the compiler overwrites the bases and the
+      // perm sums in place by itself, and an empty asm that names the perm sums or the H sums here brings v_mov back: DESIGN 4.1)
       acc[A_N_HU] = fma(h_n, tn, acc[A_N_HU]);
       acc[A_N_HD] = fma(h_n, dn, acc[A_N_HD]);
-      acc[A_S_HC] = fma(h_s, cf_s, acc[A_S_HC]);
       hd_s = fma(h_s, ds, hd_s);
-      // the next gap's refresh goes behind this gap's last use of cf and the bases, so that it overwrites them in place
-      // (left free, the compiler keeps the values from before and after a refresh live together and pays in v_mov_b64)
-      asm volatile("" : "+v"(cfn_hi), "+v"(cfs_hi), "+v"(base_n), "+v"(base_s), "+v"(acc[A_N_HC]), "+v"(acc[A_S_HC]));
     } else {
+      // the next gap's refresh goes behind this gap's last use of the bases, so that it overwrites them in place
       asm volatile("" : "+v"(base_n), "+v"(base_s), "+v"(acc[A_N_Q2]), "+v"(acc[A_S_Q2]));
     }
   };
@@ -558,6 +589,10 @@ __device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChai
     g += 2;
   }
   if (g < g1) step(cur.x, cur.y, en, es);
+  if constexpr (GRAD) {  // step 3: a lane exposed by the piece's end
+    acc[A_N_HC] = abd_hc_close(acc[A_N_HC], acc[A_N_H], __builtin_amdgcn_inverse_ballot_w64(seen.n));
+    acc[A_S_HC] = abd_hc_close(acc[A_S_HC], acc[A_S_H], __builtin_amdgcn_inverse_ballot_w64(seen.s));
+  }
   acc[A_S_HD] += wj ? hd_s : 0.0;  // d rho_j / d rho_s = waner_j
 }
 
@@ -965,10 +1000,10 @@ __device__ __forceinline__ void dense_body(const ARGS& a) {
     rows_left -= g1 - g0;
     if (j < N) {
       if constexpr (PL)
-        dense_walk_planes<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, plane_row(p.pl, lg, G), pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi,
-                                       cfs_hi, seen, tab_e2, c2v, acc);
+        dense_walk_planes<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, plane_row(p.pl, lg, G), pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, seen,
+                                       tab_e2, c2v, acc);
       else
-        dense_walk<R, GRAD, XC>(a, kc, rs_n, rs_s, dict_n, dict_s, ibase, vbase, 2u * (uint32_t)j, pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi, cfs_hi,
+        dense_walk<R, GRAD, XC, !TRAINK>(a, kc, rs_n, rs_s, dict_n, dict_s, ibase, vbase, 2u * (uint32_t)j, pl, lane, g0, g1, pl.wj != 0, tn, dn, ts, ds, cfn_hi, cfs_hi,
                                 tab_e2, c2v, acc);
     }
     if (rows_left <= 0) break;

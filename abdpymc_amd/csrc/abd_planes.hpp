@@ -8,8 +8,9 @@
 // masks of a pair of gaps with one wide scalar load and keeps "exposed so far" as two lane masks in scalar registers.
 //
 // Here: the layout's index functions, the tile transpose as a reference loop (the device does it with ballots:
-// abd_small.hpp: abd_planes_kernel), and the exposure bookkeeping of one gap in plain C++ -- the same functions run in the
-// kernel and in tests/native/planes_harness.cpp.
+// abd_small.hpp: abd_planes_kernel), the exposure bookkeeping of one gap and the steps that turn the running H sums into
+// the perm sums in plain C++ -- the same functions run in the kernel and in tests/native/planes_harness.cpp,
+// tests/native/hc_sum_harness.cpp.
 #pragma once
 
 #include "abd_types.hpp"
@@ -65,4 +66,30 @@ __host__ __device__ inline ExposureSeen abd_exposure_new(const ExposureSeen& see
 __host__ __device__ inline void abd_exposure_mark(ExposureSeen& seen, uint64_t m_i, uint64_t m_v) {
   seen.n |= m_i;
   seen.s |= m_i | m_v;
+}
+
+// ---- the perm sums from the H sums (abd_terms.hpp: A_N_HC, A_S_HC) ----
+// sum over a piece's gaps of h cf, cf = "exposed so far" in {0, 1}, is per lane the lane's H sum over the gaps from its first
+// exposure on: H at the piece's end minus H just before the first-exposure gap's h was added.  The difference is taken in the
+// HC accumulator itself, with H the running accumulator (it goes on across the pieces of a range), in three steps:
+//   1. piece start:  a lane exposed before the piece            HC <- HC - H      (abd_hc_open)
+//   2. the gap of a lane's first exposure inside the piece,
+//      before that gap's h is added                              HC <- HC - H      (abd_hc_open)
+//   3. piece end:    a lane exposed by then                      HC <- HC + H      (abd_hc_close)
+// Each is one rounded fp64 add under a lane select; a lane that is never exposed keeps HC as it was (exactly 0.0 from zero).
+// Both forms of the gap loop and tests/native/hc_sum_harness.cpp call these.
+__host__ __device__ inline double abd_hc_open(double hc, double H, bool lane_on) {
+  const double d = hc - H;
+  return lane_on ? d : hc;
+}
+__host__ __device__ inline double abd_hc_close(double hc, double H, bool lane_on) {
+  const double d = hc + H;
+  return lane_on ? d : hc;
+}
+
+// High word of the S boost e_i + e_v in {0.0, 1.0, 2.0} (unit boosts, abd.py:272) from "either" and "both" of the gap's
+// infection and vaccination indicators (the low word is zero): two selects instead of an fp64 add, the same double bit for bit.
+__host__ __device__ inline uint32_t abd_s_boost_hi(bool either, bool both) {
+  const uint32_t one = either ? 0x3FF00000u : 0u;
+  return both ? 0x40000000u : one;
 }
