@@ -596,20 +596,39 @@ int create_pipes(abd_ctx* c) {
 
 }  // namespace
 
+namespace {
+
+// The walk's fields of chain slot `chain` at theta: the only place ChainPar is copied into them
+CellWalk cell_walk(const abd_ctx* c, int chain, const double* theta) {
+  const ChainPar p = chain_par(c, chain, theta);
+  CellWalk w;
+  w.vw = c->vw, w.iw = p.iw, w.waner = p.waner, w.last = c->d_last;
+  w.rho_n = p.rho_n, w.rho_s = p.rho_s, w.init_n = p.init_n, w.perm_n = p.perm_n, w.temp_n = p.temp_n;
+  w.init_s = p.init_s, w.perm_s = p.perm_s;
+  w.G = c->G, w.N = c->N, w.nt = c->nt;
+  return w;
+}
+
+// who takes a workgroup's share of a cell kernel (abd_cells.hpp): a wave an individual, or the workgroup a slab of them.
+// Either way at most 8 workgroups per CU, and no result depends on the grid.
+enum class CellGrid { Individuals, Slabs };
+
+// One launch of a cell kernel on stream st: `narrow` for cohorts of up to ABD_MAXT words of gaps, `wide` beyond;
+// own_lds bytes of dynamic LDS behind the power tables
+template <typename K, typename... A>
+int launch_cells(const abd_ctx* c, K narrow, K wide, CellGrid grid, size_t own_lds, hipStream_t st, const A&... args) {
+  const int shares = grid == CellGrid::Slabs ? abd_curves_slabs(c->N) : (c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK;
+  const int blocks = std::max(1, std::min(shares, c->n_cu * 8));
+  HIP_TRY(launch_kernel(c->nt > ABD_MAXT ? wide : narrow, dim3(blocks), dim3(ABD_BLOCK), cell_tables_bytes(c->G) + own_lds, st, args...));
+  return ABD_OK;
+}
+
+}  // namespace
+
 int launch_deterministics(abd_ctx* c, int chain, const double* theta, hipStream_t st, int8_t* out_i, double* out_mun, double* out_mus,
                           double* sums) {
-  EvalArgs a;
-  base_args(c, a);
-  a.n_chains = 1;
-  a.ch[0] = chain_par(c, chain, theta);
-  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
-  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
-  if (c->nt > ABD_MAXT)
-    hipLaunchKernelGGL(abd_deterministics_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a, out_i, out_mun, out_mus, sums);
-  else
-    hipLaunchKernelGGL(abd_deterministics_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a, out_i, out_mun, out_mus, sums);
-  HIP_TRY(hipGetLastError());
-  return ABD_OK;
+  return launch_cells(c, abd_deterministics_kernel<ABD_MAXT>, abd_deterministics_kernel<ABD_MAXT_MAX>, CellGrid::Individuals, 0, st,
+                      cell_walk(c, chain, theta), out_i, out_mun, out_mus, sums);
 }
 
 size_t curves_row_cols(const abd_ctx* c) { return (size_t)abd_curves_row_cols(c->G); }
@@ -617,29 +636,16 @@ size_t curves_scratch_cols(const abd_ctx* c) { return (size_t)abd_curves_slabs(c
 
 int launch_curves(abd_ctx* c, int chain, const double* theta, double thr_s, double thr_n, hipStream_t st, unsigned long long* scratch,
                   unsigned long long* row) {
-  const ChainPar p = chain_par(c, chain, theta);
   CurvesArgs a;
-  a.vw = c->vw;
-  a.iw = p.iw;
-  a.waner = p.waner;
-  a.last = c->d_last;
+  a.w = cell_walk(c, chain, theta);
   a.slab_rows = scratch;
-  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
-  a.init_s = p.init_s, a.perm_s = p.perm_s;
   a.thr_s = thr_s, a.thr_n = thr_n;
-  a.G = c->G, a.N = c->N, a.nt = c->nt, a.n_slabs = abd_curves_slabs(c->N);
-  // power tables, then the slab's row: [2][G] doubles, [4][G] + 8 ints (41 KB at 512 gaps)
-  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)2 * c->G * sizeof(double) + ((size_t)4 * c->G + ABD_CURVES_NBIN) * sizeof(int);
-  const int blocks = std::max(1, std::min(a.n_slabs, c->n_cu * 8));  // (a slab's row does not depend on who computes it)
-  if (c->nt > ABD_MAXT)
-    hipLaunchKernelGGL(abd_curves_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  else
-    hipLaunchKernelGGL(abd_curves_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  HIP_TRY(hipGetLastError());
+  a.n_slabs = abd_curves_slabs(c->N);
+  if (int rc = launch_cells(c, abd_curves_kernel<ABD_MAXT>, abd_curves_kernel<ABD_MAXT_MAX>, CellGrid::Slabs, abd_curves_lds_bytes(c->G), st, a))
+    return rc;
   const int sum_blocks = (int)((curves_row_cols(c) + ABD_CURVES_SUM_COLS - 1) / ABD_CURVES_SUM_COLS);
-  hipLaunchKernelGGL(abd_curves_sum_kernel, dim3(sum_blocks), dim3(ABD_CURVES_SUM_PARTS * ABD_CURVES_SUM_COLS), 0, st, scratch, a.n_slabs,
-                     c->G, row);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_kernel(abd_curves_sum_kernel, dim3(sum_blocks), dim3(ABD_CURVES_SUM_PARTS * ABD_CURVES_SUM_COLS), 0, st, scratch, a.n_slabs,
+                        c->G, row));
   return ABD_OK;
 }
 
@@ -652,24 +658,11 @@ void split_curves_row(const abd_ctx* c, const unsigned long long* row, int64_t* 
 
 int launch_diag(abd_ctx* c, int chain, const double* theta, hipStream_t st, int64_t d, int64_t H, int64_t L, double* tit, uint32_t* inf,
                 unsigned long long* cb2) {
-  const ChainPar p = chain_par(c, chain, theta);
   DiagArgs a;
-  a.vw = c->vw;
-  a.iw = p.iw;
-  a.waner = p.waner;
+  a.w = cell_walk(c, chain, theta);
   a.tit = tit, a.inf = reinterpret_cast<DiagInf*>(inf), a.cb2 = cb2;
-  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
-  a.init_s = p.init_s, a.perm_s = p.perm_s;
-  a.w = diag_draw(d, H, L);
-  a.G = c->G, a.N = c->N, a.nt = c->nt;
-  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
-  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
-  if (c->nt > ABD_MAXT)
-    hipLaunchKernelGGL(abd_diag_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  else
-    hipLaunchKernelGGL(abd_diag_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  HIP_TRY(hipGetLastError());
-  return ABD_OK;
+  a.d = diag_draw(d, H, L);
+  return launch_cells(c, abd_diag_kernel<ABD_MAXT>, abd_diag_kernel<ABD_MAXT_MAX>, CellGrid::Individuals, 0, st, a);
 }
 
 int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsigned long long* dst, hipStream_t st) {
@@ -682,26 +675,12 @@ int launch_diag_export(abd_ctx* c, const void* src, int stride, int width, unsig
 
 int launch_timeline(abd_ctx* c, int chain, const double* theta, const double range_n[2], const double range_s[2], hipStream_t st,
                     uint32_t* hist_n, uint32_t* hist_s, uint32_t* cell, uint32_t* ninf) {
-  const ChainPar p = chain_par(c, chain, theta);
   TimelineArgs a;
-  a.vw = c->vw;
-  a.iw = p.iw;
-  a.waner = p.waner;
-  a.last = c->d_last;
+  a.w = cell_walk(c, chain, theta);
   a.hist_n = hist_n, a.hist_s = hist_s, a.cell = reinterpret_cast<TimelineCell*>(cell), a.ninf = ninf;
-  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
-  a.init_s = p.init_s, a.perm_s = p.perm_s;
   a.rn = timeline_range(range_n[0], range_n[1]), a.rs = timeline_range(range_s[0], range_s[1]);
-  a.G = c->G, a.N = c->N, a.nt = c->nt;
   a.n_splits = c->n_chunks - 1, a.s0 = c->splits[0], a.s1 = c->splits[1];
-  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
-  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
-  if (c->nt > ABD_MAXT)
-    hipLaunchKernelGGL(abd_timeline_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  else
-    hipLaunchKernelGGL(abd_timeline_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  HIP_TRY(hipGetLastError());
-  return ABD_OK;
+  return launch_cells(c, abd_timeline_kernel<ABD_MAXT>, abd_timeline_kernel<ABD_MAXT_MAX>, CellGrid::Individuals, 0, st, a);
 }
 
 int launch_timeline_hist_export(abd_ctx* c, const uint32_t* src, int g0, int n_g, void* dst, hipStream_t st) {
@@ -744,34 +723,20 @@ int check_risk_spec(const abd_ctx* c, const abd_risk_spec* spec) {
 
 int launch_risk(abd_ctx* c, int chain, const double* theta, const abd_risk_spec& spec, hipStream_t st, unsigned long long* scratch,
                 uint32_t* table) {
-  const ChainPar p = chain_par(c, chain, theta);
   RiskArgs a;
-  a.vw = c->vw;
-  a.iw = p.iw;
-  a.waner = p.waner;
-  a.last = c->d_last;
+  a.w = cell_walk(c, chain, theta);
   a.slab_rows = scratch;
-  a.rho_n = p.rho_n, a.rho_s = p.rho_s, a.init_n = p.init_n, a.perm_n = p.perm_n, a.temp_n = p.temp_n;
-  a.init_s = p.init_s, a.perm_s = p.perm_s;
   for (int k = 0; k < ABD_RISK_MAX_EDGES; ++k) {
     a.edges_s[k] = k < spec.n_edges_s ? spec.edges_s[k] : HUGE_VAL;
     a.edges_n[k] = k < spec.n_edges_n ? spec.edges_n[k] : HUGE_VAL;
   }
-  a.G = c->G, a.N = c->N, a.nt = c->nt, a.n_slabs = abd_curves_slabs(c->N);
+  a.n_slabs = abd_curves_slabs(c->N);
   a.start = spec.start, a.end = spec.end, a.first_only = spec.first_only;
-  // power tables, then the slab's packed row: [4][G] 64-bit words, then the edges (41 KB at 512 gaps)
-  const size_t lds = (size_t)3 * (c->G + 1) * sizeof(double2_t) + (size_t)abd_risk_packed_cols(c->G) * sizeof(unsigned long long) +
-                     (size_t)2 * ABD_RISK_MAX_EDGES * sizeof(double);
-  const int blocks = std::max(1, std::min(a.n_slabs, c->n_cu * 8));  // (a slab's row does not depend on who computes it)
-  if (c->nt > ABD_MAXT)
-    hipLaunchKernelGGL(abd_risk_kernel<ABD_MAXT_MAX>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  else
-    hipLaunchKernelGGL(abd_risk_kernel<ABD_MAXT>, dim3(blocks), dim3(ABD_BLOCK), lds, st, a);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_cells(c, abd_risk_kernel<ABD_MAXT>, abd_risk_kernel<ABD_MAXT_MAX>, CellGrid::Slabs, abd_risk_lds_bytes(c->G), st, a))
+    return rc;
   const int sum_blocks = (int)((abd_risk_packed_cols(c->G) + ABD_RISK_SUM_COLS - 1) / ABD_RISK_SUM_COLS);
-  hipLaunchKernelGGL(abd_risk_sum_kernel, dim3(sum_blocks), dim3(ABD_RISK_SUM_PARTS * ABD_RISK_SUM_COLS), 0, st, scratch, a.n_slabs, c->G,
-                     table);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_kernel(abd_risk_sum_kernel, dim3(sum_blocks), dim3(ABD_RISK_SUM_PARTS * ABD_RISK_SUM_COLS), 0, st, scratch, a.n_slabs, c->G,
+                        table));
   return ABD_OK;
 }
 

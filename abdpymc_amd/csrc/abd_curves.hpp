@@ -10,7 +10,7 @@
 //                        seropos_n      #{j followed at g: ab_n_mu[g, j] >= thr_n}
 //   int64 n_infections[8]  individuals with last[j] >= 0 by their number of infections in gaps 0 .. last[j]; [7]: 7 or more
 //   double titer_sums[2][G]  sums over the followed j of ab_s_mu[g, j], of ab_n_mu[g, j]
-// The titers are the expressions of abd_deterministics_kernel (abd_small.hpp), not a second formula.
+// The titers are cell_titers (abd_cells.hpp), what abd_deterministics_kernel records: not a second formula.
 //
 // Reproducibility rule: a row depends on (N, G, last, the slot's state, theta, the thresholds) and on nothing else -- not on
 // the grid, the number of CUs, what else runs, or timing.  The individuals are cut into SLABS of ABD_CURVES_SLAB consecutive
@@ -20,7 +20,7 @@
 // ... in order, and the parts are added in order.  Every addition has its place; there are no atomics of any kind.
 #pragma once
 
-#include "abd_device.hpp"
+#include "abd_cells.hpp"
 
 #define ABD_CURVES_SLAB 64       // individuals per slab: 16 per wave (the power tables' fill is shared by the workgroup's slabs)
 #define ABD_CURVES_SUM_PARTS 16  // abd_curves_sum_kernel: partial sums per column ...
@@ -32,32 +32,30 @@ __host__ __device__ inline int64_t abd_curves_int_cols(int G) { return (int64_t)
 __host__ __device__ inline int64_t abd_curves_row_cols(int G) { return (int64_t)6 * G + ABD_CURVES_NBIN; }
 __host__ __device__ inline int abd_curves_slabs(int N) { return (N + ABD_CURVES_SLAB - 1) / ABD_CURVES_SLAB; }
 
-// The launch's own small argument block (a 2 KB EvalArgs would take the scalar registers the packed words live in)
+// The launch's argument block: the walk and the curves' own fields (in this order the kernels spill fewer scalar registers
+// than with the pointer first; tools/resource_usage.py)
 struct CurvesArgs {
-  const uint64_t* vw;      // [nt][N] packed vaccinations
-  const uint64_t* iw;      // [nt][N] the chain slot's constrained infections
-  const int8_t* waner;     // [N]
-  const int32_t* last;     // [N] end of follow-up; nullptr: G - 1 for everyone
-  unsigned long long* slab_rows;  // [slabs][6 G + 8] scratch, one row per slab
-  double rho_n, rho_s, init_n, perm_n, temp_n, init_s, perm_s;
+  CellWalk w;
   double thr_s, thr_n;
-  int32_t G, N, nt, n_slabs;
+  unsigned long long* slab_rows;  // [slabs][6 G + 8] scratch, one row per slab
+  int32_t n_slabs;
 };
+
+// dynamic LDS behind the power tables, the slab's row: [2][G] doubles, [4][G] + 8 ints (41 KB with the tables at 512 gaps)
+__host__ __device__ inline size_t abd_curves_lds_bytes(int G) {
+  return (size_t)2 * G * sizeof(double) + ((size_t)4 * G + ABD_CURVES_NBIN) * sizeof(int);
+}
 
 template <int MT>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_curves_kernel(const CurvesArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int G = a.G, N = a.N, nt = a.nt, tstride = G + 1;
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  double2_t* tab_ones = tabs + 2 * tstride;
-  double* red_d = reinterpret_cast<double*>(tabs + 3 * tstride);  // [2][G]: ab_s_mu, ab_n_mu
-  int* red_c = reinterpret_cast<int*>(red_d + 2 * G);              // [4][G] counts, then [8] bins
+  const CellWalk& w = a.w;
+  const int G = w.G, N = w.N, nt = w.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fill_pow_table(tabs, a.rho_n, tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, a.rho_s, tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
-  __syncthreads();
+  const CellTables tabs = cell_tables(smem, w, tid);
+  double* red_d = reinterpret_cast<double*>(tabs.behind);  // [2][G]: ab_s_mu, ab_n_mu
+  int* red_c = reinterpret_cast<int*>(red_d + 2 * G);       // [4][G] counts, then [8] bins
   const int64_t n_int = abd_curves_int_cols(G), n_row = abd_curves_row_cols(G);
   for (int slab = blockIdx.x; slab < a.n_slabs; slab += gridDim.x) {
     // the lane's partials of gap 64 t + lane over its wave's individuals of this slab
@@ -71,76 +69,41 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_curves_kernel(const CurvesArgs 
     int bins = 0;  // lane k < 8: individuals of this wave with k infections
     const int j_end = min(N, (slab + 1) * ABD_CURVES_SLAB);
     for (int j = slab * ABD_CURVES_SLAB + wave; j < j_end; j += ABD_WAVES_PER_BLOCK) {
-      const int last = a.last ? __builtin_amdgcn_readfirstlane(a.last[j]) : G - 1;
+      const int last = last_gap(w, j);
       if (last < 0) continue;  // never followed (wave-uniform)
       uint64_t V[MT], I[MT];
-      int n_inf = 0;
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        V[t] = I[t] = 0;
-        if (t < nt) {
-          V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-          I[t] = uniform_word(a.iw, (int64_t)t * N + j);
-          const int rel = last - t * 64;  // bits <= rel of this word are followed gaps
-          const uint64_t le = rel >= 63 ? ~0ull : (rel < 0 ? 0ull : ((2ull << rel) - 1ull));
-          n_inf += __builtin_popcountll(I[t] & le);
-        }
-      }
-      bins += lane == min(n_inf, ABD_CURVES_NBIN - 1);
-      const bool wj = __builtin_amdgcn_readfirstlane((int)a.waner[j]) != 0;
-      const double2_t* ts = wj ? tabs + tstride : tab_ones;
+      const double2_t* ts = load_individual<MT>(w, j, tabs, V, I);
+      bins += lane == min(followed_infections<MT>(I, last, nt), ABD_CURVES_NBIN - 1);
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         const int g = t * 64 + lane;
         if (t < nt && t * 64 <= last && g < G) {
-          const Resp rs = responses<MT>(g, t + 1, I, V, tabs, ts);
+          const CellTiters c = cell_titers<MT>(w, V, I, tabs.tab_n, ts, g, t + 1);
           const int bit = (int)((I[t] >> lane) & 1ull);
-          const double mun = a.init_n + (rs.cum_i ? a.perm_n : 0.0) + a.temp_n * rs.un;
-          const double mus = a.init_s + (rs.cum_iv ? a.perm_s : 0.0) + rs.us;
           if (g <= last) {
             c_inf[t] += bit;
-            c_ever[t] += rs.cum_i ? 1 : 0;
-            c_ps[t] += mus >= a.thr_s ? 1 : 0;
-            c_pn[t] += mun >= a.thr_n ? 1 : 0;
-            s_s[t] += mus;
-            s_n[t] += mun;
+            c_ever[t] += c.cum_i ? 1 : 0;
+            c_ps[t] += c.mus >= a.thr_s ? 1 : 0;
+            c_pn[t] += c.mun >= a.thr_n ? 1 : 0;
+            s_s[t] += c.mus;
+            s_n[t] += c.mun;
           }
         }
       }
     }
-    // the slab's row: wave 0 stores, waves 1, 2, 3 add in turn
-    for (int w = 0; w < ABD_WAVES_PER_BLOCK; ++w) {
-      if (wave == w) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          const int g = t * 64 + lane;
-          if (t < nt && g < G) {
-            if (w == 0) {
-              red_c[g] = c_inf[t];
-              red_c[G + g] = c_ever[t];
-              red_c[2 * G + g] = c_ps[t];
-              red_c[3 * G + g] = c_pn[t];
-              red_d[g] = s_s[t];
-              red_d[G + g] = s_n[t];
-            } else {
-              red_c[g] += c_inf[t];
-              red_c[G + g] += c_ever[t];
-              red_c[2 * G + g] += c_ps[t];
-              red_c[3 * G + g] += c_pn[t];
-              red_d[g] += s_s[t];
-              red_d[G + g] += s_n[t];
-            }
-          }
-        }
-        if (lane < ABD_CURVES_NBIN) {
-          if (w == 0)
-            red_c[4 * G + lane] = bins;
-          else
-            red_c[4 * G + lane] += bins;
-        }
-      }
-      __syncthreads();
-    }
+    slab_reduce<MT>(
+        wave, lane, G, nt,
+        [&](bool first, int t, int g) {
+          slab_put(first, red_c[g], c_inf[t]);
+          slab_put(first, red_c[G + g], c_ever[t]);
+          slab_put(first, red_c[2 * G + g], c_ps[t]);
+          slab_put(first, red_c[3 * G + g], c_pn[t]);
+          slab_put(first, red_d[g], s_s[t]);
+          slab_put(first, red_d[G + g], s_n[t]);
+        },
+        [&](bool first) {
+          if (lane < ABD_CURVES_NBIN) slab_put(first, red_c[4 * G + lane], bins);
+        });
     unsigned long long* row = a.slab_rows + (int64_t)slab * n_row;
     for (int e = tid; e < (int)n_int; e += ABD_BLOCK) row[e] = (unsigned long long)(long long)red_c[e];
     for (int e = tid; e < 2 * G; e += ABD_BLOCK) row[n_int + e] = (unsigned long long)__double_as_longlong(red_d[e]);

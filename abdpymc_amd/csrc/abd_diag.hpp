@@ -88,51 +88,35 @@ __host__ __device__ inline void diag_update_inf(DiagInf& c, unsigned long long& 
 
 #if defined(__HIPCC__)
 
-#include "abd_device.hpp"
+#include "abd_cells.hpp"
 
-// The launch's own small argument block (a 2 KB EvalArgs would take the scalar registers the packed words live in)
+// The launch's argument block: the walk and the accumulators' own fields (the draw in front of the pointers: fewer scalar
+// spills; tools/resource_usage.py)
 struct DiagArgs {
-  const uint64_t* vw;     // [nt][N] packed vaccinations
-  const uint64_t* iw;     // [nt][N] the chain slot's constrained infections
-  const int8_t* waner;    // [N]
+  CellWalk w;
+  abdi::DiagDraw d;
   double* tit;            // the chain's [2][kDiagTiterPlanes][N * G] planes: ab_n_mu, then ab_s_mu
   abdi::DiagInf* inf;     // [N * G]
   unsigned long long* cb2;  // [N * G]
-  double rho_n, rho_s, init_n, perm_n, temp_n, init_s, perm_s;
-  abdi::DiagDraw w;
-  int32_t G, N, nt;
 };
 
-// One draw of one chain into its accumulators.  The titers are the expressions of abd_deterministics_kernel (abd_small.hpp),
-// not a second formula.  Reads the slot's state and indicator words only: dense and list cohorts run the same code.
+// One draw of one chain into its accumulators.  The titers are cell_titers (abd_cells.hpp), what abd_deterministics_kernel
+// records: not a second formula.  Reads the slot's state and indicator words only: dense and list cohorts run the same code.
 template <int MT>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_diag_kernel(const DiagArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  const int G = a.G, N = a.N, nt = a.nt, tstride = G + 1;
-  double2_t* tab_ones = tabs + 2 * tstride;
+  const CellWalk& cw = a.w;
+  const int G = cw.G, N = cw.N, nt = cw.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fill_pow_table(tabs, a.rho_n, tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, a.rho_s, tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
-  __syncthreads();
-  const abdi::DiagDraw w = a.w;
+  const CellTables tabs = cell_tables(smem, cw, tid);
+  const abdi::DiagDraw w = a.d;
   const int64_t cells = (int64_t)G * N;
   const int half_at = w.half ? abdi::kDiagMean1 : abdi::kDiagMean0;
   const int waves_total = gridDim.x * ABD_WAVES_PER_BLOCK;
   for (int j = blockIdx.x * ABD_WAVES_PER_BLOCK + wave; j < N; j += waves_total) {
     uint64_t V[MT], I[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      V[t] = I[t] = 0;
-      if (t < nt) {
-        V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-        I[t] = uniform_word(a.iw, (int64_t)t * N + j);
-      }
-    }
-    const bool wj = __builtin_amdgcn_readfirstlane((int)a.waner[j]) != 0;
-    const double2_t* ts = wj ? tabs + tstride : tab_ones;
+    const double2_t* ts = load_individual<MT>(cw, j, tabs, V, I);
     for (int t = 0; t < nt; ++t) {
       const int g = t * 64 + lane;
       if (g < G) {
@@ -151,9 +135,9 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_diag_kernel(const DiagArgs a) {
         }
         abdi::DiagInf ci = a.inf[o];
         unsigned long long cb2 = w.close_batch ? a.cb2[o] : 0ull;
-        const Resp rs = responses<MT>(g, t + 1, I, V, tabs, ts);
+        const CellTiters ct = cell_titers<MT>(cw, V, I, tabs.tab_n, ts, g, t + 1);
         const uint32_t bit = (uint32_t)((I[t] >> lane) & 1ull);
-        const double x[2] = {a.init_n + (rs.cum_i ? a.perm_n : 0.0) + a.temp_n * rs.un, a.init_s + (rs.cum_iv ? a.perm_s : 0.0) + rs.us};
+        const double x[2] = {ct.mun, ct.mus};
         for (int v = 0; v < 2; ++v) {
           abdi::diag_update_titer(c[v], x[v], w);
           double* pl = a.tit + (int64_t)v * abdi::kDiagTiterPlanes * cells + o;

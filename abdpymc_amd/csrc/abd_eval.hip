@@ -566,7 +566,7 @@ int launch_readings(abd_ctx* c, int chain, const Transformed& tr, const Op& op, 
   if (c->dense) {
     k = f32 ? (wide ? abd_readings_dense_kernel<Op, float, ABD_MAXT_MAX> : abd_readings_dense_kernel<Op, float, ABD_MAXT>)
             : (wide ? abd_readings_dense_kernel<Op, double, ABD_MAXT_MAX> : abd_readings_dense_kernel<Op, double, ABD_MAXT>);
-    lds = (size_t)3 * (c->G + 1) * sizeof(double2_t);
+    lds = cell_tables_bytes(c->G);
     blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
   } else {
     k = f32 ? (wide ? abd_readings_lists_kernel<Op, float, ABD_MAXT_MAX> : abd_readings_lists_kernel<Op, float, ABD_MAXT>)

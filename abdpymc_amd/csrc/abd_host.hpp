@@ -300,7 +300,7 @@ size_t risk_table_cols(const abd_ctx* c);
 size_t risk_scratch_cols(const abd_ctx* c);
 // Draw d (= iteration - tune, in [0, 2 H)) of chain `chain` at theta into its convergence accumulators on stream st
 // (abd_diag.hpp; H the half length, L the batch length): tit [2][7][G*N], inf [G*N][4] and cb2 [G*N] are the chain's own
-// planes.  Touches no member of the context.
+// planes.  Touches no member of the context (its block carries d_last as every cell kernel's does; the kernel does not read it).
 int launch_diag(abd_ctx* c, int chain, const double* theta, hipStream_t st, int64_t d, int64_t H, int64_t L, double* tit, uint32_t* inf,
                 unsigned long long* cb2);
 // One individual-major plane of the accumulators (first element src, elements `stride` bytes apart, `width` 4 or 8 bytes

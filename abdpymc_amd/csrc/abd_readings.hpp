@@ -30,9 +30,11 @@
 // individual, then gap): for a dense panel reading (g, j) is k = j G + g, the individual-major yxi panel; for observation lists
 // the order of the uploaded lists.  A row holds the S readings, then N.  Every reading belongs to exactly one lane and every
 // chain has its own rows: a fixed-order read-modify-write, no atomics.
-// Included by abd_eval.hip (after abd_eval_kernels.hpp: responses, the power tables, exp2_reduced, rcp_newton).
+// Included by abd_eval.hip (after abd_eval_kernels.hpp: responses, the power tables, exp2_reduced, rcp_newton); the dense
+// walker shares its prologue and its individual's loads with the other cell kernels (abd_cells.hpp).
 #pragma once
 
+#include "abd_cells.hpp"
 #include "abd_obs.hpp"
 
 enum : int { kAgS = 0, kAgN = 1 };  // antigen index of the per-antigen constants (and of the predictive stream's counter)
@@ -181,18 +183,14 @@ template <typename Op, typename R, int MT>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_readings_dense_kernel(const ReadingArgs<Op> a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const Readings& w = a.rd;
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  const int G = w.G, N = w.N, nt = w.nt, tstride = G + 1;
-  double2_t* tab_ones = tabs + 2 * tstride;
+  const int G = w.G, N = w.N, nt = w.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fill_pow_table(tabs, w.rho[kAgN], tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, w.rho[kAgS], tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
-  __syncthreads();
+  const CellTables tabs = cell_tables(smem, w.rho[kAgN], w.rho[kAgS], G, tid);
   const YX<R>* yxn = reinterpret_cast<const YX<R>*>(w.y_n);
   const YX<R>* yxs = reinterpret_cast<const YX<R>*>(w.y_s);
-  // the curve constants live in vector registers: the scalar file holds the individual's packed words
+  // the curve constants live in vector registers: the scalar file holds the individual's packed words.  That is why the two
+  // titer lines below are cell_titers' (abd_cells.hpp) written out on the VGPR copies and not a call of it
   const double init_n = to_vgpr(w.init[kAgN]), perm_n = to_vgpr(w.perm[kAgN]), temp_n = to_vgpr(w.temp_n);
   const typename Op::Side on = a.op.side(w, kAgN);
   const double init_s = to_vgpr(w.init[kAgS]), perm_s = to_vgpr(w.perm[kAgS]);
@@ -200,20 +198,11 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_readings_dense_kernel(const Rea
   const int waves_total = gridDim.x * ABD_WAVES_PER_BLOCK;
   for (int j = blockIdx.x * ABD_WAVES_PER_BLOCK + wave; j < N; j += waves_total) {
     uint64_t V[MT], I[MT];
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      V[t] = I[t] = 0;
-      if (t < nt) {
-        V[t] = uniform_word(w.vw, (int64_t)t * N + j);
-        I[t] = uniform_word(w.iw, (int64_t)t * N + j);
-      }
-    }
-    const bool wj = __builtin_amdgcn_readfirstlane((int)w.waner[j]) != 0;
-    const double2_t* ts = wj ? tabs + tstride : tab_ones;
+    const double2_t* ts = load_individual<MT>(w.vw, w.iw, w.waner, N, nt, j, tabs, V, I);
     for (int t = 0; t < nt; ++t) {
       const int g = t * 64 + lane;
       if (g < G) {
-        const Resp rs = responses<MT>(g, t + 1, I, V, tabs, ts);
+        const Resp rs = responses<MT>(g, t + 1, I, V, tabs.tab_n, ts);
         const int64_t k = (int64_t)j * G + g;
         const double an = init_n + (rs.cum_i ? perm_n : 0.0) + temp_n * rs.un;
         const double as = init_s + (rs.cum_iv ? perm_s : 0.0) + rs.us;

@@ -7,7 +7,7 @@
 // every start < g' < g; it is an EVENT iff it is at risk and i[g, j] = 1.  The table is
 //   int64 table[2][2][G][8]   antigen (S, N) x (at risk, events) x gap x bin
 // where the bin of a cell is #{e in edges: x >= e} of the titer of the PREVIOUS gap, x = ab_s_mu[g - 1, j] or
-// ab_n_mu[g - 1, j]: the expressions of abd_deterministics_kernel (abd_small.hpp), not a second formula.  A NaN titer fails
+// ab_n_mu[g - 1, j]: cell_titers (abd_cells.hpp) at g - 1, what abd_deterministics_kernel records, not a second formula.  A NaN titer fails
 // every comparison: bin 0.
 //
 // The kernel pair has the shape of the curves': slabs of ABD_CURVES_SLAB individuals, a wave per individual, a lane per gap of
@@ -32,31 +32,29 @@ __host__ __device__ inline int64_t abd_risk_packed_cols(int G) { return (int64_t
 __host__ __device__ inline int64_t abd_risk_table_cols(int G) { return (int64_t)4 * G * ABD_RISK_NBIN; }
 
 struct RiskArgs {
-  const uint64_t* vw;      // [nt][N] packed vaccinations
-  const uint64_t* iw;      // [nt][N] the chain slot's constrained infections
-  const int8_t* waner;     // [N]
-  const int32_t* last;     // [N] end of follow-up; nullptr: G - 1 for everyone
+  CellWalk w;
   unsigned long long* slab_rows;  // [slabs][4 G] packed scratch, one row per slab
-  double rho_n, rho_s, init_n, perm_n, temp_n, init_s, perm_s;
   double edges_s[ABD_RISK_MAX_EDGES], edges_n[ABD_RISK_MAX_EDGES];  // unused edges are +inf: never reached
-  int32_t G, N, nt, n_slabs;
+  int32_t n_slabs;
   int32_t start, end, first_only;
 };
+
+// dynamic LDS behind the power tables: the slab's packed row [4][G], then the edges (41 KB with the tables at 512 gaps)
+__host__ __device__ inline size_t abd_risk_lds_bytes(int G) {
+  return (size_t)abd_risk_packed_cols(G) * sizeof(unsigned long long) + (size_t)2 * ABD_RISK_MAX_EDGES * sizeof(double);
+}
 
 template <int MT>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_risk_kernel(const RiskArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int G = a.G, N = a.N, nt = a.nt, tstride = G + 1;
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  double2_t* tab_ones = tabs + 2 * tstride;
-  unsigned long long* red = reinterpret_cast<unsigned long long*>(tabs + 3 * tstride);  // [4][G] packed
+  const CellWalk& w = a.w;
+  const int G = w.G, N = w.N, nt = w.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fill_pow_table(tabs, a.rho_n, tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, a.rho_s, tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(smem + cell_tables_bytes(G));  // [4][G] packed
   const int n_row = (int)abd_risk_packed_cols(G);
-  // the edges live in LDS (every lane reads the same address: a broadcast), not in 28 scalar registers beside the packed words
+  // the edges live in LDS (every lane reads the same address: a broadcast), not in 28 scalar registers beside the packed words;
+  // stored in front of the prologue's barrier
   double* edges = reinterpret_cast<double*>(red + n_row);  // [2][ABD_RISK_MAX_EDGES]
   if (tid == 0) {
 #pragma unroll
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_risk_kernel(const RiskArgs a) {
       edges[ABD_RISK_MAX_EDGES + e] = a.edges_n[e];
     }
   }
-  __syncthreads();
+  const CellTables tabs = cell_tables(smem, w, tid);
   for (int slab = blockIdx.x; slab < a.n_slabs; slab += gridDim.x) {
     // the lane's packed counters of gap 64 t + lane over its wave's individuals of this slab
     unsigned long long r_s[MT], e_s[MT], r_n[MT], e_n[MT];
@@ -73,45 +71,32 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_risk_kernel(const RiskArgs a) {
     for (int t = 0; t < MT; ++t) r_s[t] = e_s[t] = r_n[t] = e_n[t] = 0ull;
     const int j_end = min(N, (slab + 1) * ABD_CURVES_SLAB);
     for (int j = slab * ABD_CURVES_SLAB + wave; j < j_end; j += ABD_WAVES_PER_BLOCK) {
-      const int last = a.last ? __builtin_amdgcn_readfirstlane(a.last[j]) : G - 1;
+      const int last = last_gap(w, j);  // (read first: one vector register less, a wave more per SIMD)
       uint64_t V[MT], I[MT];
+      const double2_t* ts = load_individual<MT>(w, j, tabs, V, I);
       // the last gap at risk (wave-uniform): the end of the window, of the follow-up and, under first_only, the first
       // infection after `start`
       int limit = min(last, a.end - 1);
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        V[t] = I[t] = 0;
-        if (t < nt) {
-          V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-          I[t] = uniform_word(a.iw, (int64_t)t * N + j);
-        }
-      }
       if (a.first_only) {
         int first = G;
 #pragma unroll
         for (int t = MT - 1; t >= 0; --t) {
-          const int rel = a.start - t * 64;  // bits <= rel of this word are gaps up to `start`
-          const uint64_t le = rel >= 63 ? ~0ull : (rel < 0 ? 0ull : ((2ull << rel) - 1ull));
-          const uint64_t after = I[t] & ~le;
+          const uint64_t after = I[t] & ~bits_upto(a.start - t * 64);  // gaps of this word behind `start`
           if (after) first = t * 64 + __builtin_ctzll(after);
         }
         limit = min(limit, first);
       }
       if (limit <= a.start) continue;  // nothing at risk (wave-uniform)
-      const bool wj = __builtin_amdgcn_readfirstlane((int)a.waner[j]) != 0;
-      const double2_t* ts = wj ? tabs + tstride : tab_ones;
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         const int g = t * 64 + lane;
         if (t < nt && t * 64 <= limit && t * 64 + 63 > a.start && g > a.start && g <= limit) {
-          const Resp rs = responses<MT>(g - 1, t + 1, I, V, tabs, ts);  // the predecessor's titers
-          const double mun = a.init_n + (rs.cum_i ? a.perm_n : 0.0) + a.temp_n * rs.un;
-          const double mus = a.init_s + (rs.cum_iv ? a.perm_s : 0.0) + rs.us;
+          const CellTiters c = cell_titers<MT>(w, V, I, tabs.tab_n, ts, g - 1, t + 1);  // the predecessor's titers
           int bs = 0, bn = 0;
 #pragma unroll
           for (int e = 0; e < ABD_RISK_MAX_EDGES; ++e) {
-            bs += mus >= edges[e] ? 1 : 0;
-            bn += mun >= edges[ABD_RISK_MAX_EDGES + e] ? 1 : 0;
+            bs += c.mus >= edges[e] ? 1 : 0;
+            bn += c.mun >= edges[ABD_RISK_MAX_EDGES + e] ? 1 : 0;
           }
           const unsigned long long bit = (I[t] >> lane) & 1ull;
           r_s[t] += 1ull << (8 * bs);
@@ -121,29 +106,16 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_risk_kernel(const RiskArgs a) {
         }
       }
     }
-    // the slab's row: wave 0 stores, waves 1, 2, 3 add in turn (no byte passes 64)
-    for (int w = 0; w < ABD_WAVES_PER_BLOCK; ++w) {
-      if (wave == w) {
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          const int g = t * 64 + lane;
-          if (t < nt && g < G) {
-            if (w == 0) {
-              red[g] = r_s[t];
-              red[G + g] = e_s[t];
-              red[2 * G + g] = r_n[t];
-              red[3 * G + g] = e_n[t];
-            } else {
-              red[g] += r_s[t];
-              red[G + g] += e_s[t];
-              red[2 * G + g] += r_n[t];
-              red[3 * G + g] += e_n[t];
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
+    // (no byte passes 64)
+    slab_reduce<MT>(
+        wave, lane, G, nt,
+        [&](bool first, int t, int g) {
+          slab_put(first, red[g], r_s[t]);
+          slab_put(first, red[G + g], e_s[t]);
+          slab_put(first, red[2 * G + g], r_n[t]);
+          slab_put(first, red[3 * G + g], e_n[t]);
+        },
+        [](bool) {});
     unsigned long long* row = a.slab_rows + (int64_t)slab * n_row;
     for (int e = tid; e < n_row; e += ABD_BLOCK) row[e] = red[e];
     __syncthreads();  // (the next slab's wave 0 stores over red)

@@ -7,6 +7,75 @@
 #include <deque>
 #include <memory>
 
+// The per-draw summaries of a sampler (abd_sampler_enable_*): each is its device buffers, what it was enabled with and the
+// layout of the buffers -- stated once, as the offset of chain j's part (j = n: the buffer's length), for the enable function,
+// the launch and the read-out alike.  planned(): the draws it was sized for; launch(): draw d = iteration - tune of sampler
+// chain j (slot `chain`, point q) on stream st.
+struct CurvesSummary {  // abd_curves.hpp: every draw's row, and every chain's own slab rows (the chains' launches run side by side)
+  DevBuf<unsigned long long> rows, scratch;
+  int64_t capacity = 0;
+  double thr_s = 0.0, thr_n = 0.0;
+  bool on() const { return rows != nullptr; }
+  int64_t planned() const { return capacity; }
+  size_t row_at(const abd_ctx* c, int j, int64_t d) const { return ((size_t)j * capacity + (size_t)d) * abdi::curves_row_cols(c); }
+  size_t scratch_at(const abd_ctx* c, int j) const { return (size_t)j * abdi::curves_scratch_cols(c); }
+  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
+    return abdi::launch_curves(c, chain, q, thr_s, thr_n, st, scratch + scratch_at(c, j), rows + row_at(c, j, d));
+  }
+};
+
+struct RiskSummary {  // abd_risk.hpp: every draw's table of 32 G 32-bit counts, and every chain's own packed slab rows
+  DevBuf<uint32_t> tables;
+  DevBuf<unsigned long long> scratch;
+  int64_t capacity = 0;
+  abd_risk_spec spec = {};
+  bool on() const { return tables != nullptr; }
+  int64_t planned() const { return capacity; }
+  size_t table_at(const abd_ctx* c, int j, int64_t d) const { return ((size_t)j * capacity + (size_t)d) * abdi::risk_table_cols(c); }
+  size_t scratch_at(const abd_ctx* c, int j) const { return (size_t)j * abdi::risk_scratch_cols(c); }
+  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
+    return abdi::launch_risk(c, chain, q, spec, st, scratch + scratch_at(c, j), tables + table_at(c, j, d));
+  }
+};
+
+// abd_diag.hpp: convergence accumulators over all draws, individual-major planes per chain -- [n][2][7][G*N] of the two titers
+// (ab_n_mu, then ab_s_mu), [n][G*N][4] and [n][G*N] of i -- and one plane [G*N] of staging for the read-out
+struct DiagSummary {
+  DevBuf<double> tit;
+  DevBuf<uint32_t> inf;
+  DevBuf<unsigned long long> cb2, stage;
+  int64_t draws = 0, H = 0, L = 0;  // planned draws D, H = D / 2, batch length
+  bool on() const { return tit != nullptr; }
+  int64_t planned() const { return draws; }
+  static size_t cells(const abd_ctx* c) { return (size_t)c->G * c->N; }
+  size_t tit_at(const abd_ctx* c, int j, int titer = 0, int plane = 0) const { return (((size_t)j * 2 + titer) * 7 + plane) * cells(c); }
+  size_t inf_at(const abd_ctx* c, int j) const { return (size_t)j * 4 * cells(c); }
+  size_t cb2_at(const abd_ctx* c, int j) const { return (size_t)j * cells(c); }
+  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
+    if (d >= 2 * H) return ABD_OK;  // (an odd D: the last draw belongs to neither half)
+    return abdi::launch_diag(c, chain, q, st, d, H, L, tit + tit_at(c, j), inf + inf_at(c, j), cb2 + cb2_at(c, j));
+  }
+};
+
+// abd_timeline.hpp: per-individual timelines over all draws, individual-major planes per chain -- [n][2][G*N][32] words of the
+// two titers' histograms (ab_n_mu, then ab_s_mu), [n][G*N][2] inf and cum, [n][N][8] ninf -- and the read-out's staging
+struct TimelineSummary {
+  DevBuf<uint32_t> hist, cell, ninf;
+  DevBuf<unsigned long long> stage;
+  size_t stage_bytes = 0;
+  int64_t draws = 0;  // planned draws
+  double range_n[2] = {0.0, 0.0}, range_s[2] = {0.0, 0.0};
+  bool on() const { return hist != nullptr; }
+  int64_t planned() const { return draws; }
+  size_t hist_at(const abd_ctx* c, int j, int titer = 0) const { return ((size_t)j * 2 + titer) * c->G * c->N * (ABD_TIMELINE_BINS / 2); }
+  size_t cell_at(const abd_ctx* c, int j) const { return (size_t)j * 2 * c->G * c->N; }
+  size_t ninf_at(const abd_ctx* c, int j) const { return (size_t)j * ABD_TIMELINE_NINF * c->N; }
+  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t, hipStream_t st) const {
+    return abdi::launch_timeline(c, chain, q, range_n, range_s, st, hist + hist_at(c, j, 0), hist + hist_at(c, j, 1), cell + cell_at(c, j),
+                                 ninf + ninf_at(c, j));
+  }
+};
+
 struct abd_sampler {
   ~abd_sampler();  // quiesces; then the members go in reverse order (abd_host.hpp)
   abd_ctx* c = nullptr;
@@ -70,30 +139,11 @@ struct abd_sampler {
   // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
   // predictive mean, mean tail probability per reading
   DevBuf<double> d_pp_acc;
-  // epidemic curves of every draw (abd_curves.hpp): [n][curves_capacity] rows of 6 G + 8 columns, and every chain's own slab
-  // rows [n][curves_scratch_cols] (the chains' launches run side by side)
-  DevBuf<unsigned long long> d_curves, d_curves_scratch;
-  int64_t curves_capacity = 0;
-  double curves_thr_s = 0.0, curves_thr_n = 0.0;
-  // risk table of every draw (abd_risk.hpp): [n][risk_capacity] tables of 32 G 32-bit counts, and every chain's own packed slab
-  // rows [n][risk_scratch_cols]
-  DevBuf<uint32_t> d_risk;
-  DevBuf<unsigned long long> d_risk_scratch;
-  int64_t risk_capacity = 0;
-  abd_risk_spec risk_spec = {};
-  // convergence accumulators over all draws (abd_diag.hpp), individual-major planes per chain: [n][2][7][G*N] of the two
-  // titers, [n][G*N][4] and [n][G*N] of i, and one plane [G*N] of staging for the read-out
-  DevBuf<double> d_diag_tit;
-  DevBuf<uint32_t> d_diag_inf;
-  DevBuf<unsigned long long> d_diag_cb2, d_diag_stage;
-  int64_t diag_draws = 0, diag_H = 0, diag_L = 0;  // planned draws D, H = D / 2, batch length
-  // per-individual timelines over all draws (abd_timeline.hpp), individual-major planes per chain: [n][2][G*N][32] words of
-  // the two titers' histograms (ab_n_mu, then ab_s_mu), [n][G*N][2] inf and cum, [n][N][8] ninf, and the read-out's staging
-  DevBuf<uint32_t> d_tl_hist, d_tl_cell, d_tl_ninf;
-  DevBuf<unsigned long long> d_tl_stage;
-  size_t tl_stage_bytes = 0;
-  int64_t tl_draws = 0;  // planned draws
-  double tl_range_n[2] = {0.0, 0.0}, tl_range_s[2] = {0.0, 0.0};
+  // the per-draw summaries (above), in the order queue_draw launches them
+  CurvesSummary curves;
+  DiagSummary diag;
+  TimelineSummary timelines;
+  RiskSummary risk;
 };
 
 namespace {
@@ -260,6 +310,28 @@ int read_acc(abd_sampler* s, const double* acc, int32_t k, int rows, const char*
   const ReadingOut o[3] = {{out, out + Ks}, {out + Kt, out + Kt + Ks}, {out + 2 * Kt, out + 2 * Kt + Ks}};
   scatter_readings(c, o, [hp = h.data(), at](int v, size_t r) { return at(hp, v, r); });
   if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
+  return ABD_OK;
+}
+
+// What the four abd_sampler_enable_* do alike once their arguments are good: refuse after the first run call, drop what the
+// summary holds (nothing has been launched on it: the sampler has not run) and -- want -- let `alloc` fill a fresh one (its
+// buffers on the context's stream, its parameters; returns the hipError_t), which the sampler takes whole or not at all.
+// bytes: what an out-of-memory message names.
+template <typename S, typename Alloc>
+int enable_summary(abd_sampler* s, S& summary, const char* name, bool want, size_t bytes, Alloc alloc) {
+  if (s->ran) return fail(ABD_ERR_STATE, "%s must be enabled before the first abd_sampler_run call", name);
+  HIP_TRY(hipSetDevice(s->c->device));
+  summary = S();
+  if (!want) return ABD_OK;
+  S fresh;
+  const hipError_t e = alloc(fresh);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "%s: %zu bytes of device memory", name, bytes);
+  }
+  if (e != hipSuccess) return fail(ABD_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
+  HIP_TRY(hipStreamSynchronize(s->c->stream));  // (the buffers' zeroes)
+  summary = std::move(fresh);
   return ABD_OK;
 }
 
@@ -525,27 +597,18 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
     if (int rc = launch_predictive(c, chain, q, st, s->o.seed, (uint32_t)((int64_t)chain + s->o.chain_offset), (uint64_t)iter, yrep,
                                    nullptr, pacc, iter - s->o.tune + 1))
       return rc;
-  // epidemic curves: every draw's row, whatever is recorded (abd_sampler_run_record has checked the capacity)
-  if (draw && s->d_curves)
-    if (int rc = launch_curves(c, chain, q, s->curves_thr_s, s->curves_thr_n, st, s->d_curves_scratch + (size_t)j * curves_scratch_cols(c),
-                               s->d_curves + ((size_t)j * s->curves_capacity + (size_t)(iter - s->o.tune)) * curves_row_cols(c)))
-      return rc;
-  // convergence accumulators: every draw of the two halves, whatever is recorded (abd_sampler_run_record has checked D)
-  if (draw && s->d_diag_tit && iter - s->o.tune < 2 * s->diag_H)
-    if (int rc = launch_diag(c, chain, q, st, iter - s->o.tune, s->diag_H, s->diag_L, s->d_diag_tit + (size_t)j * 2 * 7 * cells,
-                             s->d_diag_inf + (size_t)j * 4 * cells, s->d_diag_cb2 + (size_t)j * cells))
-      return rc;
-  // timelines: every draw, whatever is recorded (abd_sampler_run_record has checked the planned draws)
-  if (draw && s->d_tl_hist)
-    if (int rc = launch_timeline(c, chain, q, s->tl_range_n, s->tl_range_s, st, s->d_tl_hist + (size_t)j * 2 * cells * (ABD_TIMELINE_BINS / 2),
-                                 s->d_tl_hist + ((size_t)j * 2 + 1) * cells * (ABD_TIMELINE_BINS / 2), s->d_tl_cell + (size_t)j * 2 * cells,
-                                 s->d_tl_ninf + (size_t)j * ABD_TIMELINE_NINF * N))
-      return rc;
-  // risk table: every draw's, as the curves
-  if (draw && s->d_risk)
-    if (int rc = launch_risk(c, chain, q, s->risk_spec, st, s->d_risk_scratch + (size_t)j * risk_scratch_cols(c),
-                             s->d_risk + ((size_t)j * s->risk_capacity + (size_t)(iter - s->o.tune)) * risk_table_cols(c)))
-      return rc;
+  // the summaries: every draw, whatever is recorded (abd_sampler_run_record has checked the planned draws)
+  if (draw) {
+    const int64_t d = iter - s->o.tune;
+    if (s->curves.on())
+      if (int rc = s->curves.launch(c, j, chain, q, d, st)) return rc;
+    if (s->diag.on())
+      if (int rc = s->diag.launch(c, j, chain, q, d, st)) return rc;
+    if (s->timelines.on())
+      if (int rc = s->timelines.launch(c, j, chain, q, d, st)) return rc;
+    if (s->risk.on())
+      if (int rc = s->risk.launch(c, j, chain, q, d, st)) return rc;
+  }
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
     if (int rc = record_flush_chain(s, f.rec, j, sg.flushed_to, sg.staged, st)) return rc;
@@ -1069,18 +1132,15 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   if (n_iter < 0) return fail(ABD_ERR_ARG, "n_iter=%lld is negative", (long long)n_iter);
   abd_ctx* c = s->c;
   const int n = s->n;
-  if (s->d_curves && s->it + n_iter - s->o.tune > s->curves_capacity)  // (before anything is launched or marked as run)
-    return fail(ABD_ERR_STATE, "curves: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
-                (long long)s->curves_capacity);
-  if (s->d_diag_tit && s->it + n_iter - s->o.tune > s->diag_draws)
-    return fail(ABD_ERR_STATE, "diagnostics: draws up to %lld pass the planned %lld", (long long)(s->it + n_iter - s->o.tune),
-                (long long)s->diag_draws);
-  if (s->d_risk && s->it + n_iter - s->o.tune > s->risk_capacity)
-    return fail(ABD_ERR_STATE, "risk: draws up to %lld do not fit capacity %lld", (long long)(s->it + n_iter - s->o.tune),
-                (long long)s->risk_capacity);
-  if (s->d_tl_hist && s->it + n_iter - s->o.tune > s->tl_draws)
-    return fail(ABD_ERR_STATE, "timelines: draws up to %lld pass the planned %lld", (long long)(s->it + n_iter - s->o.tune),
-                (long long)s->tl_draws);
+  // (before anything is launched or marked as run)
+  const int64_t upto = s->it + n_iter - s->o.tune;
+  const struct { const char* what; bool on; int64_t planned; } summaries[4] = {
+      {"curves: draws up to %lld do not fit capacity %lld", s->curves.on(), s->curves.planned()},
+      {"diagnostics: draws up to %lld pass the planned %lld", s->diag.on(), s->diag.planned()},
+      {"risk: draws up to %lld do not fit capacity %lld", s->risk.on(), s->risk.planned()},
+      {"timelines: draws up to %lld pass the planned %lld", s->timelines.on(), s->timelines.planned()}};
+  for (const auto& x : summaries)
+    if (x.on && upto > x.planned) return fail(ABD_ERR_STATE, x.what, (long long)upto, (long long)x.planned);
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
@@ -1177,35 +1237,22 @@ int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t
 int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, double thr_n) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
-  if (s->ran) return fail(ABD_ERR_STATE, "curves must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  s->d_curves.reset();  // (nothing has been launched on them: the sampler has not run)
-  s->d_curves_scratch.reset();
-  s->curves_capacity = 0;
-  if (capacity == 0) return ABD_OK;
-  const size_t n_rows = (size_t)s->n * (size_t)capacity * curves_row_cols(c);
-  DevBuf<unsigned long long> rows, scratch;  // (the sampler takes both or neither)
-  hipError_t e = rows.alloc(n_rows);
-  if (e == hipSuccess) e = scratch.alloc((size_t)s->n * curves_scratch_cols(c));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "curves: %zu bytes of device memory", n_rows * sizeof(unsigned long long));
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "curves: %s", hipGetErrorString(e));
-  s->d_curves = std::move(rows);
-  s->d_curves_scratch = std::move(scratch);
-  s->curves_capacity = capacity;
-  s->curves_thr_s = thr_s;
-  s->curves_thr_n = thr_n;
-  return ABD_OK;
+  const abd_ctx* c = s->c;
+  CurvesSummary f;
+  f.capacity = capacity, f.thr_s = thr_s, f.thr_n = thr_n;
+  return enable_summary(s, s->curves, "curves", capacity > 0, f.row_at(c, s->n, 0) * sizeof(unsigned long long), [&](CurvesSummary& x) {
+    x = std::move(f);
+    hipError_t e = x.rows.alloc(x.row_at(c, s->n, 0));
+    if (e == hipSuccess) e = x.scratch.alloc(x.scratch_at(c, s->n));
+    return e;
+  });
 }
 
 int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections, double* titer_sums,
                        int64_t* n_draws) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_curves) return fail(ABD_ERR_STATE, "curves are not enabled (abd_sampler_enable_curves)");
+  if (!s->curves.on()) return fail(ABD_ERR_STATE, "curves are not enabled (abd_sampler_enable_curves)");
   const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
   if (n_draws) *n_draws = have;
   if (first < 0 || count < 0 || first > have || count > have - first)
@@ -1217,8 +1264,7 @@ int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, 
   HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
   const size_t n_row = curves_row_cols(c), G = (size_t)c->G;
   std::vector<unsigned long long> h((size_t)count * n_row);
-  HIP_TRY(hipMemcpy(h.data(), s->d_curves + ((size_t)k * s->curves_capacity + (size_t)first) * n_row, h.size() * sizeof(unsigned long long),
-                    hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), s->curves.rows + s->curves.row_at(c, k, first), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   for (size_t d = 0; d < (size_t)count; ++d)
     split_curves_row(c, h.data() + d * n_row, counts ? counts + d * 4 * G : nullptr, n_infections ? n_infections + d * 8 : nullptr,
                      titer_sums ? titer_sums + d * 2 * G : nullptr);
@@ -1229,45 +1275,27 @@ int abd_sampler_enable_diagnostics(abd_sampler* s, int64_t planned_draws, int64_
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (planned_draws < 0 || planned_draws == 1) return fail(ABD_ERR_ARG, "diagnostics: planned_draws=%lld is neither 0 nor >= 2", (long long)planned_draws);
   if (planned_draws && batch_len < 1) return fail(ABD_ERR_ARG, "diagnostics: batch_len=%lld is below 1", (long long)batch_len);
-  if (s->ran) return fail(ABD_ERR_STATE, "diagnostics must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  s->d_diag_tit.reset();  // (nothing has been launched on them: the sampler has not run)
-  s->d_diag_inf.reset();
-  s->d_diag_cb2.reset();
-  s->d_diag_stage.reset();
-  s->diag_draws = s->diag_H = s->diag_L = 0;
-  if (planned_draws == 0) return ABD_OK;
-  const size_t cells = (size_t)c->G * c->N, n = (size_t)s->n;
-  const size_t bytes = n * cells * (2 * 7 * sizeof(double) + 4 * sizeof(uint32_t) + sizeof(unsigned long long)) + cells * sizeof(unsigned long long);
-  DevBuf<double> tit;  // (the sampler takes all four or none)
-  DevBuf<uint32_t> inf;
-  DevBuf<unsigned long long> cb2, stage;
-  hipError_t e = tit.alloc_zero(std::max<size_t>(1, n * 2 * 7 * cells), c->stream);
-  if (e == hipSuccess) e = inf.alloc_zero(std::max<size_t>(1, n * 4 * cells), c->stream);
-  if (e == hipSuccess) e = cb2.alloc_zero(std::max<size_t>(1, n * cells), c->stream);
-  if (e == hipSuccess) e = stage.alloc(std::max<size_t>(1, cells));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "diagnostics: %zu bytes of device memory", bytes);
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "diagnostics: %s", hipGetErrorString(e));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  s->d_diag_tit = std::move(tit);
-  s->d_diag_inf = std::move(inf);
-  s->d_diag_cb2 = std::move(cb2);
-  s->d_diag_stage = std::move(stage);
-  s->diag_draws = planned_draws;
-  s->diag_H = planned_draws / 2;
-  s->diag_L = batch_len;
-  return ABD_OK;
+  const abd_ctx* c = s->c;
+  DiagSummary f;
+  f.draws = planned_draws, f.H = planned_draws / 2, f.L = batch_len;
+  const size_t cells = (size_t)c->G * c->N;
+  const size_t bytes =
+      f.tit_at(c, s->n) * sizeof(double) + f.inf_at(c, s->n) * sizeof(uint32_t) + (f.cb2_at(c, s->n) + cells) * sizeof(unsigned long long);
+  return enable_summary(s, s->diag, "diagnostics", planned_draws > 0, bytes, [&](DiagSummary& x) {
+    x = std::move(f);
+    hipError_t e = x.tit.alloc_zero(std::max<size_t>(1, x.tit_at(c, s->n)), c->stream);
+    if (e == hipSuccess) e = x.inf.alloc_zero(std::max<size_t>(1, x.inf_at(c, s->n)), c->stream);
+    if (e == hipSuccess) e = x.cb2.alloc_zero(std::max<size_t>(1, x.cb2_at(c, s->n)), c->stream);
+    if (e == hipSuccess) e = x.stage.alloc(std::max<size_t>(1, cells));
+    return e;
+  });
 }
 
 int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double* ab_n_mu, double* ab_s_mu, int64_t* info) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_diag_tit) return fail(ABD_ERR_STATE, "diagnostics are not enabled (abd_sampler_enable_diagnostics)");
-  const int64_t H = s->diag_H, L = s->diag_L, B = H / L;
+  if (!s->diag.on()) return fail(ABD_ERR_STATE, "diagnostics are not enabled (abd_sampler_enable_diagnostics)");
+  const int64_t H = s->diag.H, L = s->diag.L, B = H / L;
   const int64_t have = std::max<int64_t>(0, s->it - s->o.tune), n0 = std::min(have, H), n1 = std::min(std::max<int64_t>(0, have - H), H);
   if (info) {
     info[0] = n0;
@@ -1283,26 +1311,25 @@ int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double
   // one plane at a time through the staging plane: transposed on the device, copied out (the copy waits for the kernel and
   // the next kernel for the copy: the context's stream)
   auto plane = [&](const void* src, int stride, int width, void* out) -> int {
-    if (int rc = launch_diag_export(c, src, stride, width, s->d_diag_stage, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s->d_diag_stage, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = launch_diag_export(c, src, stride, width, s->diag.stage, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, s->diag.stage, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return ABD_OK;
   };
   if (!cells) return ABD_OK;
   if (i_counts) {
-    const uint32_t* inf = s->d_diag_inf + (size_t)k * 4 * cells;
+    const uint32_t* inf = s->diag.inf + s->diag.inf_at(c, k);
     const int comp[3] = {0, 1, 3};  // c_h0, c_h1, sum_cb of the 16-byte element (cur is not handed out)
     for (int v = 0; v < 3; ++v)
       if (int rc = plane(inf + comp[v], 16, 4, i_counts + (size_t)v * cells)) return rc;
-    if (int rc = plane(s->d_diag_cb2 + (size_t)k * cells, 8, 8, i_counts + 3 * cells)) return rc;
+    if (int rc = plane(s->diag.cb2 + s->diag.cb2_at(c, k), 8, 8, i_counts + 3 * cells)) return rc;
   }
   double* outs[2] = {ab_n_mu, ab_s_mu};
   const int planes[6] = {0, 1, 2, 3, 5, 6};  // mean_h0, M2_h0, mean_h1, M2_h1, bm_mean, bm_M2 (cur is not handed out)
   for (int x = 0; x < 2; ++x) {
     if (!outs[x]) continue;
-    const double* tit = s->d_diag_tit + ((size_t)k * 2 + x) * 7 * cells;
     for (int v = 0; v < 6; ++v)
-      if (int rc = plane(tit + (size_t)planes[v] * cells, 8, 8, outs[x] + (size_t)v * cells)) return rc;
+      if (int rc = plane(s->diag.tit + s->diag.tit_at(c, k, x, planes[v]), 8, 8, outs[x] + (size_t)v * cells)) return rc;
   }
   return ABD_OK;
 }
@@ -1317,47 +1344,28 @@ int abd_sampler_enable_timelines(abd_sampler* s, int64_t planned_draws, double l
       if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi) || !std::isfinite(x.hi - x.lo))
         return fail(ABD_ERR_ARG, "timelines: the range [%g, %g) of %s is not finite and ascending", x.lo, x.hi, x.name);
   }
-  if (s->ran) return fail(ABD_ERR_STATE, "timelines must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  s->d_tl_hist.reset();  // (nothing has been launched on them: the sampler has not run)
-  s->d_tl_cell.reset();
-  s->d_tl_ninf.reset();
-  s->d_tl_stage.reset();
-  s->tl_draws = 0;
-  s->tl_stage_bytes = 0;
-  if (planned_draws == 0) return ABD_OK;
-  const size_t cells = (size_t)c->G * c->N, n = (size_t)s->n, line = ABD_TIMELINE_BINS * sizeof(uint16_t);
+  const abd_ctx* c = s->c;
+  TimelineSummary f;
+  f.draws = planned_draws;
+  f.range_n[0] = lo_n, f.range_n[1] = hi_n, f.range_s[0] = lo_s, f.range_s[1] = hi_s;
   // staging of the read-out: a plane of 8 bytes per cell, and at least one gap's row of histograms
-  const size_t stage_bytes = std::max(cells * sizeof(unsigned long long), (size_t)c->N * line);
-  const size_t bytes = n * (cells * (2 * line + 2 * sizeof(uint32_t)) + (size_t)c->N * ABD_TIMELINE_NINF * sizeof(uint32_t)) + stage_bytes;
-  DevBuf<uint32_t> hist, cell, ninf;  // (the sampler takes all four or none)
-  DevBuf<unsigned long long> stage;
-  hipError_t e = hist.alloc_zero(n * 2 * cells * (line / sizeof(uint32_t)), c->stream);
-  if (e == hipSuccess) e = cell.alloc_zero(n * 2 * cells, c->stream);
-  if (e == hipSuccess) e = ninf.alloc_zero(n * ABD_TIMELINE_NINF * (size_t)c->N, c->stream);
-  if (e == hipSuccess) e = stage.alloc(stage_bytes / sizeof(unsigned long long));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "timelines: %zu bytes of device memory", bytes);
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "timelines: %s", hipGetErrorString(e));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  s->d_tl_hist = std::move(hist);
-  s->d_tl_cell = std::move(cell);
-  s->d_tl_ninf = std::move(ninf);
-  s->d_tl_stage = std::move(stage);
-  s->tl_stage_bytes = stage_bytes;
-  s->tl_draws = planned_draws;
-  s->tl_range_n[0] = lo_n, s->tl_range_n[1] = hi_n, s->tl_range_s[0] = lo_s, s->tl_range_s[1] = hi_s;
-  return ABD_OK;
+  f.stage_bytes = std::max((size_t)c->G * c->N * sizeof(unsigned long long), (size_t)c->N * ABD_TIMELINE_BINS * sizeof(uint16_t));
+  const size_t bytes = (f.hist_at(c, s->n) + f.cell_at(c, s->n) + f.ninf_at(c, s->n)) * sizeof(uint32_t) + f.stage_bytes;
+  return enable_summary(s, s->timelines, "timelines", planned_draws > 0, bytes, [&](TimelineSummary& x) {
+    x = std::move(f);
+    hipError_t e = x.hist.alloc_zero(x.hist_at(c, s->n), c->stream);
+    if (e == hipSuccess) e = x.cell.alloc_zero(x.cell_at(c, s->n), c->stream);
+    if (e == hipSuccess) e = x.ninf.alloc_zero(x.ninf_at(c, s->n), c->stream);
+    if (e == hipSuccess) e = x.stage.alloc(x.stage_bytes / sizeof(unsigned long long));
+    return e;
+  });
 }
 
 int abd_sampler_timelines(abd_sampler* s, int32_t k, uint16_t* hist_n, uint16_t* hist_s, int64_t* inf, int64_t* cum, int64_t* ninf,
                           int64_t* n_draws) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_tl_hist) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
+  if (!s->timelines.on()) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
   if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
   if (!hist_n && !hist_s && !inf && !cum && !ninf) return ABD_OK;
   abd_ctx* c = s->c;
@@ -1368,26 +1376,26 @@ int abd_sampler_timelines(abd_sampler* s, int32_t k, uint16_t* hist_n, uint16_t*
   int64_t* planes[2] = {inf, cum};
   for (int v = 0; v < 2; ++v) {
     if (!planes[v]) continue;
-    if (int rc = launch_diag_export(c, s->d_tl_cell + (size_t)k * 2 * cells + v, 8, 4, s->d_tl_stage, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(planes[v], s->d_tl_stage, cells * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = launch_diag_export(c, s->timelines.cell + s->timelines.cell_at(c, k) + v, 8, 4, s->timelines.stage, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(planes[v], s->timelines.stage, cells * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
   uint16_t* hists[2] = {hist_n, hist_s};
-  const int rows = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->G, s->tl_stage_bytes / (N * line)));  // gap rows per pass
+  const int rows = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->G, s->timelines.stage_bytes / (N * line)));  // gap rows per pass
   for (int v = 0; v < 2; ++v) {
     if (!hists[v]) continue;
-    const uint32_t* src = s->d_tl_hist + ((size_t)k * 2 + v) * cells * (line / sizeof(uint32_t));
+    const uint32_t* src = s->timelines.hist + s->timelines.hist_at(c, k, v);
     for (int g0 = 0; g0 < c->G; g0 += rows) {
       const int n_g = std::min(rows, c->G - g0);
-      if (int rc = launch_timeline_hist_export(c, src, g0, n_g, s->d_tl_stage, c->stream)) return rc;
-      HIP_TRY(hipMemcpyAsync(hists[v] + (size_t)g0 * N * ABD_TIMELINE_BINS, s->d_tl_stage, (size_t)n_g * N * line, hipMemcpyDeviceToHost,
+      if (int rc = launch_timeline_hist_export(c, src, g0, n_g, s->timelines.stage, c->stream)) return rc;
+      HIP_TRY(hipMemcpyAsync(hists[v] + (size_t)g0 * N * ABD_TIMELINE_BINS, s->timelines.stage, (size_t)n_g * N * line, hipMemcpyDeviceToHost,
                              c->stream));
       HIP_TRY(hipStreamSynchronize(c->stream));
     }
   }
   if (ninf) {
     std::vector<uint32_t> h(N * ABD_TIMELINE_NINF);
-    HIP_TRY(hipMemcpy(h.data(), s->d_tl_ninf + (size_t)k * ABD_TIMELINE_NINF * N, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data(), s->timelines.ninf + s->timelines.ninf_at(c, k), h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t e = 0; e < h.size(); ++e) ninf[e] = (int64_t)h[e];
   }
   return ABD_OK;
@@ -1399,12 +1407,12 @@ int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q,
   if (!q) return fail(ABD_ERR_ARG, "timelines: q is NULL");
   for (int e = 0; e < n_q; ++e)
     if (!(q[e] >= 0.0 && q[e] <= 1.0)) return fail(ABD_ERR_ARG, "timelines: q[%d]=%g outside [0, 1]", e, q[e]);
-  if (!s->d_tl_hist) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
+  if (!s->timelines.on()) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
   if (!out_n && !out_s) return ABD_OK;
   abd_ctx* c = s->c;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t cells = (size_t)c->G * c->N, words = ABD_TIMELINE_BINS / 2;
+  const size_t cells = (size_t)c->G * c->N;
   DevBuf<double> d_q, d_out;  // the read-out's own: n_q planes of 8 bytes per cell
   hipError_t e = d_q.upload(q, (size_t)n_q);
   if (e == hipSuccess) e = d_out.alloc((size_t)n_q * cells);
@@ -1414,11 +1422,12 @@ int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q,
   }
   if (e != hipSuccess) return fail(ABD_ERR_HIP, "timelines: %s", hipGetErrorString(e));
   double* outs[2] = {out_n, out_s};
-  const double* ranges[2] = {s->tl_range_n, s->tl_range_s};
+  const double* ranges[2] = {s->timelines.range_n, s->timelines.range_s};
   for (int v = 0; v < 2; ++v) {
     if (!outs[v]) continue;
-    if (int rc = launch_timeline_quantiles(c, s->d_tl_hist + (size_t)v * cells * words, (int64_t)(2 * cells * words), s->n, ranges[v], n_q, d_q,
-                                           d_out, c->stream))
+    const TimelineSummary& tl = s->timelines;  // (chain 0's plane of titer v; a chain's planes are hist_at(c, 1) words apart)
+    if (int rc = launch_timeline_quantiles(c, tl.hist + tl.hist_at(c, 0, v), (int64_t)tl.hist_at(c, 1), s->n, ranges[v], n_q, d_q, d_out,
+                                           c->stream))
       return rc;
     HIP_TRY(hipMemcpyAsync(outs[v], d_out, (size_t)n_q * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1429,36 +1438,24 @@ int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q,
 int abd_sampler_enable_risk(abd_sampler* s, int64_t capacity, const abd_risk_spec* spec) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
-  if (s->ran) return fail(ABD_ERR_STATE, "risk must be enabled before the first abd_sampler_run call");
-  abd_ctx* c = s->c;
-  if (capacity > 0)
+  const abd_ctx* c = s->c;
+  if (capacity > 0 && !s->ran)  // (a sampler that has run is refused below, whatever the spec)
     if (int rc = check_risk_spec(c, spec)) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  s->d_risk.reset();  // (nothing has been launched on them: the sampler has not run)
-  s->d_risk_scratch.reset();
-  s->risk_capacity = 0;
-  if (capacity == 0) return ABD_OK;
-  const size_t n_counts = (size_t)s->n * (size_t)capacity * risk_table_cols(c);
-  DevBuf<uint32_t> rows;
-  DevBuf<unsigned long long> scratch;  // (the sampler takes both or neither)
-  hipError_t e = rows.alloc(n_counts);
-  if (e == hipSuccess) e = scratch.alloc((size_t)s->n * risk_scratch_cols(c));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "risk: %zu bytes of device memory", n_counts * sizeof(uint32_t));
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "risk: %s", hipGetErrorString(e));
-  s->d_risk = std::move(rows);
-  s->d_risk_scratch = std::move(scratch);
-  s->risk_capacity = capacity;
-  s->risk_spec = *spec;
-  return ABD_OK;
+  RiskSummary f;
+  f.capacity = capacity;
+  if (capacity > 0 && spec) f.spec = *spec;
+  return enable_summary(s, s->risk, "risk", capacity > 0, f.table_at(c, s->n, 0) * sizeof(uint32_t), [&](RiskSummary& x) {
+    x = std::move(f);
+    hipError_t e = x.tables.alloc(x.table_at(c, s->n, 0));
+    if (e == hipSuccess) e = x.scratch.alloc(x.scratch_at(c, s->n));
+    return e;
+  });
 }
 
 int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* table, int64_t* n_draws) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_risk) return fail(ABD_ERR_STATE, "risk is not enabled (abd_sampler_enable_risk)");
+  if (!s->risk.on()) return fail(ABD_ERR_STATE, "risk is not enabled (abd_sampler_enable_risk)");
   const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
   if (n_draws) *n_draws = have;
   if (first < 0 || count < 0 || first > have || count > have - first)
@@ -1470,8 +1467,7 @@ int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, in
   HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
   const size_t n_tab = risk_table_cols(c);
   std::vector<uint32_t> h((size_t)count * n_tab);
-  HIP_TRY(hipMemcpy(h.data(), s->d_risk + ((size_t)k * s->risk_capacity + (size_t)first) * n_tab, h.size() * sizeof(uint32_t),
-                    hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h.data(), s->risk.tables + s->risk.table_at(c, k, first), h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (size_t e = 0; e < h.size(); ++e) table[e] = (int64_t)h[e];
   return ABD_OK;
 }

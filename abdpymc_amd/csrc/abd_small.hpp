@@ -2,7 +2,7 @@
 // Deterministics (abd.py:649/667, 341, 389-391), the hardware-queue probe.
 #pragma once
 
-#include "abd_device.hpp"
+#include "abd_cells.hpp"
 #include "abd_planes.hpp"
 
 // One wave that stays on the device for `ticks` of the 100 MHz s_memrealtime counter and says when (abd_context.hip:
@@ -131,57 +131,40 @@ __global__ __launch_bounds__(64) void abd_planes_kernel(const PlaneArgs a) {
 
 // Deterministics "i", "ab_n_mu", "ab_s_mu" for one chain, written (G, N) gap-major as PyMC records them;
 // with `sums` ([3][G*N]: i, ab_n_mu, ab_s_mu) they are also added to running sums (posterior means on device).
+// The titers are cell_titers (abd_cells.hpp): the per-draw summaries reduce the same values.
 template <int MT>
-__global__ __launch_bounds__(ABD_BLOCK) void abd_deterministics_kernel(const EvalArgs a, int8_t* __restrict__ out_i,
+__global__ __launch_bounds__(ABD_BLOCK) void abd_deterministics_kernel(const CellWalk w, int8_t* __restrict__ out_i,
                                                                        double* __restrict__ out_mun,
                                                                        double* __restrict__ out_mus,
                                                                        double* __restrict__ sums) {
   extern __shared__ __align__(16) unsigned char smem[];
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  const int G = a.G, N = a.N, nt = a.nt, tstride = G + 1;
-  double2_t* tab_ones = tabs + 2 * tstride;
+  const int G = w.G, N = w.N, nt = w.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const ChainPar& p = a.ch[0];
-  fill_pow_table(tabs, p.rho_n, tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, p.rho_s, tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
-  __syncthreads();
+  const CellTables tabs = cell_tables(smem, w, tid);
   const int waves_total = gridDim.x * ABD_WAVES_PER_BLOCK;
   for (int j = blockIdx.x * ABD_WAVES_PER_BLOCK + wave; j < N; j += waves_total) {
-    uint64_t V[MT], I[MT];  // vaccinations; the chain's constrained infections (kept with the slot)
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      V[t] = I[t] = 0;
-      if (t < nt) {
-        V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-        I[t] = uniform_word(p.iw, (int64_t)t * N + j);
-      }
-    }
-    const bool wj = __builtin_amdgcn_readfirstlane((int)p.waner[j]) != 0;
-    const double2_t* ts = wj ? tabs + tstride : tab_ones;
+    uint64_t V[MT], I[MT];
+    const double2_t* ts = load_individual<MT>(w, j, tabs, V, I);
     for (int t = 0; t < nt; ++t) {
       const int g = t * 64 + lane;
       if (g < G) {
-        const Resp rs = responses<MT>(g, t + 1, I, V, tabs, ts);
+        const CellTiters c = cell_titers<MT>(w, V, I, tabs.tab_n, ts, g, t + 1);
         const int64_t o = (int64_t)g * N + j;
         const int bit = (int)((I[t] >> lane) & 1ull);
-        const double mun = p.init_n + (rs.cum_i ? p.perm_n : 0.0) + p.temp_n * rs.un;
-        const double mus = p.init_s + (rs.cum_iv ? p.perm_s : 0.0) + rs.us;
         if (out_i) out_i[o] = (int8_t)bit;
-        if (out_mun) out_mun[o] = mun;
-        if (out_mus) out_mus[o] = mus;
+        if (out_mun) out_mun[o] = c.mun;
+        if (out_mus) out_mus[o] = c.mus;
         if (sums) {
           const int64_t cells = (int64_t)G * N;
           sums[o] += (double)bit;
-          sums[cells + o] += mun;
-          sums[2 * cells + o] += mus;
+          sums[cells + o] += c.mun;
+          sums[2 * cells + o] += c.mus;
         }
       }
     }
   }
 }
-
 
 // packed words [nt][N] -> (G, N) gap-major int8, for reading a chain's i_raw back
 __global__ __launch_bounds__(256) void abd_unpack_bits_kernel(const uint64_t* __restrict__ src, int8_t* __restrict__ dst,

@@ -113,69 +113,46 @@ struct alignas(8) TimelineCell {  // a cell of i
 
 #if defined(__HIPCC__)
 
-#include "abd_device.hpp"
+#include "abd_cells.hpp"
 
-// The launch's own small argument block (a 2 KB EvalArgs would take the scalar registers the packed words live in)
+// The launch's argument block: the walk and the timelines' own fields
 struct TimelineArgs {
-  const uint64_t* vw;     // [nt][N] packed vaccinations
-  const uint64_t* iw;     // [nt][N] the chain slot's constrained infections
-  const int8_t* waner;    // [N]
-  const int32_t* last;    // [N] end of follow-up; nullptr: G - 1 for everyone
+  CellWalk w;
   uint32_t* hist_n;       // the chain's [N * G][32] words = [N * G][64] 16-bit counters of ab_n_mu
   uint32_t* hist_s;       // ... of ab_s_mu
   abdi::TimelineCell* cell;  // [N * G]
   uint32_t* ninf;         // [N][8]
-  double rho_n, rho_s, init_n, perm_n, temp_n, init_s, perm_s;
   abdi::TimelineRange rn, rs;
-  int32_t G, N, nt;
   int32_t n_splits, s0, s1;  // the chunks' inner borders
 };
 
-// One draw of one chain into its timeline counters.  The walker is abd_diag_kernel's (one wave per individual, lanes over the
-// gaps of a word) and the titers are the expressions of abd_deterministics_kernel (abd_small.hpp), not a third formula.  Reads
-// the slot's state and indicator words only: dense and list cohorts run the same code.
+// One draw of one chain into its timeline counters.  The walk is abd_diag_kernel's and the titers are cell_titers
+// (abd_cells.hpp), what abd_deterministics_kernel records: not a third formula.  Reads the slot's state and indicator words
+// only: dense and list cohorts run the same code.
 template <int MT>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_timeline_kernel(const TimelineArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
-  double2_t* tabs = reinterpret_cast<double2_t*>(smem);
-  const int G = a.G, N = a.N, nt = a.nt, tstride = G + 1;
-  double2_t* tab_ones = tabs + 2 * tstride;
+  const CellWalk& w = a.w;
+  const int G = w.G, N = w.N, nt = w.nt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  fill_pow_table(tabs, a.rho_n, tstride, tid, ABD_BLOCK);
-  fill_pow_table(tabs + tstride, a.rho_s, tstride, tid, ABD_BLOCK);
-  fill_ones_table(tab_ones, tstride, tid, ABD_BLOCK);
-  __syncthreads();
+  const CellTables tabs = cell_tables(smem, w, tid);
   const int waves_total = gridDim.x * ABD_WAVES_PER_BLOCK;
   for (int j = blockIdx.x * ABD_WAVES_PER_BLOCK + wave; j < N; j += waves_total) {
-    const int last = a.last ? __builtin_amdgcn_readfirstlane(a.last[j]) : G - 1;
+    const int last = last_gap(w, j);
     uint64_t V[MT], I[MT];
-    int n_inf = 0;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      V[t] = I[t] = 0;
-      if (t < nt) {
-        V[t] = uniform_word(a.vw, (int64_t)t * N + j);
-        I[t] = uniform_word(a.iw, (int64_t)t * N + j);
-        const int rel = last - t * 64;  // bits <= rel of this word are followed gaps
-        const uint64_t le = rel >= 63 ? ~0ull : (rel < 0 ? 0ull : ((2ull << rel) - 1ull));
-        n_inf += __builtin_popcountll(I[t] & le);
-      }
-    }
+    const double2_t* ts = load_individual<MT>(w, j, tabs, V, I);
+    const int n_inf = followed_infections<MT>(I, last, nt);
     // the individual's row of ninf: one counter moves, its lane's (a never-followed individual's row stays 0)
     if (last >= 0 && lane == min(n_inf, ABD_TL_NINF - 1)) a.ninf[(int64_t)j * ABD_TL_NINF + lane] += 1u;
-    const bool wj = __builtin_amdgcn_readfirstlane((int)a.waner[j]) != 0;
-    const double2_t* ts = wj ? tabs + tstride : tab_ones;
     for (int t = 0; t < nt; ++t) {
       const int g = t * 64 + lane;
       if (g < G) {
         const int64_t o = (int64_t)j * G + g;  // individual-major: the cell's own line in either histogram
         abdi::TimelineCell ci = a.cell[o];  // (in flight while the responses are summed)
-        const Resp rs = responses<MT>(g, t + 1, I, V, tabs, ts);
-        const double mun = a.init_n + (rs.cum_i ? a.perm_n : 0.0) + a.temp_n * rs.un;
-        const double mus = a.init_s + (rs.cum_iv ? a.perm_s : 0.0) + rs.us;
-        const int bn = abdi::timeline_bin(mun, a.rn.lo, a.rn.hi, a.rn.inv_w);
-        const int bs = abdi::timeline_bin(mus, a.rs.lo, a.rs.hi, a.rs.inv_w);
+        const CellTiters c = cell_titers<MT>(w, V, I, tabs.tab_n, ts, g, t + 1);
+        const int bn = abdi::timeline_bin(c.mun, a.rn.lo, a.rn.hi, a.rn.inv_w);
+        const int bs = abdi::timeline_bin(c.mus, a.rs.lo, a.rs.hi, a.rs.inv_w);
         uint32_t* wn = a.hist_n + o * (ABD_TL_BINS / 2) + (bn >> 1);
         uint32_t* ws = a.hist_s + o * (ABD_TL_BINS / 2) + (bs >> 1);
         const uint32_t hn = *wn, hs = *ws;
