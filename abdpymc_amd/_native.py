@@ -237,6 +237,15 @@ def _ptr(arr, ctype=None):
         return arr.ctypes.data
 
 
+def _theta(theta):
+    """``theta`` as the (17,) float64 array one evaluation takes.  (``Context``'s timed evaluation methods check inline: a call
+    costs them.)"""
+    t = _as(theta, np.float64)
+    if t.shape != (N_THETA,):
+        raise ValueError(f"theta must have shape ({N_THETA},)")
+    return t
+
+
 def _out(arr, dtype, shape=None, name="output array"):
     """Address of an array the LIBRARY WRITES: it must be writeable, C-contiguous, of the exact dtype (ctypes sees only an
     address, so nothing else would catch a read-only memmap or a float32 buffer before the library writes through it)."""
@@ -533,9 +542,7 @@ class Context:
         {"counts": (4, G) int64 -- infected, ever_infected, seropos_s, seropos_n --, "n_infections": (8,) int64,
         "titer_sums": (2, G) -- ab_s_mu, ab_n_mu}: ``curves.from_deterministics`` of ``deterministics(chain, theta)`` under
         the context's follow-up (``set_follow_up``)."""
-        t = _as(theta, np.float64)
-        if t.shape != (N_THETA,):
-            raise ValueError(f"theta must have shape ({N_THETA},)")
+        t = _theta(theta)
         G = self.n_gaps
         counts, n_inf, sums = np.empty((4, G), np.int64), np.empty(8, np.int64), np.empty((2, G))
         _check(self._lib, self._lib.abd_curves(self._h, int(chain), _ptr(t, C.c_double), float(thr_s), float(thr_n),
@@ -546,9 +553,7 @@ class Context:
         """The infection-risk-by-titer table of (theta, the chain slot's discrete state), reduced over the individuals on the
         device -> (2, 2, G, 8) int64, antigen (S, N) x (at risk, events) x gap x bin: ``risk.from_deterministics`` of
         ``deterministics(chain, theta)`` under the context's follow-up (``set_follow_up``) and ``spec`` (``risk.spec``)."""
-        t = _as(theta, np.float64)
-        if t.shape != (N_THETA,):
-            raise ValueError(f"theta must have shape ({N_THETA},)")
+        t = _theta(theta)
         sp = _risk_spec(spec)
         table = np.empty((2, 2, self.n_gaps, 8), np.int64)
         _check(self._lib, self._lib.abd_risk(self._h, int(chain), _ptr(t, C.c_double), C.byref(sp), _out(table, np.int64)))
@@ -557,9 +562,7 @@ class Context:
     def pointwise_loglik(self, chain: int, theta):
         """Log-density of every OD reading at (theta, the chain slot's discrete state) -> (ll_s, ll_n), each in the order the
         readings were given (what ``pm.compute_log_likelihood`` records per draw for ``it_s_lik`` / ``it_n_lik``)."""
-        t = _as(theta, np.float64)
-        if t.shape != (N_THETA,):
-            raise ValueError(f"theta must have shape ({N_THETA},)")
+        t = _theta(theta)
         ll_s, ll_n = np.empty(self.n_obs_s), np.empty(self.n_obs_n)
         _check(self._lib, self._lib.abd_pointwise_loglik(self._h, int(chain), _ptr(t, C.c_double), _ptr(ll_s, C.c_double),
                                                          _ptr(ll_n, C.c_double)))
@@ -570,9 +573,7 @@ class Context:
         each in the order the readings were given; ``mean=True`` adds the noise-free means (m_s, m_n).  The normals are keyed
         by (seed, stream, draw) and the reading (abd_hip.h: abd_posterior_predictive): the native sampler's recorded replicate
         of chain c at iteration t is ``posterior_predictive(.., seed, chain_offset + c, t)``."""
-        t = _as(theta, np.float64)
-        if t.shape != (N_THETA,):
-            raise ValueError(f"theta must have shape ({N_THETA},)")
+        t = _theta(theta)
         y_s, y_n = np.empty(self.n_obs_s), np.empty(self.n_obs_n)
         m_s, m_n = (np.empty(self.n_obs_s), np.empty(self.n_obs_n)) if mean else (None, None)
         _check(self._lib, self._lib.abd_posterior_predictive(
@@ -619,9 +620,7 @@ class Context:
 
     def theta_prior(self, theta):
         """The theta-only part of the joint logp (continuous priors + Jacobians) and its gradient."""
-        t = _as(theta, np.float64)
-        if t.shape != (N_THETA,):
-            raise ValueError(f"theta must have shape ({N_THETA},)")
+        t = _theta(theta)
         out = C.c_double()
         g = np.empty(N_THETA)
         _check(self._lib, self._lib.abd_theta_prior(self._h, _ptr(t, C.c_double), C.byref(out), _ptr(g, C.c_double)))
@@ -635,18 +634,31 @@ class Context:
                 dense_metric: bool = False, pointwise: bool = False, predictive: bool = False, curves: int = 0,
                 sero_thresholds=None, diagnostics=None, risk: int = 0, risk_spec=None, timelines=None) -> "NativeSampler":
         """The compound step [NUTS; Gibbs sweep] for several chains, driven inside the library: the chains advance as
-        independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  ``pointwise``: accumulate the
-        pointwise log-likelihood statistics of every draw on the device (``NativeSampler.pointwise_stats``); ``predictive``:
-        the posterior predictive check statistics (``NativeSampler.predictive_stats``); ``curves``: keep the epidemic curves
-        of that many draws per chain on the device (``NativeSampler.curves``), seropositive at ``sero_thresholds`` = (thr_s,
-        thr_n) on the titer scale (``None``: off); ``diagnostics`` = (D, L): accumulate per cell what split R-hat and a
-        batch-means ESS need over the D planned draws, in batches of L (``NativeSampler.diagnostics``; ``None``: off); ``risk``:
-        keep the infection-risk-by-titer table of that many draws per chain on the device, counted under ``risk_spec``
-        (``risk.spec``; ``NativeSampler.risk``); ``timelines`` = (D, (lo_n, hi_n), (lo_s, hi_s)): accumulate per cell the titer
-        histograms over those ranges and the infection timing counters over the D planned draws (``NativeSampler.timelines`` /
-        ``timeline_quantiles``; ``None``: off)."""
-        return NativeSampler(self, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate, chain_offset,
-                             dense_metric, pointwise, predictive, curves, sero_thresholds, diagnostics, risk, risk_spec, timelines)
+        independent units on their own HIP streams (abd_hip.h: abd_sampler_create).  The summary keywords map onto
+        ``NativeSampler``'s ``enable_*`` methods, which say what each keeps: ``pointwise`` / ``predictive``: on or off;
+        ``curves`` / ``risk``: the draws per chain to keep (0: off), with ``sero_thresholds`` / ``risk_spec``; ``diagnostics`` = (D,
+        L) and ``timelines`` = (D, (lo_n, hi_n), (lo_s, hi_s)) for D planned draws (``None``: off)."""
+        if int(curves) < 0:
+            raise ValueError(f"curves must be a number of draws >= 0, got {curves}")
+        if int(risk) < 0:
+            raise ValueError(f"risk must be a number of draws >= 0, got {risk}")
+        if int(risk) and risk_spec is None:
+            raise ValueError("risk needs a risk_spec (risk.spec)")
+        smp = NativeSampler(self, chains, theta0, tune=tune, seed=seed, target_accept=target_accept, max_treedepth=max_treedepth,
+                            gibbs=gibbs, accumulate=accumulate, chain_offset=chain_offset, dense_metric=dense_metric)
+        if pointwise:
+            smp.enable_pointwise()
+        if predictive:
+            smp.enable_predictive()
+        if int(curves):
+            smp.enable_curves(curves, sero_thresholds)
+        if diagnostics is not None:
+            smp.enable_diagnostics(*diagnostics)
+        if int(risk):
+            smp.enable_risk(risk, risk_spec)
+        if timelines is not None:
+            smp.enable_timelines(*timelines)
+        return smp
 
     # -- measurement --------------------------------------------------------------------------
     def kernel_timing(self, mode):
@@ -724,9 +736,8 @@ class NativeSampler:
     """``abd_sampler_*``: what ``pm.sample`` runs for this model (abd.py:921-922): independent chains, one evaluation launch
     per leapfrog of a unit of 1-4 chains, leapfrog trains (abd_hip.h)."""
 
-    def __init__(self, ctx: Context, chains, theta0, tune, seed, target_accept, max_treedepth, gibbs, accumulate,
-                 chain_offset=0, dense_metric=False, pointwise=False, predictive=False, curves=0, sero_thresholds=None,
-                 diagnostics=None, risk=0, risk_spec=None, timelines=None):
+    def __init__(self, ctx: Context, chains, theta0, tune, seed=0, target_accept=0.8, max_treedepth=10, gibbs=True,
+                 accumulate=False, chain_offset=0, dense_metric=False):
         self._ctx = ctx  # keeps the context alive
         self._lib = ctx._lib
         self._h = _P()
@@ -735,6 +746,7 @@ class NativeSampler:
         if t0.shape != (ch.size, N_THETA):
             raise ValueError(f"theta0 must have shape ({ch.size}, {N_THETA})")
         self.n = int(ch.size)
+        self.n_obs = (ctx.n_obs_s, ctx.n_obs_n)  # readings of it_s_lik / it_n_lik
         self._chains = ch.copy()
         o = _SamplerOpts()
         o.tune, o.seed = int(tune), int(seed) & (2**64 - 1)
@@ -745,37 +757,43 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_create(ctx._h, self.n, _ptr(ch, C.c_int32), _ptr(t0, C.c_double), C.byref(o),
                                                        C.byref(self._h)))
         ctx._samplers.add(self)
-        if pointwise:
-            _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
-        if predictive:
-            _check(self._lib, self._lib.abd_sampler_enable_predictive(self._h, 1))
-        if int(curves) < 0:
-            raise ValueError(f"curves must be a number of draws >= 0, got {curves}")
-        if int(curves):
-            thr_s, thr_n = (np.inf, np.inf) if sero_thresholds is None else sero_thresholds
-            _check(self._lib, self._lib.abd_sampler_enable_curves(self._h, int(curves), float(thr_s), float(thr_n)))
-        if diagnostics is not None:
-            planned, batch = diagnostics
-            _check(self._lib, self._lib.abd_sampler_enable_diagnostics(self._h, int(planned), int(batch)))
-        if int(risk) < 0:
-            raise ValueError(f"risk must be a number of draws >= 0, got {risk}")
-        if int(risk):
-            if risk_spec is None:
-                raise ValueError("risk needs a risk_spec (risk.spec)")
-            sp = _risk_spec(risk_spec)
-            _check(self._lib, self._lib.abd_sampler_enable_risk(self._h, int(risk), C.byref(sp)))
-        if timelines is not None:
-            planned, (lo_n, hi_n), (lo_s, hi_s) = timelines
-            _check(self._lib, self._lib.abd_sampler_enable_timelines(self._h, int(planned), float(lo_n), float(hi_n), float(lo_s),
-                                                                     float(hi_s)))
+
+    # -- the per-draw summaries: switched on before the first draw, read out by the method named -----------------------------
+    def enable_pointwise(self):
+        """Accumulate the pointwise log-likelihood statistics of every draw on the device (``pointwise_stats``)."""
+        _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
+
+    def enable_predictive(self):
+        """Accumulate the posterior predictive check statistics of every draw on the device (``predictive_stats``)."""
+        _check(self._lib, self._lib.abd_sampler_enable_predictive(self._h, 1))
+
+    def enable_curves(self, draws: int, sero_thresholds=None):
+        """Keep the epidemic curves of ``draws`` draws per chain on the device (``curves``), seropositive at ``sero_thresholds`` =
+        (thr_s, thr_n) on the titer scale (``None``: off)."""
+        thr_s, thr_n = (np.inf, np.inf) if sero_thresholds is None else sero_thresholds
+        _check(self._lib, self._lib.abd_sampler_enable_curves(self._h, int(draws), float(thr_s), float(thr_n)))
+
+    def enable_diagnostics(self, planned: int, batch: int):
+        """Accumulate per cell what split R-hat and a batch-means ESS need over the ``planned`` draws, in batches of ``batch``
+        (``diagnostics``)."""
+        _check(self._lib, self._lib.abd_sampler_enable_diagnostics(self._h, int(planned), int(batch)))
+
+    def enable_risk(self, draws: int, spec):
+        """Keep the infection-risk-by-titer table of ``draws`` draws per chain on the device, counted under ``spec`` (``risk.spec``;
+        ``risk``)."""
+        sp = _risk_spec(spec)
+        _check(self._lib, self._lib.abd_sampler_enable_risk(self._h, int(draws), C.byref(sp)))
+
+    def enable_timelines(self, planned: int, range_n, range_s):
+        """Accumulate per cell the titer histograms over ``range_n`` = (lo_n, hi_n) and ``range_s`` and the infection timing counters
+        over the ``planned`` draws (``timelines`` / ``timeline_quantiles``)."""
+        (lo_n, hi_n), (lo_s, hi_s) = range_n, range_s
+        _check(self._lib, self._lib.abd_sampler_enable_timelines(self._h, int(planned), float(lo_n), float(hi_n), float(lo_s),
+                                                                 float(hi_s)))
 
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
-        theta = np.empty((self.n, n_iter, N_THETA))
-        stats = np.empty((self.n, n_iter, N_STATS))
-        self._ctx._bump(self._chains)  # the sweeps rewrite the chains' discrete state
-        _check(self._lib, self._lib.abd_sampler_run(self._h, int(n_iter), _ptr(theta, C.c_double), _ptr(stats, C.c_double)))
-        return theta, {name: stats[:, :, k].copy() for k, name in enumerate(STAT_NAMES)}
+        return self.run_record(n_iter, 0)
 
     def run_record(self, n_iter: int, first: int, i_raw=None, ab_s_waner=None, i=None, ab_n_mu=None, ab_s_mu=None, thin: int = 1,
                    ll_s=None, ll_n=None, yrep_s=None, yrep_n=None):
@@ -811,9 +829,9 @@ class NativeSampler:
         rec.capacity, rec.first, rec.thin = int(cap or 0), int(first), int(thin)
         theta = np.empty((self.n, n_iter, N_THETA))
         stats = np.empty((self.n, n_iter, N_STATS))
-        self._ctx._bump(self._chains)
+        self._ctx._bump(self._chains)  # the sweeps rewrite the chains' discrete state
         _check(self._lib, self._lib.abd_sampler_run_record(self._h, int(n_iter), _ptr(theta, C.c_double), _ptr(stats, C.c_double),
-                                                           C.byref(rec)))
+                                                           None if cap is None else C.byref(rec)))  # (no array: abd_sampler_run)
         return theta, {name: stats[:, :, k].copy() for k, name in enumerate(STAT_NAMES)}
 
     def means(self, k: int):
@@ -841,17 +859,21 @@ class NativeSampler:
         probability P(y_rep <= y) (predictive.merge)."""
         return self._reading_stats(self._lib.abd_sampler_predictive_stats, k)
 
+    def _kept_draws(self, fn, k: int, *tails):
+        """What a summary kept of every draw of the k-th chain so far: ``fn`` is asked for their number d, then for draws [0, d)
+        into one new array of shape (d,) + tail per (tail, dtype) of ``tails``."""
+        n = C.c_int64()
+        _check(self._lib, fn(self._h, int(k), 0, 0, *[None] * len(tails), C.byref(n)))
+        out = [np.empty((n.value,) + tail, dt) for tail, dt in tails]
+        if n.value:
+            _check(self._lib, fn(self._h, int(k), 0, n.value, *[_out(o, o.dtype) for o in out], None))
+        return out
+
     def curves(self, k: int):
         """The epidemic curves of every draw of the k-th chain so far (``Context.curves`` per draw) -> {"counts": (draws, 4, G)
         int64, "n_infections": (draws, 8) int64, "titer_sums": (draws, 2, G)}."""
         G = self._ctx.n_gaps
-        n = C.c_int64()
-        _check(self._lib, self._lib.abd_sampler_curves(self._h, int(k), 0, 0, None, None, None, C.byref(n)))
-        d = n.value
-        counts, n_inf, sums = np.empty((d, 4, G), np.int64), np.empty((d, 8), np.int64), np.empty((d, 2, G))
-        if d:
-            _check(self._lib, self._lib.abd_sampler_curves(self._h, int(k), 0, d, _out(counts, np.int64), _out(n_inf, np.int64),
-                                                           _out(sums, np.float64), None))
+        counts, n_inf, sums = self._kept_draws(self._lib.abd_sampler_curves, k, ((4, G), np.int64), ((8,), np.int64), ((2, G), np.float64))
         return {"counts": counts, "n_infections": n_inf, "titer_sums": sums}
 
     def diagnostics(self, k: int):
@@ -897,14 +919,7 @@ class NativeSampler:
     def risk(self, k: int):
         """The infection-risk-by-titer table of every draw of the k-th chain so far (``Context.risk`` per draw) -> (draws, 2, 2, G,
         8) int64."""
-        G = self._ctx.n_gaps
-        n = C.c_int64()
-        _check(self._lib, self._lib.abd_sampler_risk(self._h, int(k), 0, 0, None, C.byref(n)))
-        d = n.value
-        table = np.empty((d, 2, 2, G, 8), np.int64)
-        if d:
-            _check(self._lib, self._lib.abd_sampler_risk(self._h, int(k), 0, d, _out(table, np.int64), None))
-        return table
+        return self._kept_draws(self._lib.abd_sampler_risk, k, ((2, 2, self._ctx.n_gaps, 8), np.int64))[0]
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

@@ -22,9 +22,12 @@ from typing import Dict, Iterable, Mapping, Tuple
 
 import numpy as np
 
+from .summaries import Summary, per_reading_result
+
 Stats = Tuple[np.ndarray, np.ndarray, np.ndarray, int]  # (lse, mean, m2, n)
 
 WARN_P_WAIC = 0.4
+WAIC_KEYS = ("elpd_waic_i_it_s_lik", "elpd_waic_i_it_n_lik", "p_waic_i_it_s_lik", "p_waic_i_it_n_lik")  # what the CLI adds per reading
 
 
 def stats_from_matrix(ll) -> Stats:
@@ -127,3 +130,42 @@ def compare(results: Mapping[str, Mapping[str, np.ndarray]]) -> Dict[str, Dict[s
                          elpd_diff=float(best["elpd_waic"] - v["elpd_waic"]),
                          dse=float(np.sqrt(K * np.var(diff))) if K else 0.0, n_warn=v["n_warn"])
     return out
+
+
+class _Waic(Summary):
+    """``waic``: accumulate the per-reading statistics of the pointwise log-likelihood over ALL draws on the device (any cohort
+    size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n; S readings first), ``waic_n_draws``
+    (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``waic`` reads them.  The trajectories do not change."""
+
+    name = "waic"
+    options = {"waic": False}
+    prefix = "waic_"
+    derived_keys = WAIC_KEYS
+    dims = {k: ["it_s_lik_dim_0" if "it_s_lik" in k else "it_n_lik_dim_0"] for k in WAIC_KEYS}
+    record_row = "log_likelihood"
+    native_only = ("log_likelihood / waic need the native sampler (sample(native=True)): the pointwise log-likelihood "
+                   "is recorded and accumulated inside it")
+
+    def enable(self, smp, plan):
+        smp.enable_pointwise()
+
+    def collect(self, smp, plan, last_gap):
+        return per_reading_result("waic_", ("lse", "mean", "m2"), [smp.pointwise_stats(c) for c in range(plan["chains"])], smp.n_obs)
+
+    def add_arguments(self, parser):
+        parser.add_argument("--waic", help="Accumulate the pointwise log-likelihood of the OD readings on the device over all draws and "
+                            "report WAIC (elpd_waic, p_waic, se; per reading elpd_waic_i / p_waic_i in the output).", action="store_true")
+
+    def report(self, res, data):
+        """The per-reading values go into ``res`` (keys WAIC_KEYS)."""
+        w = waic(res)
+        res["elpd_waic_i_it_s_lik"], res["elpd_waic_i_it_n_lik"] = w["elpd_waic_i_s"], w["elpd_waic_i_n"]
+        res["p_waic_i_it_s_lik"], res["p_waic_i_it_n_lik"] = w["p_waic_i_s"], w["p_waic_i_n"]
+        return [f"WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_readings']} readings, "
+                f"{w['n_draws']} draws; {w['n_warn']} readings with p_waic_i > 0.4)"]
+
+    def group(self, key):
+        return "constant_data" if key in WAIC_KEYS else None  # (the accumulators themselves are not written)
+
+
+SUMMARY = _Waic()

@@ -22,10 +22,11 @@ NumPy only.
 """
 from __future__ import annotations
 
-import warnings
 from typing import Dict, Sequence
 
 import numpy as np
+
+from .summaries import Summary, interval
 
 COUNT_NAMES = ("infected", "ever_infected", "seropos_s", "seropos_n")
 N_BINS = 8
@@ -110,15 +111,6 @@ def merge_individual_shards(parts: Sequence[dict]) -> Dict[str, np.ndarray]:
     return out
 
 
-def _interval(x: np.ndarray, prob: float) -> Dict[str, np.ndarray]:
-    """Median and equal-tailed interval over axis 0; NaN columns stay NaN."""
-    lo = (1.0 - prob) / 2.0
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)  # (an all-NaN column: nobody followed at that gap)
-        q = np.nanquantile(x, [lo, 0.5, 1.0 - lo], axis=0) if x.shape[0] else np.full((3,) + x.shape[1:], np.nan)
-    return {"lower": q[0], "median": q[1], "upper": q[2]}
-
-
 def summary(res, prob: float = 0.95) -> Dict[str, object]:
     """Medians and equal-tailed ``prob`` intervals of the curves, chains and draws pooled.  Per gap, each a dict of
     ``median`` / ``lower`` / ``upper`` (G,), as shares of the individuals followed at the gap (NaN where nobody is):
@@ -147,13 +139,13 @@ def summary(res, prob: float = 0.95) -> Dict[str, object]:
 
     attack = share("curves_ever_infected")
     out: Dict[str, object] = {
-        "incidence": _interval(share("curves_infected"), prob),
-        "attack_rate": _interval(attack, prob),
-        "first_incidence": _interval(np.diff(attack, axis=1, prepend=0.0), prob),
-        "seroprev_s": _interval(share("curves_seropos_s"), prob),
-        "seroprev_n": _interval(share("curves_seropos_n"), prob),
-        "mean_titer_s": _interval(share("curves_titer_s"), prob),
-        "mean_titer_n": _interval(share("curves_titer_n"), prob),
+        "incidence": interval(share("curves_infected"), prob),
+        "attack_rate": interval(attack, prob),
+        "first_incidence": interval(np.diff(attack, axis=1, prepend=0.0), prob),
+        "seroprev_s": interval(share("curves_seropos_s"), prob),
+        "seroprev_n": interval(share("curves_seropos_n"), prob),
+        "mean_titer_s": interval(share("curves_titer_s"), prob),
+        "mean_titer_n": interval(share("curves_titer_n"), prob),
     }
     bins = c["curves_n_infections"].reshape(-1, N_BINS).astype(np.float64)
     tot = bins.sum(axis=1, keepdims=True)
@@ -170,3 +162,61 @@ def summary_arrays(sm: dict) -> Dict[str, np.ndarray]:
     out = {f"curves_summary_{k}": np.stack([v["lower"], v["median"], v["upper"]]) for k, v in sm.items() if isinstance(v, dict)}
     out["curves_summary_n_infections"] = np.asarray(sm["n_infections"])
     return out
+
+
+class _Curves(Summary):
+    """``curves``: keep the epidemic curves of EVERY draw, reduced over the individuals on the device (``thin`` does not apply):
+    ``curves_infected`` / ``curves_ever_infected`` / ``curves_seropos_s`` / ``curves_seropos_n`` (counts) and ``curves_titer_s`` /
+    ``curves_titer_n`` (titer sums), each (chains, draws, G), ``curves_n_infections`` (chains, draws, 8) and ``curves_n_followed``
+    (chains, G); ``summary`` reads them.  An individual counts up to its last serum sample (``model.data.last_gap`` where the
+    model's data has one, else every gap); ``sero_thresholds`` = (thr_s, thr_n) on the titer scale switch the seropositive counts
+    on.  The arrays are not counted against the host budget.  The trajectories do not change."""
+
+    name = "curves"
+    options = {"curves": False, "sero_thresholds": None}
+    prefix = "curves_"
+    draw_keys = RESULT_KEYS[:-1]  # one row per draw; the number followed and the summary have no draw axis
+    dims = {**{k: ["gap"] for k in RESULT_KEYS[:-2]}, "curves_n_followed": ["chain", "gap"]}
+    follow_up = True
+    native_only = "curves need the native sampler (sample(native=True)): every draw is reduced on the device inside it"
+
+    def enable(self, smp, plan):
+        smp.enable_curves(plan["draws"], plan["sero_thresholds"])
+
+    def collect(self, smp, plan, last_gap):
+        per_chain = [smp.curves(c) for c in range(plan["chains"])]
+        G, N = plan["G"], plan["N"]
+        return as_result(*(np.stack([pc[k] for pc in per_chain]) for k in ("counts", "n_infections", "titer_sums")),
+                         n_followed(np.full(N, G - 1) if last_gap is None else last_gap, G))
+
+    def add_arguments(self, parser):
+        parser.add_argument("--curves", help="Keep the epidemic curves of every draw (infections per gap, cumulative attack rate, "
+                            "seroprevalence, mean titers; reduced over the individuals on the device, --thin does not apply) and report "
+                            "the final cumulative attack rate and the peak monthly incidence with 95 %% intervals (curves_* in the "
+                            "output).  An individual counts up to its last serum sample.", action="store_true")
+        parser.add_argument("--sero_threshold_s", help="With --curves: S titer from which an individual counts as seropositive.",
+                            type=float, default=float("inf"))
+        parser.add_argument("--sero_threshold_n", help="With --curves: N titer from which an individual counts as seropositive.",
+                            type=float, default=float("inf"))
+
+    def cli_options(self, args, data, chains, world):
+        return {"curves": args.curves, "sero_thresholds": (args.sero_threshold_s, args.sero_threshold_n)}
+
+    def report(self, res, data):
+        """``summary``'s arrays go into ``res`` (``curves_summary_*``: rows lower, median, upper per gap)."""
+        sm = summary(res)
+        res.update(summary_arrays(sm))
+        followed = np.flatnonzero(sm["n_followed"] > 0)
+        if not (followed.size and sm["n_draws"]):
+            return []
+        g, inc = followed[-1], sm["incidence"]
+        peak = followed[np.argmax(inc["median"][followed])]
+        ar = sm["attack_rate"]
+        pct = int(round(100 * sm["prob"]))
+        return [f"curves: cumulative attack rate at gap {g} {100 * ar['median'][g]:.1f} % ({pct} % interval "
+                f"{100 * ar['lower'][g]:.1f}-{100 * ar['upper'][g]:.1f}; {sm['n_followed'][g]} followed); peak monthly incidence "
+                f"{100 * inc['median'][peak]:.1f} % ({100 * inc['lower'][peak]:.1f}-{100 * inc['upper'][peak]:.1f}) at gap {peak}; "
+                f"{sm['n_draws']} draws"]
+
+
+SUMMARY = _Curves()

@@ -31,6 +31,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from .summaries import Summary
+
 # what sample(..., diagnostics=True) returns: (chains, 4, G, N) int64, (chains, 6, G, N) twice, (chains, 4) int64
 RESULT_KEYS = ("diag_i_counts", "diag_ab_n_mu", "diag_ab_s_mu", "diag_info")
 VARIABLES = {"i": "diag_i_counts", "ab_n_mu": "diag_ab_n_mu", "ab_s_mu": "diag_ab_s_mu"}
@@ -292,3 +294,72 @@ def summary_arrays(sm: dict) -> Dict[str, np.ndarray]:
     out["diag_summary_scalar_names"] = np.array(names)
     out["diag_summary_scalars"] = np.array([[sm["scalars"][n][k] for n in names] for k in ("rhat", "ess", "mcse")]).reshape(3, len(names))
     return out
+
+
+class _Diagnostics(Summary):
+    """``diagnostics``: accumulate per cell, over ALL draws on the device, what split R-hat and a batch-means effective sample
+    size of ``i``, ``ab_n_mu``, ``ab_s_mu`` need (``thin`` does not apply): ``diag_i_counts`` (chains, 4, G, N) int64,
+    ``diag_ab_n_mu`` / ``diag_ab_s_mu`` (chains, 6, G, N) and ``diag_info`` (chains, 4); ``rhat`` / ``ess`` / ``summary`` read them.
+    ``diag_batch`` is the batch length (default ``default_batch(draws)``).  Needs ``draws >= 2``; the arrays' host bytes count
+    against ``budget_bytes``.  The trajectories do not change."""
+
+    name = "diagnostics"
+    options = {"diagnostics": False, "diag_batch": None}
+    prefix = "diag_"
+    native_only = "diagnostics need the native sampler (sample(native=True)): the moments of every draw are accumulated inside it"
+
+    def plan(self, opts, draws, chains, G, N):
+        p = super().plan(opts, draws, chains, G, N)
+        if p is None:
+            return None
+        if draws < 2:
+            raise ValueError(f"diagnostics need draws >= 2 (two half-chains), got {draws}")
+        p["batch"] = default_batch(draws) if p["diag_batch"] is None else int(p["diag_batch"])
+        if p["batch"] < 1:
+            raise ValueError(f"diag_batch must be >= 1, got {p['batch']}")
+        return p
+
+    def host_bytes(self, plan):
+        return result_bytes(plan["chains"], plan["G"], plan["N"])
+
+    def over_budget(self, plan, own, before, budget):
+        return (f"the diagnostics of {plan['chains']} chains x ({plan['G']}, {plan['N']}) take {own / 2 ** 30:.2f} GiB of host arrays "
+                f"(16 planes of 8 bytes per cell and chain) and the recorded draws {before / 2 ** 30:.2f} GiB, over the budget of "
+                f"{budget / 2 ** 30:.2f} GiB: record fewer draws (thin, no_deterministics / record_discrete=False) or raise "
+                f"ABD_RECORD_BUDGET_GB")
+
+    def enable(self, smp, plan):
+        smp.enable_diagnostics(plan["draws"], plan["batch"])
+
+    def collect(self, smp, plan, last_gap):
+        per_chain = [smp.diagnostics(c) for c in range(plan["chains"])]
+        return {"diag_" + key: np.stack([pc[key] for pc in per_chain]) for key in ("i_counts", "ab_n_mu", "ab_s_mu", "info")}
+
+    def add_arguments(self, parser):
+        parser.add_argument("--diagnostics", help="Accumulate per cell of i / ab_n_mu / ab_s_mu, over all draws on the device, what split "
+                            "R-hat and a batch-means effective sample size need (--thin does not apply) and report the largest R-hat, the "
+                            "share of cells above 1.01 and the smallest ESS per variable, and the worst of the 17 scalars (diag_* and "
+                            "diag_summary_* in the output).", action="store_true")
+        parser.add_argument("--diag_batch", help="With --diagnostics: draws per batch of the batch-means ESS (default: the square root of "
+                            "half the draws).", type=int)
+
+    def report(self, res, data):
+        """``summary``'s arrays go into ``res`` (``diag_summary_*``); the line: per variable over the followed cells, then the worst
+        scalar."""
+        sm = summary(res, getattr(data, "last_gap", None))
+        res.update(summary_arrays(sm))
+        parts = []
+        for var in ("i", "ab_n_mu", "ab_s_mu"):
+            f = sm[var].get("followed", sm[var])
+            parts.append(f"{var} max R-hat {f['max_rhat']:.3f}, {100 * f['share_rhat_above_1.01']:.1f} % of {f['n_cells'] - f['n_constant']} "
+                         f"non-constant followed cells above 1.01, min ESS {f['min_ess']:.0f}")
+        sc = {k: v["rhat"] for k, v in sm["scalars"].items() if np.isfinite(v["rhat"])}
+        worst = max(sc, key=sc.get) if sc else None
+        parts.append(f"worst scalar {worst} R-hat {sc[worst]:.3f}" if worst else "no scalar with a finite R-hat")
+        return ["diagnostics: " + "; ".join(parts)]
+
+    def group(self, key):
+        return None if key == "diag_summary_scalar_names" else "constant_data"  # (strings; nothing here has a draw axis)
+
+
+SUMMARY = _Diagnostics()

@@ -21,10 +21,13 @@ from typing import Dict, Iterable, Mapping, Tuple
 
 import numpy as np
 
+from .summaries import Summary, per_reading_result
+
 Stats = Tuple[np.ndarray, np.ndarray, np.ndarray, int]  # (mean, m2, pit, n)
 
 TAIL = 0.025  # p_k below TAIL or above 1 - TAIL counts as extreme
 N_BINS = 20
+PPC_KEYS = ("ppc_p_it_s_lik", "ppc_p_it_n_lik")  # what the CLI adds per reading
 
 
 def stats_from_matrix(m, pit) -> Stats:
@@ -110,3 +113,42 @@ def sample_posterior_predictive(model, res: Mapping[str, np.ndarray], tune: int,
             out_s[c, r], out_n[c, r] = ctx.posterior_predictive(slot, theta[c, d], seed=seed, stream=chain_offset + c,
                                                                 draw=int(tune) + int(d))
     return {"it_s_lik": out_s, "it_n_lik": out_n}
+
+
+class _Ppc(Summary):
+    """``ppc``: accumulate per-reading check statistics over ALL draws on the device -- ``ppc_mean`` / ``ppc_m2`` (mean and sum of
+    squared deviations of the predictive mean) and ``ppc_pit`` (mean of P(y_rep <= y | draw)), each (chains, K_s + K_n), S readings
+    first, ``ppc_n_draws`` (chains,) and ``ppc_n_obs`` (chains, 2): ``summary`` reads them.  It draws from no random stream the
+    chains use: their trajectories do not change."""
+
+    name = "ppc"
+    options = {"ppc": False}
+    prefix = "ppc_"
+    dims = {"ppc_p_it_s_lik": ["it_s_lik_dim_0"], "ppc_p_it_n_lik": ["it_n_lik_dim_0"]}
+    record_row = "posterior_predictive"
+    native_only = ("posterior_predictive / ppc need the native sampler (sample(native=True)): the replicates and the check "
+                   "statistics are drawn and accumulated inside it")
+
+    def enable(self, smp, plan):
+        smp.enable_predictive()
+
+    def collect(self, smp, plan, last_gap):
+        return per_reading_result("ppc_", ("mean", "m2", "pit"), [smp.predictive_stats(c) for c in range(plan["chains"])], smp.n_obs)
+
+    def add_arguments(self, parser):
+        parser.add_argument("--ppc", help="Accumulate a posterior predictive check of the OD readings on the device over all draws and "
+                            "report per antigen the readings with an extreme tail probability p = P(y_rep <= y | y) (per reading "
+                            "ppc_p_it_s_lik / ppc_p_it_n_lik in the output).", action="store_true")
+
+    def report(self, res, data):
+        """The tail probability of every reading goes into ``res`` (keys PPC_KEYS)."""
+        sm = summary(res)
+        res["ppc_p_it_s_lik"], res["ppc_p_it_n_lik"] = sm["it_s_lik"]["p"], sm["it_n_lik"]["p"]
+        return [f"PPC {name}: {a['n_extreme']} of {a['n_readings']} readings ({100 * a['share_extreme']:.2f} %) with p < 0.025 "
+                f"({a['n_low']}) or p > 0.975 ({a['n_high']}); {sm['n_draws']} draws" for name, a in ((n, sm[n]) for n in ("it_s_lik", "it_n_lik"))]
+
+    def group(self, key):
+        return "constant_data" if key in PPC_KEYS else None  # (the accumulators themselves are not written)
+
+
+SUMMARY = _Ppc()

@@ -23,10 +23,11 @@ NumPy only.
 """
 from __future__ import annotations
 
-import warnings
 from typing import Dict, Optional, Sequence
 
 import numpy as np
+
+from .summaries import Summary, interval
 
 N_BINS = 8
 MAX_EDGES = N_BINS - 1
@@ -198,15 +199,6 @@ def rate_ratio(at_risk, events, reference_bin: int = 0) -> np.ndarray:
         return np.where(den > 0, num / np.where(den > 0, den, 1.0), np.nan)
 
 
-def _interval(x: np.ndarray, prob: float) -> Dict[str, np.ndarray]:
-    """Median and equal-tailed interval over axis 0, NaN draws ignored and counted (``n_defined``)."""
-    lo = (1.0 - prob) / 2.0
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)  # (a column that is NaN in every draw)
-        q = np.nanquantile(x, [lo, 0.5, 1.0 - lo], axis=0) if x.shape[0] else np.full((3,) + x.shape[1:], np.nan)
-    return {"lower": q[0], "median": q[1], "upper": q[2], "n_defined": np.isfinite(x).sum(axis=0).astype(np.int64)}
-
-
 def per_draw(table, reference_bin: int = 0) -> Dict[str, np.ndarray]:
     """Per-draw quantities of ``table`` (..., 2, 2, G, 8): ``by_bin`` (..., 2, 2, 8) the table summed over the gaps, ``rate``
     (..., 2, 8) events / person-gaps (NaN for an empty bin), ``rate_ratio`` (..., 2, 8) (``rate_ratio``)."""
@@ -241,10 +233,9 @@ def summary(res, prob: float = 0.95, reference_bin: int = 0) -> Dict[str, object
     out: Dict[str, object] = {}
     for a, name in enumerate(ANTIGENS):
         rr = pd["rate_ratio"][:, a]
-        out[name] = {"person_gaps": _interval(pd["by_bin"][:, a, 0].astype(np.float64), prob),
-                     "events": _interval(pd["by_bin"][:, a, 1].astype(np.float64), prob),
-                     "rate": _interval(pd["rate"][:, a], prob), "rate_ratio": _interval(rr, prob),
-                     "protection": _interval(1.0 - rr, prob)}
+        out[name] = {k: interval(x, prob, count_defined=True) for k, x in (
+            ("person_gaps", pd["by_bin"][:, a, 0].astype(np.float64)), ("events", pd["by_bin"][:, a, 1].astype(np.float64)),
+            ("rate", pd["rate"][:, a]), ("rate_ratio", rr), ("protection", 1.0 - rr))}
     out["n_draws"] = int(t.shape[0])
     out["prob"], out["reference_bin"] = float(prob), int(reference_bin)
     for k in ("edges_s", "edges_n"):
@@ -304,3 +295,96 @@ def survival_arrays(i_mean, ab_s_mu_mean, ab_n_mu_mean, last_gap, start: int, en
     exposure = np.clip(exposure, 0.0, 1.0)
     exposure[np.isnan(infected)] = np.nan
     return {"infected": infected, "exposure": exposure, "s_titer": s_mu.T[:, start:end - 1].copy(), "n_titer": n_mu.T[:, start:end - 1].copy()}
+
+
+class _Risk(Summary):
+    """``risk`` = a ``spec``: keep the infection-risk-by-titer table of EVERY draw, reduced over the individuals on the device
+    (``thin`` does not apply): ``risk_table`` (chains, draws, 2, 2, G, 8) int64 -- antigen (S, N) x (at risk, events) x gap x bin of
+    the previous gap's titer -- and the spec, one row per chain: ``risk_edges_s`` / ``risk_edges_n`` (chains, 7), NaN beyond the
+    edges given, and ``risk_window`` (chains, 3) = (start, end, first_only); ``summary`` reads them.  The follow-up is the curves'.
+    The table's host bytes count against ``budget_bytes``.  The trajectories do not change."""
+
+    name = "risk"
+    options = {"risk": None}
+    prefix = "risk_"
+    draw_keys = ("risk_table", "risk_by_bin", "risk_rate_ratio")
+    follow_up = True
+    native_only = "risk needs the native sampler (sample(native=True)): every draw is reduced on the device inside it"
+
+    def on(self, opts):
+        return opts["risk"] is not None
+
+    def plan(self, opts, draws, chains, G, N):
+        p = super().plan(opts, draws, chains, G, N)
+        if p is not None:
+            p["spec"] = _checked(p["risk"], G)
+        return p
+
+    def host_bytes(self, plan):
+        return plan["chains"] * plan["draws"] * 4 * plan["G"] * N_BINS * 8
+
+    def over_budget(self, plan, own, before, budget):
+        return (f"the risk tables of {plan['chains']} chains x {plan['draws']} draws x {plan['G']} gaps take {own / 2 ** 30:.2f} GiB of "
+                f"host arrays (32 counts of 8 bytes per gap and draw) and the other recorded arrays {before / 2 ** 30:.2f} GiB, over "
+                f"the budget of {budget / 2 ** 30:.2f} GiB: fewer draws, record less (thin, no_deterministics / record_discrete=False) "
+                f"or raise ABD_RECORD_BUDGET_GB")
+
+    def enable(self, smp, plan):
+        smp.enable_risk(plan["draws"], plan["spec"])
+
+    def collect(self, smp, plan, last_gap):
+        return as_result(np.stack([smp.risk(c) for c in range(plan["chains"])]), plan["spec"])
+
+    def add_arguments(self, parser):
+        parser.add_argument("--risk", help="Keep the infection-risk-by-titer table of every draw (person-gaps at risk and infections by gap "
+                            "and by bin of the previous gap's titer; reduced over the individuals on the device, --thin does not apply) "
+                            "and report per antigen the protection (1 - the rate ratio stratified by gap) of the highest populated bin "
+                            "against bin 0 with its 95 %% interval (risk_* in the output).  An individual counts up to its last serum "
+                            "sample and, without --risk_all_infections, up to its first infection inside the window.", action="store_true")
+        parser.add_argument("--risk_edges_s", help="With --risk: up to 7 ascending S titer bin edges, separated by commas.", default="")
+        parser.add_argument("--risk_edges_n", help="With --risk: up to 7 ascending N titer bin edges, separated by commas.", default="")
+        parser.add_argument("--risk_start", help="With --risk: the window's first gap; risk is counted from the gap after it.", type=int,
+                            default=0)
+        parser.add_argument("--risk_end", help="With --risk: the end of the window, one past its last gap (default: the number of gaps).",
+                            type=int)
+        parser.add_argument("--risk_all_infections", help="With --risk: count every infection of an individual inside the window, not "
+                            "only the first.", action="store_true")
+
+    def cli_options(self, args, data, chains, world):
+        """The ``spec`` the --risk flags ask for (``None`` without --risk); ``SystemExit`` for what ``spec`` refuses."""
+        if not args.risk:
+            return {"risk": None}
+        try:
+            edges = [[float(x) for x in text.split(",") if x.strip()] for text in (args.risk_edges_s, args.risk_edges_n)]
+            return {"risk": spec(args.risk_start, args.risk_end, edges[0], edges[1], not args.risk_all_infections, n_gaps=data.n_gaps)}
+        except ValueError as e:
+            raise SystemExit(f"--risk: {e}")
+
+    def report(self, res, data):
+        """The per-draw table is replaced in ``res`` by what a posterior file keeps of it: ``risk_by_bin`` (chains, draws, 2, 2, 8)
+        the table summed over the gaps, ``risk_rate_ratio`` (chains, draws, 2, 8) the per-draw rate ratios against bin 0,
+        ``risk_table_sum`` (chains, 2, 2, G, 8) the table summed over the draws, and ``risk_summary_*``.  The line: per antigen the
+        highest populated bin against bin 0."""
+        sm = summary(res)
+        table = res.pop("risk_table")
+        pd = per_draw(table)
+        res["risk_by_bin"], res["risk_rate_ratio"] = pd["by_bin"], pd["rate_ratio"]
+        res["risk_table_sum"] = table.sum(axis=1)
+        res.update(summary_arrays(sm))
+        pct = int(round(100 * sm["prob"]))
+        parts = []
+        for name in ANTIGENS:
+            a = sm[name]
+            used = np.flatnonzero(np.nan_to_num(a["person_gaps"]["median"]) > 0)
+            top = int(used[-1]) if used.size else 0
+            if top == 0:
+                parts.append(f"{name.upper()} no populated bin above bin 0")
+                continue
+            p = a["protection"]
+            parts.append(f"{name.upper()} protection of bin {top} against bin 0 {100 * p['median'][top]:.1f} % ({pct} % interval "
+                         f"{100 * p['lower'][top]:.1f} to {100 * p['upper'][top]:.1f}; defined in {int(p['n_defined'][top])} of "
+                         f"{sm['n_draws']} draws)")
+        return ["risk: " + "; ".join(parts)]
+
+
+SUMMARY = _Risk()

@@ -299,11 +299,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                   record_discrete: bool = True, progress: Optional[Callable[[int, int, int], None]] = None,
                   target_accept: float = 0.8, max_treedepth: int = 10, chunk: int = 50,
                   chain_offset: int = 0, dense_metric: bool = False, thin: int = 1,
-                  budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-                  waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-                  sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None,
-                  risk=None, timelines: bool = False, timeline_ranges=((-4, 8), (-4, 8)), timeline_q=(0.025, 0.5, 0.975),
-                  timelines_hist: bool = False) -> Dict[str, np.ndarray]:
+                  budget_bytes: Optional[int] = None, log_likelihood: bool = False, posterior_predictive: bool = False,
+                  **summary_options) -> Dict[str, np.ndarray]:
     """
     The compound step inside the library (``abd_sampler_*``): the chains advance as independent units, each at its own
     pace (NUTS transitions as leapfrog trains on the device, the Gibbs sweep, the re-evaluation at the new state); nothing
@@ -319,129 +316,55 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
 
     ``log_likelihood``: also record the pointwise log-likelihood of every OD reading at the recorded draws (thinned like the
     (gap, ind) arrays) as ``log_likelihood_it_s_lik`` / ``log_likelihood_it_n_lik`` (chains, n_rec, K), what
-    ``pm.compute_log_likelihood`` adds to an InferenceData.  ``waic``: accumulate its per-reading statistics over ALL
-    draws on the device (any cohort size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n;
-    S readings first), ``waic_n_draws`` (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``compare.waic`` reads them.
+    ``pm.compute_log_likelihood`` adds to an InferenceData.
 
     ``posterior_predictive``: also record a posterior predictive replicate of every OD reading at the recorded draws (thinned
     likewise) as ``posterior_predictive_it_s_lik`` / ``posterior_predictive_it_n_lik`` (chains, n_rec, K), what
     ``pm.sample_posterior_predictive`` returns; chain c's replicate of iteration t (tune included) is
-    ``Context.posterior_predictive(.., seed, chain_offset + c, t)`` (``predictive.sample_posterior_predictive``).  ``ppc``:
-    accumulate per-reading check statistics over ALL draws on the device -- ``ppc_mean`` / ``ppc_m2`` (mean and sum of squared
-    deviations of the predictive mean) and ``ppc_pit`` (mean of P(y_rep <= y | draw)), each (chains, K_s + K_n), S readings
-    first, ``ppc_n_draws`` (chains,) and ``ppc_n_obs`` (chains, 2): ``predictive.summary`` reads them.  Neither option draws
-    from any random stream the chains use: their trajectories do not change.
+    ``Context.posterior_predictive(.., seed, chain_offset + c, t)`` (``predictive.sample_posterior_predictive``).  It draws from
+    no random stream the chains use: their trajectories do not change.
 
-    ``curves``: keep the epidemic curves of EVERY draw, reduced over the individuals on the device (``curves.py``; ``thin`` does
-    not apply): ``curves_infected`` / ``curves_ever_infected`` / ``curves_seropos_s`` / ``curves_seropos_n`` (counts) and
-    ``curves_titer_s`` / ``curves_titer_n`` (titer sums), each (chains, draws, G), ``curves_n_infections`` (chains, draws, 8) and
-    ``curves_n_followed`` (chains, G); ``curves.summary`` reads them.  An individual counts up to its last serum sample
-    (``model.data.last_gap`` where the model's data has one, else every gap); ``sero_thresholds`` = (thr_s, thr_n) on the titer
-    scale switch the seropositive counts on.  The trajectories do not change either.
-
-    ``diagnostics``: accumulate per cell, over ALL draws on the device, what split R-hat and a batch-means effective sample size
-    of ``i``, ``ab_n_mu``, ``ab_s_mu`` need (``diagnostics.py``; ``thin`` does not apply): ``diag_i_counts`` (chains, 4, G, N) int64,
-    ``diag_ab_n_mu`` / ``diag_ab_s_mu`` (chains, 6, G, N) and ``diag_info`` (chains, 4); ``diagnostics.rhat`` / ``ess`` / ``summary``
-    read them.  ``diag_batch`` is the batch length (default ``max(1, floor(sqrt(draws // 2)))``).  Needs ``draws >= 2``; the
-    arrays' host bytes count against ``budget_bytes``.  The trajectories do not change either.
-
-    ``risk`` = a ``risk.spec``: keep the infection-risk-by-titer table of EVERY draw, reduced over the individuals on the device
-    (``risk.py``; ``thin`` does not apply): ``risk_table`` (chains, draws, 2, 2, G, 8) int64 -- antigen (S, N) x (at risk, events)
-    x gap x bin of the previous gap's titer -- and the spec, one row per chain: ``risk_edges_s`` / ``risk_edges_n`` (chains, 7),
-    NaN beyond the edges given, and ``risk_window`` (chains, 3) = (start, end, first_only); ``risk.summary`` reads them.  The
-    follow-up is the curves'.  The table's host bytes count against ``budget_bytes``.  The trajectories do not change either.
-
-    ``timelines``: accumulate per cell, over ALL draws on the device, what a per-individual timeline needs (``timelines.py``;
-    ``thin`` does not apply): histograms of the two titers over ``timeline_ranges`` = ((lo_n, hi_n), (lo_s, hi_s)) (default: the
-    reference's plot range) and the infection timing counters.  Per chain ``tl_inf`` / ``tl_cum`` (chains, G, N) int64 -- draws
-    with an infection in the cell; with one so far in the cell's time chunk --, ``tl_ninf`` (chains, N, 8) int64 -- draws by the
-    number of infections within follow-up (the curves') --, ``tl_info`` (chains, 1) the draws, ``tl_range`` (chains, 2, 2) and
-    ``tl_q`` (chains, Q); pooled over the chains by a device kernel ``tl_q_n`` / ``tl_q_s`` (Q, G, N), the quantiles ``timeline_q``
-    (1 to 8 levels; ``timelines.summary`` reads the smallest, the one nearest 0.5 and the largest as lower, median and upper;
-    ``None``: no pooled quantiles, none of the three keys -- for a caller that pools the histograms of several processes itself)
-    of ``ab_n_mu`` / ``ab_s_mu``; with ``timelines_hist`` also the histograms ``tl_hist_n`` / ``tl_hist_s`` (chains,
-    G, N, 64) uint16.  ``timelines.summary`` / ``individual`` read them.  At most 65535 draws per chain; the arrays' host bytes
-    count against ``budget_bytes``.  The trajectories do not change either.
+    ``summary_options``: the keywords of the summaries computed over ALL draws inside the sampler (``summaries.registry()``).
+    Each is documented once, on its summary: ``help(m.SUMMARY)`` for the module m that reads the result.  A keyword none of them
+    owns is a ``TypeError``.  Their arrays' host bytes count against ``budget_bytes`` after the recorded ones, in the registry's
+    order, and the first summary that passes it refuses the run.
     """
-    from . import curves as curves_mod
-    from . import timelines as tl_mod
-    from . import diagnostics as diag_mod
-    from . import risk as risk_mod
+    from . import summaries
     from .model import THETA_NAMES, constrain
 
+    opts = summaries.resolve(summary_options)
     ctx = model.ctx
     G, N = model.n_gaps, model.n_inds
     if thin < 1:
         raise ValueError(f"thin must be >= 1, got {thin}")
     n_rec = (draws + thin - 1) // thin
-    K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if (log_likelihood or waic or posterior_predictive or ppc) else (0, 0)  # readings of it_s_lik / it_n_lik
     per_reading = log_likelihood or posterior_predictive  # per-draw rows of the readings
-    if diagnostics:
-        if draws < 2:
-            raise ValueError(f"diagnostics need draws >= 2 (two half-chains), got {draws}")
-        diag_batch = diag_mod.default_batch(draws) if diag_batch is None else int(diag_batch)
-        if diag_batch < 1:
-            raise ValueError(f"diag_batch must be >= 1, got {diag_batch}")
+    K_s, K_n = (ctx.n_obs_s, ctx.n_obs_n) if per_reading else (0, 0)  # readings of it_s_lik / it_n_lik
+    # everything from here to the active plans happens before the device is touched
+    budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
+    held = 0  # host bytes so far
     if record_deterministics or record_discrete or per_reading:
-        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
-        need = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
+        held = record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
                             n_readings=(K_s + K_n) if log_likelihood else 0,
                             n_replicates=(K_s + K_n) if posterior_predictive else 0)
-        if need > budget:
-            per_draw = need // max(n_rec, 1)
+        if held > budget:
+            per_draw = held // max(n_rec, 1)
             fit = max(1, budget // max(per_draw, 1))          # draws per chain set that fit
             thin_fit = -(-draws // fit)
             raise ValueError(
-                f"recording {n_rec} draws of {chains} chains x ({G}, {N}) needs {need / 2 ** 30:.1f} GiB of host arrays, over the "
+                f"recording {n_rec} draws of {chains} chains x ({G}, {N}) needs {held / 2 ** 30:.1f} GiB of host arrays, over the "
                 f"budget of {budget / 2 ** 30:.1f} GiB: thin >= {thin_fit} fits (or record less: no_deterministics / "
                 f"record_discrete=False; the posterior means are returned either way; ABD_RECORD_BUDGET_GB raises the budget)")
-    if diagnostics:
-        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
-        own = diag_mod.result_bytes(chains, G, N)
-        need = own + record_bytes(chains, n_rec, G, N, record_deterministics, record_discrete,
-                                  n_readings=(K_s + K_n) if log_likelihood else 0,
-                                  n_replicates=(K_s + K_n) if posterior_predictive else 0)
-        if need > budget:
-            raise ValueError(
-                f"the diagnostics of {chains} chains x ({G}, {N}) take {own / 2 ** 30:.2f} GiB of host arrays (16 planes of 8 bytes "
-                f"per cell and chain) and the recorded draws {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
-                f"{budget / 2 ** 30:.2f} GiB: record fewer draws (thin, no_deterministics / record_discrete=False) or raise "
-                f"ABD_RECORD_BUDGET_GB")
-    if risk is not None:
-        risk = risk_mod.spec(risk["start"], risk["end"], risk["edges_s"], risk["edges_n"], risk["first_only"], n_gaps=G)
-        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
-        own = chains * draws * 4 * G * risk_mod.N_BINS * 8
-        need = own + (diag_mod.result_bytes(chains, G, N) if diagnostics else 0) + record_bytes(
-            chains, n_rec, G, N, record_deterministics, record_discrete, n_readings=(K_s + K_n) if log_likelihood else 0,
-            n_replicates=(K_s + K_n) if posterior_predictive else 0)
-        if need > budget:
-            raise ValueError(
-                f"the risk tables of {chains} chains x {draws} draws x {G} gaps take {own / 2 ** 30:.2f} GiB of host arrays (32 counts "
-                f"of 8 bytes per gap and draw) and the other recorded arrays {(need - own) / 2 ** 30:.2f} GiB, over the budget of "
-                f"{budget / 2 ** 30:.2f} GiB: fewer draws, record less (thin, no_deterministics / record_discrete=False) or raise "
-                f"ABD_RECORD_BUDGET_GB")
-    if timelines:
-        timeline_ranges = tuple(tl_mod.check_range(*r) for r in timeline_ranges)
-        if len(timeline_ranges) != 2:
-            raise ValueError("timeline_ranges must be ((lo_n, hi_n), (lo_s, hi_s))")
-        pooled = timeline_q is not None  # (None: the device's pooled quantiles are not read out)
-        timeline_q = np.atleast_1d(np.asarray(timeline_q if pooled else [0.5], dtype=np.float64))
-        if timeline_q.ndim != 1 or not 1 <= timeline_q.size <= tl_mod.MAX_Q or not ((timeline_q >= 0) & (timeline_q <= 1)).all():
-            raise ValueError(f"timeline_q must be 1 to {tl_mod.MAX_Q} numbers in [0, 1]")
-        if not 1 <= draws <= tl_mod.MAX_DRAWS:
-            raise ValueError(f"timelines count in 16 bits: 1 to {tl_mod.MAX_DRAWS} draws per chain, got {draws}")
-        budget = record_budget_bytes() if budget_bytes is None else int(budget_bytes)
-        own = tl_mod.result_bytes(chains, G, N, timeline_q.size if pooled else 0, timelines_hist)
-        need = own + (diag_mod.result_bytes(chains, G, N) if diagnostics else 0) + (
-            chains * draws * 4 * G * risk_mod.N_BINS * 8 if risk is not None else 0) + record_bytes(
-            chains, n_rec, G, N, record_deterministics, record_discrete, n_readings=(K_s + K_n) if log_likelihood else 0,
-            n_replicates=(K_s + K_n) if posterior_predictive else 0)
-        if need > budget:
-            raise ValueError(
-                f"the timelines of {chains} chains x ({G}, {N}) take {own / 2 ** 30:.2f} GiB ({own} bytes) of host arrays"
-                f"{' (the histograms: 256 bytes per cell and chain)' if timelines_hist else ''} and the other recorded arrays "
-                f"{(need - own) / 2 ** 30:.2f} GiB, over the budget of {budget / 2 ** 30:.2f} GiB: record less (thin, "
-                f"no_deterministics / record_discrete=False) or raise ABD_RECORD_BUDGET_GB")
+    active = []  # (summary, its plan)
+    for s in summaries.registry():
+        plan = s.plan(opts, draws, chains, G, N)
+        if plan is None:
+            continue
+        own = s.host_bytes(plan)
+        if held + own > budget:
+            raise ValueError(s.over_budget(plan, own, held, budget))
+        held += own
+        active.append((s, plan))
     chunk = max(thin, chunk - chunk % thin) if thin > 1 else chunk  # calls record iterations 0, thin, ... of THEIR range
     pt = model.initial_point()
     q0 = np.empty((chains, len(THETA_NAMES)))
@@ -451,12 +374,11 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         q0[c] = model.ravel(pt) + rng.uniform(-1, 1, size=len(THETA_NAMES))  # start jitter U(-1, 1) on the value variables: pm.sample's default init 'jitter+adapt_diag'
     smp = ctx.sampler(np.arange(chains), q0, tune=tune, seed=seed, target_accept=target_accept,
                       max_treedepth=max_treedepth, gibbs=True, accumulate=True, chain_offset=chain_offset,
-                      dense_metric=dense_metric, pointwise=waic, predictive=ppc, curves=draws if curves else 0,
-                      sero_thresholds=sero_thresholds, diagnostics=(draws, diag_batch) if diagnostics else None,
-                      risk=draws if risk is not None else 0, risk_spec=risk,
-                      timelines=(draws, *timeline_ranges) if timelines else None)
-    if curves or risk is not None or timelines:
-        last_gap = getattr(getattr(model, "data", None), "last_gap", None)
+                      dense_metric=dense_metric)
+    for s, plan in active:
+        s.enable(smp, plan)
+    last_gap = getattr(getattr(model, "data", None), "last_gap", None)
+    if any(s.follow_up for s, _ in active):
         ctx.set_follow_up(last_gap)
     n_grad = chains  # the evaluation at the starting points
     done = 0
@@ -512,34 +434,8 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
         res["log_likelihood_it_s_lik"], res["log_likelihood_it_n_lik"] = ll["ll_s"], ll["ll_n"]
     if posterior_predictive:
         res["posterior_predictive_it_s_lik"], res["posterior_predictive_it_n_lik"] = ll["yrep_s"], ll["yrep_n"]
-    for on, stats_of, prefix, names in ((waic, smp.pointwise_stats, "waic", ("lse", "mean", "m2")),
-                                        (ppc, smp.predictive_stats, "ppc", ("mean", "m2", "pit"))):
-        if not on:
-            continue
-        per_chain = [stats_of(c) for c in range(chains)]
-        for j, name in enumerate(names):
-            res[f"{prefix}_{name}"] = np.stack([o[j] for o, _ in per_chain])
-        res[f"{prefix}_n_draws"] = np.array([n for _, n in per_chain], dtype=np.int64)
-        res[f"{prefix}_n_obs"] = np.tile(np.array([K_s, K_n], dtype=np.int64), (chains, 1))
-    if curves:
-        per_chain = [smp.curves(c) for c in range(chains)]
-        res.update(curves_mod.as_result(*(np.stack([pc[k] for pc in per_chain]) for k in ("counts", "n_infections", "titer_sums")),
-                                        curves_mod.n_followed(np.full(N, G - 1) if last_gap is None else last_gap, G)))
-    if risk is not None:
-        res.update(risk_mod.as_result(np.stack([smp.risk(c) for c in range(chains)]), risk))
-    if diagnostics:
-        per_chain = [smp.diagnostics(c) for c in range(chains)]
-        for key, name in (("i_counts", "diag_i_counts"), ("ab_n_mu", "diag_ab_n_mu"), ("ab_s_mu", "diag_ab_s_mu"), ("info", "diag_info")):
-            res[name] = np.stack([pc[key] for pc in per_chain])
-    if timelines:
-        per_chain = [smp.timelines(c, hist=timelines_hist) for c in range(chains)]
-        for key in ("inf", "cum", "ninf") + (("hist_n", "hist_s") if timelines_hist else ()):
-            res["tl_" + key] = np.stack([pc[key] for pc in per_chain])
-        res["tl_info"] = np.array([[pc["n_draws"]] for pc in per_chain], dtype=np.int64)
-        res["tl_range"] = np.tile(np.array(timeline_ranges, dtype=np.float64), (chains, 1, 1))
-        if pooled:
-            res["tl_q"] = np.tile(timeline_q, (chains, 1))
-            res["tl_q_n"], res["tl_q_s"] = smp.timeline_quantiles(timeline_q)
+    for s, plan in active:
+        res.update(s.collect(smp, plan, last_gap))
     if record_discrete or det is not None or per_reading:
         res["draw_index"] = np.tile(np.arange(0, draws, thin, dtype=np.int64), (chains, 1))  # which draws the (gap, ind) arrays hold
     if draws:
@@ -559,35 +455,22 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
            progress: Optional[Callable[[int, int, int], None]] = None, device_gibbs: bool = True,
            native: bool = True, record_discrete: bool = True, chain_offset: int = 0,
            dense_metric: bool = False, thin: int = 1, budget_bytes: Optional[int] = None, log_likelihood: bool = False,
-           waic: bool = False, posterior_predictive: bool = False, ppc: bool = False, curves: bool = False,
-           sero_thresholds=None, diagnostics: bool = False, diag_batch: Optional[int] = None, risk=None,
-           timelines: bool = False, timeline_ranges=((-4, 8), (-4, 8)), timeline_q=(0.025, 0.5, 0.975),
-           timelines_hist: bool = False) -> Dict[str, np.ndarray]:
+           posterior_predictive: bool = False, **summary_options) -> Dict[str, np.ndarray]:
     """``pm.sample(tune, draws)`` for the abd model: returns arrays with leading (chain, draw) axes (the per-draw
-    (gap, ind) arrays hold every ``thin``-th draw: ``sample_native``)."""
+    (gap, ind) arrays hold every ``thin``-th draw; ``summary_options``: ``sample_native``)."""
+    from . import summaries
+
     if chains > model.n_chains:
         raise ValueError(f"model was built with {model.n_chains} chain slots, {chains} requested")
     if native and device_gibbs and hasattr(model.ctx, "sampler"):
         return sample_native(model, tune, draws, chains, seed, record_deterministics, record_discrete, progress,
                              chain_offset=chain_offset, dense_metric=dense_metric, thin=thin, budget_bytes=budget_bytes,
-                             log_likelihood=log_likelihood, waic=waic, posterior_predictive=posterior_predictive, ppc=ppc,
-                             curves=curves, sero_thresholds=sero_thresholds, diagnostics=diagnostics, diag_batch=diag_batch,
-                             risk=risk, timelines=timelines, timeline_ranges=timeline_ranges, timeline_q=timeline_q,
-                             timelines_hist=timelines_hist)
-    if timelines:
-        raise ValueError("timelines need the native sampler (sample(native=True)): the counters of every draw are accumulated inside it")
-    if risk is not None:
-        raise ValueError("risk needs the native sampler (sample(native=True)): every draw is reduced on the device inside it")
-    if diagnostics:
-        raise ValueError("diagnostics need the native sampler (sample(native=True)): the moments of every draw are accumulated inside it")
-    if curves:
-        raise ValueError("curves need the native sampler (sample(native=True)): every draw is reduced on the device inside it")
-    if posterior_predictive or ppc:
-        raise ValueError("posterior_predictive / ppc need the native sampler (sample(native=True)): the replicates and the check "
-                         "statistics are drawn and accumulated inside it")
-    if log_likelihood or waic:
-        raise ValueError("log_likelihood / waic need the native sampler (sample(native=True)): the pointwise log-likelihood "
-                         "is recorded and accumulated inside it")
+                             log_likelihood=log_likelihood, posterior_predictive=posterior_predictive, **summary_options)
+    opts = summaries.resolve(summary_options)
+    rows = {"log_likelihood": log_likelihood, "posterior_predictive": posterior_predictive}
+    for s in reversed(summaries.registry()):
+        if s.on(opts) or rows.get(s.record_row):
+            raise ValueError(s.native_only)
     if chain_offset or dense_metric or thin != 1:
         raise ValueError("chain_offset / dense_metric / thin need the native sampler")
     per_chain = []

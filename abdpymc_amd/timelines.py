@@ -27,6 +27,8 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
+from .summaries import Summary
+
 N_BINS = 64      # counters per histogram: underflow, 62 interior bins, overflow
 N_NINF = 8       # bins of the number of infections
 MAX_DRAWS = 65535  # per chain: 16-bit counters
@@ -285,3 +287,127 @@ def line(sm) -> str:
             total += int(sel.sum())
     parts.append(f"{100 * touched / max(total, 1):.2f} % of cell bands touch an under- or overflow bin")
     return "timelines: " + "; ".join(parts) + f"; {sm['draws']} draws"
+
+
+def add_summary(res: dict, last_gap=None) -> dict:
+    """``summary`` of a gathered ``timelines=True`` result: its arrays go into ``res`` (``tl_summary_*``), the summary is returned.
+    A result gathered from several ranks carries the histograms and no pooled quantiles (``timeline_q=None``): they are pooled
+    here (``merge`` / ``quantiles`` at ``DEFAULT_Q``) and the histograms are dropped from ``res``."""
+    sm = summary(res, last_gap)
+    if "tl_q_n" not in res:
+        m = merge(res)
+        q = np.array(DEFAULT_Q)
+        res["tl_q"] = np.tile(q, (np.asarray(res["tl_inf"]).shape[0], 1))
+        res["tl_q_n"] = quantiles(m["hist_n"], q, *m["range"][0])
+        res["tl_q_s"] = quantiles(m["hist_s"], q, *m["range"][1])
+        for k in HIST_KEYS:
+            res.pop(k)
+    res.update(summary_arrays(sm))
+    return sm
+
+
+class _Timelines(Summary):
+    """``timelines``: accumulate per cell, over ALL draws on the device, what a per-individual timeline needs (``thin`` does not
+    apply): histograms of the two titers over ``timeline_ranges`` = ((lo_n, hi_n), (lo_s, hi_s)) (default: the reference's plot
+    range) and the infection timing counters.  Per chain ``tl_inf`` / ``tl_cum`` (chains, G, N) int64 -- draws with an infection in
+    the cell; with one so far in the cell's time chunk --, ``tl_ninf`` (chains, N, 8) int64 -- draws by the number of infections
+    within follow-up (the curves') --, ``tl_info`` (chains, 1) the draws, ``tl_range`` (chains, 2, 2) and ``tl_q`` (chains, Q); pooled
+    over the chains by a device kernel ``tl_q_n`` / ``tl_q_s`` (Q, G, N), the quantiles ``timeline_q`` (1 to 8 levels; ``summary``
+    reads the smallest, the one nearest 0.5 and the largest as lower, median and upper; ``None``: no pooled quantiles, none of the
+    three keys -- for a caller that pools the histograms of several processes itself) of ``ab_n_mu`` / ``ab_s_mu``; with
+    ``timelines_hist`` also the histograms ``tl_hist_n`` / ``tl_hist_s`` (chains, G, N, 64) uint16.  ``summary`` / ``individual``
+    read them.  At most 65535 draws per chain; the arrays' host bytes count against ``budget_bytes``.  The trajectories do not
+    change."""
+
+    name = "timelines"
+    options = {"timelines": False, "timeline_ranges": ((-4, 8), (-4, 8)), "timeline_q": DEFAULT_Q, "timelines_hist": False}
+    prefix = "tl_"
+    follow_up = True
+    native_only = "timelines need the native sampler (sample(native=True)): the counters of every draw are accumulated inside it"
+
+    def plan(self, opts, draws, chains, G, N):
+        p = super().plan(opts, draws, chains, G, N)
+        if p is None:
+            return None
+        ranges = tuple(check_range(*r) for r in p["timeline_ranges"])
+        if len(ranges) != 2:
+            raise ValueError("timeline_ranges must be ((lo_n, hi_n), (lo_s, hi_s))")
+        q = p["timeline_q"]  # (None: the device's pooled quantiles are not read out)
+        if q is not None:
+            q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+            if q.ndim != 1 or not 1 <= q.size <= MAX_Q or not ((q >= 0) & (q <= 1)).all():
+                raise ValueError(f"timeline_q must be 1 to {MAX_Q} numbers in [0, 1]")
+        if not 1 <= draws <= MAX_DRAWS:
+            raise ValueError(f"timelines count in 16 bits: 1 to {MAX_DRAWS} draws per chain, got {draws}")
+        p.update(ranges=ranges, q=q, hist=bool(p["timelines_hist"]))
+        return p
+
+    def host_bytes(self, plan):
+        return result_bytes(plan["chains"], plan["G"], plan["N"], 0 if plan["q"] is None else plan["q"].size, plan["hist"])
+
+    def over_budget(self, plan, own, before, budget):
+        return (f"the timelines of {plan['chains']} chains x ({plan['G']}, {plan['N']}) take {own / 2 ** 30:.2f} GiB ({own} bytes) of "
+                f"host arrays{' (the histograms: 256 bytes per cell and chain)' if plan['hist'] else ''} and the other recorded arrays "
+                f"{before / 2 ** 30:.2f} GiB, over the budget of {budget / 2 ** 30:.2f} GiB: record less (thin, "
+                f"no_deterministics / record_discrete=False) or raise ABD_RECORD_BUDGET_GB")
+
+    def enable(self, smp, plan):
+        smp.enable_timelines(plan["draws"], *plan["ranges"])
+
+    def collect(self, smp, plan, last_gap):
+        chains, q = plan["chains"], plan["q"]
+        per_chain = [smp.timelines(c, hist=plan["hist"]) for c in range(chains)]
+        res = {"tl_" + key: np.stack([pc[key] for pc in per_chain])
+               for key in ("inf", "cum", "ninf") + (("hist_n", "hist_s") if plan["hist"] else ())}
+        res["tl_info"] = np.array([[pc["n_draws"]] for pc in per_chain], dtype=np.int64)
+        res["tl_range"] = np.tile(np.array(plan["ranges"], dtype=np.float64), (chains, 1, 1))
+        if q is not None:
+            res["tl_q"] = np.tile(q, (chains, 1))
+            res["tl_q_n"], res["tl_q_s"] = smp.timeline_quantiles(q)
+        return res
+
+    def add_arguments(self, parser):
+        parser.add_argument("--timelines", help="Accumulate per cell, over all draws on the device, what a per-individual timeline needs "
+                            "(--thin does not apply): histograms of the S and N titers, from which the median and a 95 %% band are read, "
+                            "the infection probability and the exact probability of at least one infection so far in the cell's time "
+                            "chunk, and per individual the distribution of the number of infections (tl_* and tl_summary_* in the "
+                            "output).  Reports the individuals more likely infected than not, the median width of the bands and the share "
+                            "of bands that touch the ends of the range.", action="store_true")
+        parser.add_argument("--timeline_range_s", help="With --timelines: the S titer range of the histograms, --timeline_range_s=lo,hi.", default="-4,8")
+        parser.add_argument("--timeline_range_n", help="With --timelines: the N titer range of the histograms, --timeline_range_n=lo,hi.", default="-4,8")
+
+    def cli_options(self, args, data, chains, world):
+        """Over several processes every rank hands its chains' histograms to rank 0, which pools them (``add_summary``): no pooled
+        quantiles from the device then, and the run is refused (by every rank alike, before anything runs) when what rank 0 holds
+        after the gather -- the histograms and counters of all chains beside their recorded draws -- would not fit its host
+        budget."""
+        opts = {"timelines": args.timelines, "timeline_q": None if world > 1 else DEFAULT_Q, "timelines_hist": args.timelines and world > 1}
+        if not args.timelines:
+            return opts
+        ranges = []
+        for flag, text in (("--timeline_range_n", args.timeline_range_n), ("--timeline_range_s", args.timeline_range_s)):
+            try:
+                lo, hi = (float(x) for x in text.split(","))
+                ranges.append(check_range(lo, hi))
+            except ValueError as e:
+                raise SystemExit(f"{flag}: need lo,hi with lo < hi, got {text!r} ({e})")
+        opts["timeline_ranges"] = tuple(ranges)
+        if world > 1:
+            from .sampler import record_budget_bytes, record_bytes
+
+            K = (len(data.s) + len(data.n)) if (args.log_likelihood or args.posterior_predictive) else 0
+            own = result_bytes(chains, data.n_gaps, data.n_inds, n_q=0, hist=True)
+            rest = record_bytes(chains, -(-args.draws // args.thin), data.n_gaps, data.n_inds, not args.no_deterministics, not args.no_discrete,
+                                n_readings=K if args.log_likelihood else 0, n_replicates=K if args.posterior_predictive else 0)
+            if own + rest > record_budget_bytes():
+                raise SystemExit(f"--timelines over {world} processes gathers the histograms of {chains} chains on one rank: {own} bytes "
+                                 f"beside {rest} bytes of recorded draws, over the host budget of {record_budget_bytes()} bytes "
+                                 f"(ABD_RECORD_BUDGET_GB raises it; --thin, --no_deterministics, --no_discrete record less; one process "
+                                 f"needs no histograms on the host)")
+        return opts
+
+    def report(self, res, data):
+        return [line(add_summary(res, getattr(data, "last_gap", None)))]
+
+
+SUMMARY = _Timelines()
