@@ -173,6 +173,9 @@ SYMBOLS = {
     "abd_sampler_timelines": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_timeline_quantiles": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_sampler_adaptation": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
+    "abd_sampler_enable_leapfrog_log": (C.c_int, [_P, C.c_int64]),
+    "abd_sampler_leapfrog_log": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_launch_shape": (C.c_int, [_P, _I32]),
     "abd_theta_prior": (C.c_int, [_P, _D, _D, _D]),
     "abd_set_individual_offset": (C.c_int, [_P, C.c_int64]),
     "abd_kernel_timing": (C.c_int, [_P, C.c_int32]),
@@ -940,6 +943,38 @@ class NativeSampler:
         m = np.empty((N_THETA, N_THETA))
         _check(self._lib, self._lib.abd_sampler_adaptation(self._h, int(k), None, None, _ptr(m, C.c_double)))
         return m
+
+    # -- a test and debug facility: every evaluation the chains consume, and the launch shape they are evaluated with ----------
+    LEAPFROG_COLS = 58
+    _leapfrog_capacity = 0
+    TRAIN_KINDS = ("none", "lists", "dense")
+
+    def enable_leapfrog_log(self, rows_per_chain: int):
+        """Log every evaluation a chain's NUTS state consumes, up to ``rows_per_chain`` rows per chain (0: off); before the first
+        run (abd_hip.h: abd_sampler_enable_leapfrog_log)."""
+        _check(self._lib, self._lib.abd_sampler_enable_leapfrog_log(self._h, int(rows_per_chain)))
+        self._leapfrog_capacity = int(rows_per_chain)
+
+    def leapfrog_log(self, k: int):
+        """The k-th chain's log so far -> (rows, n_total): one record per kept row with the fields ``kind`` (0 the start point, 1
+        a transition's start point evaluated again after a sweep, 2 a leaf), ``iteration``, ``depth``, ``n_leaf``, ``dir``,
+        ``eps``, ``lp`` and ``q``, ``p_half``, ``g`` (17 each); n_total counts the rows beyond the capacity too."""
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_leapfrog_log(self._h, int(k), 0, 0, None, C.byref(n)))
+        have = min(n.value, self._leapfrog_capacity)
+        rows = np.empty((have, self.LEAPFROG_COLS))
+        if have:
+            _check(self._lib, self._lib.abd_sampler_leapfrog_log(self._h, int(k), 0, have, _ptr(rows, C.c_double), None))
+        dt = np.dtype([("kind", "f8"), ("iteration", "f8"), ("depth", "f8"), ("n_leaf", "f8"), ("dir", "f8"), ("eps", "f8"),
+                       ("lp", "f8"), ("q", "f8", (N_THETA,)), ("p_half", "f8", (N_THETA,)), ("g", "f8", (N_THETA,))])
+        return rows.view(dt).reshape(have), n.value
+
+    def launch_shape(self):
+        """{"unit": chains per unit, "trains": "none" / "lists" / "dense", "workgroups": workgroups with a range of a unit's leapfrog
+        launch as the kernel sees it, "threads": host threads} (abd_hip.h: abd_sampler_launch_shape)."""
+        out = np.zeros(4, np.int32)
+        _check(self._lib, self._lib.abd_sampler_launch_shape(self._h, _ptr(out, C.c_int32)))
+        return {"unit": int(out[0]), "trains": self.TRAIN_KINDS[int(out[1])], "workgroups": int(out[2]), "threads": int(out[3])}
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

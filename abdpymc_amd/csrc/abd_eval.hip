@@ -203,6 +203,8 @@ LaunchPlan plan_launch(const abd_ctx* c, const Caller& who, int n, int steps) {
   return p;
 }
 
+int eval_grid(const abd_ctx* c, Caller::Kind kind, int n) { return (int)plan_launch(c, Caller{kind}, n, 1).grid.x; }
+
 int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows, int steps) {
   const LaunchPlan p = plan_launch(c, who, n, steps);
   const int n_rows = n * steps;  // chains of the launch as the kernel sees them: step s, chain j is row s * n + j
@@ -430,6 +432,10 @@ TrainKernel train_kernel(int cb, bool xc, bool planes) {
   return xc ? train_kernel_form<R, 1, true>(planes) : train_kernel_form<R, 1, false>(planes);
 }
 
+// The service workgroup takes a workgroup slot: a grid that fills the chip exactly leaves it one (the ranges are equal shares of
+// the plane whatever their number), or the last range would only start when the first workgroup has left.
+int dense_train_ranges(const abd_ctx* c, int blocks) { return (blocks > 1 && blocks % c->n_cu == 0) ? blocks - 1 : blocks; }
+
 // Queue one launch of a train unit of cb (1, 2 or 4) chains on pipe pi: a->tc[0 .. cb) filled by the caller, everything
 // else here.  `blocks`: workgroups with a range (the unit's fixed shape: its chains' numbers depend on nothing else).
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a) {
@@ -474,11 +480,9 @@ int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* 
   a->prior_const = c->prior_const;
   a->xcd_remap = c->xcd_remap ? 1 : 0;
   a->service = any_fwd ? 1 : 0;
-  // the service workgroup takes a workgroup slot: a grid that fills the chip exactly leaves it one (the ranges are equal
-  // shares of the plane whatever their number), or the last range would only start when the first workgroup has left.
-  // ALWAYS, whether this launch carries a service workgroup or not: the split of the plane decides the order of the sums, and
-  // a chain's numbers must not depend on what its unit's other chains happen to have pending
-  if (any_step && blocks > 1 && blocks % c->n_cu == 0) blocks -= 1;
+  // dense_train_ranges ALWAYS, whether this launch carries a service workgroup or not: the split of the plane decides the order
+  // of the sums, and a chain's numbers must not depend on what its unit's other chains happen to have pending
+  if (any_step) blocks = dense_train_ranges(c, blocks);
   a->G = c->G;
   a->N = c->N;
   a->n_lg = c->n_lg;

@@ -335,6 +335,10 @@ int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* 
 int enqueue_group(abd_ctx* c, const Caller& who, int n, const int32_t* chains, const HostTerms* host, bool grad, double* rows, int steps = 1);
 int fetch_slot(abd_ctx* c, int slot, double* logp, double* grad, bool with_priors = true);
 int enqueue_dense_train(abd_ctx* c, int pi, int cb, int blocks, DenseTrainArgs* a);
+// workgroups with a range, as the kernel sees them: of a stepping train launch queued with `blocks` (enqueue_dense_train), and of a
+// `kind` launch of n chains (enqueue_group)
+int dense_train_ranges(const abd_ctx* c, int blocks);
+int eval_grid(const abd_ctx* c, Caller::Kind kind, int n);
 int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1, int steps = 1);
 
 // Pointwise log-likelihood of chain `chain` at theta on stream st (abd_readings.hpp: LogLik): the row ll (sorted order, S

@@ -32,11 +32,52 @@
 #include <cstdint>
 #include <cstring>
 #include <limits>
+#include <vector>
 
 namespace abdnuts {
 
 constexpr int D = 17;        // continuous value variables
 constexpr int MAX_DEPTH = 16;  // hard cap on the tree depth the checkpoints are sized for
+
+// The leapfrog log: a test and debug facility, off unless a driver attaches one (Nuts::attach_log).  One row of LOG_COLS
+// doubles per evaluation the chain CONSUMED -- whatever is handed to Nuts::attach_log (the chain's point when the log is
+// attached: the start point a driver created it with), Nuts::set_point (the start point of a transition, evaluated again
+// because the discrete state changed under the chain) and Nuts::feed (a leaf); evaluations a device took beyond the end of a
+// tree are never fed and so never logged:
+//   [LOG_KIND] LOG_INIT / LOG_START / LOG_LEAF   [LOG_ITERATION] Nuts::iteration   [LOG_DEPTH], [LOG_N_LEAF], [LOG_DIR] the
+//   half the leaf belongs to (the doubling at `depth`), its index in that half and the half's direction (0 unless a leaf)
+//   [LOG_EPS] the chain's step size   [LOG_LP] logp as handed over   [LOG_Q ..] the 17 unconstrained values that were
+//   evaluated   [LOG_P_HALF ..] the half-kicked momentum the leaf was reached with (0 unless a leaf)   [LOG_G ..] the
+//   gradient as handed over
+// The iteration rule: [LOG_ITERATION] is the driver's counter of the transition the row belongs to (a LOG_START row: the one
+// that starts from it), so the discrete state a row was evaluated under is the state at the start of the run for the run's
+// first iteration and whenever the driver has no sweep, else the state the sweep of iteration - 1 left.
+// Rows beyond the capacity are counted (n_total) and dropped.  A chain owns its log: no locking.
+enum { LOG_KIND = 0, LOG_ITERATION, LOG_DEPTH, LOG_N_LEAF, LOG_DIR, LOG_EPS, LOG_LP, LOG_Q, LOG_P_HALF = LOG_Q + D, LOG_G = LOG_P_HALF + D, LOG_COLS = LOG_G + D };
+enum { LOG_INIT = 0, LOG_START = 1, LOG_LEAF = 2 };
+struct LeapfrogLog {
+  std::vector<double> rows;  // [capacity][LOG_COLS]
+  int64_t capacity = 0, n_total = 0;
+  explicit LeapfrogLog(int64_t capacity_rows = 0) : rows((size_t)capacity_rows * LOG_COLS), capacity(capacity_rows) {}
+  int64_t stored() const { return n_total < capacity ? n_total : capacity; }
+  void append(int kind, int64_t iteration, int depth, int n_leaf, int dir, double eps, double lp, const double* q, const double* p_half,
+              const double* g) {
+    if (n_total++ >= capacity) return;
+    double* r = rows.data() + (size_t)(n_total - 1) * LOG_COLS;
+    r[LOG_KIND] = kind;
+    r[LOG_ITERATION] = (double)iteration;
+    r[LOG_DEPTH] = depth;
+    r[LOG_N_LEAF] = n_leaf;
+    r[LOG_DIR] = dir;
+    r[LOG_EPS] = eps;
+    r[LOG_LP] = lp;
+    for (int d = 0; d < D; ++d) {
+      r[LOG_Q + d] = q[d];
+      r[LOG_P_HALF + d] = p_half ? p_half[d] : 0.0;
+      r[LOG_G + d] = g[d];
+    }
+  }
+};
 
 // xoshiro256++ (Blackman & Vigna), seeded through splitmix64: one independent stream per chain
 struct Rng {
@@ -216,6 +257,8 @@ struct Nuts {
   int max_depth = 10;
   Rng rng;
   Stats stats;
+  LeapfrogLog* log = nullptr;  // not owned; nullptr: off
+  int64_t iteration = 0;       // the driver's counter of the transition in progress or about to begin (LeapfrogLog: the iteration rule)
 
   // ---- one transition ----
   bool active = false;
@@ -245,6 +288,7 @@ struct Nuts {
       for (int c = 0; c < D; ++c) cov[r][c] = chol[r][c] = r == c ? 1.0 : 0.0;
     rng.seed(seed, stream);
     active = false;
+    iteration = 0;
   }
   // install a dense M^-1; returns false (and keeps the old one) if it is not positive definite
   bool set_dense_metric(const double m[D][D]) {
@@ -281,8 +325,14 @@ struct Nuts {
     }
   }
   void set_point(double lp0, const double* g0) {  // the discrete state changed under the chain
+    if (log) log->append(LOG_START, iteration, 0, 0, 0, eps, lp0, q, nullptr, g0);
     lp = lp0;
     std::memcpy(g, g0, sizeof(g));
+  }
+  // from now on every evaluation the chain consumes is logged (nullptr: none); the first row is the chain's point as it is
+  void attach_log(LeapfrogLog* l) {
+    log = l;
+    if (log) log->append(LOG_INIT, iteration, 0, 0, 0, eps, lp, q, nullptr, g);
   }
 
   double kinetic(const double* p) const {
@@ -363,6 +413,7 @@ struct Nuts {
   // point is adopted there too
   void feed(double lp1, const double* g1, const double* next_q = nullptr, const double* next_p_half = nullptr, bool across_halves = false) {
     const int half_before = depth;
+    if (log) log->append(LOG_LEAF, iteration, depth, n_leaf, dir, eps, lp1, req_q, p_half, g1);
     feed_(lp1, g1);
     if (next_q && active && (across_halves || (depth == half_before && n_leaf > 0))) {
       std::memcpy(req_q, next_q, sizeof(req_q));
@@ -548,6 +599,7 @@ struct AdaptiveNuts {
       if (it == tune - 1) nuts.eps = da.final_eps();
     }
     it += 1;
+    nuts.iteration = it;
   }
 };
 

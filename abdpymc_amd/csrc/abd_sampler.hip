@@ -88,6 +88,7 @@ struct abd_sampler {
   int64_t rec_chunk = 0;      // recording: device staging of up to rec_chunk draws per chain, [n][rec_chunk][...] per variable
   bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise / _predictive are refused after that)
   std::vector<double> lp, gr;  // starting points' logp / gradient
+  std::vector<abdnuts::LeapfrogLog> lf_log;  // abd_sampler_enable_leapfrog_log: chain k's log, ch[k].nuts points at it (empty: off)
   int unit = 1;                // chains per independent unit (sampler_run_units)
   int threads = 1;  // host threads that drive the units (sampler_run_units)
   // Leapfrog trains of observation lists (abd_types.hpp: TrainArgs): one chain per unit, diagonal metric.  Every evaluation of such a
@@ -618,6 +619,16 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   return ABD_OK;
 }
 
+// host threads that drive the units of sampler_run_units: a power of two <= 8, so that units that share a HIP stream (u and
+// u + 8) share their thread (one thread while abd_kernel_timing is on: the event bookkeeping of enqueue_group belongs to the
+// context, not to a unit)
+int unit_threads(const abd_sampler* s) {
+  const int n_units = (s->n + s->unit - 1) / s->unit;
+  int T = 1;
+  while (s->c->timing == 0 && 2 * T <= std::min({s->threads, n_units, (int)kMaxPipes})) T *= 2;
+  return T;
+}
+
 // The sampler's chains run as independent UNITS of `unit` consecutive chains (1 for large dense cohorts, 4 otherwise;
 // abd_sampler_create), unit u on HIP stream u mod 8 with its own private result rows (slot kSyncSlot + u):
 //   tree:      one evaluation launch per leapfrog for the unit's chains whose tree is still growing
@@ -645,10 +656,7 @@ int sampler_run_units(RunFrame& f) {
     std::vector<double> th, lp, gr;
   };
   std::vector<Unit> units((size_t)n_units);
-  // host threads (see below): a power of two <= 8, so that units that share a HIP stream (u and u + 8) share their thread
-  // (one thread while abd_kernel_timing is on: the event bookkeeping of enqueue_group belongs to the context, not to a unit)
-  int T_all = 1;
-  while (c->timing == 0 && 2 * T_all <= std::min({s->threads, n_units, (int)kMaxPipes})) T_all *= 2;
+  const int T_all = unit_threads(s);
   // one completion-tag sequence per unit, disjoint from the context's and from each other's (unit u: (u + 1) 2^40 + k).  It
   // belongs to the CONTEXT, like the result rows kSyncSlot + u the tags are compared against: monotone for the life of
   // those rows, whichever sampler drives them
@@ -1206,6 +1214,52 @@ int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* mu_n_me
     for (size_t e = 0; e < cells; ++e) outs[v][e] *= inv;
   }
   if (n_draws) *n_draws = s->n_accumulated;
+  return ABD_OK;
+}
+
+static_assert(abdnuts::LOG_COLS == ABD_LEAPFROG_COLS && abdnuts::LOG_INIT == ABD_LEAPFROG_INIT && abdnuts::LOG_START == ABD_LEAPFROG_START &&
+                  abdnuts::LOG_LEAF == ABD_LEAPFROG_LEAF && abdnuts::D == ABD_N_THETA,
+              "abd_hip.h states the leapfrog log's row as abd_nuts.hpp writes it");
+
+int abd_sampler_enable_leapfrog_log(abd_sampler* s, int64_t capacity_rows_per_chain) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (capacity_rows_per_chain < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity_rows_per_chain);
+  if (s->ran) return fail(ABD_ERR_STATE, "the leapfrog log must be enabled before the first abd_sampler_run call");
+  for (auto& ch : s->ch) ch.nuts.attach_log(nullptr);
+  s->lf_log.clear();
+  if (capacity_rows_per_chain == 0) return ABD_OK;
+  try {
+    s->lf_log.assign((size_t)s->n, abdnuts::LeapfrogLog(capacity_rows_per_chain));
+  } catch (const std::bad_alloc&) {
+    s->lf_log.clear();
+    return fail(ABD_ERR_NOMEM, "leapfrog log: %lld rows for each of %d chains", (long long)capacity_rows_per_chain, s->n);
+  }
+  for (int k = 0; k < s->n; ++k) s->ch[(size_t)k].nuts.attach_log(&s->lf_log[(size_t)k]);  // (row 0: the start point)
+  return ABD_OK;
+}
+
+int abd_sampler_leapfrog_log(abd_sampler* s, int32_t k, int64_t first, int64_t count, double* rows, int64_t* n_total) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (s->lf_log.empty()) return fail(ABD_ERR_STATE, "the leapfrog log is not enabled (abd_sampler_enable_leapfrog_log)");
+  const abdnuts::LeapfrogLog& log = s->lf_log[(size_t)k];
+  const int64_t have = log.stored();
+  if (n_total) *n_total = log.n_total;
+  if (first < 0 || count < 0 || first > have || count > have - first)
+    return fail(ABD_ERR_ARG, "leapfrog log: rows [%lld, %lld) are beyond the %lld the chain holds", (long long)first, (long long)(first + count),
+                (long long)have);
+  if (count && !rows) return fail(ABD_ERR_ARG, "rows is NULL");
+  if (count) std::memcpy(rows, log.rows.data() + (size_t)first * abdnuts::LOG_COLS, (size_t)count * abdnuts::LOG_COLS * sizeof(double));
+  return ABD_OK;
+}
+
+int abd_sampler_launch_shape(abd_sampler* s, int32_t out[4]) {
+  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  const abd_ctx* c = s->c;
+  out[0] = s->unit;
+  out[1] = s->dtrains ? ABD_TRAINS_DENSE : (s->trains ? ABD_TRAINS_LISTS : ABD_TRAINS_NONE);
+  out[2] = s->dtrains ? dense_train_ranges(c, s->dtrain_blocks) : eval_grid(c, s->trains ? Caller::Train : Caller::Unit, s->unit);
+  out[3] = s->dtrains ? 1 : unit_threads(s);
   return ABD_OK;
 }
 

@@ -298,6 +298,10 @@ int abd_simulate_staged(abd_ctx* ctx, const abd_sim_params* params, const double
  * are driven by the calling thread alone.
  * Step size: dual averaging to `target_accept`; metric: diagonal, windowed running variance of the tuning draws
  * (abdpymc_amd/csrc/abd_nuts.hpp).
+ * Every evaluation a chain consumes on any of these drivers can be logged for tests (abd_sampler_enable_leapfrog_log below):
+ * one row of 58 doubles -- kind, iteration, depth, n_leaf, dir, eps, lp, q[17], p_half[17], g[17] -- per start point and
+ * leaf, where `iteration` names the tree the row belongs to and so the discrete state it was evaluated under: the state at
+ * the start of the run for the run's first iteration and with gibbs = 0, else the state the sweep of iteration - 1 left.
  * Iterations [0, tune) adapt; later ones are draws.  Randomness: one xoshiro256++ stream per chain keyed by
  * (seed, chain slot) for NUTS; Philox keyed by (seed, iteration) for the sweep. */
 typedef struct abd_sampler abd_sampler;
@@ -494,6 +498,45 @@ int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* 
  * k between two abd_sampler_run calls, e.g. one adaptation pooled over the chains (PyMC: pm.sample(step=pm.NUTS(scaling=...,
  * step_scale=...))).  During iterations < tune the chain goes on adapting from there. */
 int abd_sampler_set_adaptation(abd_sampler* s, int32_t k, const double* inv_mass, double step_size);
+
+/* The leapfrog log: a test and debug facility (no per-draw summary; off by default, one branch per evaluation when off).  Every
+ * evaluation a chain's NUTS state CONSUMES is appended to the chain's own host buffer as one row of ABD_LEAPFROG_COLS doubles,
+ * on all three drivers (dense trains, observation-list trains, host-driven units) at the one place they share
+ * (abdpymc_amd/csrc/abd_nuts.hpp: attach_log / set_point / feed).  Steps the device took beyond the end of a tree are never fed
+ * and so never logged.  Columns:
+ *   0 kind        ABD_LEAPFROG_INIT: the chain's start point (row 0, written when the log is enabled);  ABD_LEAPFROG_START: the
+ *                 start point of a transition, evaluated again after a sweep;  ABD_LEAPFROG_LEAF: a leapfrog of a tree
+ *   1 iteration   the sampler's iteration counter of the tree the row belongs to (a START row: the tree that starts from it; the
+ *                 one behind the last iteration of a run call: the next call's first)
+ *   2 depth, 3 n_leaf, 4 dir   the doubling the leaf belongs to, its index in that half, the half's direction +-1 (0 unless LEAF)
+ *   5 eps         the chain's step size
+ *   6 lp          logp as the evaluation gave it
+ *   7 .. 23   q       the unconstrained point that was evaluated
+ *   24 .. 40  p_half  the half-kicked momentum the leaf was reached with (0 unless LEAF)
+ *   41 .. 57  g       the gradient as the evaluation gave it
+ * The iteration rule: a row was evaluated under the discrete state at the start of the run if its iteration is the run's
+ * first or opts.gibbs is 0, else under the state the sweep of iteration - 1 left (abd_record: i_raw, ab_s_waner of that draw).
+ * Consecutive LEAF rows a, b of one half (same iteration and depth, n_leaf_b = n_leaf_a + 1) are one leapfrog apart: with
+ * ve = dir eps,  q_b = q_a + ve M^-1 (p_half_a + ve g_a)  and  p_half_b = p_half_a + ve g_a.
+ * capacity_rows_per_chain = 0 turns the log off.  Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it). */
+#define ABD_LEAPFROG_COLS 58
+#define ABD_LEAPFROG_INIT 0
+#define ABD_LEAPFROG_START 1
+#define ABD_LEAPFROG_LEAF 2
+int abd_sampler_enable_leapfrog_log(abd_sampler* s, int64_t capacity_rows_per_chain);
+/* Rows first .. first + count - 1 of chain k's log into rows ([count][ABD_LEAPFROG_COLS]); *n_total (may be NULL): the rows the
+ * chain has produced so far -- those beyond the capacity are counted and dropped, and asking for one is ABD_ERR_ARG.  May be
+ * called between run calls. */
+int abd_sampler_leapfrog_log(abd_sampler* s, int32_t k, int64_t first, int64_t count, double* rows, int64_t* n_total);
+/* The launch shape the sampler settled on: out[0] chains per unit; out[1] how its leapfrogs run (ABD_TRAINS_*); out[2] the
+ * workgroups with a range that a leapfrog launch of a full unit has as the kernel sees it (dense trains: more than 256 sum
+ * their partial rows in two levels; host-driven units: the grid of an evaluation launch of all the unit's chains); out[3] the
+ * host threads that drive the units.  What ABD_SAMPLER_UNIT, ABD_SAMPLER_TRAINS, ABD_TRAIN_BLOCKS_PER_CU and
+ * ABD_GROUP_BLOCKS_PER_CU came to. */
+#define ABD_TRAINS_NONE 0
+#define ABD_TRAINS_LISTS 1
+#define ABD_TRAINS_DENSE 2
+int abd_sampler_launch_shape(abd_sampler* s, int32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------------
  * One chain over several GPUs (cohorts too large or too slow for one): the joint logp is a sum over

@@ -2,9 +2,24 @@
 // independent-normal target whose moments are known in closed form.  Built by tests/test_nuts_native.py with g++.
 #include "abd_nuts.hpp"
 
+namespace {
+// the leapfrog log of a harness run (abd_nuts.hpp: LeapfrogLog): chain c's rows go to rows[c][capacity][LOG_COLS], the rows it
+// produced -- kept or not -- to n_total[c]; capacity < 0: no log is attached
+struct LogOut {
+  long long capacity = -1;
+  double* rows = nullptr;
+  long long* n_total = nullptr;
+  void take(int c, const abdnuts::LeapfrogLog& log) const {
+    if (capacity < 0) return;
+    if (log.stored()) std::memcpy(rows + (size_t)c * capacity * abdnuts::LOG_COLS, log.rows.data(), (size_t)log.stored() * abdnuts::LOG_COLS * sizeof(double));
+    n_total[c] = log.n_total;
+  }
+};
+
 // target: independent normals (prec == NULL: mean, sd) or a correlated normal with precision matrix prec (17 x 17)
-extern "C" int nuts_harness_run(const double* mean, const double* sd, const double* prec, long long tune, long long draws,
-                                unsigned long long seed, int n_chains, int dense, double* out_q, double* out_stats) {
+// eval_first: every transition starts with an evaluation of its start point (set_point), as a host-driven unit does after a sweep
+int run_classic(const double* mean, const double* sd, const double* prec, long long tune, long long draws, unsigned long long seed,
+                int n_chains, int dense, int eval_first, const LogOut& lo, double* out_q, double* out_stats) {
   using namespace abdnuts;
   auto eval = [&](const double* q, double* g) {
     double lp = 0;
@@ -26,14 +41,23 @@ extern "C" int nuts_harness_run(const double* mean, const double* sd, const doub
   };
   // chains advance in lock step, one pending evaluation each, the way the device driver batches them
   AdaptiveNuts* ch = new AdaptiveNuts[n_chains];
+  std::vector<LeapfrogLog> logs((size_t)n_chains, LeapfrogLog(lo.capacity < 0 ? 0 : lo.capacity));
   for (int c = 0; c < n_chains; ++c) {
     double q0[D], g0[D];
     for (int d = 0; d < D; ++d) q0[d] = mean[d] + sd[d] * (c % 2 ? 1.5 : -1.5);
     const double lp0 = eval(q0, g0);
     ch[c].init(q0, lp0, g0, seed, (unsigned long long)c, tune, 10, 0.8, dense != 0);
+    if (lo.capacity >= 0) ch[c].nuts.attach_log(&logs[(size_t)c]);
   }
   for (long long it = 0; it < tune + draws; ++it) {
-    for (int c = 0; c < n_chains; ++c) ch[c].begin();
+    for (int c = 0; c < n_chains; ++c) {
+      if (eval_first) {
+        double g[D];
+        const double lp = eval(ch[c].nuts.q, g);
+        ch[c].nuts.set_point(lp, g);
+      }
+      ch[c].begin();
+    }
     bool any = true;
     while (any) {
       any = false;
@@ -61,8 +85,15 @@ extern "C" int nuts_harness_run(const double* mean, const double* sd, const doub
       }
     }
   }
+  for (int c = 0; c < n_chains; ++c) lo.take(c, logs[(size_t)c]);
   delete[] ch;
   return 0;
+}
+}  // namespace
+
+extern "C" int nuts_harness_run(const double* mean, const double* sd, const double* prec, long long tune, long long draws,
+                                unsigned long long seed, int n_chains, int dense, double* out_q, double* out_stats) {
+  return run_classic(mean, sd, prec, tune, draws, seed, n_chains, dense, 0, LogOut(), out_q, out_stats);
 }
 
 // ---- the leapfrog-train protocol (abd_train.hpp <-> abd_sampler.hip: sampler_run_trains), with the DEVICE's part restated on
@@ -191,8 +222,9 @@ bool dev_step(DeviceChain& st, double lp, const double* g, DeviceRecord& rec) {
 // independent normals, diagonal metric; eval_first: every transition starts with an evaluation of its start point (what the
 // compound step does after a sweep: begin_draw / set_point / begin_finish / adopt_request); run_on: steps the device takes
 // beyond the end of a tree before the host stops it (the look-ahead: never looked at)
-extern "C" int nuts_harness_run_trains(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed,
-                                       int n_chains, int eval_first, int run_on, double* out_q, double* out_stats) {
+namespace {
+int run_trains(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed, int n_chains, int eval_first,
+               int run_on, const LogOut& lo, double* out_q, double* out_stats) {
   using namespace abdnuts;
   auto eval = [&](const double* q, double* g) {
     double lp = 0;
@@ -209,6 +241,8 @@ extern "C" int nuts_harness_run_trains(const double* mean, const double* sd, lon
     double q0[D], g0[D];
     for (int d = 0; d < D; ++d) q0[d] = mean[d] + sd[d] * (c % 2 ? 1.5 : -1.5);
     ch.init(q0, eval(q0, g0), g0, seed, (unsigned long long)c, tune, 10, 0.8, false);
+    LeapfrogLog log(lo.capacity < 0 ? 0 : lo.capacity);
+    if (lo.capacity >= 0) ch.nuts.attach_log(&log);
     for (long long it = 0; it < tune + draws; ++it) {
       Nuts& nu = ch.nuts;
       DeviceRecord rec;
@@ -251,6 +285,26 @@ extern "C" int nuts_harness_run_trains(const double* mean, const double* sd, lon
         s[5] = nu.stats.diverging ? 1.0 : 0.0;
       }
     }
+    lo.take(c, log);
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int nuts_harness_run_trains(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed,
+                                       int n_chains, int eval_first, int run_on, double* out_q, double* out_stats) {
+  return run_trains(mean, sd, tune, draws, seed, n_chains, eval_first, run_on, LogOut(), out_q, out_stats);
+}
+
+// Either driver with the leapfrog log on (trains = 0: the classic loop, run_on ignored; capacity < 0: no log is attached):
+// rows [n_chains][capacity][abdnuts::LOG_COLS], n_total [n_chains].  Independent normals, diagonal metric.
+extern "C" int nuts_harness_run_logged(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed,
+                                       int n_chains, int trains, int eval_first, int run_on, long long capacity, double* rows,
+                                       long long* n_total, double* out_q, double* out_stats) {
+  LogOut lo;
+  lo.capacity = capacity;
+  lo.rows = rows;
+  lo.n_total = n_total;
+  return trains ? run_trains(mean, sd, tune, draws, seed, n_chains, eval_first, run_on, lo, out_q, out_stats)
+                : run_classic(mean, sd, nullptr, tune, draws, seed, n_chains, 0, eval_first, lo, out_q, out_stats);
 }

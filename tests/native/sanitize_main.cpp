@@ -1,6 +1,7 @@
 // AddressSanitizer / UBSan driver for the HIP-free host code (CPU only; the GPU side is never sanitised):
 //   * the NUTS state machine of the native sampler (abdpymc_amd/csrc/abd_nuts.hpp) through tests/native/nuts_harness.cpp,
-//     classic loop and leapfrog-train protocol
+//     classic loop and leapfrog-train protocol, and both again with the leapfrog log on: a buffer that holds every row, one that
+//     fills up, one of no rows
 //   * the plain-C restatement oracle/abd_oracle.c: logp + gradient (dense and ragged observation lists, 0-2 splits,
 //     ignore_pcrpos) and the Gibbs sweep
 // Built and run by tests/test_sanitizers.py with -fsanitize=address,undefined -fno-sanitize-recover=all.
@@ -14,6 +15,9 @@ extern "C" int nuts_harness_run(const double* mean, const double* sd, const doub
                                 unsigned long long seed, int n_chains, int dense, double* out_q, double* out_stats);
 extern "C" int nuts_harness_run_trains(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed,
                                        int n_chains, int eval_first, int run_on, double* out_q, double* out_stats);
+extern "C" int nuts_harness_run_logged(const double* mean, const double* sd, long long tune, long long draws, unsigned long long seed,
+                                       int n_chains, int trains, int eval_first, int run_on, long long capacity, double* rows,
+                                       long long* n_total, double* out_q, double* out_stats);
 extern "C" int abd_oracle_logp_dlogp(int G, int N, int n_splits, const int* splits, const int8_t* vacs, const int8_t* pcrpos,
                                      int64_t K_s, const int32_t* s_gap, const int32_t* s_ind, const double* s_x,
                                      const double* s_y, int64_t K_n, const int32_t* n_gap, const int32_t* n_ind,
@@ -118,6 +122,25 @@ int main() {
         REQUIRE(rc == 0);
         REQUIRE(q2 == q);
       }
+      // the leapfrog log (abd_nuts.hpp: LeapfrogLog), buffers sized exactly: the append, the full buffer, the empty one
+      const int cols = 58;
+      long long full[2] = {0, 0};
+      for (long long cap : {100000ll, 41ll, 1ll, 0ll})
+        for (int trains = 0; trains < 2; ++trains) {
+          std::vector<double> rows((size_t)chains * cap * cols, -7.0);
+          long long n_total[2] = {-1, -1};
+          rc = nuts_harness_run_logged(mean.data(), sd.data(), tune, draws, 7ull, chains, trains, trains, 3, cap, rows.data(), n_total,
+                                       q2.data(), st2.data());
+          REQUIRE(rc == 0);
+          REQUIRE(q2 == q);
+          for (int c = 0; c < chains; ++c) {
+            if (cap == 100000 && trains == 0) full[c] = n_total[c];
+            REQUIRE(n_total[c] > 41 && n_total[c] < 100000);
+            REQUIRE(n_total[c] == full[c] + (trains ? tune + draws : 0));  // (+ every transition's start point)
+            const long long kept = n_total[c] < cap ? n_total[c] : cap;
+            for (long long r = 0; r < cap; ++r) REQUIRE((rows[((size_t)c * cap + r) * cols] != -7.0) == (r < kept));
+          }
+        }
     }
   }
   // ---- oracle: shapes the reference's tests and BASELINE configs use, small ----

@@ -133,3 +133,79 @@ def test_the_leapfrog_train_protocol_gives_the_classic_draws(harness, tmp_path):
         np.testing.assert_array_equal(q, q_ref, err_msg=f"eval_first={eval_first} run_on={run_on}")
         np.testing.assert_array_equal(st, st_ref)
     assert st_ref[..., 1].max() >= 3  # trees with several doublings, i.e. halves the device entered by itself
+
+
+LOG_COLS = 7 + 3 * 17  # abd_nuts.hpp: LOG_COLS -- kind, iteration, depth, n_leaf, dir, eps, lp, q, p_half, g
+
+
+def _run_logged(lib_path, mean, sd, tune, draws, seed, chains, trains, eval_first, run_on, capacity):
+    """nuts_harness_run_logged -> (rows per chain, n_total per chain, q, stats); one guard row behind every chain's buffer."""
+    lib = C.CDLL(lib_path)
+    dp, lp = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+    lib.nuts_harness_run_logged.argtypes = [dp, dp, C.c_longlong, C.c_longlong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_longlong, dp, lp, dp, dp]
+    lib.nuts_harness_run_logged.restype = C.c_int
+    cap = max(capacity, 0)
+    buf = np.full((chains * cap + 1, LOG_COLS), -7.0)  # (the guard: a row past the last chain's capacity stays as it is)
+    n_total = np.full(chains, -1, dtype=np.longlong)
+    q = np.empty((chains, draws, 17))
+    st = np.empty((chains, draws, 6))
+    rc = lib.nuts_harness_run_logged(mean.ctypes.data_as(dp), sd.ctypes.data_as(dp), tune, draws, seed, chains, trains, eval_first, run_on,
+                                     capacity, buf.ctypes.data_as(dp), n_total.ctypes.data_as(lp), q.ctypes.data_as(dp), st.ctypes.data_as(dp))
+    assert rc == 0, rc
+    assert np.all(buf[-1] == -7.0)
+    rows = [buf[c * cap:c * cap + min(cap, max(int(n_total[c]), 0))] for c in range(chains)]
+    return rows, n_total, q, st
+
+
+def test_the_leapfrog_log_holds_what_the_chain_consumed(harness):
+    """abd_nuts.hpp: LeapfrogLog on both drivers of the harness (the classic request / feed loop, the restated train protocol),
+    with and without an evaluation of every transition's start point: every row is the target at the row's point, an iteration
+    has as many leaf rows as its n_steps, steps taken beyond the end of a tree leave no row, both drivers log the same rows, a
+    full buffer counts what it drops, and the log changes no draw."""
+    mean, sd = _target()
+    tune, draws, chains, seed, big = 60, 40, 2, 13, 40000
+    q_off = None
+    for eval_first in (0, 1):
+        logged = {}
+        for trains, run_on in ((0, 0), (1, 0), (1, 5)):
+            rows, n_total, q, st = _run_logged(harness.lib_path, mean, sd, tune, draws, seed, chains, trains, eval_first, run_on, big)
+            logged[(trains, run_on)] = rows
+            assert np.all(n_total < big) and [len(r) for r in rows] == list(n_total)
+            for c, r in enumerate(rows):
+                kind, it = r[:, 0], r[:, 1]
+                pts, p_half, g = r[:, 7:24], r[:, 24:41], r[:, 41:58]
+                # the target's closed form at the logged point
+                np.testing.assert_allclose(r[:, 6], -0.5 * (((pts - mean) / sd) ** 2).sum(-1), rtol=1e-10, atol=1e-10)
+                np.testing.assert_allclose(g, -(pts - mean) / sd ** 2, rtol=1e-10, atol=1e-10)
+                # row 0 is the start point; every transition's start point follows if it is evaluated, under its own iteration
+                assert kind[0] == 0 and it[0] == 0 and np.all(kind[1:] > 0)
+                np.testing.assert_array_equal(it[kind == 1], np.arange(tune + draws) if eval_first else [])
+                assert np.all(p_half[kind != 2] == 0) and np.all(r[kind != 2, 2:5] == 0)
+                assert np.all(np.diff(it) >= 0) and np.all(np.abs(r[kind == 2, 4]) == 1)
+                # as many leaf rows as the transition took steps (the stats are those of the draws)
+                leaves = np.bincount(it[kind == 2].astype(int), minlength=tune + draws)
+                np.testing.assert_array_equal(leaves[tune:], st[c, :, 2])
+                # consecutive leaves of a half are one leapfrog apart (stage_leapfrog; the metric is diagonal, and known only through
+                # the step: check the momentum, which needs no metric)
+                a, b = r[:-1], r[1:]
+                same = (a[:, 0] == 2) & (b[:, 0] == 2) & (a[:, 1] == b[:, 1]) & (a[:, 2] == b[:, 2]) & (b[:, 3] == a[:, 3] + 1)
+                assert same.sum() > 100
+                ve = (a[:, 4] * a[:, 5])[same, None]
+                np.testing.assert_allclose(b[same, 24:41], a[same, 24:41] + ve * a[same, 41:58], rtol=1e-12, atol=1e-12)
+            if q_off is None:  # the log off: the same draws, bit for bit
+                _, n_off, q_off, st_off = _run_logged(harness.lib_path, mean, sd, tune, draws, seed, chains, 0, 0, 0, -1)
+                assert np.all(n_off == -1)
+                np.testing.assert_array_equal(q_off, q)
+                np.testing.assert_array_equal(st_off, st)
+            np.testing.assert_array_equal(q, q_off)  # (evaluating the start point again changes nothing on this target either)
+        for key in ((1, 0), (1, 5)):
+            for c in range(chains):
+                np.testing.assert_array_equal(logged[key][c], logged[(0, 0)][c], err_msg=f"eval_first={eval_first} trains, run_on={key[1]}")
+        # a full buffer: the first rows are kept, the rest counted and dropped (0: every row is dropped)
+        for cap in (37, 1, 0):
+            rows, n_total, q, _ = _run_logged(harness.lib_path, mean, sd, tune, draws, seed, chains, 1, eval_first, 2, cap)
+            for c in range(chains):
+                assert n_total[c] == len(logged[(0, 0)][c]) and len(rows[c]) == cap
+                np.testing.assert_array_equal(rows[c], logged[(0, 0)][c][:cap])
+            np.testing.assert_array_equal(q, q_off)
