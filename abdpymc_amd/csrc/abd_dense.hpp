@@ -115,23 +115,34 @@ __device__ __forceinline__ RowDesc<XC> row_desc(const ARGS& a, int antigen, int 
   }
   return d;
 }
-// row `row` (relative to the descriptor's base) for this lane: scalar row offset + a constant per-lane offset
+// A row for this lane: a scalar offset from the descriptor's base + a constant per-lane offset.  The offset's unit is the one
+// in which a row is a plain stride -- bytes of the pair panel, cells of the split panels (whose two panels differ in cell
+// size): row_stride() of it is one row.  The plane form keeps the offset running (abd_planes.hpp: abd_row_off_next).
 template <typename R, bool XC>
-__device__ __forceinline__ RowData<R, XC> row_load(const RowDesc<XC>& d, int lane, int row, int N) {
+__device__ __forceinline__ uint32_t row_stride(int N) {
+  if constexpr (XC) return 64u;
+  else return (uint32_t)N * (uint32_t)sizeof(YX<R>);
+}
+template <typename R, bool XC>
+__device__ __forceinline__ RowData<R, XC> row_load_at(const RowDesc<XC>& d, int lane, uint32_t off) {
   RowData<R, XC> r;
   if constexpr (XC) {
-    const uint32_t soff = (uint32_t)row * 64u;
     if constexpr (sizeof(R) == 8) {
-      const abd_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(d.rs_y, (uint32_t)lane * 8u, soff * 8u, 0);
+      const abd_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(d.rs_y, (uint32_t)lane * 8u, off * 8u, 0);
       r.y = __hiloint2double((int)v.y, (int)v.x);
     } else {
-      r.y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(d.rs_y, (uint32_t)lane * 4u, soff * 4u, 0));
+      r.y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(d.rs_y, (uint32_t)lane * 4u, off * 4u, 0));
     }
-    r.code = __builtin_amdgcn_raw_buffer_load_b8(d.rs_c, (uint32_t)lane, soff, 0);
+    r.code = __builtin_amdgcn_raw_buffer_load_b8(d.rs_c, (uint32_t)lane, off, 0);
   } else {
-    r.v = load_yx<R>(d.rs, (uint32_t)lane * (uint32_t)sizeof(YX<R>), (uint32_t)row * (uint32_t)N * (uint32_t)sizeof(YX<R>));
+    r.v = load_yx<R>(d.rs, (uint32_t)lane * (uint32_t)sizeof(YX<R>), off);
   }
   return r;
+}
+// row `row` (relative to the descriptor's base)
+template <typename R, bool XC>
+__device__ __forceinline__ RowData<R, XC> row_load(const RowDesc<XC>& d, int lane, int row, int N) {
+  return row_load_at<R, XC>(d, lane, (uint32_t)row * row_stride<R, XC>(N));
 }
 template <typename R, bool XC>
 __device__ __forceinline__ double row_y(const RowData<R, XC>& r) {
@@ -484,7 +495,7 @@ __device__ __forceinline__ void dense_walk(const ARGS& a, const DenseChain& k, c
 
 // ---- the plane form of the walk (abd_planes.hpp) ----
 // The same arithmetic, operation for operation, with the exposure bookkeeping taken out of the vector unit: the lane masks
-// of the coming pair of gaps arrive by one scalar load (constant address space: loads only), the indicator e_i is one
+// of a gap of the coming pair arrive by one scalar load (constant address space: loads only), the indicator e_i is one
 // v_cndmask on the mask and the S boost e_i + e_v two (on m_i | m_v and m_i & m_v), and the bases c init + cf c perm are
 // loop-carried registers that are rewritten only in a gap that exposes a lane for the first time -- scalar mask arithmetic
 // and one branch per gap.  The refreshed base is fma(1.0, c perm, c init): the bits the legacy form's fma(cf, c perm, c init)
@@ -524,8 +535,9 @@ __device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChai
     acc[A_N_HC] = abd_hc_open(acc[A_N_HC], acc[A_N_H], before_n);
     acc[A_S_HC] = abd_hc_open(acc[A_S_HC], acc[A_S_H], before_s);
   }
-  const int last = g1 - 1 - g0;
-  auto ldrow = [&](const RowDesc<XC>& rs, int g) { return row_load<R, XC>(rs, lane, min(g - g0, last), N); };
+  // the row to refill a buffer from, two gaps ahead and never past the piece's last row: a running offset (abd_planes.hpp)
+  const uint32_t row_step = row_stride<R, XC>(N), row_last = (uint32_t)(g1 - 1 - g0) * row_step;
+  auto ldrow = [&](const RowDesc<XC>& rs, uint32_t off) { return row_load_at<R, XC>(rs, lane, off); };
 
   auto step = [&](uint64_t m_i, uint64_t m_v, const RowData<R, XC>& on, const RowData<R, XC>& os) {
     // first exposures of this gap (it already counts, abd.py:306): rare, wave-uniform
@@ -564,31 +576,41 @@ __device__ __forceinline__ void dense_walk_planes(const ARGS& a, const DenseChai
     }
   };
 
-  // rows as in the legacy form: one buffer for the even and one for the odd gaps per antigen, refilled two gaps ahead; the
-  // masks of a pair of gaps are fetched while the pair before it is walked
+  // rows as in the legacy form: one buffer for the even and one for the odd gaps per antigen, refilled two gaps ahead.  The
+  // masks likewise: one set of scalar registers for the even and one for the odd gap of a pair, each refilled for the next
+  // pair right behind the gap that used it (16 bytes per load, the next pair of the row: abd_plane_gaps pads it).  So a set is
+  // loaded into the registers it is read from and nothing is copied from pair to pair.  The loop's scalar side is kept short
+  // on purpose: with four waves on a SIMD a scalar instruction still takes its wave's issue turn (eight more of
+  // them per pair of gaps cost 1.1 %), so the row offset runs (one add, one min: abd_planes.hpp), the fetch pointer runs,
+  // and the loop counts pairs down.
   RowData<R, XC> en = pl.en, es = pl.es, on = pl.on, os = pl.os;
-  int g = g0;
-  abd_u64x4 cur = *(plane_pair_ptr)(prow + ((g0 + 1) & ~1));  // (the row is padded: abd_plane_gaps)
-  if (g & 1) {
-    const abd_u64x2 m = prow[g];
+  uint32_t off = min(2u * row_step, row_last);  // of row min(g - g0 + 2, last) for the gap g about to be walked
+  plane_gap_ptr fetch = prow + abd_plane_first_pair(g0);
+  abd_u64x2 me = fetch[0], mo = fetch[1];
+  int left = g1 - g0;  // gaps still to walk
+  if (g0 & 1) {
+    const abd_u64x2 m = prow[g0];
     step(m.x, m.y, on, os);
-    on = ldrow(rs_n, g + 2);
-    os = ldrow(rs_s, g + 2);
-    ++g;
+    on = ldrow(rs_n, off);
+    os = ldrow(rs_s, off);
+    off = abd_row_off_next(off, row_step, row_last);
+    --left;
   }
-  while (g + 1 < g1) {
-    const abd_u64x4 nxt = *(plane_pair_ptr)(prow + g + 2);
-    __builtin_amdgcn_sched_barrier(0);  // (the fetch stays up here: left free it sinks to the end of the pair and is waited for at once)
-    step(cur.x, cur.y, en, es);
-    en = ldrow(rs_n, g + 2);
-    es = ldrow(rs_s, g + 2);
-    step(cur.z, cur.w, on, os);
-    on = ldrow(rs_n, g + 3);
-    os = ldrow(rs_s, g + 3);
-    cur = nxt;
-    g += 2;
+  for (int pairs = left >> 1; pairs > 0; --pairs) {
+    __builtin_amdgcn_sched_barrier(0);  // (a pair is scheduled by itself)
+    step(me.x, me.y, en, es);
+    me = fetch[2];
+    en = ldrow(rs_n, off);
+    es = ldrow(rs_s, off);
+    off = abd_row_off_next(off, row_step, row_last);
+    step(mo.x, mo.y, on, os);
+    mo = fetch[3];
+    on = ldrow(rs_n, off);
+    os = ldrow(rs_s, off);
+    off = abd_row_off_next(off, row_step, row_last);
+    fetch += 2;
   }
-  if (g < g1) step(cur.x, cur.y, en, es);
+  if (left & 1) step(me.x, me.y, en, es);
   if constexpr (GRAD) {  // step 3: a lane exposed by the piece's end
     acc[A_N_HC] = abd_hc_close(acc[A_N_HC], acc[A_N_H], __builtin_amdgcn_inverse_ballot_w64(seen.n));
     acc[A_S_HC] = abd_hc_close(acc[A_S_HC], acc[A_S_H], __builtin_amdgcn_inverse_ballot_w64(seen.s));

@@ -5,17 +5,18 @@
 // individual has been exposed before (abd.py:306).  All of that is a function of the chain's discrete state alone, which
 // changes once per sweep and not once per evaluation, so it is kept TRANSPOSED beside `iw`: for every (lane group, gap) one
 // 64-bit lane mask of the constrained infections and one of the vaccinations (abd_types.hpp: PlaneGap).  A wave fetches the
-// masks of a pair of gaps with one wide scalar load and keeps "exposed so far" as two lane masks in scalar registers.
+// masks of a gap with one 16-byte scalar load, a pair of gaps ahead, and keeps "exposed so far" as two lane masks in scalar
+// registers.
 //
 // Here: the layout's index functions, the tile transpose as a reference loop (the device does it with ballots:
 // abd_small.hpp: abd_planes_kernel), the exposure bookkeeping of one gap and the steps that turn the running H sums into
-// the perm sums in plain C++ -- the same functions run in the kernel and in tests/native/planes_harness.cpp,
-// tests/native/hc_sum_harness.cpp.
+// the perm sums and the loop's scalar index steps in plain C++ -- the same functions run in the kernel and in
+// tests/native/planes_harness.cpp, hc_sum_harness.cpp, plane_fetch_harness.cpp.
 #pragma once
 
 #include "abd_types.hpp"
 
-// gaps per lane group in a plane: G rounded up to even (a pair of gaps is one aligned 32-byte load) plus one pair of zeros
+// gaps per lane group in a plane: G rounded up to even (a pair of gaps is 32 aligned bytes) plus one pair of zeros
 // (the loop fetches one pair ahead: the last fetch of a row reads gaps <= G + 1)
 __host__ __device__ inline int abd_plane_gaps(int G) { return ((G + 1) & ~1) + 2; }
 // 64-bit words of one slot's planes
@@ -24,6 +25,21 @@ __host__ __device__ inline size_t abd_plane_words(int n_lg, int G) { return (siz
 __host__ __device__ inline size_t abd_plane_index(int lg, int g, int G, int which) {
   return ((size_t)lg * (size_t)abd_plane_gaps(G) + (size_t)g) * 2 + (size_t)which;
 }
+
+// ---- the scalar bookkeeping of the plane form's gap loop (abd_dense.hpp: dense_walk_planes) ----
+// The loop walks a piece [g0, g1) of a row a pair of gaps at a time and refills its row buffers two gaps ahead, so near the
+// piece's end it asks for rows past the last one; those loads are aimed at the last row instead (they are never used).  The
+// offset of the row to load is kept running and clamped, one add and one min per row, instead of being worked out from the
+// gap index (add, min, multiply, shift): `off` is the offset of row min(r, last) in any unit, `step` one row in that unit,
+// `last_off` = last * step.  A clamped offset stays clamped: min(min(u, L) + s, L) = min(u + s, L) for s >= 0.
+__host__ __device__ inline uint32_t abd_row_off_next(uint32_t off, uint32_t step, uint32_t last_off) {
+  const uint32_t n = off + step;
+  return n < last_off ? n : last_off;
+}
+// The masks of a pair of gaps are fetched one pair ahead, from a pointer that advances by a pair: the first fetch of a piece is
+// the pair that holds its first even gap, and the last one reads the pair after the last pair it walks -- at most gaps G and
+// G + 1, inside the row's padding (abd_plane_gaps).
+__host__ __device__ inline int abd_plane_first_pair(int g0) { return (g0 + 1) & ~1; }
 
 // Reference transpose: words [nt][N] (word t of individual j: gaps 64 t .. 64 t + 63, as rw / iw / vw) -> the `which` masks
 // of planes [n_lg][abd_plane_gaps(G)] (everything else is left as it is).  Bit l of the mask of (lg, g) = bit g of
