@@ -37,7 +37,7 @@
 //   * e^u = 2^(t/1024), t = 1024 e + j + f: T[j] = 2^(j/1024) from a 1024-entry LDS table, a cubic in f,
 //     the exponent e added into T's high word -- the table is pre-biased (abd_types.hpp), so that is hi + (k << 10) of the
 //     clamped k, with no shift to separate e; 1 + 2^t is ONE fma (tools/exp2_table.py: 3.5e-16)
-//   * one v_rcp_f64 per cell for both antigens (1/A = B/(AB))
+//   * one v_rcp_f64 per cell for both antigens (1/A = B/(AB)); h' = q s (1 - s) takes 1 - s as e s (obs_pair_scaled)
 //   * gap rows are addressed as scalar row offset + a constant per-lane offset (no vector address arithmetic)
 #pragma once
 
@@ -170,7 +170,7 @@ __device__ __forceinline__ uint32_t word32(const uint32_t* base, uint32_t j2, in
 // takes one scalar operand, and left alone the compiler re-materialises that constant with a v_mov_b64 per evaluation.
 #define ABD_EXP2_C2 0x1.ebfbe033445b4p-23
 __device__ __forceinline__ void one_plus_exp2_pair(double t_n, double t_s, const double* tab /* LDS */, double c2v, double& A,
-                                                   double& B) {
+                                                   double& E_n, double& E_s) {
 #pragma clang fp contract(off)  // (the operations below are the ones issued: see obs_pair_scaled)
   const double kf_n = __builtin_rint(t_n), kf_s = __builtin_rint(t_s);
   const double f_n = t_n - kf_n, f_s = t_s - kf_s;
@@ -189,11 +189,13 @@ __device__ __forceinline__ void one_plus_exp2_pair(double t_n, double t_s, const
   const double Ts_n = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T_n), kc_n), __double2loint(T_n));  // T 2^e: v_lshl_add_u32
   const double Ts_s = __hiloint2double((int)abd_exp2_scaled_hi((uint32_t)__double2hiint(T_s), kc_s), __double2loint(T_s));
   A = fma(Ts_n, p_n, 1.0);
-  B = fma(Ts_s, p_s, 1.0);
+  E_n = Ts_n * p_n;  // 2^(t / 1024) itself: 1 - s = e s keeps the digits of e that 1 + e rounds away (obs_pair_scaled)
+  E_s = Ts_s * p_s;  // (B = 1 + e_s is never formed: the product and 1/A take e_s as it is)
 }
 
 // Both antigens of one cell at once: the two reciprocals 1/(1+e_n), 1/(1+e_s) come from ONE v_rcp_f64 (quarter
-// rate) of the product -- 1/A = B/(AB), 1/B = A/(AB).  t_n = 1024 log2(e) b_n (a_n - x_n), t_s likewise.
+// rate) of the product -- 1/A = B/(AB), 1/B = A/(AB).  t_n = 1024 log2(e) b_n (a_n - x_n), t_s likewise.  B = 1 + e_s is not
+// formed: A B = A e_s + A and r B = r e_s + r are one fma each, and e_n, e_s themselves are wanted for 1 - s = e s.
 // The arithmetic is pinned: contraction is off here, in one_plus_exp2_pair and in dense_walk, and every operation is written
 // as the instruction it is (an fma where the sum takes the unrounded product, a multiply or an add where it does not), so
 // that the bits of the 13 sums do not depend on how the compiler cuts the gap loop into blocks.
@@ -201,10 +203,10 @@ template <bool GRAD>
 __device__ __forceinline__ void obs_pair_scaled(double t_n, double yn, double d_n, double t_s, double ys, double d_s,
                                                 const double* tab, double c2v, double (&acc)[16], double& h_n, double& h_s) {
 #pragma clang fp contract(off)
-  double A, B;
-  one_plus_exp2_pair(t_n, t_s, tab, c2v, A, B);
-  const double r = rcp_newton(A * B);
-  const double s_n = r * B, s_s = r * A;  // logistic / d
+  double A, E_n, E_s;
+  one_plus_exp2_pair(t_n, t_s, tab, c2v, A, E_n, E_s);
+  const double r = rcp_newton(fma(A, E_s, A));           // 1 / (A B), B = 1 + e_s
+  const double s_n = fma(r, E_s, r), s_s = r * A;        // logistic / d: 1/A = r B, 1/B = r A
   const double q_n = fma(-d_n, s_n, yn), q_s = fma(-d_s, s_s, ys);
   acc[A_N_Q2] = fma(q_n, q_n, acc[A_N_Q2]);
   acc[A_S_Q2] = fma(q_s, q_s, acc[A_S_Q2]);
@@ -212,8 +214,10 @@ __device__ __forceinline__ void obs_pair_scaled(double t_n, double yn, double d_
     const double u_n = q_n * s_n, u_s = q_s * s_s;  // (rounded: h is built on it)
     acc[A_N_QS] = fma(s_n, q_n, acc[A_N_QS]);       // sum q s takes the unrounded product
     acc[A_S_QS] = fma(s_s, q_s, acc[A_S_QS]);
-    h_n = fma(-u_n, s_n, u_n);  // q s (1 - s)
-    h_s = fma(-u_s, s_s, u_s);
+    // q s (1 - s) with 1 - s = e s.  u - u s would take 1 - s from the rounded s: where a reading is saturated (s = 1 to the last
+    // bit) the shared reciprocal leaves s = 1 +- 20 u, and h' would be 20 u |q| of noise instead of q e
+    h_n = u_n * (E_n * s_n);
+    h_s = u_s * (E_s * s_s);
     acc[A_N_H] += h_n;  // plain adds
     acc[A_S_H] += h_s;
     acc[A_N_HX] = fma(h_n, t_n, acc[A_N_HX]);  // c_n sum h (a - x): the host divides by c_n (abd_context.hip: assemble)

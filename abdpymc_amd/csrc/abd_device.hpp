@@ -311,7 +311,7 @@ __device__ __forceinline__ void obs_term(double a, double x, double y, double b,
   if (GRAD) {
     const double u = q * s;
     sqs += u;
-    const double h = fma(-u, s, u);  // q s (1 - s)
+    const double h = u * (e * s);  // q s (1 - s) with 1 - s = e s: 1 - s from the rounded s loses the digits of e below u
     sh += h;
     shx = fma(h, amx, shx);
     h_out = h;

@@ -17,6 +17,11 @@ Pinning status
   (``pymc`` is an unpinned dependency, ``pyproject.toml:10``) and are cross-checked against
   ``scipy.stats`` and central finite differences in ``tests/test_oracle_logp.py``.
 
+* Away from typical parameter values ``logp_dlogp`` is checked against a 40-digit restatement (``tests/mp_reference.py``,
+  ``tests/test_tail_reference_cpu.py``): within 48 u S_k (S_k: the sum of the absolute values of output k's addends) wherever it
+  is finite.  It is NOT finite where ``exp(b (a - x))`` overflows (``e * s = inf * 0`` in ``lik``): some gradient entries are
+  NaN at b = +40 with perm = e^3 and at b = +300; logp is right there.
+
 Two forms are provided:
 
 * *faithful*: literal restatement of the dense ``(G, G, N)`` design used by the reference model
@@ -254,7 +259,10 @@ def constrain_infections(i_raw, pcrpos_gn, splits=None) -> np.ndarray:
 
 
 def _sigmoid(t):
-    return 1.0 / (1.0 + math.exp(-t))
+    try:
+        return 1.0 / (1.0 + math.exp(-t))
+    except OverflowError:  # t < -709.78: exp(-t) is beyond float64 and the quotient below its smallest subnormal
+        return 0.0
 
 
 def constrained(theta) -> dict:
@@ -503,7 +511,8 @@ def logp_dlogp(theta, i_raw, waner, cohort: Cohort, splits=None, ignore_pcrpos=F
     kg, ki = cohort.n.idx_gap, cohort.n.idx_ind
     grad[1] += float(np.sum(ga * cum_n[kg, ki])) * c["perm_n"]
     grad[2] += float(np.sum(ga * Un[kg, ki])) * c["temp_n"]
-    grad[3] += float(np.sum(ga * Dn[kg, ki])) * c["temp_n"] * c["rho_n"] * (1 - c["rho_n"])
+    # d rho / d logit = rho (1 - rho) with 1 - rho = sigmoid(-t): 1 - c["rho"] would cancel to nothing as rho approaches 1
+    grad[3] += float(np.sum(ga * Dn[kg, ki])) * c["temp_n"] * c["rho_n"] * _sigmoid(-t[3])
     grad[4] += float(np.sum(ga))
     grad[11] += gb
     grad[12] += gd
@@ -513,7 +522,7 @@ def logp_dlogp(theta, i_raw, waner, cohort: Cohort, splits=None, ignore_pcrpos=F
     lp += ll
     kg, ki = cohort.s.idx_gap, cohort.s.idx_ind
     grad[5] += float(np.sum(ga * cum_s[kg, ki])) * c["perm_s"]
-    grad[6] += float(np.sum(ga * Ds[kg, ki])) * c["rho_s"] * (1 - c["rho_s"])
+    grad[6] += float(np.sum(ga * Ds[kg, ki])) * c["rho_s"] * _sigmoid(-t[6])
     grad[10] += float(np.sum(ga))
     grad[14] += gb
     grad[15] += gd

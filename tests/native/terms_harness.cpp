@@ -3,8 +3,8 @@
 // fetched evaluation goes through (assemble_terms).
 #include "abd_terms.hpp"
 
-extern "C" int terms_compare(const double* theta, const double* sums, int G, double N, double Kn, double Ks, int dense,
-                             double* lp_serial, double* g_serial, double* lp_lanes, double* g_lanes) {
+static int compare(const double* theta, const double* sums, int G, double N, double Kn, double Ks, int dense, double prior_const,
+                   double* lp_serial, double* g_serial, double* lp_lanes, double* g_lanes) {
   using namespace abdi;
   ModelSizes m;
   m.G = G;
@@ -13,7 +13,7 @@ extern "C" int terms_compare(const double* theta, const double* sums, int G, dou
   m.cells = (double)G * N;
   m.Kn = Kn;
   m.Ks = Ks;
-  m.prior_const = 0.25;
+  m.prior_const = prior_const;
   const HostTerms h = prepare(theta);
   assemble_terms(m, h, theta, sums, lp_serial, g_serial, true);
   double lp = 0.0;
@@ -30,4 +30,16 @@ extern "C" int terms_compare(const double* theta, const double* sums, int G, dou
   }
   *lp_lanes = lp;
   return 0;
+}
+
+extern "C" int terms_compare(const double* theta, const double* sums, int G, double N, double Kn, double Ks, int dense,
+                             double* lp_serial, double* g_serial, double* lp_lanes, double* g_lanes) {
+  return compare(theta, sums, G, N, Kn, Ks, dense, 0.25, lp_serial, g_serial, lp_lanes, g_lanes);
+}
+
+// with the cohort's own constant (abd_context.hip: prior_constant), so that both forms return the model's logp
+// (tests/test_tail_reference_cpu.py: against the 40-digit reference)
+extern "C" int terms_compare_const(const double* theta, const double* sums, int G, double N, double Kn, double Ks, int dense,
+                                   double prior_const, double* lp_serial, double* g_serial, double* lp_lanes, double* g_lanes) {
+  return compare(theta, sums, G, N, Kn, Ks, dense, prior_const, lp_serial, g_serial, lp_lanes, g_lanes);
 }
