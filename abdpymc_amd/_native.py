@@ -119,6 +119,11 @@ def _risk_spec(spec) -> "_RiskSpec":
     return r
 
 
+# abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
+GIBBS_RECORD = np.dtype([("value", "<f8"), ("log_u", "<f8"), ("dim", "<i2"), ("gf", "<i2"), ("stop", "<i2"), ("path", "u1"),
+                         ("accepted", "u1")])
+GIBBS_PATHS = {"prior": 1, "early": 2, "walk": 3, "tail": 4, "wave_waner": 5, "wave_overflow": 6, "list": 7, "list_prior": 8}
+
 _P = C.c_void_p
 # array arguments (double*, int32_t*, int8_t*) are passed as plain addresses: building a typed ctypes pointer per argument
 # (ndarray.ctypes.data_as) costs 1.5-3 us each, which is a third of a synchronous call on a small cohort
@@ -135,6 +140,8 @@ SYMBOLS = {
     "abd_flip_discrete": (C.c_int, [_P, C.c_int32, C.c_int64]),
     "abd_get_discrete": (C.c_int, [_P, C.c_int32, _I8, _I8]),
     "abd_gibbs_sweep": (C.c_int, [_P, C.c_int32, _I32, _D, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "abd_gibbs_sweep_log": (C.c_int, [_P, C.c_int32, _I32, _D, C.c_uint64, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      _P, C.c_int64, _I32]),
     "abd_logp": (C.c_int, [_P, C.c_int32, _D, _D]),
     "abd_logp_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_loglik_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
@@ -410,8 +417,12 @@ class Context:
         _check(self._lib, self._lib.abd_get_discrete(self._h, chain, _ptr(i, C.c_int8), _ptr(w, C.c_int8)))
         return i, w
 
-    def gibbs_sweep(self, chains, theta, seed: int, sweep: int):
-        """One binary Gibbs-Metropolis sweep of each chain's [i_raw, ab_s_waner] in place -> (accepted, proposed)."""
+    def gibbs_sweep(self, chains, theta, seed: int, sweep: int, log: bool = False):
+        """One binary Gibbs-Metropolis sweep of each chain's [i_raw, ab_s_waner] in place -> (accepted, proposed).
+        ``log=True`` (tests; the same decisions from a logging instantiation of the kernel) -> (accepted, proposed, records,
+        n_records): ``records`` a GIBBS_RECORD array (chains, n_inds, n_gaps + 1) -- what the kernel decided each proposal
+        of an individual with, in the individual's order, ``abd_gibbs_record`` of include/abd_hip.h -- of which the first
+        ``n_records[chain, individual]`` are filled."""
         ch = _as(np.atleast_1d(chains), np.int32)
         t = _as(np.atleast_2d(theta), np.float64)
         if t.shape != (ch.size, N_THETA):
@@ -419,10 +430,16 @@ class Context:
         acc = np.zeros(ch.size, dtype=np.int64)
         prop = np.zeros(ch.size, dtype=np.int64)
         self._bump(ch)
-        _check(self._lib, self._lib.abd_gibbs_sweep(self._h, ch.size, _ptr(ch, C.c_int32), _ptr(t, C.c_double),
-                                                    C.c_uint64(seed & (2**64 - 1)), C.c_uint32(sweep & 0xFFFFFFFF),
-                                                    _tptr(acc, C.c_int64), _tptr(prop, C.c_int64)))
-        return acc, prop
+        head = (self._h, ch.size, _ptr(ch, C.c_int32), _ptr(t, C.c_double), C.c_uint64(seed & (2**64 - 1)),
+                C.c_uint32(sweep & 0xFFFFFFFF), _tptr(acc, C.c_int64), _tptr(prop, C.c_int64))
+        if not log:
+            _check(self._lib, self._lib.abd_gibbs_sweep(*head))
+            return acc, prop
+        rec = np.zeros((ch.size, self.n_inds, self.n_gaps + 1), dtype=GIBBS_RECORD)
+        n_rec = np.zeros((ch.size, self.n_inds), dtype=np.int32)
+        _check(self._lib, self._lib.abd_gibbs_sweep_log(*head, _out(rec, GIBBS_RECORD), self.n_inds * (self.n_gaps + 1),
+                                                        _out(n_rec, np.int32)))
+        return acc, prop, rec, n_rec
 
     # -- evaluations ------------------------------------------------------------------------
     def logp(self, chain: int, theta) -> float:

@@ -7,7 +7,8 @@
 namespace abdi {
 
 using GibbsKernel = void (*)(const GibbsArgs);
-// dense panels: lanes = proposals (abd_gibbs_dense.hpp; `stats`: the variant with the scheduler's development counters);
+// dense panels: lanes = proposals (abd_gibbs_dense.hpp; `stats`: the variant with the scheduler's development counters and the
+// decision log; for lists it selects the logging instantiation);
 // observation lists: lanes = observations (abd_gibbs_lists.hpp).  Both for 4 or 8 words per individual (<= 256 / <= 512 gaps);
 // lists of at most 64 gaps -- the reference's own cohorts have 26 and 31 -- get a one-word instantiation: it holds the
 // individual's packed rows in scalar registers, and with one word instead of four they fit (profiles/r04)
@@ -16,13 +17,15 @@ GibbsKernel gibbs_kernel(const abd_ctx* c, bool stats) {
   const bool wide = c->nt > ABD_MAXT;
   if (c->dense && stats) return wide ? abd_gibbs_dense_kernel<R, true, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, true, ABD_MAXT>;
   if (c->dense) return wide ? abd_gibbs_dense_kernel<R, false, ABD_MAXT_MAX> : abd_gibbs_dense_kernel<R, false, ABD_MAXT>;
+  if (stats && c->nt == 1) return abd_gibbs_kernel<R, 1, true>;
+  if (stats) return wide ? abd_gibbs_kernel<R, ABD_MAXT_MAX, true> : abd_gibbs_kernel<R, ABD_MAXT, true>;
   if (c->nt == 1) return abd_gibbs_kernel<R, 1>;
   return wide ? abd_gibbs_kernel<R, ABD_MAXT_MAX> : abd_gibbs_kernel<R, ABD_MAXT>;
 }
 
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
                          uint32_t stream_offset, hipStream_t st, unsigned long long* counts_dev, unsigned int* work_dev,
-                         unsigned long long* stats_dev) {
+                         unsigned long long* stats_dev, const GibbsLogDev& log) {
   GibbsArgs ga;
   base_args(c, ga.e);
   ga.e.n_chains = m;
@@ -47,6 +50,9 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
   ga.tail_lanes = c->g2_tail_lanes;
   ga.tail_age = c->g2_tail_age;
   ga.stats = stats_dev;
+  ga.log = log.rec;
+  ga.log_n = log.n;
+  ga.log_cap = log.cap;
   if (stats_dev) HIP_TRY(hipMemsetAsync(stats_dev, 0, 8 * sizeof(unsigned long long), st));
   dim3 grid, block(ABD_BLOCK);
   size_t lds;
@@ -66,7 +72,7 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
     grid = dim3(std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8)), m);
     lds = abd_gibbs_lds(c->G);
   }
-  const bool stats = stats_dev != nullptr;  // ABD_GIBBS_STATS=1
+  const bool stats = (c->dense && stats_dev != nullptr) || log.rec != nullptr;  // ABD_GIBBS_STATS=1, abd_gibbs_sweep_log
   const GibbsKernel k = c->storage == ABD_STORE_F32 ? gibbs_kernel<float>(c, stats) : gibbs_kernel<double>(c, stats);
   HIP_TRY(launch_kernel(k, grid, block, lds, st, ga));
   // the sweep rewrote iw (abd_gibbs.hpp: gibbs_store_state): the exposure planes of its chains follow on the same stream
@@ -75,10 +81,20 @@ int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta,
 
 }  // namespace abdi
 
-extern "C" {
+static_assert(sizeof(abd_gibbs_record) == sizeof(GibbsRecord) && offsetof(abd_gibbs_record, log_u) == offsetof(GibbsRecord, log_u) &&
+                  offsetof(abd_gibbs_record, dim) == offsetof(GibbsRecord, dim) && offsetof(abd_gibbs_record, gf) == offsetof(GibbsRecord, gf) &&
+                  offsetof(abd_gibbs_record, stop) == offsetof(GibbsRecord, stop) && offsetof(abd_gibbs_record, path) == offsetof(GibbsRecord, path) &&
+                  offsetof(abd_gibbs_record, accepted) == offsetof(GibbsRecord, accepted),
+              "header / kernel record layout mismatch");
+static_assert(ABD_GIBBS_PATH_PRIOR == ABD_GLOG_PRIOR && ABD_GIBBS_PATH_EARLY == ABD_GLOG_EARLY && ABD_GIBBS_PATH_WALK == ABD_GLOG_WALK &&
+                  ABD_GIBBS_PATH_TAIL == ABD_GLOG_TAIL && ABD_GIBBS_PATH_WAVE_WANER == ABD_GLOG_WAVE_WANER &&
+                  ABD_GIBBS_PATH_WAVE_OVERFLOW == ABD_GLOG_WAVE_OVERFLOW && ABD_GIBBS_PATH_LIST == ABD_GLOG_LIST &&
+                  ABD_GIBBS_PATH_LIST_PRIOR == ABD_GLOG_LIST_PRIOR,
+              "header / kernel path codes mismatch");
 
-int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
-                    int64_t* accepted, int64_t* proposed) {
+// the sweep of abd_gibbs_sweep; with `records`, logged (abd_gibbs_sweep_log)
+static int gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
+                       int64_t* accepted, int64_t* proposed, abd_gibbs_record* records, int64_t capacity, int32_t* n_records) {
   if (!c || !chains || !theta) return fail(ABD_ERR_ARG, "NULL argument");
   int rc = check_chains(c, n, chains);
   if (rc) return rc;
@@ -88,13 +104,34 @@ int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* 
   HIP_TRY(hipSetDevice(c->device));
   if (int frc = flush_ring(c)) return frc;
   std::vector<unsigned long long> counts((size_t)n * 2, 0);
+  // the log of one launch's chains: device memory of this call alone
+  DevBuf<GibbsRecord> d_rec;
+  DevBuf<int32_t> d_nrec;
+  const int m_max = std::min<int>(ABD_MAX_BATCH, n);
+  if (records) {
+    HIP_TRY(d_rec.alloc((size_t)m_max * (size_t)capacity));
+    HIP_TRY(d_nrec.alloc((size_t)m_max * c->N));
+  }
   static const bool want_stats = env_int("ABD_GIBBS_STATS", 0) != 0;
   for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
     const int m = std::min(ABD_MAX_BATCH, n - k0);
     unsigned long long* stats_dev = want_stats ? c->d_counts + (size_t)c->n_slots * 2 : nullptr;
+    GibbsLogDev log;
+    if (records) {
+      log.rec = d_rec;
+      log.n = d_nrec;
+      log.cap = capacity;
+      HIP_TRY(hipMemsetAsync(d_rec, 0, (size_t)m * (size_t)capacity * sizeof(GibbsRecord), c->stream));
+      HIP_TRY(hipMemsetAsync(d_nrec, 0, (size_t)m * c->N * sizeof(int32_t), c->stream));
+    }
     rc = enqueue_gibbs(c, m, chains + k0, theta + (size_t)k0 * ABD_N_THETA, seed, sweep, 0u, c->stream, c->d_counts,
-                       c->d_work, stats_dev);
+                       c->d_work, stats_dev, log);
     if (rc) return rc;
+    if (records) {
+      HIP_TRY(hipMemcpyAsync(records + (size_t)k0 * (size_t)capacity, d_rec, (size_t)m * (size_t)capacity * sizeof(GibbsRecord),
+                             hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(n_records + (size_t)k0 * c->N, d_nrec, (size_t)m * c->N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipMemcpyAsync(counts.data() + (size_t)k0 * 2, c->d_counts, (size_t)m * 2 * sizeof(unsigned long long),
                            hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -112,6 +149,22 @@ int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* 
     if (proposed) proposed[k] = (int64_t)counts[(size_t)k * 2 + 1];
   }
   return ABD_OK;
+}
+
+extern "C" {
+
+int abd_gibbs_sweep(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
+                    int64_t* accepted, int64_t* proposed) {
+  return gibbs_sweep(c, n, chains, theta, seed, sweep, accepted, proposed, nullptr, 0, nullptr);
+}
+
+int abd_gibbs_sweep_log(abd_ctx* c, int32_t n, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
+                        int64_t* accepted, int64_t* proposed, abd_gibbs_record* records, int64_t capacity, int32_t* n_records) {
+  if (!c || !records || !n_records) return fail(ABD_ERR_ARG, "NULL argument");
+  if (capacity < (int64_t)c->N * (c->G + 1))
+    return fail(ABD_ERR_ARG, "capacity %lld: a chain's log takes n_inds * (n_gaps + 1) = %lld records", (long long)capacity,
+                (long long)c->N * (c->G + 1));
+  return gibbs_sweep(c, n, chains, theta, seed, sweep, accepted, proposed, records, capacity, n_records);
 }
 
 }  // extern "C"

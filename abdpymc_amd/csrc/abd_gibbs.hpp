@@ -63,6 +63,28 @@ __device__ __forceinline__ double gibbs_prior_delta(bool one, double logodds) { 
 // metrop_select: keep the flip if delta > 0 or delta > log(u)
 __device__ __forceinline__ bool gibbs_accept(double delta, double log_u) { return delta > 0.0 || delta > log_u; }
 
+// ---- the decision log (abd_gibbs_sweep_log; the logging instantiations only) ----
+// the records of individual j of the launch's chain c: one per position in the individual's order, G + 1 at most
+__device__ __forceinline__ GibbsRecord* gibbs_log_rows(const GibbsArgs& ga, int c, int j) {
+  return ga.log ? ga.log + (int64_t)c * ga.log_cap + (int64_t)j * (ga.e.G + 1) : nullptr;
+}
+// the record of position pos, in two halves: how the proposal is evaluated, and what came out.  A lane-owned evaluation
+// writes both at once; a whole-wave one gets the first from the lane that classified it, the second from lane 0 at the frontier.
+// An evaluation redone after an acceptance overwrites its position.
+__device__ __forceinline__ void gibbs_log_how(GibbsRecord* rows, int pos, int dim, int path, int gf, int stop) {
+  if (!rows) return;
+  rows[pos].dim = (int16_t)dim;
+  rows[pos].gf = (int16_t)gf;
+  rows[pos].stop = (int16_t)stop;
+  rows[pos].path = (uint8_t)path;
+}
+__device__ __forceinline__ void gibbs_log_outcome(GibbsRecord* rows, int pos, double value, double log_u, bool accepted) {
+  if (!rows) return;
+  rows[pos].value = value;
+  rows[pos].log_u = log_u;
+  rows[pos].accepted = accepted ? 1 : 0;
+}
+
 // ---- an individual's state in its chain's slot ----
 struct GibbsSlot {
   uint64_t* rw;   // [nt][N] raw bits, updated in place

@@ -296,7 +296,8 @@ __device__ __forceinline__ int g2_append_positions(uint64_t m, int t, int lane, 
   return n;
 }
 
-// STATS: the development counters of ABD_GIBBS_STATS=1 (seven wave-uniform 64-bit counters)
+// STATS: the development counters of ABD_GIBBS_STATS=1 (seven wave-uniform 64-bit counters), and the decision log of
+// abd_gibbs_sweep_log (ga.log: one GibbsRecord per committed proposal, abd_types.hpp).  The shipped sweep is STATS = false.
 template <typename R, bool STATS, int MT>
 __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G2_MAX_WAVES), MT > ABD_MAXT ? 2 : 3) void abd_gibbs_dense_kernel(const GibbsArgs ga) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -462,6 +463,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
       }
     }
     for (int e = lane; e <= G; e += 64) result[e] = ABD_G2_PENDING;
+    GibbsRecord* const lrec = STATS ? gibbs_log_rows(ga, c, j) : nullptr;
 
     // ---- the current state: constrained infections, position lists, chunk facts, terms, suffix sums ----
     double total_cur = 0.0;
@@ -583,6 +585,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
           lu = log_uniform_u32(accw[d], tab_e2);  // log of the acceptance uniform, ~18 instructions
           if (d == G) {
             result[pidx] = ABD_G2_COMPLEX;  // ab_s_waner: evaluated by the whole wave at the frontier
+            if (STATS) gibbs_log_how(lrec, pidx, d, ABD_GLOG_WAVE_WANER, 0, G);
           } else {
             // how the flip of raw bit d changes i0 (abd.py:643-647 / 818 + 771): one position leaves (a_rm), one enters (b_add)
             const bool was_one = ((row_r[d >> 6] >> (d & 63)) & 1ull) != 0;
@@ -662,9 +665,15 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
             }
             if (gf >= ABD_G2_NONE) {
               // the constrained infections do not change: the prior term decides
-              result[pidx] = gibbs_accept(delta0, lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+              const bool acc = gibbs_accept(delta0, lu);
+              result[pidx] = acc ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+              if (STATS) {
+                gibbs_log_how(lrec, pidx, d, ABD_GLOG_PRIOR, -1, -1);
+                gibbs_log_outcome(lrec, pidx, delta0, lu, acc);
+              }
             } else if (overflow) {
               result[pidx] = ABD_G2_COMPLEX;  // more new infections than a lane holds: the whole wave evaluates it at the frontier
+              if (STATS) gibbs_log_how(lrec, pidx, d, ABD_GLOG_WAVE_OVERFLOW, gf, G);
             } else {
               B0 = delta0 + suf[gf];  // everything the current state holds from gf on is given up
               thr = lu - 1e-9 * (fabs(B0) + 1.0);
@@ -729,7 +738,12 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
         const bool dead = fma(S, 1.0 - 1e-9, B0) < thr;
         if (dead || g >= G) {
           const double delta = B0 + S;
-          result[pidx] = (!dead && gibbs_accept(delta, lu)) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          const bool acc = !dead && gibbs_accept(delta, lu);
+          result[pidx] = acc ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          if (STATS) {  // (an early stop compared the bound B0 + S, not delta; at the last gap the bound IS delta)
+            gibbs_log_how(lrec, pidx, plist[pidx], g < G ? ABD_GLOG_EARLY : ABD_GLOG_WALK, g_first, g);
+            gibbs_log_outcome(lrec, pidx, delta, lu, acc);
+          }
           active = false;
           finished = true;
         }
@@ -762,7 +776,12 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
         const double rest = wave_sum_uniform(tsum);
         if (lane == Lw) {
           const double delta = B0 + (S + rest);
-          result[pidx] = gibbs_accept(delta, lu) ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          const bool acc = gibbs_accept(delta, lu);
+          result[pidx] = acc ? ABD_G2_ACCEPT : ABD_G2_REJECT;
+          if (STATS) {
+            gibbs_log_how(lrec, pidx, plist[pidx], ABD_GLOG_TAIL, g_first, G);
+            gibbs_log_outcome(lrec, pidx, delta, lu, acc);
+          }
           active = false;
         }
         dirty = true;
@@ -826,6 +845,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
           const double delta = delta_prior + (wave_sum_uniform(tsum) - total_cur);
           const double log_u = readfirstlane_f64(log_uniform_u32(accw[d], tab_e2));
           accepted = gibbs_accept(delta, log_u);
+          if (STATS && lane == 0) gibbs_log_outcome(lrec, frontier, delta, log_u, accepted);
           if (accepted && d == G) wj = wn;
         }
         if (accepted && d < G && lane == 0) row_r[d >> 6] ^= 1ull << (d & 63);
@@ -842,6 +862,7 @@ __global__ __launch_bounds__(64 * (MT > ABD_MAXT ? ABD_G2_MAX_WAVES_WIDE : ABD_G
       }
     }
     n_prop_total += (unsigned int)frontier;
+    if (STATS && ga.log_n && lane == 0) ga.log_n[(int64_t)c * N + j] = frontier;
 
     // ---- write the individual's state back ----
     int pc1;

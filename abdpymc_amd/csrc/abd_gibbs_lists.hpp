@@ -123,7 +123,8 @@ __device__ __forceinline__ uint64_t gibbs_lane_word(const uint64_t (&w)[MT], int
   return v;
 }
 
-template <typename R, int MT>
+// LOG: the decision log of abd_gibbs_sweep_log (ga.log: one GibbsRecord per proposal, abd_types.hpp).  The shipped sweep is LOG = false.
+template <typename R, int MT, bool LOG = false>
 __global__ __launch_bounds__(ABD_BLOCK) void abd_gibbs_kernel(const GibbsArgs ga) {
   extern __shared__ __align__(16) unsigned char smem[];  // abd_gibbs_lds(G)
   const EvalArgs& a = ga.e;
@@ -189,6 +190,8 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_gibbs_kernel(const GibbsArgs ga
     double cur = sparse_terms<R, MT>(a, p, j, lane, I, V, tabs, wj ? tabs + tstride : tab_ones, is2_n, is2_s, first, n_obs);
 
     // ---- the sweep ----
+    GibbsRecord* const lrec = LOG ? gibbs_log_rows(ga, c, j) : nullptr;
+    int n_rec = 0;
     for (int k = 0; k < n_dims; ++k) {
       const int d = __builtin_amdgcn_readfirstlane((int)order[k]);
       if (!__builtin_amdgcn_readfirstlane((int)transit[d])) continue;  // same value proposed: nothing to do
@@ -224,7 +227,16 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_gibbs_kernel(const GibbsArgs ga
         nxt = sparse_terms<R, MT>(a, p, j, lane, In, V, tabs, wn ? tabs + tstride : tab_ones, is2_n, is2_s, first, n_obs);
         delta += wave_sum_uniform(nxt - cur);
       }
-      if (gibbs_accept(delta, readfirstlane_f64(logu[d]))) {
+      const double log_u = readfirstlane_f64(logu[d]);
+      const bool accepted = gibbs_accept(delta, log_u);
+      if (LOG) {
+        if (lane == 0) {
+          gibbs_log_how(lrec, n_rec, d, changed ? ABD_GLOG_LIST : ABD_GLOG_LIST_PRIOR, -1, -1);
+          gibbs_log_outcome(lrec, n_rec, delta, log_u, accepted);
+        }
+        ++n_rec;
+      }
+      if (accepted) {
 #pragma unroll
         for (int t = 0; t < MT; ++t) {
           if (t == (d >> 6)) Rw[t] ^= bit;
@@ -238,6 +250,7 @@ __global__ __launch_bounds__(ABD_BLOCK) void abd_gibbs_kernel(const GibbsArgs ga
 
     gibbs_store_state(slot, N, j, nt, lane, gibbs_lane_word<MT>(Rw, lane), gibbs_lane_word<MT>(I, lane), wj, pc0,
                       gibbs_state_counts<MT>(Rw, wj), d_n1, d_m1);
+    if (LOG && ga.log_n && lane == 0) ga.log_n[(int64_t)c * N + j] = n_rec;
   }
   gibbs_finish(ga, p, c, lane0, d_n1, d_m1, n_acc, n_prop);
 }

@@ -376,8 +376,15 @@ void scatter_readings(const abd_ctx* c, const ReadingOut (&out)[R], At at) {
 }
 
 // ---- abd_gibbs.hip
+// the decision log of the launch's m chains in device memory, zeroed by the caller (abd_gibbs_sweep_log): rec [m][cap], n [m][N];
+// with one, the sweep runs its logging instantiation
+struct GibbsLogDev {
+  GibbsRecord* rec = nullptr;
+  int32_t* n = nullptr;
+  int64_t cap = 0;
+};
 int enqueue_gibbs(abd_ctx* c, int m, const int32_t* chains, const double* theta, uint64_t seed, uint32_t sweep,
                   uint32_t stream_offset, hipStream_t st, unsigned long long* counts_dev, unsigned int* work_dev,
-                  unsigned long long* stats_dev);
+                  unsigned long long* stats_dev, const GibbsLogDev& log = GibbsLogDev());
 
 }  // namespace abdi

@@ -327,6 +327,27 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
 #define ABD_TRANSIT_P_U32 3435973836u  // floor(0.8 * 2^32): propose iff word 1 < this   (transit_p = 0.8)
 #endif
 
+// One committed proposal of a logged sweep (abd_gibbs_sweep_log; layout of abd_gibbs_record, include/abd_hip.h): what the kernel
+// decided with.  Written with ordinary stores by the lane that owns the result (lane 0 on the whole-wave paths).
+#define ABD_GLOG_PRIOR 1         // dense: the constrained infections do not change, the prior alone decides
+#define ABD_GLOG_EARLY 2         // dense: a lane's walk stopped before the last gap; value = the BOUND B0 + S at the stop, not delta
+#define ABD_GLOG_WALK 3          // dense: a lane's walk to the last gap (accepted or rejected there: the bound is delta)
+#define ABD_GLOG_TAIL 4          // dense: a lane's walk finished by the whole wave
+#define ABD_GLOG_WAVE_WANER 5    // dense: whole-wave evaluation at the frontier, the ab_s_waner flip
+#define ABD_GLOG_WAVE_OVERFLOW 6 // dense: ... an i_raw flip with more new kept infections than a lane holds
+#define ABD_GLOG_LIST 7          // lists: the constrained state changed, every observation re-evaluated
+#define ABD_GLOG_LIST_PRIOR 8    // lists: it did not, the prior alone decides
+struct GibbsRecord {
+  double value;  // what was compared with log u
+  double log_u;
+  int16_t dim;   // 0 .. G-1: i_raw[dim, j]; G: ab_s_waner[j]
+  int16_t gf;    // first gap whose constrained infection changes (0 for the ab_s_waner flip); -1: none / not worked out
+  int16_t stop;  // the evaluation covered gaps [gf, stop)
+  uint8_t path;  // ABD_GLOG_*
+  uint8_t accepted;
+};
+static_assert(sizeof(GibbsRecord) == 24, "GibbsRecord is abd_gibbs_record: 24 bytes");
+
 struct GibbsArgs {
   EvalArgs e;  // panels, packed words, chain parameters (ch[k].rw / waner are updated IN PLACE)
   uint32_t seed_lo, seed_hi, sweep;
@@ -340,6 +361,10 @@ struct GibbsArgs {
   unsigned int* work;              // [n_chains]: next individual of each chain (abd_gibbs_dense_kernel's work queue), zeroed per launch
   unsigned long long* stats;       // nullptr, or 8 development counters of abd_gibbs_dense_kernel (ABD_GIBBS_STATS=1)
   int32_t refill_min, tail_lanes, tail_age;  // scheduler knobs of abd_gibbs_dense_kernel (abd_gibbs_dense.hpp)
+  // the decision log (abd_gibbs_sweep_log; nullptr: none.  Only the logging instantiations read these)
+  GibbsRecord* log;         // [n_chains][log_cap], zeroed: the record of position k of individual j at j * (G + 1) + k
+  int32_t* log_n;           // [n_chains][N]: records of each individual
+  int64_t log_cap;          // records per chain, >= N * (G + 1)
 };
 
 

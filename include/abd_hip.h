@@ -113,6 +113,43 @@ int abd_get_discrete(abd_ctx* ctx, int32_t chain, int8_t* i_raw, int8_t* waner);
 int abd_gibbs_sweep(abd_ctx* ctx, int32_t n, const int32_t* chains, const double* theta, uint64_t seed,
                     uint32_t sweep, int64_t* accepted, int64_t* proposed);
 
+/* The same sweep with a decision log, for tests: one record per proposal, in the individual's order, holding what the kernel
+ * decided with.  It leaves the slot in exactly the state abd_gibbs_sweep does (same decisions, bit for bit) but runs a
+ * logging instantiation of the kernel, so it is not the call to time.
+ *   value     what was compared with log u: the log-ratio delta -- except on ABD_GIBBS_PATH_EARLY, where the walk over the gaps
+ *             stopped at `stop` because the BOUND  prior - (current terms of gaps >= gf) + (new terms of gaps [gf, stop))
+ *             had fallen below log u: value is that bound, and delta <= value
+ *   log_u     the log of the acceptance uniform as the kernel computed it
+ *   dim       0 .. G-1: i_raw[dim, individual]; G: ab_s_waner[individual]
+ *   gf        dense panels: the first gap whose constrained infection the flip changes (0 for the ab_s_waner flip); -1: none
+ *   stop      dense panels: the evaluation covered gaps [gf, stop); -1 where there was none
+ *   path      ABD_GIBBS_PATH_*
+ *   accepted  0 / 1
+ * records: n x capacity, capacity >= n_inds * (n_gaps + 1) records per chain; the records of individual j of chain k start at
+ * records[k * capacity + j * (n_gaps + 1)] and n_records[k * n_inds + j] of them are written (the rest is zero). */
+enum {
+  ABD_GIBBS_PATH_PRIOR = 1,          /* dense: the constrained infections do not change, the prior alone decides      */
+  ABD_GIBBS_PATH_EARLY = 2,          /* dense: a lane's walk, stopped before the last gap (value is the bound)       */
+  ABD_GIBBS_PATH_WALK = 3,           /* dense: a lane's walk to the last gap                                          */
+  ABD_GIBBS_PATH_TAIL = 4,           /* dense: a lane's walk finished by the whole wave                               */
+  ABD_GIBBS_PATH_WAVE_WANER = 5,     /* dense: whole-wave evaluation, the ab_s_waner flip                             */
+  ABD_GIBBS_PATH_WAVE_OVERFLOW = 6,  /* dense: whole-wave evaluation, more new infections than a lane holds           */
+  ABD_GIBBS_PATH_LIST = 7,           /* observation lists: the constrained state changed                              */
+  ABD_GIBBS_PATH_LIST_PRIOR = 8      /* observation lists: it did not, the prior alone decides                        */
+};
+typedef struct {
+  double value;
+  double log_u;
+  int16_t dim;
+  int16_t gf;
+  int16_t stop;
+  uint8_t path;
+  uint8_t accepted;
+} abd_gibbs_record;
+int abd_gibbs_sweep_log(abd_ctx* ctx, int32_t n, const int32_t* chains, const double* theta, uint64_t seed,
+                        uint32_t sweep, int64_t* accepted, int64_t* proposed, abd_gibbs_record* records, int64_t capacity,
+                        int32_t* n_records);
+
 /* Scalar joint logp at (theta, resident discrete state of `chain`).  Replaces Model.compile_logp()'s
  * point function (a17). */
 int abd_logp(abd_ctx* ctx, int32_t chain, const double* theta, double* logp);

@@ -13,7 +13,12 @@ S); ``b == 0`` is the limit ``s = 1/2``.
 
 ``tests/golden/make_tail_fixtures.py`` evaluates the case table below with it and commits the results rounded to float64
 (``tests/golden/tail_parity.npz``); the GPU tests read that file and need no mpmath.
+
+The binary Gibbs-Metropolis sweep is restated here too (``sweep``: Philox in Python, the order and rule of ``abd_gibbs.hpp``, per-gap
+likelihood terms at 40 digits): ``tests/golden/make_sweep_fixtures.py`` runs it over the same table and commits per proposal what a
+kernel decides with (``tests/golden/sweep_decisions.npz``, read through ``SweepSet``).
 """
+import functools
 import math
 
 import numpy as np
@@ -266,6 +271,146 @@ def deterministics(theta, i_raw, waner, cohort, splits=None, ignore_pcrpos=False
 
 
 # --------------------------------------------------------------------------------------------------------------------------
+# The binary Gibbs-Metropolis sweep (abdpymc_amd/csrc/abd_gibbs.hpp) at 40 digits: same random stream, same order, and per
+# proposal what a kernel decides with
+# --------------------------------------------------------------------------------------------------------------------------
+
+GIBBS_TRANSIT_U32 = 3435973836  # floor(0.8 * 2^32): a dim is proposed iff word 1 of its draw is below
+LOG_U_TOL = 8e-15  # |log u| <= 32 log 2 + log 2 = 22.9: 2 ulp there (3.55e-15 each), rounded up
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    m = 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & m, p1 & m, ((p0 >> 32) ^ c3 ^ k1) & m, p0 & m
+        k0, k1 = (k0 + 0x9E3779B9) & m, (k1 + 0xBB67AE85) & m
+    return c0, c1, c2, c3
+
+
+def gibbs_order(G, j, chain, seed, sweep):
+    """[(dim, acceptance word)] of individual j's PROPOSED dims in the sweep's order (dim G: ab_s_waner)"""
+    k0 = (seed & 0xFFFFFFFF) ^ ((sweep * 0x9E3779B9) & 0xFFFFFFFF)
+    k1 = (seed >> 32) & 0xFFFFFFFF
+    r = [philox4x32_10(d, j, chain, 0, k0, k1) for d in range(G + 1)]
+    return [(d, r[d][2]) for d in sorted(range(G + 1), key=lambda d: (r[d][0] & ~0x1FF) | d) if r[d][1] < GIBBS_TRANSIT_U32]
+
+
+class _SweepTerms:
+    """Per gap of one individual: both antigens' likelihood terms -1/2 (q / sigma)^2 that depend on the discrete state"""
+
+    def __init__(self, mp, theta, obs_n, obs_s, vac, G):
+        t = _theta_mp(mp, theta)
+        sig = lambda z: 1 / (1 + mp.exp(-z))  # noqa: E731
+        self.mp, self.G, self.vac = mp, G, [int(v) for v in vac]
+        self.perm_n, self.temp_n, self.rho_n, self.init_n = mp.exp(t[1]), mp.exp(t[2]), sig(t[3]), t[4]
+        self.perm_s, self.rho_s, self.init_s = mp.exp(t[5]), sig(t[6]), t[10]
+        self.n = (t[11], t[12], 2 * mp.exp(2 * t[13]), obs_n)
+        self.s = (t[14], t[15], 2 * mp.exp(2 * t[16]), obs_s)
+
+    def _gap(self, par, g, a):
+        b, d, two_s2, obs = par
+        acc = self.mp.mpf(0)
+        for x, y in obs.get(g, ()):
+            q = y - d / (1 + self.mp.exp(b * (a - x)))
+            acc -= q * q / two_s2
+        return acc
+
+    def run(self, inf, waner, g0=0, carry=None):
+        """terms and scan states of gaps g0 .. G-1; carry: the state (tn, ts, ci, civ) after gap g0 - 1"""
+        F = self.mp.mpf
+        tn, ts, ci, civ = carry if carry is not None else (F(0), F(0), 0, 0)
+        rj = self.rho_s if waner else F(1)
+        terms, states = [], []
+        for g in range(g0, self.G):
+            e_i, e_v = int(inf[g]), self.vac[g]
+            tn = tn * self.rho_n + e_i
+            ts = ts * rj + e_i + e_v
+            ci += e_i
+            civ += e_i + e_v
+            a_n = (self.perm_n if ci else 0) + self.temp_n * tn + self.init_n
+            a_s = (self.perm_s if civ else 0) + ts + self.init_s
+            terms.append(self._gap(self.n, g, a_n) + self._gap(self.s, g, a_s))
+            states.append((tn, ts, ci, civ))
+        return terms, states
+
+
+def sweep(theta, i_raw, waner, cohort, splits=None, ignore_pcrpos=False, chain=0, seed=0, sweep=0, per_gap=False, individuals=None):
+    """One sweep of chain slot `chain` -> (i_raw, waner, accepted, proposed, records).  records: one dict per proposal, individual by
+    individual in the sweep's order, floats rounded to float64:
+      ind, dim, accepted;
+      gf         the first gap whose constrained infection differs (0 for the ab_s_waner flip, -1 if none does);
+      delta      the log-ratio; log_u: the log of the acceptance uniform (w + 1/2) / 2^32; the rule is delta > log_u (log_u < 0);
+      S_changed  |prior| + sum over g >= gf of |current term| + |new term|: the addends the dense kernel forms delta from;
+      S_full     the same over all gaps (= |prior| if nothing changes): the list kernel's and the C restatement's addends;
+      cur_tail   the sum of the current terms of gaps >= gf;
+      new, crossed (per_gap): the new terms of gaps gf, gf + 1, ... up to two gaps past the first one -- index `crossed` of `new`,
+                 -1 if there is none -- at which the bound prior - cur_tail + (new terms so far) lies below log_u
+    individuals: only these (default all); the others keep their state."""
+    mp = _mp()
+    F = mp.mpf
+    i_raw, waner = np.array(i_raw, dtype=np.int8), np.array(waner, dtype=np.int8)
+    G, N = cohort.n_gaps, cohort.n_inds
+    pcr = np.zeros((G, N)) if ignore_pcrpos else np.asarray(cohort.pcrpos, dtype=float).T
+    vacs = np.asarray(cohort.vacs)
+    by_ind = []
+    for obs in (cohort.n, cohort.s):
+        d = {}
+        for g, i, x, y in zip(np.asarray(obs.idx_gap), np.asarray(obs.idx_ind), np.asarray(obs.log_dilution, float), np.asarray(obs.od, float)):
+            d.setdefault(int(i), {}).setdefault(int(g), []).append((F(float(x)), F(float(y))))
+        by_ind.append(d)
+    th0, th7 = F(float(theta[0])), F(float(theta[7]))
+    records, accepted, proposed = [], 0, 0
+    for j in range(N) if individuals is None else individuals:
+        T = _SweepTerms(mp, theta, by_ind[0].get(j, {}), by_ind[1].get(j, {}), vacs[j], G)
+        con = lambda r: O.constrain_infections(r[:, None], pcr[:, j:j + 1], splits)[:, 0].astype(np.int64)  # noqa: E731
+        raw, w = i_raw[:, j].copy(), int(waner[j])
+        inf = con(raw)
+        cur, states = T.run(inf, w)
+        for d, word in gibbs_order(G, j, chain, seed, sweep):
+            proposed += 1
+            raw_n, w_n, inf_n, gf = raw, w, inf, -1
+            if d < G:
+                prior = -th0 if raw[d] else th0
+                raw_n = raw.copy()
+                raw_n[d] ^= 1
+                inf_n = con(raw_n)
+                if not np.array_equal(inf, inf_n):
+                    gf = int(np.argmax(inf != inf_n))
+            else:
+                w_n, gf = 1 - w, 0
+                prior = th7 if w_n else -th7
+            delta, S_changed, S_full, cur_tail, new, new_states = prior, abs(prior), abs(prior), F(0), [], []
+            if gf >= 0:
+                new, new_states = T.run(inf_n, w_n, gf, states[gf - 1] if gf > 0 else None)
+                cur_tail = sum(cur[gf:], F(0))
+                delta = prior + (sum(new, F(0)) - cur_tail)
+                S_changed += sum((abs(v) for v in cur[gf:]), F(0)) + sum((abs(v) for v in new), F(0))
+                S_full = S_changed + 2 * sum((abs(v) for v in cur[:gf]), F(0))
+            log_u = mp.log((F(word) + F(1) / 2) / F(2) ** 32)
+            acc = bool(delta > log_u)
+            rec = dict(ind=j, dim=d, gf=gf, accepted=acc, delta=float(delta), log_u=float(log_u), S_changed=float(S_changed),
+                       S_full=float(S_full), cur_tail=float(cur_tail))
+            if per_gap:
+                bound, crossed = prior - cur_tail, -1
+                for k, v in enumerate(new):
+                    bound += v
+                    if bound < log_u:
+                        crossed = k
+                        break
+                rec["crossed"] = crossed
+                rec["new"] = np.array([float(v) for v in (new if crossed < 0 else new[:crossed + 3])])
+            records.append(rec)
+            if acc:
+                accepted += 1
+                raw, w, inf = raw_n, w_n, inf_n
+                if gf >= 0:
+                    cur, states = cur[:gf] + new, states[:gf] + new_states
+        i_raw[:, j], waner[j] = raw, w
+    return i_raw, waner, accepted, proposed, records
+
+
+# --------------------------------------------------------------------------------------------------------------------------
 # The case table (shared by the generator and by every test, which rebuild the inputs and check them against the checksums)
 # --------------------------------------------------------------------------------------------------------------------------
 
@@ -380,7 +525,89 @@ def set_cases(name):
     return out
 
 
-def load_fixture(golden_dir):
+def load_fixture(golden_dir, name=FIXTURE):
     import os
 
-    return dict(np.load(os.path.join(golden_dir, FIXTURE)))
+    return dict(np.load(os.path.join(golden_dir, name)))
+
+
+# The sets of the sweep fixture (tests/golden/make_sweep_fixtures.py -> sweep_decisions.npz): sets of SETS by name -- 20x13 again with
+# one split, two splits and without PCR+, two of the five cases each -- and one wide set for the sweep kernels' 8-word instantiations.
+# per_gap: the per-gap new terms are stored (what an early stop's bound is made of); float_inds: the individuals whose proposals'
+# numbers are stored (None: all; every individual's decisions, first changed gaps and end state are).  Case k of a set runs in chain slot k.
+SWEEP_FIXTURE = "sweep_decisions.npz"
+PER_GAP_CROSSED = 14  # per-gap terms are stored for the rows whose bound crosses log u within this many gaps of the first changed one
+_SWEEP_DEFAULT = dict(splits=None, ignore_pcrpos=False, f32=False, per_gap=False, sweeps=2, seed=2024, float_inds=None, only=None)
+_TWO = ("b=+40 perm=e^2.5", "rho -800/-800")
+SWEEP_SETS = {
+    "65x33": dict(_SWEEP_DEFAULT, of="65x33", f32=True, float_inds=(0, 1, 2, 64)),
+    "7x65": dict(_SWEEP_DEFAULT, of="7x65", per_gap=True),
+    "20x13": dict(_SWEEP_DEFAULT, of="20x13", per_gap=True),
+    "20x13 one split": dict(_SWEEP_DEFAULT, of="20x13", splits=(5,), per_gap=True, only=_TWO),
+    "20x13 two splits": dict(_SWEEP_DEFAULT, of="20x13", splits=(4, 9), per_gap=True, only=_TWO),
+    "20x13 no pcrpos": dict(_SWEEP_DEFAULT, of="20x13", ignore_pcrpos=True, per_gap=True, only=_TWO),
+    "sparse": dict(_SWEEP_DEFAULT, of="sparse"),
+    "4x257": dict(_SWEEP_DEFAULT, of=None, per_gap=True, sweeps=1),
+}
+
+
+class SweepSet:
+    """One set and storage of the sweep fixture: the rows of a case's sweep, individual by individual in the sweep's order"""
+
+    def __init__(self, fx, name, st="f64"):
+        self.name, self.st, self.spec, self.fx, self.k = name, st, SWEEP_SETS[name], fx, f"{name}.{st}."
+        self.n = self.get("n")  # (cases, sweeps, N)
+        self.G = self.get("i_raw").shape[2]
+        self.first = np.concatenate([[0], np.cumsum(self.n.sum(axis=2).reshape(-1))])  # by case * sweeps + sweep
+        # which rows carry numbers, and where: row r's numbers are at at[r] of d, S and crossed
+        keep = np.ones(self.n.shape[2], dtype=bool)
+        if self.spec["float_inds"] is not None:
+            keep[:] = False
+            keep[list(self.spec["float_inds"])] = True
+        self.has = np.repeat(np.broadcast_to(keep, self.n.shape).reshape(-1), self.n.reshape(-1))
+        self.at = np.cumsum(self.has) - 1
+        assert int(self.has.sum()) == len(self.get("d")) == len(self.get("S")) and len(self.has) == len(self.get("gf"))
+        if self.spec["per_gap"]:
+            cr, gf = self.get("crossed").astype(np.int64), self.get("gf")[self.has].astype(np.int64)
+            self.new_first = np.concatenate([[0], np.cumsum(np.where((cr >= 0) & (cr < PER_GAP_CROSSED), np.minimum(cr + 3, self.G - gf), 0))])
+            assert self.new_first[-1] == len(self.get("new"))
+
+    def get(self, key):
+        k = self.k + key
+        return self.fx[k] if k in self.fx else self.fx[k.replace(".f32.", ".f64.")]  # (an f32 array equal to its f64 twin is stored once)
+
+    def rows(self, c, s0, s1=None):
+        """the slice of the set's rows that is sweep s0 (sweeps s0 .. s1) of case c"""
+        n_s = self.n.shape[1]
+        return slice(int(self.first[c * n_s + s0]), int(self.first[c * n_s + (s0 if s1 is None else s1) + 1]))
+
+    def dims(self, c, s):
+        """the dims of those rows: the sweep's order of every individual"""
+        return np.array([d for j in range(self.n.shape[2]) for d, _ in gibbs_order(self.G, j, c, self.spec["seed"], s)], dtype=np.int16)
+
+    def numbers(self, rows):
+        """(mask of the rows of the slice that carry numbers, d, S, crossed or None of those)"""
+        has = self.has[rows]
+        at = self.at[rows][has]
+        cr = self.get("crossed")[at] if self.spec["per_gap"] else None
+        return has, self.get("d")[at], self.get("S")[at].astype(np.float64), cr
+
+    def new_terms(self, row):
+        """the stored per-gap new terms of a row (absolute index) that carries numbers: gaps gf, gf + 1, ... (none unless it crosses
+        within PER_GAP_CROSSED gaps)"""
+        k = int(self.at[row])
+        return self.get("new")[int(self.new_first[k]):int(self.new_first[k + 1])]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_cases(name):
+    """[(case name, theta, i_raw, waner, cohort)] of one sweep set"""
+    of, only = SWEEP_SETS[name]["of"], SWEEP_SETS[name]["only"]
+    if of is not None:
+        return [r for r in set_cases(of) if only is None or r[0] in only]
+    coh, out = cohort(("dense", 4, 257, "full")), []  # the wide set: two rows of the table, and an all-ones state at the typical point
+    for cname, theta, st, _ in case_table(257):
+        if cname in ("b=+40 perm=e^3", "sigma=e^-12"):
+            out.append((cname, theta) + state(4, 257, st) + (coh,))
+    out.append(("ones", _th(257)) + state(4, 257, "ones") + (coh,))
+    return out

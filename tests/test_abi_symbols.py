@@ -39,6 +39,25 @@ def test_argument_errors_need_no_gpu():
     assert b"NULL" in lib.abd_last_error()
 
 
+def test_gibbs_record_layout_matches_the_header():
+    """abd_gibbs_record as include/abd_hip.h declares it, field by field, against the structured dtype gibbs_sweep(log=True) returns;
+    the path codes against the header's enum; the logged call refuses NULL without a GPU."""
+    import numpy as np
+
+    from abdpymc_amd import _native
+
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "abd_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\} abd_gibbs_record;", src).group(1)
+    fields = re.findall(r"(double|int16_t|uint8_t)\s+(\w+);", body)
+    ctype = {"double": "<f8", "int16_t": "<i2", "uint8_t": "u1"}
+    assert np.dtype([(n, ctype[t]) for t, n in fields]) == _native.GIBBS_RECORD and _native.GIBBS_RECORD.itemsize == 24
+    codes = {n.lower(): int(v) for n, v in re.findall(r"ABD_GIBBS_PATH_(\w+) = (\d+)", src)}
+    assert codes == _native.GIBBS_PATHS and len(set(codes.values())) == 8
+    lib = _native.load()
+    assert lib.abd_gibbs_sweep_log(None, 0, None, None, 0, 0, None, None, None, 0, None) == -1
+    assert b"NULL" in lib.abd_last_error()
+
+
 def test_missing_library_fails_loudly():
     code = "import abdpymc_amd._native as n; n.load()"
     env = dict(os.environ, ABD_HIP_LIB="/nonexistent/libabd_hip.so", PYTHONPATH=ROOT)
