@@ -157,6 +157,7 @@ SYMBOLS = {
     "abd_set_follow_up": (C.c_int, [_P, _I32]),
     "abd_risk": (C.c_int, [_P, C.c_int32, _D, C.POINTER(_RiskSpec), _D]),
     "abd_pointwise_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
+    "abd_individual_loglik": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_posterior_predictive": (C.c_int, [_P, C.c_int32, _D, C.c_uint64, C.c_uint32, C.c_uint64, _D, _D, _D, _D]),
     "abd_simulate": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, _I8, _D, _D, _D, _D, _D]),
     "abd_simulate_staged": (C.c_int, [_P, C.POINTER(_SimParams), _D, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64, _I8, _D, _D, _D, _D, _D]),
@@ -168,6 +169,8 @@ SYMBOLS = {
     "abd_sampler_means": (C.c_int, [_P, C.c_int32, _D, _D, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_pointwise": (C.c_int, [_P, C.c_int32]),
     "abd_sampler_pointwise_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_individual_loglik": (C.c_int, [_P, C.c_int32]),
+    "abd_sampler_individual_loglik_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64), _D]),
     "abd_sampler_enable_predictive": (C.c_int, [_P, C.c_int32]),
     "abd_sampler_predictive_stats": (C.c_int, [_P, C.c_int32, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_curves": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double]),
@@ -588,6 +591,16 @@ class Context:
                                                          _ptr(ll_n, C.c_double)))
         return ll_s, ll_n
 
+    def individual_loglik(self, chain: int, theta):
+        """Per individual, the sum of ``pointwise_loglik`` over its S readings and over its N readings at (theta, the chain
+        slot's discrete state) -> (ll_s, ll_n), each (n_inds,); 0 where the individual has no reading of that antigen.  Summed
+        on the device in a fixed order: the same state gives the same bits."""
+        t = _theta(theta)
+        ll_s, ll_n = np.empty(self.n_inds), np.empty(self.n_inds)
+        _check(self._lib, self._lib.abd_individual_loglik(self._h, int(chain), _ptr(t, C.c_double), _ptr(ll_s, C.c_double),
+                                                          _ptr(ll_n, C.c_double)))
+        return ll_s, ll_n
+
     def posterior_predictive(self, chain: int, theta, seed: int = 0, stream: int = 0, draw: int = 0, mean: bool = False):
         """Posterior predictive replicate of every OD reading at (theta, the chain slot's discrete state) -> (yrep_s, yrep_n),
         each in the order the readings were given; ``mean=True`` adds the noise-free means (m_s, m_n).  The normals are keyed
@@ -783,6 +796,11 @@ class NativeSampler:
         """Accumulate the pointwise log-likelihood statistics of every draw on the device (``pointwise_stats``)."""
         _check(self._lib, self._lib.abd_sampler_enable_pointwise(self._h, 1))
 
+    def enable_individual_loglik(self):
+        """Accumulate the statistics of every individual's joint log-likelihood over every draw on the device
+        (``individual_loglik_stats``)."""
+        _check(self._lib, self._lib.abd_sampler_enable_individual_loglik(self._h, 1))
+
     def enable_predictive(self):
         """Accumulate the posterior predictive check statistics of every draw on the device (``predictive_stats``)."""
         _check(self._lib, self._lib.abd_sampler_enable_predictive(self._h, 1))
@@ -872,6 +890,17 @@ class NativeSampler:
         """Pointwise log-likelihood statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S
         readings then N in the caller's order; rows log sum exp(ll), mean(ll), sum of squared deviations (compare.merge)."""
         return self._reading_stats(self._lib.abd_sampler_pointwise_stats, k)
+
+    def individual_loglik_stats(self, k: int):
+        """Statistics of every individual's joint log-likelihood T_j (``Context.individual_loglik``: ll_s + ll_n) of the k-th
+        chain over its draws -> (out, n_draws, n_readings): out is (3, n_inds), rows as ``pointwise_stats``; n_readings
+        (n_inds,) int64, the individual's readings of both antigens."""
+        N = self._ctx.n_inds
+        out, n_readings = np.empty((3, N)), np.empty(N, np.int64)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_individual_loglik_stats(self._h, int(k), _ptr(out, C.c_double), C.byref(n),
+                                                                        _out(n_readings, np.int64)))
+        return out, n.value, n_readings
 
     def predictive_stats(self, k: int):
         """Posterior predictive check statistics of the k-th chain over its draws -> (out, n_draws): out is (3, K_s + K_n), S

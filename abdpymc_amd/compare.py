@@ -12,6 +12,13 @@ Convention (``az.waic(..., scale="log")``): over the S draws of all chains poole
     se        = sqrt(n * Var_i(elpd_i)), ddof 0, n readings
     warning   when some p_waic_i > 0.4 (the count is returned)
 
+The readings of one individual are not exchangeable draws: they all hang on that individual's infection column and waner
+flag.  ``by="individual"`` (``sample(..., waic=True, waic_by="individual")``) runs the same formulas over the
+joint log-likelihood of every individual's readings, T_sj = sum over j's readings of ll_sk: ``elpd_i`` / ``p_waic_i`` have one
+entry per individual, ``se`` and ``compare``'s ``dse`` run over the individuals that have a reading (the others contribute an
+exact 0 to the sums), and the p_waic > 0.4 count is of individuals.  WAIC is less reliable the larger the unit: expect more
+individuals above 0.4 than readings.
+
 Accumulated statistics per reading -- ``lse`` = log sum_s exp(ll_si) (not divided by the count), ``mean`` = the mean of ll_si,
 ``m2`` = sum_s (ll_si - mean)^2, with the draw count ``n`` -- merge exactly over chains and processes: log-add-exp for
 ``lse``, Chan et al.'s pairwise update for ``mean`` / ``m2``.
@@ -28,6 +35,8 @@ Stats = Tuple[np.ndarray, np.ndarray, np.ndarray, int]  # (lse, mean, m2, n)
 
 WARN_P_WAIC = 0.4
 WAIC_KEYS = ("elpd_waic_i_it_s_lik", "elpd_waic_i_it_n_lik", "p_waic_i_it_s_lik", "p_waic_i_it_n_lik")  # what the CLI adds per reading
+IND_KEYS = ("elpd_waic_ind", "p_waic_ind")  # ... and per individual
+WAIC_BY = ("reading", "individual", "both")
 
 
 def stats_from_matrix(ll) -> Stats:
@@ -68,10 +77,48 @@ def merge(*stats: Stats) -> Stats:
     return lse, mean, m2, n
 
 
-def chain_stats(res: Mapping[str, np.ndarray]) -> Iterable[Stats]:
-    """The per-chain statistics of a ``sample(..., waic=True)`` result (leading chain axis, gathered over ranks or not)."""
+def chain_stats(res: Mapping[str, np.ndarray], by: str = "reading") -> Iterable[Stats]:
+    """The per-chain statistics of a ``sample(..., waic=True)`` result (leading chain axis, gathered over ranks or not):
+    per reading, or -- ``by="individual"`` -- per individual (``waic_by``)."""
+    pre = {"reading": "waic_", "individual": "waic_ind_"}[by]
     for c in range(np.asarray(res["waic_n_draws"]).shape[0]):
-        yield res["waic_lse"][c], res["waic_mean"][c], res["waic_m2"][c], int(res["waic_n_draws"][c])
+        yield res[pre + "lse"][c], res[pre + "mean"][c], res[pre + "m2"][c], int(res["waic_n_draws"][c])
+
+
+def individual_matrix(ll_s, ll_n, idx_ind_s, idx_ind_n, n_inds: int) -> np.ndarray:
+    """Pointwise log-likelihood matrices (..., K_s) and (..., K_n) (``log_likelihood_it_s_lik`` / ``_it_n_lik``) with the
+    individual of every reading -> (..., n_inds): every individual's joint log-likelihood, S readings added in the order
+    given, then N; 0 for an individual without readings."""
+    ll_s, ll_n = np.asarray(ll_s, dtype=np.float64), np.asarray(ll_n, dtype=np.float64)
+    if ll_s.shape[:-1] != ll_n.shape[:-1]:
+        raise ValueError(f"ll_s {ll_s.shape} and ll_n {ll_n.shape} differ in their leading axes")
+    out = np.zeros(ll_s.shape[:-1] + (int(n_inds),))
+    for ll, idx in ((ll_s, idx_ind_s), (ll_n, idx_ind_n)):
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if idx.size != ll.shape[-1]:
+            raise ValueError(f"{idx.size} individuals for {ll.shape[-1]} readings")
+        if idx.size and (idx.min() < 0 or idx.max() >= n_inds):
+            raise ValueError(f"individual outside [0, {n_inds})")
+        np.add.at(out, (Ellipsis, idx), ll)
+    return out
+
+
+def waic_from_individual_stats(stats: Stats, n_readings) -> Dict[str, object]:
+    """WAIC by individual (module docstring) from the merged statistics of T_j and ``n_readings`` (N,), every individual's
+    number of readings.  The dictionary of ``waic_from_stats`` with one entry per individual in ``elpd_i`` / ``p_waic_i``
+    (an exact 0 without readings), plus ``n_individuals`` (those with a reading: ``se`` runs over them) and ``n_readings_i``."""
+    lse, mean, m2, n = stats
+    if n < 1:
+        raise ValueError("no draws")
+    n_readings = np.asarray(n_readings, dtype=np.int64)
+    has = n_readings > 0
+    p_waic_i = np.where(has, np.asarray(m2, float) / n, 0.0)
+    elpd_i = np.where(has, np.asarray(lse, float) - np.log(n) - p_waic_i, 0.0)
+    m = int(has.sum())
+    return dict(elpd_waic=float(elpd_i.sum()), p_waic=float(p_waic_i.sum()),
+                se=float(np.sqrt(m * np.var(elpd_i[has]))) if m else 0.0, elpd_i=elpd_i, p_waic_i=p_waic_i,
+                n_warn=int((p_waic_i > WARN_P_WAIC).sum()), n_draws=int(n), n_readings=int(n_readings.sum()),
+                n_individuals=m, n_readings_i=n_readings)
 
 
 def waic_from_stats(stats: Stats, n_obs=None) -> Dict[str, object]:
@@ -93,10 +140,21 @@ def waic_from_stats(stats: Stats, n_obs=None) -> Dict[str, object]:
     return out
 
 
-def waic(res: Mapping[str, np.ndarray]) -> Dict[str, object]:
+def waic(res: Mapping[str, np.ndarray], by=None) -> Dict[str, object]:
     """WAIC of a ``sample(..., waic=True)`` result: the chains' accumulators merged, then ``waic_from_stats``.  A result
-    that holds only the recorded matrices (``log_likelihood=True``) is handed to ``waic_from_matrix``."""
-    if "waic_n_draws" in res:
+    that holds only the recorded matrices (``log_likelihood=True``) is handed to ``waic_from_matrix``.
+    ``by``: "reading", "individual" (``waic_by``; ``waic_from_individual_stats``) or ``None``: per reading where the result
+    has it, else per individual."""
+    if by not in (None, "reading", "individual"):
+        raise ValueError(f"by must be 'reading' or 'individual', got {by!r}")
+    if by is None:
+        by = "individual" if "waic_ind_lse" in res and "waic_lse" not in res else "reading"
+    if by == "individual":
+        if "waic_ind_lse" not in res:
+            raise ValueError("the result has no waic_ind_* accumulators (sample(..., waic=True, waic_by='individual')); a recorded "
+                             "matrix is regrouped with individual_matrix and handed to waic_from_matrix(..., groups=...)")
+        return waic_from_individual_stats(merge(*chain_stats(res, by="individual")), np.asarray(res["waic_ind_n_readings"])[0])
+    if "waic_lse" in res:
         n_obs = np.asarray(res["waic_n_obs"])[0] if "waic_n_obs" in res else None
         return waic_from_stats(merge(*chain_stats(res)), n_obs)
     if "log_likelihood_it_s_lik" in res:
@@ -105,26 +163,58 @@ def waic(res: Mapping[str, np.ndarray]) -> Dict[str, object]:
     raise ValueError("the result has neither waic_* accumulators nor log_likelihood_* matrices")
 
 
-def waic_from_matrix(ll, n_obs=None) -> Dict[str, object]:
-    """WAIC of a pointwise log-likelihood matrix (chains, draws, K) or (draws, K): the draws of all chains are pooled."""
+def waic_from_matrix(ll, n_obs=None, groups=None, n_groups=None) -> Dict[str, object]:
+    """WAIC of a pointwise log-likelihood matrix (chains, draws, K) or (draws, K): the draws of all chains are pooled.
+    ``groups`` (K,): the individual of every column -- the columns are summed by individual first (``n_groups`` of them,
+    default ``max(groups) + 1``) and the result is WAIC by individual (``waic_from_individual_stats``)."""
     ll = np.asarray(ll, dtype=np.float64)
-    return waic_from_stats(stats_from_matrix(ll.reshape(-1, ll.shape[-1])), n_obs)
+    if groups is None:
+        return waic_from_stats(stats_from_matrix(ll.reshape(-1, ll.shape[-1])), n_obs)
+    groups = np.asarray(groups, dtype=np.int64).reshape(-1)
+    n_groups = int(n_groups) if n_groups is not None else (int(groups.max()) + 1 if groups.size else 0)
+    T = individual_matrix(ll, ll[..., :0], groups, groups[:0], n_groups)
+    return waic_from_individual_stats(stats_from_matrix(T.reshape(-1, n_groups)), np.bincount(groups, minlength=n_groups))
 
 
-def compare(results: Mapping[str, Mapping[str, np.ndarray]]) -> Dict[str, Dict[str, float]]:
+def compare(results: Mapping[str, Mapping[str, np.ndarray]], by=None) -> Dict[str, Dict[str, float]]:
     """Rank fitted variants of ONE cohort (same readings in the same order) by elpd_waic.  Per variant: ``elpd_waic``,
     ``p_waic``, ``se``, ``elpd_diff`` (best minus this one, >= 0) and its paired standard error
-    ``dse = sqrt(K * Var_i(elpd_i^best - elpd_i^this))`` (ddof 0; ``az.compare``'s), ``rank`` (0 = best)."""
-    w = {name: (r if "elpd_i" in r else waic(r)) for name, r in results.items()}
+    ``dse = sqrt(K * Var_i(elpd_i^best - elpd_i^this))`` (ddof 0; ``az.compare``'s), ``rank`` (0 = best).
+    ``by`` as in ``waic``.  By individual, i runs over the n individuals with a reading: ``dse = sqrt(n * Var_j(elpd_j^best -
+    elpd_j^this))``.  Variants that lack the statistics asked for, or that are not all of one kind, are a ``ValueError``
+    that names them."""
+    w, lacking = {}, []
+    for name, r in results.items():
+        if "elpd_i" in r:  # a dictionary of waic / waic_from_*
+            if by is not None and (by == "individual") != ("n_individuals" in r):
+                lacking.append(name)
+            w[name] = r
+            continue
+        try:
+            w[name] = waic(r, by)
+        except ValueError:
+            if by is None:
+                raise
+            lacking.append(name)
+    if lacking:
+        raise ValueError(f"variants without WAIC by {by}: {sorted(lacking)}")
+    kinds = {name: "individual" if "n_individuals" in v else "reading" for name, v in w.items()}
+    if len(set(kinds.values())) > 1:
+        raise ValueError(f"variants mix WAIC by reading and by individual: {kinds}")
+    individual = "individual" in kinds.values()
     sizes = {name: v["elpd_i"].size for name, v in w.items()}
     if len(set(sizes.values())) > 1:
-        raise ValueError(f"variants differ in their readings: {sizes}")
+        raise ValueError(f"variants differ in their {'individuals' if individual else 'readings'}: {sizes}")
+    if individual and any(not np.array_equal(v["n_readings_i"] > 0, next(iter(w.values()))["n_readings_i"] > 0) for v in w.values()):
+        raise ValueError("variants differ in which individuals have readings")
     order = sorted(w, key=lambda k: -w[k]["elpd_waic"])
     best = w[order[0]]
     out = {}
     for rank, name in enumerate(order):
         v = w[name]
         diff = best["elpd_i"] - v["elpd_i"]
+        if individual:
+            diff = diff[v["n_readings_i"] > 0]
         K = diff.size
         out[name] = dict(rank=rank, elpd_waic=v["elpd_waic"], p_waic=v["p_waic"], se=v["se"],
                          elpd_diff=float(best["elpd_waic"] - v["elpd_waic"]),
@@ -135,37 +225,81 @@ def compare(results: Mapping[str, Mapping[str, np.ndarray]]) -> Dict[str, Dict[s
 class _Waic(Summary):
     """``waic``: accumulate the per-reading statistics of the pointwise log-likelihood over ALL draws on the device (any cohort
     size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n; S readings first), ``waic_n_draws``
-    (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``waic`` reads them.  The trajectories do not change."""
+    (chains,) and ``waic_n_obs`` (chains, 2) = (K_s, K_n): ``waic`` reads them.  The trajectories do not change.
+
+    ``waic_by``: the unit the statistics are kept for.  "reading" (the default): the above.  "individual": the same
+    statistics of every individual's joint log-likelihood T_j (the sum over its readings of both antigens, summed on the
+    device in a fixed order) as ``waic_ind_lse`` / ``waic_ind_mean`` / ``waic_ind_m2`` (chains, N), with
+    ``waic_ind_n_readings`` (chains, N) and ``waic_n_draws``; nothing is kept per reading.  "both": both sets."""
 
     name = "waic"
-    options = {"waic": False}
+    options = {"waic": False, "waic_by": "reading"}
     prefix = "waic_"
-    derived_keys = WAIC_KEYS
-    dims = {k: ["it_s_lik_dim_0" if "it_s_lik" in k else "it_n_lik_dim_0"] for k in WAIC_KEYS}
+    derived_keys = WAIC_KEYS + IND_KEYS
+    dims = dict({k: ["it_s_lik_dim_0" if "it_s_lik" in k else "it_n_lik_dim_0"] for k in WAIC_KEYS}, **{k: ["ind"] for k in IND_KEYS})
     record_row = "log_likelihood"
     native_only = ("log_likelihood / waic need the native sampler (sample(native=True)): the pointwise log-likelihood "
                    "is recorded and accumulated inside it")
 
+    def plan(self, opts, draws, chains, G, N):
+        if opts["waic_by"] not in WAIC_BY:
+            raise ValueError(f"waic_by must be one of {WAIC_BY}, got {opts['waic_by']!r}")
+        return super().plan(opts, draws, chains, G, N)
+
     def enable(self, smp, plan):
-        smp.enable_pointwise()
+        if plan["waic_by"] != "individual":
+            smp.enable_pointwise()
+        if plan["waic_by"] != "reading":
+            smp.enable_individual_loglik()
 
     def collect(self, smp, plan, last_gap):
-        return per_reading_result("waic_", ("lse", "mean", "m2"), [smp.pointwise_stats(c) for c in range(plan["chains"])], smp.n_obs)
+        res = {}
+        if plan["waic_by"] != "individual":
+            res = per_reading_result("waic_", ("lse", "mean", "m2"), [smp.pointwise_stats(c) for c in range(plan["chains"])], smp.n_obs)
+        if plan["waic_by"] != "reading":
+            per_chain = [smp.individual_loglik_stats(c) for c in range(plan["chains"])]
+            for j, name in enumerate(("lse", "mean", "m2")):
+                res["waic_ind_" + name] = np.stack([o[j] for o, _, _ in per_chain])
+            res["waic_ind_n_readings"] = np.stack([np.asarray(r, dtype=np.int64) for _, _, r in per_chain])
+            res["waic_n_draws"] = np.array([n for _, n, _ in per_chain], dtype=np.int64)
+        return res
 
     def add_arguments(self, parser):
         parser.add_argument("--waic", help="Accumulate the pointwise log-likelihood of the OD readings on the device over all draws and "
                             "report WAIC (elpd_waic, p_waic, se; per reading elpd_waic_i / p_waic_i in the output).", action="store_true")
+        parser.add_argument("--waic_by", choices=WAIC_BY, default=None,
+                            help="With --waic: the unit WAIC is computed over.  reading (default): every OD reading.  individual: the "
+                            "joint log-likelihood of each individual's readings, the exchangeable unit of the cohort (se over "
+                            "individuals; elpd_waic_ind / p_waic_ind in the output).  both: both.")
+
+    def cli_options(self, args, data, chains, world):
+        if args.waic_by is not None and not args.waic:
+            raise SystemExit("--waic_by needs --waic")
+        return {"waic": args.waic, "waic_by": args.waic_by or "reading"}
 
     def report(self, res, data):
-        """The per-reading values go into ``res`` (keys WAIC_KEYS)."""
-        w = waic(res)
-        res["elpd_waic_i_it_s_lik"], res["elpd_waic_i_it_n_lik"] = w["elpd_waic_i_s"], w["elpd_waic_i_n"]
-        res["p_waic_i_it_s_lik"], res["p_waic_i_it_n_lik"] = w["p_waic_i_s"], w["p_waic_i_n"]
-        return [f"WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_readings']} readings, "
-                f"{w['n_draws']} draws; {w['n_warn']} readings with p_waic_i > 0.4)"]
+        """The per-reading values go into ``res`` (keys WAIC_KEYS), the per-individual ones too (IND_KEYS)."""
+        lines = []
+        if "waic_lse" in res:
+            w = waic(res, by="reading")
+            res["elpd_waic_i_it_s_lik"], res["elpd_waic_i_it_n_lik"] = w["elpd_waic_i_s"], w["elpd_waic_i_n"]
+            res["p_waic_i_it_s_lik"], res["p_waic_i_it_n_lik"] = w["p_waic_i_s"], w["p_waic_i_n"]
+            lines.append(f"WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_readings']} readings, "
+                         f"{w['n_draws']} draws; {w['n_warn']} readings with p_waic_i > 0.4)")
+        if "waic_ind_lse" in res:
+            w = waic(res, by="individual")
+            res["elpd_waic_ind"], res["p_waic_ind"] = w["elpd_i"], w["p_waic_i"]
+            line = (f"WAIC by individual: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  "
+                    f"({w['n_individuals']} individuals, {w['n_draws']} draws; {w['n_warn']} with p_waic_j > 0.4")
+            if w["n_individuals"]:  # the individual the model predicts worst, among those with readings
+                j = int(np.argmin(np.where(w["n_readings_i"] > 0, w["elpd_i"], np.inf)))
+                ids = getattr(data, "coords", {}).get("ind")
+                line += f"; worst: individual {j if ids is None else ids[j]} elpd {w['elpd_i'][j]:.3f}"
+            lines.append(line + ")")
+        return lines
 
     def group(self, key):
-        return "constant_data" if key in WAIC_KEYS else None  # (the accumulators themselves are not written)
+        return "constant_data" if key in WAIC_KEYS + IND_KEYS else None  # (the accumulators themselves are not written)
 
 
 SUMMARY = _Waic()

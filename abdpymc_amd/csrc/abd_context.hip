@@ -497,6 +497,8 @@ int upload_panels(abd_ctx* c, const abd_desc* d, SortedObs& so_s, SortedObs& so_
   if (int rc = upload(c, d->n, so_n, c->n)) return rc;
   c->order_s = std::move(so_s.order);  // sorted position -> caller's index (abd_eval.hip: scatter_readings)
   c->order_n = std::move(so_n.order);
+  c->seg_s = std::move(so_s.ptr);  // (observation lists: the device's copies are s.ptr, n.ptr)
+  c->seg_n = std::move(so_n.ptr);
   c->xc_ok = c->dense && c->s.od && c->n.od;
   c->xc_max_cb = tune_int("ABD_XC_MAX_CB", c->xc_max_cb);
   const size_t words = (size_t)c->nt * N;

@@ -5,6 +5,7 @@
 #include "abd_eval_kernels.hpp"
 #include "abd_train.hpp"
 #include "abd_readings.hpp"
+#include "abd_individual.hpp"
 #include "abd_simulate.hpp"
 
 namespace abdi {
@@ -598,6 +599,37 @@ int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st,
   return launch_readings(c, chain, tr, op, st);
 }
 
+int launch_individual_loglik(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc,
+                             int64_t n_draw) {
+  if (!ll_s && !ll_n && !acc) return ABD_OK;
+  const Transformed tr = transform(theta);
+  IndLogLik op;
+  std::memset(&op, 0, sizeof op);
+  op.ll_s = ll_s;
+  op.ll_n = ll_n;
+  op.acc = acc;
+  op.seg_s = c->s.ptr;  // (observation lists: uploaded with them, empty segments and all; dense panels have none)
+  op.seg_n = c->n.ptr;
+  op.n_draw = acc ? n_draw : 0;
+  op.inv_n = acc ? 1.0 / (double)n_draw : 0.0;
+  op.inv_sig[kAgN] = 1.0 / tr.sig_n;
+  op.inv_sig[kAgS] = 1.0 / tr.sig_s;
+  op.lnorm[kAgN] = -(theta[13] + 0.5 * kLog2Pi);  // as launch_pointwise
+  op.lnorm[kAgS] = -(theta[16] + 0.5 * kLog2Pi);
+  // one wave per individual in both layouts, three power tables, at most 8 workgroups per CU; a cohort without readings is
+  // a lists cohort of empty segments: the launch writes its zeros
+  const ReadingArgs<IndLogLik> a{readings_of(c, chain, tr), op};
+  const bool f32 = c->storage == ABD_STORE_F32, wide = c->nt > ABD_MAXT;
+  using Kernel = void (*)(const ReadingArgs<IndLogLik>);
+  const Kernel k = c->dense ? (f32 ? (wide ? abd_individual_dense_kernel<float, ABD_MAXT_MAX> : abd_individual_dense_kernel<float, ABD_MAXT>)
+                                   : (wide ? abd_individual_dense_kernel<double, ABD_MAXT_MAX> : abd_individual_dense_kernel<double, ABD_MAXT>))
+                            : (f32 ? (wide ? abd_individual_lists_kernel<float, ABD_MAXT_MAX> : abd_individual_lists_kernel<float, ABD_MAXT>)
+                                   : (wide ? abd_individual_lists_kernel<double, ABD_MAXT_MAX> : abd_individual_lists_kernel<double, ABD_MAXT>));
+  const int blocks = std::max(1, std::min((c->N + ABD_WAVES_PER_BLOCK - 1) / ABD_WAVES_PER_BLOCK, c->n_cu * 8));
+  HIP_TRY(launch_kernel(k, dim3(blocks), dim3(ABD_BLOCK), cell_tables_bytes(c->G), st, a));
+  return ABD_OK;
+}
+
 int upload_order(abd_ctx* c) {
   if (c->d_order) return ABD_OK;
   const int64_t Ks = c->s.K, Kn = c->n.K;
@@ -744,6 +776,21 @@ int abd_pointwise_loglik(abd_ctx* c, int32_t chain, const double* theta, double*
     return rc;
   const ReadingOut out[1] = {{ll_s, ll_n}};
   if (!h.empty()) scatter_readings(c, out, [&](int, size_t k) { return h[k]; });
+  return ABD_OK;
+}
+
+int abd_individual_loglik(abd_ctx* c, int32_t chain, const double* theta, double* ll_s, double* ll_n) {
+  if (!c || !theta || (!ll_s && !ll_n)) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = check_chains(c, 1, &chain)) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (int rc = flush_ring(c)) return rc;
+  const size_t N = (size_t)c->N;
+  if (!c->d_ind_stage) HIP_TRY(c->d_ind_stage.alloc(2 * N));
+  double* const d = c->d_ind_stage;
+  if (int rc = launch_individual_loglik(c, chain, theta, c->stream, ll_s ? d : nullptr, ll_n ? d + N : nullptr, nullptr, 0)) return rc;
+  if (ll_s) HIP_TRY(hipMemcpyAsync(ll_s, d, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (ll_n) HIP_TRY(hipMemcpyAsync(ll_n, d + N, N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return ABD_OK;
 }
 

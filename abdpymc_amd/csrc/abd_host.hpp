@@ -201,6 +201,7 @@ struct abd_ctx {
   std::vector<uint32_t> win_mask;   // ... and which pipes had work in it
   AntigenDev s, n;
   std::vector<int64_t> order_s, order_n;  // reading k of the device's sorted order is the caller's reading order_*[k]
+  std::vector<int32_t> seg_s, seg_n;  // [N + 1] offset of every individual's first reading in the sorted order
   DevBuf<uint64_t> vw;  // [nt][N]
   DevBuf<uint64_t> pw;  // [nt][N]
   DevBuf<double> exp2_tab;  // dense cohorts: 2^(j/1024) (abd_dense.hpp)
@@ -238,6 +239,7 @@ struct abd_ctx {
   int g2_refill_min = ABD_G2_REFILL_MIN, g2_tail_lanes = ABD_G2_TAIL_LANES, g2_tail_age = ABD_G2_TAIL_AGE;  // scheduler knobs of abd_gibbs_dense_kernel (ABD_G2_*)
   DevBuf<double> d_stage;                  // staging of abd_pointwise_loglik / abd_posterior_predictive: stage_rows rows of K_s + K_n doubles
   int stage_rows = 0;
+  DevBuf<double> d_ind_stage;              // staging of abd_individual_loglik: [2][N] (S_j, N_j), allocated on first use
   DevBuf<uint32_t> d_order;                // order_s then order_n as uint32 (the predictive stream's counter), uploaded on first use
   DevBuf<double> d_det;                    // staging of abd_deterministics: mu_n, mu_s (G*N doubles each), i (G*N bytes)
   DevBuf<int32_t> d_last;                  // [N] end of follow-up (abd_set_follow_up); empty: G - 1 for everyone
@@ -345,6 +347,12 @@ int dense_blocks(const abd_ctx* c, int cpw, int share = 0, int grid_rows = 1, in
 // readings then N; nullptr skips) and / or the accumulators acc ([4][K_s + K_n]) updated by draw n_draw >= 1 (acc nullptr:
 // not updated)
 int launch_pointwise(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll, double* acc, int64_t n_draw);
+// Per-individual sums of the pointwise log-likelihood of chain `chain` at theta on stream st (abd_individual.hpp): the rows
+// ll_s, ll_n ([N] each, S_j and N_j; nullptr skips) and / or the accumulators acc ([4][N]) updated with T_j = S_j + N_j by draw
+// n_draw >= 1 (acc nullptr: not updated).  A context without readings gets its zeros.  Writes no member of the context:
+// the sampler's host threads call it side by side.
+int launch_individual_loglik(abd_ctx* c, int chain, const double* theta, hipStream_t st, double* ll_s, double* ll_n, double* acc,
+                             int64_t n_draw);
 // The caller's reading order on the device (c->d_order), uploaded once; ABD_ERR_ARG for 2^32 readings or more of an antigen.
 // Not thread-safe: callers upload before any run loop starts.
 int upload_order(abd_ctx* c);

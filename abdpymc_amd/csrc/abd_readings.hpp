@@ -71,6 +71,47 @@ struct ReadingArgs {
   Op op;
 };
 
+// ll_k of one reading at titer response a, log dilution x, od y -- the ONE place it is written (LogLik below; the
+// per-individual sums of abd_individual.hpp): the residual as obs_term forms it (q = y - d s)
+__device__ __forceinline__ double reading_loglik(double b2, double d, double inv_sig, double lnorm, double a, double x, double y) {
+  const double t = fmin(b2 * (a - x), 1021.0);
+  const double s = rcp_newton(1.0 + exp2_reduced(t));
+  const double z = fma(-d, s, y) * inv_sig;
+  return fma(-0.5 * z, z, lnorm);
+}
+
+// Draw n_draw's value v into column r of a chain's accumulators acc [4][kt] (rows M, S, mean, M2): the one lane that owns
+// the column reads, updates and writes it
+__device__ __forceinline__ void waic_update(double* acc, int64_t r, int64_t kt, double v, int64_t n_draw, double inv_n) {
+  double M, S, mean, M2;
+  if (n_draw == 1) {
+    M = v;
+    S = 1.0;
+    mean = v;
+    M2 = 0.0;
+  } else {
+    M = acc[r];
+    S = acc[kt + r];
+    mean = acc[2 * kt + r];
+    M2 = acc[3 * kt + r];
+    // e^u for u <= 0 by the same 2^t polynomial as the curve (its constants are already in registers), clamped where
+    // e^u is 0 anyway
+    if (v > M) {
+      S = fma(S, exp2_reduced(fmax((M - v) * 1.4426950408889634074, -1100.0)), 1.0);
+      M = v;
+    } else {
+      S += exp2_reduced(fmax((v - M) * 1.4426950408889634074, -1100.0));
+    }
+    const double dlt = v - mean;
+    mean = fma(dlt, inv_n, mean);
+    M2 = fma(dlt, v - mean, M2);
+  }
+  acc[r] = M;
+  acc[kt + r] = S;
+  acc[2 * kt + r] = mean;
+  acc[3 * kt + r] = M2;
+}
+
 // The pointwise log-likelihood: the row and / or the draw's update of the WAIC accumulators
 struct LogLik {
   double* ll;             // [K_s + K_n] device row; nullptr: not written
@@ -85,41 +126,11 @@ struct LogLik {
   __device__ __forceinline__ Side side(const Readings& w, int ag) const {
     return {to_vgpr(w.b2[ag]), to_vgpr(w.d[ag]), to_vgpr(inv_sig[ag]), to_vgpr(lnorm[ag])};
   }
-  // reading r (column of the S-then-N row of kt readings): the residual as obs_term forms it (q = y - d s)
+  // reading r (column of the S-then-N row of kt readings)
   __device__ __forceinline__ void operator()(const Side& c, int64_t r, int64_t kt, double a, double x, double y) const {
-    const double t = fmin(c.b2 * (a - x), 1021.0);
-    const double s = rcp_newton(1.0 + exp2_reduced(t));
-    const double z = fma(-c.d, s, y) * c.inv_sig;
-    const double v = fma(-0.5 * z, z, c.lnorm);
+    const double v = reading_loglik(c.b2, c.d, c.inv_sig, c.lnorm, a, x, y);
     if (ll) ll[r] = v;
-    if (!acc) return;
-    double M, S, mean, M2;
-    if (n_draw == 1) {
-      M = v;
-      S = 1.0;
-      mean = v;
-      M2 = 0.0;
-    } else {
-      M = acc[r];
-      S = acc[kt + r];
-      mean = acc[2 * kt + r];
-      M2 = acc[3 * kt + r];
-      // e^u for u <= 0 by the same 2^t polynomial as the curve (its constants are already in registers), clamped where
-      // e^u is 0 anyway
-      if (v > M) {
-        S = fma(S, exp2_reduced(fmax((M - v) * 1.4426950408889634074, -1100.0)), 1.0);
-        M = v;
-      } else {
-        S += exp2_reduced(fmax((v - M) * 1.4426950408889634074, -1100.0));
-      }
-      const double dlt = v - mean;
-      mean = fma(dlt, inv_n, mean);
-      M2 = fma(dlt, v - mean, M2);
-    }
-    acc[r] = M;
-    acc[kt + r] = S;
-    acc[2 * kt + r] = mean;
-    acc[3 * kt + r] = M2;
+    if (acc) waic_update(acc, r, kt, v, n_draw, inv_n);
   }
 };
 

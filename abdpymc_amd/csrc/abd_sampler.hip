@@ -136,6 +136,8 @@ struct abd_sampler {
   // pointwise log-likelihood statistics of every draw (abd_readings.hpp: LogLik): [n][4][K_s + K_n] running max, scaled sum
   // of exp, mean, M2 per reading
   DevBuf<double> d_pw_acc;
+  // the same statistics of every individual's joint log-likelihood T_j (abd_individual.hpp): [n][4][N]
+  DevBuf<double> d_ind_acc;
   DevBuf<double> d_rec_yrep;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
   // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
   // predictive mean, mean tail probability per reading
@@ -268,9 +270,10 @@ int alloc_rec_rows(abd_sampler* s, DevBuf<double>& d, const char* what) {
   return ABD_OK;
 }
 
-// A per-chain block of `rows` x (K_s + K_n) accumulators (abd_sampler_enable_pointwise / _predictive): the old one freed, a
-// new one allocated and zeroed if `accumulate` (after the upload of the reading order if the launches read it: `order`)
-int enable_acc(abd_sampler* s, DevBuf<double>& acc, int rows, int32_t accumulate, bool order, const char* what) {
+// A per-chain block of `rows` x `cols` accumulators (abd_sampler_enable_pointwise / _predictive: K_s + K_n columns;
+// _individual_loglik: N): the old one freed, a new one allocated and zeroed if `accumulate` (after the upload of the reading
+// order if the launches read it: `order`)
+int enable_acc(abd_sampler* s, DevBuf<double>& acc, int rows, size_t cols, int32_t accumulate, bool order, const char* what) {
   if (s->ran) return fail(ABD_ERR_STATE, "%s accumulation must be enabled before the first abd_sampler_run call", what);
   abd_ctx* c = s->c;
   HIP_TRY(hipSetDevice(c->device));
@@ -281,7 +284,7 @@ int enable_acc(abd_sampler* s, DevBuf<double>& acc, int rows, int32_t accumulate
   if (!accumulate) return ABD_OK;
   if (order)
     if (int rc = upload_order(c)) return rc;
-  const size_t n_acc = std::max<size_t>(1, (size_t)s->n * rows * (size_t)(c->s.K + c->n.K));
+  const size_t n_acc = std::max<size_t>(1, (size_t)s->n * rows * cols);
   DevBuf<double> fresh;  // (acc stays empty unless the block is there and zeroed)
   const hipError_t e = fresh.alloc_zero(n_acc, c->stream);
   if (e == hipErrorOutOfMemory) {
@@ -590,6 +593,10 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   double* acc = (draw && s->d_pw_acc) ? s->d_pw_acc + (size_t)j * 4 * Kt : nullptr;
   if (ll || acc)
     if (int rc = launch_pointwise(c, chain, q, st, ll, acc, iter - s->o.tune + 1)) return rc;
+  // ... and per individual: a draw, accumulation on -- the running statistics of T_j
+  if (draw && s->d_ind_acc)
+    if (int rc = launch_individual_loglik(c, chain, q, st, nullptr, nullptr, s->d_ind_acc + (size_t)j * 4 * N, iter - s->o.tune + 1))
+      return rc;
   // posterior predictive: the record's replicate row (keyed by seed, the chain's global id and the iteration, so that
   // abd_posterior_predictive reproduces it) and / or -- a draw, accumulation on -- the check statistics
   double* yrep = (rec && (rec->yrep_s || rec->yrep_n)) ? s->d_rec_yrep + at * Kt : nullptr;
@@ -1265,7 +1272,7 @@ int abd_sampler_launch_shape(abd_sampler* s, int32_t out[4]) {
 
 int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  return enable_acc(s, s->d_pw_acc, 4, accumulate, false, "pointwise");
+  return enable_acc(s, s->d_pw_acc, 4, (size_t)(s->c->s.K + s->c->n.K), accumulate, false, "pointwise");
 }
 
 int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
@@ -1277,9 +1284,40 @@ int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t*
   });
 }
 
+int abd_sampler_enable_individual_loglik(abd_sampler* s, int32_t accumulate) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  return enable_acc(s, s->d_ind_acc, 4, (size_t)s->c->N, accumulate, false, "individual_loglik");
+}
+
+int abd_sampler_individual_loglik_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws, int64_t* n_readings) {
+  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
+  if (!s->d_ind_acc) return fail(ABD_ERR_STATE, "individual_loglik accumulation is not enabled (abd_sampler_enable_individual_loglik)");
+  abd_ctx* c = s->c;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
+    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
+  const size_t N = (size_t)c->N;
+  std::vector<double> h(4 * N);
+  HIP_TRY(hipMemcpy(h.data(), s->d_ind_acc + (size_t)k * 4 * N, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  // rows M, S, mean, M2 -> M + log S (-inf before the first draw), mean, M2: as abd_sampler_pointwise_stats
+  for (size_t j = 0; j < N; ++j) {
+    out[j] = h[j] + std::log(h[N + j]);
+    out[N + j] = h[2 * N + j];
+    out[2 * N + j] = h[3 * N + j];
+  }
+  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
+  if (n_readings) {
+    for (size_t j = 0; j < N; ++j)
+      n_readings[j] = (int64_t)(c->seg_s[j + 1] - c->seg_s[j]) + (int64_t)(c->seg_n[j + 1] - c->seg_n[j]);
+  }
+  return ABD_OK;
+}
+
 int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  return enable_acc(s, s->d_pp_acc, 3, accumulate, true, "predictive");
+  return enable_acc(s, s->d_pp_acc, 3, (size_t)(s->c->s.K + s->c->n.K), accumulate, true, "predictive");
 }
 
 int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {

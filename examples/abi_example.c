@@ -78,6 +78,15 @@ int main(void) {
   printf("logp = %.6f, %.6f; d logp / d it_n_d = %.6f\n", logp[0], logp[1], grad[12]);
   if (!isfinite(logp[0]) || !isfinite(grad[12])) return 1;
 
+  /* the joint log-likelihood of every individual's readings: its sum over the cohort is the log-likelihood */
+  static double ind_s[N], ind_n[N];
+  CHECK(abd_individual_loglik(ctx, 0, theta, ind_s, ind_n));
+  double loglik = 0.0, ind_total = 0.0;
+  CHECK(abd_loglik_dlogp(ctx, 0, theta, &loglik, grad));
+  for (int j = 0; j < N; ++j) ind_total += ind_s[j] + ind_n[j];
+  printf("log-likelihood = %.6f, summed over the individuals %.6f\n", loglik, ind_total);
+  if (!(fabs(ind_total - loglik) <= 1e-6 * fabs(loglik))) return 1;
+
   abd_sampler_opts o;
   o.tune = 150;
   o.seed = 7;
@@ -90,6 +99,7 @@ int main(void) {
   o.reserved = 0;
   abd_sampler* smp = NULL;
   CHECK(abd_sampler_create(ctx, C, chains, theta, &o, &smp));
+  CHECK(abd_sampler_enable_individual_loglik(smp, 1));
   enum { DRAWS = 150 };
   static double draws[C * DRAWS * ABD_N_THETA], stats[C * DRAWS * ABD_N_STATS];
   CHECK(abd_sampler_run(smp, o.tune, NULL, NULL));
@@ -109,6 +119,14 @@ int main(void) {
   for (int k = 0; k < DRAWS; ++k) d_n += draws[k * ABD_N_THETA + 12];
   printf("%lld draws: it_n_d = %.3f, infection found for %.0f%% of the infected, %.1f%% of the others\n", (long long)n_draws,
          d_n / DRAWS, 100.0 * found, 100.0 * spurious);
+  /* per individual: log sum exp, mean and M2 of its joint log-likelihood over the draws, and how many readings it has */
+  static double ind_stats[3 * N];
+  static int64_t n_readings[N];
+  int64_t n_ind_draws = 0;
+  CHECK(abd_sampler_individual_loglik_stats(smp, 0, ind_stats, &n_ind_draws, n_readings));
+  printf("individual 0: %lld readings, mean joint log-likelihood %.3f over %lld draws\n", (long long)n_readings[0], ind_stats[N],
+         (long long)n_ind_draws);
+  if (n_ind_draws != DRAWS || n_readings[0] != 2 * G || !isfinite(ind_stats[N])) return 1;
   abd_sampler_destroy(smp);
   CHECK(abd_destroy(ctx));
   return (found > 0.8 && spurious < 0.1) ? 0 : 2;

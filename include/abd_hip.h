@@ -244,6 +244,13 @@ int abd_risk(abd_ctx* ctx, int32_t chain, const double* theta, const abd_risk_sp
  * abd_loglik_dlogp's loglik to rounding. */
 int abd_pointwise_loglik(abd_ctx* ctx, int32_t chain, const double* theta, double* ll_s, double* ll_n);
 
+/* Per individual j of the context: the sum of the pointwise log-likelihood over j's S readings (ll_s[N]) and N readings
+ * (ll_n[N]); either pointer may be NULL, not both.  0 where j has no reading of that antigen.  The joint log-likelihood of
+ * individual j is ll_s[j] + ll_n[j].  Summed on the device in a fixed order (one wave per individual, its readings in
+ * ascending gap, a fixed butterfly over the lanes): two calls at the same state return the same bits, and a row differs from
+ * any other summation of abd_pointwise_loglik's values by rounding only. */
+int abd_individual_loglik(abd_ctx* ctx, int32_t chain, const double* theta, double* ll_s, double* ll_n);
+
 /* Posterior predictive of the two observed Normals at theta and chain slot `chain`'s discrete state (what
  * pm.sample_posterior_predictive draws for one draw): per OD reading the noise-free mean m = d / (1 + exp(-b (x - a))) into
  * mean_*, and the replicate y_rep = m + sigma z into yrep_*, s.n_obs / n.n_obs doubles each in the caller's reading order; any
@@ -416,6 +423,15 @@ int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate);
  * squared deviations from it (M2).  They merge exactly over chains and processes: log-add-exp for row 0, Chan et al.'s
  * pairwise formulas for rows 1 and 2 (abdpymc_amd/compare.py).  *n_draws (may be NULL) receives the number of draws. */
 int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws);
+/* As abd_sampler_enable_pointwise, for T_j = S_j + N_j; refused after the first abd_sampler_run*.  The joint log-likelihood
+ * of every individual's readings (abd_individual_loglik: ll_s[j] + ll_n[j]) at every draw (iteration >= tune, whatever is
+ * recorded or thinned); accumulate = 1 allocates 4 x N doubles per chain, 0 releases them.  Independent of
+ * abd_sampler_enable_pointwise: either, both or neither may be on.  The chains' trajectories do not change. */
+int abd_sampler_enable_individual_loglik(abd_sampler* s, int32_t accumulate);
+/* out[3][N]: lse, mean, m2 of T_j over the draws so far (as abd_sampler_pointwise_stats); n_readings[N] (may be NULL):
+ * j's readings of both antigens.  An individual without readings has T_j = 0 at every draw: lse = log(n_draws), mean = m2 = 0.
+ * *n_draws (may be NULL) receives the number of draws. */
+int abd_sampler_individual_loglik_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws, int64_t* n_readings);
 /* Posterior predictive check statistics of every draw (iteration >= tune), accumulated on the device per chain and reading.
  * Allowed before the first abd_sampler_run* call (ABD_ERR_STATE after it); accumulate = 1 allocates 3 x (K_s + K_n) doubles
  * per chain, 0 releases them.  No random numbers are drawn: the chains' trajectories do not change. */

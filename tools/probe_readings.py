@@ -1,7 +1,9 @@
 """
 Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals x 200 gaps, 4 M readings): wall time of a
 4-chain compound sampler run with and without on-device WAIC accumulation (``--leg waic``: sample(..., waic=True)) or posterior
-predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the epidemic curves of every draw (``--leg curves``:
+predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the per-individual WAIC accumulation alone (``--leg
+individual``: sample(..., waic=True, waic_by="individual"); ``--profile``: waic_by="both", so that abd_individual_dense_kernel runs
+beside abd_readings_dense_kernel<LogLik, ...> in one trace) or the epidemic curves of every draw (``--leg curves``:
 sample(..., curves=True); not a per-reading output, but the same question) or the per-cell convergence accumulators
 (``--leg diagnostics``: sample(..., diagnostics=True); likewise) or the infection-risk-by-titer table of every draw (``--leg
 risk``: sample(..., risk=spec) with 7 edges per antigen, the whole window, first infections only; likewise) or the per-individual
@@ -35,7 +37,7 @@ from abdpymc_amd.sampler import sample  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("waic", "ppc", "curves", "diagnostics", "risk", "timelines"), default="waic")
+    ap.add_argument("--leg", choices=("waic", "individual", "ppc", "curves", "diagnostics", "risk", "timelines"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
@@ -53,6 +55,8 @@ def main():
     spec = risk.spec(0, a.gaps, 0.5 * np.arange(1, 8), 0.5 * np.arange(1, 8), 1)
 
     def leg_kw(on):  # the option of this leg, switched on or off
+        if a.leg == "individual":
+            return dict(waic=on, waic_by="individual")
         return dict(risk=spec if on else None) if a.leg == "risk" else {a.leg: on}
 
     if a.profile:
@@ -62,6 +66,8 @@ def main():
             on = dict(curves=True)
         if a.leg == "timelines":
             on = dict(timelines=True, diagnostics=True)
+        if a.leg == "individual":
+            on = dict(waic=True, waic_by="both")
         sample(m, draws=a.draws[0], **on, **(leg_kw(True) if a.leg == "risk" else {}), **kw)
         print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on, risk=a.leg == "risk",
                               wall_s=time.perf_counter() - t0)))
