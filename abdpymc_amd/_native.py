@@ -119,6 +119,13 @@ def _risk_spec(spec) -> "_RiskSpec":
     return r
 
 
+class _SurvivalDesc(C.Structure):  # abd_survival_desc
+    _fields_ = [("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_titers", C.c_int32), ("device", C.c_int32),
+                ("infected", C.c_void_p), ("exposure", C.c_void_p), ("titer", C.c_void_p * 2),
+                ("ab_sd", C.c_double), ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double),
+                ("lam0_z_sd", C.c_double)]
+
+
 # abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
 GIBBS_RECORD = np.dtype([("value", "<f8"), ("log_u", "<f8"), ("dim", "<i2"), ("gf", "<i2"), ("stop", "<i2"), ("path", "u1"),
                          ("accepted", "u1")])
@@ -196,6 +203,11 @@ SYMBOLS = {
     "abd_stream_queues": (C.c_int, [_P, _I32, C.c_int32]),
     "abd_n_pipes": (C.c_int, [_P]),
     "abd_is_dense": (C.c_int, [_P]),
+    "abd_survival_create": (C.c_int, [C.POINTER(_SurvivalDesc), C.POINTER(_P)]),
+    "abd_survival_destroy": (C.c_int, [_P]),
+    "abd_survival_dim": (C.c_int32, [_P]),
+    "abd_survival_logp_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
+    "abd_survival_loglik_sums": (C.c_int, [_P, _D, _D]),
 }
 
 
@@ -1025,6 +1037,62 @@ class NativeSampler:
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.abd_sampler_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Survival:
+    """One survival model's data resident on the device (abd_hip.h: ``abd_survival``): ``infected``, ``exposure`` (N, T) and one or
+    two titer arrays (N, T); ``priors`` = (ab_sd, lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd).  The library checks the cells."""
+
+    def __init__(self, infected, exposure, titers, priors, device: int = -1):
+        lib = load()
+        self._lib = lib
+        self._h = _P()
+        y, e = _as(infected, np.float64), _as(exposure, np.float64)
+        xs = [_as(x, np.float64) for x in titers]
+        if y.ndim != 2 or e.shape != y.shape or any(x.shape != y.shape for x in xs):
+            raise ValueError("infected, exposure and the titers must share a shape (N, T)")
+        if len(xs) not in (1, 2):
+            raise ValueError(f"one or two titer arrays, got {len(xs)}")
+        d = _SurvivalDesc()
+        d.n_inds, d.n_intervals, d.n_titers, d.device = y.shape[0], y.shape[1], len(xs), device
+        d.infected, d.exposure = y.ctypes.data, e.ctypes.data
+        for k, x in enumerate(xs):
+            d.titer[k] = x.ctypes.data
+        d.ab_sd, d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd = (float(v) for v in priors)
+        _check(lib, lib.abd_survival_create(C.byref(d), C.byref(self._h)))
+        self.n_inds, self.n_intervals, self.n_titers = y.shape[0], y.shape[1], len(xs)
+        self.dim = int(lib.abd_survival_dim(self._h))
+
+    def logp_dlogp(self, theta):
+        """``theta`` (D,) -> (logp, grad (D,)); (n, D) -> (logp (n,), grad (n, D))."""
+        t = _as(theta, np.float64)
+        one = t.ndim == 1
+        t2 = t.reshape(1, -1) if one else t
+        if t2.ndim != 2 or t2.shape[1] != self.dim:
+            raise ValueError(f"theta must have shape ({self.dim},) or (n, {self.dim}), got {t.shape}")
+        lp, g = np.empty(t2.shape[0]), np.empty(t2.shape)
+        _check(self._lib, self._lib.abd_survival_logp_dlogp(self._h, t2.shape[0], _ptr(t2), _ptr(lp), _ptr(g)))
+        return (float(lp[0]), g[0]) if one else (lp, g)
+
+    def loglik_sums(self, theta):
+        """The raw device sums at one point: S_t (T), L, W_0, W_k (K)."""
+        t = _as(theta, np.float64)
+        if t.shape != (self.dim,):
+            raise ValueError(f"theta must have shape ({self.dim},)")
+        out = np.empty(self.n_intervals + 2 + self.n_titers)
+        _check(self._lib, self._lib.abd_survival_loglik_sums(self._h, _ptr(t), _ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.abd_survival_destroy(self._h)
             self._h = _P()
 
     def __del__(self):

@@ -1,5 +1,7 @@
 // abd_eval.hip -- evaluation launches of the C ABI (include/abd_hip.h): the dense-panel and observation-list kernels,
 // the pipes (HIP streams) stream-ordered launches rotate over, completion tags in mapped host memory, device timing.
+#include <memory>
+
 #include "abd_host.hpp"
 #include "abd_fuse_plan.hpp"
 #include "abd_eval_kernels.hpp"
@@ -7,6 +9,8 @@
 #include "abd_readings.hpp"
 #include "abd_individual.hpp"
 #include "abd_simulate.hpp"
+#include "abd_survival.hpp"
+#include "abd_survival_terms.hpp"
 
 namespace abdi {
 
@@ -1060,6 +1064,185 @@ int abd_simulate_staged(abd_ctx* c, const abd_sim_params* par, const double* lam
     if (rc) return rc;
     HIP_TRY(se);
   }
+  return ABD_OK;
+}
+
+}  // extern "C"
+
+// ---- the survival models of a finished run (abd_survival.hpp, abd_survival_terms.hpp) ----
+
+struct abd_survival {
+  int N = 0, T = 0, K = 0, D = 0, device = 0;
+  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0, par_stride = 0, out_stride = 0;
+  SurvivalPriors priors{};
+  std::vector<double> Y;  // Y_t = sum_j y_jt
+  double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
+  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
+  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
+  std::vector<double> work;        // log lambda, 1 - lambda of the points in flight
+  Stream stream;
+};
+
+namespace abdi {
+namespace {
+
+// the sums of n <= ABD_MAX_BATCH points into s->h_out (rows of out_stride)
+int survival_launch(abd_survival* s, int n, const double* theta) {
+  const int T = s->T, K = s->K;
+  for (int q = 0; q < n; ++q)
+    survival_prepare(K, T, theta + (size_t)q * s->D, s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * T);
+  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->par_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.par = s->d_par;
+  a.s_part = s->d_s_part;
+  a.w_part = s->d_w_part;
+  a.out = s->d_out;
+  a.T = T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.nseg = s->nseg;
+  a.seg_len = s->seg_len;
+  a.par_stride = s->par_stride;
+  const dim3 grid((unsigned)((s->nw + 3) / 4), (unsigned)n);
+  HIP_TRY(launch_kernel(K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, grid, dim3(256), 0, s->stream, a));
+  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, a));
+  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return ABD_OK;
+}
+
+}  // namespace
+}  // namespace abdi
+
+extern "C" {
+
+namespace {
+int survival_create(const abd_survival_desc* d, abd_survival** out);
+}
+
+int abd_survival_create(const abd_survival_desc* d, abd_survival** out) {
+  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  try {
+    return survival_create(d, out);
+  } catch (const std::bad_alloc&) {  // the host copies of the planes: nothing may be thrown across the C ABI
+    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
+  }
+}
+
+namespace {
+int survival_create(const abd_survival_desc* d, abd_survival** out) {
+  const int K = d->n_titers;
+  if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
+  if (d->n_inds < 1) return fail(ABD_ERR_ARG, "n_inds=%d must be >= 1", d->n_inds);
+  if (d->n_intervals < 1 || d->n_intervals > ABD_MAX_GAPS - 1)
+    return fail(ABD_ERR_ARG, "n_intervals=%d outside [1, %d]", d->n_intervals, ABD_MAX_GAPS - 1);
+  if (!d->infected || !d->exposure || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+  const double pos[4] = {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
+  for (double v : pos)
+    if (!(v > 0.0) || !std::isfinite(v)) return fail(ABD_ERR_ARG, "ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd must be positive and finite, got %g", v);
+  if (!std::isfinite(d->lam0_mu_mean)) return fail(ABD_ERR_ARG, "lam0_mu_mean must be finite, got %g", d->lam0_mu_mean);
+  const int N = d->n_inds, T = d->n_intervals;
+  const int ntile = (N + 63) / 64;
+  const size_t ld = (size_t)ntile * 64, plane = ld * (size_t)T;
+  // [interval][individual] planes, padded with cells that have no follow-up
+  std::vector<double> y(plane, 0.0), e(plane, 0.0), x0(plane, 0.0), x1(K == 2 ? plane : 0, 0.0);
+  std::vector<SurvivalSum> Ysum((size_t)T);
+  SurvivalSum Csum;
+  for (int j = 0; j < N; ++j)
+    for (int t = 0; t < T; ++t) {
+      const size_t src = (size_t)j * T + t, dst = (size_t)t * ld + j;
+      double yy = d->infected[src], ee = d->exposure[src], xx[2] = {d->titer[0][src], K == 2 ? d->titer[1][src] : 0.0};
+      if (const char* msg = survival_check_cell(K, yy, ee, xx)) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", j, t, msg);
+      y[dst] = yy;
+      e[dst] = ee;
+      x0[dst] = xx[0];
+      if (K == 2) x1[dst] = xx[1];
+      Ysum[t].add(yy);
+      if (yy > 0.0) Csum.add(yy * std::log(ee));
+      Csum.add(-std::lgamma(yy + 1.0));
+    }
+  std::vector<double> Y((size_t)T);
+  for (int t = 0; t < T; ++t) Y[t] = Ysum[t].value();
+  const double C = Csum.value();
+  abd_survival* s = new (std::nothrow) abd_survival;
+  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
+  std::unique_ptr<abd_survival> own(s);
+  s->N = N;
+  s->T = T;
+  s->K = K;
+  s->D = survival_dim(K, T);
+  s->priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
+  s->Y = std::move(Y);
+  s->C = C;
+  s->ld = (int)ld;
+  s->ntile = ntile;
+  // ranges of intervals: enough waves for the chip (about 4096) while a wave keeps at least one interval; from N and T alone
+  const int want_seg = std::max(1, std::min(T, (4096 + ntile - 1) / ntile));
+  s->seg_len = (T + want_seg - 1) / want_seg;
+  s->nseg = (T + s->seg_len - 1) / s->seg_len;
+  s->nw = s->ntile * s->nseg;
+  s->par_stride = T + 2 * K;
+  s->out_stride = T + ABD_SURV_NW;
+  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  if (d->device >= 0) {
+    s->device = d->device;
+  } else {
+    HIP_TRY(hipGetDevice(&s->device));
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->stream.create());
+  HIP_TRY(s->d_y.upload(y.data(), plane));
+  HIP_TRY(s->d_e.upload(e.data(), plane));
+  HIP_TRY(s->d_x0.upload(x0.data(), plane));
+  if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), plane));
+  HIP_TRY(s->d_par.alloc((size_t)ABD_MAX_BATCH * s->par_stride));
+  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
+  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
+  HIP_TRY(s->d_out.alloc((size_t)ABD_MAX_BATCH * s->out_stride));
+  HIP_TRY(s->h_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->par_stride));
+  HIP_TRY(s->h_out.alloc_pinned((size_t)ABD_MAX_BATCH * s->out_stride));
+  *out = own.release();
+  return ABD_OK;
+}
+}  // namespace
+
+int abd_survival_destroy(abd_survival* s) {
+  if (!s) return ABD_OK;
+  (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  delete s;
+  return ABD_OK;
+}
+
+int32_t abd_survival_dim(abd_survival* s) { return s ? s->D : -1; }
+
+int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, double* logp, double* grad) {
+  if (!s || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_launch(s, nb, theta + (size_t)k0 * s->D)) return rc;
+    for (int q = 0; q < nb; ++q) {
+      const size_t k = (size_t)k0 + q;
+      logp[k] = survival_combine(s->priors, s->K, s->T, theta + k * s->D, s->Y.data(), s->C, s->h_out.host() + (size_t)q * s->out_stride,
+                                 s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * s->T, grad + k * s->D);
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums) {
+  if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = survival_launch(s, 1, theta)) return rc;
+  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
   return ABD_OK;
 }
 

@@ -1,6 +1,6 @@
 /*
  * The C ABI from plain C (C99): build a small dense cohort, evaluate logp + gradient, run the compound sampler,
- * read the posterior means back.  What a non-Python host (or a cffi / cgo / JNI stub) would do.
+ * read the posterior means back, evaluate a survival model of them.  What a non-Python host (or a cffi / cgo / JNI stub) would do.
  *
  *   gcc -std=c99 -Wall -Wextra -pedantic -I include examples/abi_example.c -L abdpymc_amd -labd_hip \
  *       -Wl,-rpath,$PWD/abdpymc_amd -lm -o build/abi_example
@@ -104,9 +104,9 @@ int main(void) {
   static double draws[C * DRAWS * ABD_N_THETA], stats[C * DRAWS * ABD_N_STATS];
   CHECK(abd_sampler_run(smp, o.tune, NULL, NULL));
   CHECK(abd_sampler_run(smp, DRAWS, draws, stats));
-  static double i_mean[K];
+  static double i_mean[K], n_mean[K];
   int64_t n_draws = 0;
-  CHECK(abd_sampler_means(smp, 0, i_mean, NULL, NULL, &n_draws));
+  CHECK(abd_sampler_means(smp, 0, i_mean, n_mean, NULL, &n_draws));
   double found = 0.0, spurious = 0.0;
   for (int j = 0; j < N; ++j) {
     double any = 0.0; /* posterior mass of "infected somewhere in gaps 5..8" */
@@ -129,5 +129,44 @@ int main(void) {
   if (n_ind_draws != DRAWS || n_readings[0] != 2 * G || !isfinite(ind_stats[N])) return 1;
   abd_sampler_destroy(smp);
   CHECK(abd_destroy(ctx));
+  /* the plug-in survival model of the N titer (reference survival.py: model_alone): infection probability of gap t + 1 against
+   * the titer of gap t, at most one infection per individual, exposure = what is left of it */
+  enum { T = G - 1, D = 2 + 2 + T };
+  static double infected[N * T], exposure[N * T], titer[N * T];
+  for (int j = 0; j < N; ++j) {
+    double left = 1.0;
+    for (int t = 0; t < T; ++t) {
+      const double p = i_mean[(t + 1) * N + j] < left ? i_mean[(t + 1) * N + j] : left;
+      infected[j * T + t] = p;
+      exposure[j * T + t] = left;
+      titer[j * T + t] = n_mean[t * N + j];
+      left -= p;
+      if (left < 0.0) left = 0.0;
+    }
+  }
+  abd_survival_desc sd;
+  sd.n_inds = N;
+  sd.n_intervals = T;
+  sd.n_titers = 1;
+  sd.device = -1;
+  sd.infected = infected;
+  sd.exposure = exposure;
+  sd.titer[0] = titer;
+  sd.titer[1] = NULL;
+  sd.ab_sd = 1.0;
+  sd.lam0_mu_mean = -3.0;
+  sd.lam0_mu_sd = 0.5;
+  sd.lam0_sd_rate = 2.0;
+  sd.lam0_z_sd = 1.0;
+  abd_survival* sv = NULL;
+  CHECK(abd_survival_create(&sd, &sv));
+  if (abd_survival_dim(sv) != D) return 1;
+  static double q[D], sgrad[D];
+  double slp = 0.0;
+  q[2] = -3.0; /* a = b = 0, _lam0_raw_mu = -3, sd = 1, z = 0 */
+  CHECK(abd_survival_logp_dlogp(sv, 1, q, &slp, sgrad));
+  printf("survival model of the N titer at its start point: logp = %.3f, d/db = %.3f\n", slp, sgrad[1]);
+  if (!isfinite(slp) || !isfinite(sgrad[1])) return 1;
+  CHECK(abd_survival_destroy(sv));
   return (found > 0.8 && spurious < 0.1) ? 0 : 2;
 }

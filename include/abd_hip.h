@@ -641,6 +641,44 @@ int abd_is_dense(abd_ctx* ctx);
 int abd_n_pipes(abd_ctx* ctx);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The survival models of a finished run (reference survival.py:116-153: model_alone, model_combined): Poisson hazard
+ *   infected[j, t] ~ Poisson(exposure[j, t] * lam0[t] * invlogit(sum_k b_k (titer_k[j, t] - a_k)))
+ * over N individuals and T intervals, with K = 1 titer (alone) or K = 2 (combined: S, N).  A handle keeps the arrays on the
+ * device; an evaluation returns logp and its gradient at unconstrained points
+ *   theta[D] = a[K], b[K], _lam0_raw_mu, _lam0_raw_sd_log__, __lam0_raw_z[T]        D = 2 K + 2 + T
+ * (PyMC's creation order; lam0 = invlogit(_lam0_raw_mu + exp(_lam0_raw_sd_log__) * __lam0_raw_z)).  It is independent of
+ * abd_ctx.  Python: abdpymc_amd.survival. */
+typedef struct {
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T = end - start - 1, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_titers;            /* K: 1 or 2 */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const double* infected;      /* (N, T) row-major; >= 0, may be fractional; NaN = no follow-up in that cell */
+  const double* exposure;      /* (N, T) row-major; >= 0; NaN likewise; a cell with infected > 0 and exposure 0 is refused */
+  const double* titer[2];      /* (N, T) row-major each, finite wherever the cell is followed; titer[1] is read for K = 2 only */
+  double ab_sd;                /* a_k, b_k ~ Normal(0, ab_sd): 1 alone, 0.5 combined (survival.py:121-122, 140-143) */
+  double lam0_mu_mean;         /* _lam0_raw_mu ~ Normal(lam0_mu_mean, lam0_mu_sd): -3, 0.5 */
+  double lam0_mu_sd;
+  double lam0_sd_rate;         /* _lam0_raw_sd ~ Exponential(lam0_sd_rate): 2 */
+  double lam0_z_sd;            /* __lam0_raw_z ~ Normal(0, lam0_z_sd): 1 */
+} abd_survival_desc;
+
+typedef struct abd_survival abd_survival;
+
+/* Checks the descriptor and every cell (ABD_ERR_ARG; before the device is touched), copies the arrays to the device. */
+int abd_survival_create(const abd_survival_desc* desc, abd_survival** out);
+int abd_survival_destroy(abd_survival* s);
+/* D = 2 K + 2 + T, or -1 for NULL. */
+int32_t abd_survival_dim(abd_survival* s);
+/* logp[n] and grad[n][D] at theta[n][D]; up to ABD_MAX_BATCH points share a launch (more are split).  A point's result is
+ * the same bits alone and in any batch. */
+int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, double* logp, double* grad);
+/* The raw device sums at one point, for parity tests: sums[T + 2 + K] = S_t[T], L, W_0, W_k[K] with
+ * sigma = invlogit(eta), S_t = sum_j exposure sigma, L = sum_{infected > 0} infected log sigma,
+ * w = (infected - exposure lam0_t sigma)(1 - sigma), W_0 = sum w, W_k = sum w titer_k. */
+int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums);
+
+/* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).
  * This table is complete: the product library calls getenv for nothing else (development knobs of launch shapes
  * exist only in a tuning build compiled with -DABD_TUNING, tools/README.md).

@@ -1,0 +1,109 @@
+"""
+What the survival evaluator costs: microseconds per ``logp_dlogp`` call for 1 and 4 points per launch, the wall time
+of a 1000 + 1000 x 4-chain fit of the combined model, and the NumPy restatement's time per evaluation on this host beside them,
+at N x T = 1 520 x 30 and 10 000 x 199.  Data are simulated from the model (seeded).
+
+    python tools/probe_survival.py [--out FILE] [--tune 1000] [--draws 1000] [--no_fit]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from abdpymc_amd import survival  # noqa: E402
+from tests import survival_restatement as R  # noqa: E402
+
+SIZES = ((1520, 30), (10000, 199))
+
+
+def simulate(N, T, seed=0):
+    """(y, e, [x_s, x_n]) from the combined model at a = (1.5, 1), b = (1.5, 0.5), lam0 in [0.02, 0.08]; one infection at most,
+    exposure 1 until it, no follow-up (NaN) after a random last interval."""
+    rng = np.random.default_rng([seed, N, T])
+    xs = [rng.uniform(0.0, 4.0, size=(N, T)) for _ in range(2)]
+    lam0 = rng.uniform(0.02, 0.08, size=T)
+    eta = 1.5 * (xs[0] - 1.5) + 0.5 * (xs[1] - 1.0)
+    event = rng.random((N, T)) < lam0[None, :] / (1.0 + np.exp(-eta))
+    y = (event & (np.cumsum(event, axis=1) == 1)).astype(np.float64)
+    e = np.ones_like(y)
+    e[:, 1:] -= np.cumsum(y, axis=1)[:, :-1]
+    gone = np.arange(T)[None, :] >= rng.integers(max(1, T // 2), T + 1, size=N)[:, None]
+    y[gone], e[gone] = np.nan, np.nan
+    return y, e, xs
+
+
+def per_call(fn, q, seconds=1.0):
+    fn(q)
+    n, t0 = 0, time.perf_counter()
+    while True:
+        for _ in range(20):
+            fn(q)
+        n += 20
+        dt = time.perf_counter() - t0
+        if dt >= seconds:
+            return 1e6 * dt / n
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    ap.add_argument("--tune", type=int, default=1000)
+    ap.add_argument("--draws", type=int, default=1000)
+    ap.add_argument("--no_fit", action="store_true")
+    args = ap.parse_args(argv)
+    rows = []
+    for N, T in SIZES:
+        y, e, xs = simulate(N, T)
+        rs = R.Restatement(y, e, xs)
+        model = survival.SurvivalModel(y, e, xs, ("S", "N"))
+        rng = np.random.default_rng(1)
+        q = np.zeros((4, model.dim))
+        q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+        q += rng.uniform(-0.5, 0.5, size=q.shape)
+        row = {"N": N, "T": T, "K": 2, "dim": model.dim, "cells": N * T, "data_bytes": 32 * N * T}
+        row["device_us_per_call_n1"] = per_call(model.logp_dlogp, q[0])
+        row["device_us_per_call_n4"] = per_call(model.logp_dlogp, q)
+        row["numpy_us_per_evaluation"] = per_call(rs.logp_dlogp, q[0])
+        lp_d, g_d = model.logp_dlogp(q[0])
+        lp_r, g_r = rs.logp_dlogp(q[0])
+        row["logp_device"], row["logp_numpy"] = lp_d, lp_r
+        row["grad_max_rel_diff"] = float(np.abs(g_d - g_r).max() / np.abs(g_r).max())
+        print(json.dumps(row), flush=True)
+        if not args.no_fit:
+            t0 = time.perf_counter()
+            count = [0]
+
+            def counted(x):  # (a sign of life every 50 000 evaluations)
+                count[0] += 1
+                if count[0] % 50000 == 0:
+                    print(f"  {count[0]} evaluations, {time.perf_counter() - t0:.0f} s", file=sys.stderr, flush=True)
+                return model.logp_dlogp(x)
+
+            fit = survival.sample(model, tune=args.tune, draws=args.draws, chains=4, seed=0, evaluator=counted)
+            row["fit_evaluations"] = count[0]
+            row["fit_wall_s"] = time.perf_counter() - t0
+            row["fit_tune"], row["fit_draws"], row["fit_chains"] = args.tune, args.draws, 4
+            row["fit_leapfrogs_kept_draws"] = int(fit["stat_n_steps"].sum())
+            row["fit_mean_tree_depth"] = float(fit["stat_tree_depth"].mean())
+            sm = survival.summary(fit)
+            row["fit_rhat_max_ab"] = float(max(np.max(sm["a"]["rhat"]), np.max(sm["b"]["rhat"])))
+            row["fit_a_median"] = np.median(fit["a"], axis=(0, 1)).tolist()
+            row["fit_b_median"] = np.median(fit["b"], axis=(0, 1)).tolist()
+            print(json.dumps({k: v for k, v in row.items() if k.startswith("fit_")}), flush=True)
+        model.close()
+        rows.append(row)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rows, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
