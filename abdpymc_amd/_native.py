@@ -126,6 +126,15 @@ class _SurvivalDesc(C.Structure):  # abd_survival_desc
                 ("lam0_z_sd", C.c_double)]
 
 
+class _SurvivalGroupsDesc(C.Structure):  # abd_survival_groups_desc
+    _fields_ = [("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_groups", C.c_int32), ("device", C.c_int32),
+                ("infected", C.c_void_p), ("exposure", C.c_void_p), ("titer", C.c_void_p), ("group", C.c_void_p),
+                ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double), ("lam0_z_sd", C.c_double),
+                ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
+
+
+SURVIVAL_MAX_GROUPS = 256  # ABD_SURVIVAL_MAX_GROUPS
+
 # abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
 GIBBS_RECORD = np.dtype([("value", "<f8"), ("log_u", "<f8"), ("dim", "<i2"), ("gf", "<i2"), ("stop", "<i2"), ("path", "u1"),
                          ("accepted", "u1")])
@@ -204,6 +213,7 @@ SYMBOLS = {
     "abd_n_pipes": (C.c_int, [_P]),
     "abd_is_dense": (C.c_int, [_P]),
     "abd_survival_create": (C.c_int, [C.POINTER(_SurvivalDesc), C.POINTER(_P)]),
+    "abd_survival_create_groups": (C.c_int, [C.POINTER(_SurvivalGroupsDesc), C.POINTER(_P)]),
     "abd_survival_destroy": (C.c_int, [_P]),
     "abd_survival_dim": (C.c_int32, [_P]),
     "abd_survival_logp_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
@@ -1069,6 +1079,7 @@ class Survival:
         _check(lib, lib.abd_survival_create(C.byref(d), C.byref(self._h)))
         self.n_inds, self.n_intervals, self.n_titers = y.shape[0], y.shape[1], len(xs)
         self.dim = int(lib.abd_survival_dim(self._h))
+        self.n_sums = y.shape[1] + 2 + len(xs)
 
     def logp_dlogp(self, theta):
         """``theta`` (D,) -> (logp, grad (D,)); (n, D) -> (logp (n,), grad (n, D))."""
@@ -1082,11 +1093,11 @@ class Survival:
         return (float(lp[0]), g[0]) if one else (lp, g)
 
     def loglik_sums(self, theta):
-        """The raw device sums at one point: S_t (T), L, W_0, W_k (K)."""
+        """The raw device sums at one point: S_t (T), L, W_0, W_k (K); of a grouped handle S_t (T), L, W_x, W0_g (Gr)."""
         t = _as(theta, np.float64)
         if t.shape != (self.dim,):
             raise ValueError(f"theta must have shape ({self.dim},)")
-        out = np.empty(self.n_intervals + 2 + self.n_titers)
+        out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_loglik_sums(self._h, _ptr(t), _ptr(out)))
         return out
 
@@ -1100,3 +1111,29 @@ class Survival:
             self.close()
         except Exception:
             pass
+
+
+class SurvivalGroups(Survival):
+    """The survival model by group resident on the device (abd_hip.h: ``abd_survival_create_groups``): ``infected``, ``exposure``,
+    ``titer`` (N, T), ``group`` (N,) indices in [0, ``n_groups``), ``priors`` = (lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd,
+    a_mu_sd, a_sd_rate, a_z_sd, b_sd).  The library checks the labels and the cells; the evaluations are ``Survival``'s."""
+
+    def __init__(self, infected, exposure, titer, group, n_groups: int, priors, device: int = -1):
+        lib = load()
+        self._lib = lib
+        self._h = _P()
+        y, e, x = _as(infected, np.float64), _as(exposure, np.float64), _as(titer, np.float64)
+        g = _as(group, np.int32)
+        if y.ndim != 2 or e.shape != y.shape or x.shape != y.shape:
+            raise ValueError("infected, exposure and the titer must share a shape (N, T)")
+        if g.shape != (y.shape[0],):
+            raise ValueError(f"group must have shape ({y.shape[0]},), got {g.shape}")
+        d = _SurvivalGroupsDesc()
+        d.n_inds, d.n_intervals, d.n_groups, d.device = y.shape[0], y.shape[1], int(n_groups), device
+        d.infected, d.exposure, d.titer, d.group = y.ctypes.data, e.ctypes.data, x.ctypes.data, g.ctypes.data
+        (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
+         d.b_sd) = (float(v) for v in priors)
+        _check(lib, lib.abd_survival_create_groups(C.byref(d), C.byref(self._h)))
+        self.n_inds, self.n_intervals, self.n_titers, self.n_groups = y.shape[0], y.shape[1], 1, int(n_groups)
+        self.dim = int(lib.abd_survival_dim(self._h))
+        self.n_sums = y.shape[1] + 2 + int(n_groups)

@@ -10,6 +10,8 @@
 #include "abd_individual.hpp"
 #include "abd_simulate.hpp"
 #include "abd_survival.hpp"
+#include "abd_survival_groups.hpp"
+#include "abd_survival_groups_terms.hpp"
 #include "abd_survival_terms.hpp"
 
 namespace abdi {
@@ -1074,7 +1076,10 @@ int abd_simulate_staged(abd_ctx* c, const abd_sim_params* par, const double* lam
 struct abd_survival {
   int N = 0, T = 0, K = 0, D = 0, device = 0;
   int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0, par_stride = 0, out_stride = 0;
+  int Gr = 0;  // > 0: the model by group (abd_survival_groups.hpp), K = 1
   SurvivalPriors priors{};
+  SurvivalGroupsPriors gpriors{};
+  DevBuf<int32_t> d_tile_group, d_group_tile;
   std::vector<double> Y;  // Y_t = sum_j y_jt
   double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
   DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
@@ -1087,7 +1092,39 @@ namespace abdi {
 namespace {
 
 // the sums of n <= ABD_MAX_BATCH points into s->h_out (rows of out_stride)
+int survival_groups_launch(abd_survival* s, int n, const double* theta) {
+  const int T = s->T, Gr = s->Gr;
+  for (int q = 0; q < n; ++q)
+    survival_groups_prepare(T, Gr, theta + (size_t)q * s->D, s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * T);
+  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->par_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalGroupsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.x = s->d_x0;
+  a.par = s->d_par;
+  a.tile_group = s->d_tile_group;
+  a.group_tile = s->d_group_tile;
+  a.s_part = s->d_s_part;
+  a.w_part = s->d_w_part;
+  a.out = s->d_out;
+  a.T = T;
+  a.Gr = Gr;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.nseg = s->nseg;
+  a.seg_len = s->seg_len;
+  a.par_stride = s->par_stride;
+  HIP_TRY(launch_kernel(abd_survival_groups_kernel, dim3((unsigned)((s->nw + 3) / 4), (unsigned)n), dim3(256), 0, s->stream, a));
+  HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (Gr + 3) / 4), (unsigned)n), dim3(256), 0,
+                        s->stream, a));
+  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return ABD_OK;
+}
+
 int survival_launch(abd_survival* s, int n, const double* theta) {
+  if (s->Gr > 0) return survival_groups_launch(s, n, theta);
   const int T = s->T, K = s->K;
   for (int q = 0; q < n; ++q)
     survival_prepare(K, T, theta + (size_t)q * s->D, s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * T);
@@ -1212,6 +1249,98 @@ int survival_create(const abd_survival_desc* d, abd_survival** out) {
 }
 }  // namespace
 
+namespace {
+int survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out);
+}
+
+int abd_survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out) {
+  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  try {
+    return survival_create_groups(d, out);
+  } catch (const std::bad_alloc&) {  // the host copies of the planes: nothing may be thrown across the C ABI
+    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
+  }
+}
+
+namespace {
+int survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out) {
+  const int N = d->n_inds, T = d->n_intervals, Gr = d->n_groups;
+  if (N < 1) return fail(ABD_ERR_ARG, "n_inds=%d must be >= 1", N);
+  if (T < 1 || T > ABD_MAX_GAPS - 1) return fail(ABD_ERR_ARG, "n_intervals=%d outside [1, %d]", T, ABD_MAX_GAPS - 1);
+  if (Gr < 1 || Gr > ABD_SURVIVAL_MAX_GROUPS) return fail(ABD_ERR_ARG, "n_groups=%d outside [1, %d]", Gr, ABD_SURVIVAL_MAX_GROUPS);
+  if (!d->infected || !d->exposure || !d->titer || !d->group) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+  const double pos[7] = {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+  for (double v : pos)
+    if (!(v > 0.0) || !std::isfinite(v))
+      return fail(ABD_ERR_ARG, "lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd must be positive and finite, got %g", v);
+  if (!std::isfinite(d->lam0_mu_mean)) return fail(ABD_ERR_ARG, "lam0_mu_mean must be finite, got %g", d->lam0_mu_mean);
+  for (int j = 0; j < N; ++j)
+    if (d->group[j] < 0 || d->group[j] >= Gr) return fail(ABD_ERR_ARG, "individual %d: group %d outside [0, %d)", j, d->group[j], Gr);
+  // the individuals sorted by group, every group padded to whole tiles: a tile belongs to one group
+  std::vector<int32_t> slot((size_t)N), tile_group((size_t)(N + 63) / 64 + Gr), group_tile((size_t)Gr + 1);
+  const int ntile = survival_groups_layout(N, Gr, d->group, slot.data(), tile_group.data(), group_tile.data());
+  const size_t ld = (size_t)ntile * 64, plane = ld * (size_t)T;
+  std::vector<double> y(plane, 0.0), e(plane, 0.0), x(plane, 0.0);
+  std::vector<SurvivalSum> Ysum((size_t)T);
+  SurvivalSum Csum;
+  for (int j = 0; j < N; ++j)
+    for (int t = 0; t < T; ++t) {
+      const size_t src = (size_t)j * T + t, dst = (size_t)t * ld + slot[j];
+      double yy = d->infected[src], ee = d->exposure[src], xx = d->titer[src];
+      if (const char* msg = survival_check_cell(1, yy, ee, &xx)) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", j, t, msg);
+      y[dst] = yy;
+      e[dst] = ee;
+      x[dst] = xx;
+      Ysum[t].add(yy);
+      if (yy > 0.0) Csum.add(yy * std::log(ee));
+      Csum.add(-std::lgamma(yy + 1.0));
+    }
+  abd_survival* s = new (std::nothrow) abd_survival;
+  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
+  std::unique_ptr<abd_survival> own(s);
+  s->N = N;
+  s->T = T;
+  s->K = 1;
+  s->Gr = Gr;
+  s->D = survival_groups_dim(T, Gr);
+  s->gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+  s->Y.resize((size_t)T);
+  for (int t = 0; t < T; ++t) s->Y[t] = Ysum[t].value();
+  s->C = Csum.value();
+  s->ld = (int)ld;
+  s->ntile = ntile;
+  // ranges of intervals as in survival_create: from the tile count and T alone
+  const int want_seg = std::max(1, std::min(T, (4096 + ntile - 1) / ntile));
+  s->seg_len = (T + want_seg - 1) / want_seg;
+  s->nseg = (T + s->seg_len - 1) / s->seg_len;
+  s->nw = s->ntile * s->nseg;
+  s->par_stride = T + Gr + 1;
+  s->out_stride = T + 2 + Gr;
+  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  if (d->device >= 0) {
+    s->device = d->device;
+  } else {
+    HIP_TRY(hipGetDevice(&s->device));
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->stream.create());
+  HIP_TRY(s->d_y.upload(y.data(), plane));
+  HIP_TRY(s->d_e.upload(e.data(), plane));
+  HIP_TRY(s->d_x0.upload(x.data(), plane));
+  HIP_TRY(s->d_tile_group.upload(tile_group.data(), (size_t)ntile));
+  HIP_TRY(s->d_group_tile.upload(group_tile.data(), (size_t)Gr + 1));
+  HIP_TRY(s->d_par.alloc((size_t)ABD_MAX_BATCH * s->par_stride));
+  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
+  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
+  HIP_TRY(s->d_out.alloc((size_t)ABD_MAX_BATCH * s->out_stride));
+  HIP_TRY(s->h_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->par_stride));
+  HIP_TRY(s->h_out.alloc_pinned((size_t)ABD_MAX_BATCH * s->out_stride));
+  *out = own.release();
+  return ABD_OK;
+}
+}  // namespace
+
 int abd_survival_destroy(abd_survival* s) {
   if (!s) return ABD_OK;
   (void)hipSetDevice(s->device);
@@ -1231,8 +1360,11 @@ int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, dou
     if (int rc = survival_launch(s, nb, theta + (size_t)k0 * s->D)) return rc;
     for (int q = 0; q < nb; ++q) {
       const size_t k = (size_t)k0 + q;
-      logp[k] = survival_combine(s->priors, s->K, s->T, theta + k * s->D, s->Y.data(), s->C, s->h_out.host() + (size_t)q * s->out_stride,
-                                 s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * s->T, grad + k * s->D);
+      const double* sums = s->h_out.host() + (size_t)q * s->out_stride;
+      const double* par = s->h_par.host() + (size_t)q * s->par_stride;
+      const double* work = s->work.data() + (size_t)q * 2 * s->T;
+      logp[k] = s->Gr > 0 ? survival_groups_combine(s->gpriors, s->T, s->Gr, theta + k * s->D, s->Y.data(), s->C, sums, par, work, grad + k * s->D)
+                          : survival_combine(s->priors, s->K, s->T, theta + k * s->D, s->Y.data(), s->C, sums, par, work, grad + k * s->D);
     }
   }
   return ABD_OK;
@@ -1242,7 +1374,7 @@ int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums)
   if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = survival_launch(s, 1, theta)) return rc;
-  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
+  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + (s->Gr > 0 ? s->Gr : s->K)) * sizeof(double));
   return ABD_OK;
 }
 

@@ -46,6 +46,28 @@ __device__ __forceinline__ double surv_exp_neg(double abs_eta) {
   return ldexp(exp2_reduced(f), (int)k);
 }
 
+// One cell given eta: e sigma, summed over the wave into *s_t by lane 0; returns w = (y - mu)(1 - sigma) and the cell's
+// y log sigma.  The one statement of the cell: abd_survival_kernel<K> and the grouped kernel (abd_survival_groups.hpp) differ
+// in how they form eta.
+struct SurvCell {
+  double w, ly;
+};
+__device__ __forceinline__ SurvCell surv_cell(double eta, double y, double e, double lam, int lane, double* s_t) {
+  const double en = surv_exp_neg(fabs(eta));
+  double r = rcp_newton(1.0 + en);
+  r = fma(fma(-(1.0 + en), r, 1.0), r, r);
+  const double er = en * r;
+  const bool pos = eta >= 0.0;
+  const double sig = pos ? r : er, oms = pos ? er : r;  // sigma, 1 - sigma
+  const double es = e * sig;
+  const double S = wave_sum_uniform(es);
+  if (lane == 0) *s_t = S;
+  // log sigma = min(eta, 0) - log1p(e^-|eta|); a cell with y = 0 has no log term
+  const double ls = fmin(eta, 0.0) - log1p(en);
+  const double ly = y > 0.0 ? y * ls : 0.0;
+  return SurvCell{fma(-lam, es, y) * oms, ly};
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void abd_survival_kernel(const SurvivalArgs a) {
   const int lane = threadIdx.x & 63;
@@ -70,19 +92,9 @@ __global__ __launch_bounds__(256) void abd_survival_kernel(const SurvivalArgs a)
       x1 = a.x1[idx];
       eta = fma(b1, x1 - a1, eta);
     }
-    const double en = surv_exp_neg(fabs(eta));
-    double r = rcp_newton(1.0 + en);
-    r = fma(fma(-(1.0 + en), r, 1.0), r, r);
-    const double er = en * r;
-    const bool pos = eta >= 0.0;
-    const double sig = pos ? r : er, oms = pos ? er : r;  // sigma, 1 - sigma
-    const double es = e * sig;
-    const double S = wave_sum_uniform(es);
-    if (lane == 0) s_row[t] = S;
-    // log sigma = min(eta, 0) - log1p(e^-|eta|); a cell with y = 0 has no log term
-    const double ls = fmin(eta, 0.0) - log1p(en);
-    L += y > 0.0 ? y * ls : 0.0;
-    const double wc = fma(-lam, es, y) * oms;  // (y - mu)(1 - sigma)
+    const SurvCell c = surv_cell(eta, y, e, lam, lane, s_row + t);
+    L += c.ly;
+    const double wc = c.w;
     W0 += wc;
     W1 = fma(wc, x0, W1);
     if (K == 2) W2 = fma(wc, x1, W2);
@@ -113,35 +125,51 @@ __device__ __forceinline__ double surv_sum_strided(const double* __restrict__ p,
   return v;
 }
 
+// S_t of 64 intervals by one workgroup of 256 threads: thread (g, t) adds the tiles g, g + 4, g + 8, ... in ascending order, then
+// ((g0 + g1) + g2) + g3.  s_part: [points][ntile][T] partials; sm: 256 doubles.
+__device__ __forceinline__ void surv_finalize_s(const double* s_part, int point, int ntile, int T, int block, double* sm, double* out) {
+  const int tid = threadIdx.x;
+  const int t = block * 64 + (tid & 63), g = tid >> 6;
+  const bool live = t < T;
+  const double* sp = s_part + (int64_t)point * ntile * T + (int64_t)g * T + (live ? t : 0);
+  const int n = (ntile - g + 3) / 4;  // tiles g, g + 4, ... below ntile
+  const double v = live ? surv_sum_strided(sp, n, 4 * (int64_t)T) : 0.0;
+  sm[tid] = v;
+  __syncthreads();
+  if (g == 0 && live) out[t] = ((sm[tid] + sm[tid + 64]) + sm[tid + 128]) + sm[tid + 192];
+}
+
+// The ABD_SURV_NW columns of the nw rows of wp by one workgroup of 256 threads, as 64 interleaved partial sums (rows part,
+// part + 64, ...) left in sm (256 doubles); after it, thread k < ABD_SURV_NW takes column k's sum with surv_sum_parts(sm, k).
+__device__ __forceinline__ void surv_finalize_w(const double* wp, int nw, double* sm) {
+  const int tid = threadIdx.x;
+  const int k = tid % ABD_SURV_NW, part = tid / ABD_SURV_NW;  // 64 parts: waves part, part + 64, ...
+  sm[part * ABD_SURV_NW + k] = surv_sum_strided(wp + (int64_t)part * ABD_SURV_NW + k, part < nw ? (nw - part + 63) / 64 : 0, 64 * ABD_SURV_NW);
+  __syncthreads();
+}
+
+// the 64-way sum of column k's partial sums, in ascending order
+__device__ __forceinline__ double surv_sum_parts(const double* sm, int k) {
+  double t = 0.0;
+#pragma unroll
+  for (int q = 0; q < 64; ++q) t += sm[q * ABD_SURV_NW + k];
+  return t;
+}
+
 // The fixed-order sums over tiles and waves.  Grid (ceil(T / 64) + 1, points), 256 threads.  Workgroup x < ceil(T / 64): S_t of
-// 64 intervals -- thread (g, t) adds the tiles g, g + 4, g + 8, ... in ascending order, then ((g0 + g1) + g2) + g3.  The last
-// workgroup: L and W_* over the waves as 64 interleaved partial sums and a 64-way sum.  The order depends on N and T alone.
+// 64 intervals (surv_finalize_s).  The last workgroup: L and W_* over the waves (surv_finalize_w).  The order depends on N and T
+// alone.
 __global__ __launch_bounds__(256) void abd_survival_finalize(const SurvivalArgs a) {
   __shared__ double sm[64 * ABD_SURV_NW];
   const int tid = threadIdx.x, point = blockIdx.y;
   double* out = a.out + (int64_t)point * (a.T + ABD_SURV_NW);
   if (blockIdx.x + 1 < gridDim.x) {
-    const int t = blockIdx.x * 64 + (tid & 63), g = tid >> 6;
-    const bool live = t < a.T;
-    const double* sp = a.s_part + (int64_t)point * a.ntile * a.T + (int64_t)g * a.T + (live ? t : 0);
-    const int n = (a.ntile - g + 3) / 4;  // tiles g, g + 4, ... below ntile
-    const double v = live ? surv_sum_strided(sp, n, 4 * (int64_t)a.T) : 0.0;
-    sm[tid] = v;
-    __syncthreads();
-    if (g == 0 && live) out[t] = ((sm[tid] + sm[tid + 64]) + sm[tid + 128]) + sm[tid + 192];
+    surv_finalize_s(a.s_part, point, a.ntile, a.T, blockIdx.x, sm, out);
     return;
   }
   const int nw = a.ntile * a.nseg;
-  const double* wp = a.w_part + (int64_t)point * nw * ABD_SURV_NW;
-  const int k = tid % ABD_SURV_NW, part = tid / ABD_SURV_NW;  // 64 parts: waves part, part + 64, ...
-  sm[part * ABD_SURV_NW + k] = surv_sum_strided(wp + (int64_t)part * ABD_SURV_NW + k, part < nw ? (nw - part + 63) / 64 : 0, 64 * ABD_SURV_NW);
-  __syncthreads();
-  if (tid < ABD_SURV_NW) {
-    double t = 0.0;
-#pragma unroll
-    for (int q = 0; q < 64; ++q) t += sm[q * ABD_SURV_NW + tid];
-    out[a.T + tid] = t;
-  }
+  surv_finalize_w(a.w_part + (int64_t)point * nw * ABD_SURV_NW, nw, sm);
+  if (tid < ABD_SURV_NW) out[a.T + tid] = surv_sum_parts(sm, tid);
 }
 
 }  // namespace abdi

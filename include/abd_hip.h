@@ -668,7 +668,7 @@ typedef struct abd_survival abd_survival;
 /* Checks the descriptor and every cell (ABD_ERR_ARG; before the device is touched), copies the arrays to the device. */
 int abd_survival_create(const abd_survival_desc* desc, abd_survival** out);
 int abd_survival_destroy(abd_survival* s);
-/* D = 2 K + 2 + T, or -1 for NULL. */
+/* D = 2 K + 2 + T (T + Gr + 5 for a handle of abd_survival_create_groups), or -1 for NULL. */
 int32_t abd_survival_dim(abd_survival* s);
 /* logp[n] and grad[n][D] at theta[n][D]; up to ABD_MAX_BATCH points share a launch (more are split).  A point's result is
  * the same bits alone and in any batch. */
@@ -677,6 +677,38 @@ int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, dou
  * sigma = invlogit(eta), S_t = sum_j exposure sigma, L = sum_{infected > 0} infected log sigma,
  * w = (infected - exposure lam0_t sigma)(1 - sigma), W_0 = sum w, W_k = sum w titer_k. */
 int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums);
+
+/* The survival model by group (reference survival.py:155-174: model_alone_groups): one titer, one shared slope b, and a
+ * midpoint a_g per group of individuals under a hierarchical prior,
+ *   infected[j, t] ~ Poisson(exposure[j, t] * lam0[t] * invlogit(b (titer[j, t] - a[group[j]])))
+ *   theta[D] = _lam0_raw_mu, _lam0_raw_sd_log__, __lam0_raw_z[T], a_mu, a_sd_log__, _a_z[Gr], b        D = T + Gr + 5
+ * (PyMC's creation order for this model; a_g = a_mu + exp(a_sd_log__) * _a_z_g).  The handle is an abd_survival: abd_survival_dim,
+ * _logp_dlogp, _loglik_sums and _destroy work on it.  Its loglik_sums are sums[T + 2 + Gr] = S_t[T], L, W_x, W0_g[Gr] with S_t, L
+ * and w as above, W_x = sum w titer, W0_g = sum of w over the individuals of group g. */
+#define ABD_SURVIVAL_MAX_GROUPS 256
+
+typedef struct {
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_groups;            /* Gr, 1 <= Gr <= ABD_SURVIVAL_MAX_GROUPS; a group may be empty */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const double* infected;      /* (N, T) row-major, as in abd_survival_desc */
+  const double* exposure;      /* (N, T) row-major */
+  const double* titer;         /* (N, T) row-major, finite wherever the cell is followed */
+  const int32_t* group;        /* (N), each in [0, Gr) */
+  double lam0_mu_mean;         /* _lam0_raw_mu ~ Normal(lam0_mu_mean, lam0_mu_sd): 0, 0.5 (this model passes no hyper_mu) */
+  double lam0_mu_sd;
+  double lam0_sd_rate;         /* _lam0_raw_sd ~ Exponential(lam0_sd_rate): 2 */
+  double lam0_z_sd;            /* __lam0_raw_z ~ Normal(0, lam0_z_sd): 1 */
+  double a_mu_sd;              /* a_mu ~ Normal(0, a_mu_sd): 0.5 */
+  double a_sd_rate;            /* a_sd ~ Exponential(a_sd_rate): 2 */
+  double a_z_sd;               /* _a_z ~ Normal(0, a_z_sd): 1 */
+  double b_sd;                 /* b ~ Normal(0, b_sd): 0.5 */
+} abd_survival_groups_desc;
+
+/* Checks the descriptor, every label and every cell (ABD_ERR_ARG; before the device is touched), copies the arrays to the device
+ * sorted by group. */
+int abd_survival_create_groups(const abd_survival_groups_desc* desc, abd_survival** out);
 
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).

@@ -1,9 +1,12 @@
 """
 What the survival evaluator costs: microseconds per ``logp_dlogp`` call for 1 and 4 points per launch, the wall time
 of a 1000 + 1000 x 4-chain fit of the combined model, and the NumPy restatement's time per evaluation on this host beside them,
-at N x T = 1 520 x 30 and 10 000 x 199.  Data are simulated from the model (seeded).
+at N x T = 1 520 x 30 and 10 000 x 199.  Data are simulated from the model (seeded).  ``--groups Gr [Gr]`` times the model by
+group instead, with Gr groups at every size or one Gr per size, beside the ungrouped K = 1 model on the same data in
+the same run: microseconds per call for 1 and 4 points, the tile counts, and the ratio.
 
     python tools/probe_survival.py [--out FILE] [--tune 1000] [--draws 1000] [--no_fit]
+    python tools/probe_survival.py --groups 4 8 [--out FILE]
 """
 import argparse
 import json
@@ -50,15 +53,48 @@ def per_call(fn, q, seconds=1.0):
             return 1e6 * dt / n
 
 
+def probe_groups(N, T, Gr):
+    """One row: the grouped model (labels ``j % Gr``: groups of equal size, interleaved) and the ungrouped K = 1 model on the S titer
+    of ``simulate(N, T)``, timed one after the other, twice, the smaller figure kept."""
+    y, e, xs = simulate(N, T)
+    groups = np.arange(N) % Gr
+    alone = survival.SurvivalModel(y, e, xs[:1], ("S",))
+    grouped = survival.SurvivalGroupsModel(y, e, xs[0], "S", groups)
+    rng = np.random.default_rng(1)
+    qg = np.tile(grouped.initial_point(), (4, 1)) + rng.uniform(-0.5, 0.5, size=(4, grouped.dim))
+    q1 = np.zeros((4, alone.dim))
+    q1[:, 2], q1[:, 3] = -3.0, np.log(0.5)
+    q1 += rng.uniform(-0.5, 0.5, size=q1.shape)
+    sizes = np.bincount(groups, minlength=Gr)
+    row = {"N": N, "T": T, "Gr": Gr, "dim": grouped.dim, "tiles_ungrouped": (N + 63) // 64, "tiles_grouped": int(((sizes + 63) // 64).sum())}
+    row["tile_ratio"] = row["tiles_grouped"] / row["tiles_ungrouped"]
+    for _ in range(2):
+        for name, fn, q in (("ungrouped_us_per_call_n1", alone.logp_dlogp, q1[0]), ("grouped_us_per_call_n1", grouped.logp_dlogp, qg[0]),
+                            ("ungrouped_us_per_call_n4", alone.logp_dlogp, q1), ("grouped_us_per_call_n4", grouped.logp_dlogp, qg)):
+            row[name] = min(row.get(name, np.inf), per_call(fn, q))
+    row["ratio_n1"] = row["grouped_us_per_call_n1"] / row["ungrouped_us_per_call_n1"]
+    row["ratio_n4"] = row["grouped_us_per_call_n4"] / row["ungrouped_us_per_call_n4"]
+    alone.close()
+    grouped.close()
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, nargs="+", help="time the model by group with this many groups (one figure, or one per size)")
     ap.add_argument("--out")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
     ap.add_argument("--no_fit", action="store_true")
     args = ap.parse_args(argv)
     rows = []
-    for N, T in SIZES:
+    if args.groups:
+        if len(args.groups) not in (1, len(SIZES)):
+            ap.error(f"--groups takes one figure or {len(SIZES)}")
+        for (N, T), Gr in zip(SIZES, args.groups * (len(SIZES) if len(args.groups) == 1 else 1)):
+            rows.append(probe_groups(N, T, Gr))
+            print(json.dumps(rows[-1]), flush=True)
+    for N, T in SIZES if not args.groups else ():
         y, e, xs = simulate(N, T)
         rs = R.Restatement(y, e, xs)
         model = survival.SurvivalModel(y, e, xs, ("S", "N"))
