@@ -218,6 +218,10 @@ SYMBOLS = {
     "abd_survival_dim": (C.c_int32, [_P]),
     "abd_survival_logp_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
     "abd_survival_loglik_sums": (C.c_int, [_P, _D, _D]),
+    "abd_survival_individual_loglik": (C.c_int, [_P, C.c_int32, _D, _D]),
+    "abd_survival_waic_reset": (C.c_int, [_P]),
+    "abd_survival_waic_accumulate": (C.c_int, [_P, C.c_int32, _D]),
+    "abd_survival_waic_stats": (C.c_int, [_P, _D, _D, _D, C.POINTER(C.c_int64), _I32]),
 }
 
 
@@ -1100,6 +1104,38 @@ class Survival:
         out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_loglik_sums(self._h, _ptr(t), _ptr(out)))
         return out
+
+    def _points(self, theta):
+        t = _as(theta, np.float64)
+        t = t.reshape(1, -1) if t.ndim == 1 else t
+        if t.ndim != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"theta must have shape ({self.dim},) or (n, {self.dim}), got {t.shape}")
+        return t
+
+    def individual_loglik(self, theta):
+        """``theta`` (n, D) (or (D,)) -> (n, N): every individual's Poisson log-likelihood over its intervals at every point, in
+        the caller's order of individuals; exactly 0 for an individual without a followed cell."""
+        t = self._points(theta)
+        out = np.empty((t.shape[0], self.n_inds))
+        _check(self._lib, self._lib.abd_survival_individual_loglik(self._h, t.shape[0], _ptr(t), _ptr(out)))
+        return out
+
+    def waic_reset(self):
+        _check(self._lib, self._lib.abd_survival_waic_reset(self._h))
+
+    def waic_accumulate(self, theta):
+        """Folds the draws ``theta`` (n, D), in order, into the running statistics of ``individual_loglik`` kept on the device."""
+        t = self._points(theta)
+        _check(self._lib, self._lib.abd_survival_waic_accumulate(self._h, t.shape[0], _ptr(t)))
+
+    def waic_stats(self):
+        """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of all draws folded, each (N,), and every individual's
+        number of followed cells (N,) int64."""
+        N = self.n_inds
+        lse, mean, m2, cells = np.empty(N), np.empty(N), np.empty(N), np.empty(N, np.int32)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_survival_waic_stats(self._h, _ptr(lse), _ptr(mean), _ptr(m2), C.byref(n), _ptr(cells, C.c_int32)))
+        return (lse, mean, m2, int(n.value)), cells.astype(np.int64)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

@@ -12,6 +12,8 @@
 #include "abd_survival.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
+#include "abd_survival_pointwise.hpp"
+#include "abd_survival_pointwise_terms.hpp"
 #include "abd_survival_terms.hpp"
 
 namespace abdi {
@@ -1085,6 +1087,14 @@ struct abd_survival {
   DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
   MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
   std::vector<double> work;        // log lambda, 1 - lambda of the points in flight
+  // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
+  std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
+  std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
+  std::vector<double> cj;          // [ld] C_j per slot, uploaded at the first pointwise call
+  int pw_stride = 0, pw_nab = 0;   // the pointwise parameter row: lambda[T], log lambda[T], ab[pw_nab], 1 / n_draw
+  DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
+  MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
+  int64_t waic_n = 0;              // draws folded into d_acc
   Stream stream;
 };
 
@@ -1150,6 +1160,81 @@ int survival_launch(abd_survival* s, int n, const double* theta) {
   HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, a));
   HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride * sizeof(double), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return ABD_OK;
+}
+
+// ---- the per-individual log-likelihood (abd_survival_pointwise.hpp) ----
+
+// At creation, on the host: C_j per slot and the followed cells per individual from the planes y, e [T][ld]; slot[N] is the
+// grouped layout's column of every individual (null: the individual's own index); n_ab entries follow lambda in a parameter row.
+void survival_pointwise_setup(abd_survival* s, const double* y, const double* e, const int32_t* slot, int n_ab) {
+  std::vector<int32_t> cells((size_t)s->ld);
+  s->cj.resize((size_t)s->ld);
+  survival_pointwise_constants(s->T, s->ld, y, e, s->cj.data(), cells.data());
+  if (slot) s->slot.assign(slot, slot + s->N);
+  s->n_cells.resize((size_t)s->N);
+  for (int j = 0; j < s->N; ++j) s->n_cells[j] = cells[slot ? slot[j] : j];
+  s->pw_nab = n_ab;
+  s->pw_stride = survival_pointwise_stride(s->T, n_ab);
+}
+
+// the buffers of the pointwise launches, at the first of them
+int survival_pointwise_ensure(abd_survival* s) {
+  if (s->d_ll) return ABD_OK;
+  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->ld));
+  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->ld));
+  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->ld));
+  return ABD_OK;
+}
+
+// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll.  fold: the rows go into the accumulators as draws waic_n + 1 ..
+// waic_n + n; else they are copied to s->h_ll.
+int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool fold) {
+  if (int rc = survival_pointwise_ensure(s)) return rc;
+  const int T = s->T;
+  for (int q = 0; q < n; ++q) {
+    double* par = s->h_par.host() + (size_t)q * s->par_stride;
+    double* work = s->work.data() + (size_t)q * 2 * T;
+    if (s->Gr > 0) {
+      survival_groups_prepare(T, s->Gr, theta + (size_t)q * s->D, par, work);
+    } else {
+      survival_prepare(s->K, T, theta + (size_t)q * s->D, par, work);
+    }
+    survival_pointwise_row(T, s->pw_nab, par, work, fold ? s->waic_n + q + 1 : 0, s->h_pw_par.host() + (size_t)q * s->pw_stride);
+  }
+  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalPointArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.cj = s->d_cj;
+  a.par = s->d_pw_par;
+  a.tile_group = s->d_tile_group;
+  a.ll = s->d_ll;
+  a.T = T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.par_stride = s->pw_stride;
+  a.n_ab = s->pw_nab;
+  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
+  HIP_TRY(launch_kernel(s->Gr > 0   ? abd_survival_individual_kernel<0>
+                        : s->K == 2 ? abd_survival_individual_kernel<2>
+                                    : abd_survival_individual_kernel<1>,
+                        grid, dim3(256), 0, s->stream, a));
+  if (fold) {
+    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->ld, s->stream));
+    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_ll,
+                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->ld, (int32_t)s->pw_stride,
+                          (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
+  } else {
+    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (fold) s->waic_n += n;
   return ABD_OK;
 }
 
@@ -1227,6 +1312,7 @@ int survival_create(const abd_survival_desc* d, abd_survival** out) {
   s->par_stride = T + 2 * K;
   s->out_stride = T + ABD_SURV_NW;
   s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  survival_pointwise_setup(s, y.data(), e.data(), nullptr, 2 * K);
   if (d->device >= 0) {
     s->device = d->device;
   } else {
@@ -1318,6 +1404,7 @@ int survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out
   s->par_stride = T + Gr + 1;
   s->out_stride = T + 2 + Gr;
   s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  survival_pointwise_setup(s, y.data(), e.data(), slot.data(), Gr + 1);
   if (d->device >= 0) {
     s->device = d->device;
   } else {
@@ -1375,6 +1462,58 @@ int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums)
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = survival_launch(s, 1, theta)) return rc;
   std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + (s->Gr > 0 ? s->Gr : s->K)) * sizeof(double));
+  return ABD_OK;
+}
+
+int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* theta, double* ll) {
+  if (!s || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  const int32_t* slot = s->slot.empty() ? nullptr : s->slot.data();
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->D, false)) return rc;
+    for (int q = 0; q < nb; ++q) {  // slots to the caller's order
+      const double* row = s->h_ll.host() + (size_t)q * s->ld;
+      double* out = ll + ((size_t)k0 + q) * s->N;
+      for (int j = 0; j < s->N; ++j) out[j] = row[slot ? slot[j] : j];
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_waic_reset(abd_survival* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  s->waic_n = 0;  // the first draw folded overwrites its column: the accumulators need no clearing
+  return ABD_OK;
+}
+
+int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta) {
+  if (!s || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
+    if (int rc = survival_pointwise_launch(s, std::min(ABD_MAX_BATCH, n - k0), theta + (size_t)k0 * s->D, true)) return rc;
+  return ABD_OK;
+}
+
+int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
+  if (!s || !lse || !mean || !m2 || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
+  if (s->waic_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_waic_accumulate comes first)");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t ld = (size_t)s->ld;
+  if (!s->h_acc.host()) HIP_TRY(s->h_acc.alloc_pinned(4 * ld));
+  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, 4 * ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const double* acc = s->h_acc.host();
+  for (int j = 0; j < s->N; ++j) {
+    const size_t c = s->slot.empty() ? (size_t)j : (size_t)s->slot[j];
+    lse[j] = acc[c] + std::log(acc[ld + c]);  // M + log S
+    mean[j] = acc[2 * ld + c];
+    m2[j] = acc[3 * ld + c];
+    n_cells[j] = s->n_cells[j];
+  }
+  *n_draws = s->waic_n;
   return ABD_OK;
 }
 

@@ -11,8 +11,14 @@ models; ``protection`` is what ``plotting.plot_protection`` draws.  ``model_alon
 own midpoint ``a`` under a hierarchical prior, with one slope ``b`` (``abd_survival_create_groups``).  Per-draw
 (non-plug-in) fits are not here.
 
-    python -m abdpymc_amd.survival --posterior FILE --ititers_data DIR --start S --end E --model s|n|combined --out FILE
+Which titer predicts protection?  ``waic(model, fit)`` scores a fitted model by WAIC over the individuals -- the device gives every
+individual's log-likelihood at every draw and keeps the running statistics (``abd_survival_individual_loglik``,
+``abd_survival_waic_*``) -- and ``compare({"S": fit_s, "N": fit_n, ...})`` ranks the fits of one cohort and window
+with paired standard errors (``compare.compare``).
+
+    python -m abdpymc_amd.survival --posterior FILE --ititers_data DIR --start S --end E --model s|n|combined --out FILE [--waic]
     python -m abdpymc_amd.survival ... --model s_groups|n_groups --groups FILE [--group_name NAME]
+    python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz
 """
 from __future__ import annotations
 
@@ -23,6 +29,7 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
+from . import compare as _compare
 from . import risk
 from .sampler import DualAveraging, Nuts
 from .summaries import interval
@@ -75,6 +82,7 @@ class SurvivalModel:
         self.K = len(titers)
         self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
         self._dev = Survival(infected, exposure, titers, self.priors, device=device)
+        self.n_cells = followed_cells(infected, exposure)
         self.T = self._dev.n_intervals
         self.dim = self._dev.dim
         ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
@@ -86,11 +94,33 @@ class SurvivalModel:
     def loglik_sums(self, q):
         return self._dev.loglik_sums(q)
 
+    def individual_loglik(self, q):
+        """(n, D) -> (n, N): every individual's log-likelihood over its intervals at every point (0 without a followed cell)."""
+        return self._dev.individual_loglik(q)
+
+    def waic_reset(self):
+        self._dev.waic_reset()
+
+    def waic_accumulate(self, q):
+        """Folds the draws ``q`` (n, D), in order, into the statistics of ``individual_loglik`` that the device keeps."""
+        self._dev.waic_accumulate(q)
+
+    def waic_stats(self):
+        """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
+        return self._dev.waic_stats()
+
     def constrain(self, q) -> Dict[str, np.ndarray]:
         return constrain(q, self.K)
 
     def close(self):
         self._dev.close()
+
+
+def followed_cells(infected, exposure) -> np.ndarray:
+    """(N,) int64: every individual's number of followed cells, exposure > 0 (NaN in either array: no follow-up)."""
+    y, e = np.asarray(infected, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return ((e > 0) & ~np.isnan(y)).sum(axis=1).astype(np.int64)
 
 
 def constrain(q, K: int) -> Dict[str, np.ndarray]:
@@ -158,6 +188,7 @@ class SurvivalGroupsModel:
             raise ValueError(f"{self.Gr} groups: at most {SURVIVAL_MAX_GROUPS}")
         self.priors = PRIORS_GROUPS if priors is None else tuple(float(v) for v in priors)
         self._dev = SurvivalGroups(infected, exposure, titer, self.group_index, self.Gr, self.priors, device=device)
+        self.n_cells = followed_cells(infected, exposure)
         self.T = self._dev.n_intervals
         self.dim = self._dev.dim
         self.names = names_groups(self.T, self.Gr)
@@ -167,6 +198,21 @@ class SurvivalGroupsModel:
 
     def loglik_sums(self, q):
         return self._dev.loglik_sums(q)
+
+    def individual_loglik(self, q):
+        """(n, D) -> (n, N): every individual's log-likelihood over its intervals at every point (0 without a followed cell)."""
+        return self._dev.individual_loglik(q)
+
+    def waic_reset(self):
+        self._dev.waic_reset()
+
+    def waic_accumulate(self, q):
+        """Folds the draws ``q`` (n, D), in order, into the statistics of ``individual_loglik`` that the device keeps."""
+        self._dev.waic_accumulate(q)
+
+    def waic_stats(self):
+        """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
+        return self._dev.waic_stats()
 
     def constrain(self, q) -> Dict[str, np.ndarray]:
         return constrain_groups(q, self.T, self.Gr)
@@ -199,7 +245,7 @@ class SurvivalAnalysis:
         if antigen not in ("S", "N"):
             raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
         titer = self.s_titer if antigen == "S" else self.n_titer
-        return SurvivalModel(self.infected, self.exposure, [titer], (antigen,), device=self.device)
+        return self._windowed(SurvivalModel(self.infected, self.exposure, [titer], (antigen,), device=self.device))
 
     def model_alone_groups(self, antigen: str, groups, group_name: str = "group") -> SurvivalGroupsModel:
         """The reference's ``model_alone_groups``: ``groups`` holds one label per individual (any sortable values); the model's
@@ -207,10 +253,14 @@ class SurvivalAnalysis:
         if antigen not in ("S", "N"):
             raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
         titer = self.s_titer if antigen == "S" else self.n_titer
-        return SurvivalGroupsModel(self.infected, self.exposure, titer, antigen, groups, group_name, device=self.device)
+        return self._windowed(SurvivalGroupsModel(self.infected, self.exposure, titer, antigen, groups, group_name, device=self.device))
 
     def model_combined(self) -> SurvivalModel:
-        return SurvivalModel(self.infected, self.exposure, [self.s_titer, self.n_titer], ("S", "N"), device=self.device)
+        return self._windowed(SurvivalModel(self.infected, self.exposure, [self.s_titer, self.n_titer], ("S", "N"), device=self.device))
+
+    def _windowed(self, model):
+        model.start, model.end = self.start, self.end  # what ``waic`` records in a fit, and ``compare`` checks
+        return model
 
 
 def _chain(fn: Callable, dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8,
@@ -279,6 +329,88 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
         res["groups"] = np.asarray(model.groups)
         res["group_name"] = np.array(getattr(model, "group_name", "group"))
     return res
+
+
+WAIC_FIT_KEYS = ("elpd_waic_ind", "p_waic_ind", "waic_n_cells", "waic_n_draws")  # what ``waic`` records in a fit
+
+
+def fit_points(model, fit) -> np.ndarray:
+    """(chains x draws, D): the unconstrained points of a fit under ``model.names``, chain after chain."""
+    q = np.stack([np.asarray(fit[name], dtype=np.float64) for name in model.names], axis=-1)
+    return np.ascontiguousarray(q.reshape(-1, q.shape[-1]))
+
+
+def waic(model, fit, pointwise: Optional[Callable] = None) -> Dict[str, object]:
+    """WAIC by individual of a fitted survival model over all draws of ``fit``: ``compare.waic_from_individual_stats`` of the
+    statistics the device accumulates (``model.waic_reset`` / ``waic_accumulate`` / ``waic_stats``), the draws folded chain after
+    chain.  ``elpd_i`` / ``p_waic_i`` have one entry per individual, an exact 0 without follow-up; ``n_readings_i`` holds the
+    followed cells.  The entries ``WAIC_FIT_KEYS`` (and ``start`` / ``end`` where the model knows its window) are recorded in
+    ``fit``: ``write`` stores them and ``compare`` reads them.
+    ``pointwise``: a host callable (n, D) -> (n, N) in the device's place (tests); the model then needs ``names`` and ``n_cells``."""
+    q = fit_points(model, fit)
+    if pointwise is not None:
+        stats, n_cells = _compare.stats_from_matrix(np.asarray(pointwise(q), dtype=np.float64)), np.asarray(model.n_cells)
+    else:
+        model.waic_reset()
+        model.waic_accumulate(q)
+        stats, n_cells = model.waic_stats()
+    w = _compare.waic_from_individual_stats(stats, n_cells)
+    fit["elpd_waic_ind"], fit["p_waic_ind"] = w["elpd_i"], w["p_waic_i"]
+    fit["waic_n_cells"], fit["waic_n_draws"] = w["n_readings_i"], np.array(w["n_draws"], dtype=np.int64)
+    for k in ("start", "end"):
+        if hasattr(model, k):
+            fit[k] = np.array(getattr(model, k), dtype=np.int64)
+    return w
+
+
+def waic_of_fit(fit) -> Dict[str, object]:
+    """The dictionary of ``waic`` again from the entries it recorded in a fit (or that ``write`` stored)."""
+    lacking = [k for k in WAIC_FIT_KEYS if k not in fit]
+    if lacking:
+        raise ValueError(f"no WAIC in the fit (waic(model, fit), or --waic): {lacking} missing")
+    elpd_i, p_waic_i = np.asarray(fit["elpd_waic_ind"], dtype=np.float64), np.asarray(fit["p_waic_ind"], dtype=np.float64)
+    n_cells = np.asarray(fit["waic_n_cells"], dtype=np.int64)
+    has = n_cells > 0
+    m = int(has.sum())
+    return dict(elpd_waic=float(elpd_i.sum()), p_waic=float(p_waic_i.sum()), se=float(np.sqrt(m * np.var(elpd_i[has]))) if m else 0.0,
+                elpd_i=elpd_i, p_waic_i=p_waic_i, n_warn=int((p_waic_i > _compare.WARN_P_WAIC).sum()),
+                n_draws=int(np.asarray(fit["waic_n_draws"])), n_readings=int(n_cells.sum()), n_individuals=m, n_readings_i=n_cells)
+
+
+def compare(fits) -> Dict[str, Dict[str, float]]:
+    """Rank fitted survival models of ONE cohort and window by elpd_waic: ``compare.compare`` (rank, elpd_waic, p_waic, se,
+    elpd_diff, dse over the followed individuals) of ``{name: fit}``, every fit with the entries of ``waic``.  Fits that differ
+    in ``start`` / ``end``, in the number of individuals or in which of them are followed are a ``ValueError`` that names the
+    odd ones out."""
+    w, window = {}, {}
+    for name, fit in fits.items():
+        try:
+            w[name] = waic_of_fit(fit)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        span = tuple(int(np.asarray(fit[k])) if k in fit else None for k in ("start", "end"))
+        window[name] = (span, w[name]["elpd_i"].size, (w[name]["n_readings_i"] > 0).tobytes())
+    kinds = list(window.values())
+    usual = max(kinds, key=kinds.count)  # the first of the most frequent
+    odd = [name for name, k in window.items() if k != usual]
+    if odd:
+        what = [("start / end", 0), ("the number of individuals", 1), ("which individuals are followed", 2)]
+        raise ValueError("; ".join(f"{name} differs from the others in " + ", ".join(t for t, i in what if window[name][i] != usual[i])
+                                   + (f" (start {window[name][0][0]}, end {window[name][0][1]} against {usual[0][0]}, {usual[0][1]})"
+                                      if window[name][0] != usual[0] else "") for name in odd))
+    return _compare.compare(w, by="individual")
+
+
+def waic_line(w) -> str:
+    return (f"survival WAIC: elpd_waic {w['elpd_waic']:.3f}  p_waic {w['p_waic']:.3f}  se {w['se']:.3f}  ({w['n_individuals']} individuals, "
+            f"{w['n_draws']} draws; {w['n_warn']} with p_waic_j > 0.4)")
+
+
+def compare_lines(table) -> list:
+    """One row per model of ``compare``'s table, best first."""
+    width = max(len(str(name)) for name in table)
+    return [f"{str(name):<{width}}  rank {v['rank']}  elpd_waic {v['elpd_waic']:.3f}  p_waic {v['p_waic']:.3f}  se {v['se']:.3f}  "
+            f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}" for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
 
 
 def protection(res, x, antigen: Optional[str] = None, prob: float = 0.95, group=None) -> Dict[str, np.ndarray]:
@@ -397,21 +529,30 @@ def read_groups(path: str, n_inds: int) -> np.ndarray:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m abdpymc_amd.survival", description="Fit a survival model of a finished run.  Prints one line on stdout: medians and intervals of a and b, "
-                                 "the protection at titers 0, 2 and 4, the largest R-hat of a and b.")
-    ap.add_argument("--posterior", required=True, help="A posterior .npz of abdpymc-infer (mean_i, mean_ab_s_mu, mean_ab_n_mu, or draws).")
-    ap.add_argument("--ititers_data", required=True, help="The cohort directory the run was made from.")
-    ap.add_argument("--start", type=int, required=True, help="First gap of the analysis (titers from here).")
-    ap.add_argument("--end", type=int, required=True, help="One past the last gap of the analysis.")
+                                 "the protection at titers 0, 2 and 4, the largest R-hat of a and b.  With --compare: rank fits written with --waic.")
+    ap.add_argument("--compare", nargs="+", metavar="FIT", help="Rank these fits of one cohort and window (.npz written with --waic) by WAIC over the "
+                    "individuals: one row per model on stdout (rank, elpd_waic, p_waic, se, elpd_diff, dse).  Needs neither a cohort nor a GPU.")
+    ap.add_argument("--posterior", help="A posterior .npz of abdpymc-infer (mean_i, mean_ab_s_mu, mean_ab_n_mu, or draws).")
+    ap.add_argument("--ititers_data", help="The cohort directory the run was made from.")
+    ap.add_argument("--start", type=int, help="First gap of the analysis (titers from here).")
+    ap.add_argument("--end", type=int, help="One past the last gap of the analysis.")
     ap.add_argument("--model", choices=("s", "n", "combined", "s_groups", "n_groups"), default="combined")
     ap.add_argument("--groups", help="With --model s_groups / n_groups: a .npy or text file, one label per individual in cohort order.")
     ap.add_argument("--group_name", default="group", help="What the labels of --groups are (the reference's coordinate name).")
-    ap.add_argument("--out", required=True, help="Output file (.npz; NetCDF where ArviZ imports and the name does not end in .npz).")
+    ap.add_argument("--out", help="Output file (.npz; NetCDF where ArviZ imports and the name does not end in .npz).")
+    ap.add_argument("--waic", action="store_true", help="Score the fit by WAIC over the individuals on the device: a second line on stdout, and "
+                    "elpd_waic_ind, p_waic_ind, waic_n_cells, waic_n_draws, start, end in the output (what --compare reads).")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
     ap.add_argument("--chains", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=-1)
     args = ap.parse_args(argv)
+    if args.compare:
+        return _main_compare(args.compare)
+    missing = [f"--{k}" for k in ("posterior", "ititers_data", "start", "end", "out") if getattr(args, k) is None]
+    if missing:
+        ap.error("the following arguments are required: " + ", ".join(missing))
     from .data import TiterData
 
     data = TiterData.from_disk(args.ititers_data)
@@ -426,24 +567,50 @@ def main(argv=None) -> int:
     except ValueError as e:
         raise SystemExit(f"survival: {e}")
     res = sample(model, tune=args.tune, draws=args.draws, chains=args.chains, seed=args.seed)
+    w = waic(model, res) if args.waic else None
     model.close()
     print(report_line(res))  # the one line, on stdout; progress and the file's name go to stderr
+    if w is not None:
+        print(waic_line(w))  # --waic: and this one
     out = write(res, args.out, sa)
     print(f"wrote {out}", file=sys.stderr)
     return 0
 
 
+def _main_compare(paths) -> int:
+    import os
+
+    fits = {}
+    for path in paths:
+        name = os.path.splitext(os.path.basename(str(path)))[0]
+        if name in fits:
+            raise SystemExit(f"survival: two fits are called {name}")
+        with np.load(path, allow_pickle=False) as f:
+            fits[name] = {k: f[k] for k in WAIC_FIT_KEYS + ("start", "end") if k in f.files}
+    try:
+        table = compare(fits)
+    except ValueError as e:
+        raise SystemExit(f"survival: {e}")
+    for line in compare_lines(table):
+        print(line)
+    return 0
+
+
 def write(res, path: str, sa: "SurvivalAnalysis") -> str:
     """``.npz``; NetCDF through ``cli.write_posterior`` where ArviZ imports and the name does not end in ``.npz`` (no test covers
-    that branch: ArviZ is optional and the suite does not require it)."""
+    that branch: ArviZ is optional and the suite does not require it).  A fit that ``waic`` has scored is stored with its
+    ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` and the window ``start`` / ``end`` -- in the ``.npz`` form,
+    which is what ``--compare`` reads; the NetCDF form holds the draws alone."""
     path = str(path)
+    if "elpd_waic_ind" in res:
+        res = dict(res, start=np.array(sa.start, dtype=np.int64), end=np.array(sa.end, dtype=np.int64))
     if not path.endswith(".npz"):
         try:
             import arviz  # noqa: F401
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name")}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "start", "end") + WAIC_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

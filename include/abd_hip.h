@@ -710,6 +710,21 @@ typedef struct {
  * sorted by group. */
 int abd_survival_create_groups(const abd_survival_groups_desc* desc, abd_survival** out);
 
+/* The per-individual log-likelihood of a handle of either kind, for comparing fitted models of one cohort (WAIC by individual):
+ *   ll[p][j] = sum_t log Poisson(infected[j, t] | exposure[j, t] * lam0[t] * invlogit(eta[j, t]))
+ * at theta[n][D] in the handle's layout, with PyMC's convention for fractional infected
+ * (y log mu - mu - lgamma(y + 1), a cell with y = 0 has no log term).  ll is (n, N) row-major in the caller's order of
+ * individuals, also for a grouped handle; an individual without a followed cell gets exactly 0.  Any n: up to ABD_MAX_BATCH
+ * points share a launch.  A point's row is the same bits alone and in any batch; sum_j ll[p][j] is the data part of logp. */
+int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* theta, double* ll);
+/* Running statistics of ll[.][j] over draws, kept on the device.  _accumulate folds the n draws of theta[n][D] in order (any n;
+ * the result does not depend on how the draws are split over calls); _reset forgets all draws; _stats reads, in the caller's
+ * order of individuals, lse[N] = log sum_draws exp(ll), mean[N], m2[N] = sum_draws (ll - mean)^2, the number of draws folded and
+ * n_cells[N], every individual's number of followed cells (exposure > 0).  _stats before any _accumulate is ABD_ERR_ARG. */
+int abd_survival_waic_reset(abd_survival* s);
+int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta);
+int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells);
+
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).
  * This table is complete: the product library calls getenv for nothing else (development knobs of launch shapes

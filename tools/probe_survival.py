@@ -5,8 +5,13 @@ at N x T = 1 520 x 30 and 10 000 x 199.  Data are simulated from the model (seed
 group instead, with Gr groups at every size or one Gr per size, beside the ungrouped K = 1 model on the same data in
 the same run: microseconds per call for 1 and 4 points, the tile counts, and the ratio.
 
+``--leg waic`` times what scoring a fit costs: ``waic_accumulate`` of ``--points`` jittered points of the combined model
+(launches of 16, a host clock around calls that end in a synchronise) beside ``logp_dlogp`` at one point per call on the same
+handle, alternating, ``--reps`` times; per repeat and at its best, microseconds per draw, per single-point evaluation, the ratio.
+
     python tools/probe_survival.py [--out FILE] [--tune 1000] [--draws 1000] [--no_fit]
     python tools/probe_survival.py --groups 4 8 [--out FILE]
+    python tools/probe_survival.py --leg waic [--points 4000] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -79,8 +84,40 @@ def probe_groups(N, T, Gr):
     return row
 
 
+def probe_waic(N, T, points, reps):
+    """One row: ``waic_accumulate`` of ``points`` draws against ``logp_dlogp`` at one point per call, on one handle of the combined
+    model of ``simulate(N, T)``."""
+    y, e, xs = simulate(N, T)
+    model = survival.SurvivalModel(y, e, xs, ("S", "N"))
+    rng = np.random.default_rng(1)
+    q = np.zeros((points, model.dim))
+    q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+    q += rng.uniform(-0.5, 0.5, size=q.shape)
+    row = {"N": N, "T": T, "K": 2, "points": points, "launches": (points + 15) // 16, "waves_per_launch": ((N + 63) // 64) * min(16, points),
+           "accumulate_us_per_draw": [], "logp_dlogp_us_per_call_n1": []}
+    model.waic_accumulate(q[:64])  # warm up: the buffers of the first call, the code objects
+    model.logp_dlogp(q[0])
+    for _ in range(reps):
+        model.waic_reset()
+        t0 = time.perf_counter()
+        model.waic_accumulate(q)
+        row["accumulate_us_per_draw"].append(1e6 * (time.perf_counter() - t0) / points)
+        row["logp_dlogp_us_per_call_n1"].append(per_call(model.logp_dlogp, q[0]))
+    (lse, mean, m2, n), cells = model.waic_stats()
+    w = survival.waic(model, {name: q[None, :, k] for k, name in enumerate(model.names)})
+    row["n_draws"], row["elpd_waic"], row["p_waic"] = n, w["elpd_waic"], w["p_waic"]
+    row["best_accumulate_us_per_draw"] = min(row["accumulate_us_per_draw"])
+    row["best_logp_dlogp_us_per_call_n1"] = min(row["logp_dlogp_us_per_call_n1"])
+    row["draw_over_single_evaluation"] = row["best_accumulate_us_per_draw"] / row["best_logp_dlogp_us_per_call_n1"]
+    model.close()
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", choices=("eval", "waic"), default="eval", help="eval: the evaluator and a fit (the default); waic: scoring a fit")
+    ap.add_argument("--points", type=int, default=4000, help="--leg waic: draws folded per repeat")
+    ap.add_argument("--reps", type=int, default=3, help="--leg waic: repeats")
     ap.add_argument("--groups", type=int, nargs="+", help="time the model by group with this many groups (one figure, or one per size)")
     ap.add_argument("--out")
     ap.add_argument("--tune", type=int, default=1000)
@@ -88,13 +125,17 @@ def main(argv=None):
     ap.add_argument("--no_fit", action="store_true")
     args = ap.parse_args(argv)
     rows = []
+    if args.leg == "waic":
+        for N, T in SIZES:
+            rows.append(probe_waic(N, T, args.points, args.reps))
+            print(json.dumps(rows[-1]), flush=True)
     if args.groups:
         if len(args.groups) not in (1, len(SIZES)):
             ap.error(f"--groups takes one figure or {len(SIZES)}")
         for (N, T), Gr in zip(SIZES, args.groups * (len(SIZES) if len(args.groups) == 1 else 1)):
             rows.append(probe_groups(N, T, Gr))
             print(json.dumps(rows[-1]), flush=True)
-    for N, T in SIZES if not args.groups else ():
+    for N, T in SIZES if not args.groups and args.leg == "eval" else ():
         y, e, xs = simulate(N, T)
         rs = R.Restatement(y, e, xs)
         model = survival.SurvivalModel(y, e, xs, ("S", "N"))
