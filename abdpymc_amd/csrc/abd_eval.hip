@@ -1,7 +1,5 @@
 // abd_eval.hip -- evaluation launches of the C ABI (include/abd_hip.h): the dense-panel and observation-list kernels,
 // the pipes (HIP streams) stream-ordered launches rotate over, completion tags in mapped host memory, device timing.
-#include <memory>
-
 #include "abd_host.hpp"
 #include "abd_fuse_plan.hpp"
 #include "abd_eval_kernels.hpp"
@@ -9,12 +7,6 @@
 #include "abd_readings.hpp"
 #include "abd_individual.hpp"
 #include "abd_simulate.hpp"
-#include "abd_survival.hpp"
-#include "abd_survival_groups.hpp"
-#include "abd_survival_groups_terms.hpp"
-#include "abd_survival_pointwise.hpp"
-#include "abd_survival_pointwise_terms.hpp"
-#include "abd_survival_terms.hpp"
 
 namespace abdi {
 
@@ -1068,452 +1060,6 @@ int abd_simulate_staged(abd_ctx* c, const abd_sim_params* par, const double* lam
     if (rc) return rc;
     HIP_TRY(se);
   }
-  return ABD_OK;
-}
-
-}  // extern "C"
-
-// ---- the survival models of a finished run (abd_survival.hpp, abd_survival_terms.hpp) ----
-
-struct abd_survival {
-  int N = 0, T = 0, K = 0, D = 0, device = 0;
-  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0, par_stride = 0, out_stride = 0;
-  int Gr = 0;  // > 0: the model by group (abd_survival_groups.hpp), K = 1
-  SurvivalPriors priors{};
-  SurvivalGroupsPriors gpriors{};
-  DevBuf<int32_t> d_tile_group, d_group_tile;
-  std::vector<double> Y;  // Y_t = sum_j y_jt
-  double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
-  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
-  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
-  std::vector<double> work;        // log lambda, 1 - lambda of the points in flight
-  // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
-  std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
-  std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
-  std::vector<double> cj;          // [ld] C_j per slot, uploaded at the first pointwise call
-  int pw_stride = 0, pw_nab = 0;   // the pointwise parameter row: lambda[T], log lambda[T], ab[pw_nab], 1 / n_draw
-  DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
-  MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
-  int64_t waic_n = 0;              // draws folded into d_acc
-  Stream stream;
-};
-
-namespace abdi {
-namespace {
-
-// the sums of n <= ABD_MAX_BATCH points into s->h_out (rows of out_stride)
-int survival_groups_launch(abd_survival* s, int n, const double* theta) {
-  const int T = s->T, Gr = s->Gr;
-  for (int q = 0; q < n; ++q)
-    survival_groups_prepare(T, Gr, theta + (size_t)q * s->D, s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * T);
-  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->par_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  SurvivalGroupsArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.x = s->d_x0;
-  a.par = s->d_par;
-  a.tile_group = s->d_tile_group;
-  a.group_tile = s->d_group_tile;
-  a.s_part = s->d_s_part;
-  a.w_part = s->d_w_part;
-  a.out = s->d_out;
-  a.T = T;
-  a.Gr = Gr;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
-  a.nseg = s->nseg;
-  a.seg_len = s->seg_len;
-  a.par_stride = s->par_stride;
-  HIP_TRY(launch_kernel(abd_survival_groups_kernel, dim3((unsigned)((s->nw + 3) / 4), (unsigned)n), dim3(256), 0, s->stream, a));
-  HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (Gr + 3) / 4), (unsigned)n), dim3(256), 0,
-                        s->stream, a));
-  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return ABD_OK;
-}
-
-int survival_launch(abd_survival* s, int n, const double* theta) {
-  if (s->Gr > 0) return survival_groups_launch(s, n, theta);
-  const int T = s->T, K = s->K;
-  for (int q = 0; q < n; ++q)
-    survival_prepare(K, T, theta + (size_t)q * s->D, s->h_par.host() + (size_t)q * s->par_stride, s->work.data() + (size_t)q * 2 * T);
-  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->par_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  SurvivalArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.x0 = s->d_x0;
-  a.x1 = s->d_x1;
-  a.par = s->d_par;
-  a.s_part = s->d_s_part;
-  a.w_part = s->d_w_part;
-  a.out = s->d_out;
-  a.T = T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
-  a.nseg = s->nseg;
-  a.seg_len = s->seg_len;
-  a.par_stride = s->par_stride;
-  const dim3 grid((unsigned)((s->nw + 3) / 4), (unsigned)n);
-  HIP_TRY(launch_kernel(K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, grid, dim3(256), 0, s->stream, a));
-  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, a));
-  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return ABD_OK;
-}
-
-// ---- the per-individual log-likelihood (abd_survival_pointwise.hpp) ----
-
-// At creation, on the host: C_j per slot and the followed cells per individual from the planes y, e [T][ld]; slot[N] is the
-// grouped layout's column of every individual (null: the individual's own index); n_ab entries follow lambda in a parameter row.
-void survival_pointwise_setup(abd_survival* s, const double* y, const double* e, const int32_t* slot, int n_ab) {
-  std::vector<int32_t> cells((size_t)s->ld);
-  s->cj.resize((size_t)s->ld);
-  survival_pointwise_constants(s->T, s->ld, y, e, s->cj.data(), cells.data());
-  if (slot) s->slot.assign(slot, slot + s->N);
-  s->n_cells.resize((size_t)s->N);
-  for (int j = 0; j < s->N; ++j) s->n_cells[j] = cells[slot ? slot[j] : j];
-  s->pw_nab = n_ab;
-  s->pw_stride = survival_pointwise_stride(s->T, n_ab);
-}
-
-// the buffers of the pointwise launches, at the first of them
-int survival_pointwise_ensure(abd_survival* s) {
-  if (s->d_ll) return ABD_OK;
-  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->ld));
-  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->ld));
-  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->ld));
-  return ABD_OK;
-}
-
-// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll.  fold: the rows go into the accumulators as draws waic_n + 1 ..
-// waic_n + n; else they are copied to s->h_ll.
-int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool fold) {
-  if (int rc = survival_pointwise_ensure(s)) return rc;
-  const int T = s->T;
-  for (int q = 0; q < n; ++q) {
-    double* par = s->h_par.host() + (size_t)q * s->par_stride;
-    double* work = s->work.data() + (size_t)q * 2 * T;
-    if (s->Gr > 0) {
-      survival_groups_prepare(T, s->Gr, theta + (size_t)q * s->D, par, work);
-    } else {
-      survival_prepare(s->K, T, theta + (size_t)q * s->D, par, work);
-    }
-    survival_pointwise_row(T, s->pw_nab, par, work, fold ? s->waic_n + q + 1 : 0, s->h_pw_par.host() + (size_t)q * s->pw_stride);
-  }
-  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  SurvivalPointArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.x0 = s->d_x0;
-  a.x1 = s->d_x1;
-  a.cj = s->d_cj;
-  a.par = s->d_pw_par;
-  a.tile_group = s->d_tile_group;
-  a.ll = s->d_ll;
-  a.T = T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
-  a.par_stride = s->pw_stride;
-  a.n_ab = s->pw_nab;
-  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
-  HIP_TRY(launch_kernel(s->Gr > 0   ? abd_survival_individual_kernel<0>
-                        : s->K == 2 ? abd_survival_individual_kernel<2>
-                                    : abd_survival_individual_kernel<1>,
-                        grid, dim3(256), 0, s->stream, a));
-  if (fold) {
-    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->ld, s->stream));
-    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_ll,
-                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->ld, (int32_t)s->pw_stride,
-                          (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
-  } else {
-    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (fold) s->waic_n += n;
-  return ABD_OK;
-}
-
-}  // namespace
-}  // namespace abdi
-
-extern "C" {
-
-namespace {
-int survival_create(const abd_survival_desc* d, abd_survival** out);
-}
-
-int abd_survival_create(const abd_survival_desc* d, abd_survival** out) {
-  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  try {
-    return survival_create(d, out);
-  } catch (const std::bad_alloc&) {  // the host copies of the planes: nothing may be thrown across the C ABI
-    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
-  }
-}
-
-namespace {
-int survival_create(const abd_survival_desc* d, abd_survival** out) {
-  const int K = d->n_titers;
-  if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
-  if (d->n_inds < 1) return fail(ABD_ERR_ARG, "n_inds=%d must be >= 1", d->n_inds);
-  if (d->n_intervals < 1 || d->n_intervals > ABD_MAX_GAPS - 1)
-    return fail(ABD_ERR_ARG, "n_intervals=%d outside [1, %d]", d->n_intervals, ABD_MAX_GAPS - 1);
-  if (!d->infected || !d->exposure || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
-  const double pos[4] = {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
-  for (double v : pos)
-    if (!(v > 0.0) || !std::isfinite(v)) return fail(ABD_ERR_ARG, "ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd must be positive and finite, got %g", v);
-  if (!std::isfinite(d->lam0_mu_mean)) return fail(ABD_ERR_ARG, "lam0_mu_mean must be finite, got %g", d->lam0_mu_mean);
-  const int N = d->n_inds, T = d->n_intervals;
-  const int ntile = (N + 63) / 64;
-  const size_t ld = (size_t)ntile * 64, plane = ld * (size_t)T;
-  // [interval][individual] planes, padded with cells that have no follow-up
-  std::vector<double> y(plane, 0.0), e(plane, 0.0), x0(plane, 0.0), x1(K == 2 ? plane : 0, 0.0);
-  std::vector<SurvivalSum> Ysum((size_t)T);
-  SurvivalSum Csum;
-  for (int j = 0; j < N; ++j)
-    for (int t = 0; t < T; ++t) {
-      const size_t src = (size_t)j * T + t, dst = (size_t)t * ld + j;
-      double yy = d->infected[src], ee = d->exposure[src], xx[2] = {d->titer[0][src], K == 2 ? d->titer[1][src] : 0.0};
-      if (const char* msg = survival_check_cell(K, yy, ee, xx)) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", j, t, msg);
-      y[dst] = yy;
-      e[dst] = ee;
-      x0[dst] = xx[0];
-      if (K == 2) x1[dst] = xx[1];
-      Ysum[t].add(yy);
-      if (yy > 0.0) Csum.add(yy * std::log(ee));
-      Csum.add(-std::lgamma(yy + 1.0));
-    }
-  std::vector<double> Y((size_t)T);
-  for (int t = 0; t < T; ++t) Y[t] = Ysum[t].value();
-  const double C = Csum.value();
-  abd_survival* s = new (std::nothrow) abd_survival;
-  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
-  std::unique_ptr<abd_survival> own(s);
-  s->N = N;
-  s->T = T;
-  s->K = K;
-  s->D = survival_dim(K, T);
-  s->priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
-  s->Y = std::move(Y);
-  s->C = C;
-  s->ld = (int)ld;
-  s->ntile = ntile;
-  // ranges of intervals: enough waves for the chip (about 4096) while a wave keeps at least one interval; from N and T alone
-  const int want_seg = std::max(1, std::min(T, (4096 + ntile - 1) / ntile));
-  s->seg_len = (T + want_seg - 1) / want_seg;
-  s->nseg = (T + s->seg_len - 1) / s->seg_len;
-  s->nw = s->ntile * s->nseg;
-  s->par_stride = T + 2 * K;
-  s->out_stride = T + ABD_SURV_NW;
-  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
-  survival_pointwise_setup(s, y.data(), e.data(), nullptr, 2 * K);
-  if (d->device >= 0) {
-    s->device = d->device;
-  } else {
-    HIP_TRY(hipGetDevice(&s->device));
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(s->stream.create());
-  HIP_TRY(s->d_y.upload(y.data(), plane));
-  HIP_TRY(s->d_e.upload(e.data(), plane));
-  HIP_TRY(s->d_x0.upload(x0.data(), plane));
-  if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), plane));
-  HIP_TRY(s->d_par.alloc((size_t)ABD_MAX_BATCH * s->par_stride));
-  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
-  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
-  HIP_TRY(s->d_out.alloc((size_t)ABD_MAX_BATCH * s->out_stride));
-  HIP_TRY(s->h_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->par_stride));
-  HIP_TRY(s->h_out.alloc_pinned((size_t)ABD_MAX_BATCH * s->out_stride));
-  *out = own.release();
-  return ABD_OK;
-}
-}  // namespace
-
-namespace {
-int survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out);
-}
-
-int abd_survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out) {
-  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  try {
-    return survival_create_groups(d, out);
-  } catch (const std::bad_alloc&) {  // the host copies of the planes: nothing may be thrown across the C ABI
-    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
-  }
-}
-
-namespace {
-int survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out) {
-  const int N = d->n_inds, T = d->n_intervals, Gr = d->n_groups;
-  if (N < 1) return fail(ABD_ERR_ARG, "n_inds=%d must be >= 1", N);
-  if (T < 1 || T > ABD_MAX_GAPS - 1) return fail(ABD_ERR_ARG, "n_intervals=%d outside [1, %d]", T, ABD_MAX_GAPS - 1);
-  if (Gr < 1 || Gr > ABD_SURVIVAL_MAX_GROUPS) return fail(ABD_ERR_ARG, "n_groups=%d outside [1, %d]", Gr, ABD_SURVIVAL_MAX_GROUPS);
-  if (!d->infected || !d->exposure || !d->titer || !d->group) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
-  const double pos[7] = {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
-  for (double v : pos)
-    if (!(v > 0.0) || !std::isfinite(v))
-      return fail(ABD_ERR_ARG, "lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd must be positive and finite, got %g", v);
-  if (!std::isfinite(d->lam0_mu_mean)) return fail(ABD_ERR_ARG, "lam0_mu_mean must be finite, got %g", d->lam0_mu_mean);
-  for (int j = 0; j < N; ++j)
-    if (d->group[j] < 0 || d->group[j] >= Gr) return fail(ABD_ERR_ARG, "individual %d: group %d outside [0, %d)", j, d->group[j], Gr);
-  // the individuals sorted by group, every group padded to whole tiles: a tile belongs to one group
-  std::vector<int32_t> slot((size_t)N), tile_group((size_t)(N + 63) / 64 + Gr), group_tile((size_t)Gr + 1);
-  const int ntile = survival_groups_layout(N, Gr, d->group, slot.data(), tile_group.data(), group_tile.data());
-  const size_t ld = (size_t)ntile * 64, plane = ld * (size_t)T;
-  std::vector<double> y(plane, 0.0), e(plane, 0.0), x(plane, 0.0);
-  std::vector<SurvivalSum> Ysum((size_t)T);
-  SurvivalSum Csum;
-  for (int j = 0; j < N; ++j)
-    for (int t = 0; t < T; ++t) {
-      const size_t src = (size_t)j * T + t, dst = (size_t)t * ld + slot[j];
-      double yy = d->infected[src], ee = d->exposure[src], xx = d->titer[src];
-      if (const char* msg = survival_check_cell(1, yy, ee, &xx)) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", j, t, msg);
-      y[dst] = yy;
-      e[dst] = ee;
-      x[dst] = xx;
-      Ysum[t].add(yy);
-      if (yy > 0.0) Csum.add(yy * std::log(ee));
-      Csum.add(-std::lgamma(yy + 1.0));
-    }
-  abd_survival* s = new (std::nothrow) abd_survival;
-  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
-  std::unique_ptr<abd_survival> own(s);
-  s->N = N;
-  s->T = T;
-  s->K = 1;
-  s->Gr = Gr;
-  s->D = survival_groups_dim(T, Gr);
-  s->gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
-  s->Y.resize((size_t)T);
-  for (int t = 0; t < T; ++t) s->Y[t] = Ysum[t].value();
-  s->C = Csum.value();
-  s->ld = (int)ld;
-  s->ntile = ntile;
-  // ranges of intervals as in survival_create: from the tile count and T alone
-  const int want_seg = std::max(1, std::min(T, (4096 + ntile - 1) / ntile));
-  s->seg_len = (T + want_seg - 1) / want_seg;
-  s->nseg = (T + s->seg_len - 1) / s->seg_len;
-  s->nw = s->ntile * s->nseg;
-  s->par_stride = T + Gr + 1;
-  s->out_stride = T + 2 + Gr;
-  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
-  survival_pointwise_setup(s, y.data(), e.data(), slot.data(), Gr + 1);
-  if (d->device >= 0) {
-    s->device = d->device;
-  } else {
-    HIP_TRY(hipGetDevice(&s->device));
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(s->stream.create());
-  HIP_TRY(s->d_y.upload(y.data(), plane));
-  HIP_TRY(s->d_e.upload(e.data(), plane));
-  HIP_TRY(s->d_x0.upload(x.data(), plane));
-  HIP_TRY(s->d_tile_group.upload(tile_group.data(), (size_t)ntile));
-  HIP_TRY(s->d_group_tile.upload(group_tile.data(), (size_t)Gr + 1));
-  HIP_TRY(s->d_par.alloc((size_t)ABD_MAX_BATCH * s->par_stride));
-  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
-  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
-  HIP_TRY(s->d_out.alloc((size_t)ABD_MAX_BATCH * s->out_stride));
-  HIP_TRY(s->h_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->par_stride));
-  HIP_TRY(s->h_out.alloc_pinned((size_t)ABD_MAX_BATCH * s->out_stride));
-  *out = own.release();
-  return ABD_OK;
-}
-}  // namespace
-
-int abd_survival_destroy(abd_survival* s) {
-  if (!s) return ABD_OK;
-  (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  delete s;
-  return ABD_OK;
-}
-
-int32_t abd_survival_dim(abd_survival* s) { return s ? s->D : -1; }
-
-int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, double* logp, double* grad) {
-  if (!s || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
-  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
-    if (int rc = survival_launch(s, nb, theta + (size_t)k0 * s->D)) return rc;
-    for (int q = 0; q < nb; ++q) {
-      const size_t k = (size_t)k0 + q;
-      const double* sums = s->h_out.host() + (size_t)q * s->out_stride;
-      const double* par = s->h_par.host() + (size_t)q * s->par_stride;
-      const double* work = s->work.data() + (size_t)q * 2 * s->T;
-      logp[k] = s->Gr > 0 ? survival_groups_combine(s->gpriors, s->T, s->Gr, theta + k * s->D, s->Y.data(), s->C, sums, par, work, grad + k * s->D)
-                          : survival_combine(s->priors, s->K, s->T, theta + k * s->D, s->Y.data(), s->C, sums, par, work, grad + k * s->D);
-    }
-  }
-  return ABD_OK;
-}
-
-int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums) {
-  if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
-  HIP_TRY(hipSetDevice(s->device));
-  if (int rc = survival_launch(s, 1, theta)) return rc;
-  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + (s->Gr > 0 ? s->Gr : s->K)) * sizeof(double));
-  return ABD_OK;
-}
-
-int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* theta, double* ll) {
-  if (!s || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
-  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
-  const int32_t* slot = s->slot.empty() ? nullptr : s->slot.data();
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
-    if (int rc = survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->D, false)) return rc;
-    for (int q = 0; q < nb; ++q) {  // slots to the caller's order
-      const double* row = s->h_ll.host() + (size_t)q * s->ld;
-      double* out = ll + ((size_t)k0 + q) * s->N;
-      for (int j = 0; j < s->N; ++j) out[j] = row[slot ? slot[j] : j];
-    }
-  }
-  return ABD_OK;
-}
-
-int abd_survival_waic_reset(abd_survival* s) {
-  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
-  s->waic_n = 0;  // the first draw folded overwrites its column: the accumulators need no clearing
-  return ABD_OK;
-}
-
-int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta) {
-  if (!s || !theta) return fail(ABD_ERR_ARG, "NULL argument");
-  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
-    if (int rc = survival_pointwise_launch(s, std::min(ABD_MAX_BATCH, n - k0), theta + (size_t)k0 * s->D, true)) return rc;
-  return ABD_OK;
-}
-
-int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
-  if (!s || !lse || !mean || !m2 || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
-  if (s->waic_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_waic_accumulate comes first)");
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t ld = (size_t)s->ld;
-  if (!s->h_acc.host()) HIP_TRY(s->h_acc.alloc_pinned(4 * ld));
-  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, 4 * ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  const double* acc = s->h_acc.host();
-  for (int j = 0; j < s->N; ++j) {
-    const size_t c = s->slot.empty() ? (size_t)j : (size_t)s->slot[j];
-    lse[j] = acc[c] + std::log(acc[ld + c]);  // M + log S
-    mean[j] = acc[2 * ld + c];
-    m2[j] = acc[3 * ld + c];
-    n_cells[j] = s->n_cells[j];
-  }
-  *n_draws = s->waic_n;
   return ABD_OK;
 }
 

@@ -3,6 +3,7 @@
 //   abd_eval.hip     evaluation launches (dense panels / observation lists), pipes, completion tags, timing
 //   abd_gibbs.hip    the device Gibbs sweep
 //   abd_sampler.hip  the native compound sampler (NUTS state machine in abd_nuts.hpp + the sweep)
+//   abd_survival.hip the survival models of a finished run (a handle of its own, nothing of an abd_ctx)
 // Nothing here is part of the C ABI (include/abd_hip.h).
 //
 // Device resources are members of owning handles (abd_owned.hpp); nothing is freed by hand.  Teardown: the destructors of

@@ -1,0 +1,381 @@
+// abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
+// handle of either form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators.  A
+// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp and
+// abd_survival_pointwise.hpp; the closed forms, the packing of the planes and the form of a model (SurvivalForm) are plain C++
+// in the three *_terms.hpp beside them.
+#include <memory>
+
+#include "abd_host.hpp"
+#include "abd_survival.hpp"
+#include "abd_survival_groups.hpp"
+#include "abd_survival_groups_terms.hpp"
+#include "abd_survival_pointwise.hpp"
+#include "abd_survival_pointwise_terms.hpp"
+#include "abd_survival_terms.hpp"
+
+namespace abdi {
+// what a creator decides: the rest of a handle follows from it and from the data
+struct SurvivalSpec {
+  SurvivalForm form;  // K titers, or by group (abd_survival_groups.hpp)
+  int N = 0, device = 0;
+  SurvivalPriors priors{};         // of the form with K titers
+  SurvivalGroupsPriors gpriors{};  // of the form by group
+};
+}  // namespace abdi
+
+struct abd_survival : SurvivalSpec {
+  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
+  DevBuf<int32_t> d_tile_group, d_group_tile;
+  std::vector<double> Y;  // Y_t = sum_j y_jt
+  double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
+  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
+  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
+  std::vector<double> work;        // log lambda, 1 - lambda of the points in flight
+  // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
+  std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
+  std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
+  std::vector<double> cj;          // [ld] C_j per slot, uploaded at the first pointwise call
+  int pw_stride = 0;               // the pointwise parameter row: lambda[T], log lambda[T], ab[n_ab], 1 / n_draw
+  DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
+  MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
+  int64_t waic_n = 0;              // draws folded into d_acc
+  Stream stream;
+
+  int column(int j) const { return slot.empty() ? j : slot[j]; }
+};
+
+namespace abdi {
+namespace {
+
+// par and work of n <= ABD_MAX_BATCH points: rows of s->h_par and s->work
+void survival_prepare_points(abd_survival* s, int n, const double* theta) {
+  const int D = s->form.dim(), stride = s->form.par_stride(), T = s->form.T;
+  for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * 2 * T);
+}
+
+// what the argument structs of the two forms have in common
+template <typename Args>
+Args survival_args(const abd_survival* s) {
+  Args a;
+  std::memset(&a, 0, sizeof a);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.par = s->d_par;
+  a.s_part = s->d_s_part;
+  a.w_part = s->d_w_part;
+  a.out = s->d_out;
+  a.T = s->form.T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.nseg = s->nseg;
+  a.seg_len = s->seg_len;
+  a.par_stride = s->form.par_stride();
+  return a;
+}
+
+// the sums of n <= ABD_MAX_BATCH points into s->h_out (rows of out_stride)
+int survival_launch(abd_survival* s, int n, const double* theta) {
+  const int T = s->form.T;
+  survival_prepare_points(s, n, theta);
+  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->form.par_stride() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  const dim3 grid((unsigned)((s->nw + 3) / 4), (unsigned)n);
+  if (s->form.grouped()) {  // the one place that picks the pair of kernels
+    SurvivalGroupsArgs a = survival_args<SurvivalGroupsArgs>(s);
+    a.x = s->d_x0;
+    a.tile_group = s->d_tile_group;
+    a.group_tile = s->d_group_tile;
+    a.Gr = s->form.Gr;
+    HIP_TRY(launch_kernel(abd_survival_groups_kernel, grid, dim3(256), 0, s->stream, a));
+    HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (a.Gr + 3) / 4), (unsigned)n), dim3(256), 0,
+                          s->stream, a));
+  } else {
+    SurvivalArgs a = survival_args<SurvivalArgs>(s);
+    a.x0 = s->d_x0;
+    a.x1 = s->d_x1;
+    HIP_TRY(launch_kernel(s->form.K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, grid, dim3(256), 0, s->stream, a));
+    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, a));
+  }
+  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->form.out_stride() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return ABD_OK;
+}
+
+// ---- the per-individual log-likelihood (abd_survival_pointwise.hpp) ----
+
+// At creation, on the host: C_j per slot and the followed cells per individual from the planes y, e [T][ld]
+void survival_pointwise_setup(abd_survival* s, const double* y, const double* e) {
+  std::vector<int32_t> cells((size_t)s->ld);
+  s->cj.resize((size_t)s->ld);
+  survival_pointwise_constants(s->form.T, s->ld, y, e, s->cj.data(), cells.data());
+  s->n_cells.resize((size_t)s->N);
+  for (int j = 0; j < s->N; ++j) s->n_cells[j] = cells[s->column(j)];
+  s->pw_stride = survival_pointwise_stride(s->form.T, s->form.n_ab());
+}
+
+// the buffers of the pointwise launches, at the first of them
+int survival_pointwise_ensure(abd_survival* s) {
+  if (s->d_ll) return ABD_OK;
+  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->ld));
+  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->ld));
+  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->ld));
+  return ABD_OK;
+}
+
+// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll.  fold: the rows go into the accumulators as draws waic_n + 1 ..
+// waic_n + n; else they are copied to s->h_ll.
+int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool fold) {
+  if (int rc = survival_pointwise_ensure(s)) return rc;
+  const int T = s->form.T, n_ab = s->form.n_ab(), stride = s->form.par_stride();
+  survival_prepare_points(s, n, theta);
+  for (int q = 0; q < n; ++q)
+    survival_pointwise_row(T, n_ab, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * 2 * T, fold ? s->waic_n + q + 1 : 0,
+                           s->h_pw_par.host() + (size_t)q * s->pw_stride);
+  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalPointArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.cj = s->d_cj;
+  a.par = s->d_pw_par;
+  a.tile_group = s->d_tile_group;
+  a.ll = s->d_ll;
+  a.T = T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.par_stride = s->pw_stride;
+  a.n_ab = n_ab;
+  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
+  void (*const kernels[3])(const SurvivalPointArgs) = {abd_survival_individual_kernel<0>, abd_survival_individual_kernel<1>,
+                                                       abd_survival_individual_kernel<2>};
+  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), 0, s->stream, a));
+  if (fold) {
+    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->ld, s->stream));
+    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_ll,
+                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->ld, (int32_t)s->pw_stride,
+                          (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
+  } else {
+    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (fold) s->waic_n += n;
+  return ABD_OK;
+}
+
+// ---- creation ----
+
+int survival_check_shape(int N, int T) {
+  if (N < 1) return fail(ABD_ERR_ARG, "n_inds=%d must be >= 1", N);
+  if (T < 1 || T > ABD_MAX_GAPS - 1) return fail(ABD_ERR_ARG, "n_intervals=%d outside [1, %d]", T, ABD_MAX_GAPS - 1);
+  return ABD_OK;
+}
+
+// the scales and rates of a form's priors (`names` is what the message calls them), then the mean of _lam0_raw_mu
+int survival_check_priors(const char* names, std::initializer_list<double> positive, double lam0_mu_mean) {
+  for (double v : positive)
+    if (!(v > 0.0) || !std::isfinite(v)) return fail(ABD_ERR_ARG, "%s must be positive and finite, got %g", names, v);
+  if (!std::isfinite(lam0_mu_mean)) return fail(ABD_ERR_ARG, "lam0_mu_mean must be finite, got %g", lam0_mu_mean);
+  return ABD_OK;
+}
+
+// the layout of the grouped form (survival_groups_layout): a tile belongs to one group
+struct SurvivalLayout {
+  int ntile = 0;
+  std::vector<int32_t> slot, tile_group, group_tile;
+};
+
+// Everything after a creator's own checks: the planes, the plan of the launches, the device and its buffers.  spec.device is
+// what the caller asked for (< 0: the current device); layout is null for the ungrouped form (individual j in column j).
+int survival_create_common(const SurvivalSpec& spec, const double* infected, const double* exposure, const double* const* titer,
+                           const SurvivalLayout* layout, abd_survival** out) {
+  const int N = spec.N, T = spec.form.T, K = spec.form.K;
+  const int ntile = layout ? layout->ntile : (N + 63) / 64;
+  SurvivalPlanes p;  // [interval][individual] planes, padded with cells that have no follow-up
+  const SurvivalRefusal bad = survival_pack(N, T, K, infected, exposure, titer, layout ? layout->slot.data() : nullptr, (size_t)ntile * 64, &p);
+  if (bad.msg) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", bad.j, bad.t, bad.msg);
+  std::unique_ptr<abd_survival> s(new (std::nothrow) abd_survival);
+  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
+  static_cast<SurvivalSpec&>(*s) = spec;
+  s->ntile = ntile;
+  s->ld = ntile * 64;
+  if (layout) s->slot = layout->slot;
+  s->Y = std::move(p.Y);
+  s->C = p.C;
+  // ranges of intervals: enough waves for the chip (about 4096) while a wave keeps at least one interval; from the tile count and
+  // T alone
+  const int want_seg = std::max(1, std::min(T, (4096 + s->ntile - 1) / s->ntile));
+  s->seg_len = (T + want_seg - 1) / want_seg;
+  s->nseg = (T + s->seg_len - 1) / s->seg_len;
+  s->nw = s->ntile * s->nseg;
+  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  survival_pointwise_setup(s.get(), p.y.data(), p.e.data());
+  if (s->device < 0) HIP_TRY(hipGetDevice(&s->device));
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->stream.create());
+  const size_t plane = (size_t)s->ld * T;
+  HIP_TRY(s->d_y.upload(p.y.data(), plane));
+  HIP_TRY(s->d_e.upload(p.e.data(), plane));
+  HIP_TRY(s->d_x0.upload(p.x0.data(), plane));
+  if (K == 2) HIP_TRY(s->d_x1.upload(p.x1.data(), plane));
+  if (layout) {
+    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->ntile));
+    HIP_TRY(s->d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
+  }
+  const size_t par_stride = (size_t)s->form.par_stride(), out_stride = (size_t)s->form.out_stride();
+  HIP_TRY(s->d_par.alloc(ABD_MAX_BATCH * par_stride));
+  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
+  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
+  HIP_TRY(s->d_out.alloc(ABD_MAX_BATCH * out_stride));
+  HIP_TRY(s->h_par.alloc_pinned(ABD_MAX_BATCH * par_stride));
+  HIP_TRY(s->h_out.alloc_pinned(ABD_MAX_BATCH * out_stride));
+  *out = s.release();
+  return ABD_OK;
+}
+
+// The frame of both creators around `create`, the creator's own checks and its call of survival_create_common: nothing may be
+// thrown across the C ABI (the host copies of the planes are the large allocations).
+template <typename Desc, typename Create>
+int survival_create(const Desc* d, abd_survival** out, Create create) {
+  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  try {
+    return create();
+  } catch (const std::bad_alloc&) {
+    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
+  }
+}
+
+}  // namespace
+}  // namespace abdi
+
+extern "C" {
+
+int abd_survival_create(const abd_survival_desc* d, abd_survival** out) {
+  return survival_create(d, out, [&] {
+    const int K = d->n_titers;
+    if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
+    if (int rc = survival_check_shape(d->n_inds, d->n_intervals)) return rc;
+    if (!d->infected || !d->exposure || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_priors("ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd", {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd},
+                                       d->lam0_mu_mean))
+      return rc;
+    SurvivalSpec spec{SurvivalForm{K, 0, d->n_intervals}, d->n_inds, d->device};
+    spec.priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
+    return survival_create_common(spec, d->infected, d->exposure, d->titer, nullptr, out);
+  });
+}
+
+int abd_survival_create_groups(const abd_survival_groups_desc* d, abd_survival** out) {
+  return survival_create(d, out, [&] {
+    const int N = d->n_inds, Gr = d->n_groups;
+    if (int rc = survival_check_shape(N, d->n_intervals)) return rc;
+    if (Gr < 1 || Gr > ABD_SURVIVAL_MAX_GROUPS) return fail(ABD_ERR_ARG, "n_groups=%d outside [1, %d]", Gr, ABD_SURVIVAL_MAX_GROUPS);
+    if (!d->infected || !d->exposure || !d->titer || !d->group) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_priors("lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd",
+                                       {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd}, d->lam0_mu_mean))
+      return rc;
+    for (int j = 0; j < N; ++j)
+      if (d->group[j] < 0 || d->group[j] >= Gr) return fail(ABD_ERR_ARG, "individual %d: group %d outside [0, %d)", j, d->group[j], Gr);
+    // the individuals sorted by group, every group padded to whole tiles: a tile belongs to one group
+    SurvivalLayout lay;
+    lay.slot.resize((size_t)N);
+    lay.tile_group.resize((size_t)(N + 63) / 64 + Gr);
+    lay.group_tile.resize((size_t)Gr + 1);
+    lay.ntile = survival_groups_layout(N, Gr, d->group, lay.slot.data(), lay.tile_group.data(), lay.group_tile.data());
+    SurvivalSpec spec{SurvivalForm{1, Gr, d->n_intervals}, N, d->device};
+    spec.gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+    return survival_create_common(spec, d->infected, d->exposure, &d->titer, &lay, out);
+  });
+}
+
+int abd_survival_destroy(abd_survival* s) {
+  if (!s) return ABD_OK;
+  (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  delete s;
+  return ABD_OK;
+}
+
+int32_t abd_survival_dim(abd_survival* s) { return s ? s->form.dim() : -1; }
+
+int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, double* logp, double* grad) {
+  if (!s || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t D = (size_t)s->form.dim(), out_stride = (size_t)s->form.out_stride(), par_stride = (size_t)s->form.par_stride();
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_launch(s, nb, theta + k0 * D)) return rc;
+    for (int q = 0; q < nb; ++q) {
+      const size_t k = (size_t)k0 + q;
+      logp[k] = s->form.combine(s->priors, s->gpriors, theta + k * D, s->Y.data(), s->C, s->h_out.host() + q * out_stride,
+                                s->h_par.host() + q * par_stride, s->work.data() + (size_t)q * 2 * s->form.T, grad + k * D);
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums) {
+  if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = survival_launch(s, 1, theta)) return rc;
+  std::memcpy(sums, s->h_out.host(), (size_t)s->form.n_sums() * sizeof(double));
+  return ABD_OK;
+}
+
+int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* theta, double* ll) {
+  if (!s || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t D = (size_t)s->form.dim();
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_pointwise_launch(s, nb, theta + k0 * D, false)) return rc;
+    for (int q = 0; q < nb; ++q) {  // slots to the caller's order
+      const double* row = s->h_ll.host() + (size_t)q * s->ld;
+      double* out = ll + ((size_t)k0 + q) * s->N;
+      for (int j = 0; j < s->N; ++j) out[j] = row[s->column(j)];
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_waic_reset(abd_survival* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  s->waic_n = 0;  // the first draw folded overwrites its column: the accumulators need no clearing
+  return ABD_OK;
+}
+
+int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta) {
+  if (!s || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  HIP_TRY(hipSetDevice(s->device));
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
+    if (int rc = survival_pointwise_launch(s, std::min(ABD_MAX_BATCH, n - k0), theta + (size_t)k0 * s->form.dim(), true)) return rc;
+  return ABD_OK;
+}
+
+int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
+  if (!s || !lse || !mean || !m2 || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
+  if (s->waic_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_waic_accumulate comes first)");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t ld = (size_t)s->ld;
+  if (!s->h_acc.host()) HIP_TRY(s->h_acc.alloc_pinned(4 * ld));
+  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, 4 * ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const double* acc = s->h_acc.host();
+  for (int j = 0; j < s->N; ++j) {
+    const size_t c = (size_t)s->column(j);
+    lse[j] = acc[c] + std::log(acc[ld + c]);  // M + log S
+    mean[j] = acc[2 * ld + c];
+    m2[j] = acc[3 * ld + c];
+    n_cells[j] = s->n_cells[j];
+  }
+  *n_draws = s->waic_n;
+  return ABD_OK;
+}
+
+}  // extern "C"

@@ -16,10 +16,9 @@
 #pragma once
 
 #include "abd_device.hpp"
+#include "abd_survival_terms.hpp"  // ABD_SURV_NW
 
 namespace abdi {
-
-#define ABD_SURV_NW 4  // L, W_0, W_1, W_2 of one wave (a row of w_part; the last is unused for K = 1)
 
 struct SurvivalArgs {
   const double* y;    // [T][ld]
@@ -46,6 +45,20 @@ __device__ __forceinline__ double surv_exp_neg(double abs_eta) {
   return ldexp(exp2_reduced(f), (int)k);
 }
 
+// en = e^-|eta|, sigma and 1 - sigma of one cell: the one formation of sigma, for the sums (surv_cell) and for the per-individual
+// log-likelihood (abd_survival_pointwise.hpp).
+struct SurvSigma {
+  double en, sig, oms;
+};
+__device__ __forceinline__ SurvSigma surv_sigma(double eta) {
+  const double en = surv_exp_neg(fabs(eta));
+  double r = rcp_newton(1.0 + en);
+  r = fma(fma(-(1.0 + en), r, 1.0), r, r);
+  const double er = en * r;
+  const bool pos = eta >= 0.0;
+  return SurvSigma{en, pos ? r : er, pos ? er : r};
+}
+
 // One cell given eta: e sigma, summed over the wave into *s_t by lane 0; returns w = (y - mu)(1 - sigma) and the cell's
 // y log sigma.  The one statement of the cell: abd_survival_kernel<K> and the grouped kernel (abd_survival_groups.hpp) differ
 // in how they form eta.
@@ -53,19 +66,14 @@ struct SurvCell {
   double w, ly;
 };
 __device__ __forceinline__ SurvCell surv_cell(double eta, double y, double e, double lam, int lane, double* s_t) {
-  const double en = surv_exp_neg(fabs(eta));
-  double r = rcp_newton(1.0 + en);
-  r = fma(fma(-(1.0 + en), r, 1.0), r, r);
-  const double er = en * r;
-  const bool pos = eta >= 0.0;
-  const double sig = pos ? r : er, oms = pos ? er : r;  // sigma, 1 - sigma
-  const double es = e * sig;
+  const SurvSigma sg = surv_sigma(eta);
+  const double es = e * sg.sig;
   const double S = wave_sum_uniform(es);
   if (lane == 0) *s_t = S;
   // log sigma = min(eta, 0) - log1p(e^-|eta|); a cell with y = 0 has no log term
-  const double ls = fmin(eta, 0.0) - log1p(en);
+  const double ls = fmin(eta, 0.0) - log1p(sg.en);
   const double ly = y > 0.0 ? y * ls : 0.0;
-  return SurvCell{fma(-lam, es, y) * oms, ly};
+  return SurvCell{fma(-lam, es, y) * sg.oms, ly};
 }
 
 template <int K>

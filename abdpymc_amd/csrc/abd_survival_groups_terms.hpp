@@ -1,7 +1,7 @@
 // abd_survival_groups_terms.hpp -- the closed-form part of the Poisson hazard model by group: what one unconstrained
 // point gives the kernel (lambda_t, a_g, b), and the combination of the device sums with the priors into logp and gradient.
-// Plain C++, no HIP: one source for the library (abd_eval.hip) and for the native harness
-// (tests/native/survival_groups_harness.cpp).
+// Plain C++, no HIP: one source for the library (abd_survival.hip) and for the native harness
+// (tests/native/survival_groups_harness.cpp).  At the end, SurvivalForm: which of the two models a handle holds, asked in one place.
 //
 //   theta = m, s, z[T], a_mu, a_sl, az[Gr], b     (PyMC's creation order for this model; sd = e^s, a_sd = e^a_sl)
 //   r_t = m + sd z_t, lambda_t = invlogit(r_t);  a_g = a_mu + a_sd az_g
@@ -115,5 +115,32 @@ inline int survival_groups_layout(int N, int Gr, const int32_t* group, int32_t* 
   for (int j = 0; j < N; ++j) slot[j] = next[group[j]]++;
   return tile;
 }
+
+// The form of a handle's model: K titers (Gr = 0; abd_survival_terms.hpp), or by group (Gr > 0, K = 1; this file).  Everything
+// that differs between the two on the host is answered here: the sizes of a point and of its rows, and which pair of closed
+// forms makes the parameter row of a point and combines its sums.
+struct SurvivalForm {
+  int K = 0, Gr = 0, T = 0;
+  bool grouped() const { return Gr > 0; }
+  int dim() const { return grouped() ? survival_groups_dim(T, Gr) : survival_dim(K, T); }
+  int n_ab() const { return grouped() ? Gr + 1 : 2 * K; }            // a[Gr], b, or a[K], b[K]: what follows lambda[T] in a parameter row
+  int par_stride() const { return T + n_ab(); }
+  int n_sums() const { return T + 2 + (grouped() ? Gr : K); }        // the sums of a point that mean something
+  int out_stride() const { return grouped() ? T + 2 + Gr : T + ABD_SURV_NW; }  // the row the finalize kernel of the form writes
+  int mode() const { return grouped() ? 0 : K; }                     // MODE of abd_survival_individual_kernel
+  void prepare(const double* theta, double* par, double* work) const {
+    if (grouped()) {
+      survival_groups_prepare(T, Gr, theta, par, work);
+    } else {
+      survival_prepare(K, T, theta, par, work);
+    }
+  }
+  // the priors of the other form are not read
+  double combine(const SurvivalPriors& p, const SurvivalGroupsPriors& gp, const double* theta, const double* Y, double C,
+                 const double* sums, const double* par, const double* work, double* grad) const {
+    return grouped() ? survival_groups_combine(gp, T, Gr, theta, Y, C, sums, par, work, grad)
+                     : survival_combine(p, K, T, theta, Y, C, sums, par, work, grad);
+  }
+};
 
 }  // namespace abdi

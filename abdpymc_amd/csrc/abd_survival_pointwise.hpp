@@ -13,8 +13,7 @@
 // order of every sum is fixed by T alone: a point's row is the same bits alone, as any row of a full launch and in any split
 // of a longer call.  Cells without follow-up and the padding hold y = e = x = 0 and C = 0: sigma is finite, e sigma = 0, and
 // the lane writes exactly 0.0.  The grouped form reads its tile's a_g through tile_group as abd_survival_groups_kernel does.
-// sigma is formed as surv_cell forms it (surv_exp_neg, the twice-refined reciprocal); surv_cell itself is not called, it
-// carries the wave sum of S_t.
+// sigma is surv_cell's (surv_sigma); surv_cell itself is not called, it carries the wave sum of S_t.
 //
 // abd_survival_waic_fold: thread = slot; the launch's n rows go into the handle's accumulators [4][ld] (rows M, S, mean, M2)
 // in ascending order by waic_update (abd_readings.hpp), a plain read-modify-write of a column that one thread owns.  Folding
@@ -67,13 +66,10 @@ __global__ __launch_bounds__(256) void abd_survival_individual_kernel(const Surv
     const double y = a.y[idx], e = a.e[idx];
     double eta = b0 * (a.x0[idx] - a0);
     if (MODE == 2) eta = fma(b1, a.x1[idx] - a1, eta);
-    const double en = surv_exp_neg(fabs(eta));
-    double r = rcp_newton(1.0 + en);
-    r = fma(fma(-(1.0 + en), r, 1.0), r, r);
-    const double sig = eta >= 0.0 ? r : en * r;
-    const double ls = fmin(eta, 0.0) - log1p(en);
+    const SurvSigma sg = surv_sigma(eta);
+    const double ls = fmin(eta, 0.0) - log1p(sg.en);
     A += y > 0.0 ? y * (loglam[t] + ls) : 0.0;
-    B = fma(lam[t], e * sig, B);
+    B = fma(lam[t], e * sg.sig, B);
   }
   a.ll[(int64_t)point * a.ld + slot] = (a.cj[slot] + A) - B;
 }

@@ -1,7 +1,7 @@
 // abd_survival_pointwise_terms.hpp -- the host half of the per-individual log-likelihood of the survival models: the
 // constant of the data C_j and the number of followed cells of every column of the resident planes, and the parameter row one
 // point gives abd_survival_individual_kernel and abd_survival_waic_fold.  Plain C++, no HIP: one source for the library
-// (abd_eval.hip) and for the native harness (tests/native/survival_pointwise_harness.cpp).
+// (abd_survival.hip) and for the native harness (tests/native/survival_pointwise_harness.cpp).
 //
 //   ll_j = C_j + A_j - B_j
 //   A_j  = sum_t [ y > 0 ? y (log lambda_t + log sigma_jt) : 0 ]      B_j = sum_t e lambda_t sigma_jt      (the device, ascending t)

@@ -1,6 +1,7 @@
 // abd_survival_terms.hpp -- the closed-form part of the Poisson hazard models: what one unconstrained point gives
 // the kernel (lambda_t, a, b), and the combination of the device sums with the priors into logp and gradient.  Plain C++,
-// no HIP: one source for the library (abd_eval.hip) and for the native harness (tests/native/survival_harness.cpp).
+// no HIP: one source for the library (abd_survival.hip) and for the native harness (tests/native/survival_harness.cpp).
+// Also what creation makes of the caller's arrays: the rule for one cell and the planes the kernels read (survival_pack).
 //
 //   theta = a[K], b[K], m, s, z[T]            (PyMC's creation order; sd = e^s)
 //   r_t = m + sd z_t, lambda_t = invlogit(r_t)
@@ -9,6 +10,11 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#define ABD_SURV_NW 4  // L, W_0, W_1, W_2 of one wave (a row of w_part; the last is unused for K = 1)
 
 namespace abdi {
 
@@ -116,6 +122,50 @@ inline const char* survival_check_cell(int K, double& y, double& e, double* x) {
   for (int k = 0; k < K; ++k)
     if (!std::isfinite(x[k])) return "titer of a followed cell must be finite";
   return nullptr;
+}
+
+// What creation keeps of the data: the [interval][individual] planes, padded to ld columns with cells that have no follow-up,
+// Y_t = sum_j y_jt and C = sum_{y > 0} y log e - sum lgamma(y + 1).
+struct SurvivalPlanes {
+  std::vector<double> y, e, x0, x1;  // [T][ld]; x1 for K = 2 only
+  std::vector<double> Y;             // [T]
+  double C = 0.0;
+};
+
+struct SurvivalRefusal {
+  int j, t;         // the individual and the interval of the refused cell
+  const char* msg;  // null: every cell was taken
+};
+
+// The one transpose of the caller's arrays [N][T] (infected, exposure, K titers) into planes [T][ld]: individual j goes to
+// column slot[j], or to column j where slot is null.  The cells are taken with j ascending, then t ascending -- the order of the
+// terms of Y_t and C -- each through survival_check_cell; the first refused cell ends it.
+inline SurvivalRefusal survival_pack(int N, int T, int K, const double* infected, const double* exposure, const double* const* titer,
+                                     const int32_t* slot, size_t ld, SurvivalPlanes* p) {
+  const size_t plane = ld * (size_t)T;
+  p->y.assign(plane, 0.0);
+  p->e.assign(plane, 0.0);
+  p->x0.assign(plane, 0.0);
+  p->x1.assign(K == 2 ? plane : 0, 0.0);
+  std::vector<SurvivalSum> Ysum((size_t)T);
+  SurvivalSum Csum;
+  for (int j = 0; j < N; ++j)
+    for (int t = 0; t < T; ++t) {
+      const size_t src = (size_t)j * T + t, dst = (size_t)t * ld + (slot ? slot[j] : j);
+      double yy = infected[src], ee = exposure[src], xx[2] = {titer[0][src], K == 2 ? titer[1][src] : 0.0};
+      if (const char* msg = survival_check_cell(K, yy, ee, xx)) return SurvivalRefusal{j, t, msg};
+      p->y[dst] = yy;
+      p->e[dst] = ee;
+      p->x0[dst] = xx[0];
+      if (K == 2) p->x1[dst] = xx[1];
+      Ysum[t].add(yy);
+      if (yy > 0.0) Csum.add(yy * std::log(ee));
+      Csum.add(-std::lgamma(yy + 1.0));
+    }
+  p->Y.resize((size_t)T);
+  for (int t = 0; t < T; ++t) p->Y[t] = Ysum[t].value();
+  p->C = Csum.value();
+  return SurvivalRefusal{-1, -1, nullptr};
 }
 
 }  // namespace abdi

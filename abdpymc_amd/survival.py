@@ -71,22 +71,8 @@ def _means(src) -> Dict[str, np.ndarray]:
     return out
 
 
-class SurvivalModel:
-    """One Poisson hazard model: ``names`` of the unconstrained point's entries, ``dim``, ``logp_dlogp(q)`` on the device
-    ((D,) -> (logp, grad); (n, D) -> arrays, up to 16 points per launch), ``constrain(q)`` and ``close()``."""
-
-    def __init__(self, infected, exposure, titers, antigens, priors=None, device: int = -1):
-        from ._native import Survival
-
-        self.antigens = tuple(antigens)
-        self.K = len(titers)
-        self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
-        self._dev = Survival(infected, exposure, titers, self.priors, device=device)
-        self.n_cells = followed_cells(infected, exposure)
-        self.T = self._dev.n_intervals
-        self.dim = self._dev.dim
-        ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
-        self.names = tuple(ab + ["_lam0_raw_mu", "_lam0_raw_sd_log__"] + [f"__lam0_raw_z_{t}" for t in range(self.T)])
+class _DeviceModel:
+    """What both models pass on to their handle ``_dev`` (``_native.Survival`` or ``SurvivalGroups``)."""
 
     def logp_dlogp(self, q):
         return self._dev.logp_dlogp(q)
@@ -109,11 +95,29 @@ class SurvivalModel:
         """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
         return self._dev.waic_stats()
 
-    def constrain(self, q) -> Dict[str, np.ndarray]:
-        return constrain(q, self.K)
-
     def close(self):
         self._dev.close()
+
+
+class SurvivalModel(_DeviceModel):
+    """One Poisson hazard model: ``names`` of the unconstrained point's entries, ``dim``, ``logp_dlogp(q)`` on the device
+    ((D,) -> (logp, grad); (n, D) -> arrays, up to 16 points per launch), ``constrain(q)`` and ``close()``."""
+
+    def __init__(self, infected, exposure, titers, antigens, priors=None, device: int = -1):
+        from ._native import Survival
+
+        self.antigens = tuple(antigens)
+        self.K = len(titers)
+        self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
+        self._dev = Survival(infected, exposure, titers, self.priors, device=device)
+        self.n_cells = followed_cells(infected, exposure)
+        self.T = self._dev.n_intervals
+        self.dim = self._dev.dim
+        ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
+        self.names = tuple(ab + ["_lam0_raw_mu", "_lam0_raw_sd_log__"] + [f"__lam0_raw_z_{t}" for t in range(self.T)])
+
+    def constrain(self, q) -> Dict[str, np.ndarray]:
+        return constrain(q, self.K)
 
 
 def followed_cells(infected, exposure) -> np.ndarray:
@@ -171,7 +175,7 @@ def initial_point_groups(T: int, Gr: int, priors=PRIORS_GROUPS) -> np.ndarray:
     return q0
 
 
-class SurvivalGroupsModel:
+class SurvivalGroupsModel(_DeviceModel):
     """The Poisson hazard model by group: ``names``, ``dim``, ``groups`` (the sorted unique labels), ``group_name``,
     ``logp_dlogp(q)`` and ``loglik_sums(q)`` on the device, ``constrain(q)``, ``initial_point()`` and ``close()``."""
 
@@ -193,35 +197,11 @@ class SurvivalGroupsModel:
         self.dim = self._dev.dim
         self.names = names_groups(self.T, self.Gr)
 
-    def logp_dlogp(self, q):
-        return self._dev.logp_dlogp(q)
-
-    def loglik_sums(self, q):
-        return self._dev.loglik_sums(q)
-
-    def individual_loglik(self, q):
-        """(n, D) -> (n, N): every individual's log-likelihood over its intervals at every point (0 without a followed cell)."""
-        return self._dev.individual_loglik(q)
-
-    def waic_reset(self):
-        self._dev.waic_reset()
-
-    def waic_accumulate(self, q):
-        """Folds the draws ``q`` (n, D), in order, into the statistics of ``individual_loglik`` that the device keeps."""
-        self._dev.waic_accumulate(q)
-
-    def waic_stats(self):
-        """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
-        return self._dev.waic_stats()
-
     def constrain(self, q) -> Dict[str, np.ndarray]:
         return constrain_groups(q, self.T, self.Gr)
 
     def initial_point(self) -> np.ndarray:
         return initial_point_groups(self.T, self.Gr, self.priors)
-
-    def close(self):
-        self._dev.close()
 
 
 class SurvivalAnalysis:

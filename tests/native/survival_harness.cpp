@@ -1,7 +1,9 @@
 // CPU harness for abd_survival_terms.hpp (tests/test_survival_terms_native.py): what the library makes of one point (lambda_t, a,
-// b for the kernel) and of the device sums (logp, gradient), and its verdict on one cell, as plain functions.
+// b for the kernel) and of the device sums (logp, gradient), its verdict on one cell, and the planes creation makes of the
+// caller's arrays, as plain functions.
 #include <cstring>
 
+#include "abd_survival_groups_terms.hpp"
 #include "abd_survival_terms.hpp"
 
 extern "C" int survival_terms(int K, int T, const double* priors, const double* theta, const double* Y, double C, const double* sums,
@@ -21,4 +23,38 @@ extern "C" int survival_cell(int K, double* cell, char* msg, int msg_len) {
   std::strncpy(msg, m ? m : "", (size_t)msg_len - 1);
   msg[msg_len - 1] = 0;
   return m ? 1 : 0;
+}
+
+// survival_pack as creation calls it.  group null: individual j in column j; else the columns of survival_groups_layout of the
+// labels group[N] in [0, Gr).  Returns ld (at most ld_cap, else -1) with planes = y, e, x0, x1 [4][T][ld] (x1 untouched for
+// K = 1), Y[T], *C and slot[N]; or 0 for a refused cell, with bad = j, t and its message.
+extern "C" int survival_planes(int N, int T, int K, const double* infected, const double* exposure, const double* x0, const double* x1,
+                               const int32_t* group, int Gr, int ld_cap, double* planes, double* Y, double* C, int32_t* slot, int* bad,
+                               char* msg, int msg_len) {
+  using namespace abdi;
+  int ntile = (N + 63) / 64;
+  if (group) {
+    std::vector<int32_t> tile_group((size_t)ntile + Gr), group_tile((size_t)Gr + 1);
+    ntile = survival_groups_layout(N, Gr, group, slot, tile_group.data(), group_tile.data());
+  } else {
+    for (int j = 0; j < N; ++j) slot[j] = j;
+  }
+  const size_t ld = (size_t)ntile * 64, plane = ld * T;
+  if (ld > (size_t)ld_cap) return -1;
+  const double* titer[2] = {x0, x1};
+  SurvivalPlanes p;
+  const SurvivalRefusal r = survival_pack(N, T, K, infected, exposure, titer, group ? slot : nullptr, ld, &p);
+  std::strncpy(msg, r.msg ? r.msg : "", (size_t)msg_len - 1);
+  msg[msg_len - 1] = 0;
+  if (r.msg) {
+    bad[0] = r.j;
+    bad[1] = r.t;
+    return 0;
+  }
+  const std::vector<double>* src[4] = {&p.y, &p.e, &p.x0, &p.x1};
+  for (int k = 0; k < 4; ++k)
+    if (!src[k]->empty()) std::memcpy(planes + k * plane, src[k]->data(), plane * sizeof(double));
+  std::memcpy(Y, p.Y.data(), (size_t)T * sizeof(double));
+  *C = p.C;
+  return (int)ld;
 }

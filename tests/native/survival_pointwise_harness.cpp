@@ -18,8 +18,8 @@ int main(int argc, char** argv) {
   if (std::fread(h, sizeof(int64_t), 5, in) != 5) return 4;
   const int T = (int)h[0], ld = (int)h[1], K = (int)h[2], Gr = (int)h[3];
   if (T < 1 || ld < 1 || (Gr == 0 && K != 1 && K != 2) || Gr < 0) return 5;
-  const int D = Gr > 0 ? survival_groups_dim(T, Gr) : survival_dim(K, T);
-  const int n_ab = Gr > 0 ? Gr + 1 : 2 * K;
+  const SurvivalForm form{K, Gr, T};
+  const int D = form.dim(), n_ab = form.n_ab();
   const size_t plane = (size_t)T * ld;
   std::vector<double> y(plane), e(plane), theta((size_t)D);
   if (std::fread(y.data(), sizeof(double), plane, in) != plane) return 4;
@@ -30,11 +30,7 @@ int main(int argc, char** argv) {
   std::vector<int32_t> cells((size_t)ld);
   survival_pointwise_constants(T, ld, y.data(), e.data(), C.data(), cells.data());
   for (int j = 0; j < ld; ++j) cells_d[j] = cells[j];
-  if (Gr > 0) {
-    survival_groups_prepare(T, Gr, theta.data(), par.data(), work.data());
-  } else {
-    survival_prepare(K, T, theta.data(), par.data(), work.data());
-  }
+  form.prepare(theta.data(), par.data(), work.data());
   std::vector<double> row((size_t)survival_pointwise_stride(T, n_ab));
   survival_pointwise_row(T, n_ab, par.data(), work.data(), h[4], row.data());
   std::FILE* out = std::fopen(argv[2], "wb");

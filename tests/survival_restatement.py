@@ -42,6 +42,15 @@ def c_device(name):
     return C_FACTOR * E_NP[name]
 
 
+def _worst(got, ref, S, what):
+    """max |got - ref| / (u S); where S = 0 the value is an empty sum and must be exactly 0"""
+    got, ref, S = np.atleast_1d(got), np.atleast_1d(ref), np.atleast_1d(S)
+    assert np.isfinite(got).all(), what
+    assert (got[S == 0] == 0).all(), what
+    m = S > 0
+    return float((np.abs(got - ref)[m] / S[m] / U).max()) if m.any() else 0.0
+
+
 FIXTURES = {1: "survival_reference_k1.npz", 2: "survival_reference_k2.npz"}  # one file per K: each stays below 1 MiB
 
 

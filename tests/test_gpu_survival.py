@@ -11,6 +11,7 @@ import pytest
 from abdpymc_amd import _native, survival
 from abdpymc_amd.data import TiterData
 from tests import survival_restatement as R
+from tests.survival_restatement import _worst
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +24,6 @@ def reference(golden_dir):
 def _handle(N, T, K):
     y, e, xs = R.make_data(N, T, K)
     return _native.Survival(y, e, xs, R.PRIORS[K])
-
-
-def _worst(got, ref, S, what):
-    """max |got - ref| / (u S); where S = 0 the value is an empty sum and must be exactly 0"""
-    got, ref, S = np.atleast_1d(got), np.atleast_1d(ref), np.atleast_1d(S)
-    assert np.isfinite(got).all(), what
-    assert (got[S == 0] == 0).all(), what
-    m = S > 0
-    return float((np.abs(got - ref)[m] / S[m] / R.U).max()) if m.any() else 0.0
 
 
 @pytest.mark.parametrize("K", [1, 2])

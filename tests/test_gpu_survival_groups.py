@@ -13,6 +13,7 @@ from abdpymc_amd import _native, survival
 from abdpymc_amd.data import TiterData
 from tests import survival_groups_restatement as R
 from tests import survival_restatement as R1
+from tests.survival_restatement import _worst
 from tests.test_survival_groups_cpu import simulate
 
 pytestmark = pytest.mark.gpu
@@ -26,15 +27,6 @@ def reference(golden_dir):
 def _handle(N, T, Gr):
     y, e, x, group = R.make_case(N, T, Gr)
     return _native.SurvivalGroups(y, e, x, group, Gr, R.PRIORS)
-
-
-def _worst(got, ref, S, what):
-    """max |got - ref| / (u S); where S = 0 the value is an empty sum and must be exactly 0"""
-    got, ref, S = np.atleast_1d(got), np.atleast_1d(ref), np.atleast_1d(S)
-    assert np.isfinite(got).all(), what
-    assert (got[S == 0] == 0).all(), what
-    m = S > 0
-    return float((np.abs(got - ref)[m] / S[m] / R.U).max()) if m.any() else 0.0
 
 
 @pytest.mark.parametrize("N,T,Gr", R.SHAPES)

@@ -6,10 +6,18 @@
     ABD_HIP_LIB=$PWD/abdpymc_amd/libabd_hip.so python tools/ab_package.py run . <out B>
     python tools/ab_package.py compare <out A> <out B>
 
+A refactor of the library's own host side: archive the whole parent (its `tests/` too), build its library there, and give each
+`run` its own tree's library in `ABD_HIP_LIB`.
+
 `run` (a process per tree): `sample()` with every summary and record row on (`thin=3`, `timelines_hist`), and with nothing on,
 on the dense 67 x 65 cohort and the golden `test_cohort` of `tests/test_gpu_summaries_together.py`, then `abdpymc-infer` with
-every flag, each saved as `.npz`; the CLI's stderr is the caller's to keep.  `compare`: the same files and key sets, every array
-equal in dtype, shape and bytes -- the chains are deterministic per seed, so this is a condition, not a tolerance."""
+every flag, each saved as `.npz`; the CLI's stderr is the caller's to keep.  Then the survival models (`survival.npz`): handles
+of `_native.Survival` on `tests.survival_restatement.make_data` at (N, T) = (1, 1), (67, 30), (130, 65) with K = 1 and 2, and of
+`_native.SurvivalGroups` on `tests.survival_groups_restatement.make_case` at (67, 30, 3) and (130, 65, 4) -- `loglik_sums` at every
+point of the restatement's `POINTS`, `logp_dlogp` and `individual_loglik` of 19 stacked points (two launches), the WAIC
+accumulators of the same 19 -- and one short `survival.sample` with `survival.waic` per form on 300 x 6 simulated cells.
+`compare`: the same six files and key sets, every array equal in dtype, shape and bytes -- the chains are deterministic per seed,
+so this is a condition, not a tolerance."""
 import os
 import sys
 from types import SimpleNamespace
@@ -66,11 +74,53 @@ def run(tree, out):
                    "--risk_edges_n", "0.5,1.0", "--risk_start", "1", "--risk_all_infections", "--timelines", "--timeline_range_s=-2,6",
                    "--timeline_range_n=-3,7", "--netcdf", os.path.join(out, "cli.npz")])
     assert rc == 0
+    run_survival(out)
+
+
+def run_survival(out):
+    """The survival leg of `run`, through API that every tree since DESIGN 21 has."""
+    from abdpymc_amd import _native, survival
+    from tests import survival_groups_restatement as RG
+    from tests import survival_restatement as R
+    from tests.test_gpu_survival import _simulated
+    from tests.test_survival_groups_cpu import simulate
+
+    res = {}
+
+    def handle(tag, h, points):
+        for name, q in points.items():
+            res[f"{tag}/{name}/sums"] = h.loglik_sums(q)
+        q19 = np.stack([list(points.values())[k % len(points)] for k in range(19)])
+        res[f"{tag}/logp"], res[f"{tag}/grad"] = h.logp_dlogp(q19)
+        res[f"{tag}/ll"] = h.individual_loglik(q19)
+        h.waic_reset()
+        h.waic_accumulate(q19)
+        (res[f"{tag}/lse"], res[f"{tag}/mean"], res[f"{tag}/m2"], n), res[f"{tag}/n_cells"] = h.waic_stats()
+        res[f"{tag}/n_draws"] = np.array(n)
+        h.close()
+
+    for N, T in ((1, 1), (67, 30), (130, 65)):
+        for K in (1, 2):
+            y, e, xs = R.make_data(N, T, K)
+            handle(f"N{N}_T{T}_K{K}", _native.Survival(y, e, xs, R.PRIORS[K]), {name: R.make_point(name, T, K) for name in R.POINTS})
+    for N, T, Gr in ((67, 30, 3), (130, 65, 4)):
+        y, e, x, group = RG.make_case(N, T, Gr)
+        handle(f"N{N}_T{T}_G{Gr}", _native.SurvivalGroups(y, e, x, group, Gr, RG.PRIORS), {name: RG.make_point(name, T, Gr) for name in RG.POINTS})
+    y, e, xs = _simulated()
+    yg, eg, xg, group = simulate(N=300, T=6, seed=3, a=(0.5, 1.5, 2.5), b=2.0)
+    for tag, model in (("fit", survival.SurvivalModel(y, e, xs, ("S",))), ("fit_groups", survival.SurvivalGroupsModel(yg, eg, xg, "S", group))):
+        fit = survival.sample(model, tune=20, draws=20, chains=2, seed=0)
+        w = survival.waic(model, fit)  # records its arrays in the fit
+        model.close()
+        res.update({f"{tag}/{k}": np.asarray(v) for k, v in fit.items()})
+        res.update({f"{tag}/waic_{k}": np.asarray(w[k]) for k in ("elpd_waic", "p_waic", "se")})
+    np.savez(os.path.join(out, "survival.npz"), **res)
+    print("survival", len(res), "arrays", flush=True)
 
 
 def compare(a, b):
     files = sorted(os.listdir(a))
-    assert files == sorted(os.listdir(b)) and len(files) == 5, (files, sorted(os.listdir(b)))
+    assert files == sorted(os.listdir(b)) and len(files) == 6, (files, sorted(os.listdir(b)))
     bad = n = nbytes = 0
     for f in files:
         za, zb = np.load(os.path.join(a, f), allow_pickle=False), np.load(os.path.join(b, f), allow_pickle=False)
