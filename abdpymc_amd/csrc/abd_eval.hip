@@ -315,21 +315,24 @@ int flush_ring(abd_ctx* c) {
   return flush_pending(c);
 }
 
+int rows_never_tagged(abd_ctx* c, int slot, int first, int n, double tag) {
+  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
+  for (int q = first; q < n; ++q)
+    if (rows[(size_t)q * ABD_NOUT + ABD_NOUT - 1] != tag) return fail(ABD_ERR_STATE, "result row %d of slot %d never received its completion tag", q, slot);
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  return ABD_OK;
+}
+
 // Wait for the rows of a synchronous call (written into mapped host memory) by polling their completion tag;
 // falls back to a stream synchronise if it does not show up quickly.
 int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st) {
-  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
-  // every row is written by its own workgroup (row, system-scope fence, tag), in no particular order: wait for
-  // each tag.  Rows of an earlier group of the same call carry a smaller tag and count as landed once a later
-  // group's rows are there (groups complete in stream order), so only the last group's tag value is awaited.
+  // every row is written by its own workgroup, in no particular order: wait for each tag (rows_missing).  Rows of an earlier
+  // group of the same call carry a smaller tag and count as landed once a later group's rows are there (groups complete in
+  // stream order), so only the last group's tag value is awaited.
   const int first = ((n - 1) / ABD_MAX_BATCH) * ABD_MAX_BATCH;
   int k = n - 1;
   for (int spin = 0; spin < 2000000; ++spin) {
-    while (k >= first && rows[(size_t)k * ABD_NOUT + ABD_NOUT - 1] == tag) --k;
-    if (k < first) {
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      return ABD_OK;
-    }
+    if ((k = rows_missing(c, slot, first, k, tag)) < first) return ABD_OK;
     __builtin_ia32_pause();
   }
   // the tag did not show within ~2 M polls (tens of ms): the stream synchronise below is always correct, but it should
@@ -337,10 +340,7 @@ int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st) {
   // lacks its tag afterwards is an error, not a result
   __atomic_fetch_add(&c->wait_fallbacks, (int64_t)1, __ATOMIC_RELAXED);
   HIP_TRY(hipStreamSynchronize(st ? st : c->stream));
-  for (int q = first; q < n; ++q)
-    if (rows[(size_t)q * ABD_NOUT + ABD_NOUT - 1] != tag) return fail(ABD_ERR_STATE, "result row %d of slot %d never received its completion tag", q, slot);
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return ABD_OK;
+  return rows_never_tagged(c, slot, first, n, tag);
 }
 
 // Wait until every row of a stream-ordered slot carries its completion tag (the rows are in mapped host memory).

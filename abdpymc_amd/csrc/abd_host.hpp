@@ -2,7 +2,8 @@
 //   abd_context.hip  context life cycle, discrete state, Deterministics, the closed-form host terms (priors, Jacobians)
 //   abd_eval.hip     evaluation launches (dense panels / observation lists), pipes, completion tags, timing
 //   abd_gibbs.hip    the device Gibbs sweep
-//   abd_sampler.hip  the native compound sampler (NUTS state machine in abd_nuts.hpp + the sweep)
+//   abd_sampler.hip  the native compound sampler (NUTS state machine in abd_nuts.hpp + the sweep): creation and the run loops
+//   abd_sampler_summaries.hip  what a caller of the sampler switches on before the first run and reads after one (abd_sampler.hpp)
 //   abd_survival.hip the survival models of a finished run (a handle of its own, nothing of an abd_ctx)
 // Nothing here is part of the C ABI (include/abd_hip.h).
 //
@@ -330,6 +331,16 @@ int flush_pipe(abd_ctx* c, int pi);
 int join_pipes(abd_ctx* c);
 int flush_pending(abd_ctx* c);
 int flush_ring(abd_ctx* c);
+// Rows k, k - 1, ... first of result slot `slot` (mapped host memory), each written by its own workgroup as row, system-scope
+// fence, tag: the last of them that does not carry `tag` yet, or first - 1 (and an acquire fence) when all have landed.  Never blocks.
+inline int rows_missing(const abd_ctx* c, int slot, int first, int k, double tag) {
+  volatile const double* rows = c->out.host() + (size_t)slot * c->n_slots * ABD_NOUT;
+  while (k >= first && rows[(size_t)k * ABD_NOUT + ABD_NOUT - 1] == tag) --k;
+  if (k < first) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  return k;
+}
+// once the rows' stream has been synchronised: ABD_OK if rows [first, n) of the slot carry `tag`, else the first that never got it
+int rows_never_tagged(abd_ctx* c, int slot, int first, int n, double tag);
 int wait_rows(abd_ctx* c, int slot, int n, double tag, hipStream_t st = nullptr);
 // queue the evaluation of n chains at theta into result slot `slot` (groups of <= ABD_MAX_BATCH chains, one launch each)
 int enqueue_slot(abd_ctx* c, const Caller& who, int slot, int n, const int32_t* chains, const double* theta, bool grad);

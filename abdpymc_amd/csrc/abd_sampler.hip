@@ -1,153 +1,10 @@
 // abd_sampler.hip -- the native compound sampler of the C ABI (abd_sampler_*; include/abd_hip.h): the step pm.sample
 // assigns to this model (abd.py:921-922) -- NUTS on the 17 continuous variables (abd_nuts.hpp), the device Gibbs sweep on
 // [i_raw, ab_s_waner], recording of the Deterministics -- run against the evaluation path without leaving the library.
-#include "abd_host.hpp"
-#include "abd_nuts.hpp"
+#include "abd_sampler.hpp"
 
 #include <deque>
 #include <memory>
-
-// The per-draw summaries of a sampler (abd_sampler_enable_*): each is its device buffers, what it was enabled with and the
-// layout of the buffers -- stated once, as the offset of chain j's part (j = n: the buffer's length), for the enable function,
-// the launch and the read-out alike.  planned(): the draws it was sized for; launch(): draw d = iteration - tune of sampler
-// chain j (slot `chain`, point q) on stream st.
-struct CurvesSummary {  // abd_curves.hpp: every draw's row, and every chain's own slab rows (the chains' launches run side by side)
-  DevBuf<unsigned long long> rows, scratch;
-  int64_t capacity = 0;
-  double thr_s = 0.0, thr_n = 0.0;
-  bool on() const { return rows != nullptr; }
-  int64_t planned() const { return capacity; }
-  size_t row_at(const abd_ctx* c, int j, int64_t d) const { return ((size_t)j * capacity + (size_t)d) * abdi::curves_row_cols(c); }
-  size_t scratch_at(const abd_ctx* c, int j) const { return (size_t)j * abdi::curves_scratch_cols(c); }
-  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
-    return abdi::launch_curves(c, chain, q, thr_s, thr_n, st, scratch + scratch_at(c, j), rows + row_at(c, j, d));
-  }
-};
-
-struct RiskSummary {  // abd_risk.hpp: every draw's table of 32 G 32-bit counts, and every chain's own packed slab rows
-  DevBuf<uint32_t> tables;
-  DevBuf<unsigned long long> scratch;
-  int64_t capacity = 0;
-  abd_risk_spec spec = {};
-  bool on() const { return tables != nullptr; }
-  int64_t planned() const { return capacity; }
-  size_t table_at(const abd_ctx* c, int j, int64_t d) const { return ((size_t)j * capacity + (size_t)d) * abdi::risk_table_cols(c); }
-  size_t scratch_at(const abd_ctx* c, int j) const { return (size_t)j * abdi::risk_scratch_cols(c); }
-  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
-    return abdi::launch_risk(c, chain, q, spec, st, scratch + scratch_at(c, j), tables + table_at(c, j, d));
-  }
-};
-
-// abd_diag.hpp: convergence accumulators over all draws, individual-major planes per chain -- [n][2][7][G*N] of the two titers
-// (ab_n_mu, then ab_s_mu), [n][G*N][4] and [n][G*N] of i -- and one plane [G*N] of staging for the read-out
-struct DiagSummary {
-  DevBuf<double> tit;
-  DevBuf<uint32_t> inf;
-  DevBuf<unsigned long long> cb2, stage;
-  int64_t draws = 0, H = 0, L = 0;  // planned draws D, H = D / 2, batch length
-  bool on() const { return tit != nullptr; }
-  int64_t planned() const { return draws; }
-  static size_t cells(const abd_ctx* c) { return (size_t)c->G * c->N; }
-  size_t tit_at(const abd_ctx* c, int j, int titer = 0, int plane = 0) const { return (((size_t)j * 2 + titer) * 7 + plane) * cells(c); }
-  size_t inf_at(const abd_ctx* c, int j) const { return (size_t)j * 4 * cells(c); }
-  size_t cb2_at(const abd_ctx* c, int j) const { return (size_t)j * cells(c); }
-  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, hipStream_t st) const {
-    if (d >= 2 * H) return ABD_OK;  // (an odd D: the last draw belongs to neither half)
-    return abdi::launch_diag(c, chain, q, st, d, H, L, tit + tit_at(c, j), inf + inf_at(c, j), cb2 + cb2_at(c, j));
-  }
-};
-
-// abd_timeline.hpp: per-individual timelines over all draws, individual-major planes per chain -- [n][2][G*N][32] words of the
-// two titers' histograms (ab_n_mu, then ab_s_mu), [n][G*N][2] inf and cum, [n][N][8] ninf -- and the read-out's staging
-struct TimelineSummary {
-  DevBuf<uint32_t> hist, cell, ninf;
-  DevBuf<unsigned long long> stage;
-  size_t stage_bytes = 0;
-  int64_t draws = 0;  // planned draws
-  double range_n[2] = {0.0, 0.0}, range_s[2] = {0.0, 0.0};
-  bool on() const { return hist != nullptr; }
-  int64_t planned() const { return draws; }
-  size_t hist_at(const abd_ctx* c, int j, int titer = 0) const { return ((size_t)j * 2 + titer) * c->G * c->N * (ABD_TIMELINE_BINS / 2); }
-  size_t cell_at(const abd_ctx* c, int j) const { return (size_t)j * 2 * c->G * c->N; }
-  size_t ninf_at(const abd_ctx* c, int j) const { return (size_t)j * ABD_TIMELINE_NINF * c->N; }
-  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t, hipStream_t st) const {
-    return abdi::launch_timeline(c, chain, q, range_n, range_s, st, hist + hist_at(c, j, 0), hist + hist_at(c, j, 1), cell + cell_at(c, j),
-                                 ninf + ninf_at(c, j));
-  }
-};
-
-struct abd_sampler {
-  ~abd_sampler();  // quiesces; then the members go in reverse order (abd_host.hpp)
-  abd_ctx* c = nullptr;
-  int n = 0;
-  abd_sampler_opts o{};
-  std::vector<int32_t> chains;
-  std::vector<abdnuts::AdaptiveNuts> ch;
-  int64_t it = 0;
-  int64_t n_accumulated = 0;  // draws in d_sums
-  int64_t rec_chunk = 0;      // recording: device staging of up to rec_chunk draws per chain, [n][rec_chunk][...] per variable
-  bool ran = false;  // abd_sampler_run* has been called (abd_sampler_enable_pointwise / _predictive are refused after that)
-  std::vector<double> lp, gr;  // starting points' logp / gradient
-  std::vector<abdnuts::LeapfrogLog> lf_log;  // abd_sampler_enable_leapfrog_log: chain k's log, ch[k].nuts points at it (empty: off)
-  int unit = 1;                // chains per independent unit (sampler_run_units)
-  int threads = 1;  // host threads that drive the units (sampler_run_units)
-  // Leapfrog trains of observation lists (abd_types.hpp: TrainArgs): one chain per unit, diagonal metric.  Every evaluation of such a
-  // sampler is a train launch -- it assembles logp and gradient on the device and leaves the next point of the half for
-  // the launch queued behind it -- and the host keeps up to `lookahead` launches of a half queued ahead of the record it
-  // is waiting for, so a chain's leapfrogs follow each other at the device's pace, not at the host's round trip.
-  bool trains = false;
-  bool unit_tags = false;  // the units' launches are tagged from the context's per-unit sequences (several host threads)
-  int lookahead = 8;
-  static constexpr int kTrainRing = 32;  // records per unit: > lookahead + 1
-  struct TrainUnit {
-    DevBuf<TrainPoint> slots;        // [2]
-    MappedBuf<TrainRecord> rec;      // [kTrainRing]
-    uint64_t prod = 0, cons = 0;     // launches queued / records taken (or given up: the rest of a half that ended early)
-    double tags[kTrainRing] = {};
-    int next_slot = 0;               // the slot the last queued launch leaves its successor's point in
-    bool last_own_record = true;     // did the launch queued last write its own record (else its successor passes it on)
-    int queued_in_half = 0;          // launches queued for the half that is being built
-  };
-  std::vector<TrainUnit> tu;
-  // Leapfrog trains of dense cohorts (abd_types.hpp: TrainChain; abd_train.hpp): units of 1, 2 or 4 chains share their
-  // launches, the device goes on from one half of a tree into the next by itself, the host's tree logic follows behind on
-  // the records, and a chain's sweep runs on a stream of its own beside the unit's launches for the other chains.
-  bool dtrains = false;
-  int dtrain_blocks = 0;     // workgroups (with a range) of a unit's launch: the unit's fixed shape
-  int dtrain_lookahead = 3;  // steps of a unit the host keeps queued ahead of the oldest record it has not seen
-  struct DChain {
-    Stream side;                     // the chain's sweep and its recording kernels
-    DevBuf<TrainChain> st;
-    MappedBuf<TrainRecord> ring;     // [ABD_TRAIN_RING]
-    MappedBuf<TrainBegin> begin;     // [kBeginBlocks]
-    // [0], [1] the sweep's accepted / proposed counts, [2] (as a double) the tag of the sweep they belong to
-    MappedBuf<unsigned long long> done;
-    double sweep_tag = 0.0;          // tag of the chain's last sweep (1, 2, 3, ...)
-    int64_t n_rec = 0;               // records the steps queued so far produce (index of the next one)
-    int64_t n_begin = 0;             // transitions handed over so far
-  };
-  static constexpr int kBeginBlocks = 4;
-  std::vector<DChain> dc;
-  // device buffers, declared behind the trains' streams: they go first
-  DevBuf<double> d_sums;  // [n][3][G*N]
-  DevBuf<double> d_rec_mu;   // [2][n][rec_chunk][G*N]  (ab_n_mu, ab_s_mu)
-  DevBuf<int8_t> d_rec_i8;   // [2][n][rec_chunk][G*N]  (i_raw, i) then [n][rec_chunk][N] (waner)
-  DevBuf<double> d_rec_ll;   // [n][rec_chunk][K_s + K_n]  pointwise log-likelihood, the device's sorted order (S, then N)
-  // pointwise log-likelihood statistics of every draw (abd_readings.hpp: LogLik): [n][4][K_s + K_n] running max, scaled sum
-  // of exp, mean, M2 per reading
-  DevBuf<double> d_pw_acc;
-  // the same statistics of every individual's joint log-likelihood T_j (abd_individual.hpp): [n][4][N]
-  DevBuf<double> d_ind_acc;
-  DevBuf<double> d_rec_yrep;  // [n][rec_chunk][K_s + K_n]  posterior predictive replicates, the device's sorted order
-  // posterior predictive check statistics of every draw (abd_readings.hpp: Predictive): [n][3][K_s + K_n] mean, M2 of the
-  // predictive mean, mean tail probability per reading
-  DevBuf<double> d_pp_acc;
-  // the per-draw summaries (above), in the order queue_draw launches them
-  CurvesSummary curves;
-  DiagSummary diag;
-  TimelineSummary timelines;
-  RiskSummary risk;
-};
 
 namespace {
 
@@ -261,81 +118,160 @@ bool train_ready(const abd_sampler* s, int u) {
   return true;
 }
 
-// Record staging of one per-reading row per draw ([n][rec_chunk][K_s + K_n]: d_rec_ll, d_rec_yrep), allocated on first use
-int alloc_rec_rows(abd_sampler* s, DevBuf<double>& d, const char* what) {
-  if (d) return ABD_OK;
-  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
-  if (const hipError_t e = d.alloc(std::max<size_t>(1, (size_t)s->n * s->rec_chunk * Kt)))
-    return fail(ABD_ERR_HIP, "record staging (%s): %s", what, hipGetErrorString(e));
+// ---- The two ways a unit of sampler_run_units gets an evaluation (RowEval, TrainEval), with the same four operations ----
+//   eval(u, m, ids, th)   evaluate the points th[0 .. m) of the chains with slot ids ids[0 .. m)
+//   grow(u, un)           launch the next leapfrog of every tree of the unit that is still growing; un.m: how many are
+//   ready(u)              has the oldest outstanding result of the unit landed?  Never blocks.
+//   take(u, lp, gr, ...)  that result: logp and gradient per chain evaluated and, from a train, the successor's point
+// and for the starting points' blocking wait (wait_eval): kSpins, the polls before it synchronises the unit's stream, and
+// never(u), the error of a result that is not there even then.  s->trains is asked where a back-end is chosen, nowhere else.
+
+// One unit of sampler_run_units: chains [lo, hi) of the sampler move through their iterations together
+struct Unit {
+  int lo = 0, hi = 0, m = 0, state = 0;  // m: chains in the evaluation that is outstanding, who[0 .. m) of the sampler
+  int64_t k = 0;                         // iterations completed in this call
+  std::chrono::steady_clock::time_point t_queued;  // profile: when its last evaluation was about to be queued
+  std::vector<int32_t> ids, who;
+  std::vector<double> th, lp, gr;
+  Unit(int lo, int hi) : lo(lo), hi(hi), ids(hi - lo), who(hi - lo), th((hi - lo) * ABD_N_THETA), lp(hi - lo), gr((hi - lo) * ABD_N_THETA) {}
+  // ids, who, th, m of the next evaluation: `growing` -- the chains whose tree is still growing, at the point it asks for;
+  // else all of them, at the point they are at
+  void stage(abd_sampler* s, bool growing) {
+    m = 0;
+    for (int j = lo; j < hi; ++j) {
+      abdnuts::Nuts& nu = s->ch[(size_t)j].nuts;
+      if (growing && !nu.active) continue;
+      ids[(size_t)m] = s->chains[(size_t)j];
+      who[(size_t)m] = j;
+      std::memcpy(th.data() + (size_t)m * ABD_N_THETA, growing ? nu.request() : nu.q, sizeof(double) * ABD_N_THETA);
+      ++m;
+    }
+  }
+};
+
+// Result rows: one evaluation launch for the unit's chains into its private rows (slot kSyncSlot + u), tagged from the unit's
+// own sequence when several host threads drive the units, else from the context's
+struct RowEval {
+  static constexpr long kSpins = 2000000;
+  abd_sampler* s;
+  bool unit_seq;
+  std::vector<std::pair<int, double>> out;  // per unit: the rows of its last launch and their tag
+  RowEval(abd_sampler* s, bool unit_seq) : s(s), unit_seq(unit_seq), out((size_t)n_units(s)) {}
+  int eval(int u, int m, const int32_t* ids, const double* th) {
+    abd_ctx* c = s->c;
+    double* seqp = unit_seq ? &c->unit_seq[(size_t)u] : nullptr;
+    if (int rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u), seqp}, kSyncSlot + u, m, ids, th, true)) return rc;
+    out[(size_t)u] = {m, seqp ? *seqp : c->seq};
+    return ABD_OK;
+  }
+  int grow(int u, Unit& un) {
+    un.stage(s, true);
+    return un.m ? eval(u, un.m, un.ids.data(), un.th.data()) : ABD_OK;
+  }
+  bool ready(int u) const { return rows_missing(s->c, kSyncSlot + u, 0, out[(size_t)u].first - 1, out[(size_t)u].second) < 0; }
+  int take(int u, double* lp, double* gr, const double*&, const double*&) { return fetch_slot(s->c, kSyncSlot + u, lp, gr); }
+  int never(int u) const { return rows_never_tagged(s->c, kSyncSlot + u, 0, out[(size_t)u].first, out[(size_t)u].second); }
+};
+
+// Observation-list trains (abd_sampler::trains; one chain per unit): every evaluation is a train launch that assembles its
+// own result into the unit's record ring, a plain one with ve = 0
+struct TrainEval {
+  static constexpr long kSpins = 4000000;
+  abd_sampler* s;
+  const double* metric = nullptr;  // of a plain evaluation (it cannot tell at ve = 0); nullptr: the chain's own
+  int eval(int u, int, const int32_t*, const double* th) {
+    return train_launch(s, u, th, nullptr, 0.0, metric ? metric : s->ch[(size_t)u].nuts.inv_mass, true);
+  }
+  int grow(int u, Unit& un) {
+    abdnuts::Nuts& nu = s->ch[(size_t)u].nuts;
+    abd_sampler::TrainUnit& t = s->tu[(size_t)u];
+    un.m = nu.active ? 1 : 0;
+    if (!nu.active) {
+      t.cons = t.prod;  // what is still queued for a half that ended early is never read
+      return ABD_OK;
+    }
+    un.who[0] = u;
+    if (nu.n_leaf == 0) return train_begin(s, u);  // a new half: its first point is staged on the host
+    if (t.queued_in_half < nu.n_target) {          // the half goes on: keep the look-ahead full
+      t.queued_in_half += 1;
+      return train_launch(s, u, nullptr, nullptr, nu.signed_step(), nu.inv_mass, s->lookahead == 0 || t.queued_in_half == nu.n_target);
+    }
+    return ABD_OK;
+  }
+  bool ready(int u) const { return train_ready(s, u); }
+  int take(int u, double* lp, double* gr, const double*& next_q, const double*& next_p_half) {
+    abd_sampler::TrainUnit& t = s->tu[(size_t)u];
+    const TrainRecord& r = t.rec.host()[t.cons % abd_sampler::kTrainRing];
+    *lp = r.lp;
+    std::memcpy(gr, r.g, sizeof(double) * ABD_N_THETA);
+    next_q = r.next_theta;  // (the slot is not written again before kTrainRing more launches have been queued)
+    next_p_half = r.next_p_half;
+    t.cons += 1;
+    return ABD_OK;
+  }
+  int never(int u) const { return fail(ABD_ERR_STATE, "the record of chain %d's starting point never received its tag", s->chains[(size_t)u]); }
+};
+
+// Block until unit u's evaluation has landed: polls ready(); a result that has not shown after kSpins polls (tens of ms) is
+// waited for with a synchronise of the unit's stream, which is counted (abd_wait_fallbacks), and is an error if it is not there then
+template <typename Eval>
+int wait_eval(Eval& ev, int u) {
+  abd_ctx* c = ev.s->c;
+  for (long spin = 0; !ev.ready(u); ++spin) {
+    if (spin < Eval::kSpins) {
+      __builtin_ia32_pause();
+      continue;
+    }
+    __atomic_fetch_add(&c->wait_fallbacks, (int64_t)1, __ATOMIC_RELAXED);
+    HIP_TRY(hipStreamSynchronize(c->pipe[unit_pipe(c, u)].st));
+    return ev.ready(u) ? ABD_OK : ev.never(u);
+  }
   return ABD_OK;
 }
 
-// A per-chain block of `rows` x `cols` accumulators (abd_sampler_enable_pointwise / _predictive: K_s + K_n columns;
-// _individual_loglik: N): the old one freed, a new one allocated and zeroed if `accumulate` (after the upload of the reading
-// order if the launches read it: `order`)
-int enable_acc(abd_sampler* s, DevBuf<double>& acc, int rows, size_t cols, int32_t accumulate, bool order, const char* what) {
-  if (s->ran) return fail(ABD_ERR_STATE, "%s accumulation must be enabled before the first abd_sampler_run call", what);
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  if (acc) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    acc.reset();
+// logp and gradient at the starting points, unit by unit through the launch shape the units will use
+template <typename Eval>
+int start_points(Eval ev, const double* theta0) {
+  abd_sampler* s = ev.s;
+  for (int u = 0, lo = 0; lo < s->n; ++u, lo += s->unit) {
+    const double *next_q, *next_p_half;
+    if (int rc = ev.eval(u, std::min(s->unit, s->n - lo), s->chains.data() + lo, theta0 + (size_t)lo * ABD_N_THETA)) return rc;
+    if (int rc = wait_eval(ev, u)) return rc;
+    if (int rc = ev.take(u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA, next_q, next_p_half)) return rc;
   }
-  if (!accumulate) return ABD_OK;
-  if (order)
+  return ABD_OK;
+}
+
+// Record staging, allocated at the first call that records: up to rec_chunk draws per chain of the Deterministics and the
+// discrete state, and -- each at the first call that asks for it -- one per-reading row per draw ([n][rec_chunk][K_s + K_n])
+// of the pointwise log-likelihood and of the posterior predictive replicates
+int alloc_record_staging(abd_sampler* s, bool with_ll, bool with_yrep) {
+  abd_ctx* c = s->c;
+  const size_t n = (size_t)s->n, cells = (size_t)c->G * c->N, Kt = (size_t)(c->s.K + c->n.K);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!s->d_rec_mu) {
+    const size_t per_draw = n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0) +
+                                 (with_yrep ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
+    s->rec_chunk = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(((size_t)256 << 20) / per_draw)));
+    DevBuf<double> mu;  // (the sampler takes both or neither: d_rec_mu is the "allocated" flag)
+    DevBuf<int8_t> i8;
+    HIP_TRY(mu.alloc(2 * n * s->rec_chunk * cells));
+    HIP_TRY(i8.alloc(2 * n * s->rec_chunk * cells + n * s->rec_chunk * c->N));
+    s->d_rec_mu = std::move(mu);
+    s->d_rec_i8 = std::move(i8);
+  }
+  auto rows = [&](DevBuf<double>& d, const char* what) -> int {
+    if (d) return ABD_OK;
+    if (const hipError_t e = d.alloc(std::max<size_t>(1, n * s->rec_chunk * Kt)))
+      return fail(ABD_ERR_HIP, "record staging (%s): %s", what, hipGetErrorString(e));
+    return ABD_OK;
+  };
+  if (with_ll)
+    if (int rc = rows(s->d_rec_ll, "pointwise log-likelihood")) return rc;
+  if (with_yrep) {
     if (int rc = upload_order(c)) return rc;
-  const size_t n_acc = std::max<size_t>(1, (size_t)s->n * rows * cols);
-  DevBuf<double> fresh;  // (acc stays empty unless the block is there and zeroed)
-  const hipError_t e = fresh.alloc_zero(n_acc, c->stream);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "%s accumulators: %zu bytes of device memory", what, n_acc * sizeof(double));
+    if (int rc = rows(s->d_rec_yrep, "posterior predictive")) return rc;
   }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "%s accumulators: %s", what, hipGetErrorString(e));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  acc = std::move(fresh);
-  return ABD_OK;
-}
-
-// Chain k's block of `rows` x (K_s + K_n) accumulators, once every update has landed, as three rows in the caller's reading
-// order (S readings, then N) into out: row v of sorted reading r is at(h, v, r) of the host copy h; n_draws: the draws it holds
-template <typename At>
-int read_acc(abd_sampler* s, const double* acc, int32_t k, int rows, const char* what, double* out, int64_t* n_draws, At at) {
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!acc) return fail(ABD_ERR_STATE, "%s accumulation is not enabled (abd_sampler_enable_%s)", what, what);
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
-    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
-  const size_t Ks = (size_t)c->s.K, Kt = Ks + (size_t)c->n.K;
-  std::vector<double> h((size_t)rows * Kt);
-  if (Kt) HIP_TRY(hipMemcpy(h.data(), acc + (size_t)k * rows * Kt, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  const ReadingOut o[3] = {{out, out + Ks}, {out + Kt, out + Kt + Ks}, {out + 2 * Kt, out + 2 * Kt + Ks}};
-  scatter_readings(c, o, [hp = h.data(), at](int v, size_t r) { return at(hp, v, r); });
-  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
-  return ABD_OK;
-}
-
-// What the four abd_sampler_enable_* do alike once their arguments are good: refuse after the first run call, drop what the
-// summary holds (nothing has been launched on it: the sampler has not run) and -- want -- let `alloc` fill a fresh one (its
-// buffers on the context's stream, its parameters; returns the hipError_t), which the sampler takes whole or not at all.
-// bytes: what an out-of-memory message names.
-template <typename S, typename Alloc>
-int enable_summary(abd_sampler* s, S& summary, const char* name, bool want, size_t bytes, Alloc alloc) {
-  if (s->ran) return fail(ABD_ERR_STATE, "%s must be enabled before the first abd_sampler_run call", name);
-  HIP_TRY(hipSetDevice(s->c->device));
-  summary = S();
-  if (!want) return ABD_OK;
-  S fresh;
-  const hipError_t e = alloc(fresh);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "%s: %zu bytes of device memory", name, bytes);
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "%s: %s", name, hipGetErrorString(e));
-  HIP_TRY(hipStreamSynchronize(s->c->stream));  // (the buffers' zeroes)
-  summary = std::move(fresh);
   return ABD_OK;
 }
 
@@ -409,7 +345,7 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
   // the starting points through the launch shape the units will use
   if (hipSetDevice(c->device) != hipSuccess) return fail(ABD_ERR_HIP, "hipSetDevice failed");
   if (int rc = flush_ring(c)) return rc;
-  if ((n + s->unit - 1) / s->unit > 1 && tune_int("ABD_PROBE_QUEUES", 1) != 0)
+  if (n_units(s) > 1 && tune_int("ABD_PROBE_QUEUES", 1) != 0)
     if (int rc = probe_stream_queues(c)) return rc;
   s->trains = trains_ok && !c->dense && s->unit == 1;
   if (s->dtrains) {
@@ -419,9 +355,8 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
     // per CU are slower again: profiles/r04/b_train_grid_*.txt): chains finish their trees and iterations at different times, and
     // a unit that is alone for a while gets through its launches faster on the larger grid.  A unit that is alone for the whole run
     // takes four per CU where its ranges are long enough to pay for the set-up (config 5: 77 gap rows per range)
-    const int n_units = (n + s->unit - 1) / s->unit;
     int per_cu = std::min(2, c->dbpc);
-    if (n_units == 1) {
+    if (n_units(s) == 1) {
       const int64_t rows = (int64_t)c->n_lg * c->G, nsub = ABD_WAVES_PER_BLOCK / std::max(1, s->unit);
       if (rows / ((int64_t)c->n_cu * c->dbpc * nsub) >= 32) per_cu = c->dbpc;
     }
@@ -434,31 +369,9 @@ int abd_sampler_create(abd_ctx* c, int32_t n, const int32_t* chains, const doubl
   s->lookahead = std::max(0, std::min(abd_sampler::kTrainRing - 2, tune_int("ABD_TRAIN_LOOKAHEAD", 8)));
   if (s->trains)
     if (int rc = train_alloc(s)) return rc;
-  for (int u = 0, lo = 0; lo < n; ++u, lo += s->unit) {
-    const int m = std::min(s->unit, n - lo);
-    if (s->trains) {  // every evaluation of this sampler is assembled on the device (see abd_sampler::trains)
-      const double ones[ABD_N_THETA] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-      if (int rc = train_launch(s, u, theta0 + (size_t)lo * ABD_N_THETA, nullptr, 0.0, ones, true)) return rc;
-      for (long spin = 0; !train_ready(s, u); ++spin) {
-        if (spin > 4000000) {
-          __atomic_fetch_add(&c->wait_fallbacks, (int64_t)1, __ATOMIC_RELAXED);
-          if (hipStreamSynchronize(c->pipe[unit_pipe(c, u)].st) != hipSuccess) return fail(ABD_ERR_HIP, "hipStreamSynchronize failed");
-          if (!train_ready(s, u)) return fail(ABD_ERR_STATE, "the record of chain %d's starting point never received its tag", chains[lo]);
-          break;
-        }
-        __builtin_ia32_pause();
-      }
-      abd_sampler::TrainUnit& t = s->tu[(size_t)u];
-      const TrainRecord& r = t.rec.host()[t.cons % abd_sampler::kTrainRing];
-      s->lp[(size_t)lo] = r.lp;
-      std::memcpy(s->gr.data() + (size_t)lo * ABD_N_THETA, r.g, sizeof(double) * ABD_N_THETA);
-      t.cons += 1;
-      continue;
-    }
-    if (int rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u)}, kSyncSlot + u, m, chains + lo, theta0 + (size_t)lo * ABD_N_THETA, true)) return rc;
-    if (int rc = wait_rows(c, kSyncSlot + u, m, c->seq, c->pipe[unit_pipe(c, u)].st)) return rc;
-    if (int rc = fetch_slot(c, kSyncSlot + u, s->lp.data() + lo, s->gr.data() + (size_t)lo * ABD_N_THETA)) return rc;
-  }
+  // (every evaluation of a sampler with trains is assembled on the device: see abd_sampler::trains)
+  const double ones[ABD_N_THETA] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  if (int rc = s->trains ? start_points(TrainEval{s, ones}, theta0) : start_points(RowEval(s, false), theta0)) return rc;
   for (int k = 0; k < n; ++k) {
     if (!std::isfinite(s->lp[(size_t)k])) return fail(ABD_ERR_ARG, "logp at the starting point of chain %d is not finite", chains[k]);
     s->ch[(size_t)k].init(theta0 + (size_t)k * ABD_N_THETA, s->lp[(size_t)k], s->gr.data() + (size_t)k * ABD_N_THETA,
@@ -475,6 +388,8 @@ void abd_sampler_destroy(abd_sampler* s) { delete s; }
 int abd_sampler_run(abd_sampler* s, int64_t n_iter, double* theta, double* stats) {
   return abd_sampler_run_record(s, n_iter, theta, stats, nullptr);
 }
+
+}  // extern "C"
 
 namespace {
 
@@ -525,6 +440,7 @@ struct RunFrame {
   const abd_record* rec;  // nullptr: nothing is recorded
   int64_t thin;           // iterations 0, thin, 2 thin, ... of the call are recorded
   std::chrono::steady_clock::time_point t_begin;
+  bool profile;           // ABD_SAMPLER_PROFILE (arm_profile)
   struct Staging {
     int64_t staged = 0, flushed_to = 0;
   };
@@ -608,14 +524,11 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   // the summaries: every draw, whatever is recorded (abd_sampler_run_record has checked the planned draws)
   if (draw) {
     const int64_t d = iter - s->o.tune;
-    if (s->curves.on())
-      if (int rc = s->curves.launch(c, j, chain, q, d, st)) return rc;
-    if (s->diag.on())
-      if (int rc = s->diag.launch(c, j, chain, q, d, st)) return rc;
-    if (s->timelines.on())
-      if (int rc = s->timelines.launch(c, j, chain, q, d, st)) return rc;
-    if (s->risk.on())
-      if (int rc = s->risk.launch(c, j, chain, q, d, st)) return rc;
+    auto launch = [&](const auto& x) { return x.on() ? x.launch(c, j, chain, q, d, st) : ABD_OK; };
+    if (int rc = launch(s->curves)) return rc;
+    if (int rc = launch(s->diag)) return rc;
+    if (int rc = launch(s->timelines)) return rc;
+    if (int rc = launch(s->risk)) return rc;
   }
   if (rec) sg.staged += 1;
   if (f.rec && (sg.staged == s->rec_chunk || k + 1 == f.n_iter)) {
@@ -630,99 +543,92 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
 // u + 8) share their thread (one thread while abd_kernel_timing is on: the event bookkeeping of enqueue_group belongs to the
 // context, not to a unit)
 int unit_threads(const abd_sampler* s) {
-  const int n_units = (s->n + s->unit - 1) / s->unit;
   int T = 1;
-  while (s->c->timing == 0 && 2 * T <= std::min({s->threads, n_units, (int)kMaxPipes})) T *= 2;
+  while (s->c->timing == 0 && 2 * T <= std::min({s->threads, n_units(s), (int)kMaxPipes})) T *= 2;
   return T;
 }
 
+// ABD_SAMPLER_PROFILE=1 (read once): both run loops report to stderr where the host's time went.  A run call clears the
+// account of the time inside the launch calls (abd_host.hpp: LaunchProfile) and -- `launches`: its loop runs on one thread,
+// which the account needs -- arms it; the call disarms it when its loop has ended.
+bool arm_profile(bool launches) {
+  static const bool profile = env_int("ABD_SAMPLER_PROFILE", 0) != 0;
+  g_launch_profile = LaunchProfile();
+  g_launch_profile.on = profile && launches;
+  return profile;
+}
+
+// The profile of one host thread of sampler_run_units: how much of the wall time it spends handling results and queueing
+// launches, and on what.  With the profile off every member is a test of `on` and nothing else.
+struct Laps {
+  using clk = std::chrono::steady_clock;
+  const bool on;
+  clk::time_point t_begin, t_busy, t_lap;
+  bool busy = false;  // a result has been handled in this pass over the units: the thread is busy until the pass ends
+  double busy_s = 0.0, fetch = 0.0, feed = 0.0, launch = 0.0, wait = 0.0;
+  long handled = 0;
+  explicit Laps(bool on) : on(on) {
+    if (on) t_begin = clk::now();
+  }
+  static double seconds(clk::duration d) { return std::chrono::duration<double>(d).count(); }
+  void result(const Unit& un) {  // a result of the unit has been seen: the laps of its handling start
+    if (!on) return;
+    t_lap = clk::now();
+    if (!busy) t_busy = t_lap;
+    busy = true;
+    wait += seconds(t_lap - un.t_queued);
+    ++handled;
+  }
+  void operator()(double Laps::*account) {  // the time since the last lap goes to `account`
+    if (!on) return;
+    const clk::time_point t = clk::now();
+    this->*account += seconds(t - t_lap);
+    t_lap = t;
+  }
+  void pass_end() {
+    if (on && busy) busy_s += seconds(clk::now() - t_busy);
+    busy = false;
+  }
+  void report(int tid, int T, int n_units, int B) const {
+    if (!on) return;
+    const double wall = seconds(clk::now() - t_begin), per = handled ? 1e6 / handled : 0.0;
+    std::fprintf(stderr, "abd sampler: thread %d of %d, %d units of %d chains in all, %ld results handled in %.3f s: host busy %.0f %% "
+                 "(%.2f us per result: %.2f assemble, %.2f NUTS, %.2f queueing the next evaluation); evaluation queued -> result seen %.2f us\n",
+                 tid, T, n_units, B, handled, wall, 100.0 * busy_s / wall, per * busy_s, per * fetch, per * feed, per * launch, per * wait);
+    if (g_launch_profile.on)
+      std::fprintf(stderr, "abd sampler: inside hipLaunchKernelGGL: %.2f us per evaluation launch (%ld), %.2f us per sum launch (%ld)\n",
+                   g_launch_profile.evals ? 1e6 * g_launch_profile.eval_s / g_launch_profile.evals : 0.0, g_launch_profile.evals,
+                   g_launch_profile.sums ? 1e6 * g_launch_profile.sum_s / g_launch_profile.sums : 0.0, g_launch_profile.sums);
+  }
+};
+
 // The sampler's chains run as independent UNITS of `unit` consecutive chains (1 for large dense cohorts, 4 otherwise;
-// abd_sampler_create), unit u on HIP stream u mod 8 with its own private result rows (slot kSyncSlot + u):
+// abd_sampler_create), unit u on HIP stream u mod 8, its evaluations through the back-end `ev` (above):
 //   tree:      one evaluation launch per leapfrog for the unit's chains whose tree is still growing
 //   sweep:     when all its trees have stopped, the unit's Gibbs sweep and the evaluation at the new state are queued
 //              back to back on its stream (stream order: no host wait in between), counts copied to pinned memory
 //   recording: queued on the same stream behind them
-// The host polls the completion tags of whatever is in flight and moves each unit's state machine on.  No unit waits
+// The host polls for the result of whatever is in flight and moves each unit's state machine on.  No unit waits
 // for another one's trees -- in lock step an iteration lasts as long as the LONGEST tree of all chains -- and the
 // units' launches overlap on the device.  Within a unit the chains share launches (small cohorts are launch-bound:
 // ~6 us of host time per evaluation launch).  Same compound step per chain, same random streams, and the numbers a
 // unit's launch produces depend only on the unit (fixed grid), never on the other units or on timing.
-int sampler_run_units(RunFrame& f) {
+// The units are driven by T host threads, thread t the units u = t (mod T): what a thread touches is private to its
+// units (stream, result rows or record ring, tag sequence, chains, the caller's arrays per chain) or read-only, so the
+// threads share nothing but the HIP runtime.  T = 1 for dense cohorts (the device bounds them), up to 4 for observation
+// lists, where the host's two launches per evaluation (~7 us) are what bounds a single thread.
+template <typename Eval>
+int run_units(RunFrame& f, Eval ev, const int T) {
   abd_sampler* s = f.s;
   abd_ctx* c = s->c;
   const int64_t n_iter = f.n_iter;
-  const int n = s->n, B = s->unit;
-  const int n_units = (n + B - 1) / B;
-  enum { EVAL, POST, DONE };
-  struct Unit {
-    int lo = 0, hi = 0, m = 0, state = EVAL;
-    int64_t k = 0;       // iterations completed in this call
-    double tag = 0.0;
-    std::chrono::steady_clock::time_point t_queued;  // profile: when its last evaluation had been queued
-    std::vector<int32_t> ids, who;
-    std::vector<double> th, lp, gr;
-  };
-  std::vector<Unit> units((size_t)n_units);
-  const int T_all = unit_threads(s);
-  // one completion-tag sequence per unit, disjoint from the context's and from each other's (unit u: (u + 1) 2^40 + k).  It
-  // belongs to the CONTEXT, like the result rows kSyncSlot + u the tags are compared against: monotone for the life of
-  // those rows, whichever sampler drives them
-  while (c->unit_seq.size() < (size_t)n_units) c->unit_seq.push_back((double)(c->unit_seq.size() + 1) * 1099511627776.0);
-  s->unit_tags = T_all > 1;
+  const int U = n_units(s);
+  enum { EVAL, POST, DONE };  // a unit waits for: a leapfrog of its trees; the evaluation behind its sweep; nothing
+  std::vector<Unit> units;
   auto stream_of = [&](int u) -> hipStream_t { return c->pipe[unit_pipe(c, u)].st; };
-  // evaluate the points th[0 .. m) of the unit's chains who[0 .. m)
-  auto launch_eval = [&](int u) -> int {
-    Unit& un = units[(size_t)u];
-    if (s->trains) {  // a plain evaluation (no leapfrog: ve = 0), assembled on the device like every other of this sampler
-      un.t_queued = std::chrono::steady_clock::now();
-      return train_launch(s, u, un.th.data(), nullptr, 0.0, s->ch[(size_t)u].nuts.inv_mass, true);
-    }
-    double* seqp = T_all > 1 ? &c->unit_seq[(size_t)u] : nullptr;
-    int rc = enqueue_slot(c, Caller{Caller::Unit, unit_pipe(c, u), seqp}, kSyncSlot + u, un.m, un.ids.data(), un.th.data(), true);
-    if (rc) return rc;
-    un.tag = seqp ? *seqp : c->seq;
-    un.t_queued = std::chrono::steady_clock::now();
-    return ABD_OK;
-  };
-  auto launch_tree = [&](int u) -> int {  // the next leapfrog of every tree of the unit that is still growing
-    Unit& un = units[(size_t)u];
-    if (s->trains) {
-      abdnuts::Nuts& nu = s->ch[(size_t)u].nuts;
-      abd_sampler::TrainUnit& t = s->tu[(size_t)u];
-      un.m = nu.active ? 1 : 0;
-      if (!nu.active) {
-        t.cons = t.prod;  // what is still queued for a half that ended early is never read
-        return ABD_OK;
-      }
-      un.who[0] = u;
-      un.t_queued = std::chrono::steady_clock::now();
-      if (nu.n_leaf == 0) return train_begin(s, u);  // a new half: its first point is staged on the host
-      if (t.queued_in_half < nu.n_target) {          // the half goes on: keep the look-ahead full
-        t.queued_in_half += 1;
-        return train_launch(s, u, nullptr, nullptr, nu.signed_step(), nu.inv_mass, s->lookahead == 0 || t.queued_in_half == nu.n_target);
-      }
-      return ABD_OK;
-    }
-    un.m = 0;
-    for (int j = un.lo; j < un.hi; ++j) {
-      abdnuts::Nuts& nu = s->ch[(size_t)j].nuts;
-      if (!nu.active) continue;
-      un.ids[(size_t)un.m] = s->chains[(size_t)j];
-      un.who[(size_t)un.m] = j;
-      std::memcpy(un.th.data() + (size_t)un.m * ABD_N_THETA, nu.request(), sizeof(double) * ABD_N_THETA);
-      ++un.m;
-    }
-    if (!un.m) return ABD_OK;
-    return launch_eval(u);
-  };
-  auto ready = [&](int u) -> bool {  // have all result rows of the unit's launch landed? (never blocks)
-    const Unit& un = units[(size_t)u];
-    if (s->trains) return train_ready(s, u);
-    volatile const double* rows = c->out.host() + (size_t)(kSyncSlot + u) * c->n_slots * ABD_NOUT;
-    for (int k = un.m - 1; k >= 0; --k)
-      if (rows[(size_t)k * ABD_NOUT + ABD_NOUT - 1] != un.tag) return false;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    return true;
+  auto grow = [&](int u) -> int {
+    if (f.profile) units[(size_t)u].t_queued = Laps::clk::now();
+    return ev.grow(u, units[(size_t)u]);
   };
   // end of iteration un.k of the unit's chains (points and discrete states are final): outputs, running sums, recording;
   // then the next iteration's first leapfrogs, or DONE
@@ -736,7 +642,7 @@ int sampler_run_units(RunFrame& f) {
     if (!last) {
       for (int j = un.lo; j < un.hi; ++j) s->ch[(size_t)j].begin();
       un.state = EVAL;
-      if (int rc = launch_tree(u)) return rc;
+      if (int rc = grow(u)) return rc;
     }
     for (int j = un.lo; j < un.hi; ++j)
       if (int rc = queue_draw(f, j, un.k, stream_of(u))) return rc;
@@ -744,138 +650,75 @@ int sampler_run_units(RunFrame& f) {
     if (last) un.state = DONE;
     return ABD_OK;
   };
-  for (int u = 0; u < n_units; ++u) {
+  // binary Gibbs-Metropolis on [i_raw, ab_s_waner] of the unit's chains, then logp and gradient at the new states: queued
+  // back to back on the unit's stream
+  auto sweep_and_eval = [&](int u) -> int {
     Unit& un = units[(size_t)u];
-    un.lo = u * B;
-    un.hi = std::min(n, un.lo + B);
-    const size_t cap = (size_t)(un.hi - un.lo);
-    un.ids.resize(cap);
-    un.who.resize(cap);
-    un.th.resize(cap * ABD_N_THETA);
-    un.lp.resize(cap);
-    un.gr.resize(cap * ABD_N_THETA);
-    if (n_iter == 0) {
-      un.state = DONE;
-      continue;
-    }
+    hipStream_t st = stream_of(u);
+    un.stage(s, false);
+    if (int rc = queue_sweep(s, un.lo, un.m, un.ids.data(), un.th.data(), un.k, st)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_counts_chain.host() + 2 * (size_t)un.lo, c->d_counts_chain + 2 * (size_t)un.lo,
+                           (size_t)un.m * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    un.state = POST;
+    if (f.profile) un.t_queued = Laps::clk::now();
+    return ev.eval(u, un.m, un.ids.data(), un.th.data());
+  };
+  for (int u = 0; u < U; ++u) units.emplace_back(u * s->unit, std::min(s->n, (u + 1) * s->unit));
+  for (int u = 0; u < U; ++u) {
+    Unit& un = units[(size_t)u];
+    un.state = n_iter ? EVAL : DONE;
+    if (n_iter == 0) continue;
     for (int j = un.lo; j < un.hi; ++j) s->ch[(size_t)j].begin();
-    if (int rc = launch_tree(u)) return rc;
+    if (int rc = grow(u)) return rc;
   }
-  // The units are driven by T host threads, thread t the units u = t (mod T): what a thread touches is private to its
-  // units (stream, result rows, tag sequence, chains, the caller's arrays per chain) or read-only, so the threads
-  // share nothing but the HIP runtime.  T = 1 for dense cohorts (the device bounds them), up to 4 for observation lists,
-  // where the host's two launches per evaluation (~7 us) are what bounds a single thread.
-  // ABD_SAMPLER_PROFILE=1: how much of the wall time a host thread spends handling results and queueing launches.
-  static const bool profile = env_int("ABD_SAMPLER_PROFILE", 0) != 0;
-  const int T = T_all;
-  g_launch_profile = LaunchProfile();
-  g_launch_profile.on = profile && T == 1;
-  using clk = std::chrono::steady_clock;
   std::atomic<int> first_error{ABD_OK};
   std::vector<std::string> errors((size_t)T);
   auto worker = [&](int tid) -> int {
     if (hipSetDevice(c->device) != hipSuccess) return fail(ABD_ERR_HIP, "hipSetDevice failed");
-    const clk::time_point t_begin = clk::now();
-    clk::time_point t_handle;
-    double busy_s = 0.0, prof_fetch = 0.0, prof_feed = 0.0, prof_launch = 0.0, prof_wait = 0.0;
-    long handled = 0;
+    Laps lap(f.profile);
     for (long spins = 0;;) {
       bool any = false, progressed = false;
       if (first_error.load(std::memory_order_relaxed) != ABD_OK) return ABD_OK;  // another thread failed: stop queueing
-      for (int u = tid; u < n_units; u += T) {
+      for (int u = tid; u < U; u += T) {
         Unit& un = units[(size_t)u];
         if (un.state == DONE) continue;
         any = true;
-        if (progressed && profile) {  // close the previous unit's handling interval
-          busy_s += std::chrono::duration<double>(clk::now() - t_handle).count();
-          t_handle = clk::now();
-        }
-        if (!ready(u)) continue;
-        if (profile && !progressed) t_handle = clk::now();
-        if (profile) prof_wait += std::chrono::duration<double>(clk::now() - un.t_queued).count();
+        if (!ev.ready(u)) continue;
         progressed = true;
-        ++handled;
-        clk::time_point tp0;
-        if (profile) tp0 = clk::now();
+        lap.result(un);
         const double *next_q = nullptr, *next_p_half = nullptr;
-        if (s->trains) {  // the launch assembled its own result: take the record
-          abd_sampler::TrainUnit& t = s->tu[(size_t)u];
-          const TrainRecord& r = t.rec.host()[t.cons % abd_sampler::kTrainRing];
-          un.lp[0] = r.lp;
-          std::memcpy(un.gr.data(), r.g, sizeof(double) * ABD_N_THETA);
-          next_q = r.next_theta;  // (the slot is not written again before kTrainRing more launches have been queued)
-          next_p_half = r.next_p_half;
-          t.cons += 1;
-        } else if (int frc = fetch_slot(c, kSyncSlot + u, un.lp.data(), un.gr.data())) {
-          return frc;
-        }
-        if (profile) {
-          const clk::time_point t1 = clk::now();
-          prof_fetch += std::chrono::duration<double>(t1 - tp0).count();
-          tp0 = t1;
-        }
-        if (un.state == EVAL) {
-          for (int q = 0; q < un.m; ++q)
-            s->ch[(size_t)un.who[(size_t)q]].nuts.feed(un.lp[(size_t)q], un.gr.data() + (size_t)q * ABD_N_THETA, next_q, next_p_half);
-          if (profile) {
-            const clk::time_point t1 = clk::now();
-            prof_feed += std::chrono::duration<double>(t1 - tp0).count();
-            tp0 = t1;
-          }
-          const int lrc = launch_tree(u);
-          if (profile) prof_launch += std::chrono::duration<double>(clk::now() - tp0).count();
-          if (lrc) return lrc;
-          if (un.m) continue;  // some tree of the unit is still growing
-          for (int j = un.lo; j < un.hi; ++j) s->ch[(size_t)j].end_transition();
-          if (!s->o.gibbs) {
-            if (int rc = finish_iteration(u, false)) return rc;
-            continue;
-          }
-          // binary Gibbs-Metropolis on [i_raw, ab_s_waner] of the unit's chains, then logp and gradient at the new
-          // states: queued back to back on the unit's stream
-          hipStream_t st = stream_of(u);
-          un.m = un.hi - un.lo;
-          for (int j = un.lo; j < un.hi; ++j) {
-            un.ids[(size_t)(j - un.lo)] = s->chains[(size_t)j];
-            un.who[(size_t)(j - un.lo)] = j;
-            std::memcpy(un.th.data() + (size_t)(j - un.lo) * ABD_N_THETA, s->ch[(size_t)j].nuts.q, sizeof(double) * ABD_N_THETA);
-          }
-          if (int rc = queue_sweep(s, un.lo, un.m, un.ids.data(), un.th.data(), un.k, st)) return rc;
-          HIP_TRY(hipMemcpyAsync(c->h_counts_chain.host() + 2 * (size_t)un.lo, c->d_counts_chain + 2 * (size_t)un.lo,
-                                 (size_t)un.m * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-          un.state = POST;
-          if (int rc = launch_eval(u)) return rc;
-        } else {  // POST: the sweep and the evaluation behind it are done (the counts landed before: same stream)
+        if (int rc = ev.take(u, un.lp.data(), un.gr.data(), next_q, next_p_half)) return rc;
+        lap(&Laps::fetch);
+        if (un.state == POST) {  // the sweep and the evaluation behind it are done (the counts landed before: same stream)
           for (int q = 0; q < un.m; ++q)
             s->ch[(size_t)un.who[(size_t)q]].nuts.set_point(un.lp[(size_t)q], un.gr.data() + (size_t)q * ABD_N_THETA);
           if (int rc = finish_iteration(u, true)) return rc;
+          continue;
         }
+        for (int q = 0; q < un.m; ++q)
+          s->ch[(size_t)un.who[(size_t)q]].nuts.feed(un.lp[(size_t)q], un.gr.data() + (size_t)q * ABD_N_THETA, next_q, next_p_half);
+        lap(&Laps::feed);
+        const int rc = grow(u);
+        lap(&Laps::launch);
+        if (rc) return rc;
+        if (un.m) continue;  // some tree of the unit is still growing
+        for (int j = un.lo; j < un.hi; ++j) s->ch[(size_t)j].end_transition();
+        if (int rc2 = s->o.gibbs ? sweep_and_eval(u) : finish_iteration(u, false)) return rc2;
       }
-      if (progressed && profile) busy_s += std::chrono::duration<double>(clk::now() - t_handle).count();
+      lap.pass_end();
       if (!any) break;
       if (progressed) {
         spins = 0;
       } else if (++spins > 4000000) {
         __atomic_fetch_add(&c->wait_fallbacks, (int64_t)1, __ATOMIC_RELAXED);  // no tag for tens of ms: synchronise the streams in flight (see abd_wait_fallbacks)
-        for (int u = tid; u < n_units; u += T)
+        for (int u = tid; u < U; u += T)
           if (units[(size_t)u].state != DONE) HIP_TRY(hipStreamSynchronize(stream_of(u)));
         spins = 0;
       } else {
         __builtin_ia32_pause();
       }
     }
-    if (profile) {
-      const double wall = std::chrono::duration<double>(clk::now() - t_begin).count();
-      std::fprintf(stderr, "abd sampler: thread %d of %d, %d units of %d chains in all, %ld results handled in %.3f s: host busy %.0f %% "
-                   "(%.2f us per result: %.2f assemble, %.2f NUTS, %.2f queueing the next evaluation); evaluation queued -> result seen %.2f us\n",
-                   tid, T, n_units, B, handled, wall, 100.0 * busy_s / wall, handled ? 1e6 * busy_s / handled : 0.0,
-                   handled ? 1e6 * prof_fetch / handled : 0.0, handled ? 1e6 * prof_feed / handled : 0.0,
-                   handled ? 1e6 * prof_launch / handled : 0.0, handled ? 1e6 * prof_wait / handled : 0.0);
-      if (g_launch_profile.on)
-        std::fprintf(stderr, "abd sampler: inside hipLaunchKernelGGL: %.2f us per evaluation launch (%ld), %.2f us per sum launch (%ld)\n",
-                     g_launch_profile.evals ? 1e6 * g_launch_profile.eval_s / g_launch_profile.evals : 0.0, g_launch_profile.evals,
-                     g_launch_profile.sums ? 1e6 * g_launch_profile.sum_s / g_launch_profile.sums : 0.0, g_launch_profile.sums);
-    }
+    lap.report(tid, T, U, s->unit);
     return ABD_OK;
   };
   auto run_worker = [&](int tid) {
@@ -892,13 +735,24 @@ int sampler_run_units(RunFrame& f) {
     run_worker(0);
     for (auto& th : pool) th.join();
   }
-  g_launch_profile.on = false;
   if (first_error.load() != ABD_OK) {
     for (int t = 0; t < T; ++t)
       if (!errors[(size_t)t].empty()) return fail(first_error.load(), "%s", errors[(size_t)t].c_str());
     return fail(first_error.load(), "sampler thread failed");
   }
   return ABD_OK;
+}
+
+// ... with the back-end the sampler was created for, and its tags: one completion-tag sequence per unit when several threads
+// drive them, disjoint from the context's and from each other's (unit u: (u + 1) 2^40 + k).  It belongs to the CONTEXT, like
+// the result rows kSyncSlot + u the tags are compared against: monotone for the life of those rows, whichever sampler drives them
+int sampler_run_units(RunFrame& f) {
+  abd_sampler* s = f.s;
+  abd_ctx* c = s->c;
+  const int T = unit_threads(s);
+  while (c->unit_seq.size() < (size_t)n_units(s)) c->unit_seq.push_back((double)(c->unit_seq.size() + 1) * 1099511627776.0);
+  s->unit_tags = T > 1;
+  return s->trains ? run_units(f, TrainEval{s}, T) : run_units(f, RowEval(s, T > 1), T);
 }
 
 // ---- dense cohorts: the compound step over leapfrog-train units (abd_sampler::dtrains) ----
@@ -915,7 +769,7 @@ int sampler_run_trains(RunFrame& f) {
   abd_ctx* c = s->c;
   const int64_t n_iter = f.n_iter;
   const int n = s->n, B = s->unit;
-  const int n_units = (n + B - 1) / B;
+  const int n_units = abdi::n_units(s);
   enum { NEED_BEGIN, TREE, SWEEP, DONE };
   struct Step {
     int64_t idx;     // record index
@@ -935,9 +789,6 @@ int sampler_run_trains(RunFrame& f) {
     std::deque<Step> fifo;
   };
   std::vector<Run> runs((size_t)n);
-  static const bool profile = env_int("ABD_SAMPLER_PROFILE", 0) != 0;
-  g_launch_profile = LaunchProfile();
-  g_launch_profile.on = profile;
   long n_launches = 0, n_records = 0, n_stale = 0;
 
   auto stage_begin = [&](int j, bool eval_first, bool eval_only) {
@@ -1129,9 +980,8 @@ int sampler_run_trains(RunFrame& f) {
   // what the device still has queued beyond the ends of the last trees must be through before anybody reuses the chains' state
   for (int u = 0; u < n_units; ++u) (void)hipStreamSynchronize(c->pipe[unit_pipe(c, u)].st);
   for (int j = 0; j < n; ++j) (void)hipStreamSynchronize(s->dc[(size_t)j].side);
-  g_launch_profile.on = false;
   if (rc_loop != ABD_OK) return rc_loop;
-  if (profile) {
+  if (f.profile) {
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - f.t_begin).count();
     std::fprintf(stderr, "abd sampler (trains): %d units of %d chains, %ld launches, %ld records (%ld stale steps) in %.3f s; %.2f us inside the "
                  "launch call per launch\n", n_units, B, n_launches, n_records, n_stale, wall,
@@ -1141,6 +991,8 @@ int sampler_run_trains(RunFrame& f) {
 }
 
 }  // namespace
+
+extern "C" {
 
 int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double* stats, const abd_record* rec) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
@@ -1159,7 +1011,6 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   const bool with_ll = rec && (rec->ll_s || rec->ll_n);
   const bool with_yrep = rec && (rec->yrep_s || rec->yrep_n);
   const bool recording = rec && (rec->i_raw || rec->ab_s_waner || rec->i || rec->ab_n_mu || rec->ab_s_mu || with_ll || with_yrep);
-  const size_t Kt = (size_t)(c->s.K + c->n.K);
   s->ran = true;
   if (recording) {
     if (rec->thin < 0) return fail(ABD_ERR_ARG, "record: thin=%lld is negative", (long long)rec->thin);
@@ -1167,96 +1018,25 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
     if (rec->first < 0 || rec->first + n_rec > rec->capacity)
       return fail(ABD_ERR_ARG, "record: draws [%lld, %lld) do not fit capacity %lld", (long long)rec->first,
                   (long long)(rec->first + n_rec), (long long)rec->capacity);
-    if (!s->d_rec_mu) {
-      HIP_TRY(hipSetDevice(c->device));
-      const size_t cells = (size_t)c->G * c->N;
-      const size_t per_draw = (size_t)n * (cells * 18 + c->N + (with_ll ? Kt * sizeof(double) : 0) +
-                                           (with_yrep ? Kt * sizeof(double) : 0));  // bytes staged per draw, all chains
-      s->rec_chunk = std::max<int64_t>(1, std::min<int64_t>(256, (int64_t)(((size_t)256 << 20) / per_draw)));
-      DevBuf<double> mu;  // (the sampler takes both or neither: d_rec_mu is the "allocated" flag)
-      DevBuf<int8_t> i8;
-      HIP_TRY(mu.alloc((size_t)2 * n * s->rec_chunk * cells));
-      HIP_TRY(i8.alloc((size_t)2 * n * s->rec_chunk * cells + (size_t)n * s->rec_chunk * c->N));
-      s->d_rec_mu = std::move(mu);
-      s->d_rec_i8 = std::move(i8);
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (with_ll)
-      if (int rc = alloc_rec_rows(s, s->d_rec_ll, "pointwise log-likelihood")) return rc;
-    if (with_yrep) {
-      if (int rc = upload_order(c)) return rc;
-      if (int rc = alloc_rec_rows(s, s->d_rec_yrep, "posterior predictive")) return rc;
-    }
+    if (int rc = alloc_record_staging(s, with_ll, with_yrep)) return rc;
   }
-  RunFrame f{s, n_iter, theta, stats, recording ? rec : nullptr, recording ? std::max<int64_t>(1, rec->thin) : 1, {}, {}};
+  RunFrame f{s, n_iter, theta, stats, recording ? rec : nullptr, recording ? std::max<int64_t>(1, rec->thin) : 1, {}, false, {}};
   f.staging.resize((size_t)n);
   for (auto& sg : f.staging) sg.flushed_to = recording ? rec->first : 0;
   HIP_TRY(hipSetDevice(c->device));
   if (int rc = flush_ring(c)) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));  // whatever the caller queued on the context's stream comes first
+  f.profile = arm_profile(s->dtrains || unit_threads(s) == 1);
   f.t_begin = std::chrono::steady_clock::now();
-  if (int rc = s->dtrains ? sampler_run_trains(f) : sampler_run_units(f)) return rc;
+  const int rc = s->dtrains ? sampler_run_trains(f) : sampler_run_units(f);
+  g_launch_profile.on = false;
+  if (rc) return rc;
   // the context's stream continues behind everything the run queued
   for (int pi = 1; pi < c->n_streams; ++pi) c->pipe[pi].busy = true;
   if (int rc = join_pipes(c)) return rc;
   const int64_t first_draw = std::max<int64_t>(s->it, s->o.tune);
   if (s->d_sums && s->it + n_iter > first_draw) s->n_accumulated += s->it + n_iter - first_draw;
   s->it += n_iter;
-  return ABD_OK;
-}
-
-int abd_sampler_means(abd_sampler* s, int32_t k, double* i_mean, double* mu_n_mean, double* mu_s_mean, int64_t* n_draws) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_sums) return fail(ABD_ERR_STATE, "the sampler was created without accumulate");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const size_t cells = (size_t)c->G * c->N;
-  double* outs[3] = {i_mean, mu_n_mean, mu_s_mean};
-  const double inv = s->n_accumulated ? 1.0 / (double)s->n_accumulated : 0.0;
-  for (int v = 0; v < 3; ++v) {
-    if (!outs[v]) continue;
-    HIP_TRY(hipMemcpy(outs[v], s->d_sums + ((size_t)k * 3 + v) * cells, cells * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < cells; ++e) outs[v][e] *= inv;
-  }
-  if (n_draws) *n_draws = s->n_accumulated;
-  return ABD_OK;
-}
-
-static_assert(abdnuts::LOG_COLS == ABD_LEAPFROG_COLS && abdnuts::LOG_INIT == ABD_LEAPFROG_INIT && abdnuts::LOG_START == ABD_LEAPFROG_START &&
-                  abdnuts::LOG_LEAF == ABD_LEAPFROG_LEAF && abdnuts::D == ABD_N_THETA,
-              "abd_hip.h states the leapfrog log's row as abd_nuts.hpp writes it");
-
-int abd_sampler_enable_leapfrog_log(abd_sampler* s, int64_t capacity_rows_per_chain) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (capacity_rows_per_chain < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity_rows_per_chain);
-  if (s->ran) return fail(ABD_ERR_STATE, "the leapfrog log must be enabled before the first abd_sampler_run call");
-  for (auto& ch : s->ch) ch.nuts.attach_log(nullptr);
-  s->lf_log.clear();
-  if (capacity_rows_per_chain == 0) return ABD_OK;
-  try {
-    s->lf_log.assign((size_t)s->n, abdnuts::LeapfrogLog(capacity_rows_per_chain));
-  } catch (const std::bad_alloc&) {
-    s->lf_log.clear();
-    return fail(ABD_ERR_NOMEM, "leapfrog log: %lld rows for each of %d chains", (long long)capacity_rows_per_chain, s->n);
-  }
-  for (int k = 0; k < s->n; ++k) s->ch[(size_t)k].nuts.attach_log(&s->lf_log[(size_t)k]);  // (row 0: the start point)
-  return ABD_OK;
-}
-
-int abd_sampler_leapfrog_log(abd_sampler* s, int32_t k, int64_t first, int64_t count, double* rows, int64_t* n_total) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (s->lf_log.empty()) return fail(ABD_ERR_STATE, "the leapfrog log is not enabled (abd_sampler_enable_leapfrog_log)");
-  const abdnuts::LeapfrogLog& log = s->lf_log[(size_t)k];
-  const int64_t have = log.stored();
-  if (n_total) *n_total = log.n_total;
-  if (first < 0 || count < 0 || first > have || count > have - first)
-    return fail(ABD_ERR_ARG, "leapfrog log: rows [%lld, %lld) are beyond the %lld the chain holds", (long long)first, (long long)(first + count),
-                (long long)have);
-  if (count && !rows) return fail(ABD_ERR_ARG, "rows is NULL");
-  if (count) std::memcpy(rows, log.rows.data() + (size_t)first * abdnuts::LOG_COLS, (size_t)count * abdnuts::LOG_COLS * sizeof(double));
   return ABD_OK;
 }
 
@@ -1267,330 +1047,6 @@ int abd_sampler_launch_shape(abd_sampler* s, int32_t out[4]) {
   out[1] = s->dtrains ? ABD_TRAINS_DENSE : (s->trains ? ABD_TRAINS_LISTS : ABD_TRAINS_NONE);
   out[2] = s->dtrains ? dense_train_ranges(c, s->dtrain_blocks) : eval_grid(c, s->trains ? Caller::Train : Caller::Unit, s->unit);
   out[3] = s->dtrains ? 1 : unit_threads(s);
-  return ABD_OK;
-}
-
-int abd_sampler_enable_pointwise(abd_sampler* s, int32_t accumulate) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  return enable_acc(s, s->d_pw_acc, 4, (size_t)(s->c->s.K + s->c->n.K), accumulate, false, "pointwise");
-}
-
-int abd_sampler_pointwise_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
-  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
-  // rows M, S, mean, M2 -> M + log S = log sum exp(ll) (-inf before the first draw), mean, M2
-  return read_acc(s, s->d_pw_acc, k, 4, "pointwise", out, n_draws, [Kt](const double* h, int v, size_t r) {
-    return v == 0 ? h[r] + std::log(h[Kt + r]) : h[(v + 1) * Kt + r];
-  });
-}
-
-int abd_sampler_enable_individual_loglik(abd_sampler* s, int32_t accumulate) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  return enable_acc(s, s->d_ind_acc, 4, (size_t)s->c->N, accumulate, false, "individual_loglik");
-}
-
-int abd_sampler_individual_loglik_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws, int64_t* n_readings) {
-  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->d_ind_acc) return fail(ABD_ERR_STATE, "individual_loglik accumulation is not enabled (abd_sampler_enable_individual_loglik)");
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (const auto& d : s->dc)  // (dense trains: the updates run on the chains' side streams)
-    if (d.side) HIP_TRY(hipStreamSynchronize(d.side));
-  const size_t N = (size_t)c->N;
-  std::vector<double> h(4 * N);
-  HIP_TRY(hipMemcpy(h.data(), s->d_ind_acc + (size_t)k * 4 * N, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  // rows M, S, mean, M2 -> M + log S (-inf before the first draw), mean, M2: as abd_sampler_pointwise_stats
-  for (size_t j = 0; j < N; ++j) {
-    out[j] = h[j] + std::log(h[N + j]);
-    out[N + j] = h[2 * N + j];
-    out[2 * N + j] = h[3 * N + j];
-  }
-  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
-  if (n_readings) {
-    for (size_t j = 0; j < N; ++j)
-      n_readings[j] = (int64_t)(c->seg_s[j + 1] - c->seg_s[j]) + (int64_t)(c->seg_n[j + 1] - c->seg_n[j]);
-  }
-  return ABD_OK;
-}
-
-int abd_sampler_enable_predictive(abd_sampler* s, int32_t accumulate) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  return enable_acc(s, s->d_pp_acc, 3, (size_t)(s->c->s.K + s->c->n.K), accumulate, true, "predictive");
-}
-
-int abd_sampler_predictive_stats(abd_sampler* s, int32_t k, double* out, int64_t* n_draws) {
-  if (!s || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  const size_t Kt = (size_t)(s->c->s.K + s->c->n.K);
-  return read_acc(s, s->d_pp_acc, k, 3, "predictive", out, n_draws, [Kt](const double* h, int v, size_t r) { return h[v * Kt + r]; });
-}
-
-int abd_sampler_enable_curves(abd_sampler* s, int64_t capacity, double thr_s, double thr_n) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
-  const abd_ctx* c = s->c;
-  CurvesSummary f;
-  f.capacity = capacity, f.thr_s = thr_s, f.thr_n = thr_n;
-  return enable_summary(s, s->curves, "curves", capacity > 0, f.row_at(c, s->n, 0) * sizeof(unsigned long long), [&](CurvesSummary& x) {
-    x = std::move(f);
-    hipError_t e = x.rows.alloc(x.row_at(c, s->n, 0));
-    if (e == hipSuccess) e = x.scratch.alloc(x.scratch_at(c, s->n));
-    return e;
-  });
-}
-
-int abd_sampler_curves(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* counts, int64_t* n_infections, double* titer_sums,
-                       int64_t* n_draws) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->curves.on()) return fail(ABD_ERR_STATE, "curves are not enabled (abd_sampler_enable_curves)");
-  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
-  if (n_draws) *n_draws = have;
-  if (first < 0 || count < 0 || first > have || count > have - first)
-    return fail(ABD_ERR_ARG, "curves: draws [%lld, %lld) are beyond the %lld the chain has", (long long)first, (long long)(first + count),
-                (long long)have);
-  if (count == 0) return ABD_OK;
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t n_row = curves_row_cols(c), G = (size_t)c->G;
-  std::vector<unsigned long long> h((size_t)count * n_row);
-  HIP_TRY(hipMemcpy(h.data(), s->curves.rows + s->curves.row_at(c, k, first), h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  for (size_t d = 0; d < (size_t)count; ++d)
-    split_curves_row(c, h.data() + d * n_row, counts ? counts + d * 4 * G : nullptr, n_infections ? n_infections + d * 8 : nullptr,
-                     titer_sums ? titer_sums + d * 2 * G : nullptr);
-  return ABD_OK;
-}
-
-int abd_sampler_enable_diagnostics(abd_sampler* s, int64_t planned_draws, int64_t batch_len) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (planned_draws < 0 || planned_draws == 1) return fail(ABD_ERR_ARG, "diagnostics: planned_draws=%lld is neither 0 nor >= 2", (long long)planned_draws);
-  if (planned_draws && batch_len < 1) return fail(ABD_ERR_ARG, "diagnostics: batch_len=%lld is below 1", (long long)batch_len);
-  const abd_ctx* c = s->c;
-  DiagSummary f;
-  f.draws = planned_draws, f.H = planned_draws / 2, f.L = batch_len;
-  const size_t cells = (size_t)c->G * c->N;
-  const size_t bytes =
-      f.tit_at(c, s->n) * sizeof(double) + f.inf_at(c, s->n) * sizeof(uint32_t) + (f.cb2_at(c, s->n) + cells) * sizeof(unsigned long long);
-  return enable_summary(s, s->diag, "diagnostics", planned_draws > 0, bytes, [&](DiagSummary& x) {
-    x = std::move(f);
-    hipError_t e = x.tit.alloc_zero(std::max<size_t>(1, x.tit_at(c, s->n)), c->stream);
-    if (e == hipSuccess) e = x.inf.alloc_zero(std::max<size_t>(1, x.inf_at(c, s->n)), c->stream);
-    if (e == hipSuccess) e = x.cb2.alloc_zero(std::max<size_t>(1, x.cb2_at(c, s->n)), c->stream);
-    if (e == hipSuccess) e = x.stage.alloc(std::max<size_t>(1, cells));
-    return e;
-  });
-}
-
-int abd_sampler_diagnostics(abd_sampler* s, int32_t k, int64_t* i_counts, double* ab_n_mu, double* ab_s_mu, int64_t* info) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->diag.on()) return fail(ABD_ERR_STATE, "diagnostics are not enabled (abd_sampler_enable_diagnostics)");
-  const int64_t H = s->diag.H, L = s->diag.L, B = H / L;
-  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune), n0 = std::min(have, H), n1 = std::min(std::max<int64_t>(0, have - H), H);
-  if (info) {
-    info[0] = n0;
-    info[1] = n1;
-    info[2] = std::min(n0 / L, B) + std::min(n1 / L, B);
-    info[3] = L;
-  }
-  if (!i_counts && !ab_n_mu && !ab_s_mu) return ABD_OK;
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t cells = (size_t)c->G * c->N;
-  // one plane at a time through the staging plane: transposed on the device, copied out (the copy waits for the kernel and
-  // the next kernel for the copy: the context's stream)
-  auto plane = [&](const void* src, int stride, int width, void* out) -> int {
-    if (int rc = launch_diag_export(c, src, stride, width, s->diag.stage, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, s->diag.stage, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ABD_OK;
-  };
-  if (!cells) return ABD_OK;
-  if (i_counts) {
-    const uint32_t* inf = s->diag.inf + s->diag.inf_at(c, k);
-    const int comp[3] = {0, 1, 3};  // c_h0, c_h1, sum_cb of the 16-byte element (cur is not handed out)
-    for (int v = 0; v < 3; ++v)
-      if (int rc = plane(inf + comp[v], 16, 4, i_counts + (size_t)v * cells)) return rc;
-    if (int rc = plane(s->diag.cb2 + s->diag.cb2_at(c, k), 8, 8, i_counts + 3 * cells)) return rc;
-  }
-  double* outs[2] = {ab_n_mu, ab_s_mu};
-  const int planes[6] = {0, 1, 2, 3, 5, 6};  // mean_h0, M2_h0, mean_h1, M2_h1, bm_mean, bm_M2 (cur is not handed out)
-  for (int x = 0; x < 2; ++x) {
-    if (!outs[x]) continue;
-    for (int v = 0; v < 6; ++v)
-      if (int rc = plane(s->diag.tit + s->diag.tit_at(c, k, x, planes[v]), 8, 8, outs[x] + (size_t)v * cells)) return rc;
-  }
-  return ABD_OK;
-}
-
-int abd_sampler_enable_timelines(abd_sampler* s, int64_t planned_draws, double lo_n, double hi_n, double lo_s, double hi_s) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (planned_draws < 0 || planned_draws > ABD_TIMELINE_MAX_DRAWS)
-    return fail(ABD_ERR_ARG, "timelines: planned_draws=%lld outside [0, %d] (16-bit counters)", (long long)planned_draws, ABD_TIMELINE_MAX_DRAWS);
-  if (planned_draws) {
-    const struct { const char* name; double lo, hi; } ag[2] = {{"ab_n_mu", lo_n, hi_n}, {"ab_s_mu", lo_s, hi_s}};
-    for (const auto& x : ag)
-      if (!std::isfinite(x.lo) || !std::isfinite(x.hi) || !(x.lo < x.hi) || !std::isfinite(x.hi - x.lo))
-        return fail(ABD_ERR_ARG, "timelines: the range [%g, %g) of %s is not finite and ascending", x.lo, x.hi, x.name);
-  }
-  const abd_ctx* c = s->c;
-  TimelineSummary f;
-  f.draws = planned_draws;
-  f.range_n[0] = lo_n, f.range_n[1] = hi_n, f.range_s[0] = lo_s, f.range_s[1] = hi_s;
-  // staging of the read-out: a plane of 8 bytes per cell, and at least one gap's row of histograms
-  f.stage_bytes = std::max((size_t)c->G * c->N * sizeof(unsigned long long), (size_t)c->N * ABD_TIMELINE_BINS * sizeof(uint16_t));
-  const size_t bytes = (f.hist_at(c, s->n) + f.cell_at(c, s->n) + f.ninf_at(c, s->n)) * sizeof(uint32_t) + f.stage_bytes;
-  return enable_summary(s, s->timelines, "timelines", planned_draws > 0, bytes, [&](TimelineSummary& x) {
-    x = std::move(f);
-    hipError_t e = x.hist.alloc_zero(x.hist_at(c, s->n), c->stream);
-    if (e == hipSuccess) e = x.cell.alloc_zero(x.cell_at(c, s->n), c->stream);
-    if (e == hipSuccess) e = x.ninf.alloc_zero(x.ninf_at(c, s->n), c->stream);
-    if (e == hipSuccess) e = x.stage.alloc(x.stage_bytes / sizeof(unsigned long long));
-    return e;
-  });
-}
-
-int abd_sampler_timelines(abd_sampler* s, int32_t k, uint16_t* hist_n, uint16_t* hist_s, int64_t* inf, int64_t* cum, int64_t* ninf,
-                          int64_t* n_draws) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->timelines.on()) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
-  if (n_draws) *n_draws = std::max<int64_t>(0, s->it - s->o.tune);
-  if (!hist_n && !hist_s && !inf && !cum && !ninf) return ABD_OK;
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t cells = (size_t)c->G * c->N, N = (size_t)c->N, line = ABD_TIMELINE_BINS * sizeof(uint16_t);
-  // through the staging buffer on the context's stream: the copy waits for the kernel and the next kernel for the copy
-  int64_t* planes[2] = {inf, cum};
-  for (int v = 0; v < 2; ++v) {
-    if (!planes[v]) continue;
-    if (int rc = launch_diag_export(c, s->timelines.cell + s->timelines.cell_at(c, k) + v, 8, 4, s->timelines.stage, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(planes[v], s->timelines.stage, cells * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  uint16_t* hists[2] = {hist_n, hist_s};
-  const int rows = (int)std::max<size_t>(1, std::min<size_t>((size_t)c->G, s->timelines.stage_bytes / (N * line)));  // gap rows per pass
-  for (int v = 0; v < 2; ++v) {
-    if (!hists[v]) continue;
-    const uint32_t* src = s->timelines.hist + s->timelines.hist_at(c, k, v);
-    for (int g0 = 0; g0 < c->G; g0 += rows) {
-      const int n_g = std::min(rows, c->G - g0);
-      if (int rc = launch_timeline_hist_export(c, src, g0, n_g, s->timelines.stage, c->stream)) return rc;
-      HIP_TRY(hipMemcpyAsync(hists[v] + (size_t)g0 * N * ABD_TIMELINE_BINS, s->timelines.stage, (size_t)n_g * N * line, hipMemcpyDeviceToHost,
-                             c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-  }
-  if (ninf) {
-    std::vector<uint32_t> h(N * ABD_TIMELINE_NINF);
-    HIP_TRY(hipMemcpy(h.data(), s->timelines.ninf + s->timelines.ninf_at(c, k), h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < h.size(); ++e) ninf[e] = (int64_t)h[e];
-  }
-  return ABD_OK;
-}
-
-int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q, double* out_n, double* out_s) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (n_q < 1 || n_q > ABD_TIMELINE_MAX_Q) return fail(ABD_ERR_ARG, "timelines: n_q=%d outside [1, %d]", n_q, ABD_TIMELINE_MAX_Q);
-  if (!q) return fail(ABD_ERR_ARG, "timelines: q is NULL");
-  for (int e = 0; e < n_q; ++e)
-    if (!(q[e] >= 0.0 && q[e] <= 1.0)) return fail(ABD_ERR_ARG, "timelines: q[%d]=%g outside [0, 1]", e, q[e]);
-  if (!s->timelines.on()) return fail(ABD_ERR_STATE, "timelines are not enabled (abd_sampler_enable_timelines)");
-  if (!out_n && !out_s) return ABD_OK;
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t cells = (size_t)c->G * c->N;
-  DevBuf<double> d_q, d_out;  // the read-out's own: n_q planes of 8 bytes per cell
-  hipError_t e = d_q.upload(q, (size_t)n_q);
-  if (e == hipSuccess) e = d_out.alloc((size_t)n_q * cells);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    return fail(ABD_ERR_NOMEM, "timelines: %zu bytes of device memory for the quantiles", (size_t)n_q * cells * sizeof(double));
-  }
-  if (e != hipSuccess) return fail(ABD_ERR_HIP, "timelines: %s", hipGetErrorString(e));
-  double* outs[2] = {out_n, out_s};
-  const double* ranges[2] = {s->timelines.range_n, s->timelines.range_s};
-  for (int v = 0; v < 2; ++v) {
-    if (!outs[v]) continue;
-    const TimelineSummary& tl = s->timelines;  // (chain 0's plane of titer v; a chain's planes are hist_at(c, 1) words apart)
-    if (int rc = launch_timeline_quantiles(c, tl.hist + tl.hist_at(c, 0, v), (int64_t)tl.hist_at(c, 1), s->n, ranges[v], n_q, d_q, d_out,
-                                           c->stream))
-      return rc;
-    HIP_TRY(hipMemcpyAsync(outs[v], d_out, (size_t)n_q * cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  return ABD_OK;
-}
-
-int abd_sampler_enable_risk(abd_sampler* s, int64_t capacity, const abd_risk_spec* spec) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (capacity < 0) return fail(ABD_ERR_ARG, "capacity=%lld is negative", (long long)capacity);
-  const abd_ctx* c = s->c;
-  if (capacity > 0 && !s->ran)  // (a sampler that has run is refused below, whatever the spec)
-    if (int rc = check_risk_spec(c, spec)) return rc;
-  RiskSummary f;
-  f.capacity = capacity;
-  if (capacity > 0 && spec) f.spec = *spec;
-  return enable_summary(s, s->risk, "risk", capacity > 0, f.table_at(c, s->n, 0) * sizeof(uint32_t), [&](RiskSummary& x) {
-    x = std::move(f);
-    hipError_t e = x.tables.alloc(x.table_at(c, s->n, 0));
-    if (e == hipSuccess) e = x.scratch.alloc(x.scratch_at(c, s->n));
-    return e;
-  });
-}
-
-int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* table, int64_t* n_draws) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  if (!s->risk.on()) return fail(ABD_ERR_STATE, "risk is not enabled (abd_sampler_enable_risk)");
-  const int64_t have = std::max<int64_t>(0, s->it - s->o.tune);
-  if (n_draws) *n_draws = have;
-  if (first < 0 || count < 0 || first > have || count > have - first)
-    return fail(ABD_ERR_ARG, "risk: draws [%lld, %lld) are beyond the %lld the chain has", (long long)first, (long long)(first + count),
-                (long long)have);
-  if (count == 0 || !table) return ABD_OK;
-  abd_ctx* c = s->c;
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // (a run call ends with every stream joined into the context's)
-  const size_t n_tab = risk_table_cols(c);
-  std::vector<uint32_t> h((size_t)count * n_tab);
-  HIP_TRY(hipMemcpy(h.data(), s->risk.tables + s->risk.table_at(c, k, first), h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (size_t e = 0; e < h.size(); ++e) table[e] = (int64_t)h[e];
-  return ABD_OK;
-}
-
-int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  const abdnuts::Nuts& nu = s->ch[(size_t)k].nuts;
-  if (inv_mass) std::memcpy(inv_mass, nu.inv_mass, sizeof(double) * ABD_N_THETA);
-  if (step_size) *step_size = nu.eps;
-  if (metric)
-    for (int r = 0; r < ABD_N_THETA; ++r)
-      for (int c = 0; c < ABD_N_THETA; ++c)
-        metric[r * ABD_N_THETA + c] = nu.dense ? nu.cov[r][c] : (r == c ? nu.inv_mass[r] : 0.0);
-  return ABD_OK;
-}
-
-int abd_sampler_set_adaptation(abd_sampler* s, int32_t k, const double* inv_mass, double step_size) {
-  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
-  if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);
-  abdnuts::Nuts& nu = s->ch[(size_t)k].nuts;
-  if (nu.dense) return fail(ABD_ERR_STATE, "chain %d runs a dense metric", k);
-  if (inv_mass) {
-    for (int d = 0; d < ABD_N_THETA; ++d)
-      if (!(inv_mass[d] > 0.0) || !std::isfinite(inv_mass[d])) return fail(ABD_ERR_ARG, "inv_mass[%d]=%g is not a positive finite number", d, inv_mass[d]);
-    std::memcpy(nu.inv_mass, inv_mass, sizeof(double) * ABD_N_THETA);
-  }
-  if (step_size > 0.0) {
-    if (!std::isfinite(step_size)) return fail(ABD_ERR_ARG, "step_size is not finite");
-    nu.eps = step_size;
-  }
   return ABD_OK;
 }
 

@@ -2,7 +2,7 @@
 Every per-draw summary of the native sampler switched on in ONE run -- the curves, the risk tables, the convergence accumulators,
 the timelines with their histograms, WAIC and PPC, beside the recorded Deterministics -- against four runs with one summary each:
 a summary's arrays do not depend on what else is on, byte for byte, and nothing the chains draw does.  The summaries share the
-sampler's per-draw launch sequence and address their chain's part of every buffer by the same accessors (abd_sampler.hip), which
+sampler's per-draw launch sequence and address their chain's part of every buffer by the same accessors (abd_sampler.hpp), which
 only a run with several of them on can get wrong.  Conditions only: nothing here is a tolerance.
 """
 import os

@@ -11,12 +11,15 @@ A refactor of the library's own host side: archive the whole parent (its `tests/
 
 `run` (a process per tree): `sample()` with every summary and record row on (`thin=3`, `timelines_hist`), and with nothing on,
 on the dense 67 x 65 cohort and the golden `test_cohort` of `tests/test_gpu_summaries_together.py`, then `abdpymc-infer` with
-every flag, each saved as `.npz`; the CLI's stderr is the caller's to keep.  Then the survival models (`survival.npz`): handles
+every flag, each saved as `.npz`; the CLI's stderr is the caller's to keep.  The same pair of `sample()` calls again under
+each environment of `LEGS`, which reach what the defaults (observation-list trains; dense trains with units of one) do not: the
+sampler's result-row back-end on several host threads and on one with units of two chains, and dense trains that share a launch
+(units of two, four chains).  Then the survival models (`survival.npz`): handles
 of `_native.Survival` on `tests.survival_restatement.make_data` at (N, T) = (1, 1), (67, 30), (130, 65) with K = 1 and 2, and of
 `_native.SurvivalGroups` on `tests.survival_groups_restatement.make_case` at (67, 30, 3) and (130, 65, 4) -- `loglik_sums` at every
 point of the restatement's `POINTS`, `logp_dlogp` and `individual_loglik` of 19 stacked points (two launches), the WAIC
 accumulators of the same 19 -- and one short `survival.sample` with `survival.waic` per form on 300 x 6 simulated cells.
-`compare`: the same six files and key sets, every array equal in dtype, shape and bytes -- the chains are deterministic per seed,
+`compare`: the same sixteen files and key sets, every array equal in dtype, shape and bytes -- the chains are deterministic per seed,
 so this is a condition, not a tolerance."""
 import os
 import sys
@@ -27,6 +30,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "test_cohort")
 CHAINS, TUNE, DRAWS = 3, 3, 8
+# (file prefix, environment of the library while the leg's samplers are created, chains, cohorts)
+LEGS = (("", {}, CHAINS, ("dense", "test")),
+        ("rows_", {"ABD_SAMPLER_TRAINS": "0"}, CHAINS, ("dense", "test")),
+        ("rows_unit2_", {"ABD_SAMPLER_TRAINS": "0", "ABD_SAMPLER_UNIT": "2", "ABD_SAMPLER_THREADS": "1"}, CHAINS, ("dense", "test")),
+        ("unit2_", {"ABD_SAMPLER_UNIT": "2"}, 4, ("dense",)))
+N_FILES = 2 * sum(len(leg[3]) for leg in LEGS) + 2  # everything / nothing per leg and cohort, cli.npz, survival.npz
 
 
 def run(tree, out):
@@ -42,9 +51,9 @@ def run(tree, out):
     print("package", os.path.relpath(abdpymc_amd.__file__, ROOT), "library", os.path.relpath(_native.LIB_PATH, ROOT), flush=True)
     os.makedirs(out, exist_ok=True)
 
-    def cohort(which):
+    def cohort(which, chains):
         if which == "test":
-            return model(TiterData.from_disk(GOLDEN), n_chains=CHAINS)
+            return model(TiterData.from_disk(GOLDEN), n_chains=chains)
         N, G = 67, 65
         sc = synthetic.make_cohort(N, G, seed=11)
         last = np.full(N, G - 1, dtype=np.int32)
@@ -54,20 +63,24 @@ def run(tree, out):
         d = SimpleNamespace(n_gaps=sc.n_gaps, n_inds=sc.n_inds, vacs=sc.vacs, pcrpos=sc.pcrpos, last_gap=last,
                             coords={"gap": np.arange(sc.n_gaps), "ind": np.arange(sc.n_inds)},
                             s=SimpleNamespace(obs=sc.s_obs), n=SimpleNamespace(obs=sc.n_obs))
-        return AbdModel(d, n_chains=CHAINS)
+        return AbdModel(d, n_chains=chains)
 
-    for which in ("dense", "test"):
-        m = cohort(which)
+    for prefix, env, chains, which in ((p, e, c, w) for p, e, c, ws in LEGS for w in ws):
+        assert not any(k in os.environ for leg in LEGS for k in leg[1]), "the legs set the sampler's environment themselves"
+        os.environ.update(env)
+        m = cohort(which, chains)
         sp = risk.spec(0, m.n_gaps, 0.5 * np.arange(1, 8), 0.25 * np.arange(1, 8), 1)
-        kw = dict(tune=TUNE, draws=DRAWS, chains=CHAINS, seed=7)
+        kw = dict(tune=TUNE, draws=DRAWS, chains=chains, seed=7)
         everything = sample(m, log_likelihood=True, posterior_predictive=True, thin=3, waic=True, ppc=True, curves=True,
                             sero_thresholds=(1.0, 0.5), diagnostics=True, diag_batch=2, risk=sp, timelines=True,
                             timeline_ranges=((-3, 7), (-2, 6)), timeline_q=(0.1, 0.5, 0.8, 0.9), timelines_hist=True, **kw)
-        np.savez(os.path.join(out, f"{which}_everything.npz"), **everything)
+        np.savez(os.path.join(out, f"{prefix}{which}_everything.npz"), **everything)
         nothing = sample(m, **kw)
-        np.savez(os.path.join(out, f"{which}_nothing.npz"), **nothing)
-        print(which, "everything", len(everything), "keys; nothing", len(nothing), "keys", flush=True)
+        np.savez(os.path.join(out, f"{prefix}{which}_nothing.npz"), **nothing)
+        print(prefix + which, "everything", len(everything), "keys; nothing", len(nothing), "keys", flush=True)
         m.close()
+        for k in env:
+            del os.environ[k]
     rc = cli.main(["--tune", "6", "--draws", "8", "--cores", "1", "--chains", "2", "--seed", "5", "--ititers_data", GOLDEN, "--thin", "3",
                    "--waic", "--log_likelihood", "--posterior_predictive", "--ppc", "--curves", "--sero_threshold_s", "2.0",
                    "--sero_threshold_n", "1.0", "--diagnostics", "--diag_batch", "2", "--risk", "--risk_edges_s", "0.5,1.5,2.5",
@@ -120,7 +133,7 @@ def run_survival(out):
 
 def compare(a, b):
     files = sorted(os.listdir(a))
-    assert files == sorted(os.listdir(b)) and len(files) == 6, (files, sorted(os.listdir(b)))
+    assert files == sorted(os.listdir(b)) and len(files) == N_FILES, (files, sorted(os.listdir(b)))
     bad = n = nbytes = 0
     for f in files:
         za, zb = np.load(os.path.join(a, f), allow_pickle=False), np.load(os.path.join(b, f), allow_pickle=False)
