@@ -133,6 +133,13 @@ class _SurvivalGroupsDesc(C.Structure):  # abd_survival_groups_desc
                 ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
 
 
+class _SurvivalPeriodsDesc(C.Structure):  # abd_survival_periods_desc
+    _fields_ = [("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_periods", C.c_int32), ("device", C.c_int32),
+                ("infected", C.c_void_p), ("exposure", C.c_void_p), ("titer", C.c_void_p), ("period", C.c_void_p),
+                ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double), ("lam0_z_sd", C.c_double),
+                ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
+
+
 SURVIVAL_MAX_GROUPS = 256  # ABD_SURVIVAL_MAX_GROUPS
 
 # abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
@@ -214,6 +221,7 @@ SYMBOLS = {
     "abd_is_dense": (C.c_int, [_P]),
     "abd_survival_create": (C.c_int, [C.POINTER(_SurvivalDesc), C.POINTER(_P)]),
     "abd_survival_create_groups": (C.c_int, [C.POINTER(_SurvivalGroupsDesc), C.POINTER(_P)]),
+    "abd_survival_create_periods": (C.c_int, [C.POINTER(_SurvivalPeriodsDesc), C.POINTER(_P)]),
     "abd_survival_destroy": (C.c_int, [_P]),
     "abd_survival_dim": (C.c_int32, [_P]),
     "abd_survival_logp_dlogp": (C.c_int, [_P, C.c_int32, _D, _D, _D]),
@@ -1097,7 +1105,8 @@ class Survival:
         return (float(lp[0]), g[0]) if one else (lp, g)
 
     def loglik_sums(self, theta):
-        """The raw device sums at one point: S_t (T), L, W_0, W_k (K); of a grouped handle S_t (T), L, W_x, W0_g (Gr)."""
+        """The raw device sums at one point: S_t (T), L, W_0, W_k (K); of a grouped handle S_t (T), L, W_x, W0_g (Gr); of a handle
+        by period S_t (T), L, W_x, W0_t (T)."""
         t = _as(theta, np.float64)
         if t.shape != (self.dim,):
             raise ValueError(f"theta must have shape ({self.dim},)")
@@ -1173,3 +1182,29 @@ class SurvivalGroups(Survival):
         self.n_inds, self.n_intervals, self.n_titers, self.n_groups = y.shape[0], y.shape[1], 1, int(n_groups)
         self.dim = int(lib.abd_survival_dim(self._h))
         self.n_sums = y.shape[1] + 2 + int(n_groups)
+
+
+class SurvivalPeriods(Survival):
+    """The survival model by period resident on the device (abd_hip.h: ``abd_survival_create_periods``): ``infected``, ``exposure``,
+    ``titer`` (N, T), ``period`` (T,) indices in [0, ``n_periods``), ``priors`` = (lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd,
+    a_mu_sd, a_sd_rate, a_z_sd, b_sd).  The library checks the labels and the cells; the evaluations are ``Survival``'s."""
+
+    def __init__(self, infected, exposure, titer, period, n_periods: int, priors, device: int = -1):
+        lib = load()
+        self._lib = lib
+        self._h = _P()
+        y, e, x = _as(infected, np.float64), _as(exposure, np.float64), _as(titer, np.float64)
+        p = _as(period, np.int32)
+        if y.ndim != 2 or e.shape != y.shape or x.shape != y.shape:
+            raise ValueError("infected, exposure and the titer must share a shape (N, T)")
+        if p.shape != (y.shape[1],):
+            raise ValueError(f"period must have shape ({y.shape[1]},), got {p.shape}")
+        d = _SurvivalPeriodsDesc()
+        d.n_inds, d.n_intervals, d.n_periods, d.device = y.shape[0], y.shape[1], int(n_periods), device
+        d.infected, d.exposure, d.titer, d.period = y.ctypes.data, e.ctypes.data, x.ctypes.data, p.ctypes.data
+        (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
+         d.b_sd) = (float(v) for v in priors)
+        _check(lib, lib.abd_survival_create_periods(C.byref(d), C.byref(self._h)))
+        self.n_inds, self.n_intervals, self.n_titers, self.n_periods = y.shape[0], y.shape[1], 1, int(n_periods)
+        self.dim = int(lib.abd_survival_dim(self._h))
+        self.n_sums = 2 * y.shape[1] + 2

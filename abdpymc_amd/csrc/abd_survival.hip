@@ -1,14 +1,16 @@
-// abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*; DESIGN 19-21): creation of a
-// handle of either form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators.  A
-// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp and
-// abd_survival_pointwise.hpp; the closed forms, the packing of the planes and the form of a model (SurvivalForm) are plain C++
-// in the three *_terms.hpp beside them.
+// abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*; DESIGN 19-21, 24): creation of a
+// handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators.  A
+// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp
+// and abd_survival_pointwise.hpp; the closed forms, the packing of the planes and the form of a model (SurvivalForm) are plain
+// C++ in the four *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
 #include <memory>
 
 #include "abd_host.hpp"
 #include "abd_survival.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
+#include "abd_survival_periods.hpp"
+#include "abd_survival_periods_terms.hpp"
 #include "abd_survival_pointwise.hpp"
 #include "abd_survival_pointwise_terms.hpp"
 #include "abd_survival_terms.hpp"
@@ -16,10 +18,10 @@
 namespace abdi {
 // what a creator decides: the rest of a handle follows from it and from the data
 struct SurvivalSpec {
-  SurvivalForm form;  // K titers, or by group (abd_survival_groups.hpp)
+  SurvivalForm form;  // K titers, by group (abd_survival_groups.hpp) or by period (abd_survival_periods.hpp)
   int N = 0, device = 0;
   SurvivalPriors priors{};         // of the form with K titers
-  SurvivalGroupsPriors gpriors{};  // of the form by group
+  SurvivalGroupsPriors gpriors{};  // of the forms by group and by period
 };
 }  // namespace abdi
 
@@ -28,9 +30,9 @@ struct abd_survival : SurvivalSpec {
   DevBuf<int32_t> d_tile_group, d_group_tile;
   std::vector<double> Y;  // Y_t = sum_j y_jt
   double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
-  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
+  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w0_part, d_w_part, d_out;
   MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
-  std::vector<double> work;        // log lambda, 1 - lambda of the points in flight
+  std::vector<double> work;        // rows of form.work_stride(): log lambda, 1 - lambda (and the form's own) of the points in flight
   // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
   std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
   std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
@@ -49,11 +51,11 @@ namespace {
 
 // par and work of n <= ABD_MAX_BATCH points: rows of s->h_par and s->work
 void survival_prepare_points(abd_survival* s, int n, const double* theta) {
-  const int D = s->form.dim(), stride = s->form.par_stride(), T = s->form.T;
-  for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * 2 * T);
+  const int D = s->form.dim(), stride = s->form.par_stride(), ws = s->form.work_stride();
+  for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * ws);
 }
 
-// what the argument structs of the two forms have in common
+// what the argument structs of the three forms have in common
 template <typename Args>
 Args survival_args(const abd_survival* s) {
   Args a;
@@ -79,7 +81,13 @@ int survival_launch(abd_survival* s, int n, const double* theta) {
   survival_prepare_points(s, n, theta);
   HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->form.par_stride() * sizeof(double), hipMemcpyHostToDevice, s->stream));
   const dim3 grid((unsigned)((s->nw + 3) / 4), (unsigned)n);
-  if (s->form.grouped()) {  // the one place that picks the pair of kernels
+  if (s->form.by_period()) {  // the one place that picks the pair of kernels
+    SurvivalPeriodsArgs a = survival_args<SurvivalPeriodsArgs>(s);
+    a.x = s->d_x0;
+    a.w0_part = s->d_w0_part;
+    HIP_TRY(launch_kernel(abd_survival_periods_kernel, grid, dim3(256), 0, s->stream, a));
+    HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, s->stream, a));
+  } else if (s->form.grouped()) {
     SurvivalGroupsArgs a = survival_args<SurvivalGroupsArgs>(s);
     a.x = s->d_x0;
     a.tile_group = s->d_tile_group;
@@ -130,7 +138,7 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
   const int T = s->form.T, n_ab = s->form.n_ab(), stride = s->form.par_stride();
   survival_prepare_points(s, n, theta);
   for (int q = 0; q < n; ++q)
-    survival_pointwise_row(T, n_ab, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * 2 * T, fold ? s->waic_n + q + 1 : 0,
+    survival_pointwise_row(T, n_ab, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * s->form.work_stride(), fold ? s->waic_n + q + 1 : 0,
                            s->h_pw_par.host() + (size_t)q * s->pw_stride);
   HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
   SurvivalPointArgs a;
@@ -149,8 +157,8 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
   a.par_stride = s->pw_stride;
   a.n_ab = n_ab;
   const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
-  void (*const kernels[3])(const SurvivalPointArgs) = {abd_survival_individual_kernel<0>, abd_survival_individual_kernel<1>,
-                                                       abd_survival_individual_kernel<2>};
+  void (*const kernels[4])(const SurvivalPointArgs) = {abd_survival_individual_kernel<0>, abd_survival_individual_kernel<1>,
+                                                       abd_survival_individual_kernel<2>, abd_survival_individual_kernel<3>};
   HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), 0, s->stream, a));
   if (fold) {
     if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->ld, s->stream));
@@ -210,7 +218,7 @@ int survival_create_common(const SurvivalSpec& spec, const double* infected, con
   s->seg_len = (T + want_seg - 1) / want_seg;
   s->nseg = (T + s->seg_len - 1) / s->seg_len;
   s->nw = s->ntile * s->nseg;
-  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  s->work.resize((size_t)ABD_MAX_BATCH * s->form.work_stride());
   survival_pointwise_setup(s.get(), p.y.data(), p.e.data());
   if (s->device < 0) HIP_TRY(hipGetDevice(&s->device));
   HIP_TRY(hipSetDevice(s->device));
@@ -227,6 +235,7 @@ int survival_create_common(const SurvivalSpec& spec, const double* infected, con
   const size_t par_stride = (size_t)s->form.par_stride(), out_stride = (size_t)s->form.out_stride();
   HIP_TRY(s->d_par.alloc(ABD_MAX_BATCH * par_stride));
   HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
+  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
   HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
   HIP_TRY(s->d_out.alloc(ABD_MAX_BATCH * out_stride));
   HIP_TRY(s->h_par.alloc_pinned(ABD_MAX_BATCH * par_stride));
@@ -235,7 +244,7 @@ int survival_create_common(const SurvivalSpec& spec, const double* infected, con
   return ABD_OK;
 }
 
-// The frame of both creators around `create`, the creator's own checks and its call of survival_create_common: nothing may be
+// The frame of the creators around `create`, the creator's own checks and its call of survival_create_common: nothing may be
 // thrown across the C ABI (the host copies of the planes are the large allocations).
 template <typename Desc, typename Create>
 int survival_create(const Desc* d, abd_survival** out, Create create) {
@@ -291,6 +300,23 @@ int abd_survival_create_groups(const abd_survival_groups_desc* d, abd_survival**
   });
 }
 
+int abd_survival_create_periods(const abd_survival_periods_desc* d, abd_survival** out) {
+  return survival_create(d, out, [&] {
+    const int T = d->n_intervals, P = d->n_periods;
+    if (int rc = survival_check_shape(d->n_inds, T)) return rc;
+    if (P < 1 || P > T) return fail(ABD_ERR_ARG, "n_periods=%d outside [1, %d]", P, T);
+    if (!d->infected || !d->exposure || !d->titer || !d->period) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_priors("lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd",
+                                       {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd}, d->lam0_mu_mean))
+      return rc;
+    for (int t = 0; t < T; ++t)
+      if (d->period[t] < 0 || d->period[t] >= P) return fail(ABD_ERR_ARG, "interval %d: period %d outside [0, %d)", t, d->period[t], P);
+    SurvivalSpec spec{SurvivalForm{1, 0, T, P, std::vector<int32_t>(d->period, d->period + T)}, d->n_inds, d->device};
+    spec.gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+    return survival_create_common(spec, d->infected, d->exposure, &d->titer, nullptr, out);  // no layout: the caller's order
+  });
+}
+
 int abd_survival_destroy(abd_survival* s) {
   if (!s) return ABD_OK;
   (void)hipSetDevice(s->device);
@@ -312,7 +338,7 @@ int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, dou
     for (int q = 0; q < nb; ++q) {
       const size_t k = (size_t)k0 + q;
       logp[k] = s->form.combine(s->priors, s->gpriors, theta + k * D, s->Y.data(), s->C, s->h_out.host() + q * out_stride,
-                                s->h_par.host() + q * par_stride, s->work.data() + (size_t)q * 2 * s->form.T, grad + k * D);
+                                s->h_par.host() + q * par_stride, s->work.data() + (size_t)q * s->form.work_stride(), grad + k * D);
     }
   }
   return ABD_OK;

@@ -1,7 +1,7 @@
 // abd_survival_groups_terms.hpp -- the closed-form part of the Poisson hazard model by group: what one unconstrained
 // point gives the kernel (lambda_t, a_g, b), and the combination of the device sums with the priors into logp and gradient.
 // Plain C++, no HIP: one source for the library (abd_survival.hip) and for the native harness
-// (tests/native/survival_groups_harness.cpp).  At the end, SurvivalForm: which of the two models a handle holds, asked in one place.
+// (tests/native/survival_groups_harness.cpp).  At the end, SurvivalForm: which of the three models a handle holds, asked in one place.
 //
 //   theta = m, s, z[T], a_mu, a_sl, az[Gr], b     (PyMC's creation order for this model; sd = e^s, a_sd = e^a_sl)
 //   r_t = m + sd z_t, lambda_t = invlogit(r_t);  a_g = a_mu + a_sd az_g
@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "abd_survival_periods_terms.hpp"  // SurvivalForm, at the end
 #include "abd_survival_terms.hpp"
 
 namespace abdi {
@@ -116,28 +117,44 @@ inline int survival_groups_layout(int N, int Gr, const int32_t* group, int32_t* 
   return tile;
 }
 
-// The form of a handle's model: K titers (Gr = 0; abd_survival_terms.hpp), or by group (Gr > 0, K = 1; this file).  Everything
-// that differs between the two on the host is answered here: the sizes of a point and of its rows, and which pair of closed
-// forms makes the parameter row of a point and combines its sums.
+// The form of a handle's model: K titers (Gr = 0, no periods; abd_survival_terms.hpp), by group (Gr > 0, K = 1; this file), or by
+// period (P > 0, period holds the T labels, K = 1; this file's closed forms around abd_survival_periods_terms.hpp).  Everything
+// that differs between the three on the host is answered here: the sizes of a point and of its rows, and which closed forms make
+// the parameter row of a point and combine its sums.
 struct SurvivalForm {
-  int K = 0, Gr = 0, T = 0;
+  int K = 0, Gr = 0, T = 0, P = 0;
+  std::vector<int32_t> period{};  // [T], by period only
   bool grouped() const { return Gr > 0; }
-  int dim() const { return grouped() ? survival_groups_dim(T, Gr) : survival_dim(K, T); }
-  int n_ab() const { return grouped() ? Gr + 1 : 2 * K; }            // a[Gr], b, or a[K], b[K]: what follows lambda[T] in a parameter row
+  bool by_period() const { return P > 0; }
+  int dim() const { return by_period() ? survival_periods_dim(T, P) : grouped() ? survival_groups_dim(T, Gr) : survival_dim(K, T); }
+  // a_t[T], b, or a[Gr], b, or a[K], b[K]: what follows lambda[T] in a parameter row
+  int n_ab() const { return by_period() ? T + 1 : grouped() ? Gr + 1 : 2 * K; }
   int par_stride() const { return T + n_ab(); }
-  int n_sums() const { return T + 2 + (grouped() ? Gr : K); }        // the sums of a point that mean something
-  int out_stride() const { return grouped() ? T + 2 + Gr : T + ABD_SURV_NW; }  // the row the finalize kernel of the form writes
-  int mode() const { return grouped() ? 0 : K; }                     // MODE of abd_survival_individual_kernel
+  int n_sums() const { return by_period() ? 2 * T + 2 : T + 2 + (grouped() ? Gr : K); }  // the sums of a point that mean something
+  // the row the finalize kernel of the form writes
+  int out_stride() const { return by_period() ? 2 * T + 2 : grouped() ? T + 2 + Gr : T + ABD_SURV_NW; }
+  int work_stride() const { return by_period() ? survival_periods_work(T, P) : 2 * T; }  // the host's row of a point in flight
+  int mode() const { return by_period() ? 3 : grouped() ? 0 : K; }                        // MODE of abd_survival_individual_kernel
   void prepare(const double* theta, double* par, double* work) const {
-    if (grouped()) {
+    if (by_period()) {  // the grouped row of the point into work, then one a per interval
+      double* gpar = survival_periods_gpar(T, work);
+      survival_groups_prepare(T, P, theta, gpar, work);
+      survival_periods_expand(T, P, period.data(), gpar, par);
+    } else if (grouped()) {
       survival_groups_prepare(T, Gr, theta, par, work);
     } else {
       survival_prepare(K, T, theta, par, work);
     }
   }
-  // the priors of the other form are not read
+  // p: the priors of the form with K titers; gp: those of the forms by group and by period.  The other struct is not read.
+  // work: the row prepare made of the point (by period, the folded sums are left in it)
   double combine(const SurvivalPriors& p, const SurvivalGroupsPriors& gp, const double* theta, const double* Y, double C,
-                 const double* sums, const double* par, const double* work, double* grad) const {
+                 const double* sums, const double* par, double* work, double* grad) const {
+    if (by_period()) {  // W0_t into W0_p, then the grouped closed form on (T, P, W0_p, a_p)
+      double* gsums = survival_periods_gsums(T, P, work);
+      survival_periods_fold(T, P, period.data(), sums, gsums, survival_periods_comp(T, P, work));
+      return survival_groups_combine(gp, T, P, theta, Y, C, gsums, survival_periods_gpar(T, work), work, grad);
+    }
     return grouped() ? survival_groups_combine(gp, T, Gr, theta, Y, C, sums, par, work, grad)
                      : survival_combine(p, K, T, theta, Y, C, sums, par, work, grad);
   }

@@ -12,7 +12,8 @@
 // stay in the lane: no cross-lane operation, no LDS, no barrier, no atomics.  The point is the grid's second dimension.  The
 // order of every sum is fixed by T alone: a point's row is the same bits alone, as any row of a full launch and in any split
 // of a longer call.  Cells without follow-up and the padding hold y = e = x = 0 and C = 0: sigma is finite, e sigma = 0, and
-// the lane writes exactly 0.0.  The grouped form reads its tile's a_g through tile_group as abd_survival_groups_kernel does.
+// the lane writes exactly 0.0.  The grouped form reads its tile's a_g through tile_group as abd_survival_groups_kernel does; the
+// form by period reads its interval's a_t inside the loop as abd_survival_periods_kernel does.
 // sigma is surv_cell's (surv_sigma); surv_cell itself is not called, it carries the wave sum of S_t.
 //
 // abd_survival_waic_fold: thread = slot; the launch's n rows go into the handle's accumulators [4][ld] (rows M, S, mean, M2)
@@ -37,7 +38,7 @@ struct SurvivalPointArgs {
   int32_t T, ld, ntile, par_stride, n_ab;
 };
 
-// MODE 1, 2: K titers, ab = a[K], b[K].  MODE 0: by group, ab = a[Gr], b.
+// MODE 1, 2: K titers, ab = a[K], b[K].  MODE 0: by group, ab = a[Gr], b.  MODE 3: by period, ab = a_t[T], b.
 template <int MODE>
 __global__ __launch_bounds__(256) void abd_survival_individual_kernel(const SurvivalPointArgs a) {
   const int lane = threadIdx.x & 63;
@@ -50,6 +51,9 @@ __global__ __launch_bounds__(256) void abd_survival_individual_kernel(const Surv
   double a0, b0, a1 = 0.0, b1 = 0.0;
   if (MODE == 0) {
     a0 = ab[a.tile_group[tile]];
+    b0 = ab[a.n_ab - 1];
+  } else if (MODE == 3) {
+    a0 = 0.0;  // per interval, below
     b0 = ab[a.n_ab - 1];
   } else {
     a0 = ab[0];
@@ -64,6 +68,7 @@ __global__ __launch_bounds__(256) void abd_survival_individual_kernel(const Surv
   double A = 0.0, B = 0.0;
   for (int t = 0; t < a.T; ++t, idx += a.ld) {
     const double y = a.y[idx], e = a.e[idx];
+    if (MODE == 3) a0 = ab[t];
     double eta = b0 * (a.x0[idx] - a0);
     if (MODE == 2) eta = fma(b1, a.x1[idx] - a1, eta);
     const SurvSigma sg = surv_sigma(eta);

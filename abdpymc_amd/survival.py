@@ -8,8 +8,10 @@ infection hazard of month g?
 ``model_combined`` put them on the device, where one kernel gives the data sums of logp and its gradient (``abd_survival`` in
 ``include/abd_hip.h``); ``sample`` runs ``sampler.Nuts`` on that evaluator as PyMC's NUTS runs on the reference's
 models; ``protection`` is what ``plotting.plot_protection`` draws.  ``model_alone_groups`` gives every group of individuals its
-own midpoint ``a`` under a hierarchical prior, with one slope ``b`` (``abd_survival_create_groups``).  Per-draw
-(non-plug-in) fits are not here.
+own midpoint ``a`` under a hierarchical prior, with one slope ``b`` (``abd_survival_create_groups``; DESIGN 20);
+``model_alone_periods`` does the same along the time axis, one midpoint per month or per era of intervals
+(``abd_survival_create_periods``): the fit ``plotting.plot_protection(interval=)`` reads.  Per-draw (non-plug-in) fits
+are not here.
 
 Which titer predicts protection?  ``waic(model, fit)`` scores a fitted model by WAIC over the individuals -- the device gives every
 individual's log-likelihood at every draw and keeps the running statistics (``abd_survival_individual_loglik``,
@@ -18,6 +20,7 @@ with paired standard errors (``compare.compare``).
 
     python -m abdpymc_amd.survival --posterior FILE --ititers_data DIR --start S --end E --model s|n|combined --out FILE [--waic]
     python -m abdpymc_amd.survival ... --model s_groups|n_groups --groups FILE [--group_name NAME]
+    python -m abdpymc_amd.survival ... --model s_periods|n_periods [--periods monthly|splits|FILE] [--split_delta] [--split_omicron]
     python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz
 """
 from __future__ import annotations
@@ -34,12 +37,17 @@ from . import risk
 from .sampler import DualAveraging, Nuts
 from .summaries import interval
 
+_interval_of_draws = interval  # ``protection`` has an argument called ``interval``
+
 # ab_sd, lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd (survival.py:121-122, 140-143; make_hierarchical_lam0)
 PRIORS = {1: (1.0, -3.0, 0.5, 2.0, 1.0), 2: (0.5, -3.0, 0.5, 2.0, 1.0)}
 
 # lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd (survival.py:167-169: make_hierarchical_lam0
 # without hyper_mu, make_hierarchical_normal("a"), b ~ N(0, 0.5))
 PRIORS_GROUPS = (0.0, 0.5, 2.0, 1.0, 0.5, 2.0, 1.0, 0.5)
+
+# the same eight for model_alone_periods: make_hierarchical_lam0(hyper_mu=-3.0) as model_alone, the rest as the grouped model
+PRIORS_PERIODS = (-3.0, 0.5, 2.0, 1.0, 0.5, 2.0, 1.0, 0.5)
 
 
 def _month_add(t0: str, months: int) -> str:
@@ -72,7 +80,7 @@ def _means(src) -> Dict[str, np.ndarray]:
 
 
 class _DeviceModel:
-    """What both models pass on to their handle ``_dev`` (``_native.Survival`` or ``SurvivalGroups``)."""
+    """What the models pass on to their handle ``_dev`` (``_native.Survival``, ``SurvivalGroups`` or ``SurvivalPeriods``)."""
 
     def logp_dlogp(self, q):
         return self._dev.logp_dlogp(q)
@@ -204,6 +212,43 @@ class SurvivalGroupsModel(_DeviceModel):
         return initial_point_groups(self.T, self.Gr, self.priors)
 
 
+def period_indices(periods, n_intervals: int):
+    """(labels, indices): the sorted unique labels and each interval's index into them."""
+    periods = np.asarray(periods)
+    if periods.shape != (n_intervals,):
+        raise ValueError(f"periods must hold one label per interval, shape ({n_intervals},), got {periods.shape}")
+    labels, idx = np.unique(periods, return_inverse=True)
+    return labels, idx.reshape(-1).astype(np.int32)
+
+
+class SurvivalPeriodsModel(_DeviceModel):
+    """The Poisson hazard model by period: ``names``, ``dim``, ``periods`` (the sorted unique labels), ``period_index`` (T,),
+    ``period_name``, ``logp_dlogp(q)`` and ``loglik_sums(q)`` on the device, ``constrain(q)``, ``initial_point()`` and ``close()``.
+    The unconstrained point has the grouped model's layout with one ``_a_z`` per period."""
+
+    K = 1
+
+    def __init__(self, infected, exposure, titer, antigen, periods, period_name="period", priors=None, device: int = -1):
+        from ._native import SurvivalPeriods
+
+        self.antigens = (antigen,)
+        self.period_name = str(period_name)
+        self.periods, self.period_index = period_indices(periods, np.asarray(infected).shape[1])
+        self.P = len(self.periods)
+        self.priors = PRIORS_PERIODS if priors is None else tuple(float(v) for v in priors)
+        self._dev = SurvivalPeriods(infected, exposure, titer, self.period_index, self.P, self.priors, device=device)
+        self.n_cells = followed_cells(infected, exposure)
+        self.T = self._dev.n_intervals
+        self.dim = self._dev.dim
+        self.names = names_groups(self.T, self.P)
+
+    def constrain(self, q) -> Dict[str, np.ndarray]:
+        return constrain_groups(q, self.T, self.P)
+
+    def initial_point(self) -> np.ndarray:
+        return initial_point_groups(self.T, self.P, self.priors)
+
+
 class SurvivalAnalysis:
     """The reference's ``SurvivalAnalysis(abd_inference, start, end, cohort_data)``: ``infected``, ``exposure``, ``s_titer``,
     ``n_titer`` (n_ind, n_int), ``n_int = end - start - 1``, ``intervals``, ``t0`` (the month of the arrays' first interval).
@@ -234,6 +279,26 @@ class SurvivalAnalysis:
             raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
         titer = self.s_titer if antigen == "S" else self.n_titer
         return self._windowed(SurvivalGroupsModel(self.infected, self.exposure, titer, antigen, groups, group_name, device=self.device))
+
+    def model_alone_periods(self, antigen: str, periods=None, period_name: Optional[str] = None) -> SurvivalPeriodsModel:
+        """One midpoint ``a`` per period of time, one slope ``b``.  ``periods=None``: monthly, every interval its own period, and
+        ``a`` carries the reference's dimension ``intervals`` (what ``plotting.plot_protection(interval=)`` reads).  Otherwise
+        ``periods`` holds one label per interval (any sortable values, need not be monotone; ``periods_from_splits`` gives the
+        variant eras); the model's ``periods`` are the sorted unique labels and ``a`` has one entry per label in that order."""
+        if antigen not in ("S", "N"):
+            raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
+        titer = self.s_titer if antigen == "S" else self.n_titer
+        if periods is None:
+            periods, period_name = self.intervals, "intervals" if period_name is None else period_name
+        name = "period" if period_name is None else period_name
+        return self._windowed(SurvivalPeriodsModel(self.infected, self.exposure, titer, antigen, periods, name, device=self.device))
+
+    def periods_from_splits(self, splits) -> np.ndarray:
+        """(n_int,) labels: interval t, which covers gap ``start + 1 + t``, gets the number of ``splits`` (gaps, as
+        ``TiterData.calculate_splits`` gives them) that are <= that gap -- 0 before the first split, 1 from it on, ..."""
+        splits = np.asarray(list(splits), dtype=np.int64).reshape(-1)
+        gaps = self.start + 1 + self.intervals
+        return (splits[None, :] <= gaps[:, None]).sum(axis=1).astype(np.int64)
 
     def model_combined(self) -> SurvivalModel:
         return self._windowed(SurvivalModel(self.infected, self.exposure, [self.s_titer, self.n_titer], ("S", "N"), device=self.device))
@@ -288,7 +353,7 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
     """NUTS on ``model`` (a ``SurvivalModel``, or anything with ``dim``, ``names``, ``K``): (chains, draws) arrays of the
     unconstrained entries under ``model.names``, of ``a``, ``b``, ``lam0``, ``_lam0_raw_mu``, ``_lam0_raw_sd``, and ``stat_*``.
     A model that offers ``initial_point()`` and ``constrain(q)`` (``SurvivalGroupsModel``) is started and read through them; its
-    fit also holds ``groups`` and ``group_name`` where the model has them.
+    fit also holds ``groups`` and ``group_name``, or ``periods``, ``period_name`` and ``period_index``, where the model has them.
     ``evaluator``: a callable ``q -> (logp, grad)`` in place of the device (tests)."""
     fn = evaluator if evaluator is not None else model.logp_dlogp
     dim, K = model.dim, model.K
@@ -308,6 +373,10 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
     if hasattr(model, "groups"):
         res["groups"] = np.asarray(model.groups)
         res["group_name"] = np.array(getattr(model, "group_name", "group"))
+    if hasattr(model, "periods"):
+        res["periods"] = np.asarray(model.periods)
+        res["period_name"] = np.array(getattr(model, "period_name", "period"))
+        res["period_index"] = np.asarray(model.period_index, dtype=np.int32)
     return res
 
 
@@ -393,11 +462,28 @@ def compare_lines(table) -> list:
             f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}" for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
 
 
-def protection(res, x, antigen: Optional[str] = None, prob: float = 0.95, group=None) -> Dict[str, np.ndarray]:
+def protection(res, x, antigen: Optional[str] = None, prob: float = 0.95, group=None, period=None, interval=None) -> Dict[str, np.ndarray]:
     """``1 - 1 / (1 + exp(-b (x - a)))`` at titers ``x`` per draw, over all draws of all chains: ``mean``, ``median``, ``lower``,
     ``upper`` (each of ``x``'s shape).  ``antigen``: which titer of a combined fit ('S' or 'N'; the other held at its midpoint).
-    ``group``: which group's ``a`` of a grouped fit (one of ``res["groups"]``)."""
+    ``group``: which group's ``a`` of a grouped fit (one of ``res["groups"]``).  Of a fit by period either ``period``, one of
+    ``res["periods"]``, or ``interval``, an index in [0, T): the ``a`` of the period that interval belongs to."""
     a, b = np.asarray(res["a"], dtype=np.float64), np.asarray(res["b"], dtype=np.float64)
+    if "periods" in res:
+        labels, index = np.asarray(res["periods"]), np.asarray(res["period_index"])
+        if (period is None) == (interval is None):
+            raise ValueError(f"a fit by period: give period= (one of {labels.tolist()}) or interval= (0 to {len(index) - 1})")
+        if interval is not None:
+            if not (isinstance(interval, (int, np.integer)) and 0 <= interval < len(index)):
+                raise ValueError(f"a fit by period: interval must be an index from 0 to {len(index) - 1}, got {interval!r}")
+            k = int(index[interval])
+        else:
+            hit = np.flatnonzero(labels == period)
+            if len(hit) != 1:
+                raise ValueError(f"a fit by period: period must be one of {labels.tolist()}, got {period!r}")
+            k = int(hit[0])
+        a = a[..., k]
+    elif period is not None or interval is not None:
+        raise ValueError("period= and interval= are for a fit by period (model_alone_periods)")
     if "groups" in res:
         labels = np.asarray(res["groups"])
         hit = np.flatnonzero(labels == group) if group is not None else []
@@ -418,7 +504,7 @@ def protection(res, x, antigen: Optional[str] = None, prob: float = 0.95, group=
     a, b = a.reshape((-1,) + (1,) * x.ndim), b.reshape((-1,) + (1,) * x.ndim)
     with np.errstate(over="ignore"):
         p = 1.0 - 1.0 / (1.0 + np.exp(-b * (x[None] - a)))
-    out = interval(p, prob)
+    out = _interval_of_draws(p, prob)
     out["mean"] = p.mean(axis=0)
     return out
 
@@ -448,6 +534,8 @@ def report_line(res, prob: float = 0.95) -> str:
     parts = []
     if "groups" in res:
         return _report_line_groups(res, prob, pct, names[0])
+    if "periods" in res:
+        return _report_line_groups(res, prob, pct, names[0], labels="periods", label_name="period_name", by="period")
     for k, ag in enumerate(names):
         for v in "ab":
             d = np.asarray(res[v])
@@ -468,14 +556,14 @@ def _rhat_part(rhat: float) -> str:
                                              "do not read the pooled figures, look at a and b per chain" if not rhat <= RHAT_WARN else "")
 
 
-def _report_line_groups(res, prob: float, pct: int, ag: str) -> str:
+def _report_line_groups(res, prob: float, pct: int, ag: str, labels: str = "groups", label_name: str = "group_name", by: str = "group") -> str:
     """A grouped fit's line: per group ``a`` with its interval and the protection at titers 0 / 2 / 4, ``b`` once, the largest
-    R-hat of the ``a_g`` and ``b``."""
-    gname = str(np.asarray(res.get("group_name", "group")))
+    R-hat of the ``a_g`` and ``b``.  A fit by period has the same line over its periods (``labels="periods"``, ...)."""
+    gname = str(np.asarray(res.get(label_name, by)))
     parts = []
-    for k, label in enumerate(np.asarray(res["groups"]).tolist()):
+    for k, label in enumerate(np.asarray(res[labels]).tolist()):
         iv = interval(np.asarray(res["a"])[..., k].reshape(-1), prob)
-        pr = protection(res, np.array([0.0, 2.0, 4.0]), prob=prob, group=label)
+        pr = protection(res, np.array([0.0, 2.0, 4.0]), prob=prob, **{by: label})
         parts.append(f"a[{ag}, {gname} {label}] {iv['median']:.3f} ({pct} % interval {iv['lower']:.3f} to {iv['upper']:.3f}), "
                      "protection at titer 0 / 2 / 4: " + " / ".join(
                          f"{100 * m:.1f} % ({100 * lo:.1f} to {100 * hi:.1f})" for m, lo, hi in zip(pr["median"], pr["lower"], pr["upper"])))
@@ -507,6 +595,14 @@ def read_groups(path: str, n_inds: int) -> np.ndarray:
     return labels
 
 
+def read_periods(path: str, n_intervals: int) -> np.ndarray:
+    """One label per interval from ``.npy`` or a text file, read as ``read_groups`` reads its labels."""
+    try:
+        return read_groups(path, n_intervals)
+    except ValueError as e:
+        raise ValueError(str(e).replace("individuals", "intervals")) from None
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m abdpymc_amd.survival", description="Fit a survival model of a finished run.  Prints one line on stdout: medians and intervals of a and b, "
                                  "the protection at titers 0, 2 and 4, the largest R-hat of a and b.  With --compare: rank fits written with --waic.")
@@ -516,9 +612,15 @@ def main(argv=None) -> int:
     ap.add_argument("--ititers_data", help="The cohort directory the run was made from.")
     ap.add_argument("--start", type=int, help="First gap of the analysis (titers from here).")
     ap.add_argument("--end", type=int, help="One past the last gap of the analysis.")
-    ap.add_argument("--model", choices=("s", "n", "combined", "s_groups", "n_groups"), default="combined")
+    ap.add_argument("--model", choices=("s", "n", "combined", "s_groups", "n_groups", "s_periods", "n_periods"), default="combined")
     ap.add_argument("--groups", help="With --model s_groups / n_groups: a .npy or text file, one label per individual in cohort order.")
     ap.add_argument("--group_name", default="group", help="What the labels of --groups are (the reference's coordinate name).")
+    ap.add_argument("--periods", default="monthly", help="With --model s_periods / n_periods: 'monthly' (one midpoint per interval, the default), "
+                    "'splits' (one per variant era, from --split_delta / --split_omicron as abdpymc-infer takes them), or a .npy or text "
+                    "file with one label per interval.")
+    ap.add_argument("--split_delta", action="store_true", help="With --periods splits: a new period where delta started to circulate.")
+    ap.add_argument("--split_omicron", action="store_true", help="With --periods splits: a new period where omicron started to circulate.")
+    ap.add_argument("--period_name", help="What the labels of --periods are (default: 'intervals' for monthly, else 'period').")
     ap.add_argument("--out", help="Output file (.npz; NetCDF where ArviZ imports and the name does not end in .npz).")
     ap.add_argument("--waic", action="store_true", help="Score the fit by WAIC over the individuals on the device: a second line on stdout, and "
                     "elpd_waic_ind, p_waic_ind, waic_n_cells, waic_n_draws, start, end in the output (what --compare reads).")
@@ -533,12 +635,27 @@ def main(argv=None) -> int:
     missing = [f"--{k}" for k in ("posterior", "ititers_data", "start", "end", "out") if getattr(args, k) is None]
     if missing:
         ap.error("the following arguments are required: " + ", ".join(missing))
+    by_period = args.model.endswith("_periods")
+    if by_period and args.periods == "splits" and not (args.split_delta or args.split_omicron):
+        ap.error("--periods splits needs --split_delta and / or --split_omicron")
+    if (args.split_delta or args.split_omicron) and not (by_period and args.periods == "splits"):
+        ap.error("--split_delta / --split_omicron go with --model s_periods | n_periods --periods splits")
+    if not by_period and (args.periods != "monthly" or args.period_name is not None):
+        ap.error("--periods / --period_name go with --model s_periods | n_periods")
     from .data import TiterData
 
     data = TiterData.from_disk(args.ititers_data)
     try:
         sa = SurvivalAnalysis(args.posterior, args.start, args.end, data, device=args.device)
-        if args.model.endswith("_groups"):
+        if by_period:
+            if args.periods == "monthly":
+                periods = None
+            elif args.periods == "splits":
+                periods = sa.periods_from_splits(data.calculate_splits(delta=args.split_delta, omicron=args.split_omicron))
+            else:
+                periods = read_periods(args.periods, sa.n_int)
+            model = sa.model_alone_periods(args.model[0].upper(), periods, args.period_name)
+        elif args.model.endswith("_groups"):
             if not args.groups:
                 raise ValueError(f"--model {args.model} needs --groups FILE")
             model = sa.model_alone_groups(args.model[0].upper(), read_groups(args.groups, sa.infected.shape[0]), args.group_name)
@@ -580,7 +697,9 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
     """``.npz``; NetCDF through ``cli.write_posterior`` where ArviZ imports and the name does not end in ``.npz`` (no test covers
     that branch: ArviZ is optional and the suite does not require it).  A fit that ``waic`` has scored is stored with its
     ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` and the window ``start`` / ``end`` -- in the ``.npz`` form,
-    which is what ``--compare`` reads; the NetCDF form holds the draws alone."""
+    which is what ``--compare`` reads; the NetCDF form holds the draws alone.  Likewise ``groups`` / ``group_name`` and ``periods`` /
+    ``period_name`` / ``period_index`` are stored in the ``.npz`` form only: ``protection(group= / period= / interval=)`` needs a fit
+    written as ``.npz``."""
     path = str(path)
     if "elpd_waic_ind" in res:
         res = dict(res, start=np.array(sa.start, dtype=np.int64), end=np.array(sa.end, dtype=np.int64))
@@ -590,7 +709,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "start", "end") + WAIC_FIT_KEYS}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

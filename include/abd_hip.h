@@ -668,7 +668,8 @@ typedef struct abd_survival abd_survival;
 /* Checks the descriptor and every cell (ABD_ERR_ARG; before the device is touched), copies the arrays to the device. */
 int abd_survival_create(const abd_survival_desc* desc, abd_survival** out);
 int abd_survival_destroy(abd_survival* s);
-/* D = 2 K + 2 + T (T + Gr + 5 for a handle of abd_survival_create_groups), or -1 for NULL. */
+/* D = 2 K + 2 + T (T + Gr + 5 for a handle of abd_survival_create_groups, T + P + 5 for one of abd_survival_create_periods), or
+ * -1 for NULL. */
 int32_t abd_survival_dim(abd_survival* s);
 /* logp[n] and grad[n][D] at theta[n][D]; up to ABD_MAX_BATCH points share a launch (more are split).  A point's result is
  * the same bits alone and in any batch. */
@@ -710,7 +711,40 @@ typedef struct {
  * sorted by group. */
 int abd_survival_create_groups(const abd_survival_groups_desc* desc, abd_survival** out);
 
-/* The per-individual log-likelihood of a handle of either kind, for comparing fitted models of one cohort (WAIC by individual):
+/* The survival model by period (put together from the reference's helpers as model_alone_groups is, for the fits that
+ * plotting.plot_protection(interval=) and plot_protection_timevariable read): one titer, one shared slope b, and a midpoint a_p
+ * per period of time under a hierarchical prior, every interval t belonging to one period p(t),
+ *   infected[j, t] ~ Poisson(exposure[j, t] * lam0[t] * invlogit(b (titer[j, t] - a[period[t]])))
+ *   theta[D] = _lam0_raw_mu, _lam0_raw_sd_log__, __lam0_raw_z[T], a_mu, a_sd_log__, _a_z[P], b        D = T + P + 5
+ * (the grouped layout with Gr -> P; a_p = a_mu + exp(a_sd_log__) * _a_z_p).  P = T with period[t] = t is the time-variable model,
+ * P = 2 or 3 one midpoint per variant era; the labels need not be monotone.  The handle is an abd_survival: abd_survival_dim,
+ * _logp_dlogp, _loglik_sums, _individual_loglik, the three _waic_* and _destroy work on it.  Its loglik_sums are
+ * sums[2 T + 2] = S_t[T], L, W_x, W0_t[T] with S_t, L and w as above, W_x = sum w titer, W0_t = sum of w over the individuals in
+ * interval t; the library folds W0_t into W0_p = sum_{t in p} W0_t on the host (d/da_p = -b W0_p). */
+typedef struct {
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_periods;           /* P, 1 <= P <= T; a period may be without intervals (its _a_z sees its prior alone) */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const double* infected;      /* (N, T) row-major, as in abd_survival_desc */
+  const double* exposure;      /* (N, T) row-major */
+  const double* titer;         /* (N, T) row-major, finite wherever the cell is followed */
+  const int32_t* period;       /* (T), each in [0, P) */
+  double lam0_mu_mean;         /* _lam0_raw_mu ~ Normal(lam0_mu_mean, lam0_mu_sd): -3, 0.5 (hyper_mu = -3, as model_alone) */
+  double lam0_mu_sd;
+  double lam0_sd_rate;         /* _lam0_raw_sd ~ Exponential(lam0_sd_rate): 2 */
+  double lam0_z_sd;            /* __lam0_raw_z ~ Normal(0, lam0_z_sd): 1 */
+  double a_mu_sd;              /* a_mu ~ Normal(0, a_mu_sd): 0.5 */
+  double a_sd_rate;            /* a_sd ~ Exponential(a_sd_rate): 2 */
+  double a_z_sd;               /* _a_z ~ Normal(0, a_z_sd): 1 */
+  double b_sd;                 /* b ~ Normal(0, b_sd): 0.5 */
+} abd_survival_periods_desc;
+
+/* Checks the descriptor, every label and every cell (ABD_ERR_ARG; before the device is touched), copies the arrays to the device
+ * in the caller's order of individuals. */
+int abd_survival_create_periods(const abd_survival_periods_desc* desc, abd_survival** out);
+
+/* The per-individual log-likelihood of a handle of any kind, for comparing fitted models of one cohort (WAIC by individual):
  *   ll[p][j] = sum_t log Poisson(infected[j, t] | exposure[j, t] * lam0[t] * invlogit(eta[j, t]))
  * at theta[n][D] in the handle's layout, with PyMC's convention for fractional infected
  * (y log mu - mu - lgamma(y + 1), a cell with y = 0 has no log term).  ll is (n, N) row-major in the caller's order of

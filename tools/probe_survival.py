@@ -9,8 +9,13 @@ the same run: microseconds per call for 1 and 4 points, the tile counts, and the
 (launches of 16, a host clock around calls that end in a synchronise) beside ``logp_dlogp`` at one point per call on the same
 handle, alternating, ``--reps`` times; per repeat and at its best, microseconds per draw, per single-point evaluation, the ratio.
 
+``--periods P [P]`` times the model by period in the same way, with P periods of equal length (0: monthly, P = T),
+every P at both sizes, beside the ungrouped K = 1 model on the same data in the same run; ``--fit`` adds the wall time of a
+``--tune`` + ``--draws`` x 4-chain fit of each of them and of the K = 1 model.
+
     python tools/probe_survival.py [--out FILE] [--tune 1000] [--draws 1000] [--no_fit]
     python tools/probe_survival.py --groups 4 8 [--out FILE]
+    python tools/probe_survival.py --periods 3 0 [--fit] [--out FILE]
     python tools/probe_survival.py --leg waic [--points 4000] [--reps 3] [--out FILE]
 """
 import argparse
@@ -84,6 +89,50 @@ def probe_groups(N, T, Gr):
     return row
 
 
+def timed_fit(model, tune, draws):
+    """wall time, evaluations, mean tree depth and the largest R-hat of a and b of a tune + draws x 4-chain fit"""
+    count = [0]
+
+    def counted(x):
+        count[0] += 1
+        return model.logp_dlogp(x)
+
+    t0 = time.perf_counter()
+    fit = survival.sample(model, tune=tune, draws=draws, chains=4, seed=0, evaluator=counted)
+    wall = time.perf_counter() - t0
+    sm = survival.summary(fit)
+    return {"fit_wall_s": wall, "fit_evaluations": count[0], "fit_mean_tree_depth": float(fit["stat_tree_depth"].mean()),
+            "fit_rhat_max_ab": float(max(np.max(sm["a"]["rhat"]), np.max(sm["b"]["rhat"])))}
+
+
+def probe_periods(N, T, P, fit, tune, draws):
+    """One row: the model by period (P periods of equal length; P = T: monthly) and the ungrouped K = 1 model on the S titer of
+    ``simulate(N, T)``, timed one after the other, twice, the smaller figure kept; with ``fit`` a fit of each."""
+    y, e, xs = simulate(N, T)
+    periods = np.arange(T) * P // T
+    alone = survival.SurvivalModel(y, e, xs[:1], ("S",))
+    by_period = survival.SurvivalPeriodsModel(y, e, xs[0], "S", periods)
+    rng = np.random.default_rng(1)
+    qp = np.tile(by_period.initial_point(), (4, 1)) + rng.uniform(-0.5, 0.5, size=(4, by_period.dim))
+    q1 = np.zeros((4, alone.dim))
+    q1[:, 2], q1[:, 3] = -3.0, np.log(0.5)
+    q1 += rng.uniform(-0.5, 0.5, size=q1.shape)
+    row = {"N": N, "T": T, "P": P, "dim": by_period.dim, "tiles": (N + 63) // 64}
+    for _ in range(2):
+        for name, fn, q in (("ungrouped_us_per_call_n1", alone.logp_dlogp, q1[0]), ("periods_us_per_call_n1", by_period.logp_dlogp, qp[0]),
+                            ("ungrouped_us_per_call_n4", alone.logp_dlogp, q1), ("periods_us_per_call_n4", by_period.logp_dlogp, qp)):
+            row[name] = min(row.get(name, np.inf), per_call(fn, q))
+    row["ratio_n1"] = row["periods_us_per_call_n1"] / row["ungrouped_us_per_call_n1"]
+    row["ratio_n4"] = row["periods_us_per_call_n4"] / row["ungrouped_us_per_call_n4"]
+    if fit:
+        row.update({"fit_tune": tune, "fit_draws": draws, "fit_chains": 4})
+        row.update({"periods_" + k: v for k, v in timed_fit(by_period, tune, draws).items()})
+        row.update({"ungrouped_" + k: v for k, v in timed_fit(alone, tune, draws).items()})
+    alone.close()
+    by_period.close()
+    return row
+
+
 def probe_waic(N, T, points, reps):
     """One row: ``waic_accumulate`` of ``points`` draws against ``logp_dlogp`` at one point per call, on one handle of the combined
     model of ``simulate(N, T)``."""
@@ -119,6 +168,8 @@ def main(argv=None):
     ap.add_argument("--points", type=int, default=4000, help="--leg waic: draws folded per repeat")
     ap.add_argument("--reps", type=int, default=3, help="--leg waic: repeats")
     ap.add_argument("--groups", type=int, nargs="+", help="time the model by group with this many groups (one figure, or one per size)")
+    ap.add_argument("--periods", type=int, nargs="+", help="time the model by period with this many periods (0: monthly), each at every size")
+    ap.add_argument("--fit", action="store_true", help="--periods: also time a fit of the model by period and of the K = 1 model")
     ap.add_argument("--out")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
@@ -135,7 +186,17 @@ def main(argv=None):
         for (N, T), Gr in zip(SIZES, args.groups * (len(SIZES) if len(args.groups) == 1 else 1)):
             rows.append(probe_groups(N, T, Gr))
             print(json.dumps(rows[-1]), flush=True)
-    for N, T in SIZES if not args.groups and args.leg == "eval" else ():
+    for N, T in SIZES if args.periods else ():
+        for P in args.periods:
+            if not 0 <= P <= T:
+                ap.error(f"--periods: {P} outside [0, {T}]")
+            rows.append(probe_periods(N, T, P or T, args.fit, args.tune, args.draws))
+            print(json.dumps(rows[-1]), flush=True)
+            if args.out:  # kept row by row: a long run that is cut short leaves what it measured
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "w") as f:
+                    json.dump(rows, f, indent=1)
+    for N, T in SIZES if not args.groups and not args.periods and args.leg == "eval" else ():
         y, e, xs = simulate(N, T)
         rs = R.Restatement(y, e, xs)
         model = survival.SurvivalModel(y, e, xs, ("S", "N"))
