@@ -564,6 +564,31 @@ struct AdaptiveNuts {
     it = 0;
   }
   bool tuning() const { return it < tune; }
+  // Install a diagonal M^-1 (nullptr keeps the chain's) and / or a step size (<= 0 keeps the chain's) between two transitions
+  // (PyMC: pm.NUTS(scaling=..., step_scale=...)); the caller has checked the values, and that the chain's metric is diagonal.
+  // After tuning that is all.  While it < tune the adaptations would overwrite both at the end of the next transition, so they
+  // are re-seeded to go on FROM the installed values: the dual average starts over around the step size (mu = log(10 eps),
+  // as init does), the metric's foreground window becomes the prior "10 draws at the chain's current point with variance
+  // inv_mass" (mass.init's prior with the installed variance in place of 1) and the background window and the window count
+  // start over.
+  void install(const double* inv_mass, double step_size) {
+    if (inv_mass) {
+      std::memcpy(nuts.inv_mass, inv_mass, sizeof(nuts.inv_mass));
+      if (it < tune) {
+        mass.fg.n = 10.0;
+        for (int k = 0; k < D; ++k) {
+          mass.fg.mean[k] = nuts.q[k];
+          mass.fg.m2[k] = 10.0 * inv_mass[k];
+        }
+        mass.bg.reset();
+        mass.n_seen = 0;
+      }
+    }
+    if (step_size > 0.0) {
+      nuts.eps = step_size;
+      if (it < tune) da.init(step_size, target);
+    }
+  }
   // start the transition of iteration `it`
   void begin() {
     begin_draw();

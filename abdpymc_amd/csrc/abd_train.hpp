@@ -35,9 +35,17 @@ __device__ __forceinline__ void train_put_point(TrainPoint* nx, int lane, double
 }
 
 // half kick + drift from (q, p, g) with signed step ve (abd_nuts.hpp: stage_leapfrog)
+// The first leaf of a transition that begins without an evaluation of its start point (the first of a run call; every one when
+// no sweep runs) is staged TWICE from the same numbers: here, where it is evaluated, and by the host, whose tree and leapfrog log
+// hold it.  The two must be the same bits, so no product may be fused into a sum here: the __dadd_rn / __dmul_rn of this
+// toolchain are plain operators, which the compiler contracted to fma (found by tests/test_gpu_nuts_replay.py: a run in calls
+// of one iteration parted from the same run in one call at the second transition).
 __device__ __forceinline__ void train_stage(double q, double p, double g, double ve, double im, double& t2, double& ph) {
-  ph = __dadd_rn(p, __dmul_rn(__dmul_rn(0.5, ve), g));  // p_half = cur.p + 0.5 ve cur.g
-  t2 = __dadd_rn(q, __dmul_rn(ve, __dmul_rn(im, ph)));  // req_q = cur.q + ve (M^-1 p_half)
+#pragma clang fp contract(off)
+  const double half_ve = 0.5 * ve, kick = half_ve * g;
+  ph = p + kick;  // p_half = cur.p + 0.5 ve cur.g
+  const double v = im * ph, drift = ve * v;
+  t2 = q + drift;  // req_q = cur.q + ve (M^-1 p_half)
 }
 
 // the record of step tc.rec_idx / tc.fwd_idx goes to the host: fields first, the tag behind a system-scope fence

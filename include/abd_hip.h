@@ -549,7 +549,12 @@ int abd_sampler_timeline_quantiles(abd_sampler* s, int32_t n_q, const double* q,
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric);
 /* Install a diagonal M^-1 (17 entries, all > 0; NULL keeps the chain's) and / or a step size (<= 0 keeps the chain's) for chain
  * k between two abd_sampler_run calls, e.g. one adaptation pooled over the chains (PyMC: pm.sample(step=pm.NUTS(scaling=...,
- * step_scale=...))).  During iterations < tune the chain goes on adapting from there. */
+ * step_scale=...))).  The next transition runs with exactly these values.  After tuning they stay.  During iterations < tune
+ * the chain goes on adapting from there, which re-seeds the adaptation that a value replaces: a step size starts the dual
+ * average over (no history, mu = log(10 step_size)); a metric makes the variance estimate's foreground window the prior "10
+ * draws at the chain's current point with variance inv_mass", empties its background window and starts the count of its
+ * 101-draw windows over.  A value that is kept leaves its adaptation untouched.  Nothing is installed when a value is refused
+ * (ABD_ERR_ARG), or when the chain already runs a dense metric (ABD_ERR_STATE). */
 int abd_sampler_set_adaptation(abd_sampler* s, int32_t k, const double* inv_mass, double step_size);
 
 /* The leapfrog log: a test and debug facility (no per-draw summary; off by default, one branch per evaluation when off).  Every

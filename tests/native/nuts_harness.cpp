@@ -308,3 +308,98 @@ extern "C" int nuts_harness_run_logged(const double* mean, const double* sd, lon
   return trains ? run_trains(mean, sd, tune, draws, seed, n_chains, eval_first, run_on, lo, out_q, out_stats)
                 : run_classic(mean, sd, nullptr, tune, draws, seed, n_chains, 0, eval_first, lo, out_q, out_stats);
 }
+
+// ---- the classic loop with everything a replay of its transitions needs (tests/test_nuts_replay_cpu.py): either target, either
+// metric, eval_first, a tree depth of the caller's choice, and installations as abd_sampler_set_adaptation makes them
+// (AdaptiveNuts::install, between two transitions).  inst: n_inst rows of INST_COLS doubles -- the iteration before whose
+// transition the values are installed, the chain, whether a metric is given, the step size (<= 0: kept), the 17 entries of the
+// metric; an installation on a chain that runs a dense metric is refused as the library refuses it (counted in the result, which
+// is otherwise 0).  For ALL tune + draws iterations: out_q [C][T][17]; out_stats [C][T][8] -- lp, tree_depth, n_steps,
+// mean_tree_accept, step_size, diverging, energy, max_energy_error; and what the chain holds once the iteration has ended (what
+// abd_sampler_adaptation reads then): out_eps [C][T], out_inv_mass [C][T][17], out_metric [C][T][17][17] (the diagonal matrix
+// while the metric is diagonal).  The leapfrog log as in nuts_harness_run_logged.
+enum { INST_COLS = 4 + abdnuts::D };
+extern "C" int nuts_harness_run_adapt(const double* mean, const double* sd, const double* prec, long long tune, long long draws,
+                                      unsigned long long seed, int n_chains, int dense, int eval_first, int max_depth, int n_inst,
+                                      const double* inst, long long capacity, double* rows, long long* n_total, double* out_q,
+                                      double* out_stats, double* out_eps, double* out_inv_mass, double* out_metric) {
+  using namespace abdnuts;
+  LogOut lo;
+  lo.capacity = capacity;
+  lo.rows = rows;
+  lo.n_total = n_total;
+  auto eval = [&](const double* q, double* g) {
+    double lp = 0;
+    if (prec) {
+      for (int r = 0; r < D; ++r) {
+        double s = 0;
+        for (int c = 0; c < D; ++c) s += prec[r * D + c] * (q[c] - mean[c]);
+        g[r] = -s;
+        lp -= 0.5 * s * (q[r] - mean[r]);
+      }
+      return lp;
+    }
+    for (int d = 0; d < D; ++d) {
+      const double z = (q[d] - mean[d]) / sd[d];
+      lp -= 0.5 * z * z;
+      g[d] = -z / sd[d];
+    }
+    return lp;
+  };
+  const long long T = tune + draws;
+  int refused = 0;
+  std::vector<AdaptiveNuts> ch((size_t)n_chains);
+  std::vector<LeapfrogLog> logs((size_t)n_chains, LeapfrogLog(capacity < 0 ? 0 : capacity));
+  for (int c = 0; c < n_chains; ++c) {
+    double q0[D], g0[D];
+    for (int d = 0; d < D; ++d) q0[d] = mean[d] + sd[d] * (c % 2 ? 1.5 : -1.5);
+    const double lp0 = eval(q0, g0);
+    ch[(size_t)c].init(q0, lp0, g0, seed, (unsigned long long)c, tune, max_depth, 0.8, dense != 0);
+    if (capacity >= 0) ch[(size_t)c].nuts.attach_log(&logs[(size_t)c]);
+  }
+  for (long long it = 0; it < T; ++it) {
+    for (int i = 0; i < n_inst; ++i) {
+      const double* r = inst + (size_t)i * INST_COLS;
+      if ((long long)r[0] != it) continue;
+      AdaptiveNuts& a = ch[(size_t)r[1]];
+      if (a.nuts.dense) {
+        refused += 1;
+        continue;
+      }
+      a.install(r[2] != 0.0 ? r + 4 : nullptr, r[3]);
+    }
+    for (int c = 0; c < n_chains; ++c) {
+      AdaptiveNuts& a = ch[(size_t)c];
+      if (eval_first) {
+        double g[D];
+        const double lp = eval(a.nuts.q, g);
+        a.nuts.set_point(lp, g);
+      }
+      a.begin();
+      while (a.nuts.active) {
+        double g[D];
+        const double lp = eval(a.nuts.request(), g);
+        a.nuts.feed(lp, g);
+      }
+      a.end_transition();
+      const size_t row = (size_t)c * T + it;
+      const Nuts& nu = a.nuts;
+      for (int d = 0; d < D; ++d) out_q[row * D + d] = nu.q[d];
+      double* s = out_stats + row * 8;
+      s[0] = nu.stats.lp;
+      s[1] = nu.stats.tree_depth;
+      s[2] = nu.stats.n_steps;
+      s[3] = nu.stats.mean_tree_accept;
+      s[4] = nu.stats.step_size;
+      s[5] = nu.stats.diverging ? 1.0 : 0.0;
+      s[6] = nu.stats.energy;
+      s[7] = nu.stats.max_energy_error;
+      out_eps[row] = nu.eps;
+      for (int d = 0; d < D; ++d) out_inv_mass[row * D + d] = nu.inv_mass[d];
+      for (int r = 0; r < D; ++r)
+        for (int k = 0; k < D; ++k) out_metric[(row * D + r) * D + k] = nu.dense ? nu.cov[r][k] : (r == k ? nu.inv_mass[r] : 0.0);
+    }
+  }
+  for (int c = 0; c < n_chains; ++c) lo.take(c, logs[(size_t)c]);
+  return refused;
+}
