@@ -230,7 +230,15 @@ SYMBOLS = {
     "abd_survival_waic_reset": (C.c_int, [_P]),
     "abd_survival_waic_accumulate": (C.c_int, [_P, C.c_int32, _D]),
     "abd_survival_waic_stats": (C.c_int, [_P, _D, _D, _D, C.POINTER(C.c_int64), _I32]),
+    "abd_survival_predictive_configure": (C.c_int, [_P, C.c_int32, _P, _I32, _P, C.c_uint64]),
+    "abd_survival_predictive_reset": (C.c_int, [_P]),
+    "abd_survival_predictive_accumulate": (C.c_int, [_P, C.c_int32, _D, _D, _P]),
+    "abd_survival_predictive_stats": (C.c_int, [_P, _D, _P, _P, C.POINTER(C.c_int64)]),
+    "abd_survival_predictive_observed": (C.c_int, [_P, _D, _D, _P, _D]),
+    "abd_survival_replicate": (C.c_int, [_P, C.c_int32, _D, C.c_int64, _I32]),
 }
+
+SURVIVAL_PREDICTIVE_BINS = 8  # ABD_SURV_PRED_BINS: bins of a binning variable (up to 7 edges)
 
 
 def load():
@@ -1145,6 +1153,60 @@ class Survival:
         n = C.c_int64()
         _check(self._lib, self._lib.abd_survival_waic_stats(self._h, _ptr(lse), _ptr(mean), _ptr(m2), C.byref(n), _ptr(cells, C.c_int32)))
         return (lse, mean, m2, int(n.value)), cells.astype(np.int64)
+
+    def predictive_configure(self, titers, edges, seed: int = 0):
+        """The binning variables of the posterior predictive checks: one or two titer arrays (N, T) with their edges (each up to 7,
+        finite, strictly ascending).  The library checks them, computes the constants and sets the draw counter to 0."""
+        xs = [_as(x, np.float64) for x in titers]
+        es = [_as(np.asarray(e, dtype=np.float64).reshape(-1), np.float64) for e in edges]
+        if len(xs) != len(es):
+            raise ValueError(f"{len(xs)} binning variables with {len(es)} sets of edges")
+        if any(x.shape != (self.n_inds, self.n_intervals) for x in xs):
+            raise ValueError(f"a binning variable must have shape ({self.n_inds}, {self.n_intervals})")
+        n = len(xs)
+        tp = (C.c_void_p * max(n, 1))(*[x.ctypes.data for x in xs])
+        ep = (C.c_void_p * max(n, 1))(*[e.ctypes.data if e.size else None for e in es])
+        ne = np.array([e.size for e in es] or [0], dtype=np.int32)
+        _check(self._lib, self._lib.abd_survival_predictive_configure(self._h, n, C.addressof(tp), _ptr(ne), C.addressof(ep),
+                                                                      int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.n_predictive_vars = n
+
+    def predictive_reset(self):
+        _check(self._lib, self._lib.abd_survival_predictive_reset(self._h))
+
+    def predictive_accumulate(self, theta):
+        """Folds the draws ``theta`` (n, D) in order; returns (expected (n, n_var, 8) float64, replicate (n, n_var, 8) int64): per draw
+        the expected and the replicated infections of every bin of every binning variable."""
+        t = self._points(theta)
+        nv = getattr(self, "n_predictive_vars", 0) or 1  # before predictive_configure the library refuses the call
+        exp_, rep = np.zeros((t.shape[0], nv, SURVIVAL_PREDICTIVE_BINS)), np.zeros((t.shape[0], nv, SURVIVAL_PREDICTIVE_BINS), np.int64)
+        _check(self._lib, self._lib.abd_survival_predictive_accumulate(self._h, t.shape[0], _ptr(t), _ptr(exp_), _ptr(rep)))
+        return exp_, rep
+
+    def predictive_stats(self):
+        """(sum_e, sum_r, n_pos, n_draws): per individual (N,) over the draws folded, the sums of E_j and of R_j and the number of
+        draws with R_j >= 1."""
+        N = self.n_inds
+        sum_e, sum_r, n_pos = np.empty(N), np.empty(N, np.int64), np.empty(N, np.int64)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_survival_predictive_stats(self._h, _ptr(sum_e), _ptr(sum_r), _ptr(n_pos), C.byref(n)))
+        return sum_e, sum_r, n_pos, int(n.value)
+
+    def predictive_observed(self):
+        """(observed (n_var, 8), person_time (n_var, 8), n_cells (n_var, 8) int64, observed_ind (N,)): the constants of the data."""
+        nv = getattr(self, "n_predictive_vars", 0) or 1
+        obs, pt = np.zeros((nv, SURVIVAL_PREDICTIVE_BINS)), np.zeros((nv, SURVIVAL_PREDICTIVE_BINS))
+        cells, ind = np.zeros((nv, SURVIVAL_PREDICTIVE_BINS), np.int64), np.zeros(self.n_inds)
+        _check(self._lib, self._lib.abd_survival_predictive_observed(self._h, _ptr(obs), _ptr(pt), _ptr(cells), _ptr(ind)))
+        return obs, pt, cells, ind
+
+    def replicate(self, theta, draw0: int = 0):
+        """``theta`` (n, D) -> (n, N, T) int32: the per-cell replicates of the draws ``draw0 .. draw0 + n - 1``, in the caller's order;
+        what ``predictive_accumulate`` draws for those indices.  Folds nothing."""
+        t = self._points(theta)
+        out = np.zeros((t.shape[0], self.n_inds, self.n_intervals), np.int32)
+        _check(self._lib, self._lib.abd_survival_replicate(self._h, t.shape[0], _ptr(t), int(draw0), _ptr(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

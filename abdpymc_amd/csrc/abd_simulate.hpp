@@ -38,7 +38,7 @@
 
 namespace abdi {
 
-constexpr uint32_t kSimExposure = 0x40000000u, kSimProtection = 0x40000001u, kSimNoise = 0x40000010u;  // c3 of the streams
+// c3 of the streams (kSimExposure, kSimProtection, kSimNoise) and sim_uniform: abd_types.hpp, beside philox4x32_10
 
 // what the walk reads of one antigen's parameters
 struct SimWalkAb {
@@ -56,11 +56,6 @@ struct SimState {
 };
 
 __host__ __device__ inline SimState sim_start(const SimWalkPar& p) { return {p.s.init, p.n.init, 0.0, 0.0, false, false}; }
-
-__host__ __device__ inline double sim_uniform(uint32_t a, uint32_t b) {
-  constexpr double kTwo53 = 1.0 / 9007199254740992.0;
-  return ((double)(((uint64_t)(a >> 5) << 26) | (b >> 6)) + 0.5) * kTwo53;
-}
 
 __host__ __device__ inline double sim_p_protection(const SimWalkAb& ab, double titer) {
   return 1.0 / (1.0 + exp(-ab.protect_b * (titer - ab.protect_a)));

@@ -1,8 +1,9 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
-// handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators.  A
-// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp
-// and abd_survival_pointwise.hpp; the closed forms, the packing of the planes and the form of a model (SurvivalForm) are plain
-// C++ in the four *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
+// handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, the
+// posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate).  A
+// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp,
+// abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the packing of the planes and the form of a model
+// (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
 #include <memory>
 
 #include "abd_host.hpp"
@@ -13,6 +14,8 @@
 #include "abd_survival_periods_terms.hpp"
 #include "abd_survival_pointwise.hpp"
 #include "abd_survival_pointwise_terms.hpp"
+#include "abd_survival_predictive.hpp"
+#include "abd_survival_predictive_terms.hpp"
 #include "abd_survival_terms.hpp"
 
 namespace abdi {
@@ -23,6 +26,7 @@ struct SurvivalSpec {
   SurvivalPriors priors{};         // of the form with K titers
   SurvivalGroupsPriors gpriors{};  // of the forms by group and by period
 };
+constexpr int kSurvRepBatch = 4;  // points per launch of abd_survival_replicate: its per-cell buffer holds this many
 }  // namespace abdi
 
 struct abd_survival : SurvivalSpec {
@@ -41,6 +45,19 @@ struct abd_survival : SurvivalSpec {
   DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
   MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
   int64_t waic_n = 0;              // draws folded into d_acc
+  // the posterior predictive checks (abd_survival_predictive.hpp)
+  int pp_nvar = 0;                 // binning variables of the configuration; 0: abd_survival_predictive_configure has not run
+  uint32_t pp_seed_lo = 0, pp_seed_hi = 0;
+  SurvPredConstants pp_const;      // observed, person-time and followed cells per (variable, bin); O_j in the caller's order
+  DevBuf<uint8_t> d_pp_bins;       // [T][ld]
+  DevBuf<int32_t> d_pp_slot_j, d_pp_rj, d_pp_rep;  // [ld], [ABD_MAX_BATCH][ld], [kSurvRepBatch][T][ld] (at the first abd_survival_replicate)
+  DevBuf<uint32_t> d_pp_r_part;                    // [ABD_MAX_BATCH][ntile][ABD_SURV_PRED_COLS]
+  DevBuf<double> d_pp_e_part, d_pp_ej, d_pp_out_e, d_pp_acc_e;  // as d_pp_r_part, [ABD_MAX_BATCH][ld], [ABD_MAX_BATCH][COLS], [ld]
+  DevBuf<int64_t> d_pp_out_r, d_pp_acc_r;          // [ABD_MAX_BATCH][COLS]; [2][ld]: sum of R_j, draws with R_j >= 1
+  MappedBuf<double> h_pp_out_e, h_pp_acc_e;        // pinned
+  MappedBuf<int64_t> h_pp_out_r, h_pp_acc_r;
+  MappedBuf<int32_t> h_pp_rep;
+  int64_t pp_n = 0;                // draws folded since the last reset
   Stream stream;
 
   int column(int j) const { return slot.empty() ? j : slot[j]; }
@@ -170,6 +187,85 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (fold) s->waic_n += n;
+  return ABD_OK;
+}
+
+// ---- the posterior predictive checks (abd_survival_predictive.hpp) ----
+
+int survival_predictive_configured(const abd_survival* s) {
+  if (s->pp_nvar < 1) return fail(ABD_ERR_ARG, "no binning variables (abd_survival_predictive_configure comes first)");
+  return ABD_OK;
+}
+
+// the buffers of the predictive launches, at the first of them
+int survival_predictive_ensure(abd_survival* s) {
+  if (s->d_pp_ej) return ABD_OK;
+  const size_t ld = (size_t)s->ld, part = (size_t)ABD_MAX_BATCH * s->ntile * ABD_SURV_PRED_COLS, out = (size_t)ABD_MAX_BATCH * ABD_SURV_PRED_COLS;
+  HIP_TRY(s->d_pp_e_part.alloc(part));
+  HIP_TRY(s->d_pp_r_part.alloc(part));
+  HIP_TRY(s->d_pp_rj.alloc(ABD_MAX_BATCH * ld));
+  HIP_TRY(s->d_pp_out_e.alloc(out));
+  HIP_TRY(s->d_pp_out_r.alloc(out));
+  HIP_TRY(s->h_pp_out_e.alloc_pinned(out));
+  HIP_TRY(s->h_pp_out_r.alloc_pinned(out));
+  HIP_TRY(s->d_pp_acc_e.alloc(ld));
+  HIP_TRY(s->d_pp_acc_r.alloc(2 * ld));
+  HIP_TRY(s->d_pp_ej.alloc(ABD_MAX_BATCH * ld));
+  return ABD_OK;
+}
+
+// The replicates of n <= ABD_MAX_BATCH points (n <= kSurvRepBatch where rep) as draws draw0 .. draw0 + n - 1.  fold: the bin sums
+// go to s->h_pp_out_e / h_pp_out_r and the rows E_j, R_j into the accumulators; rep: the per-cell replicates go to s->h_pp_rep.
+int survival_predictive_launch(abd_survival* s, int n, const double* theta, int64_t draw0, bool fold, bool rep) {
+  if (int rc = survival_predictive_ensure(s)) return rc;
+  const int T = s->form.T;
+  const size_t cells = (size_t)T * s->ld;
+  if (rep && !s->d_pp_rep) {
+    HIP_TRY(s->h_pp_rep.alloc_pinned(kSurvRepBatch * cells));
+    HIP_TRY(s->d_pp_rep.alloc(kSurvRepBatch * cells));
+  }
+  survival_prepare_points(s, n, theta);
+  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->form.par_stride() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalReplicateArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.e = s->d_e;
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.bins = s->d_pp_bins;
+  a.slot_j = s->d_pp_slot_j;
+  a.par = s->d_par;
+  a.tile_group = s->d_tile_group;
+  a.e_part = s->d_pp_e_part;
+  a.r_part = s->d_pp_r_part;
+  a.ej = s->d_pp_ej;
+  a.rj = s->d_pp_rj;
+  a.rep = rep ? (int32_t*)s->d_pp_rep : nullptr;
+  a.draw0 = draw0;
+  a.seed_lo = s->pp_seed_lo;
+  a.seed_hi = s->pp_seed_hi;
+  a.T = T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.par_stride = s->form.par_stride();
+  a.n_ab = s->form.n_ab();
+  a.n_var = s->pp_nvar;
+  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
+  void (*const kernels[4])(const SurvivalReplicateArgs) = {abd_survival_replicate_kernel<0>, abd_survival_replicate_kernel<1>,
+                                                           abd_survival_replicate_kernel<2>, abd_survival_replicate_kernel<3>};
+  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), survival_replicate_lds(s->pp_nvar), s->stream, a));
+  if (fold) {
+    HIP_TRY(launch_kernel(abd_survival_predictive_finalize, dim3(1, (unsigned)n), dim3(256), 0, s->stream, (const double*)s->d_pp_e_part,
+                          (const uint32_t*)s->d_pp_r_part, (double*)s->d_pp_out_e, (int64_t*)s->d_pp_out_r, (int32_t)s->ntile,
+                          (int32_t)(s->pp_nvar * ABD_SURV_PRED_BINS)));
+    HIP_TRY(launch_kernel(abd_survival_predictive_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_pp_ej,
+                          (const int32_t*)s->d_pp_rj, (double*)s->d_pp_acc_e, (int64_t*)s->d_pp_acc_r, (int64_t*)s->d_pp_acc_r + s->ld,
+                          (int32_t)s->ld, (int32_t)n, draw0));
+    const size_t out = (size_t)n * ABD_SURV_PRED_COLS;
+    HIP_TRY(hipMemcpyAsync(s->h_pp_out_e.host(), s->d_pp_out_e, out * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_pp_out_r.host(), s->d_pp_out_r, out * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+  }
+  if (rep) HIP_TRY(hipMemcpyAsync(s->h_pp_rep.host(), s->d_pp_rep, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
   return ABD_OK;
 }
 
@@ -401,6 +497,122 @@ int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* 
     n_cells[j] = s->n_cells[j];
   }
   *n_draws = s->waic_n;
+  return ABD_OK;
+}
+
+int abd_survival_predictive_configure(abd_survival* s, int32_t n_var, const double* const* titers, const int32_t* n_edges,
+                                      const double* const* edges, uint64_t seed) {
+  if (!s || !titers || !n_edges || !edges) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n_var != 1 && n_var != 2) return fail(ABD_ERR_ARG, "n_var=%d: one or two binning variables", n_var);
+  for (int v = 0; v < n_var; ++v) {
+    if (!titers[v] || (n_edges[v] > 0 && !edges[v])) return fail(ABD_ERR_ARG, "NULL array of binning variable %d", v);
+    if (const char* msg = surv_pred_check_edges(n_edges[v], edges[v])) return fail(ABD_ERR_ARG, "binning variable %d: %s", v, msg);
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  try {
+    const int T = s->form.T;
+    const size_t ld = (size_t)s->ld, plane = ld * T;
+    std::vector<double> y(plane), e(plane);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(y.data(), s->d_y, plane * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(e.data(), s->d_e, plane * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> bins(plane);
+    std::vector<int32_t> slot_j(ld);
+    SurvPredConstants c;
+    const SurvivalRefusal bad = surv_pred_pack(s->N, T, ld, s->slot.empty() ? nullptr : s->slot.data(), y.data(), e.data(), n_var, titers,
+                                               n_edges, edges, bins.data(), slot_j.data(), &c);
+    if (bad.msg) return fail(ABD_ERR_ARG, "individual %d, interval %d: %s", bad.j, bad.t, bad.msg);  // the earlier configuration stands
+    HIP_TRY(s->d_pp_bins.upload(bins.data(), plane));
+    HIP_TRY(s->d_pp_slot_j.upload(slot_j.data(), ld));
+    s->pp_const = std::move(c);
+  } catch (const std::bad_alloc&) {
+    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", s->N, s->form.T);
+  }
+  s->pp_nvar = n_var;
+  s->pp_seed_lo = (uint32_t)seed;
+  s->pp_seed_hi = (uint32_t)(seed >> 32);
+  s->pp_n = 0;  // the first draw folded overwrites its column: the accumulators need no clearing
+  return ABD_OK;
+}
+
+int abd_survival_predictive_reset(abd_survival* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  s->pp_n = 0;
+  return ABD_OK;
+}
+
+int abd_survival_predictive_accumulate(abd_survival* s, int32_t n, const double* theta, double* expected, int64_t* replicate) {
+  if (!s || !theta || !expected || !replicate) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  if (int rc = survival_predictive_configured(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t row = (size_t)s->pp_nvar * ABD_SURV_PRED_BINS;
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_predictive_launch(s, nb, theta + (size_t)k0 * s->form.dim(), s->pp_n, true, false)) return rc;
+    s->pp_n += nb;
+    for (int q = 0; q < nb; ++q) {
+      std::memcpy(expected + ((size_t)k0 + q) * row, s->h_pp_out_e.host() + (size_t)q * ABD_SURV_PRED_COLS, row * sizeof(double));
+      std::memcpy(replicate + ((size_t)k0 + q) * row, s->h_pp_out_r.host() + (size_t)q * ABD_SURV_PRED_COLS, row * sizeof(int64_t));
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_predictive_stats(abd_survival* s, double* sum_e, int64_t* sum_r, int64_t* n_pos, int64_t* n_draws) {
+  if (!s || !sum_e || !sum_r || !n_pos || !n_draws) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_predictive_configured(s)) return rc;
+  if (s->pp_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_predictive_accumulate comes first)");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t ld = (size_t)s->ld;
+  if (!s->h_pp_acc_e.host()) {
+    HIP_TRY(s->h_pp_acc_e.alloc_pinned(ld));
+    HIP_TRY(s->h_pp_acc_r.alloc_pinned(2 * ld));
+  }
+  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_e.host(), s->d_pp_acc_e, ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_r.host(), s->d_pp_acc_r, 2 * ld * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (int j = 0; j < s->N; ++j) {
+    const size_t c = (size_t)s->column(j);
+    sum_e[j] = s->h_pp_acc_e.host()[c];
+    sum_r[j] = s->h_pp_acc_r.host()[c];
+    n_pos[j] = s->h_pp_acc_r.host()[ld + c];
+  }
+  *n_draws = s->pp_n;
+  return ABD_OK;
+}
+
+int abd_survival_predictive_observed(abd_survival* s, double* observed, double* person_time, int64_t* n_cells, double* observed_ind) {
+  if (!s || !observed || !person_time || !n_cells || !observed_ind) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_predictive_configured(s)) return rc;
+  const size_t row = (size_t)s->pp_nvar * ABD_SURV_PRED_BINS;
+  std::memcpy(observed, s->pp_const.observed, row * sizeof(double));
+  std::memcpy(person_time, s->pp_const.person_time, row * sizeof(double));
+  std::memcpy(n_cells, s->pp_const.n_cells, row * sizeof(int64_t));
+  std::memcpy(observed_ind, s->pp_const.observed_ind.data(), (size_t)s->N * sizeof(double));
+  return ABD_OK;
+}
+
+int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int64_t draw0, int32_t* rep) {
+  if (!s || !theta || !rep) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  if (draw0 < 0) return fail(ABD_ERR_ARG, "draw0=%lld is negative", (long long)draw0);
+  if (int rc = survival_predictive_configured(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const int T = s->form.T;
+  const size_t ld = (size_t)s->ld;
+  for (int k0 = 0; k0 < n; k0 += kSurvRepBatch) {
+    const int nb = std::min(kSurvRepBatch, n - k0);
+    if (int rc = survival_predictive_launch(s, nb, theta + (size_t)k0 * s->form.dim(), draw0 + k0, false, true)) return rc;
+    for (int q = 0; q < nb; ++q) {  // [T][ld] in slots to [N][T] in the caller's order
+      const int32_t* plane = s->h_pp_rep.host() + (size_t)q * T * ld;
+      int32_t* out = rep + ((size_t)k0 + q) * s->N * T;
+      for (int j = 0; j < s->N; ++j) {
+        const size_t c = (size_t)s->column(j);
+        for (int t = 0; t < T; ++t) out[(size_t)j * T + t] = plane[(size_t)t * ld + c];
+      }
+    }
+  }
   return ABD_OK;
 }
 

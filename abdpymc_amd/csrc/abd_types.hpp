@@ -323,6 +323,17 @@ __host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
   return o;
 }
 
+// c3 of the keyed streams: the simulator's three (abd_simulate.hpp; the noise stream ors the antigen in) and the survival
+// models' replicates (abd_survival_predictive_terms.hpp).  The sweep's counters have c3 = 0 and the predictive stream of the
+// readings sets c3's top bit: none of them meet.
+constexpr uint32_t kSimExposure = 0x40000000u, kSimProtection = 0x40000001u, kSimNoise = 0x40000010u, kSurvReplicate = 0x40000020u;
+
+// a uniform in (0, 1) from two words, 53 bits: u = ((a >> 5) 2^26 + (b >> 6) + 0.5) 2^-53
+__host__ __device__ inline double sim_uniform(uint32_t a, uint32_t b) {
+  constexpr double kTwo53 = 1.0 / 9007199254740992.0;
+  return ((double)(((uint64_t)(a >> 5) << 26) | (b >> 6)) + 0.5) * kTwo53;
+}
+
 #ifndef ABD_TRANSIT_P_U32  // (a diagnostic build may set it to 0: a sweep that proposes nothing measures the per-individual set-up)
 #define ABD_TRANSIT_P_U32 3435973836u  // floor(0.8 * 2^32): propose iff word 1 < this   (transit_p = 0.8)
 #endif

@@ -22,6 +22,12 @@ with paired standard errors (``compare.compare``).
     python -m abdpymc_amd.survival ... --model s_groups|n_groups --groups FILE [--group_name NAME]
     python -m abdpymc_amd.survival ... --model s_periods|n_periods [--periods monthly|splits|FILE] [--split_delta] [--split_omicron]
     python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz
+    python -m abdpymc_amd.survival ... --ppc [--ppc_edges_s E1,E2,...] [--ppc_edges_n E1,...] [--ppc_seed SEED]
+
+Does the best of them fit?  ``predictive(model, fit, by)`` is the posterior predictive check: per draw the device forms every cell's
+expected count, draws a Poisson replicate of it and sums both over titer bins of one or two freely chosen binning variables and
+over individuals (``abd_survival_predictive_*``, ``abd_survival_replicate``); the observed infections of a bin are
+set against the replicated ones.  ``sample_posterior_predictive`` gives the per-cell replicates of chosen draws.
 """
 from __future__ import annotations
 
@@ -103,6 +109,29 @@ class _DeviceModel:
         """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
         return self._dev.waic_stats()
 
+    def predictive_configure(self, titers, edges, seed: int = 0):
+        """The binning variables of ``predictive``: one or two titer arrays (N, T), each with up to 7 strictly ascending edges."""
+        self._dev.predictive_configure(titers, edges, seed)
+
+    def predictive_reset(self):
+        self._dev.predictive_reset()
+
+    def predictive_accumulate(self, q):
+        """Folds the draws ``q`` (n, D), in order: (expected, replicate), each (n, n_var, 8), per draw and bin."""
+        return self._dev.predictive_accumulate(q)
+
+    def predictive_stats(self):
+        """(sum_e, sum_r, n_pos, n_draws): per individual over the draws folded since ``predictive_reset``."""
+        return self._dev.predictive_stats()
+
+    def predictive_observed(self):
+        """(observed, person_time, n_cells (n_var, 8), observed_ind (N,)): the constants of the configuration."""
+        return self._dev.predictive_observed()
+
+    def replicate(self, q, draw0: int = 0):
+        """(n, D) -> (n, N, T) int32: the per-cell replicates of the draws ``draw0 .. draw0 + n - 1``."""
+        return self._dev.replicate(q, draw0)
+
     def close(self):
         self._dev.close()
 
@@ -119,6 +148,7 @@ class SurvivalModel(_DeviceModel):
         self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
         self._dev = Survival(infected, exposure, titers, self.priors, device=device)
         self.n_cells = followed_cells(infected, exposure)
+        self.followed = followed_mask(infected, exposure)
         self.T = self._dev.n_intervals
         self.dim = self._dev.dim
         ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
@@ -133,6 +163,13 @@ def followed_cells(infected, exposure) -> np.ndarray:
     y, e = np.asarray(infected, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
     with np.errstate(invalid="ignore"):
         return ((e > 0) & ~np.isnan(y)).sum(axis=1).astype(np.int64)
+
+
+def followed_mask(infected, exposure) -> np.ndarray:
+    """(N, T) bool: the followed cells, exposure > 0 (NaN in either array: no follow-up)."""
+    y, e = np.asarray(infected, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return (e > 0) & ~np.isnan(y)
 
 
 def constrain(q, K: int) -> Dict[str, np.ndarray]:
@@ -201,6 +238,7 @@ class SurvivalGroupsModel(_DeviceModel):
         self.priors = PRIORS_GROUPS if priors is None else tuple(float(v) for v in priors)
         self._dev = SurvivalGroups(infected, exposure, titer, self.group_index, self.Gr, self.priors, device=device)
         self.n_cells = followed_cells(infected, exposure)
+        self.followed = followed_mask(infected, exposure)
         self.T = self._dev.n_intervals
         self.dim = self._dev.dim
         self.names = names_groups(self.T, self.Gr)
@@ -238,6 +276,7 @@ class SurvivalPeriodsModel(_DeviceModel):
         self.priors = PRIORS_PERIODS if priors is None else tuple(float(v) for v in priors)
         self._dev = SurvivalPeriods(infected, exposure, titer, self.period_index, self.P, self.priors, device=device)
         self.n_cells = followed_cells(infected, exposure)
+        self.followed = followed_mask(infected, exposure)
         self.T = self._dev.n_intervals
         self.dim = self._dev.dim
         self.names = names_groups(self.T, self.P)
@@ -462,6 +501,178 @@ def compare_lines(table) -> list:
             f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}" for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
 
 
+# ---- posterior predictive checks (abd_survival_predictive_*) ----
+
+PPC_MAX_EDGES = 7  # up to 8 bins per binning variable
+PPC_FLAG = 0.025   # a bin is flagged where min(p_low, p_high) is below this
+# what ``predictive`` records in a fit (the variables stacked in the order of ``ppc_variables``; bins past a variable's own hold
+# NaN in the float arrays and 0 in the integer ones)
+PPC_FIT_KEYS = ("ppc_variables", "ppc_edges", "ppc_n_bins", "ppc_observed", "ppc_person_time", "ppc_n_cells", "ppc_expected", "ppc_replicate",
+                "ppc_p_low", "ppc_p_high", "ppc_expected_ind", "ppc_p_infected_ind", "ppc_replicate_mean_ind", "ppc_observed_ind",
+                "ppc_n_draws", "ppc_seed")
+
+
+def default_edges(titer, followed) -> np.ndarray:
+    """The seven octiles of the followed cells' titers as bin edges, made strictly ascending: each is a titer of the data (the
+    lower of the two beside a quantile), repeated values are dropped and so is an edge at the smallest titer, so that with the rule
+    bin = #{edges <= x} every bin holds a followed cell.  Fewer than seven edges where the titers repeat."""
+    x, m = np.asarray(titer, dtype=np.float64), np.asarray(followed, dtype=bool)
+    if x.shape != m.shape:
+        raise ValueError(f"titer {x.shape} and followed {m.shape} must share a shape")
+    v = x[m]
+    if v.size == 0:
+        raise ValueError("no followed cell: no default edges")
+    if not np.isfinite(v).all():
+        raise ValueError("titer of a followed cell must be finite")
+    q = np.unique(np.quantile(v, np.arange(1, PPC_MAX_EDGES + 1) / (PPC_MAX_EDGES + 1), method="lower"))
+    return q[q > v.min()]
+
+
+def check_edges(edges) -> np.ndarray:
+    """``edges`` as a float64 vector of at most 7 finite, strictly ascending values (``ValueError`` otherwise)."""
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if e.size > PPC_MAX_EDGES:
+        raise ValueError(f"{e.size} edges: at most {PPC_MAX_EDGES} (8 bins)")
+    if not np.isfinite(e).all():
+        raise ValueError("edges must be finite")
+    if (np.diff(e) <= 0).any():
+        raise ValueError("edges must be strictly ascending")
+    return e
+
+
+def _bin_sums(values, bins, nb):
+    """(n, N, T) values summed over the cells of each bin: (n, nb); ``bins`` (N, T) holds -1 for cells that belong to no bin"""
+    return np.stack([values[:, bins == b].sum(axis=1) for b in range(nb)], axis=1)
+
+
+def predictive(model, fit, by, edges=None, seed: int = 0, replicate: Optional[Callable] = None, prob: float = 0.95) -> Dict[str, object]:
+    """Posterior predictive check of a fitted survival model over all draws of ``fit``, folded chain after chain: does the model
+    reproduce the infections the cohort saw at low, middle and high titers?  ``by`` maps one or two names to titer arrays (N, T),
+    the binning variables -- free of the model's own predictor: an S-only fit binned by the N titer is the residual check against
+    the omitted variable.  ``edges`` maps a name to up to 7 strictly ascending edges (bin = #{edges <= x}, ``risk.bin_of``'s rule);
+    a name without edges gets ``default_edges`` of the model's followed cells.  Draw d's replicates depend on (``seed``, d, the
+    individual, the interval) alone.
+
+    Returns ``variables[name]`` with ``edges``, ``observed``, ``person_time``, ``n_cells`` (nb,), ``expected`` and ``replicate``
+    (n_draws, nb), ``expected_median`` / ``_lower`` / ``_upper``, ``ratio`` = observed / expected per draw as ``ratio_median`` /
+    ``_lower`` / ``_upper``, ``p_low`` = mean(R <= O), ``p_high`` = mean(R >= O) and ``flagged``, the bins with
+    min(p_low, p_high) < 0.025; and per individual ``expected_i``, ``p_infected_i`` (the share of draws with a replicated
+    infection), ``replicate_mean_i`` and ``observed_i``.  The entries ``PPC_FIT_KEYS`` are recorded in ``fit``; ``write`` stores
+    them.
+    ``replicate``: a host callable ``(q, draw0) -> (mu, r)``, both (n, N, T), in the device's place (tests); the model then needs
+    ``names``, ``infected`` and ``exposure``."""
+    names = [str(k) for k in by]
+    if len(names) not in (1, 2):
+        raise ValueError(f"one or two binning variables, got {len(names)}")
+    titers = [np.asarray(by[k], dtype=np.float64) for k in by]
+    edges = dict(edges or {})
+    unknown = [k for k in edges if str(k) not in names]
+    if unknown:
+        raise ValueError(f"edges for {unknown}, which are not binning variables ({names})")
+    edge_list = []
+    for name, x in zip(names, titers):
+        if edges.get(name) is not None:
+            edge_list.append(check_edges(edges[name]))
+        else:
+            if not hasattr(model, "followed"):
+                raise ValueError(f"no edges for {name} and the model has no followed cells to take the default from")
+            edge_list.append(default_edges(x, model.followed))
+    q = fit_points(model, fit)
+    n, nv = q.shape[0], len(names)
+    if n < 1:
+        raise ValueError("the fit holds no draws")
+    if replicate is not None:
+        y, e = np.asarray(model.infected, dtype=np.float64), np.asarray(model.exposure, dtype=np.float64)
+        m = followed_mask(y, e)
+        mu, r = replicate(q, 0)
+        mu, r = np.asarray(mu, dtype=np.float64), np.asarray(r, dtype=np.int64)
+        if mu.shape != (n,) + y.shape or r.shape != mu.shape:
+            raise ValueError(f"replicate must return two arrays of shape {(n,) + y.shape}")
+        obs, pt, cells = np.zeros((nv, 8)), np.zeros((nv, 8)), np.zeros((nv, 8), np.int64)
+        E, R = np.zeros((n, nv, 8)), np.zeros((n, nv, 8), np.int64)
+        for v, (x, ed) in enumerate(zip(titers, edge_list)):
+            if not np.isfinite(x[m]).all():
+                raise ValueError(f"{names[v]}: titer of a followed cell must be finite")
+            bins = np.where(m, risk.bin_of(np.where(m, x, 0.0), ed), -1)
+            for b in range(ed.size + 1):
+                sel = bins == b
+                obs[v, b], pt[v, b], cells[v, b] = math.fsum(y[sel]), math.fsum(e[sel]), int(sel.sum())
+            E[:, v, :ed.size + 1], R[:, v, :ed.size + 1] = _bin_sums(mu, bins, ed.size + 1), _bin_sums(r, bins, ed.size + 1)
+        mu_f, r_f = np.where(m, mu, 0.0), np.where(m, r, 0)
+        sum_e, sum_r, n_pos = mu_f.sum(axis=2).sum(axis=0), r_f.sum(axis=2).sum(axis=0), (r_f.sum(axis=2) >= 1).sum(axis=0)
+        obs_i = np.array([math.fsum(row[mk]) for row, mk in zip(y, m)])
+    else:
+        model.predictive_configure(titers, edge_list, seed)
+        model.predictive_reset()
+        E, R = model.predictive_accumulate(q)
+        sum_e, sum_r, n_pos, n_folded = model.predictive_stats()
+        assert n_folded == n
+        obs, pt, cells, obs_i = model.predictive_observed()
+    out = {"n_draws": n, "seed": int(seed), "variables": {}, "expected_i": sum_e / n, "p_infected_i": n_pos / n, "replicate_mean_i": sum_r / n,
+           "observed_i": obs_i}
+    p_low, p_high = np.full((nv, 8), np.nan), np.full((nv, 8), np.nan)
+    for v, (name, ed) in enumerate(zip(names, edge_list)):
+        nb = ed.size + 1
+        Ev, Rv, Ov = E[:, v, :nb], R[:, v, :nb], obs[v, :nb]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(Ev > 0, Ov[None, :] / Ev, np.nan)
+        ie, ir = _interval_of_draws(Ev, prob), _interval_of_draws(ratio, prob)
+        p_low[v, :nb], p_high[v, :nb] = (Rv <= Ov[None, :]).mean(axis=0), (Rv >= Ov[None, :]).mean(axis=0)
+        tail = np.minimum(p_low[v, :nb], p_high[v, :nb])
+        out["variables"][name] = dict(
+            edges=ed, observed=Ov, person_time=pt[v, :nb], n_cells=cells[v, :nb], expected=Ev, replicate=Rv, expected_median=ie["median"],
+            expected_lower=ie["lower"], expected_upper=ie["upper"], ratio_median=ir["median"], ratio_lower=ir["lower"], ratio_upper=ir["upper"],
+            p_low=p_low[v, :nb], p_high=p_high[v, :nb], flagged=np.flatnonzero((tail < PPC_FLAG) & (cells[v, :nb] > 0)))
+    pad = np.full((nv, PPC_MAX_EDGES), np.nan)
+    for v, ed in enumerate(edge_list):
+        pad[v, :ed.size] = ed
+    past = np.arange(8)[None, :] >= np.array([ed.size + 1 for ed in edge_list])[:, None]
+    fit["ppc_variables"], fit["ppc_edges"], fit["ppc_n_bins"] = np.array(names), pad, np.array([ed.size + 1 for ed in edge_list], dtype=np.int64)
+    fit["ppc_observed"], fit["ppc_person_time"], fit["ppc_n_cells"] = np.where(past, np.nan, obs), np.where(past, np.nan, pt), np.asarray(cells, np.int64)
+    fit["ppc_expected"], fit["ppc_replicate"] = np.where(past[None], np.nan, E), np.asarray(R, dtype=np.int64)
+    fit["ppc_p_low"], fit["ppc_p_high"] = p_low, p_high
+    fit["ppc_expected_ind"], fit["ppc_p_infected_ind"] = out["expected_i"], out["p_infected_i"]
+    fit["ppc_replicate_mean_ind"], fit["ppc_observed_ind"] = out["replicate_mean_i"], np.asarray(obs_i, dtype=np.float64)
+    fit["ppc_n_draws"], fit["ppc_seed"] = np.array(n, dtype=np.int64), np.array(int(seed), dtype=np.int64)
+    return out
+
+
+def sample_posterior_predictive(model, fit, draws=None, seed: int = 0) -> np.ndarray:
+    """(n, N, T) int32: the per-cell replicated infections of the draws ``draws`` of ``fit`` (indices into its points chain after
+    chain; all of them by default), through ``abd_survival_replicate``: for the same ``seed`` exactly the replicates ``predictive``
+    sums for those draws.  A model that ``predictive`` has not configured is configured with one bin (and one that it has loses its
+    folded draws: the configuration carries the seed)."""
+    q = fit_points(model, fit)
+    idx = np.arange(q.shape[0]) if draws is None else np.asarray(draws, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= q.shape[0]):
+        raise ValueError(f"draws must be indices in [0, {q.shape[0]})")
+    N = model.followed.shape[0]
+    model.predictive_configure([np.zeros(model.followed.shape)], [np.empty(0)], seed)
+    out = np.empty((idx.size, N, model.T), dtype=np.int32)
+    start = 0
+    while start < idx.size:  # runs of consecutive draws share a call
+        stop = start + 1
+        while stop < idx.size and idx[stop] == idx[stop - 1] + 1:
+            stop += 1
+        out[start:stop] = model.replicate(q[idx[start]:idx[start] + stop - start], draw0=int(idx[start]))
+        start = stop
+    return out
+
+
+def predictive_line(p) -> str:
+    """One line per binning variable: observed over expected (the median over the draws) of every bin, and the worst bin with its
+    tail probability min(p_low, p_high), marked where it is flagged."""
+    lines = []
+    for name, v in p["variables"].items():
+        cells = " ".join(f"{o:.1f}/{m:.1f}" for o, m in zip(v["observed"], v["expected_median"]))
+        tail = np.where(v["n_cells"] > 0, np.minimum(v["p_low"], v["p_high"]), np.inf)
+        k = int(np.argmin(tail))
+        side = "p_low" if v["p_low"][k] <= v["p_high"][k] else "p_high"
+        lines.append(f"survival PPC by {name}: observed/expected per bin {cells}; worst bin {k} ({side} {tail[k]:.4f}"
+                     + (", FLAGGED" if k in v["flagged"] else "") + f"); {len(v['flagged'])} of {len(v['observed'])} bins flagged ({p['n_draws']} draws)")
+    return "\n".join(lines)
+
+
 def protection(res, x, antigen: Optional[str] = None, prob: float = 0.95, group=None, period=None, interval=None) -> Dict[str, np.ndarray]:
     """``1 - 1 / (1 + exp(-b (x - a)))`` at titers ``x`` per draw, over all draws of all chains: ``mean``, ``median``, ``lower``,
     ``upper`` (each of ``x``'s shape).  ``antigen``: which titer of a combined fit ('S' or 'N'; the other held at its midpoint).
@@ -624,6 +835,11 @@ def main(argv=None) -> int:
     ap.add_argument("--out", help="Output file (.npz; NetCDF where ArviZ imports and the name does not end in .npz).")
     ap.add_argument("--waic", action="store_true", help="Score the fit by WAIC over the individuals on the device: a second line on stdout, and "
                     "elpd_waic_ind, p_waic_ind, waic_n_cells, waic_n_draws, start, end in the output (what --compare reads).")
+    ap.add_argument("--ppc", action="store_true", help="Posterior predictive check on the device: per titer bin the observed infections against the "
+                    "expected and replicated ones of every draw; one more line on stdout per binning variable, and the ppc_* entries in the output.")
+    ap.add_argument("--ppc_edges_s", help="With --ppc: comma-separated bin edges of the S titer (up to 7, ascending; default: the octiles).")
+    ap.add_argument("--ppc_edges_n", help="With --ppc: comma-separated bin edges of the N titer (up to 7, ascending; default: the octiles).")
+    ap.add_argument("--ppc_seed", type=int, help="With --ppc: the seed of the replicates (default: --seed).")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
     ap.add_argument("--chains", type=int, default=4)
@@ -642,6 +858,15 @@ def main(argv=None) -> int:
         ap.error("--split_delta / --split_omicron go with --model s_periods | n_periods --periods splits")
     if not by_period and (args.periods != "monthly" or args.period_name is not None):
         ap.error("--periods / --period_name go with --model s_periods | n_periods")
+    if not args.ppc and (args.ppc_edges_s is not None or args.ppc_edges_n is not None or args.ppc_seed is not None):
+        ap.error("--ppc_edges_s / --ppc_edges_n / --ppc_seed go with --ppc")
+    ppc_edges = {}
+    for name, text in (("S", args.ppc_edges_s), ("N", args.ppc_edges_n)):
+        if text is not None:
+            try:
+                ppc_edges[name] = check_edges([float(v) for v in text.split(",")])
+            except ValueError as e:
+                ap.error(f"--ppc_edges_{name.lower()}: {e}")
     from .data import TiterData
 
     data = TiterData.from_disk(args.ititers_data)
@@ -665,10 +890,17 @@ def main(argv=None) -> int:
         raise SystemExit(f"survival: {e}")
     res = sample(model, tune=args.tune, draws=args.draws, chains=args.chains, seed=args.seed)
     w = waic(model, res) if args.waic else None
+    try:  # both titers, whatever the model's own predictor is
+        ppc = predictive(model, res, {"S": sa.s_titer, "N": sa.n_titer}, edges=ppc_edges,
+                         seed=args.seed if args.ppc_seed is None else args.ppc_seed) if args.ppc else None
+    except ValueError as e:
+        raise SystemExit(f"survival: {e}")
     model.close()
     print(report_line(res))  # the one line, on stdout; progress and the file's name go to stderr
     if w is not None:
         print(waic_line(w))  # --waic: and this one
+    if ppc is not None:
+        print(predictive_line(ppc))  # --ppc: and one per binning variable
     out = write(res, args.out, sa)
     print(f"wrote {out}", file=sys.stderr)
     return 0
@@ -699,7 +931,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
     ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` and the window ``start`` / ``end`` -- in the ``.npz`` form,
     which is what ``--compare`` reads; the NetCDF form holds the draws alone.  Likewise ``groups`` / ``group_name`` and ``periods`` /
     ``period_name`` / ``period_index`` are stored in the ``.npz`` form only: ``protection(group= / period= / interval=)`` needs a fit
-    written as ``.npz``."""
+    written as ``.npz``.  So are the entries ``PPC_FIT_KEYS`` of a fit that ``predictive`` has checked."""
     path = str(path)
     if "elpd_waic_ind" in res:
         res = dict(res, start=np.array(sa.start, dtype=np.int64), end=np.array(sa.end, dtype=np.int64))
@@ -709,7 +941,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + PPC_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

@@ -764,6 +764,36 @@ int abd_survival_waic_reset(abd_survival* s);
 int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta);
 int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells);
 
+/* Posterior predictive checks of a handle of any kind.  For draw d and cell (j, t):
+ *   mu = exposure[j, t] * lam0[t] * invlogit(eta[j, t]),   r ~ Poisson(mu)
+ * where r is a function of (seed, d, the caller's index j, t) alone: Philox4x32-10 with key (seed lo, seed hi) and counter
+ * (j, t, low word of d, 0x40000020), inverted sequentially.  Both are summed over the cells of titer bins and over individuals.
+ *
+ * _configure: n_var in {1, 2} binning variables, chosen freely (they need not be the model's own titer).  titers[v] is (N, T) in
+ * the caller's order, edges[v] holds n_edges[v] <= 7 finite, strictly ascending edges; the bin of a cell is the number of edges
+ * <= its titer, at most 8 bins.  Cells without follow-up belong to no bin.  Computes the constants of the data, uploads the bin
+ * planes and sets the draw counter to 0.  ABD_ERR_ARG: n_var outside {1, 2}, more than 7 edges, edges not finite or not strictly
+ * ascending, a non-finite titer in a followed cell, an exposure above 4; the handle keeps its earlier configuration then.  A
+ * second call reconfigures. */
+int abd_survival_predictive_configure(abd_survival* s, int32_t n_var, const double* const* titers, const int32_t* n_edges,
+                                      const double* const* edges, uint64_t seed);
+/* The draw counter back to 0: the next draw folded is draw 0 and the per-individual accumulators start again. */
+int abd_survival_predictive_reset(abd_survival* s);
+/* Folds the n draws theta[n][D] (any n; up to ABD_MAX_BATCH share a launch) as draws n0 .. n0 + n - 1, n0 the number folded since
+ * the last reset or configuration.  expected[n][n_var][8] = sum of mu and replicate[n][n_var][8] = sum of r over the cells of
+ * each bin (0 for a bin without followed cells).  Every output and every accumulator is the same bits however the draws are
+ * split over calls.  ABD_ERR_ARG before _configure. */
+int abd_survival_predictive_accumulate(abd_survival* s, int32_t n, const double* theta, double* expected, int64_t* replicate);
+/* Per individual, in the caller's order, over the draws folded: sum_e[N] = sum_d sum_t mu, sum_r[N] = sum_d sum_t r, n_pos[N] =
+ * the draws with sum_t r >= 1; n_draws.  ABD_ERR_ARG before _configure and before any draw. */
+int abd_survival_predictive_stats(abd_survival* s, double* sum_e, int64_t* sum_r, int64_t* n_pos, int64_t* n_draws);
+/* The constants of the configuration: observed[n_var][8] = sum of infected, person_time[n_var][8] = sum of exposure and
+ * n_cells[n_var][8] = the followed cells of each bin (compensated sums on the host), observed_ind[N] = sum_t infected[j, t]. */
+int abd_survival_predictive_observed(abd_survival* s, double* observed, double* person_time, int64_t* n_cells, double* observed_ind);
+/* The per-cell replicates rep[n][N][T] (caller's order) of theta[n][D] as draws draw0 .. draw0 + n - 1: exactly the replicates
+ * _accumulate draws for those indices.  Folds nothing and leaves the draw counter alone.  ABD_ERR_ARG before _configure. */
+int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int64_t draw0, int32_t* rep);
+
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).
  * This table is complete: the product library calls getenv for nothing else (development knobs of launch shapes

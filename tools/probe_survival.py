@@ -9,6 +9,10 @@ the same run: microseconds per call for 1 and 4 points, the tile counts, and the
 (launches of 16, a host clock around calls that end in a synchronise) beside ``logp_dlogp`` at one point per call on the same
 handle, alternating, ``--reps`` times; per repeat and at its best, microseconds per draw, per single-point evaluation, the ratio.
 
+``--leg ppc`` times the posterior predictive check in the same way: ``predictive_accumulate`` of ``--points`` jittered points of
+the combined model, binned by both titers in octiles, beside ``waic_accumulate`` of the same points on the same handle,
+alternating, ``--reps`` times; per repeat and at its best, microseconds per draw of each and the ratio.
+
 ``--periods P [P]`` times the model by period in the same way, with P periods of equal length (0: monthly, P = T),
 every P at both sizes, beside the ungrouped K = 1 model on the same data in the same run; ``--fit`` adds the wall time of a
 ``--tune`` + ``--draws`` x 4-chain fit of each of them and of the K = 1 model.
@@ -17,6 +21,7 @@ every P at both sizes, beside the ungrouped K = 1 model on the same data in the 
     python tools/probe_survival.py --groups 4 8 [--out FILE]
     python tools/probe_survival.py --periods 3 0 [--fit] [--out FILE]
     python tools/probe_survival.py --leg waic [--points 4000] [--reps 3] [--out FILE]
+    python tools/probe_survival.py --leg ppc [--points 4000] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -162,11 +167,46 @@ def probe_waic(N, T, points, reps):
     return row
 
 
+def probe_ppc(N, T, points, reps):
+    """One row: ``predictive_accumulate`` of ``points`` draws, binned by both titers, against ``waic_accumulate`` of the same draws, on
+    one handle of the combined model of ``simulate(N, T)``."""
+    y, e, xs = simulate(N, T)
+    model = survival.SurvivalModel(y, e, xs, ("S", "N"))
+    rng = np.random.default_rng(1)
+    q = np.zeros((points, model.dim))
+    q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+    q += rng.uniform(-0.5, 0.5, size=q.shape)
+    edges = [survival.default_edges(x, model.followed) for x in xs]
+    model.predictive_configure(xs, edges, 0)
+    row = {"N": N, "T": T, "K": 2, "points": points, "launches": (points + 15) // 16, "waves_per_launch": ((N + 63) // 64) * min(16, points),
+           "n_bins": [len(ed) + 1 for ed in edges], "ppc_us_per_draw": [], "waic_us_per_draw": []}
+    model.predictive_accumulate(q[:64])  # warm up: the buffers of the first call, the code objects
+    model.waic_accumulate(q[:64])
+    for _ in range(reps):
+        model.predictive_reset()
+        t0 = time.perf_counter()
+        E, Rr = model.predictive_accumulate(q)
+        row["ppc_us_per_draw"].append(1e6 * (time.perf_counter() - t0) / points)
+        model.waic_reset()
+        t0 = time.perf_counter()
+        model.waic_accumulate(q)
+        row["waic_us_per_draw"].append(1e6 * (time.perf_counter() - t0) / points)
+    row["n_draws"] = model.predictive_stats()[3]
+    row["expected_total_mean"], row["replicate_total_mean"] = float(E[:, 0].sum(axis=1).mean()), float(Rr[:, 0].sum(axis=1).mean())
+    row["observed_total"] = float(model.predictive_observed()[0][0].sum())
+    row["best_ppc_us_per_draw"], row["best_waic_us_per_draw"] = min(row["ppc_us_per_draw"]), min(row["waic_us_per_draw"])
+    row["ppc_fold_ms"], row["waic_fold_ms"] = 1e-3 * points * row["best_ppc_us_per_draw"], 1e-3 * points * row["best_waic_us_per_draw"]
+    row["ppc_over_waic"] = row["best_ppc_us_per_draw"] / row["best_waic_us_per_draw"]
+    model.close()
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("eval", "waic"), default="eval", help="eval: the evaluator and a fit (the default); waic: scoring a fit")
-    ap.add_argument("--points", type=int, default=4000, help="--leg waic: draws folded per repeat")
-    ap.add_argument("--reps", type=int, default=3, help="--leg waic: repeats")
+    ap.add_argument("--leg", choices=("eval", "waic", "ppc"), default="eval",
+                    help="eval: the evaluator and a fit (the default); waic: scoring a fit; ppc: the posterior predictive check beside the WAIC fold")
+    ap.add_argument("--points", type=int, default=4000, help="--leg waic / ppc: draws folded per repeat")
+    ap.add_argument("--reps", type=int, default=3, help="--leg waic / ppc: repeats")
     ap.add_argument("--groups", type=int, nargs="+", help="time the model by group with this many groups (one figure, or one per size)")
     ap.add_argument("--periods", type=int, nargs="+", help="time the model by period with this many periods (0: monthly), each at every size")
     ap.add_argument("--fit", action="store_true", help="--periods: also time a fit of the model by period and of the K = 1 model")
@@ -179,6 +219,10 @@ def main(argv=None):
     if args.leg == "waic":
         for N, T in SIZES:
             rows.append(probe_waic(N, T, args.points, args.reps))
+            print(json.dumps(rows[-1]), flush=True)
+    if args.leg == "ppc":
+        for N, T in SIZES:
+            rows.append(probe_ppc(N, T, args.points, args.reps))
             print(json.dumps(rows[-1]), flush=True)
     if args.groups:
         if len(args.groups) not in (1, len(SIZES)):
