@@ -140,6 +140,13 @@ class _SurvivalPeriodsDesc(C.Structure):  # abd_survival_periods_desc
                 ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
 
 
+class _SurvivalDrawsDesc(C.Structure):  # abd_survival_draws_desc
+    _fields_ = [("n_datasets", C.c_int32), ("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_titers", C.c_int32), ("device", C.c_int32),
+                ("n_risk", C.c_void_p), ("event", C.c_void_p), ("titer", C.c_void_p * 2),
+                ("ab_sd", C.c_double), ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double),
+                ("lam0_z_sd", C.c_double)]
+
+
 SURVIVAL_MAX_GROUPS = 256  # ABD_SURVIVAL_MAX_GROUPS
 
 # abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
@@ -236,6 +243,11 @@ SYMBOLS = {
     "abd_survival_predictive_stats": (C.c_int, [_P, _D, _P, _P, C.POINTER(C.c_int64)]),
     "abd_survival_predictive_observed": (C.c_int, [_P, _D, _D, _P, _D]),
     "abd_survival_replicate": (C.c_int, [_P, C.c_int32, _D, C.c_int64, _I32]),
+    "abd_survival_draws_create": (C.c_int, [C.POINTER(_SurvivalDrawsDesc), C.POINTER(_P)]),
+    "abd_survival_draws_destroy": (C.c_int, [_P]),
+    "abd_survival_draws_dim": (C.c_int32, [_P]),
+    "abd_survival_draws_logp_dlogp": (C.c_int, [_P, C.c_int32, _I32, _D, _D, _D]),
+    "abd_survival_draws_loglik_sums": (C.c_int, [_P, C.c_int32, _D, _D]),
 }
 
 SURVIVAL_PREDICTIVE_BINS = 8  # ABD_SURV_PRED_BINS: bins of a binning variable (up to 7 edges)
@@ -1270,3 +1282,64 @@ class SurvivalPeriods(Survival):
         self.n_inds, self.n_intervals, self.n_titers, self.n_periods = y.shape[0], y.shape[1], 1, int(n_periods)
         self.dim = int(lib.abd_survival_dim(self._h))
         self.n_sums = 2 * y.shape[1] + 2
+
+
+class SurvivalDraws:
+    """An ensemble of per-draw datasets resident on the device (abd_hip.h: ``abd_survival_draws``): ``n_risk``, ``event`` (M, N) int32
+    and one or two titer arrays (M, T, N); ``priors`` as ``Survival``'s.  Every point names its dataset.  The library checks the
+    datasets.  A handle of its own kind: it has no per-individual, WAIC or predictive calls."""
+
+    def __init__(self, n_risk, event, titers, priors, device: int = -1):
+        lib = load()
+        self._lib = lib
+        self._h = _P()
+        nr, ev = _as(n_risk, np.int32), _as(event, np.int32)
+        xs = [_as(x, np.float64) for x in titers]
+        if nr.ndim != 2 or ev.shape != nr.shape:
+            raise ValueError("n_risk and event must share a shape (M, N)")
+        if len(xs) not in (1, 2):
+            raise ValueError(f"one or two titer arrays, got {len(xs)}")
+        if any(x.ndim != 3 or (x.shape[0], x.shape[2]) != nr.shape or x.shape != xs[0].shape for x in xs):
+            raise ValueError(f"the titers must share a shape (M, T, N) with (M, N) = {nr.shape}")
+        d = _SurvivalDrawsDesc()
+        d.n_datasets, d.n_inds, d.n_intervals, d.n_titers, d.device = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs), device
+        d.n_risk, d.event = nr.ctypes.data, ev.ctypes.data
+        for k, x in enumerate(xs):
+            d.titer[k] = x.ctypes.data
+        d.ab_sd, d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd = (float(v) for v in priors)
+        _check(lib, lib.abd_survival_draws_create(C.byref(d), C.byref(self._h)))
+        self.n_datasets, self.n_inds, self.n_intervals, self.n_titers = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs)
+        self.dim = int(lib.abd_survival_draws_dim(self._h))
+        self.n_sums = self.n_intervals + 2 + len(xs)
+
+    def logp_dlogp(self, dataset, theta):
+        """``dataset`` an index and ``theta`` (D,) -> (logp, grad (D,)); ``dataset`` (n,) and ``theta`` (n, D) -> (logp (n,), grad (n, D))."""
+        t = _as(theta, np.float64)
+        one = t.ndim == 1
+        t2 = t.reshape(1, -1) if one else t
+        ds = _as(dataset, np.int32).reshape(-1)
+        if t2.ndim != 2 or t2.shape[1] != self.dim or ds.shape != (t2.shape[0],):
+            raise ValueError(f"theta must have shape ({self.dim},) or (n, {self.dim}) with one dataset index per point, got {t.shape} and {ds.shape}")
+        lp, g = np.empty(t2.shape[0]), np.empty(t2.shape)
+        _check(self._lib, self._lib.abd_survival_draws_logp_dlogp(self._h, t2.shape[0], _ptr(ds), _ptr(t2), _ptr(lp), _ptr(g)))
+        return (float(lp[0]), g[0]) if one else (lp, g)
+
+    def loglik_sums(self, dataset: int, theta):
+        """The raw device sums of one point on one dataset: S_t (T), L, W_0, W_k (K)."""
+        t = _as(theta, np.float64)
+        if t.shape != (self.dim,):
+            raise ValueError(f"theta must have shape ({self.dim},)")
+        out = np.empty(self.n_sums)
+        _check(self._lib, self._lib.abd_survival_draws_loglik_sums(self._h, int(dataset), _ptr(t), _ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.abd_survival_draws_destroy(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

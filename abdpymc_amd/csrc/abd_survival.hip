@@ -1,6 +1,7 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
 // handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, the
-// posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate).  A
+// posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
+// per-draw datasets, a handle of its own kind (abd_survival_draws_*; abd_survival_draws.hpp).  A
 // handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp,
 // abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the packing of the planes and the form of a model
 // (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
@@ -8,6 +9,7 @@
 
 #include "abd_host.hpp"
 #include "abd_survival.hpp"
+#include "abd_survival_draws.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
 #include "abd_survival_periods.hpp"
@@ -613,6 +615,194 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
       }
     }
   }
+  return ABD_OK;
+}
+
+}  // extern "C"
+
+// ---- the ensemble of per-draw datasets (abd_survival_draws.hpp) ----
+
+struct abd_survival_draws {
+  int M = 0, N = 0, T = 0, K = 0, device = 0;
+  SurvivalPriors priors{};
+  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
+  std::vector<double> Y;  // [M][T]: the events of dataset m in interval t, an integer
+  DevBuf<double> d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
+  DevBuf<int32_t> d_n_risk, d_event;
+  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
+  std::vector<double> work;        // [ABD_MAX_BATCH][2 T]: log lambda, 1 - lambda of the points in flight
+  Stream stream;
+
+  int par_stride() const { return T + 2 * K + 1; }  // lambda[T], a[K], b[K], the dataset index
+  int out_stride() const { return T + ABD_SURV_NW; }
+};
+
+namespace abdi {
+namespace {
+
+// the sums of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->h_out (rows of out_stride)
+int survival_draws_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta) {
+  const int T = s->T, K = s->K, stride = s->par_stride();
+  const size_t D = (size_t)survival_dim(K, T);
+  for (int q = 0; q < n; ++q) {
+    double* par = s->h_par.host() + (size_t)q * stride;
+    survival_prepare(K, T, theta + q * D, par, s->work.data() + (size_t)q * 2 * T);
+    par[T + 2 * K] = 0.0;
+    std::memcpy(par + T + 2 * K, dataset + q, sizeof(int32_t));
+  }
+  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  SurvivalDrawsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.n_risk = s->d_n_risk;
+  a.event = s->d_event;
+  a.par = s->d_par;
+  a.s_part = s->d_s_part;
+  a.w_part = s->d_w_part;
+  a.T = T;
+  a.ld = s->ld;
+  a.ntile = s->ntile;
+  a.nseg = s->nseg;
+  a.seg_len = s->seg_len;
+  a.par_stride = stride;
+  SurvivalArgs f;  // the finalize of abd_survival, as it is: it reads the partials, T, ntile and nseg
+  std::memset(&f, 0, sizeof f);
+  f.s_part = s->d_s_part;
+  f.w_part = s->d_w_part;
+  f.out = s->d_out;
+  f.T = T;
+  f.ld = s->ld;
+  f.ntile = s->ntile;
+  f.nseg = s->nseg;
+  f.seg_len = s->seg_len;
+  f.par_stride = stride;
+  HIP_TRY(launch_kernel(K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, dim3((unsigned)((s->nw + 3) / 4), (unsigned)n),
+                        dim3(256), 0, s->stream, a));
+  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, f));
+  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return ABD_OK;
+}
+
+int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int32_t* dataset) {
+  for (int q = 0; q < n; ++q)
+    if (dataset[q] < 0 || dataset[q] >= s->M) return fail(ABD_ERR_ARG, "point %d: dataset %d outside [0, %d)", q, dataset[q], s->M);
+  return ABD_OK;
+}
+
+int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws** out) {
+  const int M = d->n_datasets, N = d->n_inds, T = d->n_intervals, K = d->n_titers;
+  if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
+  if (M < 1) return fail(ABD_ERR_ARG, "n_datasets=%d must be >= 1", M);
+  if (int rc = survival_check_shape(N, T)) return rc;
+  if (!d->n_risk || !d->event || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+  if (int rc = survival_check_priors("ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd", {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd},
+                                     d->lam0_mu_mean))
+    return rc;
+  std::unique_ptr<abd_survival_draws> s(new (std::nothrow) abd_survival_draws);
+  if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
+  s->M = M, s->N = N, s->T = T, s->K = K, s->device = d->device;
+  s->priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
+  s->ntile = (N + 63) / 64;
+  s->ld = s->ntile * 64;
+  // the split of abd_survival (survival_create_common): from the tile count and T alone
+  const int want_seg = std::max(1, std::min(T, (4096 + s->ntile - 1) / s->ntile));
+  s->seg_len = (T + want_seg - 1) / want_seg;
+  s->nseg = (T + s->seg_len - 1) / s->seg_len;
+  s->nw = s->ntile * s->nseg;
+  // every dataset, individual after individual: the first offender is named; the padded copies as the kernel reads them
+  const size_t ld = (size_t)s->ld, plane = ld * T;
+  std::vector<int32_t> n_risk((size_t)M * ld, 0), event((size_t)M * ld, -1);
+  std::vector<double> x0((size_t)M * plane, 0.0), x1(K == 2 ? (size_t)M * plane : 0, 0.0);
+  s->Y.assign((size_t)M * T, 0.0);
+  for (int m = 0; m < M; ++m)
+    for (int j = 0; j < N; ++j) {
+      const int nr = d->n_risk[(size_t)m * N + j], ev = d->event[(size_t)m * N + j];
+      if (nr < 0 || nr > T) return fail(ABD_ERR_ARG, "dataset %d, individual %d: n_risk=%d outside [0, %d]", m, j, nr, T);
+      if (ev != -1 && ev != nr - 1)
+        return fail(ABD_ERR_ARG, "dataset %d, individual %d, interval %d: event must be -1 or n_risk - 1 = %d", m, j, ev, nr - 1);
+      n_risk[(size_t)m * ld + j] = nr;
+      event[(size_t)m * ld + j] = ev;
+      if (ev >= 0) s->Y[(size_t)m * T + ev] += 1.0;
+      for (int k = 0; k < K; ++k) {
+        const double* src = d->titer[k] + (size_t)m * T * N + j;
+        double* dst = (k ? x1 : x0).data() + (size_t)m * plane + j;
+        for (int t = 0; t < T; ++t) dst[(size_t)t * ld] = src[(size_t)t * N];  // cells not at risk as they are: the kernel drops them
+        for (int t = 0; t < nr; ++t)
+          if (!std::isfinite(src[(size_t)t * N]))
+            return fail(ABD_ERR_ARG, "dataset %d, individual %d, interval %d: titer %d of a cell at risk must be finite", m, j, t, k);
+      }
+    }
+  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
+  if (s->device < 0) HIP_TRY(hipGetDevice(&s->device));
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(s->stream.create());
+  HIP_TRY(s->d_x0.upload(x0.data(), x0.size()));
+  if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), x1.size()));
+  HIP_TRY(s->d_n_risk.upload(n_risk.data(), n_risk.size()));
+  HIP_TRY(s->d_event.upload(event.data(), event.size()));
+  const size_t par_stride = (size_t)s->par_stride(), out_stride = (size_t)s->out_stride();
+  HIP_TRY(s->d_par.alloc(ABD_MAX_BATCH * par_stride));
+  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
+  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
+  HIP_TRY(s->d_out.alloc(ABD_MAX_BATCH * out_stride));
+  HIP_TRY(s->h_par.alloc_pinned(ABD_MAX_BATCH * par_stride));
+  HIP_TRY(s->h_out.alloc_pinned(ABD_MAX_BATCH * out_stride));
+  *out = s.release();
+  return ABD_OK;
+}
+
+}  // namespace
+}  // namespace abdi
+
+extern "C" {
+
+int abd_survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws** out) {
+  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
+  *out = nullptr;
+  try {
+    return survival_draws_create(d, out);
+  } catch (const std::bad_alloc&) {
+    return fail(ABD_ERR_NOMEM, "out of host memory for %d datasets of %d x %d cells", d->n_datasets, d->n_inds, d->n_intervals);
+  }
+}
+
+int abd_survival_draws_destroy(abd_survival_draws* s) {
+  if (!s) return ABD_OK;
+  (void)hipSetDevice(s->device);
+  if (s->stream) (void)hipStreamSynchronize(s->stream);
+  delete s;
+  return ABD_OK;
+}
+
+int32_t abd_survival_draws_dim(abd_survival_draws* s) { return s ? survival_dim(s->K, s->T) : -1; }
+
+int abd_survival_draws_logp_dlogp(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* logp, double* grad) {
+  if (!s || !dataset || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  if (int rc = survival_draws_check_datasets(s, n, dataset)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const int T = s->T, K = s->K;
+  const size_t D = (size_t)survival_dim(K, T);
+  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
+    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+    if (int rc = survival_draws_launch(s, nb, dataset + k0, theta + k0 * D)) return rc;
+    for (int q = 0; q < nb; ++q) {
+      const size_t k = (size_t)k0 + q;
+      logp[k] = survival_combine(s->priors, K, T, theta + k * D, s->Y.data() + (size_t)dataset[k] * T, 0.0, s->h_out.host() + (size_t)q * s->out_stride(),
+                                 s->h_par.host() + (size_t)q * s->par_stride(), s->work.data() + (size_t)q * 2 * T, grad + k * D);
+    }
+  }
+  return ABD_OK;
+}
+
+int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const double* theta, double* sums) {
+  if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_draws_check_datasets(s, 1, &dataset)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = survival_draws_launch(s, 1, &dataset, theta)) return rc;
+  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
   return ABD_OK;
 }
 

@@ -142,6 +142,102 @@ class Nuts:
                                           diverging=not s and j < self.max_treedepth and acc == 0.0)
 
 
+class NutsGen(Nuts):
+    """``Nuts`` with the evaluator turned inside out: ``find_reasonable_eps`` and ``step`` are generators that YIELD the point they
+    need evaluated and are sent ``(logp, grad)`` for it; what ``Nuts`` returns comes back as the generator's return value.  Statement
+    for statement the code of ``Nuts`` (the same operations and the same use of ``rng`` in the same order), so that a chain driven
+    through it is bit for bit the chain of ``Nuts`` on the same evaluator -- and many chains can wait on one batched evaluation
+    (``survival.sample_draws``).  ``fn`` is not used."""
+
+    def __init__(self, dim: int, rng: np.random.Generator, max_treedepth: int = 10, target_accept: float = 0.8):
+        super().__init__(None, dim, rng, max_treedepth=max_treedepth, target_accept=target_accept)
+
+    def _grad(self, q):
+        self.n_grad += 1
+        lp, g = yield q
+        if not np.isfinite(lp):
+            return -np.inf, np.zeros_like(q)
+        return float(lp), np.asarray(g, dtype=float)
+
+    def _leapfrog(self, q, p, g, eps):
+        p = p + 0.5 * eps * g
+        q = q + eps * self.inv_mass * p
+        lp, g = yield from self._grad(q)
+        p = p + 0.5 * eps * g
+        return q, p, lp, g
+
+    def find_reasonable_eps(self, q, lp, g):
+        eps = 0.1
+        p = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
+        h0 = self._energy(lp, p)
+        _, p1, lp1, _ = yield from self._leapfrog(q, p, g, eps)
+        dh = self._energy(lp1, p1) - h0
+        a = 1.0 if (np.isfinite(dh) and dh > math.log(0.5)) else -1.0
+        for _ in range(50):
+            if not np.isfinite(dh):
+                dh = -np.inf
+            if a * dh <= -a * math.log(2.0):
+                break
+            eps *= 2.0**a
+            _, p1, lp1, _ = yield from self._leapfrog(q, p, g, eps)
+            dh = self._energy(lp1, p1) - h0
+        return eps
+
+    def _build(self, q, p, g, log_u, v, j, eps, h0):
+        if j == 0:
+            q1, p1, lp1, g1 = yield from self._leapfrog(q, p, g, v * eps)
+            h1 = self._energy(lp1, p1)
+            if not np.isfinite(h1):
+                h1 = -np.inf
+            n1 = int(log_u <= h1)
+            s1 = log_u < h1 + 1000.0
+            alpha = min(1.0, math.exp(min(0.0, h1 - h0))) if np.isfinite(h1) else 0.0
+            return q1, p1, g1, q1, p1, g1, q1, lp1, g1, n1, s1, alpha, 1
+        qm, pm, gm, qp, pp, gp, q1, lp1, g1, n1, s1, a1, na1 = yield from self._build(q, p, g, log_u, v, j - 1, eps, h0)
+        if s1:
+            if v == -1:
+                qm, pm, gm, _, _, _, q2, lp2, g2, n2, s2, a2, na2 = yield from self._build(qm, pm, gm, log_u, v, j - 1, eps, h0)
+            else:
+                _, _, _, qp, pp, gp, q2, lp2, g2, n2, s2, a2, na2 = yield from self._build(qp, pp, gp, log_u, v, j - 1, eps, h0)
+            if n2 > 0 and self.rng.random() < n2 / max(n1 + n2, 1):
+                q1, lp1, g1 = q2, lp2, g2
+            a1, na1 = a1 + a2, na1 + na2
+            dq = qp - qm
+            s1 = s2 and float(np.dot(dq, self.inv_mass * pm)) >= 0 and float(np.dot(dq, self.inv_mass * pp)) >= 0
+            n1 += n2
+        return qm, pm, gm, qp, pp, gp, q1, lp1, g1, n1, s1, a1, na1
+
+    def step(self, q, lp, g, adapt: bool):
+        """One transition, as a generator.  Returns (q, logp, grad, stats)."""
+        eps = self.eps
+        p0 = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
+        h0 = self._energy(lp, p0)
+        log_u = h0 + math.log(self.rng.random() + 1e-300)
+        qm = qp = q
+        pm = pp = p0
+        gm = gp = g
+        j, n, s = 0, 1, True
+        q_new, lp_new, g_new = q, lp, g
+        alpha, n_alpha = 0.0, 1
+        while s and j < self.max_treedepth:
+            v = -1 if self.rng.random() < 0.5 else 1
+            if v == -1:
+                qm, pm, gm, _, _, _, q1, lp1, g1, n1, s1, alpha, n_alpha = yield from self._build(qm, pm, gm, log_u, v, j, eps, h0)
+            else:
+                _, _, _, qp, pp, gp, q1, lp1, g1, n1, s1, alpha, n_alpha = yield from self._build(qp, pp, gp, log_u, v, j, eps, h0)
+            if s1 and self.rng.random() < min(1.0, n1 / n):
+                q_new, lp_new, g_new = q1, lp1, g1
+            n += n1
+            dq = qp - qm
+            s = s1 and float(np.dot(dq, self.inv_mass * pm)) >= 0 and float(np.dot(dq, self.inv_mass * pp)) >= 0
+            j += 1
+        acc = alpha / max(n_alpha, 1)
+        if adapt and self.da is not None:
+            self.eps = self.da.update(acc)
+        return q_new, lp_new, g_new, dict(tree_depth=j, mean_tree_accept=acc, step_size=eps, n_steps=n_alpha,
+                                          diverging=not s and j < self.max_treedepth and acc == 0.0)
+
+
 # ---------------------------------------------------------------------------------------------------
 # Binary Gibbs-Metropolis (PyMC's BinaryGibbsMetropolis.astep semantics: transit_p = 0.8, shuffled order)
 # ---------------------------------------------------------------------------------------------------

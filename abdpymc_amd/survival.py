@@ -10,8 +10,14 @@ infection hazard of month g?
 models; ``protection`` is what ``plotting.plot_protection`` draws.  ``model_alone_groups`` gives every group of individuals its
 own midpoint ``a`` under a hierarchical prior, with one slope ``b`` (``abd_survival_create_groups``; DESIGN 20);
 ``model_alone_periods`` does the same along the time axis, one midpoint per month or per era of intervals
-(``abd_survival_create_periods``): the fit ``plotting.plot_protection(interval=)`` reads.  Per-draw (non-plug-in) fits
-are not here.
+(``abd_survival_create_periods``): the fit ``plotting.plot_protection(interval=)`` reads.
+
+Those are plug-in fits: the data are posterior means.  Per-draw fits carry the run's uncertainty about who was infected when, and
+at which titer, into a, b and the protection (multiple imputation): ``SurvivalAnalysis.draws`` makes a dataset of every
+chosen recorded draw (``event_time`` of ``risk.survival_arrays``), ``model_alone_draws`` / ``model_combined_draws`` keep all of them
+on the device, where every point of a launch reads its own dataset (``abd_survival_draws``), ``sample_draws`` runs one ``_chain``
+per dataset with up to 16 of them sharing every launch, and ``draws_summary`` pools them and says how much of the variance lies
+between the datasets.  Per-draw fits of the grouped and period models, and WAIC / PPC of a per-draw fit, are not built.
 
 Which titer predicts protection?  ``waic(model, fit)`` scores a fitted model by WAIC over the individuals -- the device gives every
 individual's log-likelihood at every draw and keeps the running statistics (``abd_survival_individual_loglik``,
@@ -23,6 +29,7 @@ with paired standard errors (``compare.compare``).
     python -m abdpymc_amd.survival ... --model s_periods|n_periods [--periods monthly|splits|FILE] [--split_delta] [--split_omicron]
     python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz
     python -m abdpymc_amd.survival ... --ppc [--ppc_edges_s E1,E2,...] [--ppc_edges_n E1,...] [--ppc_seed SEED]
+    python -m abdpymc_amd.survival ... --model s|n|combined --per_draw M [--per_draw_chains C]
 
 Does the best of them fit?  ``predictive(model, fit, by)`` is the posterior predictive check: per draw the device forms every cell's
 expected count, draws a Poisson replicate of it and sums both over titer bins of one or two freely chosen binning variables and
@@ -83,6 +90,122 @@ def _means(src) -> Dict[str, np.ndarray]:
             raise ValueError(f"{name}: expected (G, N) means, (chains, G, N) means or (chains, draws, G, N) draws, got {v.shape}")
         out[name] = v
     return out
+
+
+def posterior_draws(src) -> Dict[str, np.ndarray]:
+    """``i``, ``ab_s_mu``, ``ab_n_mu`` as (chains, draws, G, N) arrays: the recorded draws of a result of ``sampler.sample`` or of a
+    posterior ``.npz`` of this package.  ``ValueError`` where only the means are there."""
+    if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
+        with np.load(src) as f:
+            src = {k: f[k] for k in f.files if k in ("i", "ab_s_mu", "ab_n_mu")}
+    out = {}
+    for name in ("i", "ab_s_mu", "ab_n_mu"):
+        v = np.asarray(src[name]) if name in src else None
+        if v is None or v.ndim != 4:
+            raise ValueError(f"no draws of {name} in the posterior (only means, or a dict of means): per-draw fits need the recorded "
+                             "(chains, draws, G, N) arrays -- record them with abdpymc-infer --thin K (and without --no_deterministics)")
+        out[name] = v
+    if not (out["i"].shape == out["ab_s_mu"].shape == out["ab_n_mu"].shape):
+        raise ValueError("i, ab_s_mu, ab_n_mu must share a shape (chains, draws, G, N)")
+    return out
+
+
+def event_time(infected, exposure):
+    """(n_risk, event), each (N,) int32, of arrays (N, T) in event-time form -- what ``risk.survival_arrays`` makes of a draw's
+    binary infections: per individual ``exposure`` is 1 on a prefix of ``n_risk`` intervals and 0 or NaN behind it, and ``infected``
+    is 1 in at most one cell, which is then cell ``event = n_risk - 1``, and 0 or NaN everywhere else (``event = -1`` without an
+    infection).  ``ValueError`` for arrays of any other form (a fractional ``infected``: the plug-in arrays of posterior means)."""
+    y, e = np.asarray(infected, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
+    if y.ndim != 2 or e.shape != y.shape:
+        raise ValueError("infected and exposure must share a shape (N, T)")
+    N, T = y.shape
+    at = e == 1.0
+    n_risk = at.sum(axis=1).astype(np.int32)
+    t = np.arange(T)[None, :]
+    prefix = t < n_risk[:, None]
+    with np.errstate(invalid="ignore"):
+        rest_e = np.isnan(e) | (e == 0.0)
+        zero_y = np.isnan(y) | (y == 0.0)
+    if not (at == prefix).all() or not rest_e[~prefix].all():
+        j = int(np.flatnonzero(((at != prefix) | (~prefix & ~rest_e)).any(axis=1))[0])
+        raise ValueError(f"individual {j}: exposure is not 1 on a prefix of the intervals and 0 or NaN behind it (not a per-draw dataset)")
+    one = y == 1.0
+    if not (one | zero_y).all():
+        j = int(np.flatnonzero((~(one | zero_y)).any(axis=1))[0])
+        raise ValueError(f"individual {j}: infected must be 0, 1 or NaN in every cell (a fractional value: these are plug-in arrays "
+                         "of posterior means, not a per-draw dataset)")
+    event = np.where(one.any(axis=1), one.argmax(axis=1), -1).astype(np.int32)
+    bad = (one.sum(axis=1) > 1) | ((event >= 0) & (event != n_risk - 1))
+    if bad.any():
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"individual {j}: the one infection must lie in the last interval at risk, n_risk - 1 = {int(n_risk[j]) - 1}")
+    return n_risk, event
+
+
+def event_time_arrays(n_risk, event, T: int):
+    """(infected, exposure), each (N, T): the arrays ``event_time`` reads, NaN behind the intervals at risk."""
+    n_risk, event = np.asarray(n_risk), np.asarray(event)
+    t = np.arange(int(T))[None, :]
+    at = t < n_risk[:, None]
+    return np.where(at, (t == event[:, None]).astype(np.float64), np.nan), np.where(at, 1.0, np.nan)
+
+
+class SurvivalDraws:
+    """M per-draw datasets of one cohort and window (``SurvivalAnalysis.draws``): ``n_risk``, ``event`` (M, N) int32, ``s_titer``,
+    ``n_titer`` (M, T, N) -- interval-major, the rows ``start .. end - 2`` of the draw's (G, N) arrays as they are -- and ``source``
+    (M, 2), the (chain, draw) every dataset was made from.  ``events()`` gives Y (M, T), the infections per interval."""
+
+    def __init__(self, n_risk, event, s_titer, n_titer, source):
+        self.n_risk, self.event = np.ascontiguousarray(n_risk, dtype=np.int32), np.ascontiguousarray(event, dtype=np.int32)
+        self.s_titer, self.n_titer = np.ascontiguousarray(s_titer, dtype=np.float64), np.ascontiguousarray(n_titer, dtype=np.float64)
+        self.source = np.asarray(source, dtype=np.int64).reshape(-1, 2)
+        self.n_datasets, self.n_inds = self.n_risk.shape
+        self.n_int = self.s_titer.shape[1]
+        if self.event.shape != self.n_risk.shape or self.s_titer.shape != (self.n_datasets, self.n_int, self.n_inds) \
+                or self.n_titer.shape != self.s_titer.shape or self.source.shape[0] != self.n_datasets:
+            raise ValueError("n_risk, event (M, N), s_titer, n_titer (M, T, N) and source (M, 2) do not fit together")
+
+    def events(self) -> np.ndarray:
+        Y = np.zeros((self.n_datasets, self.n_int))
+        m, j = np.nonzero(self.event >= 0)
+        np.add.at(Y, (m, self.event[m, j]), 1.0)
+        return Y
+
+    def arrays(self, m: int):
+        """Dataset m as ``SurvivalModel`` takes it: (infected, exposure, s_titer, n_titer), each (N, T)."""
+        y, e = event_time_arrays(self.n_risk[m], self.event[m], self.n_int)
+        return y, e, self.s_titer[m].T.copy(), self.n_titer[m].T.copy()
+
+
+class SurvivalDrawsModel:
+    """One Poisson hazard model over an ensemble of per-draw datasets (``abd_survival_draws`` in ``include/abd_hip.h``):
+    ``names``, ``dim``, ``K``, ``n_datasets``, ``logp_dlogp(dataset, q)`` on the device -- an index and (D,) -> (logp, grad); (n,) and
+    (n, D) -> arrays, every point on its own dataset, up to 16 per launch -- ``loglik_sums(dataset, q)``, ``constrain(q)`` and
+    ``close()``.  It has no WAIC and no predictive checks: those are the plug-in model's."""
+
+    def __init__(self, draws: SurvivalDraws, titers, antigens, priors=None, device: int = -1):
+        from ._native import SurvivalDraws as _Dev
+
+        self.antigens = tuple(antigens)
+        self.K = len(titers)
+        self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
+        self._dev = _Dev(draws.n_risk, draws.event, titers, self.priors, device=device)
+        self.n_datasets, self.T, self.dim = draws.n_datasets, draws.n_int, self._dev.dim
+        self.source = draws.source
+        ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
+        self.names = tuple(ab + ["_lam0_raw_mu", "_lam0_raw_sd_log__"] + [f"__lam0_raw_z_{t}" for t in range(self.T)])
+
+    def logp_dlogp(self, dataset, q):
+        return self._dev.logp_dlogp(dataset, q)
+
+    def loglik_sums(self, dataset, q):
+        return self._dev.loglik_sums(dataset, q)
+
+    def constrain(self, q) -> Dict[str, np.ndarray]:
+        return constrain(q, self.K)
+
+    def close(self):
+        self._dev.close()
 
 
 class _DeviceModel:
@@ -295,6 +418,7 @@ class SurvivalAnalysis:
 
     def __init__(self, means_or_idata, start: int, end: int, cohort_data, device: int = -1):
         self.start, self.end, self.cohort_data, self.device = int(start), int(end), cohort_data, device
+        self._src = means_or_idata  # ``draws`` reads the recorded draws from it
         mean = _means(means_or_idata)
         last_gap = getattr(cohort_data, "last_gap", None)
         arrays = risk.survival_arrays(mean["i"], mean["ab_s_mu"], mean["ab_n_mu"], last_gap, self.start, self.end)
@@ -341,6 +465,47 @@ class SurvivalAnalysis:
 
     def model_combined(self) -> SurvivalModel:
         return self._windowed(SurvivalModel(self.infected, self.exposure, [self.s_titer, self.n_titer], ("S", "N"), device=self.device))
+
+    def draws(self, n_datasets: Optional[int] = None, index=None) -> "SurvivalDraws":
+        """The per-draw datasets of this cohort and window: ``risk.survival_arrays`` of one recorded draw's binary ``i`` with its own
+        titers, in event-time form (``event_time``), for M draws of the flattened chain x draw axis -- all of them by default,
+        ``n_datasets`` of them spaced evenly (``np.linspace(0, n - 1, M)`` rounded), or those of ``index``.  Needs a posterior with
+        recorded draws (``posterior_draws``)."""
+        d = posterior_draws(self._src)
+        C, Dn, G, N = d["i"].shape
+        if index is not None and n_datasets is not None:
+            raise ValueError("give n_datasets or index, not both")
+        if index is not None:
+            idx = np.asarray(index, dtype=np.int64).reshape(-1)
+        elif n_datasets is not None:
+            if not 1 <= int(n_datasets) <= C * Dn:
+                raise ValueError(f"n_datasets must be in [1, {C * Dn}] (chains x draws recorded), got {n_datasets}")
+            idx = np.rint(np.linspace(0, C * Dn - 1, int(n_datasets))).astype(np.int64)
+        else:
+            idx = np.arange(C * Dn)
+        if idx.size < 1 or idx.min() < 0 or idx.max() >= C * Dn:
+            raise ValueError(f"index must hold draws in [0, {C * Dn}) of the flattened chain x draw axis")
+        last_gap = getattr(self.cohort_data, "last_gap", None)
+        T = self.n_int
+        n_risk, event = np.empty((idx.size, N), np.int32), np.empty((idx.size, N), np.int32)
+        s_titer, n_titer = np.empty((idx.size, T, N)), np.empty((idx.size, T, N))
+        for m, k in enumerate(idx):
+            c, dr = divmod(int(k), Dn)
+            arr = risk.survival_arrays(d["i"][c, dr], d["ab_s_mu"][c, dr], d["ab_n_mu"][c, dr], last_gap, self.start, self.end)
+            try:
+                n_risk[m], event[m] = event_time(arr["infected"], arr["exposure"])
+            except ValueError as e:
+                raise ValueError(f"chain {c}, draw {dr}: {e}") from None
+            s_titer[m], n_titer[m] = d["ab_s_mu"][c, dr, self.start:self.end - 1], d["ab_n_mu"][c, dr, self.start:self.end - 1]
+        return SurvivalDraws(n_risk, event, s_titer, n_titer, np.stack(np.divmod(idx, Dn), axis=1))
+
+    def model_alone_draws(self, antigen: str, draws: "SurvivalDraws") -> "SurvivalDrawsModel":
+        if antigen not in ("S", "N"):
+            raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
+        return self._windowed(SurvivalDrawsModel(draws, [draws.s_titer if antigen == "S" else draws.n_titer], (antigen,), device=self.device))
+
+    def model_combined_draws(self, draws: "SurvivalDraws") -> "SurvivalDrawsModel":
+        return self._windowed(SurvivalDrawsModel(draws, [draws.s_titer, draws.n_titer], ("S", "N"), device=self.device))
 
     def _windowed(self, model):
         model.start, model.end = self.start, self.end  # what ``waic`` records in a fit, and ``compare`` checks
@@ -396,13 +561,8 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
     ``evaluator``: a callable ``q -> (logp, grad)`` in place of the device (tests)."""
     fn = evaluator if evaluator is not None else model.logp_dlogp
     dim, K = model.dim, model.K
-    if hasattr(model, "initial_point"):
-        q0 = np.asarray(model.initial_point(), dtype=np.float64)
-    else:
-        q0 = np.zeros(dim)
-        pri = getattr(model, "priors", PRIORS[K])
-        q0[2 * K], q0[2 * K + 1] = pri[1], -math.log(pri[3])  # PyMC's initial point: the prior means of _lam0_raw_mu and _lam0_raw_sd
-    per_chain = [_chain(fn, dim, tune, draws, np.random.default_rng([seed, c]), target_accept, q0) for c in range(chains)]
+    q0 = _initial_point(model)
+    per_chain =[_chain(fn, dim, tune, draws, np.random.default_rng([seed, c]), target_accept, q0) for c in range(chains)]
     q = np.stack([p[0] for p in per_chain])
     res = {name: q[:, :, k].copy() for k, name in enumerate(model.names)}
     res.update(model.constrain(q) if hasattr(model, "constrain") else constrain(q, K))
@@ -417,6 +577,186 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
         res["period_name"] = np.array(getattr(model, "period_name", "period"))
         res["period_index"] = np.asarray(model.period_index, dtype=np.int32)
     return res
+
+
+def _initial_point(model) -> np.ndarray:
+    """The point ``sample`` starts every chain's jitter from."""
+    if hasattr(model, "initial_point"):
+        return np.asarray(model.initial_point(), dtype=np.float64)
+    K = model.K
+    q0 = np.zeros(model.dim)
+    pri = getattr(model, "priors", PRIORS[K])
+    q0[2 * K], q0[2 * K + 1] = pri[1], -math.log(pri[3])  # PyMC's initial point: the prior means of _lam0_raw_mu and _lam0_raw_sd
+    return q0
+
+
+def _chain_gen(dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8, q0: Optional[np.ndarray] = None):
+    """``_chain`` (with ``adapt=True``) as a generator on ``sampler.NutsGen``: it yields every point it needs evaluated, is sent
+    ``(logp, grad)`` for it, and returns (draws (draws, dim), stats).  Statement for statement ``_chain``: driven with the values
+    ``fn`` would give, it is that chain bit for bit."""
+    from .sampler import NutsGen
+
+    q = (np.zeros(dim) if q0 is None else np.asarray(q0, dtype=np.float64)) + rng.uniform(-1, 1, size=dim)
+    nuts = NutsGen(dim, rng, target_accept=target_accept)
+    lp, g = yield q
+    nuts.eps = yield from nuts.find_reasonable_eps(q, lp, g)
+    nuts.da = DualAveraging(nuts.eps, target=target_accept)
+    out = np.empty((draws, dim))
+    stats = {k: np.empty(draws) for k in ("lp", "tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging")}
+    window_start, window_len = max(10, tune // 10), max(20, tune // 8)
+    window = []
+    for it in range(tune + draws):
+        tuning = it < tune
+        q, lp, g, st = yield from nuts.step(q, lp, g, adapt=tuning)
+        if tuning:
+            if it >= window_start:
+                window.append(q.copy())
+            if len(window) >= window_len and it < tune - 20:
+                var = np.var(np.asarray(window), axis=0)
+                nuts.inv_mass = (len(window) / (len(window) + 5.0)) * var + 1e-3 * (5.0 / (len(window) + 5.0))
+                window, window_len = [], int(window_len * 1.5)
+                nuts.eps = yield from nuts.find_reasonable_eps(q, lp, g)
+                nuts.da = DualAveraging(nuts.eps, target=target_accept)
+            if it == tune - 1:
+                nuts.eps = nuts.da.final()
+        else:
+            k = it - tune
+            out[k] = q
+            stats["lp"][k] = lp
+            for name in ("tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging"):
+                stats[name][k] = st[name]
+    return out, stats
+
+
+MAX_BATCH = 16  # ABD_MAX_BATCH: the points of one launch, and the chains ``sample_draws`` keeps in flight
+
+
+def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset: int = 1, seed: int = 0, target_accept: float = 0.8,
+                 evaluator: Optional[Callable] = None) -> Dict[str, np.ndarray]:
+    """NUTS on every dataset of ``model`` (a ``SurvivalDrawsModel``, or anything with ``dim``, ``names``, ``K``, ``n_datasets``):
+    M x ``chains_per_dataset`` chains, chain (m, c) exactly ``_chain`` on dataset m with ``np.random.default_rng([seed, m, c])`` from
+    ``sample``'s initial point.  The chains are generators (``_chain_gen``) that hand out the point they need; up to ``MAX_BATCH`` of
+    them are in flight, and every call of the evaluator carries one point of each -- on the device one launch for up to 16 chains
+    of different datasets.  A finished chain's slot goes to the next waiting chain at once.
+
+    Returns the keys of ``sample`` with a leading axis of M x c "chains", dataset-major (``protection``, ``summary`` and
+    ``report_line`` read it as they read a fit of ``sample``), and ``dataset`` (M c,) the dataset of every chain, ``source`` (M, 2)
+    where the model has it, ``n_evaluations`` and ``n_calls``.
+    ``evaluator``: a callable ``(datasets (n,), q (n, D)) -> (logp (n,), grad (n, D))`` in place of the device (tests)."""
+    fn = evaluator if evaluator is not None else model.logp_dlogp
+    dim, K, M, c = model.dim, model.K, int(model.n_datasets), int(chains_per_dataset)
+    if M < 1 or c < 1:
+        raise ValueError(f"at least one dataset and one chain per dataset, got {M} and {c}")
+    q0 = _initial_point(model)
+    jobs = [(m, k) for m in range(M) for k in range(c)]
+    per_chain = [None] * len(jobs)
+    waiting = iter(range(len(jobs)))
+    flight = []  # [job, generator, the point it waits for]
+
+    def start():
+        """the next waiting chain into flight, up to its first point"""
+        job = next(waiting, None)
+        if job is None:
+            return
+        m, k = jobs[job]
+        gen = _chain_gen(dim, tune, draws, np.random.default_rng([seed, m, k]), target_accept, q0)
+        flight.append([job, gen, next(gen)])
+
+    for _ in range(min(MAX_BATCH, len(jobs))):
+        start()
+    n_eval = n_calls = 0
+    while flight:
+        lp, g = fn(np.array([jobs[f[0]][0] for f in flight], dtype=np.int32), np.stack([f[2] for f in flight]))
+        n_eval, n_calls = n_eval + len(flight), n_calls + 1
+        done = []
+        for i, f in enumerate(flight):
+            try:
+                f[2] = f[1].send((float(lp[i]), np.array(g[i], dtype=np.float64)))
+            except StopIteration as fin:
+                per_chain[f[0]] = fin.value
+                done.append(i)
+        for i in reversed(done):
+            del flight[i]
+        for _ in done:
+            start()
+    q = np.stack([p[0] for p in per_chain])
+    res = {name: q[:, :, k].copy() for k, name in enumerate(model.names)}
+    res.update(model.constrain(q) if hasattr(model, "constrain") else constrain(q, K))
+    for name in per_chain[0][1]:
+        res["stat_" + name] = np.stack([p[1][name] for p in per_chain])
+    res["antigens"] = np.array(getattr(model, "antigens", ("S", "N")[:K]))
+    res["dataset"] = np.array([m for m, _ in jobs], dtype=np.int64)
+    if hasattr(model, "source"):
+        res["source"] = np.asarray(model.source, dtype=np.int64)
+    res["n_evaluations"], res["n_calls"] = np.array(n_eval, dtype=np.int64), np.array(n_calls, dtype=np.int64)
+    return res
+
+
+DRAWS_TITERS = (0.0, 2.0, 4.0)  # where ``draws_summary`` (and ``report_line``) read the protection
+
+
+def _draws_quantities(fit) -> Dict[str, np.ndarray]:
+    """(chains, draws) arrays of a, b and the protection at ``DRAWS_TITERS``, per antigen: ``a[S]``, ``b[S]``, ``protection[S]@0`` ..."""
+    names = [str(v) for v in np.asarray(fit["antigens"])]
+    a, b = np.asarray(fit["a"], dtype=np.float64), np.asarray(fit["b"], dtype=np.float64)
+    out = {}
+    for k, ag in enumerate(names):
+        ak, bk = (a[..., k], b[..., k]) if a.ndim == 3 else (a, b)
+        out[f"a[{ag}]"], out[f"b[{ag}]"] = ak, bk
+        for x in DRAWS_TITERS:
+            with np.errstate(over="ignore"):
+                out[f"protection[{ag}]@{x:g}"] = 1.0 - 1.0 / (1.0 + np.exp(-bk * (x - ak)))  # ``protection``'s formula, per draw
+    return out
+
+
+def draws_summary(fit, plug_in=None, prob: float = 0.95) -> Dict[str, Dict[str, object]]:
+    """The pooled read-out of a fit of ``sample_draws`` (multiple imputation over the datasets): for ``a``, ``b`` and the protection
+    at titers 0, 2 and 4 of every antigen -- keys ``a[S]``, ``b[S]``, ``protection[S]@0``, ... -- a dict with
+
+        median, lower, upper   of all draws of all datasets pooled (``prob`` equal-tailed)
+        sd                     of the pooled draws (ddof = 1)
+        W                      the mean over the datasets of the variance within a dataset (ddof = 1, its chains pooled)
+        B                      the variance of the datasets' means (ddof = 1; 0 for one dataset)
+        frac_between           B / (B + W): the share of the variance that the plug-in fit cannot see (0 where B + W = 0)
+        dataset_median         (M,) the median within every dataset
+        n_negative, n_positive the datasets whose median is below / above 0 -- for ``b``, where the model's flat second mode
+                                shows as datasets on either side
+        sd_ratio               with ``plug_in=`` (a fit of ``sample`` on the posterior means): pooled sd over the plug-in fit's sd
+    """
+    ds = np.asarray(fit["dataset"]).reshape(-1)
+    labels = np.unique(ds)
+    plug = _draws_quantities(plug_in) if plug_in is not None else None
+    out = {}
+    for name, x in _draws_quantities(fit).items():
+        if x.shape[0] != ds.size:
+            raise ValueError(f"{name}: {x.shape[0]} chains for {ds.size} entries of dataset")
+        per = [x[ds == m].reshape(-1) for m in labels]
+        W = float(np.mean([np.var(v, ddof=1) for v in per]))
+        B = float(np.var([v.mean() for v in per], ddof=1)) if len(per) > 1 else 0.0
+        med = np.array([np.median(v) for v in per])
+        iv = interval(x.reshape(-1), prob)
+        row = dict(median=float(iv["median"]), lower=float(iv["lower"]), upper=float(iv["upper"]), sd=float(np.std(x.reshape(-1), ddof=1)),
+                   W=W, B=B, frac_between=B / (B + W) if B + W > 0 else 0.0, dataset_median=med,
+                   n_negative=int((med < 0).sum()), n_positive=int((med > 0).sum()))
+        if plug is not None:
+            if name not in plug:
+                raise ValueError(f"the plug-in fit has no {name}: it is of other antigens")
+            row["sd_ratio"] = row["sd"] / float(np.std(plug[name].reshape(-1), ddof=1))
+        out[name] = row
+    return out
+
+
+# what a fit of ``sample_draws`` holds beyond one of ``sample``, and what ``--per_draw`` adds to it (``draws_fit_keys``)
+DRAWS_FIT_KEYS = ("dataset", "source", "n_evaluations", "n_calls", "draws_quantity", "draws_W", "draws_B", "draws_frac_between", "draws_dataset_median")
+
+
+def draws_fit_keys(summary_) -> Dict[str, np.ndarray]:
+    """What ``--per_draw`` adds to the output file: per quantity of ``draws_summary`` (rows in the order of ``draws_quantity``) W, B,
+    frac_between and the datasets' medians."""
+    names = list(summary_)
+    return {"draws_quantity": np.array(names), "draws_W": np.array([summary_[k]["W"] for k in names]),
+            "draws_B": np.array([summary_[k]["B"] for k in names]), "draws_frac_between": np.array([summary_[k]["frac_between"] for k in names]),
+            "draws_dataset_median": np.stack([summary_[k]["dataset_median"] for k in names])}
 
 
 WAIC_FIT_KEYS = ("elpd_waic_ind", "p_waic_ind", "waic_n_cells", "waic_n_draws")  # what ``waic`` records in a fit
@@ -840,6 +1180,12 @@ def main(argv=None) -> int:
     ap.add_argument("--ppc_edges_s", help="With --ppc: comma-separated bin edges of the S titer (up to 7, ascending; default: the octiles).")
     ap.add_argument("--ppc_edges_n", help="With --ppc: comma-separated bin edges of the N titer (up to 7, ascending; default: the octiles).")
     ap.add_argument("--ppc_seed", type=int, help="With --ppc: the seed of the replicates (default: --seed).")
+    ap.add_argument("--per_draw", type=int, metavar="M", help="Per-draw fits (multiple imputation) with --model s | n | combined: fit the model to M "
+                    "recorded draws of the posterior, each with its own infections and titers, spaced evenly over chains x draws, and pool "
+                    "them.  The line on stdout is of the pooled draws and ends with the share of the variance of a and b that lies between "
+                    "the datasets; the output also holds dataset, source, n_evaluations and the draws_* entries.  Needs a posterior with "
+                    "recorded draws (abdpymc-infer --thin).")
+    ap.add_argument("--per_draw_chains", type=int, metavar="C", help="With --per_draw: chains per dataset (default 1); --chains is not used then.")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
     ap.add_argument("--chains", type=int, default=4)
@@ -860,6 +1206,15 @@ def main(argv=None) -> int:
         ap.error("--periods / --period_name go with --model s_periods | n_periods")
     if not args.ppc and (args.ppc_edges_s is not None or args.ppc_edges_n is not None or args.ppc_seed is not None):
         ap.error("--ppc_edges_s / --ppc_edges_n / --ppc_seed go with --ppc")
+    if args.per_draw is None and args.per_draw_chains is not None:
+        ap.error("--per_draw_chains goes with --per_draw")
+    if args.per_draw is not None:
+        if args.model not in ("s", "n", "combined"):
+            ap.error(f"--per_draw fits --model s | n | combined; per-draw fits of --model {args.model} are not built")
+        if args.waic or args.ppc:
+            ap.error("--per_draw does not go with --waic / --ppc: WAIC and predictive checks of a per-draw fit are not built")
+        if args.per_draw < 1 or (args.per_draw_chains is not None and args.per_draw_chains < 1):
+            ap.error("--per_draw and --per_draw_chains must be >= 1")
     ppc_edges = {}
     for name, text in (("S", args.ppc_edges_s), ("N", args.ppc_edges_n)):
         if text is not None:
@@ -872,6 +1227,8 @@ def main(argv=None) -> int:
     data = TiterData.from_disk(args.ititers_data)
     try:
         sa = SurvivalAnalysis(args.posterior, args.start, args.end, data, device=args.device)
+        if args.per_draw is not None:
+            return _main_per_draw(args, sa)
         if by_period:
             if args.periods == "monthly":
                 periods = None
@@ -901,6 +1258,24 @@ def main(argv=None) -> int:
         print(waic_line(w))  # --waic: and this one
     if ppc is not None:
         print(predictive_line(ppc))  # --ppc: and one per binning variable
+    out = write(res, args.out, sa)
+    print(f"wrote {out}", file=sys.stderr)
+    return 0
+
+
+def _main_per_draw(args, sa) -> int:
+    """--per_draw: ``sample_draws`` on M datasets, the pooled line, the file.  A ``ValueError`` (a posterior without draws) is the
+    caller's to report."""
+    datasets = sa.draws(n_datasets=args.per_draw)
+    model = sa.model_combined_draws(datasets) if args.model == "combined" else sa.model_alone_draws(args.model.upper(), datasets)
+    try:
+        res = sample_draws(model, tune=args.tune, draws=args.draws, chains_per_dataset=args.per_draw_chains or 1, seed=args.seed)
+    finally:
+        model.close()
+    sm = draws_summary(res)
+    res.update(draws_fit_keys(sm))
+    between = ", ".join(f"{k} {sm[k]['frac_between']:.3f}" for k in sm if k[0] in "ab")
+    print(f"{report_line(res)}; per-draw fits of {datasets.n_datasets} datasets, share of the variance between datasets: {between}")
     out = write(res, args.out, sa)
     print(f"wrote {out}", file=sys.stderr)
     return 0
@@ -941,7 +1316,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + PPC_FIT_KEYS}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + PPC_FIT_KEYS + DRAWS_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

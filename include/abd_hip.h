@@ -794,6 +794,44 @@ int abd_survival_predictive_observed(abd_survival* s, double* observed, double* 
  * _accumulate draws for those indices.  Folds nothing and leaves the draw counter alone.  ABD_ERR_ARG before _configure. */
 int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int64_t draw0, int32_t* rep);
 
+/* Per-draw fits: the model of abd_survival_desc over an ensemble of M datasets, one per recorded draw of the run, all
+ * resident at once; every point of an evaluation names the dataset it is evaluated on, so that chains on different datasets
+ * share a launch.  A dataset made from a draw's binary infections has event-time form: individual j is at risk (exposure 1) in
+ * the intervals t < n_risk[j] and is infected in interval event[j], which is n_risk[j] - 1 or -1 (never infected while followed).
+ * The handle is a type of its own: the per-individual, WAIC and predictive calls of abd_survival do not take it.  theta, D and
+ * the priors are those of abd_survival_desc; the constant C of the data is 0 and Y_t counts the events of interval t. */
+typedef struct {
+  int32_t n_datasets;          /* M >= 1 */
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_titers;            /* K: 1 or 2 */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const int32_t* n_risk;       /* (M, N) row-major, each in [0, T] */
+  const int32_t* event;        /* (M, N) row-major, each -1 or n_risk - 1 */
+  const double* titer[2];      /* (M, T, N) row-major each: interval-major planes; finite wherever t < n_risk, anything elsewhere
+                                  (it is not read into a sum); titer[1] is read for K = 2 only */
+  double ab_sd;                /* the five priors of abd_survival_desc */
+  double lam0_mu_mean;
+  double lam0_mu_sd;
+  double lam0_sd_rate;
+  double lam0_z_sd;
+} abd_survival_draws_desc;
+
+typedef struct abd_survival_draws abd_survival_draws;
+
+/* Checks the descriptor and every dataset (ABD_ERR_ARG, naming the dataset, the individual and the interval of the first
+ * offender; before the device is touched), copies the titer planes and the two integers per individual to the device. */
+int abd_survival_draws_create(const abd_survival_draws_desc* desc, abd_survival_draws** out);
+int abd_survival_draws_destroy(abd_survival_draws* s);
+/* D = 2 K + 2 + T, or -1 for NULL. */
+int32_t abd_survival_draws_dim(abd_survival_draws* s);
+/* logp[n] and grad[n][D] at theta[n][D], point q on dataset[q] in [0, M) (ABD_ERR_ARG otherwise; nothing is launched then).  Any
+ * n: up to ABD_MAX_BATCH points share a launch.  A point's result is the same bits alone, in any batch and in any row of it, and
+ * the same bits an abd_survival handle made of that dataset's (infected, exposure, titer) arrays returns. */
+int abd_survival_draws_logp_dlogp(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* logp, double* grad);
+/* The raw device sums of one point on one dataset, as abd_survival_loglik_sums: sums[T + 2 + K]. */
+int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const double* theta, double* sums);
+
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).
  * This table is complete: the product library calls getenv for nothing else (development knobs of launch shapes
