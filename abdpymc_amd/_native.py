@@ -1088,18 +1088,50 @@ class NativeSampler:
             pass
 
 
-class Survival:
+class _SurvivalHandle:
+    """What the handles of the survival models share: the library, the handle ``_h`` (destroyed by the library's ``_destroy``) and
+    the check of the points of a call."""
+
+    _destroy = None  # the name of the library's destroy function
+
+    def __init__(self):
+        self._lib = load()
+        self._h = _P()
+
+    def _created(self, rc: int, dim_fn: str, n_sums: int):
+        """after the library's creator: its refusal raised, else ``dim`` read and ``n_sums`` kept"""
+        _check(self._lib, rc)
+        self.dim = int(getattr(self._lib, dim_fn)(self._h))
+        self.n_sums = n_sums
+
+    def _points(self, theta):
+        t = _as(theta, np.float64)
+        t = t.reshape(1, -1) if t.ndim == 1 else t
+        if t.ndim != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"theta must have shape ({self.dim},) or (n, {self.dim}), got {t.shape}")
+        return t
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Survival(_SurvivalHandle):
     """One survival model's data resident on the device (abd_hip.h: ``abd_survival``): ``infected``, ``exposure`` (N, T) and one or
     two titer arrays (N, T); ``priors`` = (ab_sd, lam0_mu_mean, lam0_mu_sd, lam0_sd_rate, lam0_z_sd).  The library checks the cells."""
 
+    _destroy = "abd_survival_destroy"
+
     def __init__(self, infected, exposure, titers, priors, device: int = -1):
-        lib = load()
-        self._lib = lib
-        self._h = _P()
-        y, e = _as(infected, np.float64), _as(exposure, np.float64)
-        xs = [_as(x, np.float64) for x in titers]
-        if y.ndim != 2 or e.shape != y.shape or any(x.shape != y.shape for x in xs):
-            raise ValueError("infected, exposure and the titers must share a shape (N, T)")
+        super().__init__()
+        y, e, *xs = self._planes(infected, exposure, titers, "titers")
         if len(xs) not in (1, 2):
             raise ValueError(f"one or two titer arrays, got {len(xs)}")
         d = _SurvivalDesc()
@@ -1108,10 +1140,16 @@ class Survival:
         for k, x in enumerate(xs):
             d.titer[k] = x.ctypes.data
         d.ab_sd, d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd = (float(v) for v in priors)
-        _check(lib, lib.abd_survival_create(C.byref(d), C.byref(self._h)))
+        self._created(self._lib.abd_survival_create(C.byref(d), C.byref(self._h)), "abd_survival_dim", y.shape[1] + 2 + len(xs))
+
+    def _planes(self, infected, exposure, titers, what: str):
+        """infected, exposure and the titers as float64 arrays of one shape (N, T); ``n_inds``, ``n_intervals``, ``n_titers``"""
+        y, e = _as(infected, np.float64), _as(exposure, np.float64)
+        xs = [_as(x, np.float64) for x in titers]
+        if y.ndim != 2 or e.shape != y.shape or any(x.shape != y.shape for x in xs):
+            raise ValueError(f"infected, exposure and the {what} must share a shape (N, T)")
         self.n_inds, self.n_intervals, self.n_titers = y.shape[0], y.shape[1], len(xs)
-        self.dim = int(lib.abd_survival_dim(self._h))
-        self.n_sums = y.shape[1] + 2 + len(xs)
+        return [y, e] + xs
 
     def logp_dlogp(self, theta):
         """``theta`` (D,) -> (logp, grad (D,)); (n, D) -> (logp (n,), grad (n, D))."""
@@ -1133,13 +1171,6 @@ class Survival:
         out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_loglik_sums(self._h, _ptr(t), _ptr(out)))
         return out
-
-    def _points(self, theta):
-        t = _as(theta, np.float64)
-        t = t.reshape(1, -1) if t.ndim == 1 else t
-        if t.ndim != 2 or t.shape[1] != self.dim:
-            raise ValueError(f"theta must have shape ({self.dim},) or (n, {self.dim}), got {t.shape}")
-        return t
 
     def individual_loglik(self, theta):
         """``theta`` (n, D) (or (D,)) -> (n, N): every individual's Poisson log-likelihood over its intervals at every point, in
@@ -1220,17 +1251,6 @@ class Survival:
         _check(self._lib, self._lib.abd_survival_replicate(self._h, t.shape[0], _ptr(t), int(draw0), _ptr(out)))
         return out
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.abd_survival_destroy(self._h)
-            self._h = _P()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class SurvivalGroups(Survival):
     """The survival model by group resident on the device (abd_hip.h: ``abd_survival_create_groups``): ``infected``, ``exposure``,
@@ -1238,13 +1258,9 @@ class SurvivalGroups(Survival):
     a_mu_sd, a_sd_rate, a_z_sd, b_sd).  The library checks the labels and the cells; the evaluations are ``Survival``'s."""
 
     def __init__(self, infected, exposure, titer, group, n_groups: int, priors, device: int = -1):
-        lib = load()
-        self._lib = lib
-        self._h = _P()
-        y, e, x = _as(infected, np.float64), _as(exposure, np.float64), _as(titer, np.float64)
+        _SurvivalHandle.__init__(self)
+        y, e, x = self._planes(infected, exposure, [titer], "titer")
         g = _as(group, np.int32)
-        if y.ndim != 2 or e.shape != y.shape or x.shape != y.shape:
-            raise ValueError("infected, exposure and the titer must share a shape (N, T)")
         if g.shape != (y.shape[0],):
             raise ValueError(f"group must have shape ({y.shape[0]},), got {g.shape}")
         d = _SurvivalGroupsDesc()
@@ -1252,10 +1268,8 @@ class SurvivalGroups(Survival):
         d.infected, d.exposure, d.titer, d.group = y.ctypes.data, e.ctypes.data, x.ctypes.data, g.ctypes.data
         (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
          d.b_sd) = (float(v) for v in priors)
-        _check(lib, lib.abd_survival_create_groups(C.byref(d), C.byref(self._h)))
-        self.n_inds, self.n_intervals, self.n_titers, self.n_groups = y.shape[0], y.shape[1], 1, int(n_groups)
-        self.dim = int(lib.abd_survival_dim(self._h))
-        self.n_sums = y.shape[1] + 2 + int(n_groups)
+        self.n_groups = int(n_groups)
+        self._created(self._lib.abd_survival_create_groups(C.byref(d), C.byref(self._h)), "abd_survival_dim", y.shape[1] + 2 + int(n_groups))
 
 
 class SurvivalPeriods(Survival):
@@ -1264,13 +1278,9 @@ class SurvivalPeriods(Survival):
     a_mu_sd, a_sd_rate, a_z_sd, b_sd).  The library checks the labels and the cells; the evaluations are ``Survival``'s."""
 
     def __init__(self, infected, exposure, titer, period, n_periods: int, priors, device: int = -1):
-        lib = load()
-        self._lib = lib
-        self._h = _P()
-        y, e, x = _as(infected, np.float64), _as(exposure, np.float64), _as(titer, np.float64)
+        _SurvivalHandle.__init__(self)
+        y, e, x = self._planes(infected, exposure, [titer], "titer")
         p = _as(period, np.int32)
-        if y.ndim != 2 or e.shape != y.shape or x.shape != y.shape:
-            raise ValueError("infected, exposure and the titer must share a shape (N, T)")
         if p.shape != (y.shape[1],):
             raise ValueError(f"period must have shape ({y.shape[1]},), got {p.shape}")
         d = _SurvivalPeriodsDesc()
@@ -1278,21 +1288,19 @@ class SurvivalPeriods(Survival):
         d.infected, d.exposure, d.titer, d.period = y.ctypes.data, e.ctypes.data, x.ctypes.data, p.ctypes.data
         (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
          d.b_sd) = (float(v) for v in priors)
-        _check(lib, lib.abd_survival_create_periods(C.byref(d), C.byref(self._h)))
-        self.n_inds, self.n_intervals, self.n_titers, self.n_periods = y.shape[0], y.shape[1], 1, int(n_periods)
-        self.dim = int(lib.abd_survival_dim(self._h))
-        self.n_sums = 2 * y.shape[1] + 2
+        self.n_periods = int(n_periods)
+        self._created(self._lib.abd_survival_create_periods(C.byref(d), C.byref(self._h)), "abd_survival_dim", 2 * y.shape[1] + 2)
 
 
-class SurvivalDraws:
+class SurvivalDraws(_SurvivalHandle):
     """An ensemble of per-draw datasets resident on the device (abd_hip.h: ``abd_survival_draws``): ``n_risk``, ``event`` (M, N) int32
     and one or two titer arrays (M, T, N); ``priors`` as ``Survival``'s.  Every point names its dataset.  The library checks the
     datasets.  A handle of its own kind: it has no per-individual, WAIC or predictive calls."""
 
+    _destroy = "abd_survival_draws_destroy"
+
     def __init__(self, n_risk, event, titers, priors, device: int = -1):
-        lib = load()
-        self._lib = lib
-        self._h = _P()
+        super().__init__()
         nr, ev = _as(n_risk, np.int32), _as(event, np.int32)
         xs = [_as(x, np.float64) for x in titers]
         if nr.ndim != 2 or ev.shape != nr.shape:
@@ -1307,10 +1315,8 @@ class SurvivalDraws:
         for k, x in enumerate(xs):
             d.titer[k] = x.ctypes.data
         d.ab_sd, d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd = (float(v) for v in priors)
-        _check(lib, lib.abd_survival_draws_create(C.byref(d), C.byref(self._h)))
         self.n_datasets, self.n_inds, self.n_intervals, self.n_titers = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs)
-        self.dim = int(lib.abd_survival_draws_dim(self._h))
-        self.n_sums = self.n_intervals + 2 + len(xs)
+        self._created(self._lib.abd_survival_draws_create(C.byref(d), C.byref(self._h)), "abd_survival_draws_dim", self.n_intervals + 2 + len(xs))
 
     def logp_dlogp(self, dataset, theta):
         """``dataset`` an index and ``theta`` (D,) -> (logp, grad (D,)); ``dataset`` (n,) and ``theta`` (n, D) -> (logp (n,), grad (n, D))."""
@@ -1332,14 +1338,3 @@ class SurvivalDraws:
         out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_draws_loglik_sums(self._h, int(dataset), _ptr(t), _ptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._lib.abd_survival_draws_destroy(self._h)
-            self._h = _P()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -1,10 +1,11 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
 // handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, the
 // posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
-// per-draw datasets, a handle of its own kind (abd_survival_draws_*; abd_survival_draws.hpp).  A
-// handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp,
-// abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the packing of the planes and the form of a model
-// (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
+// per-draw datasets, a handle of its own kind (abd_survival_draws_*; abd_survival_draws.hpp).  Both kinds run their
+// sums launches on one SurvivalSums.  A handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp,
+// abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the
+// packing of the planes and the form of a model (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at
+// the end of abd_survival_groups_terms.hpp).
 #include <memory>
 
 #include "abd_host.hpp"
@@ -29,16 +30,72 @@ struct SurvivalSpec {
   SurvivalGroupsPriors gpriors{};  // of the forms by group and by period
 };
 constexpr int kSurvRepBatch = 4;  // points per launch of abd_survival_replicate: its per-cell buffer holds this many
+
+// What a launch of the data sums runs on, for a handle of either kind (abd_survival, abd_survival_draws): the device, the stream,
+// the plan of the launch and the buffers of ABD_MAX_BATCH points.  A handle holds it by value, ahead of its own buffers: members go
+// in reverse declaration order, so those are freed first, then the buffers here, and the stream is the last to go (abd_host.hpp).
+struct SurvivalSums {
+  int device = 0;
+  int T = 0, ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
+  int par_stride = 0, out_stride = 0;  // the rows of a point in d_par / h_par and in d_out / h_out
+  Stream stream;
+  DevBuf<double> d_par, d_s_part, d_w_part, d_out;
+  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
+  std::vector<double> work;        // [ABD_MAX_BATCH] rows of the caller's: log lambda, 1 - lambda (and a form's own) of the points in flight
+
+  // The one place that splits a launch: ntile tiles of 64 individuals, and ranges of intervals -- enough waves for the chip (about
+  // 4096) while a wave keeps at least one interval.  From the tile count and T alone: the partial sums of two handles with the same
+  // (ntile, T) are added in the same order, whatever their kind.
+  void plan(int ntile_, int T_) {
+    T = T_;
+    ntile = ntile_;
+    ld = ntile * 64;
+    const int want_seg = std::max(1, std::min(T, (4096 + ntile - 1) / ntile));
+    seg_len = (T + want_seg - 1) / want_seg;
+    nseg = (T + seg_len - 1) / seg_len;
+    nw = ntile * nseg;
+  }
+  // after plan(): the device (`dev` < 0: the current one), the stream and the buffers
+  int alloc(int dev, int par_stride_, int out_stride_, int work_stride) {
+    device = dev;
+    par_stride = par_stride_;
+    out_stride = out_stride_;
+    work.resize((size_t)ABD_MAX_BATCH * work_stride);
+    if (device < 0) HIP_TRY(hipGetDevice(&device));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(stream.create());
+    HIP_TRY(d_par.alloc((size_t)ABD_MAX_BATCH * par_stride));
+    HIP_TRY(d_s_part.alloc((size_t)ABD_MAX_BATCH * ntile * T));
+    HIP_TRY(d_w_part.alloc((size_t)ABD_MAX_BATCH * nw * ABD_SURV_NW));
+    HIP_TRY(d_out.alloc((size_t)ABD_MAX_BATCH * out_stride));
+    HIP_TRY(h_par.alloc_pinned((size_t)ABD_MAX_BATCH * par_stride));
+    HIP_TRY(h_out.alloc_pinned((size_t)ABD_MAX_BATCH * out_stride));
+    return ABD_OK;
+  }
+  // the rows of n <= ABD_MAX_BATCH points: h_par to the device ahead of the launches, and d_out back to h_out behind them
+  int upload(int n) {
+    HIP_TRY(hipMemcpyAsync(d_par, h_par.host(), (size_t)n * par_stride * sizeof(double), hipMemcpyHostToDevice, stream));
+    return ABD_OK;
+  }
+  int download(int n) {
+    HIP_TRY(hipMemcpyAsync(h_out.host(), d_out, (size_t)n * out_stride * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return ABD_OK;
+  }
+  dim3 grid(int n) const { return dim3((unsigned)((nw + 3) / 4), (unsigned)n); }  // of a sums kernel: a wave per (tile, range)
+  void quiesce() {  // before the handle goes
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};
 }  // namespace abdi
 
 struct abd_survival : SurvivalSpec {
-  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
+  SurvivalSums sums;  // first: the last to go
   DevBuf<int32_t> d_tile_group, d_group_tile;
   std::vector<double> Y;  // Y_t = sum_j y_jt
   double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
-  DevBuf<double> d_y, d_e, d_x0, d_x1, d_par, d_s_part, d_w0_part, d_w_part, d_out;
-  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
-  std::vector<double> work;        // rows of form.work_stride(): log lambda, 1 - lambda (and the form's own) of the points in flight
+  DevBuf<double> d_y, d_e, d_x0, d_x1, d_w0_part;
   // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
   std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
   std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
@@ -60,7 +117,6 @@ struct abd_survival : SurvivalSpec {
   MappedBuf<int64_t> h_pp_out_r, h_pp_acc_r;
   MappedBuf<int32_t> h_pp_rep;
   int64_t pp_n = 0;                // draws folded since the last reset
-  Stream stream;
 
   int column(int j) const { return slot.empty() ? j : slot[j]; }
 };
@@ -68,72 +124,92 @@ struct abd_survival : SurvivalSpec {
 namespace abdi {
 namespace {
 
-// par and work of n <= ABD_MAX_BATCH points: rows of s->h_par and s->work
+// par and work of n <= ABD_MAX_BATCH points: rows of s->sums.h_par and s->sums.work
 void survival_prepare_points(abd_survival* s, int n, const double* theta) {
   const int D = s->form.dim(), stride = s->form.par_stride(), ws = s->form.work_stride();
-  for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * ws);
+  for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->sums.h_par.host() + (size_t)q * stride, s->sums.work.data() + (size_t)q * ws);
 }
 
-// what the argument structs of the three forms have in common
+// what the argument structs of the sums kernels have in common: the buffers and the plan of a launch
 template <typename Args>
-Args survival_args(const abd_survival* s) {
+Args survival_args(const SurvivalSums& c) {
   Args a;
   std::memset(&a, 0, sizeof a);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.par = s->d_par;
-  a.s_part = s->d_s_part;
-  a.w_part = s->d_w_part;
-  a.out = s->d_out;
-  a.T = s->form.T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
-  a.nseg = s->nseg;
-  a.seg_len = s->seg_len;
-  a.par_stride = s->form.par_stride();
+  a.par = c.d_par;
+  a.s_part = c.d_s_part;
+  a.w_part = c.d_w_part;
+  a.T = c.T;
+  a.ld = c.ld;
+  a.ntile = c.ntile;
+  a.nseg = c.nseg;
+  a.seg_len = c.seg_len;
+  a.par_stride = c.par_stride;
   return a;
 }
 
-// the sums of n <= ABD_MAX_BATCH points into s->h_out (rows of out_stride)
+// ... and those of the three forms of an abd_survival, whose kernel and finalize share one struct
+template <typename Args>
+Args survival_args(const abd_survival* s) {
+  Args a = survival_args<Args>(s->sums);
+  a.y = s->d_y;
+  a.e = s->d_e;
+  a.out = s->sums.d_out;
+  return a;
+}
+
+// fn(k0, nb) for the points k0 .. k0 + nb - 1 of n, at most `batch` of them at a time, until one fails
+template <typename Fn>
+int survival_batches(int n, int batch, Fn fn) {
+  for (int k0 = 0; k0 < n; k0 += batch)
+    if (int rc = fn(k0, std::min(batch, n - k0))) return rc;
+  return ABD_OK;
+}
+
+template <typename Handle>
+int survival_destroy(Handle* s) {
+  if (!s) return ABD_OK;
+  s->sums.quiesce();
+  delete s;
+  return ABD_OK;
+}
+
+// the sums of n <= ABD_MAX_BATCH points into s->sums.h_out (rows of out_stride)
 int survival_launch(abd_survival* s, int n, const double* theta) {
-  const int T = s->form.T;
+  SurvivalSums& c = s->sums;
+  const int T = c.T;
   survival_prepare_points(s, n, theta);
-  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->form.par_stride() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  const dim3 grid((unsigned)((s->nw + 3) / 4), (unsigned)n);
+  if (int rc = c.upload(n)) return rc;
   if (s->form.by_period()) {  // the one place that picks the pair of kernels
     SurvivalPeriodsArgs a = survival_args<SurvivalPeriodsArgs>(s);
     a.x = s->d_x0;
     a.w0_part = s->d_w0_part;
-    HIP_TRY(launch_kernel(abd_survival_periods_kernel, grid, dim3(256), 0, s->stream, a));
-    HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, s->stream, a));
+    HIP_TRY(launch_kernel(abd_survival_periods_kernel, c.grid(n), dim3(256), 0, c.stream, a));
+    HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, c.stream, a));
   } else if (s->form.grouped()) {
     SurvivalGroupsArgs a = survival_args<SurvivalGroupsArgs>(s);
     a.x = s->d_x0;
     a.tile_group = s->d_tile_group;
     a.group_tile = s->d_group_tile;
     a.Gr = s->form.Gr;
-    HIP_TRY(launch_kernel(abd_survival_groups_kernel, grid, dim3(256), 0, s->stream, a));
-    HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (a.Gr + 3) / 4), (unsigned)n), dim3(256), 0,
-                          s->stream, a));
+    HIP_TRY(launch_kernel(abd_survival_groups_kernel, c.grid(n), dim3(256), 0, c.stream, a));
+    HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (a.Gr + 3) / 4), (unsigned)n), dim3(256), 0, c.stream, a));
   } else {
     SurvivalArgs a = survival_args<SurvivalArgs>(s);
     a.x0 = s->d_x0;
     a.x1 = s->d_x1;
-    HIP_TRY(launch_kernel(s->form.K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, grid, dim3(256), 0, s->stream, a));
-    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, a));
+    HIP_TRY(launch_kernel(s->form.K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
+    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, a));
   }
-  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->form.out_stride() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return ABD_OK;
+  return c.download(n);
 }
 
 // ---- the per-individual log-likelihood (abd_survival_pointwise.hpp) ----
 
 // At creation, on the host: C_j per slot and the followed cells per individual from the planes y, e [T][ld]
 void survival_pointwise_setup(abd_survival* s, const double* y, const double* e) {
-  std::vector<int32_t> cells((size_t)s->ld);
-  s->cj.resize((size_t)s->ld);
-  survival_pointwise_constants(s->form.T, s->ld, y, e, s->cj.data(), cells.data());
+  std::vector<int32_t> cells((size_t)s->sums.ld);
+  s->cj.resize((size_t)s->sums.ld);
+  survival_pointwise_constants(s->form.T, s->sums.ld, y, e, s->cj.data(), cells.data());
   s->n_cells.resize((size_t)s->N);
   for (int j = 0; j < s->N; ++j) s->n_cells[j] = cells[s->column(j)];
   s->pw_stride = survival_pointwise_stride(s->form.T, s->form.n_ab());
@@ -142,11 +218,11 @@ void survival_pointwise_setup(abd_survival* s, const double* y, const double* e)
 // the buffers of the pointwise launches, at the first of them
 int survival_pointwise_ensure(abd_survival* s) {
   if (s->d_ll) return ABD_OK;
-  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->ld));
+  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->sums.ld));
   HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
   HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->ld));
-  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->ld));
+  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->sums.ld));
+  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->sums.ld));
   return ABD_OK;
 }
 
@@ -157,9 +233,9 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
   const int T = s->form.T, n_ab = s->form.n_ab(), stride = s->form.par_stride();
   survival_prepare_points(s, n, theta);
   for (int q = 0; q < n; ++q)
-    survival_pointwise_row(T, n_ab, s->h_par.host() + (size_t)q * stride, s->work.data() + (size_t)q * s->form.work_stride(), fold ? s->waic_n + q + 1 : 0,
+    survival_pointwise_row(T, n_ab, s->sums.h_par.host() + (size_t)q * stride, s->sums.work.data() + (size_t)q * s->form.work_stride(), fold ? s->waic_n + q + 1 : 0,
                            s->h_pw_par.host() + (size_t)q * s->pw_stride);
-  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->sums.stream));
   SurvivalPointArgs a;
   std::memset(&a, 0, sizeof a);
   a.y = s->d_y;
@@ -171,23 +247,23 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
   a.tile_group = s->d_tile_group;
   a.ll = s->d_ll;
   a.T = T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
+  a.ld = s->sums.ld;
+  a.ntile = s->sums.ntile;
   a.par_stride = s->pw_stride;
   a.n_ab = n_ab;
-  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
+  const dim3 grid((unsigned)((s->sums.ntile + 3) / 4), (unsigned)n);
   void (*const kernels[4])(const SurvivalPointArgs) = {abd_survival_individual_kernel<0>, abd_survival_individual_kernel<1>,
                                                        abd_survival_individual_kernel<2>, abd_survival_individual_kernel<3>};
-  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), 0, s->stream, a));
+  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), 0, s->sums.stream, a));
   if (fold) {
-    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->ld, s->stream));
-    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_ll,
-                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->ld, (int32_t)s->pw_stride,
+    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->sums.ld, s->sums.stream));
+    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_ll,
+                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->sums.ld, (int32_t)s->pw_stride,
                           (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
   } else {
-    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->sums.ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
   }
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
   if (fold) s->waic_n += n;
   return ABD_OK;
 }
@@ -202,7 +278,7 @@ int survival_predictive_configured(const abd_survival* s) {
 // the buffers of the predictive launches, at the first of them
 int survival_predictive_ensure(abd_survival* s) {
   if (s->d_pp_ej) return ABD_OK;
-  const size_t ld = (size_t)s->ld, part = (size_t)ABD_MAX_BATCH * s->ntile * ABD_SURV_PRED_COLS, out = (size_t)ABD_MAX_BATCH * ABD_SURV_PRED_COLS;
+  const size_t ld = (size_t)s->sums.ld, part = (size_t)ABD_MAX_BATCH * s->sums.ntile * ABD_SURV_PRED_COLS, out = (size_t)ABD_MAX_BATCH * ABD_SURV_PRED_COLS;
   HIP_TRY(s->d_pp_e_part.alloc(part));
   HIP_TRY(s->d_pp_r_part.alloc(part));
   HIP_TRY(s->d_pp_rj.alloc(ABD_MAX_BATCH * ld));
@@ -221,13 +297,13 @@ int survival_predictive_ensure(abd_survival* s) {
 int survival_predictive_launch(abd_survival* s, int n, const double* theta, int64_t draw0, bool fold, bool rep) {
   if (int rc = survival_predictive_ensure(s)) return rc;
   const int T = s->form.T;
-  const size_t cells = (size_t)T * s->ld;
+  const size_t cells = (size_t)T * s->sums.ld;
   if (rep && !s->d_pp_rep) {
     HIP_TRY(s->h_pp_rep.alloc_pinned(kSurvRepBatch * cells));
     HIP_TRY(s->d_pp_rep.alloc(kSurvRepBatch * cells));
   }
   survival_prepare_points(s, n, theta);
-  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * s->form.par_stride() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  if (int rc = s->sums.upload(n)) return rc;
   SurvivalReplicateArgs a;
   std::memset(&a, 0, sizeof a);
   a.e = s->d_e;
@@ -235,7 +311,7 @@ int survival_predictive_launch(abd_survival* s, int n, const double* theta, int6
   a.x1 = s->d_x1;
   a.bins = s->d_pp_bins;
   a.slot_j = s->d_pp_slot_j;
-  a.par = s->d_par;
+  a.par = s->sums.d_par;
   a.tile_group = s->d_tile_group;
   a.e_part = s->d_pp_e_part;
   a.r_part = s->d_pp_r_part;
@@ -246,28 +322,28 @@ int survival_predictive_launch(abd_survival* s, int n, const double* theta, int6
   a.seed_lo = s->pp_seed_lo;
   a.seed_hi = s->pp_seed_hi;
   a.T = T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
+  a.ld = s->sums.ld;
+  a.ntile = s->sums.ntile;
   a.par_stride = s->form.par_stride();
   a.n_ab = s->form.n_ab();
   a.n_var = s->pp_nvar;
-  const dim3 grid((unsigned)((s->ntile + 3) / 4), (unsigned)n);
+  const dim3 grid((unsigned)((s->sums.ntile + 3) / 4), (unsigned)n);
   void (*const kernels[4])(const SurvivalReplicateArgs) = {abd_survival_replicate_kernel<0>, abd_survival_replicate_kernel<1>,
                                                            abd_survival_replicate_kernel<2>, abd_survival_replicate_kernel<3>};
-  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), survival_replicate_lds(s->pp_nvar), s->stream, a));
+  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), survival_replicate_lds(s->pp_nvar), s->sums.stream, a));
   if (fold) {
-    HIP_TRY(launch_kernel(abd_survival_predictive_finalize, dim3(1, (unsigned)n), dim3(256), 0, s->stream, (const double*)s->d_pp_e_part,
-                          (const uint32_t*)s->d_pp_r_part, (double*)s->d_pp_out_e, (int64_t*)s->d_pp_out_r, (int32_t)s->ntile,
+    HIP_TRY(launch_kernel(abd_survival_predictive_finalize, dim3(1, (unsigned)n), dim3(256), 0, s->sums.stream, (const double*)s->d_pp_e_part,
+                          (const uint32_t*)s->d_pp_r_part, (double*)s->d_pp_out_e, (int64_t*)s->d_pp_out_r, (int32_t)s->sums.ntile,
                           (int32_t)(s->pp_nvar * ABD_SURV_PRED_BINS)));
-    HIP_TRY(launch_kernel(abd_survival_predictive_fold, dim3((unsigned)((s->ld + 255) / 256)), dim3(256), 0, s->stream, (const double*)s->d_pp_ej,
-                          (const int32_t*)s->d_pp_rj, (double*)s->d_pp_acc_e, (int64_t*)s->d_pp_acc_r, (int64_t*)s->d_pp_acc_r + s->ld,
-                          (int32_t)s->ld, (int32_t)n, draw0));
+    HIP_TRY(launch_kernel(abd_survival_predictive_fold, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_pp_ej,
+                          (const int32_t*)s->d_pp_rj, (double*)s->d_pp_acc_e, (int64_t*)s->d_pp_acc_r, (int64_t*)s->d_pp_acc_r + s->sums.ld,
+                          (int32_t)s->sums.ld, (int32_t)n, draw0));
     const size_t out = (size_t)n * ABD_SURV_PRED_COLS;
-    HIP_TRY(hipMemcpyAsync(s->h_pp_out_e.host(), s->d_pp_out_e, out * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->h_pp_out_r.host(), s->d_pp_out_r, out * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_pp_out_e.host(), s->d_pp_out_e, out * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+    HIP_TRY(hipMemcpyAsync(s->h_pp_out_r.host(), s->d_pp_out_r, out * sizeof(int64_t), hipMemcpyDeviceToHost, s->sums.stream));
   }
-  if (rep) HIP_TRY(hipMemcpyAsync(s->h_pp_rep.host(), s->d_pp_rep, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (rep) HIP_TRY(hipMemcpyAsync(s->h_pp_rep.host(), s->d_pp_rep, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
   return ABD_OK;
 }
 
@@ -305,53 +381,45 @@ int survival_create_common(const SurvivalSpec& spec, const double* infected, con
   std::unique_ptr<abd_survival> s(new (std::nothrow) abd_survival);
   if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
   static_cast<SurvivalSpec&>(*s) = spec;
-  s->ntile = ntile;
-  s->ld = ntile * 64;
+  s->sums.plan(ntile, T);
   if (layout) s->slot = layout->slot;
   s->Y = std::move(p.Y);
   s->C = p.C;
-  // ranges of intervals: enough waves for the chip (about 4096) while a wave keeps at least one interval; from the tile count and
-  // T alone
-  const int want_seg = std::max(1, std::min(T, (4096 + s->ntile - 1) / s->ntile));
-  s->seg_len = (T + want_seg - 1) / want_seg;
-  s->nseg = (T + s->seg_len - 1) / s->seg_len;
-  s->nw = s->ntile * s->nseg;
-  s->work.resize((size_t)ABD_MAX_BATCH * s->form.work_stride());
   survival_pointwise_setup(s.get(), p.y.data(), p.e.data());
-  if (s->device < 0) HIP_TRY(hipGetDevice(&s->device));
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(s->stream.create());
-  const size_t plane = (size_t)s->ld * T;
+  if (int rc = s->sums.alloc(spec.device, s->form.par_stride(), s->form.out_stride(), s->form.work_stride())) return rc;
+  const size_t plane = (size_t)s->sums.ld * T;
   HIP_TRY(s->d_y.upload(p.y.data(), plane));
   HIP_TRY(s->d_e.upload(p.e.data(), plane));
   HIP_TRY(s->d_x0.upload(p.x0.data(), plane));
   if (K == 2) HIP_TRY(s->d_x1.upload(p.x1.data(), plane));
   if (layout) {
-    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->ntile));
+    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->sums.ntile));
     HIP_TRY(s->d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
   }
-  const size_t par_stride = (size_t)s->form.par_stride(), out_stride = (size_t)s->form.out_stride();
-  HIP_TRY(s->d_par.alloc(ABD_MAX_BATCH * par_stride));
-  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
-  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
-  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
-  HIP_TRY(s->d_out.alloc(ABD_MAX_BATCH * out_stride));
-  HIP_TRY(s->h_par.alloc_pinned(ABD_MAX_BATCH * par_stride));
-  HIP_TRY(s->h_out.alloc_pinned(ABD_MAX_BATCH * out_stride));
+  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->sums.ntile * T));
   *out = s.release();
   return ABD_OK;
 }
 
-// The frame of the creators around `create`, the creator's own checks and its call of survival_create_common: nothing may be
+// what a creator says when the host has no memory for its copies of the data
+template <typename Desc>
+int survival_no_memory(const Desc* d) {
+  return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
+}
+int survival_no_memory(const abd_survival_draws_desc* d) {
+  return fail(ABD_ERR_NOMEM, "out of host memory for %d datasets of %d x %d cells", d->n_datasets, d->n_inds, d->n_intervals);
+}
+
+// The frame of the creators of both kinds of handle around `create`, the creator's own checks and what it builds: nothing may be
 // thrown across the C ABI (the host copies of the planes are the large allocations).
-template <typename Desc, typename Create>
-int survival_create(const Desc* d, abd_survival** out, Create create) {
+template <typename Desc, typename Handle, typename Create>
+int survival_create(const Desc* d, Handle** out, Create create) {
   if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
   *out = nullptr;
   try {
     return create();
   } catch (const std::bad_alloc&) {
-    return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
+    return survival_no_memory(d);
   }
 }
 
@@ -415,56 +483,48 @@ int abd_survival_create_periods(const abd_survival_periods_desc* d, abd_survival
   });
 }
 
-int abd_survival_destroy(abd_survival* s) {
-  if (!s) return ABD_OK;
-  (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  delete s;
-  return ABD_OK;
-}
+int abd_survival_destroy(abd_survival* s) { return survival_destroy(s); }
 
 int32_t abd_survival_dim(abd_survival* s) { return s ? s->form.dim() : -1; }
 
 int abd_survival_logp_dlogp(abd_survival* s, int32_t n, const double* theta, double* logp, double* grad) {
   if (!s || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   const size_t D = (size_t)s->form.dim(), out_stride = (size_t)s->form.out_stride(), par_stride = (size_t)s->form.par_stride();
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_launch(s, nb, theta + k0 * D)) return rc;
     for (int q = 0; q < nb; ++q) {
       const size_t k = (size_t)k0 + q;
-      logp[k] = s->form.combine(s->priors, s->gpriors, theta + k * D, s->Y.data(), s->C, s->h_out.host() + q * out_stride,
-                                s->h_par.host() + q * par_stride, s->work.data() + (size_t)q * s->form.work_stride(), grad + k * D);
+      logp[k] = s->form.combine(s->priors, s->gpriors, theta + k * D, s->Y.data(), s->C, s->sums.h_out.host() + q * out_stride,
+                                s->sums.h_par.host() + q * par_stride, s->sums.work.data() + (size_t)q * s->form.work_stride(), grad + k * D);
     }
-  }
-  return ABD_OK;
+    return (int)ABD_OK;
+  });
 }
 
 int abd_survival_loglik_sums(abd_survival* s, const double* theta, double* sums) {
   if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   if (int rc = survival_launch(s, 1, theta)) return rc;
-  std::memcpy(sums, s->h_out.host(), (size_t)s->form.n_sums() * sizeof(double));
+  std::memcpy(sums, s->sums.h_out.host(), (size_t)s->form.n_sums() * sizeof(double));
   return ABD_OK;
 }
 
 int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* theta, double* ll) {
   if (!s || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   const size_t D = (size_t)s->form.dim();
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_pointwise_launch(s, nb, theta + k0 * D, false)) return rc;
     for (int q = 0; q < nb; ++q) {  // slots to the caller's order
-      const double* row = s->h_ll.host() + (size_t)q * s->ld;
+      const double* row = s->h_ll.host() + (size_t)q * s->sums.ld;
       double* out = ll + ((size_t)k0 + q) * s->N;
       for (int j = 0; j < s->N; ++j) out[j] = row[s->column(j)];
     }
-  }
-  return ABD_OK;
+    return (int)ABD_OK;
+  });
 }
 
 int abd_survival_waic_reset(abd_survival* s) {
@@ -476,20 +536,19 @@ int abd_survival_waic_reset(abd_survival* s) {
 int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta) {
   if (!s || !theta) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
-  HIP_TRY(hipSetDevice(s->device));
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH)
-    if (int rc = survival_pointwise_launch(s, std::min(ABD_MAX_BATCH, n - k0), theta + (size_t)k0 * s->form.dim(), true)) return rc;
-  return ABD_OK;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  return survival_batches(n, ABD_MAX_BATCH,
+                          [&](int k0, int nb) { return survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->form.dim(), true); });
 }
 
 int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
   if (!s || !lse || !mean || !m2 || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
   if (s->waic_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_waic_accumulate comes first)");
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t ld = (size_t)s->ld;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld;
   if (!s->h_acc.host()) HIP_TRY(s->h_acc.alloc_pinned(4 * ld));
-  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, 4 * ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, 4 * ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
   const double* acc = s->h_acc.host();
   for (int j = 0; j < s->N; ++j) {
     const size_t c = (size_t)s->column(j);
@@ -510,12 +569,12 @@ int abd_survival_predictive_configure(abd_survival* s, int32_t n_var, const doub
     if (!titers[v] || (n_edges[v] > 0 && !edges[v])) return fail(ABD_ERR_ARG, "NULL array of binning variable %d", v);
     if (const char* msg = surv_pred_check_edges(n_edges[v], edges[v])) return fail(ABD_ERR_ARG, "binning variable %d: %s", v, msg);
   }
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   try {
     const int T = s->form.T;
-    const size_t ld = (size_t)s->ld, plane = ld * T;
+    const size_t ld = (size_t)s->sums.ld, plane = ld * T;
     std::vector<double> y(plane), e(plane);
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->sums.stream));
     HIP_TRY(hipMemcpy(y.data(), s->d_y, plane * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(e.data(), s->d_e, plane * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<uint8_t> bins(plane);
@@ -547,33 +606,32 @@ int abd_survival_predictive_accumulate(abd_survival* s, int32_t n, const double*
   if (!s || !theta || !expected || !replicate) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
   if (int rc = survival_predictive_configured(s)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   const size_t row = (size_t)s->pp_nvar * ABD_SURV_PRED_BINS;
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_predictive_launch(s, nb, theta + (size_t)k0 * s->form.dim(), s->pp_n, true, false)) return rc;
     s->pp_n += nb;
     for (int q = 0; q < nb; ++q) {
       std::memcpy(expected + ((size_t)k0 + q) * row, s->h_pp_out_e.host() + (size_t)q * ABD_SURV_PRED_COLS, row * sizeof(double));
       std::memcpy(replicate + ((size_t)k0 + q) * row, s->h_pp_out_r.host() + (size_t)q * ABD_SURV_PRED_COLS, row * sizeof(int64_t));
     }
-  }
-  return ABD_OK;
+    return (int)ABD_OK;
+  });
 }
 
 int abd_survival_predictive_stats(abd_survival* s, double* sum_e, int64_t* sum_r, int64_t* n_pos, int64_t* n_draws) {
   if (!s || !sum_e || !sum_r || !n_pos || !n_draws) return fail(ABD_ERR_ARG, "NULL argument");
   if (int rc = survival_predictive_configured(s)) return rc;
   if (s->pp_n < 1) return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_predictive_accumulate comes first)");
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t ld = (size_t)s->ld;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld;
   if (!s->h_pp_acc_e.host()) {
     HIP_TRY(s->h_pp_acc_e.alloc_pinned(ld));
     HIP_TRY(s->h_pp_acc_r.alloc_pinned(2 * ld));
   }
-  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_e.host(), s->d_pp_acc_e, ld * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_r.host(), s->d_pp_acc_r, 2 * ld * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_e.host(), s->d_pp_acc_e, ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipMemcpyAsync(s->h_pp_acc_r.host(), s->d_pp_acc_r, 2 * ld * sizeof(int64_t), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
   for (int j = 0; j < s->N; ++j) {
     const size_t c = (size_t)s->column(j);
     sum_e[j] = s->h_pp_acc_e.host()[c];
@@ -600,11 +658,10 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
   if (draw0 < 0) return fail(ABD_ERR_ARG, "draw0=%lld is negative", (long long)draw0);
   if (int rc = survival_predictive_configured(s)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   const int T = s->form.T;
-  const size_t ld = (size_t)s->ld;
-  for (int k0 = 0; k0 < n; k0 += kSurvRepBatch) {
-    const int nb = std::min(kSurvRepBatch, n - k0);
+  const size_t ld = (size_t)s->sums.ld;
+  return survival_batches(n, kSurvRepBatch, [&](int k0, int nb) {
     if (int rc = survival_predictive_launch(s, nb, theta + (size_t)k0 * s->form.dim(), draw0 + k0, false, true)) return rc;
     for (int q = 0; q < nb; ++q) {  // [T][ld] in slots to [N][T] in the caller's order
       const int32_t* plane = s->h_pp_rep.host() + (size_t)q * T * ld;
@@ -614,8 +671,8 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
         for (int t = 0; t < T; ++t) out[(size_t)j * T + t] = plane[(size_t)t * ld + c];
       }
     }
-  }
-  return ABD_OK;
+    return (int)ABD_OK;
+  });
 }
 
 }  // extern "C"
@@ -623,66 +680,39 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
 // ---- the ensemble of per-draw datasets (abd_survival_draws.hpp) ----
 
 struct abd_survival_draws {
-  int M = 0, N = 0, T = 0, K = 0, device = 0;
+  int M = 0, N = 0, T = 0, K = 0;
   SurvivalPriors priors{};
-  int ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
+  SurvivalSums sums;      // first: the last to go.  Rows of par: lambda[T], a[K], b[K], the dataset index; of work: log lambda, 1 - lambda
   std::vector<double> Y;  // [M][T]: the events of dataset m in interval t, an integer
-  DevBuf<double> d_x0, d_x1, d_par, d_s_part, d_w_part, d_out;
+  DevBuf<double> d_x0, d_x1;
   DevBuf<int32_t> d_n_risk, d_event;
-  MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
-  std::vector<double> work;        // [ABD_MAX_BATCH][2 T]: log lambda, 1 - lambda of the points in flight
-  Stream stream;
-
-  int par_stride() const { return T + 2 * K + 1; }  // lambda[T], a[K], b[K], the dataset index
-  int out_stride() const { return T + ABD_SURV_NW; }
 };
 
 namespace abdi {
 namespace {
 
-// the sums of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->h_out (rows of out_stride)
+// the sums of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->sums.h_out (rows of out_stride)
 int survival_draws_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta) {
-  const int T = s->T, K = s->K, stride = s->par_stride();
+  SurvivalSums& c = s->sums;
+  const int T = s->T, K = s->K;
   const size_t D = (size_t)survival_dim(K, T);
   for (int q = 0; q < n; ++q) {
-    double* par = s->h_par.host() + (size_t)q * stride;
-    survival_prepare(K, T, theta + q * D, par, s->work.data() + (size_t)q * 2 * T);
+    double* par = c.h_par.host() + (size_t)q * c.par_stride;
+    survival_prepare(K, T, theta + q * D, par, c.work.data() + (size_t)q * 2 * T);
     par[T + 2 * K] = 0.0;
     std::memcpy(par + T + 2 * K, dataset + q, sizeof(int32_t));
   }
-  HIP_TRY(hipMemcpyAsync(s->d_par, s->h_par.host(), (size_t)n * stride * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  SurvivalDrawsArgs a;
-  std::memset(&a, 0, sizeof a);
+  if (int rc = c.upload(n)) return rc;
+  SurvivalDrawsArgs a = survival_args<SurvivalDrawsArgs>(c);
   a.x0 = s->d_x0;
   a.x1 = s->d_x1;
   a.n_risk = s->d_n_risk;
   a.event = s->d_event;
-  a.par = s->d_par;
-  a.s_part = s->d_s_part;
-  a.w_part = s->d_w_part;
-  a.T = T;
-  a.ld = s->ld;
-  a.ntile = s->ntile;
-  a.nseg = s->nseg;
-  a.seg_len = s->seg_len;
-  a.par_stride = stride;
-  SurvivalArgs f;  // the finalize of abd_survival, as it is: it reads the partials, T, ntile and nseg
-  std::memset(&f, 0, sizeof f);
-  f.s_part = s->d_s_part;
-  f.w_part = s->d_w_part;
-  f.out = s->d_out;
-  f.T = T;
-  f.ld = s->ld;
-  f.ntile = s->ntile;
-  f.nseg = s->nseg;
-  f.seg_len = s->seg_len;
-  f.par_stride = stride;
-  HIP_TRY(launch_kernel(K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, dim3((unsigned)((s->nw + 3) / 4), (unsigned)n),
-                        dim3(256), 0, s->stream, a));
-  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, s->stream, f));
-  HIP_TRY(hipMemcpyAsync(s->h_out.host(), s->d_out, (size_t)n * s->out_stride() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return ABD_OK;
+  SurvivalArgs f = survival_args<SurvivalArgs>(c);  // the finalize of abd_survival, as it is: it reads the partials, T, ntile and nseg
+  f.out = c.d_out;
+  HIP_TRY(launch_kernel(K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
+  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, f));
+  return c.download(n);
 }
 
 int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int32_t* dataset) {
@@ -702,17 +732,11 @@ int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws**
     return rc;
   std::unique_ptr<abd_survival_draws> s(new (std::nothrow) abd_survival_draws);
   if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
-  s->M = M, s->N = N, s->T = T, s->K = K, s->device = d->device;
+  s->M = M, s->N = N, s->T = T, s->K = K;
   s->priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
-  s->ntile = (N + 63) / 64;
-  s->ld = s->ntile * 64;
-  // the split of abd_survival (survival_create_common): from the tile count and T alone
-  const int want_seg = std::max(1, std::min(T, (4096 + s->ntile - 1) / s->ntile));
-  s->seg_len = (T + want_seg - 1) / want_seg;
-  s->nseg = (T + s->seg_len - 1) / s->seg_len;
-  s->nw = s->ntile * s->nseg;
+  s->sums.plan((N + 63) / 64, T);  // the split of an abd_survival of N individuals
   // every dataset, individual after individual: the first offender is named; the padded copies as the kernel reads them
-  const size_t ld = (size_t)s->ld, plane = ld * T;
+  const size_t ld = (size_t)s->sums.ld, plane = ld * T;
   std::vector<int32_t> n_risk((size_t)M * ld, 0), event((size_t)M * ld, -1);
   std::vector<double> x0((size_t)M * plane, 0.0), x1(K == 2 ? (size_t)M * plane : 0, 0.0);
   s->Y.assign((size_t)M * T, 0.0);
@@ -734,21 +758,11 @@ int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws**
             return fail(ABD_ERR_ARG, "dataset %d, individual %d, interval %d: titer %d of a cell at risk must be finite", m, j, t, k);
       }
     }
-  s->work.resize((size_t)ABD_MAX_BATCH * 2 * T);
-  if (s->device < 0) HIP_TRY(hipGetDevice(&s->device));
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(s->stream.create());
+  if (int rc = s->sums.alloc(d->device, T + 2 * K + 1, T + ABD_SURV_NW, 2 * T)) return rc;  // rows of par, out and work
   HIP_TRY(s->d_x0.upload(x0.data(), x0.size()));
   if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), x1.size()));
   HIP_TRY(s->d_n_risk.upload(n_risk.data(), n_risk.size()));
   HIP_TRY(s->d_event.upload(event.data(), event.size()));
-  const size_t par_stride = (size_t)s->par_stride(), out_stride = (size_t)s->out_stride();
-  HIP_TRY(s->d_par.alloc(ABD_MAX_BATCH * par_stride));
-  HIP_TRY(s->d_s_part.alloc((size_t)ABD_MAX_BATCH * s->ntile * T));
-  HIP_TRY(s->d_w_part.alloc((size_t)ABD_MAX_BATCH * s->nw * ABD_SURV_NW));
-  HIP_TRY(s->d_out.alloc(ABD_MAX_BATCH * out_stride));
-  HIP_TRY(s->h_par.alloc_pinned(ABD_MAX_BATCH * par_stride));
-  HIP_TRY(s->h_out.alloc_pinned(ABD_MAX_BATCH * out_stride));
   *out = s.release();
   return ABD_OK;
 }
@@ -759,22 +773,10 @@ int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws**
 extern "C" {
 
 int abd_survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws** out) {
-  if (!d || !out) return fail(ABD_ERR_ARG, "NULL argument");
-  *out = nullptr;
-  try {
-    return survival_draws_create(d, out);
-  } catch (const std::bad_alloc&) {
-    return fail(ABD_ERR_NOMEM, "out of host memory for %d datasets of %d x %d cells", d->n_datasets, d->n_inds, d->n_intervals);
-  }
+  return survival_create(d, out, [&] { return survival_draws_create(d, out); });
 }
 
-int abd_survival_draws_destroy(abd_survival_draws* s) {
-  if (!s) return ABD_OK;
-  (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  delete s;
-  return ABD_OK;
-}
+int abd_survival_draws_destroy(abd_survival_draws* s) { return survival_destroy(s); }
 
 int32_t abd_survival_draws_dim(abd_survival_draws* s) { return s ? survival_dim(s->K, s->T) : -1; }
 
@@ -782,27 +784,26 @@ int abd_survival_draws_logp_dlogp(abd_survival_draws* s, int32_t n, const int32_
   if (!s || !dataset || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
   if (int rc = survival_draws_check_datasets(s, n, dataset)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   const int T = s->T, K = s->K;
   const size_t D = (size_t)survival_dim(K, T);
-  for (int k0 = 0; k0 < n; k0 += ABD_MAX_BATCH) {
-    const int nb = std::min(ABD_MAX_BATCH, n - k0);
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_draws_launch(s, nb, dataset + k0, theta + k0 * D)) return rc;
     for (int q = 0; q < nb; ++q) {
       const size_t k = (size_t)k0 + q;
-      logp[k] = survival_combine(s->priors, K, T, theta + k * D, s->Y.data() + (size_t)dataset[k] * T, 0.0, s->h_out.host() + (size_t)q * s->out_stride(),
-                                 s->h_par.host() + (size_t)q * s->par_stride(), s->work.data() + (size_t)q * 2 * T, grad + k * D);
+      logp[k] = survival_combine(s->priors, K, T, theta + k * D, s->Y.data() + (size_t)dataset[k] * T, 0.0, s->sums.h_out.host() + (size_t)q * s->sums.out_stride,
+                                 s->sums.h_par.host() + (size_t)q * s->sums.par_stride, s->sums.work.data() + (size_t)q * 2 * T, grad + k * D);
     }
-  }
-  return ABD_OK;
+    return (int)ABD_OK;
+  });
 }
 
 int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const double* theta, double* sums) {
   if (!s || !theta || !sums) return fail(ABD_ERR_ARG, "NULL argument");
   if (int rc = survival_draws_check_datasets(s, 1, &dataset)) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->sums.device));
   if (int rc = survival_draws_launch(s, 1, &dataset, theta)) return rc;
-  std::memcpy(sums, s->h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
+  std::memcpy(sums, s->sums.h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
   return ABD_OK;
 }
 

@@ -40,10 +40,26 @@ class DualAveraging:
         return math.exp(self.log_eps_bar)
 
 
-class Nuts:
-    """One NUTS transition kernel over q in R^d for ``fn(q) -> (logp, grad)``."""
+def drive(gen, fn):
+    """Runs a generator that yields the points it needs evaluated against ``fn(q) -> (logp, grad)``: what it returns."""
+    try:
+        q = next(gen)
+        while True:
+            q = gen.send(fn(q))
+    except StopIteration as fin:
+        return fin.value
 
-    def __init__(self, fn: Callable[[np.ndarray], Tuple[float, np.ndarray]], dim: int, rng: np.random.Generator,
+
+class Nuts:
+    """One NUTS transition kernel over q in R^d for ``fn(q) -> (logp, grad)``.
+
+    The kernel is written once, with the evaluator turned inside out: ``step_gen`` and ``find_reasonable_eps_gen`` are generators
+    that YIELD the point they need evaluated and are sent ``(logp, grad)`` for it; their result is the generator's return value.
+    ``step`` and ``find_reasonable_eps`` drive them against ``fn`` (``drive``).  A caller that evaluates elsewhere -- many chains
+    waiting on one batched evaluation, ``survival.sample_draws`` -- passes ``fn=None`` and drives the generators itself: the
+    operations and the use of ``rng`` are the same code in the same order, so the chain is the same bit for bit."""
+
+    def __init__(self, fn: Optional[Callable[[np.ndarray], Tuple[float, np.ndarray]]], dim: int, rng: np.random.Generator,
                  max_treedepth: int = 10, target_accept: float = 0.8):
         self.fn, self.dim, self.rng = fn, dim, rng
         self.max_treedepth = max_treedepth
@@ -52,105 +68,6 @@ class Nuts:
         self.eps = 0.1
         self.target_accept = target_accept
         self.n_grad = 0
-
-    def _grad(self, q):
-        self.n_grad += 1
-        lp, g = self.fn(q)
-        if not np.isfinite(lp):
-            return -np.inf, np.zeros_like(q)
-        return float(lp), np.asarray(g, dtype=float)
-
-    def _leapfrog(self, q, p, g, eps):
-        p = p + 0.5 * eps * g
-        q = q + eps * self.inv_mass * p
-        lp, g = self._grad(q)
-        p = p + 0.5 * eps * g
-        return q, p, lp, g
-
-    def _energy(self, lp, p):
-        return lp - 0.5 * float(np.sum(self.inv_mass * p * p))
-
-    def find_reasonable_eps(self, q, lp, g) -> float:
-        eps = 0.1
-        p = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
-        h0 = self._energy(lp, p)
-        _, p1, lp1, _ = self._leapfrog(q, p, g, eps)
-        dh = self._energy(lp1, p1) - h0
-        a = 1.0 if (np.isfinite(dh) and dh > math.log(0.5)) else -1.0
-        for _ in range(50):
-            if not np.isfinite(dh):
-                dh = -np.inf
-            if a * dh <= -a * math.log(2.0):
-                break
-            eps *= 2.0**a
-            _, p1, lp1, _ = self._leapfrog(q, p, g, eps)
-            dh = self._energy(lp1, p1) - h0
-        return eps
-
-    def _build(self, q, p, g, log_u, v, j, eps, h0):
-        if j == 0:
-            q1, p1, lp1, g1 = self._leapfrog(q, p, g, v * eps)
-            h1 = self._energy(lp1, p1)
-            if not np.isfinite(h1):
-                h1 = -np.inf
-            n1 = int(log_u <= h1)
-            s1 = log_u < h1 + 1000.0
-            alpha = min(1.0, math.exp(min(0.0, h1 - h0))) if np.isfinite(h1) else 0.0
-            return q1, p1, g1, q1, p1, g1, q1, lp1, g1, n1, s1, alpha, 1
-        qm, pm, gm, qp, pp, gp, q1, lp1, g1, n1, s1, a1, na1 = self._build(q, p, g, log_u, v, j - 1, eps, h0)
-        if s1:
-            if v == -1:
-                qm, pm, gm, _, _, _, q2, lp2, g2, n2, s2, a2, na2 = self._build(qm, pm, gm, log_u, v, j - 1, eps, h0)
-            else:
-                _, _, _, qp, pp, gp, q2, lp2, g2, n2, s2, a2, na2 = self._build(qp, pp, gp, log_u, v, j - 1, eps, h0)
-            if n2 > 0 and self.rng.random() < n2 / max(n1 + n2, 1):
-                q1, lp1, g1 = q2, lp2, g2
-            a1, na1 = a1 + a2, na1 + na2
-            dq = qp - qm
-            s1 = s2 and float(np.dot(dq, self.inv_mass * pm)) >= 0 and float(np.dot(dq, self.inv_mass * pp)) >= 0
-            n1 += n2
-        return qm, pm, gm, qp, pp, gp, q1, lp1, g1, n1, s1, a1, na1
-
-    def step(self, q, lp, g, adapt: bool):
-        """One transition.  Returns (q, logp, grad, stats)."""
-        eps = self.eps
-        p0 = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
-        h0 = self._energy(lp, p0)
-        log_u = h0 + math.log(self.rng.random() + 1e-300)
-        qm = qp = q
-        pm = pp = p0
-        gm = gp = g
-        j, n, s = 0, 1, True
-        q_new, lp_new, g_new = q, lp, g
-        alpha, n_alpha = 0.0, 1
-        while s and j < self.max_treedepth:
-            v = -1 if self.rng.random() < 0.5 else 1
-            if v == -1:
-                qm, pm, gm, _, _, _, q1, lp1, g1, n1, s1, alpha, n_alpha = self._build(qm, pm, gm, log_u, v, j, eps, h0)
-            else:
-                _, _, _, qp, pp, gp, q1, lp1, g1, n1, s1, alpha, n_alpha = self._build(qp, pp, gp, log_u, v, j, eps, h0)
-            if s1 and self.rng.random() < min(1.0, n1 / n):
-                q_new, lp_new, g_new = q1, lp1, g1
-            n += n1
-            dq = qp - qm
-            s = s1 and float(np.dot(dq, self.inv_mass * pm)) >= 0 and float(np.dot(dq, self.inv_mass * pp)) >= 0
-            j += 1
-        acc = alpha / max(n_alpha, 1)
-        if adapt and self.da is not None:
-            self.eps = self.da.update(acc)
-        return q_new, lp_new, g_new, dict(tree_depth=j, mean_tree_accept=acc, step_size=eps, n_steps=n_alpha,
-                                          diverging=not s and j < self.max_treedepth and acc == 0.0)
-
-
-class NutsGen(Nuts):
-    """``Nuts`` with the evaluator turned inside out: ``find_reasonable_eps`` and ``step`` are generators that YIELD the point they
-    need evaluated and are sent ``(logp, grad)`` for it; what ``Nuts`` returns comes back as the generator's return value.  Statement
-    for statement the code of ``Nuts`` (the same operations and the same use of ``rng`` in the same order), so that a chain driven
-    through it is bit for bit the chain of ``Nuts`` on the same evaluator -- and many chains can wait on one batched evaluation
-    (``survival.sample_draws``).  ``fn`` is not used."""
-
-    def __init__(self, dim: int, rng: np.random.Generator, max_treedepth: int = 10, target_accept: float = 0.8):
-        super().__init__(None, dim, rng, max_treedepth=max_treedepth, target_accept=target_accept)
 
     def _grad(self, q):
         self.n_grad += 1
@@ -166,7 +83,10 @@ class NutsGen(Nuts):
         p = p + 0.5 * eps * g
         return q, p, lp, g
 
-    def find_reasonable_eps(self, q, lp, g):
+    def _energy(self, lp, p):
+        return lp - 0.5 * float(np.sum(self.inv_mass * p * p))
+
+    def find_reasonable_eps_gen(self, q, lp, g):
         eps = 0.1
         p = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
         h0 = self._energy(lp, p)
@@ -182,6 +102,9 @@ class NutsGen(Nuts):
             _, p1, lp1, _ = yield from self._leapfrog(q, p, g, eps)
             dh = self._energy(lp1, p1) - h0
         return eps
+
+    def find_reasonable_eps(self, q, lp, g) -> float:
+        return drive(self.find_reasonable_eps_gen(q, lp, g), self.fn)
 
     def _build(self, q, p, g, log_u, v, j, eps, h0):
         if j == 0:
@@ -207,7 +130,7 @@ class NutsGen(Nuts):
             n1 += n2
         return qm, pm, gm, qp, pp, gp, q1, lp1, g1, n1, s1, a1, na1
 
-    def step(self, q, lp, g, adapt: bool):
+    def step_gen(self, q, lp, g, adapt: bool):
         """One transition, as a generator.  Returns (q, logp, grad, stats)."""
         eps = self.eps
         p0 = self.rng.standard_normal(self.dim) / np.sqrt(self.inv_mass)
@@ -236,6 +159,40 @@ class NutsGen(Nuts):
             self.eps = self.da.update(acc)
         return q_new, lp_new, g_new, dict(tree_depth=j, mean_tree_accept=acc, step_size=eps, n_steps=n_alpha,
                                           diverging=not s and j < self.max_treedepth and acc == 0.0)
+
+    def step(self, q, lp, g, adapt: bool):
+        """One transition.  Returns (q, logp, grad, stats)."""
+        return drive(self.step_gen(q, lp, g, adapt), self.fn)
+
+
+class WindowedAdaptation:
+    """The tuning of one ``Nuts`` over ``tune`` iterations: step size by ``find_reasonable_eps`` and dual averaging (towards
+    ``target``), the diagonal metric from the variances of the tuning draws in expanding windows, shrunk by n / (n + 5); after a
+    metric is installed the step size is searched again and dual averaging starts over; the last tuning iteration installs
+    ``da.final()``.  ``restart`` and ``update`` are generators like the kernel's, since the search needs evaluations: ``yield
+    from`` them in a chain that is itself a generator, or ``drive`` them."""
+
+    def __init__(self, nuts: Nuts, tune: int, target: float = 0.8):
+        self.nuts, self.tune, self.target = nuts, tune, target
+        self.window_start, self.window_len = max(10, tune // 10), max(20, tune // 8)
+        self.window = []
+
+    def restart(self, q, lp, g):
+        """The step size search from the chain's state, and dual averaging from what it finds."""
+        self.nuts.eps = yield from self.nuts.find_reasonable_eps_gen(q, lp, g)
+        self.nuts.da = DualAveraging(self.nuts.eps, target=self.target)
+
+    def update(self, it: int, q, lp, g):
+        """After tuning iteration ``it`` < tune, whose transition has fed dual averaging: ``q`` is its draw."""
+        if it >= self.window_start:
+            self.window.append(q.copy())
+        if len(self.window) >= self.window_len and it < self.tune - 20:
+            n = len(self.window)
+            self.nuts.inv_mass = (n / (n + 5.0)) * np.var(np.asarray(self.window), axis=0) + 1e-3 * (5.0 / (n + 5.0))
+            self.window, self.window_len = [], int(self.window_len * 1.5)
+            yield from self.restart(q, lp, g)
+        if it == self.tune - 1:
+            self.nuts.eps = self.nuts.da.final()
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -291,8 +248,8 @@ def sample_chain(model, chain: int, tune: int, draws: int, seed: int, record_det
 
     nuts = Nuts(fn, len(THETA_NAMES), rng)
     lp, g = fn(q)
-    nuts.eps = nuts.find_reasonable_eps(q, lp, g)
-    nuts.da = DualAveraging(nuts.eps)
+    adaptation = WindowedAdaptation(nuts, tune)  # the metric from the variances of the tuning draws in expanding windows
+    drive(adaptation.restart(q, lp, g), fn)
 
     n_bits = G * N + N
     use_device_sweep = hasattr(ctx, "gibbs_sweep") and device_gibbs
@@ -321,9 +278,6 @@ def sample_chain(model, chain: int, tune: int, draws: int, seed: int, record_det
     if record_deterministics:
         det = dict(i=np.empty((draws, G, N), dtype=np.int8), ab_n_mu=np.empty((draws, G, N)), ab_s_mu=np.empty((draws, G, N)))
 
-    # mass-matrix adaptation: variances of the tuning draws in expanding windows
-    window_start, window_len = max(10, tune // 10), max(20, tune // 8)
-    window = []
     for it in range(tune + draws):
         tuning = it < tune
         q, lp, g, st = nuts.step(q, lp, g, adapt=tuning)
@@ -337,16 +291,7 @@ def sample_chain(model, chain: int, tune: int, draws: int, seed: int, record_det
             lp, n_acc, n_prop = binary_gibbs_sweep(n_bits, flip_logp, unflip, lp, rng)
         lp, g = fn(q)  # logp and gradient at the new discrete state
         if tuning:
-            if it >= window_start:
-                window.append(q.copy())
-            if len(window) >= window_len and it < tune - 20:
-                var = np.var(np.asarray(window), axis=0)
-                nuts.inv_mass = (len(window) / (len(window) + 5.0)) * var + 1e-3 * (5.0 / (len(window) + 5.0))
-                window, window_len = [], int(window_len * 1.5)
-                nuts.eps = nuts.find_reasonable_eps(q, lp, g)
-                nuts.da = DualAveraging(nuts.eps)
-            if it == tune - 1:
-                nuts.eps = nuts.da.final()
+            drive(adaptation.update(it, q, lp, g), fn)
         else:
             k = it - tune
             out_q[k] = q

@@ -19,6 +19,10 @@ on the device, where every point of a launch reads its own dataset (``abd_surviv
 per dataset with up to 16 of them sharing every launch, and ``draws_summary`` pools them and says how much of the variance lies
 between the datasets.  Per-draw fits of the grouped and period models, and WAIC / PPC of a per-draw fit, are not built.
 
+There is one chain, ``_chain_gen``: a generator over ``sampler.Nuts`` and ``sampler.WindowedAdaptation`` that yields the points it
+needs evaluated.  ``_chain`` (and so ``sample``) drives it against a callable; ``sample_draws`` drives many against one batched
+evaluator.  A per-draw fit of another model needs an evaluator of ``(datasets, points)`` and nothing here.
+
 Which titer predicts protection?  ``waic(model, fit)`` scores a fitted model by WAIC over the individuals -- the device gives every
 individual's log-likelihood at every draw and keeps the running statistics (``abd_survival_individual_loglik``,
 ``abd_survival_waic_*``) -- and ``compare({"S": fit_s, "N": fit_n, ...})`` ranks the fits of one cohort and window
@@ -47,7 +51,7 @@ import numpy as np
 
 from . import compare as _compare
 from . import risk
-from .sampler import DualAveraging, Nuts
+from .sampler import Nuts, WindowedAdaptation, drive
 from .summaries import interval
 
 _interval_of_draws = interval  # ``protection`` has an argument called ``interval``
@@ -512,37 +516,26 @@ class SurvivalAnalysis:
         return model
 
 
-def _chain(fn: Callable, dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8,
-           q0: Optional[np.ndarray] = None, adapt: bool = True, step_size: Optional[float] = None):
-    """One chain of ``sampler.Nuts`` on ``fn(q) -> (logp, grad)`` with ``sampler.sample_chain``'s adaptation: start jitter U(-1, 1),
-    ``find_reasonable_eps``, dual averaging, variances of the tuning draws in expanding windows.  ``adapt=False`` keeps the unit
-    metric and ``step_size`` (tests).  Returns (draws (draws, dim), stats)."""
+def _chain_gen(dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8, q0: Optional[np.ndarray] = None,
+               adapt: bool = True, step_size: Optional[float] = None):
+    """One chain of ``sampler.Nuts`` with ``sampler.WindowedAdaptation`` (what ``sampler.sample_chain`` tunes with), from ``q0`` (the
+    origin by default) plus a start jitter U(-1, 1), as a generator: it yields every point it needs evaluated, is sent ``(logp, grad)``
+    for it, and returns (draws (draws, dim), stats).  ``adapt=False`` keeps the unit metric and ``step_size`` (tests)."""
     q = (np.zeros(dim) if q0 is None else np.asarray(q0, dtype=np.float64)) + rng.uniform(-1, 1, size=dim)
-    nuts = Nuts(fn, dim, rng, target_accept=target_accept)
-    lp, g = fn(q)
+    nuts = Nuts(None, dim, rng, target_accept=target_accept)
+    adaptation = WindowedAdaptation(nuts, tune, target=target_accept)
+    lp, g = yield q
     if adapt:
-        nuts.eps = nuts.find_reasonable_eps(q, lp, g)
-        nuts.da = DualAveraging(nuts.eps, target=target_accept)
+        yield from adaptation.restart(q, lp, g)
     else:
         nuts.eps = float(step_size)
     out = np.empty((draws, dim))
     stats = {k: np.empty(draws) for k in ("lp", "tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging")}
-    window_start, window_len = max(10, tune // 10), max(20, tune // 8)
-    window = []
     for it in range(tune + draws):
         tuning = it < tune
-        q, lp, g, st = nuts.step(q, lp, g, adapt=tuning and adapt)
+        q, lp, g, st = yield from nuts.step_gen(q, lp, g, adapt=tuning and adapt)
         if tuning and adapt:
-            if it >= window_start:
-                window.append(q.copy())
-            if len(window) >= window_len and it < tune - 20:
-                var = np.var(np.asarray(window), axis=0)
-                nuts.inv_mass = (len(window) / (len(window) + 5.0)) * var + 1e-3 * (5.0 / (len(window) + 5.0))
-                window, window_len = [], int(window_len * 1.5)
-                nuts.eps = nuts.find_reasonable_eps(q, lp, g)
-                nuts.da = DualAveraging(nuts.eps, target=target_accept)
-            if it == tune - 1:
-                nuts.eps = nuts.da.final()
+            yield from adaptation.update(it, q, lp, g)
         elif not tuning:
             k = it - tune
             out[k] = q
@@ -550,6 +543,24 @@ def _chain(fn: Callable, dim: int, tune: int, draws: int, rng: np.random.Generat
             for name in ("tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging"):
                 stats[name][k] = st[name]
     return out, stats
+
+
+def _chain(fn: Callable, dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8,
+           q0: Optional[np.ndarray] = None, adapt: bool = True, step_size: Optional[float] = None):
+    """``_chain_gen`` driven against ``fn(q) -> (logp, grad)``.  Returns (draws (draws, dim), stats)."""
+    return drive(_chain_gen(dim, tune, draws, rng, target_accept, q0, adapt, step_size), fn)
+
+
+def _fit_arrays(model, per_chain) -> Dict[str, np.ndarray]:
+    """What ``sample`` and ``sample_draws`` make of their chains' (draws, stats): the unconstrained entries under ``model.names``,
+    the constrained ones, ``stat_*`` and ``antigens``, each with the chains on the leading axis."""
+    q = np.stack([p[0] for p in per_chain])
+    res = {name: q[:, :, k].copy() for k, name in enumerate(model.names)}
+    res.update(model.constrain(q) if hasattr(model, "constrain") else constrain(q, model.K))
+    for name in per_chain[0][1]:
+        res["stat_" + name] = np.stack([p[1][name] for p in per_chain])
+    res["antigens"] = np.array(getattr(model, "antigens", ("S", "N")[:model.K]))
+    return res
 
 
 def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: int = 0, target_accept: float = 0.8,
@@ -560,15 +571,8 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
     fit also holds ``groups`` and ``group_name``, or ``periods``, ``period_name`` and ``period_index``, where the model has them.
     ``evaluator``: a callable ``q -> (logp, grad)`` in place of the device (tests)."""
     fn = evaluator if evaluator is not None else model.logp_dlogp
-    dim, K = model.dim, model.K
     q0 = _initial_point(model)
-    per_chain =[_chain(fn, dim, tune, draws, np.random.default_rng([seed, c]), target_accept, q0) for c in range(chains)]
-    q = np.stack([p[0] for p in per_chain])
-    res = {name: q[:, :, k].copy() for k, name in enumerate(model.names)}
-    res.update(model.constrain(q) if hasattr(model, "constrain") else constrain(q, K))
-    for name in per_chain[0][1]:
-        res["stat_" + name] = np.stack([p[1][name] for p in per_chain])
-    res["antigens"] = np.array(getattr(model, "antigens", ("S", "N")[:K]))
+    res = _fit_arrays(model, [_chain(fn, model.dim, tune, draws, np.random.default_rng([seed, c]), target_accept, q0) for c in range(chains)])
     if hasattr(model, "groups"):
         res["groups"] = np.asarray(model.groups)
         res["group_name"] = np.array(getattr(model, "group_name", "group"))
@@ -590,44 +594,6 @@ def _initial_point(model) -> np.ndarray:
     return q0
 
 
-def _chain_gen(dim: int, tune: int, draws: int, rng: np.random.Generator, target_accept: float = 0.8, q0: Optional[np.ndarray] = None):
-    """``_chain`` (with ``adapt=True``) as a generator on ``sampler.NutsGen``: it yields every point it needs evaluated, is sent
-    ``(logp, grad)`` for it, and returns (draws (draws, dim), stats).  Statement for statement ``_chain``: driven with the values
-    ``fn`` would give, it is that chain bit for bit."""
-    from .sampler import NutsGen
-
-    q = (np.zeros(dim) if q0 is None else np.asarray(q0, dtype=np.float64)) + rng.uniform(-1, 1, size=dim)
-    nuts = NutsGen(dim, rng, target_accept=target_accept)
-    lp, g = yield q
-    nuts.eps = yield from nuts.find_reasonable_eps(q, lp, g)
-    nuts.da = DualAveraging(nuts.eps, target=target_accept)
-    out = np.empty((draws, dim))
-    stats = {k: np.empty(draws) for k in ("lp", "tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging")}
-    window_start, window_len = max(10, tune // 10), max(20, tune // 8)
-    window = []
-    for it in range(tune + draws):
-        tuning = it < tune
-        q, lp, g, st = yield from nuts.step(q, lp, g, adapt=tuning)
-        if tuning:
-            if it >= window_start:
-                window.append(q.copy())
-            if len(window) >= window_len and it < tune - 20:
-                var = np.var(np.asarray(window), axis=0)
-                nuts.inv_mass = (len(window) / (len(window) + 5.0)) * var + 1e-3 * (5.0 / (len(window) + 5.0))
-                window, window_len = [], int(window_len * 1.5)
-                nuts.eps = yield from nuts.find_reasonable_eps(q, lp, g)
-                nuts.da = DualAveraging(nuts.eps, target=target_accept)
-            if it == tune - 1:
-                nuts.eps = nuts.da.final()
-        else:
-            k = it - tune
-            out[k] = q
-            stats["lp"][k] = lp
-            for name in ("tree_depth", "mean_tree_accept", "step_size", "n_steps", "diverging"):
-                stats[name][k] = st[name]
-    return out, stats
-
-
 MAX_BATCH = 16  # ABD_MAX_BATCH: the points of one launch, and the chains ``sample_draws`` keeps in flight
 
 
@@ -644,7 +610,7 @@ def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset:
     where the model has it, ``n_evaluations`` and ``n_calls``.
     ``evaluator``: a callable ``(datasets (n,), q (n, D)) -> (logp (n,), grad (n, D))`` in place of the device (tests)."""
     fn = evaluator if evaluator is not None else model.logp_dlogp
-    dim, K, M, c = model.dim, model.K, int(model.n_datasets), int(chains_per_dataset)
+    dim, M, c = model.dim, int(model.n_datasets), int(chains_per_dataset)
     if M < 1 or c < 1:
         raise ValueError(f"at least one dataset and one chain per dataset, got {M} and {c}")
     q0 = _initial_point(model)
@@ -679,12 +645,7 @@ def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset:
             del flight[i]
         for _ in done:
             start()
-    q = np.stack([p[0] for p in per_chain])
-    res = {name: q[:, :, k].copy() for k, name in enumerate(model.names)}
-    res.update(model.constrain(q) if hasattr(model, "constrain") else constrain(q, K))
-    for name in per_chain[0][1]:
-        res["stat_" + name] = np.stack([p[1][name] for p in per_chain])
-    res["antigens"] = np.array(getattr(model, "antigens", ("S", "N")[:K]))
+    res = _fit_arrays(model, per_chain)
     res["dataset"] = np.array([m for m, _ in jobs], dtype=np.int64)
     if hasattr(model, "source"):
         res["source"] = np.asarray(model.source, dtype=np.int64)
