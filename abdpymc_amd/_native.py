@@ -237,6 +237,12 @@ SYMBOLS = {
     "abd_survival_waic_reset": (C.c_int, [_P]),
     "abd_survival_waic_accumulate": (C.c_int, [_P, C.c_int32, _D]),
     "abd_survival_waic_stats": (C.c_int, [_P, _D, _D, _D, C.POINTER(C.c_int64), _I32]),
+    "abd_survival_loo_reserve": (C.c_int, [_P, C.c_int64]),
+    "abd_survival_loo_reset": (C.c_int, [_P]),
+    "abd_survival_loo_accumulate": (C.c_int, [_P, C.c_int32, _D]),
+    "abd_survival_loo_append_rows": (C.c_int, [_P, C.c_int32, _D]),
+    "abd_survival_loo_rows": (C.c_int, [_P, C.c_int64, C.c_int64, _D]),
+    "abd_survival_loo_stats": (C.c_int, [_P, _D, _D, _D, _I32, C.POINTER(C.c_int64), _I32]),
     "abd_survival_predictive_configure": (C.c_int, [_P, C.c_int32, _P, _I32, _P, C.c_uint64]),
     "abd_survival_predictive_reset": (C.c_int, [_P]),
     "abd_survival_predictive_accumulate": (C.c_int, [_P, C.c_int32, _D, _D, _P]),
@@ -1196,6 +1202,43 @@ class Survival(_SurvivalHandle):
         n = C.c_int64()
         _check(self._lib, self._lib.abd_survival_waic_stats(self._h, _ptr(lse), _ptr(mean), _ptr(m2), C.byref(n), _ptr(cells, C.c_int32)))
         return (lse, mean, m2, int(n.value)), cells.astype(np.int64)
+
+    LOO_MAX_DRAWS = 16384  # ABD_SURVIVAL_LOO_MAX_DRAWS
+
+    def loo_reserve(self, capacity: int):
+        """Room on the device for ``capacity`` draws of the per-individual log-likelihood (PSIS-LOO); 0 releases it."""
+        _check(self._lib, self._lib.abd_survival_loo_reserve(self._h, int(capacity)))
+
+    def loo_reset(self):
+        _check(self._lib, self._lib.abd_survival_loo_reset(self._h))
+
+    def loo_accumulate(self, theta):
+        """Evaluates the draws ``theta`` (n, D) and stores their rows, in order, in the matrix ``loo_reserve`` made room for."""
+        t = self._points(theta)
+        _check(self._lib, self._lib.abd_survival_loo_accumulate(self._h, t.shape[0], _ptr(t)))
+
+    def loo_append_rows(self, ll):
+        """Stores the host rows ``ll`` (n, N), in the caller's order of individuals, in the place of evaluated ones."""
+        r = _as(ll, np.float64)
+        if r.ndim != 2 or r.shape[1] != self.n_inds:
+            raise ValueError(f"ll must have shape (n, {self.n_inds}), got {r.shape}")
+        _check(self._lib, self._lib.abd_survival_loo_append_rows(self._h, r.shape[0], _ptr(r)))
+
+    def loo_rows(self, first: int, count: int):
+        """(count, N): the stored draws ``first .. first + count - 1``."""
+        out = np.empty((max(int(count), 0), self.n_inds))
+        _check(self._lib, self._lib.abd_survival_loo_rows(self._h, int(first), int(count), _ptr(out)))
+        return out
+
+    def loo_stats(self):
+        """(elpd_loo, pareto_k, lppd (N,), n_tail (N,) int64, n_draws, n_cells (N,) int64) of the draws held."""
+        N = self.n_inds
+        elpd, k, lppd = np.empty(N), np.empty(N), np.empty(N)
+        tail, cells = np.empty(N, np.int32), np.empty(N, np.int32)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_survival_loo_stats(self._h, _ptr(elpd), _ptr(k), _ptr(lppd), _ptr(tail, C.c_int32), C.byref(n),
+                                                           _ptr(cells, C.c_int32)))
+        return elpd, k, lppd, tail.astype(np.int64), int(n.value), cells.astype(np.int64)
 
     def predictive_configure(self, titers, edges, seed: int = 0):
         """The binning variables of the posterior predictive checks: one or two titer arrays (N, T) with their edges (each up to 7,

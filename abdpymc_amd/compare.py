@@ -222,6 +222,98 @@ def compare(results: Mapping[str, Mapping[str, np.ndarray]], by=None) -> Dict[st
     return out
 
 
+# ---- PSIS-LOO over the columns of a resident matrix: the host path of ``survival.loo`` ----
+
+WARN_PARETO_K = 0.7
+
+
+def _logsumexp(v: np.ndarray) -> float:
+    m = v.max()
+    return float(m + np.log(np.exp(v - m).sum()))
+
+
+def psis_tail_len(S: int) -> int:
+    """M, the most draws the tail of S draws holds: min(S // 5, ceil(3 sqrt(S)))."""
+    return min(int(S) // 5, int(np.ceil(3.0 * np.sqrt(float(S)))))
+
+
+def pareto_k_threshold(S: int) -> float:
+    """min(1 - 1 / log10(S), 0.7): the k above which S draws are too few for the estimate (Vehtari et al. 2024)."""
+    return min(1.0 - 1.0 / np.log10(S), WARN_PARETO_K) if S > 1 else -np.inf
+
+
+def _psis_column(ll: np.ndarray):
+    """One column (S,) in draw order -> (elpd_loo, pareto_k, lppd, n_tail): DESIGN.md §27, step by step."""
+    S = ll.size
+    a = -ll
+    x = a - a.max()
+    M = psis_tail_len(S)
+    cut = max(np.partition(x, S - M - 1)[S - M - 1], np.log(np.finfo(np.float64).tiny))  # the (M + 1)-th largest, clipped
+    tail = np.flatnonzero(x > cut)
+    n = tail.size
+    k = np.inf
+    if n > 4:
+        order = tail[np.argsort(x[tail], kind="stable")]  # ascending, ties in draw order
+        ecut = np.exp(cut)
+        t = np.exp(x[order]) - ecut
+        m = 30 + int(np.floor(np.sqrt(n)))
+        j = np.arange(1, m + 1, dtype=np.float64)
+        b = (1.0 - np.sqrt(m / (j - 0.5))) / (3.0 * t[int(n / 4 + 0.5) - 1]) + 1.0 / t[-1]
+        kj = np.log1p(-b[:, None] * t[None, :]).mean(axis=1)
+        L = n * (np.log(-b / kj) - kj - 1.0)
+        w = 1.0 / np.exp(L[None, :] - L[:, None]).sum(axis=1)
+        b_hat = float((b * w).sum())
+        k_raw = float(np.log1p(-b_hat * t).mean())
+        sigma = -k_raw / b_hat
+        k = (n * k_raw + 5.0) / (n + 10.0)
+        lp = np.log1p(-(np.arange(n) + 0.5) / n)
+        q = -sigma * lp if k == 0.0 else sigma * np.expm1(-k * lp) / k
+        x = x.copy()
+        x[order] = np.minimum(np.log(q + ecut), 0.0)
+    lw = x - _logsumexp(x)
+    return _logsumexp(ll + lw), k, _logsumexp(ll) - np.log(S), n
+
+
+def psis_loo_from_matrix(ll, n_cells=None):
+    """(draws, N) per-unit log-likelihood, the draws of all chains pooled -> (elpd_i, pareto_k_i, lppd_i, n_tail_i), each (N,):
+    Pareto-smoothed importance sampling leave-one-out of every column with r_eff = 1 (DESIGN.md §27, which defines every step;
+    the device computes the same in ``abd_psis_kernel``).  ``pareto_k_i`` is +inf where the tail has at most 4 draws.
+    ``n_cells`` (N,): a unit with 0 is left out -- elpd = lppd = 0, k = NaN, n_tail = 0; default: the units whose column is
+    exactly 0 throughout, which is what a survival model gives an individual without a followed cell."""
+    ll = np.asarray(ll, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1:
+        raise ValueError(f"ll must be (draws, units) with at least one draw, got shape {ll.shape}")
+    N = ll.shape[1]
+    out = np.all(ll == 0.0, axis=0) if n_cells is None else np.asarray(n_cells).reshape(-1) == 0
+    elpd, k, lppd, n_tail = np.zeros(N), np.full(N, np.nan), np.zeros(N), np.zeros(N, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for j in np.flatnonzero(~out):
+            elpd[j], k[j], lppd[j], n_tail[j] = _psis_column(np.ascontiguousarray(ll[:, j]))
+    return elpd, k, lppd, n_tail
+
+
+def loo_from_individual(elpd_i, pareto_k_i, lppd_i, n_cells, n_draws: int) -> Dict[str, object]:
+    """PSIS-LOO by individual from the per-individual values: ``elpd_loo``, ``p_loo`` = sum(lppd_i - elpd_i), ``se`` =
+    sqrt(n Var_j(elpd_j)) (ddof 0) over the ``n_individuals`` with a followed cell, ``n_draws``; ``n_bad`` = the individuals with
+    k > 0.7 and ``n_warn`` = those above ``k_threshold`` = min(1 - 1 / log10(S), 0.7); ``worst`` = the individual with the
+    largest k (None without one); the arrays ``elpd_i``, ``p_loo_i``, ``pareto_k``, ``lppd_i`` and ``n_readings_i`` (the followed
+    cells).  An individual without a followed cell enters no sum and no count, as in ``waic_from_individual_stats``."""
+    elpd_i, lppd_i = np.asarray(elpd_i, dtype=np.float64), np.asarray(lppd_i, dtype=np.float64)
+    k_i, n_cells = np.asarray(pareto_k_i, dtype=np.float64), np.asarray(n_cells, dtype=np.int64)
+    if n_draws < 1:
+        raise ValueError("no draws")
+    has = n_cells > 0
+    elpd_i, lppd_i = np.where(has, elpd_i, 0.0), np.where(has, lppd_i, 0.0)
+    p_loo_i = lppd_i - elpd_i
+    m = int(has.sum())
+    thr = pareto_k_threshold(int(n_draws))
+    kk = np.where(has, k_i, -np.inf)
+    return dict(elpd_loo=float(elpd_i.sum()), p_loo=float(p_loo_i.sum()), se=float(np.sqrt(m * np.var(elpd_i[has]))) if m else 0.0,
+                elpd_i=elpd_i, p_loo_i=p_loo_i, pareto_k=np.where(has, k_i, np.nan), lppd_i=lppd_i, n_bad=int((kk > WARN_PARETO_K).sum()),
+                n_warn=int((kk > thr).sum()), k_threshold=float(thr), worst=int(np.argmax(kk)) if m else None, n_draws=int(n_draws),
+                n_readings=int(n_cells.sum()), n_individuals=m, n_readings_i=n_cells)
+
+
 class _Waic(Summary):
     """``waic``: accumulate the per-reading statistics of the pointwise log-likelihood over ALL draws on the device (any cohort
     size) and return them as ``waic_lse`` / ``waic_mean`` / ``waic_m2`` (chains, K_s + K_n; S readings first), ``waic_n_draws``

@@ -1,6 +1,6 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
-// handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, the
-// posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
+// handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, PSIS-LOO
+// over the resident matrix of those rows (abd_survival_loo_*; abd_psis.hpp), the posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
 // per-draw datasets, a handle of its own kind (abd_survival_draws_*; abd_survival_draws.hpp).  Both kinds run their
 // sums launches on one SurvivalSums.  A handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp,
 // abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the
@@ -9,6 +9,7 @@
 #include <memory>
 
 #include "abd_host.hpp"
+#include "abd_psis.hpp"
 #include "abd_survival.hpp"
 #include "abd_survival_draws.hpp"
 #include "abd_survival_groups.hpp"
@@ -104,6 +105,12 @@ struct abd_survival : SurvivalSpec {
   DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
   MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
   int64_t waic_n = 0;              // draws folded into d_acc
+  // PSIS-LOO by individual (abd_psis.hpp): the matrix of the draws' rows, unit = slot
+  DevBuf<double> d_loo, d_loo_out;  // [ld][loo_cap]; [3][ld]: elpd_loo, pareto k, lppd
+  DevBuf<int32_t> d_loo_cells, d_loo_tail;  // [ld] the followed cells per slot (0: padding); [ld] n_tail
+  MappedBuf<double> h_loo_out;      // pinned
+  MappedBuf<int32_t> h_loo_tail;
+  int64_t loo_cap = 0, loo_n = 0;   // the draws the matrix holds room for, and those it holds
   // the posterior predictive checks (abd_survival_predictive.hpp)
   int pp_nvar = 0;                 // binning variables of the configuration; 0: abd_survival_predictive_configure has not run
   uint32_t pp_seed_lo = 0, pp_seed_hi = 0;
@@ -226,9 +233,29 @@ int survival_pointwise_ensure(abd_survival* s) {
   return ABD_OK;
 }
 
-// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll.  fold: the rows go into the accumulators as draws waic_n + 1 ..
-// waic_n + n; else they are copied to s->h_ll.
-int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool fold) {
+// the rows of s->d_ll [n][ld] into the LOO matrix as draws loo_n .. loo_n + n - 1, queued on the stream (abd_psis.hpp)
+int survival_loo_store(abd_survival* s, int n) {
+  HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_ll, (double*)s->d_loo,
+                        (int32_t)s->sums.ld, (int64_t)s->loo_cap, (int32_t)n, (int64_t)s->loo_n));
+  return ABD_OK;
+}
+
+// what abd_survival_loo_accumulate and _append_rows check before anything is stored
+int survival_loo_room(const abd_survival* s, int32_t n) {
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  if (s->loo_cap < 1) return fail(ABD_ERR_STATE, "no matrix reserved (abd_survival_loo_reserve comes first)");
+  if (s->loo_n + n > s->loo_cap)
+    return fail(ABD_ERR_STATE, "%lld draws held and %d more would pass the capacity of %lld", (long long)s->loo_n, n, (long long)s->loo_cap);
+  return ABD_OK;
+}
+
+// where the rows of a pointwise launch go: copied to s->h_ll; folded into the WAIC accumulators as draws waic_n + 1 .. waic_n + n;
+// or stored in the LOO matrix as draws loo_n .. loo_n + n - 1
+enum class PointRows { Copy, Fold, Store };
+
+// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll, and on to `to`
+int survival_pointwise_launch(abd_survival* s, int n, const double* theta, PointRows to) {
+  const bool fold = to == PointRows::Fold;
   if (int rc = survival_pointwise_ensure(s)) return rc;
   const int T = s->form.T, n_ab = s->form.n_ab(), stride = s->form.par_stride();
   survival_prepare_points(s, n, theta);
@@ -260,11 +287,14 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, bool 
     HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_ll,
                           (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->sums.ld, (int32_t)s->pw_stride,
                           (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
+  } else if (to == PointRows::Store) {
+    if (int rc = survival_loo_store(s, n)) return rc;
   } else {
     HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->sums.ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
   }
   HIP_TRY(hipStreamSynchronize(s->sums.stream));
   if (fold) s->waic_n += n;
+  if (to == PointRows::Store) s->loo_n += n;
   return ABD_OK;
 }
 
@@ -517,7 +547,7 @@ int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* the
   HIP_TRY(hipSetDevice(s->sums.device));
   const size_t D = (size_t)s->form.dim();
   return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
-    if (int rc = survival_pointwise_launch(s, nb, theta + k0 * D, false)) return rc;
+    if (int rc = survival_pointwise_launch(s, nb, theta + k0 * D, PointRows::Copy)) return rc;
     for (int q = 0; q < nb; ++q) {  // slots to the caller's order
       const double* row = s->h_ll.host() + (size_t)q * s->sums.ld;
       double* out = ll + ((size_t)k0 + q) * s->N;
@@ -538,7 +568,7 @@ int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
   HIP_TRY(hipSetDevice(s->sums.device));
   return survival_batches(n, ABD_MAX_BATCH,
-                          [&](int k0, int nb) { return survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->form.dim(), true); });
+                          [&](int k0, int nb) { return survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->form.dim(), PointRows::Fold); });
 }
 
 int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
@@ -558,6 +588,129 @@ int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* 
     n_cells[j] = s->n_cells[j];
   }
   *n_draws = s->waic_n;
+  return ABD_OK;
+}
+
+// ---- PSIS-LOO by individual (abd_psis.hpp) ----
+
+int abd_survival_loo_reserve(abd_survival* s, int64_t capacity) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  if (capacity < 0 || capacity > ABD_SURVIVAL_LOO_MAX_DRAWS)
+    return fail(ABD_ERR_ARG, "capacity=%lld outside [0, %d]", (long long)capacity, ABD_SURVIVAL_LOO_MAX_DRAWS);
+  static_assert(ABD_SURVIVAL_LOO_MAX_DRAWS == kPsisMaxDraws, "header / kernel draw cap mismatch");
+  HIP_TRY(hipSetDevice(s->sums.device));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
+  s->d_loo.reset();
+  s->loo_cap = s->loo_n = 0;
+  if (capacity == 0) return ABD_OK;
+  const size_t ld = (size_t)s->sums.ld;
+  if (s->d_loo.alloc(ld * (size_t)capacity) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "the device cannot hold %zu bytes for %lld draws of %zu slots", ld * (size_t)capacity * sizeof(double), (long long)capacity, ld);
+  }
+  if (!s->d_loo_cells) {  // the followed cells per slot; the padding has none
+    std::vector<int32_t> cells(ld, 0);
+    for (int j = 0; j < s->N; ++j) cells[(size_t)s->column(j)] = s->n_cells[j];
+    HIP_TRY(s->d_loo_cells.upload(cells.data(), ld));
+    HIP_TRY(s->d_loo_out.alloc(3 * ld));
+    HIP_TRY(s->d_loo_tail.alloc(ld));
+    HIP_TRY(s->h_loo_out.alloc_pinned(3 * ld));
+    HIP_TRY(s->h_loo_tail.alloc_pinned(ld));
+  }
+  s->loo_cap = capacity;
+  return ABD_OK;
+}
+
+int abd_survival_loo_reset(abd_survival* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  s->loo_n = 0;  // the rows are overwritten
+  return ABD_OK;
+}
+
+int abd_survival_loo_accumulate(abd_survival* s, int32_t n, const double* theta) {
+  if (!s || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_loo_room(s, n)) return rc;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  return survival_batches(n, ABD_MAX_BATCH,
+                          [&](int k0, int nb) { return survival_pointwise_launch(s, nb, theta + (size_t)k0 * s->form.dim(), PointRows::Store); });
+}
+
+int abd_survival_loo_append_rows(abd_survival* s, int32_t n, const double* ll) {
+  if (!s || !ll) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_loo_room(s, n)) return rc;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  if (int rc = survival_pointwise_ensure(s)) return rc;
+  const size_t ld = (size_t)s->sums.ld;
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
+    std::memset(s->h_ll.host(), 0, (size_t)nb * ld * sizeof(double));  // the padding holds 0
+    for (int q = 0; q < nb; ++q) {  // the caller's order to slots
+      const double* in = ll + ((size_t)k0 + q) * s->N;
+      double* row = s->h_ll.host() + (size_t)q * ld;
+      for (int j = 0; j < s->N; ++j) row[s->column(j)] = in[j];
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_ll, s->h_ll.host(), (size_t)nb * ld * sizeof(double), hipMemcpyHostToDevice, s->sums.stream));
+    if (int rc = survival_loo_store(s, nb)) return rc;
+    HIP_TRY(hipStreamSynchronize(s->sums.stream));
+    s->loo_n += nb;
+    return (int)ABD_OK;
+  });
+}
+
+int abd_survival_loo_rows(abd_survival* s, int64_t first, int64_t count, double* ll) {
+  if (!s || !ll) return fail(ABD_ERR_ARG, "NULL argument");
+  if (first < 0 || count < 0 || first + count > s->loo_n)
+    return fail(ABD_ERR_ARG, "rows [%lld, %lld) outside the %lld draws held", (long long)first, (long long)(first + count), (long long)s->loo_n);
+  if (count == 0) return ABD_OK;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld;
+  try {
+    std::vector<double> buf(ld * (size_t)count);  // [ld][count]
+    HIP_TRY(hipStreamSynchronize(s->sums.stream));
+    HIP_TRY(hipMemcpy2D(buf.data(), (size_t)count * sizeof(double), (const double*)s->d_loo + first, (size_t)s->loo_cap * sizeof(double),
+                        (size_t)count * sizeof(double), ld, hipMemcpyDeviceToHost));
+    for (int j = 0; j < s->N; ++j) {
+      const double* col = buf.data() + (size_t)s->column(j) * count;
+      for (int64_t p = 0; p < count; ++p) ll[(size_t)p * s->N + j] = col[p];
+    }
+  } catch (const std::bad_alloc&) {
+    return fail(ABD_ERR_NOMEM, "out of host memory for %lld x %zu values", (long long)count, ld);
+  }
+  return ABD_OK;
+}
+
+int abd_survival_loo_stats(abd_survival* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws, int32_t* n_cells) {
+  if (!s || !elpd_loo || !pareto_k || !lppd || !n_tail || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
+  if (s->loo_n < 1) return fail(ABD_ERR_ARG, "no draws held (abd_survival_loo_accumulate or abd_survival_loo_append_rows comes first)");
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld;
+  PsisArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.mat = s->d_loo;
+  a.n_cells = s->d_loo_cells;
+  a.elpd = s->d_loo_out;
+  a.pareto_k = s->d_loo_out + ld;
+  a.lppd = s->d_loo_out + 2 * ld;
+  a.n_tail = s->d_loo_tail;
+  a.capacity = s->loo_cap;
+  a.S = (int32_t)s->loo_n;
+  a.M = psis_tail_len(s->loo_n);
+  a.log_S = std::log((double)s->loo_n);
+  a.log_tiny = std::log(std::numeric_limits<double>::min());
+  // the draws a thread holds in registers: the smallest of 1, 4, 16, 64 with S <= 256 VPT
+  void (*const kernel)(const PsisArgs) = a.S <= 256 ? abd_psis_kernel<1> : a.S <= 1024 ? abd_psis_kernel<4> : a.S <= 4096 ? abd_psis_kernel<16> : abd_psis_kernel<64>;
+  HIP_TRY(launch_kernel(kernel, dim3((unsigned)ld), dim3(kPsisThreads), 0, s->sums.stream, a));
+  HIP_TRY(hipMemcpyAsync(s->h_loo_out.host(), s->d_loo_out, 3 * ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipMemcpyAsync(s->h_loo_tail.host(), s->d_loo_tail, ld * sizeof(int32_t), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
+  for (int j = 0; j < s->N; ++j) {
+    const size_t c = (size_t)s->column(j);
+    elpd_loo[j] = s->h_loo_out.host()[c];
+    pareto_k[j] = s->h_loo_out.host()[ld + c];
+    lppd[j] = s->h_loo_out.host()[2 * ld + c];
+    n_tail[j] = s->h_loo_tail.host()[c];
+    n_cells[j] = s->n_cells[j];
+  }
+  *n_draws = s->loo_n;
   return ABD_OK;
 }
 

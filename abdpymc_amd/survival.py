@@ -26,9 +26,12 @@ evaluator.  A per-draw fit of another model needs an evaluator of ``(datasets, p
 Which titer predicts protection?  ``waic(model, fit)`` scores a fitted model by WAIC over the individuals -- the device gives every
 individual's log-likelihood at every draw and keeps the running statistics (``abd_survival_individual_loglik``,
 ``abd_survival_waic_*``) -- and ``compare({"S": fit_s, "N": fit_n, ...})`` ranks the fits of one cohort and window
-with paired standard errors (``compare.compare``).
+with paired standard errors (``compare.compare``).  ``loo(model, fit)`` is the better score: PSIS-LOO over the individuals, the
+whole draws x individuals matrix kept and every column Pareto-smoothed on the device (``abd_survival_loo_*``), with a
+Pareto k per individual that says whom the estimate can be trusted for; ``compare(fits, ic="loo")`` ranks by it.
 
-    python -m abdpymc_amd.survival --posterior FILE --ititers_data DIR --start S --end E --model s|n|combined --out FILE [--waic]
+    python -m abdpymc_amd.survival --posterior FILE --ititers_data DIR --start S --end E --model s|n|combined --out FILE [--waic] [--loo]
+    python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz --ic loo
     python -m abdpymc_amd.survival ... --model s_groups|n_groups --groups FILE [--group_name NAME]
     python -m abdpymc_amd.survival ... --model s_periods|n_periods [--periods monthly|splits|FILE] [--split_delta] [--split_omicron]
     python -m abdpymc_amd.survival --compare fit_s.npz fit_n.npz fit_combined.npz
@@ -235,6 +238,29 @@ class _DeviceModel:
     def waic_stats(self):
         """((lse, mean, m2, n_draws), n_cells): ``compare``'s statistics of the draws folded since ``waic_reset``."""
         return self._dev.waic_stats()
+
+    def loo_reserve(self, capacity: int):
+        """Room on the device for ``capacity`` draws of ``individual_loglik`` (at most 16384); 0 releases it."""
+        self._dev.loo_reserve(capacity)
+
+    def loo_reset(self):
+        self._dev.loo_reset()
+
+    def loo_accumulate(self, q):
+        """Evaluates the draws ``q`` (n, D) and stores their rows, in order, in the matrix on the device."""
+        self._dev.loo_accumulate(q)
+
+    def loo_append_rows(self, ll):
+        """Stores host rows (n, N) in the place of evaluated ones."""
+        self._dev.loo_append_rows(ll)
+
+    def loo_rows(self, first: int, count: int):
+        """(count, N): the stored draws ``first .. first + count - 1``."""
+        return self._dev.loo_rows(first, count)
+
+    def loo_stats(self):
+        """(elpd_loo, pareto_k, lppd, n_tail, n_draws, n_cells): PSIS-LOO of every individual over the draws held."""
+        return self._dev.loo_stats()
 
     def predictive_configure(self, titers, edges, seed: int = 0):
         """The binning variables of ``predictive``: one or two titer arrays (N, T), each with up to 7 strictly ascending edges."""
@@ -766,15 +792,75 @@ def waic_of_fit(fit) -> Dict[str, object]:
                 n_draws=int(np.asarray(fit["waic_n_draws"])), n_readings=int(n_cells.sum()), n_individuals=m, n_readings_i=n_cells)
 
 
-def compare(fits) -> Dict[str, Dict[str, float]]:
+# what ``loo`` records in a fit
+LOO_FIT_KEYS = ("elpd_loo_ind", "pareto_k_ind", "lppd_ind", "loo_n_cells", "loo_n_draws")
+
+
+def loo(model, fit, pointwise: Optional[Callable] = None) -> Dict[str, object]:
+    """PSIS-LOO by individual of a fitted survival model over all draws of ``fit``: the device keeps the whole draws x
+    individuals matrix of ``individual_loglik`` (``model.loo_reserve`` / ``loo_accumulate``, the draws chain after chain), smooths
+    every individual's column there (``loo_stats``) and releases it; ``compare.loo_from_individual`` makes the dictionary --
+    ``elpd_loo``, ``p_loo``, ``se``, ``pareto_k`` per individual and the counts of k above 0.7 and above min(1 - 1 / log10(S), 0.7).
+    The entries ``LOO_FIT_KEYS`` (and ``start`` / ``end`` where the model knows its window) are recorded in ``fit``.  A fit of more
+    than 16384 draws is refused.
+    ``pointwise``: a host callable (n, D) -> (n, N) in the device's place, smoothed by ``compare.psis_loo_from_matrix``; the
+    model then needs ``names`` and ``n_cells``."""
+    q = fit_points(model, fit)
+    if pointwise is not None:
+        n_cells, n_draws = np.asarray(model.n_cells, dtype=np.int64), q.shape[0]
+        elpd, k, lppd, _ = _compare.psis_loo_from_matrix(np.asarray(pointwise(q), dtype=np.float64), n_cells)
+    else:
+        model.loo_reserve(q.shape[0])
+        try:
+            model.loo_accumulate(q)
+            elpd, k, lppd, _, n_draws, n_cells = model.loo_stats()
+        finally:
+            model.loo_reserve(0)
+    w = _compare.loo_from_individual(elpd, k, lppd, n_cells, n_draws)
+    fit["elpd_loo_ind"], fit["pareto_k_ind"], fit["lppd_ind"] = w["elpd_i"], w["pareto_k"], w["lppd_i"]
+    fit["loo_n_cells"], fit["loo_n_draws"] = w["n_readings_i"], np.array(w["n_draws"], dtype=np.int64)
+    for key in ("start", "end"):
+        if hasattr(model, key):
+            fit[key] = np.array(getattr(model, key), dtype=np.int64)
+    return w
+
+
+def loo_of_fit(fit) -> Dict[str, object]:
+    """The dictionary of ``loo`` again from the entries it recorded in a fit (or that ``write`` stored)."""
+    lacking = [k for k in LOO_FIT_KEYS if k not in fit]
+    if lacking:
+        raise ValueError(f"no PSIS-LOO in the fit (loo(model, fit), or --loo): {lacking} missing")
+    return _compare.loo_from_individual(fit["elpd_loo_ind"], fit["pareto_k_ind"], fit["lppd_ind"], fit["loo_n_cells"],
+                                        int(np.asarray(fit["loo_n_draws"])))
+
+
+def loo_line(w) -> str:
+    """One line; it ends with a warning that names the worst individual when some k is above 0.7."""
+    line = (f"survival PSIS-LOO: elpd_loo {w['elpd_loo']:.3f}  p_loo {w['p_loo']:.3f}  se {w['se']:.3f}  ({w['n_individuals']} individuals, "
+            f"{w['n_draws']} draws; {w['n_bad']} with pareto_k > 0.7, {w['n_warn']} above {w['k_threshold']:.2f})")
+    if w["n_bad"]:
+        j = w["worst"]
+        line += f"; warning: the estimate is unreliable for them, worst: individual {j} pareto_k {w['pareto_k'][j]:.2f}"
+    return line
+
+
+def compare(fits, ic: str = "waic") -> Dict[str, Dict[str, float]]:
     """Rank fitted survival models of ONE cohort and window by elpd_waic: ``compare.compare`` (rank, elpd_waic, p_waic, se,
     elpd_diff, dse over the followed individuals) of ``{name: fit}``, every fit with the entries of ``waic``.  Fits that differ
     in ``start`` / ``end``, in the number of individuals or in which of them are followed are a ``ValueError`` that names the
-    odd ones out."""
+    odd ones out.
+    ``ic="loo"``: by elpd_loo, every fit with the entries of ``loo``; the rows hold ``elpd_loo`` / ``p_loo`` in the place of
+    ``elpd_waic`` / ``p_waic``, and ``n_warn`` counts the individuals with pareto_k > 0.7."""
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', got {ic!r}")
     w, window = {}, {}
     for name, fit in fits.items():
         try:
-            w[name] = waic_of_fit(fit)
+            if ic == "loo":  # in the terms of ``compare.compare``
+                v = loo_of_fit(fit)
+                w[name] = dict(v, elpd_waic=v["elpd_loo"], p_waic=v["p_loo"], n_warn=v["n_bad"])
+            else:
+                w[name] = waic_of_fit(fit)
         except ValueError as e:
             raise ValueError(f"{name}: {e}") from None
         span = tuple(int(np.asarray(fit[k])) if k in fit else None for k in ("start", "end"))
@@ -787,7 +873,10 @@ def compare(fits) -> Dict[str, Dict[str, float]]:
         raise ValueError("; ".join(f"{name} differs from the others in " + ", ".join(t for t, i in what if window[name][i] != usual[i])
                                    + (f" (start {window[name][0][0]}, end {window[name][0][1]} against {usual[0][0]}, {usual[0][1]})"
                                       if window[name][0] != usual[0] else "") for name in odd))
-    return _compare.compare(w, by="individual")
+    table = _compare.compare(w, by="individual")
+    if ic == "loo":
+        table = {name: {{"elpd_waic": "elpd_loo", "p_waic": "p_loo"}.get(k, k): v for k, v in row.items()} for name, row in table.items()}
+    return table
 
 
 def waic_line(w) -> str:
@@ -798,6 +887,10 @@ def waic_line(w) -> str:
 def compare_lines(table) -> list:
     """One row per model of ``compare``'s table, best first."""
     width = max(len(str(name)) for name in table)
+    if all("elpd_loo" in v for v in table.values()):  # compare(..., ic="loo")
+        return [f"{str(name):<{width}}  rank {v['rank']}  elpd_loo {v['elpd_loo']:.3f}  p_loo {v['p_loo']:.3f}  se {v['se']:.3f}  "
+                f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}  pareto_k > 0.7: {v['n_warn']}"
+                for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
     return [f"{str(name):<{width}}  rank {v['rank']}  elpd_waic {v['elpd_waic']:.3f}  p_waic {v['p_waic']:.3f}  se {v['se']:.3f}  "
             f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}" for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
 
@@ -1120,6 +1213,7 @@ def main(argv=None) -> int:
                                  "the protection at titers 0, 2 and 4, the largest R-hat of a and b.  With --compare: rank fits written with --waic.")
     ap.add_argument("--compare", nargs="+", metavar="FIT", help="Rank these fits of one cohort and window (.npz written with --waic) by WAIC over the "
                     "individuals: one row per model on stdout (rank, elpd_waic, p_waic, se, elpd_diff, dse).  Needs neither a cohort nor a GPU.")
+    ap.add_argument("--ic", choices=("waic", "loo"), help="With --compare: rank by WAIC (the default) or by PSIS-LOO (fits written with --loo).")
     ap.add_argument("--posterior", help="A posterior .npz of abdpymc-infer (mean_i, mean_ab_s_mu, mean_ab_n_mu, or draws).")
     ap.add_argument("--ititers_data", help="The cohort directory the run was made from.")
     ap.add_argument("--start", type=int, help="First gap of the analysis (titers from here).")
@@ -1136,6 +1230,9 @@ def main(argv=None) -> int:
     ap.add_argument("--out", help="Output file (.npz; NetCDF where ArviZ imports and the name does not end in .npz).")
     ap.add_argument("--waic", action="store_true", help="Score the fit by WAIC over the individuals on the device: a second line on stdout, and "
                     "elpd_waic_ind, p_waic_ind, waic_n_cells, waic_n_draws, start, end in the output (what --compare reads).")
+    ap.add_argument("--loo", action="store_true", help="Score the fit by PSIS-LOO over the individuals on the device (at most 16384 draws): a line on "
+                    "stdout after the WAIC line (elpd_loo, p_loo, se, the individuals with Pareto k above 0.7), and elpd_loo_ind, pareto_k_ind, "
+                    "lppd_ind, loo_n_cells, loo_n_draws, start, end in the output (what --compare --ic loo reads).")
     ap.add_argument("--ppc", action="store_true", help="Posterior predictive check on the device: per titer bin the observed infections against the "
                     "expected and replicated ones of every draw; one more line on stdout per binning variable, and the ppc_* entries in the output.")
     ap.add_argument("--ppc_edges_s", help="With --ppc: comma-separated bin edges of the S titer (up to 7, ascending; default: the octiles).")
@@ -1154,7 +1251,9 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=-1)
     args = ap.parse_args(argv)
     if args.compare:
-        return _main_compare(args.compare)
+        return _main_compare(args.compare, args.ic or "waic")
+    if args.ic is not None:
+        ap.error("--ic goes with --compare")
     missing = [f"--{k}" for k in ("posterior", "ititers_data", "start", "end", "out") if getattr(args, k) is None]
     if missing:
         ap.error("the following arguments are required: " + ", ".join(missing))
@@ -1174,6 +1273,8 @@ def main(argv=None) -> int:
             ap.error(f"--per_draw fits --model s | n | combined; per-draw fits of --model {args.model} are not built")
         if args.waic or args.ppc:
             ap.error("--per_draw does not go with --waic / --ppc: WAIC and predictive checks of a per-draw fit are not built")
+        if args.loo:
+            ap.error("--per_draw does not go with --loo: PSIS-LOO of a per-draw fit is not built")
         if args.per_draw < 1 or (args.per_draw_chains is not None and args.per_draw_chains < 1):
             ap.error("--per_draw and --per_draw_chains must be >= 1")
     ppc_edges = {}
@@ -1208,6 +1309,10 @@ def main(argv=None) -> int:
         raise SystemExit(f"survival: {e}")
     res = sample(model, tune=args.tune, draws=args.draws, chains=args.chains, seed=args.seed)
     w = waic(model, res) if args.waic else None
+    try:
+        lo = loo(model, res) if args.loo else None
+    except ValueError as e:  # more draws than the device keeps
+        raise SystemExit(f"survival: {e}")
     try:  # both titers, whatever the model's own predictor is
         ppc = predictive(model, res, {"S": sa.s_titer, "N": sa.n_titer}, edges=ppc_edges,
                          seed=args.seed if args.ppc_seed is None else args.ppc_seed) if args.ppc else None
@@ -1217,6 +1322,8 @@ def main(argv=None) -> int:
     print(report_line(res))  # the one line, on stdout; progress and the file's name go to stderr
     if w is not None:
         print(waic_line(w))  # --waic: and this one
+    if lo is not None:
+        print(loo_line(lo))  # --loo: after it
     if ppc is not None:
         print(predictive_line(ppc))  # --ppc: and one per binning variable
     out = write(res, args.out, sa)
@@ -1242,7 +1349,7 @@ def _main_per_draw(args, sa) -> int:
     return 0
 
 
-def _main_compare(paths) -> int:
+def _main_compare(paths, ic: str = "waic") -> int:
     import os
 
     fits = {}
@@ -1251,9 +1358,9 @@ def _main_compare(paths) -> int:
         if name in fits:
             raise SystemExit(f"survival: two fits are called {name}")
         with np.load(path, allow_pickle=False) as f:
-            fits[name] = {k: f[k] for k in WAIC_FIT_KEYS + ("start", "end") if k in f.files}
+            fits[name] = {k: f[k] for k in WAIC_FIT_KEYS + LOO_FIT_KEYS + ("start", "end") if k in f.files}
     try:
-        table = compare(fits)
+        table = compare(fits, ic=ic)
     except ValueError as e:
         raise SystemExit(f"survival: {e}")
     for line in compare_lines(table):
@@ -1264,12 +1371,12 @@ def _main_compare(paths) -> int:
 def write(res, path: str, sa: "SurvivalAnalysis") -> str:
     """``.npz``; NetCDF through ``cli.write_posterior`` where ArviZ imports and the name does not end in ``.npz`` (no test covers
     that branch: ArviZ is optional and the suite does not require it).  A fit that ``waic`` has scored is stored with its
-    ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` and the window ``start`` / ``end`` -- in the ``.npz`` form,
+    ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` (one that ``loo`` has scored with ``LOO_FIT_KEYS``) and the window ``start`` / ``end`` -- in the ``.npz`` form,
     which is what ``--compare`` reads; the NetCDF form holds the draws alone.  Likewise ``groups`` / ``group_name`` and ``periods`` /
     ``period_name`` / ``period_index`` are stored in the ``.npz`` form only: ``protection(group= / period= / interval=)`` needs a fit
     written as ``.npz``.  So are the entries ``PPC_FIT_KEYS`` of a fit that ``predictive`` has checked."""
     path = str(path)
-    if "elpd_waic_ind" in res:
+    if "elpd_waic_ind" in res or "elpd_loo_ind" in res:
         res = dict(res, start=np.array(sa.start, dtype=np.int64), end=np.array(sa.end, dtype=np.int64))
     if not path.endswith(".npz"):
         try:
@@ -1277,7 +1384,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + PPC_FIT_KEYS + DRAWS_FIT_KEYS}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + LOO_FIT_KEYS + PPC_FIT_KEYS + DRAWS_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

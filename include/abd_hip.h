@@ -764,6 +764,30 @@ int abd_survival_waic_reset(abd_survival* s);
 int abd_survival_waic_accumulate(abd_survival* s, int32_t n, const double* theta);
 int abd_survival_waic_stats(abd_survival* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells);
 
+/* PSIS-LOO by individual of a handle of any kind: the whole draws x individuals matrix of ll[.][j] is kept on the
+ * device and every individual's column is Pareto-smoothed there (Vehtari et al. 2024 with r_eff = 1; the tail of
+ * M = min(S / 5, ceil(3 sqrt(S))) draws, Zhang & Stephens' fit with the loo package's priors).
+ * _reserve: room for `capacity` draws, 8 bytes per draw and slot of 64-padded individuals; forgets the draws held; 0 releases.
+ *   ABD_ERR_ARG for a capacity that is negative or above ABD_SURVIVAL_LOO_MAX_DRAWS, ABD_ERR_NOMEM, the message naming the bytes,
+ *   when the device cannot hold them.
+ * _reset: forgets the draws held, keeps the room.
+ * _accumulate: evaluates theta[n][D] (any n) and stores the rows as the next n draws; _append_rows stores the host rows ll[n][N]
+ *   (the caller's order of individuals) in their place.  ABD_ERR_STATE, with nothing stored, when nothing is reserved or the draws
+ *   would pass the capacity.  A stored row is the bits abd_survival_individual_loglik returns.
+ * _rows: the draws first .. first + count - 1 back as ll[count][N]; ABD_ERR_ARG beyond the draws held.
+ * _stats: over the S draws held, in the caller's order of individuals: elpd_loo[N], pareto_k[N] (+inf where the tail has at most 4
+ *   draws), lppd[N] = log mean exp(ll), n_tail[N], the number of draws and n_cells[N]; an individual without a followed cell gets
+ *   elpd_loo = lppd = 0, pareto_k = NaN, n_tail = 0.  The same bits however the draws were split over calls.  Consumes nothing: it
+ *   may be called again after more draws.  ABD_ERR_ARG before any draw. */
+#define ABD_SURVIVAL_LOO_MAX_DRAWS 16384
+int abd_survival_loo_reserve(abd_survival* s, int64_t capacity);
+int abd_survival_loo_reset(abd_survival* s);
+int abd_survival_loo_accumulate(abd_survival* s, int32_t n, const double* theta);
+int abd_survival_loo_append_rows(abd_survival* s, int32_t n, const double* ll);
+int abd_survival_loo_rows(abd_survival* s, int64_t first, int64_t count, double* ll);
+int abd_survival_loo_stats(abd_survival* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws,
+                           int32_t* n_cells);
+
 /* Posterior predictive checks of a handle of any kind.  For draw d and cell (j, t):
  *   mu = exposure[j, t] * lam0[t] * invlogit(eta[j, t]),   r ~ Poisson(mu)
  * where r is a function of (seed, d, the caller's index j, t) alone: Philox4x32-10 with key (seed lo, seed hi) and counter

@@ -13,6 +13,11 @@ handle, alternating, ``--reps`` times; per repeat and at its best, microseconds 
 the combined model, binned by both titers in octiles, beside ``waic_accumulate`` of the same points on the same handle,
 alternating, ``--reps`` times; per repeat and at its best, microseconds per draw of each and the ratio.
 
+``--leg loo`` times PSIS-LOO by individual: reserve + ``loo_accumulate`` + ``loo_stats`` + release of ``--points``
+jittered points of the combined model beside ``waic_accumulate`` + ``waic_stats`` of the same points on the same handle,
+alternating, ``--reps`` times, and ``compare.psis_loo_from_matrix`` on this host over ``--host_columns`` individuals of the same
+matrix, scaled to the cohort.
+
 ``--periods P [P]`` times the model by period in the same way, with P periods of equal length (0: monthly, P = T),
 every P at both sizes, beside the ungrouped K = 1 model on the same data in the same run; ``--fit`` adds the wall time of a
 ``--tune`` + ``--draws`` x 4-chain fit of each of them and of the K = 1 model.
@@ -22,6 +27,7 @@ every P at both sizes, beside the ungrouped K = 1 model on the same data in the 
     python tools/probe_survival.py --periods 3 0 [--fit] [--out FILE]
     python tools/probe_survival.py --leg waic [--points 4000] [--reps 3] [--out FILE]
     python tools/probe_survival.py --leg ppc [--points 4000] [--reps 3] [--out FILE]
+    python tools/probe_survival.py --leg loo [--points 4000] [--reps 5] [--host_columns 500] [--out FILE]
 """
 import argparse
 import json
@@ -201,10 +207,68 @@ def probe_ppc(N, T, points, reps):
     return row
 
 
+def probe_loo(N, T, points, reps, host_columns):
+    """One row: PSIS-LOO of ``points`` draws (reserve, ``loo_accumulate``, ``loo_stats``, release) against ``waic_accumulate`` +
+    ``waic_stats`` of the same draws on one handle of the combined model of ``simulate(N, T)``, alternating; the parts of the LOO
+    on their own; and ``compare.psis_loo_from_matrix`` on this host over the first ``host_columns`` followed individuals of the
+    matrix read back, scaled to all of them (0: all)."""
+    from abdpymc_amd import compare
+
+    y, e, xs = simulate(N, T)
+    model = survival.SurvivalModel(y, e, xs, ("S", "N"))
+    rng = np.random.default_rng(1)
+    q = np.zeros((points, model.dim))
+    q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+    q += rng.uniform(-0.5, 0.5, size=q.shape)
+    row = {"N": N, "T": T, "K": 2, "points": points, "matrix_bytes": 8 * 64 * ((N + 63) // 64) * points, "loo_ms": [], "loo_accumulate_ms": [],
+           "loo_stats_ms": [], "waic_ms": []}
+    model.loo_reserve(64)  # warm up: the buffers of the first call, the code objects
+    model.loo_accumulate(q[:64])
+    model.loo_stats()
+    model.waic_accumulate(q[:64])
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        model.loo_reserve(points)
+        model.loo_accumulate(q)
+        t1 = time.perf_counter()
+        stats = model.loo_stats()
+        t2 = time.perf_counter()
+        model.loo_reserve(0)
+        row["loo_ms"].append(1e3 * (time.perf_counter() - t0))
+        row["loo_accumulate_ms"].append(1e3 * (t1 - t0))
+        row["loo_stats_ms"].append(1e3 * (t2 - t1))
+        model.waic_reset()
+        t0 = time.perf_counter()
+        model.waic_accumulate(q)
+        model.waic_stats()
+        row["waic_ms"].append(1e3 * (time.perf_counter() - t0))
+    model.loo_reserve(points)  # once more, untimed, for the host path's matrix
+    model.loo_accumulate(q)
+    ll = model.loo_rows(0, points)
+    model.close()
+    w = compare.loo_from_individual(stats[0], stats[1], stats[2], stats[5], stats[4])
+    row.update({k: w[k] for k in ("elpd_loo", "p_loo", "se", "n_bad", "n_warn", "n_individuals")})
+    cols = np.flatnonzero(stats[5] > 0)
+    cols = cols[:host_columns] if host_columns else cols
+    t0 = time.perf_counter()
+    host = compare.psis_loo_from_matrix(ll[:, cols])
+    row["host_columns"] = int(cols.size)
+    row["host_ms_all_individuals"] = 1e3 * (time.perf_counter() - t0) * w["n_individuals"] / cols.size
+    row["host_max_gap_elpd"] = float(np.abs(host[0] - stats[0][cols]).max())
+    row["host_max_gap_k"] = float(np.abs(host[1] - stats[1][cols]).max())
+    for k in ("loo_ms", "loo_accumulate_ms", "loo_stats_ms", "waic_ms"):
+        row["best_" + k], row["median_" + k] = min(row[k]), float(np.median(row[k]))
+    row["loo_over_waic"] = row["best_loo_ms"] / row["best_waic_ms"]
+    row["host_over_device_stats"] = row["host_ms_all_individuals"] / row["best_loo_stats_ms"]
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("eval", "waic", "ppc"), default="eval",
-                    help="eval: the evaluator and a fit (the default); waic: scoring a fit; ppc: the posterior predictive check beside the WAIC fold")
+    ap.add_argument("--leg", choices=("eval", "waic", "ppc", "loo"), default="eval",
+                    help="eval: the evaluator and a fit (the default); waic: scoring a fit; ppc: the posterior predictive check beside the WAIC fold; "
+                    "loo: PSIS-LOO beside the WAIC fold and beside the host path")
+    ap.add_argument("--host_columns", type=int, default=500, help="--leg loo: individuals the host path is timed on (0: all)")
     ap.add_argument("--points", type=int, default=4000, help="--leg waic / ppc: draws folded per repeat")
     ap.add_argument("--reps", type=int, default=3, help="--leg waic / ppc: repeats")
     ap.add_argument("--groups", type=int, nargs="+", help="time the model by group with this many groups (one figure, or one per size)")
@@ -223,6 +287,10 @@ def main(argv=None):
     if args.leg == "ppc":
         for N, T in SIZES:
             rows.append(probe_ppc(N, T, args.points, args.reps))
+            print(json.dumps(rows[-1]), flush=True)
+    if args.leg == "loo":
+        for N, T in SIZES:
+            rows.append(probe_loo(N, T, args.points, args.reps, args.host_columns))
             print(json.dumps(rows[-1]), flush=True)
     if args.groups:
         if len(args.groups) not in (1, len(SIZES)):
