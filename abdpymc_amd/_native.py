@@ -207,6 +207,9 @@ SYMBOLS = {
     "abd_sampler_curves": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, _D, _D, C.POINTER(C.c_int64)]),
     "abd_sampler_enable_risk": (C.c_int, [_P, C.c_int64, C.POINTER(_RiskSpec)]),
     "abd_sampler_risk": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_enable_loo": (C.c_int, [_P, C.c_int64, C.c_int32]),
+    "abd_sampler_loo_rows": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, _D, C.POINTER(C.c_int64)]),
+    "abd_sampler_loo_stats": (C.c_int, [_P, _D, _D, _D, _I32, C.POINTER(C.c_int64), _D]),
     "abd_sampler_enable_diagnostics": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "abd_sampler_diagnostics": (C.c_int, [_P, C.c_int32, _D, _D, _D, _D]),
     "abd_sampler_enable_timelines": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]),
@@ -889,6 +892,11 @@ class NativeSampler:
         _check(self._lib, self._lib.abd_sampler_enable_timelines(self._h, int(planned), float(lo_n), float(hi_n), float(lo_s),
                                                                  float(hi_s)))
 
+    def enable_loo(self, draws: int, thin: int = 1):
+        """Keep every individual's joint log-likelihood T_j of draws 0, ``thin``, 2 ``thin``, ... of the ``draws`` per chain on the
+        device for PSIS-LOO by individual (``loo_rows`` / ``loo_stats``); ``draws`` = 0 releases."""
+        _check(self._lib, self._lib.abd_sampler_enable_loo(self._h, int(draws), int(thin)))
+
     def run(self, n_iter: int):
         """Advance all chains by n_iter iterations -> theta (n, n_iter, 17), stats {name: (n, n_iter)}."""
         return self.run_record(n_iter, 0)
@@ -1029,6 +1037,28 @@ class NativeSampler:
         """The infection-risk-by-titer table of every draw of the k-th chain so far (``Context.risk`` per draw) -> (draws, 2, 2, G,
         8) int64."""
         return self._kept_draws(self._lib.abd_sampler_risk, k, ((2, 2, self._ctx.n_gaps, 8), np.int64))[0]
+
+    def loo_rows(self, k: int, first: int = 0, count=None):
+        """Kept rows [first, first + count) of the k-th chain's part of the LOO matrix (``count`` None: all it holds from ``first``)
+        -> (count, n_inds): T_j = ll_s + ll_n of ``Context.individual_loglik`` at those draws."""
+        if count is None:
+            n = C.c_int64()
+            _check(self._lib, self._lib.abd_sampler_loo_rows(self._h, int(k), 0, 0, None, C.byref(n)))
+            count = max(0, n.value - int(first))
+        out = np.empty((int(count), self._ctx.n_inds))
+        _check(self._lib, self._lib.abd_sampler_loo_rows(self._h, int(k), int(first), int(count), _ptr(out, C.c_double), None))
+        return out
+
+    def loo_stats(self):
+        """PSIS-LOO by individual over the kept draws of all chains of a finished run, smoothed on the device -> {"elpd_loo",
+        "pareto_k", "lppd": (n_inds,), "n_tail": (n_inds,) int32, "n_readings": (n_inds,) int64, "n_draws": int}."""
+        N = self._ctx.n_inds
+        elpd, k, lppd = np.empty(N), np.empty(N), np.empty(N)
+        tail, n_readings = np.empty(N, np.int32), np.empty(N, np.int64)
+        n = C.c_int64()
+        _check(self._lib, self._lib.abd_sampler_loo_stats(self._h, _ptr(elpd, C.c_double), _ptr(k, C.c_double), _ptr(lppd, C.c_double),
+                                                          _ptr(tail, C.c_int32), C.byref(n), _out(n_readings, np.int64)))
+        return {"elpd_loo": elpd, "pareto_k": k, "lppd": lppd, "n_tail": tail, "n_readings": n_readings, "n_draws": n.value}
 
     def adaptation(self, k: int):
         """(diagonal of M^-1, step size) of the k-th chain."""

@@ -15,7 +15,7 @@ import time
 
 import numpy as np
 
-from .summaries import registry
+from .summaries import every
 from .timelines import add_summary as add_timelines  # noqa: F401  (what a caller that gathers results itself pools them with)
 
 
@@ -48,7 +48,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--posterior_predictive", help="Record a posterior predictive replicate of every OD reading at the recorded "
                         "(thinned) draws: ArviZ groups posterior_predictive (it_s_lik, it_n_lik), as pm.sample_posterior_predictive, "
                         "and observed_data.", action="store_true")
-    for s in registry():  # the summaries over all draws: each adds its own flags
+    for s in every():  # the summaries over all draws: each adds its own flags
         s.add_arguments(parser)
     return parser
 
@@ -70,7 +70,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
                 "ab_s_waner": ["ind"], "mean_i": ["chain", "gap", "ind"], "mean_ab_n_mu": ["chain", "gap", "ind"],
                 "mean_ab_s_mu": ["chain", "gap", "ind"]}
         skip = ("n_grad_evals", "draw_index", "mean_i", "mean_ab_n_mu", "mean_ab_s_mu")
-        owner = {k: next((s for s in registry() if s.owns(k)), None) for k in res}  # the summary a key belongs to
+        owner = {k: next((s for s in every() if s.owns(k)), None) for k in res}  # the summary a key belongs to
         post = {k: v for k, v in res.items()
                 if not k.startswith(("stat_", "log_likelihood_", "posterior_predictive_", "observed_data_"))
                 and owner[k] is None and k not in skip}
@@ -87,7 +87,7 @@ def write_posterior(res: dict, path: str, coords: dict) -> str:
         pp = {k[len("posterior_predictive_"):]: v for k, v in res.items() if k.startswith("posterior_predictive_")}
         obs = {k[len("observed_data_"):]: v for k, v in res.items() if k.startswith("observed_data_")}
         dims.update({"it_s_lik": ["it_s_lik_dim_0"], "it_n_lik": ["it_n_lik_dim_0"]})
-        for s in registry():
+        for s in every():
             dims.update(s.dims)
         if "draw_index" in res and res["draw_index"].shape[1] != next(iter(stats.values())).shape[1]:
             # --thin: an InferenceData has ONE draw axis, so the file holds the thinned draws of every variable (what
@@ -137,7 +137,7 @@ def main(argv=None) -> int:
         raise SystemExit(f"--thin must be >= 1, got {args.thin}")
     options = {}
     try:
-        for s in registry():  # (refused by every rank alike, before anything is built)
+        for s in every():  # (refused by every rank alike, before anything is built)
             options.update(s.cli_options(args, data, chains, world))
     except SystemExit:
         if dist is not None:
@@ -167,7 +167,7 @@ def main(argv=None) -> int:
         dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else None
         res = distributed.gather_results(res, counts, dist, dev)
     if rank == 0:
-        for s in registry():
+        for s in every():
             if s.on(options):
                 for line in s.report(res, data):
                     print(line, file=sys.stderr)

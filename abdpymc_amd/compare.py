@@ -176,13 +176,23 @@ def waic_from_matrix(ll, n_obs=None, groups=None, n_groups=None) -> Dict[str, ob
     return waic_from_individual_stats(stats_from_matrix(T.reshape(-1, n_groups)), np.bincount(groups, minlength=n_groups))
 
 
-def compare(results: Mapping[str, Mapping[str, np.ndarray]], by=None) -> Dict[str, Dict[str, float]]:
+def compare(results: Mapping[str, Mapping[str, np.ndarray]], by=None, ic: str = "waic") -> Dict[str, Dict[str, float]]:
     """Rank fitted variants of ONE cohort (same readings in the same order) by elpd_waic.  Per variant: ``elpd_waic``,
     ``p_waic``, ``se``, ``elpd_diff`` (best minus this one, >= 0) and its paired standard error
     ``dse = sqrt(K * Var_i(elpd_i^best - elpd_i^this))`` (ddof 0; ``az.compare``'s), ``rank`` (0 = best).
     ``by`` as in ``waic``.  By individual, i runs over the n individuals with a reading: ``dse = sqrt(n * Var_j(elpd_j^best -
     elpd_j^this))``.  Variants that lack the statistics asked for, or that are not all of one kind, are a ``ValueError``
-    that names them."""
+    that names them.
+    ``ic="loo"``: by elpd_loo of PSIS-LOO by individual (``sample(..., loo=True)`` results, or dictionaries of
+    ``loo_from_individual``): ``rank``, ``elpd_loo``, ``p_loo``, ``se``, ``elpd_diff``, ``dse`` over the individuals with readings as
+    above, and ``n_bad``, the individuals with a Pareto k above 0.7.  Variants without ``loo_*`` keys, or whose individuals with
+    readings differ, are a ``ValueError`` that names them."""
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', got {ic!r}")
+    if ic == "loo":
+        if by not in (None, "individual"):
+            raise ValueError(f"LOO is by individual, got by={by!r}")
+        return _compare_loo(results)
     w, lacking = {}, []
     for name, r in results.items():
         if "elpd_i" in r:  # a dictionary of waic / waic_from_*
@@ -312,6 +322,49 @@ def loo_from_individual(elpd_i, pareto_k_i, lppd_i, n_cells, n_draws: int) -> Di
                 elpd_i=elpd_i, p_loo_i=p_loo_i, pareto_k=np.where(has, k_i, np.nan), lppd_i=lppd_i, n_bad=int((kk > WARN_PARETO_K).sum()),
                 n_warn=int((kk > thr).sum()), k_threshold=float(thr), worst=int(np.argmax(kk)) if m else None, n_draws=int(n_draws),
                 n_readings=int(n_cells.sum()), n_individuals=m, n_readings_i=n_cells)
+
+
+LOO_KEYS = ("loo_elpd_i", "loo_pareto_k", "loo_lppd_i", "loo_n_readings", "loo_n_draws")  # what loo_from_result reads
+
+
+def loo_from_result(res: Mapping[str, np.ndarray]) -> Dict[str, object]:
+    """``loo_from_individual`` of the ``loo_*`` keys of a ``sample(..., loo=True)`` result (``loo.loo``)."""
+    missing = [k for k in LOO_KEYS if k not in res]
+    if missing:
+        raise ValueError(f"the result lacks {missing} (sample(..., loo=True))")
+    return loo_from_individual(res["loo_elpd_i"], res["loo_pareto_k"], res["loo_lppd_i"], res["loo_n_readings"],
+                               int(np.asarray(res["loo_n_draws"]).reshape(-1)[0]))
+
+
+def _compare_loo(results) -> Dict[str, Dict[str, float]]:
+    """``compare(..., ic="loo")``"""
+    w, lacking = {}, []
+    for name, r in results.items():
+        if "elpd_loo" in r and "elpd_i" in r:  # a dictionary of loo_from_individual
+            w[name] = r
+            continue
+        try:
+            w[name] = loo_from_result(r)
+        except ValueError:
+            lacking.append(name)
+    if lacking:
+        raise ValueError(f"variants without LOO by individual (loo_* keys): {sorted(lacking)}")
+    has = {name: np.asarray(v["n_readings_i"]) > 0 for name, v in w.items()}
+    kinds = [h.tobytes() + bytes(str(h.size), "ascii") for h in has.values()]
+    usual = max(kinds, key=kinds.count)  # the first of the most frequent
+    odd = sorted(name for name, k in zip(has, kinds) if k != usual)
+    if odd:
+        raise ValueError(f"variants differ from the others in their individuals with readings: {odd}")
+    order = sorted(w, key=lambda k: -w[k]["elpd_loo"])
+    best = w[order[0]]
+    out = {}
+    for rank, name in enumerate(order):
+        v = w[name]
+        diff = (best["elpd_i"] - v["elpd_i"])[has[name]]
+        n = diff.size
+        out[name] = dict(rank=rank, elpd_loo=v["elpd_loo"], p_loo=v["p_loo"], se=v["se"], elpd_diff=float(best["elpd_loo"] - v["elpd_loo"]),
+                         dse=float(np.sqrt(n * np.var(diff))) if n else 0.0, n_bad=v["n_bad"])
+    return out
 
 
 class _Waic(Summary):

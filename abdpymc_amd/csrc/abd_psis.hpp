@@ -19,7 +19,10 @@
 // bits however the matrix was filled.  No atomics.  LDS: 14.6 KiB, static.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <limits>
 
 #include <hip/hip_runtime.h>
 
@@ -48,8 +51,9 @@ struct PsisArgs {
   double log_S, log_tiny;  // log S, log DBL_MIN: the host's
 };
 
-// rows 0 .. n - 1 of ll [n][ld] to the draws n0 .. n0 + n - 1 of mat [ld][capacity]
-__global__ __launch_bounds__(256) void abd_psis_store(const double* ll, double* mat, int32_t ld, int64_t capacity, int32_t n, int64_t n0) {
+// rows 0 .. n - 1 of ll [n][ld] to the draws n0 .. n0 + n - 1 of mat [ld][capacity] (static: the header is compiled into two
+// translation units, and only abd_survival.hip launches this one)
+static __global__ __launch_bounds__(256) void abd_psis_store(const double* ll, double* mat, int32_t ld, int64_t capacity, int32_t n, int64_t n0) {
   const int unit = blockIdx.x * 256 + threadIdx.x;
   if (unit >= ld) return;
   double* row = mat + (int64_t)unit * capacity + n0;
@@ -307,6 +311,32 @@ __global__ __launch_bounds__(256) void abd_psis_kernel(const PsisArgs a) {
     a.pareto_k[unit] = pareto_k;
     a.n_tail[unit] = n;
   }
+}
+
+// The launch over S draws, for every caller alike: the arguments -- out [3][ld]: elpd_loo, pareto k, lppd -- with M, log S and
+// log DBL_MIN from the host, and the kernel: the draws a thread holds in registers are the smallest of 1, 4, 16, 64 with
+// S <= 256 VPT.  One workgroup of kPsisThreads per unit.
+using PsisKernel = void (*)(const PsisArgs);
+struct PsisLaunch {
+  PsisKernel kernel;
+  PsisArgs args;
+};
+inline PsisLaunch psis_launch(const double* mat, const int32_t* n_cells, double* out, int32_t* n_tail, size_t ld, int64_t capacity, int64_t S) {
+  PsisArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.mat = mat;
+  a.n_cells = n_cells;
+  a.elpd = out;
+  a.pareto_k = out + ld;
+  a.lppd = out + 2 * ld;
+  a.n_tail = n_tail;
+  a.capacity = capacity;
+  a.S = (int32_t)S;
+  a.M = psis_tail_len(S);
+  a.log_S = std::log((double)S);
+  a.log_tiny = std::log(std::numeric_limits<double>::min());
+  const PsisKernel k = a.S <= 256 ? abd_psis_kernel<1> : a.S <= 1024 ? abd_psis_kernel<4> : a.S <= 4096 ? abd_psis_kernel<16> : abd_psis_kernel<64>;
+  return {k, a};
 }
 
 }  // namespace abdi

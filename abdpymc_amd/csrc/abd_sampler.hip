@@ -3,6 +3,8 @@
 // [i_raw, ab_s_waner], recording of the Deterministics -- run against the evaluation path without leaving the library.
 #include "abd_sampler.hpp"
 
+#include "abd_loo.hpp"
+
 #include <deque>
 #include <memory>
 
@@ -509,9 +511,10 @@ int queue_draw(RunFrame& f, int j, int64_t k, hipStream_t st) {
   double* acc = (draw && s->d_pw_acc) ? s->d_pw_acc + (size_t)j * 4 * Kt : nullptr;
   if (ll || acc)
     if (int rc = launch_pointwise(c, chain, q, st, ll, acc, iter - s->o.tune + 1)) return rc;
-  // ... and per individual: a draw, accumulation on -- the running statistics of T_j
-  if (draw && s->d_ind_acc)
-    if (int rc = launch_individual_loglik(c, chain, q, st, nullptr, nullptr, s->d_ind_acc + (size_t)j * 4 * N, iter - s->o.tune + 1))
+  // ... and per individual, a draw: one launch for the running statistics of T_j (accumulation on) and the rows of the LOO
+  // matrix (abd_loo.hpp), whose staging goes into the matrix when it is full and at the call's last iteration
+  if (draw && (s->d_ind_acc || s->loo.on()))
+    if (int rc = s->loo.launch(c, j, chain, q, iter - s->o.tune, k + 1 == f.n_iter, s->d_ind_acc ? s->d_ind_acc + (size_t)j * 4 * N : nullptr, st))
       return rc;
   // posterior predictive: the record's replicate row (keyed by seed, the chain's global id and the iteration, so that
   // abd_posterior_predictive reproduces it) and / or -- a draw, accumulation on -- the check statistics
@@ -1001,7 +1004,8 @@ int abd_sampler_run_record(abd_sampler* s, int64_t n_iter, double* theta, double
   const int n = s->n;
   // (before anything is launched or marked as run)
   const int64_t upto = s->it + n_iter - s->o.tune;
-  const struct { const char* what; bool on; int64_t planned; } summaries[4] = {
+  const struct { const char* what; bool on; int64_t planned; } summaries[5] = {
+      {"loo: draws up to %lld pass the planned %lld", s->loo.on(), s->loo.planned()},
       {"curves: draws up to %lld do not fit capacity %lld", s->curves.on(), s->curves.planned()},
       {"diagnostics: draws up to %lld pass the planned %lld", s->diag.on(), s->diag.planned()},
       {"risk: draws up to %lld do not fit capacity %lld", s->risk.on(), s->risk.planned()},

@@ -74,6 +74,27 @@ struct TimelineSummary {
   }
 };
 
+// abd_loo.hpp: PSIS-LOO by individual.  The kept draws' T_j = S_j + N_j in abd_psis.hpp's matrix, individual-major
+// [ld][n C] -- ld = N padded to 64, C = ceil(draws / thin) kept draws per chain, chain j's kept draw c in column j C + c -- and per
+// chain a staging block [2][kStage][ld] of the per-individual kernel's S_j rows, then its N_j rows, which abd_loo_store folds into
+// the matrix kStage draws at a time.  stored / staged: per chain, the rows in the matrix and in the staging block (a chain belongs
+// to one host thread).  launch: one per-individual launch per draw, shared with the WAIC accumulators `acc` (nullptr: off); then,
+// with the block full or at the run call's last iteration, the store.
+struct LooSummary {
+  static constexpr int kStage = 16;
+  DevBuf<double> mat, stage, out;  // out [3][ld]: elpd_loo, pareto k, lppd
+  DevBuf<int32_t> cells, tail;     // [ld]: the individual's readings (0: padding, or none); n_tail
+  int64_t draws = 0, thin = 1, C = 0;
+  size_t ld = 0;
+  std::vector<int64_t> stored, staged;
+  bool on() const { return mat != nullptr; }
+  int64_t planned() const { return draws; }
+  int64_t capacity() const { return (int64_t)stored.size() * C; }
+  double* stage_at(int j, int antigen, int64_t row) const { return stage + (((size_t)j * 2 + antigen) * kStage + (size_t)row) * ld; }
+  int launch(abd_ctx* c, int j, int chain, const double* q, int64_t d, bool last, double* acc, hipStream_t st);
+  int stats(abd_ctx* c);  // the launch of abd_psis_kernel over the whole matrix into out / tail, on the context's stream
+};
+
 struct abd_sampler {
   ~abd_sampler();  // quiesces; then the members go in reverse order (abd_host.hpp)
   abd_ctx* c = nullptr;
@@ -145,6 +166,7 @@ struct abd_sampler {
   DiagSummary diag;
   TimelineSummary timelines;
   RiskSummary risk;
+  LooSummary loo;  // (launched with the per-individual accumulators, not in that order: abd_loo.hpp)
 };
 
 namespace abdi {

@@ -409,6 +409,81 @@ int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, in
   return ABD_OK;
 }
 
+int abd_sampler_enable_loo(abd_sampler* s, int64_t draws_per_chain, int32_t thin) {
+  if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
+  if (draws_per_chain < 0) return fail(ABD_ERR_ARG, "loo: draws_per_chain=%lld is negative", (long long)draws_per_chain);
+  if (thin < 1) return fail(ABD_ERR_ARG, "loo: thin=%d is below 1", thin);
+  const abd_ctx* c = s->c;
+  LooSummary f;
+  f.draws = draws_per_chain, f.thin = thin, f.C = (draws_per_chain + thin - 1) / thin;
+  f.ld = std::max<size_t>(64, ((size_t)c->N + 63) / 64 * 64);
+  if (f.C > ABD_SAMPLER_LOO_MAX_DRAWS || (int64_t)s->n * f.C > ABD_SAMPLER_LOO_MAX_DRAWS)
+    return fail(ABD_ERR_ARG, "loo: %d chains x %lld kept draws = %lld pass the cap of %d draws (a larger thin fits)", s->n, (long long)f.C,
+                (long long)s->n * (long long)f.C, ABD_SAMPLER_LOO_MAX_DRAWS);
+  f.stored.assign((size_t)s->n, 0);
+  f.staged.assign((size_t)s->n, 0);
+  const size_t n_mat = f.ld * (size_t)f.capacity(), n_stage = (size_t)s->n * 2 * LooSummary::kStage * f.ld;
+  const size_t bytes = (n_mat + n_stage + 3 * f.ld) * sizeof(double) + 2 * f.ld * sizeof(int32_t);
+  return enable_summary(s, s->loo, "loo", draws_per_chain > 0, bytes, [&](LooSummary& x) {
+    x = std::move(f);
+    // every individual's readings of both antigens; 0 in the padding
+    std::vector<int32_t> cells(x.ld, 0);
+    for (size_t j = 0; j < (size_t)c->N; ++j) cells[j] = (c->seg_s[j + 1] - c->seg_s[j]) + (c->seg_n[j + 1] - c->seg_n[j]);
+    hipError_t e = x.mat.alloc(std::max<size_t>(1, n_mat));
+    if (e == hipSuccess) e = x.stage.alloc_zero(n_stage, c->stream);  // (its padding columns are never written)
+    if (e == hipSuccess) e = x.out.alloc(3 * x.ld);
+    if (e == hipSuccess) e = x.tail.alloc(x.ld);
+    if (e == hipSuccess) e = x.cells.upload(cells.data(), x.ld);
+    return e;
+  });
+}
+
+int abd_sampler_loo_rows(abd_sampler* s, int32_t k, int64_t first, int64_t count, double* ll, int64_t* n_rows) {
+  if (int rc = readout(s, k, [&] { return s->loo.on(); }, "loo is not enabled (abd_sampler_enable_loo)")) return rc;
+  const LooSummary& x = s->loo;
+  const int64_t have = x.stored[(size_t)k];
+  if (n_rows) *n_rows = have;
+  if (int rc = check_window("loo: rows", "holds", first, count, have)) return rc;
+  if (count == 0 || !ll) return ABD_OK;
+  // the chain's columns [first, first + count) of every individual's row, then turned to draw-major
+  const size_t N = (size_t)s->c->N, n = (size_t)count;
+  std::vector<double> h(N * n);
+  HIP_TRY(hipMemcpy2D(h.data(), n * sizeof(double), x.mat + (size_t)k * x.C + (size_t)first, (size_t)x.capacity() * sizeof(double),
+                      n * sizeof(double), N, hipMemcpyDeviceToHost));
+  for (size_t j = 0; j < N; ++j)
+    for (size_t d = 0; d < n; ++d) ll[d * N + j] = h[j * n + d];
+  return ABD_OK;
+}
+
+int abd_sampler_loo_stats(abd_sampler* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws,
+                          int64_t* n_readings) {
+  if (s && (!elpd_loo || !pareto_k || !lppd || !n_tail)) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = readout(s, 0, [&] { return s->loo.on(); }, "loo is not enabled (abd_sampler_enable_loo)")) return rc;
+  LooSummary& x = s->loo;
+  abd_ctx* c = s->c;
+  // (the matrix's rows are contiguous only when every chain's columns are full)
+  for (int k = 0; k < s->n; ++k)
+    if (x.stored[(size_t)k] != x.C)
+      return fail(ABD_ERR_STATE, "loo: chain %d holds %lld of its %lld rows: the statistics are those of a finished run", k,
+                  (long long)x.stored[(size_t)k], (long long)x.C);
+  if (int rc = x.stats(c)) return rc;
+  const size_t N = (size_t)c->N, ld = x.ld;
+  std::vector<double> h(3 * ld);
+  std::vector<int32_t> ht(ld);
+  HIP_TRY(hipMemcpyAsync(h.data(), x.out, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(ht.data(), x.tail, ht.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t j = 0; j < N; ++j) {  // (the individuals are in the caller's order: nothing to scatter)
+    elpd_loo[j] = h[j];
+    pareto_k[j] = h[ld + j];
+    lppd[j] = h[2 * ld + j];
+    n_tail[j] = ht[j];
+    if (n_readings) n_readings[j] = (int64_t)(c->seg_s[j + 1] - c->seg_s[j]) + (int64_t)(c->seg_n[j + 1] - c->seg_n[j]);
+  }
+  if (n_draws) *n_draws = x.capacity();
+  return ABD_OK;
+}
+
 int abd_sampler_adaptation(abd_sampler* s, int32_t k, double* inv_mass, double* step_size, double* metric) {
   if (!s) return fail(ABD_ERR_ARG, "sampler is NULL");
   if (k < 0 || k >= s->n) return fail(ABD_ERR_ARG, "k=%d outside [0, %d)", k, s->n);

@@ -683,22 +683,8 @@ int abd_survival_loo_stats(abd_survival* s, double* elpd_loo, double* pareto_k, 
   if (s->loo_n < 1) return fail(ABD_ERR_ARG, "no draws held (abd_survival_loo_accumulate or abd_survival_loo_append_rows comes first)");
   HIP_TRY(hipSetDevice(s->sums.device));
   const size_t ld = (size_t)s->sums.ld;
-  PsisArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.mat = s->d_loo;
-  a.n_cells = s->d_loo_cells;
-  a.elpd = s->d_loo_out;
-  a.pareto_k = s->d_loo_out + ld;
-  a.lppd = s->d_loo_out + 2 * ld;
-  a.n_tail = s->d_loo_tail;
-  a.capacity = s->loo_cap;
-  a.S = (int32_t)s->loo_n;
-  a.M = psis_tail_len(s->loo_n);
-  a.log_S = std::log((double)s->loo_n);
-  a.log_tiny = std::log(std::numeric_limits<double>::min());
-  // the draws a thread holds in registers: the smallest of 1, 4, 16, 64 with S <= 256 VPT
-  void (*const kernel)(const PsisArgs) = a.S <= 256 ? abd_psis_kernel<1> : a.S <= 1024 ? abd_psis_kernel<4> : a.S <= 4096 ? abd_psis_kernel<16> : abd_psis_kernel<64>;
-  HIP_TRY(launch_kernel(kernel, dim3((unsigned)ld), dim3(kPsisThreads), 0, s->sums.stream, a));
+  const PsisLaunch p = psis_launch(s->d_loo, s->d_loo_cells, s->d_loo_out, s->d_loo_tail, ld, s->loo_cap, s->loo_n);
+  HIP_TRY(launch_kernel(p.kernel, dim3((unsigned)ld), dim3(kPsisThreads), 0, s->sums.stream, p.args));
   HIP_TRY(hipMemcpyAsync(s->h_loo_out.host(), s->d_loo_out, 3 * ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
   HIP_TRY(hipMemcpyAsync(s->h_loo_tail.host(), s->d_loo_tail, ld * sizeof(int32_t), hipMemcpyDeviceToHost, s->sums.stream));
   HIP_TRY(hipStreamSynchronize(s->sums.stream));

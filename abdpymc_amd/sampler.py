@@ -365,7 +365,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
     ``Context.posterior_predictive(.., seed, chain_offset + c, t)`` (``predictive.sample_posterior_predictive``).  It draws from
     no random stream the chains use: their trajectories do not change.
 
-    ``summary_options``: the keywords of the summaries computed over ALL draws inside the sampler (``summaries.registry()``).
+    ``summary_options``: the keywords of the summaries computed over ALL draws inside the sampler (``summaries.every()``).
     Each is documented once, on its summary: ``help(m.SUMMARY)`` for the module m that reads the result.  A keyword none of them
     owns is a ``TypeError``.  Their arrays' host bytes count against ``budget_bytes`` after the recorded ones, in the registry's
     order, and the first summary that passes it refuses the run.
@@ -397,7 +397,7 @@ def sample_native(model, tune: int, draws: int, chains: int = 1, seed: int = 0, 
                 f"budget of {budget / 2 ** 30:.1f} GiB: thin >= {thin_fit} fits (or record less: no_deterministics / "
                 f"record_discrete=False; the posterior means are returned either way; ABD_RECORD_BUDGET_GB raises the budget)")
     active = []  # (summary, its plan)
-    for s in summaries.registry():
+    for s in summaries.every():
         plan = s.plan(opts, draws, chains, G, N)
         if plan is None:
             continue
@@ -509,7 +509,7 @@ def sample(model, tune: int, draws: int, chains: int = 1, seed: int = 0, record_
                              log_likelihood=log_likelihood, posterior_predictive=posterior_predictive, **summary_options)
     opts = summaries.resolve(summary_options)
     rows = {"log_likelihood": log_likelihood, "posterior_predictive": posterior_predictive}
-    for s in reversed(summaries.registry()):
+    for s in reversed(summaries.every()):
         if s.on(opts) or rows.get(s.record_row):
             raise ValueError(s.native_only)
     if chain_offset or dense_metric or thin != 1:

@@ -1,7 +1,7 @@
 """
 The per-draw summaries of the native sampler, as the host sees them: every summary is described ONCE, by a ``Summary`` object
 in its own module (``SUMMARY``), and ``sampler.sample`` / ``sample_native``, ``cli.main`` and ``cli.write_posterior`` loop over
-``registry()``.  A new summary is a module with such an object plus one line in ``registry()`` ("Adding a summary").
+``every()``.  A new summary is a module with such an object plus one line in ``registry()`` ("Adding a summary").
 
 ``log_likelihood`` / ``posterior_predictive`` are per-draw record rows of the sampler, not summaries: they stay in its record path.
 
@@ -16,11 +16,21 @@ import numpy as np
 
 
 def registry() -> tuple:
-    """Every summary, in the order they are planned, counted against the host budget, enabled, collected and reported.  (A
-    function, not a module constant: the six modules take their base class from this one, whichever is imported first.)"""
+    """The summaries that are kept per chain, so that chains sharded over processes gather them, in the order they are planned,
+    counted against the host budget, enabled, collected and reported.  (A function, not a module constant: the six modules take
+    their base class from this one, whichever is imported first.)"""
     from . import compare, curves, diagnostics, predictive, risk, timelines
 
     return (compare.SUMMARY, predictive.SUMMARY, curves.SUMMARY, diagnostics.SUMMARY, risk.SUMMARY, timelines.SUMMARY)
+
+
+def every() -> tuple:
+    """``registry()`` and, behind ``compare.SUMMARY``, ``loo.SUMMARY``, which pools the draws of all chains on one device and so
+    runs in one process only: what ``sample``, ``resolve`` and the command line loop over."""
+    from . import loo
+
+    reg = registry()
+    return reg[:1] + (loo.SUMMARY,) + reg[1:]
 
 
 class Summary:
@@ -82,7 +92,7 @@ class Summary:
 
 def resolve(given: dict) -> dict:
     """Every summary option with its default, overridden by ``given``; ``TypeError`` for a keyword no summary owns."""
-    opts = {k: v for s in registry() for k, v in s.options.items()}
+    opts = {k: v for s in every() for k, v in s.options.items()}
     for k in given:
         if k not in opts:
             raise TypeError(f"sample() got an unexpected keyword argument {k!r}")

@@ -466,6 +466,28 @@ int abd_sampler_enable_risk(abd_sampler* s, int64_t capacity, const abd_risk_spe
  * beyond it, ABD_ERR_STATE when the table is not enabled.  May be called between run calls. */
 int abd_sampler_risk(abd_sampler* s, int32_t k, int64_t first, int64_t count, int64_t* table, int64_t* n_draws);
 
+/* PSIS-LOO by individual for the titer model: T_j = S_j + N_j (abd_individual_loglik: ll_s[j] + ll_n[j]) of every
+ * kept draw of every chain stays on the device, a matrix of 8 bytes per kept draw and slot of 64-padded individuals, and
+ * every individual's column over all chains is Pareto-smoothed there by the estimator of abd_survival_loo_stats.
+ * _enable: before the first abd_sampler_run* call (ABD_ERR_STATE after it).  Draw d = iteration - tune is kept when
+ *   d % thin == 0: C = ceil(draws_per_chain / thin) rows per chain; 0 draws releases.  ABD_ERR_ARG, before the device is touched,
+ *   for a negative size, thin < 1 or n_chains * C above ABD_SAMPLER_LOO_MAX_DRAWS (the message names the product and the cap);
+ *   ABD_ERR_NOMEM, the message naming the bytes.  While it is enabled an abd_sampler_run* call whose draws would pass
+ *   draws_per_chain fails with ABD_ERR_STATE before anything is launched.  The per-individual launch of a draw is shared with
+ *   abd_sampler_enable_individual_loglik, whose accumulators keep their bits; the chains' trajectories do not change.
+ * _rows: chain k's kept rows first .. first + count - 1 as ll[count][N] in the caller's order of individuals (NULL: none
+ *   copied); *n_rows (may be NULL) receives the rows the chain holds.  ABD_ERR_ARG for a window beyond them.  May be called
+ *   between run calls.
+ * _stats: over the S = n_chains * C draws of a finished run, chain-major: elpd_loo[N], pareto_k[N] (+inf where the tail has at
+ *   most 4 draws), lppd[N] = log mean exp(T_j), n_tail[N], *n_draws = S and n_readings[N] (the last two may be NULL); an
+ *   individual without readings gets elpd_loo = lppd = 0, pareto_k = NaN, n_tail = 0.  ABD_ERR_STATE, naming the chain, unless
+ *   every chain holds exactly C rows.  Consumes nothing: a second call returns the same bits. */
+#define ABD_SAMPLER_LOO_MAX_DRAWS 16384
+int abd_sampler_enable_loo(abd_sampler* s, int64_t draws_per_chain, int32_t thin);
+int abd_sampler_loo_rows(abd_sampler* s, int32_t k, int64_t first, int64_t count, double* ll, int64_t* n_rows);
+int abd_sampler_loo_stats(abd_sampler* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws,
+                          int64_t* n_readings);
+
 /* Per-cell convergence accumulators over ALL draws: what split R-hat and a batch-means effective sample size of the
  * Deterministics "i", "ab_n_mu", "ab_s_mu" need, kept on the device because a run at full size never keeps its draws
  * (abdpymc_amd/csrc/abd_diag.hpp; abdpymc_amd/diagnostics.py: from_draws is the same definition as NumPy, rhat / ess read it).

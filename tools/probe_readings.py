@@ -3,7 +3,10 @@ Cost of the per-reading outputs at BASELINE config 3 (dense, 10 000 individuals 
 4-chain compound sampler run with and without on-device WAIC accumulation (``--leg waic``: sample(..., waic=True)) or posterior
 predictive check statistics (``--leg ppc``: sample(..., ppc=True)) or the per-individual WAIC accumulation alone (``--leg
 individual``: sample(..., waic=True, waic_by="individual"); ``--profile``: waic_by="both", so that abd_individual_dense_kernel runs
-beside abd_readings_dense_kernel<LogLik, ...> in one trace) or the epidemic curves of every draw (``--leg curves``:
+beside abd_readings_dense_kernel<LogLik, ...> in one trace) or PSIS-LOO by individual (``--leg loo``: sample(..., loo=True), whose
+read-out at the end of the run is abd_psis_kernel over all chains' draws; ``--profile``: with waic_by="individual" as well, so that
+the one abd_individual_dense_kernel launch per draw and chain writes the staging rows AND the accumulators, and abd_loo_store runs
+once per 16 draws) or the epidemic curves of every draw (``--leg curves``:
 sample(..., curves=True); not a per-reading output, but the same question) or the per-cell convergence accumulators
 (``--leg diagnostics``: sample(..., diagnostics=True); likewise) or the infection-risk-by-titer table of every draw (``--leg
 risk``: sample(..., risk=spec) with 7 edges per antigen, the whole window, first infections only; likewise) or the per-individual
@@ -37,7 +40,7 @@ from abdpymc_amd.sampler import sample  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("waic", "individual", "ppc", "curves", "diagnostics", "risk", "timelines"), default="waic")
+    ap.add_argument("--leg", choices=("waic", "individual", "loo", "ppc", "curves", "diagnostics", "risk", "timelines"), default="waic")
     ap.add_argument("--inds", type=int, default=10000)
     ap.add_argument("--gaps", type=int, default=200)
     ap.add_argument("--chains", type=int, default=4)
@@ -68,6 +71,8 @@ def main():
             on = dict(timelines=True, diagnostics=True)
         if a.leg == "individual":
             on = dict(waic=True, waic_by="both")
+        if a.leg == "loo":
+            on = dict(waic=True, waic_by="individual", loo=True)
         sample(m, draws=a.draws[0], **on, **(leg_kw(True) if a.leg == "risk" else {}), **kw)
         print(json.dumps(dict(inds=a.inds, gaps=a.gaps, chains=a.chains, tune=a.tune, draws=a.draws[0], **on, risk=a.leg == "risk",
                               wall_s=time.perf_counter() - t0)))
