@@ -147,6 +147,20 @@ class _SurvivalDrawsDesc(C.Structure):  # abd_survival_draws_desc
                 ("lam0_z_sd", C.c_double)]
 
 
+class _SurvivalDrawsGroupsDesc(C.Structure):  # abd_survival_draws_groups_desc
+    _fields_ = [("n_datasets", C.c_int32), ("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_groups", C.c_int32), ("device", C.c_int32),
+                ("n_risk", C.c_void_p), ("event", C.c_void_p), ("titer", C.c_void_p), ("group", C.c_void_p),
+                ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double), ("lam0_z_sd", C.c_double),
+                ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
+
+
+class _SurvivalDrawsPeriodsDesc(C.Structure):  # abd_survival_draws_periods_desc
+    _fields_ = [("n_datasets", C.c_int32), ("n_inds", C.c_int32), ("n_intervals", C.c_int32), ("n_periods", C.c_int32), ("device", C.c_int32),
+                ("n_risk", C.c_void_p), ("event", C.c_void_p), ("titer", C.c_void_p), ("period", C.c_void_p),
+                ("lam0_mu_mean", C.c_double), ("lam0_mu_sd", C.c_double), ("lam0_sd_rate", C.c_double), ("lam0_z_sd", C.c_double),
+                ("a_mu_sd", C.c_double), ("a_sd_rate", C.c_double), ("a_z_sd", C.c_double), ("b_sd", C.c_double)]
+
+
 SURVIVAL_MAX_GROUPS = 256  # ABD_SURVIVAL_MAX_GROUPS
 
 # abd_gibbs_record and its ABD_GIBBS_PATH_* codes (include/abd_hip.h)
@@ -253,6 +267,8 @@ SYMBOLS = {
     "abd_survival_predictive_observed": (C.c_int, [_P, _D, _D, _P, _D]),
     "abd_survival_replicate": (C.c_int, [_P, C.c_int32, _D, C.c_int64, _I32]),
     "abd_survival_draws_create": (C.c_int, [C.POINTER(_SurvivalDrawsDesc), C.POINTER(_P)]),
+    "abd_survival_draws_create_groups": (C.c_int, [C.POINTER(_SurvivalDrawsGroupsDesc), C.POINTER(_P)]),
+    "abd_survival_draws_create_periods": (C.c_int, [C.POINTER(_SurvivalDrawsPeriodsDesc), C.POINTER(_P)]),
     "abd_survival_draws_destroy": (C.c_int, [_P]),
     "abd_survival_draws_dim": (C.c_int32, [_P]),
     "abd_survival_draws_logp_dlogp": (C.c_int, [_P, C.c_int32, _I32, _D, _D, _D]),
@@ -1374,22 +1390,30 @@ class SurvivalDraws(_SurvivalHandle):
 
     def __init__(self, n_risk, event, titers, priors, device: int = -1):
         super().__init__()
-        nr, ev = _as(n_risk, np.int32), _as(event, np.int32)
-        xs = [_as(x, np.float64) for x in titers]
-        if nr.ndim != 2 or ev.shape != nr.shape:
-            raise ValueError("n_risk and event must share a shape (M, N)")
+        nr, ev, *xs = self._datasets(n_risk, event, titers)
         if len(xs) not in (1, 2):
             raise ValueError(f"one or two titer arrays, got {len(xs)}")
-        if any(x.ndim != 3 or (x.shape[0], x.shape[2]) != nr.shape or x.shape != xs[0].shape for x in xs):
-            raise ValueError(f"the titers must share a shape (M, T, N) with (M, N) = {nr.shape}")
         d = _SurvivalDrawsDesc()
         d.n_datasets, d.n_inds, d.n_intervals, d.n_titers, d.device = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs), device
         d.n_risk, d.event = nr.ctypes.data, ev.ctypes.data
         for k, x in enumerate(xs):
             d.titer[k] = x.ctypes.data
         d.ab_sd, d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd = (float(v) for v in priors)
-        self.n_datasets, self.n_inds, self.n_intervals, self.n_titers = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs)
         self._created(self._lib.abd_survival_draws_create(C.byref(d), C.byref(self._h)), "abd_survival_draws_dim", self.n_intervals + 2 + len(xs))
+
+    def _datasets(self, n_risk, event, titers):
+        """n_risk, event as int32 arrays of one shape (M, N) and the titers as float64 arrays of one shape (M, T, N); ``n_datasets``,
+        ``n_inds``, ``n_intervals``, ``n_titers``"""
+        nr, ev = _as(n_risk, np.int32), _as(event, np.int32)
+        xs = [_as(x, np.float64) for x in titers]
+        if nr.ndim != 2 or ev.shape != nr.shape:
+            raise ValueError("n_risk and event must share a shape (M, N)")
+        if not xs:
+            raise ValueError("one or two titer arrays, got 0")
+        if any(x.ndim != 3 or (x.shape[0], x.shape[2]) != nr.shape or x.shape != xs[0].shape for x in xs):
+            raise ValueError(f"the titers must share a shape (M, T, N) with (M, N) = {nr.shape}")
+        self.n_datasets, self.n_inds, self.n_intervals, self.n_titers = nr.shape[0], nr.shape[1], xs[0].shape[1], len(xs)
+        return [nr, ev] + xs
 
     def logp_dlogp(self, dataset, theta):
         """``dataset`` an index and ``theta`` (D,) -> (logp, grad (D,)); ``dataset`` (n,) and ``theta`` (n, D) -> (logp (n,), grad (n, D))."""
@@ -1404,10 +1428,52 @@ class SurvivalDraws(_SurvivalHandle):
         return (float(lp[0]), g[0]) if one else (lp, g)
 
     def loglik_sums(self, dataset: int, theta):
-        """The raw device sums of one point on one dataset: S_t (T), L, W_0, W_k (K)."""
+        """The raw device sums of one point on one dataset: S_t (T), L, W_0, W_k (K); of a grouped ensemble S_t (T), L, W_x, W0_g (Gr);
+        of an ensemble by period S_t (T), L, W_x, W0_t (T)."""
         t = _as(theta, np.float64)
         if t.shape != (self.dim,):
             raise ValueError(f"theta must have shape ({self.dim},)")
         out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_draws_loglik_sums(self._h, int(dataset), _ptr(t), _ptr(out)))
         return out
+
+
+class SurvivalDrawsGroups(SurvivalDraws):
+    """The survival model by group over an ensemble of per-draw datasets (abd_hip.h: ``abd_survival_draws_create_groups``): ``n_risk``,
+    ``event`` (M, N) int32, ``titer`` (M, T, N), ``group`` (N,) indices in [0, ``n_groups``) shared by all datasets, ``priors`` as
+    ``SurvivalGroups``'.  The library checks the labels and the datasets; the evaluations are ``SurvivalDraws``'."""
+
+    def __init__(self, n_risk, event, titer, group, n_groups: int, priors, device: int = -1):
+        _SurvivalHandle.__init__(self)
+        nr, ev, x = self._datasets(n_risk, event, [titer])
+        g = _as(group, np.int32)
+        if g.shape != (nr.shape[1],):
+            raise ValueError(f"group must have shape ({nr.shape[1]},), got {g.shape}")
+        d = _SurvivalDrawsGroupsDesc()
+        d.n_datasets, d.n_inds, d.n_intervals, d.n_groups, d.device = nr.shape[0], nr.shape[1], x.shape[1], int(n_groups), device
+        d.n_risk, d.event, d.titer, d.group = nr.ctypes.data, ev.ctypes.data, x.ctypes.data, g.ctypes.data
+        (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
+         d.b_sd) = (float(v) for v in priors)
+        self.n_groups = int(n_groups)
+        self._created(self._lib.abd_survival_draws_create_groups(C.byref(d), C.byref(self._h)), "abd_survival_draws_dim",
+                      self.n_intervals + 2 + int(n_groups))
+
+
+class SurvivalDrawsPeriods(SurvivalDraws):
+    """The survival model by period over an ensemble of per-draw datasets (abd_hip.h: ``abd_survival_draws_create_periods``):
+    ``n_risk``, ``event`` (M, N) int32, ``titer`` (M, T, N), ``period`` (T,) indices in [0, ``n_periods``), ``priors`` as
+    ``SurvivalPeriods``'.  The library checks the labels and the datasets; the evaluations are ``SurvivalDraws``'."""
+
+    def __init__(self, n_risk, event, titer, period, n_periods: int, priors, device: int = -1):
+        _SurvivalHandle.__init__(self)
+        nr, ev, x = self._datasets(n_risk, event, [titer])
+        p = _as(period, np.int32)
+        if p.shape != (x.shape[1],):
+            raise ValueError(f"period must have shape ({x.shape[1]},), got {p.shape}")
+        d = _SurvivalDrawsPeriodsDesc()
+        d.n_datasets, d.n_inds, d.n_intervals, d.n_periods, d.device = nr.shape[0], nr.shape[1], x.shape[1], int(n_periods), device
+        d.n_risk, d.event, d.titer, d.period = nr.ctypes.data, ev.ctypes.data, x.ctypes.data, p.ctypes.data
+        (d.lam0_mu_mean, d.lam0_mu_sd, d.lam0_sd_rate, d.lam0_z_sd, d.a_mu_sd, d.a_sd_rate, d.a_z_sd,
+         d.b_sd) = (float(v) for v in priors)
+        self.n_periods = int(n_periods)
+        self._created(self._lib.abd_survival_draws_create_periods(C.byref(d), C.byref(self._h)), "abd_survival_draws_dim", 2 * self.n_intervals + 2)

@@ -1,7 +1,7 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
 // handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, PSIS-LOO
 // over the resident matrix of those rows (abd_survival_loo_*; abd_psis.hpp), the posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
-// per-draw datasets, a handle of its own kind (abd_survival_draws_*; abd_survival_draws.hpp).  Both kinds run their
+// per-draw datasets, a handle of its own kind and of any form (abd_survival_draws_*; abd_survival_draws.hpp, abd_survival_draws_forms.hpp).  Both kinds run their
 // sums launches on one SurvivalSums.  A handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp,
 // abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the
 // packing of the planes and the form of a model (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at
@@ -12,6 +12,7 @@
 #include "abd_psis.hpp"
 #include "abd_survival.hpp"
 #include "abd_survival_draws.hpp"
+#include "abd_survival_draws_forms.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
 #include "abd_survival_periods.hpp"
@@ -393,11 +394,52 @@ int survival_check_priors(const char* names, std::initializer_list<double> posit
   return ABD_OK;
 }
 
+// what the creators of the forms by group and by period, of either kind of handle, check of their eight priors and make of them
+template <typename Desc>
+int survival_check_gpriors(const Desc* d) {
+  return survival_check_priors("lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd",
+                               {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd}, d->lam0_mu_mean);
+}
+template <typename Desc>
+SurvivalGroupsPriors survival_gpriors(const Desc* d) {
+  return SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+}
+
+// ... and of their counts and labels
+int survival_check_n_groups(int Gr) {
+  if (Gr < 1 || Gr > ABD_SURVIVAL_MAX_GROUPS) return fail(ABD_ERR_ARG, "n_groups=%d outside [1, %d]", Gr, ABD_SURVIVAL_MAX_GROUPS);
+  return ABD_OK;
+}
+int survival_check_groups(int N, int Gr, const int32_t* group) {
+  for (int j = 0; j < N; ++j)
+    if (group[j] < 0 || group[j] >= Gr) return fail(ABD_ERR_ARG, "individual %d: group %d outside [0, %d)", j, group[j], Gr);
+  return ABD_OK;
+}
+int survival_check_n_periods(int T, int P) {
+  if (P < 1 || P > T) return fail(ABD_ERR_ARG, "n_periods=%d outside [1, %d]", P, T);
+  return ABD_OK;
+}
+int survival_check_periods(int T, int P, const int32_t* period) {
+  for (int t = 0; t < T; ++t)
+    if (period[t] < 0 || period[t] >= P) return fail(ABD_ERR_ARG, "interval %d: period %d outside [0, %d)", t, period[t], P);
+  return ABD_OK;
+}
+
 // the layout of the grouped form (survival_groups_layout): a tile belongs to one group
 struct SurvivalLayout {
   int ntile = 0;
   std::vector<int32_t> slot, tile_group, group_tile;
 };
+
+// the individuals sorted by group, every group padded to whole tiles; the labels lie in [0, Gr)
+SurvivalLayout survival_layout(int N, int Gr, const int32_t* group) {
+  SurvivalLayout lay;
+  lay.slot.resize((size_t)N);
+  lay.tile_group.resize((size_t)(N + 63) / 64 + Gr);
+  lay.group_tile.resize((size_t)Gr + 1);
+  lay.ntile = survival_groups_layout(N, Gr, group, lay.slot.data(), lay.tile_group.data(), lay.group_tile.data());
+  return lay;
+}
 
 // Everything after a creator's own checks: the planes, the plan of the launches, the device and its buffers.  spec.device is
 // what the caller asked for (< 0: the current device); layout is null for the ungrouped form (individual j in column j).
@@ -436,9 +478,10 @@ template <typename Desc>
 int survival_no_memory(const Desc* d) {
   return fail(ABD_ERR_NOMEM, "out of host memory for %d x %d cells", d->n_inds, d->n_intervals);
 }
-int survival_no_memory(const abd_survival_draws_desc* d) {
-  return fail(ABD_ERR_NOMEM, "out of host memory for %d datasets of %d x %d cells", d->n_datasets, d->n_inds, d->n_intervals);
-}
+int survival_draws_no_memory(int M, int N, int T) { return fail(ABD_ERR_NOMEM, "out of host memory for %d datasets of %d x %d cells", M, N, T); }
+int survival_no_memory(const abd_survival_draws_desc* d) { return survival_draws_no_memory(d->n_datasets, d->n_inds, d->n_intervals); }
+int survival_no_memory(const abd_survival_draws_groups_desc* d) { return survival_draws_no_memory(d->n_datasets, d->n_inds, d->n_intervals); }
+int survival_no_memory(const abd_survival_draws_periods_desc* d) { return survival_draws_no_memory(d->n_datasets, d->n_inds, d->n_intervals); }
 
 // The frame of the creators of both kinds of handle around `create`, the creator's own checks and what it builds: nothing may be
 // thrown across the C ABI (the host copies of the planes are the large allocations).
@@ -477,21 +520,13 @@ int abd_survival_create_groups(const abd_survival_groups_desc* d, abd_survival**
   return survival_create(d, out, [&] {
     const int N = d->n_inds, Gr = d->n_groups;
     if (int rc = survival_check_shape(N, d->n_intervals)) return rc;
-    if (Gr < 1 || Gr > ABD_SURVIVAL_MAX_GROUPS) return fail(ABD_ERR_ARG, "n_groups=%d outside [1, %d]", Gr, ABD_SURVIVAL_MAX_GROUPS);
+    if (int rc = survival_check_n_groups(Gr)) return rc;
     if (!d->infected || !d->exposure || !d->titer || !d->group) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
-    if (int rc = survival_check_priors("lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd",
-                                       {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd}, d->lam0_mu_mean))
-      return rc;
-    for (int j = 0; j < N; ++j)
-      if (d->group[j] < 0 || d->group[j] >= Gr) return fail(ABD_ERR_ARG, "individual %d: group %d outside [0, %d)", j, d->group[j], Gr);
-    // the individuals sorted by group, every group padded to whole tiles: a tile belongs to one group
-    SurvivalLayout lay;
-    lay.slot.resize((size_t)N);
-    lay.tile_group.resize((size_t)(N + 63) / 64 + Gr);
-    lay.group_tile.resize((size_t)Gr + 1);
-    lay.ntile = survival_groups_layout(N, Gr, d->group, lay.slot.data(), lay.tile_group.data(), lay.group_tile.data());
+    if (int rc = survival_check_gpriors(d)) return rc;
+    if (int rc = survival_check_groups(N, Gr, d->group)) return rc;
+    const SurvivalLayout lay = survival_layout(N, Gr, d->group);  // a tile belongs to one group
     SurvivalSpec spec{SurvivalForm{1, Gr, d->n_intervals}, N, d->device};
-    spec.gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+    spec.gpriors = survival_gpriors(d);
     return survival_create_common(spec, d->infected, d->exposure, &d->titer, &lay, out);
   });
 }
@@ -500,15 +535,12 @@ int abd_survival_create_periods(const abd_survival_periods_desc* d, abd_survival
   return survival_create(d, out, [&] {
     const int T = d->n_intervals, P = d->n_periods;
     if (int rc = survival_check_shape(d->n_inds, T)) return rc;
-    if (P < 1 || P > T) return fail(ABD_ERR_ARG, "n_periods=%d outside [1, %d]", P, T);
+    if (int rc = survival_check_n_periods(T, P)) return rc;
     if (!d->infected || !d->exposure || !d->titer || !d->period) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
-    if (int rc = survival_check_priors("lam0_mu_sd, lam0_sd_rate, lam0_z_sd, a_mu_sd, a_sd_rate, a_z_sd, b_sd",
-                                       {d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd}, d->lam0_mu_mean))
-      return rc;
-    for (int t = 0; t < T; ++t)
-      if (d->period[t] < 0 || d->period[t] >= P) return fail(ABD_ERR_ARG, "interval %d: period %d outside [0, %d)", t, d->period[t], P);
+    if (int rc = survival_check_gpriors(d)) return rc;
+    if (int rc = survival_check_periods(T, P, d->period)) return rc;
     SurvivalSpec spec{SurvivalForm{1, 0, T, P, std::vector<int32_t>(d->period, d->period + T)}, d->n_inds, d->device};
-    spec.gpriors = SurvivalGroupsPriors{d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd, d->a_mu_sd, d->a_sd_rate, d->a_z_sd, d->b_sd};
+    spec.gpriors = survival_gpriors(d);
     return survival_create_common(spec, d->infected, d->exposure, &d->titer, nullptr, out);  // no layout: the caller's order
   });
 }
@@ -816,15 +848,15 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
 
 }  // extern "C"
 
-// ---- the ensemble of per-draw datasets (abd_survival_draws.hpp) ----
+// ---- the ensemble of per-draw datasets (abd_survival_draws.hpp, abd_survival_draws_forms.hpp) ----
 
-struct abd_survival_draws {
-  int M = 0, N = 0, T = 0, K = 0;
-  SurvivalPriors priors{};
-  SurvivalSums sums;      // first: the last to go.  Rows of par: lambda[T], a[K], b[K], the dataset index; of work: log lambda, 1 - lambda
+struct abd_survival_draws : SurvivalSpec {  // the form, as an abd_survival knows it: K titers, by group or by period
+  int M = 0;
+  SurvivalSums sums;      // first: the last to go.  Rows of par: the form's row, then the dataset index; of work: the form's
   std::vector<double> Y;  // [M][T]: the events of dataset m in interval t, an integer
-  DevBuf<double> d_x0, d_x1;
-  DevBuf<int32_t> d_n_risk, d_event;
+  DevBuf<double> d_x0, d_x1, d_w0_part;  // titers [M][T][ld]; by period, the second plane of partials
+  DevBuf<int32_t> d_n_risk, d_event;     // [M][ld]
+  DevBuf<int32_t> d_tile_group, d_group_tile;  // by group
 };
 
 namespace abdi {
@@ -833,24 +865,51 @@ namespace {
 // the sums of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->sums.h_out (rows of out_stride)
 int survival_draws_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta) {
   SurvivalSums& c = s->sums;
-  const int T = s->T, K = s->K;
-  const size_t D = (size_t)survival_dim(K, T);
+  const SurvivalForm& form = s->form;
+  const int T = form.T, stride = form.par_stride();  // the dataset index follows the form's row
+  const size_t D = (size_t)form.dim();
   for (int q = 0; q < n; ++q) {
     double* par = c.h_par.host() + (size_t)q * c.par_stride;
-    survival_prepare(K, T, theta + q * D, par, c.work.data() + (size_t)q * 2 * T);
-    par[T + 2 * K] = 0.0;
-    std::memcpy(par + T + 2 * K, dataset + q, sizeof(int32_t));
+    form.prepare(theta + q * D, par, c.work.data() + (size_t)q * form.work_stride());
+    par[stride] = 0.0;
+    std::memcpy(par + stride, dataset + q, sizeof(int32_t));
   }
   if (int rc = c.upload(n)) return rc;
-  SurvivalDrawsArgs a = survival_args<SurvivalDrawsArgs>(c);
-  a.x0 = s->d_x0;
-  a.x1 = s->d_x1;
-  a.n_risk = s->d_n_risk;
-  a.event = s->d_event;
-  SurvivalArgs f = survival_args<SurvivalArgs>(c);  // the finalize of abd_survival, as it is: it reads the partials, T, ntile and nseg
-  f.out = c.d_out;
-  HIP_TRY(launch_kernel(K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
-  HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, f));
+  // the one place that picks the pair of kernels: the ensemble kernel of the form, then the finalize of abd_survival's handle of
+  // that form, as it is -- it reads the partials, T, ntile and nseg (and the group's tiles)
+  if (form.by_period() || form.grouped()) {
+    SurvivalDrawsFormArgs a = survival_args<SurvivalDrawsFormArgs>(c);
+    a.x = s->d_x0;
+    a.n_risk = s->d_n_risk;
+    a.event = s->d_event;
+    a.tile_group = s->d_tile_group;
+    a.w0_part = s->d_w0_part;
+    a.Gr = form.Gr;
+    if (form.by_period()) {
+      SurvivalPeriodsArgs f = survival_args<SurvivalPeriodsArgs>(c);
+      f.w0_part = s->d_w0_part;
+      f.out = c.d_out;
+      HIP_TRY(launch_kernel(abd_survival_draws_periods_kernel, c.grid(n), dim3(256), 0, c.stream, a));
+      HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, c.stream, f));
+    } else {
+      SurvivalGroupsArgs f = survival_args<SurvivalGroupsArgs>(c);
+      f.group_tile = s->d_group_tile;
+      f.Gr = form.Gr;
+      f.out = c.d_out;
+      HIP_TRY(launch_kernel(abd_survival_draws_groups_kernel, c.grid(n), dim3(256), 0, c.stream, a));
+      HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (form.Gr + 3) / 4), (unsigned)n), dim3(256), 0, c.stream, f));
+    }
+  } else {
+    SurvivalDrawsArgs a = survival_args<SurvivalDrawsArgs>(c);
+    a.x0 = s->d_x0;
+    a.x1 = s->d_x1;
+    a.n_risk = s->d_n_risk;
+    a.event = s->d_event;
+    SurvivalArgs f = survival_args<SurvivalArgs>(c);
+    f.out = c.d_out;
+    HIP_TRY(launch_kernel(form.K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
+    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, f));
+  }
   return c.download(n);
 }
 
@@ -860,20 +919,23 @@ int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int3
   return ABD_OK;
 }
 
-int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws** out) {
-  const int M = d->n_datasets, N = d->n_inds, T = d->n_intervals, K = d->n_titers;
-  if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
+// what the three creators of an ensemble check of its shape
+int survival_draws_check_shape(int M, int N, int T) {
   if (M < 1) return fail(ABD_ERR_ARG, "n_datasets=%d must be >= 1", M);
-  if (int rc = survival_check_shape(N, T)) return rc;
-  if (!d->n_risk || !d->event || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
-  if (int rc = survival_check_priors("ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd", {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd},
-                                     d->lam0_mu_mean))
-    return rc;
+  return survival_check_shape(N, T);
+}
+
+// Everything after a creator's own checks: every dataset checked, the padded copies, the plan of the launches, the device and its
+// buffers.  spec.device is what the caller asked for (< 0: the current device); layout is null for the forms in the caller's order
+// (individual j in column j), else the grouped form's, shared by all datasets.
+int survival_draws_create_common(const SurvivalSpec& spec, int M, const int32_t* n_risk_in, const int32_t* event_in, const double* const* titer,
+                                 const SurvivalLayout* layout, abd_survival_draws** out) {
+  const int N = spec.N, T = spec.form.T, K = spec.form.K;
   std::unique_ptr<abd_survival_draws> s(new (std::nothrow) abd_survival_draws);
   if (!s) return fail(ABD_ERR_NOMEM, "out of host memory");
-  s->M = M, s->N = N, s->T = T, s->K = K;
-  s->priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
-  s->sums.plan((N + 63) / 64, T);  // the split of an abd_survival of N individuals
+  static_cast<SurvivalSpec&>(*s) = spec;
+  s->M = M;
+  s->sums.plan(layout ? layout->ntile : (N + 63) / 64, T);  // the split of an abd_survival of the same form and individuals
   // every dataset, individual after individual: the first offender is named; the padded copies as the kernel reads them
   const size_t ld = (size_t)s->sums.ld, plane = ld * T;
   std::vector<int32_t> n_risk((size_t)M * ld, 0), event((size_t)M * ld, -1);
@@ -881,27 +943,34 @@ int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws**
   s->Y.assign((size_t)M * T, 0.0);
   for (int m = 0; m < M; ++m)
     for (int j = 0; j < N; ++j) {
-      const int nr = d->n_risk[(size_t)m * N + j], ev = d->event[(size_t)m * N + j];
+      const int nr = n_risk_in[(size_t)m * N + j], ev = event_in[(size_t)m * N + j];
       if (nr < 0 || nr > T) return fail(ABD_ERR_ARG, "dataset %d, individual %d: n_risk=%d outside [0, %d]", m, j, nr, T);
       if (ev != -1 && ev != nr - 1)
         return fail(ABD_ERR_ARG, "dataset %d, individual %d, interval %d: event must be -1 or n_risk - 1 = %d", m, j, ev, nr - 1);
-      n_risk[(size_t)m * ld + j] = nr;
-      event[(size_t)m * ld + j] = ev;
+      const size_t col = layout ? (size_t)layout->slot[j] : (size_t)j;
+      n_risk[(size_t)m * ld + col] = nr;
+      event[(size_t)m * ld + col] = ev;
       if (ev >= 0) s->Y[(size_t)m * T + ev] += 1.0;
       for (int k = 0; k < K; ++k) {
-        const double* src = d->titer[k] + (size_t)m * T * N + j;
-        double* dst = (k ? x1 : x0).data() + (size_t)m * plane + j;
+        const double* src = titer[k] + (size_t)m * T * N + j;
+        double* dst = (k ? x1 : x0).data() + (size_t)m * plane + col;
         for (int t = 0; t < T; ++t) dst[(size_t)t * ld] = src[(size_t)t * N];  // cells not at risk as they are: the kernel drops them
         for (int t = 0; t < nr; ++t)
           if (!std::isfinite(src[(size_t)t * N]))
             return fail(ABD_ERR_ARG, "dataset %d, individual %d, interval %d: titer %d of a cell at risk must be finite", m, j, t, k);
       }
     }
-  if (int rc = s->sums.alloc(d->device, T + 2 * K + 1, T + ABD_SURV_NW, 2 * T)) return rc;  // rows of par, out and work
+  // rows of par (the form's, then the dataset index), out and work
+  if (int rc = s->sums.alloc(spec.device, s->form.par_stride() + 1, s->form.out_stride(), s->form.work_stride())) return rc;
   HIP_TRY(s->d_x0.upload(x0.data(), x0.size()));
   if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), x1.size()));
   HIP_TRY(s->d_n_risk.upload(n_risk.data(), n_risk.size()));
   HIP_TRY(s->d_event.upload(event.data(), event.size()));
+  if (layout) {
+    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->sums.ntile));
+    HIP_TRY(s->d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
+  }
+  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->sums.ntile * T));
   *out = s.release();
   return ABD_OK;
 }
@@ -912,26 +981,67 @@ int survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws**
 extern "C" {
 
 int abd_survival_draws_create(const abd_survival_draws_desc* d, abd_survival_draws** out) {
-  return survival_create(d, out, [&] { return survival_draws_create(d, out); });
+  return survival_create(d, out, [&] {
+    const int K = d->n_titers;
+    if (K != 1 && K != 2) return fail(ABD_ERR_ARG, "n_titers=%d: 1 (alone) or 2 (combined)", K);
+    if (int rc = survival_draws_check_shape(d->n_datasets, d->n_inds, d->n_intervals)) return rc;
+    if (!d->n_risk || !d->event || !d->titer[0] || (K == 2 && !d->titer[1])) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_priors("ab_sd, lam0_mu_sd, lam0_sd_rate, lam0_z_sd", {d->ab_sd, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd},
+                                       d->lam0_mu_mean))
+      return rc;
+    SurvivalSpec spec{SurvivalForm{K, 0, d->n_intervals}, d->n_inds, d->device};
+    spec.priors = SurvivalPriors{d->ab_sd, d->lam0_mu_mean, d->lam0_mu_sd, d->lam0_sd_rate, d->lam0_z_sd};
+    return survival_draws_create_common(spec, d->n_datasets, d->n_risk, d->event, d->titer, nullptr, out);
+  });
+}
+
+int abd_survival_draws_create_groups(const abd_survival_draws_groups_desc* d, abd_survival_draws** out) {
+  return survival_create(d, out, [&] {
+    const int N = d->n_inds, Gr = d->n_groups;
+    if (int rc = survival_draws_check_shape(d->n_datasets, N, d->n_intervals)) return rc;
+    if (int rc = survival_check_n_groups(Gr)) return rc;
+    if (!d->n_risk || !d->event || !d->titer || !d->group) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_gpriors(d)) return rc;
+    if (int rc = survival_check_groups(N, Gr, d->group)) return rc;
+    const SurvivalLayout lay = survival_layout(N, Gr, d->group);  // a tile belongs to one group, in every dataset
+    SurvivalSpec spec{SurvivalForm{1, Gr, d->n_intervals}, N, d->device};
+    spec.gpriors = survival_gpriors(d);
+    return survival_draws_create_common(spec, d->n_datasets, d->n_risk, d->event, &d->titer, &lay, out);
+  });
+}
+
+int abd_survival_draws_create_periods(const abd_survival_draws_periods_desc* d, abd_survival_draws** out) {
+  return survival_create(d, out, [&] {
+    const int T = d->n_intervals, P = d->n_periods;
+    if (int rc = survival_draws_check_shape(d->n_datasets, d->n_inds, T)) return rc;
+    if (int rc = survival_check_n_periods(T, P)) return rc;
+    if (!d->n_risk || !d->event || !d->titer || !d->period) return fail(ABD_ERR_ARG, "NULL array in the descriptor");
+    if (int rc = survival_check_gpriors(d)) return rc;
+    if (int rc = survival_check_periods(T, P, d->period)) return rc;
+    SurvivalSpec spec{SurvivalForm{1, 0, T, P, std::vector<int32_t>(d->period, d->period + T)}, d->n_inds, d->device};
+    spec.gpriors = survival_gpriors(d);
+    return survival_draws_create_common(spec, d->n_datasets, d->n_risk, d->event, &d->titer, nullptr, out);  // no layout: the caller's order
+  });
 }
 
 int abd_survival_draws_destroy(abd_survival_draws* s) { return survival_destroy(s); }
 
-int32_t abd_survival_draws_dim(abd_survival_draws* s) { return s ? survival_dim(s->K, s->T) : -1; }
+int32_t abd_survival_draws_dim(abd_survival_draws* s) { return s ? s->form.dim() : -1; }
 
 int abd_survival_draws_logp_dlogp(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* logp, double* grad) {
   if (!s || !dataset || !theta || !logp || !grad) return fail(ABD_ERR_ARG, "NULL argument");
   if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
   if (int rc = survival_draws_check_datasets(s, n, dataset)) return rc;
   HIP_TRY(hipSetDevice(s->sums.device));
-  const int T = s->T, K = s->K;
-  const size_t D = (size_t)survival_dim(K, T);
+  const int T = s->form.T;
+  const size_t D = (size_t)s->form.dim();
   return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_draws_launch(s, nb, dataset + k0, theta + k0 * D)) return rc;
-    for (int q = 0; q < nb; ++q) {
+    for (int q = 0; q < nb; ++q) {  // the closed form of the handle's form on the dataset's own integer Y_t, C = 0
       const size_t k = (size_t)k0 + q;
-      logp[k] = survival_combine(s->priors, K, T, theta + k * D, s->Y.data() + (size_t)dataset[k] * T, 0.0, s->sums.h_out.host() + (size_t)q * s->sums.out_stride,
-                                 s->sums.h_par.host() + (size_t)q * s->sums.par_stride, s->sums.work.data() + (size_t)q * 2 * T, grad + k * D);
+      logp[k] = s->form.combine(s->priors, s->gpriors, theta + k * D, s->Y.data() + (size_t)dataset[k] * T, 0.0,
+                                s->sums.h_out.host() + (size_t)q * s->sums.out_stride, s->sums.h_par.host() + (size_t)q * s->sums.par_stride,
+                                s->sums.work.data() + (size_t)q * s->form.work_stride(), grad + k * D);
     }
     return (int)ABD_OK;
   });
@@ -942,7 +1052,7 @@ int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const
   if (int rc = survival_draws_check_datasets(s, 1, &dataset)) return rc;
   HIP_TRY(hipSetDevice(s->sums.device));
   if (int rc = survival_draws_launch(s, 1, &dataset, theta)) return rc;
-  std::memcpy(sums, s->sums.h_out.host(), (size_t)(s->T + 2 + s->K) * sizeof(double));
+  std::memcpy(sums, s->sums.h_out.host(), (size_t)s->form.n_sums() * sizeof(double));
   return ABD_OK;
 }
 

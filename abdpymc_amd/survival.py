@@ -17,7 +17,10 @@ at which titer, into a, b and the protection (multiple imputation): `
 chosen recorded draw (``event_time`` of ``risk.survival_arrays``), ``model_alone_draws`` / ``model_combined_draws`` keep all of them
 on the device, where every point of a launch reads its own dataset (``abd_survival_draws``), ``sample_draws`` runs one ``_chain``
 per dataset with up to 16 of them sharing every launch, and ``draws_summary`` pools them and says how much of the variance lies
-between the datasets.  Per-draw fits of the grouped and period models, and WAIC / PPC of a per-draw fit, are not built.
+between the datasets.  ``model_alone_groups_draws`` / ``model_alone_periods_draws`` are the per-draw fits of the models by group
+and by period (``abd_survival_draws_create_groups`` / ``_periods``): ``draws_summary`` then gives every midpoint against
+the first, ``a[S|label] - a[S|first label]``, with its share of variance between the datasets and the share of draws above 0.
+WAIC / LOO / PPC of a per-draw fit are not built, and the command line fits the grouped and period models plug-in only.
 
 There is one chain, ``_chain_gen``: a generator over ``sampler.Nuts`` and ``sampler.WindowedAdaptation`` that yields the points it
 needs evaluated.  ``_chain`` (and so ``sample``) drives it against a callable; ``sample_draws`` drives many against one batched
@@ -184,7 +187,26 @@ class SurvivalDraws:
         return y, e, self.s_titer[m].T.copy(), self.n_titer[m].T.copy()
 
 
-class SurvivalDrawsModel:
+class _DrawsDeviceModel:
+    """What the per-draw models pass on to their handle ``_dev`` (``_native.SurvivalDraws``, ``SurvivalDrawsGroups`` or
+    ``SurvivalDrawsPeriods``), every point on its own dataset, and what they take of the ensemble.  They have no WAIC and no
+    predictive checks: those are the plug-in models'."""
+
+    def _ensemble(self, draws: "SurvivalDraws"):
+        self.n_datasets, self.T, self.dim = draws.n_datasets, draws.n_int, self._dev.dim
+        self.source = draws.source
+
+    def logp_dlogp(self, dataset, q):
+        return self._dev.logp_dlogp(dataset, q)
+
+    def loglik_sums(self, dataset, q):
+        return self._dev.loglik_sums(dataset, q)
+
+    def close(self):
+        self._dev.close()
+
+
+class SurvivalDrawsModel(_DrawsDeviceModel):
     """One Poisson hazard model over an ensemble of per-draw datasets (``abd_survival_draws`` in ``include/abd_hip.h``):
     ``names``, ``dim``, ``K``, ``n_datasets``, ``logp_dlogp(dataset, q)`` on the device -- an index and (D,) -> (logp, grad); (n,) and
     (n, D) -> arrays, every point on its own dataset, up to 16 per launch -- ``loglik_sums(dataset, q)``, ``constrain(q)`` and
@@ -197,22 +219,12 @@ class SurvivalDrawsModel:
         self.K = len(titers)
         self.priors = PRIORS[self.K] if priors is None else tuple(float(v) for v in priors)
         self._dev = _Dev(draws.n_risk, draws.event, titers, self.priors, device=device)
-        self.n_datasets, self.T, self.dim = draws.n_datasets, draws.n_int, self._dev.dim
-        self.source = draws.source
+        self._ensemble(draws)
         ab = [f"{v}_{ag}" for v in "ab" for ag in self.antigens] if self.K > 1 else ["a", "b"]
         self.names = tuple(ab + ["_lam0_raw_mu", "_lam0_raw_sd_log__"] + [f"__lam0_raw_z_{t}" for t in range(self.T)])
 
-    def logp_dlogp(self, dataset, q):
-        return self._dev.logp_dlogp(dataset, q)
-
-    def loglik_sums(self, dataset, q):
-        return self._dev.loglik_sums(dataset, q)
-
     def constrain(self, q) -> Dict[str, np.ndarray]:
         return constrain(q, self.K)
-
-    def close(self):
-        self._dev.close()
 
 
 class _DeviceModel:
@@ -441,6 +453,61 @@ class SurvivalPeriodsModel(_DeviceModel):
         return initial_point_groups(self.T, self.P, self.priors)
 
 
+class SurvivalDrawsGroupsModel(_DrawsDeviceModel):
+    """The Poisson hazard model by group over an ensemble of per-draw datasets (``abd_survival_draws_create_groups``):
+    ``names``, ``dim``, ``K`` = 1, ``n_datasets``, ``source``, ``groups`` (the sorted unique labels), ``group_name``, ``Gr``,
+    ``initial_point()``, ``constrain(q)``, ``logp_dlogp(dataset, q)`` and ``loglik_sums(dataset, q)`` on the device, ``close()``."""
+
+    K = 1
+
+    def __init__(self, draws: SurvivalDraws, titer, antigen, groups, group_name="group", priors=None, device: int = -1):
+        from ._native import SURVIVAL_MAX_GROUPS, SurvivalDrawsGroups
+
+        self.antigens = (antigen,)
+        self.group_name = str(group_name)
+        self.groups, self.group_index = group_indices(groups, draws.n_inds)
+        self.Gr = len(self.groups)
+        if self.Gr > SURVIVAL_MAX_GROUPS:
+            raise ValueError(f"{self.Gr} groups: at most {SURVIVAL_MAX_GROUPS}")
+        self.priors = PRIORS_GROUPS if priors is None else tuple(float(v) for v in priors)
+        self._dev = SurvivalDrawsGroups(draws.n_risk, draws.event, titer, self.group_index, self.Gr, self.priors, device=device)
+        self._ensemble(draws)
+        self.names = names_groups(self.T, self.Gr)
+
+    def constrain(self, q) -> Dict[str, np.ndarray]:
+        return constrain_groups(q, self.T, self.Gr)
+
+    def initial_point(self) -> np.ndarray:
+        return initial_point_groups(self.T, self.Gr, self.priors)
+
+
+class SurvivalDrawsPeriodsModel(_DrawsDeviceModel):
+    """The Poisson hazard model by period over an ensemble of per-draw datasets (``abd_survival_draws_create_periods``):
+    ``names``, ``dim``, ``K`` = 1, ``n_datasets``, ``source``, ``periods`` (the sorted unique labels), ``period_index`` (T,),
+    ``period_name``, ``P``, ``initial_point()``, ``constrain(q)``, ``logp_dlogp(dataset, q)`` and ``loglik_sums(dataset, q)`` on the
+    device, ``close()``."""
+
+    K = 1
+
+    def __init__(self, draws: SurvivalDraws, titer, antigen, periods, period_name="period", priors=None, device: int = -1):
+        from ._native import SurvivalDrawsPeriods
+
+        self.antigens = (antigen,)
+        self.period_name = str(period_name)
+        self.periods, self.period_index = period_indices(periods, draws.n_int)
+        self.P = len(self.periods)
+        self.priors = PRIORS_PERIODS if priors is None else tuple(float(v) for v in priors)
+        self._dev = SurvivalDrawsPeriods(draws.n_risk, draws.event, titer, self.period_index, self.P, self.priors, device=device)
+        self._ensemble(draws)
+        self.names = names_groups(self.T, self.P)
+
+    def constrain(self, q) -> Dict[str, np.ndarray]:
+        return constrain_groups(q, self.T, self.P)
+
+    def initial_point(self) -> np.ndarray:
+        return initial_point_groups(self.T, self.P, self.priors)
+
+
 class SurvivalAnalysis:
     """The reference's ``SurvivalAnalysis(abd_inference, start, end, cohort_data)``: ``infected``, ``exposure``, ``s_titer``,
     ``n_titer`` (n_ind, n_int), ``n_int = end - start - 1``, ``intervals``, ``t0`` (the month of the arrays' first interval).
@@ -537,6 +604,24 @@ class SurvivalAnalysis:
     def model_combined_draws(self, draws: "SurvivalDraws") -> "SurvivalDrawsModel":
         return self._windowed(SurvivalDrawsModel(draws, [draws.s_titer, draws.n_titer], ("S", "N"), device=self.device))
 
+    def model_alone_groups_draws(self, antigen: str, groups, draws: "SurvivalDraws", group_name: str = "group") -> "SurvivalDrawsGroupsModel":
+        """``model_alone_groups`` over the per-draw datasets ``draws``: one label per individual, shared by all datasets."""
+        if antigen not in ("S", "N"):
+            raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
+        titer = draws.s_titer if antigen == "S" else draws.n_titer
+        return self._windowed(SurvivalDrawsGroupsModel(draws, titer, antigen, groups, group_name, device=self.device))
+
+    def model_alone_periods_draws(self, antigen: str, draws: "SurvivalDraws", periods=None,
+                                  period_name: Optional[str] = None) -> "SurvivalDrawsPeriodsModel":
+        """``model_alone_periods`` over the per-draw datasets ``draws``; ``periods=None`` is monthly, as there."""
+        if antigen not in ("S", "N"):
+            raise ValueError(f"antigen must be 'S' or 'N', got {antigen!r}")
+        titer = draws.s_titer if antigen == "S" else draws.n_titer
+        if periods is None:
+            periods, period_name = self.intervals, "intervals" if period_name is None else period_name
+        name = "period" if period_name is None else period_name
+        return self._windowed(SurvivalDrawsPeriodsModel(draws, titer, antigen, periods, name, device=self.device))
+
     def _windowed(self, model):
         model.start, model.end = self.start, self.end  # what ``waic`` records in a fit, and ``compare`` checks
         return model
@@ -599,6 +684,15 @@ def sample(model, tune: int = 1000, draws: int = 1000, chains: int = 4, seed: in
     fn = evaluator if evaluator is not None else model.logp_dlogp
     q0 = _initial_point(model)
     res = _fit_arrays(model, [_chain(fn, model.dim, tune, draws, np.random.default_rng([seed, c]), target_accept, q0) for c in range(chains)])
+    res.update(_label_keys(model))
+    return res
+
+
+def _label_keys(model) -> Dict[str, np.ndarray]:
+    """What a fit of ``sample`` or ``sample_draws`` records of a model's labels: ``groups`` and ``group_name``, or ``periods``,
+    ``period_name`` and ``period_index``, where the model has them -- what ``protection``, ``report_line`` and ``draws_summary`` know
+    a fit by group or by period by."""
+    res = {}
     if hasattr(model, "groups"):
         res["groups"] = np.asarray(model.groups)
         res["group_name"] = np.array(getattr(model, "group_name", "group"))
@@ -632,7 +726,8 @@ def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset:
     of different datasets.  A finished chain's slot goes to the next waiting chain at once.
 
     Returns the keys of ``sample`` with a leading axis of M x c "chains", dataset-major (``protection``, ``summary`` and
-    ``report_line`` read it as they read a fit of ``sample``), and ``dataset`` (M c,) the dataset of every chain, ``source`` (M, 2)
+    ``report_line`` read it as they read a fit of ``sample``, by group or by period too: the label keys of ``sample`` are recorded
+    where the model has them), and ``dataset`` (M c,) the dataset of every chain, ``source`` (M, 2)
     where the model has it, ``n_evaluations`` and ``n_calls``.
     ``evaluator``: a callable ``(datasets (n,), q (n, D)) -> (logp (n,), grad (n, D))`` in place of the device (tests)."""
     fn = evaluator if evaluator is not None else model.logp_dlogp
@@ -672,6 +767,7 @@ def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset:
         for _ in done:
             start()
     res = _fit_arrays(model, per_chain)
+    res.update(_label_keys(model))
     res["dataset"] = np.array([m for m, _ in jobs], dtype=np.int64)
     if hasattr(model, "source"):
         res["source"] = np.asarray(model.source, dtype=np.int64)
@@ -682,18 +778,60 @@ def sample_draws(model, tune: int = 1000, draws: int = 1000, chains_per_dataset:
 DRAWS_TITERS = (0.0, 2.0, 4.0)  # where ``draws_summary`` (and ``report_line``) read the protection
 
 
+DRAWS_CONTRAST_LABELS = (2, 8)  # with this many groups or periods ``draws_summary`` also gives every midpoint against the first
+
+
+def _fit_labels(fit):
+    """The labels of a fit by group or by period (``_label_keys``), as ``_report_line_groups`` prints them; None for any other fit."""
+    for key in ("groups", "periods"):
+        if key in fit:
+            labels = np.asarray(fit[key]).tolist()
+            a, b = np.shape(fit["a"]), np.shape(fit["b"])
+            if len(a) != 3 or a[-1] != len(labels) or len(b) != 2:
+                raise ValueError(f"a fit with {len(labels)} labels needs a (chains, draws, {len(labels)}) and b (chains, draws), got {a} and {b}")
+            return labels
+    return None
+
+
+def _protection_of_draws(a, b, x):
+    with np.errstate(over="ignore"):
+        return 1.0 - 1.0 / (1.0 + np.exp(-b * (x - a)))  # ``protection``'s formula, per draw
+
+
 def _draws_quantities(fit) -> Dict[str, np.ndarray]:
-    """(chains, draws) arrays of a, b and the protection at ``DRAWS_TITERS``, per antigen: ``a[S]``, ``b[S]``, ``protection[S]@0`` ..."""
+    """(chains, draws) arrays of a, b and the protection at ``DRAWS_TITERS``, per antigen: ``a[S]``, ``b[S]``, ``protection[S]@0`` ...
+    Of a fit by group or by period, whose ``a`` is (chains, draws, labels) of one antigen: ``a[S|label]`` per label, ``b[S]``,
+    ``protection[S|label]@0`` ..."""
     names = [str(v) for v in np.asarray(fit["antigens"])]
     a, b = np.asarray(fit["a"], dtype=np.float64), np.asarray(fit["b"], dtype=np.float64)
     out = {}
+    labels = _fit_labels(fit)
+    if labels is not None:
+        ag = names[0]
+        for k, label in enumerate(labels):
+            out[f"a[{ag}|{label}]"] = a[..., k]
+        out[f"b[{ag}]"] = b
+        for k, label in enumerate(labels):
+            for x in DRAWS_TITERS:
+                out[f"protection[{ag}|{label}]@{x:g}"] = _protection_of_draws(a[..., k], b, x)
+        return out
     for k, ag in enumerate(names):
         ak, bk = (a[..., k], b[..., k]) if a.ndim == 3 else (a, b)
         out[f"a[{ag}]"], out[f"b[{ag}]"] = ak, bk
         for x in DRAWS_TITERS:
-            with np.errstate(over="ignore"):
-                out[f"protection[{ag}]@{x:g}"] = 1.0 - 1.0 / (1.0 + np.exp(-bk * (x - ak)))  # ``protection``'s formula, per draw
+            out[f"protection[{ag}]@{x:g}"] = _protection_of_draws(ak, bk, x)
     return out
+
+
+def _draws_contrasts(fit) -> Dict[str, np.ndarray]:
+    """(chains, draws) arrays ``a[S|label] - a[S|first label]`` of a fit by group or by period with 2 to 8 labels: did the midpoint
+    move?  Empty for any other fit."""
+    labels = _fit_labels(fit)
+    if labels is None or not DRAWS_CONTRAST_LABELS[0] <= len(labels) <= DRAWS_CONTRAST_LABELS[1]:
+        return {}
+    ag = str(np.asarray(fit["antigens"])[0])
+    a = np.asarray(fit["a"], dtype=np.float64)
+    return {f"a[{ag}|{label}] - a[{ag}|{labels[0]}]": a[..., k] - a[..., 0] for k, label in enumerate(labels) if k > 0}
 
 
 def draws_summary(fit, plug_in=None, prob: float = 0.95) -> Dict[str, Dict[str, object]]:
@@ -709,12 +847,20 @@ def draws_summary(fit, plug_in=None, prob: float = 0.95) -> Dict[str, Dict[str, 
         n_negative, n_positive the datasets whose median is below / above 0 -- for ``b``, where the model's flat second mode
                                 shows as datasets on either side
         sd_ratio               with ``plug_in=`` (a fit of ``sample`` on the posterior means): pooled sd over the plug-in fit's sd
+
+    A fit by group or by period (it holds ``groups`` or ``periods``) has the keys ``a[S|label]`` per label, ``b[S]`` and
+    ``protection[S|label]@0``, ...; with 2 to 8 labels also the contrasts ``a[S|label] - a[S|first label]``, whose dicts hold
+    one entry more,
+
+        p_positive             the share of the pooled draws above 0: did the midpoint move, with ``frac_between`` beside it saying
+                               how much of the contrast's variance lies between the datasets
     """
     ds = np.asarray(fit["dataset"]).reshape(-1)
     labels = np.unique(ds)
-    plug = _draws_quantities(plug_in) if plug_in is not None else None
+    contrasts = _draws_contrasts(fit)
+    plug = {**_draws_quantities(plug_in), **_draws_contrasts(plug_in)} if plug_in is not None else None
     out = {}
-    for name, x in _draws_quantities(fit).items():
+    for name, x in {**_draws_quantities(fit), **contrasts}.items():
         if x.shape[0] != ds.size:
             raise ValueError(f"{name}: {x.shape[0]} chains for {ds.size} entries of dataset")
         per = [x[ds == m].reshape(-1) for m in labels]
@@ -725,6 +871,8 @@ def draws_summary(fit, plug_in=None, prob: float = 0.95) -> Dict[str, Dict[str, 
         row = dict(median=float(iv["median"]), lower=float(iv["lower"]), upper=float(iv["upper"]), sd=float(np.std(x.reshape(-1), ddof=1)),
                    W=W, B=B, frac_between=B / (B + W) if B + W > 0 else 0.0, dataset_median=med,
                    n_negative=int((med < 0).sum()), n_positive=int((med > 0).sum()))
+        if name in contrasts:
+            row["p_positive"] = float((x > 0).mean())
         if plug is not None:
             if name not in plug:
                 raise ValueError(f"the plug-in fit has no {name}: it is of other antigens")
@@ -1270,7 +1418,8 @@ def main(argv=None) -> int:
         ap.error("--per_draw_chains goes with --per_draw")
     if args.per_draw is not None:
         if args.model not in ("s", "n", "combined"):
-            ap.error(f"--per_draw fits --model s | n | combined; per-draw fits of --model {args.model} are not built")
+            ap.error(f"--per_draw fits --model s | n | combined here; per-draw fits of --model {args.model} are in Python: "
+                     "SurvivalAnalysis.model_alone_groups_draws / model_alone_periods_draws with sample_draws and draws_summary")
         if args.waic or args.ppc:
             ap.error("--per_draw does not go with --waic / --ppc: WAIC and predictive checks of a per-draw fit are not built")
         if args.loo:

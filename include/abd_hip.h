@@ -869,14 +869,71 @@ typedef struct abd_survival_draws abd_survival_draws;
  * offender; before the device is touched), copies the titer planes and the two integers per individual to the device. */
 int abd_survival_draws_create(const abd_survival_draws_desc* desc, abd_survival_draws** out);
 int abd_survival_draws_destroy(abd_survival_draws* s);
-/* D = 2 K + 2 + T, or -1 for NULL. */
+/* D = 2 K + 2 + T (T + Gr + 5 for a handle of abd_survival_draws_create_groups, T + P + 5 for one of
+ * abd_survival_draws_create_periods), or -1 for NULL. */
 int32_t abd_survival_draws_dim(abd_survival_draws* s);
 /* logp[n] and grad[n][D] at theta[n][D], point q on dataset[q] in [0, M) (ABD_ERR_ARG otherwise; nothing is launched then).  Any
  * n: up to ABD_MAX_BATCH points share a launch.  A point's result is the same bits alone, in any batch and in any row of it, and
  * the same bits an abd_survival handle made of that dataset's (infected, exposure, titer) arrays returns. */
 int abd_survival_draws_logp_dlogp(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* logp, double* grad);
-/* The raw device sums of one point on one dataset, as abd_survival_loglik_sums: sums[T + 2 + K]. */
+/* The raw device sums of one point on one dataset, as abd_survival_loglik_sums: sums[T + 2 + K] (T + 2 + Gr for a handle of
+ * abd_survival_draws_create_groups, 2 T + 2 for one of abd_survival_draws_create_periods). */
 int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const double* theta, double* sums);
+
+/* Per-draw fits of the models by group and by period: the model of abd_survival_groups_desc / abd_survival_periods_desc
+ * over an ensemble of M datasets in event-time form.  The labels belong to the individuals (group) or to the intervals (period)
+ * and are shared by all datasets.  The handle is an abd_survival_draws that knows its form, as an abd_survival does:
+ * abd_survival_draws_dim (D = T + Gr + 5, or T + P + 5), _logp_dlogp, _loglik_sums and _destroy work on it.  theta and the
+ * loglik_sums are those of the plug-in handle of the form; the constant C of the data is 0 and Y_t counts the events of interval t.
+ * A point on dataset m returns, bit for bit, what a handle of abd_survival_create_groups / abd_survival_create_periods made of that
+ * dataset's (infected, exposure, titer) and the same labels returns. */
+typedef struct {
+  int32_t n_datasets;          /* M >= 1 */
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_groups;            /* Gr, 1 <= Gr <= ABD_SURVIVAL_MAX_GROUPS; a group may be empty */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const int32_t* n_risk;       /* (M, N) row-major, each in [0, T] */
+  const int32_t* event;        /* (M, N) row-major, each -1 or n_risk - 1 */
+  const double* titer;         /* (M, T, N) row-major: interval-major planes; finite wherever t < n_risk, anything elsewhere */
+  const int32_t* group;        /* (N), each in [0, Gr) */
+  double lam0_mu_mean;         /* the eight priors of abd_survival_groups_desc, with its defaults: 0, 0.5 */
+  double lam0_mu_sd;
+  double lam0_sd_rate;         /* 2 */
+  double lam0_z_sd;            /* 1 */
+  double a_mu_sd;              /* 0.5 */
+  double a_sd_rate;            /* 2 */
+  double a_z_sd;               /* 1 */
+  double b_sd;                 /* 0.5 */
+} abd_survival_draws_groups_desc;
+
+typedef struct {
+  int32_t n_datasets;          /* M >= 1 */
+  int32_t n_inds;              /* N >= 1 */
+  int32_t n_intervals;         /* T, 1 <= T <= ABD_MAX_GAPS - 1 */
+  int32_t n_periods;           /* P, 1 <= P <= T; a period may be without intervals */
+  int32_t device;              /* HIP device ordinal; <0 = current device */
+  const int32_t* n_risk;       /* (M, N) row-major, each in [0, T] */
+  const int32_t* event;        /* (M, N) row-major, each -1 or n_risk - 1 */
+  const double* titer;         /* (M, T, N) row-major: interval-major planes; finite wherever t < n_risk, anything elsewhere */
+  const int32_t* period;       /* (T), each in [0, P) */
+  double lam0_mu_mean;         /* the eight priors of abd_survival_periods_desc, with its defaults: -3, 0.5 */
+  double lam0_mu_sd;
+  double lam0_sd_rate;         /* 2 */
+  double lam0_z_sd;            /* 1 */
+  double a_mu_sd;              /* 0.5 */
+  double a_sd_rate;            /* 2 */
+  double a_z_sd;               /* 1 */
+  double b_sd;                 /* 0.5 */
+} abd_survival_draws_periods_desc;
+
+/* Check the descriptor, every label and every dataset (ABD_ERR_ARG, before the device is touched: what abd_survival_draws_create
+ * refuses, naming the dataset, the individual and the interval of the first offender, datasets in order; a label outside [0, Gr)
+ * or [0, P); Gr outside [1, ABD_SURVIVAL_MAX_GROUPS]; P outside [1, T]; what the form's prior check refuses), then copy the titer
+ * planes and the two integers per individual to the device -- by group in the plug-in handle's order, sorted by group and every
+ * group padded to whole tiles of 64. */
+int abd_survival_draws_create_groups(const abd_survival_draws_groups_desc* desc, abd_survival_draws** out);
+int abd_survival_draws_create_periods(const abd_survival_draws_periods_desc* desc, abd_survival_draws** out);
 
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).

@@ -1,18 +1,21 @@
 """
-What per-draw survival fits cost (DESIGN 26), two legs in one run on one device, each alternated with its yardstick, best of
-``--reps``:
+What per-draw survival fits cost (DESIGN 26, 29), two legs in one run on one device, each alternated with its yardstick, best of
+``--reps``, for every ``--form``: ``combined`` (K = 2, the default), ``groups`` (S titer, four interleaved groups) and ``periods``
+(S titer, three eras of equal length):
 
-(a) a 16-point launch of the ensemble kernel on 16 datasets (``SurvivalDrawsModel.logp_dlogp``) against a 16-point launch of the
-    plug-in kernel on one handle (``SurvivalModel.logp_dlogp``), K = 2, at N x T = 1 520 x 30 and 10 000 x 199: microseconds per
-    call.
+(a) a 16-point launch of the ensemble kernel of the form on 16 datasets (``logp_dlogp`` of the per-draw model) against a 16-point
+    launch of the plug-in kernel of the same form on one handle, at N x T = 1 520 x 30 and 10 000 x 199: microseconds per call.
+    The probe checks that 16 points on dataset 0 are the bits the plug-in handle of dataset 0 returns, logp and gradient.
 (b) an M = ``--datasets`` fit by ``sample_draws`` (up to 16 chains of different datasets share every launch) against the same M
-    chains run as a loop of ``_chain`` over M ``SurvivalModel`` handles -- the paths a caller had before -- at 1 520 x 30, K = 2:
+    chains run as a loop of ``_chain`` over M plug-in handles of the form -- the paths a caller had before -- at 1 520 x 30:
     wall time, evaluations, evaluator calls, and where the wall time went: inside the evaluator (the device and its call) and
     outside it (the host's NUTS).  The two legs run the same chains bit for bit; the probe checks it.
 
-Data are simulated from the model, one seed per dataset (``tools/probe_survival.py: simulate``): they have event-time form.
+Data are simulated from the model, one seed per dataset (``tools/probe_survival.py: simulate``): they have event-time form.  The
+exit status is 1 where a bit check failed.
 
     python tools/probe_survival_draws.py [--out FILE] [--datasets 64] [--tune 100] [--draws 50] [--reps 3] [--leg a|b|both]
+                                         [--form combined|groups|periods|all]
 """
 import argparse
 import json
@@ -38,22 +41,41 @@ def ensemble(M, N, T):
     return d, data
 
 
-def points(n, dim, seed=1):
-    q = np.zeros((n, dim))
-    q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+FORMS = ("combined", "groups", "periods")
+N_GROUPS, N_PERIODS = 4, 3
+
+
+def models(form, d, data):
+    """(the per-draw model of ``form`` over the ensemble ``d``, a function m -> the plug-in model of dataset m, K)"""
+    N, T = d.n_inds, d.n_int
+    if form == "groups":
+        groups = np.arange(N) % N_GROUPS
+        return (survival.SurvivalDrawsGroupsModel(d, d.s_titer, "S", groups),
+                lambda m: survival.SurvivalGroupsModel(data[m][0], data[m][1], data[m][2][0], "S", groups), 1)
+    if form == "periods":
+        periods = np.arange(T) * N_PERIODS // T
+        return (survival.SurvivalDrawsPeriodsModel(d, d.s_titer, "S", periods),
+                lambda m: survival.SurvivalPeriodsModel(data[m][0], data[m][1], data[m][2][0], "S", periods), 1)
+    return (survival.SurvivalDrawsModel(d, [d.s_titer, d.n_titer], ("S", "N")),
+            lambda m: survival.SurvivalModel(data[m][0], data[m][1], data[m][2], ("S", "N")), 2)
+
+
+def points(n, model, seed=1):
+    q = np.tile(survival._initial_point(model), (n, 1))  # the prior means of lam0's hyperparameters, the rest 0
     return q + np.random.default_rng(seed).uniform(-0.5, 0.5, size=q.shape)
 
 
-def leg_a(N, T, reps):
+def leg_a(form, N, T, reps):
     d, data = ensemble(16, N, T)
-    ens = survival.SurvivalDrawsModel(d, [d.s_titer, d.n_titer], ("S", "N"))
-    one = survival.SurvivalModel(*data[0][:2], data[0][2], ("S", "N"))
-    q, ds = points(16, ens.dim), np.arange(16, dtype=np.int32)
-    row = {"leg": "a", "N": N, "T": T, "K": 2, "points": 16, "datasets": 16, "ensemble_bytes": int(16 * (16 * T * d.n_inds + 8 * d.n_inds)),
-           "plug_in_bytes_16_handles": int(16 * 32 * N * T), "ensemble_us_per_call": [], "plug_in_us_per_call": []}
-    lp_e, _ = ens.logp_dlogp(ds[:1] * 0, q[:1])
-    lp_p, _ = one.logp_dlogp(q[:1])
-    row["same_bits_on_dataset_0"] = bool(lp_e[0] == lp_p[0])
+    ens, plug_in, K = models(form, d, data)
+    one = plug_in(0)
+    q, ds = points(16, ens), np.arange(16, dtype=np.int32)
+    ld = d.n_inds if form != "groups" else 64 * int(((np.bincount(np.arange(N) % N_GROUPS) + 63) // 64).sum())  # columns of a plane
+    row = {"leg": "a", "form": form, "N": N, "T": T, "K": K, "points": 16, "datasets": 16, "ensemble_bytes": int(16 * (8 * K * T * ld + 8 * ld)),
+           "plug_in_bytes_16_handles": int(16 * 8 * (2 + K) * ld * T), "ensemble_us_per_call": [], "plug_in_us_per_call": []}
+    lp_e, g_e = ens.logp_dlogp(ds * 0, q)
+    lp_p, g_p = one.logp_dlogp(q)
+    row["same_bits_on_dataset_0"] = bool(np.array_equal(lp_e, lp_p) and np.array_equal(g_e, g_p))
     for _ in range(reps):
         row["ensemble_us_per_call"].append(per_call(lambda x: ens.logp_dlogp(ds, x), q, 0.5))
         row["plug_in_us_per_call"].append(per_call(one.logp_dlogp, q, 0.5))
@@ -79,12 +101,12 @@ class Clocked:
         return out
 
 
-def leg_b(N, T, M, tune, draws, reps, seed=0):
+def leg_b(form, N, T, M, tune, draws, reps, seed=0):
     d, data = ensemble(M, N, T)
-    ens = survival.SurvivalDrawsModel(d, [d.s_titer, d.n_titer], ("S", "N"))
-    handles = [survival.SurvivalModel(y, e, xs, ("S", "N")) for y, e, xs in data]
+    ens, plug_in, K = models(form, d, data)
+    handles = [plug_in(m) for m in range(M)]
     q0 = survival._initial_point(ens)
-    row = {"leg": "b", "N": N, "T": T, "K": 2, "datasets": M, "tune": tune, "draws": draws, "batched": [], "loop": []}
+    row = {"leg": "b", "form": form, "N": N, "T": T, "K": K, "datasets": M, "tune": tune, "draws": draws, "batched": [], "loop": []}
     for _ in range(reps):
         ev = Clocked(ens.logp_dlogp)
         t0 = time.perf_counter()
@@ -110,6 +132,7 @@ def leg_b(N, T, M, tune, draws, reps, seed=0):
     row["mean_points_per_call"] = best["batched"]["evaluations"] / best["batched"]["calls"]
     sm = survival.draws_summary(fit)
     row["frac_between"] = {k: v["frac_between"] for k, v in sm.items() if k[0] in "ab"}
+    row["p_positive"] = {k: v["p_positive"] for k, v in sm.items() if "p_positive" in v}
     ens.close()
     for h in handles:
         h.close()
@@ -123,6 +146,7 @@ def main(argv=None):
     ap.add_argument("--tune", type=int, default=100)
     ap.add_argument("--draws", type=int, default=50)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--form", choices=FORMS + ("all",), default="combined")
     ap.add_argument("--out")
     args = ap.parse_args(argv)
     rows = []
@@ -135,12 +159,13 @@ def main(argv=None):
             with open(args.out, "w") as f:
                 json.dump(rows, f, indent=1)
 
-    if args.leg in ("a", "both"):
-        for N, T in SIZES:
-            keep(leg_a(N, T, args.reps))
-    if args.leg in ("b", "both"):
-        keep(leg_b(SIZES[0][0], SIZES[0][1], args.datasets, args.tune, args.draws, args.reps))
-    return 0
+    for form in FORMS if args.form == "all" else (args.form,):
+        if args.leg in ("a", "both"):
+            for N, T in SIZES:
+                keep(leg_a(form, N, T, args.reps))
+        if args.leg in ("b", "both"):
+            keep(leg_b(form, SIZES[0][0], SIZES[0][1], args.datasets, args.tune, args.draws, args.reps))
+    return 0 if all(r.get("same_bits_on_dataset_0", True) and r.get("same_chains", True) for r in rows) else 1
 
 
 if __name__ == "__main__":
