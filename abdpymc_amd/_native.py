@@ -273,6 +273,14 @@ SYMBOLS = {
     "abd_survival_draws_dim": (C.c_int32, [_P]),
     "abd_survival_draws_logp_dlogp": (C.c_int, [_P, C.c_int32, _I32, _D, _D, _D]),
     "abd_survival_draws_loglik_sums": (C.c_int, [_P, C.c_int32, _D, _D]),
+    "abd_survival_draws_individual_loglik": (C.c_int, [_P, C.c_int32, _I32, _D, _D]),
+    "abd_survival_draws_waic_reset": (C.c_int, [_P]),
+    "abd_survival_draws_waic_accumulate": (C.c_int, [_P, C.c_int32, _I32, _D]),
+    "abd_survival_draws_waic_stats": (C.c_int, [_P, _D, _D, _D, _P, _I32]),  # n_draws is an array here: int64[M]
+    "abd_survival_draws_loo_reserve": (C.c_int, [_P, C.c_int64]),
+    "abd_survival_draws_loo_reset": (C.c_int, [_P]),
+    "abd_survival_draws_loo_accumulate": (C.c_int, [_P, C.c_int32, _I32, _D]),
+    "abd_survival_draws_loo_stats": (C.c_int, [_P, _D, _D, _D, _I32, _P]),
 }
 
 SURVIVAL_PREDICTIVE_BINS = 8  # ABD_SURV_PRED_BINS: bins of a binning variable (up to 7 edges)
@@ -1384,7 +1392,8 @@ class SurvivalPeriods(Survival):
 class SurvivalDraws(_SurvivalHandle):
     """An ensemble of per-draw datasets resident on the device (abd_hip.h: ``abd_survival_draws``): ``n_risk``, ``event`` (M, N) int32
     and one or two titer arrays (M, T, N); ``priors`` as ``Survival``'s.  Every point names its dataset.  The library checks the
-    datasets.  A handle of its own kind: it has no per-individual, WAIC or predictive calls."""
+    datasets.  A handle of its own kind: its per-individual, WAIC and PSIS-LOO calls work per dataset (abd_hip.h:
+    ``abd_survival_draws_individual_loglik`` ...); it has no predictive calls."""
 
     _destroy = "abd_survival_draws_destroy"
 
@@ -1436,6 +1445,63 @@ class SurvivalDraws(_SurvivalHandle):
         out = np.empty(self.n_sums)
         _check(self._lib, self._lib.abd_survival_draws_loglik_sums(self._h, int(dataset), _ptr(t), _ptr(out)))
         return out
+
+    def _rows(self, dataset, theta):
+        """(dataset (n,) int32, theta (n, D)): one dataset index per point; a single index goes with every point."""
+        t = self._points(theta)
+        ds = _as(dataset, np.int32).reshape(-1)
+        if ds.size == 1 and t.shape[0] != 1:
+            ds = np.full(t.shape[0], ds[0], dtype=np.int32)
+        if ds.shape != (t.shape[0],):
+            raise ValueError(f"one dataset index per point (or one for all): {ds.shape[0]} for {t.shape[0]} points")
+        return ds, t
+
+    def draws_individual_loglik(self, dataset, theta):
+        """``dataset`` (n,) (or one index) and ``theta`` (n, D) (or (D,)) -> (n, N): every individual's log-likelihood over its
+        intervals at risk in the point's dataset, in the caller's order of individuals; exactly 0 for one never at risk."""
+        ds, t = self._rows(dataset, theta)
+        out = np.empty((t.shape[0], self.n_inds))
+        _check(self._lib, self._lib.abd_survival_draws_individual_loglik(self._h, t.shape[0], _ptr(ds), _ptr(t), _ptr(out)))
+        return out
+
+    def draws_waic_reset(self):
+        _check(self._lib, self._lib.abd_survival_draws_waic_reset(self._h))
+
+    def draws_waic_accumulate(self, dataset, theta):
+        """Folds the draws ``theta`` (n, D), in order, each into the running statistics of its own dataset."""
+        ds, t = self._rows(dataset, theta)
+        _check(self._lib, self._lib.abd_survival_draws_waic_accumulate(self._h, t.shape[0], _ptr(ds), _ptr(t)))
+
+    def draws_waic_stats(self):
+        """(lse, mean, m2 (M, N), n_draws (M,) int64, n_cells (M, N) int64): ``compare``'s statistics per dataset; NaN and 0 draws
+        for a dataset nothing was folded into."""
+        M, N = self.n_datasets, self.n_inds
+        lse, mean, m2, cells = np.empty((M, N)), np.empty((M, N)), np.empty((M, N)), np.empty((M, N), np.int32)
+        n = np.zeros(M, np.int64)
+        _check(self._lib, self._lib.abd_survival_draws_waic_stats(self._h, _ptr(lse), _ptr(mean), _ptr(m2), _ptr(n), _ptr(cells)))
+        return lse, mean, m2, n, cells.astype(np.int64)
+
+    LOO_MAX_DRAWS = 16384  # ABD_SURVIVAL_LOO_MAX_DRAWS, per dataset
+
+    def draws_loo_reserve(self, capacity: int):
+        """Room on the device for ``capacity`` draws of the per-individual log-likelihood of every dataset; 0 releases it."""
+        _check(self._lib, self._lib.abd_survival_draws_loo_reserve(self._h, int(capacity)))
+
+    def draws_loo_reset(self):
+        _check(self._lib, self._lib.abd_survival_draws_loo_reset(self._h))
+
+    def draws_loo_accumulate(self, dataset, theta):
+        """Evaluates the draws ``theta`` (n, D) and stores every row as the next draw of its dataset."""
+        ds, t = self._rows(dataset, theta)
+        _check(self._lib, self._lib.abd_survival_draws_loo_accumulate(self._h, t.shape[0], _ptr(ds), _ptr(t)))
+
+    def draws_loo_stats(self):
+        """(elpd_loo, pareto_k, lppd (M, N), n_tail (M, N) int64, n_draws (M,) int64) of the draws every dataset holds."""
+        M, N = self.n_datasets, self.n_inds
+        elpd, k, lppd, tail = np.empty((M, N)), np.empty((M, N)), np.empty((M, N)), np.empty((M, N), np.int32)
+        n = np.zeros(M, np.int64)
+        _check(self._lib, self._lib.abd_survival_draws_loo_stats(self._h, _ptr(elpd), _ptr(k), _ptr(lppd), _ptr(tail), _ptr(n)))
+        return elpd, k, lppd, tail.astype(np.int64), n
 
 
 class SurvivalDrawsGroups(SurvivalDraws):

@@ -1,11 +1,13 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
 // handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, PSIS-LOO
 // over the resident matrix of those rows (abd_survival_loo_*; abd_psis.hpp), the posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
-// per-draw datasets, a handle of its own kind and of any form (abd_survival_draws_*; abd_survival_draws.hpp, abd_survival_draws_forms.hpp).  Both kinds run their
+// per-draw datasets, a handle of its own kind and of any form (abd_survival_draws_*; abd_survival_draws.hpp, abd_survival_draws_forms.hpp),
+// with its own per-individual log-likelihood, WAIC and PSIS-LOO per dataset (abd_survival_draws_pointwise.hpp).  Both kinds run their
 // sums launches on one SurvivalSums.  A handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp,
 // abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the
 // packing of the planes and the form of a model (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at
 // the end of abd_survival_groups_terms.hpp).
+#include <algorithm>
 #include <memory>
 
 #include "abd_host.hpp"
@@ -13,6 +15,7 @@
 #include "abd_survival.hpp"
 #include "abd_survival_draws.hpp"
 #include "abd_survival_draws_forms.hpp"
+#include "abd_survival_draws_pointwise.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
 #include "abd_survival_periods.hpp"
@@ -857,6 +860,21 @@ struct abd_survival_draws : SurvivalSpec {  // the form, as an abd_survival know
   DevBuf<double> d_x0, d_x1, d_w0_part;  // titers [M][T][ld]; by period, the second plane of partials
   DevBuf<int32_t> d_n_risk, d_event;     // [M][ld]
   DevBuf<int32_t> d_tile_group, d_group_tile;  // by group
+  // the per-individual log-likelihood, its WAIC accumulators and PSIS-LOO, per dataset (abd_survival_draws_pointwise.hpp)
+  std::vector<int32_t> slot;            // [N] the column of individual j; empty: j itself (the ungrouped layout)
+  std::vector<int32_t> n_cells;         // [M][N] followed cells of individual j in dataset m: its n_risk, in the caller's order
+  int pw_stride = 0;                    // the pointwise row: survival_pointwise_row's, then the draw's number and the dataset
+  DevBuf<double> d_pw_par, d_ll, d_acc;     // [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [M][4][ld]
+  MappedBuf<double> h_pw_par, h_ll, h_acc;  // pinned
+  std::vector<int64_t> waic_n, loo_n;   // [M] draws folded into dataset m's accumulators / held in its block of the matrix
+  std::vector<int64_t> pending;         // [M] scratch of a call: the rows it has for dataset m so far
+  DevBuf<double> d_loo, d_loo_out;      // [M][ld][loo_cap]; [M][3][ld]: elpd_loo, pareto k, lppd
+  DevBuf<int32_t> d_loo_tail;           // [M][ld] n_tail (the followed cells per slot are d_n_risk's rows)
+  MappedBuf<double> h_loo_out;          // pinned
+  MappedBuf<int32_t> h_loo_tail;
+  int64_t loo_cap = 0;                  // the draws every dataset's block holds room for
+
+  int column(int j) const { return slot.empty() ? j : slot[j]; }
 };
 
 namespace abdi {
@@ -919,6 +937,92 @@ int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int3
   return ABD_OK;
 }
 
+// ---- the per-individual log-likelihood of an ensemble (abd_survival_draws_pointwise.hpp) ----
+
+// the buffers of the pointwise launches, at the first of them
+int survival_draws_pointwise_ensure(abd_survival_draws* s) {
+  if (s->d_ll) return ABD_OK;
+  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
+  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->sums.ld));
+  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->sums.ld));
+  return ABD_OK;
+}
+
+// ll[n][ld] of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->d_ll, and on to `to`: copied to s->h_ll; folded into the
+// dataset's WAIC accumulators as its draws waic_n[m] + 1 ...; or stored in the dataset's block of the LOO matrix as its draws
+// loo_n[m] ...  The rows of one dataset keep their order, whatever stands between them.
+int survival_draws_pointwise_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta, PointRows to) {
+  const bool fold = to == PointRows::Fold, store = to == PointRows::Store;
+  if (int rc = survival_draws_pointwise_ensure(s)) return rc;
+  SurvivalSums& c = s->sums;
+  const SurvivalForm& form = s->form;
+  const int T = form.T, n_ab = form.n_ab(), inv_off = 2 * T + n_ab;
+  const size_t D = (size_t)form.dim(), ld = (size_t)c.ld;
+  if (fold || store) std::fill(s->pending.begin(), s->pending.end(), 0);
+  for (int q = 0; q < n; ++q) {
+    double* par = c.h_par.host() + (size_t)q * c.par_stride;
+    double* work = c.work.data() + (size_t)q * form.work_stride();
+    double* row = s->h_pw_par.host() + (size_t)q * s->pw_stride;
+    form.prepare(theta + q * D, par, work);
+    const int64_t n_draw = fold ? s->waic_n[dataset[q]] + ++s->pending[dataset[q]] : 0;
+    survival_pointwise_row(T, n_ab, par, work, n_draw, row);
+    std::memcpy(row + inv_off + kDrawsRowDraw, &n_draw, sizeof n_draw);
+    row[inv_off + kDrawsRowDataset] = 0.0;
+    std::memcpy(row + inv_off + kDrawsRowDataset, dataset + q, sizeof(int32_t));
+  }
+  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  SurvivalDrawsPointArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x0 = s->d_x0;
+  a.x1 = s->d_x1;
+  a.n_risk = s->d_n_risk;
+  a.event = s->d_event;
+  a.par = s->d_pw_par;
+  a.tile_group = s->d_tile_group;
+  a.ll = s->d_ll;
+  a.T = T;
+  a.ld = c.ld;
+  a.ntile = c.ntile;
+  a.par_stride = s->pw_stride;
+  a.n_ab = n_ab;
+  const dim3 grid((unsigned)((c.ntile + 3) / 4), (unsigned)n);
+  void (*const kernels[4])(const SurvivalDrawsPointArgs) = {abd_survival_draws_individual_kernel<0>, abd_survival_draws_individual_kernel<1>,
+                                                            abd_survival_draws_individual_kernel<2>, abd_survival_draws_individual_kernel<3>};
+  HIP_TRY(launch_kernel(kernels[form.mode()], grid, dim3(256), 0, c.stream, a));
+  if (fold) {
+    if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)s->M * 4 * ld, c.stream));
+    HIP_TRY(launch_kernel(abd_survival_draws_waic_fold, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->d_ll,
+                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)ld, (int32_t)s->pw_stride, (int32_t)inv_off, (int32_t)n));
+  } else if (store) {
+    // abd_psis_store as it is, once per run of rows of one dataset, on that dataset's block at its own draw count
+    for (int q0 = 0; q0 < n;) {
+      const int m = dataset[q0];
+      int q1 = q0 + 1;
+      while (q1 < n && dataset[q1] == m) ++q1;
+      HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->d_ll + (size_t)q0 * ld,
+                            (double*)s->d_loo + (size_t)m * ld * (size_t)s->loo_cap, (int32_t)ld, (int64_t)s->loo_cap, (int32_t)(q1 - q0),
+                            (int64_t)(s->loo_n[m] + s->pending[m])));
+      s->pending[m] += q1 - q0;
+      q0 = q1;
+    }
+  } else {
+    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * ld * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  if (fold || store) {
+    std::vector<int64_t>& count = fold ? s->waic_n : s->loo_n;
+    for (int m = 0; m < s->M; ++m) count[m] += s->pending[m];
+  }
+  return ABD_OK;
+}
+
+// what the per-individual calls of an ensemble check of (n, dataset) before the device is touched
+int survival_draws_check_points(const abd_survival_draws* s, int n, const int32_t* dataset) {
+  if (n < 0) return fail(ABD_ERR_ARG, "n=%d is negative", n);
+  return survival_draws_check_datasets(s, n, dataset);
+}
+
 // what the three creators of an ensemble check of its shape
 int survival_draws_check_shape(int M, int N, int T) {
   if (M < 1) return fail(ABD_ERR_ARG, "n_datasets=%d must be >= 1", M);
@@ -941,6 +1045,12 @@ int survival_draws_create_common(const SurvivalSpec& spec, int M, const int32_t*
   std::vector<int32_t> n_risk((size_t)M * ld, 0), event((size_t)M * ld, -1);
   std::vector<double> x0((size_t)M * plane, 0.0), x1(K == 2 ? (size_t)M * plane : 0, 0.0);
   s->Y.assign((size_t)M * T, 0.0);
+  if (layout) s->slot = layout->slot;
+  s->n_cells.assign(n_risk_in, n_risk_in + (size_t)M * N);  // a cell is followed where it is at risk
+  s->pw_stride = survival_pointwise_stride(T, s->form.n_ab()) + kDrawsRowExtra - 1;
+  s->waic_n.assign((size_t)M, 0);
+  s->loo_n.assign((size_t)M, 0);
+  s->pending.assign((size_t)M, 0);
   for (int m = 0; m < M; ++m)
     for (int j = 0; j < N; ++j) {
       const int nr = n_risk_in[(size_t)m * N + j], ev = event_in[(size_t)m * N + j];
@@ -1053,6 +1163,145 @@ int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const
   HIP_TRY(hipSetDevice(s->sums.device));
   if (int rc = survival_draws_launch(s, 1, &dataset, theta)) return rc;
   std::memcpy(sums, s->sums.h_out.host(), (size_t)s->form.n_sums() * sizeof(double));
+  return ABD_OK;
+}
+
+// ---- per individual and dataset: log-likelihood, WAIC, PSIS-LOO (abd_survival_draws_pointwise.hpp) ----
+
+int abd_survival_draws_individual_loglik(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* ll) {
+  if (!s || !dataset || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_draws_check_points(s, n, dataset)) return rc;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t D = (size_t)s->form.dim();
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
+    if (int rc = survival_draws_pointwise_launch(s, nb, dataset + k0, theta + k0 * D, PointRows::Copy)) return rc;
+    for (int q = 0; q < nb; ++q) {  // slots to the caller's order
+      const double* row = s->h_ll.host() + (size_t)q * s->sums.ld;
+      double* out = ll + ((size_t)k0 + q) * s->N;
+      for (int j = 0; j < s->N; ++j) out[j] = row[s->column(j)];
+    }
+    return (int)ABD_OK;
+  });
+}
+
+int abd_survival_draws_waic_reset(abd_survival_draws* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  std::fill(s->waic_n.begin(), s->waic_n.end(), 0);  // a dataset's first draw folded overwrites its column: no clearing
+  return ABD_OK;
+}
+
+int abd_survival_draws_waic_accumulate(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta) {
+  if (!s || !dataset || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_draws_check_points(s, n, dataset)) return rc;
+  HIP_TRY(hipSetDevice(s->sums.device));
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
+    return survival_draws_pointwise_launch(s, nb, dataset + k0, theta + (size_t)k0 * s->form.dim(), PointRows::Fold);
+  });
+}
+
+int abd_survival_draws_waic_stats(abd_survival_draws* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells) {
+  if (!s || !lse || !mean || !m2 || !n_draws || !n_cells) return fail(ABD_ERR_ARG, "NULL argument");
+  if (!std::any_of(s->waic_n.begin(), s->waic_n.end(), [](int64_t v) { return v > 0; }))
+    return fail(ABD_ERR_ARG, "no draws accumulated (abd_survival_draws_waic_accumulate comes first)");
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld, N = (size_t)s->N, all = (size_t)s->M * 4 * ld;
+  if (!s->h_acc.host()) HIP_TRY(s->h_acc.alloc_pinned(all));
+  HIP_TRY(hipMemcpyAsync(s->h_acc.host(), s->d_acc, all * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int m = 0; m < s->M; ++m) {
+    const double* acc = s->h_acc.host() + (size_t)m * 4 * ld;
+    const bool has = s->waic_n[m] > 0;  // a dataset without a draw: NaN and n_draws = 0
+    for (size_t j = 0; j < N; ++j) {
+      const size_t c = (size_t)s->column((int)j), o = (size_t)m * N + j;
+      lse[o] = has ? acc[c] + std::log(acc[ld + c]) : nan;  // M + log S
+      mean[o] = has ? acc[2 * ld + c] : nan;
+      m2[o] = has ? acc[3 * ld + c] : nan;
+      n_cells[o] = s->n_cells[o];
+    }
+    n_draws[m] = s->waic_n[m];
+  }
+  return ABD_OK;
+}
+
+int abd_survival_draws_loo_reserve(abd_survival_draws* s, int64_t capacity) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  if (capacity < 0 || capacity > ABD_SURVIVAL_LOO_MAX_DRAWS)
+    return fail(ABD_ERR_ARG, "capacity=%lld outside [0, %d]", (long long)capacity, ABD_SURVIVAL_LOO_MAX_DRAWS);
+  HIP_TRY(hipSetDevice(s->sums.device));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
+  s->d_loo.reset();
+  s->loo_cap = 0;
+  std::fill(s->loo_n.begin(), s->loo_n.end(), 0);
+  if (capacity == 0) return ABD_OK;
+  const size_t ld = (size_t)s->sums.ld, M = (size_t)s->M;
+  if (s->d_loo.alloc(M * ld * (size_t)capacity) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ABD_ERR_NOMEM, "the device cannot hold %zu bytes for %lld draws of %zu datasets of %zu slots", M * ld * (size_t)capacity * sizeof(double),
+                (long long)capacity, M, ld);
+  }
+  if (!s->d_loo_out) {
+    HIP_TRY(s->d_loo_out.alloc(M * 3 * ld));
+    HIP_TRY(s->d_loo_tail.alloc(M * ld));
+    HIP_TRY(s->h_loo_out.alloc_pinned(M * 3 * ld));
+    HIP_TRY(s->h_loo_tail.alloc_pinned(M * ld));
+  }
+  s->loo_cap = capacity;
+  return ABD_OK;
+}
+
+int abd_survival_draws_loo_reset(abd_survival_draws* s) {
+  if (!s) return fail(ABD_ERR_ARG, "NULL argument");
+  std::fill(s->loo_n.begin(), s->loo_n.end(), 0);  // the rows are overwritten
+  return ABD_OK;
+}
+
+int abd_survival_draws_loo_accumulate(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta) {
+  if (!s || !dataset || !theta) return fail(ABD_ERR_ARG, "NULL argument");
+  if (int rc = survival_draws_check_points(s, n, dataset)) return rc;
+  if (s->loo_cap < 1) return fail(ABD_ERR_STATE, "no matrix reserved (abd_survival_draws_loo_reserve comes first)");
+  std::fill(s->pending.begin(), s->pending.end(), 0);  // every dataset's rows of the whole call, before anything is launched
+  for (int q = 0; q < n; ++q) ++s->pending[dataset[q]];
+  for (int m = 0; m < s->M; ++m)
+    if (s->loo_n[m] + s->pending[m] > s->loo_cap)
+      return fail(ABD_ERR_STATE, "dataset %d: %lld draws held and %lld more would pass the capacity of %lld", m, (long long)s->loo_n[m],
+                  (long long)s->pending[m], (long long)s->loo_cap);
+  HIP_TRY(hipSetDevice(s->sums.device));
+  return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
+    return survival_draws_pointwise_launch(s, nb, dataset + k0, theta + (size_t)k0 * s->form.dim(), PointRows::Store);
+  });
+}
+
+int abd_survival_draws_loo_stats(abd_survival_draws* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws) {
+  if (!s || !elpd_loo || !pareto_k || !lppd || !n_tail || !n_draws) return fail(ABD_ERR_ARG, "NULL argument");
+  if (s->loo_cap < 1) return fail(ABD_ERR_STATE, "no matrix reserved (abd_survival_draws_loo_reserve comes first)");
+  if (!std::any_of(s->loo_n.begin(), s->loo_n.end(), [](int64_t v) { return v > 0; }))
+    return fail(ABD_ERR_ARG, "no draws held (abd_survival_draws_loo_accumulate comes first)");
+  HIP_TRY(hipSetDevice(s->sums.device));
+  const size_t ld = (size_t)s->sums.ld, N = (size_t)s->N, M = (size_t)s->M;
+  // abd_psis_kernel as it is, per dataset on that dataset's block: its S is the dataset's own count, its n_cells the dataset's n_risk
+  for (size_t m = 0; m < M; ++m) {
+    if (s->loo_n[m] < 1) continue;
+    const PsisLaunch p = psis_launch((const double*)s->d_loo + m * ld * (size_t)s->loo_cap, (const int32_t*)s->d_n_risk + m * ld,
+                                     (double*)s->d_loo_out + m * 3 * ld, (int32_t*)s->d_loo_tail + m * ld, ld, s->loo_cap, s->loo_n[m]);
+    HIP_TRY(launch_kernel(p.kernel, dim3((unsigned)ld), dim3(kPsisThreads), 0, s->sums.stream, p.args));
+  }
+  HIP_TRY(hipMemcpyAsync(s->h_loo_out.host(), s->d_loo_out, M * 3 * ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipMemcpyAsync(s->h_loo_tail.host(), s->d_loo_tail, M * ld * sizeof(int32_t), hipMemcpyDeviceToHost, s->sums.stream));
+  HIP_TRY(hipStreamSynchronize(s->sums.stream));
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t m = 0; m < M; ++m) {
+    const double* out = s->h_loo_out.host() + m * 3 * ld;
+    const bool has = s->loo_n[m] > 0;  // a dataset without a draw: NaN, n_tail = 0 and n_draws = 0
+    for (size_t j = 0; j < N; ++j) {
+      const size_t c = (size_t)s->column((int)j), o = m * N + j;
+      elpd_loo[o] = has ? out[c] : nan;
+      pareto_k[o] = has ? out[ld + c] : nan;
+      lppd[o] = has ? out[2 * ld + c] : nan;
+      n_tail[o] = has ? s->h_loo_tail.host()[m * ld + c] : 0;
+    }
+    n_draws[m] = s->loo_n[m];
+  }
   return ABD_OK;
 }
 

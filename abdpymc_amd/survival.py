@@ -20,7 +20,9 @@ per dataset with up to 16 of them sharing every launch, and ``draws_summary`` po
 between the datasets.  ``model_alone_groups_draws`` / ``model_alone_periods_draws`` are the per-draw fits of the models by group
 and by period (``abd_survival_draws_create_groups`` / ``_periods``): ``draws_summary`` then gives every midpoint against
 the first, ``a[S|label] - a[S|first label]``, with its share of variance between the datasets and the share of draws above 0.
-WAIC / LOO / PPC of a per-draw fit are not built, and the command line fits the grouped and period models plug-in only.
+``waic_draws`` / ``loo_draws`` score a per-draw fit by WAIC / PSIS-LOO over the individuals per dataset, every draw on the dataset of
+its chain, and pool the datasets by Rubin's rule; ``compare_draws`` ranks such fits of one ``SurvivalDraws``.  Predictive
+checks of a per-draw fit are not built, and the command line fits the grouped and period models plug-in only.
 
 There is one chain, ``_chain_gen``: a generator over ``sampler.Nuts`` and ``sampler.WindowedAdaptation`` that yields the points it
 needs evaluated.  ``_chain`` (and so ``sample``) drives it against a callable; ``sample_draws`` drives many against one batched
@@ -189,18 +191,50 @@ class SurvivalDraws:
 
 class _DrawsDeviceModel:
     """What the per-draw models pass on to their handle ``_dev`` (``_native.SurvivalDraws``, ``SurvivalDrawsGroups`` or
-    ``SurvivalDrawsPeriods``), every point on its own dataset, and what they take of the ensemble.  They have no WAIC and no
-    predictive checks: those are the plug-in models'."""
+    ``SurvivalDrawsPeriods``), every point on its own dataset, and what they take of the ensemble.  WAIC and PSIS-LOO by individual
+    are kept per dataset (the methods ``draws_*``, named as the C calls are; ``waic_draws``, ``loo_draws``); they have no predictive checks: those are the plug-in models'."""
 
     def _ensemble(self, draws: "SurvivalDraws"):
         self.n_datasets, self.T, self.dim = draws.n_datasets, draws.n_int, self._dev.dim
         self.source = draws.source
+        self.n_risk = draws.n_risk  # (M, N): the followed cells of every individual in every dataset
 
     def logp_dlogp(self, dataset, q):
         return self._dev.logp_dlogp(dataset, q)
 
     def loglik_sums(self, dataset, q):
         return self._dev.loglik_sums(dataset, q)
+
+    def draws_individual_loglik(self, dataset, q):
+        """(n,) (or one index) and (n, D) -> (n, N): every individual's log-likelihood at every point on the point's dataset -- the
+        bits of the plug-in model of ``SurvivalDraws.arrays(m)``."""
+        return self._dev.draws_individual_loglik(dataset, q)
+
+    def draws_waic_reset(self):
+        self._dev.draws_waic_reset()
+
+    def draws_waic_accumulate(self, dataset, q):
+        """Folds the draws ``q`` (n, D), in order, each into the statistics of its own dataset ``dataset`` (n,)."""
+        self._dev.draws_waic_accumulate(dataset, q)
+
+    def draws_waic_stats(self):
+        """(lse, mean, m2 (M, N), n_draws (M,), n_cells (M, N)): per dataset, the statistics of the draws folded since ``draws_waic_reset``."""
+        return self._dev.draws_waic_stats()
+
+    def draws_loo_reserve(self, capacity: int):
+        """Room on the device for ``capacity`` draws of ``draws_individual_loglik`` per dataset (at most 16384); 0 releases it."""
+        self._dev.draws_loo_reserve(capacity)
+
+    def draws_loo_reset(self):
+        self._dev.draws_loo_reset()
+
+    def draws_loo_accumulate(self, dataset, q):
+        """Evaluates the draws ``q`` (n, D) and stores every row as the next draw of its dataset."""
+        self._dev.draws_loo_accumulate(dataset, q)
+
+    def draws_loo_stats(self):
+        """(elpd_loo, pareto_k, lppd, n_tail (M, N), n_draws (M,)): PSIS-LOO of every individual per dataset over the draws held."""
+        return self._dev.draws_loo_stats()
 
     def close(self):
         self._dev.close()
@@ -210,7 +244,8 @@ class SurvivalDrawsModel(_DrawsDeviceModel):
     """One Poisson hazard model over an ensemble of per-draw datasets (``abd_survival_draws`` in ``include/abd_hip.h``):
     ``names``, ``dim``, ``K``, ``n_datasets``, ``logp_dlogp(dataset, q)`` on the device -- an index and (D,) -> (logp, grad); (n,) and
     (n, D) -> arrays, every point on its own dataset, up to 16 per launch -- ``loglik_sums(dataset, q)``, ``constrain(q)`` and
-    ``close()``.  It has no WAIC and no predictive checks: those are the plug-in model's."""
+    ``close()``.  ``draws_individual_loglik``, ``draws_waic_*`` and ``draws_loo_*`` work per dataset (``waic_draws``, ``loo_draws``, ``compare_draws``;
+    DESIGN 30); it has no predictive checks: those are the plug-in model's."""
 
     def __init__(self, draws: SurvivalDraws, titers, antigens, priors=None, device: int = -1):
         from ._native import SurvivalDraws as _Dev
@@ -1043,6 +1078,242 @@ def compare_lines(table) -> list:
             f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}" for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
 
 
+# ---- model comparison of per-draw fits: WAIC and PSIS-LOO by individual per dataset, pooled by Rubin's rule ----
+
+# what ``waic_draws`` / ``loo_draws`` record in a fit of ``sample_draws``: per dataset (M, N), the draws per dataset (M,)
+DRAWS_WAIC_FIT_KEYS = ("draws_elpd_waic_ind", "draws_p_waic_ind", "draws_waic_n_cells", "draws_waic_n_draws")
+DRAWS_LOO_FIT_KEYS = ("draws_elpd_loo_ind", "draws_pareto_k_ind", "draws_lppd_ind", "draws_loo_n_cells", "draws_loo_n_draws")
+
+
+def _draws_rows(model, fit):
+    """(datasets (n,), q (n, D)): the points of a fit of ``sample_draws`` chain after chain, each with its chain's dataset."""
+    q = fit_points(model, fit)
+    chain_ds = np.asarray(fit["dataset"], dtype=np.int64).reshape(-1)
+    M = int(model.n_datasets)
+    if chain_ds.size < 1 or q.shape[0] % chain_ds.size:
+        raise ValueError(f"{q.shape[0]} points for {chain_ds.size} entries of dataset: not a fit of sample_draws")
+    if chain_ds.min() < 0 or chain_ds.max() >= M:
+        raise ValueError(f"the fit names datasets outside [0, {M}) of the model")
+    lacking = sorted(set(range(M)) - set(chain_ds.tolist()))
+    if lacking:
+        raise ValueError(f"the fit has no chain on the datasets {lacking}")
+    return np.repeat(chain_ds, q.shape[0] // chain_ds.size), q
+
+
+def pool_draws(per, ic: str = "waic") -> Dict[str, object]:
+    """The pooled read-out of per-dataset WAIC / PSIS-LOO dictionaries ``per`` (one per dataset: ``waic`` / ``loo``'s), multiple
+    imputation over the datasets by Rubin's rule:
+
+        elpd, p          the means over the datasets of elpd_m and p_m
+        W                the mean of se_m^2, the variance within a dataset (over its individuals)
+        B                the variance of elpd_m over the datasets (ddof = 1; 0 for one dataset)
+        se               sqrt(W + (1 + 1 / M) B)
+        frac_between     (1 + 1 / M) B over W + (1 + 1 / M) B (0 where that is 0): what the plug-in comparison cannot see
+        n_warn           WAIC: the (dataset, individual) pairs with p_waic_j > 0.4
+        n_bad            PSIS-LOO: those with pareto_k > 0.7
+        worst            (dataset, individual) with the largest p_waic_j / pareto_k (None without a followed individual)
+        elpd_m, p_m, se_m  (M,) per dataset; ``datasets``: the list ``per``; ``n_datasets``; ``n_draws`` (M,); ``ic``"""
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', got {ic!r}")
+    M = len(per)
+    if M < 1:
+        raise ValueError("no datasets")
+    ke, kp, kw = ("elpd_waic", "p_waic", "p_waic_i") if ic == "waic" else ("elpd_loo", "p_loo", "pareto_k")
+    elpd_m, p_m, se_m = (np.array([float(w[k]) for w in per]) for k in (ke, kp, "se"))
+    W = float(np.mean(se_m ** 2))
+    B = float(np.var(elpd_m, ddof=1)) if M > 1 else 0.0
+    between = (1.0 + 1.0 / M) * B
+    total = W + between
+    score = np.stack([np.where(np.asarray(w["n_readings_i"]) > 0, np.nan_to_num(np.asarray(w[kw], dtype=np.float64), nan=-np.inf), -np.inf)
+                      for w in per])
+    worst = tuple(int(v) for v in np.unravel_index(int(np.argmax(score)), score.shape)) if (score > -np.inf).any() else None
+    out = dict(ic=ic, elpd=float(np.mean(elpd_m)), p=float(np.mean(p_m)), W=W, B=B, se=float(np.sqrt(total)),
+               frac_between=between / total if total > 0 else 0.0, n_warn=int(sum(w["n_warn"] for w in per)), worst=worst,
+               elpd_m=elpd_m, p_m=p_m, se_m=se_m, datasets=list(per), n_datasets=M, n_draws=np.array([int(w["n_draws"]) for w in per], dtype=np.int64),
+               n_individuals=int(per[0]["elpd_i"].size))
+    if ic == "loo":
+        out["n_bad"] = int(sum(w["n_bad"] for w in per))
+    return out
+
+
+def _record_window(model, fit):
+    for k in ("start", "end"):
+        if hasattr(model, k):
+            fit[k] = np.array(getattr(model, k), dtype=np.int64)
+
+
+def waic_draws(model, fit, pointwise: Optional[Callable] = None) -> Dict[str, object]:
+    """WAIC by individual of a fit of ``sample_draws``, per dataset and pooled: every draw is scored on the dataset of
+    its chain -- the device keeps one set of statistics per dataset (``model.draws_waic_reset`` / ``draws_waic_accumulate`` / ``draws_waic_stats``),
+    the chains of a dataset folded chain after chain -- and dataset m gives ``compare.waic_from_individual_stats`` with
+    ``n_cells = n_risk[m]``: what ``waic`` returns for the plug-in model of that dataset and those draws.  Returns ``pool_draws``
+    of them.  The entries ``DRAWS_WAIC_FIT_KEYS`` (and ``start`` / ``end`` where the model knows its window) are recorded in ``fit``:
+    ``write`` stores them and ``compare_draws`` reads them.  The result does not depend on the order of the chains in the fit beyond
+    the order of the chains of one dataset.
+    ``pointwise``: a host callable (datasets (n,), q (n, D)) -> (n, N) in the device's place (tests); the model then needs ``names``,
+    ``n_datasets`` and ``n_risk`` (M, N)."""
+    ds, q = _draws_rows(model, fit)
+    M = int(model.n_datasets)
+    if pointwise is not None:
+        n_cells = np.asarray(model.n_risk, dtype=np.int64)
+        stats = []
+        for m in range(M):
+            rows = q[ds == m]
+            stats.append(_compare.stats_from_matrix(np.asarray(pointwise(np.full(rows.shape[0], m, dtype=np.int32), rows), dtype=np.float64)))
+    else:
+        model.draws_waic_reset()
+        model.draws_waic_accumulate(ds, q)
+        lse, mean, m2, n_draws, n_cells = model.draws_waic_stats()
+        stats = [(lse[m], mean[m], m2[m], int(n_draws[m])) for m in range(M)]
+    per = [_compare.waic_from_individual_stats(stats[m], n_cells[m]) for m in range(M)]
+    fit["draws_elpd_waic_ind"], fit["draws_p_waic_ind"] = np.stack([w["elpd_i"] for w in per]), np.stack([w["p_waic_i"] for w in per])
+    fit["draws_waic_n_cells"] = np.stack([w["n_readings_i"] for w in per])
+    fit["draws_waic_n_draws"] = np.array([w["n_draws"] for w in per], dtype=np.int64)
+    _record_window(model, fit)
+    return pool_draws(per, "waic")
+
+
+def loo_draws(model, fit, pointwise: Optional[Callable] = None) -> Dict[str, object]:
+    """PSIS-LOO by individual of a fit of ``sample_draws``, per dataset and pooled: the device keeps one draws x
+    individuals matrix per dataset (``model.draws_loo_reserve`` with the largest number of draws of a dataset, ``draws_loo_accumulate``),
+    smooths every column of every dataset over that dataset's own draws (``draws_loo_stats``) and releases the room; dataset m gives
+    ``compare.loo_from_individual`` with ``n_cells = n_risk[m]``: what ``loo`` returns for the plug-in model of that dataset and
+    those draws.  Returns ``pool_draws`` of them and records ``DRAWS_LOO_FIT_KEYS`` in ``fit``.  More than 16384 draws of one
+    dataset are refused.
+    ``pointwise``: as in ``waic_draws``, smoothed by ``compare.psis_loo_from_matrix``."""
+    ds, q = _draws_rows(model, fit)
+    M = int(model.n_datasets)
+    n_cells = np.asarray(model.n_risk, dtype=np.int64)
+    counts = np.bincount(ds, minlength=M)
+    if pointwise is not None:
+        vals = []
+        for m in range(M):
+            rows = q[ds == m]
+            ll = np.asarray(pointwise(np.full(rows.shape[0], m, dtype=np.int32), rows), dtype=np.float64)
+            vals.append(_compare.psis_loo_from_matrix(ll, n_cells[m])[:3])
+        n_draws = counts
+    else:
+        model.draws_loo_reserve(int(counts.max()))
+        try:
+            model.draws_loo_accumulate(ds, q)
+            elpd, k, lppd, _, n_draws = model.draws_loo_stats()
+        finally:
+            model.draws_loo_reserve(0)
+        vals = [(elpd[m], k[m], lppd[m]) for m in range(M)]
+    per = [_compare.loo_from_individual(*vals[m], n_cells[m], int(n_draws[m])) for m in range(M)]
+    fit["draws_elpd_loo_ind"], fit["draws_pareto_k_ind"] = np.stack([w["elpd_i"] for w in per]), np.stack([w["pareto_k"] for w in per])
+    fit["draws_lppd_ind"], fit["draws_loo_n_cells"] = np.stack([w["lppd_i"] for w in per]), np.stack([w["n_readings_i"] for w in per])
+    fit["draws_loo_n_draws"] = np.array([w["n_draws"] for w in per], dtype=np.int64)
+    _record_window(model, fit)
+    return pool_draws(per, "loo")
+
+
+def draws_ic_of_fit(fit, ic: str = "waic") -> Dict[str, object]:
+    """The dictionary of ``waic_draws`` / ``loo_draws`` again from the entries it recorded in a fit (or that ``write`` stored)."""
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', got {ic!r}")
+    keys = DRAWS_WAIC_FIT_KEYS if ic == "waic" else DRAWS_LOO_FIT_KEYS
+    lacking = [k for k in keys if k not in fit]
+    if lacking:
+        what = "waic_draws(model, fit), or --per_draw_ic waic" if ic == "waic" else "loo_draws(model, fit), or --per_draw_ic loo"
+        raise ValueError(f"no per-draw {'WAIC' if ic == 'waic' else 'PSIS-LOO'} in the fit ({what}): {lacking} missing")
+    n_cells, n_draws = np.asarray(fit[keys[-2]], dtype=np.int64), np.asarray(fit[keys[-1]], dtype=np.int64).reshape(-1)
+    if n_cells.ndim != 2 or n_draws.size != n_cells.shape[0]:
+        raise ValueError(f"{keys[-2]} must be (M, N) with one entry of {keys[-1]} per dataset, got {n_cells.shape} and {n_draws.shape}")
+    per = []
+    for m in range(n_cells.shape[0]):
+        if ic == "waic":
+            per.append(waic_of_fit({"elpd_waic_ind": fit[keys[0]][m], "p_waic_ind": fit[keys[1]][m], "waic_n_cells": n_cells[m],
+                                    "waic_n_draws": n_draws[m]}))
+        else:
+            per.append(_compare.loo_from_individual(fit[keys[0]][m], fit[keys[1]][m], fit[keys[2]][m], n_cells[m], int(n_draws[m])))
+    return pool_draws(per, ic)
+
+
+def compare_draws(fits, ic: str = "waic") -> Dict[str, Dict[str, float]]:
+    """Rank per-draw fits of ONE ``SurvivalDraws`` (``{name: fit}``, every fit with the entries of ``waic_draws``, or of ``loo_draws``
+    for ``ic="loo"``) by their pooled elpd.  Fits without those entries (a plug-in fit among them), or that differ in ``source``, in
+    the number of datasets, in ``start`` / ``end``, in the number of individuals or in which of them are followed in which dataset,
+    are a ``ValueError`` that names the odd ones out.  Per model:
+
+        rank, elpd, p, se, frac_between   ``pool_draws``' values (rank 0 = the largest pooled elpd)
+        elpd_diff       the mean over the datasets of elpd_diff_m = elpd_m of the top-ranked model minus this one's
+        dse             sqrt(mean dse_m^2 + (1 + 1 / M) var_m(elpd_diff_m)) (ddof = 1; 0 for one dataset), dse_m the paired standard
+                        error over the individuals followed in dataset m, sqrt(n Var_j(elpd_j^top - elpd_j^this)) (ddof 0), as
+                        ``compare.compare(..., by="individual")`` computes it
+        dse_frac_between  the share of dse^2 that lies between the datasets
+        p_ahead         the share of the datasets in which this model's elpd_m is above the top-ranked one's
+        n_warn          the (dataset, individual) pairs with p_waic_j > 0.4 (``ic="loo"``: with pareto_k > 0.7)
+        elpd_diff_m, dse_m   (M,) per dataset
+    With ``ic="loo"`` the rows hold ``elpd_loo`` / ``p_loo`` beside ``elpd`` / ``p``, else ``elpd_waic`` / ``p_waic``."""
+    if ic not in ("waic", "loo"):
+        raise ValueError(f"ic must be 'waic' or 'loo', got {ic!r}")
+    if not fits:
+        raise ValueError("no fits")
+    w, kind = {}, {}
+    for name, fit in fits.items():
+        try:
+            w[name] = draws_ic_of_fit(fit, ic)
+        except ValueError as e:
+            raise ValueError(f"{name}: {e}") from None
+        if "source" not in fit:
+            raise ValueError(f"{name}: no source in the fit (the (chain, draw) of every dataset: a fit of sample_draws records it)")
+        span = tuple(int(np.asarray(fit[k])) if k in fit else None for k in ("start", "end"))
+        followed = np.stack([np.asarray(v["n_readings_i"]) > 0 for v in w[name]["datasets"]])
+        kind[name] = (np.asarray(fit["source"], dtype=np.int64).tobytes(), w[name]["n_datasets"], span, followed.shape[1], followed.tobytes())
+    kinds = list(kind.values())
+    usual = max(kinds, key=kinds.count)  # the first of the most frequent
+    odd = [name for name, k in kind.items() if k != usual]
+    if odd:
+        what = ("source", "the number of datasets", "start / end", "the number of individuals", "which individuals are followed")
+        raise ValueError("; ".join(f"{name} differs from the others in " + ", ".join(t for t, a, b in zip(what, kind[name], usual) if a != b)
+                                   for name in odd))
+    order = sorted(w, key=lambda k: -w[k]["elpd"])
+    top = w[order[0]]
+    M = top["n_datasets"]
+    out = {}
+    for rank, name in enumerate(order):
+        v = w[name]
+        diff_m, dse_m = np.zeros(M), np.zeros(M)
+        for m in range(M):
+            a, b = top["datasets"][m], v["datasets"][m]
+            d = (a["elpd_i"] - b["elpd_i"])[b["n_readings_i"] > 0]
+            diff_m[m] = top["elpd_m"][m] - v["elpd_m"][m]
+            dse_m[m] = float(np.sqrt(d.size * np.var(d))) if d.size else 0.0
+        within = float(np.mean(dse_m ** 2))
+        between = (1.0 + 1.0 / M) * (float(np.var(diff_m, ddof=1)) if M > 1 else 0.0)
+        row = dict(rank=rank, elpd=v["elpd"], p=v["p"], se=v["se"], frac_between=v["frac_between"], elpd_diff=float(np.mean(diff_m)),
+                   dse=float(np.sqrt(within + between)), dse_frac_between=between / (within + between) if within + between > 0 else 0.0,
+                   p_ahead=float(np.mean(v["elpd_m"] > top["elpd_m"])), n_warn=v["n_bad"] if ic == "loo" else v["n_warn"],
+                   elpd_diff_m=diff_m, dse_m=dse_m, n_datasets=M)
+        row["elpd_loo" if ic == "loo" else "elpd_waic"], row["p_loo" if ic == "loo" else "p_waic"] = v["elpd"], v["p"]
+        out[name] = row
+    return out
+
+
+def draws_ic_line(w) -> str:
+    """One line of ``waic_draws`` / ``loo_draws``: the pooled elpd, p, se, the share between the datasets and the warnings."""
+    if w["ic"] == "loo":
+        line = (f"survival per-draw PSIS-LOO: elpd_loo {w['elpd']:.3f}  p_loo {w['p']:.3f}  se {w['se']:.3f}  frac_between {w['frac_between']:.3f}  "
+                f"({w['n_datasets']} datasets, {w['n_individuals']} individuals; {w['n_bad']} with pareto_k > 0.7)")
+        if w["n_bad"]:
+            m, j = w["worst"]
+            line += f"; warning: the estimate is unreliable for them, worst: dataset {m} individual {j} pareto_k {w['datasets'][m]['pareto_k'][j]:.2f}"
+        return line
+    return (f"survival per-draw WAIC: elpd_waic {w['elpd']:.3f}  p_waic {w['p']:.3f}  se {w['se']:.3f}  frac_between {w['frac_between']:.3f}  "
+            f"({w['n_datasets']} datasets, {w['n_individuals']} individuals; {w['n_warn']} with p_waic_j > 0.4)")
+
+
+def draws_compare_lines(table) -> list:
+    """One row per model of ``compare_draws``' table, best first."""
+    width = max(len(str(name)) for name in table)
+    loo_ = all("elpd_loo" in v for v in table.values())
+    e, p, warn = ("elpd_loo", "p_loo", "pareto_k > 0.7") if loo_ else ("elpd_waic", "p_waic", "p_waic_j > 0.4")
+    return [f"{str(name):<{width}}  rank {v['rank']}  {e} {v['elpd']:.3f}  {p} {v['p']:.3f}  se {v['se']:.3f}  frac_between {v['frac_between']:.3f}  "
+            f"elpd_diff {v['elpd_diff']:.3f}  dse {v['dse']:.3f}  p_ahead {v['p_ahead']:.2f}  {warn}: {v['n_warn']}  ({v['n_datasets']} datasets)"
+            for name, v in sorted(table.items(), key=lambda kv: kv[1]["rank"])]
+
+
 # ---- posterior predictive checks (abd_survival_predictive_*; DESIGN 25) ----
 
 PPC_MAX_EDGES = 7  # up to 8 bins per binning variable
@@ -1392,6 +1663,10 @@ def main(argv=None) -> int:
                     "the datasets; the output also holds dataset, source, n_evaluations and the draws_* entries.  Needs a posterior with "
                     "recorded draws (abdpymc-infer --thin).")
     ap.add_argument("--per_draw_chains", type=int, metavar="C", help="With --per_draw: chains per dataset (default 1); --chains is not used then.")
+    ap.add_argument("--per_draw_ic", choices=("waic", "loo", "both"), help="With --per_draw: score every dataset's draws on that dataset by WAIC "
+                    "and / or PSIS-LOO over the individuals on the device and pool them by Rubin's rule: one more line on stdout per criterion "
+                    "(pooled elpd, p, se, the share between the datasets, the warnings), and the draws_elpd_waic_ind ... / draws_elpd_loo_ind ... "
+                    "entries, start and end in the output (what --compare reads for per-draw fits).")
     ap.add_argument("--tune", type=int, default=1000)
     ap.add_argument("--draws", type=int, default=1000)
     ap.add_argument("--chains", type=int, default=4)
@@ -1416,14 +1691,17 @@ def main(argv=None) -> int:
         ap.error("--ppc_edges_s / --ppc_edges_n / --ppc_seed go with --ppc")
     if args.per_draw is None and args.per_draw_chains is not None:
         ap.error("--per_draw_chains goes with --per_draw")
+    if args.per_draw is None and args.per_draw_ic is not None:
+        ap.error("--per_draw_ic goes with --per_draw")
     if args.per_draw is not None:
         if args.model not in ("s", "n", "combined"):
             ap.error(f"--per_draw fits --model s | n | combined here; per-draw fits of --model {args.model} are in Python: "
                      "SurvivalAnalysis.model_alone_groups_draws / model_alone_periods_draws with sample_draws and draws_summary")
         if args.waic or args.ppc:
-            ap.error("--per_draw does not go with --waic / --ppc: WAIC and predictive checks of a per-draw fit are not built")
+            ap.error("--per_draw does not go with --waic / --ppc: WAIC of a per-draw fit is --per_draw_ic waic (per dataset, pooled); "
+                     "predictive checks of a per-draw fit are not built")
         if args.loo:
-            ap.error("--per_draw does not go with --loo: PSIS-LOO of a per-draw fit is not built")
+            ap.error("--per_draw does not go with --loo: PSIS-LOO of a per-draw fit is --per_draw_ic loo (per dataset, pooled)")
         if args.per_draw < 1 or (args.per_draw_chains is not None and args.per_draw_chains < 1):
             ap.error("--per_draw and --per_draw_chains must be >= 1")
     ppc_edges = {}
@@ -1485,14 +1763,21 @@ def _main_per_draw(args, sa) -> int:
     caller's to report."""
     datasets = sa.draws(n_datasets=args.per_draw)
     model = sa.model_combined_draws(datasets) if args.model == "combined" else sa.model_alone_draws(args.model.upper(), datasets)
+    scores = []
     try:
         res = sample_draws(model, tune=args.tune, draws=args.draws, chains_per_dataset=args.per_draw_chains or 1, seed=args.seed)
+        if args.per_draw_ic in ("waic", "both"):
+            scores.append(waic_draws(model, res))
+        if args.per_draw_ic in ("loo", "both"):
+            scores.append(loo_draws(model, res))  # (a ValueError -- more draws of a dataset than the device keeps -- is the caller's)
     finally:
         model.close()
     sm = draws_summary(res)
     res.update(draws_fit_keys(sm))
     between = ", ".join(f"{k} {sm[k]['frac_between']:.3f}" for k in sm if k[0] in "ab")
     print(f"{report_line(res)}; per-draw fits of {datasets.n_datasets} datasets, share of the variance between datasets: {between}")
+    for w in scores:
+        print(draws_ic_line(w))  # --per_draw_ic: one line per criterion after the pooled line
     out = write(res, args.out, sa)
     print(f"wrote {out}", file=sys.stderr)
     return 0
@@ -1507,12 +1792,20 @@ def _main_compare(paths, ic: str = "waic") -> int:
         if name in fits:
             raise SystemExit(f"survival: two fits are called {name}")
         with np.load(path, allow_pickle=False) as f:
-            fits[name] = {k: f[k] for k in WAIC_FIT_KEYS + LOO_FIT_KEYS + ("start", "end") if k in f.files}
+            fits[name] = {k: f[k] for k in WAIC_FIT_KEYS + LOO_FIT_KEYS + DRAWS_WAIC_FIT_KEYS + DRAWS_LOO_FIT_KEYS + ("start", "end", "source")
+                          if k in f.files}
+    # per-draw fits (written with --per_draw_ic) get the pooled table; a mixture of per-draw and plug-in fits is an error
+    keys = DRAWS_WAIC_FIT_KEYS if ic == "waic" else DRAWS_LOO_FIT_KEYS
+    per_draw = [name for name, fit in fits.items() if all(k in fit for k in keys)]
+    if per_draw and len(per_draw) < len(fits):
+        rest = [name for name in fits if name not in per_draw]
+        raise SystemExit(f"survival: {', '.join(per_draw)} hold the per-draw entries {keys[0]} ... (--per_draw_ic) and {', '.join(rest)} "
+                         f"{'does' if len(rest) == 1 else 'do'} not: compare per-draw fits with per-draw fits")
     try:
-        table = compare(fits, ic=ic)
+        lines = draws_compare_lines(compare_draws(fits, ic=ic)) if per_draw else compare_lines(compare(fits, ic=ic))
     except ValueError as e:
         raise SystemExit(f"survival: {e}")
-    for line in compare_lines(table):
+    for line in lines:
         print(line)
     return 0
 
@@ -1521,11 +1814,12 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
     """``.npz``; NetCDF through ``cli.write_posterior`` where ArviZ imports and the name does not end in ``.npz`` (no test covers
     that branch: ArviZ is optional and the suite does not require it).  A fit that ``waic`` has scored is stored with its
     ``elpd_waic_ind``, ``p_waic_ind``, ``waic_n_cells``, ``waic_n_draws`` (one that ``loo`` has scored with ``LOO_FIT_KEYS``) and the window ``start`` / ``end`` -- in the ``.npz`` form,
-    which is what ``--compare`` reads; the NetCDF form holds the draws alone.  Likewise ``groups`` / ``group_name`` and ``periods`` /
+    which is what ``--compare`` reads; the NetCDF form holds the draws alone.  The same goes for a fit of ``sample_draws`` that ``waic_draws`` /
+    ``loo_draws`` have scored (``DRAWS_WAIC_FIT_KEYS``, ``DRAWS_LOO_FIT_KEYS``).  Likewise ``groups`` / ``group_name`` and ``periods`` /
     ``period_name`` / ``period_index`` are stored in the ``.npz`` form only: ``protection(group= / period= / interval=)`` needs a fit
     written as ``.npz``.  So are the entries ``PPC_FIT_KEYS`` of a fit that ``predictive`` has checked."""
     path = str(path)
-    if "elpd_waic_ind" in res or "elpd_loo_ind" in res:
+    if any(k in res for k in ("elpd_waic_ind", "elpd_loo_ind", "draws_elpd_waic_ind", "draws_elpd_loo_ind")):
         res = dict(res, start=np.array(sa.start, dtype=np.int64), end=np.array(sa.end, dtype=np.int64))
     if not path.endswith(".npz"):
         try:
@@ -1533,7 +1827,7 @@ def write(res, path: str, sa: "SurvivalAnalysis") -> str:
 
             from .cli import write_posterior
 
-            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + LOO_FIT_KEYS + PPC_FIT_KEYS + DRAWS_FIT_KEYS}
+            data = {k: v for k, v in res.items() if k not in ("antigens", "groups", "group_name", "periods", "period_name", "period_index", "start", "end") + WAIC_FIT_KEYS + LOO_FIT_KEYS + PPC_FIT_KEYS + DRAWS_FIT_KEYS + DRAWS_WAIC_FIT_KEYS + DRAWS_LOO_FIT_KEYS}
             return write_posterior(data, path, dict(gap=sa.intervals, ind=np.arange(sa.infected.shape[0])))
         except ImportError:
             path += ".npz"

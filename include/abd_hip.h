@@ -935,6 +935,35 @@ typedef struct {
 int abd_survival_draws_create_groups(const abd_survival_draws_groups_desc* desc, abd_survival_draws** out);
 int abd_survival_draws_create_periods(const abd_survival_draws_periods_desc* desc, abd_survival_draws** out);
 
+/* Model comparison of per-draw fits: the per-individual log-likelihood, its WAIC statistics and PSIS-LOO of an
+ * abd_survival_draws handle of any of the three creators, per dataset.  Every point names its dataset, point q is on dataset[q]
+ * in [0, M) (ABD_ERR_ARG otherwise, "point q: dataset m outside [0, M)"; nothing is launched then); any n, up to ABD_MAX_BATCH
+ * points of any datasets share a launch.  Per-individual outputs are in the caller's order of individuals, by group too.
+ * _individual_loglik: ll[n][N]; a row on dataset m is, bit for bit, what abd_survival_individual_loglik returns on a handle of
+ *   abd_survival_create / _create_groups / _create_periods made of that dataset's (infected, exposure, titer) and the same labels.
+ * _waic_accumulate folds the rows of theta[n][D], each into the statistics of its own dataset, in order.  The statistics of dataset
+ *   m depend on that dataset's rows and their order alone: not on how the rows were split over calls or launches, and not on which
+ *   other datasets' rows stood between them; they are the bits of abd_survival_waic_* on the plug-in handle of that dataset.
+ *   _waic_reset forgets all draws of all datasets.  _waic_stats: lse, mean, m2 [M][N], n_draws[M], n_cells[M][N] (= n_risk); a
+ *   dataset without a draw holds NaN and n_draws = 0; ABD_ERR_ARG before any draw of any dataset.
+ * _loo_reserve: room for `capacity` draws PER DATASET, 8 bytes per draw, dataset and slot of 64-padded individuals; forgets the
+ *   draws held; 0 releases.  ABD_ERR_ARG for a capacity that is negative or above ABD_SURVIVAL_LOO_MAX_DRAWS, ABD_ERR_NOMEM, the
+ *   message naming the bytes, when the device cannot hold them.  _loo_reset forgets the draws held, keeps the room.
+ * _loo_accumulate evaluates theta[n][D] and stores every row as the next draw of its dataset.  ABD_ERR_STATE, before anything is
+ *   launched and with nothing stored, when nothing is reserved or the rows of the call would take a dataset past the capacity.
+ * _loo_stats: per dataset over the S_m draws it holds, the estimator of abd_survival_loo_stats with n_cells = n_risk: elpd_loo,
+ *   pareto_k, lppd, n_tail [M][N] and n_draws[M]; the bits of abd_survival_loo_stats on the plug-in handle of that dataset with
+ *   the same draws.  A dataset without a draw holds NaN, n_tail = 0 and n_draws = 0.  ABD_ERR_STATE when nothing is reserved,
+ *   ABD_ERR_ARG before any draw of any dataset. */
+int abd_survival_draws_individual_loglik(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* ll);
+int abd_survival_draws_waic_reset(abd_survival_draws* s);
+int abd_survival_draws_waic_accumulate(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta);
+int abd_survival_draws_waic_stats(abd_survival_draws* s, double* lse, double* mean, double* m2, int64_t* n_draws, int32_t* n_cells);
+int abd_survival_draws_loo_reserve(abd_survival_draws* s, int64_t capacity_per_dataset);
+int abd_survival_draws_loo_reset(abd_survival_draws* s);
+int abd_survival_draws_loo_accumulate(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta);
+int abd_survival_draws_loo_stats(abd_survival_draws* s, double* elpd_loo, double* pareto_k, double* lppd, int32_t* n_tail, int64_t* n_draws);
+
 /* ---------------------------------------------------------------------------------------------------
  * Environment variables the library reads (all optional; read at abd_create / abd_sampler_create / first use).
  * This table is complete: the product library calls getenv for nothing else (development knobs of launch shapes

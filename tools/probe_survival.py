@@ -18,6 +18,12 @@ jittered points of the combined model beside ``waic_accumulate`` + ``waic_stats`
 alternating, ``--reps`` times, and ``compare.psis_loo_from_matrix`` on this host over ``--host_columns`` individuals of the same
 matrix, scaled to the cohort.
 
+``--leg draws_ic`` times the model comparison of per-draw fits for the combined model: (a) the ensemble WAIC fold and the
+ensemble PSIS-LOO of ``--datasets`` x ``--draws_per_dataset`` draws on one ``SurvivalDrawsModel`` against (b) what there was before it,
+a loop over the datasets of creating ``SurvivalModel(*d.arrays(m))`` and calling ``survival.waic`` / ``survival.loo`` on it, creation
+included; both in this process, alternating, ``--reps`` times; and the plug-in fold of one dataset's draws on a resident handle, for
+the per-row kernel time.
+
 ``--periods P [P]`` times the model by period in the same way, with P periods of equal length (0: monthly, P = T),
 every P at both sizes, beside the ungrouped K = 1 model on the same data in the same run; ``--fit`` adds the wall time of a
 ``--tune`` + ``--draws`` x 4-chain fit of each of them and of the K = 1 model.
@@ -28,6 +34,7 @@ every P at both sizes, beside the ungrouped K = 1 model on the same data in the 
     python tools/probe_survival.py --leg waic [--points 4000] [--reps 3] [--out FILE]
     python tools/probe_survival.py --leg ppc [--points 4000] [--reps 3] [--out FILE]
     python tools/probe_survival.py --leg loo [--points 4000] [--reps 5] [--host_columns 500] [--out FILE]
+    python tools/probe_survival.py --leg draws_ic [--datasets 64] [--draws_per_dataset 1000] [--reps 3] [--out FILE]
 """
 import argparse
 import json
@@ -263,11 +270,109 @@ def probe_loo(N, T, points, reps, host_columns):
     return row
 
 
+def simulate_draws(M, N, T, seed=0):
+    """M event-time datasets from the combined model of ``simulate``: per dataset its own titers, one infection at most, at risk
+    until it or until a random last interval."""
+    n_risk, event = np.empty((M, N), np.int32), np.empty((M, N), np.int32)
+    xs, xn = np.empty((M, T, N)), np.empty((M, T, N))
+    for m in range(M):
+        rng = np.random.default_rng([seed, m, N, T])
+        xs[m], xn[m] = rng.uniform(0.0, 4.0, size=(T, N)), rng.uniform(0.0, 4.0, size=(T, N))
+        lam0 = rng.uniform(0.02, 0.08, size=T)
+        hit = rng.random((T, N)) < lam0[:, None] / (1.0 + np.exp(-(1.5 * (xs[m] - 1.5) + 0.5 * (xn[m] - 1.0))))
+        first = np.where(hit.any(axis=0), hit.argmax(axis=0), T)
+        last = rng.integers(max(1, T // 2), T + 1, size=N)
+        n_risk[m] = np.minimum(first + 1, last)
+        event[m] = np.where(first < last, first, -1)
+    return survival.SurvivalDraws(n_risk, event, xs, xn, np.stack([np.zeros(M, np.int64), np.arange(M)], axis=1))
+
+
+def probe_draws_ic(N, T, M, S, reps):
+    """One row: WAIC and PSIS-LOO of M x S draws, every draw on its own dataset -- (a) on the ensemble handle, (b) by a loop over M
+    plug-in handles, creation included -- alternating, ``reps`` times; host clocks around calls that end in a synchronise."""
+    d = simulate_draws(M, N, T)
+    rng = np.random.default_rng(1)
+    ens = survival.SurvivalDrawsModel(d, [d.s_titer, d.n_titer], ("S", "N"))
+    q = np.zeros((M * S, ens.dim))
+    q[:, 4], q[:, 5] = -3.0, np.log(0.5)
+    q += rng.uniform(-0.5, 0.5, size=q.shape)
+    ds = np.repeat(np.arange(M, dtype=np.int32), S)  # dataset-major, as waic_draws hands a fit of sample_draws over
+    fit_of = lambda rows: {name: rows[None, :, k] for k, name in enumerate(ens.names)}  # noqa: E731
+    row = {"N": N, "T": T, "K": 2, "datasets": M, "draws_per_dataset": S, "launches": (M * S + 15) // 16,
+           "titer_bytes": 2 * 8 * M * T * 64 * ((N + 63) // 64), "loo_matrix_bytes": 8 * M * 64 * ((N + 63) // 64) * S,
+           "ensemble_waic_ms": [], "ensemble_loo_ms": [], "loop_waic_ms": [], "loop_loo_ms": [], "loop_create_ms": [], "resident_waic_ms": []}
+    ens.draws_waic_accumulate(ds[:64], q[:64])  # warm up: the buffers of the first call, the code objects
+    ens.draws_loo_reserve(64)
+    ens.draws_loo_accumulate(ds[:64], q[:64])
+    ens.draws_loo_stats()
+    ens.draws_loo_reserve(0)
+
+    def plug_in(m):
+        y, e, xs, xn = d.arrays(m)
+        return survival.SurvivalModel(y, e, [xs, xn], ("S", "N"))
+
+    resident = plug_in(0)
+    resident.waic_accumulate(q[:64])
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        ens.draws_waic_reset()
+        ens.draws_waic_accumulate(ds, q)
+        a_waic = ens.draws_waic_stats()
+        row["ensemble_waic_ms"].append(1e3 * (time.perf_counter() - t0))
+        t0 = time.perf_counter()
+        ens.draws_loo_reserve(S)
+        ens.draws_loo_accumulate(ds, q)
+        a_loo = ens.draws_loo_stats()
+        ens.draws_loo_reserve(0)
+        row["ensemble_loo_ms"].append(1e3 * (time.perf_counter() - t0))
+        create = 0.0
+        t0 = time.perf_counter()
+        for m in range(M):
+            t1 = time.perf_counter()
+            sm = plug_in(m)
+            create += time.perf_counter() - t1
+            b_waic = survival.waic(sm, fit_of(q[m * S:(m + 1) * S]))
+            sm.close()
+        row["loop_waic_ms"].append(1e3 * (time.perf_counter() - t0))
+        row["loop_create_ms"].append(1e3 * create)
+        t0 = time.perf_counter()
+        for m in range(M):
+            sm = plug_in(m)
+            b_loo = survival.loo(sm, fit_of(q[m * S:(m + 1) * S]))
+            sm.close()
+        row["loop_loo_ms"].append(1e3 * (time.perf_counter() - t0))
+        resident.waic_reset()
+        t0 = time.perf_counter()
+        resident.waic_accumulate(q[:S])
+        resident.waic_stats()
+        row["resident_waic_ms"].append(1e3 * (time.perf_counter() - t0))
+    # the last dataset's result of both paths: the same bits
+    w_last = survival._compare.waic_from_individual_stats((a_waic[0][M - 1], a_waic[1][M - 1], a_waic[2][M - 1], int(a_waic[3][M - 1])), a_waic[4][M - 1])
+    row["same_bits_waic"] = bool(np.array_equal(w_last["elpd_i"], b_waic["elpd_i"]))
+    row["same_bits_loo"] = bool(np.array_equal(a_loo[0][M - 1], b_loo["elpd_i"]) and np.array_equal(a_loo[1][M - 1], b_loo["pareto_k"], equal_nan=True))
+    resident.close()
+    ens.close()
+    for k in ("ensemble_waic_ms", "ensemble_loo_ms", "loop_waic_ms", "loop_loo_ms", "loop_create_ms", "resident_waic_ms"):
+        row["best_" + k], row["median_" + k] = min(row[k]), float(np.median(row[k]))
+    row["ensemble_waic_us_per_draw"] = 1e3 * row["best_ensemble_waic_ms"] / (M * S)
+    row["ensemble_loo_us_per_draw"] = 1e3 * row["best_ensemble_loo_ms"] / (M * S)
+    row["loop_waic_us_per_draw"] = 1e3 * row["best_loop_waic_ms"] / (M * S)
+    row["loop_loo_us_per_draw"] = 1e3 * row["best_loop_loo_ms"] / (M * S)
+    row["resident_waic_us_per_draw"] = 1e3 * row["best_resident_waic_ms"] / S
+    row["loop_over_ensemble_waic"] = row["best_loop_waic_ms"] / row["best_ensemble_waic_ms"]
+    row["loop_over_ensemble_loo"] = row["best_loop_loo_ms"] / row["best_ensemble_loo_ms"]
+    row["ensemble_over_resident_per_draw"] = row["ensemble_waic_us_per_draw"] / row["resident_waic_us_per_draw"]
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=("eval", "waic", "ppc", "loo"), default="eval",
+    ap.add_argument("--leg", choices=("eval", "waic", "ppc", "loo", "draws_ic"), default="eval",
                     help="eval: the evaluator and a fit (the default); waic: scoring a fit; ppc: the posterior predictive check beside the WAIC fold; "
-                    "loo: PSIS-LOO beside the WAIC fold and beside the host path")
+                    "loo: PSIS-LOO beside the WAIC fold and beside the host path; draws_ic: WAIC and PSIS-LOO of per-draw fits on the ensemble "
+                    "handle beside a loop over plug-in handles")
+    ap.add_argument("--datasets", type=int, default=64, help="--leg draws_ic: datasets of the ensemble")
+    ap.add_argument("--draws_per_dataset", type=int, default=1000, help="--leg draws_ic: draws scored on every dataset")
     ap.add_argument("--host_columns", type=int, default=500, help="--leg loo: individuals the host path is timed on (0: all)")
     ap.add_argument("--points", type=int, default=4000, help="--leg waic / ppc: draws folded per repeat")
     ap.add_argument("--reps", type=int, default=3, help="--leg waic / ppc: repeats")
@@ -292,6 +397,14 @@ def main(argv=None):
         for N, T in SIZES:
             rows.append(probe_loo(N, T, args.points, args.reps, args.host_columns))
             print(json.dumps(rows[-1]), flush=True)
+    if args.leg == "draws_ic":
+        for N, T in SIZES:
+            rows.append(probe_draws_ic(N, T, args.datasets, args.draws_per_dataset, args.reps))
+            print(json.dumps(rows[-1]), flush=True)
+            if args.out:  # kept row by row: a run that is cut short leaves what it measured
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "w") as f:
+                    json.dump(rows, f, indent=1)
     if args.groups:
         if len(args.groups) not in (1, len(SIZES)):
             ap.error(f"--groups takes one figure or {len(SIZES)}")
