@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 from oracle import abd_oracle as O
+from tests import fused_launches as F
 from tests import mp_reference as R
 from tests.golden.make_tail_fixtures import case_check
 
@@ -153,21 +154,29 @@ def test_dense_evaluation_f32_storage(cname):
 
 @pytest.mark.parametrize("n", [4, 1])
 def test_fused_steps(n):
-    """logp_dlogp_many with K = 8: every row of every chain at another case (the cases that share the table's discrete state)"""
+    """logp_dlogp_many, every row of every chain at another case (the cases that share the table's discrete state): with K = 8, which
+    is too short to fuse on a context of more than one pipe and pins the unfused stream-ordered rows, and with K = 16 pipes + 3, where
+    the call must have run the fused launches of abd_fuse_plan.hpp (read back from the result slots: tests/fused_launches.py)"""
     cs = cases("65x33")
-    worst = Worst(f"fused steps, K = 8, {n} chains")
     rows = [r for r in cs.rows if r[4] is cs.rows[0][4] and r[2].tobytes() == cs.rows[0][2].tobytes()]
     assert len(rows) >= 24
-    ctx = _context(rows[0][4], n_chains=4)
+    ctx = _context(rows[0][4], n_chains=5)  # (one more chain slot than chains: the result slots then tell the launches apart)
     for slot in range(4):
         ctx.set_discrete(slot, rows[0][2], rows[0][3])
-    for start in range(0, len(rows), 8 * n):
-        pick = [[rows[(start + k * n + s) % len(rows)] for s in range(n)] for k in range(8)]
-        lp, g = ctx.logp_dlogp_many(np.arange(n), np.array([[r[1] for r in step] for step in pick]))
-        for k in range(8):
-            for s in range(n):
-                cname, c = pick[k][s][0], pick[k][s][5]
-                worst.check(f"row {k} chain {s}: {cname}", lp[k, s], g[k, s], cs.get("ref", c), cs.get("S", c))
+    K_fused = F.k_fused(ctx)
+    worst = Worst(f"fused steps, K = 8 and {K_fused}, {n} chains")
+    for K in (8, K_fused):
+        for start in range(0, len(rows), K * n):
+            pick = [[rows[(start + k * n + s) % len(rows)] for s in range(n)] for k in range(K)]
+            lp, g = ctx.logp_dlogp_many(np.arange(n), np.array([[r[1] for r in step] for step in pick]))
+            if K == K_fused:
+                F.assert_fused(ctx, K, n, 4, lp, g)
+            else:
+                assert F.observed_plan(ctx, K, n, lp, g) == F.fuse_plan(K, n, ctx.n_pipes, ctx.n_result_slots)
+            for k in range(K):
+                for s in range(n):
+                    cname, c = pick[k][s][0], pick[k][s][5]
+                    worst.check(f"K = {K}, row {k} chain {s}: {cname}", lp[k, s], g[k, s], cs.get("ref", c), cs.get("S", c))
     assert ctx.wait_fallbacks == 0
     ctx.close()
     worst.done()
