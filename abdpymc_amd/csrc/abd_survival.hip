@@ -1,21 +1,20 @@
 // abd_survival.hip -- the survival models of a finished run (include/abd_hip.h: abd_survival_*): creation of a
 // handle of any form, the launches of the data sums and of the per-individual log-likelihood, the WAIC accumulators, PSIS-LOO
-// over the resident matrix of those rows (abd_survival_loo_*; abd_psis.hpp), the posterior predictive checks (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of
-// per-draw datasets, a handle of its own kind and of any form (abd_survival_draws_*; abd_survival_draws.hpp, abd_survival_draws_forms.hpp),
-// with its own per-individual log-likelihood, WAIC and PSIS-LOO per dataset (abd_survival_draws_pointwise.hpp).  Both kinds run their
-// sums launches on one SurvivalSums.  A handle shares nothing with an abd_ctx.  The kernels are in abd_survival.hpp,
-// abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and abd_survival_predictive.hpp; the closed forms, the
-// packing of the planes and the form of a model (SurvivalForm) are plain C++ in the five *_terms.hpp beside them (SurvivalForm: at
-// the end of abd_survival_groups_terms.hpp).
+// over the resident matrix of those rows (abd_survival_loo_*; abd_psis.hpp), the posterior predictive checks
+// (abd_survival_predictive_*, abd_survival_replicate), and at the end the ensemble of per-draw datasets, a handle of its
+// own kind and of any form (abd_survival_draws_*), with its own per-individual log-likelihood, WAIC and PSIS-LOO per
+// dataset.  Both kinds run their sums on one SurvivalSums through one launcher (survival_sums_launch) and their
+// per-individual rows on one SurvivalPointRows through one launcher (survival_pointwise_kernel); what differs between them is the
+// preparation of a point's rows and where the per-individual rows go.  A handle shares nothing with an abd_ctx.  The
+// kernels are in abd_survival.hpp, abd_survival_groups.hpp, abd_survival_periods.hpp, abd_survival_pointwise.hpp and
+// abd_survival_predictive.hpp; the closed forms, the packing of the planes and the form of a model (SurvivalForm) are plain C++ in
+// the five *_terms.hpp beside them (SurvivalForm: at the end of abd_survival_groups_terms.hpp).
 #include <algorithm>
 #include <memory>
 
 #include "abd_host.hpp"
 #include "abd_psis.hpp"
 #include "abd_survival.hpp"
-#include "abd_survival_draws.hpp"
-#include "abd_survival_draws_forms.hpp"
-#include "abd_survival_draws_pointwise.hpp"
 #include "abd_survival_groups.hpp"
 #include "abd_survival_groups_terms.hpp"
 #include "abd_survival_periods.hpp"
@@ -36,15 +35,24 @@ struct SurvivalSpec {
 };
 constexpr int kSurvRepBatch = 4;  // points per launch of abd_survival_replicate: its per-cell buffer holds this many
 
+// the layout of the grouped form (survival_groups_layout): a tile belongs to one group
+struct SurvivalLayout {
+  int ntile = 0;
+  std::vector<int32_t> slot, tile_group, group_tile;
+};
+
 // What a launch of the data sums runs on, for a handle of either kind (abd_survival, abd_survival_draws): the device, the stream,
-// the plan of the launch and the buffers of ABD_MAX_BATCH points.  A handle holds it by value, ahead of its own buffers: members go
-// in reverse declaration order, so those are freed first, then the buffers here, and the stream is the last to go (abd_host.hpp).
+// the plan of the launch, the buffers of ABD_MAX_BATCH points and the two tables of the grouped layout.  A handle holds it by
+// value, ahead of its own buffers: members go in reverse declaration order, so those are freed first, then the buffers here, and
+// the stream is the last to go (abd_host.hpp).
 struct SurvivalSums {
   int device = 0;
   int T = 0, ld = 0, ntile = 0, nseg = 0, seg_len = 0, nw = 0;
   int par_stride = 0, out_stride = 0;  // the rows of a point in d_par / h_par and in d_out / h_out
   Stream stream;
   DevBuf<double> d_par, d_s_part, d_w_part, d_out;
+  DevBuf<double> d_w0_part;                    // by period: the second plane of partials
+  DevBuf<int32_t> d_tile_group, d_group_tile;  // by group
   MappedBuf<double> h_par, h_out;  // pinned: the source and the target of the two copies of a launch
   std::vector<double> work;        // [ABD_MAX_BATCH] rows of the caller's: log lambda, 1 - lambda (and a form's own) of the points in flight
 
@@ -60,12 +68,13 @@ struct SurvivalSums {
     nseg = (T + seg_len - 1) / seg_len;
     nw = ntile * nseg;
   }
-  // after plan(): the device (`dev` < 0: the current one), the stream and the buffers
-  int alloc(int dev, int par_stride_, int out_stride_, int work_stride) {
+  // after plan(): the device (`dev` < 0: the current one), the stream and the buffers.  A row of par is the form's and
+  // par_extra doubles of the handle's own; layout is null for the forms in the caller's order
+  int alloc(int dev, const SurvivalForm& form, int par_extra, const SurvivalLayout* layout) {
     device = dev;
-    par_stride = par_stride_;
-    out_stride = out_stride_;
-    work.resize((size_t)ABD_MAX_BATCH * work_stride);
+    par_stride = form.par_stride() + par_extra;
+    out_stride = form.out_stride();
+    work.resize((size_t)ABD_MAX_BATCH * form.work_stride());
     if (device < 0) HIP_TRY(hipGetDevice(&device));
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(stream.create());
@@ -75,6 +84,11 @@ struct SurvivalSums {
     HIP_TRY(d_out.alloc((size_t)ABD_MAX_BATCH * out_stride));
     HIP_TRY(h_par.alloc_pinned((size_t)ABD_MAX_BATCH * par_stride));
     HIP_TRY(h_out.alloc_pinned((size_t)ABD_MAX_BATCH * out_stride));
+    if (form.by_period()) HIP_TRY(d_w0_part.alloc((size_t)ABD_MAX_BATCH * ntile * T));
+    if (layout) {
+      HIP_TRY(d_tile_group.upload(layout->tile_group.data(), (size_t)ntile));
+      HIP_TRY(d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
+    }
     return ABD_OK;
   }
   // the rows of n <= ABD_MAX_BATCH points: h_par to the device ahead of the launches, and d_out back to h_out behind them
@@ -93,21 +107,36 @@ struct SurvivalSums {
     if (stream) (void)hipStreamSynchronize(stream);
   }
 };
+
+// What a launch of the per-individual log-likelihood runs on, for a handle of either kind: the parameter rows and the rows ll of
+// ABD_MAX_BATCH points, on the device and pinned (abd_survival_pointwise.hpp).  Allocated at the first pointwise call.
+struct SurvivalPointRows {
+  int stride = 0;  // the parameter row of a point
+  DevBuf<double> d_par, d_ll;     // [ABD_MAX_BATCH][stride], [ABD_MAX_BATCH][ld]
+  MappedBuf<double> h_par, h_ll;  // pinned
+  int ensure(int ld) {
+    if (d_ll) return ABD_OK;
+    HIP_TRY(d_par.alloc((size_t)ABD_MAX_BATCH * stride));
+    HIP_TRY(h_par.alloc_pinned((size_t)ABD_MAX_BATCH * stride));
+    HIP_TRY(h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * ld));
+    HIP_TRY(d_ll.alloc((size_t)ABD_MAX_BATCH * ld));
+    return ABD_OK;
+  }
+};
 }  // namespace abdi
 
 struct abd_survival : SurvivalSpec {
   SurvivalSums sums;  // first: the last to go
-  DevBuf<int32_t> d_tile_group, d_group_tile;
   std::vector<double> Y;  // Y_t = sum_j y_jt
   double C = 0.0;         // sum_{y > 0} y log e - sum lgamma(y + 1)
-  DevBuf<double> d_y, d_e, d_x0, d_x1, d_w0_part;
+  DevBuf<double> d_y, d_e, d_x0, d_x1;
   // the per-individual log-likelihood and its WAIC accumulators (abd_survival_pointwise.hpp)
   std::vector<int32_t> slot;       // [N] the column of individual j; empty: j itself (the ungrouped layout)
   std::vector<int32_t> n_cells;    // [N] followed cells (e > 0) of individual j, in the caller's order
   std::vector<double> cj;          // [ld] C_j per slot, uploaded at the first pointwise call
-  int pw_stride = 0;               // the pointwise parameter row: lambda[T], log lambda[T], ab[n_ab], 1 / n_draw
-  DevBuf<double> d_cj, d_pw_par, d_ll, d_acc;  // [ld], [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [4][ld]
-  MappedBuf<double> h_pw_par, h_ll, h_acc;     // pinned
+  SurvivalPointRows pw;            // the parameter row: lambda[T], log lambda[T], ab[n_ab], 1 / n_draw
+  DevBuf<double> d_cj, d_acc;      // [ld], [4][ld]
+  MappedBuf<double> h_acc;         // pinned
   int64_t waic_n = 0;              // draws folded into d_acc
   // PSIS-LOO by individual (abd_psis.hpp): the matrix of the draws' rows, unit = slot
   DevBuf<double> d_loo, d_loo_out;  // [ld][loo_cap]; [3][ld]: elpd_loo, pareto k, lppd
@@ -130,6 +159,7 @@ struct abd_survival : SurvivalSpec {
   int64_t pp_n = 0;                // draws folded since the last reset
 
   int column(int j) const { return slot.empty() ? j : slot[j]; }
+  SurvivalData data() const { return SurvivalData{d_y, d_e, d_x0, d_x1, nullptr, nullptr}; }
 };
 
 namespace abdi {
@@ -139,33 +169,6 @@ namespace {
 void survival_prepare_points(abd_survival* s, int n, const double* theta) {
   const int D = s->form.dim(), stride = s->form.par_stride(), ws = s->form.work_stride();
   for (int q = 0; q < n; ++q) s->form.prepare(theta + (size_t)q * D, s->sums.h_par.host() + (size_t)q * stride, s->sums.work.data() + (size_t)q * ws);
-}
-
-// what the argument structs of the sums kernels have in common: the buffers and the plan of a launch
-template <typename Args>
-Args survival_args(const SurvivalSums& c) {
-  Args a;
-  std::memset(&a, 0, sizeof a);
-  a.par = c.d_par;
-  a.s_part = c.d_s_part;
-  a.w_part = c.d_w_part;
-  a.T = c.T;
-  a.ld = c.ld;
-  a.ntile = c.ntile;
-  a.nseg = c.nseg;
-  a.seg_len = c.seg_len;
-  a.par_stride = c.par_stride;
-  return a;
-}
-
-// ... and those of the three forms of an abd_survival, whose kernel and finalize share one struct
-template <typename Args>
-Args survival_args(const abd_survival* s) {
-  Args a = survival_args<Args>(s->sums);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.out = s->sums.d_out;
-  return a;
 }
 
 // fn(k0, nb) for the points k0 .. k0 + nb - 1 of n, at most `batch` of them at a time, until one fails
@@ -184,34 +187,46 @@ int survival_destroy(Handle* s) {
   return ABD_OK;
 }
 
-// the sums of n <= ABD_MAX_BATCH points into s->sums.h_out (rows of out_stride)
-int survival_launch(abd_survival* s, int n, const double* theta) {
-  SurvivalSums& c = s->sums;
-  const int T = c.T;
-  survival_prepare_points(s, n, theta);
+// The sums of n <= ABD_MAX_BATCH points, whose rows stand in c.h_par, into c.h_out (rows of out_stride): for a handle of either
+// kind (data.n_risk: an ensemble).  The one place that picks the pair of kernels: the sums kernel of the form and of the source,
+// then the finalize kernel of the form.
+int survival_sums_launch(SurvivalSums& c, const SurvivalForm& form, const SurvivalData& data, int n) {
   if (int rc = c.upload(n)) return rc;
-  if (s->form.by_period()) {  // the one place that picks the pair of kernels
-    SurvivalPeriodsArgs a = survival_args<SurvivalPeriodsArgs>(s);
-    a.x = s->d_x0;
-    a.w0_part = s->d_w0_part;
-    HIP_TRY(launch_kernel(abd_survival_periods_kernel, c.grid(n), dim3(256), 0, c.stream, a));
-    HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, c.stream, a));
-  } else if (s->form.grouped()) {
-    SurvivalGroupsArgs a = survival_args<SurvivalGroupsArgs>(s);
-    a.x = s->d_x0;
-    a.tile_group = s->d_tile_group;
-    a.group_tile = s->d_group_tile;
-    a.Gr = s->form.Gr;
-    HIP_TRY(launch_kernel(abd_survival_groups_kernel, c.grid(n), dim3(256), 0, c.stream, a));
-    HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (a.Gr + 3) / 4), (unsigned)n), dim3(256), 0, c.stream, a));
-  } else {
-    SurvivalArgs a = survival_args<SurvivalArgs>(s);
-    a.x0 = s->d_x0;
-    a.x1 = s->d_x1;
-    HIP_TRY(launch_kernel(s->form.K == 2 ? abd_survival_kernel<2> : abd_survival_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
-    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, a));
-  }
+  SurvivalSumsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.data = data;
+  a.par = c.d_par;
+  a.tile_group = c.d_tile_group;
+  a.group_tile = c.d_group_tile;
+  a.s_part = c.d_s_part;
+  a.w0_part = c.d_w0_part;
+  a.w_part = c.d_w_part;
+  a.out = c.d_out;
+  a.T = c.T;
+  a.Gr = form.Gr;
+  a.n_ab = form.n_ab();
+  a.ld = c.ld;
+  a.ntile = c.ntile;
+  a.nseg = c.nseg;
+  a.seg_len = c.seg_len;
+  a.par_stride = c.par_stride;
+  using Kernel = void (*)(const SurvivalSumsArgs);
+  static const Kernel kernels[4][2] = {{abd_survival_sums_kernel<0, false>, abd_survival_sums_kernel<0, true>},
+                                       {abd_survival_sums_kernel<1, false>, abd_survival_sums_kernel<1, true>},
+                                       {abd_survival_sums_kernel<2, false>, abd_survival_sums_kernel<2, true>},
+                                       {abd_survival_sums_kernel<3, false>, abd_survival_sums_kernel<3, true>}};
+  const int ns = (c.T + 63) / 64;  // workgroups of a finalize per plane of S_t partials
+  const Kernel finalize = form.by_period() ? abd_survival_periods_finalize : form.grouped() ? abd_survival_groups_finalize : abd_survival_finalize;
+  const int nfin = form.by_period() ? 2 * ns + 1 : form.grouped() ? ns + 1 + (form.Gr + 3) / 4 : ns + 1;
+  HIP_TRY(launch_kernel(kernels[form.mode()][data.n_risk != nullptr], c.grid(n), dim3(256), 0, c.stream, a));
+  HIP_TRY(launch_kernel(finalize, dim3((unsigned)nfin, (unsigned)n), dim3(256), 0, c.stream, a));
   return c.download(n);
+}
+
+// the sums of n <= ABD_MAX_BATCH points into s->sums.h_out
+int survival_launch(abd_survival* s, int n, const double* theta) {
+  survival_prepare_points(s, n, theta);
+  return survival_sums_launch(s->sums, s->form, s->data(), n);
 }
 
 // ---- the per-individual log-likelihood (abd_survival_pointwise.hpp) ----
@@ -223,23 +238,45 @@ void survival_pointwise_setup(abd_survival* s, const double* y, const double* e)
   survival_pointwise_constants(s->form.T, s->sums.ld, y, e, s->cj.data(), cells.data());
   s->n_cells.resize((size_t)s->N);
   for (int j = 0; j < s->N; ++j) s->n_cells[j] = cells[s->column(j)];
-  s->pw_stride = survival_pointwise_stride(s->form.T, s->form.n_ab());
+  s->pw.stride = survival_pointwise_stride(s->form.T, s->form.n_ab());
+}
+
+// The rows pw.h_par of n <= ABD_MAX_BATCH points to the device and ll[n][ld] of them into pw.d_ll, queued on the stream: for a
+// handle of either kind (data.n_risk: an ensemble, which has no cj).  The one place that picks the per-individual kernel.
+int survival_pointwise_kernel(const SurvivalSums& c, const SurvivalForm& form, const SurvivalData& data, const double* cj, SurvivalPointRows& pw,
+                              int n) {
+  HIP_TRY(hipMemcpyAsync(pw.d_par, pw.h_par.host(), (size_t)n * pw.stride * sizeof(double), hipMemcpyHostToDevice, c.stream));
+  SurvivalPointArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.data = data;
+  a.cj = cj;
+  a.par = pw.d_par;
+  a.tile_group = c.d_tile_group;
+  a.ll = pw.d_ll;
+  a.T = c.T;
+  a.ld = c.ld;
+  a.ntile = c.ntile;
+  a.par_stride = pw.stride;
+  a.n_ab = form.n_ab();
+  using Kernel = void (*)(const SurvivalPointArgs);
+  static const Kernel kernels[4][2] = {{abd_survival_individual_kernel<0, false>, abd_survival_individual_kernel<0, true>},
+                                       {abd_survival_individual_kernel<1, false>, abd_survival_individual_kernel<1, true>},
+                                       {abd_survival_individual_kernel<2, false>, abd_survival_individual_kernel<2, true>},
+                                       {abd_survival_individual_kernel<3, false>, abd_survival_individual_kernel<3, true>}};
+  const dim3 grid((unsigned)((c.ntile + 3) / 4), (unsigned)n);
+  HIP_TRY(launch_kernel(kernels[form.mode()][data.n_risk != nullptr], grid, dim3(256), 0, c.stream, a));
+  return ABD_OK;
 }
 
 // the buffers of the pointwise launches, at the first of them
 int survival_pointwise_ensure(abd_survival* s) {
-  if (s->d_ll) return ABD_OK;
-  HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->sums.ld));
-  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->sums.ld));
-  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->sums.ld));
-  return ABD_OK;
+  if (!s->d_cj) HIP_TRY(s->d_cj.upload(s->cj.data(), (size_t)s->sums.ld));
+  return s->pw.ensure(s->sums.ld);
 }
 
-// the rows of s->d_ll [n][ld] into the LOO matrix as draws loo_n .. loo_n + n - 1, queued on the stream (abd_psis.hpp)
+// the rows of s->pw.d_ll [n][ld] into the LOO matrix as draws loo_n .. loo_n + n - 1, queued on the stream (abd_psis.hpp)
 int survival_loo_store(abd_survival* s, int n) {
-  HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_ll, (double*)s->d_loo,
+  HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->pw.d_ll, (double*)s->d_loo,
                         (int32_t)s->sums.ld, (int64_t)s->loo_cap, (int32_t)n, (int64_t)s->loo_n));
   return ABD_OK;
 }
@@ -253,11 +290,11 @@ int survival_loo_room(const abd_survival* s, int32_t n) {
   return ABD_OK;
 }
 
-// where the rows of a pointwise launch go: copied to s->h_ll; folded into the WAIC accumulators as draws waic_n + 1 .. waic_n + n;
-// or stored in the LOO matrix as draws loo_n .. loo_n + n - 1
+// where the rows of a pointwise launch go: copied to s->pw.h_ll; folded into the WAIC accumulators as draws waic_n + 1 ..
+// waic_n + n; or stored in the LOO matrix as draws loo_n .. loo_n + n - 1
 enum class PointRows { Copy, Fold, Store };
 
-// ll[n][ld] of n <= ABD_MAX_BATCH points into s->d_ll, and on to `to`
+// ll[n][ld] of n <= ABD_MAX_BATCH points into s->pw.d_ll, and on to `to`
 int survival_pointwise_launch(abd_survival* s, int n, const double* theta, PointRows to) {
   const bool fold = to == PointRows::Fold;
   if (int rc = survival_pointwise_ensure(s)) return rc;
@@ -265,36 +302,17 @@ int survival_pointwise_launch(abd_survival* s, int n, const double* theta, Point
   survival_prepare_points(s, n, theta);
   for (int q = 0; q < n; ++q)
     survival_pointwise_row(T, n_ab, s->sums.h_par.host() + (size_t)q * stride, s->sums.work.data() + (size_t)q * s->form.work_stride(), fold ? s->waic_n + q + 1 : 0,
-                           s->h_pw_par.host() + (size_t)q * s->pw_stride);
-  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, s->sums.stream));
-  SurvivalPointArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.y = s->d_y;
-  a.e = s->d_e;
-  a.x0 = s->d_x0;
-  a.x1 = s->d_x1;
-  a.cj = s->d_cj;
-  a.par = s->d_pw_par;
-  a.tile_group = s->d_tile_group;
-  a.ll = s->d_ll;
-  a.T = T;
-  a.ld = s->sums.ld;
-  a.ntile = s->sums.ntile;
-  a.par_stride = s->pw_stride;
-  a.n_ab = n_ab;
-  const dim3 grid((unsigned)((s->sums.ntile + 3) / 4), (unsigned)n);
-  void (*const kernels[4])(const SurvivalPointArgs) = {abd_survival_individual_kernel<0>, abd_survival_individual_kernel<1>,
-                                                       abd_survival_individual_kernel<2>, abd_survival_individual_kernel<3>};
-  HIP_TRY(launch_kernel(kernels[s->form.mode()], grid, dim3(256), 0, s->sums.stream, a));
+                           s->pw.h_par.host() + (size_t)q * s->pw.stride);
+  if (int rc = survival_pointwise_kernel(s->sums, s->form, s->data(), s->d_cj, s->pw, n)) return rc;
   if (fold) {
     if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)4 * s->sums.ld, s->sums.stream));
-    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->d_ll,
-                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)s->sums.ld, (int32_t)s->pw_stride,
-                          (int32_t)(s->pw_stride - 1), (int32_t)n, (int64_t)s->waic_n));
+    HIP_TRY(launch_kernel(abd_survival_waic_fold, dim3((unsigned)((s->sums.ld + 255) / 256)), dim3(256), 0, s->sums.stream, (const double*)s->pw.d_ll,
+                          (const double*)s->pw.d_par, (double*)s->d_acc, (int32_t)s->sums.ld, (int32_t)s->pw.stride,
+                          (int32_t)(s->pw.stride - 1), (int32_t)n, (int64_t)s->waic_n));
   } else if (to == PointRows::Store) {
     if (int rc = survival_loo_store(s, n)) return rc;
   } else {
-    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * s->sums.ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
+    HIP_TRY(hipMemcpyAsync(s->pw.h_ll.host(), s->pw.d_ll, (size_t)n * s->sums.ld * sizeof(double), hipMemcpyDeviceToHost, s->sums.stream));
   }
   HIP_TRY(hipStreamSynchronize(s->sums.stream));
   if (fold) s->waic_n += n;
@@ -346,7 +364,7 @@ int survival_predictive_launch(abd_survival* s, int n, const double* theta, int6
   a.bins = s->d_pp_bins;
   a.slot_j = s->d_pp_slot_j;
   a.par = s->sums.d_par;
-  a.tile_group = s->d_tile_group;
+  a.tile_group = s->sums.d_tile_group;
   a.e_part = s->d_pp_e_part;
   a.r_part = s->d_pp_r_part;
   a.ej = s->d_pp_ej;
@@ -428,12 +446,6 @@ int survival_check_periods(int T, int P, const int32_t* period) {
   return ABD_OK;
 }
 
-// the layout of the grouped form (survival_groups_layout): a tile belongs to one group
-struct SurvivalLayout {
-  int ntile = 0;
-  std::vector<int32_t> slot, tile_group, group_tile;
-};
-
 // the individuals sorted by group, every group padded to whole tiles; the labels lie in [0, Gr)
 SurvivalLayout survival_layout(int N, int Gr, const int32_t* group) {
   SurvivalLayout lay;
@@ -461,17 +473,12 @@ int survival_create_common(const SurvivalSpec& spec, const double* infected, con
   s->Y = std::move(p.Y);
   s->C = p.C;
   survival_pointwise_setup(s.get(), p.y.data(), p.e.data());
-  if (int rc = s->sums.alloc(spec.device, s->form.par_stride(), s->form.out_stride(), s->form.work_stride())) return rc;
+  if (int rc = s->sums.alloc(spec.device, s->form, 0, layout)) return rc;
   const size_t plane = (size_t)s->sums.ld * T;
   HIP_TRY(s->d_y.upload(p.y.data(), plane));
   HIP_TRY(s->d_e.upload(p.e.data(), plane));
   HIP_TRY(s->d_x0.upload(p.x0.data(), plane));
   if (K == 2) HIP_TRY(s->d_x1.upload(p.x1.data(), plane));
-  if (layout) {
-    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->sums.ntile));
-    HIP_TRY(s->d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
-  }
-  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->sums.ntile * T));
   *out = s.release();
   return ABD_OK;
 }
@@ -584,7 +591,7 @@ int abd_survival_individual_loglik(abd_survival* s, int32_t n, const double* the
   return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_pointwise_launch(s, nb, theta + k0 * D, PointRows::Copy)) return rc;
     for (int q = 0; q < nb; ++q) {  // slots to the caller's order
-      const double* row = s->h_ll.host() + (size_t)q * s->sums.ld;
+      const double* row = s->pw.h_ll.host() + (size_t)q * s->sums.ld;
       double* out = ll + ((size_t)k0 + q) * s->N;
       for (int j = 0; j < s->N; ++j) out[j] = row[s->column(j)];
     }
@@ -677,13 +684,13 @@ int abd_survival_loo_append_rows(abd_survival* s, int32_t n, const double* ll) {
   if (int rc = survival_pointwise_ensure(s)) return rc;
   const size_t ld = (size_t)s->sums.ld;
   return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
-    std::memset(s->h_ll.host(), 0, (size_t)nb * ld * sizeof(double));  // the padding holds 0
+    std::memset(s->pw.h_ll.host(), 0, (size_t)nb * ld * sizeof(double));  // the padding holds 0
     for (int q = 0; q < nb; ++q) {  // the caller's order to slots
       const double* in = ll + ((size_t)k0 + q) * s->N;
-      double* row = s->h_ll.host() + (size_t)q * ld;
+      double* row = s->pw.h_ll.host() + (size_t)q * ld;
       for (int j = 0; j < s->N; ++j) row[s->column(j)] = in[j];
     }
-    HIP_TRY(hipMemcpyAsync(s->d_ll, s->h_ll.host(), (size_t)nb * ld * sizeof(double), hipMemcpyHostToDevice, s->sums.stream));
+    HIP_TRY(hipMemcpyAsync(s->pw.d_ll, s->pw.h_ll.host(), (size_t)nb * ld * sizeof(double), hipMemcpyHostToDevice, s->sums.stream));
     if (int rc = survival_loo_store(s, nb)) return rc;
     HIP_TRY(hipStreamSynchronize(s->sums.stream));
     s->loo_n += nb;
@@ -851,21 +858,20 @@ int abd_survival_replicate(abd_survival* s, int32_t n, const double* theta, int6
 
 }  // extern "C"
 
-// ---- the ensemble of per-draw datasets (abd_survival_draws.hpp, abd_survival_draws_forms.hpp) ----
+// ---- the ensemble of per-draw datasets (SurvSource<true, .> in abd_survival.hpp) ----
 
 struct abd_survival_draws : SurvivalSpec {  // the form, as an abd_survival knows it: K titers, by group or by period
   int M = 0;
   SurvivalSums sums;      // first: the last to go.  Rows of par: the form's row, then the dataset index; of work: the form's
   std::vector<double> Y;  // [M][T]: the events of dataset m in interval t, an integer
-  DevBuf<double> d_x0, d_x1, d_w0_part;  // titers [M][T][ld]; by period, the second plane of partials
-  DevBuf<int32_t> d_n_risk, d_event;     // [M][ld]
-  DevBuf<int32_t> d_tile_group, d_group_tile;  // by group
-  // the per-individual log-likelihood, its WAIC accumulators and PSIS-LOO, per dataset (abd_survival_draws_pointwise.hpp)
+  DevBuf<double> d_x0, d_x1;          // titers [M][T][ld]
+  DevBuf<int32_t> d_n_risk, d_event;  // [M][ld]
+  // the per-individual log-likelihood, its WAIC accumulators and PSIS-LOO, per dataset (abd_survival_pointwise.hpp)
   std::vector<int32_t> slot;            // [N] the column of individual j; empty: j itself (the ungrouped layout)
   std::vector<int32_t> n_cells;         // [M][N] followed cells of individual j in dataset m: its n_risk, in the caller's order
-  int pw_stride = 0;                    // the pointwise row: survival_pointwise_row's, then the draw's number and the dataset
-  DevBuf<double> d_pw_par, d_ll, d_acc;     // [ABD_MAX_BATCH][pw_stride], [ABD_MAX_BATCH][ld], [M][4][ld]
-  MappedBuf<double> h_pw_par, h_ll, h_acc;  // pinned
+  SurvivalPointRows pw;                 // the parameter row: survival_pointwise_row's, then the draw's number and the dataset
+  DevBuf<double> d_acc;                 // [M][4][ld]
+  MappedBuf<double> h_acc;              // pinned
   std::vector<int64_t> waic_n, loo_n;   // [M] draws folded into dataset m's accumulators / held in its block of the matrix
   std::vector<int64_t> pending;         // [M] scratch of a call: the rows it has for dataset m so far
   DevBuf<double> d_loo, d_loo_out;      // [M][ld][loo_cap]; [M][3][ld]: elpd_loo, pareto k, lppd
@@ -875,6 +881,7 @@ struct abd_survival_draws : SurvivalSpec {  // the form, as an abd_survival know
   int64_t loo_cap = 0;                  // the draws every dataset's block holds room for
 
   int column(int j) const { return slot.empty() ? j : slot[j]; }
+  SurvivalData data() const { return SurvivalData{nullptr, nullptr, d_x0, d_x1, d_n_risk, d_event}; }
 };
 
 namespace abdi {
@@ -884,7 +891,7 @@ namespace {
 int survival_draws_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta) {
   SurvivalSums& c = s->sums;
   const SurvivalForm& form = s->form;
-  const int T = form.T, stride = form.par_stride();  // the dataset index follows the form's row
+  const int stride = form.par_stride();  // the dataset index follows the form's row
   const size_t D = (size_t)form.dim();
   for (int q = 0; q < n; ++q) {
     double* par = c.h_par.host() + (size_t)q * c.par_stride;
@@ -892,43 +899,7 @@ int survival_draws_launch(abd_survival_draws* s, int n, const int32_t* dataset, 
     par[stride] = 0.0;
     std::memcpy(par + stride, dataset + q, sizeof(int32_t));
   }
-  if (int rc = c.upload(n)) return rc;
-  // the one place that picks the pair of kernels: the ensemble kernel of the form, then the finalize of abd_survival's handle of
-  // that form, as it is -- it reads the partials, T, ntile and nseg (and the group's tiles)
-  if (form.by_period() || form.grouped()) {
-    SurvivalDrawsFormArgs a = survival_args<SurvivalDrawsFormArgs>(c);
-    a.x = s->d_x0;
-    a.n_risk = s->d_n_risk;
-    a.event = s->d_event;
-    a.tile_group = s->d_tile_group;
-    a.w0_part = s->d_w0_part;
-    a.Gr = form.Gr;
-    if (form.by_period()) {
-      SurvivalPeriodsArgs f = survival_args<SurvivalPeriodsArgs>(c);
-      f.w0_part = s->d_w0_part;
-      f.out = c.d_out;
-      HIP_TRY(launch_kernel(abd_survival_draws_periods_kernel, c.grid(n), dim3(256), 0, c.stream, a));
-      HIP_TRY(launch_kernel(abd_survival_periods_finalize, dim3((unsigned)(2 * ((T + 63) / 64) + 1), (unsigned)n), dim3(256), 0, c.stream, f));
-    } else {
-      SurvivalGroupsArgs f = survival_args<SurvivalGroupsArgs>(c);
-      f.group_tile = s->d_group_tile;
-      f.Gr = form.Gr;
-      f.out = c.d_out;
-      HIP_TRY(launch_kernel(abd_survival_draws_groups_kernel, c.grid(n), dim3(256), 0, c.stream, a));
-      HIP_TRY(launch_kernel(abd_survival_groups_finalize, dim3((unsigned)((T + 63) / 64 + 1 + (form.Gr + 3) / 4), (unsigned)n), dim3(256), 0, c.stream, f));
-    }
-  } else {
-    SurvivalDrawsArgs a = survival_args<SurvivalDrawsArgs>(c);
-    a.x0 = s->d_x0;
-    a.x1 = s->d_x1;
-    a.n_risk = s->d_n_risk;
-    a.event = s->d_event;
-    SurvivalArgs f = survival_args<SurvivalArgs>(c);
-    f.out = c.d_out;
-    HIP_TRY(launch_kernel(form.K == 2 ? abd_survival_draws_kernel<2> : abd_survival_draws_kernel<1>, c.grid(n), dim3(256), 0, c.stream, a));
-    HIP_TRY(launch_kernel(abd_survival_finalize, dim3((unsigned)((T + 63) / 64 + 1), (unsigned)n), dim3(256), 0, c.stream, f));
-  }
-  return c.download(n);
+  return survival_sums_launch(c, form, s->data(), n);
 }
 
 int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int32_t* dataset) {
@@ -937,24 +908,14 @@ int survival_draws_check_datasets(const abd_survival_draws* s, int n, const int3
   return ABD_OK;
 }
 
-// ---- the per-individual log-likelihood of an ensemble (abd_survival_draws_pointwise.hpp) ----
+// ---- the per-individual log-likelihood of an ensemble (abd_survival_pointwise.hpp) ----
 
-// the buffers of the pointwise launches, at the first of them
-int survival_draws_pointwise_ensure(abd_survival_draws* s) {
-  if (s->d_ll) return ABD_OK;
-  HIP_TRY(s->d_pw_par.alloc((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_pw_par.alloc_pinned((size_t)ABD_MAX_BATCH * s->pw_stride));
-  HIP_TRY(s->h_ll.alloc_pinned((size_t)ABD_MAX_BATCH * s->sums.ld));
-  HIP_TRY(s->d_ll.alloc((size_t)ABD_MAX_BATCH * s->sums.ld));
-  return ABD_OK;
-}
-
-// ll[n][ld] of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->d_ll, and on to `to`: copied to s->h_ll; folded into the
-// dataset's WAIC accumulators as its draws waic_n[m] + 1 ...; or stored in the dataset's block of the LOO matrix as its draws
-// loo_n[m] ...  The rows of one dataset keep their order, whatever stands between them.
+// ll[n][ld] of n <= ABD_MAX_BATCH points, point q on dataset[q], into s->pw.d_ll, and on to `to`: copied to s->pw.h_ll; folded
+// into the dataset's WAIC accumulators as its draws waic_n[m] + 1 ...; or stored in the dataset's block of the LOO matrix as its
+// draws loo_n[m] ...  The rows of one dataset keep their order, whatever stands between them.
 int survival_draws_pointwise_launch(abd_survival_draws* s, int n, const int32_t* dataset, const double* theta, PointRows to) {
   const bool fold = to == PointRows::Fold, store = to == PointRows::Store;
-  if (int rc = survival_draws_pointwise_ensure(s)) return rc;
+  if (int rc = s->pw.ensure(s->sums.ld)) return rc;
   SurvivalSums& c = s->sums;
   const SurvivalForm& form = s->form;
   const int T = form.T, n_ab = form.n_ab(), inv_off = 2 * T + n_ab;
@@ -963,7 +924,7 @@ int survival_draws_pointwise_launch(abd_survival_draws* s, int n, const int32_t*
   for (int q = 0; q < n; ++q) {
     double* par = c.h_par.host() + (size_t)q * c.par_stride;
     double* work = c.work.data() + (size_t)q * form.work_stride();
-    double* row = s->h_pw_par.host() + (size_t)q * s->pw_stride;
+    double* row = s->pw.h_par.host() + (size_t)q * s->pw.stride;
     form.prepare(theta + q * D, par, work);
     const int64_t n_draw = fold ? s->waic_n[dataset[q]] + ++s->pending[dataset[q]] : 0;
     survival_pointwise_row(T, n_ab, par, work, n_draw, row);
@@ -971,43 +932,25 @@ int survival_draws_pointwise_launch(abd_survival_draws* s, int n, const int32_t*
     row[inv_off + kDrawsRowDataset] = 0.0;
     std::memcpy(row + inv_off + kDrawsRowDataset, dataset + q, sizeof(int32_t));
   }
-  HIP_TRY(hipMemcpyAsync(s->d_pw_par, s->h_pw_par.host(), (size_t)n * s->pw_stride * sizeof(double), hipMemcpyHostToDevice, c.stream));
-  SurvivalDrawsPointArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.x0 = s->d_x0;
-  a.x1 = s->d_x1;
-  a.n_risk = s->d_n_risk;
-  a.event = s->d_event;
-  a.par = s->d_pw_par;
-  a.tile_group = s->d_tile_group;
-  a.ll = s->d_ll;
-  a.T = T;
-  a.ld = c.ld;
-  a.ntile = c.ntile;
-  a.par_stride = s->pw_stride;
-  a.n_ab = n_ab;
-  const dim3 grid((unsigned)((c.ntile + 3) / 4), (unsigned)n);
-  void (*const kernels[4])(const SurvivalDrawsPointArgs) = {abd_survival_draws_individual_kernel<0>, abd_survival_draws_individual_kernel<1>,
-                                                            abd_survival_draws_individual_kernel<2>, abd_survival_draws_individual_kernel<3>};
-  HIP_TRY(launch_kernel(kernels[form.mode()], grid, dim3(256), 0, c.stream, a));
+  if (int rc = survival_pointwise_kernel(c, form, s->data(), nullptr, s->pw, n)) return rc;
   if (fold) {
     if (!s->d_acc) HIP_TRY(s->d_acc.alloc_zero((size_t)s->M * 4 * ld, c.stream));
-    HIP_TRY(launch_kernel(abd_survival_draws_waic_fold, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->d_ll,
-                          (const double*)s->d_pw_par, (double*)s->d_acc, (int32_t)ld, (int32_t)s->pw_stride, (int32_t)inv_off, (int32_t)n));
+    HIP_TRY(launch_kernel(abd_survival_draws_waic_fold, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->pw.d_ll,
+                          (const double*)s->pw.d_par, (double*)s->d_acc, (int32_t)ld, (int32_t)s->pw.stride, (int32_t)inv_off, (int32_t)n));
   } else if (store) {
     // abd_psis_store as it is, once per run of rows of one dataset, on that dataset's block at its own draw count
     for (int q0 = 0; q0 < n;) {
       const int m = dataset[q0];
       int q1 = q0 + 1;
       while (q1 < n && dataset[q1] == m) ++q1;
-      HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->d_ll + (size_t)q0 * ld,
+      HIP_TRY(launch_kernel(abd_psis_store, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, c.stream, (const double*)s->pw.d_ll + (size_t)q0 * ld,
                             (double*)s->d_loo + (size_t)m * ld * (size_t)s->loo_cap, (int32_t)ld, (int64_t)s->loo_cap, (int32_t)(q1 - q0),
                             (int64_t)(s->loo_n[m] + s->pending[m])));
       s->pending[m] += q1 - q0;
       q0 = q1;
     }
   } else {
-    HIP_TRY(hipMemcpyAsync(s->h_ll.host(), s->d_ll, (size_t)n * ld * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(s->pw.h_ll.host(), s->pw.d_ll, (size_t)n * ld * sizeof(double), hipMemcpyDeviceToHost, c.stream));
   }
   HIP_TRY(hipStreamSynchronize(c.stream));
   if (fold || store) {
@@ -1047,7 +990,7 @@ int survival_draws_create_common(const SurvivalSpec& spec, int M, const int32_t*
   s->Y.assign((size_t)M * T, 0.0);
   if (layout) s->slot = layout->slot;
   s->n_cells.assign(n_risk_in, n_risk_in + (size_t)M * N);  // a cell is followed where it is at risk
-  s->pw_stride = survival_pointwise_stride(T, s->form.n_ab()) + kDrawsRowExtra - 1;
+  s->pw.stride = survival_pointwise_stride(T, s->form.n_ab()) + kDrawsRowExtra - 1;
   s->waic_n.assign((size_t)M, 0);
   s->loo_n.assign((size_t)M, 0);
   s->pending.assign((size_t)M, 0);
@@ -1071,16 +1014,11 @@ int survival_draws_create_common(const SurvivalSpec& spec, int M, const int32_t*
       }
     }
   // rows of par (the form's, then the dataset index), out and work
-  if (int rc = s->sums.alloc(spec.device, s->form.par_stride() + 1, s->form.out_stride(), s->form.work_stride())) return rc;
+  if (int rc = s->sums.alloc(spec.device, s->form, 1, layout)) return rc;
   HIP_TRY(s->d_x0.upload(x0.data(), x0.size()));
   if (K == 2) HIP_TRY(s->d_x1.upload(x1.data(), x1.size()));
   HIP_TRY(s->d_n_risk.upload(n_risk.data(), n_risk.size()));
   HIP_TRY(s->d_event.upload(event.data(), event.size()));
-  if (layout) {
-    HIP_TRY(s->d_tile_group.upload(layout->tile_group.data(), (size_t)s->sums.ntile));
-    HIP_TRY(s->d_group_tile.upload(layout->group_tile.data(), layout->group_tile.size()));
-  }
-  if (s->form.by_period()) HIP_TRY(s->d_w0_part.alloc((size_t)ABD_MAX_BATCH * s->sums.ntile * T));
   *out = s.release();
   return ABD_OK;
 }
@@ -1166,7 +1104,7 @@ int abd_survival_draws_loglik_sums(abd_survival_draws* s, int32_t dataset, const
   return ABD_OK;
 }
 
-// ---- per individual and dataset: log-likelihood, WAIC, PSIS-LOO (abd_survival_draws_pointwise.hpp) ----
+// ---- per individual and dataset: log-likelihood, WAIC, PSIS-LOO (abd_survival_pointwise.hpp) ----
 
 int abd_survival_draws_individual_loglik(abd_survival_draws* s, int32_t n, const int32_t* dataset, const double* theta, double* ll) {
   if (!s || !dataset || !theta || !ll) return fail(ABD_ERR_ARG, "NULL argument");
@@ -1176,7 +1114,7 @@ int abd_survival_draws_individual_loglik(abd_survival_draws* s, int32_t n, const
   return survival_batches(n, ABD_MAX_BATCH, [&](int k0, int nb) {
     if (int rc = survival_draws_pointwise_launch(s, nb, dataset + k0, theta + k0 * D, PointRows::Copy)) return rc;
     for (int q = 0; q < nb; ++q) {  // slots to the caller's order
-      const double* row = s->h_ll.host() + (size_t)q * s->sums.ld;
+      const double* row = s->pw.h_ll.host() + (size_t)q * s->sums.ld;
       double* out = ll + ((size_t)k0 + q) * s->N;
       for (int j = 0; j < s->N; ++j) out[j] = row[s->column(j)];
     }

@@ -6,7 +6,7 @@
 //
 //   theta = m, s, z[T], a_mu, a_sl, az[P], b      (the grouped layout with Gr -> P)
 //   a_p = a_mu + a_sd az_p;  a_t = a_p(t)          period[t] in [0, P)
-//   par  = lambda[T], a_t[T], b                    (what abd_survival_periods_kernel reads)
+//   par  = lambda[T], a_t[T], b                    (what abd_survival_sums_kernel<3, .> reads)
 //   sums = S_t[T], L, W_x, W0_t[T]                 (what it returns)
 //   W0_p = sum_{t in p} W0_t                       (ascending t, compensated; a period without intervals: exactly 0)
 //   d/da_p = -b W0_p;  d/db = W_x - sum_p a_p W0_p (survival_groups_combine)

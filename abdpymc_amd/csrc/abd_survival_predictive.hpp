@@ -3,9 +3,9 @@
 //
 // abd_survival_replicate_kernel<MODE>: the mapping of abd_survival_individual_kernel (abd_survival_pointwise.hpp) -- lane =
 // individual slot, a wave owns one tile of 64 and walks all T intervals in ascending order, the point is the grid's second
-// dimension -- with eta formed the same way in the four modes, so E_j = sum_t mu and R_j = sum_t r stay in the lane.  The bin sums
-// are lane-private columns in LDS, [variable][bin][thread], fp64 for mu and uint32 for r: a thread reads, modifies and writes its
-// own column only, so there are no atomics, no barrier, and the order is ascending t.  After the loop a wave sums its columns
+// dimension -- with eta formed by the same SurvEta<MODE> (abd_survival.hpp), so E_j = sum_t mu and R_j = sum_t r stay in the lane.
+// The bin sums are lane-private columns in LDS, [variable][bin][thread], fp64 for mu and uint32 for r: a thread reads, modifies
+// and writes its own column only, so there are no atomics, no barrier, and the order is ascending t.  After the loop a wave sums its columns
 // over the lanes (wave_sum_uniform; the counts as doubles, exact below 2^53 in any order) and writes one partial row per (point,
 // tile).  The replicate of a cell is surv_pred_poisson at surv_pred_uniform of (seed, caller's index j, t, draw index): the
 // kernel reads j of its slot from slot_j, so the grouped layout's reordering does not reach the replicates.  Cells without
@@ -47,7 +47,7 @@ struct SurvivalReplicateArgs {
 // LDS of a launch: n_var * 8 columns of 256 doubles, then as many of 256 uint32
 inline size_t survival_replicate_lds(int n_var) { return (size_t)n_var * ABD_SURV_PRED_BINS * 256 * (sizeof(double) + sizeof(uint32_t)); }
 
-// MODE as abd_survival_individual_kernel: 1, 2: K titers, ab = a[K], b[K].  0: by group, ab = a[Gr], b.  3: by period, ab = a_t[T], b.
+// MODE as SurvEta's (abd_survival.hpp)
 template <int MODE>
 __global__ __launch_bounds__(256) void abd_survival_replicate_kernel(const SurvivalReplicateArgs a) {
   extern __shared__ double surv_pred_lds[];
@@ -64,21 +64,7 @@ __global__ __launch_bounds__(256) void abd_survival_replicate_kernel(const Survi
   }
   const double* lam = a.par + (int64_t)point * a.par_stride;
   const double* ab = lam + a.T;
-  double a0, b0, a1 = 0.0, b1 = 0.0;
-  if (MODE == 0) {
-    a0 = ab[a.tile_group[tile]];
-    b0 = ab[a.n_ab - 1];
-  } else if (MODE == 3) {
-    a0 = 0.0;  // per interval, below
-    b0 = ab[a.n_ab - 1];
-  } else {
-    a0 = ab[0];
-    b0 = ab[MODE];
-    if (MODE == 2) {
-      a1 = ab[1];
-      b1 = ab[3];
-    }
-  }
+  const SurvEta<MODE> eta_of(ab, a.n_ab, a.tile_group, tile);
   const int slot = tile * 64 + lane;
   const uint32_t j = (uint32_t)a.slot_j[slot];
   const uint32_t draw_lo = (uint32_t)(a.draw0 + point);
@@ -90,9 +76,7 @@ __global__ __launch_bounds__(256) void abd_survival_replicate_kernel(const Survi
   for (int t = 0; t < a.T; ++t, idx += a.ld) {
     const double e = a.e[idx];
     const unsigned byte = a.bins[idx];
-    if (MODE == 3) a0 = ab[t];
-    double eta = b0 * (a.x0[idx] - a0);
-    if (MODE == 2) eta = fma(b1, a.x1[idx] - a1, eta);
+    const double eta = eta_of(t, a.x0[idx], MODE == 2 ? a.x1[idx] : 0.0);
     const double mu = lam[t] * (e * surv_sigma(eta).sig);
     const int r = surv_pred_poisson(mu, surv_pred_uniform(a.seed_lo, a.seed_hi, j, (uint32_t)t, draw_lo));
     const int c0 = (int)(byte & 15u) * 256;

@@ -39,7 +39,7 @@ def _plug_in(d, m, K):
 def test_bit_equal_to_the_plug_in_kernel_on_every_dataset(N, T, K, M):
     """logp, gradient and loglik_sums of 16 points, each on its own dataset, equal BITWISE what an abd_survival handle of that
     dataset's (infected, exposure, titers) returns: the same cell function, the same split and the same finalize in the same order;
-    the cells a wave skips add exact +0 there (abd_survival_draws.hpp).  The yardstick is the kernel tests/test_gpu_survival.py
+    the cells a wave skips add exact +0 there (abd_survival.hpp, beside SurvSource).  The yardstick is the kernel tests/test_gpu_survival.py
     pins to the 40-digit fixture."""
     d = datasets(M, N, T)
     pts = _points(T, K)

@@ -1,6 +1,6 @@
 """
 Model comparison of per-draw survival fits on the device (abd_survival_draws_individual_loglik, _waic_*, _loo_*;
-abd_survival_draws_pointwise.hpp; abdpymc_amd.survival.waic_draws / loo_draws / compare_draws).
+abd_survival_pointwise.hpp; abdpymc_amd.survival.waic_draws / loo_draws / compare_draws).
 
 Every device check is bit equality against the plug-in handle of the form made of ``SurvivalDraws.arrays(m)``: the rows of
 ``draws_individual_loglik``, the WAIC statistics per dataset under any batching and interleaving, PSIS-LOO per dataset with its own
