@@ -195,6 +195,61 @@ def case(name):
 CASES = tuple(S_VALUES) + ("ties", S_WIDE)
 
 
+# ---- past a tail of 256 and up to the cap of 16 384 draws (tests/test_psis_wide_cpu.py, tests/test_gpu_psis_wide.py) ----
+# Their 40-digit values are not computed when the tests run (about 20 s): tests/golden/psis_wide_reference.npz holds them.
+
+COLUMNS_WIDE = ("positive", "huge", "constant", "few_high", "uniform", "heavy", "unfollowed")
+UNFOLLOWED_WIDE = (6,)
+# M = 8 | 48 | 64 | 96 | 97 | 128 | 192 | 256 | 257 | 384: a full sort array at 8, 64, 128 and 256; the last S of one, four and
+# sixteen draws per thread (256, 1024, 4096) and the first of sixteen (1025); the last tail of the 256-slot sort (7281) and the
+# first of the 512-slot one (7282); the cap
+S_WIDE_VALUES = (40, 256, 442, 1024, 1025, 1793, 4096, 7281, 7282, 16384)
+S_PLAIN_WIDE = (7282, 16384)  # ``matrix`` where the tail passes 256: its clipped column then has a tail of 128 and 192
+S_TIES_WIDE = 7512            # 1878 rows, each four times: M = 261 and the 262nd largest is tied with the 261st
+
+
+def n_few_high(S):
+    """the draws of the column ``few_high`` that stand out: fewer than M, so that they alone are the tail"""
+    return max(5, tail_len(S) // 3)
+
+
+def matrix_wide(S, seed=0):
+    """(S, 7): the kinds of column ``matrix`` has none of -- positive values (sums of densities), |ll| near 2e4, a constant, a
+    tail whose members are all equal, bounded ratios (k < 0), a heavy tail (k > 1) -- and an unfollowed individual (exactly 0)."""
+    rng = np.random.default_rng([28, S, seed])
+    out = np.zeros((S, len(COLUMNS_WIDE)))
+    out[:, 0] = rng.normal(35.0, 0.5, S)
+    out[:, 1] = rng.normal(-2.0e4, 3.0, S)
+    out[:, 2] = -1.25
+    out[:, 3] = -0.5
+    out[rng.choice(S, size=n_few_high(S), replace=False), 3] = -1.5
+    out[:, 4] = rng.uniform(-1.0, 0.0, S)
+    out[:, 5] = -1.5 * rng.exponential(1.0, S)
+    return out
+
+
+def matrix_ties_wide():
+    """(7512, 6): 1878 rows of ``matrix``, every one four times: the ties on the cut-off leave n_tail = 260, below M = 261 and
+    above 256."""
+    return np.tile(matrix(S_TIES_WIDE // 4, seed=1), (4, 1))
+
+
+WIDE_CASES = tuple(f"wide_{S}" for S in S_WIDE_VALUES) + tuple(f"plain_{S}" for S in S_PLAIN_WIDE) + ("ties_wide",)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(name):
+    """name of WIDE_CASES -> (ll, the unfollowed columns).  Shared; do not write to it."""
+    if name == "ties_wide":
+        ll, out = matrix_ties_wide(), UNFOLLOWED
+    elif name.startswith("plain_"):
+        ll, out = matrix(int(name[6:])), UNFOLLOWED
+    else:
+        ll, out = matrix_wide(int(name[5:])), UNFOLLOWED_WIDE
+    ll.setflags(write=False)
+    return ll, out
+
+
 def rel_gap(got, want):
     """max |got - want| / max(1, |want|) over the finite entries; the non-finite ones must agree exactly (asserted)."""
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
